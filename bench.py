@@ -5,7 +5,7 @@ BASELINE configurations the same way (each with its own roofline block). The def
 arithmetic (fp32 storage / accumulation / results, every product formed from an exact three-way bf16 split of its fp32
 operands: the top-level "arithmetic" field says so) with the exact-fp32-MFMA step timed beside it as `native_f32`.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment the script launches its own ranks — `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` on this same file, as a CHILD process started before anything
@@ -14,8 +14,19 @@ touches the GPU (the reference does the same through Lightning's `strategy="ddp"
 
 A step = token preparation + encoder + task head + loss + full backward (+ one RCCL all-reduce of the flat gradient
 buffer when N > 1) over one batch of 256 clips per GPU (weak scaling). Inputs are resident in HBM before the timed
-region. Each trial times EXACTLY --steps steps between barrier + synchronize pairs (max over ranks); `ms_per_step` is
-the median trial, p10 / p90 are reported next to it. Rank 0 prints ONE JSON line (the last line of stdout).
+region. A plain run sets up, warms up, times ONE region of exactly --steps steps between barrier + synchronize pairs (max
+over ranks; `ms_per_step` = its time / --steps), writes the outputs of the last timed step with --dump-outputs, and prints
+the result line. Rank 0 prints ONE JSON line (the last line of stdout).
+
+--full adds everything else the benchmark measures: repeated trials (>= 5 and >= --min-seconds of timed work unless --trials
+says otherwise; `ms_per_step` is then the median trial, p10 / p90 next to it), the library's launch count, the with_optimizer,
+native_f32 and dropout0 lines, the roofline block, the CPU baseline, and with N > 1 the exchange on its own and the step
+without it.
+
+--dump-outputs DIR writes what the timed step computed in its LAST step, as a caller of that step receives it: DIR/loss.npy
+and DIR/grad.<parameter>.npy (float32; a bf16 gradient is widened), at most 64 MB in all - above that, every array keeps a
+fixed, seeded sample of its entries (the same indices from run to run). The inputs, weights and dropout seeds are fixed by
+the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -53,8 +64,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--trials", type=int, default=0, help="timed repetitions of --steps (0 = auto: >= 5 and >= --min-seconds of timed region)")
+    ap.add_argument("--trials", type=int, default=None,
+                    help="timed repetitions of --steps (default: 1, with --full auto; 0 = auto: >= 5 and >= --min-seconds of timed region)")
     ap.add_argument("--min-seconds", type=float, default=3.6, help="auto trials: total timed GPU work to aim for")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: auto trials, launch count, with_optimizer / native_f32 / dropout0 "
+                         "lines, roofline, CPU baseline, and with N > 1 the exchange on its own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the parameter gradients of the last timed step to DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch clips per GPU; strong: --batch clips in total, sharded over the ranks (SURVEY.md 8e)")
     ap.add_argument("--config", default="c2", choices=["c1", "c2", "c3", "c4", "c5hhi", "c5hoi", "pnr"],
@@ -256,12 +273,17 @@ def run(args) -> int:
         ddp.use_egx_comm(egx_comm)
     one = F_egx.unit_grad(dev)
     loss_fn = wl["loss_fn"]
+    last = {}
 
     def fwd_bwd():
         for p in params:
             p.grad = None
         loss = loss_fn()
         loss.backward(gradient=one)     # persistent 1.0: no ones-fill, and the fused CE skips the multiply by it
+        if args.dump_outputs:
+            # detached: holding the loss itself would keep this step's autograd graph, AccumulateGrad nodes included, alive into
+            # the next capture (a node made on another stream breaks it). Captured: a view of the graph's output, rewritten by every replay
+            last["loss"] = loss.detach()
         return loss
 
     def sync():
@@ -307,8 +329,10 @@ def run(args) -> int:
         return out
 
     def auto_trials(step_fn, steps):
-        if args.trials > 0:
+        if args.trials:
             return args.trials
+        if args.trials is None and not args.full:
+            return 1            # a plain run times exactly --steps steps
         sync()
         t0 = time.perf_counter()
         for _ in range(20):     # (three steps put the sync latency into the estimate: 2.95 s of timed work for a 3.6 s target)
@@ -472,6 +496,12 @@ def run(args) -> int:
         step = make_step(opt)
     trials = auto_trials(step, args.steps)
     dts = time_trials(step, args.warmup, args.steps, trials)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller, before anything else runs on the model
+        names = {id(p): n for n, p in model.named_parameters()}
+        arrays = [("loss", last["loss"])] + [("grad." + names.get(id(p), f"extra_params.{i}"), p.grad)
+                                             for i, p in enumerate(params) if p.grad is not None]
+        dump_outputs(args.dump_outputs, arrays)
     dt_med = percentile(dts, 0.5)
     ms = [d / args.steps * 1e3 for d in dts]
     ms_per_step = dt_med / args.steps * 1e3
@@ -480,7 +510,7 @@ def run(args) -> int:
 
     # the exchange on its own (same buffers, same stream order), for the `allreduce_us` field
     allreduce_us = None
-    if multi:
+    if multi and args.full:
         if not any(p.grad is not None for p in params):     # (a captured step leaves .grad as the capture left it; make sure there is something to exchange)
             fwd_bwd()
             F_egx.run_deferred()
@@ -498,7 +528,7 @@ def run(args) -> int:
 
     # launches per step: kernels the library enqueues for one eager fwd + bwd (a hipGraph replay issues the same nodes)
     launches_per_step = None
-    if hasattr(lib, "egx_launch_count"):
+    if args.full and hasattr(lib, "egx_launch_count"):
         lib.egx_launch_count(1)
         fwd_bwd()
         F_egx.run_deferred()
@@ -528,11 +558,16 @@ def run(args) -> int:
                    "loss": ("weighted CE in the forward's head epilogue (egx_ce)" if (wl["name"] in ("c1", "c2") and not args.no_fused_ce)
                             else "lossAV in the encoder's launches where the per-clip kernels can (egx_token_ce)" if (wl["name"] == "c3" and not args.no_fused_ce)
                             else "separate launch(es)")},
-        "library_launches_per_step": launches_per_step,
         "step_tflops": (fwd_f + bwd_f) / (ms_per_step * 1e-3) / 1e12,
         "step_frac_of_mfma_peak": (fwd_f + bwd_f) / (ms_per_step * 1e-3) / 1e12 / PEAK_TFLOPS[dtype],
     }
+    if args.full:
+        out["library_launches_per_step"] = launches_per_step
     if multi:
+        out["overlap"] = "staged" if overlap else ("bucketed" if bucketed else "none")
+        if exch["collectives"] is not None:
+            out["collectives_per_step"] = exch["collectives"]
+    if multi and args.full:
         # what took part: the rank count as a REAL collective sees it (sum of ones over the group), its backend, and how much of the
         # exchange the step actually pays for: the same step timed without any collective (same launches, same graph policy)
         t = torch.ones(1, device=dev, dtype=torch.float32)
@@ -552,11 +587,8 @@ def run(args) -> int:
         out["exposed_collective_us"] = (ms_per_step - ms_ne) * 1e3
     if allreduce_us is not None:
         out["allreduce_us"] = allreduce_us
-        out["overlap"] = "staged" if overlap else ("bucketed" if bucketed else "none")
-        if exch["collectives"] is not None:
-            out["collectives_per_step"] = exch["collectives"]
 
-    if not args.optimizer and not args.no_optimizer_line:
+    if args.full and not args.optimizer and not args.no_optimizer_line:
         # "+ optimizer step reported separately" (SURVEY.md 8d): the same step with the Adam update inside
         opt2 = FusedAdam(params, lr=5e-4)
         if wcache_on:
@@ -569,7 +601,7 @@ def run(args) -> int:
         if wcache_on:
             F_egx.note_weights_changed()                 # (the replayed updates wrote the parameters behind torch's back)
             model.enable_weight_cache(frozen=True)
-    if dtype == "f32s" and not multi and not args.no_native_line:
+    if args.full and dtype == "f32s" and not multi and not args.no_native_line:
         # the same step on the exact fp32 MFMA path (v_mfma_f32_16x16x4_f32), for reference
         model.set_compute("f32", args.impl)
         step3 = make_step(None)
@@ -579,7 +611,7 @@ def run(args) -> int:
                              "value": B * world / (m3 * 1e-3), "unit": "clips/s",
                              "step_frac_of_mfma_peak": (fwd_f + bwd_f) / (m3 * 1e-3) / 1e12 / PEAK_TFLOPS["f32"]}
         model.set_compute("f32s", args.impl)
-    if wl["name"] in ("c1", "c2") and not multi and not args.no_native_line and hasattr(model, "dp_rate"):
+    if args.full and wl["name"] in ("c1", "c2") and not multi and not args.no_native_line and hasattr(model, "dp_rate"):
         # two series. The line above is the reference recipe (dropout 0.5 + 0.1 on the positional encoding); this is
         # the deterministic p = 0 configuration the parity tests check, the GPU partner of cpu_baseline.train_p0
         p_keep, pe_keep = model.dp_rate, model.pos_embed.dropout.p
@@ -590,7 +622,7 @@ def run(args) -> int:
         out["dropout0"] = {"dropout": 0.0, "ms_per_step": m0, "value": B * world / (m0 * 1e-3), "unit": "clips/s",
                            "note": "same step, train mode, every dropout probability 0 (no mask work in the kernels)"}
         model.dp_rate, model.pos_embed.dropout.p = p_keep, pe_keep
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         model.egx_defer_small = False
         out["roofline"] = measure_roofline(torch, lib, fwd_bwd, wl, dtype)
         # `frac` is the dominant LAUNCH's fraction; `step_frac` the whole step's (all algorithmic FLOPs of forward + backward over the step time):
@@ -599,7 +631,7 @@ def run(args) -> int:
         out["roofline"]["step_tflops"] = out["step_tflops"]
         if wl.get("producer"):
             out["producer"] = wl["producer"]
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and wl["name"] in ("c1", "c2"):
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and wl["name"] in ("c1", "c2"):
         from oracle.stock_module import time_cpu_baseline
         out["cpu_baseline"] = time_cpu_baseline(B=B, T=args.frames, n_tasks=len(wl["feats"]), dim=128, n_heads=4,
                                                 num_layers=wl["L"], dropout=0.5 if args.dropout is None else args.dropout)
@@ -619,6 +651,34 @@ def run(args) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BYTES = 60 << 20         # --dump-outputs stays under 64 MB with the .npy headers and the one-entry floor of a sampled array
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` = [(name, tensor)] -> out_dir/<name>.npy in float32 (float64 stays float64). Above DUMP_BYTES in all, every array
+    keeps the same fraction of its entries, drawn without replacement by a generator seeded with the crc32 of its name (sorted
+    flat indices: the same ones in every run and every build)."""
+    import zlib
+
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = [t.numel() * (8 if t.dtype == torch.float64 else 4) for _, t in arrays]
+    frac = min(1.0, DUMP_BYTES / max(sum(sizes), 1))
+    for name, t in arrays:
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        if frac < 1.0:
+            n = t.numel()
+            k = max(1, int(n * frac))
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, size=k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    if frac < 1.0:
+        print(f"[bench] --dump-outputs: {sum(sizes) / 2**20:.0f} MB of outputs, a seeded {frac:.3%} of every array written", file=sys.stderr)
 
 
 def csrc_sha():

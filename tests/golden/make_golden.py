@@ -264,9 +264,48 @@ def run_head():
         print("wrote", c["name"])
 
 
+def run_live():
+    """live/: the recorded outputs of two checks that once imported the reference class at test time (tests/test_oracle_golden.py
+    ::test_oracle_matches_live_reference, tests/test_oracle_dropout.py::test_oracle_masks_against_the_live_reference_class): the
+    3-task TTM translator in eval mode on fresh seeds, and in fp64 train mode with explicit dropout masks (tests/dropmask.py)."""
+    import numpy as np
+    import torch
+    from oracle import ref_harness as rh
+    from tests import dropmask as dm
+    from tests.test_oracle_dropout import _queue_for_ttm, explicit_dropout
+    from tests.util import seeded_feats, seeded_state_dict
+    live = os.path.join(HERE, "live")
+    os.makedirs(live, exist_ok=True)
+    # eval mode, fp32: L = 2, 5 clips of 17 frames per task
+    c = dict(name="ttm3_eval_B5_T17_L2", n_tasks=3, B=5, T=17, L=2, d=128, h=4, wseed=777, fseed=778)
+    m = rh.ref_ttm(3, rh.hhi_args(num_layers=c["L"]))
+    m.load_state_dict(seeded_state_dict(m, c["wseed"]))
+    m.eval()
+    feats = seeded_feats(c["fseed"], [(c["B"], c["T"], 256)] * 3)
+    with torch.no_grad():
+        ref = rh.ref_ttm_forward(m, *feats)
+    np.savez_compressed(os.path.join(live, c["name"] + ".npz"), config=np.array(json.dumps(c)), sd_keys=np.array(sd_keys(m)),
+                        out=ref.numpy())
+    print("wrote live/" + c["name"])
+    # train mode, fp64, every dropout site fed the masks of tests/dropmask.py in the reference's call order
+    c = dict(name="ttm3_trainmask_B4_T6_L2", n_tasks=3, B=4, T=6, L=2, d=128, h=4, p=0.5, p_pos=0.1, wseed=5, fseed=8, mseed=77)
+    B, T, L, d, H, p = c["B"], c["T"], c["L"], c["d"], c["h"], c["p"]
+    m = rh.ref_ttm(3, rh.hhi_args(hidden_dim=d, num_heads=H, dropout=p, num_layers=L)).double().train()
+    m.load_state_dict({k: v.double() for k, v in seeded_state_dict(m, c["wseed"]).items()})
+    feats = [f.double() for f in seeded_feats(c["fseed"], [(B, T, 256)] * 3)]
+    masks = dm.encoder_masks(c["mseed"], "fused", B, [T] * 3, d, H, 2048, L, p, c["p_pos"])
+    queue = _queue_for_ttm(masks, [T] * 3, B, H, L)
+    with explicit_dropout(queue):
+        logits = rh.ref_ttm_forward(m, *feats)
+    assert not queue
+    np.savez_compressed(os.path.join(live, c["name"] + ".npz"), config=np.array(json.dumps(c)), sd_keys=np.array(sd_keys(m)),
+                        out=logits.detach().numpy())
+    print("wrote live/" + c["name"])
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
-        {"hhi": run_hhi, "hoi": lambda: (run_hoi(), run_head())}[sys.argv[1]]()
+        {"hhi": lambda: (run_hhi(), run_live()), "live": run_live, "hoi": lambda: (run_hoi(), run_head())}[sys.argv[1]]()
     else:  # HHI and HOI share top-level package names -> one process per tree
         for tree in ("hhi", "hoi"):
             subprocess.check_call([sys.executable, os.path.abspath(__file__), tree])

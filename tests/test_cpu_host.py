@@ -9,6 +9,8 @@ import sys
 import pytest
 import torch
 
+from tests.util import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -126,6 +128,34 @@ def test_bench_flop_model_matches_baseline_md():
     assert abs(fwd / 1e9 - 14.610) < 0.01 and abs((fwd + bwd) / 1e9 - 43.075) < 0.02
 
 
+def test_bench_plain_defaults_and_dump_outputs(tmp_path, monkeypatch):
+    """A plain bench line times one region of --steps steps (--trials defaults to 1 unless --full), and --dump-outputs writes
+    float32 / float64 arrays; above the byte budget every array keeps a seeded sample, the same indices in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert a.steps == 7 and a.trials is None and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    g = torch.Generator().manual_seed(0)
+    arrays = [("loss", torch.tensor(0.5)), ("grad.w", torch.randn(64, 32, generator=g).bfloat16()),
+              ("grad.b", torch.randn(16, generator=g, dtype=torch.float64))]
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    w = np.load(tmp_path / "all" / "grad.w.npy")
+    assert w.dtype == np.float32 and w.shape == (64, 32) and np.array_equal(w, arrays[1][1].float().numpy())
+    assert np.load(tmp_path / "all" / "grad.b.npy").dtype == np.float64 and float(np.load(tmp_path / "all" / "loss.npy")) == 0.5
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["grad.b.npy", "grad.w.npy", "loss.npy"]
+    assert sum(np.load(tmp_path / "s1" / f).nbytes for f in files) <= 4096 + len(files) * 8
+    ws = np.load(tmp_path / "s1" / "grad.w.npy")
+    assert 0 < ws.size < 64 * 32 and np.isin(ws, w).all()
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+
+
 def _ddp_worker(rank, world, port, q):
     import torch.distributed as dist
     from egot2_amd import ddp
@@ -167,7 +197,7 @@ def test_two_rank_gradient_allreduce_equals_single_process():
     from oracle.stock_module import StockTTMTranslator
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_ddp_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -215,7 +245,7 @@ def test_two_rank_overlapped_allreduce():
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 31500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_overlap_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -269,7 +299,7 @@ def test_two_rank_bucketed_exchange():
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 35500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -292,7 +322,7 @@ def test_bench_self_launches_ranks_gloo():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    port = 33500 + os.getpid() % 2000
+    port = free_port()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-selftest", "--backend", "gloo",
                         "--master-port", str(port)], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -351,7 +381,7 @@ def test_two_rank_weighted_ce_normalisation_effect():
     from oracle.stock_module import StockTTMTranslator
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 35500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_ddp_weighted_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -386,7 +416,7 @@ def test_overlapped_allreduce_also_exchanges_gradients_outside_the_flat_buffer()
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 37500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_overlap_params_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -1,13 +1,15 @@
 """CPU: pins the oracle's explicit-mask arguments (oracle/translator_ref.py `masks`) to the TRAIN-mode arithmetic of the stock
 torch.nn modules the reference instantiates, and tests/dropmask.py's generator against hand-computed words.
 
-The stock module (oracle/stock_module.py = the reference class minus backbones; the live reference class when
-/root/reference is present) runs in .train() with torch.nn.functional.dropout replaced by a function that hands out the
+The stock module (oracle/stock_module.py = the reference class minus backbones; the reference class itself through its
+recorded outputs, tests/golden/live/) runs in .train() with torch.nn.functional.dropout replaced by a function that hands out the
 masks in call order — PositionalEncoding per segment, then per layer attention probabilities / dropout1 / FFN hidden /
 dropout2 — so every site, its position in the arithmetic and its layout (the reference is sequence-first) is checked
 against what torch itself does, not against our reading of it."""
 import contextlib
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -94,24 +96,22 @@ def test_oracle_masks_are_torchs_train_mode_sites(L, B, T):
         assert (prm.grad - g).abs().max().item() < 1e-9 * (1 + g.abs().max().item()), k
 
 
-@pytest.mark.reference
 def test_oracle_masks_against_the_live_reference_class():
-    """Same check with the REAL reference class (imported with import-time stubs only) instead of the stock restatement."""
-    from oracle import ref_harness as rh
-    if not rh.reference_available():
-        pytest.skip("/root/reference not present")
-    B, T, L, d, H, p = 4, 6, 2, 128, 4, 0.5
-    model = rh.ref_ttm(3, rh.hhi_args(hidden_dim=d, num_heads=H, dropout=p, num_layers=L)).double().train()
-    sd = {k: v.double() for k, v in seeded_state_dict(model, 5).items()}
-    model.load_state_dict(sd)
-    feats = [f.double() for f in seeded_feats(8, [(B, T, 256)] * 3)]
-    masks = dm.encoder_masks(77, "fused", B, [T] * 3, d, H, 2048, L, p, 0.1)
-    queue = _queue_for_ttm(masks, [T] * 3, B, H, L)
-    with explicit_dropout(queue):
-        logits = rh.ref_ttm_forward(model, *feats)
-    assert not queue
+    """Same check with the REAL reference class (imported with import-time stubs only) instead of the stock restatement: its fp64
+    train-mode logits under these masks were recorded by tests/golden/make_golden.py (golden/live/ttm3_trainmask_B4_T6_L2.npz).
+    The weights are re-derived from the seed on the stock module, whose state_dict keys and shapes must be the reference's."""
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "live", "ttm3_trainmask_B4_T6_L2.npz"))
+    c = json.loads(str(z["config"]))
+    B, T, L, d, H, p = c["B"], c["T"], c["L"], c["d"], c["h"], c["p"]
+    model = StockTTMTranslator(c["n_tasks"], d, H, p, L).double()
+    assert {k: list(v.shape) for k, v in model.state_dict().items()} == json.loads(str(z["sd_keys"]))
+    sd = {k: v.double() for k, v in seeded_state_dict(model, c["wseed"]).items()}
+    feats = [f.double() for f in seeded_feats(c["fseed"], [(B, T, 256)] * c["n_tasks"])]
+    masks = dm.encoder_masks(c["mseed"], "fused", B, [T] * c["n_tasks"], d, H, 2048, L, p, c["p_pos"])
+    logits = torch.from_numpy(z["out"])
+    assert logits.dtype == torch.float64
     ref = tr.ttm_forward(sd, H, *feats, masks=masks)
-    assert (logits - ref).abs().max().item() < 1e-10
+    assert ref.shape == logits.shape and (logits - ref).abs().max().item() < 1e-10
 
 
 def test_generator_known_answers():

@@ -1,6 +1,6 @@
 """CPU suite: the oracle restatement (oracle/translator_ref.py) and the stock-module CPU baseline against the golden
-fixtures generated from the REAL reference classes (tests/golden/make_golden.py), plus — when /root/reference is
-present — a live comparison against the imported reference."""
+fixtures generated from the REAL reference classes (tests/golden/make_golden.py), plus the recorded outputs of the reference
+class on seeds of their own (tests/golden/live/)."""
 import glob
 import json
 import os
@@ -289,18 +289,17 @@ def test_stock_module_matches_fixture():
     check_against_fixture(z, {"out": logits}, loss, {k: p.grad for k, p in m.named_parameters()}, 2e-5, 2e-4)
 
 
-@pytest.mark.reference
 def test_oracle_matches_live_reference():
-    """Where /root/reference exists: import the real class and compare on fresh seeds (not only the stored ones)."""
-    from oracle import ref_harness as rh
-    if not rh.reference_available():
-        pytest.skip("/root/reference not present")
-    m = rh.ref_ttm(3, rh.hhi_args(num_layers=2))
-    m.load_state_dict(seeded_state_dict(m, 777))
-    m.eval()
-    feats = seeded_feats(778, [(5, 17, 256)] * 3)
-    with torch.no_grad():
-        ref = rh.ref_ttm_forward(m, *feats)
+    """The real class on seeds of their own (not those of the fixtures above), eval mode: its logits were recorded by
+    tests/golden/make_golden.py into golden/live/ttm3_eval_B5_T17_L2.npz; the weights are re-derived from the seed on the stock
+    module, whose state_dict keys and shapes must be the reference's."""
+    from oracle.stock_module import StockTTMTranslator
+    c, z = load_fixture(os.path.join("live", "ttm3_eval_B5_T17_L2"))
+    m = StockTTMTranslator(c["n_tasks"], c["d"], c["h"], num_layers=c["L"])
+    assert {k: list(v.shape) for k, v in m.state_dict().items()} == json.loads(str(z["sd_keys"]))
+    m.load_state_dict(seeded_state_dict(m, c["wseed"]))
+    feats = seeded_feats(c["fseed"], [(c["B"], c["T"], 256)] * c["n_tasks"])
     sd = {k: v.detach() for k, v in m.state_dict().items()}
-    out = tr.ttm_forward(sd, 4, *feats)
-    assert (out - ref).abs().max().item() < 1e-5
+    out = tr.ttm_forward(sd, c["h"], *feats)
+    ref = torch.from_numpy(z["out"])
+    assert out.shape == ref.shape and (out - ref).abs().max().item() < 1e-5

@@ -41,3 +41,12 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
 
 def max_err(a: torch.Tensor, b: torch.Tensor) -> float:
     return (a.double().cpu() - b.double().cpu()).abs().max().item()
+
+
+def free_port() -> int:
+    """A TCP port no socket holds right now, chosen by the OS: a fixed port inside the ephemeral range (32768-60999) can be
+    held by any client connection of an earlier test, and a rank that cannot bind its rendezvous leaves the others waiting."""
+    import socket
+    with socket.socket() as s:
+        s.bind(("", 0))
+        return s.getsockname()[1]

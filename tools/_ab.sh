@@ -3,7 +3,7 @@
 base=${1:-head}; shift
 cfgs=${@:-"c2:f32s c2:bf16 c3:bf16"}
 mkdir -p gpurun_out/ab
-B="--no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline --min-seconds 1.5"
+B="--full --no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline --min-seconds 1.5"
 for rep in 1 2; do
 for cd in $cfgs; do
   cfg=${cd%%:*}; dt=${cd##*:}

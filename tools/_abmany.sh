@@ -1,6 +1,6 @@
 # usage (GPU box): bash tools/_abmany.sh "<variant names, 'new' = the product library>" "<cfg:dtype[:extra bench args] ...>" [reps] — interleaved same-box runs
 vars=$1; cfgs=$2; reps=${3:-3}
-B="--no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline --min-seconds 1.2"
+B="--full --no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline --min-seconds 1.2"
 for rep in $(seq $reps); do for cd in $cfgs; do
   cfg=$(echo $cd | cut -d: -f1); dt=$(echo $cd | cut -d: -f2); extra=$(echo $cd | cut -d: -f3- | tr ':' ' ')
   for v in $vars; do

@@ -1,7 +1,7 @@
 # usage (GPU box): bash tools/ab_round.sh — same-box, interleaved: the round-5 library (egot2_amd/_variants/lib_r5.so, built from commit af434af's csrc;
 # bench.py --no-fused-ce --no-weight-cache = the round-5 step: packing launch and weighted_ce launch inside the step) against the product library, and the cut
 # mode against the one-launch kernels on the final tree (development aid; results: profiles/r06_ab_round.txt)
-B="--no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline"
+B="--full --no-cpu-baseline --no-optimizer-line --no-native-line --no-roofline"
 for rep in 1 2 3; do
   for cd in c2:f32s c2:bf16 c3:bf16; do
     cfg=${cd%%:*}; dt=${cd##*:}

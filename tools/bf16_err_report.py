@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.test_oracle_golden import FIXTURES, build_ours, fixture_feats, load_fixture
 from tests.test_gpu_golden import hip_run
 from tests.util import seeded_state_dict

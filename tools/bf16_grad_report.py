@@ -1,5 +1,5 @@
-import sys, torch, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, torch, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import translator_ref as tr
 from tests.util import hhi_args, rel_err, seeded_feats, seeded_state_dict
 from egot2_amd import hhi_ttm

@@ -1,7 +1,7 @@
 """Error of the three compute modes of the fused kernels against the fp64 oracle (development report, GPU box).
 usage: python tools/f32s_err_report.py"""
-import sys, torch, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, torch, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import translator_ref as tr
 from tests.util import hhi_args, rel_err, seeded_feats, seeded_state_dict
 from egot2_amd import hhi_ttm

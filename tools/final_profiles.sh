@@ -11,7 +11,7 @@ bench() {   # bench <name> <bench.py args...>
   local name=$1; shift
   # (no retry: round 5 retried a failed line once because the captured collectives could abort in PyTorch's RCCL watchdog thread; since round 6 the
   # captured exchange runs on egx_allreduce, which has no such thread — a failure here is a real one)
-  if python bench.py "$@" > $OUT/bench_$name.log 2>&1; then
+  if python bench.py --full "$@" > $OUT/bench_$name.log 2>&1; then
     tail -1 $OUT/bench_$name.log > $OUT/${R}_bench_$name.json
     python tools/benchline.py $OUT/${R}_bench_$name.json $name
   else
@@ -20,7 +20,7 @@ bench() {   # bench <name> <bench.py args...>
 }
 prof() {    # prof <config> <name> <bench.py args...>
   local cfg=$1 name=$2; shift 2
-  tools/profile_bench.sh $cfg final/prof_$name "$@" > $OUT/prof_$name.txt 2>&1 || { echo "profile $name FAILED"; tail -5 $OUT/prof_$name.txt; return 1; }
+  tools/profile_bench.sh $cfg final/prof_$name --full "$@" > $OUT/prof_$name.txt 2>&1 || { echo "profile $name FAILED"; tail -5 $OUT/prof_$name.txt; return 1; }
   cp gpurun_out/final/prof_${name}_kernel_stats.csv $OUT/${R}_bench_${name}_kernel_stats.csv
 }
 if [[ $STAGES == *bench* ]]; then

@@ -59,7 +59,7 @@ def main():
             d = os.path.join(out_dir, f"pmc_{tag}_{pname}")
             subprocess.run(["rm", "-rf", d])
             cmd = ["rocprofv3", "--pmc"] + counters.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "r", "--",
-                   "python3", os.path.join(ROOT, "bench.py")] + bench_args + ["--no-graph", "--no-cpu-baseline", "--no-roofline", "--no-optimizer-line",
+                   "python3", os.path.join(ROOT, "bench.py")] + bench_args + ["--full", "--no-graph", "--no-cpu-baseline", "--no-roofline", "--no-optimizer-line",
                    "--no-native-line", "--steps", str(steps), "--warmup", str(warmup), "--trials", "1"]
             with open(d + ".log", "w") as log:
                 rc = subprocess.run(cmd, stdout=log, stderr=subprocess.STDOUT, env=env, cwd="/tmp").returncode
