@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
+#include <vector>
 
 #include "../../include/egot2x.h"
 #include "common.h"
@@ -1553,6 +1554,184 @@ int egx_dropout(float* x, int rows, int cols, float p_drop, uint64_t seed, uint3
     EGX_CHECK(x || rows * cols == 0, "egx_dropout: null pointer");
     Drop dr = make_drop(p_drop > 0.f, p_drop, seed, site >> 8, site & 0xffu);
     return apply_dropout_mask(x, rows, cols, dr.key, dr.thresh, dr.inv_keep, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- ragged batches (egx_ragged_fwd): inference over clips of their own lengths on the tiled kernels ---------------------------------
+// The tile grid of the tiled mode with per-clip offsets: clip b has S_b = sum_k T_{b,k} tokens in ceil(S_b / 48) tiles; its tiles, dense token
+// rows, log-sum-exp rows and output rows start at the prefix sums of the clips before it (fused.h RAGGED_REC). The workspace is the tiled
+// forward's layout sized for N = sum_b S_b tokens and sum_b ceil(S_b / 48) tiles, then the device copy of the batch table.
+namespace {
+struct RaggedPlan {
+    Plan vp;                    // vp.B clips, vp.vB tiles, vp.N = sum_b S_b tokens, vp.S = the longest clip
+    size_t out_rows = 0;        // head-less output rows: sum_b T_{b,0}
+    size_t off_attn = 0, off_lse = 0, off_tokens = 0, off_tab = 0, bytes = 0;
+    std::vector<int> tab;       // host copy of the batch table
+};
+
+int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp) {
+    Plan& vp = rp.vp;
+    if (make_plan(cfg, segs, B, vp)) return 1;
+    EGX_CHECK(lengths, "ragged batch: null lengths");
+    EGX_CHECK(B <= (1 << 20), "ragged batch: B=%d clips (at most %d)", B, 1 << 20);
+    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
+              "ragged batches are inference-only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g)", cfg->p_drop, cfg->p_pos, cfg->p_feat);
+    EGX_CHECK(cfg->out_tokens == 0, "ragged batch: out_tokens is not supported (head-less, the first segment of every clip is returned)");
+    EGX_CHECK(!cfg->ce && !cfg->token_ce, "ragged batch: the fused losses (egx_config.ce / token_ce) are not supported; apply the loss to the outputs");
+    EGX_CHECK(!cfg->bucket_cb, "ragged batch: bucket_cb is a backward option (the ragged call is a forward only)");
+    EGX_CHECK(!cfg->weight_cache_valid || cfg->weight_cache, "weight_cache_valid without a weight_cache");
+    EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_TILED, "ragged batch: runs on the tiled kernels (impl auto or tiled, got %d)", cfg->impl);
+    // what tiled_ok() asks of the configuration, the clip length apart
+    EGX_CHECK(vp.d == 128 && vp.H == 4 && vp.dff % 128 == 0 && vp.dff >= 128 && vp.nseg <= FUSED_MAX_SEG && vp.L >= 1 && vp.L <= FUSED_MAX_LAYERS &&
+              !packed_feats(segs, vp.nseg) && (cfg->compute == EGX_F32_SPLIT || (cfg->compute == EGX_BF16 && ffn_dw_bf16_planes())),
+              "ragged batch: needs d=128, h=4, d_ff%%128==0, <= %d segments, 1..%d layers, fp32 features, compute bf16 or f32s", FUSED_MAX_SEG, FUSED_MAX_LAYERS);
+    for (int k = 0; k < vp.nseg; ++k)
+        EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0, "ragged batch: segment %d needs a projection with d_in %% 128 == 0", k);
+    const int K = vp.nseg;
+    rp.tab.assign((size_t)B * RAGGED_REC, 0);
+    int tiles = 0, S_max = 0;
+    size_t tok = 0, out = 0;
+    for (int b = 0; b < B; ++b) {
+        int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
+        int S = 0;
+        for (int k = 0; k < K; ++k) {
+            const int T = lengths[(size_t)b * K + k];
+            EGX_CHECK(T >= 1 && T <= segs[k].T, "ragged batch: clip %d segment %d has %d frames (1 .. %d, the padded length)", b, k, T, segs[k].T);
+            rec[RG_T + k] = T; rec[RG_OFF + k] = S;
+            S += T;
+        }
+        EGX_CHECK(S <= TILED_MAX_S, "ragged batch: clip %d has S=%d tokens (at most %d)", b, S, TILED_MAX_S);
+        rec[RG_TILE0] = tiles; rec[RG_S] = S; rec[RG_TOK0] = (int)tok;
+        rec[RG_OUT0] = (int)out; rec[RG_OUTN] = rec[RG_T];      // head-less output: the first segment; with a head the call rewrites these
+        tiles += cdiv(S, FUSED_TOK_PAD);
+        tok += S; out += rec[RG_T];
+        S_max = S > S_max ? S : S_max;
+    }
+    rp.tab.resize((size_t)B * RAGGED_REC + tiles);
+    for (int b = 0; b < B; ++b) {
+        const int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
+        for (int j = 0; j < cdiv(rec[RG_S], FUSED_TOK_PAD); ++j) rp.tab[(size_t)B * RAGGED_REC + rec[RG_TILE0] + j] = b;
+    }
+    vp.vB = tiles; vp.tpc = 0; vp.N = tok; vp.S = S_max;
+    rp.out_rows = out;
+    const size_t d = vp.d;
+    rp.off_attn = align_up(fused_x1f_offset(cfg, segs, vp), 256);        // (the tiled launches write no x1f rows: fused_core_bytes with tpc > 1)
+    rp.off_lse = rp.off_attn + align_up((size_t)vp.L * vp.N * d * 4, 256);
+    rp.off_tokens = rp.off_lse + align_up((size_t)vp.L * vp.H * vp.N * 4, 256);
+    rp.off_tab = rp.off_tokens + align_up((vp.N + (size_t)B) * d * 4, 256);
+    rp.bytes = rp.off_tab + align_up(rp.tab.size() * sizeof(int), 256);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int egx_ragged_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+    if (bytes) *bytes = rp.bytes;
+    return 0;
+}
+
+int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                   const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, void* stream) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+    const Plan& vp = rp.vp;
+    EGX_CHECK(workspace && ln_w && ln_b && layers, "ragged batch: null pointer argument");
+    const bool with_head = head && head->W;
+    EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged batch: null output pointer");
+    EGX_CHECK(!with_head || (head->ln_w && head->ln_b && head->b && head->n_out >= 1 && head->n_out <= FUSED_HEAD_MAX_OUT),
+              "head needs ln_w, ln_b, W, b and 1 <= n_out <= %d", FUSED_HEAD_MAX_OUT);
+    hipStream_t st = (hipStream_t)stream;
+    const int d = vp.d, comp = cfg->compute;
+    const size_t N = vp.N;
+    char* ws = (char*)workspace;
+    float* dense = (float*)(ws + rp.off_tokens);        // with a head: every token of the last layer (N, d), then the pooled rows (B, d)
+    if (with_head)
+        for (int b = 0; b < B; ++b) {
+            int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
+            rec[RG_OUT0] = rec[RG_TOK0]; rec[RG_OUTN] = rec[RG_S];
+        }
+    // the batch table to the device, stream-ordered, in the arguments of upload launches (no host buffer has to outlive the call). Its
+    // contents depend on the lengths of THIS call: a captured hipGraph would replay them for every batch, so the call is not for capture.
+    int* tab = (int*)(ws + rp.off_tab);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+
+    FusedFwdParams fp;
+    memset(&fp, 0, sizeof(fp));
+    PackParams pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.mode = comp;
+    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, workspace, vp));
+    const bool cache_hit = cfg->weight_cache && cfg->weight_cache_valid;
+    auto add_pack = [&](const float* src, void* dst, int R, int Kd, int ld, int transpose) -> const void* {
+        if (cache_hit) return dst;
+        PackDesc& dsc = pk.d[pk.n++];
+        dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = Kd; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = 1.f;
+        return dst;
+    };
+    for (int i = 0; i < vp.nseg; ++i) {
+        FusedSeg& fs = fp.seg[i];
+        fs.feat = segs[i].feat; fs.proj_wp = add_pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0); fs.proj_b = segs[i].proj_b;
+        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos;
+        fs.T = segs[i].T; fs.d_in = segs[i].d_in; fs.pos_stride = segs[i].pos_stride;
+        fs.Tfull = segs[i].T; fs.seg_id = i;        // (the clip's own pieces come from the batch table)
+    }
+    fp.n_heads = vp.H;
+    for (int l = 0; l < vp.L; ++l) {
+        FusedLayer& fl = fp.layer[l];
+        const egx_layer& w = layers[l];
+        fl.in_proj_wp = add_pack(w.in_proj_w, PL.layer[l].in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
+        fl.out_proj_wp = add_pack(w.out_proj_w, PL.layer[l].out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
+        fl.lin1_wp = add_pack(w.lin1_w, PL.layer[l].lin1_w, vp.dff, d, d, 0); fl.lin1_b = w.lin1_b;
+        fl.lin2_wp = add_pack(w.lin2_w, PL.layer[l].lin2_w, d, vp.dff, vp.dff, 0); fl.lin2_b = w.lin2_b;
+        // the transposed copies too: a weight cache this call fills must serve a later backward as the tiled forward's does
+        add_pack(w.in_proj_w, PL.layer[l].in_wt, d, 3 * d, d, 1);
+        add_pack(w.out_proj_w, PL.layer[l].out_wt, d, d, d, 1);
+        add_pack(w.lin1_w, PL.layer[l].lin1_wt, d, vp.dff, d, 1);
+        add_pack(w.lin2_w, PL.layer[l].lin2_wt, vp.dff, d, vp.dff, 1);
+        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+    }
+    fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
+    fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = FUSED_TOK_PAD; fp.d_ff = vp.dff;
+    fp.tpc = 0; fp.S_clip = vp.S; fp.Ntok = N;
+    fp.tokens_out = with_head ? dense : tokens_out;
+    fp.saved_pre = (float*)ws;
+    fp.saved_res = (float*)ws + N * d;
+    fp.relu_bits = (uint32_t*)(ws + fused_res_bytes(vp));
+    fp.hid_out = store_hidden() ? ws + fused_hid_offset(cfg, segs, vp) : nullptr;
+    fp.x1p_out = split_planes(cfg) ? (unsigned short*)(ws + fused_x1p_offset(cfg, segs, vp)) : nullptr;
+    fp.xin_out = (float*)(ws + fused_xin_offset(cfg, segs, vp));
+    fp.qkv_out = (float*)(ws + fused_qkv_offset(cfg, segs, vp));
+    // every tile walks the FFN hidden blocks from block 0 (rot_mode 1, +2.5 % of the tiled launches' time against the staggered default):
+    // the staggered start depends on the tile's place in the grid, so a clip's result would depend on where the batch puts it
+    fp.rot_mode = 1;
+    fp.n_slices = 1;
+    fp.rtab = tab; fp.B_clips = B;
+    if (cfg->weight_cache && pk.n) pk.zero_ctl = (unsigned*)((char*)cfg->weight_cache + align_up(PL.bytes, 256));     // (as the tiled forward)
+    if (pack_weights(pk, st)) return 1;
+    float* attn = (float*)(ws + rp.off_attn);
+    float* lse = (float*)(ws + rp.off_lse);
+    fp.attn_in = attn;
+    fp.mode = FUSED_MODE_PRE;
+    if (fused_forward(fp, comp, st)) return 1;
+    for (int l = 0; l < vp.L; ++l) {
+        TiledAttnParams ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.qkv = fp.qkv_out + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * d;
+        ap.attn_o = attn + (size_t)l * N * d;
+        ap.lse = lse + (size_t)l * vp.H * N;
+        ap.B = B; ap.S = vp.S; ap.tpc = 0; ap.layer = l;
+        ap.rtab = tab;
+        if (tiled_attn_fwd(ap, comp, st)) return 1;
+        fp.mode = FUSED_MODE_POST; fp.l0 = l;
+        if (fused_forward(fp, comp, st)) return 1;
+    }
+    if (with_head)
+        return pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st);
+    return 0;
 }
 
 }  // extern "C"

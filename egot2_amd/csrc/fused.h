@@ -109,6 +109,9 @@ struct FusedFwdParams {
                             // the clips add their loss terms into the accumulator, the LAST one moves the sum to *ce_loss and leaves zeros
                             // (a one-launch forward with a valid weight cache has no earlier launch that could zero *ce_loss)
     TouchList touch;        // weight streams of a later launch to bring into the Infinity Cache (see TouchList)
+    // ---- ragged batches (egx_ragged_fwd): clips of their own lengths on the tile grid. Non-null: the tiled launches run the RAGGED
+    // instantiation, which reads its tile's clip, first token, per-segment frame counts and output rows from this table (RAGGED_REC below)
+    const int* rtab; int B_clips;     // (B_clips clip records, then the clip of each of the B tiles)
 };
 enum { FUSED_MODE_FULL = 0, FUSED_MODE_PRE = 1, FUSED_MODE_POST = 2, FUSED_MODE_ATTN = 3 };
 
@@ -294,8 +297,19 @@ struct TiledAttnParams {
     int B, S, tpc;
     uint64_t drop_key; uint32_t drop_thresh; float drop_inv;
     const uint64_t* seed_ptr; int layer;
+    const int* rtab;        // ragged batch (RAGGED_REC below): B clips of their own lengths, S = the longest; null = B clips of S tokens
 };
 constexpr int TILED_MAX_S = 512;
+// Ragged batch table (egx_ragged_fwd, built on the host, one copy to the device): B clip records of RAGGED_REC ints, then the clip of
+// each of the sum_b ceil(S_b / 48) tiles. Clip b's tiles are tiles [tile0, tile0 + ceil(S_b / 48)) of the grid (its Q | K | V rows start
+// at row 48 tile0 of the 48-row tile grid), its tokens are rows [tok0, tok0 + S_b) of the dense (N, .) arrays and its log-sum-exp rows
+// start at 4 tok0; the last layer writes its token rows [0, out_n) to rows [out0, out0 + out_n) of tokens_out.
+constexpr int RAGGED_REC = 16;
+enum { RG_TILE0 = 0, RG_S = 1, RG_TOK0 = 2, RG_OUT0 = 3, RG_OUTN = 4, RG_T = 5 /* .. 8: frames of segment k */, RG_OFF = 9 /* .. 12: first token of segment k */ };
+static_assert(RG_OFF + FUSED_MAX_SEG <= RAGGED_REC, "ragged clip record");
+// n host words -> dst (device) on the stream, carried in the kernel arguments of one small launch per 960 words: the data is captured when
+// the launch is enqueued, so the host copy may go away at once (the ragged batch table)
+int upload_words(int* dst, const int* src, size_t n, hipStream_t st);
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st);
 int tiled_attn_bwd(const TiledAttnParams& p, int compute, hipStream_t st);
 

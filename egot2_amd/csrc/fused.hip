@@ -19,6 +19,7 @@
 #include "fused.h"
 #include "fused_dev.h"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 #include <vector>
 
@@ -131,9 +132,12 @@ int debug_read_stamps(unsigned long long* out, int n) {
 // test: with the slice code compiled into the one-workgroup-per-clip kernels their B = 256 step was 1 % (f32s) / 2.5 % (bf16) slower.
 // CUT (round 5, ffn_cut.hip): the launch runs [token preparation (l0 = 0) | the saved input of layer l0] .. LayerNorm1 of layer l0 and
 // leaves x1; the FFN, the second residual and LayerNorm2 are ffn_fwd_kernel's (eight waves per clip).
-template <int CM, int NT, bool TILED, int DH, bool SLICED = false, bool CUT = false>
+// RAGGED (egx_ragged_fwd): tiled launches over clips of their own lengths; the tile's clip, first token, segment pieces and output rows
+// come from the ragged batch table (FusedFwdParams::rtab, RAGGED_REC) instead of the uniform clip / tpc arithmetic.
+template <int CM, int NT, bool TILED, int DH, bool SLICED = false, bool CUT = false, bool RAGGED = false>
 __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
     static_assert(!(TILED && SLICED), "the tiled launches are not sliced");
+    static_assert(!RAGGED || TILED, "ragged batches run the tiled launches");
     static_assert(!(CUT && (TILED || SLICED)), "the cut launches are neither tiled nor sliced");
     constexpr int HPW = FDH / DH;               // heads per wave: 1 (4 heads of 32) or 2 (8 heads of 16)
     constexpr int NHEAD = FH * HPW;
@@ -165,7 +169,14 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
     const int n_slices = SLICED ? p.n_slices : 1;
     int S, c_real, t0;                      // tokens of this workgroup, the clip they belong to, their first token within it
     size_t tokbase;                         // global index of the first token: row of the dense (Ntok, .) arrays, dropout row key
-    if constexpr (TILED) {
+    const int* rrec = nullptr;              // RAGGED: the clip's record of the batch table
+    if constexpr (RAGGED) {
+        c_real = p.rtab[(size_t)p.B_clips * RAGGED_REC + clip];
+        rrec = p.rtab + (size_t)c_real * RAGGED_REC;
+        t0 = (clip - rrec[RG_TILE0]) * 48;
+        S = min(48, rrec[RG_S] - t0);
+        tokbase = (size_t)rrec[RG_TOK0] + t0;
+    } else if constexpr (TILED) {
         c_real = clip / p.tpc;
         t0 = (clip - c_real * p.tpc) * 48;
         S = min(48, p.S_clip - t0);
@@ -191,7 +202,21 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
     const uint64_t seed_dev = dev_seed ? *p.seed_ptr : 0ull;
     const uint64_t pos_key = dev_seed ? site_key(seed_dev, 0, SITE_POS) : p.pos_key;
     int* const nseg_slot = reinterpret_cast<int*>(segtab + FUSED_MAX_SEG);
-    if constexpr (TILED) {
+    if constexpr (RAGGED) {
+        // the pieces of the clip's own segments in this tile (see below); Tfull keeps the PADDED frame count: the row stride of a clip in feat
+        if (tid == 0) {
+            int n = 0;
+            for (int i = 0; i < p.nseg; ++i) {
+                FusedSeg o = p.seg[i];
+                const int T = rrec[RG_T + i], off = rrec[RG_OFF + i];
+                const int lo = max(off, t0), hi = min(off + T, t0 + 48);
+                if (hi > lo) { o.Tfull = o.T; o.row0 = lo - off; o.T = hi - lo; o.off = lo - t0; o.seg_id = i; segtab[n++] = o; }
+            }
+            *nseg_slot = n;
+            nseg_slot[1] = rrec[RG_OUTN] - t0;      // rows of this tile that leave the last layer, at tokens_out row nseg_slot[2] (read there:
+            nseg_slot[2] = rrec[RG_OUT0] + t0;      // nothing is held in registers across the layers)
+        }
+    } else if constexpr (TILED) {
         // the segments that intersect this tile, as descriptors of their own: frames [row0, row0 + T) at tile rows [off, off + T)
         if (tid == 0) {
             int n = 0;
@@ -1200,7 +1225,8 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
         {
             bool last = (l + 1 == p.n_layers);
             ln_rows_lds(X1, S, PS + 9 * FD, PS + 10 * FD, p.eps, [&](int row, int c0, float (&x)[32], float (&y)[32]) {
-                if (last && p.tokens_out && (TILED || row < p.out_T)) store32(p.tokens_out + (TILED ? tokbase + row : (size_t)clip * p.out_T + row) * FD + c0, y);
+                if constexpr (RAGGED) { if (last && row < nseg_slot[1]) store32(p.tokens_out + ((size_t)nseg_slot[2] + row) * FD + c0, y); }
+                else if (last && p.tokens_out && (TILED || row < p.out_T)) store32(p.tokens_out + (TILED ? tokbase + row : (size_t)clip * p.out_T + row) * FD + c0, y);
                 if (!last || p.head.n_out > 0 || p.tce_W) store32(Xs + row * LDX + c0, y);
             }, [&] { store_block(sv_res2, X1, S); });        // (the LayerNorm leaves X1 alone)
         }
@@ -1431,6 +1457,40 @@ static int launch_fwd(const FusedFwdParams& p, hipStream_t st) {
     return 0;
 }
 
+constexpr int UPLOAD_WORDS = 960;
+struct UploadChunk { int* dst; int n; int v[UPLOAD_WORDS]; };
+__global__ __launch_bounds__(256) void upload_words_kernel(UploadChunk c) {
+    for (int i = threadIdx.x; i < c.n; i += 256) c.dst[i] = c.v[i];
+}
+int upload_words(int* dst, const int* src, size_t n, hipStream_t st) {
+    for (size_t i0 = 0; i0 < n; i0 += UPLOAD_WORDS) {
+        UploadChunk c;
+        c.dst = dst + i0;
+        c.n = (int)(n - i0 < (size_t)UPLOAD_WORDS ? n - i0 : (size_t)UPLOAD_WORDS);
+        memcpy(c.v, src + i0, sizeof(int) * c.n);
+        hipLaunchKernelGGL(upload_words_kernel, dim3(1), dim3(256), 0, st, c);
+        EGX_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// ragged batches (egx_ragged_fwd): the tiled launches with the batch table
+template <int CM>
+static int launch_fwd_ragged(const FusedFwdParams& p, hipStream_t st) {
+    EGX_CHECK(p.S == 48 && p.rtab && p.tokens_out, "fused: ragged launch needs S = 48, the batch table and tokens_out");
+    const size_t lds = fused_lds_bytes(3);
+    static bool attr_set = false;
+    if (!attr_set) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<CM, 3, true, 32, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    timing_begin(TIMER_FUSED_FWD, st);
+    hipLaunchKernelGGL((fused_fwd_kernel<CM, 3, true, 32, false, false, true>), dim3(p.B), dim3(256), lds, st, p);
+    timing_end(TIMER_FUSED_FWD, st);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int ffn_rot_mode() {
     static int v = -1;
     if (v < 0) { const char* e = getenv("EGX_FFN_ROT"); v = e ? atoi(e) : 4; }
@@ -1441,6 +1501,7 @@ int fused_forward(const FusedFwdParams& p, int compute, hipStream_t st) {
     if (p.mode != FUSED_MODE_FULL && p.mode != FUSED_MODE_ATTN) {        // tiled mode: bf16 and split only (the exact-fp32 mode stays on the generic kernels for S > 48)
         EGX_CHECK(compute == CM_BF16 || compute == CM_SPLIT, "tiled mode: compute must be bf16 or f32s");
         EGX_CHECK(p.n_heads == FH, "tiled mode: 4 heads of 32");
+        if (p.rtab) return compute == CM_BF16 ? launch_fwd_ragged<CM_BF16>(p, st) : launch_fwd_ragged<CM_SPLIT>(p, st);
         return compute == CM_BF16 ? launch_fwd<CM_BF16, true, 32>(p, st) : launch_fwd<CM_SPLIT, true, 32>(p, st);
     }
     if (p.n_heads == 2 * FH)        // 8 heads of 16 (the HOI PNR / OSCC and action-recognition translators)

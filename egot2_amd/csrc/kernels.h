@@ -97,6 +97,9 @@ int attention_bwd(const float* qkv, const float* out, const float* lse, const fl
 
 int pool_head_fwd(const float* tokens, int B, int S, int d, const float* ln_w, const float* ln_b, float eps,
                   const float* W, const float* b, int n_out, float* pooled, float* out, hipStream_t st);
+// ragged batch (egx_ragged_fwd): clip b = rows [tok0_b, tok0_b + S_b) of `tokens` (the device batch table, fused.h RAGGED_REC)
+int pool_head_ragged_fwd(const float* tokens, const int* rtab, int B, int d, const float* ln_w, const float* ln_b, float eps,
+                         const float* W, const float* b, int n_out, float* pooled, float* out, hipStream_t st);
 int pool_head_bwd(const float* d_out, const float* pooled, int B, int S, int d, const float* ln_w,
                   const float* ln_b, float eps, const float* W, int n_out, float* d_tokens, float* d_ln_w,
                   float* d_ln_b, float* d_W, float* d_b, hipStream_t st);

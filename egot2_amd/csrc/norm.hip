@@ -7,6 +7,7 @@
 // torch.nn.TransformerEncoderLayer post-LN residual blocks (norm1/norm2).
 #include "common.h"
 #include "kernels.h"
+#include "fused.h"       // (the ragged batch table: RAGGED_REC)
 
 namespace egx {
 
@@ -347,14 +348,13 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(256) void pool_head_fwd_kernel(const float* __restrict__ tokens, int S, int d,
-                                                             const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
-                                                             const float* __restrict__ W, const float* __restrict__ bias, int n_out,
-                                                             float* __restrict__ pooled, float* __restrict__ out) {
+// clip b = the S rows of tk (shared by the uniform kernel and the ragged-batch one)
+__device__ __forceinline__ void pool_head_fwd_clip(const float* __restrict__ tk, int b, int S, int d,
+                                                   const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                   const float* __restrict__ W, const float* __restrict__ bias, int n_out,
+                                                   float* __restrict__ pooled, float* __restrict__ out) {
     __shared__ float y[PH_MAXD];
     __shared__ float red[4];
-    const int b = blockIdx.x;
-    const float* tk = tokens + (size_t)b * S * d;
     float inv_s = 1.f / (float)S;
     float loc = 0.f;
     if (d <= 128 && d % 4 == 0) {
@@ -440,6 +440,24 @@ __global__ __launch_bounds__(256) void pool_head_fwd_kernel(const float* __restr
     } else {
         for (int c = threadIdx.x; c < d; c += 256) out[(size_t)b * d + c] = y[c];
     }
+}
+
+__global__ __launch_bounds__(256) void pool_head_fwd_kernel(const float* __restrict__ tokens, int S, int d,
+                                                             const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                             const float* __restrict__ W, const float* __restrict__ bias, int n_out,
+                                                             float* __restrict__ pooled, float* __restrict__ out) {
+    const int b = blockIdx.x;
+    pool_head_fwd_clip(tokens + (size_t)b * S * d, b, S, d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
+}
+
+// ragged batch (egx_ragged_fwd): clip b is rows [tok0_b, tok0_b + S_b) of the dense token array (the batch table, fused.h RAGGED_REC)
+__global__ __launch_bounds__(256) void pool_head_ragged_fwd_kernel(const float* __restrict__ tokens, const int* __restrict__ rtab, int d,
+                                                                   const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                                   const float* __restrict__ W, const float* __restrict__ bias, int n_out,
+                                                                   float* __restrict__ pooled, float* __restrict__ out) {
+    const int b = blockIdx.x;
+    const int* rec = rtab + (size_t)b * RAGGED_REC;
+    pool_head_fwd_clip(tokens + (size_t)rec[RG_TOK0] * d, b, rec[RG_S], d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
 }
 
 __global__ __launch_bounds__(256) void pool_head_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ pooled,
@@ -532,6 +550,16 @@ int pool_head_fwd(const float* tokens, int B, int S, int d, const float* ln_w, c
     EGX_CHECK(!W || (n_out >= 1 && n_out <= 64), "pool_head: n_out=%d out of range 1..64", n_out);
     if (B <= 0) return 0;
     hipLaunchKernelGGL(pool_head_fwd_kernel, dim3(B), dim3(256), 0, st, tokens, S, d, ln_w, ln_b, eps, W, b, n_out, pooled, out);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int pool_head_ragged_fwd(const float* tokens, const int* rtab, int B, int d, const float* ln_w, const float* ln_b, float eps,
+                         const float* W, const float* b, int n_out, float* pooled, float* out, hipStream_t st) {
+    EGX_CHECK(d <= PH_MAXD, "pool_head: d=%d exceeds %d", d, PH_MAXD);
+    EGX_CHECK(!W || (n_out >= 1 && n_out <= 64), "pool_head: n_out=%d out of range 1..64", n_out);
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(pool_head_ragged_fwd_kernel, dim3(B), dim3(256), 0, st, tokens, rtab, d, ln_w, ln_b, eps, W, b, n_out, pooled, out);
     EGX_LAUNCH_CHECK();
     return 0;
 }

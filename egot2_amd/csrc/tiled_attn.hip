@@ -141,18 +141,23 @@ __device__ __forceinline__ Frag<CM> plane_tr_frag(const unsigned short* planes, 
 }
 }  // namespace
 
-template <int CM>
+// RAGGED (egx_ragged_fwd): clip b has its own S_b <= p.S (the batch table, TiledAttnParams::rtab): Q | K | V from row 48 tile0_b of the tile
+// grid, output rows tok0_b + query, log-sum-exp rows at 4 tok0_b; the grid and the chunk rows CH are sized by the longest clip, so the
+// workgroups past a clip's last group of query tiles leave at once and a clip walks only its own (S_b + 31) / 32 key blocks.
+template <int CM, bool RAGGED = false>
 __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_fwd_planes_kernel(TiledAttnParams p, int CH) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
-    unsigned short* Kp = reinterpret_cast<unsigned short*>(lds);      // [NPL][CH][TP_LD]: K at halfword 0 of a row, V at TP_OP
-    unsigned short* Vp = Kp + TP_OP;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4, nw = blockDim.x >> 6;
     const int bh = blockIdx.x, b = bh >> 2, h = bh & 3;
-    const float* base = p.qkv + (size_t)b * p.tpc * 48 * (3 * FD) + h * FDH;     // Q of the head; K at + 128, V at + 256
+    const int* rrec = RAGGED ? p.rtab + (size_t)b * RAGGED_REC : nullptr;
+    const int S = RAGGED ? rrec[RG_S] : p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
+    unsigned short* Kp = reinterpret_cast<unsigned short*>(lds);      // [NPL][CH][TP_LD]: K at halfword 0 of a row, V at TP_OP
+    unsigned short* Vp = Kp + TP_OP;
+    const float* base = p.qkv + (RAGGED ? (size_t)rrec[RG_TILE0] : (size_t)b * p.tpc) * 48 * (3 * FD) + h * FDH;     // Q of the head; K at + 128, V at + 256
     const float vscale = p.drop_thresh ? p.drop_inv : 1.f;
     const uint64_t dkey = attn_key(p);
     const int nqt = (S + 15) >> 4, ngrp = (nqt + TA_G - 1) / TA_G;
+    if constexpr (RAGGED) { if ((int)blockIdx.y * nw >= ngrp) return; }     // (whole workgroup: before any barrier)
     const int g = blockIdx.y * nw + wave;
     const bool active = g < ngrp;
     int query[TA_G];
@@ -234,8 +239,10 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_fwd_planes_kernel(T
         lt += __shfl_xor(lt, 32, 64);
         const float inv = 1.f / lt;
         if (query[t] < S) {
-            if (q == 0) p.lse[(size_t)bh * S + query[t]] = m[t] + log2f(lt);     // log2 units (internal to these kernels)
-            float* o = p.attn_o + ((size_t)b * S + query[t]) * FD + h * FDH + 4 * q;
+            const size_t lrow = RAGGED ? (size_t)rrec[RG_TOK0] * FH + (size_t)h * S + query[t] : (size_t)bh * S + query[t];
+            const size_t orow = RAGGED ? (size_t)rrec[RG_TOK0] + query[t] : (size_t)b * S + query[t];
+            if (q == 0) p.lse[lrow] = m[t] + log2f(lt);     // log2 units (internal to these kernels)
+            float* o = p.attn_o + orow * FD + h * FDH + 4 * q;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) *reinterpret_cast<f32x4*>(o + ct * 16) = oc[t][ct] * inv;
         }
@@ -493,10 +500,30 @@ int dispatch_planes(const TiledAttnParams& p, bool bwd, hipStream_t st) {
 }
 }  // namespace
 
+// ragged batch: p.B clips, p.S = the longest, lengths and row bases in p.rtab
+template <int CM>
+int dispatch_ragged_fwd(const TiledAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.S >= 1 && p.S <= TILED_MAX_S && p.rtab, "tiled attention (ragged): longest S=%d (1 .. %d), batch table set", p.S, TILED_MAX_S);
+    static bool once = false;
+    if (!once) {
+        if (set_lds(&tiled_attn_fwd_planes_kernel<CM, true>, 158 * 1024)) return 1;
+        once = true;
+    }
+    const int SKP = (p.S + 31) & ~31, CH = planes_chunk_rows<CM>(SKP);
+    const int ngrp = ((p.S + 15) / 16 + TA_G - 1) / TA_G;
+    int nw = 8;
+    (void)range_split(p.B, ngrp, &nw);
+    const dim3 grid(p.B * FH, (ngrp + nw - 1) / nw), block(nw * 64);
+    hipLaunchKernelGGL((tiled_attn_fwd_planes_kernel<CM, true>), grid, block, (size_t)Npl<CM>::v * CH * TP_LD * 2, st, p, CH);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st) {
     EGX_CHECK(compute == CM_BF16 || compute == CM_SPLIT, "tiled attention: compute must be bf16 or f32s");
     timing_begin(TIMER_WIDE_ATTN_FWD, st);
-    int rc = compute == CM_BF16 ? dispatch_planes<CM_BF16>(p, false, st) : dispatch_planes<CM_SPLIT>(p, false, st);
+    int rc = p.rtab ? (compute == CM_BF16 ? dispatch_ragged_fwd<CM_BF16>(p, st) : dispatch_ragged_fwd<CM_SPLIT>(p, st))
+                    : (compute == CM_BF16 ? dispatch_planes<CM_BF16>(p, false, st) : dispatch_planes<CM_SPLIT>(p, false, st));
     timing_end(TIMER_WIDE_ATTN_FWD, st);
     return rc;
 }

@@ -101,6 +101,9 @@ reload_tuning_each_call = False
 _scratch_cache = {}
 _last_impl = [EGX_IMPL_AUTO]
 _last_slices = [1]
+# last_encoder_impl() of the ragged-batch forward (encoder_ragged): the ragged tiled kernels, or the per-length-group fallback
+IMPL_RAGGED, IMPL_GROUPED = 100, 101
+_IMPL_NAMES = {**{v: k for k, v in IMPL.items()}, IMPL_RAGGED: "ragged", IMPL_GROUPED: "grouped"}
 
 
 def last_encoder_slices() -> int:
@@ -110,8 +113,9 @@ def last_encoder_slices() -> int:
 
 
 def last_encoder_impl() -> str:
-    """Diagnostic: the implementation the most recent encoder forward ran ("fused" | "wide" | "generic" | ...)."""
-    return {v: k for k, v in IMPL.items()}.get(_last_impl[0], "auto")
+    """Diagnostic: the implementation the most recent encoder forward ran ("fused" | "wide" | "generic" | ...; "ragged" / "grouped" for
+    encoder_ragged)."""
+    return _IMPL_NAMES.get(_last_impl[0], "auto")
 
 # EGX_POISON=1 (testing aid): every workspace handed to the library is filled with 0xFF bytes (NaN in fp32 and bf16) first,
 # so that a kernel reading memory nobody wrote shows up as NaNs instead of passing on whatever the allocator left there
@@ -239,6 +243,30 @@ def flat_storage_view(t: torch.Tensor) -> torch.Tensor:
     return torch.empty(0, dtype=t.dtype, device=t.device).set_(st, 0, (st.nbytes() // t.element_size(),))
 
 
+def _attach_weight_cache(lib, spec: EncoderSpec, cfg: Config, segs, proj, layer_t, device):
+    """Persistent packed-weight cache (spec.wcache): valid when nothing that goes into the packed copies changed since the forward that
+    filled it. Sets cfg.weight_cache / weight_cache_valid; returns (cache, signature) — the caller stores the signature in cache.sig once
+    its call has succeeded — or (None, None) where the configuration packs no weights."""
+    wc = spec.wcache
+    if wc is None:
+        return None, None
+    nbytes = lib.egx_weight_cache_bytes(C.byref(cfg), segs)
+    if not nbytes:
+        return None, None
+    packed = proj[0::2] + [layer_t[12 * l + k] for l in range(spec.n_layers) for k in (0, 2, 4, 6)]
+    keep = (1.0 / (1.0 - spec.p_drop)) if (spec.training and 0.0 < spec.p_drop < 1.0) else 1.0
+    wc_sig = (spec.compute, keep, _weights_epoch[0], nbytes) + tuple((t.data_ptr(), t._version) for t in packed)
+    if wc.buf is None or wc.buf.numel() < nbytes or wc.buf.device != device:
+        wc.buf, wc.sig = torch.zeros(nbytes, dtype=torch.uint8, device=device), None
+    capturing = torch.cuda.is_current_stream_capturing()
+    valid = wc.sig == wc_sig and (wc.frozen or not capturing)
+    cfg.weight_cache, cfg.weight_cache_valid = wc.buf.data_ptr(), int(valid)
+    wc.hits += int(valid)
+    wc.packs += int(not valid)
+    wc.sig = None       # (set again once the call has succeeded)
+    return wc, wc_sig
+
+
 class EncoderFn(torch.autograd.Function):
     """tokens(B,S,d) = encoder(token_prep(feats)) — or, with spec.head_n_out > 0, logits(B,n_out) = head(tokens).
     Argument order: spec, task_embed|None, pos_table|None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per projecting
@@ -350,24 +378,7 @@ class EncoderFn(torch.autograd.Function):
             saved = _workspace("saved", device, sv.value)
         scratch = _workspace("scratch", device, sc.value)
         seed = C.c_uint64(spec.seed & (2**64 - 1))
-        # persistent packed-weight cache: valid when nothing that goes into the packed copies changed since the forward that filled it
-        wc, wc_sig = spec.wcache, None
-        if wc is not None:
-            nbytes = lib.egx_weight_cache_bytes(C.byref(cfg), segs)
-            if nbytes:
-                packed = proj[0::2] + [layer_t[12 * l + k] for l in range(spec.n_layers) for k in (0, 2, 4, 6)]
-                keep = (1.0 / (1.0 - spec.p_drop)) if (spec.training and 0.0 < spec.p_drop < 1.0) else 1.0
-                wc_sig = (spec.compute, keep, _weights_epoch[0], nbytes) + tuple((t.data_ptr(), t._version) for t in packed)
-                if wc.buf is None or wc.buf.numel() < nbytes or wc.buf.device != device:
-                    wc.buf, wc.sig = torch.zeros(nbytes, dtype=torch.uint8, device=device), None
-                capturing = torch.cuda.is_current_stream_capturing()
-                valid = wc.sig == wc_sig and (wc.frozen or not capturing)
-                cfg.weight_cache, cfg.weight_cache_valid = wc.buf.data_ptr(), int(valid)
-                wc.hits += int(valid)
-                wc.packs += int(not valid)
-                wc.sig = None       # (set again once the call has succeeded)
-            else:
-                wc = None
+        wc, wc_sig = _attach_weight_cache(lib, spec, cfg, segs, proj, layer_t, device)
         ce_keep = None
         if spec.ce:
             if ce_target.dtype != torch.int64 or tuple(ce_target.shape) != (B,) or ce_target.device != device:
@@ -658,6 +669,130 @@ def encoder(spec: EncoderSpec, feats: Sequence[torch.Tensor], task_embed, pos_ta
     if spec.ce:
         return EncoderFn.apply(spec, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params, ce[0], ce[1])
     return EncoderFn.apply(spec, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params)
+
+
+def ragged_lengths(lengths, B: int, T_pad: Sequence[int], order: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Frame counts of a ragged batch as the (B, K) int32 host tensor egx_ragged_fwd reads (K = len(T_pad) segments). `lengths` is a (B,)
+    tensor / sequence (every segment of clip b has lengths[b] frames) or (B, K) with one column per feature argument; `order` maps segment k
+    to its column (the argument order of the model method, where it differs from the token order). 1 <= T_{b,k} <= T_pad[k] (the padded
+    length of feature k) or ValueError."""
+    K = len(T_pad)
+    t = lengths.detach() if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"lengths must be integers, got {t.dtype}")
+    t = t.to("cpu", torch.int64)
+    if t.dim() == 1:
+        t = t[:, None].expand(t.shape[0], K)
+    if t.dim() != 2 or tuple(t.shape) != (B, K):
+        raise ValueError(f"lengths has shape {tuple(t.shape)}: expected ({B},) or ({B}, {K}), one column per feature")
+    if order is not None:
+        t = t[:, list(order)]
+    for k in range(K):
+        col = t[:, k]
+        if B and (int(col.min()) < 1 or int(col.max()) > T_pad[k]):
+            raise ValueError(f"lengths of segment {k} must lie in 1 .. {T_pad[k]} (the padded length of its feature), got "
+                             f"{int(col.min())} .. {int(col.max())}")
+    return t.to(torch.int32).contiguous()
+
+
+def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
+                   proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], head_params: Sequence[torch.Tensor] = ()):
+    """Inference forward (no autograd) over a batch of clips of their own lengths: clip b's result is that of the same model on clip b
+    alone, unpadded. feats[k] is padded (B, spec.segments[k].T, d_in); `lengths` the (B, K) int32 host tensor of ragged_lengths().
+    Returns logits (B, n_out) with head_params (spec.head_n_out > 0), else the first segment's rows of every clip packed in clip order,
+    (sum_b lengths[b, 0], d). Runs egx_ragged_fwd (last_encoder_impl() == "ragged") where the tiled kernels cover the configuration;
+    elsewhere the clips are grouped by their length tuple and each group runs the batched forward ("grouped")."""
+    if spec.training or spec.ce or spec.token_ce or spec.out_tokens:
+        raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens")
+    lib = _lib.load()
+    if reload_tuning_each_call:
+        lib.egx_tuning_reload()
+    nseg = len(spec.segments)
+    B = feats[0].shape[0]
+    device = feats[0].device
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
+        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
+    lengths = lengths.contiguous()
+    with torch.no_grad():
+        feats = [_dev_feat(t, f"feats[{i}]") for i, t in enumerate(feats)]
+        proj = [_dev_f32(t, "projection weight") for t in proj]
+        layer_t = [_dev_f32(t, "layer weight") for t in layer_params]
+        head_t = [_dev_f32(t, "head parameter") for t in head_params]
+        ln_w, ln_b = _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias")
+        task_embed = _dev_f32(task_embed, "task_embed") if task_embed is not None else None
+        pos_table = _dev_f32(pos_table, "positional table") if pos_table is not None else None
+        d = spec.d_model
+        segs = (Segment * nseg)()
+        pi = 0
+        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
+            if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
+                raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
+            segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
+            segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
+            if ss.has_proj:
+                segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
+                pi += 1
+            if ss.add_row is not None:
+                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
+            if ss.pos_row0 is not None:
+                segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
+        layers = (Layer * max(spec.n_layers, 1))()
+        for l in range(spec.n_layers):
+            for k, name in enumerate(_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
+        import dataclasses
+        cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
+        nbytes = C.c_size_t(0)
+        if lib.egx_ragged_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
+            # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged kernels do not cover
+            return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
+        ws = _workspace("saved", device, nbytes.value)
+        wc, wc_sig = _attach_weight_cache(lib, spec, cfg, segs, proj, layer_t, device)
+        if head_t:
+            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
+            out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
+            check(lib.egx_ragged_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(out), None,
+                                     ptr(ws), _stream()))
+        else:
+            out = torch.empty((int(lengths[:, 0].sum()), d), dtype=torch.float32, device=device)
+            check(lib.egx_ragged_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, None, B, None, ptr(out),
+                                     ptr(ws), _stream()))
+        if wc is not None:
+            wc.sig = wc_sig
+    _last_impl[0] = IMPL_RAGGED
+    _last_slices[0] = 1
+    return out
+
+
+def _encoder_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t):
+    """encoder_ragged where the ragged kernels do not run (exact fp32, a forced implementation, deeper stacks, clips beyond 512 tokens):
+    one batched forward per group of clips with the same length tuple, on those clips' unpadded frames; results scattered to clip order."""
+    import dataclasses
+    B, d = feats[0].shape[0], spec.d_model
+    device = feats[0].device
+    groups = {}
+    for b, row in enumerate(lengths.tolist()):
+        groups.setdefault(tuple(row), []).append(b)
+    if head_t:
+        out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
+    else:
+        first = lengths[:, 0].to(torch.int64)
+        row0 = torch.cumsum(first, 0) - first           # first output row of every clip
+        out = torch.empty((int(first.sum()), d), dtype=torch.float32, device=device)
+    for key, idx in groups.items():
+        it = torch.tensor(idx, dtype=torch.int64, device=device)
+        fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
+        gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)],
+                                    out_tokens=0 if head_t else key[0])
+        r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
+        if head_t:
+            out.index_copy_(0, it, r)
+        else:
+            dst = (row0[idx][:, None] + torch.arange(key[0])[None, :]).reshape(-1).to(device)
+            out.index_copy_(0, dst, r.reshape(-1, d))
+    _last_impl[0] = IMPL_GROUPED
+    _last_slices[0] = 1
+    return out
 
 
 def _token_ce_fused(spec: EncoderSpec, feats, proj) -> bool:

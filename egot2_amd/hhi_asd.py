@@ -6,6 +6,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import functional as F_egx
 from .backbones import freeze_params, make_backbone
 from .functional import SegmentSpec
 from .registry import make_registry
@@ -63,13 +64,23 @@ class TaskFusionMFTransformer3Task(TaskFusion3Task, TranslatorMixin):
         )
         self.output_dim = self.dim
 
-    def forward_features(self, ttm_out, lam_out, asd_out, lossav=None, labels=None):
+    def forward_features(self, ttm_out, lam_out, asd_out, lossav=None, labels=None, lengths=None):
         """(B, T, 256) features -> (B*T, d): tokens asd | ttm | lam, first T tokens returned.
         lossav (the task's lossAV module) + labels (B*T,): return lossAV.forward(tokens, labels) = (nloss, predScore, predLabel, correctNum)
-        instead (HHI/tasks/asd/video_task_taskspecific.py:24,33), evaluated by the encoder's own launches where the per-clip kernels can."""
+        instead (HHI/tasks/asd/video_task_taskspecific.py:24,33), evaluated by the encoder's own launches where the per-clip kernels can.
+        lengths (inference only): a batch of clips of their own lengths — features padded to (B, T_max, 256), lengths (B,) or (B, 3) frame
+        counts in argument order (ttm, lam, asd) -> (sum_b T_asd_b, d): the per-frame rows of every clip, packed in clip order, each clip's as
+        it alone would give them (functional.encoder_ragged). Score them with lossav.forward(rows, labels)."""
         feats = [asd_out, ttm_out, lam_out]
         segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0)
                 for f, k in zip(feats, (2, 0, 1))]
+        if lengths is not None:
+            if lossav is not None:
+                raise ValueError("ragged batches are inference-only: no fused loss (lossav=); call lossav.forward(rows, labels) on the returned rows")
+            lens = F_egx.ragged_lengths(lengths, asd_out.shape[0], [f.shape[1] for f in feats], order=(2, 0, 1))
+            return self._egx_encode(feats, segs, encoder=self.transformer_encoder, ln=self.ln,
+                                    projs=[self.proj_asd, self.proj_ttm, self.proj_lam], task_embed=self.task_embed,
+                                    pos_table=self.pos_embed.pe, p_drop=self.dp_rate, lengths=lens)
         tokens = self._egx_encode(feats, segs, encoder=self.transformer_encoder, ln=self.ln,
                                   projs=[self.proj_asd, self.proj_ttm, self.proj_lam], task_embed=self.task_embed,
                                   pos_table=self.pos_embed.pe, p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p,

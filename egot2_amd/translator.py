@@ -113,13 +113,19 @@ class TranslatorMixin:
     def _egx_encode(self, feats: Sequence[torch.Tensor], segments: List[SegmentSpec], *, encoder: nn.TransformerEncoder,
                     ln: nn.LayerNorm, projs: Sequence[Optional[nn.Linear]], task_embed: Optional[torch.Tensor],
                     pos_table: Optional[torch.Tensor], p_drop: float, p_pos: float = 0.0, p_feat: float = 0.0,
-                    head=None, out_tokens: int = 0, ce=None, token_ce=None) -> torch.Tensor:
+                    head=None, out_tokens: int = 0, ce=None, token_ce=None, lengths=None) -> torch.Tensor:
         """head = (nn.LayerNorm, nn.Linear): evaluate the pooled head with the encoder and return logits (B, n_out).
         out_tokens = T > 0: return only the first T tokens of every clip, (B, T, d) (in-kernel on the fused path).
         ce = (target, class_weight | None) with a head: also evaluate nn.CrossEntropyLoss(weight)(logits, target) inside the forward
         (egx_ce) and return (logits, loss).
         token_ce = (fc_weight, fc_bias | None, target, class_weight | None) with out_tokens: return (loss, logits, probs, pred, correct) of the
-        per-token classifier + weighted cross entropy on the returned tokens instead of the tokens (functional.encoder_token_ce)."""
+        per-token classifier + weighted cross entropy on the returned tokens instead of the tokens (functional.encoder_token_ce).
+        lengths: a ragged batch (inference only): (B,) or (B, K) frame counts in SEGMENT order (functional.ragged_lengths) of the padded
+        feats; returns logits (B, n_out) with a head, else the first segment's rows of every clip packed, (sum_b T_{b,0}, d)
+        (functional.encoder_ragged). out_tokens is then ignored: the first segment is what leaves the call."""
+        if lengths is not None:
+            return self._egx_encode_ragged(feats, segments, lengths, encoder=encoder, ln=ln, projs=projs, task_embed=task_embed,
+                                           pos_table=pos_table, head=head, ce=ce, token_ce=token_ce)
         layer0 = encoder.layers[0]
         d = ln.normalized_shape[0]
         seed_dev = getattr(self, "_egx_seed_dev", None)
@@ -152,3 +158,25 @@ class TranslatorMixin:
                                           encoder_layer_tensors(encoder), *token_ce)
         return F_egx.encoder(spec, list(feats), task_embed, pos_table, ln.weight, ln.bias, proj_t,
                              encoder_layer_tensors(encoder), head_t, ce=ce)
+
+    def _egx_encode_ragged(self, feats, segments, lengths, *, encoder, ln, projs, task_embed, pos_table, head, ce, token_ce):
+        if self.training:
+            raise ValueError("ragged batches are inference-only: call model.eval() before passing lengths=")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
+                             "(or with every parameter frozen)")
+        if ce is not None or token_ce is not None:
+            raise ValueError("ragged batches are inference-only: no fused loss (target= / lossav=); apply the loss to the returned outputs")
+        B = feats[0].shape[0]
+        lens = F_egx.ragged_lengths(lengths, B, [s.T for s in segments])
+        layer0 = encoder.layers[0]
+        spec = EncoderSpec(d_model=ln.normalized_shape[0], n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
+                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps, compute=self.egx_compute, impl=self.egx_impl,
+                           head_n_out=head[1].out_features if head is not None else 0, wcache=getattr(self, "_egx_wcache", None))
+        proj_t = []
+        for s, p in zip(segments, projs):
+            if s.has_proj:
+                proj_t += [p.weight, p.bias]
+        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        return F_egx.encoder_ragged(spec, list(feats), lens, task_embed, pos_table, ln.weight, ln.bias, proj_t,
+                                    encoder_layer_tensors(encoder), head_t)

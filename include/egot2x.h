@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define EGX_ABI_VERSION 16
+#define EGX_ABI_VERSION 17
 #define EGX_MAX_SEGMENTS 8
 
 enum { EGX_F32 = 0, EGX_BF16 = 1, EGX_F32_SPLIT = 2 };
@@ -301,6 +301,26 @@ int egx_translator_bwd(const egx_config* cfg, const egx_segment* segs, const flo
                        void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b,
                        const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, int training,
                        uint64_t seed, void* stream);
+
+/* ---- ABI v17: ragged batches (inference) ----
+ * One forward over B clips of their own lengths: clip b's result is the result of the same model on clip b alone, unpadded (the
+ * reference's batch_size=1 validation loops, HHI/tasks/ttm/video_task_2loader.py:84-97, HHI/tasks/asd/video_task_taskspecific.py:69,76).
+ *   lengths    HOST int[B * n_segments], clip-major: T_{b,k} = frames of segment k of clip b, 1 <= T_{b,k} <= segs[k].T. segs[k].feat stays
+ *              a padded (B, segs[k].T, d_in) tensor (segs[k].T is the row stride of a clip); rows t >= T_{b,k} are never read. Inside a
+ *              clip segment k starts at token sum_{j<k} T_{b,j}; positional rows restart at segs[k].pos for every segment.
+ *   head       non-NULL: logits_out (B, n_out) = Linear(LN(mean over the clip's own S_b = sum_k T_{b,k} tokens)).
+ *   head NULL  tokens_out holds the FIRST segment's rows of every clip, packed: sum_b T_{b,0} rows of d floats in clip order (the ASD
+ *              translator's per-frame output, HHI/models/asd/model_taskspecific.py:156-158).
+ * Runs on the tiled kernels: d = 128, h = 4, d_ff % 128 == 0, 1 .. 6 layers, <= 4 projected segments (d_in % 128 == 0), fp32 features,
+ * compute bf16 or f32s, impl auto or tiled, S_b <= 512 tokens per clip (clips of S_b <= 48 are single tiles). Refused: p_drop / p_pos /
+ * p_feat > 0 (inference only), out_tokens, ce, token_ce, bucket_cb. weight_cache / weight_cache_valid work as in egx_translator_fwd.
+ * `workspace`: egx_ragged_workspace() bytes (a function of sum_b S_b, the tile count and the model, not of B * max S_b). The call writes a
+ * per-clip table built from `lengths` into the workspace on `stream`: a captured hipGraph would replay THIS call's lengths for every batch,
+ * so the ragged call is not meant for graph capture. */
+int egx_ragged_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes);
+int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                   const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace,
+                   void* stream);
 
 /* pooled = mean_s tokens[b, s, :]; y = ln_w ? LN(pooled) : pooled; out = W ? y W^T + b : y.
  * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL. */
