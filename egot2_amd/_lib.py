@@ -11,7 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # EGX_LIB (development aid): load a variant build (egot2_amd/_variants/lib_<name>.so, tools/build_variant.py) instead
 LIB_PATH = os.environ.get("EGX_LIB") or os.path.join(_PKG, "libegot2x.so")
 
-EGX_ABI_VERSION = 17
+EGX_ABI_VERSION = 18
 EGX_MAX_SEGMENTS = 8
 EGX_F32, EGX_BF16, EGX_F32_SPLIT = 0, 1, 2
 EGX_IMPL_AUTO, EGX_IMPL_GENERIC, EGX_IMPL_FUSED, EGX_IMPL_WIDE, EGX_IMPL_TILED = 0, 1, 2, 3, 4
@@ -120,6 +120,8 @@ SIGNATURES = {
     "egx_ragged_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t)]),
     "egx_ragged_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.POINTER(Head), C.c_int,
                                  _fp, _fp, _fp, _fp]),
+    "egx_ragged_encode_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t)]),
+    "egx_ragged_encode": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.c_int, _fp, C.c_int, _fp, _fp]),
     "egx_translator_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.POINTER(Head),
                                      C.c_int, _fp, _fp, _fp, C.POINTER(SegmentGrads), _fp, _fp, C.POINTER(LayerGrads),
                                      C.POINTER(HeadGrads), C.c_int, C.c_uint64, _fp]),
@@ -133,6 +135,9 @@ SIGNATURES = {
     "egx_decoder_workspace": (C.c_int, [C.POINTER(DecConfig), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "egx_decoder_fwd": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int, _fp, _fp,
                                   _fp, C.c_int, C.c_uint64, _fp]),
+    "egx_decoder_ragged_workspace": (C.c_int, [C.POINTER(DecConfig), C.c_int, _fp, C.POINTER(C.c_size_t)]),
+    "egx_decoder_ragged_fwd": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int, _fp,
+                                         _fp, _fp]),
     "egx_decoder_bwd": (C.c_int, [C.POINTER(DecConfig), _fp, C.POINTER(DecLayer), _fp, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                   C.POINTER(DecLayerGrads), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_uint64, _fp]),
     "egx_comm_unique_id": (C.c_int, [_fp]),

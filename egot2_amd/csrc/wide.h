@@ -60,6 +60,8 @@ int wide_cast_flush(WideCastBatch& b, hipStream_t st);
 
 // dst[r][c] = bf16(mean_{j < pool} src[r * pool + j][c]); src fp32 or bf16 (R * pool, C), dst (R, C) bf16. C % 8 == 0.
 int wide_pool_cast(const void* src, int src_bf16, int R, int pool, int C, bf16_t* dst, hipStream_t st);
+// ragged batches: dst[r][c] = bf16(src[rows[r]][c]) for the R listed source rows (the valid frames of a padded feature, compacted). C % 8 == 0.
+int wide_gather_cast(const void* src, int src_bf16, const int* rows, int R, int C, bf16_t* dst, hipStream_t st);
 
 // Row kernels with bf16 side outputs --------------------------------------------------------------------------------
 // y[orow] = dropout(LN(x[row]) * w + b + add_vec + pos[t]); y32 and / or y16 written; stats (mean, rstd) saved.
@@ -69,8 +71,12 @@ struct WideLnFwdParams {
     int rows = 0, d = 0, T = 1, S = 1, off = 0;
     const float* add_vec = nullptr; const float* pos = nullptr; int pos_stride = 0;
     uint64_t drop_key = 0; uint32_t drop_thresh = 0; float drop_inv = 1.f;
+    // ragged batches (wide_ln_fwd_mapped): row `row` is written to y[out_map[row]] (instead of the T / S / off remap) with positional row
+    // src_map[row] % T (src_map: the padded source row of a compacted feature row; null: no positional row from it)
+    const int* out_map = nullptr; const int* src_map = nullptr;
 };
 int wide_ln_fwd(const WideLnFwdParams& p, hipStream_t st);
+int wide_ln_fwd_mapped(const WideLnFwdParams& p, hipStream_t st);
 
 // dx[row] = LN backward of (mask .* dy[orow]); dx32 = d(pre-LN sum) fp32; dx16 = out-mask .* dx as bf16 (the upstream
 // gradient of the GEMM that produced the branch; out-mask = the dropout applied to that branch in the forward, keyed by
@@ -118,10 +124,18 @@ struct WideAttnParams {
     int B = 0, S = 0, H = 0, d = 0;
     uint64_t drop_key = 0; uint32_t drop_thresh = 0; float drop_inv = 1.f;
     float* delta = nullptr;       // S > 128 backward: (B, H, S) scratch, delta = rowsum(dO . O); `out` must then hold the forward's output
+    // ragged batches (wide_attn_ragged_fwd): B clips of their own lengths. Clip clips[i] (i < B) has rtab[c * WIDE_RG_REC + WRG_S] tokens at
+    // rows [tok0, tok0 + S_c) of qkv / out (tok0 = rtab[c * WIDE_RG_REC + WRG_TOK0]); its log-sum-exp rows start at H tok0. S = the longest.
+    const int* rtab = nullptr; const int* clips = nullptr;
 };
+constexpr int WIDE_RG_MAXSEG = 8, WIDE_RG_REC = 2 + 2 * WIDE_RG_MAXSEG;      // (WIDE_RG_MAXSEG = EGX_MAX_SEGMENTS)
+enum { WRG_S = 0, WRG_TOK0 = 1, WRG_T = 2 /* .. frames of segment k */, WRG_OFF = 2 + WIDE_RG_MAXSEG /* .. first token of segment k */ };
 bool wide_attn_supported(int S, int dh);      // S <= 128: head dim 32 / 64 / 96 / 128; 128 < S <= ~480: head dim 32 / 64 (wide_attn_long_*)
 size_t wide_attn_delta_bytes(int B, int H, int S);
 int wide_attn_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_bwd(const WideAttnParams& p, hipStream_t st);
+// inference forward over the B clips of p.clips, all of one kernel class (wide_attn_ragged_class): p.S = their longest clip
+int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st);
+int wide_attn_ragged_class(int S, int dh);      // 0: S <= 64, 1: 64 < S <= 128, 2: the long kernel, -1: unsupported
 
 }  // namespace egx

@@ -153,6 +153,93 @@ __global__ __launch_bounds__(256) void wide_attn_fwd_kernel(WideAttnParams p) {
     }
 }
 
+// Ragged batches (wide_attn_ragged_fwd, inference): the same kernel for workgroup (i, h) = clip p.clips[i] of the batch table, with its own
+// length S and its rows from tok0 on (log-sum-exp rows from H tok0 + h S). A separate copy rather than a template flag on the kernel above:
+// routing both through one inlined body changed the uniform kernels' register allocation (and two of them lost a wave of occupancy).
+template <int DH, int NKT>
+__global__ __launch_bounds__(256) void wide_attn_ragged_fwd_kernel(WideAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int RS = DH * 2 + 32, SP = NKT * 16, NKB = DH / 32, NCT = DH / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* Kimg = smem;
+    unsigned char* Vimg = smem + SP * RS;
+    const int bh = blockIdx.x, h = bh % p.H;
+    const int* rec = p.rtab + (size_t)p.clips[bh / p.H] * WIDE_RG_REC;
+    const int S = rec[WRG_S], tok0 = rec[WRG_TOK0], d = p.d, ld = 3 * d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
+    {
+        ImageRegs<DH, SP> rk, rv;
+        image_fetch<DH, SP>(rk, base + d, ld, S);
+        image_fetch<DH, SP>(rv, base + 2 * d, ld, S);
+        image_store<DH, SP>(rk, Kimg);
+        image_store<DH, SP>(rv, Vimg);
+    }
+    __syncthreads();
+    const float scale = rsqrtf((float)DH);
+    const int nqt = (S + 15) / 16;
+    for (int qt = wave; qt < nqt; qt += 4) {
+        const int query = qt * 16 + r;
+        const int qrow = query < S ? query : S - 1;
+        bf16x8 qf[NKB];
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) qf[kb] = *reinterpret_cast<const bf16x8*>(base + (size_t)qrow * ld + kb * 32 + 8 * g);
+        f32x4 sc[NKT];
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            f32x4 a = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) a = mfma(rd128(Kimg + (kt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), qf[kb], a);
+            sc[kt] = a;
+        }
+        float m = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                int key = kt * 16 + 4 * g + e;
+                float s = key < S ? sc[kt][e] * scale : -INFINITY;
+                sc[kt][e] = s;
+                m = fmaxf(m, s);
+            }
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { float pv = __expf(sc[kt][e] - m); sc[kt][e] = pv; sum += pv; }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.f / sum;
+        if (g == 0 && query < S) p.lse[(size_t)tok0 * p.H + (size_t)h * S + query] = m + __logf(sum);
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pv = sc[kt][e] * inv;
+                if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)(bh * 128 + query), (uint32_t)(kt * 16 + 4 * g + e), p.drop_thresh, p.drop_inv);
+                sc[kt][e] = pv;
+            }
+        f32x4 oc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) oc[ct] = f32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int kb2 = 0; kb2 < NKT / 2; ++kb2) {
+            const bf16x8 pf = chain(sc[2 * kb2], sc[2 * kb2 + 1]);
+            const unsigned char* v0 = Vimg + (kb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) oc[ct] = mfma(rd_tr2(v0 + ct * 32, v0 + 16 * RS + ct * 32), pf, oc[ct]);
+        }
+        if (query < S) {
+            bf16_t* o = p.out + ((size_t)tok0 + query) * d + h * DH + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+                *reinterpret_cast<uint2*>(o + ct * 16) = make_uint2(pk(oc[ct][0], oc[ct][1]), pk(oc[ct][2], oc[ct][3]));
+        }
+    }
+}
+
 // ---- backward ---------------------------------------------------------------------------------------------------
 // NKT = 8 (S <= 128): 512 threads, one query tile (pass T) and one key tile (pass N) per wave, two waves per SIMD.
 template <int DH, int NKT>
@@ -414,6 +501,90 @@ __global__ __launch_bounds__(WAL_NTH) void wide_attn_long_fwd_kernel(WideAttnPar
     }
 }
 
+// ragged batches: the long forward for clip p.clips[i] of the batch table (a separate copy, as wide_attn_ragged_fwd_kernel)
+template <int DH>
+__global__ __launch_bounds__(WAL_NTH) void wide_attn_long_ragged_fwd_kernel(WideAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int RS = DH * 2 + 32, NKB = DH / 32, NCT = DH / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int bh = blockIdx.x, h = bh % p.H;
+    const int* rec = p.rtab + (size_t)p.clips[bh / p.H] * WIDE_RG_REC;
+    const int S = rec[WRG_S], tok0 = rec[WRG_TOK0];
+    // the grid's query split is sized by the class's longest clip: a workgroup past this clip's last query tile has nothing to do
+    if ((int)blockIdx.y * WAL_NW * 16 >= S) return;
+    const int SP = (S + 31) & ~31, d = p.d, ld = 3 * d;      // (key blocks padded to this clip's length)
+    unsigned char* Kimg = smem;
+    unsigned char* Vimg = smem + SP * RS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
+    image_stage<DH>(Kimg, base + d, ld, S, SP);
+    image_stage<DH>(Vimg, base + 2 * d, ld, S, SP);
+    __syncthreads();
+    const float c2 = rsqrtf((float)DH) * 1.4426950408889634f;       // scores in log2 units
+    const float vinv = p.drop_thresh ? p.drop_inv : 1.f;
+    const int nqt = (S + 15) / 16, nkb2 = SP / 32;
+    for (int qt = blockIdx.y * WAL_NW + wave; qt < nqt; qt += WAL_NW * gridDim.y) {
+        const int query = qt * 16 + r;
+        const int qrow = query < S ? query : S - 1;
+        bf16x8 qf[NKB];
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) qf[kb] = *reinterpret_cast<const bf16x8*>(base + (size_t)qrow * ld + kb * 32 + 8 * g);
+        float m = -INFINITY, l = 0.f;
+        f32x4 oc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) oc[ct] = f32x4{0, 0, 0, 0};
+        for (int kb2 = 0; kb2 < nkb2; ++kb2) {
+            f32x4 sc[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f32x4 a = f32x4{0, 0, 0, 0};
+#pragma unroll
+                for (int kb = 0; kb < NKB; ++kb) a = mfma(rd128(Kimg + (kb2 * 32 + j * 16 + r) * RS + (kb * 32 + 8 * g) * 2), qf[kb], a);
+                sc[j] = a * c2;
+            }
+            if (kb2 == nkb2 - 1) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (kb2 * 32 + j * 16 + 4 * g + e >= S) sc[j][e] = -INFINITY;
+            }
+            float mb = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])), fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
+            mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+            mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+            const float mn = fmaxf(m, mb);
+            const float corr = __builtin_amdgcn_exp2f(m - mn);
+            m = mn;
+            l *= corr;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) oc[ct] *= corr;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pv = __builtin_amdgcn_exp2f(sc[j][e] - mn);
+                    l += pv;
+                    if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)(bh * 512 + query), (uint32_t)(kb2 * 32 + j * 16 + 4 * g + e), p.drop_thresh, vinv);
+                    sc[j][e] = pv;
+                }
+            const bf16x8 pf = chain(sc[0], sc[1]);
+            const unsigned char* v0 = Vimg + (kb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) oc[ct] = mfma(rd_tr2(v0 + ct * 32, v0 + 16 * RS + ct * 32), pf, oc[ct]);
+        }
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.f / l;
+        if (query < S) {
+            if (g == 0) p.lse[(size_t)tok0 * p.H + (size_t)h * S + query] = (m + log2f(l)) * 0.6931471805599453f;
+            bf16_t* o = p.out + ((size_t)tok0 + query) * d + h * DH + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+                *reinterpret_cast<uint2*>(o + ct * 16) = make_uint2(pk(oc[ct][0] * inv, oc[ct][1] * inv), pk(oc[ct][2] * inv, oc[ct][3] * inv));
+        }
+    }
+}
+
 // query side of the long backward: dQ, delta
 template <int DH>
 __global__ __launch_bounds__(WAL_NTH) void wide_attn_long_dq_kernel(WideAttnParams p) {
@@ -644,6 +815,64 @@ static int dispatch_attn(const WideAttnParams& p, bool bwd, hipStream_t st) {
         EGX_ATTN_CASE(128)
     }
 #undef EGX_ATTN_CASE
+    return 1;
+}
+
+// ---- ragged batches (inference) ----
+int wide_attn_ragged_class(int S, int dh) {
+    if (S >= 1 && S <= 64 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) return 0;
+    if (S >= 1 && S <= 128 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) return 1;
+    return wide_attn_long_supported(S, dh) ? 2 : -1;
+}
+
+template <int DH, int NKT>
+static int launch_attn_ragged(const WideAttnParams& p, hipStream_t st) {
+    constexpr int RS = DH * 2 + 32, SP = NKT * 16;
+    const size_t lds = (size_t)2 * SP * RS;
+    static bool attr = false;
+    if (!attr) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_attn_ragged_fwd_kernel<DH, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = true;
+    }
+    hipLaunchKernelGGL((wide_attn_ragged_fwd_kernel<DH, NKT>), dim3(p.B * p.H), dim3(256), lds, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int DH>
+static int launch_attn_long_ragged(const WideAttnParams& p, hipStream_t st) {
+    constexpr int RS = DH * 2 + 32;
+    const size_t lds = 2 * (size_t)((p.S + 31) & ~31) * RS;
+    static bool attr = false;
+    if (!attr) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_attn_long_ragged_fwd_kernel<DH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr = true;
+    }
+    const int ntile = (p.S + 15) / 16;
+    int split = 256 / (p.B * p.H);
+    const int maxs = (ntile + WAL_NW - 1) / WAL_NW;
+    split = split < 1 ? 1 : (split > maxs ? maxs : split);
+    hipLaunchKernelGGL((wide_attn_long_ragged_fwd_kernel<DH>), dim3(p.B * p.H, split), dim3(WAL_NTH), lds, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_fwd: bad arguments");
+    EGX_CHECK(!p.drop_thresh, "wide_attn_ragged_fwd: inference only (no dropout)");
+    if (p.B <= 0) return 0;
+    const int dh = p.d / p.H, cls = wide_attn_ragged_class(p.S, dh);
+    EGX_CHECK(cls >= 0, "wide attention: S=%d head dim %d unsupported", p.S, dh);
+    if (cls == 2) return dh == 32 ? launch_attn_long_ragged<32>(p, st) : launch_attn_long_ragged<64>(p, st);
+#define EGX_ATTN_RG_CASE(D)                                                                   \
+    case D: return cls == 0 ? launch_attn_ragged<D, 4>(p, st) : launch_attn_ragged<D, 8>(p, st);
+    switch (dh) {
+        EGX_ATTN_RG_CASE(32)
+        EGX_ATTN_RG_CASE(64)
+        EGX_ATTN_RG_CASE(96)
+        EGX_ATTN_RG_CASE(128)
+    }
+#undef EGX_ATTN_RG_CASE
     return 1;
 }
 

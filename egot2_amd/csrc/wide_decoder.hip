@@ -13,11 +13,13 @@
 // stays on the composed path (egot2_amd/decoder.py).
 #include <string.h>
 #include <mutex>
+#include <vector>
 
 #include "../../include/egot2x.h"
 #include "common.h"
 #include "kernels.h"
 #include "wide.h"
+#include "fused.h"      // (upload_words: the ragged batch table)
 
 namespace egx {
 
@@ -46,6 +48,9 @@ struct DecAttnParams {
     int B, H, Sq, Sk, causal;
     float scale;
     uint64_t drop_key; uint32_t drop_thresh; float drop_inv;
+    // ragged memories (dec_attn_ragged, inference): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
+    // of k / v, its query / output rows c * Sq + i. Sk = the longest memory of the launch.
+    const int* mtab; const int* clips;
 };
 
 // One wave per (clip, head), four per workgroup. Lane j holds key row j (and, in the backward, value row j) in registers,
@@ -389,6 +394,168 @@ int dec_attn(DecAttnParams p, int dh, bool f32, hipStream_t st) {
     return 0;
 }
 
+// ---- ragged memories (egx_decoder_ragged_fwd, inference: no dropout) ----
+// Forward of dec_attn_kernel (bf16 operands) for clip p.clips[bh / H] with its own memory rows: separate copies, so that the uniform
+// kernels' code and register allocation stay as they are.
+template <int DH>
+__global__ __launch_bounds__(256) void dec_attn_ragged_kernel(DecAttnParams p) {
+    __shared__ float sQ[4][DA_MAXQ][DH];        // query rows (fp32)
+    __shared__ float sP[4][DA_MAXQ][64];        // probabilities
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bh = blockIdx.x * 4 + wave;
+    if (bh >= p.B * p.H) return;                // (no barrier below: every wave works alone)
+    const int b = p.clips[bh / p.H], h = bh % p.H;
+    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1];
+    const size_t m0 = (size_t)p.mtab[2 * b];
+    const bool kv_lane = lane < Sk;
+    float kr[DH];
+    {
+        const size_t krow = (m0 + (kv_lane ? lane : 0)) * p.ldk + h * DH;
+#pragma unroll
+        for (int c = 0; c < DH; c += 8) {
+            float t8[8];
+            load8<false>(p.k, krow + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
+        }
+    }
+    for (int i = lane; i < Sq * DH; i += 64) {
+        const int r = i / DH, c = i - r * DH;
+        sQ[wave][r][c] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < DA_MAXQ; ++i) {
+        if (i >= Sq) break;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < DH; c += 4) {
+            const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
+            s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
+        }
+        s = kv_lane ? s * p.scale : -INFINITY;
+        const float m = wmax64(s);
+        const float e = kv_lane ? __expf(s - m) : 0.f;
+        sP[wave][i][lane] = e / wsum64d(e);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < DH) {
+        float acc[DA_MAXQ];
+#pragma unroll
+        for (int i = 0; i < DA_MAXQ; ++i) acc[i] = 0.f;
+        const size_t v0 = m0 * p.ldv + h * DH + lane;
+        for (int j = 0; j < Sk; ++j) {
+            const float vv = load1<false>(p.v, v0 + (size_t)j * p.ldv);
+#pragma unroll
+            for (int i = 0; i < DA_MAXQ; ++i)
+                if (i < Sq) acc[i] += sP[wave][i][j] * vv;
+        }
+#pragma unroll
+        for (int i = 0; i < DA_MAXQ; ++i)
+            if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + lane] = f2bf(acc[i]);
+    }
+}
+
+// forward of dec_attn_long_kernel for clip p.clips[blockIdx.x / H] (LDS sized by the launch's longest memory, chunks by the clip's own)
+template <int DH>
+__global__ __launch_bounds__(256) void dec_attn_long_ragged_kernel(DecAttnParams p) {
+    constexpr int LDK = DH + 1;
+    extern __shared__ float dal_sm[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = p.clips[blockIdx.x / p.H], h = blockIdx.x % p.H;
+    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1], SKP = (Sk + 63) & ~63;
+    const size_t m0 = (size_t)p.mtab[2 * b];
+    float* Cs = dal_sm;                     // K or V chunk [64][DH + 1]
+    float* Qs = Cs + 64 * LDK;
+    float* Ps = Qs + DA_MAXQ * DH;          // [Sq][SKP]
+    const bf16_t* kb = reinterpret_cast<const bf16_t*>(p.k) + m0 * p.ldk + h * DH;
+    const bf16_t* vb = reinterpret_cast<const bf16_t*>(p.v) + m0 * p.ldv + h * DH;
+    auto stage = [&](const bf16_t* src, int ld, int j0) {
+        __syncthreads();
+        for (int i = tid; i < 64 * (DH / 8); i += 256) {
+            const int j = i / (DH / 8), c = (i - j * (DH / 8)) * 8;
+            float t8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (j0 + j < Sk) load8<false>(src, (size_t)(j0 + j) * ld + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) Cs[j * LDK + c + e] = t8[e];
+        }
+        __syncthreads();
+    };
+    for (int i = tid; i < Sq * DH; i += 256) {
+        const int r = i / DH, c = i - r * DH;
+        Qs[i] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
+    }
+    for (int j0 = 0; j0 < Sk; j0 += 64) {
+        stage(kb, p.ldk, j0);
+        for (int i = wave; i < Sq; i += 4) {
+            float sc = 0.f;
+#pragma unroll
+            for (int c = 0; c < DH; ++c) sc += Qs[i * DH + c] * Cs[lane * LDK + c];
+            Ps[i * SKP + j0 + lane] = j0 + lane < Sk ? sc * p.scale : -INFINITY;
+        }
+    }
+    __syncthreads();
+    for (int i = wave; i < Sq; i += 4) {
+        float m = -INFINITY;
+        for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
+        m = wmax64(m);
+        float sum = 0.f;
+        for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
+        sum = 1.f / wsum64d(sum);
+        for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;
+    }
+    constexpr int NE = DA_MAXQ * DH / 256;
+    float acc[NE];
+#pragma unroll
+    for (int u = 0; u < NE; ++u) acc[u] = 0.f;
+    for (int j0 = 0; j0 < Sk; j0 += 64) {
+        stage(vb, p.ldv, j0);
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+            if (i < Sq) {
+                float a = 0.f;
+                for (int j = 0; j < 64; ++j) a += Ps[i * SKP + j0 + j] * Cs[j * LDK + c];
+                acc[u] += a;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+        const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+        if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + c] = f2bf(acc[u]);
+    }
+}
+
+// one launch per kernel class: p.clips / p.B the clips of the class, p.Sk their longest memory
+int dec_attn_ragged(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
+    EGX_CHECK(dh == 32 || dh == 64, "decoder attention: head dim %d (32 or 64)", dh);
+    EGX_CHECK(!p.drop_thresh && !p.causal && p.Sk >= 1 && p.Sk <= DAL_MAXK, "decoder attention (ragged): bad arguments");
+    if (p.B <= 0) return 0;
+    p.scale = 1.f / sqrtf((float)dh);
+    if (!long_class) {
+        EGX_CHECK(p.Sk <= DA_MAXK, "decoder attention (ragged): short class with Sk = %d", p.Sk);
+        const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
+        if (dh == 64) hipLaunchKernelGGL(dec_attn_ragged_kernel<64>, grid, block, 0, st, p);
+        else hipLaunchKernelGGL(dec_attn_ragged_kernel<32>, grid, block, 0, st, p);
+        EGX_LAUNCH_CHECK();
+        return 0;
+    }
+    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)DA_MAXQ * dh + (size_t)DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
+    static bool attr[2] = {false, false};
+    const void* fn = dh == 64 ? reinterpret_cast<const void*>(&dec_attn_long_ragged_kernel<64>) : reinterpret_cast<const void*>(&dec_attn_long_ragged_kernel<32>);
+    if (!attr[dh == 64]) {
+        EGX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
+        attr[dh == 64] = true;
+    }
+    if (dh == 64) hipLaunchKernelGGL(dec_attn_long_ragged_kernel<64>, dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    else hipLaunchKernelGGL(dec_attn_long_ragged_kernel<32>, dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 // x32 / x16 [row] = dropout(emb[tok[row]] * scale + pe[row % sy])
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restrict__ tok, const float* __restrict__ emb, const float* __restrict__ pe,
                                                         int pe_stride, float scale, float* __restrict__ x32, bf16_t* __restrict__ x16, int rows,
@@ -490,7 +657,8 @@ size_t dmax(size_t a, size_t b) { return a > b ? a : b; }
 template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>((char*)base + off); }
 template <class T> const T* cat(const void* base, size_t off) { return reinterpret_cast<const T*>((const char*)base + off); }
 
-int make_dplan(const egx_dec_config* c, int B, DPlan& pl) {
+// mem_rows > 0 (ragged memories): the memory is that many packed rows instead of B * S
+int make_dplan(const egx_dec_config* c, int B, DPlan& pl, size_t mem_rows = 0) {
     EGX_CHECK(c, "null decoder config");
     EGX_CHECK(c->compute == EGX_BF16, "the fused decoder runs compute = bf16 (the composed path serves the other modes)");
     EGX_CHECK(c->d_model >= 256 && c->d_model <= 1024 && c->d_model % 128 == 0, "fused decoder: d_model = %d (multiples of 128 in [256, 1024])", c->d_model);
@@ -502,7 +670,7 @@ int make_dplan(const egx_dec_config* c, int B, DPlan& pl) {
     EGX_CHECK(c->vocab >= 1 && B >= 1, "fused decoder: vocab = %d, B = %d", c->vocab, B);
     memset(&pl, 0, sizeof(pl));
     pl.B = B; pl.sy = c->sy; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
-    pl.Md = (size_t)B * c->sy; pl.Nm = (size_t)B * c->S;
+    pl.Md = (size_t)B * c->sy; pl.Nm = mem_rows ? mem_rows : (size_t)B * c->S;
     const size_t d = pl.d, dff = pl.dff, Md = pl.Md, Nm = pl.Nm;
     size_t cur = 0;
     pl.zero = dtake(cur, 1024);
@@ -664,13 +832,18 @@ int egx_decoder_workspace(const egx_dec_config* cfg, int B, size_t* saved_bytes,
     return 0;
 }
 
-int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const float* emb, const float* pe, int pe_stride,
-                    const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, float* logits, void* saved, void* scratch,
-                    int training, uint64_t seed, void* stream) {
-    DPlan pl;
-    if (make_dplan(cfg, B, pl)) return 1;
-    EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && saved && scratch, "egx_decoder_fwd: null pointer argument");
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+// ragged memories (egx_decoder_ragged_fwd): the device copy of the per-clip table and the clips of the two cross-attention kernel classes
+struct DecRagged {
+    const int* mtab;                // [B][2]: first memory row, memory rows
+    const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_ragged_kernel), class 1: the chunked kernel
+};
+
+int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const float* memory, const float* emb, const float* pe,
+                    int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, float* logits, void* saved,
+                    int training, uint64_t seed, hipStream_t st, const DecRagged* rg) {
     if (refuse_captured_dropout(cfg, training, st)) return 1;
     const int d = pl.d, dff = pl.dff, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
     // device-resident seed (the encoder's forward of this step has advanced it): this call's keys, derived on the stream
@@ -774,7 +947,13 @@ int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const floa
             a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.S; a.causal = 0;
             DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CROSS);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (dec_attn<false>(a, dh, false, st)) return 1;
+            if (rg) {
+                a.mtab = rg->mtab;
+                for (int c = 0; c < 2; ++c) {
+                    a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
+                    if (dec_attn_ragged(a, dh, c == 1, st)) return 1;
+                }
+            } else if (dec_attn<false>(a, dh, false, st)) return 1;
         }
         if (nt(cat<bf16_t>(saved, o.ca), d, cat<bf16_t>(saved, o.w_ca_o), Md, d, d, w.ca_out_b, at<float>(saved, o.res2), nullptr, 0,
                ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CA_OUT), cat<float>(saved, o.x1_32))) return 1;
@@ -793,6 +972,74 @@ int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const floa
     }
     sj.forked = false;      // joined already: every layer's cross-attention waited for its kv_ev, the last side-stream operation
     return 0;
+}
+
+// the ragged call's plan: DPlan over sum_b S_b memory rows, then the batch table (host copy in `tab`)
+int decoder_ragged_plan(const egx_dec_config* cfg, int B, const int* mem_lengths, DPlan& pl, std::vector<int>& tab, int (&n)[2], int (&smax)[2],
+                        size_t& off_tab, size_t& bytes) {
+    EGX_CHECK(cfg && mem_lengths, "egx_decoder_ragged: null argument");
+    EGX_CHECK(B >= 1 && B <= (1 << 20), "egx_decoder_ragged: B=%d clips (1 .. %d)", B, 1 << 20);
+    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f, "egx_decoder_ragged: inference only: p_drop and p_pos must be 0 (got %g, %g)", cfg->p_drop, cfg->p_pos);
+    size_t rows = 0;
+    n[0] = n[1] = 0; smax[0] = smax[1] = 0;
+    tab.assign((size_t)3 * B, 0);       // [B][2] table, then the clips of class 0 and of class 1
+    for (int b = 0; b < B; ++b) {
+        const int S = mem_lengths[b];
+        EGX_CHECK(S >= 1 && S <= cfg->S, "egx_decoder_ragged: clip %d has a memory of %d rows (1 .. %d = egx_dec_config.S)", b, S, cfg->S);
+        tab[2 * b] = (int)rows; tab[2 * b + 1] = S;
+        rows += S;
+        const int c = S > DA_MAXK;
+        n[c]++; smax[c] = S > smax[c] ? S : smax[c];
+    }
+    EGX_CHECK(rows <= (size_t)1 << 30, "egx_decoder_ragged: %zu memory rows", rows);
+    int i0 = 0, i1 = n[0];
+    for (int b = 0; b < B; ++b) tab[(size_t)2 * B + (tab[2 * b + 1] > DA_MAXK ? i1++ : i0++)] = b;
+    if (make_dplan(cfg, B, pl, rows)) return 1;
+    off_tab = align_up(pl.saved_bytes, 256);
+    bytes = off_tab + align_up(tab.size() * sizeof(int), 256);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const float* emb, const float* pe, int pe_stride,
+                    const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, float* logits, void* saved, void* scratch,
+                    int training, uint64_t seed, void* stream) {
+    DPlan pl;
+    if (make_dplan(cfg, B, pl)) return 1;
+    EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && saved && scratch, "egx_decoder_fwd: null pointer argument");
+    return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, saved, training, seed, (hipStream_t)stream, nullptr);
+}
+
+int egx_decoder_ragged_workspace(const egx_dec_config* cfg, int B, const int* mem_lengths, size_t* bytes) {
+    DPlan pl;
+    std::vector<int> tab;
+    int n[2], smax[2];
+    size_t off_tab = 0, nb = 0;
+    if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb)) return 1;
+    if (bytes) *bytes = nb;
+    return 0;
+}
+
+int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const int* mem_lengths, const float* emb,
+                           const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, float* logits,
+                           void* workspace, void* stream) {
+    DPlan pl;
+    std::vector<int> tab;
+    int n[2], smax[2];
+    size_t off_tab = 0, nb = 0;
+    if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb)) return 1;
+    EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && workspace, "egx_decoder_ragged_fwd: null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    // the table goes to the device in the arguments of upload launches (stream-ordered; a captured graph would replay THESE lengths)
+    int* dtab = reinterpret_cast<int*>((char*)workspace + off_tab);
+    if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
+    DecRagged rg;
+    rg.mtab = dtab;
+    rg.clips[0] = dtab + 2 * (size_t)B; rg.clips[1] = rg.clips[0] + n[0];
+    for (int c = 0; c < 2; ++c) { rg.n[c] = n[c]; rg.Sk_max[c] = smax[c] ? smax[c] : 1; }
+    return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, workspace, 0, 0, st, &rg);
 }
 
 int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B, const float* d_logits,

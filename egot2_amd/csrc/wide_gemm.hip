@@ -1215,6 +1215,37 @@ __global__ __launch_bounds__(256) void wide_pool_cast_kernel(const void* __restr
         make_uint4(pack2(acc[0] * s, acc[1] * s), pack2(acc[2] * s, acc[3] * s), pack2(acc[4] * s, acc[5] * s), pack2(acc[6] * s, acc[7] * s));
 }
 
+// ragged batches: the listed rows of a padded feature tensor, compacted and cast (rows t >= T_b of a clip are never read)
+template <bool SRC_BF16>
+__global__ __launch_bounds__(256) void wide_gather_cast_kernel(const void* __restrict__ src, const int* __restrict__ rows, int R, int C,
+                                                               bf16_t* __restrict__ dst) {
+    const int c8 = C / 8;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)R * c8) return;
+    const int r = (int)(i / c8), c = (int)(i % c8) * 8;
+    const size_t row = (size_t)rows[r];
+    uint4 o;
+    if constexpr (SRC_BF16) {
+        o = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(src) + row * C + c);
+    } else {
+        const float* p = reinterpret_cast<const float*>(src) + row * C + c;
+        float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+        o = make_uint4(pack2(a.x, a.y), pack2(a.z, a.w), pack2(b.x, b.y), pack2(b.z, b.w));
+    }
+    *reinterpret_cast<uint4*>(dst + (size_t)r * C + c) = o;
+}
+
+int wide_gather_cast(const void* src, int src_bf16, const int* rows, int R, int C, bf16_t* dst, hipStream_t st) {
+    EGX_CHECK(src && rows && dst && C % 8 == 0, "wide_gather_cast: bad arguments");
+    if (R <= 0) return 0;
+    const size_t n = (size_t)R * (C / 8);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (src_bf16) hipLaunchKernelGGL(wide_gather_cast_kernel<true>, dim3(blocks), dim3(256), 0, st, src, rows, R, C, dst);
+    else hipLaunchKernelGGL(wide_gather_cast_kernel<false>, dim3(blocks), dim3(256), 0, st, src, rows, R, C, dst);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int wide_pool_cast(const void* src, int src_bf16, int R, int pool, int C, bf16_t* dst, hipStream_t st) {
     EGX_CHECK(src && dst && C % 8 == 0 && pool >= 1, "wide_pool_cast: bad arguments");
     if (R <= 0) return 0;

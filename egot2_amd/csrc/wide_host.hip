@@ -2,12 +2,14 @@
 // as large bf16 MFMA GEMMs with fused epilogues, MFMA attention per (clip, head), row kernels with bf16 side outputs.
 // Same call sites as the generic path (include/egot2x.h: egx_encoder_fwd / egx_encoder_bwd); only enqueues kernels.
 #include <string.h>
+#include <vector>
 
 #include "../../include/egot2x.h"
 #include "common.h"
 #include "kernels.h"
 #include "wide.h"
 #include "wide_host.h"
+#include "fused.h"      // (upload_words: the ragged batch table)
 
 namespace egx {
 
@@ -456,4 +458,236 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
     return wide_reduce_flush(rb, st);
 }
 
+// ---- ragged batches (egx_ragged_encode, inference) -------------------------------------------------------------------------------------
+// Clip b has T_{b,k} frames per segment and S_b = sum_k T_{b,k} tokens; its tokens are rows [tok0_b, tok0_b + S_b) of every (N, .) array,
+// N = sum_b S_b, segment k from row tok0_b + off_{b,k}. Token preparation gathers the valid frames of segment k into R_k = sum_b T_{b,k}
+// compacted rows (wide_gather_cast), projects them with one GEMM and scatters them to their token rows in the shared LayerNorm
+// (wide_ln_fwd_mapped); GEMMs and row kernels then run over the N token rows as in the uniform forward; the attention runs one launch per
+// kernel class over the clips of that class (wide_attn_ragged_fwd). Nothing in the workspace is sized by B * max S_b.
+namespace {
+struct WRagged {
+    int B = 0, K = 0, layout = 0;
+    size_t N = 0, R[EGX_MAX_SEGMENTS] = {}, Rmax = 0;
+    size_t zero = 0, seg_w[EGX_MAX_SEGMENTS] = {}, feat16 = 0, pre = 0;
+    size_t w_in[64] = {}, w_o[64] = {}, w1[64] = {}, w2[64] = {};
+    size_t x32 = 0, x16 = 0, qkv = 0, lse = 0, attn = 0, res = 0, x1_32 = 0, x1_16 = 0, hid = 0, tab_off = 0, bytes = 0;
+    // host copy of the batch table (ints): B clip records (WIDE_RG_REC), the clips of attention class 0 | 1 | 2, per segment the source
+    // row (b * segs[k].T + t) and the token row of every compacted row, and (out_layout 1) the output row of every token row
+    std::vector<int> tab;
+    size_t cls0 = 0, gmap[EGX_MAX_SEGMENTS] = {}, omap[EGX_MAX_SEGMENTS] = {}, outmap = 0;
+    int ncls[3] = {0, 0, 0}, Smax[3] = {0, 0, 0};
+};
+
+int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int out_layout, WRagged& rp) {
+    EGX_CHECK(cfg && segs && lengths, "ragged encode: null argument");
+    EGX_CHECK(B >= 1 && B <= (1 << 20), "ragged encode: B=%d clips (1 .. %d)", B, 1 << 20);
+    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
+              "ragged batches are inference-only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g)", cfg->p_drop, cfg->p_pos, cfg->p_feat);
+    EGX_CHECK(!cfg->ce && !cfg->token_ce, "ragged encode: the fused losses (egx_config.ce / token_ce) are not supported; apply the loss to the outputs");
+    EGX_CHECK(cfg->out_tokens == 0 && !cfg->bucket_cb, "ragged encode: out_tokens and bucket_cb are not supported");
+    EGX_CHECK(cfg->compute == EGX_BF16, "ragged encode: runs on the wide bf16 path (compute bf16, got %d)", cfg->compute);
+    EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_WIDE, "ragged encode: runs on the wide path (impl auto or wide, got %d)", cfg->impl);
+    EGX_CHECK(out_layout == 0 || out_layout == 1, "ragged encode: out_layout %d (0: packed clips, 1: frame-major segment tuples)", out_layout);
+    const int d = cfg->d_model, K = cfg->n_segments, dff = cfg->d_ff, L = cfg->n_layers;
+    EGX_CHECK((d >= 256 || cfg->impl == EGX_IMPL_WIDE) && d % 128 == 0 && d <= 1024 && dff % 128 == 0 && dff >= 128 && L >= 1 && L <= 64 &&
+              cfg->n_heads > 0 && d % cfg->n_heads == 0 && K >= 1 && K <= EGX_MAX_SEGMENTS,
+              "ragged encode: needs d_model %% 128 == 0 in [256, 1024], d_ff %% 128 == 0, 1 .. 64 layers, 1 .. %d segments", EGX_MAX_SEGMENTS);
+    const int dh = d / cfg->n_heads;
+    for (int k = 0; k < K; ++k)
+        EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0 && segs[k].pool <= 1 && segs[k].T >= 1,
+                  "ragged encode: segment %d needs a projection with d_in %% 128 == 0 and no frame pooling", k);
+    rp.B = B; rp.K = K; rp.layout = out_layout;
+    rp.tab.assign((size_t)B * WIDE_RG_REC + B, 0);
+    size_t tok = 0;
+    for (int b = 0; b < B; ++b) {
+        int* rec = rp.tab.data() + (size_t)b * WIDE_RG_REC;
+        int S = 0;
+        for (int k = 0; k < K; ++k) {
+            const int T = lengths[(size_t)b * K + k];
+            EGX_CHECK(T >= 1 && T <= segs[k].T, "ragged encode: clip %d segment %d has %d frames (1 .. %d, the padded length)", b, k, T, segs[k].T);
+            EGX_CHECK(out_layout == 0 || T == lengths[(size_t)b * K], "ragged encode: out_layout 1 needs equal segment lengths in every clip "
+                      "(clip %d: segment %d has %d frames, segment 0 %d)", b, k, T, lengths[(size_t)b * K]);
+            rec[WRG_T + k] = T; rec[WRG_OFF + k] = S;
+            S += T;
+            rp.R[k] += T;
+        }
+        const int c = wide_attn_ragged_class(S, dh);
+        EGX_CHECK(c >= 0, "ragged encode: clip %d has S=%d tokens, beyond the wide attention (head dim %d)", b, S, dh);
+        rec[WRG_S] = S; rec[WRG_TOK0] = (int)tok;
+        rp.ncls[c]++; rp.Smax[c] = S > rp.Smax[c] ? S : rp.Smax[c];
+        tok += S;
+        EGX_CHECK(tok <= ((size_t)1 << 28), "ragged encode: %zu tokens in one call", tok);
+    }
+    rp.N = tok;
+    rp.cls0 = (size_t)B * WIDE_RG_REC;
+    {
+        int at[3] = {0, rp.ncls[0], rp.ncls[0] + rp.ncls[1]};
+        for (int b = 0; b < B; ++b) {
+            const int* rec = rp.tab.data() + (size_t)b * WIDE_RG_REC;
+            rp.tab[rp.cls0 + at[wide_attn_ragged_class(rec[WRG_S], dh)]++] = b;
+        }
+    }
+    for (int k = 0; k < K; ++k) {
+        rp.gmap[k] = rp.tab.size();
+        rp.omap[k] = rp.gmap[k] + rp.R[k];
+        rp.tab.resize(rp.omap[k] + rp.R[k]);
+        size_t r = 0;
+        for (int b = 0; b < B; ++b) {
+            const int* rec = rp.tab.data() + (size_t)b * WIDE_RG_REC;
+            for (int t = 0; t < rec[WRG_T + k]; ++t, ++r) {
+                rp.tab[rp.gmap[k] + r] = b * segs[k].T + t;
+                rp.tab[rp.omap[k] + r] = rec[WRG_TOK0] + rec[WRG_OFF + k] + t;
+            }
+        }
+        rp.Rmax = smax(rp.Rmax, rp.R[k]);
+    }
+    if (out_layout == 1) {      // token (clip b, segment k, frame t) -> row K (F0_b + t) + k, F0_b = frames of the clips before b
+        rp.outmap = rp.tab.size();
+        rp.tab.resize(rp.outmap + rp.N);
+        size_t F0 = 0;
+        for (int b = 0; b < B; ++b) {
+            const int* rec = rp.tab.data() + (size_t)b * WIDE_RG_REC;
+            for (int k = 0; k < K; ++k)
+                for (int t = 0; t < rec[WRG_T + k]; ++t) rp.tab[rp.outmap + rec[WRG_TOK0] + rec[WRG_OFF + k] + t] = (int)(K * (F0 + t) + k);
+            F0 += rec[WRG_T];
+        }
+    }
+    const size_t N = rp.N, dd = d;
+    size_t cur = 0, din_max = 0;
+    rp.zero = take(cur, 1024);
+    for (int k = 0; k < K; ++k) { rp.seg_w[k] = take(cur, dd * segs[k].d_in * 2); din_max = smax(din_max, (size_t)segs[k].d_in); }
+    for (int l = 0; l < L; ++l) {
+        rp.w_in[l] = take(cur, 3 * dd * dd * 2); rp.w_o[l] = take(cur, dd * dd * 2);
+        rp.w1[l] = take(cur, (size_t)dff * dd * 2); rp.w2[l] = take(cur, (size_t)dff * dd * 2);
+    }
+    rp.feat16 = take(cur, rp.Rmax * din_max * 2);
+    rp.pre = take(cur, rp.Rmax * dd * 4);
+    rp.x32 = take(cur, N * dd * 4); rp.x16 = take(cur, N * dd * 2);
+    rp.qkv = take(cur, N * 3 * dd * 2); rp.lse = take(cur, N * cfg->n_heads * 4); rp.attn = take(cur, N * dd * 2);
+    rp.res = take(cur, N * dd * 4); rp.x1_32 = take(cur, N * dd * 4); rp.x1_16 = take(cur, N * dd * 2);
+    rp.hid = take(cur, N * (size_t)dff * 2);
+    rp.tab_off = take(cur, (rp.outmap ? rp.tab.size() : rp.tab.size() + N) * sizeof(int));   // (sized for out_layout 1 either way)
+    rp.bytes = cur;
+    return 0;
+}
+}  // namespace
+
 }  // namespace egx
+
+using namespace egx;
+
+extern "C" {
+
+int egx_ragged_encode_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, 0, rp)) return 1;
+    if (bytes) *bytes = rp.bytes;
+    return 0;
+}
+
+int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                      const egx_layer* layers, int B, float* tokens_out, int out_layout, void* workspace, void* stream) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp)) return 1;
+    EGX_CHECK(ln_w && ln_b && layers && tokens_out && workspace, "egx_ragged_encode: null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int d = cfg->d_model, dff = cfg->d_ff, L = cfg->n_layers, H = cfg->n_heads, K = rp.K, N = (int)rp.N;
+    // the batch table to the device, stream-ordered, in the arguments of upload launches: a captured hipGraph would replay THIS call's
+    // lengths for every batch, so the call is not meant for capture
+    int* tab = (int*)(ws + rp.tab_off);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    EGX_HIP(hipMemsetAsync(ws + rp.zero, 0, 1024, st));
+    const void* zero = ws + rp.zero;
+    {   // the forward's weights -> bf16, one launch
+        WideCastBatch cb;
+        for (int k = 0; k < K; ++k)
+            if (wide_cast_add(cb, segs[k].proj_w, d, segs[k].d_in, segs[k].d_in, (bf16_t*)(ws + rp.seg_w[k]), nullptr, st)) return 1;
+        for (int l = 0; l < L; ++l) {
+            const egx_layer& w = layers[l];
+            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, (bf16_t*)(ws + rp.w_in[l]), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.out_proj_w, d, d, d, (bf16_t*)(ws + rp.w_o[l]), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, (bf16_t*)(ws + rp.w1[l]), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, (bf16_t*)(ws + rp.w2[l]), nullptr, st)) return 1;
+        }
+        if (wide_cast_flush(cb, st)) return 1;
+    }
+    float* x32 = (float*)(ws + rp.x32);
+    bf16_t* x16 = (bf16_t*)(ws + rp.x16);
+    for (int k = 0; k < K; ++k) {       // token preparation: valid frames only -> projection GEMM over R_k rows -> shared LN, scattered
+        const egx_segment& sg = segs[k];
+        const int R = (int)rp.R[k];
+        bf16_t* f16 = (bf16_t*)(ws + rp.feat16);
+        float* pre = (float*)(ws + rp.pre);
+        if (wide_gather_cast(sg.feat, sg.feat_bf16, tab + rp.gmap[k], R, sg.d_in, f16, st)) return 1;
+        WideGemmParams g;
+        g.A = f16; g.B = (const bf16_t*)(ws + rp.seg_w[k]); g.M = R; g.N = d; g.K = sg.d_in; g.lda = sg.d_in; g.ldb = sg.d_in;
+        g.Cf = pre; g.ldc = d; g.bias = sg.proj_b; g.zero_page = zero;
+        if (wide_gemm_nt(g, st)) return 1;
+        WideLnFwdParams lp;
+        lp.x = pre; lp.w = ln_w; lp.b = ln_b; lp.eps = cfg->ln_eps;
+        lp.y32 = x32; lp.y16 = x16; lp.rows = R; lp.d = d; lp.T = sg.T;
+        lp.add_vec = sg.add_vec; lp.pos = sg.pos; lp.pos_stride = sg.pos_stride;
+        lp.out_map = tab + rp.omap[k]; lp.src_map = tab + rp.gmap[k];
+        if (wide_ln_fwd_mapped(lp, st)) return 1;
+    }
+    bf16_t* qkv = (bf16_t*)(ws + rp.qkv);
+    bf16_t* attn = (bf16_t*)(ws + rp.attn);
+    float* res = (float*)(ws + rp.res);
+    float* x1_32 = (float*)(ws + rp.x1_32);
+    bf16_t* x1_16 = (bf16_t*)(ws + rp.x1_16);
+    bf16_t* hid = (bf16_t*)(ws + rp.hid);
+    for (int l = 0; l < L; ++l) {
+        const egx_layer& w = layers[l];
+        const bool last = l + 1 == L;
+        {   // packed in-projection
+            WideGemmParams g;
+            g.A = x16; g.B = (const bf16_t*)(ws + rp.w_in[l]); g.M = N; g.N = 3 * d; g.K = d; g.lda = d; g.ldb = d;
+            g.Cb = qkv; g.ldc = 3 * d; g.bias = w.in_proj_b; g.zero_page = zero;
+            if (wide_gemm_nt(g, st)) return 1;
+        }
+        for (int c = 0, first = 0; c < 3; first += rp.ncls[c], ++c) {       // one launch per attention kernel class
+            if (!rp.ncls[c]) continue;
+            WideAttnParams a;
+            a.qkv = qkv; a.out = attn; a.lse = (float*)(ws + rp.lse);
+            a.B = rp.ncls[c]; a.S = rp.Smax[c]; a.H = H; a.d = d;
+            a.rtab = tab; a.clips = tab + rp.cls0 + first;
+            if (wide_attn_ragged_fwd(a, st)) return 1;
+        }
+        {   // out-projection + residual -> res
+            WideGemmParams g;
+            g.A = attn; g.B = (const bf16_t*)(ws + rp.w_o[l]); g.M = N; g.N = d; g.K = d; g.lda = d; g.ldb = d;
+            g.Cf = res; g.ldc = d; g.bias = w.out_proj_b; g.residual = x32; g.ldr = d; g.zero_page = zero;
+            if (wide_gemm_nt(g, st)) return 1;
+        }
+        {
+            WideLnFwdParams lp;
+            lp.x = res; lp.w = w.norm1_w; lp.b = w.norm1_b; lp.eps = cfg->ln_eps; lp.y32 = x1_32; lp.y16 = x1_16; lp.rows = N; lp.d = d;
+            if (wide_ln_fwd(lp, st)) return 1;
+        }
+        {   // linear1 + ReLU -> hidden (bf16)
+            WideGemmParams g;
+            g.A = x1_16; g.B = (const bf16_t*)(ws + rp.w1[l]); g.M = N; g.N = dff; g.K = d; g.lda = d; g.ldb = d;
+            g.Cb = hid; g.ldc = dff; g.bias = w.lin1_b; g.relu = 1; g.zero_page = zero;
+            if (wide_gemm_nt(g, st)) return 1;
+        }
+        {   // linear2 + residual -> res
+            WideGemmParams g;
+            g.A = hid; g.B = (const bf16_t*)(ws + rp.w2[l]); g.M = N; g.N = d; g.K = dff; g.lda = dff; g.ldb = dff;
+            g.Cf = res; g.ldc = d; g.bias = w.lin2_b; g.residual = x1_32; g.ldr = d; g.zero_page = zero;
+            if (wide_gemm_nt(g, st)) return 1;
+        }
+        {   // norm2 -> the next layer's input, or the output (out_layout 1: through the frame-major row map)
+            WideLnFwdParams lp;
+            lp.x = res; lp.w = w.norm2_w; lp.b = w.norm2_b; lp.eps = cfg->ln_eps; lp.rows = N; lp.d = d;
+            lp.y32 = last ? tokens_out : x32; lp.y16 = last ? nullptr : x16;
+            if (last && out_layout == 1) {
+                lp.out_map = tab + rp.outmap;
+                if (wide_ln_fwd_mapped(lp, st)) return 1;
+            } else if (wide_ln_fwd(lp, st)) return 1;
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

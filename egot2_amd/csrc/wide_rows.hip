@@ -77,6 +77,59 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
     }
 }
 
+// ragged batches (wide_ln_fwd_mapped): the kernel above with the output row and the positional row read from the row maps of the batch
+// table (a separate copy: a shared inlined body changed the uniform kernel's register allocation and occupancy)
+__global__ __launch_bounds__(256) void wide_ln_fwd_mapped_kernel(WideLnFwdParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int d = p.d, nv = (d + 255) / 256;
+    const float inv_d = 1.f / (float)d;
+    for (int row = blockIdx.x * 4 + wave; row < p.rows; row += gridDim.x * 4) {
+        const float* x = p.x + (size_t)row * d;
+        float4 v[LN_MAXV];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            int c = 4 * lane + 256 * i;
+            v[i] = make_float4(0, 0, 0, 0);
+            if (i < nv && c < d) v[i] = *reinterpret_cast<const float4*>(x + c);
+            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        }
+        const float mean = wsum64(s) * inv_d;
+        float ss = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            int c = 4 * lane + 256 * i;
+            if (i < nv && c < d) {
+                float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, dd = v[i].w - mean;
+                ss += (a * a + b * b) + (cc * cc + dd * dd);
+            }
+        }
+        const float rstd = rsqrtf(wsum64(ss) * inv_d + p.eps);
+        if (p.stats && lane == 0) *reinterpret_cast<float2*>(p.stats + 2 * (size_t)row) = make_float2(mean, rstd);
+        const int t_in = p.src_map ? p.src_map[row] % p.T : 0, orow = p.out_map[row];
+        const float* pos = p.pos ? p.pos + (size_t)t_in * p.pos_stride : nullptr;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            int c = 4 * lane + 256 * i;
+            if (i < nv && c < d) {
+                float4 w = *reinterpret_cast<const float4*>(p.w + c), b = *reinterpret_cast<const float4*>(p.b + c);
+                float o[4] = {(v[i].x - mean) * rstd * w.x + b.x, (v[i].y - mean) * rstd * w.y + b.y,
+                              (v[i].z - mean) * rstd * w.z + b.z, (v[i].w - mean) * rstd * w.w + b.w};
+                if (p.add_vec) { float4 a = *reinterpret_cast<const float4*>(p.add_vec + c); o[0] += a.x; o[1] += a.y; o[2] += a.z; o[3] += a.w; }
+                if (pos) { float4 a = *reinterpret_cast<const float4*>(pos + c); o[0] += a.x; o[1] += a.y; o[2] += a.z; o[3] += a.w; }
+                if (p.drop_thresh) {
+                    float ds[4];
+                    drop_scale4(dkey, (uint32_t)orow, (uint32_t)c, p.drop_thresh, p.drop_inv, ds);
+                    o[0] *= ds[0]; o[1] *= ds[1]; o[2] *= ds[2]; o[3] *= ds[3];
+                }
+                if (p.y32) *reinterpret_cast<float4*>(p.y32 + (size_t)orow * d + c) = make_float4(o[0], o[1], o[2], o[3]);
+                if (p.y16) *reinterpret_cast<uint2*>(p.y16 + (size_t)orow * d + c) = make_uint2(pk2(o[0], o[1]), pk2(o[2], o[3]));
+            }
+        }
+    }
+}
+
 int wide_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
     EGX_CHECK(p.x && p.w && p.b && (p.y32 || p.y16), "wide_ln_fwd: null pointer");
     EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_fwd: d=%d unsupported", p.d);
@@ -84,6 +137,18 @@ int wide_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
     int blocks = cdiv(p.rows, 4);
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(wide_ln_fwd_kernel, dim3(blocks), dim3(256), 0, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wide_ln_fwd_mapped(const WideLnFwdParams& p, hipStream_t st) {
+    EGX_CHECK(p.x && p.w && p.b && (p.y32 || p.y16) && p.out_map, "wide_ln_fwd_mapped: null pointer");
+    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0 && p.T >= 1, "wide_ln_fwd_mapped: d=%d unsupported", p.d);
+    EGX_CHECK(!p.pos || p.src_map, "wide_ln_fwd_mapped: a positional table needs the source-row map");
+    if (p.rows <= 0) return 0;
+    int blocks = cdiv(p.rows, 4);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(wide_ln_fwd_mapped_kernel, dim3(blocks), dim3(256), 0, st, p);
     EGX_LAUNCH_CHECK();
     return 0;
 }

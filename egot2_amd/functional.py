@@ -795,6 +795,151 @@ def _encoder_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, l
     return out
 
 
+def ragged_token_rows(lengths: torch.Tensor, out_layout: int = 0) -> torch.Tensor:
+    """Host (B, K) int32 lengths -> int64 output row of every token of encoder_ragged_tokens(), in clip-major token order (clip b,
+    segment k, frame t): packed clips (out_layout 0) or frame-major segment tuples (out_layout 1)."""
+    B, K = lengths.shape
+    S = lengths.to(torch.int64).sum(1)
+    if out_layout == 0:
+        return torch.arange(int(S.sum()), dtype=torch.int64)
+    T = lengths[:, 0].to(torch.int64)
+    F0 = torch.cumsum(T, 0) - T
+    rows = []
+    for b in range(B):
+        f = F0[b] + torch.arange(int(T[b]), dtype=torch.int64)
+        rows.append((K * f[None, :] + torch.arange(K, dtype=torch.int64)[:, None]).reshape(-1))
+    return torch.cat(rows) if rows else torch.zeros(0, dtype=torch.int64)
+
+
+def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
+                          proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], out_layout: int = 0):
+    """Inference forward (no autograd) returning EVERY token of a ragged batch: feats[k] padded (B, spec.segments[k].T, d_in), `lengths` the
+    (B, K) int32 host tensor of ragged_lengths(). out_layout 0: (sum_b S_b, d), clip after clip (S_b = sum_k T_{b,k}); out_layout 1 (every
+    clip's segments of equal length T_b): (K sum_b T_b, d), row K f + k = segment k of frame f of the batch. Runs egx_ragged_encode on the
+    wide bf16 path (last_encoder_impl() == "ragged"); configurations it does not cover run one batched forward per length tuple ("grouped")."""
+    if spec.training or spec.ce or spec.token_ce or spec.out_tokens or spec.head_n_out:
+        raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens, no head")
+    nseg = len(spec.segments)
+    B = feats[0].shape[0]
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
+        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
+    if out_layout not in (0, 1):
+        raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
+    lengths = lengths.contiguous()
+    if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
+        b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
+        raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
+    lib = _lib.load()
+    if reload_tuning_each_call:
+        lib.egx_tuning_reload()
+    device = feats[0].device
+    with torch.no_grad():
+        feats = [_dev_feat(t, f"feats[{i}]") for i, t in enumerate(feats)]
+        proj = [_dev_f32(t, "projection weight") for t in proj]
+        layer_t = [_dev_f32(t, "layer weight") for t in layer_params]
+        ln_w, ln_b = _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias")
+        task_embed = _dev_f32(task_embed, "task_embed") if task_embed is not None else None
+        pos_table = _dev_f32(pos_table, "positional table") if pos_table is not None else None
+        d = spec.d_model
+        segs = (Segment * nseg)()
+        pi = 0
+        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
+            if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
+                raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
+            segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
+            segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
+            if ss.has_proj:
+                segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
+                pi += 1
+            if ss.add_row is not None:
+                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
+            if ss.pos_row0 is not None:
+                segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
+        layers = (Layer * max(spec.n_layers, 1))()
+        for l in range(spec.n_layers):
+            for k, name in enumerate(_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
+        import dataclasses
+        cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
+        nbytes = C.c_size_t(0)
+        if lib.egx_ragged_encode_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
+            # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged wide path does not cover
+            return _encoder_tokens_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout)
+        ws = _workspace("ragged_wide", device, nbytes.value)
+        out = torch.empty((int(lengths.to(torch.int64).sum()), d), dtype=torch.float32, device=device)
+        check(lib.egx_ragged_encode(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
+                                    ptr(ws), _stream()))
+    _last_impl[0] = IMPL_RAGGED
+    _last_slices[0] = 1
+    return out
+
+
+def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
+    """encoder_ragged_tokens where egx_ragged_encode does not run (compute other than bf16, a forced implementation, a clip beyond the wide
+    attention): one batched forward per group of clips with the same length tuple, on their unpadded frames; rows scattered to their place."""
+    import dataclasses
+    d = spec.d_model
+    device = feats[0].device
+    groups = {}
+    for b, row in enumerate(lengths.tolist()):
+        groups.setdefault(tuple(row), []).append(b)
+    rows = ragged_token_rows(lengths, out_layout)
+    S = lengths.to(torch.int64).sum(1)
+    tok0 = torch.cumsum(S, 0) - S
+    out = torch.empty((int(S.sum()), d), dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for key, idx in groups.items():
+            it = torch.tensor(idx, dtype=torch.int64, device=device)
+            fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
+            gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)])
+            r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
+            src = (tok0[idx][:, None] + torch.arange(sum(key))[None, :]).reshape(-1)
+            out.index_copy_(0, rows[src].to(device), r.reshape(-1, d))
+    _last_impl[0] = IMPL_GROUPED
+    _last_slices[0] = 1
+    return out
+
+
+_last_dec_impl = ["none"]
+
+
+def last_decoder_impl() -> str:
+    """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
+    operation), "ragged" (egx_decoder_ragged_fwd) or "grouped" (a ragged memory decoded one length group at a time)."""
+    return _last_dec_impl[0]
+
+
+def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b):
+    """Inference decode (no autograd) over a packed ragged memory: tokens (B, sy) int64, memory (sum_b S_b, d) with S_b = mem_lengths[b]
+    ((B,) int32 host tensor); clip b cross-attends to its own rows only. meta as DecoderFn's (p_drop / p_pos ignored: inference).
+    Returns logits (B * sy, |V|) (egx_decoder_ragged_fwd)."""
+    lib = _lib.load()
+    n_layers = meta["n_layers"]
+    with torch.no_grad():
+        layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
+        fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
+        memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+        if tokens.dtype != torch.int64 or not tokens.is_cuda:
+            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
+        tokens = tokens.contiguous()
+        B, sy = tokens.shape
+        d = emb.shape[1]
+        ml = mem_lengths.contiguous()
+        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16, 0.0, 0.0, None)
+        nb = C.c_size_t(0)
+        check(lib.egx_decoder_ragged_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(nb)))
+        ws = _workspace("dec_ragged", memory.device, nb.value)
+        layers = (_lib.DecLayer * n_layers)()
+        for l in range(n_layers):
+            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+        logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
+        check(lib.egx_decoder_ragged_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers,
+                                         ptr(fc_w), ptr(fc_b), B, ptr(logits), ptr(ws), _stream()))
+    _last_dec_impl[0] = "ragged"
+    return logits
+
+
 def _token_ce_fused(spec: EncoderSpec, feats, proj) -> bool:
     """Does this configuration evaluate EncoderSpec.token_ce in its kernels (egx_encoder_token_ce_ok)? Probed with the real feature / projection
     tensors; the weight cache only has to exist."""

@@ -9,9 +9,10 @@ import torch
 import torch.nn as nn
 
 from .backbones import freeze_params, make_backbone
-from .functional import SegmentSpec
+from . import functional as F_egx
+from .functional import EncoderSpec, SegmentSpec
 from .decoder import DecoderMixin
-from .translator import PositionalEncoding, TranslatorMixin
+from .translator import PositionalEncoding, TranslatorMixin, encoder_layer_tensors
 
 
 class CustomDecoderLayer(nn.TransformerDecoderLayer):
@@ -78,13 +79,20 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         return mask
 
     # ---- encoder (HIP) ---------------------------------------------------------------------------------
-    def encode_features(self, task, lam_feat, ttm_feat=None, asd_feat=None):
-        """Backbone features -> decoder memory in the reference layout: (S, B, d), or (3, B*T, d) for 'asd'."""
+    def encode_features(self, task, lam_feat, ttm_feat=None, asd_feat=None, lengths=None):
+        """Backbone features -> decoder memory in the reference layout: (S, B, d), or (3, B*T, d) for 'asd'.
+
+        lengths (inference only, functional.ragged_lengths): the features are padded batches of clips of their own lengths, (B,) or (B, K)
+        frame counts in argument order (K = 1 for 'lam', else 3); padded frames are never read. Returns the packed memory of every clip,
+        (sum_b S_b, d) with S_b = sum_k T_{b,k}, for 'ttm' / 'lam' (decode(..., memory_lengths=S_b)), and the reference's (3, sum_b T_b, d)
+        for 'asd' (equal segment lengths per clip), a view of one frame-major buffer that decode() reads without a copy."""
         if task == 'lam':
             feats, projs, ids = [lam_feat], [self.proj_lam], [0]
         else:
             feats, projs, ids = [lam_feat, ttm_feat, asd_feat], [self.proj_lam, self.proj_ttm, self.proj_asd], [0, 1, 2]
         segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, ids)]
+        if lengths is not None:
+            return self._encode_features_ragged(task, feats, segs, projs, lengths)
         x = self._egx_encode(feats, segs, encoder=self.transformer_encoder, ln=self.ln, projs=projs,
                              task_embed=self.task_embed, pos_table=self.pos_embed.pe,
                              p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p)   # (B, S, d)
@@ -93,6 +101,30 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
             return torch.stack((x[:, 0:T].reshape(-1, self.dim), x[:, T:2 * T].reshape(-1, self.dim),
                                 x[:, 2 * T:3 * T].reshape(-1, self.dim)), dim=0)
         return x.permute(1, 0, 2)
+
+    def _check_inference(self, what):
+        if self.training:
+            raise ValueError(f"ragged batches are inference-only: call model.eval() before passing {what}")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
+                             "(or with every parameter frozen)")
+
+    def _encode_features_ragged(self, task, feats, segs, projs, lengths):
+        self._check_inference("lengths=")
+        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segs])
+        if task == 'asd' and not bool((lens == lens[:, :1]).all()):
+            b = int((lens != lens[:, :1]).any(1).nonzero()[0, 0])
+            raise ValueError(f"task 'asd' needs lam, ttm and asd features of equal length in every clip (clip {b}: {lens[b].tolist()})")
+        layer0 = self.transformer_encoder.layers[0]
+        spec = EncoderSpec(d_model=self.dim, n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
+                           n_layers=len(self.transformer_encoder.layers), segments=segs, ln_eps=self.ln.eps, compute=self.egx_compute,
+                           impl=self.egx_impl)
+        proj_t = [t for p in projs for t in (p.weight, p.bias)]
+        x = F_egx.encoder_ragged_tokens(spec, feats, lens, self.task_embed, self.pos_embed.pe, self.ln.weight, self.ln.bias, proj_t,
+                                        encoder_layer_tensors(self.transformer_encoder), out_layout=1 if task == 'asd' else 0)
+        if task == 'asd':
+            return x.view(-1, 3, self.dim).permute(1, 0, 2)        # (3, sum_b T_b, d): row 3 f + k of x is segment k of frame f
+        return x
 
     def encode(self, video, video_asd, audio, audio_asd, task):
         with torch.no_grad():
@@ -109,8 +141,13 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         return self.encode_features(task, lam_feat, ttm_feat, asd_feat)
 
     # ---- decoder (HIP; row F1) ---------------------------------------------------------------------------
-    def decode(self, y, encoded_x):
-        """(B, sy) tokens + (S, B, d) memory -> (sy, B, |V|); on the GPU this is the HIP decoder (egot2_amd/decoder.py)."""
+    def decode(self, y, encoded_x, memory_lengths=None):
+        """(B, sy) tokens + (S, B, d) memory -> (sy, B, |V|); on the GPU this is the HIP decoder (egot2_amd/decoder.py).
+        memory_lengths (B,) (inference only): encoded_x is the packed (sum_b S_b, d) memory of encode_features(..., lengths=) for 'ttm' /
+        'lam', clip b cross-attends to its own S_b rows."""
+        if memory_lengths is not None:
+            return self._egx_decode_ragged(y, encoded_x, memory_lengths, embedding=self.embedding, pos_embed=self.pos_embed,
+                                           decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate)
         return self._egx_decode(y, encoded_x, embedding=self.embedding, pos_embed=self.pos_embed,
                                 decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate)
 
@@ -126,4 +163,28 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         y = torch.ones((batch_size, 1)) * self.vocab[task]
         y = y.type_as(video).long()
         output = self.decode(y, encoded_x)
+        return output[0, :, -2:]
+
+    def predict_features(self, task, lam_feat, ttm_feat=None, asd_feat=None, lengths=None):
+        """predict() from backbone features: output[0, :, -2:] of decode(<task token>, encode_features(...)), (B, 2), or (B T, 2) for
+        'asd'. With lengths (inference only; see encode_features) the features are padded batches of clips of their own lengths and the
+        result is (B, 2), or (sum_b T_b, 2) for 'asd', in clip order: what predict() gives clip by clip, in one encoder and one decoder call.
+        The frozen backbones (LAM / TTM BiLSTMs, the ASD front ends) are stock PyTorch and would read padded frames: run them clip by clip
+        (or through a feature cache) and pad their features here."""
+        assert task in ['lam', 'ttm', 'asd']
+        if lengths is not None:
+            self._check_inference("lengths=")
+        encoded_x = self.encode_features(task, lam_feat, ttm_feat, asd_feat, lengths=lengths)
+        dev = lam_feat.device
+        if task == 'asd':
+            y = torch.full((encoded_x.shape[1], 1), self.vocab[task], dtype=torch.long, device=dev)
+            output = self.decode(y, encoded_x)
+        elif lengths is None:
+            y = torch.full((lam_feat.shape[0], 1), self.vocab[task], dtype=torch.long, device=dev)
+            output = self.decode(y, encoded_x)
+        else:
+            S = F_egx.ragged_lengths(lengths, lam_feat.shape[0], [f.shape[1] for f in ([lam_feat] if task == 'lam' else
+                                                                                         [lam_feat, ttm_feat, asd_feat])]).sum(1)
+            y = torch.full((lam_feat.shape[0], 1), self.vocab[task], dtype=torch.long, device=dev)
+            output = self.decode(y, encoded_x, memory_lengths=S)
         return output[0, :, -2:]

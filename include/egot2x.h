@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define EGX_ABI_VERSION 17
+#define EGX_ABI_VERSION 18
 #define EGX_MAX_SEGMENTS 8
 
 enum { EGX_F32 = 0, EGX_BF16 = 1, EGX_F32_SPLIT = 2 };
@@ -322,6 +322,26 @@ int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* le
                    const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace,
                    void* stream);
 
+/* ---- ABI v18: ragged batches on the wide bf16 path (inference) ----
+ * The EgoT2-g HHI encoder (TaskTranslationPromptTransformer.encode, HHI/models/multitask/task_prompt_model.py:230-257) over B clips of
+ * their own lengths, for the reference's batch_size=1 validation (HHI/tasks/multitask/video_tasktranslation.py:83-101,176-187). Clip b's
+ * rows equal those of the same model on clip b alone, unpadded.
+ *   lengths     HOST int[B * n_segments], clip-major, as egx_ragged_fwd: 1 <= T_{b,k} <= segs[k].T; segs[k].feat stays padded
+ *               (B, segs[k].T, d_in), rows t >= T_{b,k} are never read. Clip b has S_b = sum_k T_{b,k} tokens.
+ *   out_layout  0: tokens_out holds all S_b rows of every clip, packed clip after clip (sum_b S_b rows of d floats): the decoder memory
+ *               of the tasks ttm / lam. 1: every clip has T_{b,k} = T_b for all k; the row of (frame f of the batch, segment k) is
+ *               K f + k (frames counted over the clips in order): the asd memory of task_prompt_model.py:250-257, i.e. the (B S, d)
+ *               layout egx_decoder_fwd reads with S = K, without a copy.
+ * Runs on the wide bf16 path: compute bf16, impl auto or wide, d_model % 128 == 0 in [256, 1024] (smaller with impl wide), d_ff % 128 == 0,
+ * 1 .. 64 layers, projected segments (d_in % 128 == 0, pool <= 1), fp32 or bf16 features, S_b within the wide attention (S_b <= 128 for
+ * head dims 32 / 64 / 96 / 128; up to 480 at head dim 64 where two K | V images fit the LDS). Refused: p_drop / p_pos / p_feat > 0,
+ * ce, token_ce, out_tokens, bucket_cb, compute other than bf16 (and no head: egx_ragged_fwd has one).
+ * `workspace`: egx_ragged_encode_workspace() bytes, a function of sum_b S_b and the model (not of B * max S_b). The call writes a per-clip
+ * table built from `lengths` into the workspace on `stream`: a captured hipGraph would replay THIS call's lengths, so it is not for capture. */
+int egx_ragged_encode_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes);
+int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                      const egx_layer* layers, int B, float* tokens_out, int out_layout, void* workspace, void* stream);
+
 /* pooled = mean_s tokens[b, s, :]; y = ln_w ? LN(pooled) : pooled; out = W ? y W^T + b : y.
  * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL. */
 int egx_pool_head_fwd(const float* tokens, int B, int S, int d,
@@ -492,6 +512,16 @@ int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const floa
 int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B, const float* d_logits,
                     const void* saved, void* scratch, float* d_memory, float* d_emb, const egx_dec_layer_grads* grads, float* d_fc_w,
                     float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, void* stream);
+/* ---- ABI v18: the decoder over ragged memories (inference) ----
+ * decode() (task_prompt_model.py:260-269) of B clips whose memories differ in length: `memory` holds sum_b S_b packed rows (clip after
+ * clip, S_b = mem_lengths[b], HOST int[B]; egx_ragged_encode's out_layout 0 output), clip b's target rows cross-attend to its own S_b rows
+ * only. tokens (B, sy) int64, logits (B * sy, vocab) as egx_decoder_fwd. cfg->S is the longest memory (1 <= S_b <= cfg->S <= 1024); every
+ * other limit is egx_decoder_fwd's. Refused: p_drop / p_pos > 0. `workspace`: egx_decoder_ragged_workspace() bytes (a function of
+ * sum_b S_b). The call writes a per-clip table from `mem_lengths` into the workspace on `stream`: not for graph capture. */
+int egx_decoder_ragged_workspace(const egx_dec_config* cfg, int B, const int* mem_lengths, size_t* bytes);
+int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const int* mem_lengths, const float* emb,
+                           const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B,
+                           float* logits, void* workspace, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
