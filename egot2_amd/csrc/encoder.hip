@@ -1568,18 +1568,29 @@ struct RaggedPlan {
     size_t out_rows = 0;        // head-less output rows: sum_b T_{b,0}
     size_t off_attn = 0, off_lse = 0, off_tokens = 0, off_tab = 0, bytes = 0;
     std::vector<int> tab;       // host copy of the batch table
+    int tiles = 0;
+    size_t seg_rows[FUSED_MAX_SEG] = {0, 0, 0, 0};    // training plan: sum_b T_{b,k}, the packed rows of segment k
 };
 
-int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp) {
+// train (egx_ragged_train_*): dropout (but FEAT) and the weighted cross entropy are allowed; the table gets the packed first row of every
+// clip's segments behind the tile map (FusedBwdParams::rseg)
+int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp, bool train = false) {
     Plan& vp = rp.vp;
     if (make_plan(cfg, segs, B, vp)) return 1;
     EGX_CHECK(lengths, "ragged batch: null lengths");
     EGX_CHECK(B <= (1 << 20), "ragged batch: B=%d clips (at most %d)", B, 1 << 20);
-    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
-              "ragged batches are inference-only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g)", cfg->p_drop, cfg->p_pos, cfg->p_feat);
-    EGX_CHECK(cfg->out_tokens == 0, "ragged batch: out_tokens is not supported (head-less, the first segment of every clip is returned)");
-    EGX_CHECK(!cfg->ce && !cfg->token_ce, "ragged batch: the fused losses (egx_config.ce / token_ce) are not supported; apply the loss to the outputs");
-    EGX_CHECK(!cfg->bucket_cb, "ragged batch: bucket_cb is a backward option (the ragged call is a forward only)");
+    if (train) {
+        EGX_CHECK(cfg->p_feat == 0.f, "ragged training: feature dropout (p_feat > 0) is not supported (got %g)", cfg->p_feat);
+        EGX_CHECK(cfg->out_tokens == 0, "ragged training: out_tokens is not supported (head-less, the first segment of every clip is returned)");
+        EGX_CHECK(!cfg->token_ce, "ragged training: the fused token loss (egx_config.token_ce) is not supported; apply the loss to the returned rows");
+        EGX_CHECK(!cfg->bucket_cb && cfg->bwd_stage == 0, "ragged training: bucket_cb and the staged backward (bwd_stage) are not supported");
+    } else {
+        EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
+                  "ragged batches are inference-only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g)", cfg->p_drop, cfg->p_pos, cfg->p_feat);
+        EGX_CHECK(cfg->out_tokens == 0, "ragged batch: out_tokens is not supported (head-less, the first segment of every clip is returned)");
+        EGX_CHECK(!cfg->ce && !cfg->token_ce, "ragged batch: the fused losses (egx_config.ce / token_ce) are not supported; apply the loss to the outputs");
+        EGX_CHECK(!cfg->bucket_cb, "ragged batch: bucket_cb is a backward option (the ragged call is a forward only)");
+    }
     EGX_CHECK(!cfg->weight_cache_valid || cfg->weight_cache, "weight_cache_valid without a weight_cache");
     EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_TILED, "ragged batch: runs on the tiled kernels (impl auto or tiled, got %d)", cfg->impl);
     // what tiled_ok() asks of the configuration, the clip length apart
@@ -1608,11 +1619,20 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
         tok += S; out += rec[RG_T];
         S_max = S > S_max ? S : S_max;
     }
-    rp.tab.resize((size_t)B * RAGGED_REC + tiles);
+    rp.tab.resize((size_t)B * RAGGED_REC + tiles + (train ? (size_t)B * FUSED_MAX_SEG : 0));
     for (int b = 0; b < B; ++b) {
         const int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
         for (int j = 0; j < cdiv(rec[RG_S], FUSED_TOK_PAD); ++j) rp.tab[(size_t)B * RAGGED_REC + rec[RG_TILE0] + j] = b;
     }
+    if (train) {
+        int* rseg = rp.tab.data() + (size_t)B * RAGGED_REC + tiles;
+        for (int k = 0; k < K; ++k) {
+            size_t r = 0;
+            for (int b = 0; b < B; ++b) { rseg[(size_t)b * FUSED_MAX_SEG + k] = (int)r; r += lengths[(size_t)b * K + k]; }
+            rp.seg_rows[k] = r;
+        }
+    }
+    rp.tiles = tiles;
     vp.vB = tiles; vp.tpc = 0; vp.N = tok; vp.S = S_max;
     rp.out_rows = out;
     const size_t d = vp.d;
@@ -1731,6 +1751,383 @@ int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* le
     }
     if (with_head)
         return pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- ragged batches for training (egx_ragged_train_fwd / egx_ragged_bwd): the tiled training mode over clips of their own lengths -------
+// `saved` is egx_ragged_fwd's workspace layout for the same batch (the RAGGED forward launches already write everything the tiled backward
+// reads: layer inputs, Q | K | V, the residual sums, the FFN hidden tiles and ReLU / dropout bits, x1 planes, attention outputs, log-sum-exp
+// rows, the last layer's tokens and the per-clip token means). The backward's scratch is the tiled backward's, sized by N = sum_b S_b tokens
+// and the tile count, with d(seg) packed (sum_b T_{b,k} rows per segment), then its own copy of the batch table and the packed operands of
+// the projection-weight and feature gradients.
+namespace {
+struct RaggedTrainScratch {
+    FusedBwdScratch sc;
+    size_t tab = 0, featp[FUSED_MAX_SEG] = {0, 0, 0, 0}, dfeat = 0, bytes = 0;
+};
+RaggedTrainScratch ragged_train_scratch(const egx_config* cfg, const egx_segment* segs, const RaggedPlan& rp, int head_n_out) {
+    RaggedTrainScratch r;
+    FusedBwdScratch& s = r.sc;
+    memset(&s, 0, sizeof(s));
+    const Plan& pl = rp.vp;
+    size_t cur = 0;
+    const size_t nd = pl.N * pl.d * 4;
+    const size_t nd3 = (size_t)pl.vB * FUSED_TOK_PAD * pl.d * 6;        // g2 as three bf16 planes on the tile grid (split mode)
+    for (int l = 0; l < pl.L && l < FUSED_MAX_LAYERS; ++l) {
+        s.x1[l] = take(cur, nd); s.g2[l] = take(cur, nd3); s.attn_o[l] = take(cur, nd);
+        s.g1[l] = take(cur, nd); s.dqkv[l] = take(cur, 3 * nd);
+    }
+    for (int i = 0; i < pl.nseg; ++i) s.dseg[i] = take(cur, rp.seg_rows[i] * pl.d * 4);
+    s.P = fused_partial_len(pl.L, pl.nseg) + fused_head_partial_len(head_n_out);
+    s.partials = take(cur, (size_t)pl.vB * s.P * 4);
+    size_t slab = ffn_dw_scratch_bytes((int)pl.N, pl.dff, nullptr);
+    slab = size_max(slab, gemm_scratch_bytes(2, 3 * pl.d, pl.d, (int)pl.N));
+    slab = size_max(slab, gemm_scratch_bytes(2, pl.d, pl.d, (int)pl.N));
+    for (int i = 0; i < pl.nseg; ++i) slab = size_max(slab, gemm_scratch_bytes(2, pl.d, segs[i].d_in, (int)rp.seg_rows[i]));
+    slab = size_max(slab, (size_t)(512 + SMALL_DW_MAX * 16) * 64 * 128 * sizeof(float));
+    s.slab_bytes = slab;
+    s.slabs = take(cur, slab);
+    s.ffn_slab[0] = s.slabs;
+    for (int l = 1; l < pl.L && l < FUSED_MAX_LAYERS; ++l) s.ffn_slab[l] = take(cur, ffn_dw_scratch_bytes((int)pl.N, pl.dff, nullptr));
+    s.sdw_bytes = (size_t)(512 + SMALL_DW_MAX * 16) * 64 * 128 * sizeof(float);
+    s.sdw_tiles = take(cur, s.sdw_bytes);
+    s.dhid = take(cur, fused_hid_total(cfg, pl));
+    s.dx0 = take(cur, nd);
+    s.datt = take(cur, nd); s.dres = take(cur, nd);
+    s.delta = take(cur, (size_t)pl.H * pl.N * 4);
+    s.bytes = cur;
+    r.tab = take(cur, rp.tab.size() * sizeof(int));
+    size_t dfeat = 0;
+    for (int i = 0; i < pl.nseg; ++i) {
+        r.featp[i] = take(cur, rp.seg_rows[i] * segs[i].d_in * 4);
+        dfeat = size_max(dfeat, rp.seg_rows[i] * segs[i].d_in * 4);
+    }
+    r.dfeat = take(cur, dfeat);
+    r.bytes = cur;
+    return r;
+}
+// with a head the last layer leaves EVERY token of a clip (rows tok0 .. tok0 + S_b of the dense array); head-less its first segment, packed
+void ragged_head_rows(RaggedPlan& rp, int B, bool with_head) {
+    if (!with_head) return;
+    for (int b = 0; b < B; ++b) {
+        int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
+        rec[RG_OUT0] = rec[RG_TOK0]; rec[RG_OUTN] = rec[RG_S];
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int egx_ragged_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
+                               size_t* scratch_bytes) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    if (saved_bytes) *saved_bytes = rp.bytes;
+    if (scratch_bytes) *scratch_bytes = ragged_train_scratch(cfg, segs, rp, FUSED_HEAD_MAX_OUT).bytes;
+    return 0;
+}
+
+int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                         const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* saved,
+                         void* scratch, int training, uint64_t seed, void* stream) {
+    (void)scratch;
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    const Plan& vp = rp.vp;
+    EGX_CHECK(saved && ln_w && ln_b && layers, "ragged training: null pointer argument");
+    const bool with_head = head && head->W;
+    EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged training: null output pointer");
+    EGX_CHECK(!with_head || (head->ln_w && head->ln_b && head->b && head->n_out >= 1 && head->n_out <= FUSED_HEAD_MAX_OUT),
+              "head needs ln_w, ln_b, W, b and 1 <= n_out <= %d", FUSED_HEAD_MAX_OUT);
+    const egx_ce* ce = cfg->ce;
+    EGX_CHECK(!ce || with_head, "egx_config.ce: the fused cross entropy needs the pooled head");
+    EGX_CHECK(!ce || (ce->target && ce->loss && ce->d_logits), "egx_config.ce: target, loss and d_logits must be set");
+    hipStream_t st = (hipStream_t)stream;
+    const int d = vp.d, comp = cfg->compute;
+    const size_t N = vp.N;
+    char* ws = (char*)saved;
+    float* dense = (float*)(ws + rp.off_tokens);        // every token of the last layer (N, d), then the token means (B, d)
+    ragged_head_rows(rp, B, with_head);
+    int* tab = (int*)(ws + rp.off_tab);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+
+    FusedFwdParams fp;
+    memset(&fp, 0, sizeof(fp));
+    PackParams pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.mode = comp;
+    pk.seed_advance = (cfg->advance_seed == 1 && cfg->seed_ptr && training) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
+    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
+    const bool cache_hit = cfg->weight_cache && cfg->weight_cache_valid;
+    auto add_pack = [&](const float* src, void* dst, int R, int Kd, int ld, int transpose, float scale = 1.f) -> const void* {
+        if (cache_hit) return dst;
+        PackDesc& dsc = pk.d[pk.n++];
+        dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = Kd; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = scale;
+        return dst;
+    };
+    // the FFN keep-scale rides on the packed W1 and W2^T (as in the tiled training forward)
+    const Drop dffn = make_drop(training, cfg->p_drop, seed, 0, SITE_FFN);
+    const float ffn_scale = dffn.thresh ? dffn.inv_keep : 1.f;
+    for (int i = 0; i < vp.nseg; ++i) {
+        FusedSeg& fs = fp.seg[i];
+        fs.feat = segs[i].feat; fs.proj_wp = add_pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0); fs.proj_b = segs[i].proj_b;
+        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos;
+        fs.T = segs[i].T; fs.d_in = segs[i].d_in; fs.pos_stride = segs[i].pos_stride;
+        fs.Tfull = segs[i].T; fs.seg_id = i;        // (the clip's own pieces come from the batch table)
+    }
+    fp.n_heads = vp.H;
+    for (int l = 0; l < vp.L; ++l) {
+        FusedLayer& fl = fp.layer[l];
+        const egx_layer& w = layers[l];
+        fl.in_proj_wp = add_pack(w.in_proj_w, PL.layer[l].in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
+        fl.out_proj_wp = add_pack(w.out_proj_w, PL.layer[l].out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
+        fl.lin1_wp = add_pack(w.lin1_w, PL.layer[l].lin1_w, vp.dff, d, d, 0, ffn_scale); fl.lin1_b = w.lin1_b;
+        fl.lin2_wp = add_pack(w.lin2_w, PL.layer[l].lin2_w, d, vp.dff, vp.dff, 0); fl.lin2_b = w.lin2_b;
+        add_pack(w.in_proj_w, PL.layer[l].in_wt, d, 3 * d, d, 1);
+        add_pack(w.out_proj_w, PL.layer[l].out_wt, d, d, d, 1);
+        add_pack(w.lin1_w, PL.layer[l].lin1_wt, d, vp.dff, d, 1);
+        add_pack(w.lin2_w, PL.layer[l].lin2_wt, vp.dff, d, vp.dff, 1, ffn_scale);
+        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+        Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
+        fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
+        fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
+        fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
+        fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
+        fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
+    }
+    fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
+    fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = FUSED_TOK_PAD; fp.d_ff = vp.dff;
+    fp.tpc = 0; fp.S_clip = vp.S; fp.Ntok = N;
+    fp.tokens_out = with_head ? dense : tokens_out;
+    fp.saved_pre = (float*)ws;
+    fp.saved_res = (float*)ws + N * d;
+    fp.relu_bits = (uint32_t*)(ws + fused_res_bytes(vp));
+    fp.hid_out = store_hidden() ? ws + fused_hid_offset(cfg, segs, vp) : nullptr;
+    fp.x1p_out = split_planes(cfg) ? (unsigned short*)(ws + fused_x1p_offset(cfg, segs, vp)) : nullptr;
+    fp.xin_out = (float*)(ws + fused_xin_offset(cfg, segs, vp));
+    fp.qkv_out = (float*)(ws + fused_qkv_offset(cfg, segs, vp));
+    Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
+    fp.pos_key = dpz.key; fp.pos_thresh = dpz.thresh; fp.pos_inv = dpz.inv_keep;
+    fp.seed_ptr = cfg->seed_ptr;
+    fp.rot_mode = 1;        // (as egx_ragged_fwd: a clip's result must not depend on its place in the batch)
+    fp.n_slices = 1;
+    fp.rtab = tab; fp.B_clips = B;
+    if (cfg->weight_cache && pk.n) pk.zero_ctl = (unsigned*)((char*)cfg->weight_cache + align_up(PL.bytes, 256));
+    if (pack_weights(pk, st)) return 1;
+    float* attn = (float*)(ws + rp.off_attn);
+    float* lse = (float*)(ws + rp.off_lse);
+    fp.attn_in = attn;
+    fp.mode = FUSED_MODE_PRE;
+    if (fused_forward(fp, comp, st)) return 1;
+    for (int l = 0; l < vp.L; ++l) {
+        TiledAttnParams ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.qkv = fp.qkv_out + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * d;
+        ap.attn_o = attn + (size_t)l * N * d;
+        ap.lse = lse + (size_t)l * vp.H * N;
+        ap.B = B; ap.S = vp.S; ap.tpc = 0; ap.layer = l;
+        ap.drop_key = fp.layer[l].attn_key; ap.drop_thresh = fp.layer[l].attn_thresh; ap.drop_inv = fp.layer[l].drop_inv;
+        ap.seed_ptr = cfg->seed_ptr;
+        ap.rtab = tab;
+        if (tiled_attn_fwd(ap, comp, st)) return 1;
+        fp.mode = FUSED_MODE_POST; fp.l0 = l;
+        if (fused_forward(fp, comp, st)) return 1;
+    }
+    if (with_head) {
+        if (pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st)) return 1;
+        if (ce) return weighted_ce(logits_out, ce->target, ce->class_weight, B, head->n_out, ce->loss, ce->d_logits, st);
+    }
+    return 0;
+}
+
+int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                   const egx_layer* layers, const egx_head* head, int B, const float* d_logits, const float* d_tokens, const void* saved,
+                   void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads,
+                   const egx_head_grads* head_grads, int training, uint64_t seed, void* stream) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    const Plan& vp = rp.vp;
+    const bool with_head = head && head->W;
+    EGX_CHECK((with_head ? (const void*)d_logits : (const void*)d_tokens) && saved && scratch && ln_w && ln_b && layers && layer_grads,
+              "ragged training: null pointer argument");
+    EGX_CHECK(!with_head || (head->ln_w && head->ln_b && head->b && head->n_out >= 1 && head->n_out <= FUSED_HEAD_MAX_OUT),
+              "head needs ln_w, ln_b, W, b and 1 <= n_out <= %d", FUSED_HEAD_MAX_OUT);
+    hipStream_t st = (hipStream_t)stream;
+    const int d = vp.d, comp = cfg->compute, L = vp.L;
+    const int N = (int)vp.N;
+    RaggedTrainScratch RS = ragged_train_scratch(cfg, segs, rp, with_head ? head->n_out : 0);
+    const FusedBwdScratch& SC = RS.sc;
+    // the batch table again (the backward's own copy: nothing of the forward's call is trusted but `saved`)
+    ragged_head_rows(rp, B, with_head);
+    int* tab = (int*)((char*)scratch + RS.tab);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    const int* rseg = tab + (size_t)B * RAGGED_REC + rp.tiles;
+    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
+    FusedBwdParams bp;
+    memset(&bp, 0, sizeof(bp));
+    for (int i = 0; i < vp.nseg; ++i) {
+        FusedSeg& fs = bp.seg[i];
+        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos; fs.T = segs[i].T; fs.d_in = segs[i].d_in;
+        fs.pos_stride = segs[i].pos_stride; fs.Tfull = segs[i].T; fs.seg_id = i;
+        bp.dseg_out[i] = fptr(scratch, SC.dseg[i]);
+    }
+    bp.n_heads = vp.H;
+    bool want_pos = false;
+    for (int i = 0; i < vp.nseg && seg_grads; ++i) want_pos = want_pos || seg_grads[i].pos;
+    EGX_CHECK(!want_pos, "ragged training: learned positional tables (egx_segment_grads.pos) are not supported");
+    for (int l = 0; l < L; ++l) {
+        FusedBwdLayer& fl = bp.layer[l];
+        const egx_layer& w = layers[l];
+        fl.in_proj_wp = PL.layer[l].in_w; fl.in_proj_wtp = PL.layer[l].in_wt; fl.out_proj_wtp = PL.layer[l].out_wt;
+        fl.lin1_wp = PL.layer[l].lin1_w; fl.lin2_wtp = PL.layer[l].lin2_wt; fl.lin1_wtp = PL.layer[l].lin1_wt;
+        fl.in_proj_b = w.in_proj_b; fl.lin1_b = w.lin1_b;
+        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+        Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
+        fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
+        fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
+        fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
+        fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
+        fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
+        fl.x1_out = fptr(scratch, SC.x1[l]); fl.g2_out = fptr(scratch, SC.g2[l]);
+        fl.g1_out = fptr(scratch, SC.g1[l]); fl.dqkv_out = fptr(scratch, SC.dqkv[l]);
+        fl.x_in_out = const_cast<float*>((const float*)((const char*)saved + fused_xin_offset(cfg, segs, vp))) + (size_t)l * N * d;
+        fl.attn_o_out = const_cast<float*>((const float*)((const char*)saved + rp.off_attn)) + (size_t)l * N * d;
+    }
+    bp.ln_w = ln_w; bp.ln_b = ln_b; bp.eps = cfg->ln_eps;
+    bp.nseg = vp.nseg; bp.n_layers = L; bp.B = vp.vB; bp.S = FUSED_TOK_PAD; bp.d_ff = vp.dff;
+    bp.tiled = 1; bp.tpc = 0; bp.S_clip = vp.S; bp.Ntok = vp.N;
+    bp.rtab = tab; bp.B_clips = B; bp.rseg = rseg;
+    bp.d_tokens = d_tokens;
+    if (with_head) {
+        bp.head.ln_w = head->ln_w; bp.head.ln_b = head->ln_b; bp.head.W = head->W; bp.head.b = head->b; bp.head.n_out = head->n_out;
+        bp.d_logits = d_logits;
+        bp.d_logits_scale = cfg->d_logits_scale;
+        bp.head_off = fused_partial_len(L, vp.nseg);
+        bp.pooled = (const float*)((const char*)saved + rp.off_tokens) + vp.N * d;
+    }
+    bp.saved_pre = (const float*)saved;
+    bp.saved_res = (const float*)saved + vp.N * d;
+    bp.saved_qkv = (const float*)((const char*)saved + fused_qkv_offset(cfg, segs, vp));
+    bp.relu_bits = (const uint32_t*)((const char*)saved + fused_res_bytes(vp));
+    bp.dhid_out = store_hidden() ? (char*)scratch + SC.dhid : nullptr;
+    bp.xg_planes = split_planes(cfg) ? 1 : 0;
+    EGX_CHECK(cfg->zero_bytes % 16 == 0 && (((uintptr_t)cfg->zero_buf) & 15) == 0, "zero_buf must be 16-byte aligned and sized");
+    bp.zero_buf = (float*)cfg->zero_buf; bp.zero_n = cfg->zero_buf ? cfg->zero_bytes / 4 : 0;
+    bp.partials = fptr(scratch, SC.partials); bp.P = SC.P;
+    Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
+    bp.pos_key = dpz.key; bp.pos_thresh = dpz.thresh; bp.pos_inv = dpz.inv_keep;
+    bp.seed_ptr = cfg->seed_ptr;
+    bp.rot_mode = 1;
+    bp.n_slices = 1;
+    // L + 1 launches of the tile kernel with the attention backward of every clip between them (the tiled backward's sequence)
+    bp.datt = fptr(scratch, SC.datt); bp.dres = fptr(scratch, SC.dres);
+    const float* lse = (const float*)((const char*)saved + rp.off_lse);
+    for (int l = L - 1; l >= 0; --l) {
+        bp.l_back = l; bp.l_front = l + 1 < L ? l + 1 : -1;
+        if (fused_backward(bp, comp, st)) return 1;
+        bp.zero_buf = nullptr;
+        TiledAttnParams ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.qkv = bp.saved_qkv + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * d;
+        ap.attn_o = bp.layer[l].attn_o_out;
+        ap.lse = const_cast<float*>(lse) + (size_t)l * vp.H * vp.N;
+        ap.d_o = bp.datt; ap.delta = fptr(scratch, SC.delta); ap.dqkv = bp.layer[l].dqkv_out;
+        ap.B = B; ap.S = vp.S; ap.tpc = 0;
+        ap.drop_key = bp.layer[l].attn_key; ap.drop_thresh = bp.layer[l].attn_thresh; ap.drop_inv = bp.layer[l].drop_inv;
+        ap.seed_ptr = cfg->seed_ptr; ap.layer = l;
+        ap.rtab = tab;
+        if (tiled_attn_bwd(ap, comp, st)) return 1;
+    }
+    bp.l_back = -1; bp.l_front = 0;
+    if (fused_backward(bp, comp, st)) return 1;
+
+    // the small parameter gradients: the per-tile partial rows (padding rows of a clip's last tile add nothing: they are zero there)
+    ReducePartialsParams rpp;
+    memset(&rpp, 0, sizeof(rpp));
+    rpp.B = vp.vB; rpp.P = SC.P; rpp.partials = bp.partials;
+    auto add_dst = [&](float* dst, int off, int len) { if (dst) { rpp.d[rpp.n].dst = dst; rpp.d[rpp.n].off = off; rpp.d[rpp.n].len = len; ++rpp.n; } };
+    for (int l = 0; l < L; ++l) {
+        const egx_layer_grads& gw = layer_grads[l];
+        int o = l * FUSED_P_LAYER;
+        add_dst(gw.norm2_w, o + 0, 128); add_dst(gw.norm2_b, o + 128, 128); add_dst(gw.lin2_b, o + 256, 128);
+        add_dst(gw.norm1_w, o + 384, 128); add_dst(gw.norm1_b, o + 512, 128); add_dst(gw.out_proj_b, o + 640, 128);
+        add_dst(gw.in_proj_b, o + 768, 384);
+    }
+    const int og = L * FUSED_P_LAYER;
+    add_dst(d_ln_w, og, 128); add_dst(d_ln_b, og + 128, 128);
+    for (int i = 0; i < vp.nseg && seg_grads; ++i) {
+        add_dst(seg_grads[i].add_vec, og + 256 + i * 256, 128);
+        add_dst(seg_grads[i].proj_b, og + 256 + i * 256 + 128, 128);
+    }
+    if (with_head && head_grads) {
+        const int oh = fused_partial_len(L, vp.nseg);
+        add_dst(head_grads->ln_w, oh, 128); add_dst(head_grads->ln_b, oh + 128, 128);
+        add_dst(head_grads->b, oh + 256, head->n_out);
+        add_dst(head_grads->W, oh + 256 + FUSED_HEAD_MAX_OUT, head->n_out * 128);
+    }
+    // FFN weight gradients from the stored H / dH tiles and the x1 / g2 planes of the tile grid; their slabs are summed by the tail launch
+    SlabReduce red;
+    red.narr = 0; red.nslab = 0;
+    for (int l = 0; l < L; ++l) {
+        const egx_layer& w = layers[l];
+        const egx_layer_grads& gw = layer_grads[l];
+        if (!(gw.lin1_w || gw.lin1_b || gw.lin2_w)) continue;
+        FfnDwParams fp;
+        memset(&fp, 0, sizeof(fp));
+        fp.x1 = bp.layer[l].x1_out; fp.g = bp.layer[l].g2_out;
+        fp.w1p = PL.layer[l].lin1_w; fp.w2tp = PL.layer[l].lin2_wt; fp.b1 = w.lin1_b;
+        fp.N = N; fp.S = vp.S; fp.d_ff = vp.dff;
+        fp.drop_key = bp.layer[l].ffn_key; fp.drop_thresh = bp.layer[l].ffn_thresh; fp.drop_inv = bp.layer[l].drop_inv;
+        fp.seed_ptr = cfg->seed_ptr; fp.layer = l;
+        const size_t lo = (size_t)l * fused_hid_bytes(vp.vB, vp.dff, comp == EGX_BF16);
+        fp.hs = (const char*)saved + fused_hid_offset(cfg, segs, vp) + lo;
+        fp.dhs = (const char*)scratch + SC.dhid + lo;
+        fp.B = vp.vB;
+        fp.xg_planes = bp.xg_planes;
+        if (fp.xg_planes) fp.x1 = (const float*)((const char*)saved + fused_x1p_offset(cfg, segs, vp) + (size_t)l * vp.vB * FUSED_TOK_PAD * d * plane_elem_bytes(cfg));
+        if (ffn_dw(fp, comp, gw.lin1_w, gw.lin1_b, gw.lin2_w, (char*)scratch + SC.ffn_slab[l], st, nullptr, cfg->deterministic != 0, &red)) return 1;
+    }
+    // the projection-weight gradients read the valid feature frames only: gathered into packed rows that match the packed d(seg) rows
+    for (int i = 0; i < vp.nseg && seg_grads; ++i)
+        if (seg_grads[i].proj_w && ragged_rows(const_cast<float*>(segs[i].feat), fptr(scratch, RS.featp[i]), tab, rseg, B, segs[i].T, segs[i].d_in, i, 1, st))
+            return 1;
+    // every dense weight gradient (dW_o, dW_in per layer, dW_proj per segment) as small_dw tiles, then ONE fixed-order launch sums them, the
+    // FFN slabs and the partial rows (tail_reduce: no float atomics, bit-identical run to run)
+    uint64_t* adv = (cfg->advance_seed == 2 && cfg->seed_ptr && training) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
+    SmallDwParams sp;
+    memset(&sp, 0, sizeof(sp));
+    bool first = true;
+    auto flush = [&]() -> int {
+        if (sp.n && small_dw(sp, comp, st, (char*)scratch + SC.sdw_tiles, SC.sdw_bytes, nullptr, false)) return 1;
+        const int rc = (sp.n || first) ? tail_reduce(sp.n ? &sp : nullptr, first ? &red : nullptr, first ? &rpp : nullptr, first ? adv : nullptr, nullptr, st) : 0;
+        first = false;
+        memset(&sp, 0, sizeof(sp));
+        return rc;
+    };
+    auto add = [&](const float* G, int ldg, const float* X, int ldx, float* out, int R, int Cc, int K) -> int {
+        if (!out || K <= 0) return 0;
+        if (sp.n == SMALL_DW_MAX && flush()) return 1;
+        SmallDwProblem& q = sp.pr[sp.n++];
+        q.G = G; q.X = X; q.out = out; q.R = R; q.C = Cc; q.K = K; q.ldg = ldg; q.ldx = ldx;
+        return 0;
+    };
+    for (int l = 0; l < L; ++l) {
+        const egx_layer_grads& gw = layer_grads[l];
+        if (add(bp.layer[l].g1_out, d, bp.layer[l].attn_o_out, d, gw.out_proj_w, d, d, N)) return 1;
+        if (add(bp.layer[l].dqkv_out, 3 * d, bp.layer[l].x_in_out, d, gw.in_proj_w, 3 * d, d, N)) return 1;
+    }
+    for (int i = 0; i < vp.nseg && seg_grads; ++i)
+        if (add(bp.dseg_out[i], d, fptr(scratch, RS.featp[i]), segs[i].d_in, seg_grads[i].proj_w, d, segs[i].d_in, (int)rp.seg_rows[i])) return 1;
+    if (flush()) return 1;
+    // d(feature) (unfrozen backbones): packed d(seg) W_proj, then scattered to the padded tensor with its padded frames zeroed
+    for (int i = 0; i < vp.nseg && seg_grads; ++i) {
+        if (!seg_grads[i].feat) continue;
+        float* dfp = fptr(scratch, RS.dfeat);
+        if (linear_dx(bp.dseg_out[i], segs[i].proj_w, dfp, (int)rp.seg_rows[i], d, segs[i].d_in, nullptr, 1.f, nullptr, comp, st)) return 1;
+        if (ragged_rows(seg_grads[i].feat, dfp, tab, rseg, B, segs[i].T, segs[i].d_in, i, 0, st)) return 1;
+    }
     return 0;
 }
 

@@ -236,6 +236,10 @@ struct FusedBwdParams {
     // egx_token_ce: d tokens = g * d_logits W rebuilt per clip, the clip's partial d W / d b rows in the head section of the partial row (head_off)
     const float* tce_W; const float* tce_dlogits; int tce_C;
     TouchList touch;        // weight streams of a later launch to bring into the Infinity Cache (see TouchList)
+    // ---- ragged batches (egx_ragged_bwd): non-null = the tiled launches run the RAGGED instantiation, which takes its tile's clip, first
+    // token, segment pieces and upstream-gradient rows from the batch table (RAGGED_REC) and writes d(seg) rows PACKED: segment k of clip b
+    // at rows [rseg[b * FUSED_MAX_SEG + k], + T_{b,k}) of dseg_out[k]
+    const int* rtab; int B_clips; const int* rseg;
 };
 int fused_backward(const FusedBwdParams& p, int compute, hipStream_t st);
 // cut mode (ffn_cut.hip): the FFN of layer l as launches of their own, eight waves per clip
@@ -310,6 +314,10 @@ static_assert(RG_OFF + FUSED_MAX_SEG <= RAGGED_REC, "ragged clip record");
 // n host words -> dst (device) on the stream, carried in the kernel arguments of one small launch per 960 words: the data is captured when
 // the launch is enqueued, so the host copy may go away at once (the ragged batch table)
 int upload_words(int* dst, const int* src, size_t n, hipStream_t st);
+// ragged training (egx_ragged_bwd), segment k of a padded (B, T_pad, C) fp32 tensor against its packed rows (clip b's frames at rows
+// [rseg[b * FUSED_MAX_SEG + k], + T_{b,k}), T_{b,k} from the batch table): to_packed = 1 copies the valid frames into the packed rows,
+// 0 writes the packed rows back to the padded tensor and zeroes its padded frames. C % 4 == 0.
+int ragged_rows(float* padded, float* packed, const int* rtab, const int* rseg, int B, int T_pad, int C, int k, int to_packed, hipStream_t st);
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st);
 int tiled_attn_bwd(const TiledAttnParams& p, int compute, hipStream_t st);
 

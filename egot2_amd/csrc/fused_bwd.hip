@@ -1445,9 +1445,12 @@ int debug_read_bstamps(unsigned long long* out, int n) {
 // l_back, leaving d(attention output) and the residual gradient in HBM], or ends with the token-preparation backward.
 // CUT (round 5, ffn_cut.hip): the launch runs LayerNorm1 backward .. the in-projection input gradient of layer p.cut_layer on the dy1 rows
 // ffn_bwd_kernel left, and leaves d(layer input) in p.dxin for the layer below — or, for layer 0, runs on into the token-preparation backward.
-template <int CM, bool TILED, int DH, bool SLICED = false, bool CUT = false>      // SLICED: see fused_fwd_kernel
+// RAGGED (egx_ragged_bwd): the tiled launches over clips of their own lengths; the tile's clip, first token, segment pieces and the rows
+// of the upstream gradient come from the batch table (FusedBwdParams::rtab), d(seg) leaves packed (FusedBwdParams::rseg).
+template <int CM, bool TILED, int DH, bool SLICED = false, bool CUT = false, bool RAGGED = false>      // SLICED: see fused_fwd_kernel
 __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
     static_assert(!(TILED && SLICED), "the tiled launches are not sliced");
+    static_assert(!RAGGED || TILED, "ragged batches run the tiled launches");
     static_assert(!(CUT && (TILED || SLICED)), "the cut launches are neither tiled nor sliced");
     constexpr int HPW = FDH / DH, NHEAD = FH * HPW, NCT = DH / 16;      // heads per wave, heads, 16-channel tiles per head
     constexpr int NT = 3;
@@ -1471,7 +1474,14 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
     const int n_slices = SLICED ? p.n_slices : 1;
     int S, c_real, t0;
     size_t tok0;                            // global index of the first token (row of the dense arrays, dropout row key)
-    if constexpr (TILED) {
+    const int* rrec = nullptr;              // RAGGED: the clip's record of the batch table
+    if constexpr (RAGGED) {
+        c_real = p.rtab[(size_t)p.B_clips * RAGGED_REC + clip];
+        rrec = p.rtab + (size_t)c_real * RAGGED_REC;
+        t0 = (clip - rrec[RG_TILE0]) * 48;
+        S = min(48, rrec[RG_S] - t0);
+        tok0 = (size_t)rrec[RG_TOK0] + t0;
+    } else if constexpr (TILED) {
         c_real = clip / p.tpc;
         t0 = (clip - c_real * p.tpc) * 48;
         S = min(48, p.S_clip - t0);
@@ -1633,7 +1643,7 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
                 float g0 = d0 * lw.x, g1 = d1 * lw.y;
                 float s1 = wsum(g0 + g1) * (1.f / FD);
                 float s2 = wsum(g0 * xh0 + g1 * xh1) * (1.f / FD);
-                float inv_s = 1.f / (float)p.S_clip;
+                float inv_s = 1.f / (float)(RAGGED ? rrec[RG_S] : p.S_clip);
                 *reinterpret_cast<float2*>(pooled + 128 + 2 * lane) =
                     make_float2(rstd * (g0 - s1 - xh0 * s2) * inv_s, rstd * (g1 - s1 - xh1 * s2) * inv_s);
             }
@@ -1644,6 +1654,14 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
             }
             __syncthreads();
             pooled[tid] = 0.f;
+        } else if constexpr (RAGGED) {
+            // the clip's rows [0, out_n) carry an upstream gradient, at rows out0 + row of d_tokens (head-less: the first segment, packed)
+            const int n_up = min(S, rrec[RG_OUTN] - t0);
+            const size_t up0 = (size_t)rrec[RG_OUT0] + t0;
+            for (int i = tid; i < n_up * (FD / 4); i += 256) {
+                int row = i >> 5, c = (i & 31) << 2;
+                *reinterpret_cast<float4*>(Gs + row * LDX + c) = *reinterpret_cast<const float4*>(p.d_tokens + (up0 + row) * FD + c);
+            }
         } else {
             for (int i = tid; i < S * (FD / 4); i += 256) {
                 int row = i >> 5, c = (i & 31) << 2;
@@ -2553,7 +2571,7 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
             [&](int row, int c0, float (&dy)[32], float (&dx)[32], float (&dyx)[32]) {
                 store32(Gs + row * LDX + c0, dy);
                 store32(B3 + row * LDX + c0, dyx);
-                if (p.feat_thresh) {        // d(projection output) = d(LayerNorm input) .* feature-dropout mask (the forward's keying)
+                if (!RAGGED && p.feat_thresh) {        // d(projection output) = d(LayerNorm input) .* feature-dropout mask (the forward's keying)
 #pragma unroll
                     for (int si = 0; si < FUSED_MAX_SEG; ++si)
                         if (si < p.nseg && t0 + row >= p.seg[si].off && t0 + row < p.seg[si].off + p.seg[si].T) {
@@ -2572,9 +2590,10 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
 #pragma unroll
         for (int si = 0; si < FUSED_MAX_SEG; ++si)
             if (si < p.nseg) {
-                int r0 = p.seg[si].off - t0, r1 = r0 + p.seg[si].T;        // the segment's rows within this tile
+                const int soff = RAGGED ? rrec[RG_OFF + si] : p.seg[si].off, sT = RAGGED ? rrec[RG_T + si] : p.seg[si].T;
+                int r0 = soff - t0, r1 = r0 + sT;        // the segment's rows within this tile
                 const int lo = max(r0, 0), hi = min(r1, S);
-                float* dst = p.dseg_out[si] + ((size_t)c_real * p.seg[si].T + (lo - r0)) * FD;
+                float* dst = p.dseg_out[si] + ((RAGGED ? (size_t)p.rseg[(size_t)c_real * FUSED_MAX_SEG + si] : (size_t)c_real * sT) + (lo - r0)) * FD;
                 for (int i = tid; i < (hi - lo) * (FD / 4); i += 256) {
                     const int row = lo + (i >> 5), c4 = i & 31;
                     *reinterpret_cast<float4*>(dst + (size_t)i * 4) = *reinterpret_cast<const float4*>(B1 + row * LDX + c4 * 4);
@@ -2584,7 +2603,7 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
         if (tid < 128) pg[tid] = colsum_lds(B3, 0, S, tid);
         else pg[128 + (tid - 128)] = colsum_lds(Gs, 0, S, tid - 128);
         for (int si = 0; si < p.nseg; ++si) {
-            int r0 = p.seg[si].off - t0, r1 = r0 + p.seg[si].T;      // the segment's rows within this tile (empty ranges sum to zero)
+            int r0 = (RAGGED ? rrec[RG_OFF + si] : p.seg[si].off) - t0, r1 = r0 + (RAGGED ? rrec[RG_T + si] : p.seg[si].T);      // the segment's rows within this tile (empty ranges sum to zero)
             r0 = max(r0, 0); r1 = min(r1, S);
             if (tid < 128) pg[256 + si * 256 + tid] = colsum_lds(Gs, r0, r1, tid);
             else pg[256 + si * 256 + 128 + (tid - 128)] = colsum_lds(B1, r0, r1, tid - 128);
@@ -2644,10 +2663,29 @@ static int launch_bwd(const FusedBwdParams& p, hipStream_t st) {
     return 0;
 }
 
+// ragged batches (egx_ragged_bwd): the tiled launches with the batch table
+template <int CM>
+static int launch_bwd_ragged(const FusedBwdParams& p, hipStream_t st) {
+    EGX_CHECK(p.S == 48 && p.rtab && p.rseg, "fused backward: ragged launch needs S = 48 and the batch table");
+    const size_t lds = (size_t)(6 * 48 * LDX + FH * 3 * 48 + 2 * FD) * sizeof(float);
+    static bool attr_set = false;
+    if (!attr_set) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_bwd_kernel<CM, true, 32, false, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    timing_begin(TIMER_FUSED_BWD, st);
+    hipLaunchKernelGGL((fused_bwd_kernel<CM, true, 32, false, false, true>), dim3(p.B), dim3(256), lds, st, p);
+    timing_end(TIMER_FUSED_BWD, st);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int fused_backward(const FusedBwdParams& p, int compute, hipStream_t st) {
     EGX_CHECK(p.S <= 48, "fused backward: S=%d > 48", p.S);
     if (p.tiled) {
         EGX_CHECK(compute == CM_BF16 || compute == CM_SPLIT, "tiled mode: compute must be bf16 or f32s");
+        if (p.rtab) return compute == CM_BF16 ? launch_bwd_ragged<CM_BF16>(p, st) : launch_bwd_ragged<CM_SPLIT>(p, st);
         return compute == CM_BF16 ? launch_bwd<CM_BF16, true, 32>(p, st) : launch_bwd<CM_SPLIT, true, 32>(p, st);
     }
     if (p.n_heads == 2 * FH)

@@ -564,6 +564,31 @@ int pool_head_ragged_fwd(const float* tokens, const int* rtab, int B, int d, con
     return 0;
 }
 
+// ragged training (egx_ragged_bwd): padded (B, T_pad, C) <-> packed rows of segment k (fused.h ragged_rows). One float4 per thread and
+// step; the padded tensor's frames t >= T_{b,k} are never read (to_packed) or written with zeros (!to_packed).
+__global__ __launch_bounds__(256) void ragged_rows_kernel(float* __restrict__ padded, float* __restrict__ packed, const int* __restrict__ rtab,
+                                                          const int* __restrict__ rseg, int T_pad, int C4, int k, int to_packed, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / C4;
+        const int c4 = (int)(i - row * C4), b = (int)(row / T_pad), t = (int)(row - (size_t)b * T_pad);
+        const int T = rtab[(size_t)b * RAGGED_REC + RG_T + k];
+        float4* pd = reinterpret_cast<float4*>(padded) + i;
+        float4* pk = reinterpret_cast<float4*>(packed) + ((size_t)rseg[(size_t)b * FUSED_MAX_SEG + k] + t) * C4 + c4;
+        if (to_packed) { if (t < T) *pk = *pd; }
+        else *pd = t < T ? *pk : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+int ragged_rows(float* padded, float* packed, const int* rtab, const int* rseg, int B, int T_pad, int C, int k, int to_packed, hipStream_t st) {
+    EGX_CHECK(C % 4 == 0 && B > 0 && T_pad > 0 && k >= 0 && k < FUSED_MAX_SEG, "ragged_rows: C=%d, B=%d, T_pad=%d, k=%d", C, B, T_pad, k);
+    const size_t n4 = (size_t)B * T_pad * (C / 4);
+    const size_t blocks = (n4 + 255) / 256;
+    hipLaunchKernelGGL(ragged_rows_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, padded, packed, rtab, rseg, T_pad, C / 4,
+                       k, to_packed, n4);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int pool_head_bwd(const float* d_out, const float* pooled, int B, int S, int d, const float* ln_w,
                   const float* ln_b, float eps, const float* W, int n_out, float* d_tokens, float* d_ln_w,
                   float* d_ln_b, float* d_W, float* d_b, hipStream_t st) {

@@ -213,7 +213,8 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_fwd_planes_kernel(T
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     bool kp[4] = {true, true, true, true};
-                    if (p.drop_thresh) drop_keep4(dkey, (uint32_t)(bh * S + query[t]), (uint32_t)((key0 >> 2) + j * 4 + q), p.drop_thresh, kp);
+                    if (p.drop_thresh) drop_keep4(dkey, RAGGED ? (uint32_t)((size_t)rrec[RG_TOK0] * FH + (size_t)h * S + query[t]) : (uint32_t)(bh * S + query[t]),
+                                                  (uint32_t)((key0 >> 2) + j * 4 + q), p.drop_thresh, kp);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float pv = __builtin_amdgcn_exp2f(sc[t][j][e] - mn);
@@ -249,18 +250,24 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_fwd_planes_kernel(T
     }
 }
 
-template <int CM>
+// RAGGED (egx_ragged_bwd): as tiled_attn_fwd_planes_kernel<CM, true>: clip b's S_b, tile and token rows from the batch table; its
+// log-sum-exp / delta rows and the dropout rows start at 4 tok0_b + h S_b
+template <int CM, bool RAGGED = false>
 __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dq_planes_kernel(TiledAttnParams p, int CH) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
-    unsigned short* Kp = reinterpret_cast<unsigned short*>(lds);
-    unsigned short* Vp = Kp + TP_OP;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4, nw = blockDim.x >> 6;
     const int bh = blockIdx.x, b = bh >> 2, h = bh & 3;
-    const float* base = p.qkv + (size_t)b * p.tpc * 48 * (3 * FD) + h * FDH;
+    const int* rrec = RAGGED ? p.rtab + (size_t)b * RAGGED_REC : nullptr;
+    const int S = RAGGED ? rrec[RG_S] : p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
+    const size_t tb = RAGGED ? (size_t)rrec[RG_TOK0] : (size_t)b * S;                   // token row of query 0
+    const size_t lb = RAGGED ? (size_t)rrec[RG_TOK0] * FH + (size_t)h * S : (size_t)bh * S;      // lse / delta / dropout row of query 0
+    unsigned short* Kp = reinterpret_cast<unsigned short*>(lds);
+    unsigned short* Vp = Kp + TP_OP;
+    const float* base = p.qkv + (RAGGED ? (size_t)rrec[RG_TILE0] : (size_t)b * p.tpc) * 48 * (3 * FD) + h * FDH;
     const float vscale = p.drop_thresh ? p.drop_inv : 1.f;
     const uint64_t dkey = attn_key(p);
     const int nqt = (S + 15) >> 4, ngrp = (nqt + TA_G - 1) / TA_G;
+    if constexpr (RAGGED) { if ((int)blockIdx.y * nw >= ngrp) return; }     // (whole workgroup: before any barrier)
     const int g = blockIdx.y * nw + wave;
     const bool active = g < ngrp;
     int query[TA_G];
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dq_planes_kernel(Ti
     for (int t = 0; t < TA_G; ++t) {
         query[t] = (g * TA_G + t) * 16 + r;
         const int qrow = query[t] < S ? query[t] : S - 1;
-        const size_t tok = (size_t)b * S + qrow;
+        const size_t tok = tb + qrow;
         bq[t] = load_frag_scaled<CM>(base + (size_t)qrow * (3 * FD), q, TA_C2);
         const float* dop = p.d_o + tok * FD + h * FDH;
         const float* op = p.attn_o + tok * FD + h * FDH;
@@ -282,8 +289,8 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dq_planes_kernel(Ti
         dl += __shfl_xor(dl, 32, 64);
         delta[t] = dl;
         bdo[t] = make_frag<CM>(d0, d1);
-        L[t] = p.lse[(size_t)bh * S + qrow];
-        if (active && q == 0 && query[t] < S) p.delta[(size_t)bh * S + query[t]] = dl;
+        L[t] = p.lse[lb + qrow];
+        if (active && q == 0 && query[t] < S) p.delta[lb + query[t]] = dl;
         dq[t][0] = f32x4{0, 0, 0, 0}; dq[t][1] = f32x4{0, 0, 0, 0};
     }
     for (int c0 = 0; c0 < SKP; c0 += CH) {
@@ -307,7 +314,7 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dq_planes_kernel(Ti
                     mma<CM>(st, ak, bq[t]);         // S^T = K Q^T
                     mma<CM>(dp, av, bdo[t]);        // dP^T = V dO^T
                     bool kp[4] = {true, true, true, true};
-                    if (p.drop_thresh) drop_keep4(dkey, (uint32_t)(bh * S + query[t]), (uint32_t)((key0 >> 2) + j * 4 + q), p.drop_thresh, kp);
+                    if (p.drop_thresh) drop_keep4(dkey, (uint32_t)(lb + query[t]), (uint32_t)((key0 >> 2) + j * 4 + q), p.drop_thresh, kp);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float pv = __builtin_amdgcn_exp2f(st[e] - L[t]);
@@ -339,26 +346,30 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dq_planes_kernel(Ti
 #pragma unroll
     for (int t = 0; t < TA_G; ++t)
         if (query[t] < S) {
-            float* o = p.dqkv + ((size_t)b * S + query[t]) * (3 * FD) + h * FDH + 4 * q;
+            float* o = p.dqkv + (tb + query[t]) * (3 * FD) + h * FDH + 4 * q;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) *reinterpret_cast<f32x4*>(o + ct * 16) = dq[t][ct] * TA_SCALE;
         }
 }
 
-template <int CM>
+template <int CM, bool RAGGED = false>       // RAGGED: see tiled_attn_dq_planes_kernel
 __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dkv_planes_kernel(TiledAttnParams p, int CH) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4, nw = blockDim.x >> 6;
+    const int bh = blockIdx.x, b = bh >> 2, h = bh & 3;
+    const int* rrec = RAGGED ? p.rtab + (size_t)b * RAGGED_REC : nullptr;
+    const int S = RAGGED ? rrec[RG_S] : p.S, SKP = (S + 31) & ~31, PS = CH * TP_LD;
+    const size_t tb = RAGGED ? (size_t)rrec[RG_TOK0] : (size_t)b * S;
+    const size_t lb = RAGGED ? (size_t)rrec[RG_TOK0] * FH + (size_t)h * S : (size_t)bh * S;
     unsigned short* Qp = reinterpret_cast<unsigned short*>(lds);
     unsigned short* Op = Qp + TP_OP;                    // dO rows (x 1 / (1 - p))
     float* Ls = reinterpret_cast<float*>(Qp + Npl<CM>::v * PS);       // [CH] lse
     float* Ds = Ls + CH;                                              // [CH] delta
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4, nw = blockDim.x >> 6;
-    const int bh = blockIdx.x, b = bh >> 2, h = bh & 3;
-    const float* base = p.qkv + (size_t)b * p.tpc * 48 * (3 * FD) + h * FDH;
+    const float* base = p.qkv + (RAGGED ? (size_t)rrec[RG_TILE0] : (size_t)b * p.tpc) * 48 * (3 * FD) + h * FDH;
     const float oscale = p.drop_thresh ? p.drop_inv : 1.f;
     const uint64_t dkey = attn_key(p);
     const int nkt = (S + 15) >> 4, ngrp = (nkt + TA_G - 1) / TA_G;
+    if constexpr (RAGGED) { if ((int)blockIdx.y * nw >= ngrp) return; }     // (whole workgroup: before any barrier)
     const int g = blockIdx.y * nw + wave;
     const bool active = g < ngrp;
     int key[TA_G];
@@ -376,10 +387,10 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dkv_planes_kernel(T
         const int rows = min(CH, SKP - c0);
         if (c0) __syncthreads();
         stage_planes<CM>(Qp, PS, base, 3 * FD, c0, rows, S);
-        stage_planes<CM>(Op, PS, p.d_o + (size_t)b * S * FD + h * FDH, FD, c0, rows, S, oscale);
+        stage_planes<CM>(Op, PS, p.d_o + tb * FD + h * FDH, FD, c0, rows, S, oscale);
         for (int i = tid; i < rows; i += blockDim.x) {
-            Ls[i] = c0 + i < S ? p.lse[(size_t)bh * S + c0 + i] : 0.f;
-            Ds[i] = c0 + i < S ? p.delta[(size_t)bh * S + c0 + i] : 0.f;
+            Ls[i] = c0 + i < S ? p.lse[lb + c0 + i] : 0.f;
+            Ds[i] = c0 + i < S ? p.delta[lb + c0 + i] : 0.f;
         }
         __syncthreads();
         if (!active) continue;
@@ -402,7 +413,7 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dkv_planes_kernel(T
                     // dropout mask: the lane's four elements are four QUERIES (mask rows) of one key: one hash per lane and tile, exchanged
                     // inside the quad (common.h tile_keep_rows) instead of four
                     uint32_t m4[4] = {0xFu, 0xFu, 0xFu, 0xFu};
-                    if (p.drop_thresh) tile_keep_rows(dkey, (uint32_t)(bh * S + c0 + qt * 16), (uint32_t)((g * TA_G + t) * 4), r, q, p.drop_thresh, m4);
+                    if (p.drop_thresh) tile_keep_rows(dkey, (uint32_t)(lb + c0 + qt * 16), (uint32_t)((g * TA_G + t) * 4), r, q, p.drop_thresh, m4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int query = c0 + qt * 16 + 4 * q + e;
@@ -433,7 +444,7 @@ __global__ __launch_bounds__(TA_MAX_THREADS) void tiled_attn_dkv_planes_kernel(T
 #pragma unroll
     for (int t = 0; t < TA_G; ++t)
         if (key[t] < S) {
-            float* o = p.dqkv + ((size_t)b * S + key[t]) * (3 * FD) + FD + h * FDH + 4 * q;
+            float* o = p.dqkv + (tb + key[t]) * (3 * FD) + FD + h * FDH + 4 * q;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
                 *reinterpret_cast<f32x4*>(o + ct * 16) = dk[t][ct] * TA_SCALE;
@@ -519,6 +530,27 @@ int dispatch_ragged_fwd(const TiledAttnParams& p, hipStream_t st) {
     return 0;
 }
 
+template <int CM>
+int dispatch_ragged_bwd(const TiledAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.S >= 1 && p.S <= TILED_MAX_S && p.rtab, "tiled attention (ragged): longest S=%d (1 .. %d), batch table set", p.S, TILED_MAX_S);
+    static bool once = false;
+    if (!once) {
+        if (set_lds(&tiled_attn_dq_planes_kernel<CM, true>, 158 * 1024) || set_lds(&tiled_attn_dkv_planes_kernel<CM, true>, 158 * 1024)) return 1;
+        once = true;
+    }
+    const int SKP = (p.S + 31) & ~31, CH = planes_chunk_rows<CM>(SKP);
+    const int ngrp = ((p.S + 15) / 16 + TA_G - 1) / TA_G;
+    int nw = 8;
+    (void)range_split(p.B, ngrp, &nw);
+    const dim3 grid(p.B * FH, (ngrp + nw - 1) / nw), block(nw * 64);
+    const size_t lds_a = (size_t)Npl<CM>::v * CH * TP_LD * 2, lds_b = lds_a + (size_t)2 * CH * sizeof(float);
+    hipLaunchKernelGGL((tiled_attn_dq_planes_kernel<CM, true>), grid, block, lds_a, st, p, CH);
+    EGX_LAUNCH_CHECK();
+    hipLaunchKernelGGL((tiled_attn_dkv_planes_kernel<CM, true>), grid, block, lds_b, st, p, CH);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st) {
     EGX_CHECK(compute == CM_BF16 || compute == CM_SPLIT, "tiled attention: compute must be bf16 or f32s");
     timing_begin(TIMER_WIDE_ATTN_FWD, st);
@@ -530,7 +562,8 @@ int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st) {
 int tiled_attn_bwd(const TiledAttnParams& p, int compute, hipStream_t st) {
     EGX_CHECK(compute == CM_BF16 || compute == CM_SPLIT, "tiled attention: compute must be bf16 or f32s");
     timing_begin(TIMER_WIDE_ATTN_BWD, st);
-    int rc = compute == CM_BF16 ? dispatch_planes<CM_BF16>(p, true, st) : dispatch_planes<CM_SPLIT>(p, true, st);
+    int rc = p.rtab ? (compute == CM_BF16 ? dispatch_ragged_bwd<CM_BF16>(p, st) : dispatch_ragged_bwd<CM_SPLIT>(p, st))
+                    : (compute == CM_BF16 ? dispatch_planes<CM_BF16>(p, true, st) : dispatch_planes<CM_SPLIT>(p, true, st));
     timing_end(TIMER_WIDE_ATTN_BWD, st);
     return rc;
 }

@@ -92,6 +92,19 @@ class TaskFusionMFTransformer3Task(TaskFusion3Task, TranslatorMixin):
         N, D = asd_out.shape[0], asd_out.shape[1]
         return tokens.reshape(N * D, -1)
 
+    def forward_features_ragged(self, ttm_out, lam_out, asd_out, lengths):
+        """A batch of clips of their own lengths, differentiable (training and evaluation): features padded to (B, T_max, 256) (padded
+        frames are never read), lengths (B,) or (B, 3) frame counts in argument order (ttm, lam, asd). -> (sum_b T_asd_b, d): the per-frame
+        rows of every clip packed in clip order, each clip's those of the clip alone (functional.encoder_ragged_train). The caller applies
+        lossAV.forward(rows, labels) with the labels packed the same way."""
+        feats = [asd_out, ttm_out, lam_out]
+        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0)
+                for f, k in zip(feats, (2, 0, 1))]
+        lens = F_egx.ragged_lengths(lengths, asd_out.shape[0], [f.shape[1] for f in feats], order=(2, 0, 1))
+        return self._egx_train_ragged(feats, segs, lens, encoder=self.transformer_encoder, ln=self.ln,
+                                      projs=[self.proj_asd, self.proj_ttm, self.proj_lam], task_embed=self.task_embed,
+                                      pos_table=self.pos_embed.pe, p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p)
+
     def forward(self, video, video_asd, audio, audio_asd):
         with torch.no_grad():
             N, D, H, W = video_asd.shape

@@ -77,6 +77,17 @@ class _TTMTranslator(TaskFusion3Task, TranslatorMixin):
                                 task_embed=self.task_embed, pos_table=self.pos_embed.pe,
                                 p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p, head=head, ce=ce, lengths=lengths)
 
+    def _ragged(self, feats, projs, task_ids, lengths, target, class_weight):
+        if class_weight is not None and target is None:
+            raise ValueError("class_weight goes with target=")
+        B = feats[0].shape[0]
+        lens = F_egx.ragged_lengths(lengths, B, [f.shape[1] for f in feats])
+        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, task_ids)]
+        return self._egx_train_ragged(feats, segs, lens, encoder=self.transformer_encoder, ln=self.ln, projs=projs,
+                                      task_embed=self.task_embed, pos_table=self.pos_embed.pe, p_drop=self.dp_rate,
+                                      p_pos=self.pos_embed.dropout.p, head=(self.linear_head[0], self.linear_head[1]),
+                                      ce=None if target is None else (target, class_weight))
+
     def _head(self, tokens):
         ln, fc = self.linear_head[0], self.linear_head[1]
         return F_egx.pool_head(tokens, ln.weight, ln.bias, fc.weight, fc.bias, ln.eps)
@@ -104,6 +115,13 @@ class TaskFusionMFTransformer2Task(_TTMTranslator):
             raise ValueError("ragged batches are inference-only: no fused loss (target=); apply the loss to the returned logits")
         return self._tokens([ttm_out, lam_out], [self.proj_ttm, self.proj_lam], [0, 1], with_head=True,
                             ce=None if target is None else (target, class_weight), lengths=lengths)
+
+    def forward_features_ragged(self, ttm_out, lam_out, lengths, target=None, class_weight=None):
+        """A batch of clips of their own lengths, differentiable (training and evaluation): features padded to (B, T_max, 256) (padded
+        frames are never read), lengths (B,) or (B, 2) frame counts in argument order (ttm, lam). -> (B, 2) logits, each clip's those of the
+        clip alone with all of its frames; with target (B,) int64 [, class_weight (2,)] -> (logits, loss), the weighted cross entropy over
+        the batch (functional.encoder_ragged_train)."""
+        return self._ragged([ttm_out, lam_out], [self.proj_ttm, self.proj_lam], [0, 1], lengths, target, class_weight)
 
     def forward(self, video, audio):
         lam_out = self.lam_model(video, middle=True)  # (bs, T, 256)
@@ -134,6 +152,14 @@ class TaskFusionMFTransformer3Task(_TTMTranslator):
             raise ValueError("ragged batches are inference-only: no fused loss (target=); apply the loss to the returned logits")
         return self._tokens([ttm_out, lam_out, asd_out], [self.proj_ttm, self.proj_lam, self.proj_asd], [0, 1, 2],
                             with_head=True, ce=None if target is None else (target, class_weight), lengths=lengths)
+
+    def forward_features_ragged(self, ttm_out, lam_out, asd_out, lengths, target=None, class_weight=None):
+        """A batch of clips of their own lengths, differentiable (training and evaluation): features padded to (B, T_max, 256) (padded
+        frames are never read), lengths (B,) or (B, 3) frame counts in argument order (ttm, lam, asd). -> (B, 2) logits, each clip's those
+        of the clip alone with all of its frames; with target (B,) int64 [, class_weight (2,)] -> (logits, loss), the weighted cross
+        entropy over the batch (functional.encoder_ragged_train)."""
+        return self._ragged([ttm_out, lam_out, asd_out], [self.proj_ttm, self.proj_lam, self.proj_asd], [0, 1, 2], lengths, target,
+                            class_weight)
 
     def forward(self, video, video_asd, audio, audio_asd):
         N, D, H, W = video_asd.shape

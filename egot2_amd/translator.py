@@ -180,3 +180,29 @@ class TranslatorMixin:
         head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
         return F_egx.encoder_ragged(spec, list(feats), lens, task_embed, pos_table, ln.weight, ln.bias, proj_t,
                                     encoder_layer_tensors(encoder), head_t)
+
+    def _egx_train_ragged(self, feats, segments, lengths, *, encoder, ln, projs, task_embed, pos_table, p_drop, p_pos=0.0, head=None,
+                          ce=None):
+        """Ragged batch through the differentiable path (functional.encoder_ragged_train), in train and eval mode, with and without grad.
+        `lengths`: (B, K) int32 host tensor in SEGMENT order (functional.ragged_lengths)."""
+        if self.egx_defer_small:
+            raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
+        if ce is not None and head is None:
+            raise ValueError("the fused cross entropy needs the pooled head")
+        layer0 = encoder.layers[0]
+        seed_dev = getattr(self, "_egx_seed_dev", None)
+        training = bool(self.training)
+        spec = EncoderSpec(d_model=ln.normalized_shape[0], n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
+                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps, compute=self.egx_compute, impl=self.egx_impl,
+                           p_drop=p_drop, p_pos=p_pos, training=training, seed=self._egx_seed() if training else 0,
+                           seed_ptr=seed_dev.data_ptr() if seed_dev is not None else 0,
+                           advance_seed=1 if (seed_dev is not None and training) else 0,     # fresh masks per call
+                           head_n_out=head[1].out_features if head is not None else 0,
+                           deterministic=bool(self.egx_deterministic), ce=ce is not None)
+        proj_t = []
+        for s, p in zip(segments, projs):
+            if s.has_proj:
+                proj_t += [p.weight, p.bias]
+        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        return F_egx.encoder_ragged_train(spec, list(feats), lengths, task_embed, pos_table, ln.weight, ln.bias, proj_t,
+                                          encoder_layer_tensors(encoder), head_t, ce=ce)

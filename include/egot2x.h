@@ -342,6 +342,32 @@ int egx_ragged_encode_workspace(const egx_config* cfg, const egx_segment* segs, 
 int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
                       const egx_layer* layers, int B, float* tokens_out, int out_layout, void* workspace, void* stream);
 
+/* ---- ABI v18: ragged batches for training (d = 128 TTM / ASD translators) ----
+ * One forward + backward over B clips of their own lengths, every clip keeping all of its frames: replaces the reference's sorted
+ * ~400-frame batches truncated to their shortest clip (HHI/dataset/ttm/sampler.py:14-60, HHI/utils/ttm/utils.py:232-241) in the TTM
+ * training step (HHI/tasks/ttm/video_task_2loader.py:30-36) and the ASD one (HHI/tasks/asd/video_task_taskspecific.py:26-37).
+ *   lengths, segs, head, logits_out, tokens_out   as egx_ragged_fwd (head NULL: the first segment's rows of every clip, packed).
+ *   training, seed, seed_ptr, advance_seed, deterministic, d_logits_scale, zero_buf, weight_cache   as egx_translator_fwd / _bwd.
+ *   dropout (training != 0): site_key(seed, layer, site) / rand_quad as the other paths; with tok0_b = sum_{b' < b} S_b' the row of token s
+ *              of clip b is tok0_b + s (POS, RES1, FFN, RES2; column = feature / hidden unit) and the ATTN row of (head h, query q) is
+ *              4 tok0_b + h S_b + q (column = key). Clips of equal S > 48 thus draw exactly the masks of the tiled training call.
+ *   ce         (with a head) the weighted cross entropy of the logits is appended to the forward (loss and d_logits as egx_translator_fwd).
+ *   egx_ragged_bwd takes the SAME lengths and the forward's `saved`; d_logits (B, n_out) with a head, else d_tokens in the packed output
+ *              shape (the other segments' rows get no upstream gradient). Gradients follow egx_translator_bwd; seg_grads[k].feat (optional)
+ *              is WRITTEN as the padded (B, segs[k].T, d_in) gradient with exact zeros in the padded frames; pos gradients are refused.
+ * Runs on the tiled kernels, limits of egx_ragged_fwd; refused: p_feat > 0, out_tokens, token_ce, bucket_cb, bwd_stage != 0.
+ * `saved` / `scratch`: egx_ragged_train_workspace() bytes (functions of sum_b S_b and the tile count, not of B * max S_b). Each call
+ * writes the batch table on `stream`: not for graph capture. */
+int egx_ragged_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
+                               size_t* scratch_bytes);
+int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                         const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* saved,
+                         void* scratch, int training, uint64_t seed, void* stream);
+int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                   const egx_layer* layers, const egx_head* head, int B, const float* d_logits, const float* d_tokens, const void* saved,
+                   void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads,
+                   const egx_head_grads* head_grads, int training, uint64_t seed, void* stream);
+
 /* pooled = mean_s tokens[b, s, :]; y = ln_w ? LN(pooled) : pooled; out = W ? y W^T + b : y.
  * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL. */
 int egx_pool_head_fwd(const float* tokens, int B, int S, int d,
