@@ -145,7 +145,7 @@ static size_t fused_act_bytes(const Plan& pl) { return fused_res_bytes(pl) + ali
 // backward): per segment the projection, per layer each matrix in both orientations.
 struct FusedPackLayout {
     void* proj[EGX_MAX_SEGMENTS];
-    struct { void* in_w; void* in_wt; void* out_w; void* out_wt; void* lin1_w; void* lin1_wt; void* lin2_w; void* lin2_wt; } layer[FUSED_MAX_LAYERS];
+    struct Layer { void* in_w; void* in_wt; void* out_w; void* out_wt; void* lin1_w; void* lin1_wt; void* lin2_w; void* lin2_wt; } layer[FUSED_MAX_LAYERS];
     size_t bytes;
 };
 static FusedPackLayout fused_pack_layout(const egx_config* cfg, const egx_segment* segs, const Plan& pl, char* base) {
@@ -430,6 +430,56 @@ static Drop make_drop(int training, float p, uint64_t seed, uint32_t layer, uint
     return dr;
 }
 
+// ---- parameters of the clip / tile kernels, shared by the uniform calls (encoder_fwd_impl / encoder_bwd_impl) and the ragged ones -------
+// The descriptor list of the packing launch: a weight-cache hit (egx_config.weight_cache_valid) packs nothing, the copy is in place.
+struct Packer {
+    PackParams& pk;
+    bool cache_hit;
+    const void* operator()(const float* src, void* dst, int R, int K, int ld, int transpose, float scale = 1.f) {
+        if (cache_hit) return dst;
+        PackDesc& dsc = pk.d[pk.n++];
+        dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = K; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = scale;
+        return dst;
+    }
+};
+// segment i as both directions read it; the forward (proj_wp: its packed projection) reads the features and the projection too
+static void fill_seg(FusedSeg& fs, const egx_segment& s, int i, const void* proj_wp = nullptr) {
+    if (proj_wp) { fs.feat = s.feat; fs.proj_wp = proj_wp; fs.proj_b = s.proj_b; }
+    fs.add_vec = s.add_vec; fs.pos = s.pos; fs.T = s.T; fs.d_in = s.d_in; fs.pos_stride = s.pos_stride;
+    fs.Tfull = s.T; fs.seg_id = i;
+}
+// a forward layer: packed weights and their transposed copies for the backward kernels (also when a weight cache is filled: a later
+// backward reads them from there); the keep-scale of the FFN hidden dropout rides on the packed W1 (forward: relu(s (W1 x + b1)) =
+// s relu(W1 x + b1)) and W2^T (backward: dH = alive ? s W2^T g : 0): the FFN epilogues of the clip kernels have no multiply
+static void fill_layer(FusedLayer& fl, const egx_layer& w, const FusedPackLayout::Layer& P, int d, int dff, float ffn_scale, Packer& pack) {
+    fl.in_proj_wp = pack(w.in_proj_w, P.in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
+    fl.out_proj_wp = pack(w.out_proj_w, P.out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
+    fl.lin1_wp = pack(w.lin1_w, P.lin1_w, dff, d, d, 0, ffn_scale); fl.lin1_b = w.lin1_b;
+    fl.lin2_wp = pack(w.lin2_w, P.lin2_w, d, dff, dff, 0); fl.lin2_b = w.lin2_b;
+    pack(w.in_proj_w, P.in_wt, d, 3 * d, d, 1);
+    pack(w.out_proj_w, P.out_wt, d, d, d, 1);
+    pack(w.lin1_w, P.lin1_wt, d, dff, d, 1);
+    pack(w.lin2_w, P.lin2_wt, dff, d, dff, 1, ffn_scale);
+    fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+}
+// a backward layer's weights: the packed copies the forward left
+static void fill_bwd_layer(FusedBwdLayer& fl, const egx_layer& w, const FusedPackLayout::Layer& P) {
+    fl.in_proj_wp = P.in_w; fl.in_proj_wtp = P.in_wt; fl.out_proj_wtp = P.out_wt;
+    fl.lin1_wp = P.lin1_w; fl.lin2_wtp = P.lin2_wt; fl.lin1_wtp = P.lin1_wt;
+    fl.in_proj_b = w.in_proj_b; fl.lin1_b = w.lin1_b;
+    fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+}
+// the dropout sites of layer l (FusedLayer, FusedBwdLayer): one threshold and keep-scale, a key per site
+template <class LayerT>
+static void set_layer_drop(LayerT& fl, int training, float p, uint64_t seed, int l) {
+    const Drop da = make_drop(training, p, seed, (uint32_t)l, SITE_ATTN);
+    fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
+    fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
+    fl.res1_key = make_drop(training, p, seed, (uint32_t)l, SITE_RES1).key;
+    fl.ffn_key = make_drop(training, p, seed, (uint32_t)l, SITE_FFN).key;
+    fl.res2_key = make_drop(training, p, seed, (uint32_t)l, SITE_RES2).key;
+}
+
 static int linear_nt(const float* x, const float* W, const float* bias, float* y, int M, int N, int K, int relu,
                      const Drop& dr, const float* residual, int compute, hipStream_t st) {
     GemmParams g;
@@ -673,47 +723,19 @@ static int encoder_fwd_impl(const egx_config* cfg, const egx_segment* segs, cons
         pk.seed_advance = (cfg->advance_seed == 1 && cfg->seed_ptr && training) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
         FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
         // weight cache valid (egx_config.weight_cache_valid): the packed copies of exactly these weights are in place, nothing is packed
-        const bool cache_hit = cfg->weight_cache && cfg->weight_cache_valid;
-        auto add_pack = [&](const float* src, void* dst, int R, int K, int ld, int transpose, float scale = 1.f) -> const void* {
-            if (cache_hit) return dst;
-            PackDesc& dsc = pk.d[pk.n++];
-            dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = K; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = scale;
-            return dst;
-        };
-        // the keep-scale of the FFN hidden dropout rides on the packed W1 (forward: relu(s (W1 x + b1)) = s relu(W1 x + b1)) and
-        // W2^T (backward: dH = alive ? s W2^T g : 0): the FFN epilogues of the clip kernels have no multiply
+        Packer pack{pk, cfg->weight_cache && cfg->weight_cache_valid};
         const Drop dffn = make_drop(training, cfg->p_drop, seed, 0, SITE_FFN);
-        const float ffn_scale = dffn.thresh ? dffn.inv_keep : 1.f;
+        const float ffn_scale = dffn.thresh ? dffn.inv_keep : 1.f;      // (fill_layer)
         for (int i = 0; i < pl.nseg; ++i) {
-            FusedSeg& fs = fp.seg[i];
-            fs.feat = segs[i].feat; fs.proj_wp = add_pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0); fs.proj_b = segs[i].proj_b;
-            fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos;
-            fs.T = segs[i].T; fs.d_in = segs[i].d_in; fs.off = pl.seg_off[i]; fs.pos_stride = segs[i].pos_stride;
-            fs.row0 = 0; fs.Tfull = segs[i].T; fs.seg_id = i;
+            fill_seg(fp.seg[i], segs[i], i, pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0));
+            fp.seg[i].off = pl.seg_off[i]; fp.seg[i].row0 = 0;
             Drop df = make_drop(training, cfg->p_feat, seed, (uint32_t)i, SITE_FEAT);
             fp.feat_key[i] = df.key; fp.feat_thresh = df.thresh; fp.feat_inv = df.inv_keep;
         }
         fp.n_heads = pl.H;
         for (int l = 0; l < pl.L; ++l) {
-            FusedLayer& fl = fp.layer[l];
-            const egx_layer& w = layers[l];
-            fl.in_proj_wp = add_pack(w.in_proj_w, PL.layer[l].in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
-            fl.out_proj_wp = add_pack(w.out_proj_w, PL.layer[l].out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
-            fl.lin1_wp = add_pack(w.lin1_w, PL.layer[l].lin1_w, pl.dff, d, d, 0, ffn_scale); fl.lin1_b = w.lin1_b;
-            fl.lin2_wp = add_pack(w.lin2_w, PL.layer[l].lin2_w, d, pl.dff, pl.dff, 0); fl.lin2_b = w.lin2_b;
-            {   // transposed copies for the backward kernels
-                add_pack(w.in_proj_w, PL.layer[l].in_wt, d, 3 * d, d, 1);
-                add_pack(w.out_proj_w, PL.layer[l].out_wt, d, d, d, 1);
-                add_pack(w.lin1_w, PL.layer[l].lin1_wt, d, pl.dff, d, 1);
-                add_pack(w.lin2_w, PL.layer[l].lin2_wt, pl.dff, d, pl.dff, 1, ffn_scale);
-            }
-            fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
-            Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-            fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
-            fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
-            fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
-            fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
-            fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
+            fill_layer(fp.layer[l], layers[l], PL.layer[l], d, pl.dff, ffn_scale, pack);
+            set_layer_drop(fp.layer[l], training, cfg->p_drop, seed, l);
         }
         fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
         fp.nseg = pl.nseg; fp.n_layers = pl.L; fp.B = vp.vB; fp.S = tiled ? FUSED_TOK_PAD : S; fp.d_ff = pl.dff;
@@ -941,9 +963,8 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
             const bool touch = cfg->weight_cache != nullptr && !tiled;      // (see the forward)
             const size_t ffn_pb = packed_bytes(pl.dff, d, comp), in_pb = packed_bytes(3 * d, d, comp), out_pb = packed_bytes(d, d, comp);
             for (int i = 0; i < pl.nseg; ++i) {
-                FusedSeg& fs = bp.seg[i];
-                fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos; fs.T = segs[i].T; fs.d_in = segs[i].d_in;
-                fs.off = pl.seg_off[i]; fs.pos_stride = segs[i].pos_stride; fs.row0 = 0; fs.Tfull = segs[i].T; fs.seg_id = i;
+                fill_seg(bp.seg[i], segs[i], i);
+                bp.seg[i].off = pl.seg_off[i]; bp.seg[i].row0 = 0;
                 bp.dseg_out[i] = fptr(scratch, SC.dseg[i]);
                 Drop df = make_drop(training, cfg->p_feat, seed, (uint32_t)i, SITE_FEAT);
                 bp.feat_key[i] = df.key; bp.feat_thresh = df.thresh; bp.feat_inv = df.inv_keep;
@@ -954,17 +975,8 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
             bp.dx0_out = want_pos ? fptr(scratch, SC.dx0) : nullptr;
             for (int l = 0; l < pl.L; ++l) {
                 FusedBwdLayer& fl = bp.layer[l];
-                const egx_layer& w = layers[l];
-                fl.in_proj_wp = PL.layer[l].in_w; fl.in_proj_wtp = PL.layer[l].in_wt; fl.out_proj_wtp = PL.layer[l].out_wt;
-                fl.lin1_wp = PL.layer[l].lin1_w; fl.lin2_wtp = PL.layer[l].lin2_wt; fl.lin1_wtp = PL.layer[l].lin1_wt;
-                fl.in_proj_b = w.in_proj_b; fl.lin1_b = w.lin1_b;
-                fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
-                Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-                fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
-                fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
-                fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
-                fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
-                fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
+                fill_bwd_layer(fl, layers[l], PL.layer[l]);
+                set_layer_drop(fl, training, cfg->p_drop, seed, l);
                 fl.x1_out = fptr(scratch, SC.x1[l]); fl.g2_out = fptr(scratch, SC.g2[l]); fl.attn_o_out = fptr(scratch, SC.attn_o[l]);
                 fl.g1_out = fptr(scratch, SC.g1[l]); fl.dqkv_out = fptr(scratch, SC.dqkv[l]);
                 fl.x_in_out = const_cast<float*>((const float*)((const char*)saved + fused_xin_offset(cfg, segs, vp))) + (size_t)l * N * d;      // saved by the forward
@@ -1643,76 +1655,50 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
     rp.bytes = rp.off_tab + align_up(rp.tab.size() * sizeof(int), 256);
     return 0;
 }
-}  // namespace
-
-extern "C" {
-
-int egx_ragged_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
-    RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
-    if (bytes) *bytes = rp.bytes;
-    return 0;
+// with a head the last layer leaves EVERY token of a clip (rows tok0 .. tok0 + S_b of the dense array); head-less its first segment, packed
+void ragged_head_rows(RaggedPlan& rp, int B, bool with_head) {
+    if (!with_head) return;
+    for (int b = 0; b < B; ++b) {
+        int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
+        rec[RG_OUT0] = rec[RG_TOK0]; rec[RG_OUTN] = rec[RG_S];
+    }
 }
 
-int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
-                   const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, void* stream) {
-    RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+// The forward of egx_ragged_fwd (`train` false) and egx_ragged_train_fwd (`train`) over the caller's plan (ragged_plan(..., train)) and its
+// workspace layout. Only the train call hands the kernels dropout keys, the device seed (and its advance) and runs the cross entropy; the
+// inference call's keys stay zero and its FFN keep-scale 1.
+int ragged_forward(const egx_config* cfg, const egx_segment* segs, RaggedPlan& rp, const float* ln_w, const float* ln_b, const egx_layer* layers,
+                   const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, bool train, int training, uint64_t seed,
+                   hipStream_t st) {
     const Plan& vp = rp.vp;
-    EGX_CHECK(workspace && ln_w && ln_b && layers, "ragged batch: null pointer argument");
     const bool with_head = head && head->W;
-    EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged batch: null output pointer");
-    EGX_CHECK(!with_head || (head->ln_w && head->ln_b && head->b && head->n_out >= 1 && head->n_out <= FUSED_HEAD_MAX_OUT),
-              "head needs ln_w, ln_b, W, b and 1 <= n_out <= %d", FUSED_HEAD_MAX_OUT);
-    hipStream_t st = (hipStream_t)stream;
     const int d = vp.d, comp = cfg->compute;
     const size_t N = vp.N;
     char* ws = (char*)workspace;
-    float* dense = (float*)(ws + rp.off_tokens);        // with a head: every token of the last layer (N, d), then the pooled rows (B, d)
-    if (with_head)
-        for (int b = 0; b < B; ++b) {
-            int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
-            rec[RG_OUT0] = rec[RG_TOK0]; rec[RG_OUTN] = rec[RG_S];
-        }
+    float* dense = (float*)(ws + rp.off_tokens);        // with a head: every token of the last layer (N, d), then the token means (B, d)
+    ragged_head_rows(rp, B, with_head);
     // the batch table to the device, stream-ordered, in the arguments of upload launches (no host buffer has to outlive the call). Its
     // contents depend on the lengths of THIS call: a captured hipGraph would replay them for every batch, so the call is not for capture.
     int* tab = (int*)(ws + rp.off_tab);
     if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
 
+    const uint64_t* seed_ptr = train ? cfg->seed_ptr : nullptr;
     FusedFwdParams fp;
     memset(&fp, 0, sizeof(fp));
     PackParams pk;
     memset(&pk, 0, sizeof(pk));
     pk.mode = comp;
+    pk.seed_advance = (cfg->advance_seed == 1 && seed_ptr && training) ? const_cast<uint64_t*>(seed_ptr) : nullptr;
     FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, workspace, vp));
-    const bool cache_hit = cfg->weight_cache && cfg->weight_cache_valid;
-    auto add_pack = [&](const float* src, void* dst, int R, int Kd, int ld, int transpose) -> const void* {
-        if (cache_hit) return dst;
-        PackDesc& dsc = pk.d[pk.n++];
-        dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = Kd; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = 1.f;
-        return dst;
-    };
-    for (int i = 0; i < vp.nseg; ++i) {
-        FusedSeg& fs = fp.seg[i];
-        fs.feat = segs[i].feat; fs.proj_wp = add_pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0); fs.proj_b = segs[i].proj_b;
-        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos;
-        fs.T = segs[i].T; fs.d_in = segs[i].d_in; fs.pos_stride = segs[i].pos_stride;
-        fs.Tfull = segs[i].T; fs.seg_id = i;        // (the clip's own pieces come from the batch table)
-    }
+    Packer pack{pk, cfg->weight_cache && cfg->weight_cache_valid};
+    const Drop dffn = make_drop(training, cfg->p_drop, seed, 0, SITE_FFN);
+    const float ffn_scale = dffn.thresh ? dffn.inv_keep : 1.f;      // (fill_layer)
+    for (int i = 0; i < vp.nseg; ++i)       // (the clip's own pieces come from the batch table)
+        fill_seg(fp.seg[i], segs[i], i, pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0));
     fp.n_heads = vp.H;
     for (int l = 0; l < vp.L; ++l) {
-        FusedLayer& fl = fp.layer[l];
-        const egx_layer& w = layers[l];
-        fl.in_proj_wp = add_pack(w.in_proj_w, PL.layer[l].in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
-        fl.out_proj_wp = add_pack(w.out_proj_w, PL.layer[l].out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
-        fl.lin1_wp = add_pack(w.lin1_w, PL.layer[l].lin1_w, vp.dff, d, d, 0); fl.lin1_b = w.lin1_b;
-        fl.lin2_wp = add_pack(w.lin2_w, PL.layer[l].lin2_w, d, vp.dff, vp.dff, 0); fl.lin2_b = w.lin2_b;
-        // the transposed copies too: a weight cache this call fills must serve a later backward as the tiled forward's does
-        add_pack(w.in_proj_w, PL.layer[l].in_wt, d, 3 * d, d, 1);
-        add_pack(w.out_proj_w, PL.layer[l].out_wt, d, d, d, 1);
-        add_pack(w.lin1_w, PL.layer[l].lin1_wt, d, vp.dff, d, 1);
-        add_pack(w.lin2_w, PL.layer[l].lin2_wt, vp.dff, d, vp.dff, 1);
-        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
+        fill_layer(fp.layer[l], layers[l], PL.layer[l], d, vp.dff, ffn_scale, pack);
+        if (train) set_layer_drop(fp.layer[l], training, cfg->p_drop, seed, l);
     }
     fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
     fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = FUSED_TOK_PAD; fp.d_ff = vp.dff;
@@ -1725,6 +1711,11 @@ int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* le
     fp.x1p_out = split_planes(cfg) ? (unsigned short*)(ws + fused_x1p_offset(cfg, segs, vp)) : nullptr;
     fp.xin_out = (float*)(ws + fused_xin_offset(cfg, segs, vp));
     fp.qkv_out = (float*)(ws + fused_qkv_offset(cfg, segs, vp));
+    if (train) {
+        Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
+        fp.pos_key = dpz.key; fp.pos_thresh = dpz.thresh; fp.pos_inv = dpz.inv_keep;
+    }
+    fp.seed_ptr = seed_ptr;
     // every tile walks the FFN hidden blocks from block 0 (rot_mode 1, +2.5 % of the tiled launches' time against the staggered default):
     // the staggered start depends on the tile's place in the grid, so a clip's result would depend on where the batch puts it
     fp.rot_mode = 1;
@@ -1744,14 +1735,41 @@ int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* le
         ap.attn_o = attn + (size_t)l * N * d;
         ap.lse = lse + (size_t)l * vp.H * N;
         ap.B = B; ap.S = vp.S; ap.tpc = 0; ap.layer = l;
+        ap.drop_key = fp.layer[l].attn_key; ap.drop_thresh = fp.layer[l].attn_thresh; ap.drop_inv = fp.layer[l].drop_inv;
+        ap.seed_ptr = seed_ptr;
         ap.rtab = tab;
         if (tiled_attn_fwd(ap, comp, st)) return 1;
         fp.mode = FUSED_MODE_POST; fp.l0 = l;
         if (fused_forward(fp, comp, st)) return 1;
     }
-    if (with_head)
-        return pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st);
+    if (with_head) {
+        if (pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st)) return 1;
+        const egx_ce* ce = cfg->ce;     // (the inference plan refuses it)
+        if (ce) return weighted_ce(logits_out, ce->target, ce->class_weight, B, head->n_out, ce->loss, ce->d_logits, st);
+    }
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int egx_ragged_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+    if (bytes) *bytes = rp.bytes;
+    return 0;
+}
+
+int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                   const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, void* stream) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+    EGX_CHECK(workspace && ln_w && ln_b && layers, "ragged batch: null pointer argument");
+    const bool with_head = head && head->W;
+    EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged batch: null output pointer");
+    EGX_CHECK(!with_head || (head->ln_w && head->ln_b && head->b && head->n_out >= 1 && head->n_out <= FUSED_HEAD_MAX_OUT),
+              "head needs ln_w, ln_b, W, b and 1 <= n_out <= %d", FUSED_HEAD_MAX_OUT);
+    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, workspace, false, 0, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1808,14 +1826,6 @@ RaggedTrainScratch ragged_train_scratch(const egx_config* cfg, const egx_segment
     r.bytes = cur;
     return r;
 }
-// with a head the last layer leaves EVERY token of a clip (rows tok0 .. tok0 + S_b of the dense array); head-less its first segment, packed
-void ragged_head_rows(RaggedPlan& rp, int B, bool with_head) {
-    if (!with_head) return;
-    for (int b = 0; b < B; ++b) {
-        int* rec = rp.tab.data() + (size_t)b * RAGGED_REC;
-        rec[RG_OUT0] = rec[RG_TOK0]; rec[RG_OUTN] = rec[RG_S];
-    }
-}
 }  // namespace
 
 extern "C" {
@@ -1835,7 +1845,6 @@ int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const i
     (void)scratch;
     RaggedPlan rp;
     if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
-    const Plan& vp = rp.vp;
     EGX_CHECK(saved && ln_w && ln_b && layers, "ragged training: null pointer argument");
     const bool with_head = head && head->W;
     EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged training: null output pointer");
@@ -1844,102 +1853,7 @@ int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const i
     const egx_ce* ce = cfg->ce;
     EGX_CHECK(!ce || with_head, "egx_config.ce: the fused cross entropy needs the pooled head");
     EGX_CHECK(!ce || (ce->target && ce->loss && ce->d_logits), "egx_config.ce: target, loss and d_logits must be set");
-    hipStream_t st = (hipStream_t)stream;
-    const int d = vp.d, comp = cfg->compute;
-    const size_t N = vp.N;
-    char* ws = (char*)saved;
-    float* dense = (float*)(ws + rp.off_tokens);        // every token of the last layer (N, d), then the token means (B, d)
-    ragged_head_rows(rp, B, with_head);
-    int* tab = (int*)(ws + rp.off_tab);
-    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
-
-    FusedFwdParams fp;
-    memset(&fp, 0, sizeof(fp));
-    PackParams pk;
-    memset(&pk, 0, sizeof(pk));
-    pk.mode = comp;
-    pk.seed_advance = (cfg->advance_seed == 1 && cfg->seed_ptr && training) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
-    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
-    const bool cache_hit = cfg->weight_cache && cfg->weight_cache_valid;
-    auto add_pack = [&](const float* src, void* dst, int R, int Kd, int ld, int transpose, float scale = 1.f) -> const void* {
-        if (cache_hit) return dst;
-        PackDesc& dsc = pk.d[pk.n++];
-        dsc.src = src; dsc.dst = dst; dsc.R = R; dsc.K = Kd; dsc.ld = ld; dsc.transpose = transpose; dsc.scale = scale;
-        return dst;
-    };
-    // the FFN keep-scale rides on the packed W1 and W2^T (as in the tiled training forward)
-    const Drop dffn = make_drop(training, cfg->p_drop, seed, 0, SITE_FFN);
-    const float ffn_scale = dffn.thresh ? dffn.inv_keep : 1.f;
-    for (int i = 0; i < vp.nseg; ++i) {
-        FusedSeg& fs = fp.seg[i];
-        fs.feat = segs[i].feat; fs.proj_wp = add_pack(segs[i].proj_w, PL.proj[i], d, segs[i].d_in, segs[i].d_in, 0); fs.proj_b = segs[i].proj_b;
-        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos;
-        fs.T = segs[i].T; fs.d_in = segs[i].d_in; fs.pos_stride = segs[i].pos_stride;
-        fs.Tfull = segs[i].T; fs.seg_id = i;        // (the clip's own pieces come from the batch table)
-    }
-    fp.n_heads = vp.H;
-    for (int l = 0; l < vp.L; ++l) {
-        FusedLayer& fl = fp.layer[l];
-        const egx_layer& w = layers[l];
-        fl.in_proj_wp = add_pack(w.in_proj_w, PL.layer[l].in_w, 3 * d, d, d, 0); fl.in_proj_b = w.in_proj_b;
-        fl.out_proj_wp = add_pack(w.out_proj_w, PL.layer[l].out_w, d, d, d, 0); fl.out_proj_b = w.out_proj_b;
-        fl.lin1_wp = add_pack(w.lin1_w, PL.layer[l].lin1_w, vp.dff, d, d, 0, ffn_scale); fl.lin1_b = w.lin1_b;
-        fl.lin2_wp = add_pack(w.lin2_w, PL.layer[l].lin2_w, d, vp.dff, vp.dff, 0); fl.lin2_b = w.lin2_b;
-        add_pack(w.in_proj_w, PL.layer[l].in_wt, d, 3 * d, d, 1);
-        add_pack(w.out_proj_w, PL.layer[l].out_wt, d, d, d, 1);
-        add_pack(w.lin1_w, PL.layer[l].lin1_wt, d, vp.dff, d, 1);
-        add_pack(w.lin2_w, PL.layer[l].lin2_wt, vp.dff, d, vp.dff, 1, ffn_scale);
-        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
-        Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-        fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
-        fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
-        fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
-        fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
-        fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
-    }
-    fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
-    fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = FUSED_TOK_PAD; fp.d_ff = vp.dff;
-    fp.tpc = 0; fp.S_clip = vp.S; fp.Ntok = N;
-    fp.tokens_out = with_head ? dense : tokens_out;
-    fp.saved_pre = (float*)ws;
-    fp.saved_res = (float*)ws + N * d;
-    fp.relu_bits = (uint32_t*)(ws + fused_res_bytes(vp));
-    fp.hid_out = store_hidden() ? ws + fused_hid_offset(cfg, segs, vp) : nullptr;
-    fp.x1p_out = split_planes(cfg) ? (unsigned short*)(ws + fused_x1p_offset(cfg, segs, vp)) : nullptr;
-    fp.xin_out = (float*)(ws + fused_xin_offset(cfg, segs, vp));
-    fp.qkv_out = (float*)(ws + fused_qkv_offset(cfg, segs, vp));
-    Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
-    fp.pos_key = dpz.key; fp.pos_thresh = dpz.thresh; fp.pos_inv = dpz.inv_keep;
-    fp.seed_ptr = cfg->seed_ptr;
-    fp.rot_mode = 1;        // (as egx_ragged_fwd: a clip's result must not depend on its place in the batch)
-    fp.n_slices = 1;
-    fp.rtab = tab; fp.B_clips = B;
-    if (cfg->weight_cache && pk.n) pk.zero_ctl = (unsigned*)((char*)cfg->weight_cache + align_up(PL.bytes, 256));
-    if (pack_weights(pk, st)) return 1;
-    float* attn = (float*)(ws + rp.off_attn);
-    float* lse = (float*)(ws + rp.off_lse);
-    fp.attn_in = attn;
-    fp.mode = FUSED_MODE_PRE;
-    if (fused_forward(fp, comp, st)) return 1;
-    for (int l = 0; l < vp.L; ++l) {
-        TiledAttnParams ap;
-        memset(&ap, 0, sizeof(ap));
-        ap.qkv = fp.qkv_out + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * d;
-        ap.attn_o = attn + (size_t)l * N * d;
-        ap.lse = lse + (size_t)l * vp.H * N;
-        ap.B = B; ap.S = vp.S; ap.tpc = 0; ap.layer = l;
-        ap.drop_key = fp.layer[l].attn_key; ap.drop_thresh = fp.layer[l].attn_thresh; ap.drop_inv = fp.layer[l].drop_inv;
-        ap.seed_ptr = cfg->seed_ptr;
-        ap.rtab = tab;
-        if (tiled_attn_fwd(ap, comp, st)) return 1;
-        fp.mode = FUSED_MODE_POST; fp.l0 = l;
-        if (fused_forward(fp, comp, st)) return 1;
-    }
-    if (with_head) {
-        if (pool_head_ragged_fwd(dense, tab, B, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, dense + N * d, logits_out, st)) return 1;
-        if (ce) return weighted_ce(logits_out, ce->target, ce->class_weight, B, head->n_out, ce->loss, ce->d_logits, st);
-    }
-    return 0;
+    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, saved, true, training, seed, (hipStream_t)stream);
 }
 
 int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
@@ -1968,9 +1882,7 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     FusedBwdParams bp;
     memset(&bp, 0, sizeof(bp));
     for (int i = 0; i < vp.nseg; ++i) {
-        FusedSeg& fs = bp.seg[i];
-        fs.add_vec = segs[i].add_vec; fs.pos = segs[i].pos; fs.T = segs[i].T; fs.d_in = segs[i].d_in;
-        fs.pos_stride = segs[i].pos_stride; fs.Tfull = segs[i].T; fs.seg_id = i;
+        fill_seg(bp.seg[i], segs[i], i);
         bp.dseg_out[i] = fptr(scratch, SC.dseg[i]);
     }
     bp.n_heads = vp.H;
@@ -1979,17 +1891,8 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     EGX_CHECK(!want_pos, "ragged training: learned positional tables (egx_segment_grads.pos) are not supported");
     for (int l = 0; l < L; ++l) {
         FusedBwdLayer& fl = bp.layer[l];
-        const egx_layer& w = layers[l];
-        fl.in_proj_wp = PL.layer[l].in_w; fl.in_proj_wtp = PL.layer[l].in_wt; fl.out_proj_wtp = PL.layer[l].out_wt;
-        fl.lin1_wp = PL.layer[l].lin1_w; fl.lin2_wtp = PL.layer[l].lin2_wt; fl.lin1_wtp = PL.layer[l].lin1_wt;
-        fl.in_proj_b = w.in_proj_b; fl.lin1_b = w.lin1_b;
-        fl.norm1_w = w.norm1_w; fl.norm1_b = w.norm1_b; fl.norm2_w = w.norm2_w; fl.norm2_b = w.norm2_b;
-        Drop da = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-        fl.attn_key = da.key; fl.attn_thresh = da.thresh; fl.drop_inv = da.inv_keep;
-        fl.res_thresh = da.thresh; fl.ffn_thresh = da.thresh;
-        fl.res1_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1).key;
-        fl.ffn_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).key;
-        fl.res2_key = make_drop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2).key;
+        fill_bwd_layer(fl, layers[l], PL.layer[l]);
+        set_layer_drop(fl, training, cfg->p_drop, seed, l);
         fl.x1_out = fptr(scratch, SC.x1[l]); fl.g2_out = fptr(scratch, SC.g2[l]);
         fl.g1_out = fptr(scratch, SC.g1[l]); fl.dqkv_out = fptr(scratch, SC.dqkv[l]);
         fl.x_in_out = const_cast<float*>((const float*)((const char*)saved + fused_xin_offset(cfg, segs, vp))) + (size_t)l * N * d;

@@ -6,13 +6,14 @@ hand-written HIP kernels. There is no fallback: a missing library or a CPU tenso
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
 import torch
 
 from . import _lib
-from ._lib import (Ce, Config, Head, HeadGrads, Layer, LayerGrads, Segment, SegmentGrads, check, ptr, _LAYER_FIELDS,
+from ._lib import (Ce, Config, Head, HeadGrads, Layer, LayerGrads, Segment, SegmentGrads, check, ptr,
                    EGX_F32, EGX_BF16, EGX_F32_SPLIT, EGX_IMPL_AUTO, EGX_IMPL_GENERIC, EGX_IMPL_FUSED, EGX_IMPL_WIDE, EGX_IMPL_TILED)
 
 # "f32s": fp32 operands split exactly into three bf16 parts, six bf16 MFMAs per K-block (fp32-grade results, fused d = 128
@@ -161,6 +162,63 @@ def _elem_ptr(t: torch.Tensor, row: int, row_elems: int) -> int:
     return t.data_ptr() + 4 * row * row_elems
 
 
+def _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table, feat=_dev_feat):
+    """The tensors of one encoder call, on the device and contiguous: the features through `feat` (fp32 or bf16, or _dev_f32), the rest fp32.
+    Returns (feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table) as lists / tensors / None."""
+    return ([feat(t, f"feats[{i}]") for i, t in enumerate(feats)], [_dev_f32(t, "projection weight") for t in proj],
+            [_dev_f32(t, "layer weight") for t in layer_t], [_dev_f32(t, "head parameter") for t in head_t],
+            _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias"),
+            None if task_embed is None else _dev_f32(task_embed, "task_embed"),
+            None if pos_table is None else _dev_f32(pos_table, "positional table"))
+
+
+def _segments(spec: EncoderSpec, feats, proj, task_embed, pos_table, B: int, grads=None):
+    """The egx_segment array of a call on B clips, with the features' and projections' shapes checked. With grads = (feature gradients,
+    projection gradients (w, b per projecting segment), task_embed gradient, positional-table gradient), None where not wanted, also the
+    egx_segment_grads array: returns (segments, segment gradients)."""
+    nseg, d = len(spec.segments), spec.d_model
+    segs = (Segment * nseg)()
+    sgr = (SegmentGrads * nseg)() if grads is not None else None
+    pi = 0
+    for i, (ss, f) in enumerate(zip(spec.segments, feats)):
+        if f.shape != (B, ss.T * max(ss.pool, 1), ss.d_in):
+            raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
+        if not ss.has_proj and (f.dtype == torch.bfloat16 or ss.pool > 1):
+            raise _lib.EgxError(f"feats[{i}]: bf16 / frame-pooled features need a projection (an identity segment enters "
+                                "the shared LayerNorm as fp32 rows)")
+        segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
+        segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
+        if ss.has_proj:
+            w, b = proj[2 * pi], proj[2 * pi + 1]
+            if w.shape != (d, ss.d_in):
+                raise _lib.EgxError(f"projection {i} weight shape {tuple(w.shape)} != ({d}, {ss.d_in})")
+            segs[i].proj_w, segs[i].proj_b = ptr(w), ptr(b)
+        if ss.add_row is not None:
+            segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
+        if ss.pos_row0 is not None:
+            segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
+        if sgr is not None:
+            d_feat, d_proj, d_te, d_pos = grads
+            sgr[i].feat = ptr(d_feat[i])
+            if ss.has_proj:
+                sgr[i].proj_w, sgr[i].proj_b = ptr(d_proj[2 * pi]), ptr(d_proj[2 * pi + 1])
+            if ss.add_row is not None and d_te is not None:
+                sgr[i].add_vec = _elem_ptr(d_te, ss.add_row, d)
+            if ss.pos_row0 is not None and d_pos is not None:
+                sgr[i].pos = _elem_ptr(d_pos, ss.pos_row0, d)
+        pi += int(ss.has_proj)
+    return segs if sgr is None else (segs, sgr)
+
+
+def _layers(layer_t, n_layers: int, grads=None):
+    """The egx_layer array (12 tensors per layer in _LAYER_FIELDS order); with grads (the same order, None where not wanted) also the
+    egx_layer_grads array: returns (layers, layer gradients)."""
+    def array(struct, ts):
+        return (struct * max(n_layers, 1))(*[struct(*map(ptr, ts[12 * l:12 * l + 12])) for l in range(n_layers)])
+    layers = array(Layer, layer_t)
+    return layers if grads is None else (layers, array(LayerGrads, grads))
+
+
 class _GradPacker:
     """Allocates every requested gradient as a 16-byte-aligned view of one flat buffer. Entries marked `late` (the
     weight gradients the backward finishes last: dW_proj, dW_in, dW_o) are placed first, so that everything behind
@@ -279,9 +337,7 @@ class EncoderFn(torch.autograd.Function):
         if reload_tuning_each_call:
             lib.egx_tuning_reload()
         nseg = len(spec.segments)
-        feats = [_dev_feat(t, f"feats[{i}]") for i, t in enumerate(rest[:nseg])]
         nproj = sum(1 for s in spec.segments if s.has_proj)
-        proj = [_dev_f32(t, "projection weight") for t in rest[nseg:nseg + 2 * nproj]]
         nhead = 4 if spec.head_n_out else 0
         tce_in = None
         if spec.token_ce:
@@ -294,54 +350,21 @@ class EncoderFn(torch.autograd.Function):
                 raise _lib.EgxError("EncoderSpec.ce needs the pooled head (head_n_out > 0)")
             ce_target, ce_weight = rest[-2], rest[-1]
             rest = rest[:-2]
-        layer_t = [_dev_f32(t, "layer weight") for t in rest[nseg + 2 * nproj:len(rest) - nhead]]
-        head_t = [_dev_f32(t, "head parameter") for t in rest[len(rest) - nhead:]] if nhead else []
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(
+            rest[:nseg], rest[nseg:nseg + 2 * nproj], rest[nseg + 2 * nproj:len(rest) - nhead], rest[len(rest) - nhead:], ln_w, ln_b,
+            task_embed, pos_table)
         assert len(layer_t) == 12 * spec.n_layers, "layer parameter count mismatch"
-        ln_w = _dev_f32(ln_w, "ln.weight")
-        ln_b = _dev_f32(ln_b, "ln.bias")
-        if task_embed is not None:
-            task_embed = _dev_f32(task_embed, "task_embed")
-        if pos_table is not None:
-            pos_table = _dev_f32(pos_table, "positional table")
         d = spec.d_model
         B = feats[0].shape[0]
         device = feats[0].device
-
-        segs = (Segment * nseg)()
-        pi = 0
-        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-            if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
-                raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
-            if not ss.has_proj and (f.dtype == torch.bfloat16 or ss.pool > 1):
-                raise _lib.EgxError(f"feats[{i}]: bf16 / frame-pooled features need a projection (an identity segment enters "
-                                    "the shared LayerNorm as fp32 rows)")
-            segs[i].feat = ptr(f)
-            segs[i].T = ss.T
-            segs[i].d_in = ss.d_in
-            segs[i].feat_bf16 = int(f.dtype == torch.bfloat16)
-            segs[i].pool = int(ss.pool)
-            if ss.has_proj:
-                w, b = proj[2 * pi], proj[2 * pi + 1]
-                if tuple(w.shape) != (d, ss.d_in):
-                    raise _lib.EgxError(f"projection {i} weight shape {tuple(w.shape)} != ({d}, {ss.d_in})")
-                segs[i].proj_w, segs[i].proj_b = ptr(w), ptr(b)
-                pi += 1
-            if ss.add_row is not None:
-                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
-            if ss.pos_row0 is not None:
-                segs[i].pos = _elem_ptr(pos_table, ss.pos_row0, d)
-                segs[i].pos_stride = d
-        layers = (Layer * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
 
         # NB: grad mode is off inside Function.forward; ctx.needs_input_grad is the reliable signal.
         # needs_input_grad order: (spec, task_embed, pos_table, ln_w, ln_b, *rest)
         nig = ctx.needs_input_grad
         needs_grad = any(nig)
         if spec.impl == "auto" and (nig[2] or any(nig[5:5 + nseg])):
-            import dataclasses
             feat_grad = [bool(nig[5 + i]) for i in range(nseg)]
             probe_cfg = spec.config()
             wide_ident_only = (lib.egx_encoder_impl(C.byref(probe_cfg), segs, B) == EGX_IMPL_WIDE
@@ -360,7 +383,6 @@ class EncoderFn(torch.autograd.Function):
             raise _lib.EgxError("out_tokens (first-tokens-only output) cannot be combined with the fused pooled head: the head pools "
                                 "every token of the clip")
         if spec.out_tokens:
-            import dataclasses
             full = dataclasses.replace(spec, out_tokens=0)
             probe = full.config()
             if nhead or lib.egx_encoder_impl(C.byref(probe), segs, B) != EGX_IMPL_FUSED:
@@ -502,7 +524,6 @@ class EncoderFn(torch.autograd.Function):
         nhead = ctx.nhead
         layer_t = sv[2 + nseg + 2 * nproj:len(sv) - nhead]
         head_t = sv[len(sv) - nhead:] if nhead else []
-        d = spec.d_model
         B = ctx.B
         device = d_tokens.device
         need = ctx.needs_input_grad  # (spec, task_embed, pos_table, ln_w, ln_b, *rest)
@@ -534,35 +555,8 @@ class EncoderFn(torch.autograd.Function):
         def g(i):
             return grads[i] if i >= 0 else None
 
-        segs = (Segment * nseg)()
-        sgr = (SegmentGrads * nseg)()
-        pi = 0
-        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-            segs[i].feat = ptr(f)
-            segs[i].T = ss.T
-            segs[i].d_in = ss.d_in
-            segs[i].feat_bf16 = int(f.dtype == torch.bfloat16)
-            segs[i].pool = int(ss.pool)
-            sgr[i].feat = ptr(feat_grads[i])
-            if ss.has_proj:
-                segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
-                sgr[i].proj_w, sgr[i].proj_b = ptr(g(i_proj[2 * pi])), ptr(g(i_proj[2 * pi + 1]))
-                pi += 1
-            if ss.add_row is not None:
-                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
-                if i_te >= 0:
-                    sgr[i].add_vec = _elem_ptr(grads[i_te], ss.add_row, d)
-            if ss.pos_row0 is not None:
-                segs[i].pos = _elem_ptr(pos_table, ss.pos_row0, d)
-                segs[i].pos_stride = d
-                if i_pos >= 0:
-                    sgr[i].pos = _elem_ptr(grads[i_pos], ss.pos_row0, d)
-        layers = (Layer * max(spec.n_layers, 1))()
-        lgr = (LayerGrads * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
-                setattr(lgr[l], name, ptr(g(i_layer[12 * l + k])))
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=(feat_grads, [g(i) for i in i_proj], g(i_te), g(i_pos)))
+        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
 
         cfg = spec.config()
         cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
@@ -695,6 +689,27 @@ def ragged_lengths(lengths, B: int, T_pad: Sequence[int], order: Optional[Sequen
     return t.to(torch.int32).contiguous()
 
 
+def _check_host_lengths(lengths, B: int, nseg: int) -> torch.Tensor:
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
+        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
+    return lengths.contiguous()
+
+
+def _length_groups(spec: EncoderSpec, feats, lengths: torch.Tensor, first_only: bool = False):
+    """The clips of a ragged batch grouped by their length tuple, for the per-group fallbacks. Yields (clip indices, the same as an int64
+    tensor on the features' device, the group's spec with its segment lengths, the group's unpadded features); first_only: the group's spec
+    returns the first segment's tokens only (out_tokens)."""
+    groups = {}
+    for b, row in enumerate(lengths.tolist()):
+        groups.setdefault(tuple(row), []).append(b)
+    for key, idx in groups.items():
+        it = torch.tensor(idx, dtype=torch.int64, device=feats[0].device)
+        fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
+        gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)],
+                                    out_tokens=key[0] if first_only else spec.out_tokens)
+        yield idx, it, gspec, fs
+
+
 def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
                    proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], head_params: Sequence[torch.Tensor] = ()):
     """Inference forward (no autograd) over a batch of clips of their own lengths: clip b's result is that of the same model on clip b
@@ -707,40 +722,13 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
     lib = _lib.load()
     if reload_tuning_each_call:
         lib.egx_tuning_reload()
-    nseg = len(spec.segments)
-    B = feats[0].shape[0]
-    device = feats[0].device
-    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
-        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
-    lengths = lengths.contiguous()
+    B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
+    lengths = _check_host_lengths(lengths, B, len(spec.segments))
     with torch.no_grad():
-        feats = [_dev_feat(t, f"feats[{i}]") for i, t in enumerate(feats)]
-        proj = [_dev_f32(t, "projection weight") for t in proj]
-        layer_t = [_dev_f32(t, "layer weight") for t in layer_params]
-        head_t = [_dev_f32(t, "head parameter") for t in head_params]
-        ln_w, ln_b = _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias")
-        task_embed = _dev_f32(task_embed, "task_embed") if task_embed is not None else None
-        pos_table = _dev_f32(pos_table, "positional table") if pos_table is not None else None
-        d = spec.d_model
-        segs = (Segment * nseg)()
-        pi = 0
-        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-            if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
-                raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
-            segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
-            segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
-            if ss.has_proj:
-                segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
-                pi += 1
-            if ss.add_row is not None:
-                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
-            if ss.pos_row0 is not None:
-                segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
-        layers = (Layer * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
-        import dataclasses
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_params, head_params, ln_w, ln_b,
+                                                                                      task_embed, pos_table)
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
         cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
         nbytes = C.c_size_t(0)
         if lib.egx_ragged_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
@@ -767,51 +755,24 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
 def _encoder_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t):
     """encoder_ragged where the ragged kernels do not run (exact fp32, a forced implementation, deeper stacks, clips beyond 512 tokens):
     one batched forward per group of clips with the same length tuple, on those clips' unpadded frames; results scattered to clip order."""
-    import dataclasses
     B, d = feats[0].shape[0], spec.d_model
     device = feats[0].device
-    groups = {}
-    for b, row in enumerate(lengths.tolist()):
-        groups.setdefault(tuple(row), []).append(b)
     if head_t:
         out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
     else:
         first = lengths[:, 0].to(torch.int64)
         row0 = torch.cumsum(first, 0) - first           # first output row of every clip
         out = torch.empty((int(first.sum()), d), dtype=torch.float32, device=device)
-    for key, idx in groups.items():
-        it = torch.tensor(idx, dtype=torch.int64, device=device)
-        fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
-        gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)],
-                                    out_tokens=0 if head_t else key[0])
+    for idx, it, gspec, fs in _length_groups(spec, feats, lengths, first_only=not head_t):
         r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
         if head_t:
             out.index_copy_(0, it, r)
         else:
-            dst = (row0[idx][:, None] + torch.arange(key[0])[None, :]).reshape(-1).to(device)
+            dst = (row0[idx][:, None] + torch.arange(gspec.out_tokens)[None, :]).reshape(-1).to(device)
             out.index_copy_(0, dst, r.reshape(-1, d))
     _last_impl[0] = IMPL_GROUPED
     _last_slices[0] = 1
     return out
-
-
-def _ragged_segments(spec: EncoderSpec, feats, proj, task_embed, pos_table, B: int):
-    nseg, d = len(spec.segments), spec.d_model
-    segs = (Segment * nseg)()
-    pi = 0
-    for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-        if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
-            raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
-        segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
-        segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
-        if ss.has_proj:
-            segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
-            pi += 1
-        if ss.add_row is not None:
-            segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
-        if ss.pos_row0 is not None:
-            segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
-    return segs
 
 
 def _ragged_train_config(spec: EncoderSpec) -> Config:
@@ -839,19 +800,12 @@ class RaggedEncoderFn(torch.autograd.Function):
         ce_target = ce_weight = None
         if spec.ce:
             ce_target, ce_weight, rest = rest[-2], rest[-1], rest[:-2]
-        feats = [_dev_f32(t, f"feats[{i}]") for i, t in enumerate(rest[:nseg])]
-        proj = [_dev_f32(t, "projection weight") for t in rest[nseg:nseg + 2 * nproj]]
-        layer_t = [_dev_f32(t, "layer weight") for t in rest[nseg + 2 * nproj:len(rest) - nhead]]
-        head_t = [_dev_f32(t, "head parameter") for t in rest[len(rest) - nhead:]] if nhead else []
-        ln_w, ln_b = _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias")
-        task_embed = _dev_f32(task_embed, "task_embed") if task_embed is not None else None
-        pos_table = _dev_f32(pos_table, "positional table") if pos_table is not None else None
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(
+            rest[:nseg], rest[nseg:nseg + 2 * nproj], rest[nseg + 2 * nproj:len(rest) - nhead], rest[len(rest) - nhead:], ln_w, ln_b,
+            task_embed, pos_table, feat=_dev_f32)
         B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
-        segs = _ragged_segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = (Layer * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
         cfg = _ragged_train_config(spec)
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_ragged_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
@@ -921,7 +875,7 @@ class RaggedEncoderFn(torch.autograd.Function):
         proj = sv[2 + nseg:2 + nseg + 2 * nproj]
         layer_t = sv[2 + nseg + 2 * nproj:len(sv) - nhead]
         head_t = sv[len(sv) - nhead:] if nhead else []
-        B, d, device = ctx.B, spec.d_model, d_out.device
+        B, device = ctx.B, d_out.device
         need = ctx.needs_input_grad     # (spec, lengths, task_embed, pos_table, ln_w, ln_b, *rest)
         if need[3]:
             raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
@@ -937,22 +891,8 @@ class RaggedEncoderFn(torch.autograd.Function):
         def g(i):
             return grads[i] if i >= 0 else None
 
-        segs = _ragged_segments(spec, feats, proj, task_embed, pos_table, B)
-        sgr = (SegmentGrads * nseg)()
-        pi = 0
-        for i, ss in enumerate(spec.segments):
-            sgr[i].feat = ptr(feat_grads[i])
-            if ss.has_proj:
-                sgr[i].proj_w, sgr[i].proj_b = ptr(g(i_proj[2 * pi])), ptr(g(i_proj[2 * pi + 1]))
-                pi += 1
-            if ss.add_row is not None and i_te >= 0:
-                sgr[i].add_vec = _elem_ptr(grads[i_te], ss.add_row, d)
-        layers = (Layer * max(spec.n_layers, 1))()
-        lgr = (LayerGrads * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
-                setattr(lgr[l], name, ptr(g(i_layer[12 * l + k])))
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=(feat_grads, [g(i) for i in i_proj], g(i_te), None))
+        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
         cfg = _ragged_train_config(spec)
         cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
         if dl_scale is not None:
@@ -994,15 +934,9 @@ def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengt
     if (ce is not None) != bool(spec.ce) or (ce is not None and not spec.head_n_out):
         raise ValueError("ce = (target, class_weight) goes with spec.ce and the pooled head")
     lib = _lib.load()
-    nseg = len(spec.segments)
     B = feats[0].shape[0]
-    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
-        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
-    lengths = lengths.contiguous()
-    segs = (Segment * nseg)()
-    for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-        segs[i].T, segs[i].d_in, segs[i].proj_w = ss.T, ss.d_in, (1 if ss.has_proj else None)
-        segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
+    lengths = _check_host_lengths(lengths, B, len(spec.segments))
+    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
     sv, sc = C.c_size_t(0), C.c_size_t(0)
     if (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
             lib.egx_ragged_train_workspace(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0:
@@ -1016,24 +950,16 @@ def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengt
 def _encoder_train_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t, ce):
     """encoder_ragged_train where the ragged kernels do not run: one differentiable batched forward per group of clips with the same length
     tuple, on those clips' unpadded frames, the results put back in clip order (autograd flows through the gather and the reordering)."""
-    import dataclasses
-    B, d = feats[0].shape[0], spec.d_model
+    d = spec.d_model
     device = feats[0].device
-    groups = {}
-    for b, row in enumerate(lengths.tolist()):
-        groups.setdefault(tuple(row), []).append(b)
     parts, order = [], []
     first = lengths[:, 0].to(torch.int64)
     row0 = (torch.cumsum(first, 0) - first).tolist()         # first output row of every clip (head-less)
     gspec0 = dataclasses.replace(spec, ce=False, wcache=None)
-    for key, idx in groups.items():
-        it = torch.tensor(idx, dtype=torch.int64, device=device)
-        fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
-        gspec = dataclasses.replace(gspec0, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)],
-                                    out_tokens=0 if head_t else key[0])
+    for idx, _, gspec, fs in _length_groups(gspec0, feats, lengths, first_only=not head_t):
         r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
         parts.append(r if head_t else r.reshape(-1, d))
-        order += idx if head_t else [row0[b] + t for b in idx for t in range(key[0])]
+        order += idx if head_t else [row0[b] + t for b in idx for t in range(gspec.out_tokens)]
     inv = torch.empty(len(order), dtype=torch.int64)
     inv[torch.tensor(order, dtype=torch.int64)] = torch.arange(len(order))
     out = torch.cat(parts, 0).index_select(0, inv.to(device))
@@ -1068,13 +994,10 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
     wide bf16 path (last_encoder_impl() == "ragged"); configurations it does not cover run one batched forward per length tuple ("grouped")."""
     if spec.training or spec.ce or spec.token_ce or spec.out_tokens or spec.head_n_out:
         raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens, no head")
-    nseg = len(spec.segments)
     B = feats[0].shape[0]
-    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device.type != "cpu" or tuple(lengths.shape) != (B, nseg):
-        raise ValueError(f"lengths must be the ({B}, {nseg}) int32 host tensor of ragged_lengths()")
+    lengths = _check_host_lengths(lengths, B, len(spec.segments))
     if out_layout not in (0, 1):
         raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
-    lengths = lengths.contiguous()
     if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
         b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
         raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
@@ -1083,32 +1006,11 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
         lib.egx_tuning_reload()
     device = feats[0].device
     with torch.no_grad():
-        feats = [_dev_feat(t, f"feats[{i}]") for i, t in enumerate(feats)]
-        proj = [_dev_f32(t, "projection weight") for t in proj]
-        layer_t = [_dev_f32(t, "layer weight") for t in layer_params]
-        ln_w, ln_b = _dev_f32(ln_w, "ln.weight"), _dev_f32(ln_b, "ln.bias")
-        task_embed = _dev_f32(task_embed, "task_embed") if task_embed is not None else None
-        pos_table = _dev_f32(pos_table, "positional table") if pos_table is not None else None
+        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_params, (), ln_w, ln_b, task_embed,
+                                                                                 pos_table)
         d = spec.d_model
-        segs = (Segment * nseg)()
-        pi = 0
-        for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-            if f.dim() != 3 or f.shape[0] != B or f.shape[1] != ss.T * max(ss.pool, 1) or f.shape[2] != ss.d_in:
-                raise _lib.EgxError(f"feats[{i}] has shape {tuple(f.shape)}, expected ({B}, {ss.T * max(ss.pool, 1)}, {ss.d_in})")
-            segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
-            segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
-            if ss.has_proj:
-                segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
-                pi += 1
-            if ss.add_row is not None:
-                segs[i].add_vec = _elem_ptr(task_embed, ss.add_row, d)
-            if ss.pos_row0 is not None:
-                segs[i].pos, segs[i].pos_stride = _elem_ptr(pos_table, ss.pos_row0, d), d
-        layers = (Layer * max(spec.n_layers, 1))()
-        for l in range(spec.n_layers):
-            for k, name in enumerate(_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[12 * l + k]))
-        import dataclasses
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
         cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
         nbytes = C.c_size_t(0)
         if lib.egx_ragged_encode_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
@@ -1126,23 +1028,16 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
 def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
     """encoder_ragged_tokens where egx_ragged_encode does not run (compute other than bf16, a forced implementation, a clip beyond the wide
     attention): one batched forward per group of clips with the same length tuple, on their unpadded frames; rows scattered to their place."""
-    import dataclasses
     d = spec.d_model
     device = feats[0].device
-    groups = {}
-    for b, row in enumerate(lengths.tolist()):
-        groups.setdefault(tuple(row), []).append(b)
     rows = ragged_token_rows(lengths, out_layout)
     S = lengths.to(torch.int64).sum(1)
     tok0 = torch.cumsum(S, 0) - S
     out = torch.empty((int(S.sum()), d), dtype=torch.float32, device=device)
     with torch.no_grad():
-        for key, idx in groups.items():
-            it = torch.tensor(idx, dtype=torch.int64, device=device)
-            fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
-            gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)])
+        for idx, _, gspec, fs in _length_groups(spec, feats, lengths):
             r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
-            src = (tok0[idx][:, None] + torch.arange(sum(key))[None, :]).reshape(-1)
+            src = (tok0[idx][:, None] + torch.arange(r.shape[1])[None, :]).reshape(-1)
             out.index_copy_(0, rows[src].to(device), r.reshape(-1, d))
     _last_impl[0] = IMPL_GROUPED
     _last_slices[0] = 1
@@ -1189,23 +1084,13 @@ def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, lay
     return logits
 
 
-def _token_ce_fused(spec: EncoderSpec, feats, proj) -> bool:
+def _token_ce_fused(spec: EncoderSpec, feats, proj, task_embed, pos_table) -> bool:
     """Does this configuration evaluate EncoderSpec.token_ce in its kernels (egx_encoder_token_ce_ok)? Probed with the real feature / projection
     tensors; the weight cache only has to exist."""
-    if spec.wcache is None or spec.deterministic or not spec.out_tokens:
+    if spec.wcache is None or spec.deterministic or not spec.out_tokens or not all(f.is_cuda and f.dim() == 3 for f in feats):
         return False
     lib = _lib.load()
-    nseg = len(spec.segments)
-    segs = (Segment * nseg)()
-    pi = 0
-    for i, (ss, f) in enumerate(zip(spec.segments, feats)):
-        if not (f.is_cuda and f.dim() == 3):
-            return False
-        segs[i].feat, segs[i].T, segs[i].d_in = ptr(f), ss.T, ss.d_in
-        segs[i].feat_bf16, segs[i].pool = int(f.dtype == torch.bfloat16), int(ss.pool)
-        if ss.has_proj:
-            segs[i].proj_w, segs[i].proj_b = ptr(proj[2 * pi]), ptr(proj[2 * pi + 1])
-            pi += 1
+    segs = _segments(spec, feats, proj, task_embed, pos_table, feats[0].shape[0])
     cfg = spec.config()
     if lib.egx_encoder_impl(C.byref(cfg), segs, feats[0].shape[0]) != EGX_IMPL_FUSED:
         return False
@@ -1219,8 +1104,7 @@ def encoder_token_ce(spec: EncoderSpec, feats: Sequence[torch.Tensor], task_embe
     clip-major order, as encoder(...).reshape(B * out_tokens, d) has them): the ASD task's lossAV on the translator's per-frame output
     (HHI/tasks/asd/video_task_taskspecific.py:24,33). Where the per-clip kernels can, the encoder launches evaluate it themselves
     (egx_token_ce: two launches less per step); elsewhere encoder() + linear_cross_entropy()."""
-    import dataclasses
-    if _token_ce_fused(spec, feats, proj):
+    if _token_ce_fused(spec, feats, proj, task_embed, pos_table):
         spec = dataclasses.replace(spec, token_ce=int(fc_w.shape[0]))
         out = EncoderFn.apply(spec, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, fc_w, fc_b, target, class_weight)
         return out[1:]

@@ -102,15 +102,8 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
                                 x[:, 2 * T:3 * T].reshape(-1, self.dim)), dim=0)
         return x.permute(1, 0, 2)
 
-    def _check_inference(self, what):
-        if self.training:
-            raise ValueError(f"ragged batches are inference-only: call model.eval() before passing {what}")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
-                             "(or with every parameter frozen)")
-
     def _encode_features_ragged(self, task, feats, segs, projs, lengths):
-        self._check_inference("lengths=")
+        self._egx_check_inference("lengths=")
         lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segs])
         if task == 'asd' and not bool((lens == lens[:, :1]).all()):
             b = int((lens != lens[:, :1]).any(1).nonzero()[0, 0])
@@ -173,7 +166,7 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         (or through a feature cache) and pad their features here."""
         assert task in ['lam', 'ttm', 'asd']
         if lengths is not None:
-            self._check_inference("lengths=")
+            self._egx_check_inference("lengths=")
         encoded_x = self.encode_features(task, lam_feat, ttm_feat, asd_feat, lengths=lengths)
         dev = lam_feat.device
         if task == 'asd':

@@ -110,6 +110,26 @@ class TranslatorMixin:
         self._egx_step += 1
         return (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._egx_step * 0xD1B54A32D192ED03) & (2**63 - 1)
 
+    def _egx_spec(self, segments, encoder: nn.TransformerEncoder, ln: nn.LayerNorm, projs, head, **call):
+        """(EncoderSpec, projection tensors, head tensors) of an encoder call: the shapes of `encoder` / `ln` / `head`, the model's compute and
+        implementation, and the call's own fields (`call`)."""
+        layer0 = encoder.layers[0]
+        # impl "auto": functional.EncoderFn steers around the fused kernels when a learned `pe` needs a gradient
+        spec = EncoderSpec(d_model=ln.normalized_shape[0], n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
+                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps, compute=self.egx_compute, impl=self.egx_impl,
+                           head_n_out=head[1].out_features if head is not None else 0, **call)
+        proj_t = [t for s, p in zip(segments, projs) if s.has_proj for t in (p.weight, p.bias)]
+        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        return spec, proj_t, head_t
+
+    def _egx_check_inference(self, what: str):
+        """Ragged batches are inference-only: eval mode, and no autograd graph over the parameters."""
+        if self.training:
+            raise ValueError(f"ragged batches are inference-only: call model.eval() before passing {what}")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
+                             "(or with every parameter frozen)")
+
     def _egx_encode(self, feats: Sequence[torch.Tensor], segments: List[SegmentSpec], *, encoder: nn.TransformerEncoder,
                     ln: nn.LayerNorm, projs: Sequence[Optional[nn.Linear]], task_embed: Optional[torch.Tensor],
                     pos_table: Optional[torch.Tensor], p_drop: float, p_pos: float = 0.0, p_feat: float = 0.0,
@@ -126,29 +146,17 @@ class TranslatorMixin:
         if lengths is not None:
             return self._egx_encode_ragged(feats, segments, lengths, encoder=encoder, ln=ln, projs=projs, task_embed=task_embed,
                                            pos_table=pos_table, head=head, ce=ce, token_ce=token_ce)
-        layer0 = encoder.layers[0]
-        d = ln.normalized_shape[0]
         seed_dev = getattr(self, "_egx_seed_dev", None)
         wcache = getattr(self, "_egx_wcache", None)
         # device seed: advanced by the forward's first launch (1) or, with a frozen weight cache (no launch in front of the forward), by the
         # backward behind its last reader (2)
         adv = 0 if (seed_dev is None or not self.training) else (2 if (wcache is not None and wcache.frozen and torch.is_grad_enabled()) else 1)
-        impl = self.egx_impl    # "auto": functional.EncoderFn steers around the fused kernels when a learned `pe` needs a gradient
-        spec = EncoderSpec(d_model=d, n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
-                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps,
-                           compute=self.egx_compute, impl=impl,
-                           p_drop=p_drop, p_pos=p_pos, p_feat=p_feat,
-                           training=bool(self.training), seed=self._egx_seed() if self.training else 0,
-                           seed_ptr=seed_dev.data_ptr() if seed_dev is not None else 0,
-                           head_n_out=head[1].out_features if head is not None else 0,
-                           advance_seed=adv,   # fresh masks per (replayed) step
-                           defer_small=bool(self.egx_defer_small), deterministic=bool(self.egx_deterministic),
-                           out_tokens=int(out_tokens), wcache=wcache, ce=ce is not None)
-        proj_t = []
-        for s, p in zip(segments, projs):
-            if s.has_proj:
-                proj_t += [p.weight, p.bias]
-        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        spec, proj_t, head_t = self._egx_spec(segments, encoder, ln, projs, head, p_drop=p_drop, p_pos=p_pos, p_feat=p_feat,
+                                              training=bool(self.training), seed=self._egx_seed() if self.training else 0,
+                                              seed_ptr=seed_dev.data_ptr() if seed_dev is not None else 0,
+                                              advance_seed=adv,   # fresh masks per (replayed) step
+                                              defer_small=bool(self.egx_defer_small), deterministic=bool(self.egx_deterministic),
+                                              out_tokens=int(out_tokens), wcache=wcache, ce=ce is not None)
         if ce is not None and head is None:
             raise ValueError("the fused cross entropy needs the pooled head")
         if token_ce is not None:
@@ -160,24 +168,11 @@ class TranslatorMixin:
                              encoder_layer_tensors(encoder), head_t, ce=ce)
 
     def _egx_encode_ragged(self, feats, segments, lengths, *, encoder, ln, projs, task_embed, pos_table, head, ce, token_ce):
-        if self.training:
-            raise ValueError("ragged batches are inference-only: call model.eval() before passing lengths=")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
-                             "(or with every parameter frozen)")
+        self._egx_check_inference("lengths=")
         if ce is not None or token_ce is not None:
             raise ValueError("ragged batches are inference-only: no fused loss (target= / lossav=); apply the loss to the returned outputs")
-        B = feats[0].shape[0]
-        lens = F_egx.ragged_lengths(lengths, B, [s.T for s in segments])
-        layer0 = encoder.layers[0]
-        spec = EncoderSpec(d_model=ln.normalized_shape[0], n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
-                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps, compute=self.egx_compute, impl=self.egx_impl,
-                           head_n_out=head[1].out_features if head is not None else 0, wcache=getattr(self, "_egx_wcache", None))
-        proj_t = []
-        for s, p in zip(segments, projs):
-            if s.has_proj:
-                proj_t += [p.weight, p.bias]
-        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segments])
+        spec, proj_t, head_t = self._egx_spec(segments, encoder, ln, projs, head, wcache=getattr(self, "_egx_wcache", None))
         return F_egx.encoder_ragged(spec, list(feats), lens, task_embed, pos_table, ln.weight, ln.bias, proj_t,
                                     encoder_layer_tensors(encoder), head_t)
 
@@ -189,20 +184,12 @@ class TranslatorMixin:
             raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
         if ce is not None and head is None:
             raise ValueError("the fused cross entropy needs the pooled head")
-        layer0 = encoder.layers[0]
         seed_dev = getattr(self, "_egx_seed_dev", None)
         training = bool(self.training)
-        spec = EncoderSpec(d_model=ln.normalized_shape[0], n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
-                           n_layers=len(encoder.layers), segments=segments, ln_eps=ln.eps, compute=self.egx_compute, impl=self.egx_impl,
-                           p_drop=p_drop, p_pos=p_pos, training=training, seed=self._egx_seed() if training else 0,
-                           seed_ptr=seed_dev.data_ptr() if seed_dev is not None else 0,
-                           advance_seed=1 if (seed_dev is not None and training) else 0,     # fresh masks per call
-                           head_n_out=head[1].out_features if head is not None else 0,
-                           deterministic=bool(self.egx_deterministic), ce=ce is not None)
-        proj_t = []
-        for s, p in zip(segments, projs):
-            if s.has_proj:
-                proj_t += [p.weight, p.bias]
-        head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
+        spec, proj_t, head_t = self._egx_spec(segments, encoder, ln, projs, head, p_drop=p_drop, p_pos=p_pos, training=training,
+                                              seed=self._egx_seed() if training else 0,
+                                              seed_ptr=seed_dev.data_ptr() if seed_dev is not None else 0,
+                                              advance_seed=1 if (seed_dev is not None and training) else 0,     # fresh masks per call
+                                              deterministic=bool(self.egx_deterministic), ce=ce is not None)
         return F_egx.encoder_ragged_train(spec, list(feats), lengths, task_embed, pos_table, ln.weight, ln.bias, proj_t,
                                           encoder_layer_tensors(encoder), head_t, ce=ce)

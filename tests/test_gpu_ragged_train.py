@@ -349,3 +349,26 @@ def test_ragged_train_device_seed_and_host_seed(egx_lib, cuda):
     d = model.forward_features_ragged(*feats, lengths=lengths).detach()
     torch.cuda.synchronize()
     assert not torch.equal(c, d)                    # the device seed advances: fresh masks per call
+
+
+@pytest.mark.parametrize("compute", ["f32s", "bf16"])
+@pytest.mark.parametrize("kind", ["ttm3", "asd"])
+def test_ragged_inference_call_matches_the_training_call_in_eval(egx_lib, cuda, kind, compute):
+    """Eval mode under no_grad: forward_features(lengths=) (egx_ragged_fwd, filling then hitting the weight cache) and forward_features_ragged
+    (egx_ragged_train_fwd with training = 0) run one forward body: bit-identical logits (ttm3, with the head) or rows (asd, head-less)."""
+    from egot2_amd import functional as F_egx
+    model, _ = _model(kind, 2, compute, cuda, seed=941)
+    model.enable_weight_cache().eval()
+    feats, lengths = _pad(_clips(1950, [(15, 15, 15), (60, 61, 62), (16, 16, 17), (150, 150, 150), (1, 2, 160)]), cuda)
+    with torch.no_grad():
+        outs = []
+        for _ in range(2):
+            outs.append(model.forward_features(*feats, lengths=lengths))
+            assert F_egx.last_encoder_impl() == "ragged"
+        assert model._egx_wcache.packs == 1 and model._egx_wcache.hits == 1
+        outs.append(model.forward_features_ragged(*feats, lengths=lengths))
+        assert F_egx.last_encoder_impl() == "ragged"
+    torch.cuda.synchronize()
+    assert not torch.isnan(outs[0]).any()
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0])
