@@ -803,6 +803,8 @@ static int encoder_fwd_impl(const egx_config* cfg, const egx_segment* segs, cons
                 else if (touch && training) { touch_add(fp.touch, PL.layer[l].lin2_wt, ffn_pb); touch_add(fp.touch, PL.layer[l].lin1_wt, ffn_pb); }
                 if (ffn_cut_forward(fp, l, comp, st)) return 1;
             }
+            // deterministic mode keeps the cross entropy out of the epilogue: its own launch on the logits, as in the one-launch mode below
+            if (ce && with_head && !ce_fused) return weighted_ce(logits_out, ce->target, ce->class_weight, B, head->n_out, ce->loss, ce->d_logits, st);
             return 0;
         }
         if (!tiled) {

@@ -73,6 +73,11 @@ def self_attention(x: torch.Tensor, in_w, in_b, out_w, out_b, n_heads: int, attn
     return linear(o, out_w, out_b)
 
 
+# Optional observer of every encoder layer's FFN pre-activation: relu_probe(prefix, a) is called with the layer's key prefix and
+# a = linear1(x) (..., S, d_ff) just before the ReLU (tests/fp32_grade.py places linear1.bias away from the kink with it). None: no call.
+relu_probe = None
+
+
 def _m(x: torch.Tensor, masks, name: str) -> torch.Tensor:
     """Apply an explicit dropout keep-scale (0 or 1 / (1 - p) per element) when the caller supplies one."""
     if masks is None or masks.get(name) is None:
@@ -91,7 +96,10 @@ def encoder_layer(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str, n_h
                        g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"), n_heads,
                        None if masks is None else masks.get("attn"))
     x = layer_norm(x + _m(a, masks, "res1"), g("norm1.weight"), g("norm1.bias"), eps)
-    h = _m(torch.relu(linear(x, g("linear1.weight"), g("linear1.bias"))), masks, "ffn")
+    a = linear(x, g("linear1.weight"), g("linear1.bias"))
+    if relu_probe is not None:
+        relu_probe(prefix, a)
+    h = _m(torch.relu(a), masks, "ffn")
     f = linear(h, g("linear2.weight"), g("linear2.bias"))
     return layer_norm(x + _m(f, masks, "res2"), g("norm2.weight"), g("norm2.bias"), eps)
 

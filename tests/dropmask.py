@@ -117,3 +117,22 @@ def encoder_masks(seed: int, impl: str, B: int, seg_T, d: int, H: int, d_ff: int
             "res2": keep_scale(site_key(seed, layer, SITE_RES2), tok_rows, cols_d, p_drop),
         })
     return masks
+
+
+def ragged_clip_masks(seed, tok0, S, L, p, p_pos, H=4, d=128, d_ff=2048):
+    """The keep-scales of ONE clip of a ragged batch (first packed token tok0, S tokens) in the oracle's `masks` layout (batch of 1)."""
+    s = np.arange(S, dtype=np.int64)
+    rows = (tok0 + s)[None, :]
+    cols = np.arange(d, dtype=np.int64)
+    masks = {"layers": []}
+    if p_pos > 0:
+        masks["pos"] = keep_scale(site_key(seed, 0, SITE_POS), rows, cols, p_pos)
+    attn_rows = (tok0 * H + np.arange(H, dtype=np.int64)[:, None] * S + s[None, :])[None]     # (1, H, S)
+    for l in range(L):
+        masks["layers"].append(None if p <= 0 else {
+            "attn": keep_scale(site_key(seed, l, SITE_ATTN), attn_rows, s, p),
+            "res1": keep_scale(site_key(seed, l, SITE_RES1), rows, cols, p),
+            "ffn": keep_scale(site_key(seed, l, SITE_FFN), rows, np.arange(d_ff, dtype=np.int64), p),
+            "res2": keep_scale(site_key(seed, l, SITE_RES2), rows, cols, p),
+        })
+    return masks

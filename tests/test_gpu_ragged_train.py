@@ -2,14 +2,14 @@
 their own lengths, every clip keeping all of its frames. The oracle is built per clip on the UNPADDED clip (oracle/translator_ref.py, fp64),
 the clips' logits concatenated and the weighted cross entropy taken over the batch. Tolerances are those of tests/test_gpu_tiled.py: logits
 1e-3 / 1e-2 and every gradient 1e-2 / 8e-2 relative, for f32s / bf16. Train-mode cases use the masks the ragged kernels draw, restated
-here from tests/dropmask.py's generator with the ragged keying (row tok0_b + s; attention row 4 tok0_b + h S_b + query).
+by tests/dropmask.py ragged_clip_masks with the ragged keying (row tok0_b + s; attention row 4 tok0_b + h S_b + query).
 The padded frames of every batch are NaN unless a test says otherwise: a kernel that reads one shows up at once."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import translator_ref as tr
-from tests import dropmask as dm
+from tests.dropmask import ragged_clip_masks
 from tests.util import hhi_args, max_err, rel_err, seeded_feats, seeded_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -51,25 +51,6 @@ def _pad(clips, cuda, fill=float("nan"), grad=False):
             t[b, :c[k].shape[0]] = c[k]
         feats.append(t.to(cuda).requires_grad_(grad))
     return feats, torch.tensor([[c[k].shape[0] for k in range(K)] for c in clips])
-
-
-def ragged_clip_masks(seed, tok0, S, L, p, p_pos, H=4, d=128, d_ff=2048):
-    """The keep-scales of ONE clip of a ragged batch (first packed token tok0, S tokens) in the oracle's `masks` layout (batch of 1)."""
-    s = np.arange(S, dtype=np.int64)
-    rows = (tok0 + s)[None, :]
-    cols = np.arange(d, dtype=np.int64)
-    masks = {"layers": []}
-    if p_pos > 0:
-        masks["pos"] = dm.keep_scale(dm.site_key(seed, 0, dm.SITE_POS), rows, cols, p_pos)
-    attn_rows = (tok0 * H + np.arange(H, dtype=np.int64)[:, None] * S + s[None, :])[None]     # (1, H, S)
-    for l in range(L):
-        masks["layers"].append(None if p <= 0 else {
-            "attn": dm.keep_scale(dm.site_key(seed, l, dm.SITE_ATTN), attn_rows, s, p),
-            "res1": dm.keep_scale(dm.site_key(seed, l, dm.SITE_RES1), rows, cols, p),
-            "ffn": dm.keep_scale(dm.site_key(seed, l, dm.SITE_FFN), rows, np.arange(d_ff, dtype=np.int64), p),
-            "res2": dm.keep_scale(dm.site_key(seed, l, dm.SITE_RES2), rows, cols, p),
-        })
-    return masks
 
 
 def _oracle_ttm(sd, clips, target, L=1, seed=0, p=0.0, p_pos=0.0):
