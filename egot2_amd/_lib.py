@@ -129,6 +129,12 @@ SIGNATURES = {
                                  C.c_int, C.c_uint64, _fp]),
     "egx_ragged_encode_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t)]),
     "egx_ragged_encode": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.c_int, _fp, C.c_int, _fp, _fp]),
+    "egx_ragged_encode_train_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_size_t)]),
+    "egx_ragged_encode_train_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.c_int, _fp, C.c_int, _fp,
+                                              C.c_int, C.c_uint64, _fp]),
+    "egx_ragged_encode_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.c_int, _fp, C.c_int, _fp, _fp,
+                                        C.POINTER(SegmentGrads), _fp, _fp, C.POINTER(LayerGrads), C.c_int, C.c_uint64, _fp]),
     "egx_translator_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.POINTER(Head),
                                      C.c_int, _fp, _fp, _fp, C.POINTER(SegmentGrads), _fp, _fp, C.POINTER(LayerGrads),
                                      C.POINTER(HeadGrads), C.c_int, C.c_uint64, _fp]),
@@ -145,6 +151,11 @@ SIGNATURES = {
     "egx_decoder_ragged_workspace": (C.c_int, [C.POINTER(DecConfig), C.c_int, _fp, C.POINTER(C.c_size_t)]),
     "egx_decoder_ragged_fwd": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int, _fp,
                                          _fp, _fp]),
+    "egx_decoder_ragged_train_workspace": (C.c_int, [C.POINTER(DecConfig), C.c_int, _fp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "egx_decoder_ragged_train_fwd": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int,
+                                               _fp, _fp, _fp, C.c_int, C.c_uint64, _fp]),
+    "egx_decoder_ragged_bwd": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, C.POINTER(DecLayer), _fp, C.c_int, _fp, _fp, _fp, _fp, _fp,
+                                         C.POINTER(DecLayerGrads), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_uint64, _fp]),
     "egx_decoder_bwd": (C.c_int, [C.POINTER(DecConfig), _fp, C.POINTER(DecLayer), _fp, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                   C.POINTER(DecLayerGrads), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_uint64, _fp]),
     "egx_comm_unique_id": (C.c_int, [_fp]),

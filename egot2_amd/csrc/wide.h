@@ -91,6 +91,8 @@ struct WideLnBwdParams {
     int mask_dx32 = 0;            // 1: dx32 also gets the out-mask (feature dropout before the shared LN)
     float* partials = nullptr; int blocks = 0;   // set by wide_ln_bwd
     float* dw = nullptr; float* db = nullptr; float* dbias = nullptr; float* dadd = nullptr;   // += targets (any may be null)
+    // ragged batches (wide_ln_bwd_mapped): row `row` reads dy[dy_map[row]] (instead of the T / S / off remap) and keys the dy mask on that row
+    const int* dy_map = nullptr;
 };
 size_t wide_ln_bwd_scratch(int rows, int d);
 // Deferred row reductions (round 5): the second stage of every two-stage column sum of a backward — LayerNorm parameter gradients,
@@ -105,6 +107,7 @@ constexpr int WIDE_ROWRED_MAX = 48;
 struct WideRowReduceBatch { WideRowReduceDesc d[WIDE_ROWRED_MAX]; int n = 0, total_blocks = 0; };
 int wide_row_reduce_flush(WideRowReduceBatch& b, hipStream_t st);
 int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer = nullptr);
+int wide_ln_bwd_mapped(WideLnBwdParams p, void* scratch, hipStream_t st);
 
 // out[c] += sum_r x[r][c] over a bf16 (rows, ld) matrix, deterministic two-stage reduction; scratch >= wide_colsum_scratch
 size_t wide_colsum_scratch(int rows, int cols);
@@ -136,6 +139,12 @@ int wide_attn_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_bwd(const WideAttnParams& p, hipStream_t st);
 // inference forward over the B clips of p.clips, all of one kernel class (wide_attn_ragged_class): p.S = their longest clip
 int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st);
+// training over the same clip lists: the forward with dropout on the probabilities, and the backward (p.d_out -> p.d_qkv, every packed row
+// written once; the long class also reads p.out and writes p.delta, both with the log-sum-exp's layout: (clip, head) rows from H tok0 + h S_c).
+// Dropout rows key on (clip's index in the BATCH, head, query) with the row stride of the clip's class (128; 512 for the long kernels), so a
+// batch of equal-length clips draws the masks of the uniform call.
+int wide_attn_ragged_train_fwd(const WideAttnParams& p, hipStream_t st);
+int wide_attn_ragged_bwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_ragged_class(int S, int dh);      // 0: S <= 64, 1: 64 < S <= 128, 2: the long kernel, -1: unsupported
 
 }  // namespace egx

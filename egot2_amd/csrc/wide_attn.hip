@@ -164,7 +164,8 @@ __global__ __launch_bounds__(256) void wide_attn_ragged_fwd_kernel(WideAttnParam
     unsigned char* Kimg = smem;
     unsigned char* Vimg = smem + SP * RS;
     const int bh = blockIdx.x, h = bh % p.H;
-    const int* rec = p.rtab + (size_t)p.clips[bh / p.H] * WIDE_RG_REC;
+    const int clip = p.clips[bh / p.H];
+    const int* rec = p.rtab + (size_t)clip * WIDE_RG_REC;
     const int S = rec[WRG_S], tok0 = rec[WRG_TOK0], d = p.d, ld = 3 * d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
     const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void wide_attn_ragged_fwd_kernel(WideAttnParam
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pv = sc[kt][e] * inv;
-                if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)(bh * 128 + query), (uint32_t)(kt * 16 + 4 * g + e), p.drop_thresh, p.drop_inv);
+                if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)((clip * p.H + h) * 128 + query), (uint32_t)(kt * 16 + 4 * g + e), p.drop_thresh, p.drop_inv);
                 sc[kt][e] = pv;
             }
         f32x4 oc[NCT];
@@ -273,6 +274,164 @@ __global__ __launch_bounds__(NKT * 64) void wide_attn_bwd_kernel(WideAttnParams 
     const float scale = rsqrtf((float)DH);
     const int nt = (S + 15) / 16;
     bf16_t* gq = p.d_qkv + (size_t)b * S * ld + h * DH;
+
+    // ---- pass T: rows = key, cols = query; this wave's query tiles
+    for (int qt = wave; qt < nt; qt += NW) {
+        const int query = qt * 16 + r;
+        bf16x8 qf[NKB], df[NKB];
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            qf[kb] = rd128(Qimg + query * RS + (kb * 32 + 8 * g) * 2);
+            df[kb] = rd128(Dimg + query * RS + (kb * 32 + 8 * g) * 2);
+        }
+        const float lq = lse_s[query];
+        f32x4 pt[NKT], dpt[NKT];
+        float dl = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            f32x4 a = f32x4{0, 0, 0, 0}, c = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) {
+                a = mfma(rd128(Kimg + (kt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), qf[kb], a);
+                c = mfma(rd128(Vimg + (kt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), df[kb], c);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                int key = kt * 16 + 4 * g + e;
+                float pv = (key < S && query < S) ? __expf(a[e] * scale - lq) : 0.f;
+                float ks = p.drop_thresh ? drop_scale(dkey, (uint32_t)(bh * 128 + query), (uint32_t)key, p.drop_thresh, p.drop_inv) : 1.f;
+                float dm = c[e] * ks;
+                dl += pv * dm;
+                a[e] = pv; c[e] = dm;
+            }
+            pt[kt] = a; dpt[kt] = c;
+            __builtin_amdgcn_sched_barrier(0);      // keep the fragment reads of tile kt + 1 behind this tile (register budget)
+        }
+        dl += __shfl_xor(dl, 16, 64);
+        dl += __shfl_xor(dl, 32, 64);
+        if (g == 0) delta_s[query] = dl;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dpt[kt][e] = pt[kt][e] * (dpt[kt][e] - dl) * scale;       // dS^T
+        f32x4 dq[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) dq[ct] = f32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int kb2 = 0; kb2 < NKT / 2; ++kb2) {
+            const bf16x8 sf = chain(dpt[2 * kb2], dpt[2 * kb2 + 1]);
+            const unsigned char* k0 = Kimg + (kb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) dq[ct] = mfma(rd_tr2(k0 + ct * 32, k0 + 16 * RS + ct * 32), sf, dq[ct]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (query < S) {
+            bf16_t* o = gq + (size_t)query * ld + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+                *reinterpret_cast<uint2*>(o + ct * 16) = make_uint2(pk(dq[ct][0], dq[ct][1]), pk(dq[ct][2], dq[ct][3]));
+        }
+    }
+    __syncthreads();
+
+    // ---- pass N: rows = query, cols = key; this wave's key tiles
+    for (int kt = wave; kt < nt; kt += NW) {
+        const int key = kt * 16 + r;
+        bf16x8 kf[NKB], vf[NKB];
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            kf[kb] = rd128(Kimg + key * RS + (kb * 32 + 8 * g) * 2);
+            vf[kb] = rd128(Vimg + key * RS + (kb * 32 + 8 * g) * 2);
+        }
+        f32x4 pn[NKT], dsn[NKT];
+#pragma unroll
+        for (int qt = 0; qt < NKT; ++qt) {
+            f32x4 a = f32x4{0, 0, 0, 0}, c = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) {
+                a = mfma(rd128(Qimg + (qt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), kf[kb], a);
+                c = mfma(rd128(Dimg + (qt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), vf[kb], c);
+            }
+            const float4 l4 = *reinterpret_cast<const float4*>(lse_s + qt * 16 + 4 * g);
+            const float4 d4 = *reinterpret_cast<const float4*>(delta_s + qt * 16 + 4 * g);
+            const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq4[4] = {d4.x, d4.y, d4.z, d4.w};
+            // the lane's four elements are four mask ROWS (queries) of one key: one hash per lane and tile (common.h tile_keep_rows)
+            uint32_t m4[4] = {0xFu, 0xFu, 0xFu, 0xFu};
+            if (p.drop_thresh) tile_keep_rows(dkey, (uint32_t)(bh * 128 + qt * 16), (uint32_t)(kt * 4), r, g, p.drop_thresh, m4);
+            const float kinv = p.drop_thresh ? p.drop_inv : 1.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                int query = qt * 16 + 4 * g + e;
+                float pv = (key < S && query < S) ? __expf(a[e] * scale - lq[e]) : 0.f;
+                float ks = ((m4[e] >> (r & 3)) & 1u) ? kinv : 0.f;
+                a[e] = pv * ks;                                   // dropped P
+                c[e] = pv * (ks * c[e] - dq4[e]) * scale;         // dS
+            }
+            pn[qt] = a; dsn[qt] = c;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        f32x4 dk[NCT], dv[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) { dk[ct] = f32x4{0, 0, 0, 0}; dv[ct] = f32x4{0, 0, 0, 0}; }
+#pragma unroll
+        for (int qb2 = 0; qb2 < NKT / 2; ++qb2) {
+            const bf16x8 pf = chain(pn[2 * qb2], pn[2 * qb2 + 1]);
+            const bf16x8 sf = chain(dsn[2 * qb2], dsn[2 * qb2 + 1]);
+            const int roff = (qb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                dv[ct] = mfma(rd_tr2(Dimg + roff + ct * 32, Dimg + roff + 16 * RS + ct * 32), pf, dv[ct]);
+                dk[ct] = mfma(rd_tr2(Qimg + roff + ct * 32, Qimg + roff + 16 * RS + ct * 32), sf, dk[ct]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (key < S) {
+            bf16_t* o = gq + (size_t)key * ld + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                *reinterpret_cast<uint2*>(o + d + ct * 16) = make_uint2(pk(dk[ct][0], dk[ct][1]), pk(dk[ct][2], dk[ct][3]));
+                *reinterpret_cast<uint2*>(o + 2 * d + ct * 16) = make_uint2(pk(dv[ct][0], dv[ct][1]), pk(dv[ct][2], dv[ct][3]));
+            }
+        }
+    }
+}
+
+// Ragged batches (wide_attn_ragged_bwd): the backward above for workgroup (i, h) = clip p.clips[i] of the batch table, with its own length, its
+// rows from tok0 on (log-sum-exp rows from H tok0 + h S) and the dropout rows of ITS batch position. Every packed row of d_qkv belongs to exactly
+// one clip and is written exactly once. A separate copy, as wide_attn_ragged_fwd_kernel.
+template <int DH, int NKT>
+__global__ __launch_bounds__(NKT * 64) void wide_attn_ragged_bwd_kernel(WideAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int RS = DH * 2 + 32, SP = NKT * 16, NKB = DH / 32, NCT = DH / 16, NW = NKT, NTH = NW * 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* Qimg = smem;
+    unsigned char* Kimg = Qimg + SP * RS;
+    unsigned char* Vimg = Kimg + SP * RS;
+    unsigned char* Dimg = Vimg + SP * RS;                    // dO
+    float* lse_s = reinterpret_cast<float*>(Dimg + SP * RS); // [SP]
+    float* delta_s = lse_s + SP;                             // [SP]
+    const int h = blockIdx.x % p.H, clip = p.clips[blockIdx.x / p.H];
+    const int* rec = p.rtab + (size_t)clip * WIDE_RG_REC;
+    const int S = rec[WRG_S], tok0 = rec[WRG_TOK0], d = p.d, ld = 3 * d;
+    const int bh = clip * p.H + h;          // dropout rows: (clip of the batch, head, query)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
+    {
+        ImageRegs<DH, SP, NTH> rq, rk, rv, rd;
+        image_fetch<DH, SP, NTH>(rq, base, ld, S);
+        image_fetch<DH, SP, NTH>(rk, base + d, ld, S);
+        image_fetch<DH, SP, NTH>(rv, base + 2 * d, ld, S);
+        image_fetch<DH, SP, NTH>(rd, p.d_out + (size_t)tok0 * d + h * DH, d, S);
+        image_store<DH, SP, NTH>(rq, Qimg);
+        image_store<DH, SP, NTH>(rk, Kimg);
+        image_store<DH, SP, NTH>(rv, Vimg);
+        image_store<DH, SP, NTH>(rd, Dimg);
+    }
+    for (int i = threadIdx.x; i < SP; i += NTH) lse_s[i] = i < S ? p.lse[(size_t)tok0 * p.H + (size_t)h * S + i] : 0.f;
+    __syncthreads();
+    const float scale = rsqrtf((float)DH);
+    const int nt = (S + 15) / 16;
+    bf16_t* gq = p.d_qkv + (size_t)tok0 * ld + h * DH;
 
     // ---- pass T: rows = key, cols = query; this wave's query tiles
     for (int qt = wave; qt < nt; qt += NW) {
@@ -508,7 +667,8 @@ __global__ __launch_bounds__(WAL_NTH) void wide_attn_long_ragged_fwd_kernel(Wide
     constexpr int RS = DH * 2 + 32, NKB = DH / 32, NCT = DH / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int bh = blockIdx.x, h = bh % p.H;
-    const int* rec = p.rtab + (size_t)p.clips[bh / p.H] * WIDE_RG_REC;
+    const int clip = p.clips[bh / p.H];
+    const int* rec = p.rtab + (size_t)clip * WIDE_RG_REC;
     const int S = rec[WRG_S], tok0 = rec[WRG_TOK0];
     // the grid's query split is sized by the class's longest clip: a workgroup past this clip's last query tile has nothing to do
     if ((int)blockIdx.y * WAL_NW * 16 >= S) return;
@@ -564,7 +724,7 @@ __global__ __launch_bounds__(WAL_NTH) void wide_attn_long_ragged_fwd_kernel(Wide
                 for (int e = 0; e < 4; ++e) {
                     float pv = __builtin_amdgcn_exp2f(sc[j][e] - mn);
                     l += pv;
-                    if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)(bh * 512 + query), (uint32_t)(kb2 * 32 + j * 16 + 4 * g + e), p.drop_thresh, vinv);
+                    if (p.drop_thresh) pv *= drop_scale(dkey, (uint32_t)((clip * p.H + h) * 512 + query), (uint32_t)(kb2 * 32 + j * 16 + 4 * g + e), p.drop_thresh, vinv);
                     sc[j][e] = pv;
                 }
             const bf16x8 pf = chain(sc[0], sc[1]);
@@ -737,6 +897,166 @@ __global__ __launch_bounds__(WAL_NTH) void wide_attn_long_dkv_kernel(WideAttnPar
     }
 }
 
+// ragged batches: the query side of the long backward for clip p.clips[i] (delta rows as the log-sum-exp rows: H tok0 + h S)
+template <int DH>
+__global__ __launch_bounds__(WAL_NTH) void wide_attn_long_ragged_dq_kernel(WideAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int RS = DH * 2 + 32, NKB = DH / 32, NCT = DH / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int h = blockIdx.x % p.H, clip = p.clips[blockIdx.x / p.H];
+    const int* rec = p.rtab + (size_t)clip * WIDE_RG_REC;
+    const int S = rec[WRG_S], tok0 = rec[WRG_TOK0];
+    if ((int)blockIdx.y * WAL_NW * 16 >= S) return;      // (the grid's query split is sized by the class's longest clip)
+    const int SP = (S + 31) & ~31, d = p.d, ld = 3 * d, bh = clip * p.H + h;
+    const size_t st0 = (size_t)tok0 * p.H + (size_t)h * S;      // this (clip, head)'s log-sum-exp / delta rows
+    unsigned char* Kimg = smem;
+    unsigned char* Vimg = smem + SP * RS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
+    image_stage<DH>(Kimg, base + d, ld, S, SP);
+    image_stage<DH>(Vimg, base + 2 * d, ld, S, SP);
+    __syncthreads();
+    const float scale = rsqrtf((float)DH), c2 = scale * 1.4426950408889634f;
+    const int nqt = (S + 15) / 16, nkb2 = SP / 32;
+    bf16_t* gq = p.d_qkv + (size_t)tok0 * ld + h * DH;
+    for (int qt = blockIdx.y * WAL_NW + wave; qt < nqt; qt += WAL_NW * gridDim.y) {
+        const int query = qt * 16 + r;
+        const int qrow = query < S ? query : S - 1;
+        bf16x8 qf[NKB], df[NKB];
+        float delta = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            qf[kb] = *reinterpret_cast<const bf16x8*>(base + (size_t)qrow * ld + kb * 32 + 8 * g);
+            df[kb] = *reinterpret_cast<const bf16x8*>(p.d_out + ((size_t)tok0 + qrow) * d + h * DH + kb * 32 + 8 * g);
+            const bf16x8 of = *reinterpret_cast<const bf16x8*>(p.out + ((size_t)tok0 + qrow) * d + h * DH + kb * 32 + 8 * g);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                delta += __uint_as_float((uint32_t)(unsigned short)df[kb][e] << 16) * __uint_as_float((uint32_t)(unsigned short)of[e] << 16);
+        }
+        delta += __shfl_xor(delta, 16, 64);
+        delta += __shfl_xor(delta, 32, 64);
+        if (g == 0 && query < S) p.delta[st0 + query] = delta;
+        const float lq = p.lse[st0 + qrow] * 1.4426950408889634f;
+        f32x4 dq[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) dq[ct] = f32x4{0, 0, 0, 0};
+        for (int kb2 = 0; kb2 < nkb2; ++kb2) {
+            f32x4 ds[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f32x4 a = f32x4{0, 0, 0, 0}, c = f32x4{0, 0, 0, 0};
+#pragma unroll
+                for (int kb = 0; kb < NKB; ++kb) {
+                    a = mfma(rd128(Kimg + (kb2 * 32 + j * 16 + r) * RS + (kb * 32 + 8 * g) * 2), qf[kb], a);
+                    c = mfma(rd128(Vimg + (kb2 * 32 + j * 16 + r) * RS + (kb * 32 + 8 * g) * 2), df[kb], c);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = kb2 * 32 + j * 16 + 4 * g + e;
+                    const float pv = key < S ? __builtin_amdgcn_exp2f(a[e] * c2 - lq) : 0.f;
+                    const float ks = p.drop_thresh ? drop_scale(dkey, (uint32_t)(bh * 512 + query), (uint32_t)key, p.drop_thresh, p.drop_inv) : 1.f;
+                    ds[j][e] = pv * (ks * c[e] - delta) * scale;
+                }
+            }
+            const bf16x8 sf = chain(ds[0], ds[1]);
+            const unsigned char* k0 = Kimg + (kb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) dq[ct] = mfma(rd_tr2(k0 + ct * 32, k0 + 16 * RS + ct * 32), sf, dq[ct]);
+        }
+        if (query < S) {
+            bf16_t* o = gq + (size_t)query * ld + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+                *reinterpret_cast<uint2*>(o + ct * 16) = make_uint2(pk(dq[ct][0], dq[ct][1]), pk(dq[ct][2], dq[ct][3]));
+        }
+    }
+}
+
+// ragged batches: the key side of the long backward for clip p.clips[i]
+template <int DH>
+__global__ __launch_bounds__(WAL_NTH) void wide_attn_long_ragged_dkv_kernel(WideAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int RS = DH * 2 + 32, NKB = DH / 32, NCT = DH / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int h = blockIdx.x % p.H, clip = p.clips[blockIdx.x / p.H];
+    const int* rec = p.rtab + (size_t)clip * WIDE_RG_REC;
+    const int S = rec[WRG_S], tok0 = rec[WRG_TOK0];
+    if ((int)blockIdx.y * WAL_NW * 16 >= S) return;      // (before any barrier: the whole workgroup leaves)
+    const int SP = (S + 31) & ~31, d = p.d, ld = 3 * d, bh = clip * p.H + h;
+    const size_t st0 = (size_t)tok0 * p.H + (size_t)h * S;
+    unsigned char* Qimg = smem;
+    unsigned char* Dimg = smem + SP * RS;
+    float* lse_s = reinterpret_cast<float*>(Dimg + SP * RS);
+    float* delta_s = lse_s + SP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const bf16_t* base = p.qkv + (size_t)tok0 * ld + h * DH;
+    image_stage<DH>(Qimg, base, ld, S, SP);
+    image_stage<DH>(Dimg, p.d_out + (size_t)tok0 * d + h * DH, d, S, SP);
+    for (int i = threadIdx.x; i < SP; i += WAL_NTH) {
+        lse_s[i] = i < S ? p.lse[st0 + i] * 1.4426950408889634f : 0.f;
+        delta_s[i] = i < S ? p.delta[st0 + i] : 0.f;
+    }
+    __syncthreads();
+    const float scale = rsqrtf((float)DH), c2 = scale * 1.4426950408889634f;
+    const int nkt = (S + 15) / 16, nqb2 = SP / 32;
+    bf16_t* gq = p.d_qkv + (size_t)tok0 * ld + h * DH;
+    for (int kt = blockIdx.y * WAL_NW + wave; kt < nkt; kt += WAL_NW * gridDim.y) {
+        const int key = kt * 16 + r;
+        const int krow = key < S ? key : S - 1;
+        bf16x8 kf[NKB], vf[NKB];
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            kf[kb] = *reinterpret_cast<const bf16x8*>(base + (size_t)krow * ld + d + kb * 32 + 8 * g);
+            vf[kb] = *reinterpret_cast<const bf16x8*>(base + (size_t)krow * ld + 2 * d + kb * 32 + 8 * g);
+        }
+        f32x4 dk[NCT], dv[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) { dk[ct] = f32x4{0, 0, 0, 0}; dv[ct] = f32x4{0, 0, 0, 0}; }
+        for (int qb2 = 0; qb2 < nqb2; ++qb2) {
+            f32x4 pn[2], dsn[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int qt = 2 * qb2 + j;
+                f32x4 a = f32x4{0, 0, 0, 0}, c = f32x4{0, 0, 0, 0};
+#pragma unroll
+                for (int kb = 0; kb < NKB; ++kb) {
+                    a = mfma(rd128(Qimg + (qt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), kf[kb], a);
+                    c = mfma(rd128(Dimg + (qt * 16 + r) * RS + (kb * 32 + 8 * g) * 2), vf[kb], c);
+                }
+                const float4 l4 = *reinterpret_cast<const float4*>(lse_s + qt * 16 + 4 * g);
+                const float4 d4 = *reinterpret_cast<const float4*>(delta_s + qt * 16 + 4 * g);
+                const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq4[4] = {d4.x, d4.y, d4.z, d4.w};
+                uint32_t m4[4] = {0xFu, 0xFu, 0xFu, 0xFu};      // (common.h tile_keep_rows: one hash per lane and tile)
+                if (p.drop_thresh) tile_keep_rows(dkey, (uint32_t)(bh * 512 + qt * 16), (uint32_t)(kt * 4), r, g, p.drop_thresh, m4);
+                const float kinv = p.drop_thresh ? p.drop_inv : 1.f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int query = qt * 16 + 4 * g + e;
+                    const float pv = (key < S && query < S) ? __builtin_amdgcn_exp2f(a[e] * c2 - lq[e]) : 0.f;
+                    const float ks = ((m4[e] >> (r & 3)) & 1u) ? kinv : 0.f;
+                    pn[j][e] = pv * ks;
+                    dsn[j][e] = pv * (ks * c[e] - dq4[e]) * scale;
+                }
+            }
+            const bf16x8 pf = chain(pn[0], pn[1]), sf = chain(dsn[0], dsn[1]);
+            const int roff = (qb2 * 32 + 4 * g + (r >> 2)) * RS + 8 * (r & 3);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                dv[ct] = mfma(rd_tr2(Dimg + roff + ct * 32, Dimg + roff + 16 * RS + ct * 32), pf, dv[ct]);
+                dk[ct] = mfma(rd_tr2(Qimg + roff + ct * 32, Qimg + roff + 16 * RS + ct * 32), sf, dk[ct]);
+            }
+        }
+        if (key < S) {
+            bf16_t* o = gq + (size_t)key * ld + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                *reinterpret_cast<uint2*>(o + d + ct * 16) = make_uint2(pk(dk[ct][0], dk[ct][1]), pk(dk[ct][2], dk[ct][3]));
+                *reinterpret_cast<uint2*>(o + 2 * d + ct * 16) = make_uint2(pk(dv[ct][0], dv[ct][1]), pk(dv[ct][2], dv[ct][3]));
+            }
+        }
+    }
+}
+
 bool wide_attn_long_supported(int S, int dh) {
     // two images of ((S + 31) & ~31) x (2 dh + 32) bytes (+ the per-query statistics of the key side) in 160 KB of LDS
     if (S <= 128 || S > 512 || (dh != 32 && dh != 64)) return false;      // 512: the dropout row key is bh * 512 + query
@@ -818,7 +1138,7 @@ static int dispatch_attn(const WideAttnParams& p, bool bwd, hipStream_t st) {
     return 1;
 }
 
-// ---- ragged batches (inference) ----
+// ---- ragged batches ----
 int wide_attn_ragged_class(int S, int dh) {
     if (S >= 1 && S <= 64 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) return 0;
     if (S >= 1 && S <= 128 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) return 1;
@@ -857,9 +1177,8 @@ static int launch_attn_long_ragged(const WideAttnParams& p, hipStream_t st) {
     return 0;
 }
 
-int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
-    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_fwd: bad arguments");
-    EGX_CHECK(!p.drop_thresh, "wide_attn_ragged_fwd: inference only (no dropout)");
+// training forward (dropout on the probabilities, rows keyed by the clip's batch position) and inference forward: the same kernels
+static int attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
     if (p.B <= 0) return 0;
     const int dh = p.d / p.H, cls = wide_attn_ragged_class(p.S, dh);
     EGX_CHECK(cls >= 0, "wide attention: S=%d head dim %d unsupported", p.S, dh);
@@ -873,6 +1192,75 @@ int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
         EGX_ATTN_RG_CASE(128)
     }
 #undef EGX_ATTN_RG_CASE
+    return 1;
+}
+
+int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_fwd: bad arguments");
+    EGX_CHECK(!p.drop_thresh, "wide_attn_ragged_fwd: inference only (no dropout)");
+    return attn_ragged_fwd(p, st);
+}
+
+int wide_attn_ragged_train_fwd(const WideAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_train_fwd: bad arguments");
+    return attn_ragged_fwd(p, st);
+}
+
+template <int DH, int NKT>
+static int launch_attn_ragged_bwd(const WideAttnParams& p, hipStream_t st) {
+    constexpr int RS = DH * 2 + 32, SP = NKT * 16;
+    const size_t lds = (size_t)4 * SP * RS + 2 * SP * sizeof(float);
+    static bool attr = false;
+    if (!attr) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_attn_ragged_bwd_kernel<DH, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = true;
+    }
+    hipLaunchKernelGGL((wide_attn_ragged_bwd_kernel<DH, NKT>), dim3(p.B * p.H), dim3(NKT * 64), lds, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int DH>
+static int launch_attn_long_ragged_bwd(const WideAttnParams& p, hipStream_t st) {
+    constexpr int RS = DH * 2 + 32;
+    const size_t SP = (size_t)((p.S + 31) & ~31);       // LDS by the class's longest clip; a workgroup lays its images out by its own
+    const size_t lds2 = 2 * SP * RS, lds_b = lds2 + 2 * SP * sizeof(float);
+    static bool attr = false;
+    if (!attr) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_attn_long_ragged_dq_kernel<DH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_attn_long_ragged_dkv_kernel<DH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr = true;
+    }
+    const int ntile = (p.S + 15) / 16;
+    int split = 256 / (p.B * p.H);
+    const int maxs = (ntile + WAL_NW - 1) / WAL_NW;
+    split = split < 1 ? 1 : (split > maxs ? maxs : split);
+    const dim3 grid(p.B * p.H, split);
+    hipLaunchKernelGGL((wide_attn_long_ragged_dq_kernel<DH>), grid, dim3(WAL_NTH), lds2, st, p);
+    count_launch();
+    hipLaunchKernelGGL((wide_attn_long_ragged_dkv_kernel<DH>), grid, dim3(WAL_NTH), lds_b, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wide_attn_ragged_bwd(const WideAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.qkv && p.lse && p.d_out && p.d_qkv && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_bwd: bad arguments");
+    if (p.B <= 0) return 0;
+    const int dh = p.d / p.H, cls = wide_attn_ragged_class(p.S, dh);
+    EGX_CHECK(cls >= 0, "wide attention: S=%d head dim %d unsupported", p.S, dh);
+    if (cls == 2) {
+        EGX_CHECK(p.delta && p.out, "wide attention (S > 128): the backward needs the saved attention output and a delta buffer");
+        return dh == 32 ? launch_attn_long_ragged_bwd<32>(p, st) : launch_attn_long_ragged_bwd<64>(p, st);
+    }
+#define EGX_ATTN_RGB_CASE(D)                                                                   \
+    case D: return cls == 0 ? launch_attn_ragged_bwd<D, 4>(p, st) : launch_attn_ragged_bwd<D, 8>(p, st);
+    switch (dh) {
+        EGX_ATTN_RGB_CASE(32)
+        EGX_ATTN_RGB_CASE(64)
+        EGX_ATTN_RGB_CASE(96)
+        EGX_ATTN_RGB_CASE(128)
+    }
+#undef EGX_ATTN_RGB_CASE
     return 1;
 }
 

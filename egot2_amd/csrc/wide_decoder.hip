@@ -556,6 +556,313 @@ int dec_attn_ragged(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
     return 0;
 }
 
+// ---- ragged memories, training (egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd) ----
+// dec_attn_kernel (bf16 operands) and dec_attn_long_kernel for clip p.clips[i] with its own memory rows [mtab[2c], + mtab[2c + 1]), forward with
+// dropout and backward. Separate copies: the uniform kernels and the inference copies above keep their code and register allocation.
+template <int DH, bool BWD>
+__global__ __launch_bounds__(256) void dec_attn_ragged_train_kernel(DecAttnParams p) {
+    constexpr bool F32 = false;
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    __shared__ float sQ[4][DA_MAXQ][DH];        // query rows (fp32)
+    __shared__ float sG[4][DA_MAXQ][DH];        // dO rows (backward)
+    __shared__ float sP[4][DA_MAXQ][64];        // probabilities after dropout
+    __shared__ float sD[4][DA_MAXQ][64];        // dS (backward)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wi = blockIdx.x * 4 + wave;
+    if (wi >= p.B * p.H) return;                // (no barrier below: every wave works alone)
+    const int b = p.clips[wi / p.H], h = wi % p.H, bh = b * p.H + h;       // (dropout rows: the clip's batch position, as the uniform kernel)
+    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1];
+    const size_t m0 = (size_t)p.mtab[2 * b];
+    const bool kv_lane = lane < Sk;
+    // key row of this lane
+    float kr[DH], vr[BWD ? DH : 1];
+    {
+        const size_t krow = (m0 + (kv_lane ? lane : 0)) * p.ldk + h * DH;
+#pragma unroll
+        for (int c = 0; c < DH; c += 8) {
+            float t8[8];
+            load8<F32>(p.k, krow + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
+        }
+        if constexpr (BWD) {
+            const size_t vrow = (m0 + (kv_lane ? lane : 0)) * p.ldv + h * DH;
+#pragma unroll
+            for (int c = 0; c < DH; c += 8) {
+                float t8[8];
+                load8<F32>(p.v, vrow + c, t8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vr[c + e] = t8[e];
+            }
+        }
+    }
+    // query (and dO) rows -> LDS
+    for (int i = lane; i < Sq * DH; i += 64) {
+        const int r = i / DH, c = i - r * DH;
+        sQ[wave][r][c] = load1<F32>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
+        if constexpr (BWD) sG[wave][r][c] = bf1(p.d_o[((size_t)b * Sq + r) * p.ldo + h * DH + c]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    float ds_reg[BWD ? DA_MAXQ : 1];            // dS[i][lane]
+#pragma unroll
+    for (int i = 0; i < DA_MAXQ; ++i) {         // (static indices: a runtime-indexed register array would live in scratch)
+        if (i >= Sq) break;
+        const bool live = kv_lane && !(p.causal && lane > i);
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < DH; c += 4) {
+            const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
+            s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
+        }
+        s = live ? s * p.scale : -INFINITY;
+        const float m = wmax64(s);
+        const float e = live ? __expf(s - m) : 0.f;
+        const float prob = e / wsum64d(e);
+        float mask = 1.f;
+        if (p.drop_thresh) mask = drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)lane, p.drop_thresh, p.drop_inv);
+        sP[wave][i][lane] = prob * mask;
+        if constexpr (BWD) {
+            float dp = 0.f;
+#pragma unroll
+            for (int c = 0; c < DH; c += 4) {
+                const float4 gv = *reinterpret_cast<const float4*>(&sG[wave][i][c]);
+                dp += (gv.x * vr[c] + gv.y * vr[c + 1]) + (gv.z * vr[c + 2] + gv.w * vr[c + 3]);
+            }
+            dp = live ? dp * mask : 0.f;
+            const float delta = wsum64d(prob * dp);
+            const float dsv = live ? prob * (dp - delta) * p.scale : 0.f;
+            ds_reg[i] = dsv;
+            sD[wave][i][lane] = dsv;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (!BWD) {
+        // lane c: O[i][c] = sum_j P[i][j] V[j][c]
+        if (lane < DH) {
+            float acc[DA_MAXQ];
+#pragma unroll
+            for (int i = 0; i < DA_MAXQ; ++i) acc[i] = 0.f;
+            const size_t v0 = m0 * p.ldv + h * DH + lane;
+            for (int j = 0; j < Sk; ++j) {
+                const float vv = load1<F32>(p.v, v0 + (size_t)j * p.ldv);
+#pragma unroll
+                for (int i = 0; i < DA_MAXQ; ++i)
+                    if (i < Sq) acc[i] += sP[wave][i][j] * vv;
+            }
+#pragma unroll
+            for (int i = 0; i < DA_MAXQ; ++i)
+                if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + lane] = f2bf(acc[i]);
+        }
+    } else {
+        // lane j: dK[j][:] = sum_i dS[i][j] Q[i][:]  (row store)
+        if (kv_lane) {
+            const size_t dk0 = (m0 + lane) * p.ldk + h * DH;
+#pragma unroll
+            for (int c = 0; c < DH; c += 8) {
+                float a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < DA_MAXQ; ++i) {
+                    if (i >= Sq) break;
+                    const float4 q0 = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
+                    const float4 q1 = *reinterpret_cast<const float4*>(&sQ[wave][i][c + 4]);
+                    const float dsv = ds_reg[i];
+                    a[0] += dsv * q0.x; a[1] += dsv * q0.y; a[2] += dsv * q0.z; a[3] += dsv * q0.w;
+                    a[4] += dsv * q1.x; a[5] += dsv * q1.y; a[6] += dsv * q1.z; a[7] += dsv * q1.w;
+                }
+                store8<F32>(p.dk, dk0 + c, a);
+            }
+        }
+        // lane c: dQ[i][c] = sum_j dS[i][j] K[j][c];  dV[j][c] = sum_i P[i][j] dO[i][c]
+        if (lane < DH) {
+            float accq[DA_MAXQ], go[DA_MAXQ];
+#pragma unroll
+            for (int i = 0; i < DA_MAXQ; ++i) { accq[i] = 0.f; go[i] = i < Sq ? sG[wave][i][lane] : 0.f; }
+            const size_t k0 = m0 * p.ldk + h * DH + lane, dv0 = m0 * p.ldv + h * DH + lane;
+            for (int j = 0; j < Sk; ++j) {
+                const float kk = load1<F32>(p.k, k0 + (size_t)j * p.ldk);
+                float av = 0.f;
+#pragma unroll
+                for (int i = 0; i < DA_MAXQ; ++i)
+                    if (i < Sq) { accq[i] += sD[wave][i][j] * kk; av += sP[wave][i][j] * go[i]; }
+                store1<F32>(p.dv, dv0 + (size_t)j * p.ldv, av);
+            }
+#pragma unroll
+            for (int i = 0; i < DA_MAXQ; ++i)
+                if (i < Sq) store1<F32>(p.dq, ((size_t)b * Sq + i) * p.ldq + h * DH + lane, accq[i]);
+        }
+    }
+}
+
+template <int DH, bool BWD>
+__global__ __launch_bounds__(256) void dec_attn_long_ragged_train_kernel(DecAttnParams p) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
+    constexpr int LDK = DH + 1;
+    extern __shared__ float dal_sm[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = p.clips[blockIdx.x / p.H], h = blockIdx.x % p.H, bh = b * p.H + h;
+    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1], SKP = (Sk + 63) & ~63;
+    const size_t m0 = (size_t)p.mtab[2 * b];
+    float* Cs = dal_sm;                     // K or V chunk [64][DH + 1]
+    float* Qs = Cs + 64 * LDK;
+    float* Gs = Qs + DA_MAXQ * DH;
+    float* Ps = Gs + DA_MAXQ * DH;          // [Sq][SKP]
+    float* Ds = Ps + DA_MAXQ * SKP;         // backward only
+    const bf16_t* kb = reinterpret_cast<const bf16_t*>(p.k) + m0 * p.ldk + h * DH;
+    const bf16_t* vb = reinterpret_cast<const bf16_t*>(p.v) + m0 * p.ldv + h * DH;
+    auto stage = [&](const bf16_t* src, int ld, int j0) {
+        __syncthreads();
+        for (int i = tid; i < 64 * (DH / 8); i += 256) {
+            const int j = i / (DH / 8), c = (i - j * (DH / 8)) * 8;
+            float t8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (j0 + j < Sk) load8<false>(src, (size_t)(j0 + j) * ld + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) Cs[j * LDK + c + e] = t8[e];
+        }
+        __syncthreads();
+    };
+    for (int i = tid; i < Sq * DH; i += 256) {
+        const int r = i / DH, c = i - r * DH;
+        Qs[i] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
+        if constexpr (BWD) Gs[i] = bf1(p.d_o[((size_t)b * Sq + r) * p.ldo + h * DH + c]);
+    }
+    for (int j0 = 0; j0 < Sk; j0 += 64) {          // scores: wave w owns queries w, w + 4; lane = key within the chunk
+        stage(kb, p.ldk, j0);
+        for (int i = wave; i < Sq; i += 4) {
+            float sc = 0.f;
+#pragma unroll
+            for (int c = 0; c < DH; ++c) sc += Qs[i * DH + c] * Cs[lane * LDK + c];
+            Ps[i * SKP + j0 + lane] = j0 + lane < Sk ? sc * p.scale : -INFINITY;
+        }
+    }
+    __syncthreads();
+    for (int i = wave; i < Sq; i += 4) {
+        float m = -INFINITY;
+        for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
+        m = wmax64(m);
+        float sum = 0.f;
+        for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
+        sum = 1.f / wsum64d(sum);
+        for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;
+    }
+    auto keep = [&](int i, int j) { return p.drop_thresh ? drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)j, p.drop_thresh, p.drop_inv) : 1.f; };
+    constexpr int NE = DA_MAXQ * DH / 256;          // (query, column) accumulators per thread: 1 (DH = 32) or 2 (DH = 64)
+    float acc[NE];
+#pragma unroll
+    for (int u = 0; u < NE; ++u) acc[u] = 0.f;
+    if constexpr (BWD) {
+        for (int j0 = 0; j0 < Sk; j0 += 64) {      // dP = dO V^T
+            stage(vb, p.ldv, j0);
+            for (int i = wave; i < Sq; i += 4) {
+                float dp = 0.f;
+#pragma unroll
+                for (int c = 0; c < DH; ++c) dp += Gs[i * DH + c] * Cs[lane * LDK + c];
+                Ds[i * SKP + j0 + lane] = dp;
+            }
+        }
+        __syncthreads();
+        for (int i = wave; i < Sq; i += 4) {
+            float delta = 0.f;
+            for (int j = lane; j < SKP; j += 64) {
+                const float dp = Ds[i * SKP + j] * keep(i, j);
+                Ds[i * SKP + j] = dp;
+                delta += Ps[i * SKP + j] * dp;
+            }
+            delta = wsum64d(delta);
+            for (int j = lane; j < SKP; j += 64) {
+                const float pr = Ps[i * SKP + j];
+                Ds[i * SKP + j] = pr * (Ds[i * SKP + j] - delta) * p.scale;
+                Ps[i * SKP + j] = pr * keep(i, j);
+            }
+        }
+        bf16_t* dkb = reinterpret_cast<bf16_t*>(p.dk) + m0 * p.ldk + h * DH;
+        bf16_t* dvb = reinterpret_cast<bf16_t*>(p.dv) + m0 * p.ldv + h * DH;
+        for (int j0 = 0; j0 < Sk; j0 += 64) {      // dQ += dS K; dK = dS^T Q, dV = P^T dO for the chunk's keys
+            stage(kb, p.ldk, j0);
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+                if (i < Sq) {
+                    float a = 0.f;
+                    for (int j = 0; j < 64; ++j) a += Ds[i * SKP + j0 + j] * Cs[j * LDK + c];
+                    acc[u] += a;
+                }
+            }
+            for (int e = tid; e < 64 * (DH / 8); e += 256) {
+                const int j = e / (DH / 8), c = (e - j * (DH / 8)) * 8;
+                if (j0 + j < Sk) {
+                    float ak[8] = {0, 0, 0, 0, 0, 0, 0, 0}, av[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    for (int i = 0; i < Sq; ++i) {
+                        const float dsv = Ds[i * SKP + j0 + j], pv = Ps[i * SKP + j0 + j];
+#pragma unroll
+                        for (int x = 0; x < 8; ++x) { ak[x] += dsv * Qs[i * DH + c + x]; av[x] += pv * Gs[i * DH + c + x]; }
+                    }
+                    store8<false>(dkb, (size_t)(j0 + j) * p.ldk + c, ak);
+                    store8<false>(dvb, (size_t)(j0 + j) * p.ldv + c, av);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+            if (i < Sq) store1<false>(p.dq, ((size_t)b * Sq + i) * p.ldq + h * DH + c, acc[u]);
+        }
+    } else {
+        if (p.drop_thresh) {
+            for (int i = wave; i < Sq; i += 4)
+                for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= keep(i, j);
+        }
+        for (int j0 = 0; j0 < Sk; j0 += 64) {
+            stage(vb, p.ldv, j0);
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+                if (i < Sq) {
+                    float a = 0.f;
+                    for (int j = 0; j < 64; ++j) a += Ps[i * SKP + j0 + j] * Cs[j * LDK + c];
+                    acc[u] += a;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
+            if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + c] = f2bf(acc[u]);
+        }
+    }
+}
+
+// training over ragged memories: forward with dropout on the probabilities (BWD = false) and backward (dq for the clip's Sq target rows, dk / dv
+// for the clip's own memory rows, written packed: every memory row belongs to one clip). One launch per kernel class, as dec_attn_ragged.
+template <bool BWD>
+int dec_attn_ragged_train(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
+    EGX_CHECK(dh == 32 || dh == 64, "decoder attention: head dim %d (32 or 64)", dh);
+    EGX_CHECK(!p.causal && p.Sk >= 1 && p.Sk <= DAL_MAXK && p.mtab && p.clips, "decoder attention (ragged training): bad arguments");
+    if (p.B <= 0) return 0;
+    p.scale = 1.f / sqrtf((float)dh);
+    if (!long_class) {
+        EGX_CHECK(p.Sk <= DA_MAXK, "decoder attention (ragged): short class with Sk = %d", p.Sk);
+        const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
+        if (dh == 64) hipLaunchKernelGGL((dec_attn_ragged_train_kernel<64, BWD>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((dec_attn_ragged_train_kernel<32, BWD>), grid, block, 0, st, p);
+        EGX_LAUNCH_CHECK();
+        return 0;
+    }
+    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)2 * DA_MAXQ * dh + (size_t)2 * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
+    static bool attr[2] = {false, false};
+    const void* fn = dh == 64 ? reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<64, BWD>)
+                              : reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<32, BWD>);
+    if (!attr[dh == 64]) {
+        EGX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
+        attr[dh == 64] = true;
+    }
+    if (dh == 64) hipLaunchKernelGGL((dec_attn_long_ragged_train_kernel<64, BWD>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    else hipLaunchKernelGGL((dec_attn_long_ragged_train_kernel<32, BWD>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 // x32 / x16 [row] = dropout(emb[tok[row]] * scale + pe[row % sy])
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restrict__ tok, const float* __restrict__ emb, const float* __restrict__ pe,
                                                         int pe_stride, float scale, float* __restrict__ x32, bf16_t* __restrict__ x16, int rows,
@@ -839,6 +1146,7 @@ namespace {
 struct DecRagged {
     const int* mtab;                // [B][2]: first memory row, memory rows
     const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_ragged_kernel), class 1: the chunked kernel
+    bool train;                     // the training kernels (dropout on the probabilities; their backward reads the same table)
 };
 
 int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const float* memory, const float* emb, const float* pe,
@@ -951,7 +1259,7 @@ int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
                 a.mtab = rg->mtab;
                 for (int c = 0; c < 2; ++c) {
                     a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
-                    if (dec_attn_ragged(a, dh, c == 1, st)) return 1;
+                    if (rg->train ? dec_attn_ragged_train<false>(a, dh, c == 1, st) : dec_attn_ragged(a, dh, c == 1, st)) return 1;
                 }
             } else if (dec_attn<false>(a, dh, false, st)) return 1;
         }
@@ -975,11 +1283,12 @@ int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
 }
 
 // the ragged call's plan: DPlan over sum_b S_b memory rows, then the batch table (host copy in `tab`)
+// (train: the training entry points, which take dropout; `bytes` is then the size of `saved`, the table behind the uniform plan's saved region)
 int decoder_ragged_plan(const egx_dec_config* cfg, int B, const int* mem_lengths, DPlan& pl, std::vector<int>& tab, int (&n)[2], int (&smax)[2],
-                        size_t& off_tab, size_t& bytes) {
+                        size_t& off_tab, size_t& bytes, bool train = false) {
     EGX_CHECK(cfg && mem_lengths, "egx_decoder_ragged: null argument");
     EGX_CHECK(B >= 1 && B <= (1 << 20), "egx_decoder_ragged: B=%d clips (1 .. %d)", B, 1 << 20);
-    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f, "egx_decoder_ragged: inference only: p_drop and p_pos must be 0 (got %g, %g)", cfg->p_drop, cfg->p_pos);
+    EGX_CHECK(train || (cfg->p_drop == 0.f && cfg->p_pos == 0.f), "egx_decoder_ragged: inference only: p_drop and p_pos must be 0 (got %g, %g)", cfg->p_drop, cfg->p_pos);
     size_t rows = 0;
     n[0] = n[1] = 0; smax[0] = smax[1] = 0;
     tab.assign((size_t)3 * B, 0);       // [B][2] table, then the clips of class 0 and of class 1
@@ -998,6 +1307,14 @@ int decoder_ragged_plan(const egx_dec_config* cfg, int B, const int* mem_lengths
     off_tab = align_up(pl.saved_bytes, 256);
     bytes = off_tab + align_up(tab.size() * sizeof(int), 256);
     return 0;
+}
+DecRagged dec_ragged_view(const int* dtab, int B, const int (&n)[2], const int (&smax)[2], bool train) {
+    DecRagged rg;
+    rg.mtab = dtab;
+    rg.clips[0] = dtab + 2 * (size_t)B; rg.clips[1] = rg.clips[0] + n[0];
+    for (int c = 0; c < 2; ++c) { rg.n[c] = n[c]; rg.Sk_max[c] = smax[c] ? smax[c] : 1; }
+    rg.train = train;
+    return rg;
 }
 }  // namespace
 
@@ -1035,20 +1352,19 @@ int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, con
     // the table goes to the device in the arguments of upload launches (stream-ordered; a captured graph would replay THESE lengths)
     int* dtab = reinterpret_cast<int*>((char*)workspace + off_tab);
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
-    DecRagged rg;
-    rg.mtab = dtab;
-    rg.clips[0] = dtab + 2 * (size_t)B; rg.clips[1] = rg.clips[0] + n[0];
-    for (int c = 0; c < 2; ++c) { rg.n[c] = n[c]; rg.Sk_max[c] = smax[c] ? smax[c] : 1; }
+    const DecRagged rg = dec_ragged_view(dtab, B, n, smax, false);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, workspace, 0, 0, st, &rg);
 }
 
-int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B, const float* d_logits,
-                    const void* saved, void* scratch, float* d_memory, float* d_emb, const egx_dec_layer_grads* grads, float* d_fc_w,
-                    float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, void* stream) {
-    DPlan pl;
-    if (make_dplan(cfg, B, pl)) return 1;
-    EGX_CHECK(tokens && layers && fc_w && d_logits && saved && scratch && grads, "egx_decoder_bwd: null pointer argument");
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+// the decoder backward over `pl` (uniform: B * S memory rows; rg: the packed rows of a ragged memory, whose cross-attention backward runs per
+// kernel class over the batch table — everything else is row-wise over the B * sy target rows and the pl.Nm memory rows)
+int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B,
+                    const float* d_logits, const void* saved, void* scratch, float* d_memory, float* d_emb, const egx_dec_layer_grads* grads,
+                    float* d_fc_w, float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, hipStream_t st,
+                    const DecRagged* rg) {
     if (refuse_captured_dropout(cfg, training, st)) return 1;
     const int d = pl.d, dff = pl.dff, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
     const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f);
@@ -1191,7 +1507,13 @@ int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_
             a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.S; a.causal = 0;
             DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CROSS);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (dec_attn<true>(a, dh, false, st)) return 1;
+            if (rg) {
+                a.mtab = rg->mtab;
+                for (int c = 0; c < 2; ++c) {
+                    a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
+                    if (dec_attn_ragged_train<true>(a, dh, c == 1, st)) return 1;
+                }
+            } else if (dec_attn<true>(a, dh, false, st)) return 1;
         }
         if (fork()) return 1;
         if (gw.ca_in_b) {
@@ -1273,6 +1595,65 @@ int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_
     if (wide_row_reduce_flush(rrb, st)) return 1;   // every queued LayerNorm / bias column sum
     if (wide_tn_queue_flush(tq, st)) return 1;      // every queued weight gradient: one grid per tile variant, then their slab sums
     return wide_reduce_flush(rb, st);
+}
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B, const float* d_logits,
+                    const void* saved, void* scratch, float* d_memory, float* d_emb, const egx_dec_layer_grads* grads, float* d_fc_w,
+                    float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, void* stream) {
+    DPlan pl;
+    if (make_dplan(cfg, B, pl)) return 1;
+    EGX_CHECK(tokens && layers && fc_w && d_logits && saved && scratch && grads, "egx_decoder_bwd: null pointer argument");
+    return decoder_bwd_run(cfg, pl, tokens, layers, fc_w, B, d_logits, saved, scratch, d_memory, d_emb, grads, d_fc_w, d_fc_b, zero_buf, zero_bytes,
+                           training, seed, (hipStream_t)stream, nullptr);
+}
+
+/* ---- training over ragged memories (the decoder side of HHI/tasks/multitask/video_tasktranslation.py:39-66 on the mixed-length batches its
+ * SequenceBatchSampler, :144-156, cannot form; decode() of HHI/models/multitask/task_prompt_model.py:260-269) ---- */
+int egx_decoder_ragged_train_workspace(const egx_dec_config* cfg, int B, const int* mem_lengths, size_t* saved_bytes, size_t* scratch_bytes) {
+    DPlan pl;
+    std::vector<int> tab;
+    int n[2], smax[2];
+    size_t off_tab = 0, nb = 0;
+    if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb, true)) return 1;
+    if (saved_bytes) *saved_bytes = nb;
+    if (scratch_bytes) *scratch_bytes = pl.scratch_bytes;
+    return 0;
+}
+
+int egx_decoder_ragged_train_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const int* mem_lengths, const float* emb,
+                                 const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B,
+                                 float* logits, void* saved, void* scratch, int training, uint64_t seed, void* stream) {
+    DPlan pl;
+    std::vector<int> tab;
+    int n[2], smax[2];
+    size_t off_tab = 0, nb = 0;
+    if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb, true)) return 1;
+    EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && saved, "egx_decoder_ragged_train_fwd: null pointer argument");
+    (void)scratch;
+    hipStream_t st = (hipStream_t)stream;
+    int* dtab = reinterpret_cast<int*>((char*)saved + off_tab);       // (kept in `saved`: the backward reads the same table)
+    if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
+    const DecRagged rg = dec_ragged_view(dtab, B, n, smax, true);
+    return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, saved, training, seed, st, &rg);
+}
+
+int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, const int* mem_lengths, const egx_dec_layer* layers, const float* fc_w,
+                           int B, const float* d_logits, const void* saved, void* scratch, float* d_memory, float* d_emb,
+                           const egx_dec_layer_grads* grads, float* d_fc_w, float* d_fc_b, void* zero_buf, size_t zero_bytes, int training,
+                           uint64_t seed, void* stream) {
+    DPlan pl;
+    std::vector<int> tab;
+    int n[2], smax[2];
+    size_t off_tab = 0, nb = 0;
+    if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb, true)) return 1;
+    EGX_CHECK(tokens && layers && fc_w && d_logits && saved && scratch && grads, "egx_decoder_ragged_bwd: null pointer argument");
+    // (the forward left the table in `saved`; the host copy rebuilt from the same lengths gives its layout)
+    const DecRagged rg = dec_ragged_view(reinterpret_cast<const int*>((const char*)saved + off_tab), B, n, smax, true);
+    return decoder_bwd_run(cfg, pl, tokens, layers, fc_w, B, d_logits, saved, scratch, d_memory, d_emb, grads, d_fc_w, d_fc_b, zero_buf, zero_bytes,
+                           training, seed, (hipStream_t)stream, &rg);
 }
 
 }  // extern "C"

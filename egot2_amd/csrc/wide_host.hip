@@ -25,6 +25,7 @@ struct WPlan {
     int B, S, d, H, dff, L, nseg;
     size_t N;
     int seg_off[EGX_MAX_SEGMENTS];
+    size_t tab;         // ragged training: the device copy of the batch table (the backward reads what the forward uploaded)
     size_t keys;        // dropout keys derived from a device-resident seed (derive_keys): (max(L, nseg) layers) x 8 slots
     size_t zero, seg_w[EGX_MAX_SEGMENTS], seg_feat16[EGX_MAX_SEGMENTS], seg_pre[EGX_MAX_SEGMENTS], seg_stats[EGX_MAX_SEGMENTS];
     WLayer layer[64];
@@ -33,25 +34,41 @@ struct WPlan {
     size_t gA, gB, dres, dy16, dhid16, dattn16, dqkv16, adelta, dseg16, slabs, slab_all, slab_all_bytes, lnpart, cspart, rowpart, rowpart_bytes, scratch_bytes;
 };
 
+// a ragged batch (see "ragged batches" below): the host copy of its table and, for the inference call, its workspace layout
+struct WRagged {
+    int B = 0, K = 0, layout = 0;
+    size_t N = 0, R[EGX_MAX_SEGMENTS] = {}, Rmax = 0;
+    size_t zero = 0, seg_w[EGX_MAX_SEGMENTS] = {}, feat16 = 0, pre = 0;
+    size_t w_in[64] = {}, w_o[64] = {}, w1[64] = {}, w2[64] = {};
+    size_t x32 = 0, x16 = 0, qkv = 0, lse = 0, attn = 0, res = 0, x1_32 = 0, x1_16 = 0, hid = 0, tab_off = 0, bytes = 0;
+    // host copy of the batch table (ints): B clip records (WIDE_RG_REC), the clips of attention class 0 | 1 | 2, per segment the source
+    // row (b * segs[k].T + t) and the token row of every compacted row, and (out_layout 1) the output row of every token row
+    std::vector<int> tab;
+    size_t cls0 = 0, gmap[EGX_MAX_SEGMENTS] = {}, omap[EGX_MAX_SEGMENTS] = {}, outmap = 0;
+    int ncls[3] = {0, 0, 0}, Smax[3] = {0, 0, 0};
+};
+
 size_t take(size_t& cur, size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
 size_t smax(size_t a, size_t b) { return a > b ? a : b; }
 
-void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl) {
+// rg: a ragged batch — N = sum_b S_b packed token rows and R_k compacted rows of segment k instead of B * S and B * T_k; nothing is sized by B * max S_b
+void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl, const WRagged* rg = nullptr) {
     memset(&pl, 0, sizeof(pl));
     pl.B = B; pl.d = cfg->d_model; pl.H = cfg->n_heads; pl.dff = cfg->d_ff; pl.L = cfg->n_layers; pl.nseg = cfg->n_segments;
     int S = 0;
     for (int i = 0; i < pl.nseg; ++i) { pl.seg_off[i] = S; S += segs[i].T; }
-    pl.S = S; pl.N = (size_t)B * S;
+    pl.S = S; pl.N = rg ? rg->N : (size_t)B * S;
+    auto seg_rows = [&](int i) { return rg ? rg->R[i] : (size_t)B * segs[i].T; };
     const size_t d = pl.d, N = pl.N, dff = pl.dff;
     size_t cur = 0;
     pl.zero = take(cur, 1024);
     pl.keys = take(cur, (size_t)64 * DROP_KEY_SLOTS * sizeof(uint64_t));
     for (int i = 0; i < pl.nseg; ++i) {
-        size_t rows = (size_t)B * segs[i].T;
+        size_t rows = seg_rows(i);
         if (segs[i].proj_w) {
             pl.seg_w[i] = take(cur, d * segs[i].d_in * 2);
             // bf16 copy of the features (the projection GEMM's operand); features that arrive in bf16 and un-pooled are used in place
-            if (!(segs[i].feat_bf16 && segs[i].pool <= 1)) pl.seg_feat16[i] = take(cur, rows * segs[i].d_in * 2);
+            if (rg || !(segs[i].feat_bf16 && segs[i].pool <= 1)) pl.seg_feat16[i] = take(cur, rows * segs[i].d_in * 2);
             pl.seg_pre[i] = take(cur, rows * d * 4);
         }
         pl.seg_stats[i] = take(cur, rows * 2 * 4);
@@ -66,7 +83,7 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
         o.x32 = l == 0 ? x0_32 : take(cur, N * d * 4);
         o.x16 = take(cur, N * d * 2);
         o.qkv = take(cur, N * 3 * d * 2);
-        o.lse = take(cur, (size_t)B * pl.H * S * 4);
+        o.lse = take(cur, N * pl.H * 4);        // (B, H, S); ragged: (clip, head) rows from H tok0_b + h S_b
         o.attn = take(cur, N * d * 2);
         o.res1 = take(cur, N * d * 4);
         o.stats1 = take(cur, N * 2 * 4);
@@ -76,6 +93,7 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
         o.res2 = take(cur, N * d * 4);
         o.stats2 = take(cur, N * 2 * 4);
     }
+    if (rg) pl.tab = take(cur, (rg->outmap ? rg->tab.size() : rg->tab.size() + N) * sizeof(int));     // (sized for out_layout 1 either way)
     pl.saved_bytes = cur;
 
     size_t sc = 0;
@@ -86,9 +104,9 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
     pl.dhid16 = take(sc, N * dff * 2);
     pl.dattn16 = take(sc, N * d * 2);
     pl.dqkv16 = take(sc, N * 3 * d * 2);
-    pl.adelta = take(sc, wide_attn_delta_bytes(B, pl.H, S));
+    pl.adelta = take(sc, rg ? (rg->ncls[2] ? N * pl.H * sizeof(float) : 0) : wide_attn_delta_bytes(B, pl.H, S));
     size_t segrows = 0;
-    for (int i = 0; i < pl.nseg; ++i) segrows = smax(segrows, (size_t)B * segs[i].T);
+    for (int i = 0; i < pl.nseg; ++i) segrows = smax(segrows, seg_rows(i));
     pl.dseg16 = take(sc, segrows * d * 2);
     size_t slab = 0;
     slab = smax(slab, wide_gemm_tn_scratch(3 * pl.d, pl.d, (int)N));
@@ -96,20 +114,20 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
     slab = smax(slab, wide_gemm_tn_scratch(pl.dff, pl.d, (int)N));
     slab = smax(slab, wide_gemm_tn_scratch(pl.d, pl.dff, (int)N));
     for (int i = 0; i < pl.nseg; ++i)
-        if (segs[i].proj_w) slab = smax(slab, wide_gemm_tn_scratch(pl.d, segs[i].d_in, B * segs[i].T));
+        if (segs[i].proj_w) slab = smax(slab, wide_gemm_tn_scratch(pl.d, segs[i].d_in, (int)seg_rows(i)));
     pl.slabs = take(sc, slab);
     // one slab region per weight gradient of a backward (their reductions run as ONE launch at its end)
     size_t all = 0;
     auto add = [&](int M, int Nn, int K) { all += (wide_gemm_tn_scratch(M, Nn, K) + 255) / 256 * 256; };
     for (int l = 0; l < pl.L; ++l) { add(pl.d, pl.dff, (int)N); add(pl.dff, pl.d, (int)N); add(pl.d, pl.d, (int)N); add(3 * pl.d, pl.d, (int)N); }
     for (int i = 0; i < pl.nseg; ++i)
-        if (segs[i].proj_w) add(pl.d, segs[i].d_in, B * segs[i].T);
+        if (segs[i].proj_w) add(pl.d, segs[i].d_in, (int)seg_rows(i));
     if (all > ((size_t)400 << 20)) all = 0;      // measured break-even (wide_encoder_bwd): 283 MB pays, 764 MB does not
     pl.slab_all = take(sc, all);
     pl.slab_all_bytes = all;
     pl.lnpart = take(sc, wide_ln_bwd_scratch((int)N, pl.d));
     size_t cs = smax(wide_colsum_scratch((int)N, 3 * pl.d), (size_t)(4 * cdiv((int)N, 256) + 4) * pl.dff * 4);
-    for (int i = 0; i < pl.nseg; ++i) cs = smax(cs, wide_pos_grad_scratch(B, segs[i].T, pl.d));
+    if (!rg) for (int i = 0; i < pl.nseg; ++i) cs = smax(cs, wide_pos_grad_scratch(B, segs[i].T, pl.d));      // (ragged: no learned-position gradient)
     pl.cspart = take(sc, cs);
     // a partial buffer per deferred row reduction of a backward (wide_row_reduce_flush: ONE launch sums them all at its end):
     // two LayerNorm backwards + the lin1 / in-projection bias column sums per layer
@@ -168,10 +186,12 @@ void wide_workspace(const egx_config* cfg, const egx_segment* segs, int B, size_
     *scratch = pl.scratch_bytes;
 }
 
-int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float* ln_w, const float* ln_b, const egx_layer* layers,
-                     int B, float* tokens_out, void* saved, int training, uint64_t seed, hipStream_t st) {
-    WPlan pl;
-    make_wplan(cfg, segs, B, pl);
+namespace {
+// the wide forward over `pl`. rg (with `tab`, the device copy of its table): a ragged batch — token preparation through the row maps, the attention
+// one launch per kernel class over the batch table, and (rg->layout 1) the last LayerNorm's rows scattered to the frame-major output; every other
+// launch is the uniform one over the pl.N packed token rows.
+int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* segs, const float* ln_w, const float* ln_b, const egx_layer* layers,
+                    int B, float* tokens_out, void* saved, int training, uint64_t seed, hipStream_t st, const WRagged* rg, const int* tab) {
     const int d = pl.d, S = pl.S, dff = pl.dff, N = (int)pl.N;
     // device-resident seed: one small launch advances it (training forward with advance_seed) and derives every key of this
     // call into `saved`; the kernels below read their keys from there, and so does the backward
@@ -200,14 +220,16 @@ int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float
     }
     for (int i = 0; i < pl.nseg; ++i) {
         const egx_segment& sg = segs[i];
-        const int rows = B * sg.T;
+        const int rows = rg ? (int)rg->R[i] : B * sg.T;
         const float* pre = sg.feat;
         if (sg.proj_w) {
             bf16_t* w16 = at<bf16_t>(saved, pl.seg_w[i]);
-            const bool in_place = sg.feat_bf16 && sg.pool <= 1;
+            const bool in_place = !rg && sg.feat_bf16 && sg.pool <= 1;
             const bf16_t* f16 = in_place ? reinterpret_cast<const bf16_t*>(sg.feat) : at<bf16_t>(saved, pl.seg_feat16[i]);
             float* po = at<float>(saved, pl.seg_pre[i]);
-            if (!in_place && wide_pool_cast(sg.feat, sg.feat_bf16, rows, sg.pool > 1 ? sg.pool : 1, sg.d_in, at<bf16_t>(saved, pl.seg_feat16[i]), st)) return 1;
+            // ragged: the valid frames only, compacted (kept in `saved`: the operand of the projection's weight gradient)
+            if (rg && wide_gather_cast(sg.feat, sg.feat_bf16, tab + rg->gmap[i], rows, sg.d_in, at<bf16_t>(saved, pl.seg_feat16[i]), st)) return 1;
+            if (!rg && !in_place && wide_pool_cast(sg.feat, sg.feat_bf16, rows, sg.pool > 1 ? sg.pool : 1, sg.d_in, at<bf16_t>(saved, pl.seg_feat16[i]), st)) return 1;
             WideGemmParams g;
             g.A = f16; g.B = w16; g.M = rows; g.N = d; g.K = sg.d_in; g.lda = sg.d_in; g.ldb = sg.d_in;
             g.Cf = po; g.ldc = d; g.bias = sg.proj_b; g.zero_page = zero;
@@ -223,7 +245,10 @@ int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float
         lp.add_vec = sg.add_vec; lp.pos = sg.pos; lp.pos_stride = sg.pos_stride;
         Drop dp = mkdrop(training, cfg->p_pos, seed, 0, SITE_POS);
         lp.drop_key = dp.key; lp.drop_thresh = dp.thresh; lp.drop_inv = dp.inv;
-        if (wide_ln_fwd(lp, st)) return 1;
+        if (rg) {       // compacted row -> its token row (the positional dropout keys on that row, as in the uniform layout)
+            lp.out_map = tab + rg->omap[i]; lp.src_map = tab + rg->gmap[i];
+            if (wide_ln_fwd_mapped(lp, st)) return 1;
+        } else if (wide_ln_fwd(lp, st)) return 1;
     }
 
     for (int l = 0; l < pl.L; ++l) {
@@ -248,7 +273,14 @@ int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float
             a.B = B; a.S = S; a.H = pl.H; a.d = d;
             Drop da = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (wide_attn_fwd(a, st)) return 1;
+            if (rg) {
+                a.rtab = tab;
+                for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {       // one launch per attention kernel class
+                    if (!rg->ncls[c]) continue;
+                    a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
+                    if (wide_attn_ragged_train_fwd(a, st)) return 1;
+                }
+            } else if (wide_attn_fwd(a, st)) return 1;
         }
         {   // out-projection + dropout1 + residual -> res1
             WideGemmParams g;
@@ -286,17 +318,30 @@ int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float
             WideLnFwdParams lp;
             lp.x = cat<float>(saved, o.res2); lp.w = w.norm2_w; lp.b = w.norm2_b; lp.eps = cfg->ln_eps;
             lp.stats = at<float>(saved, o.stats2); lp.y32 = xo32; lp.y16 = xo16; lp.rows = N; lp.d = d;
-            if (wide_ln_fwd(lp, st)) return 1;
+            if (last && rg && rg->layout == 1) {        // the output in frame-major segment tuples
+                lp.out_map = tab + rg->outmap;
+                if (wide_ln_fwd_mapped(lp, st)) return 1;
+            } else if (wide_ln_fwd(lp, st)) return 1;
         }
     }
     return 0;
 }
+}  // namespace
 
-int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float* ln_w, const egx_layer* layers, int B,
-                     const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w,
-                     float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, hipStream_t st) {
+int wide_encoder_fwd(const egx_config* cfg, const egx_segment* segs, const float* ln_w, const float* ln_b, const egx_layer* layers,
+                     int B, float* tokens_out, void* saved, int training, uint64_t seed, hipStream_t st) {
     WPlan pl;
     make_wplan(cfg, segs, B, pl);
+    return encoder_fwd_run(cfg, pl, segs, ln_w, ln_b, layers, B, tokens_out, saved, training, seed, st, nullptr, nullptr);
+}
+
+namespace {
+// the wide backward over `pl`; rg / tab as encoder_fwd_run: the attention backward per kernel class, d_tokens read through the output map
+// (rg->layout 1) and the token-preparation backward through the maps the forward scattered with. All other launches are row-wise over pl.N rows.
+int encoder_bwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* segs, const float* ln_w, const egx_layer* layers, int B,
+                    const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w,
+                    float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, hipStream_t st, const WRagged* rg,
+                    const int* tab) {
     const int d = pl.d, S = pl.S, dff = pl.dff, N = (int)pl.N;
     const void* zero = cat<char>(saved, pl.zero);
     // device-resident seed: the forward left this step's keys in `saved`
@@ -363,7 +408,10 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
             Drop d2 = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2);
             b.out_key = d2.key; b.out_thresh = d2.thresh; b.out_inv = d2.inv;
             b.dw = gw.norm2_w; b.db = gw.norm2_b; b.dbias = gw.lin2_b;
-            if (ln_bwd_q(b)) return 1;
+            if (rg && rg->layout == 1 && l == pl.L - 1) {       // d_tokens arrives in the frame-major layout: read back through the same map
+                b.dy_map = tab + rg->outmap;
+                if (wide_ln_bwd_mapped(b, lnpart, st)) return 1;
+            } else if (ln_bwd_q(b)) return 1;
         }
         if (dw_tn(dy16, d, cat<bf16_t>(saved, o.hid), dff, gw.lin2_w, d, dff, N)) return 1;
         {   // d(hidden) = (dy W2) .* alive / keep, column sums -> d(lin1_b)
@@ -407,7 +455,14 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
             a.d_out = dattn16; a.d_qkv = dqkv16; a.B = B; a.S = S; a.H = pl.H; a.d = d;
             Drop da = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (wide_attn_bwd(a, st)) return 1;
+            if (rg) {
+                a.rtab = tab;
+                for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {
+                    if (!rg->ncls[c]) continue;
+                    a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
+                    if (wide_attn_ragged_bwd(a, st)) return 1;
+                }
+            } else if (wide_attn_bwd(a, st)) return 1;
         }
         if (gw.in_proj_b) {
             void* reg = row_region(wide_colsum_scratch(N, 3 * d));
@@ -436,7 +491,8 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
         // d(features): an identity segment's feature gradient IS the LayerNorm backward's fp32 input gradient (the trainable
         // SlowFast head of the LTA translators feeds such a segment); projected features stay frozen on this path
         EGX_CHECK(!sgr.feat || !sg.proj_w, "wide path: gradients into PROJECTED features are not supported (use impl = generic)");
-        const int rows = B * sg.T;
+        const int rows = rg ? (int)rg->R[i] : B * sg.T;
+        EGX_CHECK(!rg || !sgr.pos, "ragged encode: a learned positional table gets no gradient from the ragged kernels");
         if (sgr.pos && wide_pos_grad(g, B, S, pl.seg_off[i], sg.T, d, sgr.pos, sg.pos_stride, dp.key, dp.thresh, dp.inv, cspart, st)) return 1;
         const bool need = (sg.proj_w && (sgr.proj_w || sgr.proj_b)) || d_ln_w || d_ln_b || sgr.add_vec || sgr.feat;
         if (!need) continue;
@@ -450,12 +506,25 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
         }
         b.dw = d_ln_w; b.db = d_ln_b; b.dadd = sgr.add_vec; b.dbias = sg.proj_w ? sgr.proj_b : nullptr;
         // (not queued: every segment adds into the SAME shared-LayerNorm gradient; queued reductions run concurrently and must have targets of their own)
-        if (wide_ln_bwd(b, lnpart, st)) return 1;
-        const bf16_t* f16 = (sg.feat_bf16 && sg.pool <= 1) ? reinterpret_cast<const bf16_t*>(sg.feat) : cat<bf16_t>(saved, pl.seg_feat16[i]);
+        if (rg) {       // compacted row r reads the gradient of its token row (and that row's positional mask)
+            b.dy_map = tab + rg->omap[i];
+            if (wide_ln_bwd_mapped(b, lnpart, st)) return 1;
+        } else if (wide_ln_bwd(b, lnpart, st)) return 1;
+        const bf16_t* f16 = (!rg && sg.feat_bf16 && sg.pool <= 1) ? reinterpret_cast<const bf16_t*>(sg.feat) : cat<bf16_t>(saved, pl.seg_feat16[i]);
         if (sg.proj_w && dw_tn(dseg16, d, f16, sg.d_in, sgr.proj_w, d, sg.d_in, rows)) return 1;
     }
     if (wide_row_reduce_flush(rrb, st)) return 1;
     return wide_reduce_flush(rb, st);
+}
+}  // namespace
+
+int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float* ln_w, const egx_layer* layers, int B,
+                     const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w,
+                     float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, hipStream_t st) {
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl);
+    return encoder_bwd_run(cfg, pl, segs, ln_w, layers, B, d_tokens, saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, training, seed, st,
+                           nullptr, nullptr);
 }
 
 // ---- ragged batches (egx_ragged_encode, inference) -------------------------------------------------------------------------------------
@@ -465,26 +534,16 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
 // (wide_ln_fwd_mapped); GEMMs and row kernels then run over the N token rows as in the uniform forward; the attention runs one launch per
 // kernel class over the clips of that class (wide_attn_ragged_fwd). Nothing in the workspace is sized by B * max S_b.
 namespace {
-struct WRagged {
-    int B = 0, K = 0, layout = 0;
-    size_t N = 0, R[EGX_MAX_SEGMENTS] = {}, Rmax = 0;
-    size_t zero = 0, seg_w[EGX_MAX_SEGMENTS] = {}, feat16 = 0, pre = 0;
-    size_t w_in[64] = {}, w_o[64] = {}, w1[64] = {}, w2[64] = {};
-    size_t x32 = 0, x16 = 0, qkv = 0, lse = 0, attn = 0, res = 0, x1_32 = 0, x1_16 = 0, hid = 0, tab_off = 0, bytes = 0;
-    // host copy of the batch table (ints): B clip records (WIDE_RG_REC), the clips of attention class 0 | 1 | 2, per segment the source
-    // row (b * segs[k].T + t) and the token row of every compacted row, and (out_layout 1) the output row of every token row
-    std::vector<int> tab;
-    size_t cls0 = 0, gmap[EGX_MAX_SEGMENTS] = {}, omap[EGX_MAX_SEGMENTS] = {}, outmap = 0;
-    int ncls[3] = {0, 0, 0}, Smax[3] = {0, 0, 0};
-};
-
-int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int out_layout, WRagged& rp) {
+// train: the training entry points (dropout allowed; the workspace layout at the end is the inference call's and unused there: make_wplan lays
+// `saved` / `scratch` out over the same table)
+int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int out_layout, WRagged& rp, bool train = false) {
     EGX_CHECK(cfg && segs && lengths, "ragged encode: null argument");
     EGX_CHECK(B >= 1 && B <= (1 << 20), "ragged encode: B=%d clips (1 .. %d)", B, 1 << 20);
-    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
+    EGX_CHECK(train || (cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f),
               "ragged batches are inference-only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g)", cfg->p_drop, cfg->p_pos, cfg->p_feat);
     EGX_CHECK(!cfg->ce && !cfg->token_ce, "ragged encode: the fused losses (egx_config.ce / token_ce) are not supported; apply the loss to the outputs");
     EGX_CHECK(cfg->out_tokens == 0 && !cfg->bucket_cb, "ragged encode: out_tokens and bucket_cb are not supported");
+    EGX_CHECK(!train || cfg->bwd_stage == 0, "ragged encode: the staged backward (bwd_stage) is not supported");
     EGX_CHECK(cfg->compute == EGX_BF16, "ragged encode: runs on the wide bf16 path (compute bf16, got %d)", cfg->compute);
     EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_WIDE, "ragged encode: runs on the wide path (impl auto or wide, got %d)", cfg->impl);
     EGX_CHECK(out_layout == 0 || out_layout == 1, "ragged encode: out_layout %d (0: packed clips, 1: frame-major segment tuples)", out_layout);
@@ -688,6 +747,51 @@ int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int*
         }
     }
     return 0;
+}
+
+/* ---- training (the encoder side of HHI/tasks/multitask/video_tasktranslation.py:39-66 on the mixed-length batches its SequenceBatchSampler,
+ * :144-156, cannot form; encode() of HHI/models/multitask/task_prompt_model.py:230-258) ---- */
+int egx_ragged_encode_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
+                                      size_t* scratch_bytes) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, 0, rp, true)) return 1;
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl, &rp);
+    if (saved_bytes) *saved_bytes = pl.saved_bytes;
+    if (scratch_bytes) *scratch_bytes = pl.scratch_bytes;
+    return 0;
+}
+
+int egx_ragged_encode_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                                const egx_layer* layers, int B, float* tokens_out, int out_layout, void* saved, int training, uint64_t seed,
+                                void* stream) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp, true)) return 1;
+    EGX_CHECK(ln_w && ln_b && layers && tokens_out && saved, "egx_ragged_encode_train_fwd: null pointer argument");
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl, &rp);
+    hipStream_t st = (hipStream_t)stream;
+    // the batch table into `saved` (the backward reads it there), stream-ordered in the arguments of upload launches: not for graph capture
+    int* tab = (int*)((char*)saved + pl.tab);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    return encoder_fwd_run(cfg, pl, segs, ln_w, ln_b, layers, B, tokens_out, saved, training, seed, st, &rp, tab);
+}
+
+int egx_ragged_encode_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const egx_layer* layers, int B,
+                          const float* d_tokens, int out_layout, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                          float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, void* stream) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp, true)) return 1;
+    EGX_CHECK(ln_w && layers && d_tokens && saved && scratch && layer_grads, "egx_ragged_encode_bwd: null pointer argument");
+    for (int k = 0; k < rp.K; ++k) {
+        EGX_CHECK(!seg_grads || !seg_grads[k].feat, "ragged encode: gradients into PROJECTED features are not supported");
+        EGX_CHECK(!seg_grads || !seg_grads[k].pos, "ragged encode: a learned positional table gets no gradient from the ragged kernels");
+    }
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl, &rp);
+    // (the host copy of the table rebuilt from the same lengths gives the offsets; the device copy is the forward's)
+    return encoder_bwd_run(cfg, pl, segs, ln_w, layers, B, d_tokens, saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, training, seed,
+                           (hipStream_t)stream, &rp, (const int*)((const char*)saved + pl.tab));
 }
 
 }  // extern "C"

@@ -244,6 +244,98 @@ __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int
     }
 }
 
+// ragged batches (wide_ln_bwd_mapped): the kernel above with the upstream row (and with it the row key of the dropout behind the LayerNorm) read
+// from a row map of the batch table: the mirror of wide_ln_fwd_mapped_kernel's out_map. A separate copy, as that kernel.
+__global__ __launch_bounds__(256) void wide_ln_bwd_mapped_kernel(WideLnBwdParams p, int rows_per_block) {
+    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull, okey = p.out_thresh ? resolve_key(p.out_key) : 0ull;
+    __shared__ float red[3][4][1024];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int d = p.d, nv = (d + 255) / 256;
+    const float inv_d = 1.f / (float)d;
+    float4 aw[LN_MAXV], ab[LN_MAXV], ac[LN_MAXV], wv[LN_MAXV];
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+        aw[i] = ab[i] = ac[i] = wv[i] = make_float4(0, 0, 0, 0);
+        int c = 4 * lane + 256 * i;
+        if (i < nv && c < d) wv[i] = *reinterpret_cast<const float4*>(p.w + c);
+    }
+    const int r0 = blockIdx.x * rows_per_block, r1 = min(p.rows, r0 + rows_per_block);
+    for (int row = r0 + wave; row < r1; row += 4) {
+        const int orow = p.dy_map[row];
+        const float* dy = p.dy + (size_t)orow * d;
+        const float* pre = p.pre + (size_t)row * d;
+        const float2 st2 = *reinterpret_cast<const float2*>(p.stats + 2 * (size_t)row);
+        const float mean = st2.x, rstd = st2.y;
+        float4 gq[LN_MAXV], xh[LN_MAXV];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            int c = 4 * lane + 256 * i;
+            gq[i] = xh[i] = make_float4(0, 0, 0, 0);
+            if (i < nv && c < d) {
+                float4 g = *reinterpret_cast<const float4*>(dy + c);
+                if (p.drop_thresh) {
+                    float ds[4];
+                    drop_scale4(dkey, (uint32_t)orow, (uint32_t)c, p.drop_thresh, p.drop_inv, ds);
+                    g.x *= ds[0]; g.y *= ds[1]; g.z *= ds[2]; g.w *= ds[3];
+                }
+                float4 x = *reinterpret_cast<const float4*>(pre + c);
+                x.x = (x.x - mean) * rstd; x.y = (x.y - mean) * rstd; x.z = (x.z - mean) * rstd; x.w = (x.w - mean) * rstd;
+                aw[i].x += g.x * x.x; aw[i].y += g.y * x.y; aw[i].z += g.z * x.z; aw[i].w += g.w * x.w;
+                ab[i].x += g.x; ab[i].y += g.y; ab[i].z += g.z; ab[i].w += g.w;
+                g.x *= wv[i].x; g.y *= wv[i].y; g.z *= wv[i].z; g.w *= wv[i].w;
+                s1 += (g.x + g.y) + (g.z + g.w);
+                s2 += (g.x * x.x + g.y * x.y) + (g.z * x.z + g.w * x.w);
+                gq[i] = g; xh[i] = x;
+            }
+        }
+        s1 = wsum64(s1) * inv_d;
+        s2 = wsum64(s2) * inv_d;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            int c = 4 * lane + 256 * i;
+            if (i < nv && c < d) {
+                float o[4] = {rstd * (gq[i].x - s1 - xh[i].x * s2), rstd * (gq[i].y - s1 - xh[i].y * s2),
+                              rstd * (gq[i].z - s1 - xh[i].z * s2), rstd * (gq[i].w - s1 - xh[i].w * s2)};
+                float m[4] = {o[0], o[1], o[2], o[3]};
+                if (p.out_thresh) {
+                    float ds[4];
+                    drop_scale4(okey, (uint32_t)row, (uint32_t)c, p.out_thresh, p.out_inv, ds);
+                    m[0] *= ds[0]; m[1] *= ds[1]; m[2] *= ds[2]; m[3] *= ds[3];
+                }
+                if (p.dx32) {
+                    const float* q = p.mask_dx32 ? m : o;
+                    *reinterpret_cast<float4*>(p.dx32 + (size_t)row * d + c) = make_float4(q[0], q[1], q[2], q[3]);
+                }
+                if (p.dx16) {
+                    uint2 u = make_uint2(pk2(m[0], m[1]), pk2(m[2], m[3]));
+                    *reinterpret_cast<uint2*>(p.dx16 + (size_t)row * d + c) = u;
+                    // the bias gradient is the column sum of the operand AS STORED (bf16-rounded)
+                    ac[i].x += bff(u.x & 0xffffu); ac[i].y += bff(u.x >> 16); ac[i].z += bff(u.y & 0xffffu); ac[i].w += bff(u.y >> 16);
+                } else {
+                    ac[i].x += m[0]; ac[i].y += m[1]; ac[i].z += m[2]; ac[i].w += m[3];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+        int c = 4 * lane + 256 * i;
+        if (i < nv && c < d) {
+            *reinterpret_cast<float4*>(&red[0][wave][c]) = aw[i];
+            *reinterpret_cast<float4*>(&red[1][wave][c]) = ab[i];
+            *reinterpret_cast<float4*>(&red[2][wave][c]) = ac[i];
+        }
+    }
+    __syncthreads();
+    float* out = p.partials + (size_t)blockIdx.x * 3 * d;
+    for (int i = threadIdx.x; i < 3 * d; i += 256) {
+        int k = i / d, c = i % d;
+        out[i] = (red[k][0][c] + red[k][1][c]) + (red[k][2][c] + red[k][3][c]);
+    }
+}
+
+
 // Fixed-order sum over the rows of a partial buffer: 1024 threads = 16 waves per 64 columns; wave w adds rows w, w + 16, ...
 // (four independent accumulators), the 16 wave sums are combined in wave order through LDS. Bitwise reproducible.
 __device__ __forceinline__ float reduce_rows_1024(const float* __restrict__ part, int nt, size_t ld, int col, bool valid, float (*red)[64]) {
@@ -340,6 +432,22 @@ int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceB
         q.first_block = 0; q.out_ld = 0; q.row_len = 1; q.pad_ = 0;
         if (row_reduce_queue(*defer, q)) return 0;
     }
+    if (p.dw || p.db || p.dbias || p.dadd)
+        hipLaunchKernelGGL(wide_ln_bwd_reduce_kernel, dim3(cdiv(3 * p.d, 64)), dim3(1024), 0, st, (const float*)p.partials, p.blocks,
+                           p.d, p.dw, p.db, p.dbias, p.dadd);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wide_ln_bwd_mapped(WideLnBwdParams p, void* scratch, hipStream_t st) {
+    EGX_CHECK(p.dy && p.pre && p.stats && p.w && scratch && p.dy_map, "wide_ln_bwd_mapped: null pointer");
+    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_bwd_mapped: d=%d unsupported", p.d);
+    if (p.rows <= 0) return 0;
+    p.blocks = ln_bwd_blocks(p.rows);
+    p.partials = (float*)scratch;
+    const int rpb = cdiv(p.rows, p.blocks);
+    p.blocks = cdiv(p.rows, rpb);
+    hipLaunchKernelGGL(wide_ln_bwd_mapped_kernel, dim3(p.blocks), dim3(256), 0, st, p, rpb);
     if (p.dw || p.db || p.dbias || p.dadd)
         hipLaunchKernelGGL(wide_ln_bwd_reduce_kernel, dim3(cdiv(3 * p.d, 64)), dim3(1024), 0, st, (const float*)p.partials, p.blocks,
                            p.d, p.dw, p.db, p.dbias, p.dadd);

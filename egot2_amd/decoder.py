@@ -127,3 +127,59 @@ class DecoderMixin:
             out.index_copy_(1, it.to(o.device), o)
         F_egx._last_dec_impl[0] = "grouped"
         return out
+
+    def _egx_decode_ragged_train(self, y: torch.Tensor, memory: torch.Tensor, memory_lengths, *, embedding: nn.Embedding, pos_embed,
+                                 decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
+        """Differentiable decode over a packed ragged memory, in train and eval mode: y (B, sy) int64, memory (sum_b S_b, d), memory_lengths
+        (B,) -> (sy, B, |V|); gradients reach the decoder, the embedding, `fc` and the packed memory. One egx_decoder_ragged_train_fwd /
+        egx_decoder_ragged_bwd pair where the fused decoder serves the shapes (last_decoder_impl() == "ragged"); elsewhere one differentiable
+        _egx_decode per memory length ("grouped"), whose dropout masks differ from the ragged kernels'. Validation is host work and runs first."""
+        B, sy = y.shape
+        d = memory.shape[-1]
+        ml = memory_lengths.detach() if isinstance(memory_lengths, torch.Tensor) else torch.as_tensor(memory_lengths)
+        if ml.dtype.is_floating_point or ml.dtype.is_complex or ml.dtype == torch.bool:
+            raise ValueError(f"memory_lengths must be integers, got {ml.dtype}")
+        ml = ml.to("cpu", torch.int64)
+        if ml.dim() != 1 or ml.shape[0] != B:
+            raise ValueError(f"memory_lengths has shape {tuple(ml.shape)}: expected ({B},), one memory length per target row")
+        if memory.dim() != 2 or (B and (int(ml.min()) < 1 or int(ml.sum()) != memory.shape[0])):
+            raise ValueError(f"memory must be the packed (sum_b S_b, d) rows of the clips: {tuple(memory.shape)} rows, lengths sum to "
+                             f"{int(ml.sum())} (each >= 1)")
+        comp_model = getattr(self, "egx_compute", "f32")
+        d_ff = decoder.layers[0].linear1.out_features
+        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
+        S_max = int(ml.max()) if B else 1
+        train = bool(self.training)
+        if (post_ln and F_egx.decoder_supported(comp_model, d, n_heads, d_ff, sy, S_max, len(decoder.layers))
+                and not getattr(self, "egx_composed_decoder", False)):
+            meta = dict(n_layers=len(decoder.layers), n_heads=n_heads, d_ff=d_ff, ln_eps=decoder.layers[0].norm1.eps,
+                        p_drop=p_drop if train else 0.0, p_pos=pos_embed.dropout.p if train else 0.0, training=train,
+                        seed=self._egx_seed() if train else 0,
+                        seed_ptr=(self._egx_seed_dev.data_ptr() if train and getattr(self, "_egx_seed_dev", None) is not None else 0))
+            params = []
+            for layer in decoder.layers:
+                sa, ca = layer.self_attn, layer.multihead_attn
+                params += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias,
+                           ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
+                           layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm3.weight, layer.norm3.bias]
+            out = F_egx.RaggedDecoderFn.apply(meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :], *params,
+                                              fc.weight, fc.bias)
+            return out.view(B, sy, -1).permute(1, 0, 2)
+        # grouped: one differentiable decode per memory length, on (S, G, d) memories gathered from the packed rows
+        row0 = torch.cumsum(ml, 0) - ml
+        groups = {}
+        for b, S in enumerate(ml.tolist()):
+            groups.setdefault(S, []).append(b)
+        parts, order = [], []
+        for S, idx in groups.items():
+            rows = (row0[idx][:, None] + torch.arange(S)[None, :]).reshape(-1).to(memory.device)
+            mem = memory.index_select(0, rows).view(len(idx), S, d).permute(1, 0, 2)
+            it = torch.tensor(idx, dtype=torch.int64, device=y.device)
+            parts.append(self._egx_decode(y.index_select(0, it), mem, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
+                                          n_heads=n_heads, p_drop=p_drop))
+            order += idx
+        inv = torch.empty(B, dtype=torch.int64)
+        inv[torch.tensor(order, dtype=torch.int64)] = torch.arange(B)
+        out = torch.cat(parts, 1).index_select(1, inv.to(parts[0].device))
+        F_egx._last_dec_impl[0] = "grouped"
+        return out

@@ -1044,12 +1044,149 @@ def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_t
     return out
 
 
+class RaggedWideEncoderFn(torch.autograd.Function):
+    """Training forward + backward of the wide bf16 encoder over a ragged batch (egx_ragged_encode_train_fwd / egx_ragged_encode_bwd): every
+    token of every clip, packed (out_layout 0) or in frame-major segment tuples (out_layout 1). Argument order: spec, lengths (the (B, K)
+    int32 host tensor of ragged_lengths()), out_layout, task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per
+    segment, 12 tensors per layer. The call owns its `saved` workspace (batch table, bf16 weight copies, activations, dropout keys): a forward of
+    the same module in between cannot change what a pending backward reads."""
+
+    @staticmethod
+    def forward(ctx, spec: EncoderSpec, lengths, out_layout: int, task_embed, pos_table, ln_w, ln_b, *rest):
+        lib = _lib.load()
+        if reload_tuning_each_call:
+            lib.egx_tuning_reload()
+        nseg = len(spec.segments)
+        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(rest[:nseg], rest[nseg:3 * nseg], rest[3 * nseg:], (), ln_w, ln_b,
+                                                                                 task_embed, pos_table)
+        B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
+        cfg = _ragged_train_config(spec)
+        sv, sc = C.c_size_t(0), C.c_size_t(0)
+        check(lib.egx_ragged_encode_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
+        needs_grad = any(ctx.needs_input_grad)
+        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=device) if needs_grad else _workspace("ragged_wide_saved", device, sv.value)
+        if needs_grad and _POISON:
+            saved.fill_(255)
+        out = torch.empty((int(lengths.to(torch.int64).sum()), d), dtype=torch.float32, device=device)
+        seed = C.c_uint64(spec.seed & (2**64 - 1))
+        check(lib.egx_ragged_encode_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
+                                              ptr(saved), int(spec.training), seed, _stream()))
+        _last_impl[0] = IMPL_RAGGED
+        _last_slices[0] = 1
+        ctx.spec, ctx.lengths, ctx.B, ctx.out_layout, ctx.nseg = spec, lengths, B, int(out_layout), nseg
+        ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
+        ctx.has_te, ctx.has_pos = task_embed is not None, pos_table is not None
+        ctx.save_for_backward(*([t for t in (task_embed, pos_table) if t is not None] + [ln_w, ln_b] + feats + proj + layer_t))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        spec: EncoderSpec = ctx.spec
+        lib = _lib.load()
+        if reload_tuning_each_call:
+            lib.egx_tuning_reload()
+        sv = list(ctx.saved_tensors)
+        task_embed = sv.pop(0) if ctx.has_te else None
+        pos_table = sv.pop(0) if ctx.has_pos else None
+        ln_w, ln_b = sv[0], sv[1]
+        nseg = ctx.nseg
+        feats, proj, layer_t = sv[2:2 + nseg], sv[2 + nseg:2 + 3 * nseg], sv[2 + 3 * nseg:]
+        B, device = ctx.B, d_out.device
+        need = ctx.needs_input_grad     # (spec, lengths, out_layout, task_embed, pos_table, ln_w, ln_b, *rest)
+        if need[4]:
+            raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
+        if any(need[7:7 + nseg]):
+            raise _lib.EgxError("ragged training: gradients into PROJECTED features are not supported on the wide path (detach the features)")
+        pk = _GradPacker()
+        i_te = pk.add(task_embed, need[3])
+        i_lnw, i_lnb = pk.add(ln_w, need[5]), pk.add(ln_b, need[6])
+        i_proj = [pk.add(t, need[7 + nseg + i]) for i, t in enumerate(proj)]
+        i_layer = [pk.add(t, need[7 + 3 * nseg + i]) for i, t in enumerate(layer_t)]
+        grads = pk.materialise(device, zero=False)      # zero-filled by the backward's first launch (egx_config.zero_buf)
+
+        def g(i):
+            return grads[i] if i >= 0 else None
+
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=([None] * nseg, [g(i) for i in i_proj], g(i_te), None))
+        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
+        cfg = _ragged_train_config(spec)
+        cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
+        scratch = _workspace("scratch", device, ctx.scratch_bytes)
+        seed = C.c_uint64(spec.seed & (2**64 - 1))
+        up = d_out if (d_out.dtype == torch.float32 and d_out.is_contiguous()) else d_out.float().contiguous()
+        check(lib.egx_ragged_encode_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), layers, B, ptr(up), ctx.out_layout,
+                                        ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(g(i_lnw)), ptr(g(i_lnb)), lgr, int(spec.training), seed,
+                                        _stream()))
+        return (None, None, None, g(i_te), None, g(i_lnw), g(i_lnb)) + (None,) * nseg + tuple(g(i) for i in i_proj) + tuple(g(i) for i in i_layer)
+
+
+def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
+                                proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], out_layout: int = 0):
+    """Differentiable encoder_ragged_tokens (training and evaluation, with and without grad): every token of a ragged batch, with dropout in
+    training mode and gradients for the projections, task_embed, the shared LayerNorm and the encoder layers; the features themselves get none
+    (projected features stay frozen on the wide path). Runs egx_ragged_encode_train_fwd / egx_ragged_encode_bwd (last_encoder_impl() ==
+    "ragged"); configurations they do not cover (compute other than bf16, a forced implementation, a clip beyond the wide attention) run one
+    differentiable batched forward per length tuple ("grouped"), whose dropout masks are keyed per group and differ from the ragged kernels'.
+    The bucketed gradient exchange (functional.bucket_hook / egx_config.bucket_cb) is refused."""
+    if spec.ce or spec.token_ce or spec.out_tokens or spec.head_n_out or spec.p_feat:
+        raise ValueError("ragged training on the wide path: no fused losses, no out_tokens, no head, no feature dropout")
+    if spec.defer_small:
+        raise ValueError("ragged training: the staged backward (defer_small) is not supported")
+    if bucket_hook is not None:
+        raise ValueError("ragged training: the bucketed per-layer gradient exchange (bucket_cb) is not supported; exchange the gradients "
+                         "after the backward (ddp.allreduce_gradients)")
+    B = feats[0].shape[0]
+    lengths = _check_host_lengths(lengths, B, len(spec.segments))
+    if out_layout not in (0, 1):
+        raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
+    if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
+        b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
+        raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
+    if len(proj) != 2 * len(spec.segments):
+        raise ValueError("ragged training on the wide path: every segment needs a projection")
+    lib = _lib.load()
+    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+    sv, sc = C.c_size_t(0), C.c_size_t(0)
+    if (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
+            lib.egx_ragged_encode_train_workspace(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0:
+        # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged wide path does not cover
+        return _encoder_tokens_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, out_layout)
+    feats = [f.detach() for f in feats]      # (frozen backbone features: no gradient path on the wide projections)
+    return RaggedWideEncoderFn.apply(spec, lengths, int(out_layout), task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params)
+
+
+def _encoder_tokens_train_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
+    """encoder_ragged_tokens_train where the ragged kernels do not run: one differentiable batched forward per group of clips with the same
+    length tuple, on those clips' unpadded frames; the rows put in their place (autograd flows through the gather and the reordering)."""
+    d = spec.d_model
+    device = feats[0].device
+    rows = ragged_token_rows(lengths, out_layout)
+    S = lengths.to(torch.int64).sum(1)
+    tok0 = torch.cumsum(S, 0) - S
+    parts, dst = [], []
+    gspec0 = dataclasses.replace(spec, wcache=None)
+    for idx, _, gspec, fs in _length_groups(gspec0, feats, lengths):
+        r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
+        parts.append(r.reshape(-1, d))
+        dst.append(rows[(tok0[idx][:, None] + torch.arange(r.shape[1])[None, :]).reshape(-1)])
+    dst = torch.cat(dst)
+    inv = torch.empty(dst.numel(), dtype=torch.int64)
+    inv[dst] = torch.arange(dst.numel())
+    out = torch.cat(parts, 0).index_select(0, inv.to(device))
+    _last_impl[0] = IMPL_GROUPED
+    _last_slices[0] = 1
+    return out
+
+
 _last_dec_impl = ["none"]
 
 
 def last_decoder_impl() -> str:
     """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
-    operation), "ragged" (egx_decoder_ragged_fwd) or "grouped" (a ragged memory decoded one length group at a time)."""
+    operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd) or "grouped" (a ragged memory decoded one length group at a
+    time)."""
     return _last_dec_impl[0]
 
 
@@ -1480,6 +1617,87 @@ class DecoderFn(torch.autograd.Function):
         if bucket_hook is not None and pk.total:
             bucket_hook(pk.flat, 0, pk.total)        # the decoder's gradients are exchanged while the encoder's backward runs
         return (None, None, d_memory, g(i_emb), None) + tuple(g(i) for i in i_layer) + (g(i_fcw), g(i_fcb))
+
+
+class RaggedDecoderFn(torch.autograd.Function):
+    """DecoderFn over a packed ragged memory (egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd): logits (B * sy, |V|) from target
+    tokens (B, sy) and the (sum_b S_b, d) memory, clip b cross-attending to its own S_b = mem_lengths[b] rows. Inputs after `meta`: tokens,
+    memory, mem_lengths ((B,) int32 host tensor), embedding weight, positional rows (sy, d), 18 tensors per layer, fc weight, fc bias. The
+    call owns its `saved` workspace; d_memory comes back packed."""
+
+    @staticmethod
+    def forward(ctx, meta, tokens, memory, mem_lengths, emb, pe, *rest):
+        lib = _lib.load()
+        n_layers = meta["n_layers"]
+        layer_t = [_dev_f32(t, "decoder layer parameter") for t in rest[:18 * n_layers]]
+        fc_w, fc_b = _dev_f32(rest[18 * n_layers], "fc.weight"), _dev_f32(rest[18 * n_layers + 1], "fc.bias")
+        memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+        if tokens.dtype != torch.int64 or not tokens.is_cuda:
+            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
+        tokens = tokens.contiguous()
+        B, sy = tokens.shape
+        d = emb.shape[1]
+        ml = mem_lengths.contiguous()
+        cfg_args = (d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16,
+                    meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None)
+        cfg = _lib.DecConfig(*cfg_args)
+        sv, sc = C.c_size_t(0), C.c_size_t(0)
+        check(lib.egx_decoder_ragged_train_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(sv), C.byref(sc)))
+        need_grad = any(ctx.needs_input_grad)
+        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=memory.device) if need_grad else _workspace("dec_saved", memory.device, sv.value)
+        if need_grad and _POISON:
+            saved.fill_(255)
+        scratch = _workspace("dec_scratch", memory.device, sc.value)
+        layers = (_lib.DecLayer * n_layers)()
+        for l in range(n_layers):
+            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+        logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
+        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
+        check(lib.egx_decoder_ragged_train_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers,
+                                               ptr(fc_w), ptr(fc_b), B, ptr(logits), ptr(saved), ptr(scratch), int(meta["training"]), seed, _stream()))
+        _last_dec_impl[0] = "ragged"
+        ctx.meta, ctx.cfg_args, ctx.B, ctx.ml, ctx.saved_buf, ctx.scratch_bytes = meta, cfg_args, B, ml, saved, sc.value
+        ctx.save_for_backward(tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        lib = _lib.load()
+        meta = ctx.meta
+        n_layers = meta["n_layers"]
+        sv = list(ctx.saved_tensors)
+        tokens, memory, emb, pe = sv[:4]
+        layer_t = sv[4:4 + 18 * n_layers]
+        fc_w, fc_b = sv[4 + 18 * n_layers], sv[5 + 18 * n_layers]
+        B = ctx.B
+        need = ctx.needs_input_grad      # (meta, tokens, memory, mem_lengths, emb, pe, *layer_t, fc_w, fc_b)
+        device = d_logits.device
+        pk = _GradPacker()
+        i_emb = pk.add(emb, need[4])
+        i_layer = [pk.add(t, need[6 + i]) for i, t in enumerate(layer_t)]
+        i_fcw = pk.add(fc_w, need[6 + 18 * n_layers])
+        i_fcb = pk.add(fc_b, need[7 + 18 * n_layers])
+        grads = pk.materialise(device, zero=False)
+
+        def g(i):
+            return grads[i] if i >= 0 else None
+
+        d_memory = torch.empty_like(memory) if need[2] else None
+        cfg = _lib.DecConfig(*ctx.cfg_args)
+        layers = (_lib.DecLayer * n_layers)()
+        lgr = (_lib.DecLayerGrads * n_layers)()
+        for l in range(n_layers):
+            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+                setattr(lgr[l], name, ptr(g(i_layer[18 * l + k])))
+        scratch = _workspace("dec_scratch", device, ctx.scratch_bytes)
+        dl = d_logits.float().contiguous()
+        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
+        check(lib.egx_decoder_ragged_bwd(C.byref(cfg), ptr(tokens), ctx.ml.data_ptr(), layers, ptr(fc_w), B, ptr(dl), ptr(ctx.saved_buf),
+                                         ptr(scratch), ptr(d_memory), ptr(g(i_emb)), lgr, ptr(g(i_fcw)), ptr(g(i_fcb)), ptr(pk.flat),
+                                         pk.flat.numel() * 4, int(meta["training"]), seed, _stream()))
+        return (None, None, d_memory, None, g(i_emb), None) + tuple(g(i) for i in i_layer) + (g(i_fcw), g(i_fcb))
 
 
 def decoder_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S: int, n_layers: int) -> bool:

@@ -119,6 +119,59 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
             return x.view(-1, 3, self.dim).permute(1, 0, 2)        # (3, sum_b T_b, d): row 3 f + k of x is segment k of frame f
         return x
 
+    def encode_features_ragged(self, task, lam_feat, ttm_feat=None, asd_feat=None, *, lengths):
+        """encode_features(..., lengths=) for TRAINING: works in train and eval mode, under autograd, with dropout on every site in train
+        mode. The features are padded batches of clips of their own lengths (`lengths` as encode_features); padded frames are never read and a
+        clip's rows, and its contribution to every gradient, are what that clip gives alone and unpadded. Returns the packed (sum_b S_b, d)
+        memory for 'ttm' / 'lam' (decode_ragged(..., memory_lengths=S_b)) and the reference's (3, sum_b T_b, d) for 'asd' (decode() reads it:
+        its memory is sum_b T_b "clips" of exactly 3 rows). Gradients reach the projections, task_embed, the shared LayerNorm and the encoder;
+        the (frozen) backbone features get none. One ragged forward / backward pair on the wide bf16 path (last_encoder_impl() == "ragged");
+        configurations it does not cover run one differentiable uniform call per length group ("grouped", other dropout masks). In eval mode the
+        result equals encode_features(..., lengths=) bit for bit."""
+        assert task in ['lam', 'ttm', 'asd']
+        if task == 'lam':
+            feats, projs, ids = [lam_feat], [self.proj_lam], [0]
+        else:
+            feats, projs, ids = [lam_feat, ttm_feat, asd_feat], [self.proj_lam, self.proj_ttm, self.proj_asd], [0, 1, 2]
+        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, ids)]
+        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segs])       # (host work: before any device work)
+        if task == 'asd' and not bool((lens == lens[:, :1]).all()):
+            b = int((lens != lens[:, :1]).any(1).nonzero()[0, 0])
+            raise ValueError(f"task 'asd' needs lam, ttm and asd features of equal length in every clip (clip {b}: {lens[b].tolist()})")
+        if self.egx_defer_small:
+            raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
+        seed_dev = getattr(self, "_egx_seed_dev", None)
+        training = bool(self.training)
+        spec, proj_t, _ = self._egx_spec(segs, self.transformer_encoder, self.ln, projs, None,
+                                         p_drop=self.dp_rate if training else 0.0, p_pos=self.pos_embed.dropout.p if training else 0.0,
+                                         training=training, seed=self._egx_seed() if training else 0,
+                                         seed_ptr=seed_dev.data_ptr() if (seed_dev is not None and training) else 0,
+                                         advance_seed=1 if (seed_dev is not None and training) else 0)      # fresh masks per call
+        x = F_egx.encoder_ragged_tokens_train(spec, feats, lens, self.task_embed, self.pos_embed.pe, self.ln.weight, self.ln.bias, proj_t,
+                                              encoder_layer_tensors(self.transformer_encoder), out_layout=1 if task == 'asd' else 0)
+        if task == 'asd':
+            return x.view(-1, 3, self.dim).permute(1, 0, 2)        # (3, sum_b T_b, d): row 3 f + k of x is segment k of frame f
+        return x
+
+    def decode_ragged(self, y, memory, memory_lengths):
+        """decode(..., memory_lengths=) for TRAINING (train and eval mode, under autograd): (B, sy) tokens + the packed (sum_b S_b, d) memory of
+        encode_features_ragged for 'ttm' / 'lam' -> (sy, B, |V|); clip b cross-attends to its own S_b rows, and the memory gradient comes back
+        packed. last_decoder_impl() reports "ragged", or "grouped" where the fused decoder does not serve the shapes."""
+        return self._egx_decode_ragged_train(y, memory, memory_lengths, embedding=self.embedding, pos_embed=self.pos_embed,
+                                             decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate)
+
+    def forward_features_ragged(self, task, lam_feat, ttm_feat, asd_feat, target, *, lengths):
+        """forward() from backbone features over a ragged batch, for the training step of HHI/tasks/multitask/video_tasktranslation.py:39-66:
+        (B, |V|, sy) logits — (sum_b T_b, |V|, sy) for 'asd', one target row per frame — ready for nn.CrossEntropyLoss. The frozen backbones
+        are stock PyTorch and would read padded frames: run them clip by clip (or through a feature cache) and pad their features here."""
+        assert task in ['lam', 'ttm', 'asd']
+        encoded_x = self.encode_features_ragged(task, lam_feat, ttm_feat, asd_feat, lengths=lengths)
+        if task == 'asd':
+            return self.decode(target, encoded_x).permute(1, 2, 0)
+        feats = [lam_feat] if task == 'lam' else [lam_feat, ttm_feat, asd_feat]
+        S = F_egx.ragged_lengths(lengths, lam_feat.shape[0], [f.shape[1] for f in feats]).sum(1)
+        return self.decode_ragged(target, encoded_x, S).permute(1, 2, 0)
+
     def encode(self, video, video_asd, audio, audio_asd, task):
         with torch.no_grad():
             lam_feat = self.lam_model(video, middle=True)

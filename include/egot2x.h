@@ -342,6 +342,33 @@ int egx_ragged_encode_workspace(const egx_config* cfg, const egx_segment* segs, 
 int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
                       const egx_layer* layers, int B, float* tokens_out, int out_layout, void* workspace, void* stream);
 
+/* ---- ABI v18: ragged batches on the wide bf16 path, training (EgoT2-g HHI) ----
+ * The encoder side of one training step of the EgoT2-g HHI model (HHI/tasks/multitask/video_tasktranslation.py:39-66) over B clips of their
+ * own lengths: the reference cannot batch such clips, so it feeds same-length mini-batches of <= 15 clips (SequenceBatchSampler,
+ * video_tasktranslation.py:144-156) through encode() (HHI/models/multitask/task_prompt_model.py:230-258). lengths, segs, out_layout and
+ * tokens_out as egx_ragged_encode; a clip's rows, and its contribution to every gradient, are what that clip gives alone and unpadded.
+ *   training / seed / cfg->seed_ptr / cfg->advance_seed   dropout as egx_encoder_fwd (p_drop, p_pos; p_feat on the projections). Row sites
+ *               (positional, the two residual branches, FFN hidden) key on the packed token row, the feature dropout on the compacted row of its
+ *               segment, the attention on (clip's index in the batch, head, query) with the row stride of the clip's kernel class (128 for
+ *               S_b <= 128, 512 beyond): a batch whose clips all have the padded lengths draws the masks of egx_encoder_fwd with that seed.
+ *   egx_ragged_encode_bwd takes the SAME lengths and out_layout and the forward's `saved`; d_tokens in the layout of tokens_out (out_layout 1:
+ *               read back through the same row map). Gradients are ADDED into the egx_segment_grads / egx_layer_grads targets after
+ *               cfg->zero_buf / zero_bytes (if set) has been zero-filled, as egx_encoder_bwd. All cross-workgroup sums run in a fixed order:
+ *               the same batch and seed give bit-identical gradients.
+ * Limits of egx_ragged_encode. Refused with a message: ce, token_ce, out_tokens, bucket_cb, bwd_stage != 0, compute other than bf16, a clip
+ * beyond the wide attention, egx_segment_grads.feat (gradients into projected features) and egx_segment_grads.pos (a learned positional table).
+ * `saved` / `scratch`: egx_ragged_encode_train_workspace() bytes, functions of sum_b S_b and the model (never of B * max S_b). The forward
+ * writes a per-clip table built from `lengths` into `saved` on `stream` (the backward reads it there): a captured hipGraph would replay THIS
+ * call's lengths, so the calls are not for graph capture. */
+int egx_ragged_encode_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
+                                      size_t* scratch_bytes);
+int egx_ragged_encode_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                                const egx_layer* layers, int B, float* tokens_out, int out_layout, void* saved, int training, uint64_t seed,
+                                void* stream);
+int egx_ragged_encode_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const egx_layer* layers, int B,
+                          const float* d_tokens, int out_layout, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                          float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, void* stream);
+
 /* ---- ABI v18: ragged batches for training (d = 128 TTM / ASD translators) ----
  * One forward + backward over B clips of their own lengths, every clip keeping all of its frames: replaces the reference's sorted
  * ~400-frame batches truncated to their shortest clip (HHI/dataset/ttm/sampler.py:14-60, HHI/utils/ttm/utils.py:232-241) in the TTM
@@ -548,6 +575,23 @@ int egx_decoder_ragged_workspace(const egx_dec_config* cfg, int B, const int* me
 int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const int* mem_lengths, const float* emb,
                            const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B,
                            float* logits, void* workspace, void* stream);
+/* ---- ABI v18: the decoder over ragged memories, training ----
+ * The decoder side of the same training step (decode(), task_prompt_model.py:260-269, inside video_tasktranslation.py:39-66; the
+ * mixed-length batches of :144-156): egx_decoder_fwd / egx_decoder_bwd over a packed memory of sum_b S_b rows (mem_lengths as
+ * egx_decoder_ragged_fwd), with dropout on every site. Clip b's target rows cross-attend to its own rows only; d_memory is packed
+ * (sum_b S_b, d) and a clip's rows receive gradient from that clip's target rows alone. Dropout keys as the uniform decoder: target row, and
+ * (clip's index in the batch, head, query) on the attention probabilities, so equal memories draw egx_decoder_fwd's masks. The self-attention
+ * and all row-wise parts are the uniform code over B * sy target rows and sum_b S_b memory rows. egx_decoder_ragged_bwd takes the SAME
+ * mem_lengths and the forward's `saved`; every other argument as egx_decoder_bwd. `saved` / `scratch`: egx_decoder_ragged_train_workspace()
+ * bytes (functions of sum_b S_b). The forward writes the per-clip table into `saved` on `stream`: not for graph capture. */
+int egx_decoder_ragged_train_workspace(const egx_dec_config* cfg, int B, const int* mem_lengths, size_t* saved_bytes, size_t* scratch_bytes);
+int egx_decoder_ragged_train_fwd(const egx_dec_config* cfg, const int64_t* tokens, const float* memory, const int* mem_lengths, const float* emb,
+                                 const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B,
+                                 float* logits, void* saved, void* scratch, int training, uint64_t seed, void* stream);
+int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, const int* mem_lengths, const egx_dec_layer* layers, const float* fc_w,
+                           int B, const float* d_logits, const void* saved, void* scratch, float* d_memory, float* d_emb,
+                           const egx_dec_layer_grads* grads, float* d_fc_w, float* d_fc_b, void* zero_buf, size_t zero_bytes, int training,
+                           uint64_t seed, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
