@@ -137,13 +137,12 @@ bool wide_attn_supported(int S, int dh);      // S <= 128: head dim 32 / 64 / 96
 size_t wide_attn_delta_bytes(int B, int H, int S);
 int wide_attn_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_bwd(const WideAttnParams& p, hipStream_t st);
-// inference forward over the B clips of p.clips, all of one kernel class (wide_attn_ragged_class): p.S = their longest clip
-int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st);
-// training over the same clip lists: the forward with dropout on the probabilities, and the backward (p.d_out -> p.d_qkv, every packed row
-// written once; the long class also reads p.out and writes p.delta, both with the log-sum-exp's layout: (clip, head) rows from H tok0 + h S_c).
+// forward over the B clips of p.clips, all of one kernel class (wide_attn_ragged_class): p.S = their longest clip; dropout on the probabilities
+// when p.drop_thresh is set. The backward runs over the same clip lists (p.d_out -> p.d_qkv, every packed row written once; the long class also
+// reads p.out and writes p.delta, both with the log-sum-exp's layout: (clip, head) rows from H tok0 + h S_c).
 // Dropout rows key on (clip's index in the BATCH, head, query) with the row stride of the clip's class (128; 512 for the long kernels), so a
 // batch of equal-length clips draws the masks of the uniform call.
-int wide_attn_ragged_train_fwd(const WideAttnParams& p, hipStream_t st);
+int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_ragged_bwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_ragged_class(int S, int dh);      // 0: S <= 64, 1: 64 < S <= 128, 2: the long kernel, -1: unsupported
 

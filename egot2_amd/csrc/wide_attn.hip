@@ -1178,7 +1178,8 @@ static int launch_attn_long_ragged(const WideAttnParams& p, hipStream_t st) {
 }
 
 // training forward (dropout on the probabilities, rows keyed by the clip's batch position) and inference forward: the same kernels
-static int attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
+int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
+    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_fwd: bad arguments");
     if (p.B <= 0) return 0;
     const int dh = p.d / p.H, cls = wide_attn_ragged_class(p.S, dh);
     EGX_CHECK(cls >= 0, "wide attention: S=%d head dim %d unsupported", p.S, dh);
@@ -1193,17 +1194,6 @@ static int attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
     }
 #undef EGX_ATTN_RG_CASE
     return 1;
-}
-
-int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st) {
-    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_fwd: bad arguments");
-    EGX_CHECK(!p.drop_thresh, "wide_attn_ragged_fwd: inference only (no dropout)");
-    return attn_ragged_fwd(p, st);
-}
-
-int wide_attn_ragged_train_fwd(const WideAttnParams& p, hipStream_t st) {
-    EGX_CHECK(p.qkv && p.out && p.lse && p.rtab && p.clips && p.H > 0 && p.d % p.H == 0 && p.d % 8 == 0, "wide_attn_ragged_train_fwd: bad arguments");
-    return attn_ragged_fwd(p, st);
 }
 
 template <int DH, int NKT>

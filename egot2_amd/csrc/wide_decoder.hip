@@ -48,7 +48,7 @@ struct DecAttnParams {
     int B, H, Sq, Sk, causal;
     float scale;
     uint64_t drop_key; uint32_t drop_thresh; float drop_inv;
-    // ragged memories (dec_attn_ragged, inference): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
+    // ragged memories (dec_attn_ragged_train): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
     // of k / v, its query / output rows c * Sq + i. Sk = the longest memory of the launch.
     const int* mtab; const int* clips;
 };
@@ -394,171 +394,9 @@ int dec_attn(DecAttnParams p, int dh, bool f32, hipStream_t st) {
     return 0;
 }
 
-// ---- ragged memories (egx_decoder_ragged_fwd, inference: no dropout) ----
-// Forward of dec_attn_kernel (bf16 operands) for clip p.clips[bh / H] with its own memory rows: separate copies, so that the uniform
-// kernels' code and register allocation stay as they are.
-template <int DH>
-__global__ __launch_bounds__(256) void dec_attn_ragged_kernel(DecAttnParams p) {
-    __shared__ float sQ[4][DA_MAXQ][DH];        // query rows (fp32)
-    __shared__ float sP[4][DA_MAXQ][64];        // probabilities
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bh = blockIdx.x * 4 + wave;
-    if (bh >= p.B * p.H) return;                // (no barrier below: every wave works alone)
-    const int b = p.clips[bh / p.H], h = bh % p.H;
-    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1];
-    const size_t m0 = (size_t)p.mtab[2 * b];
-    const bool kv_lane = lane < Sk;
-    float kr[DH];
-    {
-        const size_t krow = (m0 + (kv_lane ? lane : 0)) * p.ldk + h * DH;
-#pragma unroll
-        for (int c = 0; c < DH; c += 8) {
-            float t8[8];
-            load8<false>(p.k, krow + c, t8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
-        }
-    }
-    for (int i = lane; i < Sq * DH; i += 64) {
-        const int r = i / DH, c = i - r * DH;
-        sQ[wave][r][c] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < DA_MAXQ; ++i) {
-        if (i >= Sq) break;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < DH; c += 4) {
-            const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
-            s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
-        }
-        s = kv_lane ? s * p.scale : -INFINITY;
-        const float m = wmax64(s);
-        const float e = kv_lane ? __expf(s - m) : 0.f;
-        sP[wave][i][lane] = e / wsum64d(e);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane < DH) {
-        float acc[DA_MAXQ];
-#pragma unroll
-        for (int i = 0; i < DA_MAXQ; ++i) acc[i] = 0.f;
-        const size_t v0 = m0 * p.ldv + h * DH + lane;
-        for (int j = 0; j < Sk; ++j) {
-            const float vv = load1<false>(p.v, v0 + (size_t)j * p.ldv);
-#pragma unroll
-            for (int i = 0; i < DA_MAXQ; ++i)
-                if (i < Sq) acc[i] += sP[wave][i][j] * vv;
-        }
-#pragma unroll
-        for (int i = 0; i < DA_MAXQ; ++i)
-            if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + lane] = f2bf(acc[i]);
-    }
-}
-
-// forward of dec_attn_long_kernel for clip p.clips[blockIdx.x / H] (LDS sized by the launch's longest memory, chunks by the clip's own)
-template <int DH>
-__global__ __launch_bounds__(256) void dec_attn_long_ragged_kernel(DecAttnParams p) {
-    constexpr int LDK = DH + 1;
-    extern __shared__ float dal_sm[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = p.clips[blockIdx.x / p.H], h = blockIdx.x % p.H;
-    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1], SKP = (Sk + 63) & ~63;
-    const size_t m0 = (size_t)p.mtab[2 * b];
-    float* Cs = dal_sm;                     // K or V chunk [64][DH + 1]
-    float* Qs = Cs + 64 * LDK;
-    float* Ps = Qs + DA_MAXQ * DH;          // [Sq][SKP]
-    const bf16_t* kb = reinterpret_cast<const bf16_t*>(p.k) + m0 * p.ldk + h * DH;
-    const bf16_t* vb = reinterpret_cast<const bf16_t*>(p.v) + m0 * p.ldv + h * DH;
-    auto stage = [&](const bf16_t* src, int ld, int j0) {
-        __syncthreads();
-        for (int i = tid; i < 64 * (DH / 8); i += 256) {
-            const int j = i / (DH / 8), c = (i - j * (DH / 8)) * 8;
-            float t8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (j0 + j < Sk) load8<false>(src, (size_t)(j0 + j) * ld + c, t8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) Cs[j * LDK + c + e] = t8[e];
-        }
-        __syncthreads();
-    };
-    for (int i = tid; i < Sq * DH; i += 256) {
-        const int r = i / DH, c = i - r * DH;
-        Qs[i] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
-    }
-    for (int j0 = 0; j0 < Sk; j0 += 64) {
-        stage(kb, p.ldk, j0);
-        for (int i = wave; i < Sq; i += 4) {
-            float sc = 0.f;
-#pragma unroll
-            for (int c = 0; c < DH; ++c) sc += Qs[i * DH + c] * Cs[lane * LDK + c];
-            Ps[i * SKP + j0 + lane] = j0 + lane < Sk ? sc * p.scale : -INFINITY;
-        }
-    }
-    __syncthreads();
-    for (int i = wave; i < Sq; i += 4) {
-        float m = -INFINITY;
-        for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
-        m = wmax64(m);
-        float sum = 0.f;
-        for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
-        sum = 1.f / wsum64d(sum);
-        for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;
-    }
-    constexpr int NE = DA_MAXQ * DH / 256;
-    float acc[NE];
-#pragma unroll
-    for (int u = 0; u < NE; ++u) acc[u] = 0.f;
-    for (int j0 = 0; j0 < Sk; j0 += 64) {
-        stage(vb, p.ldv, j0);
-#pragma unroll
-        for (int u = 0; u < NE; ++u) {
-            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-            if (i < Sq) {
-                float a = 0.f;
-                for (int j = 0; j < 64; ++j) a += Ps[i * SKP + j0 + j] * Cs[j * LDK + c];
-                acc[u] += a;
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-        const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-        if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + c] = f2bf(acc[u]);
-    }
-}
-
-// one launch per kernel class: p.clips / p.B the clips of the class, p.Sk their longest memory
-int dec_attn_ragged(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
-    EGX_CHECK(dh == 32 || dh == 64, "decoder attention: head dim %d (32 or 64)", dh);
-    EGX_CHECK(!p.drop_thresh && !p.causal && p.Sk >= 1 && p.Sk <= DAL_MAXK, "decoder attention (ragged): bad arguments");
-    if (p.B <= 0) return 0;
-    p.scale = 1.f / sqrtf((float)dh);
-    if (!long_class) {
-        EGX_CHECK(p.Sk <= DA_MAXK, "decoder attention (ragged): short class with Sk = %d", p.Sk);
-        const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
-        if (dh == 64) hipLaunchKernelGGL(dec_attn_ragged_kernel<64>, grid, block, 0, st, p);
-        else hipLaunchKernelGGL(dec_attn_ragged_kernel<32>, grid, block, 0, st, p);
-        EGX_LAUNCH_CHECK();
-        return 0;
-    }
-    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)DA_MAXQ * dh + (size_t)DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
-    static bool attr[2] = {false, false};
-    const void* fn = dh == 64 ? reinterpret_cast<const void*>(&dec_attn_long_ragged_kernel<64>) : reinterpret_cast<const void*>(&dec_attn_long_ragged_kernel<32>);
-    if (!attr[dh == 64]) {
-        EGX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
-        attr[dh == 64] = true;
-    }
-    if (dh == 64) hipLaunchKernelGGL(dec_attn_long_ragged_kernel<64>, dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
-    else hipLaunchKernelGGL(dec_attn_long_ragged_kernel<32>, dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
-    EGX_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- ragged memories, training (egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd) ----
+// ---- ragged memories (egx_decoder_ragged_fwd, egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd) ----
 // dec_attn_kernel (bf16 operands) and dec_attn_long_kernel for clip p.clips[i] with its own memory rows [mtab[2c], + mtab[2c + 1]), forward with
-// dropout and backward. Separate copies: the uniform kernels and the inference copies above keep their code and register allocation.
+// dropout (none at drop_thresh 0: the inference call) and backward. Separate copies: the uniform kernels keep their code and register allocation.
 template <int DH, bool BWD>
 __global__ __launch_bounds__(256) void dec_attn_ragged_train_kernel(DecAttnParams p) {
     constexpr bool F32 = false;
@@ -833,8 +671,9 @@ __global__ __launch_bounds__(256) void dec_attn_long_ragged_train_kernel(DecAttn
     }
 }
 
-// training over ragged memories: forward with dropout on the probabilities (BWD = false) and backward (dq for the clip's Sq target rows, dk / dv
-// for the clip's own memory rows, written packed: every memory row belongs to one clip). One launch per kernel class, as dec_attn_ragged.
+// over ragged memories: forward with dropout on the probabilities (BWD = false) and backward (dq for the clip's Sq target rows, dk / dv for the
+// clip's own memory rows, written packed: every memory row belongs to one clip). One launch per kernel class: p.clips / p.B the clips of the
+// class, p.Sk their longest memory.
 template <bool BWD>
 int dec_attn_ragged_train(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
     EGX_CHECK(dh == 32 || dh == 64, "decoder attention: head dim %d (32 or 64)", dh);
@@ -849,7 +688,8 @@ int dec_attn_ragged_train(DecAttnParams p, int dh, bool long_class, hipStream_t 
         EGX_LAUNCH_CHECK();
         return 0;
     }
-    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)2 * DA_MAXQ * dh + (size_t)2 * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
+    // Cs, Qs, Gs, Ps and (backward only) Ds: the forward does not reserve Ds, which would cut the workgroups per CU at long memories
+    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)2 * DA_MAXQ * dh + (size_t)(BWD ? 2 : 1) * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
     static bool attr[2] = {false, false};
     const void* fn = dh == 64 ? reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<64, BWD>)
                               : reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<32, BWD>);
@@ -1145,8 +985,7 @@ namespace {
 // ragged memories (egx_decoder_ragged_fwd): the device copy of the per-clip table and the clips of the two cross-attention kernel classes
 struct DecRagged {
     const int* mtab;                // [B][2]: first memory row, memory rows
-    const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_ragged_kernel), class 1: the chunked kernel
-    bool train;                     // the training kernels (dropout on the probabilities; their backward reads the same table)
+    const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_ragged_train_kernel), class 1: the chunked kernel
 };
 
 int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const float* memory, const float* emb, const float* pe,
@@ -1259,7 +1098,7 @@ int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
                 a.mtab = rg->mtab;
                 for (int c = 0; c < 2; ++c) {
                     a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
-                    if (rg->train ? dec_attn_ragged_train<false>(a, dh, c == 1, st) : dec_attn_ragged(a, dh, c == 1, st)) return 1;
+                    if (dec_attn_ragged_train<false>(a, dh, c == 1, st)) return 1;
                 }
             } else if (dec_attn<false>(a, dh, false, st)) return 1;
         }
@@ -1308,12 +1147,11 @@ int decoder_ragged_plan(const egx_dec_config* cfg, int B, const int* mem_lengths
     bytes = off_tab + align_up(tab.size() * sizeof(int), 256);
     return 0;
 }
-DecRagged dec_ragged_view(const int* dtab, int B, const int (&n)[2], const int (&smax)[2], bool train) {
+DecRagged dec_ragged_view(const int* dtab, int B, const int (&n)[2], const int (&smax)[2]) {
     DecRagged rg;
     rg.mtab = dtab;
     rg.clips[0] = dtab + 2 * (size_t)B; rg.clips[1] = rg.clips[0] + n[0];
     for (int c = 0; c < 2; ++c) { rg.n[c] = n[c]; rg.Sk_max[c] = smax[c] ? smax[c] : 1; }
-    rg.train = train;
     return rg;
 }
 }  // namespace
@@ -1352,7 +1190,7 @@ int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, con
     // the table goes to the device in the arguments of upload launches (stream-ordered; a captured graph would replay THESE lengths)
     int* dtab = reinterpret_cast<int*>((char*)workspace + off_tab);
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
-    const DecRagged rg = dec_ragged_view(dtab, B, n, smax, false);
+    const DecRagged rg = dec_ragged_view(dtab, B, n, smax);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, workspace, 0, 0, st, &rg);
 }
 
@@ -1636,7 +1474,7 @@ int egx_decoder_ragged_train_fwd(const egx_dec_config* cfg, const int64_t* token
     hipStream_t st = (hipStream_t)stream;
     int* dtab = reinterpret_cast<int*>((char*)saved + off_tab);       // (kept in `saved`: the backward reads the same table)
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
-    const DecRagged rg = dec_ragged_view(dtab, B, n, smax, true);
+    const DecRagged rg = dec_ragged_view(dtab, B, n, smax);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, saved, training, seed, st, &rg);
 }
 
@@ -1651,7 +1489,7 @@ int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, con
     if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb, true)) return 1;
     EGX_CHECK(tokens && layers && fc_w && d_logits && saved && scratch && grads, "egx_decoder_ragged_bwd: null pointer argument");
     // (the forward left the table in `saved`; the host copy rebuilt from the same lengths gives its layout)
-    const DecRagged rg = dec_ragged_view(reinterpret_cast<const int*>((const char*)saved + off_tab), B, n, smax, true);
+    const DecRagged rg = dec_ragged_view(reinterpret_cast<const int*>((const char*)saved + off_tab), B, n, smax);
     return decoder_bwd_run(cfg, pl, tokens, layers, fc_w, B, d_logits, saved, scratch, d_memory, d_emb, grads, d_fc_w, d_fc_b, zero_buf, zero_bytes,
                            training, seed, (hipStream_t)stream, &rg);
 }

@@ -34,13 +34,11 @@ struct WPlan {
     size_t gA, gB, dres, dy16, dhid16, dattn16, dqkv16, adelta, dseg16, slabs, slab_all, slab_all_bytes, lnpart, cspart, rowpart, rowpart_bytes, scratch_bytes;
 };
 
-// a ragged batch (see "ragged batches" below): the host copy of its table and, for the inference call, its workspace layout
+// a ragged batch (see "ragged batches" below): the host copy of its table
 struct WRagged {
     int B = 0, K = 0, layout = 0;
+    bool train = false;     // the training entry points; else egx_ragged_encode, whose workspace make_wplan lays out for inference
     size_t N = 0, R[EGX_MAX_SEGMENTS] = {}, Rmax = 0;
-    size_t zero = 0, seg_w[EGX_MAX_SEGMENTS] = {}, feat16 = 0, pre = 0;
-    size_t w_in[64] = {}, w_o[64] = {}, w1[64] = {}, w2[64] = {};
-    size_t x32 = 0, x16 = 0, qkv = 0, lse = 0, attn = 0, res = 0, x1_32 = 0, x1_16 = 0, hid = 0, tab_off = 0, bytes = 0;
     // host copy of the batch table (ints): B clip records (WIDE_RG_REC), the clips of attention class 0 | 1 | 2, per segment the source
     // row (b * segs[k].T + t) and the token row of every compacted row, and (out_layout 1) the output row of every token row
     std::vector<int> tab;
@@ -51,24 +49,34 @@ struct WRagged {
 size_t take(size_t& cur, size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
 size_t smax(size_t a, size_t b) { return a > b ? a : b; }
 
-// rg: a ragged batch — N = sum_b S_b packed token rows and R_k compacted rows of segment k instead of B * S and B * T_k; nothing is sized by B * max S_b
+// rg: a ragged batch — N = sum_b S_b packed token rows and R_k compacted rows of segment k instead of B * S and B * T_k; nothing is sized by B * max S_b.
+// An inference batch (rg->train false: egx_ragged_encode) keeps nothing for a backward: one set of activation buffers serves every layer and every
+// segment, res2 / stats2 reuse res1 / stats1, and no W^T is laid out (offset 0, the zero page's); only `saved` is used.
 void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl, const WRagged* rg = nullptr) {
     memset(&pl, 0, sizeof(pl));
     pl.B = B; pl.d = cfg->d_model; pl.H = cfg->n_heads; pl.dff = cfg->d_ff; pl.L = cfg->n_layers; pl.nseg = cfg->n_segments;
     int S = 0;
     for (int i = 0; i < pl.nseg; ++i) { pl.seg_off[i] = S; S += segs[i].T; }
     pl.S = S; pl.N = rg ? rg->N : (size_t)B * S;
+    const bool infer = rg && !rg->train;
+    size_t din_max = 0;
+    for (int i = 0; i < pl.nseg; ++i) din_max = smax(din_max, (size_t)segs[i].d_in);
     auto seg_rows = [&](int i) { return rg ? rg->R[i] : (size_t)B * segs[i].T; };
     const size_t d = pl.d, N = pl.N, dff = pl.dff;
     size_t cur = 0;
+    auto take_wt = [&](size_t bytes) { return infer ? (size_t)0 : take(cur, bytes); };
     pl.zero = take(cur, 1024);
     pl.keys = take(cur, (size_t)64 * DROP_KEY_SLOTS * sizeof(uint64_t));
     for (int i = 0; i < pl.nseg; ++i) {
-        size_t rows = seg_rows(i);
+        if (segs[i].proj_w) pl.seg_w[i] = take(cur, d * segs[i].d_in * 2);
+        if (infer && i > 0) {
+            pl.seg_feat16[i] = pl.seg_feat16[0]; pl.seg_pre[i] = pl.seg_pre[0]; pl.seg_stats[i] = pl.seg_stats[0];
+            continue;
+        }
+        const size_t rows = infer ? rg->Rmax : seg_rows(i), din = infer ? din_max : (size_t)segs[i].d_in;
         if (segs[i].proj_w) {
-            pl.seg_w[i] = take(cur, d * segs[i].d_in * 2);
             // bf16 copy of the features (the projection GEMM's operand); features that arrive in bf16 and un-pooled are used in place
-            if (rg || !(segs[i].feat_bf16 && segs[i].pool <= 1)) pl.seg_feat16[i] = take(cur, rows * segs[i].d_in * 2);
+            if (rg || !(segs[i].feat_bf16 && segs[i].pool <= 1)) pl.seg_feat16[i] = take(cur, rows * din * 2);
             pl.seg_pre[i] = take(cur, rows * d * 4);
         }
         pl.seg_stats[i] = take(cur, rows * 2 * 4);
@@ -76,10 +84,12 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
     size_t x0_32 = take(cur, N * d * 4);
     for (int l = 0; l < pl.L; ++l) {
         WLayer& o = pl.layer[l];
-        o.w_in = take(cur, 3 * d * d * 2); o.w_in_t = take(cur, 3 * d * d * 2);
-        o.w_o = take(cur, d * d * 2); o.w_o_t = take(cur, d * d * 2);
-        o.w1 = take(cur, dff * d * 2); o.w1_t = take(cur, dff * d * 2);
-        o.w2 = take(cur, dff * d * 2); o.w2_t = take(cur, dff * d * 2);
+        if (infer && l > 0) o = pl.layer[0];        // (its weights are replaced below)
+        o.w_in = take(cur, 3 * d * d * 2); o.w_in_t = take_wt(3 * d * d * 2);
+        o.w_o = take(cur, d * d * 2); o.w_o_t = take_wt(d * d * 2);
+        o.w1 = take(cur, dff * d * 2); o.w1_t = take_wt(dff * d * 2);
+        o.w2 = take(cur, dff * d * 2); o.w2_t = take_wt(dff * d * 2);
+        if (infer && l > 0) continue;
         o.x32 = l == 0 ? x0_32 : take(cur, N * d * 4);
         o.x16 = take(cur, N * d * 2);
         o.qkv = take(cur, N * 3 * d * 2);
@@ -90,8 +100,8 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
         o.x1_32 = take(cur, N * d * 4);
         o.x1_16 = take(cur, N * d * 2);
         o.hid = take(cur, N * dff * 2);
-        o.res2 = take(cur, N * d * 4);
-        o.stats2 = take(cur, N * 2 * 4);
+        o.res2 = infer ? o.res1 : take(cur, N * d * 4);
+        o.stats2 = infer ? o.stats1 : take(cur, N * 2 * 4);
     }
     if (rg) pl.tab = take(cur, (rg->outmap ? rg->tab.size() : rg->tab.size() + N) * sizeof(int));     // (sized for out_layout 1 either way)
     pl.saved_bytes = cur;
@@ -208,13 +218,14 @@ int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
         WideCastBatch cb;
         for (int i = 0; i < pl.nseg; ++i)
             if (segs[i].proj_w && wide_cast_add(cb, segs[i].proj_w, d, segs[i].d_in, segs[i].d_in, at<bf16_t>(saved, pl.seg_w[i]), nullptr, st)) return 1;
+        auto wt = [&](size_t off) { return off ? at<bf16_t>(saved, off) : nullptr; };       // (0: the plan laid out no W^T)
         for (int l = 0; l < pl.L; ++l) {
             const WLayer& o = pl.layer[l];
             const egx_layer& w = layers[l];
-            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, at<bf16_t>(saved, o.w_in), at<bf16_t>(saved, o.w_in_t), st)) return 1;
-            if (wide_cast_add(cb, w.out_proj_w, d, d, d, at<bf16_t>(saved, o.w_o), at<bf16_t>(saved, o.w_o_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(saved, o.w1), at<bf16_t>(saved, o.w1_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(saved, o.w2), at<bf16_t>(saved, o.w2_t), st)) return 1;
+            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, at<bf16_t>(saved, o.w_in), wt(o.w_in_t), st)) return 1;
+            if (wide_cast_add(cb, w.out_proj_w, d, d, d, at<bf16_t>(saved, o.w_o), wt(o.w_o_t), st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(saved, o.w1), wt(o.w1_t), st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(saved, o.w2), wt(o.w2_t), st)) return 1;
         }
         if (wide_cast_flush(cb, st)) return 1;
     }
@@ -278,7 +289,7 @@ int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
                 for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {       // one launch per attention kernel class
                     if (!rg->ncls[c]) continue;
                     a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
-                    if (wide_attn_ragged_train_fwd(a, st)) return 1;
+                    if (wide_attn_ragged_fwd(a, st)) return 1;
                 }
             } else if (wide_attn_fwd(a, st)) return 1;
         }
@@ -527,15 +538,14 @@ int wide_encoder_bwd(const egx_config* cfg, const egx_segment* segs, const float
                            nullptr, nullptr);
 }
 
-// ---- ragged batches (egx_ragged_encode, inference) -------------------------------------------------------------------------------------
+// ---- ragged batches (egx_ragged_encode, egx_ragged_encode_train_*) ---------------------------------------------------------------------
 // Clip b has T_{b,k} frames per segment and S_b = sum_k T_{b,k} tokens; its tokens are rows [tok0_b, tok0_b + S_b) of every (N, .) array,
 // N = sum_b S_b, segment k from row tok0_b + off_{b,k}. Token preparation gathers the valid frames of segment k into R_k = sum_b T_{b,k}
 // compacted rows (wide_gather_cast), projects them with one GEMM and scatters them to their token rows in the shared LayerNorm
 // (wide_ln_fwd_mapped); GEMMs and row kernels then run over the N token rows as in the uniform forward; the attention runs one launch per
 // kernel class over the clips of that class (wide_attn_ragged_fwd). Nothing in the workspace is sized by B * max S_b.
 namespace {
-// train: the training entry points (dropout allowed; the workspace layout at the end is the inference call's and unused there: make_wplan lays
-// `saved` / `scratch` out over the same table)
+// train: the training entry points (dropout allowed). make_wplan lays the workspace out over the table.
 int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int out_layout, WRagged& rp, bool train = false) {
     EGX_CHECK(cfg && segs && lengths, "ragged encode: null argument");
     EGX_CHECK(B >= 1 && B <= (1 << 20), "ragged encode: B=%d clips (1 .. %d)", B, 1 << 20);
@@ -555,7 +565,7 @@ int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, co
     for (int k = 0; k < K; ++k)
         EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0 && segs[k].pool <= 1 && segs[k].T >= 1,
                   "ragged encode: segment %d needs a projection with d_in %% 128 == 0 and no frame pooling", k);
-    rp.B = B; rp.K = K; rp.layout = out_layout;
+    rp.B = B; rp.K = K; rp.layout = out_layout; rp.train = train;
     rp.tab.assign((size_t)B * WIDE_RG_REC + B, 0);
     size_t tok = 0;
     for (int b = 0; b < B; ++b) {
@@ -611,23 +621,23 @@ int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, co
             F0 += rec[WRG_T];
         }
     }
-    const size_t N = rp.N, dd = d;
-    size_t cur = 0, din_max = 0;
-    rp.zero = take(cur, 1024);
-    for (int k = 0; k < K; ++k) { rp.seg_w[k] = take(cur, dd * segs[k].d_in * 2); din_max = smax(din_max, (size_t)segs[k].d_in); }
-    for (int l = 0; l < L; ++l) {
-        rp.w_in[l] = take(cur, 3 * dd * dd * 2); rp.w_o[l] = take(cur, dd * dd * 2);
-        rp.w1[l] = take(cur, (size_t)dff * dd * 2); rp.w2[l] = take(cur, (size_t)dff * dd * 2);
-    }
-    rp.feat16 = take(cur, rp.Rmax * din_max * 2);
-    rp.pre = take(cur, rp.Rmax * dd * 4);
-    rp.x32 = take(cur, N * dd * 4); rp.x16 = take(cur, N * dd * 2);
-    rp.qkv = take(cur, N * 3 * dd * 2); rp.lse = take(cur, N * cfg->n_heads * 4); rp.attn = take(cur, N * dd * 2);
-    rp.res = take(cur, N * dd * 4); rp.x1_32 = take(cur, N * dd * 4); rp.x1_16 = take(cur, N * dd * 2);
-    rp.hid = take(cur, N * (size_t)dff * 2);
-    rp.tab_off = take(cur, (rp.outmap ? rp.tab.size() : rp.tab.size() + N) * sizeof(int));   // (sized for out_layout 1 either way)
-    rp.bytes = cur;
     return 0;
+}
+
+// the forward of a ragged batch (egx_ragged_encode, egx_ragged_encode_train_fwd): table and arguments checked before the first device call
+int ragged_encode_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b, const egx_layer* layers,
+                      int B, float* tokens_out, int out_layout, void* saved, int training, uint64_t seed, void* stream, bool train, const char* who) {
+    WRagged rp;
+    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp, train)) return 1;
+    EGX_CHECK(ln_w && ln_b && layers && tokens_out && saved, "%s: null pointer argument", who);
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl, &rp);
+    hipStream_t st = (hipStream_t)stream;
+    // the batch table into `saved` (a training backward reads it there), stream-ordered in the arguments of upload launches: a captured hipGraph
+    // would replay THIS call's lengths for every batch, so the call is not meant for capture
+    int* tab = (int*)((char*)saved + pl.tab);
+    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    return encoder_fwd_run(cfg, pl, segs, ln_w, ln_b, layers, B, tokens_out, saved, training, seed, st, &rp, tab);
 }
 }  // namespace
 
@@ -640,113 +650,15 @@ extern "C" {
 int egx_ragged_encode_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
     WRagged rp;
     if (ragged_encode_plan(cfg, segs, B, lengths, 0, rp)) return 1;
-    if (bytes) *bytes = rp.bytes;
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl, &rp);
+    if (bytes) *bytes = pl.saved_bytes;
     return 0;
 }
 
 int egx_ragged_encode(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
                       const egx_layer* layers, int B, float* tokens_out, int out_layout, void* workspace, void* stream) {
-    WRagged rp;
-    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp)) return 1;
-    EGX_CHECK(ln_w && ln_b && layers && tokens_out && workspace, "egx_ragged_encode: null pointer argument");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int d = cfg->d_model, dff = cfg->d_ff, L = cfg->n_layers, H = cfg->n_heads, K = rp.K, N = (int)rp.N;
-    // the batch table to the device, stream-ordered, in the arguments of upload launches: a captured hipGraph would replay THIS call's
-    // lengths for every batch, so the call is not meant for capture
-    int* tab = (int*)(ws + rp.tab_off);
-    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
-    EGX_HIP(hipMemsetAsync(ws + rp.zero, 0, 1024, st));
-    const void* zero = ws + rp.zero;
-    {   // the forward's weights -> bf16, one launch
-        WideCastBatch cb;
-        for (int k = 0; k < K; ++k)
-            if (wide_cast_add(cb, segs[k].proj_w, d, segs[k].d_in, segs[k].d_in, (bf16_t*)(ws + rp.seg_w[k]), nullptr, st)) return 1;
-        for (int l = 0; l < L; ++l) {
-            const egx_layer& w = layers[l];
-            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, (bf16_t*)(ws + rp.w_in[l]), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.out_proj_w, d, d, d, (bf16_t*)(ws + rp.w_o[l]), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, (bf16_t*)(ws + rp.w1[l]), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, (bf16_t*)(ws + rp.w2[l]), nullptr, st)) return 1;
-        }
-        if (wide_cast_flush(cb, st)) return 1;
-    }
-    float* x32 = (float*)(ws + rp.x32);
-    bf16_t* x16 = (bf16_t*)(ws + rp.x16);
-    for (int k = 0; k < K; ++k) {       // token preparation: valid frames only -> projection GEMM over R_k rows -> shared LN, scattered
-        const egx_segment& sg = segs[k];
-        const int R = (int)rp.R[k];
-        bf16_t* f16 = (bf16_t*)(ws + rp.feat16);
-        float* pre = (float*)(ws + rp.pre);
-        if (wide_gather_cast(sg.feat, sg.feat_bf16, tab + rp.gmap[k], R, sg.d_in, f16, st)) return 1;
-        WideGemmParams g;
-        g.A = f16; g.B = (const bf16_t*)(ws + rp.seg_w[k]); g.M = R; g.N = d; g.K = sg.d_in; g.lda = sg.d_in; g.ldb = sg.d_in;
-        g.Cf = pre; g.ldc = d; g.bias = sg.proj_b; g.zero_page = zero;
-        if (wide_gemm_nt(g, st)) return 1;
-        WideLnFwdParams lp;
-        lp.x = pre; lp.w = ln_w; lp.b = ln_b; lp.eps = cfg->ln_eps;
-        lp.y32 = x32; lp.y16 = x16; lp.rows = R; lp.d = d; lp.T = sg.T;
-        lp.add_vec = sg.add_vec; lp.pos = sg.pos; lp.pos_stride = sg.pos_stride;
-        lp.out_map = tab + rp.omap[k]; lp.src_map = tab + rp.gmap[k];
-        if (wide_ln_fwd_mapped(lp, st)) return 1;
-    }
-    bf16_t* qkv = (bf16_t*)(ws + rp.qkv);
-    bf16_t* attn = (bf16_t*)(ws + rp.attn);
-    float* res = (float*)(ws + rp.res);
-    float* x1_32 = (float*)(ws + rp.x1_32);
-    bf16_t* x1_16 = (bf16_t*)(ws + rp.x1_16);
-    bf16_t* hid = (bf16_t*)(ws + rp.hid);
-    for (int l = 0; l < L; ++l) {
-        const egx_layer& w = layers[l];
-        const bool last = l + 1 == L;
-        {   // packed in-projection
-            WideGemmParams g;
-            g.A = x16; g.B = (const bf16_t*)(ws + rp.w_in[l]); g.M = N; g.N = 3 * d; g.K = d; g.lda = d; g.ldb = d;
-            g.Cb = qkv; g.ldc = 3 * d; g.bias = w.in_proj_b; g.zero_page = zero;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        for (int c = 0, first = 0; c < 3; first += rp.ncls[c], ++c) {       // one launch per attention kernel class
-            if (!rp.ncls[c]) continue;
-            WideAttnParams a;
-            a.qkv = qkv; a.out = attn; a.lse = (float*)(ws + rp.lse);
-            a.B = rp.ncls[c]; a.S = rp.Smax[c]; a.H = H; a.d = d;
-            a.rtab = tab; a.clips = tab + rp.cls0 + first;
-            if (wide_attn_ragged_fwd(a, st)) return 1;
-        }
-        {   // out-projection + residual -> res
-            WideGemmParams g;
-            g.A = attn; g.B = (const bf16_t*)(ws + rp.w_o[l]); g.M = N; g.N = d; g.K = d; g.lda = d; g.ldb = d;
-            g.Cf = res; g.ldc = d; g.bias = w.out_proj_b; g.residual = x32; g.ldr = d; g.zero_page = zero;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {
-            WideLnFwdParams lp;
-            lp.x = res; lp.w = w.norm1_w; lp.b = w.norm1_b; lp.eps = cfg->ln_eps; lp.y32 = x1_32; lp.y16 = x1_16; lp.rows = N; lp.d = d;
-            if (wide_ln_fwd(lp, st)) return 1;
-        }
-        {   // linear1 + ReLU -> hidden (bf16)
-            WideGemmParams g;
-            g.A = x1_16; g.B = (const bf16_t*)(ws + rp.w1[l]); g.M = N; g.N = dff; g.K = d; g.lda = d; g.ldb = d;
-            g.Cb = hid; g.ldc = dff; g.bias = w.lin1_b; g.relu = 1; g.zero_page = zero;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {   // linear2 + residual -> res
-            WideGemmParams g;
-            g.A = hid; g.B = (const bf16_t*)(ws + rp.w2[l]); g.M = N; g.N = d; g.K = dff; g.lda = dff; g.ldb = dff;
-            g.Cf = res; g.ldc = d; g.bias = w.lin2_b; g.residual = x1_32; g.ldr = d; g.zero_page = zero;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {   // norm2 -> the next layer's input, or the output (out_layout 1: through the frame-major row map)
-            WideLnFwdParams lp;
-            lp.x = res; lp.w = w.norm2_w; lp.b = w.norm2_b; lp.eps = cfg->ln_eps; lp.rows = N; lp.d = d;
-            lp.y32 = last ? tokens_out : x32; lp.y16 = last ? nullptr : x16;
-            if (last && out_layout == 1) {
-                lp.out_map = tab + rp.outmap;
-                if (wide_ln_fwd_mapped(lp, st)) return 1;
-            } else if (wide_ln_fwd(lp, st)) return 1;
-        }
-    }
-    return 0;
+    return ragged_encode_fwd(cfg, segs, lengths, ln_w, ln_b, layers, B, tokens_out, out_layout, workspace, 0, 0, stream, false, "egx_ragged_encode");
 }
 
 /* ---- training (the encoder side of HHI/tasks/multitask/video_tasktranslation.py:39-66 on the mixed-length batches its SequenceBatchSampler,
@@ -765,16 +677,8 @@ int egx_ragged_encode_train_workspace(const egx_config* cfg, const egx_segment* 
 int egx_ragged_encode_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
                                 const egx_layer* layers, int B, float* tokens_out, int out_layout, void* saved, int training, uint64_t seed,
                                 void* stream) {
-    WRagged rp;
-    if (ragged_encode_plan(cfg, segs, B, lengths, out_layout, rp, true)) return 1;
-    EGX_CHECK(ln_w && ln_b && layers && tokens_out && saved, "egx_ragged_encode_train_fwd: null pointer argument");
-    WPlan pl;
-    make_wplan(cfg, segs, B, pl, &rp);
-    hipStream_t st = (hipStream_t)stream;
-    // the batch table into `saved` (the backward reads it there), stream-ordered in the arguments of upload launches: not for graph capture
-    int* tab = (int*)((char*)saved + pl.tab);
-    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
-    return encoder_fwd_run(cfg, pl, segs, ln_w, ln_b, layers, B, tokens_out, saved, training, seed, st, &rp, tab);
+    return ragged_encode_fwd(cfg, segs, lengths, ln_w, ln_b, layers, B, tokens_out, out_layout, saved, training, seed, stream, true,
+                             "egx_ragged_encode_train_fwd");
 }
 
 int egx_ragged_encode_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const egx_layer* layers, int B,

@@ -18,6 +18,27 @@ _SITE0 = 0x4000     # decoder dropout sites live above the encoder's (layer << 8
 
 
 class DecoderMixin:
+    def _egx_decoder_args(self, decoder: nn.TransformerDecoder, pos_embed, n_heads: int, p_drop: float):
+        """(meta, 18 tensors per layer) of a fused decoder call (DecoderFn, RaggedDecoderFn, functional.decoder_ragged)."""
+        train = bool(self.training)
+        meta = dict(n_layers=len(decoder.layers), n_heads=n_heads, d_ff=decoder.layers[0].linear1.out_features, ln_eps=decoder.layers[0].norm1.eps,
+                    p_drop=p_drop if train else 0.0, p_pos=pos_embed.dropout.p if train else 0.0, training=train,
+                    seed=self._egx_seed() if train else 0,
+                    seed_ptr=(self._egx_seed_dev.data_ptr() if train and getattr(self, "_egx_seed_dev", None) is not None else 0))
+        params = []
+        for layer in decoder.layers:
+            sa, ca = layer.self_attn, layer.multihead_attn
+            params += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias,
+                       ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
+                       layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm3.weight, layer.norm3.bias]
+        return meta, params
+
+    def _egx_fused_decoder_ok(self, decoder: nn.TransformerDecoder, d: int, n_heads: int, sy: int, S: int) -> bool:
+        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
+        return (post_ln and F_egx.decoder_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, sy, S,
+                                                    len(decoder.layers))
+                and not getattr(self, "egx_composed_decoder", False))
+
     def _egx_decode(self, y: torch.Tensor, encoded_x: torch.Tensor, *, embedding: nn.Embedding, pos_embed, decoder: nn.TransformerDecoder,
                     fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
         """y (B, sy) int64, encoded_x (S, B, d) decoder memory -> (sy, B, |V|) logits, as the reference's decode()."""
@@ -25,22 +46,9 @@ class DecoderMixin:
         sy = y.shape[1]
         if y.shape[0] != B:
             raise ValueError(f"target batch {y.shape[0]} != memory batch {B}")
-        comp_model = getattr(self, "egx_compute", "f32")
-        d_ff = decoder.layers[0].linear1.out_features
-        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
-        if post_ln and F_egx.decoder_supported(comp_model, d, n_heads, d_ff, sy, S, len(decoder.layers)) and not getattr(self, "egx_composed_decoder", False):
+        if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, S):
             # ONE library call per direction (egx_decoder_fwd / egx_decoder_bwd): bf16 MFMA GEMMs over all B * sy target rows
-            train = bool(self.training)
-            meta = dict(n_layers=len(decoder.layers), n_heads=n_heads, d_ff=d_ff, ln_eps=decoder.layers[0].norm1.eps,
-                        p_drop=p_drop if train else 0.0, p_pos=pos_embed.dropout.p if train else 0.0, training=train,
-                        seed=self._egx_seed() if train else 0,
-                        seed_ptr=(self._egx_seed_dev.data_ptr() if train and getattr(self, "_egx_seed_dev", None) is not None else 0))
-            params = []
-            for layer in decoder.layers:
-                sa, ca = layer.self_attn, layer.multihead_attn
-                params += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias,
-                           ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
-                           layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm3.weight, layer.norm3.bias]
+            meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, p_drop)
             mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
             F_egx._last_dec_impl[0] = "fused"
             out = F_egx.DecoderFn.apply(meta, y, mem2d, embedding.weight, pos_embed.pe[:sy, 0, :], *params, fc.weight, fc.bias)
@@ -79,54 +87,9 @@ class DecoderMixin:
         """Inference decode over a packed ragged memory: y (B, sy) int64, memory (sum_b S_b, d), memory_lengths (B,) with S_b rows for
         clip b -> (sy, B, |V|), each clip's logits as decode() gives them on its own (S_b, 1, d) memory. One egx_decoder_ragged_fwd call
         where the fused decoder serves the shapes (last_decoder_impl() == "ragged"); elsewhere one _egx_decode per memory length ("grouped")."""
-        if self.training:
-            raise ValueError("ragged batches are inference-only: call model.eval() before passing memory_lengths=")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
-                             "(or with every parameter frozen)")
-        B, sy = y.shape
-        d = memory.shape[-1]
-        ml = memory_lengths.detach() if isinstance(memory_lengths, torch.Tensor) else torch.as_tensor(memory_lengths)
-        if ml.dtype.is_floating_point or ml.dtype == torch.bool:
-            raise ValueError(f"memory_lengths must be integers, got {ml.dtype}")
-        ml = ml.to("cpu", torch.int64)
-        if ml.dim() != 1 or ml.shape[0] != B:
-            raise ValueError(f"memory_lengths has shape {tuple(ml.shape)}: expected ({B},), one memory length per target row")
-        if memory.dim() != 2 or (B and (int(ml.min()) < 1 or int(ml.sum()) != memory.shape[0])):
-            raise ValueError(f"memory must be the packed (sum_b S_b, d) rows of the clips: {tuple(memory.shape)} rows, lengths sum to "
-                             f"{int(ml.sum())} (each >= 1)")
-        comp_model = getattr(self, "egx_compute", "f32")
-        d_ff = decoder.layers[0].linear1.out_features
-        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
-        S_max = int(ml.max()) if B else 1
-        if (post_ln and F_egx.decoder_supported(comp_model, d, n_heads, d_ff, sy, S_max, len(decoder.layers))
-                and not getattr(self, "egx_composed_decoder", False)):
-            meta = dict(n_layers=len(decoder.layers), n_heads=n_heads, d_ff=d_ff, ln_eps=decoder.layers[0].norm1.eps)
-            params = []
-            for layer in decoder.layers:
-                sa, ca = layer.self_attn, layer.multihead_attn
-                params += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias,
-                           ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
-                           layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm3.weight, layer.norm3.bias]
-            out = F_egx.decoder_ragged(meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :], params, fc.weight, fc.bias)
-            return out.view(B, sy, -1).permute(1, 0, 2)
-        # grouped: one decode per memory length, on (S, G, d) memories gathered from the packed rows
-        row0 = torch.cumsum(ml, 0) - ml
-        out = None
-        groups = {}
-        for b, S in enumerate(ml.tolist()):
-            groups.setdefault(S, []).append(b)
-        for S, idx in groups.items():
-            rows = (row0[idx][:, None] + torch.arange(S)[None, :]).reshape(-1).to(memory.device)
-            mem = memory.index_select(0, rows).view(len(idx), S, d).permute(1, 0, 2)
-            it = torch.tensor(idx, dtype=torch.int64, device=y.device)
-            o = self._egx_decode(y.index_select(0, it), mem, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
-                                 n_heads=n_heads, p_drop=p_drop)
-            if out is None:
-                out = torch.empty((sy, B, o.shape[-1]), dtype=o.dtype, device=o.device)
-            out.index_copy_(1, it.to(o.device), o)
-        F_egx._last_dec_impl[0] = "grouped"
-        return out
+        self._egx_check_inference("memory_lengths=")
+        return self._egx_decode_packed(y, memory, memory_lengths, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
+                                       n_heads=n_heads, p_drop=p_drop, inference=True)
 
     def _egx_decode_ragged_train(self, y: torch.Tensor, memory: torch.Tensor, memory_lengths, *, embedding: nn.Embedding, pos_embed,
                                  decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
@@ -134,6 +97,11 @@ class DecoderMixin:
         (B,) -> (sy, B, |V|); gradients reach the decoder, the embedding, `fc` and the packed memory. One egx_decoder_ragged_train_fwd /
         egx_decoder_ragged_bwd pair where the fused decoder serves the shapes (last_decoder_impl() == "ragged"); elsewhere one differentiable
         _egx_decode per memory length ("grouped"), whose dropout masks differ from the ragged kernels'. Validation is host work and runs first."""
+        return self._egx_decode_packed(y, memory, memory_lengths, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
+                                       n_heads=n_heads, p_drop=p_drop, inference=False)
+
+    def _egx_decode_packed(self, y, memory, memory_lengths, *, embedding, pos_embed, decoder, fc, n_heads, p_drop, inference: bool):
+        """_egx_decode_ragged (inference: functional.decoder_ragged, no autograd) and _egx_decode_ragged_train (RaggedDecoderFn)."""
         B, sy = y.shape
         d = memory.shape[-1]
         ml = memory_lengths.detach() if isinstance(memory_lengths, torch.Tensor) else torch.as_tensor(memory_lengths)
@@ -145,27 +113,15 @@ class DecoderMixin:
         if memory.dim() != 2 or (B and (int(ml.min()) < 1 or int(ml.sum()) != memory.shape[0])):
             raise ValueError(f"memory must be the packed (sum_b S_b, d) rows of the clips: {tuple(memory.shape)} rows, lengths sum to "
                              f"{int(ml.sum())} (each >= 1)")
-        comp_model = getattr(self, "egx_compute", "f32")
-        d_ff = decoder.layers[0].linear1.out_features
-        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
-        S_max = int(ml.max()) if B else 1
-        train = bool(self.training)
-        if (post_ln and F_egx.decoder_supported(comp_model, d, n_heads, d_ff, sy, S_max, len(decoder.layers))
-                and not getattr(self, "egx_composed_decoder", False)):
-            meta = dict(n_layers=len(decoder.layers), n_heads=n_heads, d_ff=d_ff, ln_eps=decoder.layers[0].norm1.eps,
-                        p_drop=p_drop if train else 0.0, p_pos=pos_embed.dropout.p if train else 0.0, training=train,
-                        seed=self._egx_seed() if train else 0,
-                        seed_ptr=(self._egx_seed_dev.data_ptr() if train and getattr(self, "_egx_seed_dev", None) is not None else 0))
-            params = []
-            for layer in decoder.layers:
-                sa, ca = layer.self_attn, layer.multihead_attn
-                params += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias,
-                           ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
-                           layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm3.weight, layer.norm3.bias]
-            out = F_egx.RaggedDecoderFn.apply(meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :], *params,
-                                              fc.weight, fc.bias)
+        if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, int(ml.max()) if B else 1):
+            meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, p_drop)
+            args = (meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :])
+            if inference:
+                out = F_egx.decoder_ragged(*args, params, fc.weight, fc.bias)
+            else:
+                out = F_egx.RaggedDecoderFn.apply(*args, *params, fc.weight, fc.bias)
             return out.view(B, sy, -1).permute(1, 0, 2)
-        # grouped: one differentiable decode per memory length, on (S, G, d) memories gathered from the packed rows
+        # grouped: one decode per memory length, on (S, G, d) memories gathered from the packed rows (differentiable)
         row0 = torch.cumsum(ml, 0) - ml
         groups = {}
         for b, S in enumerate(ml.tolist()):

@@ -986,6 +986,14 @@ def ragged_token_rows(lengths: torch.Tensor, out_layout: int = 0) -> torch.Tenso
     return torch.cat(rows) if rows else torch.zeros(0, dtype=torch.int64)
 
 
+def _check_out_layout(lengths: torch.Tensor, B: int, out_layout: int):
+    if out_layout not in (0, 1):
+        raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
+    if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
+        b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
+        raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
+
+
 def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
                           proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], out_layout: int = 0):
     """Inference forward (no autograd) returning EVERY token of a ragged batch: feats[k] padded (B, spec.segments[k].T, d_in), `lengths` the
@@ -996,11 +1004,7 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
         raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens, no head")
     B = feats[0].shape[0]
     lengths = _check_host_lengths(lengths, B, len(spec.segments))
-    if out_layout not in (0, 1):
-        raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
-    if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
-        b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
-        raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
+    _check_out_layout(lengths, B, out_layout)
     lib = _lib.load()
     if reload_tuning_each_call:
         lib.egx_tuning_reload()
@@ -1021,25 +1025,6 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
         check(lib.egx_ragged_encode(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
                                     ptr(ws), _stream()))
     _last_impl[0] = IMPL_RAGGED
-    _last_slices[0] = 1
-    return out
-
-
-def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
-    """encoder_ragged_tokens where egx_ragged_encode does not run (compute other than bf16, a forced implementation, a clip beyond the wide
-    attention): one batched forward per group of clips with the same length tuple, on their unpadded frames; rows scattered to their place."""
-    d = spec.d_model
-    device = feats[0].device
-    rows = ragged_token_rows(lengths, out_layout)
-    S = lengths.to(torch.int64).sum(1)
-    tok0 = torch.cumsum(S, 0) - S
-    out = torch.empty((int(S.sum()), d), dtype=torch.float32, device=device)
-    with torch.no_grad():
-        for idx, _, gspec, fs in _length_groups(spec, feats, lengths):
-            r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
-            src = (tok0[idx][:, None] + torch.arange(r.shape[1])[None, :]).reshape(-1)
-            out.index_copy_(0, rows[src].to(device), r.reshape(-1, d))
-    _last_impl[0] = IMPL_GROUPED
     _last_slices[0] = 1
     return out
 
@@ -1139,11 +1124,7 @@ def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor]
                          "after the backward (ddp.allreduce_gradients)")
     B = feats[0].shape[0]
     lengths = _check_host_lengths(lengths, B, len(spec.segments))
-    if out_layout not in (0, 1):
-        raise ValueError("out_layout must be 0 (packed clips) or 1 (frame-major segment tuples)")
-    if out_layout == 1 and B and not bool((lengths == lengths[:, :1]).all()):
-        b = int((lengths != lengths[:, :1]).any(1).nonzero()[0, 0])
-        raise ValueError(f"out_layout 1 needs the segments of every clip to have equal lengths (clip {b}: {lengths[b].tolist()})")
+    _check_out_layout(lengths, B, out_layout)
     if len(proj) != 2 * len(spec.segments):
         raise ValueError("ragged training on the wide path: every segment needs a projection")
     lib = _lib.load()
@@ -1152,22 +1133,23 @@ def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor]
     if (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
             lib.egx_ragged_encode_train_workspace(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0:
         # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged wide path does not cover
-        return _encoder_tokens_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, out_layout)
+        return _encoder_tokens_grouped(dataclasses.replace(spec, wcache=None), feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
+                                       layer_params, out_layout)
     feats = [f.detach() for f in feats]      # (frozen backbone features: no gradient path on the wide projections)
     return RaggedWideEncoderFn.apply(spec, lengths, int(out_layout), task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params)
 
 
-def _encoder_tokens_train_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
-    """encoder_ragged_tokens_train where the ragged kernels do not run: one differentiable batched forward per group of clips with the same
-    length tuple, on those clips' unpadded frames; the rows put in their place (autograd flows through the gather and the reordering)."""
+def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
+    """encoder_ragged_tokens(_train) where the ragged wide path does not run (compute other than bf16, a forced implementation, a clip beyond
+    the wide attention): one batched forward per group of clips with the same length tuple, on those clips' unpadded frames; the rows put in
+    their place (autograd flows through the gather and the reordering, unless the caller runs under no_grad)."""
     d = spec.d_model
     device = feats[0].device
     rows = ragged_token_rows(lengths, out_layout)
     S = lengths.to(torch.int64).sum(1)
     tok0 = torch.cumsum(S, 0) - S
     parts, dst = [], []
-    gspec0 = dataclasses.replace(spec, wcache=None)
-    for idx, _, gspec, fs in _length_groups(gspec0, feats, lengths):
+    for idx, _, gspec, fs in _length_groups(spec, feats, lengths):
         r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
         parts.append(r.reshape(-1, d))
         dst.append(rows[(tok0[idx][:, None] + torch.arange(r.shape[1])[None, :]).reshape(-1)])
@@ -1194,29 +1176,49 @@ def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, lay
     """Inference decode (no autograd) over a packed ragged memory: tokens (B, sy) int64, memory (sum_b S_b, d) with S_b = mem_lengths[b]
     ((B,) int32 host tensor); clip b cross-attends to its own rows only. meta as DecoderFn's (p_drop / p_pos ignored: inference).
     Returns logits (B * sy, |V|) (egx_decoder_ragged_fwd)."""
+    with torch.no_grad():
+        return _decoder_ragged_fwd(None, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b)
+
+
+def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b):
+    """The forward of decoder_ragged (ctx None: egx_decoder_ragged_fwd in one shared workspace) and of RaggedDecoderFn
+    (egx_decoder_ragged_train_fwd into a `saved` of the call's own, kept in ctx for the backward)."""
     lib = _lib.load()
     n_layers = meta["n_layers"]
-    with torch.no_grad():
-        layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
-        fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
-        memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
-        if tokens.dtype != torch.int64 or not tokens.is_cuda:
-            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
-        tokens = tokens.contiguous()
-        B, sy = tokens.shape
-        d = emb.shape[1]
-        ml = mem_lengths.contiguous()
-        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16, 0.0, 0.0, None)
+    layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
+    fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
+    memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+    if tokens.dtype != torch.int64 or not tokens.is_cuda:
+        raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
+    tokens = tokens.contiguous()
+    B, sy = tokens.shape
+    d = emb.shape[1]
+    ml = mem_lengths.contiguous()
+    drop = (meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None) if ctx is not None else (0.0, 0.0, None)
+    cfg_args = (d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16, *drop)
+    cfg = _lib.DecConfig(*cfg_args)
+    layers = (_lib.DecLayer * n_layers)()
+    for l in range(n_layers):
+        for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+            setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+    logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
+    args = (C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, ptr(logits))
+    if ctx is None:
         nb = C.c_size_t(0)
         check(lib.egx_decoder_ragged_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(nb)))
-        ws = _workspace("dec_ragged", memory.device, nb.value)
-        layers = (_lib.DecLayer * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-        logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
-        check(lib.egx_decoder_ragged_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers,
-                                         ptr(fc_w), ptr(fc_b), B, ptr(logits), ptr(ws), _stream()))
+        check(lib.egx_decoder_ragged_fwd(*args, ptr(_workspace("dec_ragged", memory.device, nb.value)), _stream()))
+    else:
+        sv, sc = C.c_size_t(0), C.c_size_t(0)
+        check(lib.egx_decoder_ragged_train_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(sv), C.byref(sc)))
+        need_grad = any(ctx.needs_input_grad)
+        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=memory.device) if need_grad else _workspace("dec_saved", memory.device, sv.value)
+        if need_grad and _POISON:
+            saved.fill_(255)
+        scratch = _workspace("dec_scratch", memory.device, sc.value)
+        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
+        check(lib.egx_decoder_ragged_train_fwd(*args, ptr(saved), ptr(scratch), int(meta["training"]), seed, _stream()))
+        ctx.meta, ctx.cfg_args, ctx.B, ctx.ml, ctx.saved_buf, ctx.scratch_bytes = meta, cfg_args, B, ml, saved, sc.value
+        ctx.save_for_backward(tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
     _last_dec_impl[0] = "ragged"
     return logits
 
@@ -1627,39 +1629,8 @@ class RaggedDecoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, tokens, memory, mem_lengths, emb, pe, *rest):
-        lib = _lib.load()
-        n_layers = meta["n_layers"]
-        layer_t = [_dev_f32(t, "decoder layer parameter") for t in rest[:18 * n_layers]]
-        fc_w, fc_b = _dev_f32(rest[18 * n_layers], "fc.weight"), _dev_f32(rest[18 * n_layers + 1], "fc.bias")
-        memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
-        if tokens.dtype != torch.int64 or not tokens.is_cuda:
-            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
-        tokens = tokens.contiguous()
-        B, sy = tokens.shape
-        d = emb.shape[1]
-        ml = mem_lengths.contiguous()
-        cfg_args = (d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16,
-                    meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None)
-        cfg = _lib.DecConfig(*cfg_args)
-        sv, sc = C.c_size_t(0), C.c_size_t(0)
-        check(lib.egx_decoder_ragged_train_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(sv), C.byref(sc)))
-        need_grad = any(ctx.needs_input_grad)
-        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=memory.device) if need_grad else _workspace("dec_saved", memory.device, sv.value)
-        if need_grad and _POISON:
-            saved.fill_(255)
-        scratch = _workspace("dec_scratch", memory.device, sc.value)
-        layers = (_lib.DecLayer * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-        logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
-        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
-        check(lib.egx_decoder_ragged_train_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers,
-                                               ptr(fc_w), ptr(fc_b), B, ptr(logits), ptr(saved), ptr(scratch), int(meta["training"]), seed, _stream()))
-        _last_dec_impl[0] = "ragged"
-        ctx.meta, ctx.cfg_args, ctx.B, ctx.ml, ctx.saved_buf, ctx.scratch_bytes = meta, cfg_args, B, ml, saved, sc.value
-        ctx.save_for_backward(tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
-        return logits
+        n = 18 * meta["n_layers"]
+        return _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, rest[:n], rest[n], rest[n + 1])
 
     @staticmethod
     def backward(ctx, d_logits):

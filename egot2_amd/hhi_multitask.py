@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from .backbones import freeze_params, make_backbone
 from . import functional as F_egx
-from .functional import EncoderSpec, SegmentSpec
+from .functional import SegmentSpec
 from .decoder import DecoderMixin
 from .translator import PositionalEncoding, TranslatorMixin, encoder_layer_tensors
 
@@ -86,13 +86,10 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         frame counts in argument order (K = 1 for 'lam', else 3); padded frames are never read. Returns the packed memory of every clip,
         (sum_b S_b, d) with S_b = sum_k T_{b,k}, for 'ttm' / 'lam' (decode(..., memory_lengths=S_b)), and the reference's (3, sum_b T_b, d)
         for 'asd' (equal segment lengths per clip), a view of one frame-major buffer that decode() reads without a copy."""
-        if task == 'lam':
-            feats, projs, ids = [lam_feat], [self.proj_lam], [0]
-        else:
-            feats, projs, ids = [lam_feat, ttm_feat, asd_feat], [self.proj_lam, self.proj_ttm, self.proj_asd], [0, 1, 2]
-        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, ids)]
         if lengths is not None:
-            return self._encode_features_ragged(task, feats, segs, projs, lengths)
+            self._egx_check_inference("lengths=")
+            return self._encode_ragged(task, lam_feat, ttm_feat, asd_feat, lengths, train=False)
+        feats, segs, projs = self._encoder_segments(task, lam_feat, ttm_feat, asd_feat)
         x = self._egx_encode(feats, segs, encoder=self.transformer_encoder, ln=self.ln, projs=projs,
                              task_embed=self.task_embed, pos_table=self.pos_embed.pe,
                              p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p)   # (B, S, d)
@@ -102,19 +99,45 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
                                 x[:, 2 * T:3 * T].reshape(-1, self.dim)), dim=0)
         return x.permute(1, 0, 2)
 
-    def _encode_features_ragged(self, task, feats, segs, projs, lengths):
-        self._egx_check_inference("lengths=")
-        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segs])
+    def _encoder_segments(self, task, lam_feat, ttm_feat, asd_feat):
+        """The features, their SegmentSpecs and projections of an encoder call of `task`."""
+        if task == 'lam':
+            feats, projs, ids = [lam_feat], [self.proj_lam], [0]
+        else:
+            feats, projs, ids = [lam_feat, ttm_feat, asd_feat], [self.proj_lam, self.proj_ttm, self.proj_asd], [0, 1, 2]
+        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, ids)]
+        return feats, segs, projs
+
+    @staticmethod
+    def _ragged_lengths(task, feats, lengths):
+        """The (B, K) host lengths of a ragged batch of `task` (functional.ragged_lengths); 'asd' needs equal segment lengths in every clip."""
+        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [f.shape[1] for f in feats])
         if task == 'asd' and not bool((lens == lens[:, :1]).all()):
             b = int((lens != lens[:, :1]).any(1).nonzero()[0, 0])
             raise ValueError(f"task 'asd' needs lam, ttm and asd features of equal length in every clip (clip {b}: {lens[b].tolist()})")
-        layer0 = self.transformer_encoder.layers[0]
-        spec = EncoderSpec(d_model=self.dim, n_heads=layer0.self_attn.num_heads, d_ff=layer0.linear1.out_features,
-                           n_layers=len(self.transformer_encoder.layers), segments=segs, ln_eps=self.ln.eps, compute=self.egx_compute,
-                           impl=self.egx_impl)
-        proj_t = [t for p in projs for t in (p.weight, p.bias)]
-        x = F_egx.encoder_ragged_tokens(spec, feats, lens, self.task_embed, self.pos_embed.pe, self.ln.weight, self.ln.bias, proj_t,
-                                        encoder_layer_tensors(self.transformer_encoder), out_layout=1 if task == 'asd' else 0)
+        return lens
+
+    def _encode_ragged(self, task, lam_feat, ttm_feat, asd_feat, lengths, *, train: bool):
+        """encode_features(..., lengths=) (train False: functional.encoder_ragged_tokens) and encode_features_ragged (train True:
+        functional.encoder_ragged_tokens_train). The lengths are checked (host work) before any device work."""
+        feats, segs, projs = self._encoder_segments(task, lam_feat, ttm_feat, asd_feat)
+        lens = self._ragged_lengths(task, feats, lengths)
+        if train:
+            if self.egx_defer_small:
+                raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
+            seed_dev = getattr(self, "_egx_seed_dev", None)
+            training = bool(self.training)
+            spec, proj_t, _ = self._egx_spec(segs, self.transformer_encoder, self.ln, projs, None,
+                                             p_drop=self.dp_rate if training else 0.0, p_pos=self.pos_embed.dropout.p if training else 0.0,
+                                             training=training, seed=self._egx_seed() if training else 0,
+                                             seed_ptr=seed_dev.data_ptr() if (seed_dev is not None and training) else 0,
+                                             advance_seed=1 if (seed_dev is not None and training) else 0)      # fresh masks per call
+            encode = F_egx.encoder_ragged_tokens_train
+        else:
+            spec, proj_t, _ = self._egx_spec(segs, self.transformer_encoder, self.ln, projs, None)
+            encode = F_egx.encoder_ragged_tokens
+        x = encode(spec, feats, lens, self.task_embed, self.pos_embed.pe, self.ln.weight, self.ln.bias, proj_t,
+                   encoder_layer_tensors(self.transformer_encoder), out_layout=1 if task == 'asd' else 0)
         if task == 'asd':
             return x.view(-1, 3, self.dim).permute(1, 0, 2)        # (3, sum_b T_b, d): row 3 f + k of x is segment k of frame f
         return x
@@ -129,29 +152,7 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         configurations it does not cover run one differentiable uniform call per length group ("grouped", other dropout masks). In eval mode the
         result equals encode_features(..., lengths=) bit for bit."""
         assert task in ['lam', 'ttm', 'asd']
-        if task == 'lam':
-            feats, projs, ids = [lam_feat], [self.proj_lam], [0]
-        else:
-            feats, projs, ids = [lam_feat, ttm_feat, asd_feat], [self.proj_lam, self.proj_ttm, self.proj_asd], [0, 1, 2]
-        segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, ids)]
-        lens = F_egx.ragged_lengths(lengths, feats[0].shape[0], [s.T for s in segs])       # (host work: before any device work)
-        if task == 'asd' and not bool((lens == lens[:, :1]).all()):
-            b = int((lens != lens[:, :1]).any(1).nonzero()[0, 0])
-            raise ValueError(f"task 'asd' needs lam, ttm and asd features of equal length in every clip (clip {b}: {lens[b].tolist()})")
-        if self.egx_defer_small:
-            raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
-        seed_dev = getattr(self, "_egx_seed_dev", None)
-        training = bool(self.training)
-        spec, proj_t, _ = self._egx_spec(segs, self.transformer_encoder, self.ln, projs, None,
-                                         p_drop=self.dp_rate if training else 0.0, p_pos=self.pos_embed.dropout.p if training else 0.0,
-                                         training=training, seed=self._egx_seed() if training else 0,
-                                         seed_ptr=seed_dev.data_ptr() if (seed_dev is not None and training) else 0,
-                                         advance_seed=1 if (seed_dev is not None and training) else 0)      # fresh masks per call
-        x = F_egx.encoder_ragged_tokens_train(spec, feats, lens, self.task_embed, self.pos_embed.pe, self.ln.weight, self.ln.bias, proj_t,
-                                              encoder_layer_tensors(self.transformer_encoder), out_layout=1 if task == 'asd' else 0)
-        if task == 'asd':
-            return x.view(-1, 3, self.dim).permute(1, 0, 2)        # (3, sum_b T_b, d): row 3 f + k of x is segment k of frame f
-        return x
+        return self._encode_ragged(task, lam_feat, ttm_feat, asd_feat, lengths, train=True)
 
     def decode_ragged(self, y, memory, memory_lengths):
         """decode(..., memory_lengths=) for TRAINING (train and eval mode, under autograd): (B, sy) tokens + the packed (sum_b S_b, d) memory of
@@ -168,8 +169,7 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         encoded_x = self.encode_features_ragged(task, lam_feat, ttm_feat, asd_feat, lengths=lengths)
         if task == 'asd':
             return self.decode(target, encoded_x).permute(1, 2, 0)
-        feats = [lam_feat] if task == 'lam' else [lam_feat, ttm_feat, asd_feat]
-        S = F_egx.ragged_lengths(lengths, lam_feat.shape[0], [f.shape[1] for f in feats]).sum(1)
+        S = self._ragged_lengths(task, self._encoder_segments(task, lam_feat, ttm_feat, asd_feat)[0], lengths).sum(1)
         return self.decode_ragged(target, encoded_x, S).permute(1, 2, 0)
 
     def encode(self, video, video_asd, audio, audio_asd, task):
@@ -229,8 +229,7 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
             y = torch.full((lam_feat.shape[0], 1), self.vocab[task], dtype=torch.long, device=dev)
             output = self.decode(y, encoded_x)
         else:
-            S = F_egx.ragged_lengths(lengths, lam_feat.shape[0], [f.shape[1] for f in ([lam_feat] if task == 'lam' else
-                                                                                         [lam_feat, ttm_feat, asd_feat])]).sum(1)
+            S = self._ragged_lengths(task, self._encoder_segments(task, lam_feat, ttm_feat, asd_feat)[0], lengths).sum(1)
             y = torch.full((lam_feat.shape[0], 1), self.vocab[task], dtype=torch.long, device=dev)
             output = self.decode(y, encoded_x, memory_lengths=S)
         return output[0, :, -2:]

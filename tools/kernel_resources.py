@@ -11,7 +11,7 @@ for line in r.stderr.splitlines():
     t = m.group(1).strip()
     if t.startswith("Function Name:"):
         cur = subprocess.run(["c++filt", t.split(":", 1)[1].strip()], capture_output=True, text=True).stdout.strip()
-        cur = re.sub(r"\(.*", "", cur); rows[cur] = {}
+        cur = re.sub(r"\(.*", "", cur.replace("(anonymous namespace)::", "").replace("egx::", "")); rows[cur] = {}
     elif cur and ":" in t:
         k, v = t.split(":", 1); rows[cur][k.strip()] = v.strip()
 for k, v in rows.items():
