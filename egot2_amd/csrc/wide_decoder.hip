@@ -1495,3 +1495,355 @@ int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, con
 }
 
 }  // extern "C"
+
+// ---- greedy generation with a K/V cache (egx_decoder_generate) ----
+// The inference loop of the EgoT2-g sequence models (predict_ac, HOI/models/multitask/video_model_builder.py:201-220, 263-274; the 40-step
+// verb / noun loop of HOI/models/lta/lta_models_seqdecoder.py:181-201) as ONE call: weights and memory to bf16 once, the memory's K | V
+// projected once per layer, then per step ONE new target row per clip through the layers (self-attention over a per-layer K/V cache), the
+// fp32 vocabulary head, the argmax and the next token's embedding on the device. Arithmetic as decoder_fwd_run, choice for choice.
+namespace {
+
+struct GenAttnParams {
+    const void* qkv;        // (B, 3d): the new row's q | k | v (fp32 or bf16)
+    void* cache;            // (B, n_steps, 2d): k | v of rows 0 .. t - 1; row t is appended
+    bf16_t* o;              // (B, d)
+    int B, H, d, t, n_steps;
+    float scale;
+};
+
+// One wave per (clip, head), four per workgroup. Lane j holds key row j (j < t from the cache, j == t the new row); the query goes through a
+// per-wave LDS slice as broadcast reads; lane c accumulates column c of the output. Sums run in dec_attn_kernel's order, so a step sees the
+// scores and the output a causal decode() of the same rows computes. t < 64 = one key per lane.
+template <int DH, bool F32>
+__global__ __launch_bounds__(256) void gen_self_attn_kernel(GenAttnParams p) {
+    __shared__ __align__(16) float sQ[4][DH];   // (read as float4)
+    __shared__ float sP[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bh = blockIdx.x * 4 + wave;
+    if (bh >= p.B * p.H) return;                // (no barrier below: every wave works alone)
+    const int b = bh / p.H, h = bh % p.H, t = p.t, d = p.d;
+    const size_t nrow = (size_t)b * 3 * d + h * DH;                         // q; k at + d, v at + 2d
+    const size_t crow = (size_t)b * p.n_steps * 2 * d + h * DH;             // cache row j at + j * 2d: k; v at + d
+    float kr[DH];
+    {
+        const bool cached = lane < t;
+        const void* kb = cached ? (const void*)p.cache : p.qkv;
+        const size_t krow = cached ? crow + (size_t)lane * 2 * d : nrow + d;
+#pragma unroll
+        for (int c = 0; c < DH; c += 8) {
+            float t8[8];
+            load8<F32>(kb, krow + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
+        }
+    }
+    float vnew = 0.f;
+    if (lane < DH) {                            // append row t (read by later steps only)
+        const float knew = load1<F32>(p.qkv, nrow + d + lane);
+        vnew = load1<F32>(p.qkv, nrow + 2 * d + lane);
+        store1<F32>(p.cache, crow + (size_t)t * 2 * d + lane, knew);
+        store1<F32>(p.cache, crow + (size_t)t * 2 * d + d + lane, vnew);
+        sQ[wave][lane] = load1<F32>(p.qkv, nrow + lane);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const bool live = lane <= t;
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < DH; c += 4) {
+        const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][c]);
+        s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
+    }
+    s = live ? s * p.scale : -INFINITY;
+    const float m = wmax64(s);
+    const float e = live ? __expf(s - m) : 0.f;
+    sP[wave][lane] = e / wsum64d(e);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < DH) {
+        float acc = 0.f;
+        const size_t v0 = crow + d + lane;
+        for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + (size_t)j * 2 * d);
+        acc += sP[wave][t] * vnew;
+        p.o[(size_t)b * d + h * DH + lane] = f2bf(acc);
+    }
+}
+
+int gen_self_attn(GenAttnParams p, int dh, bool f32, hipStream_t st) {
+    EGX_CHECK(p.t >= 0 && p.t < p.n_steps && p.n_steps <= 64, "cached self-attention: step %d of %d (at most 64)", p.t, p.n_steps);
+    p.scale = 1.f / sqrtf((float)dh);
+    const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
+    if (dh == 64 && !f32) hipLaunchKernelGGL((gen_self_attn_kernel<64, false>), grid, block, 0, st, p);
+    else if (dh == 32 && !f32) hipLaunchKernelGGL((gen_self_attn_kernel<32, false>), grid, block, 0, st, p);
+    else if (dh == 64) hipLaunchKernelGGL((gen_self_attn_kernel<64, true>), grid, block, 0, st, p);
+    else if (dh == 32) hipLaunchKernelGGL((gen_self_attn_kernel<32, true>), grid, block, 0, st, p);
+    else EGX_CHECK(false, "cached self-attention: head dim %d (32 or 64)", dh);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+// The greedy head of one step: logits = x fc_w^T + fc_b in fp32 for GH_CLIPS clips per workgroup (fc_w streams once per workgroup; GH_WAVES
+// waves, each with GH_ROWS vocabulary rows in flight per pass; the clips' rows in LDS), then one wave per clip: argmax (lowest index on ties; a NaN never wins), the token to tokens_out,
+// the logits to logits_out when given, and the next step's input row emb[tok] * scale + pe_next as fp32 and bf16 (dec_embed_kernel's
+// expression). pe_next null: the last step.
+constexpr int GH_CLIPS = 4, GH_WAVES = 8, GH_ROWS = 4, GEN_MAX_STEPS = 64, GEN_MAX_VOCAB = 1024;
+struct GenHeadParams {
+    const float* x; const float* fc_w; const float* fc_b; const float* emb; const float* pe_next;
+    int64_t* tok; int tok_stride;               // clip b's token of this step at tok[b * tok_stride]
+    float* logits;                              // (B, V) rows of this step, or null
+    float* x32; bf16_t* x16;                    // (B, d): next step's input rows
+    int B, d, V;
+    float scale;
+};
+__global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p) {
+    extern __shared__ __align__(16) float gh_sm[];
+    float* sx = gh_sm;                          // [GH_CLIPS][d]
+    float* sl = gh_sm + GH_CLIPS * p.d;         // [GH_CLIPS][V]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = p.d, V = p.V;
+    const int b0 = blockIdx.x * GH_CLIPS, nb = p.B - b0 < GH_CLIPS ? p.B - b0 : GH_CLIPS;
+    for (int i = tid * 4; i < GH_CLIPS * d; i += 256 * GH_WAVES) {
+        const int r = i / d;
+        float4 v = make_float4(0, 0, 0, 0);
+        if (r < nb) v = *reinterpret_cast<const float4*>(p.x + (size_t)b0 * d + i);
+        *reinterpret_cast<float4*>(sx + i) = v;
+    }
+    __syncthreads();
+    // GH_ROWS vocabulary rows per wave and pass: their fc_w loads and wave reductions are independent and overlap (one row at a time the loop
+    // is a chain of load and shuffle latencies: 206 us per launch at V = 600, d = 512)
+    for (int v0 = wave; v0 < V; v0 += GH_WAVES * GH_ROWS) {
+        float a[GH_ROWS][GH_CLIPS];
+#pragma unroll
+        for (int u = 0; u < GH_ROWS; ++u)
+#pragma unroll
+            for (int r = 0; r < GH_CLIPS; ++r) a[u][r] = 0.f;
+        for (int c = lane * 4; c < d; c += 256) {
+            float4 w[GH_ROWS];
+#pragma unroll
+            for (int u = 0; u < GH_ROWS; ++u) {
+                const int v = v0 + u * GH_WAVES < V ? v0 + u * GH_WAVES : v0;       // (a row past the end re-reads row v0; its sums are dropped)
+                w[u] = *reinterpret_cast<const float4*>(p.fc_w + (size_t)v * d + c);
+            }
+#pragma unroll
+            for (int r = 0; r < GH_CLIPS; ++r) {
+                const float4 xv = *reinterpret_cast<const float4*>(sx + r * d + c);
+                // one explicit fma chain per (row, clip): left to the compiler's contraction (and its packed fp32 pairs) the clips of a
+                // workgroup rounded differently by their slot, and permuting a batch moved logits by an ulp
+#pragma unroll
+                for (int u = 0; u < GH_ROWS; ++u)
+                    a[u][r] = fmaf(w[u].w, xv.w, fmaf(w[u].z, xv.z, fmaf(w[u].y, xv.y, fmaf(w[u].x, xv.x, a[u][r]))));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GH_ROWS; ++u) {
+            const int v = v0 + u * GH_WAVES;
+            const float bias = p.fc_b && v < V ? p.fc_b[v] : 0.f;
+#pragma unroll
+            for (int r = 0; r < GH_CLIPS; ++r) {
+                const float sum = wsum64d(a[u][r]);
+                if (lane == 0 && v < V) sl[r * V + v] = sum + bias;
+            }
+        }
+    }
+    __syncthreads();
+    if (wave >= nb) return;
+    const int b = b0 + wave;
+    const float* row = sl + wave * V;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) {        // ascending within a lane: `>` keeps the lowest index
+        float x = row[v];
+        if (!(x == x)) x = -INFINITY;
+        if (x > best || idx == 0x7fffffff) { best = x; idx = v; }
+        if (p.logits) p.logits[(size_t)b * V + v] = row[v];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+    }
+    if (lane == 0) p.tok[(size_t)b * p.tok_stride] = (int64_t)idx;
+    if (p.pe_next) {
+        const float scale = p.scale;
+        for (int c = lane * 4; c < d; c += 256) {
+            const float4 e = *reinterpret_cast<const float4*>(p.emb + (size_t)idx * d + c);
+            const float4 pp = *reinterpret_cast<const float4*>(p.pe_next + c);
+            float o[4] = {e.x * scale + pp.x, e.y * scale + pp.y, e.z * scale + pp.z, e.w * scale + pp.w};
+            *reinterpret_cast<float4*>(p.x32 + (size_t)b * d + c) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<uint2*>(p.x16 + (size_t)b * d + c) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+        }
+    }
+}
+
+struct GLayer { size_t w_sa_in, w_sa_o, w_q, w_kv, w_ca_o, w1, w2, kv, cache; };
+struct GPlan {
+    int B, n, S, d, H, dff, L, V;
+    size_t Nm;
+    size_t zero, mem16, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
+    GLayer layer[16];
+    size_t bytes;
+};
+
+int make_gplan(const egx_dec_config* c, int B, int n_steps, GPlan& pl) {
+    EGX_CHECK(c, "null decoder config");
+    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_generate: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
+    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_generate: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
+    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_generate: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
+    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits (cfg->sy is not read)
+        egx_dec_config one = *c;
+        one.sy = 1;
+        DPlan dp;
+        if (make_dplan(&one, B, dp)) return 1;
+    }
+    memset(&pl, 0, sizeof(pl));
+    pl.B = B; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
+    pl.Nm = (size_t)B * c->S;
+    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = (size_t)B;
+    size_t cur = 0;
+    pl.zero = dtake(cur, 1024);
+    pl.mem16 = dtake(cur, Nm * d * 2);
+    for (int l = 0; l < pl.L; ++l) {
+        GLayer& o = pl.layer[l];
+        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
+        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
+        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
+        o.kv = dtake(cur, Nm * 2 * d * 2);
+        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
+    }
+    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
+    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
+    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 8);
+    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
+    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
+    pl.xL32 = dtake(cur, M * d * 4);
+    pl.bytes = cur;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps, size_t* bytes) {
+    GPlan pl;
+    if (make_gplan(cfg, B, n_steps, pl)) return 1;
+    if (bytes) *bytes = pl.bytes;
+    return 0;
+}
+
+int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                         const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
+                         float* logits_out, void* workspace, void* stream) {
+    GPlan pl;
+    if (make_gplan(cfg, B, n_steps, pl)) return 1;
+    EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && workspace, "egx_decoder_generate: null pointer argument");
+    EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_generate: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, dh = d / pl.H;
+    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
+    const void* zero = at<char>(ws, pl.zero);
+    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
+    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
+    {   // every weight -> bf16 once (no transposed copies: nothing runs backward), one launch
+        WideCastBatch cb;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
+        }
+        if (wide_cast_flush(cb, st)) return 1;
+    }
+    // step 0's input rows: emb[start] * sqrt(d) + pe[0]
+    hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)(((size_t)B * (d / 4) + 255) / 256)), dim3(256), 0, st, start, emb, pe, pe_stride,
+                       sqrtf((float)d), at<float>(ws, pl.x32), at<bf16_t>(ws, pl.x16), B, 1, d, pl.V, (uint64_t)0, (uint32_t)0, 1.f);
+    EGX_LAUNCH_CHECK();
+    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
+                     const float* residual) -> int {
+        WideGemmParams g;
+        g.A = A; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
+        g.residual = residual; g.ldr = N; g.zero_page = zero;
+        return wide_gemm_nt(g, s_);
+    };
+    auto nt = [&](const bf16_t* A, int lda, const bf16_t* W, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
+                  const float* residual) -> int { return nt_on(st, A, lda, W, B, N, K, bias, Cf, Cb, relu, residual); };
+    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
+        WideLnFwdParams lp;
+        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = B; lp.d = d;
+        return wide_ln_fwd(lp, st);
+    };
+    // the memory's K | V, once per layer: on the side stream beside step 0 (eager), on the caller's stream under capture
+    SideStream& SS = side_stream();
+    SideJoin sj(SS, st);
+    const bool side = side_wanted(SS, st);
+    if (side) {
+        if (SS.order(st, SS.s)) return 1;
+        sj.forked = true;
+    }
+    for (int l = 0; l < pl.L; ++l) {
+        const GLayer& o = pl.layer[l];
+        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
+        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
+    }
+    float* x32 = at<float>(ws, pl.x32);
+    bf16_t* x16 = at<bf16_t>(ws, pl.x16);
+    for (int t = 0; t < n_steps; ++t) {
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            const bool last = l + 1 == pl.L;
+            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
+            if (f32_self) {
+                GemmParams g;
+                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = B; g.N = 3 * d; g.K = d;
+                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
+                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
+            } else if (nt(x16, d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
+            {
+                GenAttnParams a;
+                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
+                a.cache = at<char>(ws, o.cache); a.o = at<bf16_t>(ws, pl.sa);
+                a.B = B; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
+                if (gen_self_attn(a, dh, f32_self, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
+            // cross-attention of the one new row onto the clip's S memory rows
+            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
+            if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
+            {
+                DecAttnParams a;
+                memset(&a, 0, sizeof(a));
+                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
+                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
+                a.B = B; a.H = pl.H; a.Sq = 1; a.Sk = pl.S; a.causal = 0;
+                if (dec_attn<false>(a, dh, false, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
+            // FFN
+            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
+            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? at<float>(ws, pl.xL32) : x32, last ? nullptr : x16)) return 1;
+        }
+        GenHeadParams hp;
+        hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.emb = emb;
+        hp.pe_next = t + 1 < n_steps ? pe + (size_t)(t + 1) * pe_stride : nullptr;
+        hp.tok = tokens_out + t; hp.tok_stride = n_steps;
+        hp.logits = logits_out ? logits_out + (size_t)t * B * pl.V : nullptr;
+        hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.d = d; hp.V = pl.V; hp.scale = sqrtf((float)d);
+        hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
+        EGX_LAUNCH_CHECK();
+    }
+    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    return 0;
+}
+
+}  // extern "C"

@@ -139,3 +139,76 @@ class DecoderMixin:
         out = torch.cat(parts, 1).index_select(1, inv.to(parts[0].device))
         F_egx._last_dec_impl[0] = "grouped"
         return out
+
+    def _egx_greedy(self, start: torch.Tensor, encoded_x: torch.Tensor, n_steps: int, *, embedding: nn.Embedding, pos_embed,
+                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False):
+        """Greedy generation (inference only), the loop of predict_ac (HOI/models/multitask/video_model_builder.py:201-220, 263-274) and of
+        HOI/models/lta/lta_models_seqdecoder.py:181-201: start (B,) int64 tokens, encoded_x (S, B, d) memory -> tokens (B, n_steps) int64 (the
+        n_steps tokens after `start`) and, with return_logits, each step's last-row logits (n_steps, B, |V|). Ties go to the lowest index.
+        One egx_decoder_generate call where it serves the configuration (last_decoder_impl() == "generate": K/V cache, argmax on the
+        device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first."""
+        self._egx_check_inference("it to greedy_decode", subject="greedy generation is")
+        if not isinstance(n_steps, int) or isinstance(n_steps, bool) or n_steps < 1:
+            raise ValueError(f"n_steps must be a positive int, got {n_steps!r}")
+        if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
+            raise ValueError("encoded_x must be the (S, B, d) decoder memory")
+        S, B, d = encoded_x.shape
+        if not isinstance(start, torch.Tensor) or start.dim() != 1 or start.shape[0] != B:
+            raise ValueError(f"start must be a ({B},) tensor, one start token per clip of the memory: got "
+                             f"{tuple(start.shape) if isinstance(start, torch.Tensor) else type(start).__name__}")
+        if start.dtype != torch.int64:
+            raise ValueError(f"start must be int64 tokens, got {start.dtype}")
+        if n_steps > pos_embed.pe.shape[0]:
+            raise ValueError(f"n_steps = {n_steps} exceeds the {pos_embed.pe.shape[0]} rows of the positional table")
+        if d != embedding.weight.shape[1]:
+            raise ValueError(f"memory width {d} != embedding width {embedding.weight.shape[1]}")
+        if not (encoded_x.is_cuda and start.is_cuda and embedding.weight.is_cuda):
+            raise ValueError("greedy generation runs on the GPU only (no CPU fallback): memory, start tokens and the model must be on the GPU")
+        V = embedding.weight.shape[0]
+        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
+        if (post_ln and not getattr(self, "egx_composed_decoder", False)
+                and F_egx.decoder_generate_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, S,
+                                                     len(decoder.layers), V, n_steps)):
+            meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, 0.0)
+            mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
+            return F_egx.decoder_generate(meta, start, mem2d, embedding.weight, pos_embed.pe[:n_steps, 0, :], params, fc.weight, fc.bias,
+                                          n_steps, return_logits)
+        # the reference's prefix loop: one decode() per step over the growing prefix
+        if n_steps > 8:
+            raise ValueError(f"n_steps = {n_steps}: this configuration is outside egx_decoder_generate (compute bf16, vocabulary <= 1024, "
+                             "n_steps <= 64, the fused decoder's shapes) and the prefix loop runs decode(), which serves at most 8 target tokens")
+        with torch.no_grad():
+            toks = torch.empty((B, n_steps + 1), dtype=torch.int64, device=start.device)
+            toks[:, 0] = start
+            rows = []
+            for t in range(n_steps):
+                last = self._egx_decode(toks[:, :t + 1], encoded_x, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
+                                        n_heads=n_heads, p_drop=0.0)[-1]
+                toks[:, t + 1] = _argmax_lowest(last)
+                if return_logits:
+                    rows.append(last)
+        F_egx._last_dec_impl[0] = "loop"
+        return toks[:, 1:].contiguous(), (torch.stack(rows, 0).contiguous() if return_logits else None)
+
+    def greedy_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, return_logits: bool = False):
+        """Greedy generation from the (S, B, d) decoder memory: `start_token` an int or a (B,) int64 tensor; returns tokens (B, n_steps) and,
+        with return_logits, (tokens, logits (n_steps, B, |V|)). The 40-step verb / noun schedule of lta_models_seqdecoder.py:186-201 is two
+        index operations on the result. Eval mode only; see _egx_greedy."""
+        if isinstance(start_token, torch.Tensor):
+            start = start_token
+        else:
+            if not isinstance(start_token, int) or isinstance(start_token, bool):
+                raise ValueError(f"start_token must be an int or a (B,) int64 tensor, got {type(start_token).__name__}")
+            if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
+                raise ValueError("encoded_x must be the (S, B, d) decoder memory")
+            start = torch.full((encoded_x.shape[1],), start_token, dtype=torch.int64, device=encoded_x.device)
+        tokens, logits = self._egx_greedy(start, encoded_x, n_steps, embedding=self.embedding, pos_embed=self.pos_embed,
+                                          decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits)
+        return (tokens, logits) if return_logits else tokens
+
+
+def _argmax_lowest(logits: torch.Tensor) -> torch.Tensor:
+    """Row argmax with the lowest index on ties (torch.argmax leaves ties open)."""
+    V = logits.shape[-1]
+    idx = torch.arange(V, device=logits.device).expand_as(logits)
+    return torch.where(logits == logits.max(dim=-1, keepdim=True).values, idx, V).min(dim=-1).values

@@ -1167,8 +1167,8 @@ _last_dec_impl = ["none"]
 
 def last_decoder_impl() -> str:
     """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
-    operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd) or "grouped" (a ragged memory decoded one length group at a
-    time)."""
+    operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd), "grouped" (a ragged memory decoded one length group at a
+    time), "generate" (greedy generation in one egx_decoder_generate call) or "loop" (greedy generation as a prefix loop over decode())."""
     return _last_dec_impl[0]
 
 
@@ -1675,6 +1675,44 @@ def decoder_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S:
     """Shapes egx_decoder_fwd / egx_decoder_bwd serve (include/egot2x.h); everything else stays on the composed decoder."""
     return (compute == "bf16" and 256 <= d <= 1024 and d % 128 == 0 and n_heads > 0 and d % n_heads == 0 and d // n_heads in (32, 64)
             and d_ff >= 128 and d_ff % 128 == 0 and 1 <= sy <= 8 and 1 <= S <= 1024 and 1 <= n_layers <= 16)
+
+
+def decoder_generate_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int) -> bool:
+    """Configurations egx_decoder_generate serves (include/egot2x.h): the fused decoder's limits, n_steps <= 64, vocab <= 1024."""
+    return decoder_supported(compute, d, n_heads, d_ff, 1, S, n_layers) and 1 <= n_steps <= 64 and 1 <= vocab <= 1024
+
+
+def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, return_logits: bool = False):
+    """Greedy generation in ONE asynchronous call (egx_decoder_generate; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory
+    rows, pe (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, n_steps) int64 and, with
+    return_logits, logits (n_steps, B, |V|) fp32 (else None). The workspace comes from the caching allocator: the call can be captured."""
+    lib = _lib.load()
+    n_layers = meta["n_layers"]
+    with torch.no_grad():
+        layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
+        fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
+        mem2d, emb, pe = _dev_f32(mem2d, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+        if start.dtype != torch.int64 or not start.is_cuda or start.dim() != 1:
+            raise _lib.EgxError("decoder_generate: start must be a (B,) int64 tensor on the GPU")
+        start = start.contiguous()
+        B, (V, d) = start.shape[0], emb.shape
+        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
+            raise _lib.EgxError(f"decoder_generate: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
+                                f"d = {d}, n_steps = {n_steps}")
+        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, V, 1, mem2d.shape[0] // B, meta["ln_eps"], EGX_BF16, 0.0, 0.0, None)
+        layers = (_lib.DecLayer * n_layers)()
+        for l in range(n_layers):
+            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+        nb = C.c_size_t(0)
+        check(lib.egx_decoder_generate_workspace(C.byref(cfg), B, n_steps, C.byref(nb)))
+        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=mem2d.device)
+        tokens = torch.empty((B, n_steps), dtype=torch.int64, device=mem2d.device)
+        logits = torch.empty((n_steps, B, V), dtype=torch.float32, device=mem2d.device) if return_logits else None
+        check(lib.egx_decoder_generate(C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
+                                       n_steps, ptr(tokens), ptr(logits), ptr(ws), _stream()))
+    _last_dec_impl[0] = "generate"
+    return tokens, logits
 
 
 def weighted_cross_entropy(logits, target, weight=None):

@@ -136,7 +136,14 @@ class TaskPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin):
         y = (torch.ones((batch_size, 1)) * self.vocab[task]).type_as(video[0]).long()
         return self.decode(y, encoded_x)[0, :]
 
+    # predict_ac runs greedy_decode (ONE egx_decoder_generate call) instead of the prefix loop below when the model is in eval mode AND this
+    # is set. Off by default: on a near-tie of two logits the two paths may pick different tokens (GEMM row counts differ).
+    egx_generate = False
+
     def _greedy(self, encoded_x, like, batch_size, seq_len=3):
+        if self.egx_generate and not self.training:
+            with torch.no_grad():
+                return self.greedy_decode(encoded_x, int(self.vocab['action']), seq_len - 1)
         output_tokens = (torch.ones((batch_size, seq_len))).type_as(like).long()
         output_tokens[:, 0] = self.vocab['action']
         for sy in range(1, seq_len):

@@ -122,12 +122,12 @@ class TranslatorMixin:
         head_t = (head[0].weight, head[0].bias, head[1].weight, head[1].bias) if head is not None else ()
         return spec, proj_t, head_t
 
-    def _egx_check_inference(self, what: str):
-        """Ragged batches are inference-only: eval mode, and no autograd graph over the parameters."""
+    def _egx_check_inference(self, what: str, subject: str = "ragged batches are"):
+        """Inference-only features (ragged batches, greedy generation): eval mode, and no autograd graph over the parameters."""
         if self.training:
-            raise ValueError(f"ragged batches are inference-only: call model.eval() before passing {what}")
+            raise ValueError(f"{subject} inference-only: call model.eval() before passing {what}")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise ValueError("ragged batches are inference-only: run them under torch.no_grad() / torch.inference_mode() "
+            raise ValueError(f"{subject} inference-only: run them under torch.no_grad() / torch.inference_mode() "
                              "(or with every parameter frozen)")
 
     def _egx_encode(self, feats: Sequence[torch.Tensor], segments: List[SegmentSpec], *, encoder: nn.TransformerEncoder,

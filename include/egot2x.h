@@ -592,6 +592,24 @@ int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, con
                            int B, const float* d_logits, const void* saved, void* scratch, float* d_memory, float* d_emb,
                            const egx_dec_layer_grads* grads, float* d_fc_w, float* d_fc_b, void* zero_buf, size_t zero_bytes, int training,
                            uint64_t seed, void* stream);
+/* ---- ABI v18: greedy generation with a K/V cache ----
+ * The inference loop of the EgoT2-g sequence models as ONE asynchronous call: predict_ac (HOI/models/multitask/video_model_builder.py:201-220,
+ * 263-274: start token, then each next token the argmax over a decode() of the growing prefix) and the same loop over 40 steps in
+ * HOI/models/lta/lta_models_seqdecoder.py:181-201. For t = 0 .. n_steps - 1: x_t = emb[tok_t] * sqrt(d) + pe[t] (tok_0 = start[b]) runs through
+ * the post-LN decoder layers, its causal self-attention over rows 0 .. t (a per-layer K/V cache), its cross-attention over the clip's S memory
+ * rows (K | V projected once per layer); logits_t = fc(x_t); tok_{t+1} = argmax(logits_t), the LOWEST index on ties. Dropout is off, so this is
+ * the reference loop: row t of a causal decoder does not depend on later rows. Arithmetic as egx_decoder_fwd, choice for choice (layer 0's
+ * self-attention in-projection in exact fp32 with an fp32 cache, every other GEMM bf16 with fp32 accumulation, the vocabulary head in fp32).
+ * start (B,) int64; memory (B * S, d) fp32 as egx_decoder_fwd; pe needs n_steps rows; tokens_out (B, n_steps) int64 = tok_1 .. tok_n;
+ * logits_out (n_steps, B, vocab) fp32 or NULL. Limits: egx_decoder_fwd's for d_model, heads, d_ff, layers and S; 1 <= n_steps <= 64;
+ * 1 <= vocab <= 1024; cfg->sy is not read. Refused: p_drop / p_pos > 0, compute other than EGX_BF16, null pointers. `workspace`:
+ * egx_decoder_generate_workspace() bytes (bf16 weights, the bf16 memory and its K | V per layer once; per layer a (B, n_steps, 2d) K/V cache;
+ * single-row activations). No token is read on the host: the call can be captured in a hipGraph and replayed on new start / memory contents.
+ * Under capture it stays on `stream`; eagerly the K | V projections run on the library's side stream (as egx_decoder_fwd). */
+int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps, size_t* bytes);
+int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                         const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
+                         float* logits_out /* may be NULL */, void* workspace, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
