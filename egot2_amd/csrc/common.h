@@ -42,6 +42,19 @@ void count_launch();        // kernel launches issued by the library since egx_l
         }                                                                                \
     } while (0)
 
+// Kernel-selection switches (development / test aids; INTEGRATION.md §4 has the table). The environment is read in ONE place, tuning_load() in
+// encoder.hip: at first use, and again on egx_tuning_reload() — the parity tests, which compare the modes inside one process, call it after
+// changing os.environ (egot2_amd/functional.py reload_tuning_each_call). No workspace layout depends on any of them.
+struct Tuning {
+    int ffn_cut = -1;                               // EGX_FFN_CUT = 0 | 1: cut mode of the per-clip kernels off / forced (-1: the library's policy)
+    bool has_slices = false; int slices_cap = 0;    // EGX_FFN_SLICES = 1 | 2 | 4 | 8: cap on the workgroups per clip of small batches
+    bool has_drop = false; long slice_drop = 0;     // EGX_SLICE_DROP = <hex mask>: slices whose workgroups leave at once (testing aid)
+    int dec_group = -1;                             // EGX_DEC_GROUP = 0 | 1: grouped decoder weight gradients off / forced (-1: where the side stream is not used)
+    int wide_tile = 0;                              // EGX_WIDE_TILE = 128 | 256 | 1024: NT tile variant of the wide GEMM (0: by shape)
+    int dec_side = 1;                               // EGX_DEC_SIDE = 0 | 2: no decoder side stream / fork under capture too; takes effect when the stream is first created
+};
+const Tuning& tuning();
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -13,11 +13,6 @@
 #include "wide.h"
 #include "wide_host.h"
 
-// 1: with a valid weight cache the one-launch forward publishes the fused loss through an arrival counter; 0: a 4-byte memset node in front of it (A/B switch)
-#ifndef EGX_CE_TICKET
-#define EGX_CE_TICKET 1
-#endif
-
 namespace egx {
 
 static thread_local char g_err[1024] = "";
@@ -184,7 +179,7 @@ static size_t fused_hid_offset(const egx_config* cfg, const egx_segment* segs, c
 }
 // split / bf16 mode: the FFN input x1 of every layer as bf16 planes (L, 3 or 1, B * 48, d), behind the hidden tiles
 static bool split_planes(const egx_config* cfg) {
-    return (cfg->compute == EGX_F32_SPLIT || (cfg->compute == EGX_BF16 && ffn_dw_bf16_planes())) && store_hidden();
+    return (cfg->compute == EGX_F32_SPLIT || cfg->compute == EGX_BF16) && store_hidden();
 }
 static size_t plane_elem_bytes(const egx_config* cfg) { return cfg->compute == EGX_BF16 ? 2 : 6; }   // one bf16 plane, or the three parts
 static size_t fused_x1p_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
@@ -210,11 +205,7 @@ static size_t fused_core_bytes(const egx_config* cfg, const egx_segment* segs, c
 // 25 % from the second wave per SIMD) with one layer per launch pair and the reference's d_ff; bf16's short loops and deeper / narrower
 // stacks pay more for the two extra launches per layer than the loops gain. EGX_FFN_CUT=1 forces it wherever it is supported (the
 // parity tests run every mode through it), =0 keeps the one-launch kernels.
-// Kernel-selection switches of the per-clip path (development / test aids): EGX_FFN_CUT = 0 | 1, EGX_FFN_SLICES = 1 | 2 | 4 | 8,
-// EGX_SLICE_DROP = <hex mask>. The product library reads the environment ONCE, at first use (round 6; rounds 4-5 called getenv in every
-// forward and backward); egx_tuning_reload() re-reads it — the parity tests, which compare the modes inside one process, call it after
-// changing os.environ (egot2_amd/functional.py reload_tuning_each_call). No workspace layout depends on any of them.
-struct Tuning { int ffn_cut = -1; int slices_cap = 0; bool has_slices = false; long slice_drop = 0; bool has_drop = false; };
+// The one reader of the kernel-selection switches (struct Tuning, common.h); comm.hip reads EGX_RCCL_LIB, a library path, when RCCL is first resolved.
 static Tuning g_tuning;
 static bool g_tuning_loaded = false;
 static void tuning_load() {
@@ -222,10 +213,13 @@ static void tuning_load() {
     if (const char* e = getenv("EGX_FFN_CUT")) t.ffn_cut = e[0] != '0' ? 1 : 0;
     if (const char* e = getenv("EGX_FFN_SLICES")) { t.has_slices = true; t.slices_cap = atoi(e); }
     if (const char* e = getenv("EGX_SLICE_DROP")) { t.has_drop = true; t.slice_drop = strtol(e, nullptr, 16); }
+    if (const char* e = getenv("EGX_DEC_GROUP")) t.dec_group = atoi(e);
+    if (const char* e = getenv("EGX_WIDE_TILE")) t.wide_tile = atoi(e);
+    if (const char* e = getenv("EGX_DEC_SIDE")) t.dec_side = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
     g_tuning = t;
     g_tuning_loaded = true;
 }
-static const Tuning& tuning() { if (!g_tuning_loaded) tuning_load(); return g_tuning; }
+const Tuning& tuning() { if (!g_tuning_loaded) tuning_load(); return g_tuning; }
 static bool use_cut(const Plan& pl, int n_slices, bool tiled, int compute) {
     if (tiled || n_slices != 1 || !ffn_cut_supported(pl.dff)) return false;
     if (tuning().ffn_cut >= 0) return tuning().ffn_cut != 0;
@@ -318,7 +312,6 @@ static bool tiled_ok(const egx_config* cfg, const egx_segment* segs, const Plan&
     if (pl.nseg > FUSED_MAX_SEG || pl.L > FUSED_MAX_LAYERS || pl.L < 1) return false;
     if (packed_feats(segs, pl.nseg) || cfg->p_feat > 0.f) return false;
     if (cfg->compute != EGX_BF16 && cfg->compute != EGX_F32_SPLIT) return false;     // exact-fp32 MFMA: the generic kernels
-    if (cfg->compute == EGX_BF16 && !ffn_dw_bf16_planes()) return false;
     if (cfg->out_tokens != 0 && cfg->out_tokens != pl.S) return false;
     for (int i = 0; i < pl.nseg; ++i)
         if (!segs[i].proj_w || segs[i].d_in % 128 != 0) return false;
@@ -385,12 +378,6 @@ static FusedBwdScratch fused_bwd_scratch(const egx_config* cfg, const egx_segmen
     return s;
 }
 
-// EGX_REDUCE_RIDES=0: the slab / partial-row reductions keep their own launch (tuning aid)
-static bool reduce_rides() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_REDUCE_RIDES"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
-}
 static bool use_fused(const egx_config* cfg, const egx_segment* segs, const Plan& pl, bool* err) {
     *err = false;
     bool ok = fused_ok(cfg, segs, pl);
@@ -756,8 +743,7 @@ static int encoder_fwd_impl(const egx_config* cfg, const egx_segment* segs, cons
         Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
         fp.pos_key = dpz.key; fp.pos_thresh = dpz.thresh; fp.pos_inv = dpz.inv_keep;
         fp.seed_ptr = cfg->seed_ptr;
-        fp.rot_mode = ffn_rot_mode();
-        { static const int sh = [] { const char* e = getenv("EGX_CUT_SHIFT_F"); return e ? atoi(e) + 1 : 0; }(); fp.rot_mode |= sh << 8; }    // tuning aid: older : younger wave split of ffn_fwd_kernel
+        fp.rot_mode = FFN_ROT_XCD_STAGGER;
         fp.n_slices = tiled ? 1 : fused_slices(pl, comp);
         if (fp.n_slices > 1) {
             fp.xchg = (float*)((char*)saved + fused_core_bytes(cfg, segs, vp));
@@ -774,7 +760,7 @@ static int encoder_fwd_impl(const egx_config* cfg, const egx_segment* segs, cons
             fp.ce_target = ce->target; fp.ce_weight = ce->class_weight; fp.ce_loss = ce->loss; fp.ce_dlogits = ce->d_logits; fp.ce_B = B;
             if (pk.n || pk.seed_advance || pk.zero_words) pk.zero_word2 = ce->loss;
             else if (cut) fp.zero_word = ce->loss;
-            else if (cfg->weight_cache && EGX_CE_TICKET) fp.ce_ticket = (unsigned*)((char*)cfg->weight_cache + align_up(PL.bytes, 256));   // no earlier launch: arrival counter instead of a memset node
+            else if (cfg->weight_cache) fp.ce_ticket = (unsigned*)((char*)cfg->weight_cache + align_up(PL.bytes, 256));   // no earlier launch: arrival counter instead of a memset node
             else EGX_HIP(hipMemsetAsync(ce->loss, 0, sizeof(float), st));
         }
         if (tce) {
@@ -1014,8 +1000,7 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
             Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
             bp.pos_key = dpz.key; bp.pos_thresh = dpz.thresh; bp.pos_inv = dpz.inv_keep;
             bp.seed_ptr = cfg->seed_ptr;
-            bp.rot_mode = ffn_rot_mode();
-            { static const int sh = [] { const char* e = getenv("EGX_CUT_SHIFT_B"); return e ? atoi(e) + 1 : 0; }(); bp.rot_mode |= sh << 8; }    // tuning aid: ffn_bwd_kernel
+            bp.rot_mode = FFN_ROT_XCD_STAGGER;
             const int stage = cfg->bwd_stage;
             EGX_CHECK(stage >= 0 && stage <= 2, "bwd_stage=%d", stage);
             if (stage == 2) bp.zero_buf = nullptr;
@@ -1135,20 +1120,11 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
             void* slab = (char*)scratch + SC.slabs;
             for (int l = 0; l < pl.L && stage != 2; ++l)
                 if (launch_ffn_dw(l)) return 1;
-            // One-stage backward outside the deterministic mode: the reductions ride in the grouped small-gradient launch below
-            // (its workgroups each sum 1 / grid of the slabs and partial rows first). Otherwise (two-stage backward: the late
-            // region must be complete when the exchange starts; deterministic: fixed single-adder order) they get their own launch.
-            bool any_small = false;
-            for (int l = 0; l < pl.L; ++l) any_small = any_small || layer_grads[l].out_proj_w || layer_grads[l].in_proj_w;
-            for (int i = 0; i < pl.nseg && seg_grads; ++i) any_small = any_small || seg_grads[i].proj_w;
-            SmallDwTail tail;
             // egx_config.advance_seed == 2: the backward advances the device seed behind its last reader (the last launch that can run here)
             uint64_t* adv = (cfg->advance_seed == 2 && cfg->seed_ptr && training && stage != 1) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
             // Round 6, one-stage backward: small_dw writes tiles and ONE fixed-order launch sums them, the FFN slabs and the partial rows (tail_reduce,
-            // fused_bwd.hip): no float atomics, bit-reproducible in every mode. EGX_TAIL_REDUCE=0: the round-5 launches (atomics with the reductions
-            // riding in small_dw; the slow three-pass path in deterministic mode) — tuning aid. The staged backward (stage 1 / 2) keeps its own launches.
-            static const bool tail_env = [] { const char* e = getenv("EGX_TAIL_REDUCE"); return !(e && e[0] == '0'); }();
-            if (stage == 0 && tail_env) {
+            // fused_bwd.hip): no float atomics, bit-reproducible in every mode. The staged backward (stage 1 / 2) keeps the launches of its own below.
+            if (stage == 0) {
                 TouchList tl;
                 memset(&tl, 0, sizeof(tl));
                 if (touch) {    // the next forward starts with the projections and layer 0's in-projection (one contiguous run of the cache) and out-projection
@@ -1159,7 +1135,7 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
                 memset(&sp, 0, sizeof(sp));
                 bool first = true;
                 auto flush = [&]() -> int {
-                    if (sp.n && small_dw(sp, comp, st, (char*)scratch + SC.sdw_tiles, SC.sdw_bytes, nullptr, false)) return 1;
+                    if (sp.n && small_dw(sp, comp, st, (char*)scratch + SC.sdw_tiles, SC.sdw_bytes, false)) return 1;
                     const int rc = (sp.n || first) ? tail_reduce(sp.n ? &sp : nullptr, first ? &red : nullptr, first ? &rp : nullptr, first ? adv : nullptr, first ? &tl : nullptr, st) : 0;
                     first = false;
                     memset(&sp, 0, sizeof(sp));
@@ -1181,28 +1157,18 @@ static int encoder_bwd_impl(const egx_config* cfg, const egx_segment* segs, cons
                     if (seg_grads && add(bp.dseg_out[i], d, segs[i].feat, segs[i].d_in, seg_grads[i].proj_w, d, segs[i].d_in, B * segs[i].T)) return 1;
                 return flush();
             }
-            const bool ride = stage == 0 && !cfg->deterministic && any_small && (red.narr || rp_pending) && reduce_rides();
-            if (ride) {
-                small_dw_tail_init(tail, red, rp_pending ? &rp : nullptr);
-                tail.seed_advance = adv; adv = nullptr;
-                if (touch) {    // the next forward starts with the projections and layer 0's in-projection (one contiguous run of the cache) and out-projection
-                    touch_add(tail.touch, PL.proj[0], (size_t)((const char*)PL.layer[0].in_wt - (const char*)PL.proj[0]));
-                    touch_add(tail.touch, PL.layer[0].out_w, out_pb);
-                }
-                rp_pending = false;
-            } else if (red.narr) {
+            // two-stage backward: the late region must be complete when the exchange starts, so the reductions get a launch of their own
+            if (red.narr) {
                 if (ffn_dw_reduce(red, rp_pending ? &rp : nullptr, cfg->deterministic != 0, st)) return 1;
                 rp_pending = false;
             }
             if (rp_pending && reduce_partials(rp, st, cfg->deterministic != 0)) return 1;
-            bool tail_pending = ride;
             // every remaining weight gradient (dW_o, dW_in per layer, dW_proj per segment) in grouped launches
             if (stage != 1) {
                 SmallDwParams sp;
                 memset(&sp, 0, sizeof(sp));
                 auto flush = [&]() -> int {
-                    int rc = sp.n ? small_dw(sp, comp, st, cfg->deterministic ? slab : nullptr, SC.slab_bytes, tail_pending ? &tail : nullptr) : 0;
-                    if (sp.n) tail_pending = false;
+                    int rc = sp.n ? small_dw(sp, comp, st, cfg->deterministic ? slab : nullptr, SC.slab_bytes) : 0;
                     memset(&sp, 0, sizeof(sp));
                     return rc;
                 };
@@ -1609,7 +1575,7 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
     EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_TILED, "ragged batch: runs on the tiled kernels (impl auto or tiled, got %d)", cfg->impl);
     // what tiled_ok() asks of the configuration, the clip length apart
     EGX_CHECK(vp.d == 128 && vp.H == 4 && vp.dff % 128 == 0 && vp.dff >= 128 && vp.nseg <= FUSED_MAX_SEG && vp.L >= 1 && vp.L <= FUSED_MAX_LAYERS &&
-              !packed_feats(segs, vp.nseg) && (cfg->compute == EGX_F32_SPLIT || (cfg->compute == EGX_BF16 && ffn_dw_bf16_planes())),
+              !packed_feats(segs, vp.nseg) && (cfg->compute == EGX_F32_SPLIT || cfg->compute == EGX_BF16),
               "ragged batch: needs d=128, h=4, d_ff%%128==0, <= %d segments, 1..%d layers, fp32 features, compute bf16 or f32s", FUSED_MAX_SEG, FUSED_MAX_LAYERS);
     for (int k = 0; k < vp.nseg; ++k)
         EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0, "ragged batch: segment %d needs a projection with d_in %% 128 == 0", k);
@@ -2005,7 +1971,7 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     memset(&sp, 0, sizeof(sp));
     bool first = true;
     auto flush = [&]() -> int {
-        if (sp.n && small_dw(sp, comp, st, (char*)scratch + SC.sdw_tiles, SC.sdw_bytes, nullptr, false)) return 1;
+        if (sp.n && small_dw(sp, comp, st, (char*)scratch + SC.sdw_tiles, SC.sdw_bytes, false)) return 1;
         const int rc = (sp.n || first) ? tail_reduce(sp.n ? &sp : nullptr, first ? &red : nullptr, first ? &rpp : nullptr, first ? adv : nullptr, nullptr, st) : 0;
         first = false;
         memset(&sp, 0, sizeof(sp));

@@ -63,14 +63,8 @@ constexpr int CPS = CSP * LDXH;         // one bf16 operand plane (halfwords)
 // fragments in flight per wave (a divisor of the 16 fragments of a hidden block: slot = position mod depth is then static).
 // f32s: 12 registers per fragment, f32: 8 — four is what fits 256 registers beside the 96 accumulators; bf16: 4 registers per fragment
 // and only 48 matrix-pipe cycles of work per fragment: a whole block ahead.
-#ifndef EGX_RING_SPLIT
-#define EGX_RING_SPLIT 4
-#endif
-#ifndef EGX_RING_BF16
-#define EGX_RING_BF16 16
-#endif
-template <int CM> struct RingDepth { static constexpr int v = EGX_RING_SPLIT; };
-template <> struct RingDepth<CM_BF16> { static constexpr int v = EGX_RING_BF16; };
+template <int CM> struct RingDepth { static constexpr int v = 4; };
+template <> struct RingDepth<CM_BF16> { static constexpr int v = 16; };
 
 // B-operand fragment of token tile `row0` for the K-block at feature k0: from the pre-split planes (f32s: three, bf16: one) or the fp32 block
 template <int CM>
@@ -310,7 +304,7 @@ __global__ __launch_bounds__(CT) void ffn_fwd_kernel(FusedFwdParams p, int l) {
         }
         __syncthreads();
         touch_sink(tch);
-        if (CM != CM_F32 && !have_planes) {     // no planes handed over (EGX_FFN_DW_PLANES=0): build them from the fp32 rows
+        if (CM != CM_F32 && !have_planes) {     // no planes handed over: build them from the fp32 rows
             if constexpr (CM == CM_SPLIT) block_to_split_planes(XP, X1);
             else if constexpr (CM == CM_BF16) block_to_plane(XP, X1);
             __syncthreads();

@@ -58,7 +58,7 @@ struct FusedFwdParams {
     const float* ln_w; const float* ln_b;
     float eps;
     int nseg, n_layers, B, S, d_ff;
-    int rot_mode;           // hidden-block walk order of the FFN loops (ffn_rot_mode(): tuning aid EGX_FFN_ROT)
+    int rot_mode;           // hidden-block walk order of the FFN loops (FFN_ROT_XCD_STAGGER in the clip-parallel step, 1 in the tiled one)
     float* tokens_out;      // (B, out_T, 128) or null when only the head output is wanted
     int out_T;              // tokens of every clip that leave the kernel (S, or egx_config.out_tokens)
     FusedHead head; float* logits_out;   // (B, n_out) when head.n_out > 0
@@ -154,9 +154,9 @@ static inline size_t fused_hid_bytes(int B, int d_ff, int bf16) {   // one layer
     return (size_t)B * FUSED_TOK_TILES * (d_ff / 16) * 256 * (bf16 ? 2 : 4);
 }
 size_t ffn_dw_scratch_bytes(int N, int d_ff, int* splits_out);
-bool ffn_dw_bf16_planes();
-int ffn_rot_mode();         // EGX_FFN_ROT: 4 (default): clips of an XCD start 0..3 hidden blocks apart; 0: every clip at its own block; 1: all in step;
-                            // 2 / 3: 4 / 2 phase groups per XCD; 5: 0..7 blocks apart   // bf16 mode hands x1 / g2 over as bf16 planes (the LDS-ring weight-gradient kernel)
+// rot_mode the host passes for the clip-parallel step: clips of an XCD start 0..3 hidden blocks apart. (The kernels still decode 0: every clip at its
+// own block; 1: all in step; 2 / 3: 4 / 2 phase groups per XCD; 5: 0..7 blocks apart — measured slower, DESIGN.md §7 lists folding them.)
+constexpr int FFN_ROT_XCD_STAGGER = 4;
 struct ReducePartialsParams;
 // out[k][i] += sum_z slab[k][z * n[k] + i] for up to SLAB_REDUCE_MAX arrays (three per layer: dW1, dW2^T, db1) in ONE launch
 constexpr int SLAB_REDUCE_MAX = 3 * FUSED_MAX_LAYERS;
@@ -199,7 +199,7 @@ struct FusedBwdParams {
     const float* ln_w; const float* ln_b;
     float eps;
     int nseg, n_layers, B, S, d_ff;
-    int rot_mode;           // hidden-block walk order of the FFN loops (ffn_rot_mode(): tuning aid EGX_FFN_ROT)
+    int rot_mode;           // hidden-block walk order of the FFN loops (FFN_ROT_XCD_STAGGER in the clip-parallel step, 1 in the tiled one)
     const float* d_tokens;     // (B, out_T, 128), or null when the head is fused (then d_logits drives the backward)
     int out_T;                 // tokens of every clip that carry an upstream gradient (S, or egx_config.out_tokens)
     FusedHead head; const float* d_logits; int head_off;   // head_off: offset of the head section in the partial row
@@ -260,11 +260,8 @@ struct SmallDwParams {
     float* slabs;         // deterministic mode: one dense [64][128] fp32 tile per workgroup, summed in split order afterwards
 };
 // slabs / slab_bytes: optional scratch for the deterministic (atomic-free) variant; null = atomic accumulation
-struct SmallDwTail;
-// `tail` (optional): the FFN slab reduction and the partial-row reduction, done by this launch's workgroups before their own
-// work (each takes 1 / grid of the units) instead of by a launch of their own
 // reduce_here = false (with slabs): the tiles are left for tail_reduce()
-int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs = nullptr, size_t slab_bytes = 0, const SmallDwTail* tail = nullptr, bool reduce_here = true);
+int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs = nullptr, size_t slab_bytes = 0, bool reduce_here = true);
 int seed_advance(uint64_t* seed, hipStream_t st);
 
 struct PartialDst { float* dst; int off, len; };
@@ -275,8 +272,8 @@ struct ReducePartialsParams {
     const float* partials;
 };
 int reduce_partials(const ReducePartialsParams& rp, hipStream_t st, bool deterministic = false);
+// (second argument of small_dw_kernel, unused since the reductions left that kernel for tail_reduce; kept so that its arguments stay what they were)
 struct SmallDwTail { SlabReduce red; ReducePartialsParams rp; unsigned slab_blocks; int rp_units, chunks; uint64_t* seed_advance; /* optional: *seed = lcg(*seed) by the first thread (egx_config.advance_seed == 2) */ TouchList touch; /* the next forward's first weight streams */ };
-void small_dw_tail_init(SmallDwTail& t, const SlabReduce& red, const ReducePartialsParams* rp);
 // Round 6: every cross-workgroup sum of the per-clip backward in ONE fixed-order launch (fused_bwd.hip tail_reduce_kernel): the tiles small_dw(sp, ..., slabs)
 // wrote, the FFN slabs, the per-clip partial rows; also the seed advance and the next forward's weight prefetch. Null / empty parts are skipped.
 int tail_reduce(const SmallDwParams* sp, const SlabReduce* red, const ReducePartialsParams* rp, uint64_t* seed_advance_ptr, const TouchList* touch, hipStream_t st);

@@ -23,19 +23,6 @@
 #include <type_traits>
 #include <vector>
 
-// bf16 FFN loop of the clip kernels software-pipelined across hidden blocks (see fused_fwd_kernel); 0 = the block-after-block loop of rounds 2-5.
-// OFF: the stamps of workgroup 0 show the phase at 49.3k -> 45.7k cycles, but four interleaved same-box pairs of the whole step do not
-// (profiles/r06_ab_second_half.txt): c2 bf16 +4.3 us (+2 %) with it, C3 -1.8 us (-0.4 %). Kept as a build switch with the measurements.
-#ifndef EGX_FFN_PIPE
-#define EGX_FFN_PIPE 0
-#endif
-#ifndef EGX_FFN_PIPE_RING
-#define EGX_FFN_PIPE_RING 8
-#endif
-#ifndef EGX_FFN_PIPE_VALU
-#define EGX_FFN_PIPE_VALU 6
-#endif
-
 namespace egx {
 
 __global__ __launch_bounds__(64) void pack_weights_kernel(PackParams pp) {
@@ -871,163 +858,6 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
                 for (int i = 0; i < 8; ++i) w2r[i] = load_w<CM>(w.lin2_wp, i, nhb, hb0, lane);
             }
             LSTAMP_INIT();
-            // (training with dropout only: the epilogue without the mask is half as long, and a second instantiation of the pipelined loop costs ~60
-            // registers of hoisted loop invariants; the sliced instantiation has no registers left for the second set either: 37 spills)
-            bool ffn_done = false;
-            if constexpr (CM == CM_BF16 && EGX_FFN_PIPE && !SLICED) if (w.ffn_thresh) {
-                ffn_done = true;
-                // bf16 (round 6): ONE wave per SIMD and 16 cycles of matrix pipe per MFMA against ~280 VALU instructions of epilogue per hidden
-                // block: run block after block as [W1 x1 | epilogue | W2 H] and the matrix pipe idles through every epilogue (stamps: GEMM1 11.5k +
-                // epilogue 21.8k + GEMM2 10.6k of the 49k-cycle loop; 26 % busy). The three are independent ACROSS blocks, so the loop is
-                // software-pipelined: the epilogue of block `it` is issued together with GEMM1 of block it + 1 (into a second accumulator set)
-                // and GEMM2 of block it - 1 (from the operand fragments the previous epilogue left), one MFMA per ~6 VALU instructions
-                // (sched_group_barrier). The first GEMM2 meets zero fragments and the last GEMM1 is discarded: +2 / 16 of the MFMAs, all hidden.
-                {
-                    const uint32_t rowbase = TILED ? (uint32_t)tokbase : (uint32_t)(clip * 64);
-                    f32x4 hc[2][NT];
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) hc[i][t] = f32x4{0, 0, 0, 0};
-                    {
-                        const int hb1 = hb_of(1 < nit ? 1 : 0);
-#pragma unroll
-                        for (int kb = 0; kb < FD / 32; ++kb)
-#pragma unroll
-                            for (int i = 0; i < 2; ++i) {
-                                pin(w1r[i][kb]);
-                                Frag<CM> a = w_frag<CM>(w1r[i][kb]);
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) mma<CM>(hc[i][t], a, xb[kb][t]);
-                                __builtin_amdgcn_sched_barrier(0);
-                                w1r[i][kb] = load_w<CM>(w.lin1_wp, hb1 * 2 + i, FD / 32, kb, lane);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                    }
-                    // two register sets that swap roles from block to block (no copies): (pre-activations, operand fragments) of this block / the next
-                    f32x4 hc2[2][NT];
-                    Frag<CM> hqA[NT], hqB[NT];
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) hqA[t].v = __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
-                    auto step = [&](int it, f32x4 (&hc)[2][NT], f32x4 (&hn)[2][NT], const Frag<CM> (&hq_prev)[NT], Frag<CM> (&hq)[NT]) {
-                        const int hb = hb_of(it);
-                        const int hbn = hb_of(it + 1 < nit ? it + 1 : it);
-                        const int hb2 = hb_of(it + 2 < nit ? it + 2 : nit - 1);
-                        const int hbp = hb_of(it > 0 ? it - 1 : 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        LSTAMP(0);
-                        float bv[2][4];
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            bv[i][0] = b1r[i].x * bscale; bv[i][1] = b1r[i].y * bscale; bv[i][2] = b1r[i].z * bscale; bv[i][3] = b1r[i].w * bscale;
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) b1r[i] = *reinterpret_cast<const float4*>(w.lin1_b + hbn * 32 + i * 16 + 4 * q);
-                        __builtin_amdgcn_sched_barrier(0);
-                        // 16 steps: one weight fragment's MFMAs (steps 0-7: GEMM1 of the NEXT block -> hn, the last iteration's is discarded; 8-15:
-                        // GEMM2 of the PREVIOUS block) + one slice of this block's epilogue. ONE ring of eight fragment slots (w1r) serves both
-                        // streams: a slot's fragment is requested eight steps (~1k cycles) before its MFMAs — a second set of eight costs 32 registers
-                        // the kernel does not have (the two accumulator / operand sets already take it to 512)
-                        // (2 NT slices bias + dropout of one 16 x 16 tile, NT slices alive bits + ReLU of eight units, NT slices operand fragment +
-                        // H tile of a token tile)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) hn[i][t] = f32x4{0, 0, 0, 0};
-                        uint32_t dead = 0;
-                        static_assert(4 * NT <= 16, "epilogue slices");
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) {
-                            if (k < 8) {
-                                const int kb = k >> 1, i = k & 1;
-                                pin(w1r[i][kb]);
-                                Frag<CM> a = w_frag<CM>(w1r[i][kb]);
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) mma<CM>(hn[i][t], a, xb[kb][t]);
-#if EGX_FFN_PIPE_RING == 16
-                                w1r[i][kb] = load_w<CM>(w.lin1_wp, hb2 * 2 + i, FD / 32, kb, lane);
-#else
-                                w1r[i][kb] = load_w<CM>(w.lin2_wp, k, nhb, hbp, lane);             // slot k: W2 fragment k, needed eight steps on
-#endif
-                            } else {
-                                const int j = k - 8, i = j & 1, kb = j >> 1;
-#if EGX_FFN_PIPE_RING == 16
-                                pin(w2r[j]);
-                                Frag<CM> a = w_frag<CM>(w2r[j]);
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) mma<CM>(y[j][t], a, hq_prev[t]);
-                                w2r[j] = load_w<CM>(w.lin2_wp, j, nhb, hb, lane);
-#else
-                                pin(w1r[i][kb]);
-                                Frag<CM> a = w_frag<CM>(w1r[i][kb]);
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) mma<CM>(y[j][t], a, hq_prev[t]);
-                                w1r[i][kb] = load_w<CM>(w.lin1_wp, hb2 * 2 + i, FD / 32, kb, lane);   // slot j: W1 fragment j of the block after next
-#endif
-                            }
-                            if (k < 2 * NT) {
-                                const int i = k / NT, t = k % NT;
-                                if constexpr (true) {
-                                    const uint32_t cq = (uint32_t)(hb * 32 + i * 16 + 4 * q) >> 2;
-                                    const uint2 h = rand_quad(k_ffn, rowbase + (uint32_t)(t * 16 + r), cq);
-                                    // dropped units become negative: the ReLU zeroes them and their sign bit marks them dead
-                                    hc[i][t][0] = keep_lo(h.x, w.ffn_thresh) ? hc[i][t][0] + bv[i][0] : -1.f;
-                                    hc[i][t][1] = keep_hi(h.x, w.ffn_thresh) ? hc[i][t][1] + bv[i][1] : -1.f;
-                                    hc[i][t][2] = keep_lo(h.y, w.ffn_thresh) ? hc[i][t][2] + bv[i][2] : -1.f;
-                                    hc[i][t][3] = keep_hi(h.y, w.ffn_thresh) ? hc[i][t][3] + bv[i][3] : -1.f;
-                                } else {
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) hc[i][t][e] += bv[i][e];
-                                }
-                            } else if (k < 3 * NT) {
-                                const int j = k - 2 * NT;       // units 8 (NT - j) - 1 .. 8 (NT - 1 - j): the word's bit order is the loop's below
-#pragma unroll
-                                for (int kk = 8 * (NT - j) - 1; kk >= 8 * (NT - 1 - j); --kk) {
-                                    const int i = kk / (NT * 4), t = (kk / 4) % NT, e = kk & 3;
-                                    dead = __builtin_amdgcn_alignbit(dead, __float_as_uint(hc[i][t][e]), 31);
-                                    hc[i][t][e] = __int_as_float(max(__float_as_int(hc[i][t][e]), 0));
-                                }
-                                if (k == 3 * NT - 1) p.relu_bits[bits_base + (size_t)hb * 64] = ~dead & ((1u << (2 * NT * 4)) - 1u);
-                            } else if (k < 4 * NT) {
-                                const int t = k - 3 * NT;
-                                hq[t] = chain_frag<CM>(hc[0][t], hc[1][t]);
-                                const u32x4 u = __builtin_bit_cast(u32x4, hq[t].v);
-                                store_hid_tile_bf16(hid_base + (size_t)hb * 2 * (HTILE_ELEMS * ESZ) + (size_t)t * nht * (HTILE_ELEMS * ESZ), u, lane, S - t * 16);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        LSTAMP(3);
-                    };
-                    auto last_gemm2 = [&](const Frag<CM> (&hq_last)[NT]) {      // (its W2 columns are requested here: one exposed round trip per layer)
-#if EGX_FFN_PIPE_RING != 16
-                        const int hbl = hb_of(nit - 1);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) w2r[i] = load_w<CM>(w.lin2_wp, i, nhb, hbl, lane);
-#endif
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            Frag<CM> a = w_frag<CM>(w2r[i]);
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) mma<CM>(y[i][t], a, hq_last[t]);
-                        }
-                    };
-                    int it = 0;
-                    for (; it + 1 < nit; it += 2) {
-                        step(it, hc, hc2, hqA, hqB);
-                        step(it + 1, hc2, hc, hqB, hqA);
-                    }
-                    if (it < nit) {     // odd block count (narrow FFNs, deep slicing)
-                        step(it, hc, hc2, hqA, hqB);
-                        last_gemm2(hqB);
-                    } else {
-                        last_gemm2(hqA);
-                    }
-                    LSTAMP(4);
-                }
-            }
-            if (!ffn_done)
             for (int it = 0; it < nit; ++it) {
                 const int hb = hb_of(it);
                 const int hbn = hb_of(it + 1 < nit ? it + 1 : it);     // the last block refills itself (never used)
@@ -1489,12 +1319,6 @@ static int launch_fwd_ragged(const FusedFwdParams& p, hipStream_t st) {
     timing_end(TIMER_FUSED_FWD, st);
     EGX_LAUNCH_CHECK();
     return 0;
-}
-
-int ffn_rot_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_FFN_ROT"); v = e ? atoi(e) : 4; }
-    return v;
 }
 
 int fused_forward(const FusedFwdParams& p, int compute, hipStream_t st) {

@@ -15,17 +15,6 @@
 #include "common.h"
 #include "kernels.h"
 #include "fused.h"
-// bf16 FFN input-gradient loop of the clip kernels software-pipelined across hidden blocks like the forward's (fused_bwd_kernel P4); 0 = block after
-// block. OFF: measured no faster — stamps of the phase 38.0k -> 40.5k cycles (16-slot ring) with the LayerNorm1 backward behind it 10.9k -> 17.6k,
-// c2 bf16 / C3 steps within the box noise of the plain loop (201.7 vs 201.1, 400.0 vs 390.5, 208.4 vs 217.3 us). Unlike the forward's, this loop's
-// epilogue is short (110 VALU per block: masks from the saved alive bits, pack, dH tiles): there is little to hide.
-#ifndef EGX_FFN_PIPE_BWD
-#define EGX_FFN_PIPE_BWD 0
-#endif
-#ifndef EGX_FFN_PIPE_BWD_RING
-#define EGX_FFN_PIPE_BWD_RING 16      // fragment slots of the pipelined loop: 16 = a ring per weight stream (the backward has the registers), 8 = one shared ring
-#endif
-
 #ifdef EGX_STAMPS
 namespace egx { extern __device__ unsigned long long g_bstamps[32]; }
 #define LNB_STAMP(base, k) do { if ((base) >= 0 && blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); egx::g_bstamps[(base) + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
@@ -260,17 +249,16 @@ __global__ __launch_bounds__(256, HT == 1 ? 2 : 1) void ffn_dw_kernel(FfnDwParam
 // grid (FUSED_TOK_TILES per clip); x1 / g rows of padding tokens are staged as zeros.
 // PART (round 5, f32s): 0 = both weight gradients in one workgroup (the kernel of rounds 3-4); 1 = dW1 (+ db1) only, 2 = dW2 only. A PART workgroup
 // keeps one accumulator set, stages one operand image (x1 or g: 27 KB of planes) and reads one of the H / dH tile streams: about half the
-// registers and half the LDS, so FOUR workgroups share a CU where two did. ffn_dw_split2_kernel launches both parts as one grid (blockIdx.z).
+// registers and half the LDS, so twice as many waves share a CU. ffn_dw_split2w8_kernel launches both parts as one grid (blockIdx.z).
 // NW (round 6, f32s PART workgroups only): 8 = eight waves share the staged operand image (hidden group of 128: the x1 / g planes are fetched
 // once per 128 hidden units instead of once per 64 — 805 -> 510 MB through the CUs' address paths per launch)
-// NH (round 6, f32s PART workgroups only; tuning aid EGX_FFN_DW_W8=42 | 82): hidden tiles per wave. A wave's 8 token-along-K fragments of the x1 / g
-// image (48 transposing LDS reads of 512 B per K-block) meet NH H / dH fragments: at NH = 1 the kernel issues ONE LDS read per MFMA (SQ counters,
-// profiles/r06_pmc_c2_f32s.json: 5.0 M LDS instructions for 4.7 M MFMAs, 49 % MFMA busy), NH = 2 halves that without splitting any H / dH tile twice.
-// Measured SLOWER: c2 f32s step 351 / 357 us (NH = 1, eight waves) vs 362 / 365 (NH = 2, four waves, three workgroups per CU) vs 371 / 372 (NH = 2, eight
-// waves, one per CU): the kernel wants four independent waves per SIMD more than it wants fewer LDS reads. Default unchanged.
+// NH: hidden tiles per wave. Only NH = 1 is instantiated: two per wave (half the LDS fragment reads per MFMA) measured SLOWER, c2 f32s step 351 / 357 us
+// vs 362 / 365 (four waves) and 371 / 372 (eight) — the kernel wants four independent waves per SIMD more than fewer LDS reads. The parameter stays
+// because writing the loops over it out moves the schedule of the db1 epilogue. The NH = 2 kernels, the four- and the sixteen-wave
+// PART grids last existed at 3b19ffd.
 template <int CM, int OCC, int PART, int NW = 4, int NH = 1>
 __device__ __forceinline__ void ffn_dw_stored_body(const FfnDwParams& p) {
-    static_assert(NW == 4 || ((NW == 8 || NW == 16) && CM == CM_SPLIT && PART != 0), "eight / sixteen waves: the f32s PART workgroups only");
+    static_assert(NW == 4 || (NW == 8 && CM == CM_SPLIT && PART != 0), "eight waves: the f32s PART workgroups only");
     static_assert(NH == 1 || (CM == CM_SPLIT && PART != 0), "several hidden tiles per wave: the f32s PART workgroups only");
     constexpr bool W1 = PART != 2, W2 = PART != 1;
     constexpr bool BF16 = CM == CM_BF16;
@@ -324,21 +312,7 @@ __device__ __forceinline__ void ffn_dw_stored_body(const FfnDwParams& p) {
     // 16 B of every (tensor, part) image: no split work here (the 32 workgroups of a token range used to repeat it)
     uint4 prs[SPLIT ? 12 : 1];
     auto gload = [&](int kb) {
-        if constexpr (SPLIT && NW == 16) {
-            // 1024 threads: the image's 3 x 32 x 16 sixteen-byte pieces in two passes (the second half-empty: clamped, not stored)
-            const size_t plane = (size_t)p.B * FUSED_TOK_PAD * FD;
-            const unsigned short* base = reinterpret_cast<const unsigned short*>(W1 ? p.x1 : p.g);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                int idx = tid + k * 1024;
-                idx = idx < 1536 ? idx : 1535;
-                const int part = idx >> 9, row = (idx & 511) >> 4, c8 = idx & 15;
-                const int tile = kb * 2 + (row >> 4);
-                const int tc = tile < ntile ? tile : ntile - 1;
-                const uint4 v = *reinterpret_cast<const uint4*>(base + part * plane + ((size_t)tc * 16 + (row & 15)) * FD + c8 * 8);
-                prs[k] = tile < ntile ? v : make_uint4(0, 0, 0, 0);
-            }
-        } else if constexpr (SPLIT) {
+        if constexpr (SPLIT) {
             const size_t plane = (size_t)p.B * FUSED_TOK_PAD * FD;
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
@@ -386,15 +360,6 @@ __device__ __forceinline__ void ffn_dw_stored_body(const FfnDwParams& p) {
         }
     };
     auto lstore = [&](int buf_idx) {
-        if constexpr (SPLIT && NW == 16) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int idx = tid + k * 1024;
-                const int part = idx >> 9, row = (idx & 511) >> 4, c8 = idx & 15;
-                if (idx < 1536) *reinterpret_cast<uint4*>(ldsh + part * TILEH + row * LDB + c8 * 8) = prs[k];
-            }
-            return;
-        }
         if constexpr (SPLIT) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
@@ -583,28 +548,10 @@ __device__ __forceinline__ void ffn_dw_stored_body(const FfnDwParams& p) {
 
 template <int CM, int OCC>
 __global__ __launch_bounds__(256, OCC) void ffn_dw_stored_kernel(FfnDwParams p) { ffn_dw_stored_body<CM, OCC, 0>(p); }
-// f32s: dW1 (+ db1) workgroups (blockIdx.z = 0) and dW2 workgroups (z = 1) in one grid, four per CU
-__global__ __launch_bounds__(256, 4) void ffn_dw_split2_kernel(FfnDwParams p) {
-    if (blockIdx.z == 0) ffn_dw_stored_body<CM_SPLIT, 2, 1>(p);
-    else ffn_dw_stored_body<CM_SPLIT, 2, 2>(p);
-}
+// f32s: dW1 (+ db1) workgroups (blockIdx.z = 0) and dW2 workgroups (z = 1) in one grid of eight-wave workgroups, two per CU
 __global__ __launch_bounds__(512, 2) void ffn_dw_split2w8_kernel(FfnDwParams p) {
     if (blockIdx.z == 0) ffn_dw_stored_body<CM_SPLIT, 2, 1, 8>(p);
     else ffn_dw_stored_body<CM_SPLIT, 2, 2, 8>(p);
-}
-// two hidden tiles per wave (NH = 2): four waves per workgroup = a hidden group of 128 like the eight-wave grid, three workgroups per CU (<= 168 registers)
-__global__ __launch_bounds__(256, 3) void ffn_dw_split2h2_kernel(FfnDwParams p) {
-    if (blockIdx.z == 0) ffn_dw_stored_body<CM_SPLIT, 2, 1, 4, 2>(p);
-    else ffn_dw_stored_body<CM_SPLIT, 2, 2, 4, 2>(p);
-}
-// ... and eight waves: a hidden group of 256
-__global__ __launch_bounds__(512, 1) void ffn_dw_split2w8h2_kernel(FfnDwParams p) {
-    if (blockIdx.z == 0) ffn_dw_stored_body<CM_SPLIT, 2, 1, 8, 2>(p);
-    else ffn_dw_stored_body<CM_SPLIT, 2, 2, 8, 2>(p);
-}
-__global__ __launch_bounds__(1024, 1) void ffn_dw_split2w16_kernel(FfnDwParams p) {
-    if (blockIdx.z == 0) ffn_dw_stored_body<CM_SPLIT, 2, 1, 16>(p);
-    else ffn_dw_stored_body<CM_SPLIT, 2, 2, 16>(p);
 }
 
 // bf16 stored-operand kernel with everything staged by LDS-DMA. ffn_dw_stored_kernel<CM_BF16> spends a K-block's time on
@@ -616,15 +563,14 @@ __global__ __launch_bounds__(1024, 1) void ffn_dw_split2w16_kernel(FfnDwParams p
 // + 4 waves x 4 tiles of 512 B (accumulator layout, read back token-along-K by ds_read_b64_tr_b16 as they lie). 256 threads,
 // two independent workgroups per CU.
 #define EGX_RING_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-// NW waves per workgroup share the staged x1 / g images (round 6: with four waves 24 KB per K-block for 64 MFMAs, the images 16 KB of it; eight and
-// sixteen waves measured SLOWER, 201 -> 205-219 us on the c2 bf16 step: the default stays four); D ring stages.
-template <int NW, int D>
+// Four waves per workgroup share the staged x1 / g images (round 6: 24 KB per K-block for 64 MFMAs, the images 16 KB of it; eight and sixteen
+// waves measured SLOWER, 201 -> 205-219 us on the c2 bf16 step, as did a two-stage ring; those variants last existed at 3b19ffd).
 __device__ __forceinline__ void ffn_dw_bf16_ring_body(const FfnDwParams& p) {
     constexpr int CM = CM_BF16;
+    constexpr int NW = 4, D = 3;         // waves per workgroup, ring stages
     // (two stages at three workgroups per CU, with 16 or 24 token splits, run at the same 35 us)
     constexpr int IMG = 32 * 256, TILES = NW * 4 * 512, SB = 2 * IMG + TILES;
     constexpr int IMGI = 16 / NW;        // image staging instructions per wave and K-block (two images x 32 rows = 16 wave-loads of 4 rows)
-    static_assert(NW == 4 || NW == 8 || NW == 16, "4, 8 or 16 waves");
     extern __shared__ __attribute__((aligned(16))) unsigned char ring[];
     typedef __attribute__((address_space(3))) void lds_void;
     typedef const __attribute__((address_space(1))) void glb_void;
@@ -698,10 +644,9 @@ __device__ __forceinline__ void ffn_dw_bf16_ring_body(const FfnDwParams& p) {
             const int kb = kb0 + s;
             if (kb >= kb_end) break;
             // this K-block's loads have landed; the next K-block's (IMGI + 2 per wave) may stay in flight across the barrier
-            if (kb + 1 < kb_end) {
-                if constexpr (D >= 3) { if constexpr (IMGI == 4) EGX_RING_WAIT(6); else if constexpr (IMGI == 2) EGX_RING_WAIT(4); else EGX_RING_WAIT(3); }
-                else EGX_RING_WAIT(0);
-            } else EGX_RING_WAIT(0);
+            static_assert(IMGI + 2 == 6, "the counted wait below");
+            if (kb + 1 < kb_end) EGX_RING_WAIT(6);
+            else EGX_RING_WAIT(0);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             if (kb + D - 1 < kb_end) stage(kb + D - 1, (s + D - 1) % D);
             const bool has_b = kb * 2 + 1 < ntile;
@@ -753,10 +698,8 @@ __device__ __forceinline__ void ffn_dw_bf16_ring_body(const FfnDwParams& p) {
     }
     if (r == 0) *reinterpret_cast<float4*>(p.slab_b1 + (size_t)split * p.d_ff + htile * 16 + 4 * q) = make_float4(accB4[0], accB4[1], accB4[2], accB4[3]);
 }
-__global__ __launch_bounds__(256, 2) void ffn_dw_bf16_ring_kernel(FfnDwParams p) { ffn_dw_bf16_ring_body<4, 3>(p); }
-__global__ __launch_bounds__(512, 1) void ffn_dw_bf16_ring8_kernel(FfnDwParams p) { ffn_dw_bf16_ring_body<8, 3>(p); }
-__global__ __launch_bounds__(512, 2) void ffn_dw_bf16_ring8d2_kernel(FfnDwParams p) { ffn_dw_bf16_ring_body<8, 2>(p); }
-__global__ __launch_bounds__(1024, 1) void ffn_dw_bf16_ring16_kernel(FfnDwParams p) { ffn_dw_bf16_ring_body<16, 3>(p); }
+
+__global__ __launch_bounds__(256, 2) void ffn_dw_bf16_ring_kernel(FfnDwParams p) { ffn_dw_bf16_ring_body(p); }
 
 // Three slab reductions in one launch: out_k[i] += sum_z slab_k[z * n_k + i], float4-vectorised. The same launch can
 // carry the reduction of the per-clip partial rows (blocks >= slab_blocks; see reduce_partials_kernel).
@@ -813,43 +756,13 @@ __global__ __launch_bounds__(256) void reduce_tail_kernel(SlabReduce a, ReducePa
 static int partial_chunks(int B) { return B >= 64 ? 16 : (B >= 8 ? 4 : 1); }
 
 // fp32 stored-operand kernel: three workgroups per CU (single LDS buffer, no register prefetch) with 24 token splits;
-// every other variant: two per CU, 16 splits. EGX_FFN_DW_OCC=2|3 overrides (tuning aid).
-static int ffn_dw_occ(bool stored, bool bf16) {
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("EGX_FFN_DW_OCC"); env = (e && (e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 0; }
-    if (!stored) return 2;
-    return env ? env : (bf16 ? 2 : 3);
-}
-// EGX_FFN_DW_RING=0: bf16 runs keep fp32 x1 / g2 hand-overs and ffn_dw_stored_kernel<CM_BF16> (tuning aid; read by the
-// encoder when it lays out the buffers, see ffn_dw_bf16_planes())
-static bool ffn_dw_ring() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_FFN_DW_RING"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
-}
-bool ffn_dw_bf16_planes() { return ffn_dw_ring(); }
-// waves per workgroup of the bf16 LDS-ring kernel: 4 (rounds 3-5), 8, 16, or 82 = eight waves with a two-stage ring at two workgroups per CU
-// (EGX_FFN_DW_BF16_NW, tuning aid)
-static int ffn_dw_bf16_waves(int d_ff) {
-    static const int env = [] { const char* e = getenv("EGX_FFN_DW_BF16_NW"); return e ? atoi(e) : 4; }();
-    const int nwv = env == 82 ? 8 : env;
-    if ((nwv == 8 || nwv == 16) && d_ff % (16 * nwv) == 0) return env;
-    return 4;
-}
+// every other variant: two per CU, 16 splits.
+static int ffn_dw_occ(bool stored, bool bf16) { return stored && !bf16 ? 3 : 2; }
 // most token splits any variant uses for a hidden width: a narrow FFN (the PNR / OSCC recipe's d_ff = 256: four hidden groups) needs more of them
 // to fill the chip; its slabs are small
 static int ffn_dw_max_splits(int d_ff) { return d_ff <= 512 ? 48 : 32; }
-// EGX_FFN_DW_SPLIT2=0: the one-workgroup-for-both-gradients kernel of rounds 3-4 in f32s (tuning aid)
-static bool ffn_dw_split2() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_FFN_DW_SPLIT2"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
-}
 static int ffn_dw_splits(int nkb, int occ, int d_ff, bool split2) {
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("EGX_FFN_DW_SPLITS"); env = e ? atoi(e) : 0; }     // tuning aid
     const int cap = ffn_dw_max_splits(d_ff);
-    if (env > 0) return min(nkb, min(env, cap));
     int sp = occ == 3 ? 24 : 16;
     // f32s (one grid of dW1 and dW2 workgroups, four per CU): aim at ~1024 workgroups. d_ff = 256: 1663 -> 1595 us per PNR step at 24 splits,
     // measured; 2048-wide FFNs keep 16 (12 and 24 both slower on C2)
@@ -876,81 +789,42 @@ static int launch_ffn_dw(FfnDwParams p, hipStream_t st) {
     }
     dim3 grid(p.d_ff / (64 * HT), p.splits);
     timing_begin(TIMER_FFN_DW, st);
-    if (p.hs && CM == CM_BF16 && p.xg_planes && ffn_dw_ring()) {
-        const int nw = ffn_dw_bf16_waves(p.d_ff);
-        const int nd = nw == 82 ? 2 : 3, nwv = nw == 82 ? 8 : nw;
-        const int ring_bytes = nd * (2 * 32 * 256 + nwv * 4 * 512);
+    if (!p.hs) {
+        hipLaunchKernelGGL((ffn_dw_kernel<CM, HT>), grid, dim3(256), lds, st, p);
+    } else if (CM == CM_BF16 && p.xg_planes) {
+        const int ring_bytes = 3 * (2 * 32 * 256 + 4 * 4 * 512);
         static bool attr3_set = false;
         if (!attr3_set) {
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_bf16_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (2 * 32 * 256 + 4 * 4 * 512)));
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_bf16_ring8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (2 * 32 * 256 + 8 * 4 * 512)));
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_bf16_ring8d2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (2 * 32 * 256 + 8 * 4 * 512)));
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_bf16_ring16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (2 * 32 * 256 + 16 * 4 * 512)));
+            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_bf16_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes));
             attr3_set = true;
         }
-        const dim3 g2(p.d_ff / (16 * nwv), p.splits);
-        if (nw == 16) hipLaunchKernelGGL(ffn_dw_bf16_ring16_kernel, g2, dim3(1024), ring_bytes, st, p);
-        else if (nw == 82) hipLaunchKernelGGL(ffn_dw_bf16_ring8d2_kernel, g2, dim3(512), ring_bytes, st, p);
-        else if (nw == 8) hipLaunchKernelGGL(ffn_dw_bf16_ring8_kernel, g2, dim3(512), ring_bytes, st, p);
-        else hipLaunchKernelGGL(ffn_dw_bf16_ring_kernel, grid, dim3(256), ring_bytes, st, p);
-    } else if (p.hs) {
-        EGX_CHECK(!p.xg_planes || CM == CM_SPLIT, "ffn_dw: bf16 operand planes are read by the LDS-ring kernel only (unset EGX_FFN_DW_RING)");
-        EGX_CHECK(CM != CM_SPLIT || p.xg_planes, "ffn_dw: the split-mode stored-operand kernel reads pre-split x1 / g planes");
-        const int occ = CM == CM_SPLIT ? 2 : ffn_dw_occ(true, CM == CM_BF16);
-        if (CM == CM_SPLIT) lds = (size_t)2 * 3 * 32 * 144 * sizeof(unsigned short);
-        // + per-wave staging of the H / dH tiles (4 waves x 2 tensors x parts x 1 KB)
+        hipLaunchKernelGGL(ffn_dw_bf16_ring_kernel, grid, dim3(256), ring_bytes, st, p);
+    } else if constexpr (CM == CM_SPLIT) {
+        // f32s: one grid of dW1 and dW2 workgroups. EIGHT waves per workgroup share one staged operand image (hidden group of 128). With four, the
+        // launch moved 805 MB through the CUs' address paths (24 KB of x1 / g planes + 8 KB of H / dH tiles per K-block and workgroup), 590 MB of
+        // it the planes that every hidden group of a token range re-reads; with eight 510 MB and half the staging instructions per MFMA.
+        // 76.5 -> 64.0 us, step 371 -> 360 us (three same-box pairs, profiles/r06_ab_ffn_dw_w8.txt).
+        EGX_CHECK(p.xg_planes, "ffn_dw: the split-mode stored-operand kernel reads pre-split x1 / g planes");
+        lds = (size_t)3 * 32 * 144 * sizeof(unsigned short);       // one operand image: three bf16 planes
+        static bool attr5_set = false;
+        if (!attr5_set) {
+            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            attr5_set = true;
+        }
+        hipLaunchKernelGGL(ffn_dw_split2w8_kernel, dim3(p.d_ff / 128, grid.y, 2), dim3(512), lds, st, p);
+    } else {
+        // calls without operand planes (packed feature rows, the stand-alone entry point): fp32 at three workgroups per CU on a single LDS
+        // buffer, bf16 at two with per-wave staging of the H / dH tiles (4 waves x 2 tensors x 1 KB)
+        EGX_CHECK(!p.xg_planes, "ffn_dw: bf16 operand planes are read by the LDS-ring kernel only");
+        constexpr int OCC = CM == CM_BF16 ? 2 : 3;
         const size_t tstage_bytes = CM == CM_BF16 ? (size_t)4 * 2 * 1024 : 0;
         static bool attr2_set = false;
         if (!attr2_set) {
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_stored_kernel<CM, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + tstage_bytes)));
-            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_stored_kernel<CM, 3>),
+            EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_stored_kernel<CM, OCC>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + tstage_bytes)));
             attr2_set = true;
         }
-        if (CM == CM_SPLIT && ffn_dw_split2()) {
-            static bool attr4_set = false;
-            if (!attr4_set) {
-                EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds / 2)));
-                attr4_set = true;
-            }
-            // Round 6: EIGHT waves per workgroup share one staged operand image (hidden group of 128). With four, the launch moved 805 MB through
-            // the CUs' address paths (24 KB of x1 / g planes + 8 KB of H / dH tiles per K-block and workgroup), 590 MB of it the planes that every
-            // hidden group of a token range re-reads; with eight 510 MB and half the staging instructions per MFMA. 76.5 -> 64.0 us,
-            // step 371 -> 360 us (three same-box pairs, profiles/r06_ab_ffn_dw_w8.txt); sixteen waves (one workgroup per CU) measured the same as
-            // eight. EGX_FFN_DW_W8 = 0 | 16 selects the four- / sixteen-wave grids (tuning aid).
-            static const int w8 = [] { const char* e = getenv("EGX_FFN_DW_W8"); return e ? atoi(e) : 8; }();
-            if ((w8 == 42 || w8 == 82) && p.d_ff % 256 == 0) {      // NH = 2 variants (42: four waves, 82: eight)
-                static bool attr7_set = false;
-                if (!attr7_set) {
-                    EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds / 2)));
-                    EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2w8h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds / 2)));
-                    attr7_set = true;
-                }
-                if (w8 == 42) hipLaunchKernelGGL(ffn_dw_split2h2_kernel, dim3(p.d_ff / 128, grid.y, 2), dim3(256), lds / 2, st, p);
-                else hipLaunchKernelGGL(ffn_dw_split2w8h2_kernel, dim3(p.d_ff / 256, grid.y, 2), dim3(512), lds / 2, st, p);
-            } else
-            if (w8 == 16 && p.d_ff % 256 == 0) {
-                static bool attr6_set = false;
-                if (!attr6_set) {
-                    EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2w16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds / 2)));
-                    attr6_set = true;
-                }
-                hipLaunchKernelGGL(ffn_dw_split2w16_kernel, dim3(p.d_ff / 256, grid.y, 2), dim3(1024), lds / 2, st, p);
-            } else
-            if (w8 && p.d_ff % 128 == 0) {
-                static bool attr5_set = false;
-                if (!attr5_set) {
-                    EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_dw_split2w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds / 2)));
-                    attr5_set = true;
-                }
-                hipLaunchKernelGGL(ffn_dw_split2w8_kernel, dim3(p.d_ff / 128, grid.y, 2), dim3(512), lds / 2, st, p);
-            } else
-            hipLaunchKernelGGL(ffn_dw_split2_kernel, dim3(grid.x, grid.y, 2), dim3(256), lds / 2, st, p);
-        } else if (occ == 3) hipLaunchKernelGGL((ffn_dw_stored_kernel<CM, 3>), grid, dim3(256), lds / 2 + tstage_bytes, st, p);
-        else hipLaunchKernelGGL((ffn_dw_stored_kernel<CM, 2>), grid, dim3(256), lds + tstage_bytes, st, p);
-    } else {
-        hipLaunchKernelGGL((ffn_dw_kernel<CM, HT>), grid, dim3(256), lds, st, p);
+        hipLaunchKernelGGL((ffn_dw_stored_kernel<CM, OCC>), grid, dim3(256), (OCC == 3 ? lds / 2 : lds) + tstage_bytes, st, p);
     }
     timing_end(TIMER_FFN_DW, st);
     EGX_LAUNCH_CHECK();
@@ -964,7 +838,7 @@ int ffn_dw(FfnDwParams p, int compute, float* dW1, float* db1, float* dW2, void*
     EGX_CHECK(!p.hs == !p.dhs, "ffn_dw: H and dH tiles must be given together");
     int nkb = p.hs ? (p.B * FUSED_TOK_TILES + 1) / 2 : (p.N + 31) / 32;
     int splits = ffn_dw_splits((p.N + 31) / 32, (compute == CM_SPLIT && p.hs) ? 2 : ffn_dw_occ(p.hs != nullptr, compute == CM_BF16), p.d_ff,
-                               compute == CM_SPLIT && p.hs && p.xg_planes && ffn_dw_split2());
+                               compute == CM_SPLIT && p.hs && p.xg_planes);
     p.splits = splits;
     p.kb_per_split = cdiv(nkb, splits);
     p.splits = cdiv(nkb, p.kb_per_split);
@@ -989,16 +863,6 @@ int ffn_dw(FfnDwParams p, int compute, float* dW1, float* db1, float* dW2, void*
     }
     if (defer) return 0;
     return ffn_dw_reduce(a, rp, deterministic, st);
-}
-
-void small_dw_tail_init(SmallDwTail& t, const SlabReduce& red, const ReducePartialsParams* rp) {
-    memset(&t, 0, sizeof(t));
-    t.red = red;
-    size_t total = 0;
-    for (int k = 0; k < red.narr; ++k) total += red.n[k];
-    t.slab_blocks = (unsigned)((total / 4 + 255) / 256);
-    t.chunks = 1;
-    if (rp) { t.rp = *rp; t.chunks = partial_chunks(rp->B); t.rp_units = cdiv(rp->P, 64) * t.chunks; }
 }
 
 int ffn_dw_reduce(const SlabReduce& a, const ReducePartialsParams* rp, bool deterministic, hipStream_t st) {
@@ -1054,26 +918,13 @@ __device__ unsigned long long g_sstamps[16];
 #define SSTAMP(i) do { } while (0)
 #endif
 int debug_read_sstamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sstamps), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : 1; }
-template <int CM, bool TAIL>
-__global__ __launch_bounds__(256) void small_dw_kernel(SmallDwParams p, SmallDwTail tl) {
+// (The second argument is unused: until 3b19ffd a variant of this kernel summed the FFN slabs and the partial rows ahead of its own work; tail_reduce
+// does that now in every mode. It stays in the signature so that the kernel's arguments are what they were)
+template <int CM>
+__global__ __launch_bounds__(256) void small_dw_kernel(SmallDwParams p, SmallDwTail) {
     constexpr int LDG = 64 + 4, LDXS = 128 + 4;
     __shared__ __attribute__((aligned(16))) float lds[2 * (32 * LDG + 32 * LDXS)];
     SSTAMP(0);
-    if constexpr (TAIL) {
-        // egx_config.advance_seed == 2: this is the backward's last launch and reads no dropout key: the step's seed advances here
-        if (tl.seed_advance && blockIdx.x == 0 && threadIdx.x == 0)
-            *tl.seed_advance = *tl.seed_advance * 6364136223846793005ull + 1442695040888963407ull;
-        // the next forward's first weight streams -> Infinity Cache (TouchList); consumed right away: this launch starts with reductions anyway
-        if (tl.touch.n) touch_sink(touch_lines<256>(tl.touch, blockIdx.x, gridDim.x, threadIdx.x));
-        // The FFN weight-gradient slabs and the per-clip partial rows are summed here, 1 / grid of the units per workgroup, before
-        // the workgroup's own GEMM work: the reduction launch of its own cost 14 us of mostly exposed latency. (As EXTRA
-        // workgroups of this launch the same units were limited to three per CU by its LDS footprint: +60 us.)
-        for (unsigned u = blockIdx.x; u < tl.slab_blocks; u += gridDim.x) reduce_slabs_block(tl.red, u);
-        for (int u = blockIdx.x; u < tl.rp_units; u += gridDim.x) {
-            reduce_partials_block(tl.rp, u / tl.chunks, u % tl.chunks, tl.chunks);
-            __syncthreads();
-        }
-    }
     SSTAMP(1);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1250,7 +1101,7 @@ __global__ __launch_bounds__(256) void small_dw_reduce_kernel(SmallDwParams p) {
     }
 }
 
-int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs, size_t slab_bytes, const SmallDwTail* tail, bool reduce_here) {
+int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs, size_t slab_bytes, bool reduce_here) {
     int items[SMALL_DW_MAX], nkb[SMALL_DW_MAX], total_items = 0;
     for (int i = 0; i < p.n; ++i) {
         EGX_CHECK(p.pr[i].R % 4 == 0 && p.pr[i].C % 4 == 0 && p.pr[i].ldg % 4 == 0 && p.pr[i].ldx % 4 == 0,
@@ -1268,7 +1119,6 @@ int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs, size_t 
         for (int i = 0; i < p.n; ++i) blocks += items[i] * cdiv(nkb[i], per);
         if (blocks <= 512 || per >= 4096) break;
     }
-    if (const char* e = getenv("EGX_SMALL_DW_PER")) per = max(1, atoi(e));     // tuning aid
     p.per = per;
     int blocks = 0;
     for (int i = 0; i < p.n; ++i) {
@@ -1282,17 +1132,10 @@ int small_dw(SmallDwParams& p, int compute, hipStream_t st, void* slabs, size_t 
                   (size_t)blocks * 64 * 128 * sizeof(float), slab_bytes);
         p.slabs = (float*)slabs;
     }
-    if (tail) {
-        EGX_CHECK(!p.slabs, "small_dw: the reduction tail rides only in the atomic (non-deterministic) variant");
-        if (compute == CM_BF16) hipLaunchKernelGGL((small_dw_kernel<CM_BF16, true>), dim3(blocks), dim3(256), 0, st, p, *tail);
-        else if (compute == CM_SPLIT) hipLaunchKernelGGL((small_dw_kernel<CM_SPLIT, true>), dim3(blocks), dim3(256), 0, st, p, *tail);
-        else hipLaunchKernelGGL((small_dw_kernel<CM_F32, true>), dim3(blocks), dim3(256), 0, st, p, *tail);
-    } else {
-        static SmallDwTail none;
-        if (compute == CM_BF16) hipLaunchKernelGGL((small_dw_kernel<CM_BF16, false>), dim3(blocks), dim3(256), 0, st, p, none);
-        else if (compute == CM_SPLIT) hipLaunchKernelGGL((small_dw_kernel<CM_SPLIT, false>), dim3(blocks), dim3(256), 0, st, p, none);
-        else hipLaunchKernelGGL((small_dw_kernel<CM_F32, false>), dim3(blocks), dim3(256), 0, st, p, none);
-    }
+    static SmallDwTail none;
+    if (compute == CM_BF16) hipLaunchKernelGGL((small_dw_kernel<CM_BF16>), dim3(blocks), dim3(256), 0, st, p, none);
+    else if (compute == CM_SPLIT) hipLaunchKernelGGL((small_dw_kernel<CM_SPLIT>), dim3(blocks), dim3(256), 0, st, p, none);
+    else hipLaunchKernelGGL((small_dw_kernel<CM_F32>), dim3(blocks), dim3(256), 0, st, p, none);
     if (p.slabs && reduce_here) hipLaunchKernelGGL(small_dw_reduce_kernel, dim3(total_items * 8), dim3(256), 0, st, p);
     EGX_LAUNCH_CHECK();
     return 0;
@@ -1917,124 +1760,6 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) w3r[i] = load_w<CM>(w.lin1_wtp, i, nhb, hb0, lane);
             }
-            bool ffn_done = false;
-            if constexpr (CM == CM_BF16 && EGX_FFN_PIPE_BWD && !SLICED) {
-                // bf16: the loop software-pipelined across hidden blocks as in the forward (fused.hip): the mask / pack / dH-tile work of block `it` is
-                // issued in slices behind the MFMAs of one weight fragment each — GEMM1 of block it + 1 (into a second accumulator set) and GEMM2 of
-                // block it - 1 (from the operand fragments the previous block left). One ring of eight fragment slots (w2r) serves both weight streams.
-                ffn_done = true;
-                f32x4 dc[2][NT], dc2[2][NT];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) dc[i][t] = f32x4{0, 0, 0, 0};
-                {
-                    const int hb1 = hb_of(1 < nit ? 1 : 0);
-#pragma unroll
-                    for (int kb = 0; kb < FD / 32; ++kb)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            pin(w2r[i][kb]);
-                            Frag<CM> a2 = w_frag<CM>(w2r[i][kb]);
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) mma<CM>(dc[i][t], a2, gb[kb][t]);
-                            __builtin_amdgcn_sched_barrier(0);
-                            w2r[i][kb] = load_w<CM>(w.lin2_wtp, hb1 * 2 + i, FD / 32, kb, lane);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                }
-                Frag<CM> dqA[NT], dqB[NT];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) dqA[t] = chain_frag<CM>(f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0});
-                auto step = [&](int it, f32x4 (&dcur)[2][NT], f32x4 (&dnext)[2][NT], const Frag<CM> (&dq_prev)[NT], Frag<CM> (&dq)[NT]) {
-                    const int hb = hb_of(it);
-                    const int hbn = hb_of(it + 1 < nit ? it + 1 : it);
-                    const int hb2 = hb_of(it + 2 < nit ? it + 2 : nit - 1);
-                    const int hbp = hb_of(it > 0 ? it - 1 : 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    const uint32_t bits = relu_word;
-                    __builtin_amdgcn_sched_barrier(0);
-                    relu_word = relu_bits[(size_t)hbn * 64];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) dnext[i][t] = f32x4{0, 0, 0, 0};
-                    static_assert(3 * NT <= 16, "epilogue slices");
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        if (k < 8) {
-                            const int kb = k >> 1, i = k & 1;
-                            pin(w2r[i][kb]);
-                            Frag<CM> a2 = w_frag<CM>(w2r[i][kb]);
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) mma<CM>(dnext[i][t], a2, gb[kb][t]);
-#if EGX_FFN_PIPE_BWD_RING == 16
-                            w2r[i][kb] = load_w<CM>(w.lin2_wtp, hb2 * 2 + i, FD / 32, kb, lane);
-#else
-                            w2r[i][kb] = load_w<CM>(w.lin1_wtp, k, nhb, hbp, lane);             // slot k: W1^T fragment k of the previous block, needed eight steps on
-#endif
-                        } else {
-                            const int j = k - 8, i = j & 1, kb = j >> 1;
-#if EGX_FFN_PIPE_BWD_RING == 16
-                            pin(w3r[j]);
-                            Frag<CM> a = w_frag<CM>(w3r[j]);
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) mma<CM>(dxa[j][t], a, dq_prev[t]);
-                            w3r[j] = load_w<CM>(w.lin1_wtp, j, nhb, hb, lane);      // this block's W1^T rows: GEMM2 of the next iteration
-#else
-                            pin(w2r[i][kb]);
-                            Frag<CM> a = w_frag<CM>(w2r[i][kb]);
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) mma<CM>(dxa[j][t], a, dq_prev[t]);
-                            w2r[i][kb] = load_w<CM>(w.lin2_wtp, hb2 * 2 + i, FD / 32, kb, lane);  // slot j: W2^T fragment j of the block after next
-#endif
-                        }
-                        if (k < 2 * NT) {           // alive bits -> masks of one 16 x 16 tile (see the loop below)
-                            const int i = k / NT, t = k % NT;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const int kk = (i * NT + t) * 4 + e;
-                                const int32_t m = ((int32_t)(bits << (31 - kk))) >> 31;
-                                dcur[i][t][e] = __uint_as_float(__float_as_uint(dcur[i][t][e]) & (uint32_t)m);
-                            }
-                        } else if (k < 3 * NT) {    // operand fragment + dH tile of a token tile
-                            const int t = k - 2 * NT;
-                            dq[t] = chain_frag<CM>(dcur[0][t], dcur[1][t]);
-                            if constexpr (CM == CM_BF16) {
-                                const u32x4 u = __builtin_bit_cast(u32x4, dq[t].v);
-                                store_hid_tile_bf16(dhid_base + (size_t)hb * 2 * (HTILE_ELEMS * ESZ) + (size_t)t * nht * (HTILE_ELEMS * ESZ), u, lane, S - t * 16);
-                            }
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                };
-                auto last_gemm2 = [&](const Frag<CM> (&dq_last)[NT]) {      // (its W1^T rows are requested here: one exposed round trip per layer)
-#if EGX_FFN_PIPE_BWD_RING != 16
-                    const int hbl = hb_of(nit - 1);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) w3r[i] = load_w<CM>(w.lin1_wtp, i, nhb, hbl, lane);
-#endif
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        Frag<CM> a = w_frag<CM>(w3r[i]);
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) mma<CM>(dxa[i][t], a, dq_last[t]);
-                    }
-                };
-                int it = 0;
-                for (; it + 1 < nit; it += 2) {
-                    step(it, dc, dc2, dqA, dqB);
-                    step(it + 1, dc2, dc, dqB, dqA);
-                }
-                if (it < nit) {
-                    step(it, dc, dc2, dqA, dqB);
-                    last_gemm2(dqB);
-                } else {
-                    last_gemm2(dqA);
-                }
-            }
-            if (!ffn_done)
             for (int it = 0; it < nit; ++it) {
                 const int hb = hb_of(it);
                 const int hbn = hb_of(it + 1 < nit ? it + 1 : it);     // the last block refills itself (never used)

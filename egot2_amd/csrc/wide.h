@@ -24,10 +24,9 @@ struct WideGemmParams {
     const bf16_t* mask = nullptr; int ldm = 0; float mask_scale = 1.f;       // C = mask[m][n] != 0 ? C * mask_scale : 0
     float* colsum = nullptr;      // optional [wide_gemm_nt_colsum_rows(M, N)][N]: column sums per 64 output rows (bias gradients)
     int accumulate = 0;           // TN: C += result (parameter gradients)
-    int tn_max_splits = 0;        // TN: upper bound on the split-K count (0: the cost model's choice). 1 with accumulate == 0 and a dense C
-                                  // (ldc == N) writes C directly: no slab, no reduction (launches that need no parallelism: side stream)
+    int tn_max_splits = 0;        // unused (until 3b19ffd: an upper bound on the TN split-K count); kept so that the kernels' argument layout stays
     const void* zero_page = nullptr;   // >= 256 zero bytes in device memory (source of out-of-range operand rows)
-    int epi_lds = 0;              // NT: set by wide_gemm_nt (EGX_WIDE_EPI): epilogue through LDS
+    int epi_lds = 0;              // set by wide_gemm_nt / _tn (always 2): epilogue through LDS
 };
 
 // scratch for the TN split-K slabs

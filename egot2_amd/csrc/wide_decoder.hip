@@ -928,9 +928,9 @@ SideStream& side_stream() {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) dev = 0;
     std::call_once(once[dev], [dev]() {
         SideStream& T = S[dev];
-        const char* e = getenv("EGX_DEC_SIDE");
-        if (!(e && e[0] == '0') && hipStreamCreateWithFlags(&T.s, hipStreamNonBlocking) == hipSuccess) {
-            T.on = true; T.on_captured = e && e[0] == '2';
+        const int mode = tuning().dec_side;
+        if (mode != 0 && hipStreamCreateWithFlags(&T.s, hipStreamNonBlocking) == hipSuccess) {
+            T.on = true; T.on_captured = mode == 2;
             for (auto& v : T.ev) if (hipEventCreateWithFlags(&v, hipEventDisableTiming) != hipSuccess) T.on = false;
             for (auto& v : T.kv_ev) if (hipEventCreateWithFlags(&v, hipEventDisableTiming) != hipSuccess) T.on = false;
         }
@@ -1235,11 +1235,9 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
     // by ONE launch at the end (every target is a different parameter: concurrent sums never meet)
     WideRowReduceBatch rrb;
     size_t row_cur = 0;
-    static int row_env = -2;
-    if (row_env == -2) { const char* e = getenv("EGX_ROW_DEFER"); row_env = e ? atoi(e) : 1; }
     auto row_region = [&](size_t need) -> void* {
         need = align_up(need, 256);
-        if (row_env == 0 || row_cur + need > pl.rowpart_bytes) return nullptr;
+        if (row_cur + need > pl.rowpart_bytes) return nullptr;
         void* r = at<char>(scratch, pl.rowpart) + row_cur;
         row_cur += need;
         return r;
@@ -1250,8 +1248,7 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
     // side stream already hides these GEMMs beside the target-token chain and grouping them at the end measured 1.4 % slower (C5 HOI
     // 3.80 -> 3.86 ms); captured, C5 HHI 2.42 -> 2.26 ms (profiles/r05_dec_group.txt). EGX_DEC_GROUP=0 / 1 forces either.
     WideTnQueue tq;
-    static int group_env = -2;
-    if (group_env == -2) { const char* e = getenv("EGX_DEC_GROUP"); group_env = e ? atoi(e) : -1; }
+    const int group_env = tuning().dec_group;
     const bool grouped = group_env >= 0 ? group_env != 0 : !side;
     // (ungrouped: enqueued on the side stream; the caller forks first)
     auto dw_tn = [&](const bf16_t* dy, int ldy, const bf16_t* x, int ldx, float* dW, int n_out, int k_in, int tokens_k) -> int {
@@ -1259,22 +1256,18 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
         WideGemmParams t;
         t.A = dy; t.B = x; t.M = n_out; t.N = k_in; t.K = tokens_k; t.lda = ldy; t.ldb = ldx;
         t.Cf = dW; t.ldc = k_in; t.zero_page = zero;
-        // EGX_DEC_DIRECT=1 (tuning aid, off): over <= 1024 target rows ONE split
-        // straight into dW (no slab, no reduction), at most eight over the B * S memory rows: removes the batched slab reduction
-        // (55-73 us, 230 MB per step) but lengthens the side stream - same-box A/B: C5 HOI 3.95 = 3.95 ms, C5 HHI 2.46 -> 2.62 ms
-        static int direct = -1;
-        if (direct < 0) { const char* e = getenv("EGX_DEC_DIRECT"); direct = e ? atoi(e) : 0; }
+        // (Writing straight into dW with one split over <= 1024 target rows - no slab, no batched reduction of 55-73 us - lengthened the side
+        // stream: same-box C5 HOI 3.95 = 3.95 ms, C5 HHI 2.46 -> 2.62 ms. That variant last existed at 3b19ffd.)
         // a target inside the buffer this call has just zero-filled is overwritten (saves the read of the += ), anything else keeps
         // the += contract of the header
         const char* zb = (const char*)zero_buf;
         const bool zeroed = zb && (const char*)dW >= zb && (const char*)(dW + (size_t)n_out * k_in) <= zb + zero_bytes;
         t.accumulate = zeroed ? 0 : 1;
-        t.tn_max_splits = !(direct && zeroed) ? 0 : (tokens_k <= 1024 ? 1 : (tokens_k <= 4096 ? 0 : 8));
         const size_t need = align_up(wide_gemm_tn_scratch(n_out, k_in, tokens_k), 256);
         EGX_CHECK(slab_cur + need <= pl.slab_all_bytes, "decoder backward: slab region exhausted");
         void* region = at<char>(scratch, pl.slab_all) + slab_cur;
         slab_cur += need;
-        if (grouped && !t.tn_max_splits) return wide_tn_queue_add(tq, t, region, st, &rb);
+        if (grouped) return wide_tn_queue_add(tq, t, region, st, &rb);
         return wide_gemm_tn(t, region, sd, &rb);
     };
     auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int M, int N, int K, float* Cf, bf16_t* Cb, const float* residual,

@@ -165,8 +165,7 @@ template <int TJ, int NI = 4>
 __host__ __device__ __forceinline__ constexpr int epi_lds_f32_bytes() { return (TJ >= 4 ? TJ * 4 : 16) * epi_ldf<NI>(); }      // fp32 rounds only (TN slabs)
 template <int TJ, int NI = 4>
 __host__ __device__ __forceinline__ constexpr int epi_lds_bytes() { return (TJ * 16) * epi_ldb<NI>() > epi_lds_f32_bytes<TJ, NI>() ? (TJ * 16) * epi_ldb<NI>() : epi_lds_f32_bytes<TJ, NI>(); }
-// R16: rounds of one 16-row tile through a region of 16 rows (the persistent kernel's epilogue beside its K-loop stages)
-template <int TJ, int NI = 4, bool R16 = false>
+template <int TJ, int NI = 4>
 __device__ __forceinline__ void nt_epilogue_lds(const WideGemmParams& p, f32x4 (&acc)[NI][TJ], int mb, int nb, int prow0, int r, int g, int lane, unsigned char* region) {
     constexpr int EPI_LDB = epi_ldb<NI>(), EPI_LDF = epi_ldf<NI>();
     // phase A (accumulator layout): bias, ReLU, dropout
@@ -193,7 +192,9 @@ __device__ __forceinline__ void nt_epilogue_lds(const WideGemmParams& p, f32x4 (
     if (!p.Cf && !p.residual && !p.mask && !p.colsum) {
         // bf16 out only: the whole sub-tile at once
         // a row is NI * 2 pieces of 16 bytes: RPI rows per instruction (NI = 3: 10 rows, four lanes idle)
-        constexpr int LPR = NI * 2, RPI = 64 / LPR, JR = R16 ? 1 : TJ, WR = JR * 16;      // JR row tiles per round
+        constexpr int LPR = NI * 2, RPI = 64 / LPR, JR = TJ, WR = JR * 16;
+        // (JR row tiles per round: always all of them since the persistent kernel, which went through a 16-row region, left at 3b19ffd. The loop
+        // over rounds keeps its shape because writing it out moves the register allocation of the TN kernels)
         const int rr = lane / LPR, ch = lane - rr * LPR, n = nb + ch * 8;
 #pragma unroll
         for (int h = 0; h < TJ / JR; ++h) {
@@ -478,12 +479,10 @@ int debug_read_ppstamps(unsigned long long*) { return 1; }
 // 256-column tiles leave the chip's last round half empty (N = 768: 384 tiles = 1.5 rounds, 512 tiles of 192 columns = 2 full
 // rounds of 0.75 the work). Its W half 1 is one tile (P2 / P3: 8 MFMAs), staged by one instruction per wave in P4: seven LDS-DMA
 // loads per K tile, so the uniform wait is vmcnt(8) - any five consecutive phases issue at least eight.
-// PERSIST: the launch has one workgroup per CU and each walks tiles id, id + grid, ...: the next tile's prologue (14 LDS-DMA loads
-// into the K-loop stages) is issued BEFORE the epilogue of the finished tile, which then goes through a small LDS region of its
-// own behind the stages (rounds of 16 rows) - the 3.5k-cycle prologue and part of the store drain disappear under the epilogue.
-// bytes of a wave's 16-row epilogue region in the persistent kernel: bf16 rows only for the 256-column tile (its fp32 rounds do not fit)
-template <int NWT> __host__ __device__ __forceinline__ constexpr int pp_region_bytes() { return NWT == 4 ? 16 * epi_ldb<4>() : epi_lds_f32_bytes<1, NWT>(); }
-template <int NWT, bool PERSIST>
+// (A persistent variant - one workgroup per CU walking the tiles, the next tile's prologue issued ahead of the epilogue - measured slower: with the
+// uniform vmcnt(10) waits the next tile's first phases wait for the epilogue's stores anyway; same-box C4 9.31 ms without, 9.61 ms with. It last
+// existed at 3b19ffd. Worth revisiting with exact store counts)
+template <int NWT>
 __global__ __launch_bounds__(512, 1) void wide_gemm_nt_pp_kernel(WideGemmParams p, int ntM, int ntN) {
     constexpr int BM = 256, BN = 64 * NWT, WC = 16 * NWT, SB = (BM + BN) * TBK * 2, WOFF = BM * TBK * 2;
     constexpr int H1 = NWT - 2;                  // tiles of W half 1 (half 0: tiles 0, 1)
@@ -550,13 +549,11 @@ __global__ __launch_bounds__(512, 1) void wide_gemm_nt_pp_kernel(WideGemmParams 
         stage_x(1, 0, 2); stage_w(1, 0); stage_w(1, 1);
     };
     prologue();
-    for (;;) {
 #pragma unroll
     for (int i = 0; i < NWT; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-    EGX_PP_WAIT();          // all but the first four (X quarters 0, 2 and W half 0 of tile 0) may still be in flight (after an
-                            // epilogue its stores are younger than the prologue: the wait covers some of them too - safe)
+    EGX_PP_WAIT();          // all but the first four (X quarters 0, 2 and W half 0 of tile 0) may still be in flight
     ring_barrier();
     PPSTAMP(1);
     if (wr == 1) ring_barrier();        // the stagger: waves 4-7 run one barrier behind
@@ -605,23 +602,11 @@ __global__ __launch_bounds__(512, 1) void wide_gemm_nt_pp_kernel(WideGemmParams 
     if (wr == 0) ring_barrier();        // balance the stagger
     EGX_WAIT_VM(0);                     // no LDS-DMA may outlive the workgroup (the over-fetched K tiles; they are never read)
     PPSTAMP(3);
-    if constexpr (PERSIST) {
-        ring_barrier();     // every wave's LDS-DMA has landed, every fragment read is over: the stages may be refilled
-        const int mc = m0, nc = n0, nid = id + (int)gridDim.x;
-        const bool more = nid < ntiles;
-        if (more) { set_tile(nid); prologue(); }
-        nt_epilogue_lds<8, NWT, true>(p, acc, mc + wr * 128, nc + wn * WC, mc / 64 + wr * 2, r, g, lane, smem + 2 * SB + wave * pp_region_bytes<NWT>());
-        if (!more) break;
-        id = nid;
-    } else {
-        if (NWT != 4 || nt_epilogue_simple<8, NWT>(p)) {
-            ring_barrier();     // every wave's LDS-DMA has landed (each waited for its own above): the stages are free for the wave regions
-            nt_epilogue_lds<8, NWT>(p, acc, m0 + wr * 128, n0 + wn * WC, m0 / 64 + wr * 2, r, g, lane, smem + wave * epi_lds_bytes<8, NWT>());
-        } else if constexpr (NWT == 4) {
-            nt_epilogue<8>(p, acc, m0 + wr * 128, n0 + wn * 64, m0 / 64 + wr * 2, r, g);
-        }
-        break;
-    }
+    if (NWT != 4 || nt_epilogue_simple<8, NWT>(p)) {
+        ring_barrier();     // every wave's LDS-DMA has landed (each waited for its own above): the stages are free for the wave regions
+        nt_epilogue_lds<8, NWT>(p, acc, m0 + wr * 128, n0 + wn * WC, m0 / 64 + wr * 2, r, g, lane, smem + wave * epi_lds_bytes<8, NWT>());
+    } else if constexpr (NWT == 4) {
+        nt_epilogue<8>(p, acc, m0 + wr * 128, n0 + wn * 64, m0 / 64 + wr * 2, r, g);
     }
 #undef EGX_PP_PHASE_TAIL
 #undef EGX_PP_MFMA
@@ -633,56 +618,30 @@ __global__ __launch_bounds__(512, 1) void wide_gemm_nt_pp_kernel(WideGemmParams 
 #endif
 }
 
-// persistent launch (one workgroup per CU walking the tiles): when the output needs more than one round of tiles and the
-// epilogue's 16-row regions fit behind the two stages (fp32 rows of the 256-column tile do not: 131 072 + 8 x 4 352 > 160 KB)
-// OFF by default (EGX_WIDE_PERSIST=1 enables it): with the uniform vmcnt(10) waits the first phases of the next tile wait for
-// the epilogue's stores anyway, and the 16-row epilogue rounds cost more than the hidden prologue saves - same-box C4 9.31 ms
-// without, 9.61 ms with; gemm_bench +4 % / -2 % / -2.5 % / +3 %. Worth revisiting with exact store counts.
-static int pp_persist_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_WIDE_PERSIST"); v = e ? atoi(e) : 0; }
-    return v;
-}
-template <int NWT, bool PERSIST>
-static int launch_nt_pp_impl(const WideGemmParams& p, hipStream_t st) {
+template <int NWT>
+static int launch_nt_pp(const WideGemmParams& p, hipStream_t st) {
     constexpr int BN = 64 * NWT;
     constexpr int STAGES = 2 * (256 + BN) * TBK * 2, EPI = 8 * epi_lds_bytes<8, NWT>();
-    constexpr int LDS = PERSIST ? STAGES + 8 * pp_region_bytes<NWT>() : (STAGES > EPI ? STAGES : EPI);
+    constexpr int LDS = STAGES > EPI ? STAGES : EPI;
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static bool attr = false;
     if (!attr) {
-        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_gemm_nt_pp_kernel<NWT, PERSIST>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_gemm_nt_pp_kernel<NWT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr = true;
     }
     const int ntM = cdiv(p.M, 256), ntN = cdiv(p.N, BN);
-    int grid = ntM * ntN;
-    if (PERSIST) {
-        static int cus = 0;
-        if (!cus) { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; if (cus < 8) cus = 256; cus &= ~7; }
-        if (grid > cus) grid = cus;      // a multiple of 8: the workgroup -> XCD mapping of xcd_tile() stays valid for id + k * grid
-    }
     timing_begin(TIMER_WIDE_GEMM, st);
-    hipLaunchKernelGGL((wide_gemm_nt_pp_kernel<NWT, PERSIST>), dim3(grid), dim3(512), LDS, st, p, ntM, ntN);
+    hipLaunchKernelGGL((wide_gemm_nt_pp_kernel<NWT>), dim3(ntM * ntN), dim3(512), LDS, st, p, ntM, ntN);
     timing_end(TIMER_WIDE_GEMM, st);
     EGX_LAUNCH_CHECK();
     return 0;
 }
-template <int NWT>
-static int launch_nt_pp(const WideGemmParams& p, hipStream_t st) {
-    const long tiles = (long)cdiv(p.M, 256) * cdiv(p.N, 64 * NWT);
-    const bool fp32_rounds = p.Cf || p.residual || p.mask || p.colsum;
-    if (pp_persist_mode() && tiles > 256 && p.epi_lds && (p.N & 7) == 0 && !p.colsum && !(NWT == 4 && fp32_rounds))
-        return launch_nt_pp_impl<NWT, true>(p, st);
-    return launch_nt_pp_impl<NWT, false>(p, st);
-}
 
-// tile choice. 256 x 256 (EGX_WIDE_TILE=512 forces it, =256 / =128 force the others): N a multiple of 256 and at least 3.5
-// rounds of tiles over the 256 CUs (its 1.5x lower operand traffic is worth nothing in a half-empty last round)
+// tile choice (EGX_WIDE_TILE = 1024 / 256 / 128 forces one: tools/gemm_check.py, tools/gemm_bench.py). The one-barrier 256 x 256 kernel that
+// = 512 selected lost to the ping-pong kernel on every shape and last existed at 3b19ffd.
 static int nt_variant(int M, int N) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("EGX_WIDE_TILE"); force = e ? atoi(e) : 0; }
+    const int force = tuning().wide_tile;
     if (force == 1024) return 3;        // the ping-pong 256 x 256 kernel
-    if (force == 512) return 2;
     if (force == 256) return 1;
     if (force == 128) return 0;
     const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
@@ -695,14 +654,12 @@ static int nt_variant(int M, int N) {
 // rows of the `colsum` partial buffer written by wide_gemm_nt for an (M, N) output: one per 64 output rows of every tile
 int wide_gemm_nt_colsum_rows(int M, int N) { return nt_variant(M, N) ? cdiv(M, 256) * 4 : cdiv(M, 128) * 2; }     // one per 64 rows of every tile
 
-static int epi_lds_mode() {     // EGX_WIDE_EPI: 0 = accumulator-layout stores, 1 = through LDS without mask / column sums, 2 = through LDS always
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_WIDE_EPI"); v = e ? atoi(e) : 2; }
-    return v;
-}
+// WideGemmParams::epi_lds as every launch passes it: the epilogues go through LDS always (the kernels still decode 0 = accumulator-layout stores and
+// 1 = through LDS without mask / column sums)
+constexpr int EPI_LDS_ALWAYS = 2;
 int wide_gemm_nt(const WideGemmParams& p_in, hipStream_t st) {
     WideGemmParams p = p_in;
-    p.epi_lds = epi_lds_mode();
+    p.epi_lds = EPI_LDS_ALWAYS;
     EGX_CHECK(p.A && p.B && (p.Cf || p.Cb), "wide_gemm_nt: null operand");
     EGX_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "wide_gemm_nt: empty problem %dx%dx%d", p.M, p.N, p.K);
     EGX_CHECK(p.K % TBK == 0 && p.N % 4 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.ldc % 4 == 0,
@@ -710,35 +667,27 @@ int wide_gemm_nt(const WideGemmParams& p_in, hipStream_t st) {
     const int v = nt_variant(p.M, p.N);
     if (v == 3) {
         // 256 x 192 tiles when they fill the last round better (cost = rounds x tile width): N = 768 is 1.5 rounds of 256-column
-        // tiles (2 rounds of time) or exactly 2 rounds of 192-column tiles (1.5). EGX_WIDE_PP192=0 keeps the 256 x 256 tile.
-        static int pp192 = -1;
-        if (pp192 < 0) { const char* e = getenv("EGX_WIDE_PP192"); pp192 = e ? atoi(e) : 1; }
-        if (pp192 && !p.colsum && p.N % 192 == 0) {
+        // tiles (2 rounds of time) or exactly 2 rounds of 192-column tiles (1.5).
+        if (!p.colsum && p.N % 192 == 0) {
             const long tm = cdiv(p.M, 256);
             const long c256 = cdiv(tm * cdiv(p.N, 256), 256) * 256, c192 = cdiv(tm * cdiv(p.N, 192), 256) * 192;
             if (c192 * 5 <= c256 * 4) return launch_nt_pp<3>(p, st);       // a 192-column tile costs ~0.87, not 0.75, of a 256-column one (measured: N = 2304, 0.9 of the rounds x width, lost 9 %)
         }
         return launch_nt_pp<4>(p, st);
     }
-    if (v == 2) return launch_nt<256, 256, 128, 2>(p, st);
     // 256-row tiles (8 waves, 3-stage ring) once they fill the chip twice over; 128-row tiles (4 waves) below
     if (v == 1) return launch_nt<256, 128, 64, 3>(p, st);
     // 128 x 128 tiles: two workgroups per CU with two stages each once the tiles outnumber the CUs; a launch that cannot
     // give every CU a second workgroup anyway (the decoder's B * sy <= 2048 target rows: 16-64 tiles) runs four stages deep,
-    // so that a K step costs a third of a memory round trip instead of a whole one (EGX_WIDE_SMALL_STAGES = 2 / 4 forces one)
-    static int small_stages = -1;
-    if (small_stages < 0) { const char* e = getenv("EGX_WIDE_SMALL_STAGES"); small_stages = e ? atoi(e) : 0; }
+    // so that a K step costs a third of a memory round trip instead of a whole one
     const long tiles = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
     // at most one 128 x 128 tile per CU (the decoder's projections of its B * sy target rows: 16-64 tiles; the d = 256 encoder
     // of the HHI EgoT2-g: 180): 64 x 64 tiles, four waves of 16 x 64 and four stages, put four times as many workgroups on a GEMM
     // whose duration is a chain of memory round trips, not MFMA time. Same-box sweep of the threshold (64 / 128 / 256 tiles):
     // C5 HOI 4.02 / 3.98 / 3.99 ms, C5 HHI 2.51 / 2.52 / 2.43 ms, C4 unchanged; without the variant 4.32 / 2.78 ms.
     // (the column-sum epilogue needs 64-row waves: those launches keep the 128 x 128 tiles)
-    static int tiny = -1;
-    if (tiny < 0) { const char* e = getenv("EGX_WIDE_TINY"); tiny = e ? atoi(e) : 256; }      // threshold in 128 x 128 tiles (0: off)
-    if (tiles <= tiny && !p.colsum) return launch_nt<64, 64, 16, 4>(p, st);
-    const int stages = small_stages ? small_stages : (tiles <= 256 ? 4 : 2);
-    return stages == 2 ? launch_nt<128, 128, 64, 2>(p, st) : launch_nt<128, 128, 64, 4>(p, st);
+    if (tiles <= 256 && !p.colsum) return launch_nt<64, 64, 16, 4>(p, st);
+    return tiles <= 256 ? launch_nt<128, 128, 64, 4>(p, st) : launch_nt<128, 128, 64, 2>(p, st);
 }
 
 // ---- TN ---------------------------------------------------------------------------------------------------------------
@@ -934,14 +883,9 @@ int wide_reduce_flush(WideReduceBatch& b, hipStream_t st) {
     return 0;
 }
 
-// tile variant of a TN problem: 2 = 256 x 256, 1 = 256 x 128, 0 = 128 x 128 (EGX_WIDE_TN_TILE = 512 / 256 / 128 forces one)
+// tile variant of a TN problem: 2 = 256 x 256, 1 = 256 x 128, 0 = 128 x 128
 static int tn_variant(int M, int N) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("EGX_WIDE_TN_TILE"); force = e ? atoi(e) : 0; }
     const bool ok2 = M % 256 == 0 && N % 256 == 0, ok1 = M % 256 == 0;
-    if (force == 512 && ok2) return 2;
-    if (force == 256 && ok1) return 1;
-    if (force == 128) return 0;
     if (ok2 && (long)(M / 256) * (N / 256) >= 9) return 2;      // fewer tiles: the finer variants split the tokens less
     return ok1 ? 1 : 0;
 }
@@ -972,11 +916,9 @@ size_t wide_gemm_tn_scratch(int M, int N, int K) {
     return (size_t)tn_splits(M, N, K, nullptr) * M * N * sizeof(float);
 }
 
-static int tn_slice_major() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("EGX_TN_SLICE_XCD"); v = e ? atoi(e) : 1; }
-    return v;
-}
+// by_slice as every launch passes it: the workgroups of one token slice are consecutive, so an XCD's share of them re-reads one slice of the
+// operands (the kernels still decode 0 = tile-major over a (tiles, splits) grid)
+constexpr int TN_BY_SLICE = 1;
 
 template <int BM, int BN, int WTM, int D>
 static int launch_tn(const WideGemmParams& p, int splits, int kps, float* slabs, size_t slab_stride, hipStream_t st) {
@@ -988,12 +930,8 @@ static int launch_tn(const WideGemmParams& p, int splits, int kps, float* slabs,
         attr = true;
     }
     const int ntM = p.M / BM, ntN = p.N / BN;
-    const int by_slice = tn_slice_major();
     timing_begin(TIMER_WIDE_GEMM, st);
-    if (by_slice)
-        hipLaunchKernelGGL((wide_gemm_tn_kernel<BM, BN, WTM, D>), dim3(ntM * ntN * splits), dim3(THREADS), LDS, st, p, ntM, ntN, kps, slabs, slab_stride, 1);
-    else
-        hipLaunchKernelGGL((wide_gemm_tn_kernel<BM, BN, WTM, D>), dim3(ntM * ntN, splits), dim3(THREADS), LDS, st, p, ntM, ntN, kps, slabs, slab_stride, 0);
+    hipLaunchKernelGGL((wide_gemm_tn_kernel<BM, BN, WTM, D>), dim3(ntM * ntN * splits), dim3(THREADS), LDS, st, p, ntM, ntN, kps, slabs, slab_stride, TN_BY_SLICE);
     timing_end(TIMER_WIDE_GEMM, st);
     EGX_LAUNCH_CHECK();
     return 0;
@@ -1009,7 +947,7 @@ static int launch_tn_grouped(const WideTnGroup& g, int blocks, hipStream_t st) {
         attr = true;
     }
     WideTnGroup gg = g;
-    gg.by_slice = tn_slice_major();
+    gg.by_slice = TN_BY_SLICE;
     timing_begin(TIMER_WIDE_GEMM, st);
     hipLaunchKernelGGL((wide_gemm_tn_grouped_kernel<BM, BN, WTM, D>), dim3(blocks), dim3(THREADS), LDS, st, gg);
     timing_end(TIMER_WIDE_GEMM, st);
@@ -1031,7 +969,7 @@ int wide_tn_queue_add(WideTnQueue& Q, const WideGemmParams& p, void* scratch, hi
     if (defer->n == WIDE_REDUCE_MAX) {       // the reduction reads slabs the queued GEMMs have not written yet: flush them first
         if (wide_tn_queue_flush(Q, st) || wide_reduce_flush(*defer, st)) return 1;
     }
-    g.zero_page = p.zero_page; g.epi_lds = epi_lds_mode();
+    g.zero_page = p.zero_page; g.epi_lds = EPI_LDS_ALWAYS;
     WideTnDesc& q = g.d[g.n++];
     q.A = p.A; q.B = p.B; q.M = p.M; q.N = p.N; q.K = p.K; q.lda = p.lda; q.ldb = p.ldb;
     q.ntM = p.M / (v ? 256 : 128); q.ntN = p.N / (v == 2 ? 256 : TBN); q.kps = kps; q.splits = splits;
@@ -1061,16 +999,12 @@ int wide_tn_queue_flush(WideTnQueue& Q, hipStream_t st) {
 
 int wide_gemm_tn(const WideGemmParams& p_in, void* scratch, hipStream_t st, WideReduceBatch* defer) {
     WideGemmParams p = p_in;
-    p.epi_lds = epi_lds_mode();
+    p.epi_lds = EPI_LDS_ALWAYS;
     EGX_CHECK(p.A && p.B && p.Cf && scratch && p.zero_page, "wide_gemm_tn: null operand");
     EGX_CHECK(p.M % TBM == 0 && p.N % TBN == 0 && p.K > 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.ldc % 4 == 0,
               "wide_gemm_tn: %dx%dx%d needs M, N multiples of 128 and 16-byte aligned rows", p.M, p.N, p.K);
     int kps = 0;
     int splits = tn_splits(p.M, p.N, p.K, &kps);
-    if (p.tn_max_splits > 0 && splits > p.tn_max_splits) {
-        kps = cdiv(cdiv(p.K, p.tn_max_splits), TBK) * TBK;
-        splits = cdiv(p.K, kps);
-    }
     const size_t slab_stride = (size_t)p.M * p.N;
     const int v = tn_variant(p.M, p.N);
     if (splits == 1 && !p.accumulate && p.ldc == p.N) {      // the one slab IS the output

@@ -382,9 +382,7 @@ int encoder_bwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
     // each gets a partial buffer of its own out of `rowpart` (none left, or a bucketed exchange: the shared buffer and its own launch)
     WideRowReduceBatch rrb;
     size_t row_cur = 0;
-    static int row_env = -2;
-    if (row_env == -2) { const char* e = getenv("EGX_ROW_DEFER"); row_env = e ? atoi(e) : 1; }      // 0: every second stage as its own launch (A/B aid)
-    const bool row_defer = row_env != 0 && pl.rowpart_bytes > 0 && !cfg->bucket_cb;
+    const bool row_defer = pl.rowpart_bytes > 0 && !cfg->bucket_cb;
     auto row_region = [&](size_t need) -> void* {
         need = (need + 255) / 256 * 256;
         if (!row_defer || row_cur + need > pl.rowpart_bytes) return nullptr;

@@ -231,8 +231,8 @@ int egx_abi_version(void);
 /* != 0: this configuration and batch run on kernels that evaluate egx_config.token_ce themselves (one clip per workgroup, one launch per
  * direction, a persistent weight cache, no pooled head). Elsewhere the caller composes egx_linear_ce_fwd / _bwd with the encoder calls. */
 int egx_encoder_token_ce_ok(const egx_config* cfg, const egx_segment* segs, int B);
-/* The kernel-selection switches EGX_FFN_CUT / EGX_FFN_SLICES / EGX_SLICE_DROP (development and test aids) are read from the environment once,
- * at first use; this re-reads them (the parity tests compare the modes inside one process). */
+/* The kernel-selection switches (EGX_FFN_CUT, EGX_FFN_SLICES, EGX_SLICE_DROP, EGX_DEC_GROUP, EGX_WIDE_TILE: development and test aids, INTEGRATION.md
+ * section 4) are read from the environment once, at first use; this re-reads them (the parity tests compare the modes inside one process). */
 void egx_tuning_reload(void);
 /* Bytes of egx_config.weight_cache for this configuration (0: this configuration does not run on kernels that pack weights). Depends on
  * the model dimensions and the compute mode, not on the batch. */
