@@ -12,8 +12,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libegot2x.so")
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "ffn_cut.hip", "tiled_attn.hip", "feature_sink.hip", "train.hip", "decoder.hip", "wide_gemm.hip", "wide_attn.hip", "wide_rows.hip", "wide_host.hip", "wide_decoder.hip", "comm.hip", "encoder.hip"]
-HEADERS = ["common.h", "kernels.h", "fused.h", "fused_dev.h", "wide.h", "wide_host.h", os.path.join("..", "..", "include", "egot2x.h")]
+SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "ffn_cut.hip", "tiled_attn.hip", "feature_sink.hip", "train.hip", "decoder.hip", "wide_gemm.hip", "wide_attn.hip", "wide_rows.hip", "wide_host.hip", "wide_decoder.hip", "comm.hip", "fused_host.hip", "encoder.hip"]
+HEADERS = ["common.h", "kernels.h", "fused.h", "fused_dev.h", "wide.h", "wide_host.h", "fused_host.h", os.path.join("..", "..", "include", "egot2x.h")]
 EXTRA = os.environ.get("EGX_CXXFLAGS", "").split()
 FLAGS = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 
@@ -99,7 +99,7 @@ def _build(srcs, OBJ_DIR, LIB_PATH, force, verbose) -> str:
 # exercised without a GPU. build_sanitized() recompiles exactly those translation units with AddressSanitizer + UBSan on the HOST side
 # (-fno-gpu-sanitize: GPU ASAN / XNACK are not available on this pool and are never asked for) and links them with the ordinary
 # objects of the rest; tests/test_cpu_host.py runs the host-only entry points against it in a subprocess with the ASAN runtime preloaded.
-SANITIZED_SOURCES = ["encoder.hip", "wide_host.hip", "wide_decoder.hip", "comm.hip"]
+SANITIZED_SOURCES = ["encoder.hip", "fused_host.hip", "wide_host.hip", "wide_decoder.hip", "comm.hip"]
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
 
 

@@ -53,8 +53,8 @@ def test_host_entry_points_sweep(egx_lib):
 
 
 def test_host_code_under_address_and_ub_sanitizers():
-    """SURVEY.md §5 / VERDICT r4 item 9d: the same sweep against a build whose C++ orchestration (encoder.hip, wide_host.hip,
-    wide_decoder.hip, comm.hip) is compiled with AddressSanitizer + UBSan on the HOST side (egot2_amd/build.py build_sanitized;
+    """SURVEY.md §5 / VERDICT r4 item 9d: the same sweep against a build whose C++ orchestration (encoder.hip, fused_host.hip,
+    wide_host.hip, wide_decoder.hip, comm.hip) is compiled with AddressSanitizer + UBSan on the HOST side (egot2_amd/build.py build_sanitized;
     -fno-gpu-sanitize: no GPU ASAN, no XNACK), in a subprocess with the ASAN runtime preloaded and without torch. Any report —
     an out-of-bounds read of a layout table, a signed overflow in a size computation, a misaligned access — aborts the child."""
     import subprocess

@@ -1,0 +1,293 @@
+"""Bit-for-bit comparison of two builds of libegot2x.so on the d = 128 paths: has a refactor of the HOST code left every result alone?
+(tools/isa_diff.py answers the same question for device code.)
+usage: python tools/lib_compare.py <lib_a.so> <lib_b.so> [--out DIR] [--host] [--keep]
+
+For each of the runs a0 = lib_a, a1 = lib_a again, b = lib_b one FRESH child process is started with EGX_LIB set, one at a time, each under its
+own `timeout`; the first child that exits non-zero ends the comparison and nothing is started after it. A child runs the fixed case list
+below through the public model classes (fixed weights, features and host dropout seeds) and writes every output, loss, gradient and the
+library's launch count per forward and per backward to DIR/<run>.npz (default DIR: build/lib_compare; removed after the comparison
+unless --keep). The parent then compares the files byte for byte:
+  * which arrays repeat a0 = a1 is MEASURED; only the scalar loss of a case with the fused cross entropy may differ (per-clip float atomics),
+    and never in the tiled and ragged cases (d, e, g, h), whose loss has a launch of its own;
+  * every array with a0 = a1 must have a0 = b, and every launch count must be equal;
+  * arrays that do not repeat are listed with their a0 / a1 and a0 / b maximum differences side by side.
+Exit status 1 when any of this fails. (Known: case f without the deterministic mode — stage 2 of the staged backward runs small_dw without tiles,
+which sums dW_in / dW_o with float atomics, fused.h — does not repeat and is reported as such; f_det is its bit-comparable twin.)
+
+Cases (d = 128, three segments of d_in 256, d_ff 2048, 4 heads; f32s and bf16 each):
+  a one-launch (EGX_FFN_CUT=0 EGX_FFN_SLICES=1), B 3, T 15, L 2, p 0.1, head + fused CE    b cut (EGX_FFN_CUT=1 EGX_FFN_SLICES=1), L 1; again deterministic
+  c sliced (default slice count), B 3, L 1                                               d tiled T 17 (S 51), B 3, L 2, p 0.1, head + CE; head-less with a learned position table
+  e tiled T 110 (S 330: across the 320-row chunk), B 2, L 1                              f staged backward (bwd_stage 1, then 2) on shape a; again deterministic
+  g ragged inference, lengths LENS at T_pad 16, L 2, with head and head-less             h ragged training, LENS, L 2, p 0.1, head + CE, feature gradients; L 1 head-less
+  i ASD rows (out_tokens) with the fused token loss, B 3, T 15, L 2, weight cache (two steps: the cache filled, then valid)
+
+--host: no GPU. The children drive the host-only calls of tests/host_paths*.py (workspace sizes, implementation / slice answers, refusals)
+and the ragged workspace queries through a recording proxy; the parent compares return values, sizes and egx_last_error() texts."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LENS = [[1, 1, 1], [16, 16, 16], [15, 7, 16], [16, 1, 1]]      # S_b = 3, 48 (one full tile), 38, 18
+CE_W = [0.266, 0.734]
+CHILD_TIMEOUT = 420
+
+
+# ---- child: GPU cases -------------------------------------------------------------------------------------------------------------------
+def gpu_child(path):
+    import numpy as np
+    import torch
+    from torch import nn
+    from egot2_amd import _lib, functional as F_egx, hhi_asd, hhi_ttm
+    from egot2_amd.synth import hhi_args
+    lib = _lib.load()
+    cuda = torch.device("cuda")
+    out = {}
+
+    def tune(**env):
+        for k in ("EGX_FFN_CUT", "EGX_FFN_SLICES"):
+            os.environ.pop(k, None)
+        os.environ.update({k: str(v) for k, v in env.items()})
+        lib.egx_tuning_reload()
+
+    def model_of(cls, L, p, compute, seed, det=False, learned_pe=False):
+        torch.manual_seed(seed)
+        m = cls(hhi_args(num_layers=L, dropout=p))
+        if learned_pe:
+            pe = m.pos_embed._buffers.pop("pe")
+            m.pos_embed.pe = nn.Parameter(pe.clone())
+        m = m.to(cuda).set_compute(compute).set_deterministic(det).train()
+        m.pos_embed.dropout.p = 0.1 if p > 0 else 0.0
+        m._egx_seed = lambda: 0x5EED0000 + seed
+        return m
+
+    def feats_of(seed, B, T, grad=False):
+        rng = np.random.default_rng(seed)
+        return [torch.from_numpy(rng.standard_normal((B, T, 256), dtype=np.float32)).to(cuda).requires_grad_(grad) for _ in range(3)]
+
+    def keep(tag, name, t):
+        out[f"{tag}/{name}"] = t.detach().float().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+    def step(tag, m, fwd, feats=(), finish=None):
+        """forward -> (outputs..., scalar to differentiate last); backward; everything recorded under tag/"""
+        lib.egx_launch_count(1)
+        res = fwd()
+        torch.cuda.synchronize()
+        keep(tag, "launches_fwd", lib.egx_launch_count(1))
+        res = res if isinstance(res, tuple) else (res,)
+        for i, r in enumerate(res):
+            keep(tag, f"out{i}", r)
+        if not torch.is_grad_enabled():
+            return
+        res[-1].backward() if res[-1].dim() == 0 else (res[-1] * torch.linspace(-1, 1, res[-1].numel(), device=cuda).view_as(res[-1])).sum().backward()
+        torch.cuda.synchronize()
+        keep(tag, "launches_bwd", lib.egx_launch_count(1))
+        if finish is not None:
+            finish()
+            torch.cuda.synchronize()
+            keep(tag, "launches_bwd2", lib.egx_launch_count(1))
+        for n, q in m.named_parameters():
+            if q.grad is not None:
+                keep(tag, "grad/" + n, q.grad)
+        for k, f in enumerate(feats):
+            if f.grad is not None:
+                keep(tag, f"dfeat{k}", f.grad)
+
+    w = torch.tensor(CE_W, device=cuda)
+    lens = torch.tensor(LENS)
+    TTM, ASD = hhi_ttm.TaskFusionMFTransformer3Task, hhi_asd.TaskFusionMFTransformer3Task
+    for ci, compute in enumerate(("f32s", "bf16")):
+        s0 = 100 * ci
+        tgt3, tgt2, tgt4 = torch.tensor([0, 1, 1], device=cuda), torch.tensor([1, 0], device=cuda), torch.tensor([0, 1, 1, 0], device=cuda)
+        f15 = feats_of(11, 3, 15)
+
+        def ttm_ce(m, feats, tgt):
+            return lambda: m.forward_features(*feats, target=tgt, class_weight=w)
+
+        tune(EGX_FFN_CUT=0, EGX_FFN_SLICES=1)
+        m = model_of(TTM, 2, 0.1, compute, s0 + 1)
+        step(f"a_{compute}", m, ttm_ce(m, f15, tgt3))
+        for det in (False, True):       # (the staged backward sums with float atomics unless deterministic)
+            m = model_of(TTM, 2, 0.1, compute, s0 + 6, det=det)
+            m.egx_defer_small = True
+            step(f"f{'_det' if det else ''}_{compute}", m, ttm_ce(m, f15, tgt3), finish=F_egx.run_deferred)
+        m = model_of(ASD, 2, 0.1, compute, s0 + 9).enable_weight_cache()
+        lossav = hhi_asd.lossAV(128).to(cuda)
+        labels = (torch.arange(45, device=cuda) * 7 // 3) % 2
+        for rep in (0, 1):
+            m.zero_grad(set_to_none=True)
+            step(f"i{rep}_{compute}", m, lambda: tuple(reversed(m.forward_features(*f15, lossav=lossav, labels=labels))))
+            assert F_egx.last_encoder_impl() == "fused", F_egx.last_encoder_impl()
+        tune(EGX_FFN_CUT=1, EGX_FFN_SLICES=1)
+        for det in (False, True):
+            m = model_of(TTM, 1, 0.1, compute, s0 + 2, det=det)
+            step(f"b{'_det' if det else ''}_{compute}", m, ttm_ce(m, f15, tgt3))
+        tune()
+        m = model_of(TTM, 1, 0.1, compute, s0 + 3)
+        step(f"c_{compute}", m, ttm_ce(m, f15, tgt3))
+        assert F_egx.last_encoder_impl() == "fused", F_egx.last_encoder_impl()
+        f17 = feats_of(12, 3, 17)
+        m = model_of(TTM, 2, 0.1, compute, s0 + 4)
+        step(f"d_{compute}", m, ttm_ce(m, f17, tgt3))
+        assert F_egx.last_encoder_impl() == "tiled", F_egx.last_encoder_impl()
+        m = model_of(ASD, 2, 0.1, compute, s0 + 4, learned_pe=True)
+        step(f"d_rows_{compute}", m, lambda: m.forward_features(*f17))
+        assert m.pos_embed.pe.grad is not None and F_egx.last_encoder_impl() == "tiled"
+        f110 = feats_of(13, 2, 110)
+        m = model_of(TTM, 1, 0.1, compute, s0 + 5)
+        step(f"e_{compute}", m, ttm_ce(m, f110, tgt2))
+        f16 = feats_of(14, 4, 16)
+        with torch.no_grad():
+            m = model_of(TTM, 2, 0.0, compute, s0 + 7).eval()
+            step(f"g_{compute}", m, lambda: m.forward_features(*f16, lengths=lens))
+            m = model_of(ASD, 2, 0.0, compute, s0 + 7).eval()
+            step(f"g_rows_{compute}", m, lambda: m.forward_features(*f16, lengths=lens))
+        f16g = feats_of(14, 4, 16, grad=True)
+        m = model_of(TTM, 2, 0.1, compute, s0 + 8)
+        step(f"h_{compute}", m, lambda: m.forward_features_ragged(*f16g, lengths=lens, target=tgt4, class_weight=w), feats=f16g)
+        assert F_egx.last_encoder_impl() == "ragged", F_egx.last_encoder_impl()
+        m = model_of(ASD, 1, 0.1, compute, s0 + 8)
+        step(f"h_rows_{compute}", m, lambda: m.forward_features_ragged(*f16, lengths=lens))
+    np.savez(path, **out)
+    print(f"{os.path.relpath(path, ROOT)}: {len(out)} arrays")
+
+
+# ---- child: host-only calls ------------------------------------------------------------------------------------------------------------------
+class Recorder:
+    """ctypes library proxy: every call is logged with its return value, the size_t results behind its byref arguments and the error text"""
+
+    def __init__(self, lib):
+        self._lib, self.log = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            r = fn(*args)
+            if name != "egx_last_error":
+                failed = fn.restype is C.c_int and r != 0       # (or an answer such as an implementation id: the text is then the last failure's)
+                sizes = [] if failed else [a._obj.value for a in args if isinstance(getattr(a, "_obj", None), C.c_size_t)]
+                self.log.append([name, r.decode() if isinstance(r, bytes) else r, sizes, self._lib.egx_last_error().decode() if failed else ""])
+            return r
+        return call
+
+
+def host_child(path):
+    sys.path.insert(0, ROOT)
+    from egot2_amd import _lib
+    from egot2_amd._lib import Config, Segment
+    from tests import host_paths, host_paths_generate, host_paths_ragged_g_train
+    rec = Recorder(host_paths.bind(_lib.LIB_PATH))
+    for mod in (host_paths, host_paths_generate, host_paths_ragged_g_train):
+        mod.exercise(rec)
+    nb, sv, sc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    for T_pad, lens in ((16, [[1, 1, 1], [15, 7, 15], [16, 16, 16]]), (150, [[150, 150, 150]])):
+        segs = (Segment * 3)()
+        for s in segs:
+            s.T, s.d_in, s.proj_w = T_pad, 256, 1
+        arr = (C.c_int * (3 * len(lens)))(*[t for clip in lens for t in clip])
+        for compute in (0, 1, 2):
+            for L in (1, 2, 6, 7):
+                for p in (0.0, 0.1):
+                    for det in (0, 1):
+                        cfg = Config(128, 4, 2048, L, 3, 1e-5, compute, 0, p, p, 0.0)
+                        cfg.deterministic = det
+                        rec.egx_ragged_workspace(C.byref(cfg), segs, len(lens), arr, C.byref(nb))
+                        rec.egx_ragged_train_workspace(C.byref(cfg), segs, len(lens), arr, C.byref(sv), C.byref(sc))
+    json.dump(rec.log, open(path, "w"))
+    print(f"{os.path.relpath(path, ROOT)}: {len(rec.log)} calls")
+
+
+# ---- parent ----------------------------------------------------------------------------------------------------------------------------------
+def run_children(libs, out_dir, host):
+    paths = {}
+    for run, lib in libs:
+        paths[run] = os.path.join(out_dir, run + (".json" if host else ".npz"))
+        env = dict(os.environ, EGX_LIB=os.path.abspath(lib), PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+        cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT), sys.executable, os.path.abspath(__file__), "--host-child" if host else "--child", paths[run]]
+        rc = subprocess.run(cmd, env=env, cwd=ROOT).returncode
+        if rc != 0:
+            print(f"child {run} ({lib}) exited with {rc}: stopping, nothing else is run")
+            sys.exit(2)
+    return paths
+
+
+def compare_host(paths):
+    a0, a1, b = (json.load(open(paths[k])) for k in ("a0", "a1", "b"))
+    bad = 0
+    if a0 != a1:
+        print("a0 / a1: the host calls of lib_a do not repeat")
+        bad += 1
+    if len(a0) != len(b):
+        print(f"call counts differ: {len(a0)} / {len(b)}")
+        bad += 1
+    for i, (x, y) in enumerate(zip(a0, b)):
+        if x != y:
+            bad += 1
+            if bad < 20:
+                print(f"call {i} differs:\n  a: {x}\n  b: {y}")
+    names = sorted({x[0] for x in a0})
+    print(f"host calls compared: {len(a0)} ({sum(1 for x in a0 if x[3])} with an error text) over {len(names)} entry points; differing: {bad}")
+    return 1 if bad else 0
+
+
+def compare_gpu(paths):
+    import numpy as np
+    a0, a1, b = (dict(np.load(paths[k])) for k in ("a0", "a1", "b"))
+    bad = 0
+    if not (set(a0) == set(a1) == set(b)):
+        print("array names differ:", sorted(set(a0) ^ set(b)) + sorted(set(a0) ^ set(a1)))
+        bad += 1
+
+    def same(x, y):
+        return x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
+
+    def maxdiff(x, y):
+        return float(np.max(np.abs(x.astype(np.float64) - y.astype(np.float64)))) if x.shape == y.shape and x.size else float("nan")
+
+    cases = sorted({k.split("/")[0] for k in a0})
+    print(f"{'case':<16}{'arrays':>7}{'a0=a1':>7}{'a0=b':>7}  launches fwd / bwd (a | b)")
+    for c in cases:
+        keys = [k for k in sorted(a0) if k.split("/")[0] == c and k in a1 and k in b]
+        aa = [k for k in keys if same(a0[k], a1[k])]
+        ab = [k for k in keys if same(a0[k], b[k])]
+        ln = lambda d: " / ".join(str(int(d[k])) for k in keys if "/launches_" in k)   # noqa: E731
+        print(f"{c:<16}{len(keys):>7}{len(aa):>7}{len(ab):>7}  {ln(a0)} | {ln(b)}")
+        for k in keys:
+            if "/launches_" in k and int(a0[k]) != int(b[k]):
+                print(f"  LAUNCH COUNT {k}: {int(a0[k])} / {int(b[k])}")
+                bad += 1
+            if k in aa and k not in ab:
+                print(f"  DIFFERENT {k}: repeats a0 = a1, but a0 / b max |diff| {maxdiff(a0[k], b[k]):.3e}")
+                bad += 1
+            if k not in aa:
+                loss_only = a0[k].size == 1 and "/out" in k and c[0] in "abcfi"
+                print(f"  not reproducible {k}: a0 / a1 max |diff| {maxdiff(a0[k], a1[k]):.3e}, a0 / b {maxdiff(a0[k], b[k]):.3e}"
+                      + ("" if loss_only else "  <- NOT a fused-loss scalar of a per-clip case: the comparison cannot be trusted"))
+                bad += 0 if loss_only else 1
+    print(f"arrays compared: {len(a0)}; failures: {bad}")
+    return 1 if bad else 0
+
+
+def main(argv):
+    if argv[1] == "--child":
+        return gpu_child(argv[2])
+    if argv[1] == "--host-child":
+        return host_child(argv[2])
+    host = "--host" in argv
+    out_dir = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "build", "lib_compare")
+    lib_a, lib_b = [x for x in argv[1:] if x.endswith(".so")][:2]
+    os.makedirs(out_dir, exist_ok=True)
+    print(f"# lib_a = {os.path.relpath(lib_a, ROOT)}, lib_b = {os.path.relpath(lib_b, ROOT)} ({'host calls' if host else 'GPU cases'})")
+    paths = run_children([("a0", lib_a), ("a1", lib_a), ("b", lib_b)], out_dir, host)
+    rc = compare_host(paths) if host else compare_gpu(paths)
+    if "--keep" not in argv:        # (a few hundred MB of gradients)
+        for f in paths.values():
+            os.remove(f)
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
