@@ -301,6 +301,149 @@ def flat_storage_view(t: torch.Tensor) -> torch.Tensor:
     return torch.empty(0, dtype=t.dtype, device=t.device).set_(st, 0, (st.nbytes() // t.element_size(),))
 
 
+def _load():
+    """The library; under reload_tuning_each_call it re-reads its kernel-selection switches first."""
+    lib = _lib.load()
+    if reload_tuning_each_call:
+        lib.egx_tuning_reload()
+    return lib
+
+
+def _seed64(x: int) -> C.c_uint64:
+    return C.c_uint64(int(x) & (2**64 - 1))
+
+
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    """`t` as a contiguous fp32 tensor: itself where it is one already (an upstream gradient usually is: no torch op)."""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _head(head_t, n_out: int) -> Head:
+    return Head(*map(ptr, head_t), n_out)
+
+
+def _saved_buffer(needs_grad: bool, tag: str, device: torch.device, nbytes: int) -> torch.Tensor:
+    """The `saved` workspace of a forward: a buffer of the call's own where a backward may follow (any input needs a gradient), else the
+    shared grow-only workspace `tag`. Poisoned under EGX_POISON either way."""
+    if not needs_grad:
+        return _workspace(tag, device, nbytes)
+    saved = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    if _POISON:
+        saved.fill_(255)
+    return saved
+
+
+def _ce_attach(spec: EncoderSpec, cfg: Config, target, weight, B: int, device):
+    """The fused cross entropy of the pooled head's logits (spec.ce, egx_ce) attached to cfg: returns (loss, d_logits, keep-alive), both
+    written by the forward."""
+    if target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
+        raise ValueError("target must be an int64 tensor of shape (B,) on the features' device")
+    tgt = target.contiguous()
+    cw = None if weight is None else _dev_f32(weight, "class weight")
+    if cw is not None and cw.numel() != spec.head_n_out:
+        raise ValueError("class weight must have one entry per class")
+    loss = torch.empty((), dtype=torch.float32, device=device)
+    dl = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
+    ce_struct = Ce(ptr(tgt), ptr(cw), ptr(loss), ptr(dl))
+    cfg.ce = C.cast(C.pointer(ce_struct), C.c_void_p)
+    return loss, dl, (tgt, cw, ce_struct)
+
+
+def _ce_upstream(ctx, d_out, d_loss):
+    """Upstream gradients of the (logits, loss) outputs of a forward with spec.ce -> (d_out, dl_scale), or None when neither output has one.
+    The loss's d_logits was left by the forward; its upstream gradient (loss.backward()'s ones, a loss scale) goes to the kernels as a
+    device scalar. A gradient reaching the logits directly as well is the rare case: torch ops."""
+    if d_loss is None:
+        return None if d_out is None else (d_out, None)
+    g = _f32c(d_loss)
+    if d_out is None:
+        return ctx.ce_dl, g
+    return d_out + ctx.ce_dl * g, None
+
+
+class _EncArgs:
+    """The tensor arguments of the encoder Functions, in their one order: task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg],
+    (proj_w, proj_b) per projecting segment, 12 tensors per layer in _LAYER_FIELDS order, (head_ln_w, head_ln_b, head_W, head_b) with
+    spec.head_n_out, then the tail of a fused loss (spec.ce: target, class weight | None; spec.token_ce: classifier weight, bias | None,
+    target, class weight | None). `rest` is everything behind ln_b."""
+
+    @staticmethod
+    def split(spec: EncoderSpec, rest, wide: bool = False):
+        """rest -> (feats, proj, layer_t, head_t, tail). wide (RaggedWideEncoderFn): every segment projects and nothing follows the layers,
+        by position and whatever the spec says."""
+        nseg = len(spec.segments)
+        if wide:
+            return rest[:nseg], rest[nseg:3 * nseg], rest[3 * nseg:], (), ()
+        nproj = sum(1 for s in spec.segments if s.has_proj)
+        end = len(rest) - (4 if spec.token_ce else 2 if spec.ce else 0)
+        head0 = end - (4 if spec.head_n_out else 0)
+        return rest[:nseg], rest[nseg:nseg + 2 * nproj], rest[nseg + 2 * nproj:head0], rest[head0:end], rest[end:]
+
+    @staticmethod
+    def save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tail=()):
+        """save_for_backward of a forward's (device, contiguous) tensors; `tail`: further tensors the backward reads (the token classifier's)."""
+        ctx.has_te, ctx.has_pos = task_embed is not None, pos_table is not None
+        ctx.counts = (len(feats), len(proj), len(layer_t), len(head_t))
+        ctx.save_for_backward(*[t for t in (task_embed, pos_table) if t is not None], ln_w, ln_b, *feats, *proj, *layer_t, *head_t, *tail)
+
+    @staticmethod
+    def load(ctx):
+        """-> (task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tail) as save() took them"""
+        sv = list(ctx.saved_tensors)
+        task_embed = sv.pop(0) if ctx.has_te else None
+        pos_table = sv.pop(0) if ctx.has_pos else None
+        a, b, c, e = (2 + sum(ctx.counts[:k]) for k in (1, 2, 3, 4))
+        return task_embed, pos_table, sv[0], sv[1], sv[2:a], sv[a:b], sv[b:c], sv[c:e], sv[e:]
+
+
+class _EncGrads:
+    """The gradients of one encoder backward. Everything but the feature gradients is a view of ONE flat buffer (_GradPacker), registered in
+    argument order; `need` is ctx.needs_input_grad, `at` the index of feats[0] in it (5, 6 or 7). bucketed (EncoderFn under bucket_hook): the
+    tensors of the layer the backward finishes first (the LAST one) get rank 0, ..., layer 0 rank L - 1, everything else L, so that each
+    layer's gradients are one contiguous slice; late (EncoderFn without a hook): dW_proj, dW_in, dW_o lead the buffer (_GradPacker)."""
+
+    def __init__(self, spec: EncoderSpec, need, at: int, tensors, device, late: bool = False, bucketed: bool = False):
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tail = tensors
+        n_l = spec.n_layers
+        rest_rank = n_l if bucketed else 0
+        pk = self.pk = _GradPacker()
+        for t, want in zip((task_embed, pos_table, ln_w, ln_b), need[at - 4:at]):
+            pk.add(t, want, rank=rest_rank)
+        # d(feature) is a per-sample ACTIVATION gradient: it must never sit in the flat buffer that the data-parallel exchange
+        # all-reduces (in place, on the collective's stream, while autograd hands the same memory to the upstream module).
+        # Every implementation overwrites it (input-gradient GEMM / LayerNorm backward), so it needs no zero fill either.
+        self.feats = [torch.empty(f.shape, dtype=torch.float32, device=device) if need[at + i] else None for i, f in enumerate(feats)]
+        k = at + len(feats)
+        # proj: (w, b) pairs; layer: 12 tensors in _LAYER_FIELDS order, in_proj_w / out_proj_w are indices 0 and 2
+        for i, t in enumerate(proj):
+            pk.add(t, need[k + i], late=late and i % 2 == 0, rank=rest_rank)
+        k += len(proj)
+        for i, t in enumerate(layer_t):
+            pk.add(t, need[k + i], late=late and i % 12 in (0, 2), rank=(n_l - 1 - i // 12) if bucketed else 0)
+        k += len(layer_t)
+        # (the token classifier's gradients, egx_token_ce, live in the flat buffer too: zero-filled, reduced and all-reduced with the rest)
+        for i, t in enumerate((*head_t, *tail)):
+            pk.add(t, need[k + i], rank=rest_rank)
+        g = pk.materialise(device, zero=False)      # zero-filled by the backward's first launch (egx_config.zero_buf)
+        self.flat, self.lead = pk.flat, at - 4
+        a, b, c = 4 + len(proj), 4 + len(proj) + len(layer_t), 4 + len(proj) + len(layer_t) + len(head_t)
+        self.first, self.proj, self.layers, self.head, self.tail = g[:4], g[4:a], g[a:b], g[b:c], g[c:]
+
+    def attach(self, cfg: Config):
+        cfg.zero_buf, cfg.zero_bytes = ptr(self.flat), self.flat.numel() * 4
+
+    def segments(self):
+        """The `grads` of _segments()"""
+        return self.feats, self.proj, self.first[0], self.first[1]
+
+    def head_grads(self) -> HeadGrads:
+        return HeadGrads(*map(ptr, self.head))
+
+    def result(self, trailing: int = 0):
+        """The backward's return value: None for the leading non-tensor arguments and `trailing` further ones (targets, class weights)."""
+        return (None,) * self.lead + (*self.first, *self.feats, *self.proj, *self.layers, *self.head, *self.tail) + (None,) * trailing
+
+
 def _attach_weight_cache(lib, spec: EncoderSpec, cfg: Config, segs, proj, layer_t, device):
     """Persistent packed-weight cache (spec.wcache): valid when nothing that goes into the packed copies changed since the forward that
     filled it. Sets cfg.weight_cache / weight_cache_valid; returns (cache, signature) — the caller stores the signature in cache.sig once
@@ -325,34 +468,51 @@ def _attach_weight_cache(lib, spec: EncoderSpec, cfg: Config, segs, proj, layer_
     return wc, wc_sig
 
 
+def _token_ce_attach(lib, spec: EncoderSpec, cfg: Config, segs, tce_in, fused: bool, B: int, S: int, device):
+    """The fused per-token classifier + weighted cross entropy (spec.token_ce, egx_token_ce) attached to cfg. tce_in = (classifier weight,
+    bias | None, target, class weight | None). Returns (keep-alive, (loss, logits, probs, pred, correct), d_logits, weight, bias | None)."""
+    refusal = ("EncoderSpec.token_ce: this configuration does not evaluate the token classifier in its kernels "
+               "(use functional.encoder_token_ce, which falls back to linear_cross_entropy)")
+    Cn, d, Mrows = int(spec.token_ce), spec.d_model, B * (spec.out_tokens or S)
+    if not fused:
+        raise _lib.EgxError(refusal)
+    tw = _dev_f32(tce_in[0], "classifier weight")
+    tb = _dev_f32(tce_in[1], "classifier bias") if tce_in[1] is not None else None
+    ttgt, tcw = tce_in[2], (None if tce_in[3] is None else _dev_f32(tce_in[3], "class weight"))
+    if tuple(tw.shape) != (Cn, d) or ttgt.dtype != torch.int64 or tuple(ttgt.shape) != (Mrows,) or ttgt.device != device:
+        raise ValueError(f"token classifier: weight must be ({Cn}, {d}) and target an int64 tensor of shape ({Mrows},) on the features' device")
+    ttgt = ttgt.contiguous()
+    t_logits = torch.empty((Mrows, Cn), dtype=torch.float32, device=device)
+    t_probs, t_dl = torch.empty_like(t_logits), torch.empty_like(t_logits)
+    t_pred = torch.empty((Mrows,), dtype=torch.float32, device=device)
+    t_loss = torch.empty((), dtype=torch.float32, device=device)
+    t_correct = torch.empty((), dtype=torch.float32, device=device)
+    tce_struct = _lib.TokenCe(ptr(tw), ptr(tb), ptr(ttgt), ptr(tcw), Cn, ptr(t_logits), ptr(t_probs), ptr(t_pred), ptr(t_loss),
+                              ptr(t_correct), ptr(t_dl), None, None)
+    cfg.token_ce = C.cast(C.pointer(tce_struct), C.c_void_p)
+    if not lib.egx_encoder_token_ce_ok(C.byref(cfg), segs, B):
+        raise _lib.EgxError(refusal)
+    return (tw, tb, ttgt, tcw, tce_struct), (t_loss, t_logits, t_probs, t_pred, t_correct), t_dl, tw, tb
+
+
 class EncoderFn(torch.autograd.Function):
     """tokens(B,S,d) = encoder(token_prep(feats)) — or, with spec.head_n_out > 0, logits(B,n_out) = head(tokens).
-    Argument order: spec, task_embed|None, pos_table|None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per projecting
-    segment, 12 tensors per layer in _LAYER_FIELDS order, then (head_ln_w, head_ln_b, head_W, head_b) when a head
-    is requested."""
+    Argument order: spec, then _EncArgs' (task_embed|None, pos_table|None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per projecting
+    segment, 12 tensors per layer in _LAYER_FIELDS order, then (head_ln_w, head_ln_b, head_W, head_b) when a head is requested, then
+    the tail of a fused loss)."""
 
     @staticmethod
     def forward(ctx, spec: EncoderSpec, task_embed, pos_table, ln_w, ln_b, *rest):
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
+        lib = _load()
         nseg = len(spec.segments)
-        nproj = sum(1 for s in spec.segments if s.has_proj)
         nhead = 4 if spec.head_n_out else 0
-        tce_in = None
-        if spec.token_ce:
-            if nhead or spec.ce:
-                raise _lib.EgxError("EncoderSpec.token_ce cannot be combined with the pooled head")
-            tce_in, rest = rest[-4:], rest[:-4]         # classifier weight, bias | None, target, class weight | None
-        ce_target = ce_weight = None
-        if spec.ce:
-            if not nhead:
-                raise _lib.EgxError("EncoderSpec.ce needs the pooled head (head_n_out > 0)")
-            ce_target, ce_weight = rest[-2], rest[-1]
-            rest = rest[:-2]
-        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(
-            rest[:nseg], rest[nseg:nseg + 2 * nproj], rest[nseg + 2 * nproj:len(rest) - nhead], rest[len(rest) - nhead:], ln_w, ln_b,
-            task_embed, pos_table)
+        if spec.token_ce and (nhead or spec.ce):
+            raise _lib.EgxError("EncoderSpec.token_ce cannot be combined with the pooled head")
+        if spec.ce and not nhead:
+            raise _lib.EgxError("EncoderSpec.ce needs the pooled head (head_n_out > 0)")
+        feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest)
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
+                                                                                      pos_table)
         assert len(layer_t) == 12 * spec.n_layers, "layer parameter count mismatch"
         d = spec.d_model
         B = feats[0].shape[0]
@@ -363,7 +523,6 @@ class EncoderFn(torch.autograd.Function):
         # NB: grad mode is off inside Function.forward; ctx.needs_input_grad is the reliable signal.
         # needs_input_grad order: (spec, task_embed, pos_table, ln_w, ln_b, *rest)
         nig = ctx.needs_input_grad
-        needs_grad = any(nig)
         if spec.impl == "auto" and (nig[2] or any(nig[5:5 + nseg])):
             feat_grad = [bool(nig[5 + i]) for i in range(nseg)]
             probe_cfg = spec.config()
@@ -373,8 +532,6 @@ class EncoderFn(torch.autograd.Function):
                 # gradients into projected features: only the shape-generic backward produces them (the wide path serves
                 # identity segments — the trainable action stream of the LTA translators — from its LayerNorm backward)
                 spec = dataclasses.replace(spec, impl="generic")
-            elif any(feat_grad):
-                pass
             # (a learned positional table - the HOI translators' `pe` - gets its gradient from every implementation)
         # first-tokens-only output: in-kernel on the fused path; elsewhere the full block is sliced here (and the gradient
         # scattered back in backward)
@@ -392,184 +549,90 @@ class EncoderFn(torch.autograd.Function):
         ws = lib.egx_translator_workspace if nhead else lib.egx_encoder_workspace
         check(ws(C.byref(cfg), segs, B, C.byref(sv), C.byref(sc)))
         S = sum(s.T for s in spec.segments)
-        if needs_grad:
-            saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=device)
-            if _POISON:
-                saved.fill_(255)
-        else:
-            saved = _workspace("saved", device, sv.value)
+        saved = _saved_buffer(any(nig), "saved", device, sv.value)
         scratch = _workspace("scratch", device, sc.value)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
+        seed = _seed64(spec.seed)
         wc, wc_sig = _attach_weight_cache(lib, spec, cfg, segs, proj, layer_t, device)
-        ce_keep = None
+        keep = tw = tb = None       # (keep: what cfg.ce / cfg.token_ce point to, alive across the library call)
         if spec.ce:
-            if ce_target.dtype != torch.int64 or tuple(ce_target.shape) != (B,) or ce_target.device != device:
-                raise ValueError("target must be an int64 tensor of shape (B,) on the features' device")
-            tgt = ce_target.contiguous()
-            cw = None if ce_weight is None else _dev_f32(ce_weight, "class weight")
-            if cw is not None and cw.numel() != spec.head_n_out:
-                raise ValueError("class weight must have one entry per class")
-            loss = torch.empty((), dtype=torch.float32, device=device)
-            dl = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
-            ce_struct = Ce(ptr(tgt), ptr(cw), ptr(loss), ptr(dl))
-            cfg.ce = C.cast(C.pointer(ce_struct), C.c_void_p)
-            ce_keep = (tgt, cw, ce_struct)
-        tce_keep = tce_out = None
+            loss, ctx.ce_dl, keep = _ce_attach(spec, cfg, tail[0], tail[1], B, device)
         if spec.token_ce:
-            Cn, Mrows = int(spec.token_ce), B * (spec.out_tokens or S)
-            if wc is None or py_slice:
-                raise _lib.EgxError("EncoderSpec.token_ce: this configuration does not evaluate the token classifier in its kernels "
-                                    "(use functional.encoder_token_ce, which falls back to linear_cross_entropy)")
-            tw = _dev_f32(tce_in[0], "classifier weight")
-            tb = _dev_f32(tce_in[1], "classifier bias") if tce_in[1] is not None else None
-            ttgt, tcw = tce_in[2], (None if tce_in[3] is None else _dev_f32(tce_in[3], "class weight"))
-            if tuple(tw.shape) != (Cn, d) or ttgt.dtype != torch.int64 or tuple(ttgt.shape) != (Mrows,) or ttgt.device != device:
-                raise ValueError(f"token classifier: weight must be ({Cn}, {d}) and target an int64 tensor of shape ({Mrows},) on the features' device")
-            ttgt = ttgt.contiguous()
-            t_logits = torch.empty((Mrows, Cn), dtype=torch.float32, device=device)
-            t_probs, t_dl = torch.empty_like(t_logits), torch.empty_like(t_logits)
-            t_pred = torch.empty((Mrows,), dtype=torch.float32, device=device)
-            t_loss = torch.empty((), dtype=torch.float32, device=device)
-            t_correct = torch.empty((), dtype=torch.float32, device=device)
-            tce_struct = _lib.TokenCe(ptr(tw), ptr(tb), ptr(ttgt), ptr(tcw), Cn, ptr(t_logits), ptr(t_probs), ptr(t_pred), ptr(t_loss),
-                                      ptr(t_correct), ptr(t_dl), None, None)
-            cfg.token_ce = C.cast(C.pointer(tce_struct), C.c_void_p)
-            if not lib.egx_encoder_token_ce_ok(C.byref(cfg), segs, B):
-                raise _lib.EgxError("EncoderSpec.token_ce: this configuration does not evaluate the token classifier in its kernels "
-                                    "(use functional.encoder_token_ce, which falls back to linear_cross_entropy)")
-            tce_keep = (tw, tb, ttgt, tcw, tce_struct)
-            tce_out = (t_loss, t_logits, t_probs, t_pred, t_correct)
+            keep, tce_out, ctx.tce_dl, tw, tb = _token_ce_attach(lib, spec, cfg, segs, tail, wc is not None and not py_slice, B, S, device)
         if nhead:
-            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
+            head = _head(head_t, spec.head_n_out)
             tokens = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)   # logits
             check(lib.egx_translator_fwd(C.byref(cfg), segs, ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(tokens),
                                          None, ptr(saved), ptr(scratch), int(spec.training), seed, _stream()))
-            del ce_keep
         else:
             tokens = torch.empty((B, spec.out_tokens or S, d), dtype=torch.float32, device=device)
             check(lib.egx_encoder_fwd(C.byref(cfg), segs, ptr(ln_w), ptr(ln_b), layers, B, ptr(tokens), ptr(saved),
                                       ptr(scratch), int(spec.training), seed, _stream()))
             if py_slice:
                 tokens = tokens[:, :py_slice].contiguous()
-            del tce_keep
+        del keep
         if wc is not None:
             wc.sig = wc_sig
         ctx.wcache_buf = wc.buf if wc is not None else None     # the backward reads the packed copies from the same buffer
-        ctx.py_slice, ctx.S = py_slice, S
+        ctx.py_slice, ctx.S, ctx.B = py_slice, S, B
         ctx.spec = spec
         ctx.impl = lib.egx_encoder_impl(C.byref(cfg), segs, B)       # EGX_IMPL_FUSED / EGX_IMPL_TILED / EGX_IMPL_WIDE / EGX_IMPL_GENERIC
         _last_impl[0] = ctx.impl
         _last_slices[0] = lib.egx_encoder_slices(C.byref(cfg), segs, B) if ctx.impl == EGX_IMPL_FUSED else 1
-        ctx.fused_path = ctx.impl == EGX_IMPL_FUSED
-        ctx.B = B
-        ctx.nseg, ctx.nproj, ctx.nhead = nseg, nproj, nhead
-        ctx.saved_buf = saved
-        ctx.scratch_bytes = sc.value
-        ctx.has_te = task_embed is not None
-        ctx.has_pos = pos_table is not None
-        ctx.save_for_backward(*([t for t in (task_embed, pos_table) if t is not None] + [ln_w, ln_b] + feats + proj + layer_t + head_t
-                                + ([tw] + ([tb] if tb is not None else []) if spec.token_ce else [])))
+        ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
+        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, [t for t in (tw, tb) if t is not None])
         if spec.token_ce:
-            ctx.tce_dl, ctx.tce_has_b = t_dl, tb is not None
             ctx.mark_non_differentiable(*tce_out[1:])
             ctx.set_materialize_grads(False)
             return (tokens,) + tce_out
         if spec.ce:
-            ctx.ce_dl = dl
             ctx.set_materialize_grads(False)
             return tokens, loss
         return tokens
 
     @staticmethod
     def backward(ctx, d_tokens, d_loss=None, *_aux):
-        spec0: EncoderSpec = ctx.spec
+        spec: EncoderSpec = ctx.spec
         dl_scale = None
-        if spec0.token_ce:
+        if spec.token_ce:
             # (tokens, loss, ...) outputs: the loss's d_logits was left by the forward; the backward's first launch rebuilds d tokens from it
             if d_tokens is not None:
                 raise _lib.EgxError("EncoderSpec.token_ce: a gradient through the returned tokens as well as through the fused loss is not supported "
                                     "(compose encoder() and linear_cross_entropy() instead)")
             if d_loss is None:
                 return (None,) * len(ctx.needs_input_grad)
-            dl_scale = d_loss if (d_loss.dtype == torch.float32 and d_loss.is_contiguous()) else d_loss.float().contiguous()
+            dl_scale = _f32c(d_loss)
             d_tokens = ctx.tce_dl       # (only its device is read below)
-        if spec0.ce:
-            # (logits, loss) outputs: the loss's d_logits was left by the forward; its upstream gradient (loss.backward()'s ones, a loss
-            # scale) goes to the kernels as a device scalar. A gradient reaching the logits directly as well is the rare case: torch ops.
-            if d_loss is None and d_tokens is None:
+        if spec.ce:
+            up = _ce_upstream(ctx, d_tokens, d_loss)
+            if up is None:
                 return (None,) * len(ctx.needs_input_grad)
-            if d_loss is not None:
-                g = d_loss if (d_loss.dtype == torch.float32 and d_loss.is_contiguous()) else d_loss.float().contiguous()
-                if d_tokens is None:
-                    d_tokens, dl_scale = ctx.ce_dl, g
-                else:
-                    d_tokens = d_tokens + ctx.ce_dl * g
+            d_tokens, dl_scale = up
         if ctx.py_slice:        # gradient of the python-side slice: zeros behind the first tokens
             full = torch.zeros((d_tokens.shape[0], ctx.S, d_tokens.shape[2]), dtype=torch.float32, device=d_tokens.device)
             full[:, :ctx.py_slice] = d_tokens
             d_tokens = full
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
-        spec: EncoderSpec = ctx.spec
-        sv = list(ctx.saved_tensors)
-        tce_b = sv.pop() if (spec.token_ce and ctx.tce_has_b) else None
-        tce_w = sv.pop() if spec.token_ce else None
-        task_embed = sv.pop(0) if ctx.has_te else None
-        pos_table = sv.pop(0) if ctx.has_pos else None
-        ln_w, ln_b = sv[0], sv[1]
-        nseg, nproj = ctx.nseg, ctx.nproj
-        feats = sv[2:2 + nseg]
-        proj = sv[2 + nseg:2 + nseg + 2 * nproj]
-        nhead = ctx.nhead
-        layer_t = sv[2 + nseg + 2 * nproj:len(sv) - nhead]
-        head_t = sv[len(sv) - nhead:] if nhead else []
+        lib = _load()
+        tensors = _EncArgs.load(ctx)
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tce_t = tensors
         B = ctx.B
         device = d_tokens.device
-        need = ctx.needs_input_grad  # (spec, task_embed, pos_table, ln_w, ln_b, *rest)
-
-        pk = _GradPacker()
-        _rr = spec.n_layers if bucket_hook is not None else 0
-        i_te = pk.add(task_embed, need[1], rank=_rr)
-        i_pos = pk.add(pos_table, need[2], rank=_rr)
-        i_lnw = pk.add(ln_w, need[3], rank=_rr)
-        i_lnb = pk.add(ln_b, need[4], rank=_rr)
-        # d(feature) is a per-sample ACTIVATION gradient: it must never sit in the flat buffer that the data-parallel exchange
-        # all-reduces (in place, on the collective's stream, while autograd hands the same memory to the upstream module).
-        # Every implementation overwrites it (input-gradient GEMM / LayerNorm backward), so it needs no zero fill either.
-        feat_grads = [torch.empty(f.shape, dtype=torch.float32, device=device) if need[5 + i] else None for i, f in enumerate(feats)]
-        # proj: (w, b) pairs; layer: 12 tensors in _LAYER_FIELDS order, in_proj_w / out_proj_w are indices 0 and 2
-        i_proj = [pk.add(t, need[5 + nseg + i], late=(i % 2 == 0) and bucket_hook is None, rank=_rr) for i, t in enumerate(proj)]
         hook = bucket_hook
-        n_l = spec.n_layers
-        # bucketed exchange: the backward finishes the LAST layer first -> it gets rank 0, ..., layer 0 rank L - 1, the rest L
-        lrank = (lambda i: n_l - 1 - i // 12) if hook is not None else (lambda i: 0)
-        rest_rank = n_l if hook is not None else 0
-        i_layer = [pk.add(t, need[5 + nseg + 2 * nproj + i], late=(i % 12 in (0, 2)) and hook is None, rank=lrank(i)) for i, t in enumerate(layer_t)]
-        i_head = [pk.add(t, need[5 + nseg + 2 * nproj + len(layer_t) + i], rank=rest_rank) for i, t in enumerate(head_t)]
-        # the token classifier's gradients (egx_token_ce) live in the flat buffer too: zero-filled, reduced and all-reduced with the rest
-        i_tw = pk.add(tce_w, bool(spec.token_ce) and need[-4], rank=rest_rank)
-        i_tb = pk.add(tce_b, bool(spec.token_ce) and need[-3], rank=rest_rank)
-        grads = pk.materialise(device, zero=False)      # zero-filled by the library's backward (saves a fill launch)
-
-        def g(i):
-            return grads[i] if i >= 0 else None
-
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=(feat_grads, [g(i) for i in i_proj], g(i_te), g(i_pos)))
-        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
+        gr = _EncGrads(spec, ctx.needs_input_grad, 5, tensors, device, late=hook is None, bucketed=hook is not None)
+        pk = gr.pk
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
+        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
 
         cfg = spec.config()
-        cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
+        gr.attach(cfg)
         if ctx.wcache_buf is not None:
             cfg.weight_cache = ctx.wcache_buf.data_ptr()
         if dl_scale is not None:
             cfg.d_logits_scale = dl_scale.data_ptr()
-        tce_keep = tce_grads = None
+        tce_keep = None
         if spec.token_ce:
-            tce_struct = _lib.TokenCe(ptr(tce_w), None, None, None, int(spec.token_ce), None, None, None, None, None, ptr(ctx.tce_dl),
-                                      ptr(g(i_tw)), ptr(g(i_tb)))
-            cfg.token_ce = C.cast(C.pointer(tce_struct), C.c_void_p)
-            tce_keep, tce_grads = tce_struct, (g(i_tw), g(i_tb))
+            tce_keep = _lib.TokenCe(ptr(tce_t[0]), None, None, None, int(spec.token_ce), None, None, None, None, None, ptr(ctx.tce_dl),
+                                    *map(ptr, (gr.tail + [None])[:2]))
+            cfg.token_ce = C.cast(C.pointer(tce_keep), C.c_void_p)
         announced = set()
         cb_keep = None
         if hook is not None and ctx.impl == EGX_IMPL_WIDE:
@@ -589,18 +652,17 @@ class EncoderFn(torch.autograd.Function):
                     cb_error.append(e)
             cb_keep = _lib.BUCKET_CB(_cb)
             cfg.bucket_cb = C.cast(cb_keep, C.c_void_p)
-        defer = bool(spec.defer_small) and ctx.fused_path
+        defer = bool(spec.defer_small) and ctx.impl == EGX_IMPL_FUSED
         cfg.bwd_stage = 1 if defer else 0
         scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
+        seed = _seed64(spec.seed)
         saved_buf = ctx.saved_buf
-        # raw addresses only inside `launch`: a closure that kept the gradient VIEW tensors alive would make autograd
-        # clone them instead of adopting them as .grad (they must stay views of the flat buffer)
-        p_lnw, p_lnb, flat_buf = ptr(g(i_lnw)), ptr(g(i_lnb)), pk.flat
-        if nhead:
-            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
-            hg = HeadGrads(ptr(g(i_head[0])), ptr(g(i_head[1])), ptr(g(i_head[2])), ptr(g(i_head[3])))
-            dtok = d_tokens.float().contiguous()
+        # raw addresses only inside `launch`: a closure that kept the gradient VIEW tensors alive (or `gr`, which holds them) would
+        # make autograd clone them instead of adopting them as .grad (they must stay views of the flat buffer)
+        p_lnw, p_lnb, flat_buf = ptr(gr.first[2]), ptr(gr.first[3]), pk.flat
+        if head_t:
+            head, hg = _head(head_t, spec.head_n_out), gr.head_grads()
+            dtok = _f32c(d_tokens)
 
             def launch(c):
                 check(lib.egx_translator_bwd(C.byref(c), segs, ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(dtok),
@@ -611,8 +673,7 @@ class EncoderFn(torch.autograd.Function):
             if spec.token_ce:
                 dtok = None
             else:
-                dtok = d_tokens if d_tokens.dtype == torch.float32 else d_tokens.float()
-                dtok = dtok.contiguous()
+                dtok = _f32c(d_tokens)
                 if dtok.data_ptr() == d_tokens.data_ptr() and ctx.impl == EGX_IMPL_GENERIC:
                     dtok = dtok.clone()
 
@@ -621,6 +682,7 @@ class EncoderFn(torch.autograd.Function):
                                           ptr(scratch), sgr, p_lnw, p_lnb, lgr, int(spec.training), seed,
                                           _stream()))
         launch(cfg)
+        del tce_keep
         if cb_keep is not None and cb_error:
             raise cb_error[0]
         if hook is not None and not defer:
@@ -639,20 +701,13 @@ class EncoderFn(torch.autograd.Function):
             cfg2.bwd_stage = 2
             if ctx.wcache_buf is not None:
                 cfg2.weight_cache = ctx.wcache_buf.data_ptr()
-            keep = (flat_buf, sv, dtok, scratch, saved_buf)   # noqa: F841  (referenced by `finish`: keeps the buffers alive)
+            keep = (flat_buf, tensors, dtok, scratch, saved_buf)   # noqa: F841  (referenced by `finish`: keeps the buffers alive)
 
             def finish(_keep=keep):
                 launch(cfg2)
             _deferred.append(finish)
-        out = [None, g(i_te), g(i_pos), g(i_lnw), g(i_lnb)]
-        out += feat_grads + [g(i) for i in i_proj] + [g(i) for i in i_layer] + [g(i) for i in i_head]
-        if spec.ce:
-            out += [None, None]     # target, class weight
-        if spec.token_ce:
-            nig = ctx.needs_input_grad
-            out += [tce_grads[0], tce_grads[1], None, None]
-            del tce_keep
-        return tuple(out)
+        # trailing: target, class weight (and a bias-less classifier's bias)
+        return gr.result(2 if spec.ce else 4 - len(gr.tail) if spec.token_ce else 0)
 
 
 def encoder(spec: EncoderSpec, feats: Sequence[torch.Tensor], task_embed, pos_table, ln_w, ln_b,
@@ -710,6 +765,28 @@ def _length_groups(spec: EncoderSpec, feats, lengths: torch.Tensor, first_only: 
         yield idx, it, gspec, fs
 
 
+def _ragged_infer_setup(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, query: str,
+                        out_layout: Optional[int] = None):
+    """The shared start of encoder_ragged and encoder_ragged_tokens (call it under no_grad): the lengths (and out_layout) checked, the
+    tensors on the device, segments, layers and the dropout-free configuration built, and the workspace asked for through `query`
+    (egx_ragged_workspace / egx_ragged_encode_workspace). Returns (lib, lengths, the tensors as _dev_params gives them, segments, layers,
+    config, workspace bytes — None where the ragged kernels do not cover the configuration and the grouped fallback has to run; the
+    lengths themselves are valid: ragged_lengths() checked them)."""
+    B = feats[0].shape[0]
+    lengths = _check_host_lengths(lengths, B, len(spec.segments))
+    if out_layout is not None:
+        _check_out_layout(lengths, B, out_layout)
+    lib = _load()
+    params = _dev_params(feats, proj, layer_params, head_params, ln_w, ln_b, task_embed, pos_table)
+    feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = params
+    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+    layers = _layers(layer_t, spec.n_layers)
+    cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
+    nbytes = C.c_size_t(0)
+    covered = getattr(lib, query)(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) == 0
+    return lib, lengths, params, segs, layers, cfg, (nbytes.value if covered else None)
+
+
 def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
                    proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], head_params: Sequence[torch.Tensor] = ()):
     """Inference forward (no autograd) over a batch of clips of their own lengths: clip b's result is that of the same model on clip b
@@ -719,30 +796,22 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
     elsewhere the clips are grouped by their length tuple and each group runs the batched forward ("grouped")."""
     if spec.training or spec.ce or spec.token_ce or spec.out_tokens:
         raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens")
-    lib = _lib.load()
-    if reload_tuning_each_call:
-        lib.egx_tuning_reload()
-    B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
-    lengths = _check_host_lengths(lengths, B, len(spec.segments))
     with torch.no_grad():
-        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_params, head_params, ln_w, ln_b,
-                                                                                      task_embed, pos_table)
-        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = _layers(layer_t, spec.n_layers)
-        cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
-        nbytes = C.c_size_t(0)
-        if lib.egx_ragged_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
-            # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged kernels do not cover
+        lib, lengths, params, segs, layers, cfg, nbytes = _ragged_infer_setup(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
+                                                                              layer_params, head_params, "egx_ragged_workspace")
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = params
+        if nbytes is None:
             return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
-        ws = _workspace("saved", device, nbytes.value)
+        B, device = feats[0].shape[0], feats[0].device
+        ws = _workspace("saved", device, nbytes)
         wc, wc_sig = _attach_weight_cache(lib, spec, cfg, segs, proj, layer_t, device)
         if head_t:
-            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
+            head = _head(head_t, spec.head_n_out)
             out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
             check(lib.egx_ragged_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(out), None,
                                      ptr(ws), _stream()))
         else:
-            out = torch.empty((int(lengths[:, 0].sum()), d), dtype=torch.float32, device=device)
+            out = torch.empty((int(lengths[:, 0].sum()), spec.d_model), dtype=torch.float32, device=device)
             check(lib.egx_ragged_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, None, B, None, ptr(out),
                                      ptr(ws), _stream()))
         if wc is not None:
@@ -785,50 +854,29 @@ def _ragged_train_config(spec: EncoderSpec) -> Config:
 
 class RaggedEncoderFn(torch.autograd.Function):
     """Training forward + backward over a ragged batch (egx_ragged_train_fwd / egx_ragged_bwd). Argument order: spec, lengths (the (B, K)
-    int32 host tensor of ragged_lengths()), task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per segment,
-    12 tensors per layer, (head_ln_w, head_ln_b, head_W, head_b) with spec.head_n_out, then (target, class_weight | None) with spec.ce.
-    Returns logits (B, n_out) [, loss] with a head, else the first segment's rows of every clip, packed (sum_b T_{b,0}, d)."""
+    int32 host tensor of ragged_lengths()), then _EncArgs' (task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b)
+    per segment, 12 tensors per layer, (head_ln_w, head_ln_b, head_W, head_b) with spec.head_n_out, then (target, class_weight | None) with
+    spec.ce). Returns logits (B, n_out) [, loss] with a head, else the first segment's rows of every clip, packed (sum_b T_{b,0}, d)."""
 
     @staticmethod
     def forward(ctx, spec: EncoderSpec, lengths, task_embed, pos_table, ln_w, ln_b, *rest):
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
-        nseg = len(spec.segments)
-        nproj = sum(1 for s in spec.segments if s.has_proj)
-        nhead = 4 if spec.head_n_out else 0
-        ce_target = ce_weight = None
-        if spec.ce:
-            ce_target, ce_weight, rest = rest[-2], rest[-1], rest[:-2]
-        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(
-            rest[:nseg], rest[nseg:nseg + 2 * nproj], rest[nseg + 2 * nproj:len(rest) - nhead], rest[len(rest) - nhead:], ln_w, ln_b,
-            task_embed, pos_table, feat=_dev_f32)
+        lib = _load()
+        feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest)
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
+                                                                                      pos_table, feat=_dev_f32)
         B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
         segs = _segments(spec, feats, proj, task_embed, pos_table, B)
         layers = _layers(layer_t, spec.n_layers)
         cfg = _ragged_train_config(spec)
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_ragged_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
-        needs_grad = any(ctx.needs_input_grad)
-        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=device) if needs_grad else _workspace("saved", device, sv.value)
-        if needs_grad and _POISON:
-            saved.fill_(255)
+        saved = _saved_buffer(any(ctx.needs_input_grad), "saved", device, sv.value)
         keep = None
         if spec.ce:
-            if ce_target.dtype != torch.int64 or tuple(ce_target.shape) != (B,) or ce_target.device != device:
-                raise ValueError("target must be an int64 tensor of shape (B,) on the features' device")
-            tgt = ce_target.contiguous()
-            cw = None if ce_weight is None else _dev_f32(ce_weight, "class weight")
-            if cw is not None and cw.numel() != spec.head_n_out:
-                raise ValueError("class weight must have one entry per class")
-            loss = torch.empty((), dtype=torch.float32, device=device)
-            dl = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
-            ce_struct = Ce(ptr(tgt), ptr(cw), ptr(loss), ptr(dl))
-            cfg.ce = C.cast(C.pointer(ce_struct), C.c_void_p)
-            keep = (tgt, cw, ce_struct)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
-        if nhead:
-            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
+            loss, ctx.ce_dl, keep = _ce_attach(spec, cfg, tail[0], tail[1], B, device)
+        seed = _seed64(spec.seed)
+        if head_t:
+            head = _head(head_t, spec.head_n_out)
             out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
             check(lib.egx_ragged_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(out),
                                            None, ptr(saved), None, int(spec.training), seed, _stream()))
@@ -840,12 +888,9 @@ class RaggedEncoderFn(torch.autograd.Function):
         _last_impl[0] = IMPL_RAGGED
         _last_slices[0] = 1
         ctx.spec, ctx.lengths, ctx.B = spec, lengths, B        # the host lengths: the backward rebuilds the same plan from them
-        ctx.nseg, ctx.nproj, ctx.nhead = nseg, nproj, nhead
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
-        ctx.has_te, ctx.has_pos = task_embed is not None, pos_table is not None
-        ctx.save_for_backward(*([t for t in (task_embed, pos_table) if t is not None] + [ln_w, ln_b] + feats + proj + layer_t + head_t))
+        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t)
         if spec.ce:
-            ctx.ce_dl = dl
             ctx.set_materialize_grads(False)
             return out, loss
         return out
@@ -855,66 +900,49 @@ class RaggedEncoderFn(torch.autograd.Function):
         spec: EncoderSpec = ctx.spec
         dl_scale = None
         if spec.ce:
-            if d_loss is None and d_out is None:
+            up = _ce_upstream(ctx, d_out, d_loss)
+            if up is None:
                 return (None,) * len(ctx.needs_input_grad)
-            if d_loss is not None:
-                g = d_loss if (d_loss.dtype == torch.float32 and d_loss.is_contiguous()) else d_loss.float().contiguous()
-                if d_out is None:
-                    d_out, dl_scale = ctx.ce_dl, g
-                else:
-                    d_out = d_out + ctx.ce_dl * g
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
-        sv = list(ctx.saved_tensors)
-        task_embed = sv.pop(0) if ctx.has_te else None
-        pos_table = sv.pop(0) if ctx.has_pos else None
-        ln_w, ln_b = sv[0], sv[1]
-        nseg, nproj, nhead = ctx.nseg, ctx.nproj, ctx.nhead
-        feats = sv[2:2 + nseg]
-        proj = sv[2 + nseg:2 + nseg + 2 * nproj]
-        layer_t = sv[2 + nseg + 2 * nproj:len(sv) - nhead]
-        head_t = sv[len(sv) - nhead:] if nhead else []
+            d_out, dl_scale = up
+        lib = _load()
+        tensors = _EncArgs.load(ctx)
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, _ = tensors
         B, device = ctx.B, d_out.device
         need = ctx.needs_input_grad     # (spec, lengths, task_embed, pos_table, ln_w, ln_b, *rest)
         if need[3]:
             raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
-        pk = _GradPacker()
-        i_te, i_pos = pk.add(task_embed, need[2]), pk.add(pos_table, False)
-        i_lnw, i_lnb = pk.add(ln_w, need[4]), pk.add(ln_b, need[5])
-        feat_grads = [torch.empty(f.shape, dtype=torch.float32, device=device) if need[6 + i] else None for i, f in enumerate(feats)]
-        i_proj = [pk.add(t, need[6 + nseg + i]) for i, t in enumerate(proj)]
-        i_layer = [pk.add(t, need[6 + nseg + 2 * nproj + i]) for i, t in enumerate(layer_t)]
-        i_head = [pk.add(t, need[6 + nseg + 2 * nproj + len(layer_t) + i]) for i, t in enumerate(head_t)]
-        grads = pk.materialise(device, zero=False)      # zero-filled by the backward's first launch (egx_config.zero_buf)
-
-        def g(i):
-            return grads[i] if i >= 0 else None
-
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=(feat_grads, [g(i) for i in i_proj], g(i_te), None))
-        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
+        gr = _EncGrads(spec, need, 6, tensors, device)
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
+        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
         cfg = _ragged_train_config(spec)
-        cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
+        gr.attach(cfg)
         if dl_scale is not None:
             cfg.d_logits_scale = dl_scale.data_ptr()
         scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
-        up = d_out if (d_out.dtype == torch.float32 and d_out.is_contiguous()) else d_out.float().contiguous()
-        if nhead:
-            head = Head(ptr(head_t[0]), ptr(head_t[1]), ptr(head_t[2]), ptr(head_t[3]), spec.head_n_out)
-            hg = HeadGrads(ptr(g(i_head[0])), ptr(g(i_head[1])), ptr(g(i_head[2])), ptr(g(i_head[3])))
+        seed = _seed64(spec.seed)
+        up = _f32c(d_out)
+        if head_t:
+            head, hg = _head(head_t, spec.head_n_out), gr.head_grads()
             check(lib.egx_ragged_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(up), None,
-                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(g(i_lnw)), ptr(g(i_lnb)), lgr, C.byref(hg),
+                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, C.byref(hg),
                                      int(spec.training), seed, _stream()))
         else:
             check(lib.egx_ragged_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, None, B, None, ptr(up),
-                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(g(i_lnw)), ptr(g(i_lnb)), lgr, None,
+                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, None,
                                      int(spec.training), seed, _stream()))
-        out = [None, None, g(i_te), None, g(i_lnw), g(i_lnb)]
-        out += feat_grads + [g(i) for i in i_proj] + [g(i) for i in i_layer] + [g(i) for i in i_head]
-        if spec.ce:
-            out += [None, None]
-        return tuple(out)
+        return gr.result(2 if spec.ce else 0)
+
+
+def _ragged_train_refused(spec: EncoderSpec, feats, lengths, task_embed, pos_table, proj, query: str) -> bool:
+    """The pre-flight of encoder_ragged_train and encoder_ragged_tokens_train: does the call have to take the grouped path? It does where
+    a learned positional table wants a gradient (the ragged kernels produce none) or where the workspace query refuses the configuration
+    (the lengths themselves are valid: ragged_lengths() checked them)."""
+    lib = _lib.load()
+    B = feats[0].shape[0]
+    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+    sv, sc = C.c_size_t(0), C.c_size_t(0)
+    return (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
+        getattr(lib, query)(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0
 
 
 def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
@@ -933,13 +961,8 @@ def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengt
         raise ValueError("ragged training: the staged backward (defer_small) is not supported")
     if (ce is not None) != bool(spec.ce) or (ce is not None and not spec.head_n_out):
         raise ValueError("ce = (target, class_weight) goes with spec.ce and the pooled head")
-    lib = _lib.load()
-    B = feats[0].shape[0]
-    lengths = _check_host_lengths(lengths, B, len(spec.segments))
-    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-    sv, sc = C.c_size_t(0), C.c_size_t(0)
-    if (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
-            lib.egx_ragged_train_workspace(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0:
+    lengths = _check_host_lengths(lengths, feats[0].shape[0], len(spec.segments))
+    if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_train_workspace"):
         return _encoder_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
     args = [spec, lengths, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
     if ce is not None:
@@ -1002,26 +1025,15 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
     wide bf16 path (last_encoder_impl() == "ragged"); configurations it does not cover run one batched forward per length tuple ("grouped")."""
     if spec.training or spec.ce or spec.token_ce or spec.out_tokens or spec.head_n_out:
         raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens, no head")
-    B = feats[0].shape[0]
-    lengths = _check_host_lengths(lengths, B, len(spec.segments))
-    _check_out_layout(lengths, B, out_layout)
-    lib = _lib.load()
-    if reload_tuning_each_call:
-        lib.egx_tuning_reload()
-    device = feats[0].device
     with torch.no_grad():
-        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_params, (), ln_w, ln_b, task_embed,
-                                                                                 pos_table)
-        d = spec.d_model
-        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = _layers(layer_t, spec.n_layers)
-        cfg = dataclasses.replace(spec, p_drop=0.0, p_pos=0.0, p_feat=0.0).config()
-        nbytes = C.c_size_t(0)
-        if lib.egx_ragged_encode_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(nbytes)) != 0:
-            # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged wide path does not cover
+        lib, lengths, params, segs, layers, cfg, nbytes = _ragged_infer_setup(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
+                                                                              layer_params, (), "egx_ragged_encode_workspace", out_layout)
+        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = params
+        if nbytes is None:
             return _encoder_tokens_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout)
-        ws = _workspace("ragged_wide", device, nbytes.value)
-        out = torch.empty((int(lengths.to(torch.int64).sum()), d), dtype=torch.float32, device=device)
+        B, device = feats[0].shape[0], feats[0].device
+        ws = _workspace("ragged_wide", device, nbytes)
+        out = torch.empty((int(lengths.to(torch.int64).sum()), spec.d_model), dtype=torch.float32, device=device)
         check(lib.egx_ragged_encode(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
                                     ptr(ws), _stream()))
     _last_impl[0] = IMPL_RAGGED
@@ -1032,79 +1044,55 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
 class RaggedWideEncoderFn(torch.autograd.Function):
     """Training forward + backward of the wide bf16 encoder over a ragged batch (egx_ragged_encode_train_fwd / egx_ragged_encode_bwd): every
     token of every clip, packed (out_layout 0) or in frame-major segment tuples (out_layout 1). Argument order: spec, lengths (the (B, K)
-    int32 host tensor of ragged_lengths()), out_layout, task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per
-    segment, 12 tensors per layer. The call owns its `saved` workspace (batch table, bf16 weight copies, activations, dropout keys): a forward of
-    the same module in between cannot change what a pending backward reads."""
+    int32 host tensor of ragged_lengths()), out_layout, then _EncArgs' (task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg],
+    (proj_w, proj_b) per segment, 12 tensors per layer). The call owns its `saved` workspace (batch table, bf16 weight copies, activations,
+    dropout keys): a forward of the same module in between cannot change what a pending backward reads."""
 
     @staticmethod
     def forward(ctx, spec: EncoderSpec, lengths, out_layout: int, task_embed, pos_table, ln_w, ln_b, *rest):
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
-        nseg = len(spec.segments)
-        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(rest[:nseg], rest[nseg:3 * nseg], rest[3 * nseg:], (), ln_w, ln_b,
-                                                                                 task_embed, pos_table)
+        lib = _load()
+        feats, proj, layer_t, _, _ = _EncArgs.split(spec, rest, wide=True)
+        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, (), ln_w, ln_b, task_embed, pos_table)
         B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
         segs = _segments(spec, feats, proj, task_embed, pos_table, B)
         layers = _layers(layer_t, spec.n_layers)
         cfg = _ragged_train_config(spec)
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_ragged_encode_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
-        needs_grad = any(ctx.needs_input_grad)
-        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=device) if needs_grad else _workspace("ragged_wide_saved", device, sv.value)
-        if needs_grad and _POISON:
-            saved.fill_(255)
+        saved = _saved_buffer(any(ctx.needs_input_grad), "ragged_wide_saved", device, sv.value)
         out = torch.empty((int(lengths.to(torch.int64).sum()), d), dtype=torch.float32, device=device)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
         check(lib.egx_ragged_encode_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
-                                              ptr(saved), int(spec.training), seed, _stream()))
+                                              ptr(saved), int(spec.training), _seed64(spec.seed), _stream()))
         _last_impl[0] = IMPL_RAGGED
         _last_slices[0] = 1
-        ctx.spec, ctx.lengths, ctx.B, ctx.out_layout, ctx.nseg = spec, lengths, B, int(out_layout), nseg
+        ctx.spec, ctx.lengths, ctx.B, ctx.out_layout = spec, lengths, B, int(out_layout)
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
-        ctx.has_te, ctx.has_pos = task_embed is not None, pos_table is not None
-        ctx.save_for_backward(*([t for t in (task_embed, pos_table) if t is not None] + [ln_w, ln_b] + feats + proj + layer_t))
+        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, [])
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         spec: EncoderSpec = ctx.spec
-        lib = _lib.load()
-        if reload_tuning_each_call:
-            lib.egx_tuning_reload()
-        sv = list(ctx.saved_tensors)
-        task_embed = sv.pop(0) if ctx.has_te else None
-        pos_table = sv.pop(0) if ctx.has_pos else None
-        ln_w, ln_b = sv[0], sv[1]
-        nseg = ctx.nseg
-        feats, proj, layer_t = sv[2:2 + nseg], sv[2 + nseg:2 + 3 * nseg], sv[2 + 3 * nseg:]
+        lib = _load()
+        tensors = _EncArgs.load(ctx)
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, _, _ = tensors
         B, device = ctx.B, d_out.device
         need = ctx.needs_input_grad     # (spec, lengths, out_layout, task_embed, pos_table, ln_w, ln_b, *rest)
         if need[4]:
             raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
-        if any(need[7:7 + nseg]):
+        if any(need[7:7 + len(feats)]):
             raise _lib.EgxError("ragged training: gradients into PROJECTED features are not supported on the wide path (detach the features)")
-        pk = _GradPacker()
-        i_te = pk.add(task_embed, need[3])
-        i_lnw, i_lnb = pk.add(ln_w, need[5]), pk.add(ln_b, need[6])
-        i_proj = [pk.add(t, need[7 + nseg + i]) for i, t in enumerate(proj)]
-        i_layer = [pk.add(t, need[7 + 3 * nseg + i]) for i, t in enumerate(layer_t)]
-        grads = pk.materialise(device, zero=False)      # zero-filled by the backward's first launch (egx_config.zero_buf)
-
-        def g(i):
-            return grads[i] if i >= 0 else None
-
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=([None] * nseg, [g(i) for i in i_proj], g(i_te), None))
-        layers, lgr = _layers(layer_t, spec.n_layers, [g(i) for i in i_layer])
+        gr = _EncGrads(spec, need, 7, tensors, device)
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
+        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
         cfg = _ragged_train_config(spec)
-        cfg.zero_buf, cfg.zero_bytes = ptr(pk.flat), pk.flat.numel() * 4
+        gr.attach(cfg)
         scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        seed = C.c_uint64(spec.seed & (2**64 - 1))
-        up = d_out if (d_out.dtype == torch.float32 and d_out.is_contiguous()) else d_out.float().contiguous()
+        up = _f32c(d_out)
         check(lib.egx_ragged_encode_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), layers, B, ptr(up), ctx.out_layout,
-                                        ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(g(i_lnw)), ptr(g(i_lnb)), lgr, int(spec.training), seed,
-                                        _stream()))
-        return (None, None, None, g(i_te), None, g(i_lnw), g(i_lnb)) + (None,) * nseg + tuple(g(i) for i in i_proj) + tuple(g(i) for i in i_layer)
+                                        ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, int(spec.training),
+                                        _seed64(spec.seed), _stream()))
+        return gr.result()
 
 
 def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
@@ -1127,12 +1115,7 @@ def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor]
     _check_out_layout(lengths, B, out_layout)
     if len(proj) != 2 * len(spec.segments):
         raise ValueError("ragged training on the wide path: every segment needs a projection")
-    lib = _lib.load()
-    segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-    sv, sc = C.c_size_t(0), C.c_size_t(0)
-    if (pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled()) or \
-            lib.egx_ragged_encode_train_workspace(C.byref(_ragged_train_config(spec)), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)) != 0:
-        # (the lengths are valid: ragged_lengths() checked them) a configuration the ragged wide path does not cover
+    if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_encode_train_workspace"):
         return _encoder_tokens_grouped(dataclasses.replace(spec, wcache=None), feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
                                        layer_params, out_layout)
     feats = [f.detach() for f in feats]      # (frozen backbone features: no gradient path on the wide projections)
@@ -1172,6 +1155,38 @@ def last_decoder_impl() -> str:
     return _last_dec_impl[0]
 
 
+def _dec_tensors(tokens, memory, emb, pe, layer_params, fc_w, fc_b):
+    """The tensors of one decoder call, on the device, fp32 and contiguous; tokens ((B, sy) int64, None: the caller checks its own) too.
+    Returns (tokens, memory, emb, pe, layer_t, fc_w, fc_b)."""
+    layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
+    fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
+    memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+    if tokens is not None:
+        if tokens.dtype != torch.int64 or not tokens.is_cuda:
+            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
+        tokens = tokens.contiguous()
+    return tokens, memory, emb, pe, layer_t, fc_w, fc_b
+
+
+def _dec_config(meta, d: int, V: int, sy: int, S: int, train: bool):
+    """egx_dec_config; train: with meta's dropout rates and device seed (a training entry point), else dropout-free (inference)."""
+    drop = (meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None) if train else (0.0, 0.0, None)
+    return _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], meta["n_layers"], V, sy, S, meta["ln_eps"], EGX_BF16, *drop)
+
+
+def _dec_layers(layer_t, n_layers: int, grads=None):
+    """The egx_dec_layer array (18 tensors per layer in _lib._DEC_LAYER_FIELDS order); with grads (the same order, None where not wanted)
+    also the egx_dec_layer_grads array: returns (layers, layer gradients)."""
+    def array(struct, ts):
+        arr = (struct * n_layers)()
+        for l in range(n_layers):
+            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
+                setattr(arr[l], name, ptr(ts[18 * l + k]))
+        return arr
+    layers = array(_lib.DecLayer, layer_t)
+    return layers if grads is None else (layers, array(_lib.DecLayerGrads, grads))
+
+
 def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b):
     """Inference decode (no autograd) over a packed ragged memory: tokens (B, sy) int64, memory (sum_b S_b, d) with S_b = mem_lengths[b]
     ((B,) int32 host tensor); clip b cross-attends to its own rows only. meta as DecoderFn's (p_drop / p_pos ignored: inference).
@@ -1184,24 +1199,14 @@ def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_p
     """The forward of decoder_ragged (ctx None: egx_decoder_ragged_fwd in one shared workspace) and of RaggedDecoderFn
     (egx_decoder_ragged_train_fwd into a `saved` of the call's own, kept in ctx for the backward)."""
     lib = _lib.load()
-    n_layers = meta["n_layers"]
-    layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
-    fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
-    memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
-    if tokens.dtype != torch.int64 or not tokens.is_cuda:
-        raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
-    tokens = tokens.contiguous()
+    tokens, memory, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(tokens, memory, emb, pe, layer_params, fc_w, fc_b)
     B, sy = tokens.shape
-    d = emb.shape[1]
+    V, d = emb.shape
     ml = mem_lengths.contiguous()
-    drop = (meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None) if ctx is not None else (0.0, 0.0, None)
-    cfg_args = (d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, int(ml.max()), meta["ln_eps"], EGX_BF16, *drop)
-    cfg = _lib.DecConfig(*cfg_args)
-    layers = (_lib.DecLayer * n_layers)()
-    for l in range(n_layers):
-        for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-            setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-    logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
+    cfg_args = (d, V, sy, int(ml.max()))
+    cfg = _dec_config(meta, *cfg_args, ctx is not None)
+    layers = _dec_layers(layer_t, meta["n_layers"])
+    logits = torch.empty((B * sy, V), dtype=torch.float32, device=memory.device)
     args = (C.byref(cfg), ptr(tokens), ptr(memory), ml.data_ptr(), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, ptr(logits))
     if ctx is None:
         nb = C.c_size_t(0)
@@ -1210,13 +1215,9 @@ def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_p
     else:
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_decoder_ragged_train_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(sv), C.byref(sc)))
-        need_grad = any(ctx.needs_input_grad)
-        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=memory.device) if need_grad else _workspace("dec_saved", memory.device, sv.value)
-        if need_grad and _POISON:
-            saved.fill_(255)
+        saved = _saved_buffer(any(ctx.needs_input_grad), "dec_saved", memory.device, sv.value)
         scratch = _workspace("dec_scratch", memory.device, sc.value)
-        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
-        check(lib.egx_decoder_ragged_train_fwd(*args, ptr(saved), ptr(scratch), int(meta["training"]), seed, _stream()))
+        check(lib.egx_decoder_ragged_train_fwd(*args, ptr(saved), ptr(scratch), int(meta["training"]), _seed64(meta["seed"]), _stream()))
         ctx.meta, ctx.cfg_args, ctx.B, ctx.ml, ctx.saved_buf, ctx.scratch_bytes = meta, cfg_args, B, ml, saved, sc.value
         ctx.save_for_backward(tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
     _last_dec_impl[0] = "ragged"
@@ -1283,7 +1284,7 @@ class PoolHeadFn(torch.autograd.Function):
         ln_w = sv.pop(0) if has_ln else None
         ln_b = sv.pop(0) if has_ln else None
         W = sv.pop(0) if has_W else None
-        d_out = d_out.contiguous().float()
+        d_out = _f32c(d_out)
         dev = d_out.device
         d_tokens = torch.empty((B, S, d), dtype=torch.float32, device=dev)
         need = ctx.needs_input_grad
@@ -1329,7 +1330,7 @@ class LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, W = ctx.saved_tensors[:2]
-        dy = dy.contiguous().float()
+        dy = _f32c(dy)
         if ctx.relu:                                  # d relu: zero the gradient where the output was clamped
             dy = dy.clone()
             check(lib.egx_relu_mask(ptr(dy), ptr(ctx.saved_tensors[2]), dy.numel(), _stream()))
@@ -1369,7 +1370,7 @@ class StackedLinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, Wst = ctx.saved_tensors
-        dy = dy.contiguous().float()
+        dy = _f32c(dy)
         M, K = x.shape
         N = Wst.shape[0]
         need = ctx.needs_input_grad
@@ -1418,7 +1419,7 @@ class LinearResidualFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, W = ctx.saved_tensors
-        dy = dy.contiguous().float()
+        dy = _f32c(dy)
         M, K = x.shape
         N = W.shape[0]
         need = ctx.needs_input_grad
@@ -1451,7 +1452,7 @@ class GeluFn(torch.autograd.Function):
     def backward(ctx, dh):
         lib = _lib.load()
         (z,) = ctx.saved_tensors
-        dh = dh.contiguous().float()
+        dh = _f32c(dh)
         dz = torch.empty_like(z)
         check(lib.egx_gelu_bwd(ptr(z), ptr(dh), ptr(dz), z.numel(), _stream()))
         return dz
@@ -1482,7 +1483,7 @@ class AttentionFn(torch.autograd.Function):
         lib = _lib.load()
         qkv, out, lse = ctx.saved_tensors
         B, S, H, inner = ctx.dims
-        d_out = d_out.contiguous().float()
+        d_out = _f32c(d_out)
         dqkv = torch.empty_like(qkv)
         check(lib.egx_attention_bwd(ptr(qkv), ptr(out), ptr(lse), ptr(d_out), ptr(dqkv), B, S, H, inner, 0.0, C.c_uint64(0), _stream()))
         return dqkv, None, None, None
@@ -1549,76 +1550,27 @@ class DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, tokens, memory, emb, pe, *rest):
         lib = _lib.load()
-        n_layers = meta["n_layers"]
-        layer_t = [_dev_f32(t, "decoder layer parameter") for t in rest[:18 * n_layers]]
-        fc_w, fc_b = _dev_f32(rest[18 * n_layers], "fc.weight"), _dev_f32(rest[18 * n_layers + 1], "fc.bias")
-        memory, emb, pe = _dev_f32(memory, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
-        if tokens.dtype != torch.int64 or not tokens.is_cuda:
-            raise _lib.EgxError("decoder tokens must be an int64 tensor on the GPU")
-        tokens = tokens.contiguous()
+        n = 18 * meta["n_layers"]
+        tokens, memory, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(tokens, memory, emb, pe, rest[:n], rest[n], rest[n + 1])
         B, sy = tokens.shape
-        d = emb.shape[1]
-        S = memory.shape[0] // B
-        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, S, meta["ln_eps"], EGX_BF16,
-                             meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None)
+        V, d = emb.shape
+        cfg_args = (d, V, sy, memory.shape[0] // B)
+        cfg = _dec_config(meta, *cfg_args, True)
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_decoder_workspace(C.byref(cfg), B, C.byref(sv), C.byref(sc)))
-        need_grad = any(ctx.needs_input_grad)
-        saved = torch.empty(max(sv.value, 256), dtype=torch.uint8, device=memory.device) if need_grad else _workspace("dec_saved", memory.device, sv.value)
+        saved = _saved_buffer(any(ctx.needs_input_grad), "dec_saved", memory.device, sv.value)
         scratch = _workspace("dec_scratch", memory.device, sc.value)
-        layers = (_lib.DecLayer * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-        logits = torch.empty((B * sy, emb.shape[0]), dtype=torch.float32, device=memory.device)
-        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
+        layers = _dec_layers(layer_t, meta["n_layers"])
+        logits = torch.empty((B * sy, V), dtype=torch.float32, device=memory.device)
         check(lib.egx_decoder_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
-                                  ptr(logits), ptr(saved), ptr(scratch), int(meta["training"]), seed, _stream()))
-        ctx.meta, ctx.cfg_args, ctx.B, ctx.saved_buf, ctx.scratch_bytes = meta, (d, sy, S), B, saved, sc.value
+                                  ptr(logits), ptr(saved), ptr(scratch), int(meta["training"]), _seed64(meta["seed"]), _stream()))
+        ctx.meta, ctx.cfg_args, ctx.B, ctx.saved_buf, ctx.scratch_bytes = meta, cfg_args, B, saved, sc.value
         ctx.save_for_backward(tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
         return logits
 
     @staticmethod
     def backward(ctx, d_logits):
-        lib = _lib.load()
-        meta = ctx.meta
-        n_layers = meta["n_layers"]
-        sv = list(ctx.saved_tensors)
-        tokens, memory, emb, pe = sv[:4]
-        layer_t = sv[4:4 + 18 * n_layers]
-        fc_w, fc_b = sv[4 + 18 * n_layers], sv[5 + 18 * n_layers]
-        d, sy, S = ctx.cfg_args
-        B = ctx.B
-        need = ctx.needs_input_grad      # (meta, tokens, memory, emb, pe, *layer_t, fc_w, fc_b)
-        device = d_logits.device
-        pk = _GradPacker()
-        i_emb = pk.add(emb, need[3])
-        i_layer = [pk.add(t, need[5 + i]) for i, t in enumerate(layer_t)]
-        i_fcw = pk.add(fc_w, need[5 + 18 * n_layers])
-        i_fcb = pk.add(fc_b, need[6 + 18 * n_layers])
-        grads = pk.materialise(device, zero=False)
-
-        def g(i):
-            return grads[i] if i >= 0 else None
-
-        d_memory = torch.empty_like(memory) if need[2] else None
-        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, emb.shape[0], sy, S, meta["ln_eps"], EGX_BF16,
-                             meta["p_drop"], meta["p_pos"], meta.get("seed_ptr") or None)
-        layers = (_lib.DecLayer * n_layers)()
-        lgr = (_lib.DecLayerGrads * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-                setattr(lgr[l], name, ptr(g(i_layer[18 * l + k])))
-        scratch = _workspace("dec_scratch", device, ctx.scratch_bytes)
-        dl = d_logits.float().contiguous()
-        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
-        check(lib.egx_decoder_bwd(C.byref(cfg), ptr(tokens), layers, ptr(fc_w), B, ptr(dl), ptr(ctx.saved_buf), ptr(scratch), ptr(d_memory),
-                                  ptr(g(i_emb)), lgr, ptr(g(i_fcw)), ptr(g(i_fcb)), ptr(pk.flat), pk.flat.numel() * 4, int(meta["training"]),
-                                  seed, _stream()))
-        if bucket_hook is not None and pk.total:
-            bucket_hook(pk.flat, 0, pk.total)        # the decoder's gradients are exchanged while the encoder's backward runs
-        return (None, None, d_memory, g(i_emb), None) + tuple(g(i) for i in i_layer) + (g(i_fcw), g(i_fcb))
+        return _decoder_backward(ctx, d_logits, ragged=False)
 
 
 class RaggedDecoderFn(torch.autograd.Function):
@@ -1634,41 +1586,39 @@ class RaggedDecoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_logits):
-        lib = _lib.load()
-        meta = ctx.meta
-        n_layers = meta["n_layers"]
-        sv = list(ctx.saved_tensors)
-        tokens, memory, emb, pe = sv[:4]
-        layer_t = sv[4:4 + 18 * n_layers]
-        fc_w, fc_b = sv[4 + 18 * n_layers], sv[5 + 18 * n_layers]
-        B = ctx.B
-        need = ctx.needs_input_grad      # (meta, tokens, memory, mem_lengths, emb, pe, *layer_t, fc_w, fc_b)
-        device = d_logits.device
-        pk = _GradPacker()
-        i_emb = pk.add(emb, need[4])
-        i_layer = [pk.add(t, need[6 + i]) for i, t in enumerate(layer_t)]
-        i_fcw = pk.add(fc_w, need[6 + 18 * n_layers])
-        i_fcb = pk.add(fc_b, need[7 + 18 * n_layers])
-        grads = pk.materialise(device, zero=False)
+        return _decoder_backward(ctx, d_logits, ragged=True)
 
-        def g(i):
-            return grads[i] if i >= 0 else None
 
-        d_memory = torch.empty_like(memory) if need[2] else None
-        cfg = _lib.DecConfig(*ctx.cfg_args)
-        layers = (_lib.DecLayer * n_layers)()
-        lgr = (_lib.DecLayerGrads * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
-                setattr(lgr[l], name, ptr(g(i_layer[18 * l + k])))
-        scratch = _workspace("dec_scratch", device, ctx.scratch_bytes)
-        dl = d_logits.float().contiguous()
-        seed = C.c_uint64(meta["seed"] & (2**64 - 1))
-        check(lib.egx_decoder_ragged_bwd(C.byref(cfg), ptr(tokens), ctx.ml.data_ptr(), layers, ptr(fc_w), B, ptr(dl), ptr(ctx.saved_buf),
-                                         ptr(scratch), ptr(d_memory), ptr(g(i_emb)), lgr, ptr(g(i_fcw)), ptr(g(i_fcb)), ptr(pk.flat),
-                                         pk.flat.numel() * 4, int(meta["training"]), seed, _stream()))
-        return (None, None, d_memory, None, g(i_emb), None) + tuple(g(i) for i in i_layer) + (g(i_fcw), g(i_fcb))
+def _decoder_backward(ctx, d_logits, ragged: bool):
+    """The backward of DecoderFn (egx_decoder_bwd, announced to bucket_hook as one slice) and of RaggedDecoderFn (egx_decoder_ragged_bwd):
+    ctx as their forwards left it, with cfg_args = (d, |V|, sy, S) of _dec_config."""
+    lib = _lib.load()
+    meta, B = ctx.meta, ctx.B
+    n_layers = meta["n_layers"]
+    sv = ctx.saved_tensors
+    tokens, memory, emb = sv[:3]
+    layer_t, fc_w, fc_b = sv[4:4 + 18 * n_layers], sv[4 + 18 * n_layers], sv[5 + 18 * n_layers]
+    # needs_input_grad: (meta, tokens, memory, [mem_lengths,] emb, pe, *layer_t, fc_w, fc_b); nothing for pe
+    need = ctx.needs_input_grad
+    i_emb = 4 if ragged else 3
+    pk = _GradPacker()
+    for t, want in zip((emb, *layer_t, fc_w, fc_b), (need[i_emb],) + need[i_emb + 2:]):
+        pk.add(t, want)
+    g_emb, *g_layer, g_fcw, g_fcb = pk.materialise(d_logits.device, zero=False)
+    d_memory = torch.empty_like(memory) if need[2] else None
+    cfg = _dec_config(meta, *ctx.cfg_args, True)
+    layers, lgr = _dec_layers(layer_t, n_layers, g_layer)
+    scratch = _workspace("dec_scratch", d_logits.device, ctx.scratch_bytes)
+    dl = _f32c(d_logits)
+    args = (layers, ptr(fc_w), B, ptr(dl), ptr(ctx.saved_buf), ptr(scratch), ptr(d_memory), ptr(g_emb), lgr, ptr(g_fcw), ptr(g_fcb),
+            ptr(pk.flat), pk.flat.numel() * 4, int(meta["training"]), _seed64(meta["seed"]), _stream())
+    if ragged:
+        check(lib.egx_decoder_ragged_bwd(C.byref(cfg), ptr(tokens), ctx.ml.data_ptr(), *args))
+    else:
+        check(lib.egx_decoder_bwd(C.byref(cfg), ptr(tokens), *args))
+        if bucket_hook is not None and pk.total:
+            bucket_hook(pk.flat, 0, pk.total)        # the decoder's gradients are exchanged while the encoder's backward runs
+    return (None, None, d_memory) + ((None,) if ragged else ()) + (g_emb, None, *g_layer, g_fcw, g_fcb)
 
 
 def decoder_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S: int, n_layers: int) -> bool:
@@ -1687,11 +1637,8 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
     rows, pe (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, n_steps) int64 and, with
     return_logits, logits (n_steps, B, |V|) fp32 (else None). The workspace comes from the caching allocator: the call can be captured."""
     lib = _lib.load()
-    n_layers = meta["n_layers"]
     with torch.no_grad():
-        layer_t = [_dev_f32(t, "decoder layer parameter") for t in layer_params]
-        fc_w, fc_b = _dev_f32(fc_w, "fc.weight"), _dev_f32(fc_b, "fc.bias")
-        mem2d, emb, pe = _dev_f32(mem2d, "memory"), _dev_f32(emb, "embedding.weight"), _dev_f32(pe, "positional rows")
+        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
         if start.dtype != torch.int64 or not start.is_cuda or start.dim() != 1:
             raise _lib.EgxError("decoder_generate: start must be a (B,) int64 tensor on the GPU")
         start = start.contiguous()
@@ -1699,11 +1646,8 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
         if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
             raise _lib.EgxError(f"decoder_generate: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
                                 f"d = {d}, n_steps = {n_steps}")
-        cfg = _lib.DecConfig(d, meta["n_heads"], meta["d_ff"], n_layers, V, 1, mem2d.shape[0] // B, meta["ln_eps"], EGX_BF16, 0.0, 0.0, None)
-        layers = (_lib.DecLayer * n_layers)()
-        for l in range(n_layers):
-            for k, name in enumerate(_lib._DEC_LAYER_FIELDS):
-                setattr(layers[l], name, ptr(layer_t[18 * l + k]))
+        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
+        layers = _dec_layers(layer_t, meta["n_layers"])
         nb = C.c_size_t(0)
         check(lib.egx_decoder_generate_workspace(C.byref(cfg), B, n_steps, C.byref(nb)))
         ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=mem2d.device)
@@ -1790,7 +1734,7 @@ class LinearCEFn(torch.autograd.Function):
         lib = _lib.load()
         x, W, dl = ctx.saved_tensors
         M, K, Cn = ctx.shape
-        g = g_loss.contiguous().float()
+        g = _f32c(g_loss)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.empty_like(W)
         db = torch.empty((Cn,), dtype=torch.float32, device=x.device) if ctx.has_b else None
@@ -1830,7 +1774,7 @@ class LayerNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         pre, stats, w = ctx.saved_tensors
-        dy = dy.contiguous().float()
+        dy = _f32c(dy)
         rows, d = pre.shape
         need = ctx.needs_input_grad
         dx = torch.empty_like(pre)
@@ -1853,7 +1797,7 @@ class DropoutFn(torch.autograd.Function):
         lib = _lib.load()
         y = _dev_f32(x, "x").clone()
         rows = y.numel() // y.shape[-1]
-        check(lib.egx_dropout(ptr(y), rows, y.shape[-1], float(p), C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+        check(lib.egx_dropout(ptr(y), rows, y.shape[-1], float(p), _seed64(seed), site, _stream()))
         ctx.cfg = (float(p), seed, site)
         return y
 
@@ -1861,9 +1805,9 @@ class DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         p, seed, site = ctx.cfg
-        g = dy.contiguous().float().clone()
+        g = _f32c(dy).clone()
         rows = g.numel() // g.shape[-1]
-        check(lib.egx_dropout(ptr(g), rows, g.shape[-1], p, C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+        check(lib.egx_dropout(ptr(g), rows, g.shape[-1], p, _seed64(seed), site, _stream()))
         return g, None, None, None
 
 
@@ -1888,7 +1832,7 @@ class EmbedPosFn(torch.autograd.Function):
             raise ValueError("target longer than the positional table")
         out = torch.empty((B * sy, d), dtype=torch.float32, device=emb.device)
         check(lib.egx_embed_pos_fwd(ptr(tok), ptr(emb), ptr(pe2), pe2.stride(0), float(scale), ptr(out), B, sy, d, V, float(p),
-                                    C.c_uint64(seed & (2**64 - 1)), _stream()))
+                                    _seed64(seed), _stream()))
         ctx.cfg = (float(scale), float(p), seed, V)
         ctx.save_for_backward(tok)
         return out
@@ -1900,11 +1844,11 @@ class EmbedPosFn(torch.autograd.Function):
         scale, p, seed, V = ctx.cfg
         if not ctx.needs_input_grad[1]:
             return None, None, None, None, None, None
-        dy = dy.contiguous().float()
+        dy = _f32c(dy)
         B, sy = tok.shape
         d = dy.shape[-1]
         d_emb = torch.zeros((V, d), dtype=torch.float32, device=dy.device)
-        check(lib.egx_embed_pos_bwd(ptr(tok), ptr(dy), ptr(d_emb), scale, B, sy, d, V, p, C.c_uint64(seed & (2**64 - 1)), _stream()))
+        check(lib.egx_embed_pos_bwd(ptr(tok), ptr(dy), ptr(d_emb), scale, B, sy, d, V, p, _seed64(seed), _stream()))
         return None, d_emb, None, None, None, None
 
 
@@ -1920,7 +1864,7 @@ class SelfAttnSmallFn(torch.autograd.Function):
         e = qkv.element_size()
         base = qkv.data_ptr()
         check(lib.egx_small_attention_fwd(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(out), d, B, sy, sy, H,
-                                          d // H, int(causal), float(p), C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+                                          d // H, int(causal), float(p), _seed64(seed), site, _stream()))
         ctx.cfg = (B, sy, H, int(causal), float(p), seed, site)
         ctx.save_for_backward(qkv)
         return out
@@ -1931,13 +1875,13 @@ class SelfAttnSmallFn(torch.autograd.Function):
         (qkv,) = ctx.saved_tensors
         B, sy, H, causal, p, seed, site = ctx.cfg
         d = qkv.shape[1] // 3
-        d_out = d_out.contiguous().float()
+        d_out = _f32c(d_out)
         dqkv = torch.empty_like(qkv)
         e = qkv.element_size()
         base, gb = qkv.data_ptr(), dqkv.data_ptr()
         check(lib.egx_small_attention_bwd(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(d_out), d,
                                           gb, gb + d * e, gb + 2 * d * e, B, sy, sy, H, d // H, causal, p,
-                                          C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+                                          _seed64(seed), site, _stream()))
         return dqkv, None, None, None, None, None, None, None
 
 
@@ -1953,7 +1897,7 @@ class CrossAttnSmallFn(torch.autograd.Function):
         e = kv.element_size()
         kb = kv.data_ptr()
         check(lib.egx_small_attention_fwd(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(out), d, B, sy, S, H, d // H, 0, float(p),
-                                          C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+                                          _seed64(seed), site, _stream()))
         ctx.cfg = (B, sy, S, H, float(p), seed, site)
         ctx.save_for_backward(q, kv)
         return out
@@ -1964,10 +1908,10 @@ class CrossAttnSmallFn(torch.autograd.Function):
         q, kv = ctx.saved_tensors
         B, sy, S, H, p, seed, site = ctx.cfg
         d = q.shape[1]
-        d_out = d_out.contiguous().float()
+        d_out = _f32c(d_out)
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         e = kv.element_size()
         kb, gb = kv.data_ptr(), dkv.data_ptr()
         check(lib.egx_small_attention_bwd(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(d_out), d, ptr(dq), gb, gb + d * e,
-                                          B, sy, S, H, d // H, 0, p, C.c_uint64(seed & (2**64 - 1)), site, _stream()))
+                                          B, sy, S, H, d // H, 0, p, _seed64(seed), site, _stream()))
         return dq, dkv, None, None, None, None, None, None, None

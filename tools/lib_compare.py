@@ -1,6 +1,13 @@
 """Bit-for-bit comparison of two builds of libegot2x.so on the d = 128 paths: has a refactor of the HOST code left every result alone?
 (tools/isa_diff.py answers the same question for device code.)
 usage: python tools/lib_compare.py <lib_a.so> <lib_b.so> [--out DIR] [--host] [--keep]
+       python tools/lib_compare.py --trees <dir_a> <dir_b> [--lib libegot2x.so] [--out DIR] [--keep]
+
+--trees compares two checkouts of the PYTHON bridge on ONE library (has a refactor of egot2_amd/functional.py left every result alone?): the
+children import egot2_amd from <dir_a> (twice) and <dir_b> (`git worktree add --detach <dir_a> <commit>` exports the commit to compare
+against) and all load --lib (default: this checkout's egot2_amd/libegot2x.so). Besides the arrays below every case then also records where
+its gradients live: last_grad_layout["late_floats"], the size of the latest encoder backward's flat buffer, and per gradient its offset in
+and the size of the flat storage behind it, so that "the gradient layout did not move" is compared and not assumed.
 
 For each of the runs a0 = lib_a, a1 = lib_a again, b = lib_b one FRESH child process is started with EGX_LIB set, one at a time, each under its
 own `timeout`; the first child that exits non-zero ends the comparison and nothing is started after it. A child runs the fixed case list
@@ -20,6 +27,13 @@ Cases (d = 128, three segments of d_in 256, d_ff 2048, 4 heads; f32s and bf16 ea
   e tiled T 110 (S 330: across the 320-row chunk), B 2, L 1                              f staged backward (bwd_stage 1, then 2) on shape a; again deterministic
   g ragged inference, lengths LENS at T_pad 16, L 2, with head and head-less             h ragged training, LENS, L 2, p 0.1, head + CE, feature gradients; L 1 head-less
   i ASD rows (out_tokens) with the fused token loss, B 3, T 15, L 2, weight cache (two steps: the cache filled, then valid)
+  n generic implementation forced: TTM logits with feature gradients; ASD rows (out_tokens sliced behind the library call), B 3, T 15, L 2,
+    deterministic (the generic backward sums its bias and LayerNorm gradients with float atomics otherwise: they would not repeat)
+Cases on the EgoT2-g HHI model (d 256, 4 heads, L 3 + 3, bf16, seeded weights; B 4, T_pad 16, lengths LENS, 2 target tokens):
+  j uniform encode_features + decode, p 0.1, forward + backward with d_memory; again under a recording functional.bucket_hook (its (lo, hi) calls compared)
+  k encode_features_ragged + decode_ragged, p 0.1, with d_memory: 'ttm' (packed rows) and 'asd' (frame-major tuples, decode() on S = 3)
+  l the calls of k under no_grad (their `saved` in the shared workspace), and eval-mode ragged inference (encode_features / decode with lengths)
+  m greedy_decode, 4 steps, with logits
 
 --host: no GPU. The children drive the host-only calls of tests/host_paths*.py (workspace sizes, implementation / slice answers, refusals)
 and the ragged workspace queries through a recording proxy; the parent compares return values, sizes and egx_last_error() texts."""
@@ -40,8 +54,17 @@ def gpu_child(path):
     import numpy as np
     import torch
     from torch import nn
-    from egot2_amd import _lib, functional as F_egx, hhi_asd, hhi_ttm
-    from egot2_amd.synth import hhi_args
+    import egot2_amd
+    from egot2_amd import _lib, functional as F_egx, hhi_asd, hhi_multitask, hhi_ttm
+    from egot2_amd.synth import HHI_G_VOCAB, hhi_args
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("egx_tests_util", os.path.join(ROOT, "tests", "util.py"))   # this checkout's, whichever tree is compared
+    util = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(util)
+    seeded_state_dict = util.seeded_state_dict
+    tree = os.environ.get("EGX_COMPARE_TREE")
+    assert tree is None or os.path.samefile(os.path.dirname(os.path.dirname(egot2_amd.__file__)), tree), egot2_amd.__file__
+    print(f"child: egot2_amd from {os.path.dirname(egot2_amd.__file__)}, library {_lib.LIB_PATH}")
     lib = _lib.load()
     cuda = torch.device("cuda")
     out = {}
@@ -52,13 +75,13 @@ def gpu_child(path):
         os.environ.update({k: str(v) for k, v in env.items()})
         lib.egx_tuning_reload()
 
-    def model_of(cls, L, p, compute, seed, det=False, learned_pe=False):
+    def model_of(cls, L, p, compute, seed, det=False, learned_pe=False, impl="auto"):
         torch.manual_seed(seed)
         m = cls(hhi_args(num_layers=L, dropout=p))
         if learned_pe:
             pe = m.pos_embed._buffers.pop("pe")
             m.pos_embed.pe = nn.Parameter(pe.clone())
-        m = m.to(cuda).set_compute(compute).set_deterministic(det).train()
+        m = m.to(cuda).set_compute(compute, impl).set_deterministic(det).train()
         m.pos_embed.dropout.p = 0.1 if p > 0 else 0.0
         m._egx_seed = lambda: 0x5EED0000 + seed
         return m
@@ -88,9 +111,13 @@ def gpu_child(path):
             finish()
             torch.cuda.synchronize()
             keep(tag, "launches_bwd2", lib.egx_launch_count(1))
+        flat = F_egx.last_grad_layout.get("flat")
+        keep(tag, "layout", [F_egx.last_grad_layout.get("late_floats", -1), -1 if flat is None else flat.numel()])
         for n, q in m.named_parameters():
             if q.grad is not None:
                 keep(tag, "grad/" + n, q.grad)
+                st = q.grad.untyped_storage()       # (offset in, size of) the flat buffer this gradient is a view of
+                keep(tag, "where/" + n, [(q.grad.data_ptr() - st.data_ptr()) // 4, st.nbytes() // 4])
         for k, f in enumerate(feats):
             if f.grad is not None:
                 keep(tag, f"dfeat{k}", f.grad)
@@ -150,6 +177,85 @@ def gpu_child(path):
         assert F_egx.last_encoder_impl() == "ragged", F_egx.last_encoder_impl()
         m = model_of(ASD, 1, 0.1, compute, s0 + 8)
         step(f"h_rows_{compute}", m, lambda: m.forward_features_ragged(*f16, lengths=lens))
+        f15g = feats_of(11, 3, 15, grad=True)
+        m = model_of(TTM, 2, 0.1, compute, s0 + 10, det=True, impl="generic")
+        step(f"n_{compute}", m, lambda: m.forward_features(*f15g), feats=f15g)
+        assert F_egx.last_encoder_impl() == "generic", F_egx.last_encoder_impl()
+        m = model_of(ASD, 2, 0.1, compute, s0 + 10, det=True, impl="generic")
+        step(f"n_rows_{compute}", m, lambda: m.forward_features(*f15))
+        assert F_egx.last_encoder_impl() == "generic", F_egx.last_encoder_impl()
+
+    # EgoT2-g HHI model: the wide encoder and the fused decoder, uniform and ragged
+    def g_model(seed, p=0.1):
+        m = hhi_multitask.TaskTranslationPromptTransformer(hhi_args(hidden_dim=256, num_heads=4, num_layers=3, dropout=p), HHI_G_VOCAB)
+        m.load_state_dict(seeded_state_dict(m, seed))
+        m.pos_embed.dropout.p = p
+        m = m.to(cuda).set_compute("bf16").train()
+        m._egx_seed = lambda: 0x5EED0000 + seed
+        return m
+
+    def targets(n, task, seed):
+        g = torch.Generator().manual_seed(seed)
+        return torch.stack([torch.full((n,), HHI_G_VOCAB[task]), torch.randint(5, 7, (n,), generator=g)], dim=1).to(cuda)
+
+    def g_step(tag, m, fwd):
+        """fwd() -> (memory, logits); the memory's gradient is recorded as dfeat0"""
+        held = []
+
+        def run():
+            mem, logits = fwd()
+            if torch.is_grad_enabled():
+                mem.retain_grad()
+            held.append(mem)
+            return mem, logits
+        step(tag, m, run, feats=held)
+
+    f16 = feats_of(14, 4, 16)
+    y4, frames = targets(4, "ttm", 21), lens[:, 0]
+    y_asd = targets(int(frames.sum()), "asd", 22)
+    S = F_egx.ragged_lengths(lens, 4, [16, 16, 16]).sum(1)
+
+    def uniform(m):
+        mem = m.encode_features("ttm", *f16)
+        return mem, m.decode(y4, mem)
+
+    def ragged_ttm(m):
+        mem = m.encode_features_ragged("ttm", *f16, lengths=lens)
+        return mem, m.decode_ragged(y4, mem, S)
+
+    def ragged_asd(m):
+        mem = m.encode_features_ragged("asd", *f16, lengths=frames)
+        return mem, m.decode(y_asd, mem)
+
+    m = g_model(31)
+    g_step("j", m, lambda: uniform(m))
+    assert F_egx.last_encoder_impl() == "wide" and F_egx.last_decoder_impl() == "fused", (F_egx.last_encoder_impl(), F_egx.last_decoder_impl())
+    buckets = []
+    F_egx.bucket_hook = lambda flat, lo, hi: buckets.append((flat.numel(), lo, hi))
+    try:
+        m.zero_grad(set_to_none=True)
+        g_step("j_hook", m, lambda: uniform(m))
+    finally:
+        F_egx.bucket_hook = None
+    keep("j_hook", "buckets", buckets)
+    for tag, fwd in (("k_ttm", ragged_ttm), ("k_asd", ragged_asd)):
+        m = g_model(32)
+        g_step(tag, m, lambda: fwd(m))
+        assert F_egx.last_encoder_impl() == "ragged", F_egx.last_encoder_impl()
+    with torch.no_grad():
+        m = g_model(32)
+        g_step("l_ttm", m, lambda: ragged_ttm(m))
+        g_step("l_asd", m, lambda: ragged_asd(m))
+        m.eval()
+
+        def infer():
+            mem = m.encode_features("ttm", *f16, lengths=lens)
+            return mem, m.decode(y4, mem, memory_lengths=S)
+        g_step("l_infer", m, infer)
+        assert F_egx.last_encoder_impl() == "ragged" and F_egx.last_decoder_impl() == "ragged"
+        mem = m.encode_features("ttm", *f16)
+        step("m", m, lambda: m.greedy_decode(mem, HHI_G_VOCAB["ttm"], 4, return_logits=True))
+        assert F_egx.last_decoder_impl() == "generate", F_egx.last_decoder_impl()
     np.savez(path, **out)
     print(f"{os.path.relpath(path, ROOT)}: {len(out)} arrays")
 
@@ -201,11 +307,15 @@ def host_child(path):
 
 
 # ---- parent ----------------------------------------------------------------------------------------------------------------------------------
-def run_children(libs, out_dir, host):
+def run_children(libs, out_dir, host, trees=None):
+    """libs: (run, library) pairs; trees: {run: checkout the child imports egot2_amd (and tests.util) from}, default this one"""
     paths = {}
     for run, lib in libs:
         paths[run] = os.path.join(out_dir, run + (".json" if host else ".npz"))
-        env = dict(os.environ, EGX_LIB=os.path.abspath(lib), PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+        tree = os.path.abspath(trees[run]) if trees else ROOT
+        env = dict(os.environ, EGX_LIB=os.path.abspath(lib), PYTHONPATH=tree + os.pathsep + os.environ.get("PYTHONPATH", ""))
+        if trees:
+            env["EGX_COMPARE_TREE"] = tree
         cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT), sys.executable, os.path.abspath(__file__), "--host-child" if host else "--child", paths[run]]
         rc = subprocess.run(cmd, env=env, cwd=ROOT).returncode
         if rc != 0:
@@ -278,10 +388,17 @@ def main(argv):
         return host_child(argv[2])
     host = "--host" in argv
     out_dir = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "build", "lib_compare")
-    lib_a, lib_b = [x for x in argv[1:] if x.endswith(".so")][:2]
     os.makedirs(out_dir, exist_ok=True)
-    print(f"# lib_a = {os.path.relpath(lib_a, ROOT)}, lib_b = {os.path.relpath(lib_b, ROOT)} ({'host calls' if host else 'GPU cases'})")
-    paths = run_children([("a0", lib_a), ("a1", lib_a), ("b", lib_b)], out_dir, host)
+    if "--trees" in argv:
+        i = argv.index("--trees")
+        lib_a = lib_b = argv[argv.index("--lib") + 1] if "--lib" in argv else os.path.join(ROOT, "egot2_amd", "libegot2x.so")
+        trees = {"a0": argv[i + 1], "a1": argv[i + 1], "b": argv[i + 2]}
+        print(f"# tree_a = {os.path.relpath(argv[i + 1], ROOT)}, tree_b = {os.path.relpath(argv[i + 2], ROOT)}, both on {os.path.relpath(lib_a, ROOT)} (GPU cases)")
+    else:
+        lib_a, lib_b = [x for x in argv[1:] if x.endswith(".so")][:2]
+        trees = None
+        print(f"# lib_a = {os.path.relpath(lib_a, ROOT)}, lib_b = {os.path.relpath(lib_b, ROOT)} ({'host calls' if host else 'GPU cases'})")
+    paths = run_children([("a0", lib_a), ("a1", lib_a), ("b", lib_b)], out_dir, host, trees)
     rc = compare_host(paths) if host else compare_gpu(paths)
     if "--keep" not in argv:        # (a few hundred MB of gradients)
         for f in paths.values():
