@@ -1588,6 +1588,50 @@ struct GenHeadParams {
     int B, d, V;
     float scale;
 };
+// The fp32 vocabulary head of R target rows held in LDS (sx [R][d]) -> sl [R][V] = x fc_w^T + fc_b, shared by the greedy and the beam
+// head: GH_WAVES waves, each with GH_ROWS vocabulary rows in flight per pass; per (vocabulary row, target row) one explicit fma chain over
+// the lane's columns, then the wave sum. A row's logits depend on neither R nor its slot r.
+template <int R>
+__device__ __forceinline__ void head_logits(const float* fc_w, const float* fc_b, const float* sx, float* sl,
+                                            int d, int V, int lane, int wave) {
+    // GH_ROWS vocabulary rows per wave and pass: their fc_w loads and wave reductions are independent and overlap (one row at a time the loop
+    // is a chain of load and shuffle latencies: 206 us per launch at V = 600, d = 512)
+    for (int v0 = wave; v0 < V; v0 += GH_WAVES * GH_ROWS) {
+        float a[GH_ROWS][R];
+#pragma unroll
+        for (int u = 0; u < GH_ROWS; ++u)
+#pragma unroll
+            for (int r = 0; r < R; ++r) a[u][r] = 0.f;
+        for (int c = lane * 4; c < d; c += 256) {
+            float4 w[GH_ROWS];
+#pragma unroll
+            for (int u = 0; u < GH_ROWS; ++u) {
+                const int v = v0 + u * GH_WAVES < V ? v0 + u * GH_WAVES : v0;       // (a row past the end re-reads row v0; its sums are dropped)
+                w[u] = *reinterpret_cast<const float4*>(fc_w + (size_t)v * d + c);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float4 xv = *reinterpret_cast<const float4*>(sx + r * d + c);
+                // one explicit fma chain per (row, clip): left to the compiler's contraction (and its packed fp32 pairs) the clips of a
+                // workgroup rounded differently by their slot, and permuting a batch moved logits by an ulp
+#pragma unroll
+                for (int u = 0; u < GH_ROWS; ++u)
+                    a[u][r] = fmaf(w[u].w, xv.w, fmaf(w[u].z, xv.z, fmaf(w[u].y, xv.y, fmaf(w[u].x, xv.x, a[u][r]))));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GH_ROWS; ++u) {
+            const int v = v0 + u * GH_WAVES;
+            const float bias = fc_b && v < V ? fc_b[v] : 0.f;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float sum = wsum64d(a[u][r]);
+                if (lane == 0 && v < V) sl[r * V + v] = sum + bias;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p) {
     extern __shared__ __align__(16) float gh_sm[];
     float* sx = gh_sm;                          // [GH_CLIPS][d]
@@ -1602,42 +1646,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p
         *reinterpret_cast<float4*>(sx + i) = v;
     }
     __syncthreads();
-    // GH_ROWS vocabulary rows per wave and pass: their fc_w loads and wave reductions are independent and overlap (one row at a time the loop
-    // is a chain of load and shuffle latencies: 206 us per launch at V = 600, d = 512)
-    for (int v0 = wave; v0 < V; v0 += GH_WAVES * GH_ROWS) {
-        float a[GH_ROWS][GH_CLIPS];
-#pragma unroll
-        for (int u = 0; u < GH_ROWS; ++u)
-#pragma unroll
-            for (int r = 0; r < GH_CLIPS; ++r) a[u][r] = 0.f;
-        for (int c = lane * 4; c < d; c += 256) {
-            float4 w[GH_ROWS];
-#pragma unroll
-            for (int u = 0; u < GH_ROWS; ++u) {
-                const int v = v0 + u * GH_WAVES < V ? v0 + u * GH_WAVES : v0;       // (a row past the end re-reads row v0; its sums are dropped)
-                w[u] = *reinterpret_cast<const float4*>(p.fc_w + (size_t)v * d + c);
-            }
-#pragma unroll
-            for (int r = 0; r < GH_CLIPS; ++r) {
-                const float4 xv = *reinterpret_cast<const float4*>(sx + r * d + c);
-                // one explicit fma chain per (row, clip): left to the compiler's contraction (and its packed fp32 pairs) the clips of a
-                // workgroup rounded differently by their slot, and permuting a batch moved logits by an ulp
-#pragma unroll
-                for (int u = 0; u < GH_ROWS; ++u)
-                    a[u][r] = fmaf(w[u].w, xv.w, fmaf(w[u].z, xv.z, fmaf(w[u].y, xv.y, fmaf(w[u].x, xv.x, a[u][r]))));
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < GH_ROWS; ++u) {
-            const int v = v0 + u * GH_WAVES;
-            const float bias = p.fc_b && v < V ? p.fc_b[v] : 0.f;
-#pragma unroll
-            for (int r = 0; r < GH_CLIPS; ++r) {
-                const float sum = wsum64d(a[u][r]);
-                if (lane == 0 && v < V) sl[r * V + v] = sum + bias;
-            }
-        }
-    }
+    head_logits<GH_CLIPS>(p.fc_w, p.fc_b, sx, sl, d, V, lane, wave);
     __syncthreads();
     if (wave >= nb) return;
     const int b = b0 + wave;
@@ -1834,6 +1843,443 @@ int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const 
         hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.d = d; hp.V = pl.V; hp.scale = sqrtf((float)d);
         hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
         EGX_LAUNCH_CHECK();
+    }
+    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- beam search with a K/V cache (egx_decoder_beam) ----
+// egx_decoder_generate's step over B * W rows (row b * W + w: hypothesis slot w of clip b, decode()'s (B, sy) layout, so every row-wise stage
+// and the cross-attention with Sq = W serve it unchanged) with two new kernels: the cached self-attention reads a hypothesis' history through
+// an ancestry table instead of gathering the cache, and the head ranks the W * V candidates of a clip and writes the next step's rows.
+namespace {
+
+constexpr int BEAM_MAX_W = DA_MAXQ, BEAM_DEPTH = GEN_MAX_STEPS, BEAM_LDS_LIMIT = 64 * 1024;
+
+struct BeamAttnParams {
+    const void* qkv;        // (B * W, 3d): the new rows' q | k | v (fp32 or bf16)
+    void* cache;            // (B, W, n_steps, 2d): row (b, s, j) = k | v of the row slot s of clip b ran at step j; written once
+    const int* anc;         // (B, W, BEAM_DEPTH): anc[b][w][j], j < t = the slot that ran row j of hypothesis w's history
+    bf16_t* o;              // (B * W, d)
+    int B, W, H, d, t, n_steps;
+    float scale;
+};
+
+// gen_self_attn_kernel with the ancestry lookup: one wave per (row, head), four per workgroup; lane j < t holds key row j of the
+// hypothesis, read from cache row (b, anc[b][w][j], j), lane t the new row, which lanes c < DH also append as cache row (b, w, t). Same lane
+// roles and summation order: with W = 1 (every slot 0) the same bits.
+template <int DH, bool F32>
+__global__ __launch_bounds__(256) void beam_self_attn_kernel(BeamAttnParams p) {
+    __shared__ __align__(16) float sQ[4][DH];   // (read as float4)
+    __shared__ float sP[4][64];
+    __shared__ int sS[4][64];                   // slot of history row j
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rh = blockIdx.x * 4 + wave;
+    if (rh >= p.B * p.W * p.H) return;          // (no barrier below: every wave works alone)
+    const int r = rh / p.H, h = rh % p.H, t = p.t, d = p.d, b = r / p.W;
+    const size_t nrow = (size_t)r * 3 * d + h * DH;                         // q; k at + d, v at + 2d
+    const size_t ccol = (size_t)h * DH;                                      // cache row (b, s, j) at ((b * W + s) * n_steps + j) * 2d: k; v at + d
+    const size_t cnew = ((size_t)r * p.n_steps + t) * 2 * d + ccol;
+    const bool cached = lane < t;
+    int slot = cached ? p.anc[(size_t)r * BEAM_DEPTH + lane] : 0;
+    slot = slot < 0 ? 0 : (slot >= p.W ? p.W - 1 : slot);                   // (the head writes 0 .. W - 1)
+    sS[wave][lane] = slot;
+    float kr[DH];
+    {
+        const void* kb = cached ? (const void*)p.cache : p.qkv;
+        const size_t krow = cached ? (((size_t)b * p.W + slot) * p.n_steps + lane) * 2 * d + ccol : nrow + d;
+#pragma unroll
+        for (int c = 0; c < DH; c += 8) {
+            float t8[8];
+            load8<F32>(kb, krow + c, t8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
+        }
+    }
+    float vnew = 0.f;
+    if (lane < DH) {                            // append row t (read by later steps only)
+        const float knew = load1<F32>(p.qkv, nrow + d + lane);
+        vnew = load1<F32>(p.qkv, nrow + 2 * d + lane);
+        store1<F32>(p.cache, cnew + lane, knew);
+        store1<F32>(p.cache, cnew + d + lane, vnew);
+        sQ[wave][lane] = load1<F32>(p.qkv, nrow + lane);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const bool live = lane <= t;
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < DH; c += 4) {
+        const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][c]);
+        s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
+    }
+    s = live ? s * p.scale : -INFINITY;
+    const float m = wmax64(s);
+    const float e = live ? __expf(s - m) : 0.f;
+    sP[wave][lane] = e / wsum64d(e);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < DH) {
+        float acc = 0.f;
+        const size_t v0 = (size_t)b * p.W * p.n_steps * 2 * d + ccol + d + lane;
+        for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + ((size_t)sS[wave][j] * p.n_steps + j) * 2 * d);
+        acc += sP[wave][t] * vnew;
+        p.o[(size_t)r * d + h * DH + lane] = f2bf(acc);
+    }
+}
+
+int beam_self_attn(BeamAttnParams p, int dh, bool f32, hipStream_t st) {
+    EGX_CHECK(p.t >= 0 && p.t < p.n_steps && p.n_steps <= BEAM_DEPTH, "beam self-attention: step %d of %d (at most %d)", p.t, p.n_steps, BEAM_DEPTH);
+    EGX_CHECK(p.W >= 1 && p.W <= BEAM_MAX_W, "beam self-attention: W = %d (1..%d)", p.W, BEAM_MAX_W);
+    p.scale = 1.f / sqrtf((float)dh);
+    const dim3 grid(cdiv(p.B * p.W * p.H, 4)), block(256);
+    if (dh == 64 && !f32) hipLaunchKernelGGL((beam_self_attn_kernel<64, false>), grid, block, 0, st, p);
+    else if (dh == 32 && !f32) hipLaunchKernelGGL((beam_self_attn_kernel<32, false>), grid, block, 0, st, p);
+    else if (dh == 64) hipLaunchKernelGGL((beam_self_attn_kernel<64, true>), grid, block, 0, st, p);
+    else if (dh == 32) hipLaunchKernelGGL((beam_self_attn_kernel<32, true>), grid, block, 0, st, p);
+    else EGX_CHECK(false, "beam self-attention: head dim %d (32 or 64)", dh);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+// step 0's rows: x32 / x16 [b * W + w] = emb[start[b]] * scale + pe[0] (dec_embed_kernel's expression) for every slot, and the scores
+// 0 for slot 0, -inf for the others: only slot 0 is live
+__global__ __launch_bounds__(256) void beam_init_kernel(const int64_t* __restrict__ start, const float* __restrict__ emb, const float* __restrict__ pe,
+                                                        float scale, float* __restrict__ x32, bf16_t* __restrict__ x16, float* __restrict__ score,
+                                                        int rows, int W, int d, int V) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;          // one float4 each
+    if (i >= (size_t)rows * (d / 4)) return;
+    const int row = (int)(i / (d / 4)), c = (int)(i % (d / 4)) * 4;
+    const int64_t t = start[row / W];
+    float4 e = make_float4(0, 0, 0, 0);
+    if (t >= 0 && t < V) e = *reinterpret_cast<const float4*>(emb + (size_t)t * d + c);
+    const float4 pp = *reinterpret_cast<const float4*>(pe + c);
+    float o[4] = {e.x * scale + pp.x, e.y * scale + pp.y, e.z * scale + pp.z, e.w * scale + pp.w};
+    *reinterpret_cast<float4*>(x32 + (size_t)row * d + c) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<uint2*>(x16 + (size_t)row * d + c) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+    if (c == 0) score[row] = row % W == 0 ? 0.f : -INFINITY;
+}
+
+// The beam head of one step, one workgroup per clip: the W rows' logits (head_logits, as the greedy head), per row the fp32 log-softmax
+// and candidate scores score[w] + logp[w][v] in LDS, then W rounds of a block-wide arg-max with removal over the W * V candidates (ties to
+// the lowest flat index w * V + v; a NaN ranks as -inf and never wins), then the survivors' token / parent / score, their ancestry and
+// token histories copied from the parents' (double-buffered: a survivor reads another slot's row), and the next step's input rows
+// emb[tok] * scale + pe_next. pe_next null: the last step.
+struct BeamHeadParams {
+    const float* x; const float* fc_w; const float* fc_b; const float* emb; const float* pe_next;
+    const float* score_in; float* score_out;            // (B, W); may alias: a clip's scores are read before the ranking, written after it
+    const int* anc_in; int* anc_out;                    // (B, W, BEAM_DEPTH)
+    const int64_t* hist_in; int64_t* hist_out;          // (B, W, ld): tokens 0 .. t of each hypothesis
+    int hist_in_ld, hist_out_ld;
+    int64_t* step_tok; int32_t* step_par; float* step_score;        // (B, W) of this step, or null
+    float* step_logits;                                 // (B, W, V) of this step, or null
+    float* x32; bf16_t* x16;                            // (B * W, d): next step's input rows
+    int B, W, d, V, t;
+    float scale;
+};
+constexpr int BH_THREADS = 64 * GH_WAVES;
+template <int R>
+__global__ __launch_bounds__(BH_THREADS) void beam_head_kernel(BeamHeadParams p) {
+    extern __shared__ __align__(16) float bh_sm[];
+    float* sx = bh_sm;                          // [R][d]; free after the logits: the ranking's scratch
+    float* sl = bh_sm + R * p.d;                // [R][V]: logits, then candidate scores (flat index w * V + v for the W live rows)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = p.d, V = p.V, W = p.W, t = p.t, b = blockIdx.x;
+    const size_t r0 = (size_t)b * W;
+    for (int i = tid * 4; i < R * d; i += 4 * BH_THREADS) {
+        const int r = i / d;
+        float4 v = make_float4(0, 0, 0, 0);
+        if (r < W) v = *reinterpret_cast<const float4*>(p.x + r0 * d + i);
+        *reinterpret_cast<float4*>(sx + i) = v;
+    }
+    __syncthreads();
+    head_logits<R>(p.fc_w, p.fc_b, sx, sl, d, V, lane, wave);
+    __syncthreads();
+    float* rv = sx;                             // [2][GH_WAVES] the waves' bests of a round (by round parity)
+    int* ri = reinterpret_cast<int*>(sx + 2 * GH_WAVES);
+    float* selv = sx + 4 * GH_WAVES;            // [BEAM_MAX_W] the winners
+    int* seli = reinterpret_cast<int*>(sx + 4 * GH_WAVES + BEAM_MAX_W);
+    if (wave < W) {                             // wave w: row w -> score[w] + log_softmax(logits[w]) in place
+        float* row = sl + wave * V;
+        const float prev = p.score_in[r0 + wave];
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) {
+            const float x = row[v];
+            if (p.step_logits) p.step_logits[(r0 + wave) * V + v] = x;
+            if (x == x) m = fmaxf(m, x);
+        }
+        m = wmax64(m);
+        float sum = 0.f;
+        for (int v = lane; v < V; v += 64) {
+            const float x = row[v];
+            if (x == x) sum += expf(x - m);
+        }
+        const float lse = logf(wsum64d(sum));
+        for (int v = lane; v < V; v += 64) {
+            const float x = row[v];
+            row[v] = x == x ? prev + ((x - m) - lse) : -INFINITY;
+        }
+    }
+    __syncthreads();
+    const int n = W * V;                        // <= 8192: candidate k of this thread is flat index tid + k * BH_THREADS, k < 16
+    uint32_t removed = 0;
+    for (int round = 0; round < W; ++round) {
+        float best = -INFINITY;
+        int idx = 0x7fffffff;
+        for (int k = 0, i = tid; i < n; ++k, i += BH_THREADS) {     // ascending within a thread: `>` keeps the lowest index
+            if ((removed >> k) & 1u) continue;
+            float x = sl[i];
+            if (!(x == x)) x = -INFINITY;
+            if (x > best || idx == 0x7fffffff) { best = x; idx = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(idx, o, 64);
+            if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+        }
+        float* rvp = rv + (round & 1) * GH_WAVES;
+        int* rip = ri + (round & 1) * GH_WAVES;
+        if (lane == 0) { rvp[wave] = best; rip[wave] = idx; }
+        __syncthreads();
+        best = rvp[0]; idx = rip[0];
+#pragma unroll
+        for (int w = 1; w < GH_WAVES; ++w) {
+            const float ob = rvp[w];
+            const int oi = rip[w];
+            if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+        }
+        if (idx >= n) idx = 0;                  // (cannot happen: W <= W * V candidates are left in every round)
+        if ((idx & (BH_THREADS - 1)) == tid) removed |= 1u << (idx / BH_THREADS);
+        if (tid == 0) { selv[round] = best; seli[round] = idx; }
+    }
+    __syncthreads();
+    if (tid < W) {
+        const int flat = seli[tid], par = flat / V;
+        p.score_out[r0 + tid] = selv[tid];
+        if (p.step_tok) p.step_tok[r0 + tid] = (int64_t)(flat - par * V);
+        if (p.step_par) p.step_par[r0 + tid] = par;
+        if (p.step_score) p.step_score[r0 + tid] = selv[tid];
+    }
+    // survivor k: history rows 0 .. t - 1 from its parent, row t the parent's slot (ancestry) / the new token (history)
+    for (int i = tid; i < W * (t + 1); i += BH_THREADS) {
+        const int k = i / (t + 1), j = i - k * (t + 1);
+        const int flat = seli[k], par = flat / V;
+        p.anc_out[(r0 + k) * BEAM_DEPTH + j] = j < t ? p.anc_in[(r0 + par) * BEAM_DEPTH + j] : par;
+        p.hist_out[(r0 + k) * p.hist_out_ld + j] = j < t ? p.hist_in[(r0 + par) * p.hist_in_ld + j] : (int64_t)(flat - par * V);
+    }
+    if (p.pe_next && wave < W) {
+        const int flat = seli[wave], tok = flat - (flat / V) * V;
+        const float scale = p.scale;
+        for (int c = lane * 4; c < d; c += 256) {
+            const float4 e = *reinterpret_cast<const float4*>(p.emb + (size_t)tok * d + c);
+            const float4 pp = *reinterpret_cast<const float4*>(p.pe_next + c);
+            float o[4] = {e.x * scale + pp.x, e.y * scale + pp.y, e.z * scale + pp.z, e.w * scale + pp.w};
+            *reinterpret_cast<float4*>(p.x32 + (r0 + wave) * d + c) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<uint2*>(p.x16 + (r0 + wave) * d + c) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+        }
+    }
+}
+
+size_t beam_head_lds(int W, int d, int V) { return (size_t)(W <= 4 ? 4 : 8) * (d + V) * sizeof(float); }
+
+int beam_head(const BeamHeadParams& p, hipStream_t st) {
+    const size_t lds = beam_head_lds(p.W, p.d, p.V);
+    EGX_CHECK(lds <= (size_t)BEAM_LDS_LIMIT, "beam head: %zu bytes of LDS for W = %d, d = %d, V = %d (at most %d)", lds, p.W, p.d, p.V, BEAM_LDS_LIMIT);
+    if (p.W <= 4) hipLaunchKernelGGL(beam_head_kernel<4>, dim3(p.B), dim3(BH_THREADS), lds, st, p);
+    else hipLaunchKernelGGL(beam_head_kernel<8>, dim3(p.B), dim3(BH_THREADS), lds, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+struct BPlan {
+    int B, W, n, S, d, H, dff, L, V;
+    size_t M, Nm;
+    size_t zero, mem16, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
+    size_t score, anc[2], hist[2];
+    GLayer layer[16];
+    size_t bytes;
+};
+
+// The checks of the call and of the workspace query, then egx_decoder_generate's layout over M = B * W target rows (the memory and its
+// K | V stay B * S rows) plus the beam's state. Every per-row buffer takes a multiple of 256 bytes per row, so the workspace is exactly
+// linear in B * W and in n_steps (the caches only).
+int make_bplan(const egx_dec_config* c, int B, int n_steps, int W, BPlan& pl) {
+    EGX_CHECK(c, "null decoder config");
+    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_beam: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
+    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_beam: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
+    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_beam: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
+    EGX_CHECK(W >= 1 && W <= BEAM_MAX_W, "egx_decoder_beam: W = %d (1..%d)", W, BEAM_MAX_W);
+    EGX_CHECK(W <= c->vocab, "egx_decoder_beam: W = %d exceeds vocab = %d (a step has only vocab distinct continuations of the start token)", W, c->vocab);
+    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits with W target rows per clip (cfg->sy is not read)
+        egx_dec_config one = *c;
+        one.sy = W;
+        DPlan dp;
+        if (make_dplan(&one, B, dp)) return 1;
+    }
+    EGX_CHECK(beam_head_lds(W, c->d_model, c->vocab) <= (size_t)BEAM_LDS_LIMIT, "egx_decoder_beam: the head needs %zu bytes of LDS (at most %d)",
+              beam_head_lds(W, c->d_model, c->vocab), BEAM_LDS_LIMIT);
+    EGX_CHECK((size_t)B * W <= (size_t)0x7fffffff / (size_t)(3 * c->d_model) && (size_t)B * c->S <= (size_t)0x7fffffff / (size_t)(2 * c->d_model),
+              "egx_decoder_beam: B = %d with W = %d, S = %d is too large", B, W, c->S);
+    memset(&pl, 0, sizeof(pl));
+    pl.B = B; pl.W = W; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
+    pl.M = (size_t)B * W; pl.Nm = (size_t)B * c->S;
+    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
+    size_t cur = 0;
+    pl.zero = dtake(cur, 1024);
+    pl.mem16 = dtake(cur, Nm * d * 2);
+    for (int l = 0; l < pl.L; ++l) {
+        GLayer& o = pl.layer[l];
+        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
+        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
+        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
+        o.kv = dtake(cur, Nm * 2 * d * 2);
+        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
+    }
+    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
+    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
+    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 256);
+    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
+    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
+    pl.xL32 = dtake(cur, M * d * 4);
+    pl.score = dtake(cur, M * 256);
+    for (int u = 0; u < 2; ++u) {
+        pl.anc[u] = dtake(cur, M * BEAM_DEPTH * sizeof(int));
+        pl.hist[u] = dtake(cur, M * BEAM_DEPTH * sizeof(int64_t));
+    }
+    pl.bytes = cur;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_beam_workspace(const egx_dec_config* cfg, int B, int n_steps, int W, size_t* bytes) {
+    BPlan pl;
+    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    if (bytes) *bytes = pl.bytes;
+    return 0;
+}
+
+int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                     const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
+                     float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits, void* workspace,
+                     void* stream) {
+    BPlan pl;
+    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && scores_out && workspace, "egx_decoder_beam: null pointer argument");
+    EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_beam: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, M = (int)pl.M, dh = d / pl.H;
+    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
+    const void* zero = at<char>(ws, pl.zero);
+    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
+    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
+    {   // every weight -> bf16 once, one launch (as egx_decoder_generate)
+        WideCastBatch cb;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
+        }
+        if (wide_cast_flush(cb, st)) return 1;
+    }
+    float* x32 = at<float>(ws, pl.x32);
+    bf16_t* x16 = at<bf16_t>(ws, pl.x16);
+    float* score = at<float>(ws, pl.score);
+    hipLaunchKernelGGL(beam_init_kernel, dim3((unsigned)(((size_t)M * (d / 4) + 255) / 256)), dim3(256), 0, st, start, emb, pe, sqrtf((float)d), x32,
+                       x16, score, M, W, d, pl.V);
+    EGX_LAUNCH_CHECK();
+    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* Wt, int rows, int N, int K, const float* bias, float* Cf, bf16_t* Cb,
+                     int relu, const float* residual) -> int {
+        WideGemmParams g;
+        g.A = A; g.B = Wt; g.M = rows; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
+        g.residual = residual; g.ldr = N; g.zero_page = zero;
+        return wide_gemm_nt(g, s_);
+    };
+    auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
+                  const float* residual) -> int { return nt_on(st, A, lda, Wt, M, N, K, bias, Cf, Cb, relu, residual); };
+    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
+        WideLnFwdParams lp;
+        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = M; lp.d = d;
+        return wide_ln_fwd(lp, st);
+    };
+    // the memory's K | V, once per layer and per CLIP (B * S rows): on the side stream beside step 0 (eager), on the caller's stream under capture
+    SideStream& SS = side_stream();
+    SideJoin sj(SS, st);
+    const bool side = side_wanted(SS, st);
+    if (side) {
+        if (SS.order(st, SS.s)) return 1;
+        sj.forked = true;
+    }
+    for (int l = 0; l < pl.L; ++l) {
+        const GLayer& o = pl.layer[l];
+        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
+        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
+    }
+    for (int t = 0; t < n_steps; ++t) {
+        const bool last_step = t + 1 == n_steps;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            const bool last = l + 1 == pl.L;
+            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
+            if (f32_self) {
+                GemmParams g;
+                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = M; g.N = 3 * d; g.K = d;
+                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
+                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
+            } else if (nt(x16, d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
+            {
+                BeamAttnParams a;
+                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
+                a.cache = at<char>(ws, o.cache); a.anc = cat<int>(ws, pl.anc[t & 1]); a.o = at<bf16_t>(ws, pl.sa);
+                a.B = B; a.W = W; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
+                if (beam_self_attn(a, dh, f32_self, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
+            // cross-attention of the clip's W new rows onto its S memory rows: dec_attn with Sq = W
+            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
+            if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
+            {
+                DecAttnParams a;
+                memset(&a, 0, sizeof(a));
+                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
+                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
+                a.B = B; a.H = pl.H; a.Sq = W; a.Sk = pl.S; a.causal = 0;
+                if (dec_attn<false>(a, dh, false, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
+            // FFN
+            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
+            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? at<float>(ws, pl.xL32) : x32, last ? nullptr : x16)) return 1;
+        }
+        BeamHeadParams hp;
+        memset(&hp, 0, sizeof(hp));
+        hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.emb = emb;
+        hp.pe_next = last_step ? nullptr : pe + (size_t)(t + 1) * pe_stride;
+        hp.score_in = score; hp.score_out = last_step ? scores_out : score;
+        hp.anc_in = cat<int>(ws, pl.anc[t & 1]); hp.anc_out = at<int>(ws, pl.anc[(t + 1) & 1]);
+        hp.hist_in = cat<int64_t>(ws, pl.hist[t & 1]); hp.hist_in_ld = BEAM_DEPTH;
+        hp.hist_out = last_step ? tokens_out : at<int64_t>(ws, pl.hist[(t + 1) & 1]); hp.hist_out_ld = last_step ? n_steps : BEAM_DEPTH;
+        const size_t so = (size_t)t * M;
+        hp.step_tok = step_tokens ? step_tokens + so : nullptr; hp.step_par = step_parents ? step_parents + so : nullptr;
+        hp.step_score = step_scores ? step_scores + so : nullptr; hp.step_logits = step_logits ? step_logits + so * pl.V : nullptr;
+        hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.W = W; hp.d = d; hp.V = pl.V; hp.t = t; hp.scale = sqrtf((float)d);
+        if (beam_head(hp, st)) return 1;
     }
     sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
     return 0;

@@ -140,14 +140,9 @@ class DecoderMixin:
         F_egx._last_dec_impl[0] = "grouped"
         return out
 
-    def _egx_greedy(self, start: torch.Tensor, encoded_x: torch.Tensor, n_steps: int, *, embedding: nn.Embedding, pos_embed,
-                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False):
-        """Greedy generation (inference only), the loop of predict_ac (HOI/models/multitask/video_model_builder.py:201-220, 263-274) and of
-        HOI/models/lta/lta_models_seqdecoder.py:181-201: start (B,) int64 tokens, encoded_x (S, B, d) memory -> tokens (B, n_steps) int64 (the
-        n_steps tokens after `start`) and, with return_logits, each step's last-row logits (n_steps, B, |V|). Ties go to the lowest index.
-        One egx_decoder_generate call where it serves the configuration (last_decoder_impl() == "generate": K/V cache, argmax on the
-        device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first."""
-        self._egx_check_inference("it to greedy_decode", subject="greedy generation is")
+    @staticmethod
+    def _egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, what: str):
+        """The argument checks greedy generation and beam search share (host work only); returns (S, B, d) of the memory."""
         if not isinstance(n_steps, int) or isinstance(n_steps, bool) or n_steps < 1:
             raise ValueError(f"n_steps must be a positive int, got {n_steps!r}")
         if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
@@ -163,7 +158,18 @@ class DecoderMixin:
         if d != embedding.weight.shape[1]:
             raise ValueError(f"memory width {d} != embedding width {embedding.weight.shape[1]}")
         if not (encoded_x.is_cuda and start.is_cuda and embedding.weight.is_cuda):
-            raise ValueError("greedy generation runs on the GPU only (no CPU fallback): memory, start tokens and the model must be on the GPU")
+            raise ValueError(f"{what} runs on the GPU only (no CPU fallback): memory, start tokens and the model must be on the GPU")
+        return S, B, d
+
+    def _egx_greedy(self, start: torch.Tensor, encoded_x: torch.Tensor, n_steps: int, *, embedding: nn.Embedding, pos_embed,
+                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False):
+        """Greedy generation (inference only), the loop of predict_ac (HOI/models/multitask/video_model_builder.py:201-220, 263-274) and of
+        HOI/models/lta/lta_models_seqdecoder.py:181-201: start (B,) int64 tokens, encoded_x (S, B, d) memory -> tokens (B, n_steps) int64 (the
+        n_steps tokens after `start`) and, with return_logits, each step's last-row logits (n_steps, B, |V|). Ties go to the lowest index.
+        One egx_decoder_generate call where it serves the configuration (last_decoder_impl() == "generate": K/V cache, argmax on the
+        device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first."""
+        self._egx_check_inference("it to greedy_decode", subject="greedy generation is")
+        S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, "greedy generation")
         V = embedding.weight.shape[0]
         post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
         if (post_ln and not getattr(self, "egx_composed_decoder", False)
@@ -194,17 +200,55 @@ class DecoderMixin:
         """Greedy generation from the (S, B, d) decoder memory: `start_token` an int or a (B,) int64 tensor; returns tokens (B, n_steps) and,
         with return_logits, (tokens, logits (n_steps, B, |V|)). The 40-step verb / noun schedule of lta_models_seqdecoder.py:186-201 is two
         index operations on the result. Eval mode only; see _egx_greedy."""
-        if isinstance(start_token, torch.Tensor):
-            start = start_token
-        else:
-            if not isinstance(start_token, int) or isinstance(start_token, bool):
-                raise ValueError(f"start_token must be an int or a (B,) int64 tensor, got {type(start_token).__name__}")
-            if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
-                raise ValueError("encoded_x must be the (S, B, d) decoder memory")
-            start = torch.full((encoded_x.shape[1],), start_token, dtype=torch.int64, device=encoded_x.device)
+        start = _start_tokens(start_token, encoded_x)
         tokens, logits = self._egx_greedy(start, encoded_x, n_steps, embedding=self.embedding, pos_embed=self.pos_embed,
                                           decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits)
         return (tokens, logits) if return_logits else tokens
+
+    def beam_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, beam_width: int, return_scores: bool = False,
+                    return_trace: bool = False):
+        """Beam search from the (S, B, d) decoder memory: the `beam_width` best fixed-length continuations of `start_token` (an int or a (B,)
+        int64 tensor) per clip, best first: tokens (B, beam_width, n_steps) int64; with return_scores also their scores (B, beam_width), the
+        fp32 sums of log_softmax(logits)[token]; with return_trace also a functional.BeamTrace (step_tokens, step_parents, step_scores,
+        step_logits). The K = 5 candidates of the LTA evaluation (HOI/tasks/lta/long_term_anticipation.py:233-388) are
+        beam_decode(memory, start, 40, 5). One egx_decoder_beam call (last_decoder_impl() == "beam": K/V cache read through an ancestry
+        table, ranking on the device, no host synchronisation); outside its limits a ValueError: there is no Python search to fall back on.
+        Eval mode only; validation is host work and runs first."""
+        self._egx_check_inference("it to beam_decode", subject="beam search is")
+        if not isinstance(beam_width, int) or isinstance(beam_width, bool) or not 1 <= beam_width <= 8:
+            raise ValueError(f"beam_width must be an int in 1..8, got {beam_width!r}")
+        embedding, decoder = self.embedding, self.transformer_decoder
+        V = embedding.weight.shape[0]
+        if beam_width > V:
+            raise ValueError(f"beam_width = {beam_width} exceeds the vocabulary of {V} words")
+        start = _start_tokens(start_token, encoded_x)
+        S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, self.pos_embed, "beam search")
+        compute, d_ff = getattr(self, "egx_compute", "f32"), decoder.layers[0].linear1.out_features
+        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
+        if not (post_ln and F_egx.decoder_beam_supported(compute, d, self.n_heads, d_ff, S, len(decoder.layers), V, n_steps, beam_width)):
+            raise ValueError(f"beam search is outside egx_decoder_beam's limits (compute bf16, post-LN layers, d_model a multiple of 128 in "
+                             f"[256, 1024], head dim 32 or 64, d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= 1024, "
+                             f"n_steps <= 64, beam_width <= 8): got compute {compute}, d = {d}, {self.n_heads} heads, d_ff = {d_ff}, S = {S}, "
+                             f"{len(decoder.layers)} layers, vocabulary {V}, n_steps = {n_steps}, beam_width = {beam_width}")
+        meta, params = self._egx_decoder_args(decoder, self.pos_embed, self.n_heads, 0.0)
+        mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
+        tokens, scores, trace = F_egx.decoder_beam(meta, start, mem2d, embedding.weight, self.pos_embed.pe[:n_steps, 0, :], params, self.fc.weight,
+                                                   self.fc.bias, n_steps, beam_width, return_trace)
+        out = (tokens,) + ((scores,) if return_scores else ()) + ((trace,) if return_trace else ())
+        return out if len(out) > 1 else tokens
+
+
+def _start_tokens(start_token, encoded_x):
+    """`start_token` of greedy_decode / beam_decode as a tensor: a (B,) tensor as it is, an int for every clip of the (S, B, d) memory."""
+    if isinstance(start_token, torch.Tensor):
+        start = start_token
+    else:
+        if not isinstance(start_token, int) or isinstance(start_token, bool):
+            raise ValueError(f"start_token must be an int or a (B,) int64 tensor, got {type(start_token).__name__}")
+        if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
+            raise ValueError("encoded_x must be the (S, B, d) decoder memory")
+        start = torch.full((encoded_x.shape[1],), start_token, dtype=torch.int64, device=encoded_x.device)
+    return start
 
 
 def _argmax_lowest(logits: torch.Tensor) -> torch.Tensor:

@@ -1151,7 +1151,8 @@ _last_dec_impl = ["none"]
 def last_decoder_impl() -> str:
     """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
     operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd), "grouped" (a ragged memory decoded one length group at a
-    time), "generate" (greedy generation in one egx_decoder_generate call) or "loop" (greedy generation as a prefix loop over decode())."""
+    time), "generate" (greedy generation in one egx_decoder_generate call), "loop" (greedy generation as a prefix loop over decode()) or
+    "beam" (beam search in one egx_decoder_beam call)."""
     return _last_dec_impl[0]
 
 
@@ -1657,6 +1658,56 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
                                        n_steps, ptr(tokens), ptr(logits), ptr(ws), _stream()))
     _last_dec_impl[0] = "generate"
     return tokens, logits
+
+
+def decoder_beam_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int, beam_width: int) -> bool:
+    """Configurations egx_decoder_beam serves (include/egot2x.h): egx_decoder_generate's limits, 1 <= beam_width <= 8, beam_width <= vocab."""
+    return decoder_generate_supported(compute, d, n_heads, d_ff, S, n_layers, vocab, n_steps) and 1 <= beam_width <= min(8, vocab)
+
+
+class BeamTrace:
+    """The selection trace of one decoder_beam call: step_tokens / step_parents / step_scores (n_steps, B, W) of every surviving slot
+    (int64 / int32 parent slot at the step before / fp32) and step_logits (n_steps, B, W, |V|), the logits row of each PARENT slot."""
+    __slots__ = ("step_tokens", "step_parents", "step_scores", "step_logits")
+
+    def __init__(self, step_tokens, step_parents, step_scores, step_logits):
+        self.step_tokens, self.step_parents, self.step_scores, self.step_logits = step_tokens, step_parents, step_scores, step_logits
+
+
+def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, beam_width: int,
+                 return_trace: bool = False):
+    """Beam search in ONE asynchronous call (egx_decoder_beam; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory rows, pe
+    (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, W, n_steps) int64 (best first),
+    scores (B, W) fp32 and, with return_trace, a BeamTrace (else None). The workspace comes from the caching allocator: the call can be
+    captured."""
+    lib = _lib.load()
+    with torch.no_grad():
+        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
+        if start.dtype != torch.int64 or not start.is_cuda or start.dim() != 1:
+            raise _lib.EgxError("decoder_beam: start must be a (B,) int64 tensor on the GPU")
+        start = start.contiguous()
+        B, (V, d), W = start.shape[0], emb.shape, beam_width
+        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
+            raise _lib.EgxError(f"decoder_beam: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
+                                f"d = {d}, n_steps = {n_steps}")
+        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
+        layers = _dec_layers(layer_t, meta["n_layers"])
+        nb = C.c_size_t(0)
+        check(lib.egx_decoder_beam_workspace(C.byref(cfg), B, n_steps, W, C.byref(nb)))
+        dev = mem2d.device
+        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=dev)
+        tokens = torch.empty((B, W, n_steps), dtype=torch.int64, device=dev)
+        scores = torch.empty((B, W), dtype=torch.float32, device=dev)
+        trace = None
+        if return_trace:
+            trace = BeamTrace(torch.empty((n_steps, B, W), dtype=torch.int64, device=dev), torch.empty((n_steps, B, W), dtype=torch.int32, device=dev),
+                              torch.empty((n_steps, B, W), dtype=torch.float32, device=dev),
+                              torch.empty((n_steps, B, W, V), dtype=torch.float32, device=dev))
+        tr = [ptr(getattr(trace, k)) if trace is not None else None for k in BeamTrace.__slots__]
+        check(lib.egx_decoder_beam(C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
+                                   n_steps, W, ptr(tokens), ptr(scores), *tr, ptr(ws), _stream()))
+    _last_dec_impl[0] = "beam"
+    return tokens, scores, trace
 
 
 def weighted_cross_entropy(logits, target, weight=None):

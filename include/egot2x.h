@@ -610,6 +610,31 @@ int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps
 int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
                          const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
                          float* logits_out /* may be NULL */, void* workspace, void* stream);
+/* ---- ABI v18: beam search (the W best sequences per clip) with a K/V cache ----
+ * The LTA evaluation scores K = 5 candidate sequences per clip (HOI/tasks/lta/long_term_anticipation.py:233-388, model.generate(x, k=5)); the
+ * reference draws them by sampling every position independently from the logits of the one greedy path
+ * (HOI/models/lta/lta_models_seqdecoder.py:204-216) and marks the gap at :197 ("#todo: better decoding ways"). This call is the standard
+ * answer, as ONE asynchronous call on egx_decoder_generate's step: fixed-length beam search (the schedules have no end-of-sequence word: no
+ * early stop, no length penalty). Rows are (B, W), row b * W + w = hypothesis slot w of clip b. A hypothesis' score is the fp32 sum over its
+ * steps of log_softmax(logits)[token]. At step 0 only slot 0 is live (score 0; slots 1 .. W - 1 start at -inf). At every step the W * vocab
+ * candidates score[w] + logp[w][v] of a clip are ranked and the W best survive in descending order; ties go to the LOWEST flat index
+ * w * vocab + v, a NaN never wins. tokens_out (B, W, n_steps) int64: tokens_out[b][k] the k-th best final sequence (the n_steps tokens after
+ * start[b]), scores_out (B, W) fp32 its score. The optional step_* outputs are the selection trace of step t, each (n_steps, B, W, ...):
+ * step_tokens / step_parents (int32: the parent's slot at step t - 1) / step_scores of every surviving slot, and step_logits (n_steps, B, W,
+ * vocab): for each PARENT slot w the logits row the head computed at step t (at step 0 every slot holds the start token's row).
+ * Arithmetic as egx_decoder_generate (with W = 1 the same bits: tokens, logits); the memory is converted and projected once per clip, not
+ * once per hypothesis; the per-layer K/V cache (B, W, n_steps, 2d) is written once and read through an ancestry table, never gathered.
+ * Limits: egx_decoder_generate's (compute EGX_BF16, the fused decoder's shapes, 1 <= n_steps <= 64, 1 <= vocab <= 1024, p_drop = p_pos = 0),
+ * 1 <= W <= 8 and W <= vocab; cfg->sy is not read. Every refusal is made before any device work, by the call and by the workspace query
+ * alike. No value is read on the host: the call can be captured in a hipGraph and replayed on new start / memory contents; the memory's
+ * K | V projections use the side stream as egx_decoder_generate's do. */
+int egx_decoder_beam_workspace(const egx_dec_config* cfg, int B, int n_steps, int W, size_t* bytes);
+int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                     const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W,
+                     int64_t* tokens_out /* (B, W, n_steps) */, float* scores_out /* (B, W) */,
+                     int64_t* step_tokens /* (n_steps, B, W) or NULL */, int32_t* step_parents /* (n_steps, B, W) or NULL */,
+                     float* step_scores /* (n_steps, B, W) or NULL */, float* step_logits /* (n_steps, B, W, vocab) or NULL */,
+                     void* workspace, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
