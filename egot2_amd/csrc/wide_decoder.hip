@@ -1578,7 +1578,8 @@ int gen_self_attn(GenAttnParams p, int dh, bool f32, hipStream_t st) {
 // The greedy head of one step: logits = x fc_w^T + fc_b in fp32 for GH_CLIPS clips per workgroup (fc_w streams once per workgroup; GH_WAVES
 // waves, each with GH_ROWS vocabulary rows in flight per pass; the clips' rows in LDS), then one wave per clip: argmax (lowest index on ties; a NaN never wins), the token to tokens_out,
 // the logits to logits_out when given, and the next step's input row emb[tok] * scale + pe_next as fp32 and bf16 (dec_embed_kernel's
-// expression). pe_next null: the last step.
+// expression). pe_next null: the last step. With a word list (words, n_words) the head computes the listed rows only and every other logit
+// is -inf: the argmax runs over the set.
 constexpr int GH_CLIPS = 4, GH_WAVES = 8, GH_ROWS = 4, GEN_MAX_STEPS = 64, GEN_MAX_VOCAB = 1024;
 struct GenHeadParams {
     const float* x; const float* fc_w; const float* fc_b; const float* emb; const float* pe_next;
@@ -1587,28 +1588,37 @@ struct GenHeadParams {
     float* x32; bf16_t* x16;                    // (B, d): next step's input rows
     int B, d, V;
     float scale;
+    const int32_t* words; int n_words;          // the step's word list (ascending indices, the count by value), or null: every word
 };
 // The fp32 vocabulary head of R target rows held in LDS (sx [R][d]) -> sl [R][V] = x fc_w^T + fc_b, shared by the greedy and the beam
 // head: GH_WAVES waves, each with GH_ROWS vocabulary rows in flight per pass; per (vocabulary row, target row) one explicit fma chain over
-// the lane's columns, then the wave sum. A row's logits depend on neither R nor its slot r.
-template <int R>
-__device__ __forceinline__ void head_logits(const float* fc_w, const float* fc_b, const float* sx, float* sl,
-                                            int d, int V, int lane, int wave) {
+// the lane's columns, then the wave sum. A row's logits depend on neither R nor its slot r. LISTED: entry k of the pass is vocabulary row
+// list[k] (clamped to 0 .. V - 1), k < nv: only the listed rows of fc_w are read, and a listed word's logit is the chain and wave sum the
+// unlisted loop runs for it: the same bits. Not LISTED: nv = V and entry k is row k.
+template <int R, bool LISTED>
+__device__ __forceinline__ void head_logits_rows(const float* fc_w, const float* fc_b, const float* sx, float* sl,
+                                                 int d, int V, const int32_t* list, int nv, int lane, int wave) {
     // GH_ROWS vocabulary rows per wave and pass: their fc_w loads and wave reductions are independent and overlap (one row at a time the loop
     // is a chain of load and shuffle latencies: 206 us per launch at V = 600, d = 512)
-    for (int v0 = wave; v0 < V; v0 += GH_WAVES * GH_ROWS) {
+    for (int v0 = wave; v0 < nv; v0 += GH_WAVES * GH_ROWS) {
         float a[GH_ROWS][R];
+        int vr[GH_ROWS];
 #pragma unroll
-        for (int u = 0; u < GH_ROWS; ++u)
+        for (int u = 0; u < GH_ROWS; ++u) {
+            const int k = v0 + u * GH_WAVES < nv ? v0 + u * GH_WAVES : v0;          // (an entry past the end re-reads entry v0; its sums are dropped)
+            int v = k;
+            if (LISTED) {
+                v = __builtin_amdgcn_readfirstlane(list[k]);             // (k is the wave's: one scalar index, as the unlisted row is)
+                v = v < 0 ? 0 : (v >= V ? V - 1 : v);
+            }
+            vr[u] = v;
 #pragma unroll
             for (int r = 0; r < R; ++r) a[u][r] = 0.f;
+        }
         for (int c = lane * 4; c < d; c += 256) {
             float4 w[GH_ROWS];
 #pragma unroll
-            for (int u = 0; u < GH_ROWS; ++u) {
-                const int v = v0 + u * GH_WAVES < V ? v0 + u * GH_WAVES : v0;       // (a row past the end re-reads row v0; its sums are dropped)
-                w[u] = *reinterpret_cast<const float4*>(fc_w + (size_t)v * d + c);
-            }
+            for (int u = 0; u < GH_ROWS; ++u) w[u] = *reinterpret_cast<const float4*>(fc_w + (size_t)vr[u] * d + c);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const float4 xv = *reinterpret_cast<const float4*>(sx + r * d + c);
@@ -1621,14 +1631,28 @@ __device__ __forceinline__ void head_logits(const float* fc_w, const float* fc_b
         }
 #pragma unroll
         for (int u = 0; u < GH_ROWS; ++u) {
-            const int v = v0 + u * GH_WAVES;
-            const float bias = fc_b && v < V ? fc_b[v] : 0.f;
+            const bool on = v0 + u * GH_WAVES < nv;
+            const int v = vr[u];
+            const float bias = fc_b && on ? fc_b[v] : 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const float sum = wsum64d(a[u][r]);
-                if (lane == 0 && v < V) sl[r * V + v] = sum + bias;
+                if (lane == 0 && on) sl[r * V + v] = sum + bias;
             }
         }
+    }
+}
+// Every thread of the workgroup calls it. list null: sl = the logits of all V words. list given: the `count` (clamped to 0 .. V) listed
+// words' logits, every other entry of sl -inf (filled first, behind a barrier of its own: the argmax, log-softmax and ranking read sl whole).
+template <int R>
+__device__ __forceinline__ void head_logits(const float* fc_w, const float* fc_b, const float* sx, float* sl, int d, int V,
+                                            const int32_t* list, int count, int lane, int wave) {
+    if (list) {
+        for (int i = threadIdx.x; i < R * V; i += 64 * GH_WAVES) sl[i] = -INFINITY;
+        __syncthreads();
+        head_logits_rows<R, true>(fc_w, fc_b, sx, sl, d, V, list, count < 0 ? 0 : (count > V ? V : count), lane, wave);
+    } else {
+        head_logits_rows<R, false>(fc_w, fc_b, sx, sl, d, V, nullptr, V, lane, wave);
     }
 }
 
@@ -1646,7 +1670,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p
         *reinterpret_cast<float4*>(sx + i) = v;
     }
     __syncthreads();
-    head_logits<GH_CLIPS>(p.fc_w, p.fc_b, sx, sl, d, V, lane, wave);
+    head_logits<GH_CLIPS>(p.fc_w, p.fc_b, sx, sl, d, V, p.words, p.n_words, lane, wave);
     __syncthreads();
     if (wave >= nb) return;
     const int b = b0 + wave;
@@ -1679,6 +1703,22 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p
 }
 
 struct GLayer { size_t w_sa_in, w_sa_o, w_q, w_kv, w_ca_o, w1, w2, kv, cache; };
+
+// The host checks of a token schedule (egx_decoder_generate_sched / egx_decoder_beam_sched), before any device work: period rows (0: no
+// schedule), counts a HOST int[period] with every count in 1 .. vocab, words the DEVICE int32[period][vocab] table (not read here). W > 0:
+// beam search, whose step 0 has only counts[0] continuations of the one live slot.
+constexpr int SCHED_MAX_PERIOD = 64;
+int check_sched(const char* who, int period, const int* counts, const int32_t* words, int vocab, int W) {
+    EGX_CHECK(period >= 0 && period <= SCHED_MAX_PERIOD, "%s: period = %d (0..%d)", who, period, SCHED_MAX_PERIOD);
+    if (period == 0) return 0;
+    EGX_CHECK(counts && words, "%s: period = %d with a null counts or words", who, period);
+    for (int p = 0; p < period; ++p)
+        EGX_CHECK(counts[p] >= 1 && counts[p] <= vocab, "%s: counts[%d] = %d (1..vocab = %d)", who, p, counts[p], vocab);
+    EGX_CHECK(W <= counts[0], "%s: W = %d exceeds counts[0] = %d (at step 0 only slot 0 is live: the step has only counts[0] continuations)",
+              who, W, counts[0]);
+    return 0;
+}
+
 struct GPlan {
     int B, n, S, d, H, dff, L, V;
     size_t Nm;
@@ -1723,22 +1763,13 @@ int make_gplan(const egx_dec_config* c, int B, int n_steps, GPlan& pl) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps, size_t* bytes) {
+// The one body of egx_decoder_generate (period = 0) and egx_decoder_generate_sched: step t's head takes row t % period of the schedule.
+int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                 const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
+                 float* logits_out, void* workspace, void* stream, int period, const int* counts, const int32_t* words) {
     GPlan pl;
     if (make_gplan(cfg, B, n_steps, pl)) return 1;
-    if (bytes) *bytes = pl.bytes;
-    return 0;
-}
-
-int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
-                         const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
-                         float* logits_out, void* workspace, void* stream) {
-    GPlan pl;
-    if (make_gplan(cfg, B, n_steps, pl)) return 1;
+    if (check_sched("egx_decoder_generate_sched", period, counts, words, pl.V, 0)) return 1;
     EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && workspace, "egx_decoder_generate: null pointer argument");
     EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_generate: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
     hipStream_t st = (hipStream_t)stream;
@@ -1841,11 +1872,38 @@ int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const 
         hp.tok = tokens_out + t; hp.tok_stride = n_steps;
         hp.logits = logits_out ? logits_out + (size_t)t * B * pl.V : nullptr;
         hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.d = d; hp.V = pl.V; hp.scale = sqrtf((float)d);
+        hp.words = period ? words + (size_t)(t % period) * pl.V : nullptr; hp.n_words = period ? counts[t % period] : 0;
         hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
         EGX_LAUNCH_CHECK();
     }
     sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps, size_t* bytes) {
+    GPlan pl;
+    if (make_gplan(cfg, B, n_steps, pl)) return 1;
+    if (bytes) *bytes = pl.bytes;
+    return 0;
+}
+
+int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                         const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
+                         float* logits_out, void* workspace, void* stream) {
+    return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream, 0,
+                        nullptr, nullptr);
+}
+
+int egx_decoder_generate_sched(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe,
+                               int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps,
+                               int64_t* tokens_out, float* logits_out, void* workspace, void* stream, int period, const int* counts,
+                               const int32_t* words) {
+    return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream,
+                        period, counts, words);
 }
 
 }  // extern "C"
@@ -1966,7 +2024,8 @@ __global__ __launch_bounds__(256) void beam_init_kernel(const int64_t* __restric
 // and candidate scores score[w] + logp[w][v] in LDS, then W rounds of a block-wide arg-max with removal over the W * V candidates (ties to
 // the lowest flat index w * V + v; a NaN ranks as -inf and never wins), then the survivors' token / parent / score, their ancestry and
 // token histories copied from the parents' (double-buffered: a survivor reads another slot's row), and the next step's input rows
-// emb[tok] * scale + pe_next. pe_next null: the last step.
+// emb[tok] * scale + pe_next. pe_next null: the last step. With a word list the other words' logits are -inf: exp gives them 0, so the
+// log-softmax normalises over the set, and their candidates (-inf) lose to the W * n_words finite ones.
 struct BeamHeadParams {
     const float* x; const float* fc_w; const float* fc_b; const float* emb; const float* pe_next;
     const float* score_in; float* score_out;            // (B, W); may alias: a clip's scores are read before the ranking, written after it
@@ -1978,6 +2037,7 @@ struct BeamHeadParams {
     float* x32; bf16_t* x16;                            // (B * W, d): next step's input rows
     int B, W, d, V, t;
     float scale;
+    const int32_t* words; int n_words;                  // the step's word list as GenHeadParams', or null: every word
 };
 constexpr int BH_THREADS = 64 * GH_WAVES;
 template <int R>
@@ -1995,7 +2055,7 @@ __global__ __launch_bounds__(BH_THREADS) void beam_head_kernel(BeamHeadParams p)
         *reinterpret_cast<float4*>(sx + i) = v;
     }
     __syncthreads();
-    head_logits<R>(p.fc_w, p.fc_b, sx, sl, d, V, lane, wave);
+    head_logits<R>(p.fc_w, p.fc_b, sx, sl, d, V, p.words, p.n_words, lane, wave);
     __syncthreads();
     float* rv = sx;                             // [2][GH_WAVES] the waves' bests of a round (by round parity)
     int* ri = reinterpret_cast<int*>(sx + 2 * GH_WAVES);
@@ -2153,23 +2213,14 @@ int make_bplan(const egx_dec_config* c, int B, int n_steps, int W, BPlan& pl) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int egx_decoder_beam_workspace(const egx_dec_config* cfg, int B, int n_steps, int W, size_t* bytes) {
+// The one body of egx_decoder_beam (period = 0) and egx_decoder_beam_sched: step t's head takes row t % period of the schedule.
+int beam_run(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+             const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
+             float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits, void* workspace,
+             void* stream, int period, const int* counts, const int32_t* words) {
     BPlan pl;
     if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
-    if (bytes) *bytes = pl.bytes;
-    return 0;
-}
-
-int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
-                     const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
-                     float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits, void* workspace,
-                     void* stream) {
-    BPlan pl;
-    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    if (check_sched("egx_decoder_beam_sched", period, counts, words, pl.V, W)) return 1;
     EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && scores_out && workspace, "egx_decoder_beam: null pointer argument");
     EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_beam: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
     hipStream_t st = (hipStream_t)stream;
@@ -2279,10 +2330,38 @@ int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const floa
         hp.step_tok = step_tokens ? step_tokens + so : nullptr; hp.step_par = step_parents ? step_parents + so : nullptr;
         hp.step_score = step_scores ? step_scores + so : nullptr; hp.step_logits = step_logits ? step_logits + so * pl.V : nullptr;
         hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.W = W; hp.d = d; hp.V = pl.V; hp.t = t; hp.scale = sqrtf((float)d);
+        hp.words = period ? words + (size_t)(t % period) * pl.V : nullptr; hp.n_words = period ? counts[t % period] : 0;
         if (beam_head(hp, st)) return 1;
     }
     sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_beam_workspace(const egx_dec_config* cfg, int B, int n_steps, int W, size_t* bytes) {
+    BPlan pl;
+    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    if (bytes) *bytes = pl.bytes;
+    return 0;
+}
+
+int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                     const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
+                     float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits, void* workspace,
+                     void* stream) {
+    return beam_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, W, tokens_out, scores_out, step_tokens, step_parents,
+                    step_scores, step_logits, workspace, stream, 0, nullptr, nullptr);
+}
+
+int egx_decoder_beam_sched(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                           const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
+                           float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits,
+                           void* workspace, void* stream, int period, const int* counts, const int32_t* words) {
+    return beam_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, W, tokens_out, scores_out, step_tokens, step_parents,
+                    step_scores, step_logits, workspace, stream, period, counts, words);
 }
 
 }  // extern "C"

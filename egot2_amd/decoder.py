@@ -162,15 +162,21 @@ class DecoderMixin:
         return S, B, d
 
     def _egx_greedy(self, start: torch.Tensor, encoded_x: torch.Tensor, n_steps: int, *, embedding: nn.Embedding, pos_embed,
-                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False):
+                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False, schedule=None):
         """Greedy generation (inference only), the loop of predict_ac (HOI/models/multitask/video_model_builder.py:201-220, 263-274) and of
         HOI/models/lta/lta_models_seqdecoder.py:181-201: start (B,) int64 tokens, encoded_x (S, B, d) memory -> tokens (B, n_steps) int64 (the
         n_steps tokens after `start`) and, with return_logits, each step's last-row logits (n_steps, B, |V|). Ties go to the lowest index.
         One egx_decoder_generate call where it serves the configuration (last_decoder_impl() == "generate": K/V cache, argmax on the
-        device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first."""
+        device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first.
+        `schedule` (a functional.TokenSchedule): step t takes its argmax over the words of row t % P, the other logits are -inf
+        (egx_decoder_generate_sched; the prefix loop masks the same way)."""
         self._egx_check_inference("it to greedy_decode", subject="greedy generation is")
-        S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, "greedy generation")
         V = embedding.weight.shape[0]
+        if schedule is not None:
+            F_egx.check_schedule(schedule, V)
+        S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, "greedy generation")
+        if schedule is not None:
+            F_egx.check_schedule(schedule, V, encoded_x.device)
         post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
         if (post_ln and not getattr(self, "egx_composed_decoder", False)
                 and F_egx.decoder_generate_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, S,
@@ -178,7 +184,7 @@ class DecoderMixin:
             meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, 0.0)
             mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
             return F_egx.decoder_generate(meta, start, mem2d, embedding.weight, pos_embed.pe[:n_steps, 0, :], params, fc.weight, fc.bias,
-                                          n_steps, return_logits)
+                                          n_steps, return_logits, schedule)
         # the reference's prefix loop: one decode() per step over the growing prefix
         if n_steps > 8:
             raise ValueError(f"n_steps = {n_steps}: this configuration is outside egx_decoder_generate (compute bf16, vocabulary <= 1024, "
@@ -187,33 +193,70 @@ class DecoderMixin:
             toks = torch.empty((B, n_steps + 1), dtype=torch.int64, device=start.device)
             toks[:, 0] = start
             rows = []
+            banned = None if schedule is None else ~schedule.allowed.to(start.device)
             for t in range(n_steps):
                 last = self._egx_decode(toks[:, :t + 1], encoded_x, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
                                         n_heads=n_heads, p_drop=0.0)[-1]
+                if banned is not None:
+                    last = last.masked_fill(banned[t % schedule.period], float("-inf"))
                 toks[:, t + 1] = _argmax_lowest(last)
                 if return_logits:
                     rows.append(last)
         F_egx._last_dec_impl[0] = "loop"
         return toks[:, 1:].contiguous(), (torch.stack(rows, 0).contiguous() if return_logits else None)
 
-    def greedy_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, return_logits: bool = False):
+    def token_schedule(self, allowed: torch.Tensor) -> "F_egx.TokenSchedule":
+        """A functional.TokenSchedule for greedy_decode / beam_decode on this model's device: `allowed` (P, V) bool, V the vocabulary of
+        `embedding`; step t may emit the words of row t % P. Build it once (host validation, one upload) and reuse it."""
+        V = self.embedding.weight.shape[0]
+        if isinstance(allowed, torch.Tensor) and allowed.dim() == 2 and allowed.shape[1] != V:
+            raise ValueError(f"allowed is over {allowed.shape[1]} words, the model's vocabulary has {V}")
+        return F_egx.TokenSchedule(allowed, self.embedding.weight.device)
+
+    def verb_noun_schedule(self, v_idx, n_idx) -> "F_egx.TokenSchedule":
+        """The two-row schedule of the LTA outputs (HOI/models/lta/lta_models_seqdecoder.py:190-201) from the index arrays of
+        vocab_idx_to_orig() (numpy arrays, lists or tensors; the sets may overlap): row 0, steps 0, 2, ..: the verb words v_idx; row 1,
+        steps 1, 3, ..: the noun words n_idx."""
+        V = self.embedding.weight.shape[0]
+        allowed = torch.zeros((2, V), dtype=torch.bool)
+        for row, (name, idx) in enumerate((("v_idx", v_idx), ("n_idx", n_idx))):
+            idx = torch.as_tensor(idx).detach().to("cpu")
+            if idx.numel() == 0:
+                idx = idx.to(torch.int64).view(-1)                      # (an empty list arrives as float32; the empty row is refused below)
+            if idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool or idx.dim() != 1:
+                raise ValueError(f"{name} must be a 1-D array of integer word indices, got {idx.dtype} of shape {tuple(idx.shape)}")
+            idx = idx.to(torch.int64)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= V):
+                raise ValueError(f"{name} holds an index outside the vocabulary of {V} words: {int(idx.min())} .. {int(idx.max())}")
+            allowed[row, idx] = True
+        return self.token_schedule(allowed)
+
+    def greedy_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, return_logits: bool = False, schedule=None):
         """Greedy generation from the (S, B, d) decoder memory: `start_token` an int or a (B,) int64 tensor; returns tokens (B, n_steps) and,
-        with return_logits, (tokens, logits (n_steps, B, |V|)). The 40-step verb / noun schedule of lta_models_seqdecoder.py:186-201 is two
-        index operations on the result. Eval mode only; see _egx_greedy."""
+        with return_logits, (tokens, logits (n_steps, B, |V|)). `schedule` (token_schedule / verb_noun_schedule): step t's token is the
+        argmax over the words of row t % P and the returned logits are -inf at every other word, so tokens == argmax(logits) still holds;
+        the 40-step verb / noun reading of lta_models_seqdecoder.py:190-201 is verb_noun_schedule(v_idx, n_idx). One deliberate difference:
+        the reference feeds back the full-vocabulary argmax and only reads the subset, a schedule feeds back the subset's argmax (the same
+        word whenever the full argmax lies in the set). Without a schedule nothing changes. Eval mode only; see _egx_greedy."""
         start = _start_tokens(start_token, encoded_x)
         tokens, logits = self._egx_greedy(start, encoded_x, n_steps, embedding=self.embedding, pos_embed=self.pos_embed,
-                                          decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits)
+                                          decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits,
+                                          schedule=schedule)
         return (tokens, logits) if return_logits else tokens
 
     def beam_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, beam_width: int, return_scores: bool = False,
-                    return_trace: bool = False):
+                    return_trace: bool = False, schedule=None):
         """Beam search from the (S, B, d) decoder memory: the `beam_width` best fixed-length continuations of `start_token` (an int or a (B,)
         int64 tensor) per clip, best first: tokens (B, beam_width, n_steps) int64; with return_scores also their scores (B, beam_width), the
         fp32 sums of log_softmax(logits)[token]; with return_trace also a functional.BeamTrace (step_tokens, step_parents, step_scores,
         step_logits). The K = 5 candidates of the LTA evaluation (HOI/tasks/lta/long_term_anticipation.py:233-388) are
         beam_decode(memory, start, 40, 5). One egx_decoder_beam call (last_decoder_impl() == "beam": K/V cache read through an ancestry
         table, ranking on the device, no host synchronisation); outside its limits a ValueError: there is no Python search to fall back on.
-        Eval mode only; validation is host work and runs first."""
+        `schedule` (token_schedule / verb_noun_schedule): at step t only the words of row t % P are candidates, log_softmax normalises
+        over that set (as Categorical(logits=head_x[..., v_idx]) of lta_models_seqdecoder.py:190-216 does) and step_logits is -inf
+        elsewhere; beam_width may not exceed the size of step 0's set. The LTA recipe is beam_decode(memory, start, 40, 5,
+        schedule=model.verb_noun_schedule(v_idx, n_idx)). Unlike the reference, which feeds back the full-vocabulary argmax and only
+        reads the subset, the fed-back words are the subset's. Eval mode only; validation is host work and runs first."""
         self._egx_check_inference("it to beam_decode", subject="beam search is")
         if not isinstance(beam_width, int) or isinstance(beam_width, bool) or not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be an int in 1..8, got {beam_width!r}")
@@ -221,6 +264,8 @@ class DecoderMixin:
         V = embedding.weight.shape[0]
         if beam_width > V:
             raise ValueError(f"beam_width = {beam_width} exceeds the vocabulary of {V} words")
+        if schedule is not None:
+            F_egx.check_schedule(schedule, V, None, beam_width)
         start = _start_tokens(start_token, encoded_x)
         S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, self.pos_embed, "beam search")
         compute, d_ff = getattr(self, "egx_compute", "f32"), decoder.layers[0].linear1.out_features
@@ -230,10 +275,12 @@ class DecoderMixin:
                              f"[256, 1024], head dim 32 or 64, d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= 1024, "
                              f"n_steps <= 64, beam_width <= 8): got compute {compute}, d = {d}, {self.n_heads} heads, d_ff = {d_ff}, S = {S}, "
                              f"{len(decoder.layers)} layers, vocabulary {V}, n_steps = {n_steps}, beam_width = {beam_width}")
+        if schedule is not None:
+            F_egx.check_schedule(schedule, V, encoded_x.device, beam_width)          # (where its words live: the memory is a tensor by now)
         meta, params = self._egx_decoder_args(decoder, self.pos_embed, self.n_heads, 0.0)
         mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
         tokens, scores, trace = F_egx.decoder_beam(meta, start, mem2d, embedding.weight, self.pos_embed.pe[:n_steps, 0, :], params, self.fc.weight,
-                                                   self.fc.bias, n_steps, beam_width, return_trace)
+                                                   self.fc.bias, n_steps, beam_width, return_trace, schedule)
         out = (tokens,) + ((scores,) if return_scores else ()) + ((trace,) if return_trace else ())
         return out if len(out) > 1 else tokens
 

@@ -1633,10 +1633,67 @@ def decoder_generate_supported(compute: str, d: int, n_heads: int, d_ff: int, S:
     return decoder_supported(compute, d, n_heads, d_ff, 1, S, n_layers) and 1 <= n_steps <= 64 and 1 <= vocab <= 1024
 
 
-def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, return_logits: bool = False):
+class TokenSchedule:
+    """Per-step word sets of greedy generation and beam search: `allowed` a (P, V) bool tensor, 1 <= P <= 64, no empty row; step t
+    (0-based) may emit the words of row t % P (P = 2: the verb / noun alternation of HOI/models/lta/lta_models_seqdecoder.py:190-201;
+    P = n_steps: a set per step). Validated on the host HERE (a GPU tensor is copied to the host once); holds .allowed (CPU bool (P, V)),
+    .counts (list of P ints) and .words: the (P, V) int32 table on `device` the library reads, row p's first counts[p] entries the set's
+    indices in ascending order, the rest padded with the last index. Build it once, outside any captured region, and reuse it."""
+    MAX_PERIOD = 64
+
+    def __init__(self, allowed: torch.Tensor, device):
+        if not isinstance(allowed, torch.Tensor) or allowed.dtype != torch.bool:
+            raise ValueError(f"allowed must be a (P, V) bool tensor, got {allowed.dtype if isinstance(allowed, torch.Tensor) else type(allowed).__name__}")
+        if allowed.dim() != 2:
+            raise ValueError(f"allowed must be a (P, V) bool tensor, got shape {tuple(allowed.shape)}")
+        P, V = allowed.shape
+        if not 1 <= P <= self.MAX_PERIOD or V < 1:
+            raise ValueError(f"allowed has {P} rows over {V} words: a schedule has 1..{self.MAX_PERIOD} rows over at least one word")
+        self.allowed = allowed.detach().to("cpu").clone()
+        self.counts = [int(c) for c in self.allowed.sum(dim=1).tolist()]
+        empty = [p for p, c in enumerate(self.counts) if c < 1]
+        if empty:
+            raise ValueError(f"allowed rows {empty} are empty: every step needs at least one word")
+        # a stable descending sort of the 0 / 1 row puts the allowed indices first, ascending; the tail takes the last of them
+        order = torch.sort(self.allowed.to(torch.int8), dim=1, descending=True, stable=True).indices
+        last = order.gather(1, torch.tensor(self.counts)[:, None] - 1)
+        words = torch.where(torch.arange(V)[None, :] < torch.tensor(self.counts)[:, None], order, last)
+        self.words = words.to(torch.int32).contiguous().to(device)
+
+    @property
+    def period(self) -> int:
+        return self.allowed.shape[0]
+
+    @property
+    def vocab(self) -> int:
+        return self.allowed.shape[1]
+
+    def _args(self):
+        """(period, counts as a C int array, words pointer): the three trailing arguments of the _sched entry points."""
+        return self.period, (C.c_int * self.period)(*self.counts), ptr(self.words)
+
+
+def check_schedule(schedule, vocab: int, device=None, beam_width: int = 0) -> None:
+    """The host checks of a schedule against one call (no library call): its V, for beam search step 0's set, and (device given) where its
+    words live."""
+    if not isinstance(schedule, TokenSchedule):
+        raise ValueError(f"schedule must be a functional.TokenSchedule (model.token_schedule / model.verb_noun_schedule), got {type(schedule).__name__}")
+    if schedule.vocab != vocab:
+        raise ValueError(f"the schedule is over {schedule.vocab} words, the model's vocabulary has {vocab}")
+    if beam_width > schedule.counts[0]:
+        raise ValueError(f"beam_width = {beam_width} exceeds the {schedule.counts[0]} words step 0 may emit (at step 0 only one hypothesis is "
+                         f"live: it has only that many continuations)")
+    if device is not None and schedule.words.device != torch.device(device):
+        raise ValueError(f"the schedule's words are on {schedule.words.device}, the memory on {torch.device(device)}: build the schedule on the "
+                         f"memory's device")
+
+
+def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, return_logits: bool = False,
+                     schedule: "TokenSchedule" = None):
     """Greedy generation in ONE asynchronous call (egx_decoder_generate; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory
     rows, pe (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, n_steps) int64 and, with
-    return_logits, logits (n_steps, B, |V|) fp32 (else None). The workspace comes from the caching allocator: the call can be captured."""
+    return_logits, logits (n_steps, B, |V|) fp32 (else None). The workspace comes from the caching allocator: the call can be captured.
+    With a TokenSchedule: egx_decoder_generate_sched, step t's argmax over the words of row t % P, the other logits -inf."""
     lib = _lib.load()
     with torch.no_grad():
         _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
@@ -1654,8 +1711,13 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
         ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=mem2d.device)
         tokens = torch.empty((B, n_steps), dtype=torch.int64, device=mem2d.device)
         logits = torch.empty((n_steps, B, V), dtype=torch.float32, device=mem2d.device) if return_logits else None
-        check(lib.egx_decoder_generate(C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
-                                       n_steps, ptr(tokens), ptr(logits), ptr(ws), _stream()))
+        args = (C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, n_steps, ptr(tokens),
+                ptr(logits), ptr(ws), _stream())
+        if schedule is None:
+            check(lib.egx_decoder_generate(*args))
+        else:
+            check_schedule(schedule, V, mem2d.device)
+            check(lib.egx_decoder_generate_sched(*args, *schedule._args()))
     _last_dec_impl[0] = "generate"
     return tokens, logits
 
@@ -1675,11 +1737,12 @@ class BeamTrace:
 
 
 def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, beam_width: int,
-                 return_trace: bool = False):
+                 return_trace: bool = False, schedule: "TokenSchedule" = None):
     """Beam search in ONE asynchronous call (egx_decoder_beam; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory rows, pe
     (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, W, n_steps) int64 (best first),
     scores (B, W) fp32 and, with return_trace, a BeamTrace (else None). The workspace comes from the caching allocator: the call can be
-    captured."""
+    captured. With a TokenSchedule: egx_decoder_beam_sched, step t's log_softmax and ranking over the words of row t % P, the other logits
+    -inf."""
     lib = _lib.load()
     with torch.no_grad():
         _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
@@ -1704,8 +1767,13 @@ def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tenso
                               torch.empty((n_steps, B, W), dtype=torch.float32, device=dev),
                               torch.empty((n_steps, B, W, V), dtype=torch.float32, device=dev))
         tr = [ptr(getattr(trace, k)) if trace is not None else None for k in BeamTrace.__slots__]
-        check(lib.egx_decoder_beam(C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
-                                   n_steps, W, ptr(tokens), ptr(scores), *tr, ptr(ws), _stream()))
+        args = (C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, n_steps, W, ptr(tokens),
+                ptr(scores), *tr, ptr(ws), _stream())
+        if schedule is None:
+            check(lib.egx_decoder_beam(*args))
+        else:
+            check_schedule(schedule, V, dev, W)
+            check(lib.egx_decoder_beam_sched(*args, *schedule._args()))
     _last_dec_impl[0] = "beam"
     return tokens, scores, trace
 

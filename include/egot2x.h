@@ -635,6 +635,34 @@ int egx_decoder_beam(const egx_dec_config* cfg, const int64_t* start, const floa
                      int64_t* step_tokens /* (n_steps, B, W) or NULL */, int32_t* step_parents /* (n_steps, B, W) or NULL */,
                      float* step_scores /* (n_steps, B, W) or NULL */, float* step_logits /* (n_steps, B, W, vocab) or NULL */,
                      void* workspace, void* stream);
+/* ---- ABI v18 (additions): per-step token schedules for greedy generation and beam search ----
+ * The reference reads the LTA outputs through word subsets: HOI/models/lta/lta_models_seqdecoder.py:190-201 keeps output_prob[-1, :, self.v_idx]
+ * at odd steps and [..., self.n_idx] at even steps, generate() takes the argmax (or a Categorical) over that subset, and vocab_idx_to_orig()
+ * supplies the two index arrays. A token schedule gives every step the set of words it may emit, enforced in the head of the step on the
+ * device. `period` rows P (0 <= P <= 64; 0: no schedule, the unscheduled call); step t (0-based) uses row t % P. counts: HOST int[P], the
+ * size of each row's set, 1 .. vocab. words: DEVICE int32[P][vocab], row p's first counts[p] entries the set's word indices in ascending
+ * order, the rest padded with the last index. At a scheduled step the head computes the listed vocabulary rows ONLY; every other word has
+ * logit -inf (so in logits_out / step_logits). A listed word's logit has the bits the unscheduled call gives for the same input row. Greedy
+ * takes the argmax over the set (lowest index on ties); beam takes log_softmax over the set (the normaliser sums the set's words only, as
+ * Categorical(logits=head_x[..., v_idx]) does) and ranks the W * counts finite candidates by the unscheduled tie rule. Deliberately unlike
+ * the reference, which feeds back the full-vocabulary argmax and only READS the subset, the fed-back word is the subset's argmax; the two
+ * agree whenever the full argmax lies in the set. Indices read from `words` are clamped to 0 .. vocab - 1 and counts to vocab on the
+ * device: a corrupt list gives wrong tokens, never a read outside fc_w / fc_b / emb. Every other argument, limit and the workspace
+ * (egx_decoder_generate_workspace / egx_decoder_beam_workspace) as the unscheduled calls; nothing is copied from the host per step, so the
+ * calls can be captured as those can. Refused before any device work: period < 0 or > 64; period > 0 with counts or words null; a count
+ * outside 1 .. vocab; for beam counts[0] < W (at step 0 only slot 0 is live: the step has only counts[0] continuations). */
+int egx_decoder_generate_sched(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe,
+                               int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps,
+                               int64_t* tokens_out, float* logits_out /* may be NULL */, void* workspace, void* stream, int period,
+                               const int* counts /* HOST int[period] */, const int32_t* words /* DEVICE int32[period][vocab] */);
+/* egx_decoder_beam with a token schedule (lta_models_seqdecoder.py:190-201; see egx_decoder_generate_sched). */
+int egx_decoder_beam_sched(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                           const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W,
+                           int64_t* tokens_out /* (B, W, n_steps) */, float* scores_out /* (B, W) */,
+                           int64_t* step_tokens /* (n_steps, B, W) or NULL */, int32_t* step_parents /* (n_steps, B, W) or NULL */,
+                           float* step_scores /* (n_steps, B, W) or NULL */, float* step_logits /* (n_steps, B, W, vocab) or NULL */,
+                           void* workspace, void* stream, int period, const int* counts /* HOST int[period] */,
+                           const int32_t* words /* DEVICE int32[period][vocab] */);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
