@@ -703,6 +703,119 @@ int dec_attn_ragged_train(DecAttnParams p, int dh, bool long_class, hipStream_t 
     return 0;
 }
 
+// ---- the cross-attention weights as an output (egx_cross_attention_weights, egx_decoder_cross_weights, egx_decoder_generate_attn) ----
+// What CustomDecoderLayer._mha_block asks nn.MultiheadAttention for with need_weights=True (HHI/models/multitask/task_prompt_model.py:163-172,
+// HOI/models/multitask/video_model_builder.py:20-30, HOI/models/lta/lta_models_seqdecoder.py:30-39): the head-averaged probabilities
+//   w[b, i, j] = (1 / H) sum_h softmax_j(q[b, i, h, :] . k[b, j, h, :] / sqrt(DH)).
+// One 256-thread workgroup per (clip, query row), a loop over the heads in order 0 .. H - 1. Thread t owns keys t, t + 256, t + 512, t + 768
+// (Sk <= 1024: four accumulators); it reads its key's head slice with 16-byte loads and the query slice from LDS as broadcast reads. Per head
+// a block maximum and a block sum: the wave's xor tree, then the four wave partials in wave order. Scores, max, exp, sum and the
+// normalisation are fp32; the head sum runs in head order and is multiplied by 1 / H once. No atomics: a clip's rows have the same bits
+// wherever the clip sits in the batch. Ragged (mtab): clip b's S_b = clamp(mtab[2b + 1], 0, Sk) keys are rows [mtab[2b], + S_b) of k;
+// entries j >= S_b of the Sk written ones are exact zeros.
+struct CrossWParams {
+    const void* q; const void* k; int ldq, ldk;     // rows b * Sq + i / b * Sk + j (or the table's); head h at columns h * DH
+    const int* mtab;                                // DEVICE int[B][2] or null
+    float* out; int ldo;                            // row b * Sq + i, Sk entries written
+    int B, H, Sq, Sk;
+    float scale, inv_h;
+};
+constexpr int CW_MAXK = 1024, CW_THREADS = 256, CW_KEYS = CW_MAXK / CW_THREADS;
+
+template <int DH, bool F32>
+__global__ __launch_bounds__(CW_THREADS) void dec_cross_weights_kernel(CrossWParams p) {
+    __shared__ __align__(16) float sQ[DH];      // (read as float4)
+    __shared__ float sMax[4], sSum[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.x / p.Sq, i = blockIdx.x - b * p.Sq;
+    int Sb = p.Sk;
+    size_t m0 = (size_t)b * p.Sk;
+    if (p.mtab) {
+        const int first = p.mtab[2 * b], rows = p.mtab[2 * b + 1];
+        Sb = rows < 0 ? 0 : (rows > p.Sk ? p.Sk : rows);
+        m0 = (size_t)(first < 0 ? 0 : first);
+    }
+    const size_t qrow = ((size_t)b * p.Sq + i) * p.ldq;
+    float acc[CW_KEYS];
+#pragma unroll
+    for (int c = 0; c < CW_KEYS; ++c) acc[c] = 0.f;
+    for (int h = 0; h < p.H; ++h) {             // (uniform trip count: every barrier below is reached by all 256 threads)
+        if (t < DH) sQ[t] = load1<F32>(p.q, qrow + h * DH + t);
+        __syncthreads();
+        float s[CW_KEYS];
+        float m = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < CW_KEYS; ++c) {
+            const int j = t + c * CW_THREADS;
+            s[c] = -INFINITY;
+            if (j < Sb) {
+                const size_t krow = (m0 + j) * p.ldk + h * DH;
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+                for (int e = 0; e < DH; e += 8) {
+                    float k8[8];
+                    load8<F32>(p.k, krow + e, k8);
+                    const float4 q0 = *reinterpret_cast<const float4*>(&sQ[e]);
+                    const float4 q1 = *reinterpret_cast<const float4*>(&sQ[e + 4]);
+                    a0 += q0.x * k8[0] + q1.x * k8[4]; a1 += q0.y * k8[1] + q1.y * k8[5];
+                    a2 += q0.z * k8[2] + q1.z * k8[6]; a3 += q0.w * k8[3] + q1.w * k8[7];
+                }
+                s[c] = ((a0 + a1) + (a2 + a3)) * p.scale;
+            }
+            m = fmaxf(m, s[c]);
+        }
+        m = wmax64(m);
+        if (lane == 0) sMax[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
+        float e[CW_KEYS];
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < CW_KEYS; ++c) {
+            e[c] = t + c * CW_THREADS < Sb ? __expf(s[c] - m) : 0.f;
+            sum += e[c];
+        }
+        sum = wsum64d(sum);
+        if (lane == 0) sSum[wave] = sum;
+        __syncthreads();
+        sum = ((sSum[0] + sSum[1]) + sSum[2]) + sSum[3];     // wave order
+#pragma unroll
+        for (int c = 0; c < CW_KEYS; ++c) acc[c] += e[c] / sum;     // (Sb = 0: 0 / 0 is never stored)
+    }
+    float* orow = p.out + ((size_t)b * p.Sq + i) * p.ldo;
+#pragma unroll
+    for (int c = 0; c < CW_KEYS; ++c) {
+        const int j = t + c * CW_THREADS;
+        if (j < p.Sk) orow[j] = j < Sb ? acc[c] * p.inv_h : 0.f;
+    }
+}
+
+// host checks first (no device work on a refusal), then one launch
+int cross_weights(CrossWParams p, int dh, bool f32, hipStream_t st) {
+    EGX_CHECK(p.q && p.k && p.out, "egx_cross_attention_weights: null pointer argument");
+    EGX_CHECK(dh == 16 || dh == 32 || dh == 64 || dh == 128, "egx_cross_attention_weights: head dim %d (16, 32, 64 or 128)", dh);
+    EGX_CHECK(p.Sk >= 1 && p.Sk <= CW_MAXK, "egx_cross_attention_weights: Sk = %d (1..%d)", p.Sk, CW_MAXK);
+    EGX_CHECK(p.Sq >= 1 && p.H >= 1 && p.B >= 0, "egx_cross_attention_weights: B = %d, H = %d, Sq = %d", p.B, p.H, p.Sq);
+    EGX_CHECK(p.ldo >= p.Sk, "egx_cross_attention_weights: ldo = %d < Sk = %d", p.ldo, p.Sk);
+    EGX_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldq >= p.H * dh && p.ldk >= p.H * dh,
+              "egx_cross_attention_weights: ldq = %d, ldk = %d (multiples of 8 elements, at least H * dh = %d)", p.ldq, p.ldk, p.H * dh);
+    EGX_CHECK(((uintptr_t)p.q | (uintptr_t)p.k) % 16 == 0, "egx_cross_attention_weights: q and k must be 16-byte aligned");
+    EGX_CHECK((long long)p.B * p.Sq <= 0x7fffffffLL, "egx_cross_attention_weights: B * Sq = %lld workgroups", (long long)p.B * p.Sq);
+    if (p.B == 0) return 0;
+    p.scale = 1.f / sqrtf((float)dh); p.inv_h = 1.f / (float)p.H;
+    const dim3 grid((unsigned)(p.B * p.Sq)), block(CW_THREADS);
+#define EGX_CW_LAUNCH(DH_) \
+    do { if (f32) hipLaunchKernelGGL((dec_cross_weights_kernel<DH_, true>), grid, block, 0, st, p); \
+         else hipLaunchKernelGGL((dec_cross_weights_kernel<DH_, false>), grid, block, 0, st, p); } while (0)
+    if (dh == 16) EGX_CW_LAUNCH(16);
+    else if (dh == 32) EGX_CW_LAUNCH(32);
+    else if (dh == 64) EGX_CW_LAUNCH(64);
+    else EGX_CW_LAUNCH(128);
+#undef EGX_CW_LAUNCH
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
 // x32 / x16 [row] = dropout(emb[tok[row]] * scale + pe[row % sy])
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restrict__ tok, const float* __restrict__ emb, const float* __restrict__ pe,
                                                         int pe_stride, float scale, float* __restrict__ x32, bf16_t* __restrict__ x16, int rows,
@@ -1192,6 +1305,40 @@ int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, con
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
     const DecRagged rg = dec_ragged_view(dtab, B, n, smax);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, workspace, 0, 0, st, &rg);
+}
+
+int egx_cross_attention_weights(const void* q, int ldq, const void* k, int ldk, int operands_bf16, const int* mtab, int B, int H, int dh, int Sq,
+                                int Sk, float* out, int ldo, void* stream) {
+    CrossWParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.k = k; p.ldq = ldq; p.ldk = ldk; p.mtab = mtab; p.out = out; p.ldo = ldo; p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk;
+    return cross_weights(p, dh, !operands_bf16, (hipStream_t)stream);
+}
+
+int egx_decoder_cross_weights(const egx_dec_config* cfg, int B, const int* mem_lengths, const void* saved, float* attn_out, void* stream) {
+    EGX_CHECK(cfg, "egx_decoder_cross_weights: null decoder config");
+    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f, "egx_decoder_cross_weights: inference only: p_drop and p_pos must be 0 (got %g, %g)",
+              cfg->p_drop, cfg->p_pos);
+    DPlan pl;
+    size_t off_tab = 0;
+    int S = cfg->S;
+    if (mem_lengths) {      // the plan of egx_decoder_ragged_fwd: the table that call uploaded sits behind the plan's saved region
+        std::vector<int> tab;
+        int n[2], smax[2];
+        size_t nb = 0;
+        if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb)) return 1;
+        S = smax[0] > smax[1] ? smax[0] : smax[1];
+    } else if (make_dplan(cfg, B, pl)) return 1;
+    EGX_CHECK(saved && attn_out, "egx_decoder_cross_weights: null pointer argument");
+    const int* mtab = mem_lengths ? cat<int>(saved, off_tab) : nullptr;
+    for (int l = 0; l < pl.L; ++l) {
+        CrossWParams p;
+        memset(&p, 0, sizeof(p));
+        p.q = cat<bf16_t>(saved, pl.layer[l].q); p.ldq = pl.d; p.k = cat<bf16_t>(saved, pl.layer[l].kv); p.ldk = 2 * pl.d; p.mtab = mtab;
+        p.out = attn_out + (size_t)l * B * pl.sy * S; p.ldo = S; p.B = B; p.H = pl.H; p.Sq = pl.sy; p.Sk = S;
+        if (cross_weights(p, pl.d / pl.H, false, (hipStream_t)stream)) return 1;
+    }
+    return 0;
 }
 
 }  // extern "C"
@@ -1763,10 +1910,12 @@ int make_gplan(const egx_dec_config* c, int B, int n_steps, GPlan& pl) {
     return 0;
 }
 
-// The one body of egx_decoder_generate (period = 0) and egx_decoder_generate_sched: step t's head takes row t % period of the schedule.
+// The one body of egx_decoder_generate (period = 0), egx_decoder_generate_sched and egx_decoder_generate_attn: step t's head takes row
+// t % period of the schedule; with attn_out (L, n_steps, B, S) every layer's cross-attention of a step is followed by one
+// dec_cross_weights_kernel launch on the same q and k (attn_out null: the launches of the calls without it, nothing else).
 int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
                  const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
-                 float* logits_out, void* workspace, void* stream, int period, const int* counts, const int32_t* words) {
+                 float* logits_out, void* workspace, void* stream, int period, const int* counts, const int32_t* words, float* attn_out) {
     GPlan pl;
     if (make_gplan(cfg, B, n_steps, pl)) return 1;
     if (check_sched("egx_decoder_generate_sched", period, counts, words, pl.V, 0)) return 1;
@@ -1858,6 +2007,13 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
                 a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
                 a.B = B; a.H = pl.H; a.Sq = 1; a.Sk = pl.S; a.causal = 0;
                 if (dec_attn<false>(a, dh, false, st)) return 1;
+                if (attn_out) {     // (egx_decoder_generate_attn) this step's head-averaged weights of the layer: attn_out[l][t] (B, S)
+                    CrossWParams cw;
+                    memset(&cw, 0, sizeof(cw));
+                    cw.q = a.q; cw.ldq = d; cw.k = kv; cw.ldk = 2 * d; cw.out = attn_out + ((size_t)l * n_steps + t) * B * pl.S; cw.ldo = pl.S;
+                    cw.B = B; cw.H = pl.H; cw.Sq = 1; cw.Sk = pl.S;
+                    if (cross_weights(cw, dh, false, st)) return 1;
+                }
             }
             if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
             if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
@@ -1895,7 +2051,7 @@ int egx_decoder_generate(const egx_dec_config* cfg, const int64_t* start, const 
                          const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
                          float* logits_out, void* workspace, void* stream) {
     return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream, 0,
-                        nullptr, nullptr);
+                        nullptr, nullptr, nullptr);
 }
 
 int egx_decoder_generate_sched(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe,
@@ -1903,7 +2059,16 @@ int egx_decoder_generate_sched(const egx_dec_config* cfg, const int64_t* start, 
                                int64_t* tokens_out, float* logits_out, void* workspace, void* stream, int period, const int* counts,
                                const int32_t* words) {
     return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream,
-                        period, counts, words);
+                        period, counts, words, nullptr);
+}
+
+int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe,
+                              int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps,
+                              int64_t* tokens_out, float* logits_out, void* workspace, void* stream, int period, const int* counts,
+                              const int32_t* words, float* attn_out) {
+    EGX_CHECK(attn_out, "egx_decoder_generate_attn: null attn_out (egx_decoder_generate / egx_decoder_generate_sched are the calls without it)");
+    return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream,
+                        period, counts, words, attn_out);
 }
 
 }  // extern "C"

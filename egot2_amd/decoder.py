@@ -40,17 +40,36 @@ class DecoderMixin:
                 and not getattr(self, "egx_composed_decoder", False))
 
     def _egx_decode(self, y: torch.Tensor, encoded_x: torch.Tensor, *, embedding: nn.Embedding, pos_embed, decoder: nn.TransformerDecoder,
-                    fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
-        """y (B, sy) int64, encoded_x (S, B, d) decoder memory -> (sy, B, |V|) logits, as the reference's decode()."""
+                    fc: nn.Linear, n_heads: int, p_drop: float, return_attention: bool = False):
+        """y (B, sy) int64, encoded_x (S, B, d) decoder memory -> (sy, B, |V|) logits, as the reference's decode().
+        return_attention (eval mode, no autograd): (logits, attn), attn (L, B, sy, S) fp32 the head-averaged cross-attention weights of
+        every layer, what a forward hook on the reference's CustomDecoderLayer.multihead_attn sees (task_prompt_model.py:163-172). Fused
+        path: egx_decoder_cross_weights on the forward's `saved`; composed path: egx_cross_attention_weights on the q / kv tensors of the
+        loop. The logits are the bits of the call without the flag; last_decoder_impl() reads as without it."""
         S, B, d = encoded_x.shape
         sy = y.shape[1]
         if y.shape[0] != B:
             raise ValueError(f"target batch {y.shape[0]} != memory batch {B}")
+        if return_attention:
+            self._egx_check_inference("return_attention=True", subject="attention weights are")
+            if n_heads < 1 or d % n_heads:
+                raise ValueError(f"d_model {d} is not a multiple of {n_heads} heads")
+            F_egx.check_cross_weights(d // n_heads, S)
+            with torch.no_grad():
+                return self._egx_decode_impl(y, encoded_x, embedding, pos_embed, decoder, fc, n_heads, p_drop, True)
+        return self._egx_decode_impl(y, encoded_x, embedding, pos_embed, decoder, fc, n_heads, p_drop, False)
+
+    def _egx_decode_impl(self, y, encoded_x, embedding, pos_embed, decoder, fc, n_heads, p_drop, want_attn: bool):
+        S, B, d = encoded_x.shape
+        sy = y.shape[1]
         if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, S):
             # ONE library call per direction (egx_decoder_fwd / egx_decoder_bwd): bf16 MFMA GEMMs over all B * sy target rows
             meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, p_drop)
             mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
             F_egx._last_dec_impl[0] = "fused"
+            if want_attn:
+                out, attn = F_egx.decoder_attention(meta, y, mem2d, embedding.weight, pos_embed.pe[:sy, 0, :], params, fc.weight, fc.bias)
+                return out.view(B, sy, -1).permute(1, 0, 2), attn
             out = F_egx.DecoderFn.apply(meta, y, mem2d, embedding.weight, pos_embed.pe[:sy, 0, :], *params, fc.weight, fc.bias)
             return out.view(B, sy, -1).permute(1, 0, 2)
         comp = "f32"        # (B * sy)-row GEMMs: negligible work, they always run the exact fp32 MFMA path
@@ -60,6 +79,7 @@ class DecoderMixin:
         mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)          # batch-first rows b * S + s
         x = F_egx.EmbedPosFn.apply(y, embedding.weight, pos_embed.pe[:, 0, :], math.sqrt(d),
                                    pos_embed.dropout.p if train else 0.0, seed)
+        attn = []
         for li, layer in enumerate(decoder.layers):
             if getattr(layer, "norm_first", False):
                 raise ValueError("libegot2x implements the post-LN decoder layer only (norm_first=False)")
@@ -73,6 +93,8 @@ class DecoderMixin:
             q = F_egx.linear(x, ca.in_proj_weight[:d], ca.in_proj_bias[:d], comp)
             kv = F_egx.linear(mem2d, ca.in_proj_weight[d:], ca.in_proj_bias[d:], comp_mem)
             c = F_egx.CrossAttnSmallFn.apply(q, kv, B, sy, S, n_heads, p, seed, site(3))
+            if want_attn:
+                attn.append(F_egx.cross_attention_weights(q, kv[:, :d], n_heads, sy, S))
             c = F_egx.dropout(F_egx.linear(c, ca.out_proj.weight, ca.out_proj.bias, comp), p_drop, train, seed, site(4))
             x = F_egx.layer_norm_residual(x, c, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
             h = F_egx.dropout(F_egx.linear(x, layer.linear1.weight, layer.linear1.bias, comp, relu=True), p_drop, train, seed, site(5))
@@ -80,16 +102,20 @@ class DecoderMixin:
             x = F_egx.layer_norm_residual(x, f, layer.norm3.weight, layer.norm3.bias, layer.norm3.eps)
         out = F_egx.linear(x, fc.weight, fc.bias, comp)                         # (B * sy, |V|)
         F_egx._last_dec_impl[0] = "composed"
+        if want_attn:
+            return out.view(B, sy, -1).permute(1, 0, 2), torch.stack(attn, 0)
         return out.view(B, sy, -1).permute(1, 0, 2)
 
     def _egx_decode_ragged(self, y: torch.Tensor, memory: torch.Tensor, memory_lengths, *, embedding: nn.Embedding, pos_embed,
-                           decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
+                           decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, p_drop: float, return_attention: bool = False):
         """Inference decode over a packed ragged memory: y (B, sy) int64, memory (sum_b S_b, d), memory_lengths (B,) with S_b rows for
         clip b -> (sy, B, |V|), each clip's logits as decode() gives them on its own (S_b, 1, d) memory. One egx_decoder_ragged_fwd call
-        where the fused decoder serves the shapes (last_decoder_impl() == "ragged"); elsewhere one _egx_decode per memory length ("grouped")."""
+        where the fused decoder serves the shapes (last_decoder_impl() == "ragged"); elsewhere one _egx_decode per memory length ("grouped").
+        return_attention: (logits, attn (L, B, sy, max_b S_b) fp32), zeros beyond S_b: one egx_decoder_cross_weights call on the ragged
+        workspace; grouped: each length group's weights scattered into place."""
         self._egx_check_inference("memory_lengths=")
         return self._egx_decode_packed(y, memory, memory_lengths, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
-                                       n_heads=n_heads, p_drop=p_drop, inference=True)
+                                       n_heads=n_heads, p_drop=p_drop, inference=True, want_attn=bool(return_attention))
 
     def _egx_decode_ragged_train(self, y: torch.Tensor, memory: torch.Tensor, memory_lengths, *, embedding: nn.Embedding, pos_embed,
                                  decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, p_drop: float) -> torch.Tensor:
@@ -100,7 +126,8 @@ class DecoderMixin:
         return self._egx_decode_packed(y, memory, memory_lengths, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
                                        n_heads=n_heads, p_drop=p_drop, inference=False)
 
-    def _egx_decode_packed(self, y, memory, memory_lengths, *, embedding, pos_embed, decoder, fc, n_heads, p_drop, inference: bool):
+    def _egx_decode_packed(self, y, memory, memory_lengths, *, embedding, pos_embed, decoder, fc, n_heads, p_drop, inference: bool,
+                           want_attn: bool = False):
         """_egx_decode_ragged (inference: functional.decoder_ragged, no autograd) and _egx_decode_ragged_train (RaggedDecoderFn)."""
         B, sy = y.shape
         d = memory.shape[-1]
@@ -113,9 +140,17 @@ class DecoderMixin:
         if memory.dim() != 2 or (B and (int(ml.min()) < 1 or int(ml.sum()) != memory.shape[0])):
             raise ValueError(f"memory must be the packed (sum_b S_b, d) rows of the clips: {tuple(memory.shape)} rows, lengths sum to "
                              f"{int(ml.sum())} (each >= 1)")
-        if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, int(ml.max()) if B else 1):
+        S_max = int(ml.max()) if B else 1
+        if want_attn:
+            if n_heads < 1 or d % n_heads:
+                raise ValueError(f"d_model {d} is not a multiple of {n_heads} heads")
+            F_egx.check_cross_weights(d // n_heads, S_max)
+        if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, S_max):
             meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, p_drop)
             args = (meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :])
+            if want_attn:
+                out, attn = F_egx.decoder_ragged(*args, params, fc.weight, fc.bias, return_attention=True)
+                return out.view(B, sy, -1).permute(1, 0, 2), attn
             if inference:
                 out = F_egx.decoder_ragged(*args, params, fc.weight, fc.bias)
             else:
@@ -127,18 +162,23 @@ class DecoderMixin:
         for b, S in enumerate(ml.tolist()):
             groups.setdefault(S, []).append(b)
         parts, order = [], []
+        attn = torch.zeros((len(decoder.layers), B, sy, S_max), dtype=torch.float32, device=memory.device) if want_attn else None
         for S, idx in groups.items():
             rows = (row0[idx][:, None] + torch.arange(S)[None, :]).reshape(-1).to(memory.device)
             mem = memory.index_select(0, rows).view(len(idx), S, d).permute(1, 0, 2)
             it = torch.tensor(idx, dtype=torch.int64, device=y.device)
-            parts.append(self._egx_decode(y.index_select(0, it), mem, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
-                                          n_heads=n_heads, p_drop=p_drop))
+            part = self._egx_decode(y.index_select(0, it), mem, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
+                                    n_heads=n_heads, p_drop=p_drop, return_attention=want_attn)
+            if want_attn:
+                part, w = part
+                attn[:, it.to(attn.device), :, :S] = w
+            parts.append(part)
             order += idx
         inv = torch.empty(B, dtype=torch.int64)
         inv[torch.tensor(order, dtype=torch.int64)] = torch.arange(B)
         out = torch.cat(parts, 1).index_select(1, inv.to(parts[0].device))
         F_egx._last_dec_impl[0] = "grouped"
-        return out
+        return (out, attn) if want_attn else out
 
     @staticmethod
     def _egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, what: str):
@@ -162,14 +202,17 @@ class DecoderMixin:
         return S, B, d
 
     def _egx_greedy(self, start: torch.Tensor, encoded_x: torch.Tensor, n_steps: int, *, embedding: nn.Embedding, pos_embed,
-                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False, schedule=None):
+                    decoder: nn.TransformerDecoder, fc: nn.Linear, n_heads: int, return_logits: bool = False, schedule=None,
+                    return_attention: bool = False):
         """Greedy generation (inference only), the loop of predict_ac (HOI/models/multitask/video_model_builder.py:201-220, 263-274) and of
         HOI/models/lta/lta_models_seqdecoder.py:181-201: start (B,) int64 tokens, encoded_x (S, B, d) memory -> tokens (B, n_steps) int64 (the
         n_steps tokens after `start`) and, with return_logits, each step's last-row logits (n_steps, B, |V|). Ties go to the lowest index.
         One egx_decoder_generate call where it serves the configuration (last_decoder_impl() == "generate": K/V cache, argmax on the
         device, no host synchronisation); elsewhere the prefix loop over _egx_decode ("loop"). Validation is host work and runs first.
         `schedule` (a functional.TokenSchedule): step t takes its argmax over the words of row t % P, the other logits are -inf
-        (egx_decoder_generate_sched; the prefix loop masks the same way)."""
+        (egx_decoder_generate_sched; the prefix loop masks the same way).
+        return_attention: a third result, attn (L, n_steps, B, S) fp32, step t's head-averaged cross-attention weights of every layer
+        (egx_decoder_generate_attn; the prefix loop takes the last row of each step's decode weights)."""
         self._egx_check_inference("it to greedy_decode", subject="greedy generation is")
         V = embedding.weight.shape[0]
         if schedule is not None:
@@ -177,6 +220,10 @@ class DecoderMixin:
         S, B, d = self._egx_check_generation(start, encoded_x, n_steps, embedding, pos_embed, "greedy generation")
         if schedule is not None:
             F_egx.check_schedule(schedule, V, encoded_x.device)
+        if return_attention:
+            if n_heads < 1 or d % n_heads:
+                raise ValueError(f"d_model {d} is not a multiple of {n_heads} heads")
+            F_egx.check_cross_weights(d // n_heads, S)
         post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
         if (post_ln and not getattr(self, "egx_composed_decoder", False)
                 and F_egx.decoder_generate_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, S,
@@ -184,7 +231,7 @@ class DecoderMixin:
             meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, 0.0)
             mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
             return F_egx.decoder_generate(meta, start, mem2d, embedding.weight, pos_embed.pe[:n_steps, 0, :], params, fc.weight, fc.bias,
-                                          n_steps, return_logits, schedule)
+                                          n_steps, return_logits, schedule, return_attention)
         # the reference's prefix loop: one decode() per step over the growing prefix
         if n_steps > 8:
             raise ValueError(f"n_steps = {n_steps}: this configuration is outside egx_decoder_generate (compute bf16, vocabulary <= 1024, "
@@ -192,18 +239,23 @@ class DecoderMixin:
         with torch.no_grad():
             toks = torch.empty((B, n_steps + 1), dtype=torch.int64, device=start.device)
             toks[:, 0] = start
-            rows = []
+            rows, attn = [], []
             banned = None if schedule is None else ~schedule.allowed.to(start.device)
             for t in range(n_steps):
                 last = self._egx_decode(toks[:, :t + 1], encoded_x, embedding=embedding, pos_embed=pos_embed, decoder=decoder, fc=fc,
-                                        n_heads=n_heads, p_drop=0.0)[-1]
+                                        n_heads=n_heads, p_drop=0.0, return_attention=return_attention)
+                if return_attention:
+                    attn.append(last[1][:, :, t, :])                    # (L, B, S): the new row's weights
+                    last = last[0]
+                last = last[-1]
                 if banned is not None:
                     last = last.masked_fill(banned[t % schedule.period], float("-inf"))
                 toks[:, t + 1] = _argmax_lowest(last)
                 if return_logits:
                     rows.append(last)
         F_egx._last_dec_impl[0] = "loop"
-        return toks[:, 1:].contiguous(), (torch.stack(rows, 0).contiguous() if return_logits else None)
+        out = (toks[:, 1:].contiguous(), (torch.stack(rows, 0).contiguous() if return_logits else None))
+        return out + (torch.stack(attn, 1).contiguous(),) if return_attention else out
 
     def token_schedule(self, allowed: torch.Tensor) -> "F_egx.TokenSchedule":
         """A functional.TokenSchedule for greedy_decode / beam_decode on this model's device: `allowed` (P, V) bool, V the vocabulary of
@@ -231,18 +283,49 @@ class DecoderMixin:
             allowed[row, idx] = True
         return self.token_schedule(allowed)
 
-    def greedy_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, return_logits: bool = False, schedule=None):
+    def greedy_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, return_logits: bool = False, schedule=None, *,
+                      return_attention: bool = False):
         """Greedy generation from the (S, B, d) decoder memory: `start_token` an int or a (B,) int64 tensor; returns tokens (B, n_steps) and,
         with return_logits, (tokens, logits (n_steps, B, |V|)). `schedule` (token_schedule / verb_noun_schedule): step t's token is the
         argmax over the words of row t % P and the returned logits are -inf at every other word, so tokens == argmax(logits) still holds;
         the 40-step verb / noun reading of lta_models_seqdecoder.py:190-201 is verb_noun_schedule(v_idx, n_idx). One deliberate difference:
         the reference feeds back the full-vocabulary argmax and only reads the subset, a schedule feeds back the subset's argmax (the same
-        word whenever the full argmax lies in the set). Without a schedule nothing changes. Eval mode only; see _egx_greedy."""
+        word whenever the full argmax lies in the set). Without a schedule nothing changes. Eval mode only; see _egx_greedy.
+        return_attention appends attn (L, n_steps, B, S) fp32 to the return value: per decoder layer and step the head-averaged
+        cross-attention weights of the step's new row, what a hook on the reference's CustomDecoderLayer.multihead_attn
+        (lta_models_seqdecoder.py:30-39) sees in the last row of step t; tokens and logits keep their bits. beam_decode has no such output
+        (a hypothesis changes slots every step: return_trace is the tool there)."""
         start = _start_tokens(start_token, encoded_x)
-        tokens, logits = self._egx_greedy(start, encoded_x, n_steps, embedding=self.embedding, pos_embed=self.pos_embed,
-                                          decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits,
-                                          schedule=schedule)
-        return (tokens, logits) if return_logits else tokens
+        res = self._egx_greedy(start, encoded_x, n_steps, embedding=self.embedding, pos_embed=self.pos_embed,
+                               decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, return_logits=return_logits,
+                               schedule=schedule, return_attention=bool(return_attention))
+        out = (res[0],) + ((res[1],) if return_logits else ()) + ((res[2],) if return_attention else ())
+        return out if len(out) > 1 else res[0]
+
+    @staticmethod
+    def attention_by_segment(attn: torch.Tensor, segment_lengths) -> torch.Tensor:
+        """Sums the last axis of attention weights over consecutive memory segments: attn (..., S) -> (..., K). segment_lengths (K,) ints:
+        the same split for every clip (the three T-token task blocks of the HHI 'ttm' memory: (T, T, T)); (B, K) ints: a split per clip
+        for ragged memories, attn then (..., B, sy, S) as decode(..., memory_lengths=, return_attention=True) returns it. Segments start
+        at key 0 and may stop short of S (the zero tail of a ragged clip). Pure torch."""
+        if not isinstance(attn, torch.Tensor) or attn.dim() < 1 or not attn.dtype.is_floating_point:
+            raise ValueError("attn must be a floating-point tensor whose last axis runs over the memory tokens")
+        seg = segment_lengths.detach() if isinstance(segment_lengths, torch.Tensor) else torch.as_tensor(segment_lengths)
+        if seg.dtype.is_floating_point or seg.dtype.is_complex or seg.dtype == torch.bool or seg.dim() not in (1, 2) or seg.shape[-1] < 1:
+            raise ValueError(f"segment_lengths must be (K,) or (B, K) integers, got {seg.dtype} of shape {tuple(seg.shape)}")
+        seg = seg.to("cpu", torch.int64)
+        S = attn.shape[-1]
+        if int(seg.min()) < 0 or int(seg.sum(dim=-1).max()) > S:
+            raise ValueError(f"segment_lengths must be non-negative and sum to at most the {S} memory tokens of attn")
+        if seg.dim() == 2 and (attn.dim() < 3 or attn.shape[-3] != seg.shape[0]):
+            raise ValueError(f"(B, K) segment_lengths need attn of shape (..., B, sy, S) with B = {seg.shape[0]}, got {tuple(attn.shape)}")
+        end = torch.cumsum(seg, dim=-1)
+        first = end - seg
+        j = torch.arange(S)
+        member = ((j >= first[..., :, None]) & (j < end[..., :, None])).to(attn.dtype).to(attn.device)        # (K, S) or (B, K, S)
+        if seg.dim() == 1:
+            return attn @ member.t()
+        return torch.einsum("...bis,bks->...bik", attn, member)
 
     def beam_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, beam_width: int, return_scores: bool = False,
                     return_trace: bool = False, schedule=None):

@@ -1188,15 +1188,17 @@ def _dec_layers(layer_t, n_layers: int, grads=None):
     return layers if grads is None else (layers, array(_lib.DecLayerGrads, grads))
 
 
-def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b):
+def decoder_ragged(meta, tokens, memory, mem_lengths: torch.Tensor, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b,
+                   return_attention: bool = False):
     """Inference decode (no autograd) over a packed ragged memory: tokens (B, sy) int64, memory (sum_b S_b, d) with S_b = mem_lengths[b]
     ((B,) int32 host tensor); clip b cross-attends to its own rows only. meta as DecoderFn's (p_drop / p_pos ignored: inference).
-    Returns logits (B * sy, |V|) (egx_decoder_ragged_fwd)."""
+    Returns logits (B * sy, |V|) (egx_decoder_ragged_fwd); with return_attention (logits, attn (L, B, sy, max_b S_b) fp32): one
+    egx_decoder_cross_weights call on the same workspace, zeros beyond S_b."""
     with torch.no_grad():
-        return _decoder_ragged_fwd(None, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b)
+        return _decoder_ragged_fwd(None, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b, return_attention)
 
 
-def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b):
+def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_params, fc_w, fc_b, return_attention=False):
     """The forward of decoder_ragged (ctx None: egx_decoder_ragged_fwd in one shared workspace) and of RaggedDecoderFn
     (egx_decoder_ragged_train_fwd into a `saved` of the call's own, kept in ctx for the backward)."""
     lib = _lib.load()
@@ -1212,7 +1214,13 @@ def _decoder_ragged_fwd(ctx, meta, tokens, memory, mem_lengths, emb, pe, layer_p
     if ctx is None:
         nb = C.c_size_t(0)
         check(lib.egx_decoder_ragged_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(nb)))
-        check(lib.egx_decoder_ragged_fwd(*args, ptr(_workspace("dec_ragged", memory.device, nb.value)), _stream()))
+        ws = _workspace("dec_ragged", memory.device, nb.value)
+        check(lib.egx_decoder_ragged_fwd(*args, ptr(ws), _stream()))
+        if return_attention:
+            attn = torch.empty((meta["n_layers"], B, sy, cfg_args[3]), dtype=torch.float32, device=memory.device)
+            check(lib.egx_decoder_cross_weights(C.byref(cfg), B, ml.data_ptr(), ptr(ws), ptr(attn), _stream()))
+            _last_dec_impl[0] = "ragged"
+            return logits, attn
     else:
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_decoder_ragged_train_workspace(C.byref(cfg), B, ml.data_ptr(), C.byref(sv), C.byref(sc)))
@@ -1622,6 +1630,71 @@ def _decoder_backward(ctx, d_logits, ragged: bool):
     return (None, None, d_memory) + ((None,) if ragged else ()) + (g_emb, None, *g_layer, g_fcw, g_fcb)
 
 
+def decoder_attention(meta, tokens, memory, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b):
+    """DecoderFn's forward without autograd (inference: meta's dropout rates must be 0) that also returns the cross-attention weights:
+    egx_decoder_fwd, then egx_decoder_cross_weights on the same `saved`. Returns (logits (B * sy, |V|), attn (L, B, sy, S) fp32); the
+    logits have the bits DecoderFn gives."""
+    lib = _lib.load()
+    with torch.no_grad():
+        tokens, memory, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(tokens, memory, emb, pe, layer_params, fc_w, fc_b)
+        B, sy = tokens.shape
+        V, d = emb.shape
+        S = memory.shape[0] // B
+        cfg = _dec_config(meta, d, V, sy, S, True)
+        sv, sc = C.c_size_t(0), C.c_size_t(0)
+        check(lib.egx_decoder_workspace(C.byref(cfg), B, C.byref(sv), C.byref(sc)))
+        saved = _workspace("dec_saved", memory.device, sv.value)
+        scratch = _workspace("dec_scratch", memory.device, sc.value)
+        layers = _dec_layers(layer_t, meta["n_layers"])
+        logits = torch.empty((B * sy, V), dtype=torch.float32, device=memory.device)
+        attn = torch.empty((meta["n_layers"], B, sy, S), dtype=torch.float32, device=memory.device)
+        check(lib.egx_decoder_fwd(C.byref(cfg), ptr(tokens), ptr(memory), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B,
+                                  ptr(logits), ptr(saved), ptr(scratch), 0, _seed64(0), _stream()))
+        check(lib.egx_decoder_cross_weights(C.byref(cfg), B, None, ptr(saved), ptr(attn), _stream()))
+    return logits, attn
+
+
+CROSS_WEIGHTS_HEAD_DIMS = (16, 32, 64, 128)
+CROSS_WEIGHTS_MAX_KEYS = 1024
+
+
+def check_cross_weights(head_dim: int, Sk: int) -> None:
+    """The limits of egx_cross_attention_weights as a ValueError that names them (host work, before any device call)."""
+    if head_dim not in CROSS_WEIGHTS_HEAD_DIMS or not 1 <= Sk <= CROSS_WEIGHTS_MAX_KEYS:
+        raise ValueError(f"cross-attention weights are served for head dims {CROSS_WEIGHTS_HEAD_DIMS} and 1..{CROSS_WEIGHTS_MAX_KEYS} memory "
+                         f"tokens per clip: got head dim {head_dim}, {Sk} memory tokens")
+
+
+def cross_attention_weights(q: torch.Tensor, k: torch.Tensor, n_heads: int, Sq: int, Sk: int, mtab: Optional[torch.Tensor] = None):
+    """The head-averaged attention weights w[b, i, j] = (1 / H) sum_h softmax_j(q[b, i, h] . k[b, j, h] / sqrt(dh)) that
+    nn.MultiheadAttention returns with need_weights=True (egx_cross_attention_weights; no autograd). q (B * Sq, H * dh) and k (B * Sk, H * dh),
+    both fp32 or both bf16, rows b * Sq + i / b * Sk + j, head h at columns h * dh; 2-D views with unit column stride and a row stride that
+    is a multiple of 8 elements are read in place (the q / k columns of packed projections). mtab ((B, 2) int32 on the device: first key
+    row, key rows): ragged key sets, Sk then the longest; entries beyond a clip's rows come back as zeros. dh in (16, 32, 64, 128),
+    Sk <= 1024. Returns (B, Sq, Sk) fp32."""
+    lib = _lib.load()
+    for name, t in (("q", q), ("k", k)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"cross_attention_weights: {name} must be a 2-D fp32 or bf16 tensor on the GPU")
+    if q.dtype != k.dtype or q.shape[1] != k.shape[1] or n_heads < 1 or q.shape[1] % n_heads or Sq < 1 or q.shape[0] % Sq:
+        raise ValueError(f"cross_attention_weights: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} do not fit {n_heads} heads, "
+                         f"Sq = {Sq}")
+    check_cross_weights(q.shape[1] // n_heads, Sk)
+    B = q.shape[0] // Sq
+    q, k = [t if t.stride(1) == 1 and t.stride(0) % 8 == 0 else t.contiguous() for t in (q.detach(), k.detach())]
+    if mtab is None:
+        if k.shape[0] != B * Sk:
+            raise ValueError(f"cross_attention_weights: k has {k.shape[0]} rows, expected B * Sk = {B * Sk}")
+    elif not (isinstance(mtab, torch.Tensor) and mtab.is_cuda and mtab.dtype == torch.int32 and tuple(mtab.shape) == (B, 2)):
+        raise ValueError(f"cross_attention_weights: mtab must be a ({B}, 2) int32 tensor on the GPU (first key row, key rows)")
+    else:
+        mtab = mtab.contiguous()
+    out = torch.empty((B, Sq, Sk), dtype=torch.float32, device=q.device)
+    check(lib.egx_cross_attention_weights(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), int(q.dtype == torch.bfloat16), ptr(mtab),
+                                          B, n_heads, q.shape[1] // n_heads, Sq, Sk, ptr(out), Sk, _stream()))
+    return out
+
+
 def decoder_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S: int, n_layers: int) -> bool:
     """Shapes egx_decoder_fwd / egx_decoder_bwd serve (include/egot2x.h); everything else stays on the composed decoder."""
     return (compute == "bf16" and 256 <= d <= 1024 and d % 128 == 0 and n_heads > 0 and d % n_heads == 0 and d // n_heads in (32, 64)
@@ -1689,11 +1762,13 @@ def check_schedule(schedule, vocab: int, device=None, beam_width: int = 0) -> No
 
 
 def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, return_logits: bool = False,
-                     schedule: "TokenSchedule" = None):
+                     schedule: "TokenSchedule" = None, return_attention: bool = False):
     """Greedy generation in ONE asynchronous call (egx_decoder_generate; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory
     rows, pe (>= n_steps, d) positional rows, meta as DecoderFn's (dropout ignored: inference). Returns tokens (B, n_steps) int64 and, with
     return_logits, logits (n_steps, B, |V|) fp32 (else None). The workspace comes from the caching allocator: the call can be captured.
-    With a TokenSchedule: egx_decoder_generate_sched, step t's argmax over the words of row t % P, the other logits -inf."""
+    With a TokenSchedule: egx_decoder_generate_sched, step t's argmax over the words of row t % P, the other logits -inf.
+    With return_attention: egx_decoder_generate_attn and a third result, attn (L, n_steps, B, S) fp32, step t's head-averaged
+    cross-attention weights of every layer; tokens and logits keep their bits."""
     lib = _lib.load()
     with torch.no_grad():
         _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
@@ -1713,13 +1788,17 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
         logits = torch.empty((n_steps, B, V), dtype=torch.float32, device=mem2d.device) if return_logits else None
         args = (C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, n_steps, ptr(tokens),
                 ptr(logits), ptr(ws), _stream())
-        if schedule is None:
+        if schedule is not None:
+            check_schedule(schedule, V, mem2d.device)
+        if return_attention:
+            attn = torch.empty((meta["n_layers"], n_steps, B, mem2d.shape[0] // B), dtype=torch.float32, device=mem2d.device)
+            check(lib.egx_decoder_generate_attn(*args, *((0, None, None) if schedule is None else schedule._args()), ptr(attn)))
+        elif schedule is None:
             check(lib.egx_decoder_generate(*args))
         else:
-            check_schedule(schedule, V, mem2d.device)
             check(lib.egx_decoder_generate_sched(*args, *schedule._args()))
     _last_dec_impl[0] = "generate"
-    return tokens, logits
+    return (tokens, logits, attn) if return_attention else (tokens, logits)
 
 
 def decoder_beam_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int, beam_width: int) -> bool:

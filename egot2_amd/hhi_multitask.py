@@ -16,8 +16,10 @@ from .translator import PositionalEncoding, TranslatorMixin, encoder_layer_tenso
 
 
 class CustomDecoderLayer(nn.TransformerDecoderLayer):
-    """task_prompt_model.py:163-172 (need_weights=True only changes the discarded second return value); the extra
-    is_causal argument is what torch >= 2 passes."""
+    """task_prompt_model.py:163-172. need_weights=True is the one reason the reference subclasses the layer: a forward hook on
+    `multihead_attn` then sees the head-averaged cross-attention weights (B, sy, S), which task's tokens at which time steps the task prompt
+    reads. This module is a parameter container: the HIP decoder returns those weights through decode(..., return_attention=True) and
+    greedy_decode(..., return_attention=True) (egot2_amd/decoder.py). The extra is_causal argument is what torch >= 2 passes."""
 
     def __init__(self, d_model, nhead, dropout=0.1):
         super().__init__(d_model, nhead, dropout=dropout)
@@ -187,15 +189,21 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
         return self.encode_features(task, lam_feat, ttm_feat, asd_feat)
 
     # ---- decoder (HIP; row F1) ---------------------------------------------------------------------------
-    def decode(self, y, encoded_x, memory_lengths=None):
+    def decode(self, y, encoded_x, memory_lengths=None, *, return_attention=False):
         """(B, sy) tokens + (S, B, d) memory -> (sy, B, |V|); on the GPU this is the HIP decoder (egot2_amd/decoder.py).
         memory_lengths (B,) (inference only): encoded_x is the packed (sum_b S_b, d) memory of encode_features(..., lengths=) for 'ttm' /
-        'lam', clip b cross-attends to its own S_b rows."""
+        'lam', clip b cross-attends to its own S_b rows.
+        return_attention (eval mode, no autograd): (logits, attn) with attn (L, B, sy, S) fp32, per decoder layer the head-averaged
+        cross-attention weights a forward hook on the reference's layer.multihead_attn sees (CustomDecoderLayer, task_prompt_model.py:163-172);
+        with memory_lengths S is the longest memory and clip b's entries beyond S_b are zeros. The logits are those of the call without the
+        flag, bit for bit. attention_by_segment(attn, (T, T, T)) sums the 'ttm' memory's three task blocks."""
         if memory_lengths is not None:
             return self._egx_decode_ragged(y, encoded_x, memory_lengths, embedding=self.embedding, pos_embed=self.pos_embed,
-                                           decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate)
+                                           decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate,
+                                           return_attention=return_attention)
         return self._egx_decode(y, encoded_x, embedding=self.embedding, pos_embed=self.pos_embed,
-                                decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate)
+                                decoder=self.transformer_decoder, fc=self.fc, n_heads=self.n_heads, p_drop=self.dp_rate,
+                                return_attention=return_attention)
 
     def forward(self, video, video_asd, audio, audio_asd, target, task):
         assert task in ['lam', 'ttm', 'asd']

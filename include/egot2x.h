@@ -663,6 +663,42 @@ int egx_decoder_beam_sched(const egx_dec_config* cfg, const int64_t* start, cons
                            float* step_scores /* (n_steps, B, W) or NULL */, float* step_logits /* (n_steps, B, W, vocab) or NULL */,
                            void* workspace, void* stream, int period, const int* counts /* HOST int[period] */,
                            const int32_t* words /* DEVICE int32[period][vocab] */);
+/* ---- ABI v18 (additions): the decoder's cross-attention weights as an output ----
+ * The reference subclasses nn.TransformerDecoderLayer as CustomDecoderLayer so that _mha_block calls the cross-attention with
+ * need_weights=True (HHI/models/multitask/task_prompt_model.py:163-172, HOI/models/multitask/video_model_builder.py:20-30,
+ * video_model_builder_2task.py:24, HOI/models/lta/lta_models_seqdecoder.py:30-39): a forward hook on layer.multihead_attn then sees the
+ * head-averaged weights (B, sy, S) of every decoder layer: which task's tokens, at which time steps, the task prompt reads.
+ *   w[b, i, j] = (1 / H) sum_h softmax_j(q[b, i, h, :] . k[b, j, h, :] / sqrt(dh))
+ * Scores, max, exp, sum and normalisation in fp32; the head sum in head order 0 .. H - 1, then one multiply by 1 / H; every reduction
+ * has a fixed order and there are no atomics, so a clip's rows do not depend on its position in the batch. Inference only: the
+ * reference returns the weights after dropout, which these calls do not model. Beam search has no such output (a hypothesis changes
+ * slots every step; egx_decoder_beam's step_* trace is the tool there).
+ *
+ * egx_cross_attention_weights: the primitive, on the caller's tensors. q rows b * Sq + i (row stride ldq elements), k rows b * Sk + j
+ * (stride ldk), head h at columns [h * dh, (h + 1) * dh); operands_bf16 != 0: bf16 elements, else fp32. mtab (DEVICE int[B][2] or NULL):
+ * clip b's keys are rows [mtab[2b], + S_b) of k with S_b = mtab[2b + 1] clamped to 0 .. Sk. out fp32, row b * Sq + i at stride ldo >= Sk:
+ * Sk entries are written, entries j >= S_b as exact zeros. dh 16, 32, 64 or 128; Sq >= 1; 1 <= Sk <= 1024; any B. Refused before any
+ * device work: null q / k / out, another dh, Sk outside 1 .. 1024, ldo < Sk, ldq / ldk not a multiple of 8 elements or below H * dh,
+ * q / k not 16-byte aligned. One launch, asynchronous on `stream`, capturable. */
+int egx_cross_attention_weights(const void* q, int ldq, const void* k, int ldk, int operands_bf16, const int* mtab /* DEVICE int[B][2] or NULL */,
+                                int B, int H, int dh, int Sq, int Sk, float* out, int ldo, void* stream);
+/* The weights of the decode() call (task_prompt_model.py:260-269 through CustomDecoderLayer :163-172) that egx_decoder_fwd
+ * (mem_lengths NULL) or egx_decoder_ragged_fwd (mem_lengths: the SAME HOST int[B]) has just run with the same cfg and B on the same
+ * stream: reads every layer's cross-attention q and k | v rows from that call's `saved` / `workspace` (for ragged calls also the table it
+ * uploaded) and writes attn_out (n_layers, B, sy, S) fp32, S = cfg->S, for ragged calls the longest memory (zeros beyond S_b). n_layers
+ * launches. Refused before any device work: p_drop / p_pos > 0, every limit of the forward call, null pointers. */
+int egx_decoder_cross_weights(const egx_dec_config* cfg, int B, const int* mem_lengths /* HOST int[B] or NULL */, const void* saved,
+                              float* attn_out, void* stream);
+/* egx_decoder_generate_sched (period = 0: egx_decoder_generate) that also writes attn_out (n_layers, n_steps, B, S) fp32: after each
+ * layer's cross-attention of step t one launch of the primitive with Sq = 1 on the step's q and the layer's k | v, the weights the hook on
+ * the greedy loop of lta_models_seqdecoder.py:181-201 over CustomDecoderLayer (:30-39) sees in the last row of step t. Tokens and logits
+ * have the bits of the call without attn_out, which issues exactly the launches it issued before this entry existed. attn_out NULL is
+ * refused. Capturable as egx_decoder_generate. */
+int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe,
+                              int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps,
+                              int64_t* tokens_out, float* logits_out /* may be NULL */, void* workspace, void* stream, int period,
+                              const int* counts /* HOST int[period] */, const int32_t* words /* DEVICE int32[period][vocab] */,
+                              float* attn_out /* (n_layers, n_steps, B, S) */);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
