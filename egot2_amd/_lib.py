@@ -200,6 +200,8 @@ SIGNATURES = {
     "egx_gelu_bwd": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp]),
     "egx_linear_bwd_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "egx_linear_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "egx_colsum_ordered_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "egx_colsum_ordered": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "egx_gemm": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp,
                            C.c_size_t, _fp]),
     "egx_layernorm_fwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_float, _fp, _fp, _fp, C.c_int, C.c_int, _fp]),

@@ -327,17 +327,25 @@ __global__ __launch_bounds__(256) void embed_pos_kernel(const int64_t* __restric
     if (thresh) y *= drop_scale(key, (uint32_t)row, (uint32_t)c, thresh, inv);
     out[i] = y;
 }
+// d_emb[v][c] += sum over the rows whose token is v, in row order, of mask * scale * dy[row][c]: one thread per (v, c) and no atomics, so
+// the gradient of a token that several rows share has the same bits on every run. Work is V * rows * d token tests (the atomic scatter
+// it replaces: rows * d adds); this is the composed decoder's kernel, the fused one has dec_embed_grad_small_kernel
 __global__ __launch_bounds__(256) void embed_grad_kernel(const int64_t* __restrict__ tok, const float* __restrict__ dy,
                                                          float* __restrict__ d_emb, float scale, int rows, int d, int V,
                                                          uint64_t key, uint32_t thresh, float inv) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)rows * d) return;
-    int row = (int)(i / d), c = (int)(i - (size_t)row * d);
-    int64_t t = tok[row];
-    if (t < 0 || t >= V) return;
-    float g = dy[i] * scale;
-    if (thresh) g *= drop_scale(key, (uint32_t)row, (uint32_t)c, thresh, inv);
-    atomicAdd(d_emb + (size_t)t * d + c, g);
+    const int cb = (d + 255) / 256;                                      // column blocks per token
+    const int v = (int)(blockIdx.x / cb), c = (int)(blockIdx.x % cb) * 256 + threadIdx.x;
+    if (c >= d) return;
+    float acc = 0.f;
+    bool any = false;
+    for (int row = 0; row < rows; ++row) {
+        if (tok[row] != v) continue;                                     // block-uniform
+        float g = dy[(size_t)row * d + c] * scale;
+        if (thresh) g *= drop_scale(key, (uint32_t)row, (uint32_t)c, thresh, inv);
+        acc += g;
+        any = true;
+    }
+    if (any) d_emb[(size_t)v * d + c] += acc;
 }
 
 int embed_pos_fwd(const int64_t* tok, const float* emb, const float* pe, int pe_stride, float scale, float* out, int B, int sy,
@@ -352,8 +360,9 @@ int embed_pos_fwd(const int64_t* tok, const float* emb, const float* pe, int pe_
 int embed_pos_bwd(const int64_t* tok, const float* dy, float* d_emb, float scale, int B, int sy, int d, int V, uint64_t key,
                   uint32_t thresh, float inv, hipStream_t st) {
     EGX_CHECK(tok && dy && d_emb, "embed_pos_bwd: null pointer argument");
-    size_t n = (size_t)B * sy * d;
-    hipLaunchKernelGGL(embed_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tok, dy, d_emb, scale, B * sy, d, V,
+    if (B * sy <= 0 || d <= 0 || V <= 0) return 0;
+    EGX_CHECK((size_t)V * cdiv(d, 256) <= 0x7fffffffu, "embed_pos_bwd: V = %d, d = %d", V, d);
+    hipLaunchKernelGGL(embed_grad_kernel, dim3((unsigned)((size_t)V * cdiv(d, 256))), dim3(256), 0, st, tok, dy, d_emb, scale, B * sy, d, V,
                        key, thresh, inv);
     EGX_LAUNCH_CHECK();
     return 0;

@@ -693,6 +693,17 @@ int egx_linear_residual_fwd(const float* x, const float* W, const float* b, cons
 int egx_gelu_fwd(const float* z, float* h, size_t n, void* stream) { return gelu_fwd(z, h, n, (hipStream_t)stream); }
 int egx_gelu_bwd(const float* z, const float* dh, float* dz, size_t n, void* stream) { return gelu_bwd(z, dh, dz, n, (hipStream_t)stream); }
 
+// db[N] += colsum(dy[M, N]) with the row blocks' partial sums added in block order through `scratch` (no atomics between row blocks):
+// the same bits on every run. egx_linear_bwd's own column sum meets in atomicAdd; callers that need repeatable bias gradients (the
+// composed EgoT2-g decoder) pass db = NULL there and call this.
+size_t egx_colsum_ordered_scratch(int M, int N) { return colsum_part_bytes(M, N); }
+int egx_colsum_ordered(const float* dy, int M, int N, float* db, void* scratch, size_t scratch_bytes, void* stream) {
+    EGX_CHECK(dy && db, "egx_colsum_ordered: null pointer argument");
+    EGX_CHECK(scratch_bytes >= colsum_part_bytes(M, N) && (scratch || !colsum_part_bytes(M, N)),
+              "egx_colsum_ordered: scratch of %zu bytes, egx_colsum_ordered_scratch(%d, %d) = %zu", scratch_bytes, M, N, colsum_part_bytes(M, N));
+    return colsum_accum_ordered(dy, M, N, N, db, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 size_t egx_linear_bwd_scratch(int M, int N, int K) { return size_max(gemm_scratch_bytes(2, N, K, M), gemm_scratch_bytes(1, M, K, N)); }
 
 int egx_linear_bwd(const float* dy, const float* x, const float* W, float* dx, float* dW, float* db, int M, int N, int K,

@@ -83,6 +83,9 @@ int layernorm_bwd(const LnBwdParams& p, hipStream_t st);
 
 // out[c] += sum_r x[r * ld + c], r < rows, c < cols
 int colsum_accum(const float* x, int rows, int cols, int ld, float* out, hipStream_t st);
+// ... with the row blocks' partial sums in `part` (colsum_part_bytes(rows, cols) bytes) and added in block order: run-to-run bit-identical
+size_t colsum_part_bytes(int rows, int cols);
+int colsum_accum_ordered(const float* x, int rows, int cols, int ld, float* out, void* part, size_t part_bytes, hipStream_t st);
 // learned positional gradient: dpos[t * pos_stride + c] += sum_b dtok[(b * S + off + t) * d + c]  (dropout mask re-applied)
 int pos_grad_accum(const float* dtok, int B, int S, int off, int T, int d, float* dpos, int pos_stride,
                    uint64_t drop_key, uint32_t drop_thresh, float drop_inv_keep, hipStream_t st);

@@ -251,6 +251,31 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
     }
 }
 
+// colsum_accum with the caller's scratch for the row blocks' partial sums, added in block order (no atomics between row blocks): the same
+// bits on every run. colsum_part_bytes(rows, cols) bytes make it so; with less (or none) the row blocks grow to fit, or it is colsum_accum.
+static int colsum_row_blocks(int rows, int cols) {
+    const int cb = cdiv(cols, 64);
+    return cdiv(rows, max(32, cdiv(rows, max(1, 1024 / cb))));
+}
+size_t colsum_part_bytes(int rows, int cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    const int nb = colsum_row_blocks(rows, cols);
+    return nb > 1 ? (size_t)nb * cols * sizeof(float) : 0;
+}
+int colsum_accum_ordered(const float* x, int rows, int cols, int ld, float* out, void* part, size_t part_bytes, hipStream_t st) {
+    if (rows <= 0 || cols <= 0) return 0;
+    int nb = colsum_row_blocks(rows, cols);
+    if (nb <= 1 || det_on()) return colsum_accum(x, rows, cols, ld, out, st);       // (one row block: one add per column)
+    const size_t fit = part ? part_bytes / ((size_t)cols * sizeof(float)) : 0;
+    if (fit < 2) return colsum_accum(x, rows, cols, ld, out, st);
+    if ((size_t)nb > fit) nb = (int)fit;
+    const int rpb = cdiv(rows, nb);
+    dim3 g(cdiv(cols, 64), cdiv(rows, rpb));
+    hipLaunchKernelGGL(colsum_kernel, g, dim3(256), 0, st, x, rows, cols, ld, out, rpb, (float*)part);
+    EGX_LAUNCH_CHECK();
+    return det_reduce_rows((const float*)part, (size_t)cols, (int)g.y, cols, out, st);
+}
+
 int colsum_accum(const float* x, int rows, int cols, int ld, float* out, hipStream_t st) {
     if (rows <= 0 || cols <= 0) return 0;
     int cb = cdiv(cols, 64);

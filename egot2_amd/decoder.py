@@ -7,6 +7,7 @@ are parameter containers only; projections / FFN run through the MFMA GEMM (egx_
 egx_layernorm_*, the two attentions through egx_small_attention_* and the embedding through egx_embed_pos_*."""
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -75,6 +76,8 @@ class DecoderMixin:
         comp = "f32"        # (B * sy)-row GEMMs: negligible work, they always run the exact fp32 MFMA path
         comp_mem = getattr(self, "egx_compute", "f32")     # the K / V projection of the (B * S)-row memory follows the encoder's compute type
         train = bool(self.training)
+        # bias gradients summed in a fixed order: with the counter-based masks, a training step of this path repeats bit for bit under its seed
+        lin = functools.partial(F_egx.linear, ordered_bias=True)
         seed = self._egx_seed() if train else 0
         mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)          # batch-first rows b * S + s
         x = F_egx.EmbedPosFn.apply(y, embedding.weight, pos_embed.pe[:, 0, :], math.sqrt(d),
@@ -86,21 +89,21 @@ class DecoderMixin:
             site = lambda k: _SITE0 + (li << 8) + k  # noqa: E731
             p = p_drop if train else 0.0
             sa, ca = layer.self_attn, layer.multihead_attn
-            qkv = F_egx.linear(x, sa.in_proj_weight, sa.in_proj_bias, comp)
+            qkv = lin(x, sa.in_proj_weight, sa.in_proj_bias, comp)
             a = F_egx.SelfAttnSmallFn.apply(qkv, B, sy, n_heads, True, p, seed, site(1))
-            a = F_egx.dropout(F_egx.linear(a, sa.out_proj.weight, sa.out_proj.bias, comp), p_drop, train, seed, site(2))
+            a = F_egx.dropout(lin(a, sa.out_proj.weight, sa.out_proj.bias, comp), p_drop, train, seed, site(2))
             x = F_egx.layer_norm_residual(x, a, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
-            q = F_egx.linear(x, ca.in_proj_weight[:d], ca.in_proj_bias[:d], comp)
-            kv = F_egx.linear(mem2d, ca.in_proj_weight[d:], ca.in_proj_bias[d:], comp_mem)
+            q = lin(x, ca.in_proj_weight[:d], ca.in_proj_bias[:d], comp)
+            kv = lin(mem2d, ca.in_proj_weight[d:], ca.in_proj_bias[d:], comp_mem)
             c = F_egx.CrossAttnSmallFn.apply(q, kv, B, sy, S, n_heads, p, seed, site(3))
             if want_attn:
                 attn.append(F_egx.cross_attention_weights(q, kv[:, :d], n_heads, sy, S))
-            c = F_egx.dropout(F_egx.linear(c, ca.out_proj.weight, ca.out_proj.bias, comp), p_drop, train, seed, site(4))
+            c = F_egx.dropout(lin(c, ca.out_proj.weight, ca.out_proj.bias, comp), p_drop, train, seed, site(4))
             x = F_egx.layer_norm_residual(x, c, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
-            h = F_egx.dropout(F_egx.linear(x, layer.linear1.weight, layer.linear1.bias, comp, relu=True), p_drop, train, seed, site(5))
-            f = F_egx.dropout(F_egx.linear(h, layer.linear2.weight, layer.linear2.bias, comp), p_drop, train, seed, site(6))
+            h = F_egx.dropout(lin(x, layer.linear1.weight, layer.linear1.bias, comp, relu=True), p_drop, train, seed, site(5))
+            f = F_egx.dropout(lin(h, layer.linear2.weight, layer.linear2.bias, comp), p_drop, train, seed, site(6))
             x = F_egx.layer_norm_residual(x, f, layer.norm3.weight, layer.norm3.bias, layer.norm3.eps)
-        out = F_egx.linear(x, fc.weight, fc.bias, comp)                         # (B * sy, |V|)
+        out = lin(x, fc.weight, fc.bias, comp)                         # (B * sy, |V|)
         F_egx._last_dec_impl[0] = "composed"
         if want_attn:
             return out.view(B, sy, -1).permute(1, 0, 2), torch.stack(attn, 0)

@@ -1317,10 +1317,11 @@ def pool_head(tokens, ln_w=None, ln_b=None, W=None, b=None, eps: float = 1e-5):
 
 
 class LinearFn(torch.autograd.Function):
-    """y = x W^T + b for a 2-D x, through the MFMA GEMM."""
+    """y = x W^T + b for a 2-D x, through the MFMA GEMM. ordered_bias: the bias gradient is summed in a fixed order (egx_colsum_ordered:
+    the same bits on every run) instead of egx_linear_bwd's atomic column sum."""
 
     @staticmethod
-    def forward(ctx, x, W, b, compute: str, relu: bool = False):
+    def forward(ctx, x, W, b, compute: str, relu: bool = False, ordered_bias: bool = False):
         lib = _lib.load()
         x = _dev_f32(x, "x")
         W = _dev_f32(W, "W")
@@ -1332,6 +1333,7 @@ class LinearFn(torch.autograd.Function):
         ctx.compute = compute
         ctx.has_b = b is not None
         ctx.relu = bool(relu)
+        ctx.ordered_bias = bool(ordered_bias)
         ctx.save_for_backward(*((x, W, y) if relu else (x, W)))
         return y
 
@@ -1350,11 +1352,15 @@ class LinearFn(torch.autograd.Function):
         dx = torch.empty_like(x) if need[0] else None
         dW = torch.zeros_like(W) if need[1] else None
         db = torch.zeros(N, dtype=torch.float32, device=dev) if (ctx.has_b and need[2]) else None
+        ordered = ctx.ordered_bias and db is not None
         nbytes = lib.egx_linear_bwd_scratch(M, N, K)
-        scratch = _workspace("linear", dev, nbytes)
-        check(lib.egx_linear_bwd(ptr(dy), ptr(x), ptr(W), ptr(dx), ptr(dW), ptr(db), M, N, K, COMPUTE[ctx.compute],
+        nb_cs = lib.egx_colsum_ordered_scratch(M, N) if ordered else 0
+        scratch = _workspace("linear", dev, max(nbytes, nb_cs))
+        if ordered:         # (ahead of the GEMMs that use the scratch next on the stream)
+            check(lib.egx_colsum_ordered(ptr(dy), M, N, ptr(db), ptr(scratch), nb_cs, _stream()))
+        check(lib.egx_linear_bwd(ptr(dy), ptr(x), ptr(W), ptr(dx), ptr(dW), None if ordered else ptr(db), M, N, K, COMPUTE[ctx.compute],
                                  ptr(scratch), _stream()))
-        return dx, dW, db, None, None
+        return dx, dW, db, None, None, None
 
 
 class StackedLinearFn(torch.autograd.Function):
@@ -1400,9 +1406,9 @@ class StackedLinearFn(torch.autograd.Function):
         return (dx, None, None, None, None, *gw, *gb)
 
 
-def linear(x, W, b=None, compute: str = "f32", relu: bool = False):
+def linear(x, W, b=None, compute: str = "f32", relu: bool = False, ordered_bias: bool = False):
     shp = x.shape
-    y = LinearFn.apply(x.reshape(-1, shp[-1]), W, b, compute, relu)
+    y = LinearFn.apply(x.reshape(-1, shp[-1]), W, b, compute, relu, ordered_bias)
     return y.view(*shp[:-1], W.shape[0])
 
 

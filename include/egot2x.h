@@ -424,6 +424,10 @@ size_t egx_linear_bwd_scratch(int M, int N, int K);
 int egx_linear_bwd(const float* dy, const float* x, const float* W,
                    float* dx, float* dW, float* db, int M, int N, int K,
                    int compute, void* scratch, void* stream);
+/* db[N] += colsum(dy[M,N]) summed in a fixed order (row blocks' partial sums through scratch, added in block order): the same bits on
+ * every run, where egx_linear_bwd's db meets in fp32 atomics. scratch must hold egx_colsum_ordered_scratch(M,N) bytes (0: may be NULL). */
+size_t egx_colsum_ordered_scratch(int M, int N);
+int egx_colsum_ordered(const float* dy, int M, int N, float* db, void* scratch, size_t scratch_bytes, void* stream);
 
 /* --- single-op entry points (unit parity tests) --- */
 /* layout: 0 = NT (C = A[M,K] B[N,K]^T), 1 = NN (C = A[M,K] B[K,N]), 2 = TN (C = A[K,M]^T B[K,N]). */
@@ -518,7 +522,8 @@ int egx_small_attention_bwd(const float* q, int ldq, const float* k, int ldk, co
                             int ldo, float* dq, float* dk, float* dv, int B, int Sq, int Sk, int H, int dh, int causal,
                             float p_drop, uint64_t seed, uint32_t site, void* stream);
 /* out[b, t, :] = dropout(emb[tokens[b, t]] * scale + pe[t * pe_stride ...]); tokens (B, sy) int64, emb (V, d).
- * Backward: d_emb[tokens[b, t]] += scale * mask * dy[b, t]  (atomic accumulation into a zero-filled or live buffer). */
+ * Backward: d_emb[tokens[b, t]] += scale * mask * dy[b, t], a token's rows summed in row order (no atomics: the same bits on every run)
+ * into a zero-filled or live buffer. */
 int egx_embed_pos_fwd(const int64_t* tokens, const float* emb, const float* pe, int pe_stride, float scale, float* out,
                       int B, int sy, int d, int V, float p_drop, uint64_t seed, void* stream);
 int egx_embed_pos_bwd(const int64_t* tokens, const float* dy, float* d_emb, float scale, int B, int sy, int d, int V,

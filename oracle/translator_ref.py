@@ -73,7 +73,7 @@ def self_attention(x: torch.Tensor, in_w, in_b, out_w, out_b, n_heads: int, attn
     return linear(o, out_w, out_b)
 
 
-# Optional observer of every encoder layer's FFN pre-activation: relu_probe(prefix, a) is called with the layer's key prefix and
+# Optional observer of every encoder and decoder layer's FFN pre-activation: relu_probe(prefix, a) is called with the layer's key prefix and
 # a = linear1(x) (..., S, d_ff) just before the ReLU (tests/fp32_grade.py places linear1.bias away from the kink with it). None: no call.
 relu_probe = None
 
@@ -333,9 +333,10 @@ def hoi_ga_encode(sd, n_heads: int, task: str, feat_action, feat_lta=None) -> to
 
 
 # ---- EgoT2-g sequence decoder + vocabulary head ---------------------------------------------
-def attention(q_in: torch.Tensor, kv_in: torch.Tensor, in_w, in_b, out_w, out_b, n_heads: int, causal: bool) -> torch.Tensor:
+def attention(q_in: torch.Tensor, kv_in: torch.Tensor, in_w, in_b, out_w, out_b, n_heads: int, causal: bool, masks=None) -> torch.Tensor:
     """nn.MultiheadAttention math, batch-first: q_in (B, Sq, d), kv_in (B, Sk, d); packed in-projection rows
-    [Wq; Wk; Wv]; `causal` adds the reference's lower-triangular additive mask (get_tgt_mask)."""
+    [Wq; Wk; Wv]; `causal` adds the reference's lower-triangular additive mask (get_tgt_mask).
+    masks (B, H, Sq, Sk): keep-scale of the dropout on the probabilities (F.multi_head_attention_forward: dropout(softmax)); None = eval."""
     B, Sq, d = q_in.shape
     Sk = kv_in.shape[1]
     dh = d // n_heads
@@ -349,34 +350,47 @@ def attention(q_in: torch.Tensor, kv_in: torch.Tensor, in_w, in_b, out_w, out_b,
     scores = scores - scores.max(dim=-1, keepdim=True).values
     p = torch.exp(scores)
     p = p / p.sum(dim=-1, keepdim=True)
+    if masks is not None:
+        p = p * masks.to(p.dtype)
     o = (p @ v).permute(0, 2, 1, 3).reshape(B, Sq, d)
     return linear(o, out_w, out_b)
 
 
-def decoder_layer(x, mem, sd, prefix: str, n_heads: int, eps: float = 1e-5):
+def decoder_layer(x, mem, sd, prefix: str, n_heads: int, eps: float = 1e-5, masks=None):
     """Post-LN nn.TransformerDecoderLayer as subclassed by CustomDecoderLayer
     (HHI/models/multitask/task_prompt_model.py:163-172, HOI/models/multitask/video_model_builder.py:20-30):
-    x = norm1(x + SA(x, causal)); x = norm2(x + CA(x, memory)); x = norm3(x + FFN(x))."""
+    x = norm1(x + SA(x, causal)); x = norm2(x + CA(x, memory)); x = norm3(x + FFN(x)).
+    `masks` (train mode with EXPLICIT masks; None = eval): keep-scales at the layer's six dropout sites (torch 1.12 transformer.py
+    _sa_block / _mha_block / _ff_block) - "self" (B, H, sy, sy) and "cross" (B, H, sy, S) on the softmax outputs, "sa_out" / "ca_out"
+    (B, sy, d) = dropout1 / dropout2 on the out-projections before the residual add, "ffn" (B, sy, d_ff) = dropout on the activated
+    hidden, "ffn_out" (B, sy, d) = dropout3 on linear2's output. A missing or None entry leaves its site alone."""
     g = lambda k: sd[prefix + k]  # noqa: E731
+    mk = (lambda k: masks.get(k)) if masks is not None else (lambda k: None)  # noqa: E731
     a = attention(x, x, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), g("self_attn.out_proj.weight"),
-                  g("self_attn.out_proj.bias"), n_heads, True)
-    x = layer_norm(x + a, g("norm1.weight"), g("norm1.bias"), eps)
+                  g("self_attn.out_proj.bias"), n_heads, True, mk("self"))
+    x = layer_norm(x + _m(a, masks, "sa_out"), g("norm1.weight"), g("norm1.bias"), eps)
     c = attention(x, mem, g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias"),
-                  g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"), n_heads, False)
-    x = layer_norm(x + c, g("norm2.weight"), g("norm2.bias"), eps)
-    f = linear(torch.relu(linear(x, g("linear1.weight"), g("linear1.bias"))), g("linear2.weight"), g("linear2.bias"))
-    return layer_norm(x + f, g("norm3.weight"), g("norm3.bias"), eps)
+                  g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"), n_heads, False, mk("cross"))
+    x = layer_norm(x + _m(c, masks, "ca_out"), g("norm2.weight"), g("norm2.bias"), eps)
+    a = linear(x, g("linear1.weight"), g("linear1.bias"))
+    if relu_probe is not None:
+        relu_probe(prefix, a)
+    h = _m(torch.relu(a), masks, "ffn")
+    f = linear(h, g("linear2.weight"), g("linear2.bias"))
+    return layer_norm(x + _m(f, masks, "ffn_out"), g("norm3.weight"), g("norm3.bias"), eps)
 
 
-def g_decode(sd, n_heads: int, y: torch.Tensor, memory: torch.Tensor) -> torch.Tensor:
-    """decode() of the EgoT2-g models (task_prompt_model.py:260-269 / video_model_builder.py:150-159), dropout off:
-    y (B, sy) int64 prompt/target tokens, memory (S, B, d) from encode() -> (sy, B, |V|) vocabulary logits."""
+def g_decode(sd, n_heads: int, y: torch.Tensor, memory: torch.Tensor, masks=None) -> torch.Tensor:
+    """decode() of the EgoT2-g models (task_prompt_model.py:260-269 / video_model_builder.py:150-159): y (B, sy) int64 prompt/target
+    tokens, memory (S, B, d) from encode() -> (sy, B, |V|) vocabulary logits. masks=None: dropout off. masks = {"embed": (B, sy, d),
+    "layers": [decoder_layer masks, ...]} (tests/dropmask.py decoder_masks): train mode under explicit keep-scales, "embed" on
+    `embedding * sqrt(d) + pe` (PositionalEncoding's dropout, applied to the sum)."""
     d = sd["embedding.weight"].shape[1]
     sy = y.shape[1]
-    x = sd["embedding.weight"][y] * math.sqrt(d) + sd["pos_embed.pe"][:sy, 0, :]        # (B, sy, d)
+    x = _m(sd["embedding.weight"][y] * math.sqrt(d) + sd["pos_embed.pe"][:sy, 0, :], masks, "embed")        # (B, sy, d)
     mem = memory.permute(1, 0, 2)
     for i in range(n_layers_of(sd, "transformer_decoder.")):
-        x = decoder_layer(x, mem, sd, f"transformer_decoder.layers.{i}.", n_heads)
+        x = decoder_layer(x, mem, sd, f"transformer_decoder.layers.{i}.", n_heads, masks=None if masks is None else masks["layers"][i])
     return linear(x, sd["fc.weight"], sd["fc.bias"]).permute(1, 0, 2)
 
 

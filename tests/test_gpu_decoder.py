@@ -107,6 +107,51 @@ def test_embed_pos_and_scatter_gradient(egx_lib, cuda):
     assert (e.grad.cpu().double() - er.grad).abs().max().item() < 1e-4
 
 
+@pytest.mark.parametrize("V,d,B,sy", [(70001, 64, 40, 3), (5, 320, 67, 8)])
+def test_embed_scatter_sums_shared_tokens_in_row_order(egx_lib, cuda, V, d, B, sy):
+    """egx_embed_pos_bwd without atomics: a vocabulary beyond 65535 words (one workgroup row per word and 256 columns), d beyond one
+    column block, and tokens shared by many rows (B * sy = 536 rows over 5 words): the fp64 scatter under the forward's dropout mask, and
+    the same bits on a second run."""
+    from egot2_amd import functional as F_egx
+    g = torch.Generator().manual_seed(V)
+    emb = torch.randn(V, d, generator=g)
+    pe = torch.randn(sy, d, generator=g)
+    tok = torch.randint(0, min(V, 5), (B, sy), generator=g)
+    tok[0, 0] = V - 1
+    w = torch.randn(B * sy, d, generator=g)
+    grads = []
+    for _ in range(2):
+        e = emb.to(cuda).requires_grad_(True)
+        out = F_egx.EmbedPosFn.apply(tok.to(cuda), e, pe.to(cuda), math.sqrt(d), 0.25, 77)
+        (out * w.to(cuda)).sum().backward()
+        grads.append(e.grad.clone())
+    assert torch.equal(grads[0], grads[1])
+    keep = (out.detach().cpu() != 0).double() / 0.75               # the mask the forward drew (no output is exactly 0 otherwise)
+    ref = torch.zeros(V, d, dtype=torch.float64)
+    ref.index_add_(0, tok.reshape(-1), keep * w.double() * math.sqrt(d))
+    assert (grads[0].cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+    assert grads[0][V - 1].abs().max().item() > 0 and (V <= 6 or grads[0][5:V - 1].abs().max().item() == 0)
+
+
+def test_linear_ordered_bias_gradient_repeats_bit_for_bit(egx_lib, cuda):
+    """functional.linear(ordered_bias=True): the bias gradient over many row blocks (540 rows, 32 per block) equals the fp64 column sum and
+    has the same bits on every run; the other gradients are those of the default call, bit for bit."""
+    from egot2_amd import functional as F_egx
+    g = torch.Generator().manual_seed(6)
+    x, W, b = torch.randn(540, 256, generator=g), torch.randn(512, 256, generator=g) / 16, torch.randn(512, generator=g)
+    w = torch.randn(540, 512, generator=g)
+    res = []
+    for ordered in (True, True, False):
+        t = [v.to(cuda).requires_grad_(True) for v in (x, W, b)]
+        (F_egx.linear(t[0], t[1], t[2], "f32", ordered_bias=ordered) * w.to(cuda)).sum().backward()
+        res.append([v.grad.clone() for v in t])
+    assert all(torch.equal(a, c) for a, c in zip(res[0], res[1]))
+    assert torch.equal(res[0][0], res[2][0]) and torch.equal(res[0][1], res[2][1])
+    ref = w.double().sum(0)
+    assert (res[0][2].cpu().double() - ref).abs().max().item() < 1e-4 * ref.abs().max().item()
+    assert (res[2][2].cpu().double() - ref).abs().max().item() < 1e-4 * ref.abs().max().item()
+
+
 def test_relu_linear_and_layernorm_residual(egx_lib, cuda):
     from egot2_amd import functional as F_egx
     g = torch.Generator().manual_seed(3)
@@ -131,7 +176,8 @@ def test_relu_linear_and_layernorm_residual(egx_lib, cuda):
 def test_decoder_trains_with_dropout(egx_lib, cuda, S, compute):
     """Train-mode decode (dropout on every site): finite, deterministic per seed, and gradients reach every decoder
     parameter; eval-mode decode is independent of the seed. bf16 = the fused decoder (S = 180: its long-memory cross-attention
-    kernel with dropout on the probabilities), f32 = the composed one."""
+    kernel with dropout on the probabilities), f32 = the composed one. The arithmetic under the masks (every site's placement, scale and
+    forward / backward keying against the fp64 oracle) is held by tests/test_gpu_decoder_dropout.py."""
     from types import SimpleNamespace as NS
     from egot2_amd import hhi_multitask
     from tests.util import seeded_state_dict

@@ -1,8 +1,10 @@
 """-m gpu: ragged-batch TRAINING of the EgoT2-g HHI model (egx_ragged_encode_train_fwd / egx_ragged_encode_bwd on the wide bf16 path,
 egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd): one encoder and one decoder forward + backward per batch of clips of their own
 lengths, for the training step of HHI/tasks/multitask/video_tasktranslation.py:39-66, which the reference can only feed same-length
-mini-batches (:144-156). Padded frames are NaN unless stated, no clip is left out of any comparison. The oracle has no dropout masks, so parity
-against it is asserted at p = 0 and the masks are pinned through the uniform training call (equal lengths reproduce it bit for bit). Bounds
+mini-batches (:144-156). Padded frames are NaN unless stated, no clip is left out of any comparison. Parity against the oracle is asserted
+here at p = 0, and the masks are pinned through the uniform training call (equal lengths reproduce it bit for bit); under p > 0 the wide
+encoder's masks are held to the oracle's by test_gpu_dropout_parity.py, the decoder's (uniform and ragged, clip by clip) by
+test_gpu_decoder_dropout.py. Bounds
 are the project's for this model in bf16 (test_gpu_parity_hygiene.py, test_gpu_ragged_g.py): memory 1e-2 and logits 1.5e-2 (asd logits 4e-2)
 relative to max(1, |ref|); per-parameter gradient error < 1.5e-1 for the 3 + 3-layer stack, fc.weight < 2e-2."""
 import numpy as np
@@ -154,8 +156,9 @@ def test_asd_and_lam_training_match_the_oracle(egx_lib, cuda):
 @pytest.mark.parametrize("T", [15, 60])
 def test_equal_lengths_reproduce_the_uniform_training_call_bit_for_bit(egx_lib, cuda, T):
     """T = 15: S = 45, the short attention class; T = 60: S = 180, the long class (dropout row stride 512). Same host seed, p_drop = p_pos =
-    0.1: memory, logits and every gradient equal the uniform training call's. This pins the dropout masks of the ragged kernels: the uniform
-    path's masks are held against the oracle's by test_gpu_dropout_parity.py / tests/dropmask.py."""
+    0.1: memory, logits and every gradient equal the uniform training call's. This pins the dropout masks of the ragged kernels to the uniform
+    path's, which are held against the oracle's: the wide encoder's by test_gpu_dropout_parity.py (tests/dropmask.py encoder_masks), the
+    fused decoder's by test_gpu_decoder_dropout.py (decoder_masks; its ragged case also compares mixed lengths clip by clip)."""
     from egot2_amd import functional as F_egx
     m, _ = _model(cuda, p=0.1)
     B = 16
