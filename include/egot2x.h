@@ -396,7 +396,10 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
                    const egx_head_grads* head_grads, int training, uint64_t seed, void* stream);
 
 /* pooled = mean_s tokens[b, s, :]; y = ln_w ? LN(pooled) : pooled; out = W ? y W^T + b : y.
- * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL. */
+ * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL; d <= 1024 (any d, multiple of 4 or not). Both are checked: a call
+ * outside them returns non-zero and writes nothing.
+ * Backward: d_tokens (B, S, d) is overwritten (=), the S rows of a clip all alike; d_ln_w, d_ln_b, d_W and d_b are added into (+=, the clips
+ * meet in fp32 atomics) and may each be NULL. */
 int egx_pool_head_fwd(const float* tokens, int B, int S, int d,
                       const float* ln_w, const float* ln_b, float ln_eps,
                       const float* W, const float* b, int n_out,
@@ -419,13 +422,14 @@ int egx_linear_residual_fwd(const float* x, const float* W, const float* b, cons
 int egx_gelu_fwd(const float* z, float* h, size_t n, void* stream);
 int egx_gelu_bwd(const float* z, const float* dh, float* dz, size_t n, void* stream);
 /* dx[M,K] = dy W ; dW[N,K] += dy^T x ; db[N] += colsum(dy). Any output may be NULL.
- * scratch must hold egx_linear_bwd_scratch(M,N,K) bytes. */
+ * scratch must hold egx_linear_bwd_scratch(M,N,K) bytes. dW needs it (and x); dx and db alone also run with scratch = NULL. */
 size_t egx_linear_bwd_scratch(int M, int N, int K);
 int egx_linear_bwd(const float* dy, const float* x, const float* W,
                    float* dx, float* dW, float* db, int M, int N, int K,
                    int compute, void* scratch, void* stream);
 /* db[N] += colsum(dy[M,N]) summed in a fixed order (row blocks' partial sums through scratch, added in block order): the same bits on
- * every run, where egx_linear_bwd's db meets in fp32 atomics. scratch must hold egx_colsum_ordered_scratch(M,N) bytes (0: may be NULL). */
+ * every run, where egx_linear_bwd's db meets in fp32 atomics. scratch must hold egx_colsum_ordered_scratch(M,N) bytes (0: may be NULL); a
+ * call with fewer scratch_bytes is refused and leaves db alone. */
 size_t egx_colsum_ordered_scratch(int M, int N);
 int egx_colsum_ordered(const float* dy, int M, int N, float* db, void* scratch, size_t scratch_bytes, void* stream);
 
@@ -513,7 +517,9 @@ int egx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
  * causal != 0 (needs Sq == Sk) applies the reference's lower-triangular target mask. Self-attention passes the packed
  * qkv rows three times (q, q + d, q + 2d with ld = 3d), cross-attention q and the packed kv rows of the memory.
  * p_drop > 0: dropout on the probabilities, keyed by (seed, site); the backward regenerates the same mask and
- * recomputes the probabilities (nothing is saved). */
+ * recomputes the probabilities (nothing is saved).
+ * Any head dim from 1 to 128 (not only multiples of 32) and any row strides >= H * dh, each operand its own: rows need no alignment, and
+ * nothing outside the (row, head column) windows is read or written. */
 int egx_small_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
                             int B, int Sq, int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site,
                             void* stream);
@@ -704,7 +710,8 @@ int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, c
                               int64_t* tokens_out, float* logits_out /* may be NULL */, void* workspace, void* stream, int period,
                               const int* counts /* HOST int[period] */, const int32_t* words /* DEVICE int32[period][vocab] */,
                               float* attn_out /* (n_layers, n_steps, B, S) */);
-/* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). */
+/* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). Wherever y is not > 0 (y = NaN, -0 and
+ * -inf included) dy becomes +0; a denormal y > 0 keeps its dy. n = 0 touches nothing. */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
 /* Producer side of the feature hand-off: the `middle=True` head of the frozen PNR / OSCC backbones,
  * ResNetKeyframeLocalizationHead.forward (HOI/models/pnr/head_helper.py:353-373) = AvgPool3d((kt, kh, kw), stride 1) of the res5
