@@ -171,6 +171,9 @@ SIGNATURES = {
     "egx_decoder_cross_weights": (C.c_int, [C.POINTER(DecConfig), C.c_int, _fp, _fp, _fp, _fp]),
     "egx_decoder_generate_attn": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int, C.c_int,
                                             _fp, _fp, _fp, _fp, C.c_int, C.POINTER(C.c_int), _fp, _fp]),
+    "egx_decoder_forced_workspace": (C.c_int, [C.POINTER(DecConfig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egx_decoder_forced": (C.c_int, [C.POINTER(DecConfig), _fp, _fp, _fp, _fp, _fp, C.c_int, C.POINTER(DecLayer), _fp, _fp, C.c_int, C.c_int,
+                                     C.c_int, _fp, _fp, _fp, _fp]),
     "egx_decoder_bwd": (C.c_int, [C.POINTER(DecConfig), _fp, C.POINTER(DecLayer), _fp, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                   C.POINTER(DecLayerGrads), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_uint64, _fp]),
     "egx_comm_unique_id": (C.c_int, [_fp]),

@@ -2530,3 +2530,262 @@ int egx_decoder_beam_sched(const egx_dec_config* cfg, const int64_t* start, cons
 }
 
 }  // extern "C"
+
+// ---- teacher-forced decoding on the K/V-cached step (egx_decoder_forced) ----
+// egx_decoder_generate's step over B * R rows (row b * R + r: target sequence r of clip b, as the beam's slots: the cross-attention runs with
+// Sq = R on the clip's memory) with the next input row taken from the caller's tokens instead of the argmax: every input row is embedded in
+// one launch up front, each step's last-layer rows go into an (n_steps, B * R, d) slab, and ONE head launch after the last step turns the
+// slab into logits and log-probabilities. The validation step of HOI/tasks/multitask/video_task.py:601-617 and video_task_action.py:83-88
+// (model(video, target[:, :-1], 'lta_verb') over 21 tokens) and the 40-token call of HOI/models/lta/lta_models_seqdecoder.py:175-179.
+namespace {
+
+constexpr int FORCED_MAX_R = DA_MAXQ;
+
+// x32[t * M + m] = emb[tok[m * n + t]] * scale + pe[t] (dec_embed_kernel's expression; a token outside [0, V) embeds as the zero row):
+// tokens are (M, n) row-major, the rows leave in step-major order so that step t reads M contiguous rows. Layer 0 reads the fp32 rows only.
+__global__ __launch_bounds__(256) void forced_embed_kernel(const int64_t* __restrict__ tok, const float* __restrict__ emb, const float* __restrict__ pe,
+                                                           int pe_stride, float scale, float* __restrict__ x32, int M, int n, int d, int V) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;          // one float4 each
+    if (i >= (size_t)M * n * (d / 4)) return;
+    const size_t row = i / (d / 4);                                    // output row t * M + m
+    const int c = (int)(i % (d / 4)) * 4;
+    const int t = (int)(row / M), m = (int)(row % M);
+    const int64_t w = tok[(size_t)m * n + t];
+    float4 e = make_float4(0, 0, 0, 0);
+    if (w >= 0 && w < V) e = *reinterpret_cast<const float4*>(emb + (size_t)w * d + c);
+    const float4 pp = *reinterpret_cast<const float4*>(pe + (size_t)t * pe_stride + c);
+    *reinterpret_cast<float4*>(x32 + row * d + c) = make_float4(e.x * scale + pp.x, e.y * scale + pp.y, e.z * scale + pp.z, e.w * scale + pp.w);
+}
+
+// The vocabulary head over the slab, GH_CLIPS rows per workgroup: logits by head_logits<GH_CLIPS>, unlisted (a row's logits depend on
+// neither its slot nor its neighbours: the bits gen_head_kernel computes for the row), then one wave per row: the logits row to logits_out
+// when given, and with targets logprob = logit[target] - max - log(sum exp(logit - max)) in fp32, the sum lane-strided ascending, then
+// the xor butterfly. A target outside [0, V) gives exactly 0.0; a NaN logit reaches the sum and so the row's logprob.
+struct ForcedHeadParams {
+    const float* x;             // (n * M, d): row t * M + m
+    const float* fc_w; const float* fc_b;
+    const int64_t* targets;     // (M, n) or null
+    float* logits;              // (n * M, V) or null
+    float* logprob;             // (M, n) or null
+    int rows, M, n, d, V;
+};
+__global__ __launch_bounds__(64 * GH_WAVES) void forced_head_kernel(ForcedHeadParams p) {
+    extern __shared__ __align__(16) float fh_sm[];
+    float* sx = fh_sm;                          // [GH_CLIPS][d]
+    float* sl = fh_sm + GH_CLIPS * p.d;         // [GH_CLIPS][V]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = p.d, V = p.V;
+    const int g0 = blockIdx.x * GH_CLIPS, nb = p.rows - g0 < GH_CLIPS ? p.rows - g0 : GH_CLIPS;
+    for (int i = tid * 4; i < GH_CLIPS * d; i += 256 * GH_WAVES) {
+        const int r = i / d;
+        float4 v = make_float4(0, 0, 0, 0);
+        if (r < nb) v = *reinterpret_cast<const float4*>(p.x + (size_t)g0 * d + i);
+        *reinterpret_cast<float4*>(sx + i) = v;
+    }
+    __syncthreads();
+    head_logits<GH_CLIPS>(p.fc_w, p.fc_b, sx, sl, d, V, nullptr, 0, lane, wave);
+    __syncthreads();
+    if (wave >= nb) return;
+    const int g = g0 + wave;
+    const float* row = sl + wave * V;
+    float mx = -INFINITY;
+    for (int v = lane; v < V; v += 64) {
+        const float x = row[v];
+        if (p.logits) p.logits[(size_t)g * V + v] = x;
+        mx = fmaxf(mx, x);                      // (a NaN is skipped here and caught by the sum)
+    }
+    if (!p.logprob) return;
+    mx = wmax64(mx);
+    float sum = 0.f;
+    for (int v = lane; v < V; v += 64) sum += expf(row[v] - mx);
+    const float lse = logf(wsum64d(sum));
+    if (lane == 0) {
+        const int t = g / p.M, m = g - t * p.M;
+        const size_t o = (size_t)m * p.n + t;
+        const int64_t w = p.targets[o];
+        p.logprob[o] = w >= 0 && w < V ? (row[(int)w] - mx) - lse : 0.f;
+    }
+}
+
+struct FPlan {
+    int B, R, n, S, d, H, dff, L, V;
+    size_t M, Nm;
+    size_t zero, mem16, xin32, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
+    GLayer layer[16];
+    size_t bytes;
+};
+
+// The checks of the call and of the workspace query, then egx_decoder_beam's layout over M = B * R target rows without the beam's state,
+// plus the two (n_steps, M, d) fp32 slabs: the embedded input rows and the last layer's output rows.
+int make_fplan(const egx_dec_config* c, int B, int R, int n_steps, FPlan& pl) {
+    EGX_CHECK(c, "null decoder config");
+    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_forced: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
+    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_forced: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
+    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_forced: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
+    EGX_CHECK(R >= 1 && R <= FORCED_MAX_R, "egx_decoder_forced: R = %d (1..%d)", R, FORCED_MAX_R);
+    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits with R target rows per clip (cfg->sy is not read)
+        egx_dec_config one = *c;
+        one.sy = R;
+        DPlan dp;
+        if (make_dplan(&one, B, dp)) return 1;
+    }
+    EGX_CHECK((size_t)B * R <= (size_t)0x7fffffff / (size_t)(3 * c->d_model) && (size_t)B * c->S <= (size_t)0x7fffffff / (size_t)(2 * c->d_model),
+              "egx_decoder_forced: B = %d with R = %d, S = %d is too large", B, R, c->S);
+    memset(&pl, 0, sizeof(pl));
+    pl.B = B; pl.R = R; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
+    pl.M = (size_t)B * R; pl.Nm = (size_t)B * c->S;
+    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
+    size_t cur = 0;
+    pl.zero = dtake(cur, 1024);
+    pl.mem16 = dtake(cur, Nm * d * 2);
+    for (int l = 0; l < pl.L; ++l) {
+        GLayer& o = pl.layer[l];
+        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
+        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
+        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
+        o.kv = dtake(cur, Nm * 2 * d * 2);
+        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
+    }
+    pl.xin32 = dtake(cur, M * n_steps * d * 4);
+    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
+    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
+    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 256);
+    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
+    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
+    pl.xL32 = dtake(cur, M * n_steps * d * 4);
+    pl.bytes = cur;
+    return 0;
+}
+
+int forced_run(const egx_dec_config* cfg, const int64_t* tokens, const int64_t* targets, const float* memory, const float* emb, const float* pe,
+               int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int R, int n_steps, float* logits_out,
+               float* logprob_out, void* workspace, void* stream) {
+    FPlan pl;
+    if (make_fplan(cfg, B, R, n_steps, pl)) return 1;
+    EGX_CHECK(logits_out || logprob_out, "egx_decoder_forced: logits_out and logprob_out are both null: nothing to compute");
+    EGX_CHECK(!logprob_out || targets, "egx_decoder_forced: logprob_out without targets");
+    EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && fc_b && workspace, "egx_decoder_forced: null pointer argument");
+    EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_forced: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, M = (int)pl.M, dh = d / pl.H;
+    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
+    const void* zero = at<char>(ws, pl.zero);
+    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
+    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
+    {   // every weight -> bf16 once, one launch (as egx_decoder_generate)
+        WideCastBatch cb;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
+        }
+        if (wide_cast_flush(cb, st)) return 1;
+    }
+    // every step's input rows in one launch: all B * R * n_steps tokens are known up front
+    hipLaunchKernelGGL(forced_embed_kernel, dim3((unsigned)(((size_t)M * n_steps * (d / 4) + 255) / 256)), dim3(256), 0, st, tokens, emb, pe, pe_stride,
+                       sqrtf((float)d), at<float>(ws, pl.xin32), M, n_steps, d, pl.V);
+    EGX_LAUNCH_CHECK();
+    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* Wt, int rows, int N, int K, const float* bias, float* Cf, bf16_t* Cb,
+                     int relu, const float* residual) -> int {
+        WideGemmParams g;
+        g.A = A; g.B = Wt; g.M = rows; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
+        g.residual = residual; g.ldr = N; g.zero_page = zero;
+        return wide_gemm_nt(g, s_);
+    };
+    auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
+                  const float* residual) -> int { return nt_on(st, A, lda, Wt, M, N, K, bias, Cf, Cb, relu, residual); };
+    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
+        WideLnFwdParams lp;
+        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = M; lp.d = d;
+        return wide_ln_fwd(lp, st);
+    };
+    // the memory's K | V, once per layer and per CLIP (B * S rows): on the side stream beside step 0 (eager), on the caller's stream under capture
+    SideStream& SS = side_stream();
+    SideJoin sj(SS, st);
+    const bool side = side_wanted(SS, st);
+    if (side) {
+        if (SS.order(st, SS.s)) return 1;
+        sj.forked = true;
+    }
+    for (int l = 0; l < pl.L; ++l) {
+        const GLayer& o = pl.layer[l];
+        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
+        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
+    }
+    for (int t = 0; t < n_steps; ++t) {
+        const float* xin = cat<float>(ws, pl.xin32) + (size_t)t * M * d;        // layer 0's input rows: the caller's tokens of step t
+        float* xL = at<float>(ws, pl.xL32) + (size_t)t * M * d;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = layers[l];
+            const bool last = l + 1 == pl.L;
+            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
+            const float* x32 = f32_self ? xin : cat<float>(ws, pl.x32);
+            if (f32_self) {
+                GemmParams g;
+                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = M; g.N = 3 * d; g.K = d;
+                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
+                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
+            } else if (nt(cat<bf16_t>(ws, pl.x16), d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
+            {
+                GenAttnParams a;
+                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
+                a.cache = at<char>(ws, o.cache); a.o = at<bf16_t>(ws, pl.sa);
+                a.B = M; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
+                if (gen_self_attn(a, dh, f32_self, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
+            // cross-attention of the clip's R new rows onto its S memory rows: dec_attn with Sq = R
+            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
+            if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
+            {
+                DecAttnParams a;
+                memset(&a, 0, sizeof(a));
+                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
+                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
+                a.B = B; a.H = pl.H; a.Sq = R; a.Sk = pl.S; a.causal = 0;
+                if (dec_attn<false>(a, dh, false, st)) return 1;
+            }
+            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
+            // FFN
+            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
+            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? xL : at<float>(ws, pl.x32), last ? nullptr : at<bf16_t>(ws, pl.x16))) return 1;
+        }
+    }
+    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    ForcedHeadParams hp;
+    hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.targets = targets; hp.logits = logits_out; hp.logprob = logprob_out;
+    hp.rows = M * n_steps; hp.M = M; hp.n = n_steps; hp.d = d; hp.V = pl.V;
+    hipLaunchKernelGGL(forced_head_kernel, dim3(cdiv(hp.rows, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_forced_workspace(const egx_dec_config* cfg, int B, int R, int n_steps, size_t* bytes) {
+    FPlan pl;
+    if (make_fplan(cfg, B, R, n_steps, pl)) return 1;
+    if (bytes) *bytes = pl.bytes;
+    return 0;
+}
+
+int egx_decoder_forced(const egx_dec_config* cfg, const int64_t* tokens, const int64_t* targets, const float* memory, const float* emb,
+                       const float* pe, int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int R,
+                       int n_steps, float* logits_out, float* logprob_out, void* workspace, void* stream) {
+    return forced_run(cfg, tokens, targets, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, R, n_steps, logits_out, logprob_out, workspace, stream);
+}
+
+}  // extern "C"

@@ -73,6 +73,13 @@ class DecoderMixin:
                 return out.view(B, sy, -1).permute(1, 0, 2), attn
             out = F_egx.DecoderFn.apply(meta, y, mem2d, embedding.weight, pos_embed.pe[:sy, 0, :], *params, fc.weight, fc.bias)
             return out.view(B, sy, -1).permute(1, 0, 2)
+        if (9 <= sy <= 64 and not want_attn and not self.training and not torch.is_grad_enabled()
+                and self._egx_fused_decoder_ok(decoder, d, n_heads, 1, S)
+                and F_egx.decoder_forced_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, S,
+                                                   len(decoder.layers), embedding.weight.shape[0], sy, 1)):
+            # 9 .. 64 target tokens at inference (the validation step's model(video, target[:, :-1], task)): the fused decoder stops at 8
+            # rows, so the rows run one at a time through the K/V-cached step, ONE egx_decoder_forced call
+            return self._egx_forced(encoded_x, y[:, None, :], None, True, embedding, pos_embed, decoder, fc, n_heads)[0].view(sy, B, -1)
         comp = "f32"        # (B * sy)-row GEMMs: negligible work, they always run the exact fp32 MFMA path
         comp_mem = getattr(self, "egx_compute", "f32")     # the K / V projection of the (B * S)-row memory follows the encoder's compute type
         train = bool(self.training)
@@ -329,6 +336,79 @@ class DecoderMixin:
         if seg.dim() == 1:
             return attn @ member.t()
         return torch.einsum("...bis,bks->...bik", attn, member)
+
+    def _egx_forced(self, encoded_x, y3, targets3, return_logits, embedding, pos_embed, decoder, fc, n_heads):
+        """One functional.decoder_forced call on validated arguments: y3 / targets3 (B, K, sy) -> (logits (sy, B * K, |V|) or None, logprob
+        (B, K, sy) or None)."""
+        S, B, d = encoded_x.shape
+        sy = y3.shape[2]
+        meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, 0.0)
+        mem2d = encoded_x.permute(1, 0, 2).contiguous().view(B * S, d)
+        return F_egx.decoder_forced(meta, y3, targets3, mem2d, embedding.weight, pos_embed.pe[:sy, 0, :], params, fc.weight, fc.bias,
+                                    return_logits)
+
+    def forced_decode(self, encoded_x: torch.Tensor, y: torch.Tensor, targets: torch.Tensor = None, return_logits: bool = True, *,
+                      return_attention: bool = False, memory_lengths=None):
+        """Teacher-forced decoding of up to 64 target tokens from the (S, B, d) decoder memory (inference): y (B, sy) int64 input tokens on
+        the GPU, 1 <= sy <= 64, or (B, K, sy) for K <= 8 sequences per clip on the clip's one memory (the K candidates of the LTA
+        evaluation, the hypotheses beam_decode returns). Returns logits (sy, B, |V|), for a 3-D y (sy, B, K, |V|): row t is what decode()
+        of y[..., :t + 1] gives in its last row, so forced_decode(memory, target[:, :-1]) is the reference's model(video, target[:, :-1],
+        task) of a validation step (HOI/tasks/multitask/video_task.py:601-617) before its permute. With `targets` (the shape of y) also
+        logprob, shaped like y: log_softmax(logits)[target] per position, exactly 0.0 where the target lies outside the vocabulary (padding
+        such as -100), so -logprob.sum() / count is the cross entropy and logprob.sum(-1) a sequence's score. return_logits=False returns
+        logprob alone and needs targets. One egx_decoder_forced call (last_decoder_impl() == "forced": the K/V-cached step of
+        greedy_decode with the next row taken from y; fed greedy_decode's tokens it returns greedy_decode's logits bit for bit); the
+        steps run one after the other, so this is for validation and scoring, not for training. Eval mode only; shapes and dtypes are
+        validated on the host first, token values are never read there; outside the limits a ValueError that names them."""
+        self._egx_check_inference("it to forced_decode", subject="teacher-forced decoding of up to 64 tokens is")
+        if return_attention or memory_lengths is not None:
+            raise ValueError("forced_decode serves neither return_attention nor memory_lengths: decode() returns attention weights and "
+                             "takes ragged memories for at most 8 target tokens")
+        if not isinstance(encoded_x, torch.Tensor) or encoded_x.dim() != 3:
+            raise ValueError("encoded_x must be the (S, B, d) decoder memory")
+        S, B, d = encoded_x.shape
+        if not isinstance(y, torch.Tensor) or y.dim() not in (2, 3) or y.shape[0] != B:
+            raise ValueError(f"y must be a ({B}, sy) or ({B}, K, sy) tensor of input tokens, one row (or K rows) per clip of the memory: got "
+                             f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y).__name__}")
+        if y.dtype != torch.int64:
+            raise ValueError(f"y must be int64 tokens, got {y.dtype}")
+        K, sy = (y.shape[1] if y.dim() == 3 else 1), y.shape[-1]
+        if not 1 <= K <= 8:
+            raise ValueError(f"K = {K} sequences per clip: forced_decode serves 1..8")
+        if not 1 <= sy <= 64:
+            raise ValueError(f"sy = {sy} target tokens: forced_decode serves 1..64")
+        if targets is not None:
+            if not isinstance(targets, torch.Tensor) or targets.shape != y.shape:
+                raise ValueError(f"targets must have the shape of y {tuple(y.shape)}, got "
+                                 f"{tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+            if targets.dtype != torch.int64:
+                raise ValueError(f"targets must be int64 tokens, got {targets.dtype}")
+        elif not return_logits:
+            raise ValueError("return_logits=False needs targets: without them nothing is left to return")
+        embedding, decoder, pos_embed = self.embedding, self.transformer_decoder, self.pos_embed
+        V = embedding.weight.shape[0]
+        if sy > pos_embed.pe.shape[0]:
+            raise ValueError(f"sy = {sy} exceeds the {pos_embed.pe.shape[0]} rows of the positional table")
+        if d != embedding.weight.shape[1]:
+            raise ValueError(f"memory width {d} != embedding width {embedding.weight.shape[1]}")
+        if not (encoded_x.is_cuda and y.is_cuda and embedding.weight.is_cuda and (targets is None or targets.is_cuda)):
+            raise ValueError("teacher-forced decoding runs on the GPU only (no CPU fallback): memory, tokens, targets and the model must be "
+                             "on the GPU")
+        compute, d_ff = getattr(self, "egx_compute", "f32"), decoder.layers[0].linear1.out_features
+        post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
+        if not (post_ln and F_egx.decoder_forced_supported(compute, d, self.n_heads, d_ff, S, len(decoder.layers), V, sy, K)):
+            raise ValueError(f"teacher-forced decoding is outside egx_decoder_forced's limits (compute bf16, post-LN layers, d_model a multiple "
+                             f"of 128 in [256, 1024], head dim 32 or 64, d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= "
+                             f"1024, sy <= 64, K <= 8): got compute {compute}, d = {d}, {self.n_heads} heads, d_ff = {d_ff}, S = {S}, "
+                             f"{len(decoder.layers)} layers, vocabulary {V}, sy = {sy}, K = {K}")
+        y3, t3 = y.reshape(B, K, sy), (targets.reshape(B, K, sy) if targets is not None else None)
+        logits, logprob = self._egx_forced(encoded_x, y3, t3, bool(return_logits), embedding, pos_embed, decoder, self.fc, self.n_heads)
+        if logprob is not None:
+            logprob = logprob.view(y.shape)
+        if not return_logits:
+            return logprob
+        logits = logits.view((sy, B, K, V) if y.dim() == 3 else (sy, B, V))
+        return (logits, logprob) if targets is not None else logits
 
     def beam_decode(self, encoded_x: torch.Tensor, start_token, n_steps: int, beam_width: int, return_scores: bool = False,
                     return_trace: bool = False, schedule=None):

@@ -1151,8 +1151,9 @@ _last_dec_impl = ["none"]
 def last_decoder_impl() -> str:
     """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
     operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd), "grouped" (a ragged memory decoded one length group at a
-    time), "generate" (greedy generation in one egx_decoder_generate call), "loop" (greedy generation as a prefix loop over decode()) or
-    "beam" (beam search in one egx_decoder_beam call)."""
+    time), "generate" (greedy generation in one egx_decoder_generate call), "loop" (greedy generation as a prefix loop over decode()),
+    "beam" (beam search in one egx_decoder_beam call) or "forced" (teacher-forced decoding of up to 64 target tokens in one
+    egx_decoder_forced call)."""
     return _last_dec_impl[0]
 
 
@@ -1861,6 +1862,47 @@ def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tenso
             check(lib.egx_decoder_beam_sched(*args, *schedule._args()))
     _last_dec_impl[0] = "beam"
     return tokens, scores, trace
+
+
+def decoder_forced_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int,
+                             rows_per_clip: int = 1) -> bool:
+    """Configurations egx_decoder_forced serves (include/egot2x.h): egx_decoder_generate's limits, 1 <= rows_per_clip <= 8."""
+    return decoder_generate_supported(compute, d, n_heads, d_ff, S, n_layers, vocab, n_steps) and 1 <= rows_per_clip <= 8
+
+
+def decoder_forced(meta, tokens, targets, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, return_logits: bool = True):
+    """Teacher-forced decoding in ONE asynchronous call (egx_decoder_forced; no autograd): tokens (B, R, n_steps) int64 input tokens, R
+    sequences per clip; targets the same shape or None; mem2d (B * S, d) batch-first memory rows (one memory per CLIP), pe (>= n_steps, d)
+    positional rows, meta as DecoderFn's (dropout ignored: inference). Returns (logits (n_steps, B * R, |V|) fp32 or None, logprob
+    (B, R, n_steps) fp32 or None): logprob[b, r, t] = log_softmax(logits[t, b * R + r])[targets[b, r, t]], 0.0 where the target is outside
+    the vocabulary. The workspace comes from the caching allocator: the call can be captured."""
+    lib = _lib.load()
+    with torch.no_grad():
+        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
+        if tokens.dtype != torch.int64 or not tokens.is_cuda or tokens.dim() != 3:
+            raise _lib.EgxError("decoder_forced: tokens must be a (B, R, n_steps) int64 tensor on the GPU")
+        if targets is not None and (targets.dtype != torch.int64 or not targets.is_cuda or targets.shape != tokens.shape):
+            raise _lib.EgxError(f"decoder_forced: targets must be an int64 tensor on the GPU of the tokens' shape {tuple(tokens.shape)}")
+        if targets is None and not return_logits:
+            raise _lib.EgxError("decoder_forced: return_logits=False without targets leaves nothing to compute")
+        tokens = tokens.contiguous()
+        targets = targets.contiguous() if targets is not None else None
+        (B, R, n_steps), (V, d) = tokens.shape, emb.shape
+        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
+            raise _lib.EgxError(f"decoder_forced: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
+                                f"d = {d}, n_steps = {n_steps}")
+        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
+        layers = _dec_layers(layer_t, meta["n_layers"])
+        nb = C.c_size_t(0)
+        check(lib.egx_decoder_forced_workspace(C.byref(cfg), B, R, n_steps, C.byref(nb)))
+        dev = mem2d.device
+        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=dev)
+        logits = torch.empty((n_steps, B * R, V), dtype=torch.float32, device=dev) if return_logits else None
+        logprob = torch.empty((B, R, n_steps), dtype=torch.float32, device=dev) if targets is not None else None
+        check(lib.egx_decoder_forced(C.byref(cfg), ptr(tokens), ptr(targets), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w),
+                                     ptr(fc_b), B, R, n_steps, ptr(logits), ptr(logprob), ptr(ws), _stream()))
+    _last_dec_impl[0] = "forced"
+    return logits, logprob
 
 
 def weighted_cross_entropy(logits, target, weight=None):

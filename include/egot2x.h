@@ -710,6 +710,34 @@ int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, c
                               int64_t* tokens_out, float* logits_out /* may be NULL */, void* workspace, void* stream, int period,
                               const int* counts /* HOST int[period] */, const int32_t* words /* DEVICE int32[period][vocab] */,
                               float* attn_out /* (n_layers, n_steps, B, S) */);
+/* ---- ABI v18 (additions): teacher-forced decoding of up to 64 target tokens on the K/V-cached step ----
+ * The reference runs its sequence decoders over given target tokens longer than the 8 rows egx_decoder_fwd serves: the validation step
+ * model(video, target[:, :-1], 'lta_verb') over the 21 tokens [lta_verb, 20 verbs] (HOI/tasks/multitask/video_task.py:601-617,
+ * HOI/tasks/multitask/video_task_action.py:83-88: val_loss_lta_verb / val_loss_lta_noun) and the 40-token teacher-forced call of
+ * HOI/models/lta/lta_models_seqdecoder.py:175-179. Row t of a causal decoder without dropout sees rows 0 .. t only, so the call is
+ * egx_decoder_generate's step with step t's input row taken from `tokens` instead of the argmax: x_t = emb[tokens[.., t]] * sqrt(d) + pe[t]
+ * through the layers (self-attention over the per-layer K/V cache of rows 0 .. t, cross-attention onto the clip's memory), launches and
+ * arithmetic as egx_decoder_generate, choice for choice: fed the tokens greedy generation chose, it returns that call's logits bit for bit.
+ * Sequential over the steps (inference: validation loss, scoring of candidate sequences); nothing runs backward.
+ * R target sequences per clip, 1 <= R <= 8: tokens / targets / logprob_out are (B, R, n_steps), row b * R + r = sequence r of clip b; the
+ * R rows of a clip share the clip's memory (B * S rows, converted and projected once per clip; the cross-attention runs with Sq = R, as
+ * egx_decoder_beam's W slots do). All B * R * n_steps input rows are embedded in one launch; a token outside [0, vocab) embeds as the
+ * zero row (as egx_decoder_fwd's do). Each step's last-layer rows go into an (n_steps, B * R, d) slab and ONE launch of the fp32
+ * vocabulary head after the last step writes logits_out (n_steps, B * R, vocab) when given and, with targets,
+ *   logprob_out[b][r][t] = logit[target] - max - log(sum_v exp(logit[v] - max))   (fp32; the sum in a fixed order)
+ * the log-probability of targets[b][r][t] under step t's logits; a target outside [0, vocab) (padding such as -100) gives exactly 0.0, a
+ * NaN logit propagates. A row's logits have the bits egx_decoder_generate's head computes for the same row. Limits: egx_decoder_generate's
+ * (compute EGX_BF16, the fused decoder's d_model, heads, d_ff, layers and S, 1 <= n_steps <= 64, 1 <= vocab <= 1024, p_drop = p_pos = 0);
+ * cfg->sy is not read. Refused before any device work, by the call and (where it applies) the workspace query: R outside 1 .. 8, both
+ * outputs null, logprob_out without targets, null pointers, a pe_stride below d_model or not a multiple of 4, B * R or B * S too large.
+ * No float atomics, no value read on the host: the call can be captured in a hipGraph and replayed on new tokens, targets and memory; the
+ * memory's K | V projections use the side stream as egx_decoder_generate's do. */
+int egx_decoder_forced_workspace(const egx_dec_config* cfg, int B, int R, int n_steps, size_t* bytes);
+int egx_decoder_forced(const egx_dec_config* cfg, const int64_t* tokens /* DEVICE (B, R, n_steps): the input tokens */,
+                       const int64_t* targets /* DEVICE (B, R, n_steps) or NULL */, const float* memory, const float* emb, const float* pe,
+                       int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int R, int n_steps,
+                       float* logits_out /* (n_steps, B * R, vocab) fp32 or NULL */, float* logprob_out /* (B, R, n_steps) fp32 or NULL; needs targets */,
+                       void* workspace, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). Wherever y is not > 0 (y = NaN, -0 and
  * -inf included) dy becomes +0; a denormal y > 0 keeps its dy. n = 0 touches nothing. */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
