@@ -13,6 +13,7 @@
 // stays on the composed path (egot2_amd/decoder.py).
 #include <string.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/egot2x.h"
@@ -1643,6 +1644,9 @@ int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, con
 // fp32 vocabulary head, the argmax and the next token's embedding on the device. Arithmetic as decoder_fwd_run, choice for choice.
 namespace {
 
+constexpr int GEN_MAX_STEPS = 64, BEAM_MAX_W = DA_MAXQ, BEAM_DEPTH = GEN_MAX_STEPS;
+
+// rows that each read their own history (greedy, forced): row b's history is cache rows (b, 0 .. t - 1)
 struct GenAttnParams {
     const void* qkv;        // (B, 3d): the new row's q | k | v (fp32 or bf16)
     void* cache;            // (B, n_steps, 2d): k | v of rows 0 .. t - 1; row t is appended
@@ -1650,25 +1654,57 @@ struct GenAttnParams {
     int B, H, d, t, n_steps;
     float scale;
 };
+// beam search: hypothesis slot w of clip b (row b * W + w) reads its history through an ancestry table instead of a gathered cache
+struct BeamAttnParams {
+    const void* qkv;        // (B * W, 3d): the new rows' q | k | v (fp32 or bf16)
+    void* cache;            // (B, W, n_steps, 2d): row (b, s, j) = k | v of the row slot s of clip b ran at step j; written once
+    const int* anc;         // (B, W, BEAM_DEPTH): anc[b][w][j], j < t = the slot that ran row j of hypothesis w's history
+    bf16_t* o;              // (B * W, d)
+    int B, W, H, d, t, n_steps;
+    float scale;
+};
+template <bool ANC>
+using CachedAttnParams = std::conditional_t<ANC, BeamAttnParams, GenAttnParams>;
 
-// One wave per (clip, head), four per workgroup. Lane j holds key row j (j < t from the cache, j == t the new row); the query goes through a
-// per-wave LDS slice as broadcast reads; lane c accumulates column c of the output. Sums run in dec_attn_kernel's order, so a step sees the
-// scores and the output a causal decode() of the same rows computes. t < 64 = one key per lane.
-template <int DH, bool F32>
-__global__ __launch_bounds__(256) void gen_self_attn_kernel(GenAttnParams p) {
+// One wave per (row, head), four per workgroup. Lane j holds key row j (j < t from the cache, j == t the new row, which lanes c < DH also
+// append to the cache); the query goes through a per-wave LDS slice as broadcast reads; lane c accumulates column c of the output. Sums run
+// in dec_attn_kernel's order, so a step sees the scores and the output a causal decode() of the same rows computes. t < 64 = one key per
+// lane. ANC: history row j of row (b, w) is cache row (b, anc[b][w][j], j) instead of (row, j); same lane roles and summation order, so
+// with W = 1 (every slot 0) the same bits. (The two forms of every cache address are kept apart as written: each instance's instruction
+// stream is the one of the kernel it had to itself.)
+template <int DH, bool F32, bool ANC>
+__global__ __launch_bounds__(256) void cached_self_attn_kernel(CachedAttnParams<ANC> p) {
     __shared__ __align__(16) float sQ[4][DH];   // (read as float4)
     __shared__ float sP[4][64];
+    __shared__ int sS[ANC ? 4 : 1][64];         // ANC: slot of history row j
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bh = blockIdx.x * 4 + wave;
-    if (bh >= p.B * p.H) return;                // (no barrier below: every wave works alone)
-    const int b = bh / p.H, h = bh % p.H, t = p.t, d = p.d;
-    const size_t nrow = (size_t)b * 3 * d + h * DH;                         // q; k at + d, v at + 2d
-    const size_t crow = (size_t)b * p.n_steps * 2 * d + h * DH;             // cache row j at + j * 2d: k; v at + d
+    const int rh = blockIdx.x * 4 + wave;
+    int W = 1;
+    if constexpr (ANC) W = p.W;
+    if (rh >= p.B * W * p.H) return;            // (no barrier below: every wave works alone)
+    const int r = rh / p.H, h = rh % p.H, t = p.t, d = p.d, b = r / W;
+    const size_t nrow = (size_t)r * 3 * d + h * DH;                         // q; k at + d, v at + 2d
+    // cache row (b, s, j) at ((b * W + s) * n_steps + j) * 2d + ccol: k; v at + d. Without ancestry s = w: row r's rows follow crow
+    size_t ccol = 0, cnew = 0, crow = 0;
+    if constexpr (ANC) {
+        ccol = (size_t)h * DH;
+        cnew = ((size_t)r * p.n_steps + t) * 2 * d + ccol;
+    } else {
+        crow = (size_t)r * p.n_steps * 2 * d + h * DH;
+    }
+    const bool cached = lane < t;
+    int slot = 0;
+    if constexpr (ANC) {
+        slot = cached ? p.anc[(size_t)r * BEAM_DEPTH + lane] : 0;
+        slot = slot < 0 ? 0 : (slot >= p.W ? p.W - 1 : slot);               // (the head writes 0 .. W - 1)
+        sS[wave][lane] = slot;
+    }
     float kr[DH];
     {
-        const bool cached = lane < t;
         const void* kb = cached ? (const void*)p.cache : p.qkv;
-        const size_t krow = cached ? crow + (size_t)lane * 2 * d : nrow + d;
+        size_t krow;
+        if constexpr (ANC) krow = cached ? (((size_t)b * p.W + slot) * p.n_steps + lane) * 2 * d + ccol : nrow + d;
+        else krow = cached ? crow + (size_t)lane * 2 * d : nrow + d;
 #pragma unroll
         for (int c = 0; c < DH; c += 8) {
             float t8[8];
@@ -1681,8 +1717,13 @@ __global__ __launch_bounds__(256) void gen_self_attn_kernel(GenAttnParams p) {
     if (lane < DH) {                            // append row t (read by later steps only)
         const float knew = load1<F32>(p.qkv, nrow + d + lane);
         vnew = load1<F32>(p.qkv, nrow + 2 * d + lane);
-        store1<F32>(p.cache, crow + (size_t)t * 2 * d + lane, knew);
-        store1<F32>(p.cache, crow + (size_t)t * 2 * d + d + lane, vnew);
+        if constexpr (ANC) {
+            store1<F32>(p.cache, cnew + lane, knew);
+            store1<F32>(p.cache, cnew + d + lane, vnew);
+        } else {
+            store1<F32>(p.cache, crow + (size_t)t * 2 * d + lane, knew);
+            store1<F32>(p.cache, crow + (size_t)t * 2 * d + d + lane, vnew);
+        }
         sQ[wave][lane] = load1<F32>(p.qkv, nrow + lane);
     }
     __builtin_amdgcn_wave_barrier();
@@ -1702,22 +1743,34 @@ __global__ __launch_bounds__(256) void gen_self_attn_kernel(GenAttnParams p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane < DH) {
         float acc = 0.f;
-        const size_t v0 = crow + d + lane;
-        for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + (size_t)j * 2 * d);
+        if constexpr (ANC) {
+            const size_t v0 = (size_t)b * p.W * p.n_steps * 2 * d + ccol + d + lane;
+            for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + ((size_t)sS[wave][j] * p.n_steps + j) * 2 * d);
+        } else {
+            const size_t v0 = crow + d + lane;
+            for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + (size_t)j * 2 * d);
+        }
         acc += sP[wave][t] * vnew;
-        p.o[(size_t)b * d + h * DH + lane] = f2bf(acc);
+        p.o[(size_t)r * d + h * DH + lane] = f2bf(acc);
     }
 }
 
-int gen_self_attn(GenAttnParams p, int dh, bool f32, hipStream_t st) {
-    EGX_CHECK(p.t >= 0 && p.t < p.n_steps && p.n_steps <= 64, "cached self-attention: step %d of %d (at most 64)", p.t, p.n_steps);
+template <bool ANC>
+int cached_self_attn(CachedAttnParams<ANC> p, int dh, bool f32, hipStream_t st) {
+    const char* who = ANC ? "beam self-attention" : "cached self-attention";
+    EGX_CHECK(p.t >= 0 && p.t < p.n_steps && p.n_steps <= GEN_MAX_STEPS, "%s: step %d of %d (at most %d)", who, p.t, p.n_steps, GEN_MAX_STEPS);
+    int W = 1;
+    if constexpr (ANC) {
+        EGX_CHECK(p.W >= 1 && p.W <= BEAM_MAX_W, "%s: W = %d (1..%d)", who, p.W, BEAM_MAX_W);
+        W = p.W;
+    }
     p.scale = 1.f / sqrtf((float)dh);
-    const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
-    if (dh == 64 && !f32) hipLaunchKernelGGL((gen_self_attn_kernel<64, false>), grid, block, 0, st, p);
-    else if (dh == 32 && !f32) hipLaunchKernelGGL((gen_self_attn_kernel<32, false>), grid, block, 0, st, p);
-    else if (dh == 64) hipLaunchKernelGGL((gen_self_attn_kernel<64, true>), grid, block, 0, st, p);
-    else if (dh == 32) hipLaunchKernelGGL((gen_self_attn_kernel<32, true>), grid, block, 0, st, p);
-    else EGX_CHECK(false, "cached self-attention: head dim %d (32 or 64)", dh);
+    const dim3 grid(cdiv(p.B * W * p.H, 4)), block(256);
+    if (dh == 64 && !f32) hipLaunchKernelGGL((cached_self_attn_kernel<64, false, ANC>), grid, block, 0, st, p);
+    else if (dh == 32 && !f32) hipLaunchKernelGGL((cached_self_attn_kernel<32, false, ANC>), grid, block, 0, st, p);
+    else if (dh == 64) hipLaunchKernelGGL((cached_self_attn_kernel<64, true, ANC>), grid, block, 0, st, p);
+    else if (dh == 32) hipLaunchKernelGGL((cached_self_attn_kernel<32, true, ANC>), grid, block, 0, st, p);
+    else EGX_CHECK(false, "%s: head dim %d (32 or 64)", who, dh);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -1727,7 +1780,7 @@ int gen_self_attn(GenAttnParams p, int dh, bool f32, hipStream_t st) {
 // the logits to logits_out when given, and the next step's input row emb[tok] * scale + pe_next as fp32 and bf16 (dec_embed_kernel's
 // expression). pe_next null: the last step. With a word list (words, n_words) the head computes the listed rows only and every other logit
 // is -inf: the argmax runs over the set.
-constexpr int GH_CLIPS = 4, GH_WAVES = 8, GH_ROWS = 4, GEN_MAX_STEPS = 64, GEN_MAX_VOCAB = 1024;
+constexpr int GH_CLIPS = 4, GH_WAVES = 8, GH_ROWS = 4, GEN_MAX_VOCAB = 1024;
 struct GenHeadParams {
     const float* x; const float* fc_w; const float* fc_b; const float* emb; const float* pe_next;
     int64_t* tok; int tok_stride;               // clip b's token of this step at tok[b * tok_stride]
@@ -1866,30 +1919,48 @@ int check_sched(const char* who, int period, const int* counts, const int32_t* w
     return 0;
 }
 
-struct GPlan {
-    int B, n, S, d, H, dff, L, V;
-    size_t Nm;
+// The plan of one cached-step call (greedy, beam search, teacher-forced): egx_decoder_generate's layout over M = B * rows target rows per
+// step (rows per clip: 1, W or R; the memory and its K | V stay B * S rows). Every per-row buffer except greedy's LN statistics takes a
+// multiple of 256 bytes per row, so the beam and forced workspaces are exactly linear in M and in n_steps (the caches and the slabs only).
+struct StepPlan {
+    int B, rows, n, S, d, H, dff, L, V;
+    size_t M, Nm;
     size_t zero, mem16, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
+    size_t xin32, score, anc[2], hist[2];       // a call's own buffers, taken behind the shared layout (beam_plan, forced_plan)
     GLayer layer[16];
-    size_t bytes;
+    size_t bytes;                               // the running total: dtake(pl.bytes, ...) appends
 };
 
-int make_gplan(const egx_dec_config* c, int B, int n_steps, GPlan& pl) {
+// The checks every cached-step entry point and workspace query opens with, under its own name; the call's own range checks follow.
+int step_checks(const char* who, const egx_dec_config* c, int n_steps) {
     EGX_CHECK(c, "null decoder config");
-    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_generate: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
-    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_generate: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
-    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_generate: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
-    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits (cfg->sy is not read)
+    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "%s: inference only: p_drop and p_pos must be 0 (got %g, %g)", who, c->p_drop, c->p_pos);
+    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "%s: n_steps = %d (1..%d)", who, n_steps, GEN_MAX_STEPS);
+    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "%s: vocab = %d (1..%d)", who, c->vocab, GEN_MAX_VOCAB);
+    return 0;
+}
+
+// (beam and forced) B * rows target rows and B * S memory rows within the kernels' int indices; `letter` names the rows per clip
+int step_rows_fit(const char* who, char letter, const egx_dec_config* c, int B, int rows) {
+    EGX_CHECK((size_t)B * rows <= (size_t)0x7fffffff / (size_t)(3 * c->d_model) && (size_t)B * c->S <= (size_t)0x7fffffff / (size_t)(2 * c->d_model),
+              "%s: B = %d with %c = %d, S = %d is too large", who, B, letter, rows, c->S);
+    return 0;
+}
+
+// d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits with `rows` target rows per clip (cfg->sy is not read), then the layout.
+// st_row: bytes of LN statistics per row (greedy 8, else 256); xL_steps: the steps whose last-layer rows are kept (1: a head per step).
+int step_layout(const egx_dec_config* c, int B, int rows, int n_steps, size_t st_row, int xL_steps, StepPlan& pl) {
+    {
         egx_dec_config one = *c;
-        one.sy = 1;
+        one.sy = rows;
         DPlan dp;
         if (make_dplan(&one, B, dp)) return 1;
     }
     memset(&pl, 0, sizeof(pl));
-    pl.B = B; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
-    pl.Nm = (size_t)B * c->S;
-    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = (size_t)B;
-    size_t cur = 0;
+    pl.B = B; pl.rows = rows; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
+    pl.M = (size_t)B * rows; pl.Nm = (size_t)B * c->S;
+    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
+    size_t& cur = pl.bytes;
     pl.zero = dtake(cur, 1024);
     pl.mem16 = dtake(cur, Nm * d * 2);
     for (int l = 0; l < pl.L; ++l) {
@@ -1902,37 +1973,47 @@ int make_gplan(const egx_dec_config* c, int B, int n_steps, GPlan& pl) {
     }
     pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
     pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
-    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 8);
+    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * st_row);
     pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
     pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
-    pl.xL32 = dtake(cur, M * d * 4);
-    pl.bytes = cur;
+    pl.xL32 = dtake(cur, M * xL_steps * d * 4);
     return 0;
 }
 
-// The one body of egx_decoder_generate (period = 0), egx_decoder_generate_sched and egx_decoder_generate_attn: step t's head takes row
-// t % period of the schedule; with attn_out (L, n_steps, B, S) every layer's cross-attention of a step is followed by one
-// dec_cross_weights_kernel launch on the same q and k (attn_out null: the launches of the calls without it, nothing else).
-int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
-                 const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
-                 float* logits_out, void* workspace, void* stream, int period, const int* counts, const int32_t* words, float* attn_out) {
-    GPlan pl;
-    if (make_gplan(cfg, B, n_steps, pl)) return 1;
-    if (check_sched("egx_decoder_generate_sched", period, counts, words, pl.V, 0)) return 1;
-    EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && workspace, "egx_decoder_generate: null pointer argument");
-    EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_generate: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
-    hipStream_t st = (hipStream_t)stream;
-    void* ws = workspace;
-    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, dh = d / pl.H;
-    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
-    const void* zero = at<char>(ws, pl.zero);
-    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
-    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
-    {   // every weight -> bf16 once (no transposed copies: nothing runs backward), one launch
+// One cached-step call in flight, what the three decoders share: begin(), the caller's input kernel, fork_kv(), then layers() per step and
+// joined() behind the last one. The caller keeps its input kernel, its loop over t and its head. From fork_kv() on, `sj` joins the side
+// stream on every error return.
+struct StepRun {
+    const egx_dec_config* cfg; const StepPlan& pl; const egx_dec_layer* lw; void* ws; hipStream_t st;
+    SideStream& SS; SideJoin sj; bool side = false;
+    StepRun(const egx_dec_config* c, const StepPlan& p, const egx_dec_layer* layers, void* workspace, hipStream_t s)
+        : cfg(c), pl(p), lw(layers), ws(workspace), st(s), SS(side_stream()), sj(SS, s) {}
+
+    int nt_on(hipStream_t s_, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
+              const float* residual) {
+        WideGemmParams g;
+        g.A = A; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
+        g.residual = residual; g.ldr = N; g.zero_page = at<char>(ws, pl.zero);
+        return wide_gemm_nt(g, s_);
+    }
+    int nt(const bf16_t* A, int lda, const bf16_t* W, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu, const float* residual) {
+        return nt_on(st, A, lda, W, (int)pl.M, N, K, bias, Cf, Cb, relu, residual);
+    }
+    int ln(const float* x, const float* w, const float* b, float* y32, bf16_t* y16) {
+        WideLnFwdParams lp;
+        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = (int)pl.M; lp.d = pl.d;
+        return wide_ln_fwd(lp, st);
+    }
+
+    // the zero page, the memory -> bf16, every weight -> bf16 once (no transposed copies: nothing runs backward), one launch
+    int begin(const float* memory) {
+        const int d = pl.d, dff = pl.dff;
+        EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
+        if (wide_cast(memory, (int)pl.Nm, d, d, at<bf16_t>(ws, pl.mem16), nullptr, st)) return 1;
         WideCastBatch cb;
         for (int l = 0; l < pl.L; ++l) {
             const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
+            const egx_dec_layer& w = lw[l];
             if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
             if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
             if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
@@ -1941,63 +2022,49 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
             if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
             if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
         }
-        if (wide_cast_flush(cb, st)) return 1;
+        return wide_cast_flush(cb, st);
     }
-    // step 0's input rows: emb[start] * sqrt(d) + pe[0]
-    hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)(((size_t)B * (d / 4) + 255) / 256)), dim3(256), 0, st, start, emb, pe, pe_stride,
-                       sqrtf((float)d), at<float>(ws, pl.x32), at<bf16_t>(ws, pl.x16), B, 1, d, pl.V, (uint64_t)0, (uint32_t)0, 1.f);
-    EGX_LAUNCH_CHECK();
-    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                     const float* residual) -> int {
-        WideGemmParams g;
-        g.A = A; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
-        g.residual = residual; g.ldr = N; g.zero_page = zero;
-        return wide_gemm_nt(g, s_);
-    };
-    auto nt = [&](const bf16_t* A, int lda, const bf16_t* W, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                  const float* residual) -> int { return nt_on(st, A, lda, W, B, N, K, bias, Cf, Cb, relu, residual); };
-    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
-        WideLnFwdParams lp;
-        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = B; lp.d = d;
-        return wide_ln_fwd(lp, st);
-    };
-    // the memory's K | V, once per layer: on the side stream beside step 0 (eager), on the caller's stream under capture
-    SideStream& SS = side_stream();
-    SideJoin sj(SS, st);
-    const bool side = side_wanted(SS, st);
-    if (side) {
-        if (SS.order(st, SS.s)) return 1;
-        sj.forked = true;
-    }
-    for (int l = 0; l < pl.L; ++l) {
-        const GLayer& o = pl.layer[l];
-        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
-        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
-    }
-    float* x32 = at<float>(ws, pl.x32);
-    bf16_t* x16 = at<bf16_t>(ws, pl.x16);
-    for (int t = 0; t < n_steps; ++t) {
+
+    // the memory's K | V, once per layer and per CLIP (B * S rows): on the side stream beside step 0 (eager), on the caller's stream under capture
+    int fork_kv() {
+        const int d = pl.d;
+        side = side_wanted(SS, st);
+        if (side) {
+            if (SS.order(st, SS.s)) return 1;
+            sj.forked = true;
+        }
         for (int l = 0; l < pl.L; ++l) {
             const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
+            if (nt_on(side ? SS.s : st, cat<bf16_t>(ws, pl.mem16), d, cat<bf16_t>(ws, o.w_kv), (int)pl.Nm, 2 * d, d, lw[l].ca_in_b + d, nullptr,
+                      at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
+            if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
+        }
+        return 0;
+    }
+
+    // Step t's M new rows through the layers. xin: layer 0's fp32 input rows (and the residual of its out-projection); xL: where the last
+    // layer's LN3 writes; self_attn(qkv, cache, o, f32, t, st): the call's cached self-attention of one layer; attn_out, when given,
+    // (L, n_steps, B, S): every layer's cross-attention is followed by one dec_cross_weights_kernel launch on the same q and k.
+    template <class SelfAttn>
+    int layers(int t, const float* xin, float* xL, SelfAttn&& self_attn, float* attn_out) {
+        const int d = pl.d, dff = pl.dff, dh = d / pl.H;
+        for (int l = 0; l < pl.L; ++l) {
+            const GLayer& o = pl.layer[l];
+            const egx_dec_layer& w = lw[l];
             const bool last = l + 1 == pl.L;
             const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
+            const float* x32 = f32_self ? xin : cat<float>(ws, pl.x32);
             if (f32_self) {
                 GemmParams g;
-                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = B; g.N = 3 * d; g.K = d;
+                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = (int)pl.M; g.N = 3 * d; g.K = d;
                 g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
                 if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
-            } else if (nt(x16, d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
-            {
-                GenAttnParams a;
-                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
-                a.cache = at<char>(ws, o.cache); a.o = at<bf16_t>(ws, pl.sa);
-                a.B = B; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
-                if (gen_self_attn(a, dh, f32_self, st)) return 1;
-            }
+            } else if (nt(cat<bf16_t>(ws, pl.x16), d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
+            if (self_attn(f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16), at<char>(ws, o.cache),
+                          at<bf16_t>(ws, pl.sa), f32_self, t, st)) return 1;
             if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
             if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
-            // cross-attention of the one new row onto the clip's S memory rows
+            // cross-attention of the clip's new rows onto its S memory rows: dec_attn with Sq = the rows per clip
             if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
             if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
             {
@@ -2005,13 +2072,13 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
                 memset(&a, 0, sizeof(a));
                 const bf16_t* kv = cat<bf16_t>(ws, o.kv);
                 a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
-                a.B = B; a.H = pl.H; a.Sq = 1; a.Sk = pl.S; a.causal = 0;
+                a.B = pl.B; a.H = pl.H; a.Sq = pl.rows; a.Sk = pl.S; a.causal = 0;
                 if (dec_attn<false>(a, dh, false, st)) return 1;
-                if (attn_out) {     // (egx_decoder_generate_attn) this step's head-averaged weights of the layer: attn_out[l][t] (B, S)
+                if (attn_out) {     // (egx_decoder_generate_attn, one row per clip) this step's head-averaged weights of the layer: attn_out[l][t] (B, S)
                     CrossWParams cw;
                     memset(&cw, 0, sizeof(cw));
-                    cw.q = a.q; cw.ldq = d; cw.k = kv; cw.ldk = 2 * d; cw.out = attn_out + ((size_t)l * n_steps + t) * B * pl.S; cw.ldo = pl.S;
-                    cw.B = B; cw.H = pl.H; cw.Sq = 1; cw.Sk = pl.S;
+                    cw.q = a.q; cw.ldq = d; cw.k = kv; cw.ldk = 2 * d; cw.out = attn_out + ((size_t)l * pl.n + t) * pl.B * pl.S; cw.ldo = pl.S;
+                    cw.B = pl.B; cw.H = pl.H; cw.Sq = 1; cw.Sk = pl.S;
                     if (cross_weights(cw, dh, false, st)) return 1;
                 }
             }
@@ -2020,8 +2087,55 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
             // FFN
             if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
             if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? at<float>(ws, pl.xL32) : x32, last ? nullptr : x16)) return 1;
+            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? xL : at<float>(ws, pl.x32), last ? nullptr : at<bf16_t>(ws, pl.x16))) return 1;
         }
+        return 0;
+    }
+
+    // behind the last step: joined already, every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    void joined() { sj.forked = false; }
+};
+
+// the cached self-attention of rows that each read their own history (greedy, forced): the cached self-attention without ancestry over the M rows
+auto own_history_attn(const StepPlan& pl) {
+    return [&pl](const void* qkv, void* cache, bf16_t* o, bool f32, int t, hipStream_t st) -> int {
+        GenAttnParams a;
+        a.qkv = qkv; a.cache = cache; a.o = o;
+        a.B = (int)pl.M; a.H = pl.H; a.d = pl.d; a.t = t; a.n_steps = pl.n; a.scale = 0.f;
+        return cached_self_attn<false>(a, pl.d / pl.H, f32, st);
+    };
+}
+
+int generate_plan(const egx_dec_config* c, int B, int n_steps, StepPlan& pl) {
+    if (step_checks("egx_decoder_generate", c, n_steps)) return 1;
+    return step_layout(c, B, 1, n_steps, 8, 1, pl);
+}
+
+// The one body of egx_decoder_generate (period = 0), egx_decoder_generate_sched and egx_decoder_generate_attn: step t's head takes row
+// t % period of the schedule; with attn_out (L, n_steps, B, S) every layer's cross-attention of a step is followed by one
+// dec_cross_weights_kernel launch on the same q and k (attn_out null: the launches of the calls without it, nothing else).
+int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* memory, const float* emb, const float* pe, int pe_stride,
+                 const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int64_t* tokens_out,
+                 float* logits_out, void* workspace, void* stream, int period, const int* counts, const int32_t* words, float* attn_out) {
+    StepPlan pl;
+    if (generate_plan(cfg, B, n_steps, pl)) return 1;
+    if (check_sched("egx_decoder_generate_sched", period, counts, words, pl.V, 0)) return 1;
+    EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && workspace, "egx_decoder_generate: null pointer argument");
+    EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_generate: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const int d = pl.d;
+    StepRun run(cfg, pl, layers, ws, st);
+    if (run.begin(memory)) return 1;
+    // step 0's input rows: emb[start] * sqrt(d) + pe[0]
+    float* x32 = at<float>(ws, pl.x32);
+    bf16_t* x16 = at<bf16_t>(ws, pl.x16);
+    hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)(((size_t)B * (d / 4) + 255) / 256)), dim3(256), 0, st, start, emb, pe, pe_stride,
+                       sqrtf((float)d), x32, x16, B, 1, d, pl.V, (uint64_t)0, (uint32_t)0, 1.f);
+    EGX_LAUNCH_CHECK();
+    if (run.fork_kv()) return 1;
+    for (int t = 0; t < n_steps; ++t) {
+        if (run.layers(t, x32, at<float>(ws, pl.xL32), own_history_attn(pl), attn_out)) return 1;
         GenHeadParams hp;
         hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.emb = emb;
         hp.pe_next = t + 1 < n_steps ? pe + (size_t)(t + 1) * pe_stride : nullptr;
@@ -2032,7 +2146,7 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
         hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
         EGX_LAUNCH_CHECK();
     }
-    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    run.joined();
     return 0;
 }
 
@@ -2041,8 +2155,8 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
 extern "C" {
 
 int egx_decoder_generate_workspace(const egx_dec_config* cfg, int B, int n_steps, size_t* bytes) {
-    GPlan pl;
-    if (make_gplan(cfg, B, n_steps, pl)) return 1;
+    StepPlan pl;
+    if (generate_plan(cfg, B, n_steps, pl)) return 1;
     if (bytes) *bytes = pl.bytes;
     return 0;
 }
@@ -2075,97 +2189,11 @@ int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, c
 
 // ---- beam search with a K/V cache (egx_decoder_beam) ----
 // egx_decoder_generate's step over B * W rows (row b * W + w: hypothesis slot w of clip b, decode()'s (B, sy) layout, so every row-wise stage
-// and the cross-attention with Sq = W serve it unchanged) with two new kernels: the cached self-attention reads a hypothesis' history through
-// an ancestry table instead of gathering the cache, and the head ranks the W * V candidates of a clip and writes the next step's rows.
+// and the cross-attention with Sq = W serve it unchanged) with two kernels of its own: the ANC instance of the cached self-attention reads a hypothesis'
+// history through an ancestry table instead of gathering the cache, and the head ranks the W * V candidates of a clip and writes the next step's rows.
 namespace {
 
-constexpr int BEAM_MAX_W = DA_MAXQ, BEAM_DEPTH = GEN_MAX_STEPS, BEAM_LDS_LIMIT = 64 * 1024;
-
-struct BeamAttnParams {
-    const void* qkv;        // (B * W, 3d): the new rows' q | k | v (fp32 or bf16)
-    void* cache;            // (B, W, n_steps, 2d): row (b, s, j) = k | v of the row slot s of clip b ran at step j; written once
-    const int* anc;         // (B, W, BEAM_DEPTH): anc[b][w][j], j < t = the slot that ran row j of hypothesis w's history
-    bf16_t* o;              // (B * W, d)
-    int B, W, H, d, t, n_steps;
-    float scale;
-};
-
-// gen_self_attn_kernel with the ancestry lookup: one wave per (row, head), four per workgroup; lane j < t holds key row j of the
-// hypothesis, read from cache row (b, anc[b][w][j], j), lane t the new row, which lanes c < DH also append as cache row (b, w, t). Same lane
-// roles and summation order: with W = 1 (every slot 0) the same bits.
-template <int DH, bool F32>
-__global__ __launch_bounds__(256) void beam_self_attn_kernel(BeamAttnParams p) {
-    __shared__ __align__(16) float sQ[4][DH];   // (read as float4)
-    __shared__ float sP[4][64];
-    __shared__ int sS[4][64];                   // slot of history row j
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rh = blockIdx.x * 4 + wave;
-    if (rh >= p.B * p.W * p.H) return;          // (no barrier below: every wave works alone)
-    const int r = rh / p.H, h = rh % p.H, t = p.t, d = p.d, b = r / p.W;
-    const size_t nrow = (size_t)r * 3 * d + h * DH;                         // q; k at + d, v at + 2d
-    const size_t ccol = (size_t)h * DH;                                      // cache row (b, s, j) at ((b * W + s) * n_steps + j) * 2d: k; v at + d
-    const size_t cnew = ((size_t)r * p.n_steps + t) * 2 * d + ccol;
-    const bool cached = lane < t;
-    int slot = cached ? p.anc[(size_t)r * BEAM_DEPTH + lane] : 0;
-    slot = slot < 0 ? 0 : (slot >= p.W ? p.W - 1 : slot);                   // (the head writes 0 .. W - 1)
-    sS[wave][lane] = slot;
-    float kr[DH];
-    {
-        const void* kb = cached ? (const void*)p.cache : p.qkv;
-        const size_t krow = cached ? (((size_t)b * p.W + slot) * p.n_steps + lane) * 2 * d + ccol : nrow + d;
-#pragma unroll
-        for (int c = 0; c < DH; c += 8) {
-            float t8[8];
-            load8<F32>(kb, krow + c, t8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
-        }
-    }
-    float vnew = 0.f;
-    if (lane < DH) {                            // append row t (read by later steps only)
-        const float knew = load1<F32>(p.qkv, nrow + d + lane);
-        vnew = load1<F32>(p.qkv, nrow + 2 * d + lane);
-        store1<F32>(p.cache, cnew + lane, knew);
-        store1<F32>(p.cache, cnew + d + lane, vnew);
-        sQ[wave][lane] = load1<F32>(p.qkv, nrow + lane);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const bool live = lane <= t;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < DH; c += 4) {
-        const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][c]);
-        s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
-    }
-    s = live ? s * p.scale : -INFINITY;
-    const float m = wmax64(s);
-    const float e = live ? __expf(s - m) : 0.f;
-    sP[wave][lane] = e / wsum64d(e);
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane < DH) {
-        float acc = 0.f;
-        const size_t v0 = (size_t)b * p.W * p.n_steps * 2 * d + ccol + d + lane;
-        for (int j = 0; j < t; ++j) acc += sP[wave][j] * load1<F32>(p.cache, v0 + ((size_t)sS[wave][j] * p.n_steps + j) * 2 * d);
-        acc += sP[wave][t] * vnew;
-        p.o[(size_t)r * d + h * DH + lane] = f2bf(acc);
-    }
-}
-
-int beam_self_attn(BeamAttnParams p, int dh, bool f32, hipStream_t st) {
-    EGX_CHECK(p.t >= 0 && p.t < p.n_steps && p.n_steps <= BEAM_DEPTH, "beam self-attention: step %d of %d (at most %d)", p.t, p.n_steps, BEAM_DEPTH);
-    EGX_CHECK(p.W >= 1 && p.W <= BEAM_MAX_W, "beam self-attention: W = %d (1..%d)", p.W, BEAM_MAX_W);
-    p.scale = 1.f / sqrtf((float)dh);
-    const dim3 grid(cdiv(p.B * p.W * p.H, 4)), block(256);
-    if (dh == 64 && !f32) hipLaunchKernelGGL((beam_self_attn_kernel<64, false>), grid, block, 0, st, p);
-    else if (dh == 32 && !f32) hipLaunchKernelGGL((beam_self_attn_kernel<32, false>), grid, block, 0, st, p);
-    else if (dh == 64) hipLaunchKernelGGL((beam_self_attn_kernel<64, true>), grid, block, 0, st, p);
-    else if (dh == 32) hipLaunchKernelGGL((beam_self_attn_kernel<32, true>), grid, block, 0, st, p);
-    else EGX_CHECK(false, "beam self-attention: head dim %d (32 or 64)", dh);
-    EGX_LAUNCH_CHECK();
-    return 0;
-}
+constexpr int BEAM_LDS_LIMIT = 64 * 1024;
 
 // step 0's rows: x32 / x16 [b * W + w] = emb[start[b]] * scale + pe[0] (dec_embed_kernel's expression) for every slot, and the scores
 // 0 for slot 0, -inf for the others: only slot 0 is live
@@ -2319,62 +2347,20 @@ int beam_head(const BeamHeadParams& p, hipStream_t st) {
     return 0;
 }
 
-struct BPlan {
-    int B, W, n, S, d, H, dff, L, V;
-    size_t M, Nm;
-    size_t zero, mem16, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
-    size_t score, anc[2], hist[2];
-    GLayer layer[16];
-    size_t bytes;
-};
-
-// The checks of the call and of the workspace query, then egx_decoder_generate's layout over M = B * W target rows (the memory and its
-// K | V stay B * S rows) plus the beam's state. Every per-row buffer takes a multiple of 256 bytes per row, so the workspace is exactly
-// linear in B * W and in n_steps (the caches only).
-int make_bplan(const egx_dec_config* c, int B, int n_steps, int W, BPlan& pl) {
-    EGX_CHECK(c, "null decoder config");
-    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_beam: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
-    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_beam: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
-    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_beam: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
+// The checks of the call and of the workspace query, then the shared layout over M = B * W target rows plus the beam's state.
+int beam_plan(const egx_dec_config* c, int B, int n_steps, int W, StepPlan& pl) {
+    if (step_checks("egx_decoder_beam", c, n_steps)) return 1;
     EGX_CHECK(W >= 1 && W <= BEAM_MAX_W, "egx_decoder_beam: W = %d (1..%d)", W, BEAM_MAX_W);
     EGX_CHECK(W <= c->vocab, "egx_decoder_beam: W = %d exceeds vocab = %d (a step has only vocab distinct continuations of the start token)", W, c->vocab);
-    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits with W target rows per clip (cfg->sy is not read)
-        egx_dec_config one = *c;
-        one.sy = W;
-        DPlan dp;
-        if (make_dplan(&one, B, dp)) return 1;
-    }
+    if (step_layout(c, B, W, n_steps, 256, 1, pl)) return 1;
     EGX_CHECK(beam_head_lds(W, c->d_model, c->vocab) <= (size_t)BEAM_LDS_LIMIT, "egx_decoder_beam: the head needs %zu bytes of LDS (at most %d)",
               beam_head_lds(W, c->d_model, c->vocab), BEAM_LDS_LIMIT);
-    EGX_CHECK((size_t)B * W <= (size_t)0x7fffffff / (size_t)(3 * c->d_model) && (size_t)B * c->S <= (size_t)0x7fffffff / (size_t)(2 * c->d_model),
-              "egx_decoder_beam: B = %d with W = %d, S = %d is too large", B, W, c->S);
-    memset(&pl, 0, sizeof(pl));
-    pl.B = B; pl.W = W; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
-    pl.M = (size_t)B * W; pl.Nm = (size_t)B * c->S;
-    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
-    size_t cur = 0;
-    pl.zero = dtake(cur, 1024);
-    pl.mem16 = dtake(cur, Nm * d * 2);
-    for (int l = 0; l < pl.L; ++l) {
-        GLayer& o = pl.layer[l];
-        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
-        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
-        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
-        o.kv = dtake(cur, Nm * 2 * d * 2);
-        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
-    }
-    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
-    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
-    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 256);
-    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
-    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
-    pl.xL32 = dtake(cur, M * d * 4);
-    pl.score = dtake(cur, M * 256);
+    if (step_rows_fit("egx_decoder_beam", 'W', c, B, W)) return 1;
+    pl.score = dtake(pl.bytes, pl.M * 256);
     for (int u = 0; u < 2; ++u) {
-        pl.anc[u] = dtake(cur, M * BEAM_DEPTH * sizeof(int));
-        pl.hist[u] = dtake(cur, M * BEAM_DEPTH * sizeof(int64_t));
+        pl.anc[u] = dtake(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int));
+        pl.hist[u] = dtake(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int64_t));
     }
-    pl.bytes = cur;
     return 0;
 }
 
@@ -2383,106 +2369,33 @@ int beam_run(const egx_dec_config* cfg, const int64_t* start, const float* memor
              const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int n_steps, int W, int64_t* tokens_out,
              float* scores_out, int64_t* step_tokens, int32_t* step_parents, float* step_scores, float* step_logits, void* workspace,
              void* stream, int period, const int* counts, const int32_t* words) {
-    BPlan pl;
-    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    StepPlan pl;
+    if (beam_plan(cfg, B, n_steps, W, pl)) return 1;
     if (check_sched("egx_decoder_beam_sched", period, counts, words, pl.V, W)) return 1;
     EGX_CHECK(start && memory && emb && pe && layers && fc_w && fc_b && tokens_out && scores_out && workspace, "egx_decoder_beam: null pointer argument");
     EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_beam: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
     hipStream_t st = (hipStream_t)stream;
     void* ws = workspace;
-    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, M = (int)pl.M, dh = d / pl.H;
-    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
-    const void* zero = at<char>(ws, pl.zero);
-    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
-    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
-    {   // every weight -> bf16 once, one launch (as egx_decoder_generate)
-        WideCastBatch cb;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
-            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
-        }
-        if (wide_cast_flush(cb, st)) return 1;
-    }
+    const int d = pl.d, M = (int)pl.M;
+    StepRun run(cfg, pl, layers, ws, st);
+    if (run.begin(memory)) return 1;
     float* x32 = at<float>(ws, pl.x32);
     bf16_t* x16 = at<bf16_t>(ws, pl.x16);
     float* score = at<float>(ws, pl.score);
     hipLaunchKernelGGL(beam_init_kernel, dim3((unsigned)(((size_t)M * (d / 4) + 255) / 256)), dim3(256), 0, st, start, emb, pe, sqrtf((float)d), x32,
                        x16, score, M, W, d, pl.V);
     EGX_LAUNCH_CHECK();
-    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* Wt, int rows, int N, int K, const float* bias, float* Cf, bf16_t* Cb,
-                     int relu, const float* residual) -> int {
-        WideGemmParams g;
-        g.A = A; g.B = Wt; g.M = rows; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
-        g.residual = residual; g.ldr = N; g.zero_page = zero;
-        return wide_gemm_nt(g, s_);
+    if (run.fork_kv()) return 1;
+    // a hypothesis' history is read through the ancestry table the previous step's head wrote
+    auto self_attn = [&](const void* qkv, void* cache, bf16_t* o, bool f32, int t, hipStream_t s_) -> int {
+        BeamAttnParams a;
+        a.qkv = qkv; a.cache = cache; a.anc = cat<int>(ws, pl.anc[t & 1]); a.o = o;
+        a.B = B; a.W = W; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
+        return cached_self_attn<true>(a, d / pl.H, f32, s_);
     };
-    auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                  const float* residual) -> int { return nt_on(st, A, lda, Wt, M, N, K, bias, Cf, Cb, relu, residual); };
-    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
-        WideLnFwdParams lp;
-        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = M; lp.d = d;
-        return wide_ln_fwd(lp, st);
-    };
-    // the memory's K | V, once per layer and per CLIP (B * S rows): on the side stream beside step 0 (eager), on the caller's stream under capture
-    SideStream& SS = side_stream();
-    SideJoin sj(SS, st);
-    const bool side = side_wanted(SS, st);
-    if (side) {
-        if (SS.order(st, SS.s)) return 1;
-        sj.forked = true;
-    }
-    for (int l = 0; l < pl.L; ++l) {
-        const GLayer& o = pl.layer[l];
-        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
-        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
-    }
     for (int t = 0; t < n_steps; ++t) {
         const bool last_step = t + 1 == n_steps;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
-            const bool last = l + 1 == pl.L;
-            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
-            if (f32_self) {
-                GemmParams g;
-                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = M; g.N = 3 * d; g.K = d;
-                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
-                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
-            } else if (nt(x16, d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
-            {
-                BeamAttnParams a;
-                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
-                a.cache = at<char>(ws, o.cache); a.anc = cat<int>(ws, pl.anc[t & 1]); a.o = at<bf16_t>(ws, pl.sa);
-                a.B = B; a.W = W; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
-                if (beam_self_attn(a, dh, f32_self, st)) return 1;
-            }
-            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
-            // cross-attention of the clip's W new rows onto its S memory rows: dec_attn with Sq = W
-            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
-            if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
-            {
-                DecAttnParams a;
-                memset(&a, 0, sizeof(a));
-                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
-                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
-                a.B = B; a.H = pl.H; a.Sq = W; a.Sk = pl.S; a.causal = 0;
-                if (dec_attn<false>(a, dh, false, st)) return 1;
-            }
-            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
-            // FFN
-            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
-            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? at<float>(ws, pl.xL32) : x32, last ? nullptr : x16)) return 1;
-        }
+        if (run.layers(t, x32, at<float>(ws, pl.xL32), self_attn, nullptr)) return 1;
         BeamHeadParams hp;
         memset(&hp, 0, sizeof(hp));
         hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.emb = emb;
@@ -2498,7 +2411,7 @@ int beam_run(const egx_dec_config* cfg, const int64_t* start, const float* memor
         hp.words = period ? words + (size_t)(t % period) * pl.V : nullptr; hp.n_words = period ? counts[t % period] : 0;
         if (beam_head(hp, st)) return 1;
     }
-    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    run.joined();
     return 0;
 }
 
@@ -2507,8 +2420,8 @@ int beam_run(const egx_dec_config* cfg, const int64_t* start, const float* memor
 extern "C" {
 
 int egx_decoder_beam_workspace(const egx_dec_config* cfg, int B, int n_steps, int W, size_t* bytes) {
-    BPlan pl;
-    if (make_bplan(cfg, B, n_steps, W, pl)) return 1;
+    StepPlan pl;
+    if (beam_plan(cfg, B, n_steps, W, pl)) return 1;
     if (bytes) *bytes = pl.bytes;
     return 0;
 }
@@ -2607,162 +2520,40 @@ __global__ __launch_bounds__(64 * GH_WAVES) void forced_head_kernel(ForcedHeadPa
     }
 }
 
-struct FPlan {
-    int B, R, n, S, d, H, dff, L, V;
-    size_t M, Nm;
-    size_t zero, mem16, xin32, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
-    GLayer layer[16];
-    size_t bytes;
-};
-
-// The checks of the call and of the workspace query, then egx_decoder_beam's layout over M = B * R target rows without the beam's state,
-// plus the two (n_steps, M, d) fp32 slabs: the embedded input rows and the last layer's output rows.
-int make_fplan(const egx_dec_config* c, int B, int R, int n_steps, FPlan& pl) {
-    EGX_CHECK(c, "null decoder config");
-    EGX_CHECK(c->p_drop == 0.f && c->p_pos == 0.f, "egx_decoder_forced: inference only: p_drop and p_pos must be 0 (got %g, %g)", c->p_drop, c->p_pos);
-    EGX_CHECK(n_steps >= 1 && n_steps <= GEN_MAX_STEPS, "egx_decoder_forced: n_steps = %d (1..%d)", n_steps, GEN_MAX_STEPS);
-    EGX_CHECK(c->vocab >= 1 && c->vocab <= GEN_MAX_VOCAB, "egx_decoder_forced: vocab = %d (1..%d)", c->vocab, GEN_MAX_VOCAB);
+// The checks of the call and of the workspace query, then the shared layout over M = B * R target rows with the last layer's rows of every
+// step kept, plus the (n_steps, M, d) fp32 slab of embedded input rows.
+int forced_plan(const egx_dec_config* c, int B, int R, int n_steps, StepPlan& pl) {
+    if (step_checks("egx_decoder_forced", c, n_steps)) return 1;
     EGX_CHECK(R >= 1 && R <= FORCED_MAX_R, "egx_decoder_forced: R = %d (1..%d)", R, FORCED_MAX_R);
-    {   // d, heads, d_ff, layers, S and compute: egx_decoder_fwd's limits with R target rows per clip (cfg->sy is not read)
-        egx_dec_config one = *c;
-        one.sy = R;
-        DPlan dp;
-        if (make_dplan(&one, B, dp)) return 1;
-    }
-    EGX_CHECK((size_t)B * R <= (size_t)0x7fffffff / (size_t)(3 * c->d_model) && (size_t)B * c->S <= (size_t)0x7fffffff / (size_t)(2 * c->d_model),
-              "egx_decoder_forced: B = %d with R = %d, S = %d is too large", B, R, c->S);
-    memset(&pl, 0, sizeof(pl));
-    pl.B = B; pl.R = R; pl.n = n_steps; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
-    pl.M = (size_t)B * R; pl.Nm = (size_t)B * c->S;
-    const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
-    size_t cur = 0;
-    pl.zero = dtake(cur, 1024);
-    pl.mem16 = dtake(cur, Nm * d * 2);
-    for (int l = 0; l < pl.L; ++l) {
-        GLayer& o = pl.layer[l];
-        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
-        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
-        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
-        o.kv = dtake(cur, Nm * 2 * d * 2);
-        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
-    }
-    pl.xin32 = dtake(cur, M * n_steps * d * 4);
-    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
-    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
-    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * 256);
-    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
-    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
-    pl.xL32 = dtake(cur, M * n_steps * d * 4);
-    pl.bytes = cur;
+    if (step_layout(c, B, R, n_steps, 256, n_steps, pl)) return 1;
+    if (step_rows_fit("egx_decoder_forced", 'R', c, B, R)) return 1;
+    pl.xin32 = dtake(pl.bytes, pl.M * n_steps * pl.d * 4);
     return 0;
 }
 
 int forced_run(const egx_dec_config* cfg, const int64_t* tokens, const int64_t* targets, const float* memory, const float* emb, const float* pe,
                int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int R, int n_steps, float* logits_out,
                float* logprob_out, void* workspace, void* stream) {
-    FPlan pl;
-    if (make_fplan(cfg, B, R, n_steps, pl)) return 1;
+    StepPlan pl;
+    if (forced_plan(cfg, B, R, n_steps, pl)) return 1;
     EGX_CHECK(logits_out || logprob_out, "egx_decoder_forced: logits_out and logprob_out are both null: nothing to compute");
     EGX_CHECK(!logprob_out || targets, "egx_decoder_forced: logprob_out without targets");
     EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && fc_b && workspace, "egx_decoder_forced: null pointer argument");
     EGX_CHECK(pe_stride >= pl.d && pe_stride % 4 == 0, "egx_decoder_forced: pe_stride = %d (>= d_model, a multiple of 4)", pe_stride);
     hipStream_t st = (hipStream_t)stream;
     void* ws = workspace;
-    const int d = pl.d, dff = pl.dff, Nm = (int)pl.Nm, M = (int)pl.M, dh = d / pl.H;
-    EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
-    const void* zero = at<char>(ws, pl.zero);
-    bf16_t* mem16 = at<bf16_t>(ws, pl.mem16);
-    if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
-    {   // every weight -> bf16 once, one launch (as egx_decoder_generate)
-        WideCastBatch cb;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
-            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
-        }
-        if (wide_cast_flush(cb, st)) return 1;
-    }
+    const int d = pl.d, M = (int)pl.M;
+    StepRun run(cfg, pl, layers, ws, st);
+    if (run.begin(memory)) return 1;
     // every step's input rows in one launch: all B * R * n_steps tokens are known up front
     hipLaunchKernelGGL(forced_embed_kernel, dim3((unsigned)(((size_t)M * n_steps * (d / 4) + 255) / 256)), dim3(256), 0, st, tokens, emb, pe, pe_stride,
                        sqrtf((float)d), at<float>(ws, pl.xin32), M, n_steps, d, pl.V);
     EGX_LAUNCH_CHECK();
-    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* Wt, int rows, int N, int K, const float* bias, float* Cf, bf16_t* Cb,
-                     int relu, const float* residual) -> int {
-        WideGemmParams g;
-        g.A = A; g.B = Wt; g.M = rows; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
-        g.residual = residual; g.ldr = N; g.zero_page = zero;
-        return wide_gemm_nt(g, s_);
-    };
-    auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                  const float* residual) -> int { return nt_on(st, A, lda, Wt, M, N, K, bias, Cf, Cb, relu, residual); };
-    auto ln = [&](const float* x, const float* w, const float* b, float* y32, bf16_t* y16) -> int {
-        WideLnFwdParams lp;
-        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = M; lp.d = d;
-        return wide_ln_fwd(lp, st);
-    };
-    // the memory's K | V, once per layer and per CLIP (B * S rows): on the side stream beside step 0 (eager), on the caller's stream under capture
-    SideStream& SS = side_stream();
-    SideJoin sj(SS, st);
-    const bool side = side_wanted(SS, st);
-    if (side) {
-        if (SS.order(st, SS.s)) return 1;
-        sj.forked = true;
-    }
-    for (int l = 0; l < pl.L; ++l) {
-        const GLayer& o = pl.layer[l];
-        if (nt_on(side ? SS.s : st, mem16, d, cat<bf16_t>(ws, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
-        if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
-    }
-    for (int t = 0; t < n_steps; ++t) {
-        const float* xin = cat<float>(ws, pl.xin32) + (size_t)t * M * d;        // layer 0's input rows: the caller's tokens of step t
-        float* xL = at<float>(ws, pl.xL32) + (size_t)t * M * d;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
-            const bool last = l + 1 == pl.L;
-            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
-            const float* x32 = f32_self ? xin : cat<float>(ws, pl.x32);
-            if (f32_self) {
-                GemmParams g;
-                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = M; g.N = 3 * d; g.K = d;
-                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
-                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
-            } else if (nt(cat<bf16_t>(ws, pl.x16), d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
-            {
-                GenAttnParams a;
-                a.qkv = f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16);
-                a.cache = at<char>(ws, o.cache); a.o = at<bf16_t>(ws, pl.sa);
-                a.B = M; a.H = pl.H; a.d = d; a.t = t; a.n_steps = n_steps; a.scale = 0.f;
-                if (gen_self_attn(a, dh, f32_self, st)) return 1;
-            }
-            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
-            // cross-attention of the clip's R new rows onto its S memory rows: dec_attn with Sq = R
-            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
-            if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
-            {
-                DecAttnParams a;
-                memset(&a, 0, sizeof(a));
-                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
-                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
-                a.B = B; a.H = pl.H; a.Sq = R; a.Sk = pl.S; a.causal = 0;
-                if (dec_attn<false>(a, dh, false, st)) return 1;
-            }
-            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
-            // FFN
-            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
-            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? xL : at<float>(ws, pl.x32), last ? nullptr : at<bf16_t>(ws, pl.x16))) return 1;
-        }
-    }
-    sj.forked = false;      // joined already: every layer's step-0 cross-attention waited for its kv_ev, the last side-stream operation
+    if (run.fork_kv()) return 1;
+    // step t: layer 0 reads the caller's tokens of step t, the last layer writes row block t of the slab
+    for (int t = 0; t < n_steps; ++t)
+        if (run.layers(t, cat<float>(ws, pl.xin32) + (size_t)t * M * d, at<float>(ws, pl.xL32) + (size_t)t * M * d, own_history_attn(pl), nullptr)) return 1;
+    run.joined();
     ForcedHeadParams hp;
     hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.targets = targets; hp.logits = logits_out; hp.logprob = logprob_out;
     hp.rows = M * n_steps; hp.M = M; hp.n = n_steps; hp.d = d; hp.V = pl.V;
@@ -2776,8 +2567,8 @@ int forced_run(const egx_dec_config* cfg, const int64_t* tokens, const int64_t* 
 extern "C" {
 
 int egx_decoder_forced_workspace(const egx_dec_config* cfg, int B, int R, int n_steps, size_t* bytes) {
-    FPlan pl;
-    if (make_fplan(cfg, B, R, n_steps, pl)) return 1;
+    StepPlan pl;
+    if (forced_plan(cfg, B, R, n_steps, pl)) return 1;
     if (bytes) *bytes = pl.bytes;
     return 0;
 }

@@ -1768,6 +1768,33 @@ def check_schedule(schedule, vocab: int, device=None, beam_width: int = 0) -> No
                          f"memory's device")
 
 
+def _cached_step_setup(who, lead, rank, lead_desc, meta, mem2d, emb, pe, layer_params, fc_w, fc_b, n_steps, query, also=None):
+    """What decoder_generate, decoder_beam and decoder_forced open with (under no_grad): the tensors on the device (_dec_tensors), the
+    check of the leading token tensor `lead` (of `rank`; lead_desc: its name and shape; n_steps None: its last extent), also(), the call's
+    own argument checks, the memory / positional-row fit, the dropout-free config, the layer array and the workspace query(cfg, B, n_steps,
+    nb) sizes.
+    Returns (lead, V, cfg, model, ws, keep): model = the seven arguments from the memory to fc_b, which every entry point takes in this
+    order; keep = the tensors behind them, to be held until the call is made."""
+    _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
+    if lead.dtype != torch.int64 or not lead.is_cuda or lead.dim() != rank:
+        raise _lib.EgxError(f"{who}: {lead_desc} int64 tensor on the GPU")
+    if also is not None:
+        also()
+    lead = lead.contiguous()
+    B, (V, d) = lead.shape[0], emb.shape
+    n_steps = lead.shape[-1] if n_steps is None else n_steps
+    if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
+        raise _lib.EgxError(f"{who}: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
+                            f"d = {d}, n_steps = {n_steps}")
+    cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
+    layers = _dec_layers(layer_t, meta["n_layers"])
+    nb = C.c_size_t(0)
+    check(query(C.byref(cfg), B, n_steps, C.byref(nb)))
+    ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=mem2d.device)
+    model = (ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b))
+    return lead, V, cfg, model, ws, (mem2d, emb, pe, layer_t, fc_w, fc_b)
+
+
 def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, n_steps: int, return_logits: bool = False,
                      schedule: "TokenSchedule" = None, return_attention: bool = False):
     """Greedy generation in ONE asynchronous call (egx_decoder_generate; no autograd): start (B,) int64, mem2d (B * S, d) batch-first memory
@@ -1778,27 +1805,16 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
     cross-attention weights of every layer; tokens and logits keep their bits."""
     lib = _lib.load()
     with torch.no_grad():
-        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
-        if start.dtype != torch.int64 or not start.is_cuda or start.dim() != 1:
-            raise _lib.EgxError("decoder_generate: start must be a (B,) int64 tensor on the GPU")
-        start = start.contiguous()
-        B, (V, d) = start.shape[0], emb.shape
-        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
-            raise _lib.EgxError(f"decoder_generate: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
-                                f"d = {d}, n_steps = {n_steps}")
-        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
-        layers = _dec_layers(layer_t, meta["n_layers"])
-        nb = C.c_size_t(0)
-        check(lib.egx_decoder_generate_workspace(C.byref(cfg), B, n_steps, C.byref(nb)))
-        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=mem2d.device)
-        tokens = torch.empty((B, n_steps), dtype=torch.int64, device=mem2d.device)
-        logits = torch.empty((n_steps, B, V), dtype=torch.float32, device=mem2d.device) if return_logits else None
-        args = (C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, n_steps, ptr(tokens),
-                ptr(logits), ptr(ws), _stream())
+        start, V, cfg, model, ws, keep = _cached_step_setup("decoder_generate", start, 1, "start must be a (B,)", meta, mem2d, emb, pe, layer_params,
+                                                            fc_w, fc_b, n_steps, lib.egx_decoder_generate_workspace)
+        B, dev = start.shape[0], ws.device
+        tokens = torch.empty((B, n_steps), dtype=torch.int64, device=dev)
+        logits = torch.empty((n_steps, B, V), dtype=torch.float32, device=dev) if return_logits else None
+        args = (C.byref(cfg), ptr(start), *model, B, n_steps, ptr(tokens), ptr(logits), ptr(ws), _stream())
         if schedule is not None:
-            check_schedule(schedule, V, mem2d.device)
+            check_schedule(schedule, V, dev)
         if return_attention:
-            attn = torch.empty((meta["n_layers"], n_steps, B, mem2d.shape[0] // B), dtype=torch.float32, device=mem2d.device)
+            attn = torch.empty((meta["n_layers"], n_steps, B, cfg.S), dtype=torch.float32, device=dev)
             check(lib.egx_decoder_generate_attn(*args, *((0, None, None) if schedule is None else schedule._args()), ptr(attn)))
         elif schedule is None:
             check(lib.egx_decoder_generate(*args))
@@ -1831,20 +1847,10 @@ def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tenso
     -inf."""
     lib = _lib.load()
     with torch.no_grad():
-        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
-        if start.dtype != torch.int64 or not start.is_cuda or start.dim() != 1:
-            raise _lib.EgxError("decoder_beam: start must be a (B,) int64 tensor on the GPU")
-        start = start.contiguous()
-        B, (V, d), W = start.shape[0], emb.shape, beam_width
-        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
-            raise _lib.EgxError(f"decoder_beam: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
-                                f"d = {d}, n_steps = {n_steps}")
-        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
-        layers = _dec_layers(layer_t, meta["n_layers"])
-        nb = C.c_size_t(0)
-        check(lib.egx_decoder_beam_workspace(C.byref(cfg), B, n_steps, W, C.byref(nb)))
-        dev = mem2d.device
-        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=dev)
+        W = beam_width
+        start, V, cfg, model, ws, keep = _cached_step_setup("decoder_beam", start, 1, "start must be a (B,)", meta, mem2d, emb, pe, layer_params, fc_w,
+                                                            fc_b, n_steps, lambda c, B, n, nb: lib.egx_decoder_beam_workspace(c, B, n, W, nb))
+        B, dev = start.shape[0], ws.device
         tokens = torch.empty((B, W, n_steps), dtype=torch.int64, device=dev)
         scores = torch.empty((B, W), dtype=torch.float32, device=dev)
         trace = None
@@ -1853,8 +1859,7 @@ def decoder_beam(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.Tenso
                               torch.empty((n_steps, B, W), dtype=torch.float32, device=dev),
                               torch.empty((n_steps, B, W, V), dtype=torch.float32, device=dev))
         tr = [ptr(getattr(trace, k)) if trace is not None else None for k in BeamTrace.__slots__]
-        args = (C.byref(cfg), ptr(start), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w), ptr(fc_b), B, n_steps, W, ptr(tokens),
-                ptr(scores), *tr, ptr(ws), _stream())
+        args = (C.byref(cfg), ptr(start), *model, B, n_steps, W, ptr(tokens), ptr(scores), *tr, ptr(ws), _stream())
         if schedule is None:
             check(lib.egx_decoder_beam(*args))
         else:
@@ -1878,29 +1883,21 @@ def decoder_forced(meta, tokens, targets, mem2d, emb, pe, layer_params: Sequence
     the vocabulary. The workspace comes from the caching allocator: the call can be captured."""
     lib = _lib.load()
     with torch.no_grad():
-        _, mem2d, emb, pe, layer_t, fc_w, fc_b = _dec_tensors(None, mem2d, emb, pe, layer_params, fc_w, fc_b)
-        if tokens.dtype != torch.int64 or not tokens.is_cuda or tokens.dim() != 3:
-            raise _lib.EgxError("decoder_forced: tokens must be a (B, R, n_steps) int64 tensor on the GPU")
-        if targets is not None and (targets.dtype != torch.int64 or not targets.is_cuda or targets.shape != tokens.shape):
-            raise _lib.EgxError(f"decoder_forced: targets must be an int64 tensor on the GPU of the tokens' shape {tuple(tokens.shape)}")
-        if targets is None and not return_logits:
-            raise _lib.EgxError("decoder_forced: return_logits=False without targets leaves nothing to compute")
-        tokens = tokens.contiguous()
+        def also():
+            if targets is not None and (targets.dtype != torch.int64 or not targets.is_cuda or targets.shape != tokens.shape):
+                raise _lib.EgxError(f"decoder_forced: targets must be an int64 tensor on the GPU of the tokens' shape {tuple(tokens.shape)}")
+            if targets is None and not return_logits:
+                raise _lib.EgxError("decoder_forced: return_logits=False without targets leaves nothing to compute")
+
+        tokens, V, cfg, model, ws, keep = _cached_step_setup(
+            "decoder_forced", tokens, 3, "tokens must be a (B, R, n_steps)", meta, mem2d, emb, pe, layer_params, fc_w, fc_b, None,
+            lambda c, B, n, nb: lib.egx_decoder_forced_workspace(c, B, tokens.shape[1], n, nb), also)
         targets = targets.contiguous() if targets is not None else None
-        (B, R, n_steps), (V, d) = tokens.shape, emb.shape
-        if B < 1 or mem2d.dim() != 2 or mem2d.shape[0] % B or mem2d.shape[1] != d or pe.shape[0] < n_steps:
-            raise _lib.EgxError(f"decoder_forced: memory {tuple(mem2d.shape)} / positional rows {tuple(pe.shape)} do not fit B = {B}, "
-                                f"d = {d}, n_steps = {n_steps}")
-        cfg = _dec_config(meta, d, V, 1, mem2d.shape[0] // B, False)
-        layers = _dec_layers(layer_t, meta["n_layers"])
-        nb = C.c_size_t(0)
-        check(lib.egx_decoder_forced_workspace(C.byref(cfg), B, R, n_steps, C.byref(nb)))
-        dev = mem2d.device
-        ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=dev)
+        (B, R, n_steps), dev = tokens.shape, ws.device
         logits = torch.empty((n_steps, B * R, V), dtype=torch.float32, device=dev) if return_logits else None
         logprob = torch.empty((B, R, n_steps), dtype=torch.float32, device=dev) if targets is not None else None
-        check(lib.egx_decoder_forced(C.byref(cfg), ptr(tokens), ptr(targets), ptr(mem2d), ptr(emb), ptr(pe), pe.stride(0), layers, ptr(fc_w),
-                                     ptr(fc_b), B, R, n_steps, ptr(logits), ptr(logprob), ptr(ws), _stream()))
+        check(lib.egx_decoder_forced(C.byref(cfg), ptr(tokens), ptr(targets), *model, B, R, n_steps, ptr(logits), ptr(logprob), ptr(ws),
+                                     _stream()))
     _last_dec_impl[0] = "forced"
     return logits, logprob
 

@@ -34,9 +34,18 @@ Cases on the EgoT2-g HHI model (d 256, 4 heads, L 3 + 3, bf16, seeded weights; B
   k encode_features_ragged + decode_ragged, p 0.1, with d_memory: 'ttm' (packed rows) and 'asd' (frame-major tuples, decode() on S = 3)
   l the calls of k under no_grad (their `saved` in the shared workspace), and eval-mode ragged inference (encode_features / decode with lengths)
   m greedy_decode, 4 steps, with logits
+Cases on the cached step (egx_decoder_generate / _beam / _forced) with the seeded models of tests/greedy_ref.py (hhi_model d 256, 4 heads, L 2,
+V 40; B 4, S 19; eager; every returned tensor and the call's launch count):
+  o greedy_decode, 5 steps, a period-2 schedule, logits and return_attention
+  p beam_decode, 5 steps, with scores and trace: W 3 under the schedule, W 5 free (the two beam_head_kernel instantiations)
+  q forced_decode, 9 tokens, targets and logits: one sequence per clip (R 1) and three (R 3)
+  r greedy_decode on hoi_model d 256 with 8 heads (head dim 32: the other instances of the cached self-attention), 4 steps, with logits
 
 --host: no GPU. The children drive the host-only calls of tests/host_paths*.py (workspace sizes, implementation / slice answers, refusals)
-and the ragged workspace queries through a recording proxy; the parent compares return values, sizes and egx_last_error() texts."""
+and the ragged workspace queries through a recording proxy, then a grid over the three generation workspace queries (tests/host_paths_generate.py's
+models x B 1, 37, 256 x S 1, 48, 1024 x steps 1, 2, 40, 64 x W = R 1, 3, 8) and the early refusals of the six generation entry points (those of
+tests/test_cpu_beam.py and tests/test_cpu_forced.py, null pointers, pe_stride, schedules); the parent compares return values, sizes and
+egx_last_error() texts."""
 import ctypes as C
 import json
 import os
@@ -256,6 +265,36 @@ def gpu_child(path):
         mem = m.encode_features("ttm", *f16)
         step("m", m, lambda: m.greedy_decode(mem, HHI_G_VOCAB["ttm"], 4, return_logits=True))
         assert F_egx.last_decoder_impl() == "generate", F_egx.last_decoder_impl()
+
+        # the cached-step calls on the seeded models of tests/greedy_ref.py, eagerly: every returned tensor and the launch count of the call
+        from tests import greedy_ref as gr
+
+        def cached(build, d, h, L, V, S, wseed):
+            mdl, _, start = build(d, h, L, V, wseed)
+            return mdl.to(cuda).set_compute("bf16").eval(), start, util.seeded_feats(96, [(S, 4, d)])[0].to(cuda)
+
+        def flat(res):
+            """a call's results as a tuple of tensors (a BeamTrace as its four)"""
+            res = res if isinstance(res, tuple) else (res,)
+            return tuple(t for r in res for t in ([getattr(r, k) for k in r.__slots__] if isinstance(r, F_egx.BeamTrace) else [r]))
+
+        mg, start, memg = cached(gr.hhi_model, 256, 4, 2, 40, 19, 130)
+        allowed = torch.zeros((2, 40), dtype=torch.bool)
+        allowed[0, 5:17], allowed[1, 12:40] = True, True
+        sched = mg.token_schedule(allowed)
+        step("o", mg, lambda: flat(mg.greedy_decode(memg, start, 5, return_logits=True, schedule=sched, return_attention=True)))
+        step("p_w3", mg, lambda: flat(mg.beam_decode(memg, start, 5, 3, return_scores=True, return_trace=True, schedule=sched)))
+        assert F_egx.last_decoder_impl() == "beam", F_egx.last_decoder_impl()
+        step("p_w5", mg, lambda: flat(mg.beam_decode(memg, start, 5, 5, return_scores=True, return_trace=True)))
+        g = torch.Generator().manual_seed(23)
+        y = torch.randint(0, 40, (4, 3, 9), generator=g).to(cuda)
+        tg = torch.randint(-1, 40, (4, 3, 9), generator=g).to(cuda)            # (-1: outside the vocabulary, logprob exactly 0)
+        step("q_r1", mg, lambda: flat(mg.forced_decode(memg, y[:, 0].contiguous(), targets=tg[:, 0].contiguous())))
+        assert F_egx.last_decoder_impl() == "forced", F_egx.last_decoder_impl()
+        step("q_r3", mg, lambda: flat(mg.forced_decode(memg, y, targets=tg)))
+        m32, start32, mem32 = cached(gr.hoi_model, 256, 8, 2, 12, 16, 95)      # head dim 32: the other instances of the cached self-attention
+        step("r", m32, lambda: flat(m32.greedy_decode(mem32, start32, 4, return_logits=True)))
+        assert F_egx.last_decoder_impl() == "generate", F_egx.last_decoder_impl()
     np.savez(path, **out)
     print(f"{os.path.relpath(path, ROOT)}: {len(out)} arrays")
 
@@ -302,6 +341,66 @@ def host_child(path):
                         cfg.deterministic = det
                         rec.egx_ragged_workspace(C.byref(cfg), segs, len(lens), arr, C.byref(nb))
                         rec.egx_ragged_train_workspace(C.byref(cfg), segs, len(lens), arr, C.byref(sv), C.byref(sc))
+    # the cached-step calls (greedy, beam, forced; k = W = R): every workspace size, and every refusal that comes before the first device call
+    from egot2_amd._lib import DecConfig, DecLayer
+    PTR = 1 << 12       # a non-null marker: a call that gets it is refused before anything is read
+
+    def dcfg(d=256, h=4, L=3, V=40, S=48, compute=1, p_drop=0.0, p_pos=0.0, dff=2048, sy=0):
+        return DecConfig(d, h, dff, L, V, sy, S, 1e-5, compute, p_drop, p_pos, None)
+
+    def queries(cfg, B, n, k):
+        c = C.byref(cfg) if cfg is not None else None
+        rec.egx_decoder_generate_workspace(c, B, n, C.byref(nb))
+        rec.egx_decoder_beam_workspace(c, B, n, k, C.byref(nb))
+        rec.egx_decoder_forced_workspace(c, B, k, n, C.byref(nb))
+
+    def calls(cfg, B, n, k, p=None, stride=256, period=0, counts=None, forced=None):
+        """the six entry points with every pointer p (None: the null-pointer refusal at the latest); forced: egx_decoder_forced's
+        (tokens, targets, logits, logprob, workspace) when they differ from p"""
+        c = C.byref(cfg) if cfg is not None else None
+        lay = C.cast(p, C.POINTER(DecLayer)) if p else None
+        cnt = (C.c_int * len(counts))(*counts) if counts else None
+        head, gen, beam = (c, p, p, p, p, stride, lay, p, p, B, n), (p, p, p, None), (k, p, p, p, p, p, p, p, None)
+        rec.egx_decoder_generate(*head, *gen)
+        rec.egx_decoder_generate_sched(*head, *gen, period, cnt, p)
+        rec.egx_decoder_generate_attn(*head, *gen, period, cnt, p, p)
+        rec.egx_decoder_generate_attn(*head, *gen, period, cnt, p, PTR)
+        rec.egx_decoder_beam(*head, *beam)
+        rec.egx_decoder_beam_sched(*head, *beam, period, cnt, p)
+        tok, tgt, lg, lp, ws = forced or (p,) * 5
+        rec.egx_decoder_forced(c, tok, tgt, p, p, p, stride, lay, p, p, B, k, n, lg, lp, ws, None)
+
+    for d, h, L, V in [(256, 4, 2, 7), (512, 8, 3, 600), (1024, 16, 16, 1024), (384, 12, 1, 1)]:       # tests/host_paths_generate.py's list
+        for B in (1, 37, 256):
+            for S in (1, 48, 1024):
+                for n in (1, 2, 40, 64):
+                    for k in (1, 3, 8):
+                        cfg = dcfg(d=d, h=h, L=L, V=V, S=S, sy=99)
+                        queries(cfg, B, n, k)
+                        calls(cfg, B, n, k, stride=d)
+    # the refusals of tests/test_cpu_beam.py and tests/test_cpu_forced.py, through the queries and through the calls
+    for kw, B, n, k in [(dict(sy=77), 4, 2, 3), ({}, 4, 2, 0), ({}, 4, 2, 9), ({}, 4, 2, -1), ({}, 4, 2, 8), ({}, 4, 2, 1), (dict(V=6), 4, 2, 7),
+                        (dict(V=6), 4, 2, 6), (dict(V=2), 4, 2, 8), (dict(V=2), 4, 2, 3), ({}, 4, 0, 3), ({}, 4, 65, 3), ({}, 4, 64, 3),
+                        (dict(V=1025), 4, 2, 3), (dict(V=0), 4, 2, 3), (dict(V=1024, d=1024, h=16), 4, 2, 8), (dict(p_drop=0.1), 4, 2, 3),
+                        (dict(p_pos=0.1), 4, 2, 3), (dict(p_drop=0.5), 4, 2, 3), (dict(compute=0), 4, 2, 3), (dict(compute=2), 4, 2, 3),
+                        (dict(d=192, h=3), 4, 2, 3), (dict(d=256, h=2), 4, 2, 3), (dict(dff=100), 4, 2, 3), (dict(L=17), 4, 2, 3),
+                        (dict(S=1025), 4, 2, 3), ({}, 0, 2, 3), (dict(d=1024, h=16), 100000, 2, 8), (None, 4, 2, 3)]:
+        cfg = None if kw is None else dcfg(**kw)
+        queries(cfg, B, n, k)
+        calls(cfg, B, n, k)
+        if cfg is not None:     # with every pointer given: the same first refusal, at the latest the pe_stride's (128 < d_model)
+            calls(cfg, B, n, k, p=PTR, stride=128)
+    rec.egx_decoder_generate_workspace(C.byref(dcfg()), 4, 2, None)             # queries for the verdict alone
+    rec.egx_decoder_beam_workspace(C.byref(dcfg()), 4, 2, 3, None)
+    rec.egx_decoder_forced_workspace(C.byref(dcfg()), 4, 3, 2, None)
+    for stride in (128, 258):
+        calls(dcfg(), 4, 2, 3, p=PTR, stride=stride)
+    for forced in ((PTR, PTR, None, None, PTR), (PTR, None, PTR, PTR, PTR), (None, PTR, PTR, PTR, PTR), (PTR, PTR, PTR, PTR, None)):
+        calls(dcfg(), 4, 2, 3, p=PTR, stride=128, forced=forced)                # (the stride refuses the calls `forced` does not)
+    # token schedules: checked before the pointers (a schedule that passes ends at the pe_stride)
+    for period, counts in ((65, None), (-1, None), (2, None), (2, [0, 3]), (2, [3, 41]), (2, [2, 40]), (1, [40])):
+        calls(dcfg(), 4, 2, 3, period=period, counts=counts)
+        calls(dcfg(), 4, 2, 3, p=PTR, stride=128, period=period, counts=counts)
     json.dump(rec.log, open(path, "w"))
     print(f"{os.path.relpath(path, ROOT)}: {len(rec.log)} calls")
 
