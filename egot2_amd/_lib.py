@@ -142,6 +142,10 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, _fp]),
     "egx_small_attention_bwd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, _fp]),
+    "egx_target_attention_fwd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, _fp]),
+    "egx_target_attention_bwd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, _fp]),
     "egx_embed_pos_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_float, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                     C.c_uint64, _fp]),
     "egx_embed_pos_bwd": (C.c_int, [_fp, _fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),

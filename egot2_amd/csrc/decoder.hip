@@ -7,6 +7,7 @@
 //                            Q and K/V operands: causal self-attention over the target (packed qkv rows) and cross-
 //                            attention onto the memory (Q from the target, packed kv rows from the memory projection).
 //                            One wave per (batch element, head); probabilities are recomputed in the backward.
+//                            (More than 8 queries: target_attention_fwd/bwd of target_attn.hip, behind entry points of their own.)
 //   embed_pos_fwd/bwd        y = embedding[token] * sqrt(d) + pe[position] (+ dropout), and the scatter-add of its gradient.
 //   relu_mask                dy <- dy where y > 0 (backward of the ReLU fused into the linear1 GEMM epilogue).
 //   gelu_fwd/bwd             exact (erf) GELU of the pre-LN translator's FeedForward (HOI/models/pnr/simple_vit.py:55-65).

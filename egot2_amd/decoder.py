@@ -4,7 +4,8 @@ HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video
 `embedding(y) * sqrt(d)` + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (post-LN: causal
 self-attention over the 2..5 target tokens, cross-attention onto the encoder memory, ReLU FFN) -> `fc`. The nn modules
 are parameter containers only; projections / FFN run through the MFMA GEMM (egx_linear_*), LayerNorms through
-egx_layernorm_*, the two attentions through egx_small_attention_* and the embedding through egx_embed_pos_*."""
+egx_layernorm_*, the two attentions through egx_small_attention_* (at most 8 target tokens) or egx_target_attention_* (9 .. 64, behind
+DecoderMixin.egx_long_targets) and the embedding through egx_embed_pos_*."""
 from __future__ import annotations
 
 import functools
@@ -19,6 +20,13 @@ _SITE0 = 0x4000     # decoder dropout sites live above the encoder's (layer << 8
 
 
 class DecoderMixin:
+    # decode() of 9 .. 64 target tokens WITH autograd (the reference's training_step over 21- and 40-token targets: model(video,
+    # target[:, :-1], 'lta_verb'), HOI/tasks/multitask/video_task_action.py:34-53) runs the composed fp32 decoder on egx_target_attention_*
+    # when this is set (last_decoder_impl() == "composed_long"): train mode, eval mode with autograd, and eval under no_grad where
+    # egx_decoder_forced does not serve the configuration. Off by default, as hoi_multitask's egx_generate is: with it off, and for at most 8
+    # tokens in either state, every call is what it was, down to the exception text. Its attention masks are keyed with row stride 64.
+    egx_long_targets = False
+
     def _egx_decoder_args(self, decoder: nn.TransformerDecoder, pos_embed, n_heads: int, p_drop: float):
         """(meta, 18 tensors per layer) of a fused decoder call (DecoderFn, RaggedDecoderFn, functional.decoder_ragged)."""
         train = bool(self.training)
@@ -80,6 +88,13 @@ class DecoderMixin:
             # 9 .. 64 target tokens at inference (the validation step's model(video, target[:, :-1], task)): the fused decoder stops at 8
             # rows, so the rows run one at a time through the K/V-cached step, ONE egx_decoder_forced call
             return self._egx_forced(encoded_x, y[:, None, :], None, True, embedding, pos_embed, decoder, fc, n_heads)[0].view(sy, B, -1)
+        # 9 .. 64 target tokens where the forced route above did not take the call (opt-in): the loop below with the 64-row attention
+        long_targets = bool(getattr(self, "egx_long_targets", False)) and sy > 8 and not want_attn
+        if long_targets and not F_egx.decoder_long_supported(d, n_heads, sy, S):
+            raise ValueError(f"decode() with egx_long_targets serves 9..64 target tokens, head dim <= 128 and 1..1024 memory tokens: got "
+                             f"sy = {sy}, d = {d}, {n_heads} heads, S = {S}")
+        self_attn, cross_attn = ((F_egx.SelfAttnTargetFn, F_egx.CrossAttnTargetFn) if long_targets
+                                 else (F_egx.SelfAttnSmallFn, F_egx.CrossAttnSmallFn))
         comp = "f32"        # (B * sy)-row GEMMs: negligible work, they always run the exact fp32 MFMA path
         comp_mem = getattr(self, "egx_compute", "f32")     # the K / V projection of the (B * S)-row memory follows the encoder's compute type
         train = bool(self.training)
@@ -97,12 +112,12 @@ class DecoderMixin:
             p = p_drop if train else 0.0
             sa, ca = layer.self_attn, layer.multihead_attn
             qkv = lin(x, sa.in_proj_weight, sa.in_proj_bias, comp)
-            a = F_egx.SelfAttnSmallFn.apply(qkv, B, sy, n_heads, True, p, seed, site(1))
+            a = self_attn.apply(qkv, B, sy, n_heads, True, p, seed, site(1))
             a = F_egx.dropout(lin(a, sa.out_proj.weight, sa.out_proj.bias, comp), p_drop, train, seed, site(2))
             x = F_egx.layer_norm_residual(x, a, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
             q = lin(x, ca.in_proj_weight[:d], ca.in_proj_bias[:d], comp)
             kv = lin(mem2d, ca.in_proj_weight[d:], ca.in_proj_bias[d:], comp_mem)
-            c = F_egx.CrossAttnSmallFn.apply(q, kv, B, sy, S, n_heads, p, seed, site(3))
+            c = cross_attn.apply(q, kv, B, sy, S, n_heads, p, seed, site(3))
             if want_attn:
                 attn.append(F_egx.cross_attention_weights(q, kv[:, :d], n_heads, sy, S))
             c = F_egx.dropout(lin(c, ca.out_proj.weight, ca.out_proj.bias, comp), p_drop, train, seed, site(4))
@@ -111,7 +126,7 @@ class DecoderMixin:
             f = F_egx.dropout(lin(h, layer.linear2.weight, layer.linear2.bias, comp), p_drop, train, seed, site(6))
             x = F_egx.layer_norm_residual(x, f, layer.norm3.weight, layer.norm3.bias, layer.norm3.eps)
         out = lin(x, fc.weight, fc.bias, comp)                         # (B * sy, |V|)
-        F_egx._last_dec_impl[0] = "composed"
+        F_egx._last_dec_impl[0] = "composed_long" if long_targets else "composed"
         if want_attn:
             return out.view(B, sy, -1).permute(1, 0, 2), torch.stack(attn, 0)
         return out.view(B, sy, -1).permute(1, 0, 2)

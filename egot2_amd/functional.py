@@ -1152,8 +1152,9 @@ def last_decoder_impl() -> str:
     """Diagnostic: the implementation the most recent EgoT2-g decode ran: "fused" (egx_decoder_fwd), "composed" (one library call per
     operation), "ragged" (egx_decoder_ragged_fwd / egx_decoder_ragged_train_fwd), "grouped" (a ragged memory decoded one length group at a
     time), "generate" (greedy generation in one egx_decoder_generate call), "loop" (greedy generation as a prefix loop over decode()),
-    "beam" (beam search in one egx_decoder_beam call) or "forced" (teacher-forced decoding of up to 64 target tokens in one
-    egx_decoder_forced call)."""
+    "beam" (beam search in one egx_decoder_beam call), "forced" (teacher-forced decoding of up to 64 target tokens in one
+    egx_decoder_forced call) or "composed_long" (the composed decoder over 9 .. 64 target tokens, egx_target_attention_*: the
+    differentiable route behind egx_long_targets)."""
     return _last_dec_impl[0]
 
 
@@ -1875,6 +1876,12 @@ def decoder_forced_supported(compute: str, d: int, n_heads: int, d_ff: int, S: i
     return decoder_generate_supported(compute, d, n_heads, d_ff, S, n_layers, vocab, n_steps) and 1 <= rows_per_clip <= 8
 
 
+def decoder_long_supported(d: int, n_heads: int, sy: int, S: int) -> bool:
+    """Shapes the composed decoder serves over 9 .. 64 target tokens (decoder.py, egx_long_targets; egx_target_attention_*'s limits): head
+    dim d / n_heads <= 128, 1 <= S <= 1024 memory tokens. Post-LN layers are the caller's check."""
+    return n_heads >= 1 and d >= 1 and d % n_heads == 0 and d // n_heads <= 128 and 9 <= sy <= 64 and 1 <= S <= 1024
+
+
 def decoder_forced(meta, tokens, targets, mem2d, emb, pe, layer_params: Sequence[torch.Tensor], fc_w, fc_b, return_logits: bool = True):
     """Teacher-forced decoding in ONE asynchronous call (egx_decoder_forced; no autograd): tokens (B, R, n_steps) int64 input tokens, R
     sequences per clip; targets the same shape or None; mem2d (B * S, d) batch-first memory rows (one memory per CLIP), pe (>= n_steps, d)
@@ -2095,37 +2102,77 @@ class EmbedPosFn(torch.autograd.Function):
         return None, d_emb, None, None, None, None
 
 
+def _attn_entry(entry: str, direction: str):
+    """egx_small_attention_* (at most 8 query rows, mask row stride 8) or egx_target_attention_* (at most 64, stride 64): same arguments."""
+    return getattr(_lib.load(), f"{entry}_{direction}")
+
+
+def _self_attn_fwd(ctx, entry, qkv, B: int, sy: int, H: int, causal: bool, p: float, seed: int, site: int):
+    fn = _attn_entry(entry, "fwd")
+    qkv = _dev_f32(qkv, "qkv")
+    d = qkv.shape[1] // 3
+    out = torch.empty((B * sy, d), dtype=torch.float32, device=qkv.device)
+    e = qkv.element_size()
+    base = qkv.data_ptr()
+    check(fn(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(out), d, B, sy, sy, H,
+             d // H, int(causal), float(p), _seed64(seed), site, _stream()))
+    ctx.cfg = (B, sy, H, int(causal), float(p), seed, site)
+    ctx.save_for_backward(qkv)
+    return out
+
+
+def _self_attn_bwd(ctx, entry, d_out):
+    fn = _attn_entry(entry, "bwd")
+    (qkv,) = ctx.saved_tensors
+    B, sy, H, causal, p, seed, site = ctx.cfg
+    d = qkv.shape[1] // 3
+    d_out = _f32c(d_out)
+    dqkv = torch.empty_like(qkv)
+    e = qkv.element_size()
+    base, gb = qkv.data_ptr(), dqkv.data_ptr()
+    check(fn(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(d_out), d,
+             gb, gb + d * e, gb + 2 * d * e, B, sy, sy, H, d // H, causal, p, _seed64(seed), site, _stream()))
+    return dqkv, None, None, None, None, None, None, None
+
+
+def _cross_attn_fwd(ctx, entry, q, kv, B: int, sy: int, S: int, H: int, p: float, seed: int, site: int):
+    fn = _attn_entry(entry, "fwd")
+    q, kv = _dev_f32(q, "q"), _dev_f32(kv, "kv")
+    d = q.shape[1]
+    out = torch.empty((B * sy, d), dtype=torch.float32, device=q.device)
+    e = kv.element_size()
+    kb = kv.data_ptr()
+    check(fn(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(out), d, B, sy, S, H, d // H, 0, float(p),
+             _seed64(seed), site, _stream()))
+    ctx.cfg = (B, sy, S, H, float(p), seed, site)
+    ctx.save_for_backward(q, kv)
+    return out
+
+
+def _cross_attn_bwd(ctx, entry, d_out):
+    fn = _attn_entry(entry, "bwd")
+    q, kv = ctx.saved_tensors
+    B, sy, S, H, p, seed, site = ctx.cfg
+    d = q.shape[1]
+    d_out = _f32c(d_out)
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    e = kv.element_size()
+    kb, gb = kv.data_ptr(), dkv.data_ptr()
+    check(fn(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(d_out), d, ptr(dq), gb, gb + d * e,
+             B, sy, S, H, d // H, 0, p, _seed64(seed), site, _stream()))
+    return dq, dkv, None, None, None, None, None, None, None
+
+
 class SelfAttnSmallFn(torch.autograd.Function):
     """Causal self-attention over a few target tokens from packed (B * sy, 3d) qkv rows -> (B * sy, d)."""
 
     @staticmethod
     def forward(ctx, qkv, B: int, sy: int, H: int, causal: bool, p: float, seed: int, site: int):
-        lib = _lib.load()
-        qkv = _dev_f32(qkv, "qkv")
-        d = qkv.shape[1] // 3
-        out = torch.empty((B * sy, d), dtype=torch.float32, device=qkv.device)
-        e = qkv.element_size()
-        base = qkv.data_ptr()
-        check(lib.egx_small_attention_fwd(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(out), d, B, sy, sy, H,
-                                          d // H, int(causal), float(p), _seed64(seed), site, _stream()))
-        ctx.cfg = (B, sy, H, int(causal), float(p), seed, site)
-        ctx.save_for_backward(qkv)
-        return out
+        return _self_attn_fwd(ctx, "egx_small_attention", qkv, B, sy, H, causal, p, seed, site)
 
     @staticmethod
     def backward(ctx, d_out):
-        lib = _lib.load()
-        (qkv,) = ctx.saved_tensors
-        B, sy, H, causal, p, seed, site = ctx.cfg
-        d = qkv.shape[1] // 3
-        d_out = _f32c(d_out)
-        dqkv = torch.empty_like(qkv)
-        e = qkv.element_size()
-        base, gb = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib.egx_small_attention_bwd(base, 3 * d, base + d * e, 3 * d, base + 2 * d * e, 3 * d, ptr(d_out), d,
-                                          gb, gb + d * e, gb + 2 * d * e, B, sy, sy, H, d // H, causal, p,
-                                          _seed64(seed), site, _stream()))
-        return dqkv, None, None, None, None, None, None, None
+        return _self_attn_bwd(ctx, "egx_small_attention", d_out)
 
 
 class CrossAttnSmallFn(torch.autograd.Function):
@@ -2133,28 +2180,32 @@ class CrossAttnSmallFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, B: int, sy: int, S: int, H: int, p: float, seed: int, site: int):
-        lib = _lib.load()
-        q, kv = _dev_f32(q, "q"), _dev_f32(kv, "kv")
-        d = q.shape[1]
-        out = torch.empty((B * sy, d), dtype=torch.float32, device=q.device)
-        e = kv.element_size()
-        kb = kv.data_ptr()
-        check(lib.egx_small_attention_fwd(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(out), d, B, sy, S, H, d // H, 0, float(p),
-                                          _seed64(seed), site, _stream()))
-        ctx.cfg = (B, sy, S, H, float(p), seed, site)
-        ctx.save_for_backward(q, kv)
-        return out
+        return _cross_attn_fwd(ctx, "egx_small_attention", q, kv, B, sy, S, H, p, seed, site)
 
     @staticmethod
     def backward(ctx, d_out):
-        lib = _lib.load()
-        q, kv = ctx.saved_tensors
-        B, sy, S, H, p, seed, site = ctx.cfg
-        d = q.shape[1]
-        d_out = _f32c(d_out)
-        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        e = kv.element_size()
-        kb, gb = kv.data_ptr(), dkv.data_ptr()
-        check(lib.egx_small_attention_bwd(ptr(q), d, kb, 2 * d, kb + d * e, 2 * d, ptr(d_out), d, ptr(dq), gb, gb + d * e,
-                                          B, sy, S, H, d // H, 0, p, _seed64(seed), site, _stream()))
-        return dq, dkv, None, None, None, None, None, None, None
+        return _cross_attn_bwd(ctx, "egx_small_attention", d_out)
+
+
+class SelfAttnTargetFn(torch.autograd.Function):
+    """SelfAttnSmallFn for up to 64 target tokens (egx_target_attention_*: dropout rows (b * H + h) * 64 + i)."""
+
+    @staticmethod
+    def forward(ctx, qkv, B: int, sy: int, H: int, causal: bool, p: float, seed: int, site: int):
+        return _self_attn_fwd(ctx, "egx_target_attention", qkv, B, sy, H, causal, p, seed, site)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return _self_attn_bwd(ctx, "egx_target_attention", d_out)
+
+
+class CrossAttnTargetFn(torch.autograd.Function):
+    """CrossAttnSmallFn for up to 64 target tokens (egx_target_attention_*)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, B: int, sy: int, S: int, H: int, p: float, seed: int, site: int):
+        return _cross_attn_fwd(ctx, "egx_target_attention", q, kv, B, sy, S, H, p, seed, site)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return _cross_attn_bwd(ctx, "egx_target_attention", d_out)

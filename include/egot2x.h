@@ -738,6 +738,27 @@ int egx_decoder_forced(const egx_dec_config* cfg, const int64_t* tokens /* DEVIC
                        int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, int R, int n_steps,
                        float* logits_out /* (n_steps, B * R, vocab) fp32 or NULL */, float* logprob_out /* (B, R, n_steps) fp32 or NULL; needs targets */,
                        void* workspace, void* stream);
+/* ---- ABI v18 (additions): attention of up to 64 target rows, forward and backward (training on long targets) ----
+ * The reference TRAINS its HOI action / LTA sequence decoders on 21- and 40-token targets (HOI/tasks/multitask/video_task_action.py:34-53:
+ * self.model(input, target_seq_verb[:, :-1], 'lta_verb') in training_step; HOI/models/lta/lta_models_seqdecoder.py:175-179);
+ * egx_small_attention_* stop at 8 query rows and stay as they are. These two have their semantics, operands and layout (fp32, rows at
+ * arbitrary strides >= H * dh, head h at columns [h * dh, (h + 1) * dh), self-attention passes the packed qkv rows three times,
+ * cross-attention q and the packed kv rows; rows need no alignment, nothing outside the (row, head column) windows is read or written)
+ * for 1 <= Sq <= 64, 1 <= Sk <= 1024, 1 <= dh <= 128, any B and H; causal != 0 needs Sq == Sk. fp32 on the VALU throughout. One
+ * workgroup of four waves per (b, h) walks the query rows in groups of 8, K / V chunked by 64 rows through LDS; no float atomics, every
+ * sum in a fixed order, a (b, h)'s result independent of B. The backward recomputes the probabilities and regenerates the mask (the
+ * forward saves nothing); dq / dk / dv use the strides of q / k / v and are overwritten at the call level, every (row, head column)
+ * exactly once per call (dk / dv: the owning thread assigns the first query group's sum and adds the later ones to it), so a zero-filled
+ * buffer is not assumed. p_drop > 0: dropout on the probabilities keyed like the composed decoder's sites (key layer site >> 8, site
+ * site & 0xff), row (b * H + h) * 64 + query, column key: the row stride is 64 here, 8 in egx_small_attention_*.
+ * Refused before any device work: Sq outside 1..64, Sk outside 1..1024, dh outside 1..128, causal with Sq != Sk, null pointers, a row
+ * stride below H * dh. */
+int egx_target_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                             int B, int Sq, int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site,
+                             void* stream);
+int egx_target_attention_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* d_o,
+                             int ldo, float* dq, float* dk, float* dv, int B, int Sq, int Sk, int H, int dh, int causal,
+                             float p_drop, uint64_t seed, uint32_t site, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place: backward of the ReLU fused into egx_linear_fwd(relu = 1). Wherever y is not > 0 (y = NaN, -0 and
  * -inf included) dy becomes +0; a denormal y > 0 keeps its dy. n = 0 touches nothing. */
 int egx_relu_mask(float* dy, const float* y, size_t n, void* stream);
