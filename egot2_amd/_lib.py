@@ -72,6 +72,15 @@ class TokenCe(C.Structure):
 
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
+EGX_LR_CONSTANT, EGX_LR_COSINE_ANNEALING, EGX_LR_WARMUP_COSINE, EGX_LR_WARMUP_LINEAR, EGX_LR_TABLE = 0, 1, 2, 3, 4
+EGX_LR_MAX_GROUPS = 16
+
+
+class LrSchedule(C.Structure):
+    """egx_lr_schedule: the per-step learning-rate factor f(k) that egx_lr_update evaluates on the device."""
+    _fields_ = [("kind", C.c_int), ("warmup_steps", C.c_int64), ("t_total", C.c_int64), ("T_max", C.c_int64), ("cycles", C.c_double),
+                ("factors", _fp), ("n", C.c_int64)]
+
 
 class DecConfig(C.Structure):
     _fields_ = [("d_model", C.c_int), ("n_heads", C.c_int), ("d_ff", C.c_int), ("n_layers", C.c_int), ("vocab", C.c_int),
@@ -197,6 +206,12 @@ SIGNATURES = {
     "egx_counter_add": (C.c_int, [_fp, C.c_int64, _fp]),
     "egx_adam_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_size_t, _fp, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_int, C.c_float, _fp]),
+    # ABI v18, additions: per-step learning-rate schedules and SGD for the captured step
+    "egx_lr_update": (C.c_int, [C.POINTER(LrSchedule), _fp, C.POINTER(C.c_double), C.c_int, _fp, _fp]),
+    "egx_adam_step_dev_lr": (C.c_int, [_fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float,
+                                       C.c_float, C.c_int, C.c_float, _fp]),
+    "egx_sgd_step": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                               C.c_float, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

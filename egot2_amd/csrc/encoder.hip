@@ -790,6 +790,27 @@ int egx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                      (hipStream_t)stream);
 }
 
+// ABI v18, additions: the arguments are checked on the host (train.hip lr_update / sgd_step), before any device work
+int egx_lr_update(const egx_lr_schedule* schedule, int64_t* step, const double* base_lr, int n_groups, float* lr_out, void* stream) {
+    EGX_CHECK(schedule, "lr_update: null schedule");
+    return lr_update(schedule->kind, schedule->warmup_steps, schedule->t_total, schedule->T_max, schedule->cycles, schedule->factors,
+                     schedule->n, step, base_lr, n_groups, lr_out, (hipStream_t)stream);
+}
+
+int egx_adam_step_dev_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const int64_t* step,
+                         const float* lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
+                         void* stream) {
+    EGX_CHECK(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam_step_dev_lr: invalid hyper-parameters (needs 0 <= beta < 1, eps >= 0)");
+    return adam_step_dev_lr(param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale,
+                            (hipStream_t)stream);
+}
+
+int egx_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n, const int64_t* step, const float* lr_dev, float lr,
+                 float momentum, float dampening, float weight_decay, int nesterov, float grad_scale, void* stream) {
+    return sgd_step(param, grad, momentum_buf, n, step, lr_dev, lr, momentum, dampening, weight_decay, nesterov, grad_scale,
+                    (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

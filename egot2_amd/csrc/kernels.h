@@ -118,6 +118,15 @@ int linear_ce_bwd(const float* x, const float* W, const float* dlogits, const fl
                   float* dW, float* db, void* scratch, hipStream_t st);
 int adam_step(float* p, const float* g, float* m, float* v, size_t n, const int64_t* step, float lr, float b1, float b2,
               float eps, float wd, int decoupled, float grad_scale, hipStream_t st);
+int adam_step_dev_lr(float* p, const float* g, float* m, float* v, size_t n, const int64_t* step, const float* lr, float b1, float b2,
+                     float eps, float wd, int decoupled, float grad_scale, hipStream_t st);
+// schedule kinds of lr_update (the values of the C ABI's EGX_LR_* enum) and its group limit (EGX_LR_MAX_GROUPS)
+enum LrKind { LR_CONSTANT = 0, LR_COSINE_ANNEALING = 1, LR_WARMUP_COSINE = 2, LR_WARMUP_LINEAR = 3, LR_TABLE = 4 };
+constexpr int LR_MAX_GROUPS = 16;
+int lr_update(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
+              int64_t* step, const double* base_lr, int n_groups, float* lr_out, hipStream_t st);
+int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+             float dampening, float wd, int nesterov, float grad_scale, hipStream_t st);
 
 // decoder.hip
 struct SmallAttnParams {

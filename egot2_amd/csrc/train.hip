@@ -8,6 +8,9 @@
 //                 HOI/tasks/multitask/video_task.py:624-626 (AdamW, lr 1e-4, wd 1e-4); semantics of torch.optim.Adam /
 //                 AdamW (bias-corrected, eps added outside the square root). The step counter lives in device memory so
 //                 that a captured hipGraph (forward + loss + backward + update) replays with the right bias correction.
+//   lr_update     HOI/optimizers/lta/lr_scheduler.py:11-41 (lr_factory, "interval": "step"): the per-step learning rate as a
+//                 function of the device step count, so that a replay runs the schedule too.
+//   sgd_step      HOI/optimizers/lta/optimizer.py:54-62 (torch.optim.SGD; HOI/configs/recognition/ts_ar.yaml:39-45).
 #include "common.h"
 #include "kernels.h"
 
@@ -380,41 +383,183 @@ int linear_ce_bwd(const float* x, const float* W, const float* dlogits, const fl
 
 // p, g, m, v: flat fp32 buffers of n elements (16-byte aligned). *step is the 1-based step count; the caller bumps it
 // with counter_add on the same stream before the update (race-free and replayable inside a hipGraph).
+// EGX_ADAM_UPDATE is the body of both kernels below, over their arguments p, g, m, v, n, step, b1, b2, eps, wd, decoupled, grad_scale and
+// a float `lr`: adam_kernel takes lr by value (egx_adam_step), adam_dev_lr_kernel reads the one lr_update_kernel left in device memory
+// (egx_adam_step_dev_lr). One text, so the arithmetic is the same expression for expression (as a macro and not an inlined function: that
+// changed adam_kernel's register allocation, and the by-value instances are to stay instruction-identical).
+#define EGX_ADAM_UPDATE                                                                              \
+    const float t = (float)*step;                                                                    \
+    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);                                    \
+    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);                                    \
+    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;                                         \
+    if (i >= n) return;                                                                              \
+    if (VEC && i + 4 <= n) {                                                                         \
+        float4 pv = *reinterpret_cast<float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i); \
+        float4 mv = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);       \
+        float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w};                    \
+        float ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};                    \
+_Pragma("unroll")                                                                                    \
+        for (int e = 0; e < 4; ++e) {                                                                \
+            float gg = ga[e] * grad_scale;                                                           \
+            if (decoupled) pa[e] *= 1.f - lr * wd; else gg += wd * pa[e];                            \
+            ma[e] = b1 * ma[e] + (1.f - b1) * gg;                                                    \
+            va[e] = b2 * va[e] + (1.f - b2) * gg * gg;                                               \
+            pa[e] -= step_size * ma[e] / (sqrtf(va[e]) * inv_sqrt_bc2 + eps);                        \
+        }                                                                                            \
+        *reinterpret_cast<float4*>(p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);                 \
+        *reinterpret_cast<float4*>(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);                 \
+        *reinterpret_cast<float4*>(v + i) = make_float4(va[0], va[1], va[2], va[3]);                 \
+    } else {                                                                                         \
+        for (size_t e = i + 4 < n ? i + 4 : n; i < e; ++i) {                                         \
+            float gg = g[i] * grad_scale, pp = p[i];                                                 \
+            if (decoupled) pp *= 1.f - lr * wd; else gg += wd * pp;                                  \
+            float mm = b1 * m[i] + (1.f - b1) * gg, vv = b2 * v[i] + (1.f - b2) * gg * gg;           \
+            m[i] = mm; v[i] = vv;                                                                    \
+            p[i] = pp - step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);                           \
+        }                                                                                            \
+    }
 template <bool VEC>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n, const int64_t* __restrict__ step,
                                                    float lr, float b1, float b2, float eps, float wd, int decoupled,
                                                    float grad_scale) {
-    const float t = (float)*step;
-    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
-    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
-    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    if (VEC && i + 4 <= n) {
-        float4 pv = *reinterpret_cast<float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i);
-        float4 mv = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
-        float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w};
-        float ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float gg = ga[e] * grad_scale;
-            if (decoupled) pa[e] *= 1.f - lr * wd; else gg += wd * pa[e];
-            ma[e] = b1 * ma[e] + (1.f - b1) * gg;
-            va[e] = b2 * va[e] + (1.f - b2) * gg * gg;
-            pa[e] -= step_size * ma[e] / (sqrtf(va[e]) * inv_sqrt_bc2 + eps);
+    EGX_ADAM_UPDATE
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_dev_lr_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, size_t n, const int64_t* __restrict__ step,
+                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd,
+                                                          int decoupled, float grad_scale) {
+    const float lr = *lr_dev;
+    EGX_ADAM_UPDATE
+}
+#undef EGX_ADAM_UPDATE
+
+// ---- per-step learning-rate schedule, on the device -------------------------------------------------------------------------
+// One thread: *step += 1 (what counter_add_kernel does for an unscheduled optimizer), then lr_out[g] = base_lr[g] * f(k) with
+// k = *step - 1, the 0-based index of the update about to run, and f the closed form of the reference's per-step scheduler
+// (HOI/optimizers/lta/lr_scheduler.py:11-41 lr_factory, :44-91 WarmupLinearSchedule / WarmupCosineSchedule.lr_lambda; torch's
+// CosineAnnealingLR with eta_min = 0; LambdaLR through a table), in fp64 and in the reference's operation order.
+struct LrUpdateArgs {
+    int kind, n_groups;
+    long long warmup, t_total, T_max, n_factors;
+    double cycles;
+    const double* factors;
+    double base_lr[LR_MAX_GROUPS];
+};
+__global__ void lr_update_kernel(int64_t* step, LrUpdateArgs a, float* lr_out) {
+#pragma clang fp contract(off)
+    const long long t = *step + 1;
+    *step = t;
+    const long long k = t > 1 ? t - 1 : 0;
+    const double pi = 3.141592653589793;
+    double f = 1.0;
+    if (a.kind == LR_COSINE_ANNEALING) {
+        f = 0.5 * (1.0 + cos(pi * (double)k / (double)a.T_max));
+    } else if (a.kind == LR_WARMUP_COSINE || a.kind == LR_WARMUP_LINEAR) {
+        const long long span = a.t_total - a.warmup > 1 ? a.t_total - a.warmup : 1;
+        if (k < a.warmup) {
+            f = (double)k / (double)(a.warmup > 1 ? a.warmup : 1);
+        } else if (a.kind == LR_WARMUP_COSINE) {
+            const double progress = (double)(k - a.warmup) / (double)span;
+            f = fmax(0.0, 0.5 * (1.0 + cos(pi * a.cycles * 2.0 * progress)));
+        } else {
+            f = fmax(0.0, (double)(a.t_total - k) / (double)span);
         }
-        *reinterpret_cast<float4*>(p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        *reinterpret_cast<float4*>(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *reinterpret_cast<float4*>(v + i) = make_float4(va[0], va[1], va[2], va[3]);
-    } else {
-        for (size_t e = i + 4 < n ? i + 4 : n; i < e; ++i) {
-            float gg = g[i] * grad_scale, pp = p[i];
-            if (decoupled) pp *= 1.f - lr * wd; else gg += wd * pp;
-            float mm = b1 * m[i] + (1.f - b1) * gg, vv = b2 * v[i] + (1.f - b2) * gg * gg;
-            m[i] = mm; v[i] = vv;
-            p[i] = pp - step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
+    } else if (a.kind == LR_TABLE) {
+        f = a.factors[k < a.n_factors - 1 ? k : a.n_factors - 1];
+    }
+    for (int g = 0; g < a.n_groups; ++g) lr_out[g] = (float)(a.base_lr[g] * f);
+}
+
+int lr_update(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
+              int64_t* step, const double* base_lr, int n_groups, float* lr_out, hipStream_t st) {
+    EGX_CHECK(step && base_lr && lr_out, "lr_update: null pointer argument");
+    EGX_CHECK(kind >= LR_CONSTANT && kind <= LR_TABLE, "lr_update: schedule kind %d outside 0..%d", kind, (int)LR_TABLE);
+    EGX_CHECK(n_groups >= 1 && n_groups <= LR_MAX_GROUPS, "lr_update: n_groups=%d outside 1..%d", n_groups, LR_MAX_GROUPS);
+    if (kind == LR_COSINE_ANNEALING) EGX_CHECK(T_max >= 1, "lr_update: T_max=%lld (needs T_max >= 1)", T_max);
+    if (kind == LR_WARMUP_COSINE || kind == LR_WARMUP_LINEAR) {
+        EGX_CHECK(warmup >= 0, "lr_update: warmup_steps=%lld (needs warmup_steps >= 0)", warmup);
+        EGX_CHECK(t_total >= 0, "lr_update: t_total=%lld (needs t_total >= 0)", t_total);
+    }
+    if (kind == LR_TABLE) EGX_CHECK(factors && n_factors >= 1, "lr_update: table of n=%lld factors at %p (needs n >= 1 and a pointer)", n_factors, (const void*)factors);
+    LrUpdateArgs a;
+    a.kind = kind; a.n_groups = n_groups; a.warmup = warmup; a.t_total = t_total; a.T_max = T_max; a.n_factors = n_factors;
+    a.cycles = cycles; a.factors = factors;
+    for (int g = 0; g < LR_MAX_GROUPS; ++g) a.base_lr[g] = g < n_groups ? base_lr[g] : 0.0;
+    hipLaunchKernelGGL(lr_update_kernel, dim3(1), dim3(1), 0, st, step, a, lr_out);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- SGD (torch.optim.SGD semantics) over one flat fp32 buffer --------------------------------------------------------------
+// HOI/optimizers/lta/optimizer.py:54-62 (torch.optim.SGD with momentum, dampening, weight decay and Nesterov from the SOLVER block;
+// HOI/configs/recognition/ts_ar.yaml:39-45 is momentum 0.9, weight decay 1e-4, Nesterov). 20 B per element (p, g, buf read; p, buf
+// written): 16-byte accesses on aligned buffers, at most SGD_MAX_BLOCKS workgroups striding over the rest of a large buffer.
+// buf == NULL: no momentum. The optimizer's first update (*step == 1) ASSIGNS buf = g, as torch does: what buf held is not read.
+constexpr int SGD_MAX_BLOCKS = 2048;
+struct SgdArgs {
+    float* p; const float* g; float* buf; size_t n;
+    const int64_t* step; const float* lr_dev;
+    float lr, mu, dampening, wd, grad_scale; int nesterov;
+};
+__device__ __forceinline__ float sgd_element(const SgdArgs& a, float lr, bool first, float pp, float gg, float* b) {
+    gg = gg * a.grad_scale + a.wd * pp;
+    if (b) {
+        *b = first ? gg : a.mu * *b + (1.f - a.dampening) * gg;
+        gg = a.nesterov ? gg + a.mu * *b : *b;
+    }
+    return pp - lr * gg;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void sgd_kernel(SgdArgs a) {
+    const float lr = a.lr_dev ? *a.lr_dev : a.lr;
+    const bool mom = a.buf != nullptr;
+    const bool first = mom && *a.step == 1;
+    const size_t stride = (size_t)gridDim.x * 256 * 4;
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < a.n; i += stride) {
+        if (VEC && i + 4 <= a.n) {
+            const float4 pv = *reinterpret_cast<const float4*>(a.p + i), gv = *reinterpret_cast<const float4*>(a.g + i);
+            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (mom && !first) bv = *reinterpret_cast<const float4*>(a.buf + i);
+            float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ba[4] = {bv.x, bv.y, bv.z, bv.w};
+            const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pa[e] = sgd_element(a, lr, first, pa[e], ga[e], mom ? &ba[e] : nullptr);
+            *reinterpret_cast<float4*>(a.p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);
+            if (mom) *reinterpret_cast<float4*>(a.buf + i) = make_float4(ba[0], ba[1], ba[2], ba[3]);
+        } else {
+            const size_t end = i + 4 < a.n ? i + 4 : a.n;
+            for (size_t j = i; j < end; ++j) {
+                float b = (mom && !first) ? a.buf[j] : 0.f;
+                a.p[j] = sgd_element(a, lr, first, a.p[j], a.g[j], mom ? &b : nullptr);
+                if (mom) a.buf[j] = b;
+            }
         }
     }
+}
+
+int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+             float dampening, float wd, int nesterov, float grad_scale, hipStream_t st) {
+    EGX_CHECK(p && g, "sgd_step: null pointer argument");
+    EGX_CHECK(lr_dev || lr >= 0.f, "sgd_step: lr=%g (needs lr >= 0)", (double)lr);
+    EGX_CHECK(mu >= 0.f, "sgd_step: momentum=%g (needs momentum >= 0)", (double)mu);
+    EGX_CHECK(wd >= 0.f, "sgd_step: weight_decay=%g (needs weight_decay >= 0)", (double)wd);
+    EGX_CHECK(dampening >= 0.f && dampening <= 1.f, "sgd_step: dampening=%g (needs 0 <= dampening <= 1)", (double)dampening);
+    EGX_CHECK(!nesterov || (mu > 0.f && dampening == 0.f), "sgd_step: Nesterov needs momentum > 0 and dampening == 0 (momentum=%g dampening=%g)", (double)mu, (double)dampening);
+    EGX_CHECK((mu == 0.f) == (buf == nullptr), "sgd_step: a momentum buffer goes with momentum > 0, and only with it");
+    EGX_CHECK(!buf || step, "sgd_step: momentum needs the device step count (null step)");
+    if (n == 0) return 0;
+    SgdArgs a;
+    a.p = p; a.g = g; a.buf = buf; a.n = n; a.step = step; a.lr_dev = lr_dev;
+    a.lr = lr; a.mu = mu; a.dampening = dampening; a.wd = wd; a.grad_scale = grad_scale; a.nesterov = nesterov;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf)) & 15) == 0;
+    size_t blocks = (n / 4 + 1 + 255) / 256;
+    if (blocks > SGD_MAX_BLOCKS) blocks = SGD_MAX_BLOCKS;
+    if (vec) hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    EGX_LAUNCH_CHECK();
+    return 0;
 }
 
 __global__ void counter_add_kernel(int64_t* c, int64_t inc) { *c += inc; }
@@ -434,6 +579,18 @@ int adam_step(float* p, const float* g, float* m, float* v, size_t n, const int6
     size_t blocks = (n / 4 + 1 + 255) / 256;
     if (vec) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
     else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int adam_step_dev_lr(float* p, const float* g, float* m, float* v, size_t n, const int64_t* step, const float* lr, float b1, float b2,
+                     float eps, float wd, int decoupled, float grad_scale, hipStream_t st) {
+    EGX_CHECK(p && g && m && v && step && lr, "adam_step_dev_lr: null pointer argument");
+    if (n == 0) return 0;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+    size_t blocks = (n / 4 + 1 + 255) / 256;
+    if (vec) hipLaunchKernelGGL(adam_dev_lr_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
+    else hipLaunchKernelGGL(adam_dev_lr_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
     EGX_LAUNCH_CHECK();
     return 0;
 }

@@ -6,10 +6,14 @@
 HOI/tasks/multitask/video_task.py:624-626: the translator's gradients already arrive as views of ONE flat buffer
 (functional._GradPacker), so the parameters are re-pointed into a flat buffer with the same layout and the whole
 update is a single launch per buffer, with the step count in device memory (hipGraph-replayable).
+`FusedSGD` mirrors `torch.optim.SGD` as HOI/optimizers/lta/optimizer.py:54-62 builds it on the same machinery, `LRSchedule` the reference's
+per-step learning-rate schedulers (HOI/optimizers/lta/lr_scheduler.py:11-41) evaluated on the device from that step count, and `construct_solver`
+restates construct_optimizer + lr_factory on both.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -29,23 +33,119 @@ class CrossEntropyLoss(nn.Module):
         return F_egx.weighted_cross_entropy(input, target, self.weight)
 
 
+class LRSchedule:
+    """Per-step learning-rate factor f(k), k = 0, 1, ... the 0-based index of the update (k = t - 1 for the optimizer's 1-based step count t):
+    the closed forms of the reference's per-step schedulers (HOI/optimizers/lta/lr_scheduler.py:11-41 lr_factory, "interval": "step"),
+    evaluated on the device by egx_lr_update from the optimizer's device-resident step count, so that a captured step (GraphedStep)
+    replays the schedule instead of the learning rate it was captured with. `factor(k)` is the same closed form on the host in fp64.
+
+        constant()                                   1                                            lr_policy "constant"
+        cosine_annealing(T_max)                      0.5 (1 + cos(pi k / T_max))                  "cosine" (CosineAnnealingLR, eta_min 0; periodic)
+        warmup_cosine(warmup_steps, t_total, cycles) WarmupCosineSchedule.lr_lambda               "cosine_warmup" (rises again beyond t_total)
+        warmup_linear(warmup_steps, t_total)         WarmupLinearSchedule.lr_lambda               "linear_warmup"
+        from_factors(seq) / from_lambda(fn, n_steps) seq[min(k, n - 1)]                           any LambdaLR (the get_epoch_lr policies)
+    """
+    KINDS = ("constant", "cosine_annealing", "warmup_cosine", "warmup_linear", "table")
+
+    def __init__(self, kind: str, warmup_steps: int = 0, t_total: int = 0, T_max: int = 1, cycles: float = 0.5, factors=None):
+        if kind not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind {kind!r} is not one of {self.KINDS}")
+        self.kind, self.warmup_steps, self.t_total, self.T_max, self.cycles = kind, int(warmup_steps), int(t_total), int(T_max), float(cycles)
+        self.factors = None if factors is None else [float(x) for x in factors]
+        if kind == "cosine_annealing" and self.T_max < 1:
+            raise ValueError(f"LRSchedule: T_max={self.T_max} (needs T_max >= 1)")
+        if kind in ("warmup_cosine", "warmup_linear") and (self.warmup_steps < 0 or self.t_total < 0):
+            raise ValueError(f"LRSchedule: warmup_steps={self.warmup_steps}, t_total={self.t_total} (both need to be >= 0)")
+        if kind == "table" and not self.factors:
+            raise ValueError("LRSchedule: a table needs at least one factor")
+        self._table_dev: Dict[torch.device, torch.Tensor] = {}
+
+    @classmethod
+    def constant(cls):
+        return cls("constant")
+
+    @classmethod
+    def cosine_annealing(cls, T_max: int):
+        return cls("cosine_annealing", T_max=T_max)
+
+    @classmethod
+    def warmup_cosine(cls, warmup_steps: int, t_total: int, cycles: float = 0.5):
+        return cls("warmup_cosine", warmup_steps=warmup_steps, t_total=t_total, cycles=cycles)
+
+    @classmethod
+    def warmup_linear(cls, warmup_steps: int, t_total: int):
+        return cls("warmup_linear", warmup_steps=warmup_steps, t_total=t_total)
+
+    @classmethod
+    def from_factors(cls, factors):
+        return cls("table", factors=factors)
+
+    @classmethod
+    def from_lambda(cls, fn, n_steps: int):
+        """The table fn(0), ..., fn(n_steps - 1) of a LambdaLR's function; steps beyond it keep the last factor."""
+        return cls("table", factors=[fn(k) for k in range(int(n_steps))])
+
+    def factor(self, k: int) -> float:
+        k = max(int(k), 0)
+        if self.kind == "constant":
+            return 1.0
+        if self.kind == "cosine_annealing":
+            return 0.5 * (1.0 + math.cos(math.pi * k / self.T_max))
+        if self.kind == "table":
+            return self.factors[min(k, len(self.factors) - 1)]
+        if k < self.warmup_steps:
+            return float(k) / float(max(1, self.warmup_steps))
+        span = float(max(1, self.t_total - self.warmup_steps))
+        if self.kind == "warmup_linear":
+            return max(0.0, float(self.t_total - k) / span)
+        progress = float(k - self.warmup_steps) / span
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * self.cycles * 2.0 * progress)))
+
+    def lr_at(self, k: int, base_lr: float) -> float:
+        """Learning rate of update k (fp64; the device holds it rounded to fp32)."""
+        return base_lr * self.factor(k)
+
+    def _struct(self, device) -> "_lib.LrSchedule":
+        """The C ABI's view; a table's device copy is made on first use (eagerly, before any capture: GraphedStep's warm-up steps do it)."""
+        s = _lib.LrSchedule(self.KINDS.index(self.kind), self.warmup_steps, self.t_total, self.T_max, self.cycles, None, 0)
+        if self.kind == "table":
+            device = torch.device(device)
+            t = self._table_dev.get(device)
+            if t is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("LRSchedule: the table's device copy cannot be made inside a capture; run one eager step first")
+                t = self._table_dev[device] = torch.tensor(self.factors, dtype=torch.float64, device=device)
+            s.factors, s.n = t.data_ptr(), t.numel()
+        return s
+
+
 class _Bucket:
-    __slots__ = ("sig", "param", "exp_avg", "exp_avg_sq", "numel", "members")
+    __slots__ = ("sig", "param", "exp_avg", "exp_avg_sq", "momentum_buffer", "keys", "numel", "members")
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """Adam (adamw=False) / AdamW (adamw=True) with torch.optim semantics, one launch per flat gradient buffer."""
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: gradients grouped by the flat buffer they are views of, the parameters re-pointed into a flat buffer
+    of the same layout (one launch per buffer), per-parameter state as views of per-bucket buffers, the step count in device memory, and -
+    with a `schedule` - the learning rates of the parameter groups in device memory, advanced by the same launch that bumps the count.
+    A subclass names its state buffers (_state_keys) and enqueues its update (_update)."""
 
-    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, adamw: bool = False):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
-            raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw))
+    def __init__(self, params, defaults, schedule: Optional[LRSchedule]):
+        super().__init__(params, defaults)
+        if schedule is not None and len(self.param_groups) > _lib.EGX_LR_MAX_GROUPS:
+            raise ValueError(f"{type(self).__name__}: a schedule serves at most {_lib.EGX_LR_MAX_GROUPS} parameter groups, got {len(self.param_groups)}")
+        self.schedule = schedule
         self._buckets: Dict[tuple, _Bucket] = {}
         self._step_dev: Optional[torch.Tensor] = None
+        self._lr_dev: Optional[torch.Tensor] = None
         self._resume_step = 0          # step count restored by load_state_dict before the device counter exists
 
-    def _make_bucket(self, sig, base: torch.Tensor, members) -> _Bucket:
+    def _state_keys(self, group) -> Tuple[str, ...]:
+        raise NotImplementedError
+
+    def _update(self, lib, b: _Bucket, gflat: torch.Tensor, group, lr_dev: Optional[int], stream):
+        raise NotImplementedError
+
+    def _make_bucket(self, sig, base: torch.Tensor, members, keys) -> _Bucket:
         b = _Bucket()
         b.sig = sig
         b.numel = base.numel()
@@ -57,44 +157,71 @@ class FusedAdam(torch.optim.Optimizer):
                 n = p.numel()
                 b.param[off:off + n].copy_(p.data.reshape(-1))
                 p.data = b.param[off:off + n].view(p.shape)
-        b.exp_avg = torch.zeros_like(b.param)
-        b.exp_avg_sq = torch.zeros_like(b.param)
+        b.keys = tuple(keys)
+        for key in b.keys:
+            setattr(b, key, torch.zeros_like(b.param))
         b.members = list(members)
         self._adopt_state(b)
         return b
 
     def _adopt_state(self, b: _Bucket):
-        """Make self.state[p] views of the bucket's moment buffers. Moments that are already there (restored by
+        """Make self.state[p] views of the bucket's state buffers. Values that are already there (restored by
         load_state_dict, or carried over from a bucket that had to be rebuilt) are copied in first, so a resumed run
-        continues from the saved exp_avg / exp_avg_sq instead of restarting them from zero."""
+        continues from the saved buffers instead of restarting them from zero."""
         for p, off in b.members:
             n = p.numel()
             old = self.state.get(p)
-            for key, buf in (("exp_avg", b.exp_avg), ("exp_avg_sq", b.exp_avg_sq)):
-                view = buf[off:off + n]
+            for key in b.keys:
+                view = getattr(b, key)[off:off + n]
                 if old is not None and torch.is_tensor(old.get(key)) and old[key].numel() == n \
                         and old[key].data_ptr() != view.data_ptr():
                     view.copy_(old[key].reshape(-1).to(view.device, view.dtype))
-            self.state[p] = {"step": self._step_dev, "exp_avg": b.exp_avg[off:off + n].view(p.shape),
-                             "exp_avg_sq": b.exp_avg_sq[off:off + n].view(p.shape)}
+            st = {"step": self._step_dev}
+            for key in b.keys:
+                st[key] = getattr(b, key)[off:off + n].view(p.shape)
+            self.state[p] = st
+
+    def _loaded_step(self) -> int:
+        steps = [st["step"] for st in self.state.values() if st.get("step") is not None]
+        return max((int(s.item()) if torch.is_tensor(s) else int(s)) for s in steps) if steps else 0
 
     def load_state_dict(self, state_dict):
-        """torch's Optimizer.load_state_dict replaces self.state with fresh copies; the real moments and the step count
+        """torch's Optimizer.load_state_dict replaces self.state with fresh copies; the real buffers and the step count
         live in the bucket buffers / the device counter, so push the loaded values back into them (buckets that do not
         exist yet pick them up in _make_bucket). Mirrors the optimizer resume of the reference's Lightning trainer
         (`trainer.fit(ckpt_path=...)`, HOI/scripts/pnr/train.py:57)."""
         super().load_state_dict(state_dict)
-        steps = [st["step"] for st in self.state.values() if st.get("step") is not None]
-        step = max((int(s.item()) if torch.is_tensor(s) else int(s)) for s in steps) if steps else 0
+        step = self._loaded_step()
         self._resume_step = step
         if self._step_dev is not None:
             self._step_dev.fill_(step)
         for b in self._buckets.values():
-            for p, off in b.members:        # a parameter WITHOUT loaded state starts from zero moments again (a state_dict taken before the first step)
+            for p, off in b.members:        # a parameter WITHOUT loaded state starts from zero buffers again (a state_dict taken before the first step)
                 if p not in self.state:
-                    b.exp_avg[off:off + p.numel()].zero_()
-                    b.exp_avg_sq[off:off + p.numel()].zero_()
+                    for key in b.keys:
+                        getattr(b, key)[off:off + p.numel()].zero_()
             self._adopt_state(b)
+
+    def current_lr(self) -> List[float]:
+        """The learning rate of every parameter group as the last enqueued step used it. With a schedule this reads the device values
+        (it synchronises: for logging, not for the loop); without one it is param_groups[g]["lr"]."""
+        if self.schedule is None or self._lr_dev is None:
+            return [float(g["lr"]) for g in self.param_groups]
+        return self._lr_dev[:len(self.param_groups)].tolist()
+
+    def _bump(self, lib, device, stream):
+        """Advance the device step count once per step(); with a schedule the same launch writes every group's learning rate."""
+        if self._step_dev is None:
+            self._step_dev = torch.full((), self._resume_step, dtype=torch.int64, device=device)
+        if self.schedule is None:
+            check(lib.egx_counter_add(ptr(self._step_dev), 1, stream))
+            return
+        if self._lr_dev is None:
+            self._lr_dev = torch.zeros(_lib.EGX_LR_MAX_GROUPS, dtype=torch.float32, device=device)
+        n = len(self.param_groups)
+        base = (C.c_double * n)(*[float(g["lr"]) for g in self.param_groups])     # read here: baked into a capture
+        sched = self.schedule._struct(device)
+        check(lib.egx_lr_update(C.byref(sched), ptr(self._step_dev), base, n, ptr(self._lr_dev), stream))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -112,37 +239,141 @@ class FusedAdam(torch.optim.Optimizer):
                 if g is None:
                     continue
                 if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
-                    raise ValueError("FusedAdam needs contiguous fp32 gradients on the GPU")
+                    raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients on the GPU")
                 key = g.untyped_storage().data_ptr()        # the flat buffer this gradient was carved out of: one view per buffer,
                 ent = by_base.get(key)                       # not one per parameter (25 tensor constructions per step on the TTM translator)
                 if ent is None:
                     ent = by_base[key] = (F_egx.flat_storage_view(g), [])
                 ent[1].append((p, g.storage_offset()))
             for base, members in by_base.values():
-                if self._step_dev is None:
-                    self._step_dev = torch.full((), self._resume_step, dtype=torch.int64, device=base.device)
                 if not bumped:
-                    check(lib.egx_counter_add(ptr(self._step_dev), 1, stream))
+                    self._bump(lib, base.device, stream)
                     bumped = True
                 sig = (gi,) + tuple((id(p), off) for p, off in members) + (base.numel(),)
                 b = self._buckets.get(sig)
                 if b is not None and any(p.data_ptr() != b.param.data_ptr() + 4 * off for p, off in members):
                     b = None                                 # somebody re-allocated a parameter: rebuild the bucket
                 if b is None:
-                    b = self._buckets[sig] = self._make_bucket(sig, base.reshape(-1), members)
+                    b = self._buckets[sig] = self._make_bucket(sig, base.reshape(-1), members, self._state_keys(group))
                 gflat = base.reshape(-1)
                 F_egx.note_weights_changed()       # (raw-pointer update: no version counter moves; packed-weight caches re-pack)
-                check(lib.egx_adam_step(ptr(b.param), ptr(gflat), ptr(b.exp_avg), ptr(b.exp_avg_sq), b.numel,
-                                        ptr(self._step_dev), group["lr"], group["betas"][0], group["betas"][1],
-                                        group["eps"], group["weight_decay"], int(group["adamw"]), 1.0, stream))
+                lr_dev = None if self.schedule is None else self._lr_dev.data_ptr() + 4 * gi
+                self._update(lib, b, gflat, group, lr_dev, stream)
         return loss
+
+
+class FusedAdam(_FlatOptimizer):
+    """Adam (adamw=False) / AdamW (adamw=True) with torch.optim semantics, one launch per flat gradient buffer.
+
+    `schedule` (an LRSchedule): the learning rate of update k is param_groups[g]["lr"] * schedule.factor(k), computed on the device from the
+    step count, so a captured step replays the schedule. param_groups[g]["lr"] stays the BASE learning rate; it is read when the step is
+    enqueued and is therefore baked into a capture: a changed base needs a new capture. Without a schedule nothing changes: the learning
+    rate goes to egx_adam_step by value."""
+
+    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, adamw: bool = False, schedule: Optional[LRSchedule] = None):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("invalid Adam hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw), schedule)
+
+    def _state_keys(self, group):
+        return ("exp_avg", "exp_avg_sq")
+
+    def _update(self, lib, b, gflat, group, lr_dev, stream):
+        if lr_dev is None:
+            check(lib.egx_adam_step(ptr(b.param), ptr(gflat), ptr(b.exp_avg), ptr(b.exp_avg_sq), b.numel,
+                                    ptr(self._step_dev), group["lr"], group["betas"][0], group["betas"][1],
+                                    group["eps"], group["weight_decay"], int(group["adamw"]), 1.0, stream))
+        else:
+            check(lib.egx_adam_step_dev_lr(ptr(b.param), ptr(gflat), ptr(b.exp_avg), ptr(b.exp_avg_sq), b.numel,
+                                           ptr(self._step_dev), lr_dev, group["betas"][0], group["betas"][1],
+                                           group["eps"], group["weight_decay"], int(group["adamw"]), 1.0, stream))
+
+
+class FusedSGD(_FlatOptimizer):
+    """torch.optim.SGD (momentum, dampening, weight decay, Nesterov) with one launch per flat gradient buffer: the optimizer the reference's
+    construct_optimizer builds for OPTIMIZING_METHOD "sgd" (HOI/optimizers/lta/optimizer.py:54-62; HOI/configs/recognition/ts_ar.yaml:39-45).
+
+    state[p] holds `momentum_buffer` (a view of the bucket's buffer; absent with momentum 0) and `step` (the device step count). The first
+    update ASSIGNS momentum_buffer = g, decided on the device by step == 1, as torch does on a missing buffer; with a zeroed buffer and
+    dampening 0 that equals the recurrence bit for bit. `schedule` and param_groups[g]["lr"]: as for FusedAdam.
+
+    load_state_dict accepts this class's state dicts and torch.optim.SGD's. A torch state dict has momentum buffers and no step count: the
+    count then starts at 1, so the first-update rule does not fire and the loaded buffers are continued (and a schedule continues at k = 1:
+    torch keeps its position in the scheduler's own state dict, not here)."""
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, schedule: Optional[LRSchedule] = None):
+        if lr < 0 or momentum < 0 or weight_decay < 0 or not (0 <= dampening <= 1):
+            raise ValueError("invalid SGD hyper-parameters")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov), schedule)
+
+    def _state_keys(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _loaded_step(self) -> int:
+        step = super()._loaded_step()
+        if step == 0 and any(torch.is_tensor(st.get("momentum_buffer")) and st.get("step") is None for st in self.state.values()):
+            return 1            # torch.optim.SGD's state: buffers without a count
+        return step
+
+    def _update(self, lib, b, gflat, group, lr_dev, stream):
+        buf = b.momentum_buffer if b.keys else None
+        check(lib.egx_sgd_step(ptr(b.param), ptr(gflat), ptr(buf), b.numel, ptr(self._step_dev), lr_dev, group["lr"], group["momentum"],
+                               group["dampening"], group["weight_decay"], int(group["nesterov"]), 1.0, stream))
+
+
+SOLVER_POLICIES = ("cosine", "constant", "cosine_warmup", "linear_warmup")
+
+
+def construct_solver(model, cfg, steps_in_epoch: int, lr_policy: Optional[str] = None, lr_lambda=None):
+    """-> (optimizer, schedule): the reference's construct_optimizer (HOI/optimizers/lta/optimizer.py:15-73) plus lr_factory
+    (HOI/optimizers/lta/lr_scheduler.py:11-41) restated on the fused optimizers, reading the reference's config fields: cfg.SOLVER
+    .OPTIMIZING_METHOD ("sgd" | "adam" | "adamw"), .BASE_LR, .MOMENTUM, .DAMPENING, .NESTEROV, .WEIGHT_DECAY, .LR_POLICY, .WARMUP_STEPS,
+    .MAX_EPOCH and cfg.BN.WEIGHT_DECAY. Two parameter groups as there: names containing "bn" take BN.WEIGHT_DECAY (the group may be empty),
+    the rest SOLVER.WEIGHT_DECAY. `lr_policy` (default cfg.SOLVER.LR_POLICY): "cosine", "constant", "cosine_warmup", "linear_warmup";
+    any other policy is a LambdaLR in the reference and needs `lr_lambda`, the function of the 0-based step it hands LambdaLR (for the
+    get_epoch_lr policies: lambda step: get_epoch_lr(step / steps_in_epoch, cfg)), tabulated over MAX_EPOCH * steps_in_epoch steps."""
+    S = cfg.SOLVER
+    bn, rest = [], []
+    for name, p in model.named_parameters():
+        (bn if "bn" in name else rest).append(p)
+    groups = [{"params": bn, "weight_decay": cfg.BN.WEIGHT_DECAY}, {"params": rest, "weight_decay": S.WEIGHT_DECAY}]
+    total = int(S.MAX_EPOCH) * int(steps_in_epoch)
+    policy = S.LR_POLICY if lr_policy is None else lr_policy
+    if policy == "cosine":
+        schedule = LRSchedule.cosine_annealing(total)
+    elif policy == "constant":
+        schedule = LRSchedule.constant()
+    elif policy == "cosine_warmup":
+        schedule = LRSchedule.warmup_cosine(S.WARMUP_STEPS, total)
+    elif policy == "linear_warmup":
+        schedule = LRSchedule.warmup_linear(S.WARMUP_STEPS, total)
+    elif lr_lambda is not None:
+        schedule = LRSchedule.from_lambda(lr_lambda, max(total, 1))
+    else:
+        raise ValueError(f"construct_solver: lr_policy {policy!r} is not one of {SOLVER_POLICIES}; pass lr_lambda=<function of the step> "
+                         "for a LambdaLR policy")
+    method = S.OPTIMIZING_METHOD
+    if method == "sgd":
+        opt = FusedSGD(groups, lr=S.BASE_LR, momentum=S.MOMENTUM, dampening=S.DAMPENING, weight_decay=S.WEIGHT_DECAY,
+                       nesterov=S.NESTEROV, schedule=schedule)
+    elif method == "adam":
+        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), weight_decay=S.WEIGHT_DECAY, schedule=schedule)
+    elif method == "adamw":
+        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), adamw=True, schedule=schedule)   # the groups' weight decays override the default
+    else:
+        raise NotImplementedError(f"Does not support {method} optimizer")
+    return opt, schedule
 
 
 class GraphedStep:
     """One training step — forward, loss, backward and (optionally) the optimizer update — captured ONCE as a hipGraph and replayed.
 
     The library only enqueues kernels on the current stream and keeps what changes from step to step in device memory (the dropout seed after
-    `model.enable_device_seed()`, FusedAdam's step count), so a replay is exact training work with fresh masks; what the capture removes is the
+    `model.enable_device_seed()`, the optimizer's step count and - with an `LRSchedule` - its learning rates), so a replay is exact training work with fresh masks; what the capture removes is the
     host side of the step (Python, the autograd engine's worker thread, a dozen launches: 0.54 - 0.90 ms per step on the bench configuration with
     FusedAdam against 0.41 ms of GPU time). This is the
     loop `bench.py` times, packaged for a training script:

@@ -506,6 +506,50 @@ int egx_counter_add(int64_t* counter, int64_t inc, void* stream);
 int egx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const int64_t* step,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
                   void* stream);
+/* ---- ABI v18, additions: per-step learning-rate schedules and SGD for the captured step ---------------------------
+ * The reference schedules the learning rate per optimizer step ("interval": "step",
+ * HOI/optimizers/lta/lr_scheduler.py:11-41 lr_factory; HOI/tasks/pnr/video_task.py:74-95,
+ * HOI/tasks/multitask/video_task.py:265-287). A learning rate passed by value is baked into a captured hipGraph, so
+ * the schedule is evaluated on the device from the step count instead. f(k), k = 0, 1, ... the 0-based update index:
+ *   EGX_LR_CONSTANT          1                                                        (LambdaLR(lambda x: 1), :19-20)
+ *   EGX_LR_COSINE_ANNEALING  0.5 (1 + cos(pi k / T_max))                              (CosineAnnealingLR, eta_min 0, :15-18)
+ *   EGX_LR_WARMUP_COSINE     k / max(1, warmup_steps) while k < warmup_steps, then
+ *                            max(0, 0.5 (1 + cos(pi cycles 2 (k - warmup_steps) / max(1, t_total - warmup_steps))))
+ *                            (WarmupCosineSchedule.lr_lambda, :82-91; not clamped beyond t_total: the reference's rises again)
+ *   EGX_LR_WARMUP_LINEAR     the same warm-up, then max(0, (t_total - k) / max(1, t_total - warmup_steps))
+ *                            (WarmupLinearSchedule.lr_lambda, :57-64)
+ *   EGX_LR_TABLE             factors[min(k, n - 1)], fp64 in device memory: any LambdaLR (get_epoch_lr policies, :35-38) */
+enum { EGX_LR_CONSTANT = 0, EGX_LR_COSINE_ANNEALING = 1, EGX_LR_WARMUP_COSINE = 2, EGX_LR_WARMUP_LINEAR = 3, EGX_LR_TABLE = 4 };
+#define EGX_LR_MAX_GROUPS 16
+typedef struct egx_lr_schedule {
+    int kind;              /* EGX_LR_* */
+    int64_t warmup_steps;  /* warm-up kinds: >= 0 */
+    int64_t t_total;       /* warm-up kinds: >= 0 */
+    int64_t T_max;         /* cosine annealing: >= 1 */
+    double cycles;         /* warm-up cosine: the reference's default is 0.5 */
+    const double* factors; /* table: n factors, device memory */
+    int64_t n;             /* table: >= 1 */
+} egx_lr_schedule;
+/* One single-thread launch: *step += 1 (the work of egx_counter_add), k = *step - 1, lr_out[g] = (float)(base_lr[g] * f(k))
+ * for g < n_groups (1 .. EGX_LR_MAX_GROUPS); f in fp64. step and lr_out are device memory, base_lr is host memory and
+ * is copied into the launch (a captured graph keeps the values it was captured with). */
+int egx_lr_update(const egx_lr_schedule* schedule, int64_t* step, const double* base_lr, int n_groups, float* lr_out,
+                  void* stream);
+/* egx_adam_step with the learning rate read from device memory (*lr, as egx_lr_update left it): the same arithmetic. */
+int egx_adam_step_dev_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const int64_t* step,
+                         const float* lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                         float grad_scale, void* stream);
+/* One torch.optim.SGD update of n fp32 elements:
+ *   g = grad * grad_scale + weight_decay * p;
+ *   momentum > 0:  buf = g on the optimizer's first update (*step == 1: an assignment, buf's contents are not read),
+ *                  else buf = momentum * buf + (1 - dampening) * g;   g = nesterov ? g + momentum * buf : buf;
+ *   p -= lr * g    with lr = *lr_dev, or `lr` when lr_dev == NULL.
+ * momentum == 0 takes momentum_buf == NULL (and step may be NULL); Nesterov needs momentum > 0 and dampening == 0.
+ * Replaces torch.optim.SGD as HOI/optimizers/lta/optimizer.py:54-62 builds it (HOI/configs/recognition/ts_ar.yaml:39-45:
+ * momentum 0.9, weight decay 1e-4; Nesterov and dampening 0 by HOI/configs/recognition/defaults.py:467-476). */
+int egx_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n, const int64_t* step, const float* lr_dev,
+                 float lr, float momentum, float dampening, float weight_decay, int nesterov, float grad_scale,
+                 void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over

@@ -37,6 +37,11 @@ def parser():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f32s"])
     p.add_argument("--seed", type=int, default=0)
+    # optional solver recipe (the HOI translators' SOLVER block, HOI/optimizers/lta/lr_scheduler.py:11-41): given together, the optimizer and
+    # its per-step schedule come from train.construct_solver; without them the run is the TTM recipe above, unchanged
+    p.add_argument("--optimizer", default=None, choices=["sgd", "adam", "adamw"])
+    p.add_argument("--lr-policy", dest="lr_policy", default=None, choices=["cosine", "constant", "cosine_warmup", "linear_warmup"])
+    p.add_argument("--warmup_steps", type=int, default=4)
     return p
 
 
@@ -52,7 +57,16 @@ def main(argv=None):
     args.hidden_dim2 = 512
     model = hhi_ttm.build_model(args).to(dev).set_compute(args.dtype).train()     # TalkingToMe2Loader.__init__ :20
     criterion = CrossEntropyLoss(weight=torch.FloatTensor([0.266, 0.734])).to(dev)    # :21-22
-    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)   # configure_optimizers :62-64
+    if (args.optimizer is None) != (args.lr_policy is None):
+        raise SystemExit("--optimizer and --lr-policy go together")
+    if args.optimizer is None:
+        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)   # configure_optimizers :62-64
+    else:
+        from types import SimpleNamespace as NS
+        from egot2_amd.train import construct_solver
+        solver = NS(OPTIMIZING_METHOD=args.optimizer, BASE_LR=args.lr, MOMENTUM=0.9, DAMPENING=0.0, NESTEROV=True,
+                    WEIGHT_DECAY=args.weight_decay, LR_POLICY=args.lr_policy, WARMUP_STEPS=args.warmup_steps, MAX_EPOCH=1)
+        optimizer, _ = construct_solver(model, NS(SOLVER=solver, BN=NS(WEIGHT_DECAY=0.0)), steps_in_epoch=args.steps)
     K = 2 if args.model.endswith("2Task") else 3
     g = torch.Generator().manual_seed(1234)
     # a fixed synthetic "dataset" of 4 batches whose label depends on the features, so that the loss can go down
@@ -69,7 +83,7 @@ def main(argv=None):
         loss.backward()
         optimizer.step()
         losses.append(loss.item())
-        print(f"step {step:3d}  train_loss {losses[-1]:.4f}", flush=True)
+        print(f"step {step:3d}  train_loss {losses[-1]:.4f}" + (f"  lr {optimizer.current_lr()[-1]:.3e}" if args.optimizer else ""), flush=True)
     model.eval()
     with torch.no_grad():
         feats, label = batches[0]
