@@ -49,7 +49,7 @@ struct DecAttnParams {
     int B, H, Sq, Sk, causal;
     float scale;
     uint64_t drop_key; uint32_t drop_thresh; float drop_inv;
-    // ragged memories (dec_attn_ragged_train): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
+    // ragged memories (dec_attn_ragged_train, RAGGED kernels): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
     // of k / v, its query / output rows c * Sq + i. Sk = the longest memory of the launch.
     const int* mtab; const int* clips;
 };
@@ -91,316 +91,11 @@ __device__ __forceinline__ void store8(void* base, size_t idx, const float (&a)[
     }
 }
 
-template <int DH, bool BWD, bool F32>
+// RAGGED (ragged memories, bf16 operands): wave (i, h) serves clip p.clips[i] with its own memory rows [mtab[2c], + mtab[2c + 1]); its query / output
+// rows and its dropout rows are those of the clip's batch position, as in a uniform batch. A flag on the kernel template, so that the uniform
+// kernels keep their code: see the note at wide_attn_fwd_kernel (wide_attn.hip).
+template <int DH, bool BWD, bool F32, bool RAGGED>
 __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnParams p) {
-    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
-    __shared__ float sQ[4][DA_MAXQ][DH];        // query rows (fp32)
-    __shared__ float sG[4][DA_MAXQ][DH];        // dO rows (backward)
-    __shared__ float sP[4][DA_MAXQ][64];        // probabilities after dropout
-    __shared__ float sD[4][DA_MAXQ][64];        // dS (backward)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bh = blockIdx.x * 4 + wave;
-    if (bh >= p.B * p.H) return;                // (no barrier below: every wave works alone)
-    const int b = bh / p.H, h = bh % p.H;
-    const int Sq = p.Sq, Sk = p.Sk;
-    const bool kv_lane = lane < Sk;
-    // key row of this lane
-    float kr[DH], vr[BWD ? DH : 1];
-    {
-        const size_t krow = ((size_t)b * Sk + (kv_lane ? lane : 0)) * p.ldk + h * DH;
-#pragma unroll
-        for (int c = 0; c < DH; c += 8) {
-            float t8[8];
-            load8<F32>(p.k, krow + c, t8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) kr[c + e] = t8[e];
-        }
-        if constexpr (BWD) {
-            const size_t vrow = ((size_t)b * Sk + (kv_lane ? lane : 0)) * p.ldv + h * DH;
-#pragma unroll
-            for (int c = 0; c < DH; c += 8) {
-                float t8[8];
-                load8<F32>(p.v, vrow + c, t8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vr[c + e] = t8[e];
-            }
-        }
-    }
-    // query (and dO) rows -> LDS
-    for (int i = lane; i < Sq * DH; i += 64) {
-        const int r = i / DH, c = i - r * DH;
-        sQ[wave][r][c] = load1<F32>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
-        if constexpr (BWD) sG[wave][r][c] = bf1(p.d_o[((size_t)b * Sq + r) * p.ldo + h * DH + c]);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float ds_reg[BWD ? DA_MAXQ : 1];            // dS[i][lane]
-#pragma unroll
-    for (int i = 0; i < DA_MAXQ; ++i) {         // (static indices: a runtime-indexed register array would live in scratch)
-        if (i >= Sq) break;
-        const bool live = kv_lane && !(p.causal && lane > i);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < DH; c += 4) {
-            const float4 qv = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
-            s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
-        }
-        s = live ? s * p.scale : -INFINITY;
-        const float m = wmax64(s);
-        const float e = live ? __expf(s - m) : 0.f;
-        const float prob = e / wsum64d(e);
-        float mask = 1.f;
-        if (p.drop_thresh) mask = drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)lane, p.drop_thresh, p.drop_inv);
-        sP[wave][i][lane] = prob * mask;
-        if constexpr (BWD) {
-            float dp = 0.f;
-#pragma unroll
-            for (int c = 0; c < DH; c += 4) {
-                const float4 gv = *reinterpret_cast<const float4*>(&sG[wave][i][c]);
-                dp += (gv.x * vr[c] + gv.y * vr[c + 1]) + (gv.z * vr[c + 2] + gv.w * vr[c + 3]);
-            }
-            dp = live ? dp * mask : 0.f;
-            const float delta = wsum64d(prob * dp);
-            const float dsv = live ? prob * (dp - delta) * p.scale : 0.f;
-            ds_reg[i] = dsv;
-            sD[wave][i][lane] = dsv;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (!BWD) {
-        // lane c: O[i][c] = sum_j P[i][j] V[j][c]
-        if (lane < DH) {
-            float acc[DA_MAXQ];
-#pragma unroll
-            for (int i = 0; i < DA_MAXQ; ++i) acc[i] = 0.f;
-            const size_t v0 = (size_t)b * Sk * p.ldv + h * DH + lane;
-            for (int j = 0; j < Sk; ++j) {
-                const float vv = load1<F32>(p.v, v0 + (size_t)j * p.ldv);
-#pragma unroll
-                for (int i = 0; i < DA_MAXQ; ++i)
-                    if (i < Sq) acc[i] += sP[wave][i][j] * vv;
-            }
-#pragma unroll
-            for (int i = 0; i < DA_MAXQ; ++i)
-                if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + lane] = f2bf(acc[i]);
-        }
-    } else {
-        // lane j: dK[j][:] = sum_i dS[i][j] Q[i][:]  (row store)
-        if (kv_lane) {
-            const size_t dk0 = ((size_t)b * Sk + lane) * p.ldk + h * DH;
-#pragma unroll
-            for (int c = 0; c < DH; c += 8) {
-                float a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < DA_MAXQ; ++i) {
-                    if (i >= Sq) break;
-                    const float4 q0 = *reinterpret_cast<const float4*>(&sQ[wave][i][c]);
-                    const float4 q1 = *reinterpret_cast<const float4*>(&sQ[wave][i][c + 4]);
-                    const float dsv = ds_reg[i];
-                    a[0] += dsv * q0.x; a[1] += dsv * q0.y; a[2] += dsv * q0.z; a[3] += dsv * q0.w;
-                    a[4] += dsv * q1.x; a[5] += dsv * q1.y; a[6] += dsv * q1.z; a[7] += dsv * q1.w;
-                }
-                store8<F32>(p.dk, dk0 + c, a);
-            }
-        }
-        // lane c: dQ[i][c] = sum_j dS[i][j] K[j][c];  dV[j][c] = sum_i P[i][j] dO[i][c]
-        if (lane < DH) {
-            float accq[DA_MAXQ], go[DA_MAXQ];
-#pragma unroll
-            for (int i = 0; i < DA_MAXQ; ++i) { accq[i] = 0.f; go[i] = i < Sq ? sG[wave][i][lane] : 0.f; }
-            const size_t k0 = (size_t)b * Sk * p.ldk + h * DH + lane, dv0 = (size_t)b * Sk * p.ldv + h * DH + lane;
-            for (int j = 0; j < Sk; ++j) {
-                const float kk = load1<F32>(p.k, k0 + (size_t)j * p.ldk);
-                float av = 0.f;
-#pragma unroll
-                for (int i = 0; i < DA_MAXQ; ++i)
-                    if (i < Sq) { accq[i] += sD[wave][i][j] * kk; av += sP[wave][i][j] * go[i]; }
-                store1<F32>(p.dv, dv0 + (size_t)j * p.ldv, av);
-            }
-#pragma unroll
-            for (int i = 0; i < DA_MAXQ; ++i)
-                if (i < Sq) store1<F32>(p.dq, ((size_t)b * Sq + i) * p.ldq + h * DH + lane, accq[i]);
-        }
-    }
-}
-
-// Cross-attention onto a memory of more than 64 tokens (EgoT2-g HHI on real-length TTM / ASD sequences: up to 3 x 150): one
-// workgroup of four waves per (clip, head); K and V stream through ONE 64-row LDS buffer (fp32, padded rows) chunk by chunk,
-// all Sq x Sk probabilities stay in LDS. bf16 operands and gradients; same dropout keying as dec_attn_kernel.
-constexpr int DAL_MAXK = 1024;
-template <int DH, bool BWD>
-__global__ __launch_bounds__(256) void dec_attn_long_kernel(DecAttnParams p) {
-    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
-    constexpr int LDK = DH + 1;
-    extern __shared__ float dal_sm[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int Sq = p.Sq, Sk = p.Sk, SKP = (Sk + 63) & ~63;
-    float* Cs = dal_sm;                     // K or V chunk [64][DH + 1]
-    float* Qs = Cs + 64 * LDK;
-    float* Gs = Qs + DA_MAXQ * DH;
-    float* Ps = Gs + DA_MAXQ * DH;          // [Sq][SKP]
-    float* Ds = Ps + DA_MAXQ * SKP;         // backward only
-    const bf16_t* kb = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * Sk * p.ldk + h * DH;
-    const bf16_t* vb = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * Sk * p.ldv + h * DH;
-    auto stage = [&](const bf16_t* src, int ld, int j0) {
-        __syncthreads();
-        for (int i = tid; i < 64 * (DH / 8); i += 256) {
-            const int j = i / (DH / 8), c = (i - j * (DH / 8)) * 8;
-            float t8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (j0 + j < Sk) load8<false>(src, (size_t)(j0 + j) * ld + c, t8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) Cs[j * LDK + c + e] = t8[e];
-        }
-        __syncthreads();
-    };
-    for (int i = tid; i < Sq * DH; i += 256) {
-        const int r = i / DH, c = i - r * DH;
-        Qs[i] = load1<false>(p.q, ((size_t)b * Sq + r) * p.ldq + h * DH + c);
-        if constexpr (BWD) Gs[i] = bf1(p.d_o[((size_t)b * Sq + r) * p.ldo + h * DH + c]);
-    }
-    for (int j0 = 0; j0 < Sk; j0 += 64) {          // scores: wave w owns queries w, w + 4; lane = key within the chunk
-        stage(kb, p.ldk, j0);
-        for (int i = wave; i < Sq; i += 4) {
-            float sc = 0.f;
-#pragma unroll
-            for (int c = 0; c < DH; ++c) sc += Qs[i * DH + c] * Cs[lane * LDK + c];
-            Ps[i * SKP + j0 + lane] = j0 + lane < Sk ? sc * p.scale : -INFINITY;
-        }
-    }
-    __syncthreads();
-    for (int i = wave; i < Sq; i += 4) {
-        float m = -INFINITY;
-        for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
-        m = wmax64(m);
-        float sum = 0.f;
-        for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
-        sum = 1.f / wsum64d(sum);
-        for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;
-    }
-    auto keep = [&](int i, int j) { return p.drop_thresh ? drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)j, p.drop_thresh, p.drop_inv) : 1.f; };
-    constexpr int NE = DA_MAXQ * DH / 256;          // (query, column) accumulators per thread: 1 (DH = 32) or 2 (DH = 64)
-    float acc[NE];
-#pragma unroll
-    for (int u = 0; u < NE; ++u) acc[u] = 0.f;
-    if constexpr (BWD) {
-        for (int j0 = 0; j0 < Sk; j0 += 64) {      // dP = dO V^T
-            stage(vb, p.ldv, j0);
-            for (int i = wave; i < Sq; i += 4) {
-                float dp = 0.f;
-#pragma unroll
-                for (int c = 0; c < DH; ++c) dp += Gs[i * DH + c] * Cs[lane * LDK + c];
-                Ds[i * SKP + j0 + lane] = dp;
-            }
-        }
-        __syncthreads();
-        for (int i = wave; i < Sq; i += 4) {
-            float delta = 0.f;
-            for (int j = lane; j < SKP; j += 64) {
-                const float dp = Ds[i * SKP + j] * keep(i, j);
-                Ds[i * SKP + j] = dp;
-                delta += Ps[i * SKP + j] * dp;
-            }
-            delta = wsum64d(delta);
-            for (int j = lane; j < SKP; j += 64) {
-                const float pr = Ps[i * SKP + j];
-                Ds[i * SKP + j] = pr * (Ds[i * SKP + j] - delta) * p.scale;
-                Ps[i * SKP + j] = pr * keep(i, j);
-            }
-        }
-        bf16_t* dkb = reinterpret_cast<bf16_t*>(p.dk) + (size_t)b * Sk * p.ldk + h * DH;
-        bf16_t* dvb = reinterpret_cast<bf16_t*>(p.dv) + (size_t)b * Sk * p.ldv + h * DH;
-        for (int j0 = 0; j0 < Sk; j0 += 64) {      // dQ += dS K; dK = dS^T Q, dV = P^T dO for the chunk's keys
-            stage(kb, p.ldk, j0);
-#pragma unroll
-            for (int u = 0; u < NE; ++u) {
-                const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-                if (i < Sq) {
-                    float a = 0.f;
-                    for (int j = 0; j < 64; ++j) a += Ds[i * SKP + j0 + j] * Cs[j * LDK + c];
-                    acc[u] += a;
-                }
-            }
-            for (int e = tid; e < 64 * (DH / 8); e += 256) {
-                const int j = e / (DH / 8), c = (e - j * (DH / 8)) * 8;
-                if (j0 + j < Sk) {
-                    float ak[8] = {0, 0, 0, 0, 0, 0, 0, 0}, av[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    for (int i = 0; i < Sq; ++i) {
-                        const float dsv = Ds[i * SKP + j0 + j], pv = Ps[i * SKP + j0 + j];
-#pragma unroll
-                        for (int x = 0; x < 8; ++x) { ak[x] += dsv * Qs[i * DH + c + x]; av[x] += pv * Gs[i * DH + c + x]; }
-                    }
-                    store8<false>(dkb, (size_t)(j0 + j) * p.ldk + c, ak);
-                    store8<false>(dvb, (size_t)(j0 + j) * p.ldv + c, av);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NE; ++u) {
-            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-            if (i < Sq) store1<false>(p.dq, ((size_t)b * Sq + i) * p.ldq + h * DH + c, acc[u]);
-        }
-    } else {
-        if (p.drop_thresh) {
-            for (int i = wave; i < Sq; i += 4)
-                for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= keep(i, j);
-        }
-        for (int j0 = 0; j0 < Sk; j0 += 64) {
-            stage(vb, p.ldv, j0);
-#pragma unroll
-            for (int u = 0; u < NE; ++u) {
-                const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-                if (i < Sq) {
-                    float a = 0.f;
-                    for (int j = 0; j < 64; ++j) a += Ps[i * SKP + j0 + j] * Cs[j * LDK + c];
-                    acc[u] += a;
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NE; ++u) {
-            const int e = tid + u * 256, i = e / DH, c = e - i * DH;
-            if (i < Sq) p.o[((size_t)b * Sq + i) * p.ldo + h * DH + c] = f2bf(acc[u]);
-        }
-    }
-}
-template <int DH, bool BWD>
-int dec_attn_long(const DecAttnParams& p, hipStream_t st) {
-    auto lds = [](int Sk) { return ((size_t)64 * (DH + 1) + (size_t)2 * DA_MAXQ * DH + (size_t)2 * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
-    static bool attr = false;
-    if (!attr) {
-        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_attn_long_kernel<DH, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
-        attr = true;
-    }
-    hipLaunchKernelGGL((dec_attn_long_kernel<DH, BWD>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
-    EGX_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool BWD>
-int dec_attn(DecAttnParams p, int dh, bool f32, hipStream_t st) {
-    p.scale = 1.f / sqrtf((float)dh);
-    if (p.Sk > DA_MAXK) {
-        EGX_CHECK(!f32 && !p.causal && (dh == 32 || dh == 64), "decoder attention: a memory of %d tokens needs bf16 operands and head dim 32 / 64", p.Sk);
-        return dh == 64 ? dec_attn_long<64, BWD>(p, st) : dec_attn_long<32, BWD>(p, st);
-    }
-    const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
-    if (dh == 64 && !f32) hipLaunchKernelGGL((dec_attn_kernel<64, BWD, false>), grid, block, 0, st, p);
-    else if (dh == 32 && !f32) hipLaunchKernelGGL((dec_attn_kernel<32, BWD, false>), grid, block, 0, st, p);
-    else if (dh == 64) hipLaunchKernelGGL((dec_attn_kernel<64, BWD, true>), grid, block, 0, st, p);
-    else if (dh == 32) hipLaunchKernelGGL((dec_attn_kernel<32, BWD, true>), grid, block, 0, st, p);
-    else EGX_CHECK(false, "decoder attention: head dim %d (32 or 64)", dh);
-    EGX_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- ragged memories (egx_decoder_ragged_fwd, egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd) ----
-// dec_attn_kernel (bf16 operands) and dec_attn_long_kernel for clip p.clips[i] with its own memory rows [mtab[2c], + mtab[2c + 1]), forward with
-// dropout (none at drop_thresh 0: the inference call) and backward. Separate copies: the uniform kernels keep their code and register allocation.
-template <int DH, bool BWD>
-__global__ __launch_bounds__(256) void dec_attn_ragged_train_kernel(DecAttnParams p) {
-    constexpr bool F32 = false;
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
     __shared__ float sQ[4][DA_MAXQ][DH];        // query rows (fp32)
     __shared__ float sG[4][DA_MAXQ][DH];        // dO rows (backward)
@@ -409,9 +104,9 @@ __global__ __launch_bounds__(256) void dec_attn_ragged_train_kernel(DecAttnParam
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wi = blockIdx.x * 4 + wave;
     if (wi >= p.B * p.H) return;                // (no barrier below: every wave works alone)
-    const int b = p.clips[wi / p.H], h = wi % p.H, bh = b * p.H + h;       // (dropout rows: the clip's batch position, as the uniform kernel)
-    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1];
-    const size_t m0 = (size_t)p.mtab[2 * b];
+    const int b = RAGGED ? p.clips[wi / p.H] : wi / p.H, h = wi % p.H, bh = RAGGED ? b * p.H + h : wi;      // bh: the dropout rows
+    const int Sq = p.Sq, Sk = RAGGED ? p.mtab[2 * b + 1] : p.Sk;
+    const size_t m0 = RAGGED ? (size_t)p.mtab[2 * b] : (size_t)b * Sk;                                      // the clip's first memory row
     const bool kv_lane = lane < Sk;
     // key row of this lane
     float kr[DH], vr[BWD ? DH : 1];
@@ -534,15 +229,21 @@ __global__ __launch_bounds__(256) void dec_attn_ragged_train_kernel(DecAttnParam
     }
 }
 
-template <int DH, bool BWD>
-__global__ __launch_bounds__(256) void dec_attn_long_ragged_train_kernel(DecAttnParams p) {
+// Cross-attention onto a memory of more than 64 tokens (EgoT2-g HHI on real-length TTM / ASD sequences: up to 3 x 150): one
+// workgroup of four waves per (clip, head); K and V stream through ONE 64-row LDS buffer (fp32, padded rows) chunk by chunk,
+// all Sq x Sk probabilities stay in LDS. bf16 operands and gradients; same dropout keying as dec_attn_kernel.
+constexpr int DAL_MAXK = 1024;
+template <int DH, bool BWD, bool RAGGED>
+__global__ __launch_bounds__(256) void dec_attn_long_kernel(DecAttnParams p) {
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
     constexpr int LDK = DH + 1;
     extern __shared__ float dal_sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = p.clips[blockIdx.x / p.H], h = blockIdx.x % p.H, bh = b * p.H + h;
-    const int Sq = p.Sq, Sk = p.mtab[2 * b + 1], SKP = (Sk + 63) & ~63;
-    const size_t m0 = (size_t)p.mtab[2 * b];
+    // (the ragged side divides the unsigned workgroup index, the uniform side the signed one, as each always did)
+    const int b = RAGGED ? p.clips[blockIdx.x / p.H] : (int)blockIdx.x / p.H, h = RAGGED ? blockIdx.x % p.H : (int)blockIdx.x % p.H;
+    const int bh = RAGGED ? b * p.H + h : blockIdx.x;                                                       // the dropout rows
+    const int Sq = p.Sq, Sk = RAGGED ? p.mtab[2 * b + 1] : p.Sk, SKP = (Sk + 63) & ~63;
+    const size_t m0 = RAGGED ? (size_t)p.mtab[2 * b] : (size_t)b * Sk;                                      // the clip's first memory row
     float* Cs = dal_sm;                     // K or V chunk [64][DH + 1]
     float* Qs = Cs + 64 * LDK;
     float* Gs = Qs + DA_MAXQ * DH;
@@ -671,35 +372,54 @@ __global__ __launch_bounds__(256) void dec_attn_long_ragged_train_kernel(DecAttn
         }
     }
 }
+template <int DH, bool BWD, bool RAGGED>
+int dec_attn_long(const DecAttnParams& p, hipStream_t st) {
+    // Cs, Qs, Gs, Ps and Ds. The ragged forward does not reserve Ds (backward only), which would cut the workgroups per CU at long memories; the
+    // uniform forward still does.
+    constexpr int NPS = RAGGED && !BWD ? 1 : 2;
+    auto lds = [](int Sk) { return ((size_t)64 * (DH + 1) + (size_t)2 * DA_MAXQ * DH + (size_t)NPS * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
+    static bool attr = false;
+    if (!attr) {
+        EGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_attn_long_kernel<DH, BWD, RAGGED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
+        attr = true;
+    }
+    hipLaunchKernelGGL((dec_attn_long_kernel<DH, BWD, RAGGED>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
 
-// over ragged memories: forward with dropout on the probabilities (BWD = false) and backward (dq for the clip's Sq target rows, dk / dv for the
-// clip's own memory rows, written packed: every memory row belongs to one clip). One launch per kernel class: p.clips / p.B the clips of the
-// class, p.Sk their longest memory.
+template <bool BWD>
+int dec_attn(DecAttnParams p, int dh, bool f32, hipStream_t st) {
+    p.scale = 1.f / sqrtf((float)dh);
+    if (p.Sk > DA_MAXK) {
+        EGX_CHECK(!f32 && !p.causal && (dh == 32 || dh == 64), "decoder attention: a memory of %d tokens needs bf16 operands and head dim 32 / 64", p.Sk);
+        return dh == 64 ? dec_attn_long<64, BWD, false>(p, st) : dec_attn_long<32, BWD, false>(p, st);
+    }
+    const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
+    if (dh == 64 && !f32) hipLaunchKernelGGL((dec_attn_kernel<64, BWD, false, false>), grid, block, 0, st, p);
+    else if (dh == 32 && !f32) hipLaunchKernelGGL((dec_attn_kernel<32, BWD, false, false>), grid, block, 0, st, p);
+    else if (dh == 64) hipLaunchKernelGGL((dec_attn_kernel<64, BWD, true, false>), grid, block, 0, st, p);
+    else if (dh == 32) hipLaunchKernelGGL((dec_attn_kernel<32, BWD, true, false>), grid, block, 0, st, p);
+    else EGX_CHECK(false, "decoder attention: head dim %d (32 or 64)", dh);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- ragged memories (egx_decoder_ragged_fwd, egx_decoder_ragged_train_fwd / egx_decoder_ragged_bwd) ----
+// dec_attn_kernel (bf16 operands) and dec_attn_long_kernel with RAGGED set: forward with dropout on the probabilities (none at drop_thresh 0: the
+// inference call) and backward (dq for the clip's Sq target rows, dk / dv for the clip's own memory rows, written packed: every memory row
+// belongs to one clip). One launch per kernel class: p.clips / p.B the clips of the class, p.Sk their longest memory.
 template <bool BWD>
 int dec_attn_ragged_train(DecAttnParams p, int dh, bool long_class, hipStream_t st) {
     EGX_CHECK(dh == 32 || dh == 64, "decoder attention: head dim %d (32 or 64)", dh);
     EGX_CHECK(!p.causal && p.Sk >= 1 && p.Sk <= DAL_MAXK && p.mtab && p.clips, "decoder attention (ragged training): bad arguments");
     if (p.B <= 0) return 0;
     p.scale = 1.f / sqrtf((float)dh);
-    if (!long_class) {
-        EGX_CHECK(p.Sk <= DA_MAXK, "decoder attention (ragged): short class with Sk = %d", p.Sk);
-        const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
-        if (dh == 64) hipLaunchKernelGGL((dec_attn_ragged_train_kernel<64, BWD>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((dec_attn_ragged_train_kernel<32, BWD>), grid, block, 0, st, p);
-        EGX_LAUNCH_CHECK();
-        return 0;
-    }
-    // Cs, Qs, Gs, Ps and (backward only) Ds: the forward does not reserve Ds, which would cut the workgroups per CU at long memories
-    auto lds = [dh](int Sk) { return ((size_t)64 * (dh + 1) + (size_t)2 * DA_MAXQ * dh + (size_t)(BWD ? 2 : 1) * DA_MAXQ * ((Sk + 63) & ~63)) * sizeof(float); };
-    static bool attr[2] = {false, false};
-    const void* fn = dh == 64 ? reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<64, BWD>)
-                              : reinterpret_cast<const void*>(&dec_attn_long_ragged_train_kernel<32, BWD>);
-    if (!attr[dh == 64]) {
-        EGX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(DAL_MAXK)));
-        attr[dh == 64] = true;
-    }
-    if (dh == 64) hipLaunchKernelGGL((dec_attn_long_ragged_train_kernel<64, BWD>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
-    else hipLaunchKernelGGL((dec_attn_long_ragged_train_kernel<32, BWD>), dim3(p.B * p.H), dim3(256), lds(p.Sk), st, p);
+    if (long_class) return dh == 64 ? dec_attn_long<64, BWD, true>(p, st) : dec_attn_long<32, BWD, true>(p, st);
+    EGX_CHECK(p.Sk <= DA_MAXK, "decoder attention (ragged): short class with Sk = %d", p.Sk);
+    const dim3 grid(cdiv(p.B * p.H, 4)), block(256);
+    if (dh == 64) hipLaunchKernelGGL((dec_attn_kernel<64, BWD, false, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((dec_attn_kernel<32, BWD, false, true>), grid, block, 0, st, p);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -1099,7 +819,7 @@ namespace {
 // ragged memories (egx_decoder_ragged_fwd): the device copy of the per-clip table and the clips of the two cross-attention kernel classes
 struct DecRagged {
     const int* mtab;                // [B][2]: first memory row, memory rows
-    const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_ragged_train_kernel), class 1: the chunked kernel
+    const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_kernel), class 1: the chunked kernel
 };
 
 int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const float* memory, const float* emb, const float* pe,

@@ -26,6 +26,10 @@ constexpr int LN_MAXV = 4;      // float4 per lane: d <= 1024
 
 }  // namespace
 
+// MAPPED (ragged batches: wide_ln_fwd_mapped, wide_ln_bwd_mapped): the output row and the positional row (backward: the upstream row, and with it
+// the row key of the dropout behind the LayerNorm) come from row maps of the batch table instead of the T / S / off remap. A flag on the kernel
+// template, so that the uniform kernels keep their code: see the note at wide_attn_fwd_kernel (wide_attn.hip).
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
         }
         const float rstd = rsqrtf(wsum64(ss) * inv_d + p.eps);
         if (p.stats && lane == 0) *reinterpret_cast<float2*>(p.stats + 2 * (size_t)row) = make_float2(mean, rstd);
-        const int t_in = row % p.T, orow = remap(row, p.T, p.S, p.off);
+        const int t_in = MAPPED ? (p.src_map ? p.src_map[row] % p.T : 0) : row % p.T, orow = MAPPED ? p.out_map[row] : remap(row, p.T, p.S, p.off);
         const float* pos = p.pos ? p.pos + (size_t)t_in * p.pos_stride : nullptr;
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
@@ -77,84 +81,32 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
     }
 }
 
-// ragged batches (wide_ln_fwd_mapped): the kernel above with the output row and the positional row read from the row maps of the batch
-// table (a separate copy: a shared inlined body changed the uniform kernel's register allocation and occupancy)
-__global__ __launch_bounds__(256) void wide_ln_fwd_mapped_kernel(WideLnFwdParams p) {
-    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int d = p.d, nv = (d + 255) / 256;
-    const float inv_d = 1.f / (float)d;
-    for (int row = blockIdx.x * 4 + wave; row < p.rows; row += gridDim.x * 4) {
-        const float* x = p.x + (size_t)row * d;
-        float4 v[LN_MAXV];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < LN_MAXV; ++i) {
-            int c = 4 * lane + 256 * i;
-            v[i] = make_float4(0, 0, 0, 0);
-            if (i < nv && c < d) v[i] = *reinterpret_cast<const float4*>(x + c);
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-        const float mean = wsum64(s) * inv_d;
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < LN_MAXV; ++i) {
-            int c = 4 * lane + 256 * i;
-            if (i < nv && c < d) {
-                float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, dd = v[i].w - mean;
-                ss += (a * a + b * b) + (cc * cc + dd * dd);
-            }
-        }
-        const float rstd = rsqrtf(wsum64(ss) * inv_d + p.eps);
-        if (p.stats && lane == 0) *reinterpret_cast<float2*>(p.stats + 2 * (size_t)row) = make_float2(mean, rstd);
-        const int t_in = p.src_map ? p.src_map[row] % p.T : 0, orow = p.out_map[row];
-        const float* pos = p.pos ? p.pos + (size_t)t_in * p.pos_stride : nullptr;
-#pragma unroll
-        for (int i = 0; i < LN_MAXV; ++i) {
-            int c = 4 * lane + 256 * i;
-            if (i < nv && c < d) {
-                float4 w = *reinterpret_cast<const float4*>(p.w + c), b = *reinterpret_cast<const float4*>(p.b + c);
-                float o[4] = {(v[i].x - mean) * rstd * w.x + b.x, (v[i].y - mean) * rstd * w.y + b.y,
-                              (v[i].z - mean) * rstd * w.z + b.z, (v[i].w - mean) * rstd * w.w + b.w};
-                if (p.add_vec) { float4 a = *reinterpret_cast<const float4*>(p.add_vec + c); o[0] += a.x; o[1] += a.y; o[2] += a.z; o[3] += a.w; }
-                if (pos) { float4 a = *reinterpret_cast<const float4*>(pos + c); o[0] += a.x; o[1] += a.y; o[2] += a.z; o[3] += a.w; }
-                if (p.drop_thresh) {
-                    float ds[4];
-                    drop_scale4(dkey, (uint32_t)orow, (uint32_t)c, p.drop_thresh, p.drop_inv, ds);
-                    o[0] *= ds[0]; o[1] *= ds[1]; o[2] *= ds[2]; o[3] *= ds[3];
-                }
-                if (p.y32) *reinterpret_cast<float4*>(p.y32 + (size_t)orow * d + c) = make_float4(o[0], o[1], o[2], o[3]);
-                if (p.y16) *reinterpret_cast<uint2*>(p.y16 + (size_t)orow * d + c) = make_uint2(pk2(o[0], o[1]), pk2(o[2], o[3]));
-            }
-        }
-    }
+template <bool MAPPED>
+static int launch_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
+    if (p.rows <= 0) return 0;
+    int blocks = cdiv(p.rows, 4);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(wide_ln_fwd_kernel<MAPPED>, dim3(blocks), dim3(256), 0, st, p);
+    EGX_LAUNCH_CHECK();
+    return 0;
 }
 
 int wide_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
     EGX_CHECK(p.x && p.w && p.b && (p.y32 || p.y16), "wide_ln_fwd: null pointer");
     EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_fwd: d=%d unsupported", p.d);
-    if (p.rows <= 0) return 0;
-    int blocks = cdiv(p.rows, 4);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wide_ln_fwd_kernel, dim3(blocks), dim3(256), 0, st, p);
-    EGX_LAUNCH_CHECK();
-    return 0;
+    return launch_ln_fwd<false>(p, st);
 }
 
 int wide_ln_fwd_mapped(const WideLnFwdParams& p, hipStream_t st) {
     EGX_CHECK(p.x && p.w && p.b && (p.y32 || p.y16) && p.out_map, "wide_ln_fwd_mapped: null pointer");
     EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0 && p.T >= 1, "wide_ln_fwd_mapped: d=%d unsupported", p.d);
     EGX_CHECK(!p.pos || p.src_map, "wide_ln_fwd_mapped: a positional table needs the source-row map");
-    if (p.rows <= 0) return 0;
-    int blocks = cdiv(p.rows, 4);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wide_ln_fwd_mapped_kernel, dim3(blocks), dim3(256), 0, st, p);
-    EGX_LAUNCH_CHECK();
-    return 0;
+    return launch_ln_fwd<true>(p, st);
 }
 
 // Each block owns a CONTIGUOUS range of rows; its four waves interleave over it and keep per-column partial sums in
 // registers, combined through LDS at the end: partials[block][k][d], k = 0 d(gamma), 1 d(beta), 2 column sums of dx16.
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int rows_per_block) {
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull, okey = p.out_thresh ? resolve_key(p.out_key) : 0ull;
     __shared__ float red[3][4][1024];
@@ -170,98 +122,7 @@ __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int
     }
     const int r0 = blockIdx.x * rows_per_block, r1 = min(p.rows, r0 + rows_per_block);
     for (int row = r0 + wave; row < r1; row += 4) {
-        const int orow = remap(row, p.T, p.S, p.off);
-        const float* dy = p.dy + (size_t)orow * d;
-        const float* pre = p.pre + (size_t)row * d;
-        const float2 st2 = *reinterpret_cast<const float2*>(p.stats + 2 * (size_t)row);
-        const float mean = st2.x, rstd = st2.y;
-        float4 gq[LN_MAXV], xh[LN_MAXV];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < LN_MAXV; ++i) {
-            int c = 4 * lane + 256 * i;
-            gq[i] = xh[i] = make_float4(0, 0, 0, 0);
-            if (i < nv && c < d) {
-                float4 g = *reinterpret_cast<const float4*>(dy + c);
-                if (p.drop_thresh) {
-                    float ds[4];
-                    drop_scale4(dkey, (uint32_t)orow, (uint32_t)c, p.drop_thresh, p.drop_inv, ds);
-                    g.x *= ds[0]; g.y *= ds[1]; g.z *= ds[2]; g.w *= ds[3];
-                }
-                float4 x = *reinterpret_cast<const float4*>(pre + c);
-                x.x = (x.x - mean) * rstd; x.y = (x.y - mean) * rstd; x.z = (x.z - mean) * rstd; x.w = (x.w - mean) * rstd;
-                aw[i].x += g.x * x.x; aw[i].y += g.y * x.y; aw[i].z += g.z * x.z; aw[i].w += g.w * x.w;
-                ab[i].x += g.x; ab[i].y += g.y; ab[i].z += g.z; ab[i].w += g.w;
-                g.x *= wv[i].x; g.y *= wv[i].y; g.z *= wv[i].z; g.w *= wv[i].w;
-                s1 += (g.x + g.y) + (g.z + g.w);
-                s2 += (g.x * x.x + g.y * x.y) + (g.z * x.z + g.w * x.w);
-                gq[i] = g; xh[i] = x;
-            }
-        }
-        s1 = wsum64(s1) * inv_d;
-        s2 = wsum64(s2) * inv_d;
-#pragma unroll
-        for (int i = 0; i < LN_MAXV; ++i) {
-            int c = 4 * lane + 256 * i;
-            if (i < nv && c < d) {
-                float o[4] = {rstd * (gq[i].x - s1 - xh[i].x * s2), rstd * (gq[i].y - s1 - xh[i].y * s2),
-                              rstd * (gq[i].z - s1 - xh[i].z * s2), rstd * (gq[i].w - s1 - xh[i].w * s2)};
-                float m[4] = {o[0], o[1], o[2], o[3]};
-                if (p.out_thresh) {
-                    float ds[4];
-                    drop_scale4(okey, (uint32_t)row, (uint32_t)c, p.out_thresh, p.out_inv, ds);
-                    m[0] *= ds[0]; m[1] *= ds[1]; m[2] *= ds[2]; m[3] *= ds[3];
-                }
-                if (p.dx32) {
-                    const float* q = p.mask_dx32 ? m : o;
-                    *reinterpret_cast<float4*>(p.dx32 + (size_t)row * d + c) = make_float4(q[0], q[1], q[2], q[3]);
-                }
-                if (p.dx16) {
-                    uint2 u = make_uint2(pk2(m[0], m[1]), pk2(m[2], m[3]));
-                    *reinterpret_cast<uint2*>(p.dx16 + (size_t)row * d + c) = u;
-                    // the bias gradient is the column sum of the operand AS STORED (bf16-rounded)
-                    ac[i].x += bff(u.x & 0xffffu); ac[i].y += bff(u.x >> 16); ac[i].z += bff(u.y & 0xffffu); ac[i].w += bff(u.y >> 16);
-                } else {
-                    ac[i].x += m[0]; ac[i].y += m[1]; ac[i].z += m[2]; ac[i].w += m[3];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        int c = 4 * lane + 256 * i;
-        if (i < nv && c < d) {
-            *reinterpret_cast<float4*>(&red[0][wave][c]) = aw[i];
-            *reinterpret_cast<float4*>(&red[1][wave][c]) = ab[i];
-            *reinterpret_cast<float4*>(&red[2][wave][c]) = ac[i];
-        }
-    }
-    __syncthreads();
-    float* out = p.partials + (size_t)blockIdx.x * 3 * d;
-    for (int i = threadIdx.x; i < 3 * d; i += 256) {
-        int k = i / d, c = i % d;
-        out[i] = (red[k][0][c] + red[k][1][c]) + (red[k][2][c] + red[k][3][c]);
-    }
-}
-
-// ragged batches (wide_ln_bwd_mapped): the kernel above with the upstream row (and with it the row key of the dropout behind the LayerNorm) read
-// from a row map of the batch table: the mirror of wide_ln_fwd_mapped_kernel's out_map. A separate copy, as that kernel.
-__global__ __launch_bounds__(256) void wide_ln_bwd_mapped_kernel(WideLnBwdParams p, int rows_per_block) {
-    const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull, okey = p.out_thresh ? resolve_key(p.out_key) : 0ull;
-    __shared__ float red[3][4][1024];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int d = p.d, nv = (d + 255) / 256;
-    const float inv_d = 1.f / (float)d;
-    float4 aw[LN_MAXV], ab[LN_MAXV], ac[LN_MAXV], wv[LN_MAXV];
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        aw[i] = ab[i] = ac[i] = wv[i] = make_float4(0, 0, 0, 0);
-        int c = 4 * lane + 256 * i;
-        if (i < nv && c < d) wv[i] = *reinterpret_cast<const float4*>(p.w + c);
-    }
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(p.rows, r0 + rows_per_block);
-    for (int row = r0 + wave; row < r1; row += 4) {
-        const int orow = p.dy_map[row];
+        const int orow = MAPPED ? p.dy_map[row] : remap(row, p.T, p.S, p.off);
         const float* dy = p.dy + (size_t)orow * d;
         const float* pre = p.pre + (size_t)row * d;
         const float2 st2 = *reinterpret_cast<const float2*>(p.stats + 2 * (size_t)row);
@@ -416,15 +277,15 @@ static int ln_bwd_blocks(int rows) {
 }
 size_t wide_ln_bwd_scratch(int rows, int d) { return (size_t)ln_bwd_blocks(rows) * 3 * d * sizeof(float); }
 
-int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer) {
-    EGX_CHECK(p.dy && p.pre && p.stats && p.w && scratch, "wide_ln_bwd: null pointer");
-    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_bwd: d=%d unsupported", p.d);
+// the mapped call never defers its reduction (defer = null)
+template <bool MAPPED>
+static int launch_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer) {
     if (p.rows <= 0) return 0;
     p.blocks = ln_bwd_blocks(p.rows);
     p.partials = (float*)scratch;
     const int rpb = cdiv(p.rows, p.blocks);
     p.blocks = cdiv(p.rows, rpb);
-    hipLaunchKernelGGL(wide_ln_bwd_kernel, dim3(p.blocks), dim3(256), 0, st, p, rpb);
+    hipLaunchKernelGGL(wide_ln_bwd_kernel<MAPPED>, dim3(p.blocks), dim3(256), 0, st, p, rpb);
     if (defer && (p.dw || p.db || p.dbias || p.dadd)) {
         EGX_LAUNCH_CHECK();
         WideRowReduceDesc q;
@@ -439,20 +300,16 @@ int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceB
     return 0;
 }
 
+int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer) {
+    EGX_CHECK(p.dy && p.pre && p.stats && p.w && scratch, "wide_ln_bwd: null pointer");
+    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_bwd: d=%d unsupported", p.d);
+    return launch_ln_bwd<false>(p, scratch, st, defer);
+}
+
 int wide_ln_bwd_mapped(WideLnBwdParams p, void* scratch, hipStream_t st) {
     EGX_CHECK(p.dy && p.pre && p.stats && p.w && scratch && p.dy_map, "wide_ln_bwd_mapped: null pointer");
     EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_bwd_mapped: d=%d unsupported", p.d);
-    if (p.rows <= 0) return 0;
-    p.blocks = ln_bwd_blocks(p.rows);
-    p.partials = (float*)scratch;
-    const int rpb = cdiv(p.rows, p.blocks);
-    p.blocks = cdiv(p.rows, rpb);
-    hipLaunchKernelGGL(wide_ln_bwd_mapped_kernel, dim3(p.blocks), dim3(256), 0, st, p, rpb);
-    if (p.dw || p.db || p.dbias || p.dadd)
-        hipLaunchKernelGGL(wide_ln_bwd_reduce_kernel, dim3(cdiv(3 * p.d, 64)), dim3(1024), 0, st, (const float*)p.partials, p.blocks,
-                           p.d, p.dw, p.db, p.dbias, p.dadd);
-    EGX_LAUNCH_CHECK();
-    return 0;
+    return launch_ln_bwd<true>(p, scratch, st, nullptr);
 }
 
 // ---- bf16 column sums ---------------------------------------------------------------------------------------------------

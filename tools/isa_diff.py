@@ -1,5 +1,5 @@
 """Per-kernel comparison of two gfx950 device assemblies (hipcc <build flags> --cuda-device-only -S file.hip): has a refactor left the ISA alone?
-usage: python tools/isa_diff.py <parent.s> <new.s> [--show N]
+usage: python tools/isa_diff.py <parent.s> <new.s> [--show N] [--rename REGEX=REPLACEMENT]...
 
 Each file is split at its function labels (up to .Lfunc_end), comments and directives are dropped and the local labels (.LBB<n>_<m>, .Ltmp<n>, ...)
 are renumbered in order of first appearance, so that a kernel that merely moved inside its translation unit compares equal. Per symbol of the parent:
@@ -10,6 +10,9 @@ are renumbered in order of first appearance, so that a kernel that merely moved 
   renamed    a symbol of the new file only whose mangled name differs from a parent-only symbol of the same base name just in its template arguments
               (a dropped argument that had one value left); the pair is then compared like any other
   gone / NEW  symbols of one file only
+--rename REGEX=REPLACEMENT (repeatable, applied in order with re.sub to the PARENT's mangled names before anything is paired) says which symbol
+of the new file a parent symbol became when the refactor changed its base name or added a template argument: two kernels merged under a flag,
+say, which the `renamed` pairing cannot tell apart when several instantiations of one base name gain the same argument.
 Exit status 1 when any symbol is DIFFERENT or NEW."""
 import collections
 import difflib
@@ -68,8 +71,17 @@ def main(argv):
     show = int(argv[argv.index("--show") + 1]) if "--show" in argv else 12
     pa, pb = [x for x in argv[1:] if x.endswith(".s")][:2]
     a, b = functions(pa), functions(pb)
+    renames = [argv[i + 1].split("=", 1) for i, x in enumerate(argv[:-1]) if x == "--rename"]
+    was = collections.OrderedDict()       # name after the renames -> the parent's symbol
+    for k in a:
+        new = k
+        for rx, to in renames:
+            new = re.sub(rx, to, new)
+        assert new not in was, f"--rename maps {was.get(new)} and {k} onto one name"
+        was[new] = k
+    a = collections.OrderedDict((new, a[k]) for new, k in was.items())
     bad = 0
-    print(f"# {pa}: {len(a)} functions; {pb}: {len(b)} functions")
+    print(f"# {pa}: {len(a)} functions; {pb}: {len(b)} functions" + "".join(f" --rename '{rx}={to}'" for rx, to in renames))
     # a new-only symbol takes the place of the parent-only symbol of the same base name whose stream it matches best
     gone, renamed = [k for k in a if k not in b], {}
     for k in [k for k in b if k not in a]:
@@ -85,7 +97,7 @@ def main(argv):
             continue
         kind, delta = classify(fa, b[kb])
         note = f"  ({len(fa)} instructions" + (f", {len(delta)} compare / branch lines of opposite polarity)" if kind == "inverted" else ")")
-        print(f"{kind:<10} {k}{note}" + (f"\n  renamed -> {kb}" if kb != k else ""))
+        print(f"{kind:<10} {k}{note}" + (f"\n  --rename of {was[k]}" if was[k] != k else "") + (f"\n  renamed -> {kb}" if kb != k else ""))
         if kind == "DIFFERENT":
             bad += 1
             for x in delta[:show]:
