@@ -32,7 +32,7 @@ int make_plan(const egx_config* cfg, const egx_segment* segs, int B, Plan& pl) {
     EGX_CHECK(cfg && segs, "null config/segments");
     EGX_CHECK(cfg->n_segments >= 1 && cfg->n_segments <= EGX_MAX_SEGMENTS, "n_segments=%d out of range", cfg->n_segments);
     EGX_CHECK(cfg->n_layers >= 0 && cfg->n_layers <= 64, "n_layers=%d out of range", cfg->n_layers);
-    EGX_CHECK(cfg->d_model > 0 && cfg->d_model % 4 == 0 && cfg->d_model <= 1024, "d_model=%d unsupported (multiple of 4, <= 1024)", cfg->d_model);
+    EGX_CHECK(cfg->d_model > 0 && cfg->d_model % 4 == 0 && cfg->d_model <= 2048, "d_model=%d unsupported (multiple of 4, <= 1024; <= 2048 with compute bf16, wide path)", cfg->d_model);
     EGX_CHECK(cfg->n_heads > 0 && cfg->d_model % cfg->n_heads == 0, "d_model=%d not divisible by n_heads=%d", cfg->d_model, cfg->n_heads);
     EGX_CHECK(cfg->d_ff > 0 && cfg->d_ff % 4 == 0, "d_ff=%d must be a positive multiple of 4", cfg->d_ff);
     EGX_CHECK(cfg->compute == EGX_F32 || cfg->compute == EGX_BF16 || cfg->compute == EGX_F32_SPLIT, "compute=%d unknown", cfg->compute);
@@ -51,6 +51,17 @@ int make_plan(const egx_config* cfg, const egx_segment* segs, int B, Plan& pl) {
     }
     pl.S = S;
     pl.N = (size_t)B * S;
+    // 1024 < d_model <= 2048 (the 2048-wide HOI LTA 2-task translator): the wide bf16 path alone has kernels that wide
+    if (cfg->d_model > 1024) {
+        const int dh = cfg->d_model / cfg->n_heads;
+        EGX_CHECK(cfg->compute == EGX_BF16, "d_model=%d above 1024 needs compute bf16, wide path (got compute %d: f32 / f32s stop at 1024)", cfg->d_model, cfg->compute);
+        EGX_CHECK(cfg->impl == EGX_IMPL_AUTO || cfg->impl == EGX_IMPL_WIDE, "d_model=%d above 1024 needs compute bf16, wide path (impl auto or wide, got %d)", cfg->d_model, cfg->impl);
+        EGX_CHECK(wide_attn_supported(S, dh),
+                  "d_model=%d above 1024 needs compute bf16, wide path, whose attention has no kernel for S=%d tokens at head dim %d "
+                  "(S <= 128: head dim 32 / 64 / 96 / 128; S <= %d: head dim 256 / 512)", cfg->d_model, S, dh, WIDE_ATTN_BIGHEAD_MAX_S);
+        EGX_CHECK(wide_ok(cfg, segs, B), "d_model=%d above 1024 needs compute bf16, wide path: d_model, d_ff and every projected d_in multiples of 128, "
+                  "1 .. 64 layers, identity segments d_model wide", cfg->d_model);
+    }
     size_t d = pl.d, N = pl.N;
     size_t cur = 0;
     for (int i = 0; i < pl.nseg; ++i) {
@@ -135,7 +146,7 @@ static bool use_wide(const egx_config* cfg, const egx_segment* segs, const Plan&
     *err = false;
     const bool ok = wide_ok(cfg, segs, pl.B);
     if (cfg->impl == EGX_IMPL_WIDE) {
-        if (!ok) { set_error("wide implementation does not support this configuration (needs compute = bf16, d_model >= 256, d_model / d_ff / projected d_in multiples of 128, S <= 128 with head dim 32 / 64 / 96 / 128 or S <= 480 with head dim 32 / 64)"); *err = true; }
+        if (!ok) { set_error("wide implementation does not support this configuration (needs compute = bf16, d_model >= 256, d_model / d_ff / projected d_in multiples of 128, S <= 128 with head dim 32 / 64 / 96 / 128, S <= 480 with head dim 32 / 64 or S <= 16 with head dim 256 / 512; d_model <= 2048)"); *err = true; }
         return ok;
     }
     return cfg->impl == EGX_IMPL_AUTO && ok && !fused_ok(cfg, segs, pl);

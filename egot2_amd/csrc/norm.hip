@@ -362,7 +362,10 @@ int apply_dropout_mask(float* x, int rows, int d, uint64_t key, uint32_t thresh,
 }
 
 // ---- pooled head: mean over tokens -> (LN) -> (Linear) ----------------------------------------
-constexpr int PH_MAXD = 1024;
+// PH_MAXD: the columns the LDS rows of an instance hold. d <= 1024 (any d) runs the <1024> instances (the code they always had); 1024 < d <= PH_MAXD2
+// is served for the widths the wide bf16 path produces, multiples of 128, by the <PH_MAXD2> ones (the token mean in front of MultiTaskHead of the
+// 2048-wide LTA 2-task translator).
+constexpr int PH_MAXD = 1024, PH_MAXD2 = 2048;
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -374,6 +377,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // clip b = the S rows of tk (shared by the uniform kernel and the ragged-batch one)
+template <int PH_MAXD>
 __device__ __forceinline__ void pool_head_fwd_clip(const float* __restrict__ tk, int b, int S, int d,
                                                    const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
                                                    const float* __restrict__ W, const float* __restrict__ bias, int n_out,
@@ -467,12 +471,13 @@ __device__ __forceinline__ void pool_head_fwd_clip(const float* __restrict__ tk,
     }
 }
 
+template <int PH_MAXD>
 __global__ __launch_bounds__(256) void pool_head_fwd_kernel(const float* __restrict__ tokens, int S, int d,
                                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
                                                              const float* __restrict__ W, const float* __restrict__ bias, int n_out,
                                                              float* __restrict__ pooled, float* __restrict__ out) {
     const int b = blockIdx.x;
-    pool_head_fwd_clip(tokens + (size_t)b * S * d, b, S, d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
+    pool_head_fwd_clip<PH_MAXD>(tokens + (size_t)b * S * d, b, S, d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
 }
 
 // ragged batch (egx_ragged_fwd): clip b is rows [tok0_b, tok0_b + S_b) of the dense token array (the batch table, fused.h RAGGED_REC)
@@ -482,9 +487,10 @@ __global__ __launch_bounds__(256) void pool_head_ragged_fwd_kernel(const float* 
                                                                    float* __restrict__ pooled, float* __restrict__ out) {
     const int b = blockIdx.x;
     const int* rec = rtab + (size_t)b * RAGGED_REC;
-    pool_head_fwd_clip(tokens + (size_t)rec[RG_TOK0] * d, b, rec[RG_S], d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
+    pool_head_fwd_clip<PH_MAXD>(tokens + (size_t)rec[RG_TOK0] * d, b, rec[RG_S], d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
 }
 
+template <int PH_MAXD>
 __global__ __launch_bounds__(256) void pool_head_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ pooled,
                                                              int S, int d, const float* __restrict__ ln_w, const float* __restrict__ ln_b,
                                                              float eps, const float* __restrict__ W, int n_out,
@@ -571,10 +577,11 @@ __global__ __launch_bounds__(256) void pool_head_bwd_kernel(const float* __restr
 
 int pool_head_fwd(const float* tokens, int B, int S, int d, const float* ln_w, const float* ln_b, float eps,
                   const float* W, const float* b, int n_out, float* pooled, float* out, hipStream_t st) {
-    EGX_CHECK(d <= PH_MAXD, "pool_head: d=%d exceeds %d", d, PH_MAXD);
+    EGX_CHECK(d <= PH_MAXD || (d <= PH_MAXD2 && d % 128 == 0), "pool_head: d=%d exceeds %d (up to %d for multiples of 128, the wide bf16 path's widths)", d, PH_MAXD, PH_MAXD2);
     EGX_CHECK(!W || (n_out >= 1 && n_out <= 64), "pool_head: n_out=%d out of range 1..64", n_out);
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(pool_head_fwd_kernel, dim3(B), dim3(256), 0, st, tokens, S, d, ln_w, ln_b, eps, W, b, n_out, pooled, out);
+    if (d <= PH_MAXD) hipLaunchKernelGGL(pool_head_fwd_kernel<PH_MAXD>, dim3(B), dim3(256), 0, st, tokens, S, d, ln_w, ln_b, eps, W, b, n_out, pooled, out);
+    else hipLaunchKernelGGL(pool_head_fwd_kernel<PH_MAXD2>, dim3(B), dim3(256), 0, st, tokens, S, d, ln_w, ln_b, eps, W, b, n_out, pooled, out);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -617,7 +624,7 @@ int ragged_rows(float* padded, float* packed, const int* rtab, const int* rseg, 
 int pool_head_bwd(const float* d_out, const float* pooled, int B, int S, int d, const float* ln_w,
                   const float* ln_b, float eps, const float* W, int n_out, float* d_tokens, float* d_ln_w,
                   float* d_ln_b, float* d_W, float* d_b, hipStream_t st) {
-    EGX_CHECK(d <= PH_MAXD, "pool_head: d=%d exceeds %d", d, PH_MAXD);
+    EGX_CHECK(d <= PH_MAXD || (d <= PH_MAXD2 && d % 128 == 0), "pool_head: d=%d exceeds %d (up to %d for multiples of 128, the wide bf16 path's widths)", d, PH_MAXD, PH_MAXD2);
     EGX_CHECK(!W || (n_out >= 1 && n_out <= 64), "pool_head: n_out=%d out of range 1..64", n_out);
     if (B <= 0) return 0;
     float* part = nullptr;
@@ -629,8 +636,10 @@ int pool_head_bwd(const float* d_out, const float* pooled, int B, int S, int d, 
     // a clip's d(tokens) rows are shared out over several workgroups when the batch is small and the sequence long
     int ysplit = 1;
     if (B < 256) { ysplit = 256 / B; const int maxs = cdiv(S, 16); ysplit = ysplit > maxs ? maxs : ysplit; ysplit = ysplit < 1 ? 1 : ysplit; }
-    hipLaunchKernelGGL(pool_head_bwd_kernel, dim3(B, ysplit), dim3(256), 0, st, d_out, pooled, S, d, ln_w, ln_b, eps, W, n_out,
-                       d_tokens, d_ln_w, d_ln_b, d_W, d_b, part);
+    if (d <= PH_MAXD) hipLaunchKernelGGL(pool_head_bwd_kernel<PH_MAXD>, dim3(B, ysplit), dim3(256), 0, st, d_out, pooled, S, d, ln_w, ln_b, eps, W, n_out,
+                                         d_tokens, d_ln_w, d_ln_b, d_W, d_b, part);
+    else hipLaunchKernelGGL(pool_head_bwd_kernel<PH_MAXD2>, dim3(B, ysplit), dim3(256), 0, st, d_out, pooled, S, d, ln_w, ln_b, eps, W, n_out,
+                            d_tokens, d_ln_w, d_ln_b, d_W, d_b, part);
     EGX_LAUNCH_CHECK();
     if (part) {
         if (det_reduce_rows(part, prow, B, n_out * d, d_W, st)) return 1;

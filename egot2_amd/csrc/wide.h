@@ -119,7 +119,8 @@ size_t wide_pos_grad_scratch(int B, int T, int d);
 int wide_pos_grad(const float* dtok, int B, int S, int off, int T, int d, float* dpos, int pos_stride, uint64_t key, uint32_t thresh,
                   float inv, void* scratch, hipStream_t st);
 
-// Attention over packed bf16 qkv rows (B*S, 3d): out (B*S, d) bf16, lse (B, H, S) fp32. S <= 128, head dim in {32, 64, 96, 128}.
+// Attention over packed bf16 qkv rows (B*S, 3d): out (B*S, d) bf16, lse (B, H, S) fp32. S <= 128, head dim in {32, 64, 96, 128};
+// S <= 16 with head dim 256 / 512 (wide_attn_bighead.hip: the 2048-wide LTA 2-task translator).
 struct WideAttnParams {
     const bf16_t* qkv = nullptr; bf16_t* out = nullptr; float* lse = nullptr;
     const bf16_t* d_out = nullptr; bf16_t* d_qkv = nullptr;
@@ -132,7 +133,12 @@ struct WideAttnParams {
 };
 constexpr int WIDE_RG_MAXSEG = 8, WIDE_RG_REC = 2 + 2 * WIDE_RG_MAXSEG;      // (WIDE_RG_MAXSEG = EGX_MAX_SEGMENTS)
 enum { WRG_S = 0, WRG_TOK0 = 1, WRG_T = 2 /* .. frames of segment k */, WRG_OFF = 2 + WIDE_RG_MAXSEG /* .. first token of segment k */ };
-bool wide_attn_supported(int S, int dh);      // S <= 128: head dim 32 / 64 / 96 / 128; 128 < S <= ~480: head dim 32 / 64 (wide_attn_long_*)
+bool wide_attn_supported(int S, int dh);      // S <= 128: head dim 32 / 64 / 96 / 128; 128 < S <= ~480: head dim 32 / 64 (wide_attn_long_*); S <= 16: 256 / 512
+// head dim 256 / 512 over 1 <= S <= WIDE_ATTN_BIGHEAD_MAX_S tokens (wide_attn_bighead.hip): one wave per (clip, head), uniform batches only
+constexpr int WIDE_ATTN_BIGHEAD_MAX_S = 16;
+bool wide_attn_bighead_dim(int dh);             // 256 or 512
+bool wide_attn_bighead_supported(int S, int dh);
+int wide_attn_bighead(const WideAttnParams& p, bool bwd, hipStream_t st);
 size_t wide_attn_delta_bytes(int B, int H, int S);
 int wide_attn_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_bwd(const WideAttnParams& p, hipStream_t st);
@@ -143,6 +149,6 @@ int wide_attn_bwd(const WideAttnParams& p, hipStream_t st);
 // batch of equal-length clips draws the masks of the uniform call.
 int wide_attn_ragged_fwd(const WideAttnParams& p, hipStream_t st);
 int wide_attn_ragged_bwd(const WideAttnParams& p, hipStream_t st);
-int wide_attn_ragged_class(int S, int dh);      // 0: S <= 64, 1: 64 < S <= 128, 2: the long kernel, -1: unsupported
+int wide_attn_ragged_class(int S, int dh);      // 0: S <= 64, 1: 64 < S <= 128, 2: the long kernel, -1: unsupported (head dim 256 / 512 among them)
 
 }  // namespace egx

@@ -622,7 +622,7 @@ bool wide_attn_long_supported(int S, int dh) {
 }
 
 bool wide_attn_supported(int S, int dh) {
-    return (S >= 1 && S <= 128 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) || wide_attn_long_supported(S, dh);
+    return (S >= 1 && S <= 128 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) || wide_attn_long_supported(S, dh) || wide_attn_bighead_supported(S, dh);
 }
 int wide_attn_ragged_class(int S, int dh) {
     if (S >= 1 && S <= 64 && (dh == 32 || dh == 64 || dh == 96 || dh == 128)) return 0;
@@ -703,8 +703,10 @@ static int launch_attn_class(const WideAttnParams& p, int dh, int cls, bool bwd,
 static int dispatch_attn(const WideAttnParams& p, bool bwd, hipStream_t st) {
     EGX_CHECK(p.qkv && p.lse && p.B > 0 && p.H > 0 && p.d % p.H == 0, "wide attention: bad arguments");
     const int dh = p.d / p.H;
-    EGX_CHECK(wide_attn_supported(p.S, dh), "wide attention: S=%d head dim %d unsupported (S <= 128 with head dim 32 / 64 / 96 / 128; longer sequences: head dim 32 / 64 while two images fit the LDS)", p.S, dh);
+    EGX_CHECK(!wide_attn_bighead_dim(dh) || wide_attn_bighead_supported(p.S, dh), "wide attention: S=%d head dim %d unsupported (head dim 256 / 512 serves S <= %d)", p.S, dh, WIDE_ATTN_BIGHEAD_MAX_S);
+    EGX_CHECK(wide_attn_supported(p.S, dh), "wide attention: S=%d head dim %d unsupported (S <= 128 with head dim 32 / 64 / 96 / 128; S <= 16 with head dim 256 / 512; longer sequences: head dim 32 / 64 while two images fit the LDS)", p.S, dh);
     EGX_CHECK(p.d % 8 == 0, "wide attention: d_model %% 8 != 0");
+    if (wide_attn_bighead_dim(dh)) return wide_attn_bighead(p, bwd, st);      // (wide_attn_bighead.hip; not a ragged class)
     EGX_CHECK(p.S <= 128 || !bwd || (p.delta && p.out), "wide attention (S > 128): the backward needs the saved attention output and a delta buffer");
     return launch_attn_class<false>(p, dh, wide_attn_ragged_class(p.S, dh), bwd, st);
 }

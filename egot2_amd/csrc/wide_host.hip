@@ -179,7 +179,7 @@ bool wide_ok(const egx_config* cfg, const egx_segment* segs, int B) {
     const int d = cfg->d_model, dff = cfg->d_ff;
     // impl = auto keeps d_model = 128 on the per-clip / fp32-storage kernels (the wide path's extra bf16 roundings sit at the
     // 1e-2 bound there); impl = wide may force it
-    if ((d < 256 && cfg->impl != EGX_IMPL_WIDE) || d % 128 != 0 || dff % 128 != 0 || d > 1024 || cfg->n_layers < 1 || cfg->n_layers > 64) return false;
+    if ((d < 256 && cfg->impl != EGX_IMPL_WIDE) || d % 128 != 0 || dff % 128 != 0 || d > 2048 || cfg->n_layers < 1 || cfg->n_layers > 64) return false;
     if (cfg->n_heads <= 0 || d % cfg->n_heads != 0) return false;
     int S = 0;
     for (int i = 0; i < cfg->n_segments; ++i) {

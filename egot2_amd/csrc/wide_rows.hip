@@ -23,13 +23,15 @@ __device__ __forceinline__ float bff(uint32_t lo16) { return __builtin_bit_cast(
 __device__ __forceinline__ int remap(int row, int T, int S, int off) { return (row / T) * S + off + (row % T); }
 
 constexpr int LN_MAXV = 4;      // float4 per lane: d <= 1024
+constexpr int LN_MAXV2 = 8;     // the second instance of the uniform kernels: 1024 < d <= 2048 (the 2048-wide LTA 2-task translator)
 
 }  // namespace
 
 // MAPPED (ragged batches: wide_ln_fwd_mapped, wide_ln_bwd_mapped): the output row and the positional row (backward: the upstream row, and with it
 // the row key of the dropout behind the LayerNorm) come from row maps of the batch table instead of the T / S / off remap. A flag on the kernel
 // template, so that the uniform kernels keep their code: see the note at wide_attn_fwd_kernel (wide_attn.hip).
-template <bool MAPPED>
+// LN_MAXV: the float4 count of a lane (LN_MAXV for d <= 1024, the code that instance always had; LN_MAXV2 above)
+template <bool MAPPED, int LN_MAXV>
 __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -81,20 +83,20 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
     }
 }
 
-template <bool MAPPED>
+template <bool MAPPED, int NV = LN_MAXV>
 static int launch_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
     if (p.rows <= 0) return 0;
     int blocks = cdiv(p.rows, 4);
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wide_ln_fwd_kernel<MAPPED>, dim3(blocks), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((wide_ln_fwd_kernel<MAPPED, NV>), dim3(blocks), dim3(256), 0, st, p);
     EGX_LAUNCH_CHECK();
     return 0;
 }
 
 int wide_ln_fwd(const WideLnFwdParams& p, hipStream_t st) {
     EGX_CHECK(p.x && p.w && p.b && (p.y32 || p.y16), "wide_ln_fwd: null pointer");
-    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_fwd: d=%d unsupported", p.d);
-    return launch_ln_fwd<false>(p, st);
+    EGX_CHECK(p.d > 0 && p.d <= 256 * LN_MAXV2 && p.d % 4 == 0, "wide_ln_fwd: d=%d unsupported", p.d);
+    return p.d <= 256 * LN_MAXV ? launch_ln_fwd<false>(p, st) : launch_ln_fwd<false, LN_MAXV2>(p, st);
 }
 
 int wide_ln_fwd_mapped(const WideLnFwdParams& p, hipStream_t st) {
@@ -106,10 +108,13 @@ int wide_ln_fwd_mapped(const WideLnFwdParams& p, hipStream_t st) {
 
 // Each block owns a CONTIGUOUS range of rows; its four waves interleave over it and keep per-column partial sums in
 // registers, combined through LDS at the end: partials[block][k][d], k = 0 d(gamma), 1 d(beta), 2 column sums of dx16.
-template <bool MAPPED>
+// LN_MAXV as in wide_ln_fwd_kernel. The LN_MAXV2 instance combines its three partial-sum kinds one after the other through ONE (4, 2048) LDS
+// array (three of them would be 96 KB of static LDS); the sums and their order are the same.
+template <bool MAPPED, int LN_MAXV>
 __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int rows_per_block) {
     const uint64_t dkey = p.drop_thresh ? resolve_key(p.drop_key) : 0ull, okey = p.out_thresh ? resolve_key(p.out_key) : 0ull;
-    __shared__ float red[3][4][1024];
+    constexpr bool ONE_PASS = LN_MAXV <= 4;
+    __shared__ float red[ONE_PASS ? 3 : 1][4][256 * LN_MAXV];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int d = p.d, nv = (d + 255) / 256;
     const float inv_d = 1.f / (float)d;
@@ -179,6 +184,7 @@ __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int
             }
         }
     }
+    if constexpr (ONE_PASS) {
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) {
         int c = 4 * lane + 256 * i;
@@ -193,6 +199,20 @@ __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int
     for (int i = threadIdx.x; i < 3 * d; i += 256) {
         int k = i / d, c = i % d;
         out[i] = (red[k][0][c] + red[k][1][c]) + (red[k][2][c] + red[k][3][c]);
+    }
+    } else {
+        float* out = p.partials + (size_t)blockIdx.x * 3 * d;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (k) __syncthreads();
+#pragma unroll
+            for (int i = 0; i < LN_MAXV; ++i) {
+                int c = 4 * lane + 256 * i;
+                if (i < nv && c < d) *reinterpret_cast<float4*>(&red[0][wave][c]) = k == 0 ? aw[i] : k == 1 ? ab[i] : ac[i];
+            }
+            __syncthreads();
+            for (int c = threadIdx.x; c < d; c += 256) out[k * d + c] = (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]);
+        }
     }
 }
 
@@ -278,14 +298,14 @@ static int ln_bwd_blocks(int rows) {
 size_t wide_ln_bwd_scratch(int rows, int d) { return (size_t)ln_bwd_blocks(rows) * 3 * d * sizeof(float); }
 
 // the mapped call never defers its reduction (defer = null)
-template <bool MAPPED>
+template <bool MAPPED, int NV = LN_MAXV>
 static int launch_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer) {
     if (p.rows <= 0) return 0;
     p.blocks = ln_bwd_blocks(p.rows);
     p.partials = (float*)scratch;
     const int rpb = cdiv(p.rows, p.blocks);
     p.blocks = cdiv(p.rows, rpb);
-    hipLaunchKernelGGL(wide_ln_bwd_kernel<MAPPED>, dim3(p.blocks), dim3(256), 0, st, p, rpb);
+    hipLaunchKernelGGL((wide_ln_bwd_kernel<MAPPED, NV>), dim3(p.blocks), dim3(256), 0, st, p, rpb);
     if (defer && (p.dw || p.db || p.dbias || p.dadd)) {
         EGX_LAUNCH_CHECK();
         WideRowReduceDesc q;
@@ -302,8 +322,8 @@ static int launch_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideR
 
 int wide_ln_bwd(WideLnBwdParams p, void* scratch, hipStream_t st, WideRowReduceBatch* defer) {
     EGX_CHECK(p.dy && p.pre && p.stats && p.w && scratch, "wide_ln_bwd: null pointer");
-    EGX_CHECK(p.d > 0 && p.d <= 1024 && p.d % 4 == 0, "wide_ln_bwd: d=%d unsupported", p.d);
-    return launch_ln_bwd<false>(p, scratch, st, defer);
+    EGX_CHECK(p.d > 0 && p.d <= 256 * LN_MAXV2 && p.d % 4 == 0, "wide_ln_bwd: d=%d unsupported", p.d);
+    return p.d <= 256 * LN_MAXV ? launch_ln_bwd<false>(p, scratch, st, defer) : launch_ln_bwd<false, LN_MAXV2>(p, scratch, st, defer);
 }
 
 int wide_ln_bwd_mapped(WideLnBwdParams p, void* scratch, hipStream_t st) {

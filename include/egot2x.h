@@ -121,6 +121,11 @@ typedef struct egx_layer_grads {
 struct egx_ce;
 struct egx_token_ce;
 typedef struct egx_config {
+    /* d_model: a multiple of 4 up to 1024 in every compute mode. 1024 < d_model <= 2048 (the 2048-wide HOI LTA 2-task translator) runs with
+     * compute EGX_BF16 on the wide path only: impl auto or wide, d_model % 128 == 0, d_ff % 128 == 0, and a token count S its attention
+     * serves at head dim d_model / n_heads (S <= 128: 32 / 64 / 96 / 128; S <= 16: 256 / 512). compute f32 / f32s, impl generic / fused /
+     * tiled or another (S, head dim) are refused above 1024 with an error that says "compute bf16, wide path"; ragged batches
+     * (egx_ragged_encode*) stay at 1024. Nothing above 2048 is accepted. */
     int d_model;
     int n_heads;
     int d_ff;
@@ -252,7 +257,7 @@ int egx_encoder_uses_fused(const egx_config* cfg, const egx_segment* segs, int B
 /* Which kernels this configuration runs on: EGX_IMPL_FUSED (per-clip kernels: d = 128, h = 4, S <= 48), EGX_IMPL_TILED (the same
  * kernels over 48-token tiles with the attention of the whole clip between the launches: d = 128, h = 4, 48 < S <= 512, compute bf16
  * or f32s - the reference's real TTM / ASD batches of 15 .. 150 frames per task, HHI/dataset/ttm/data_loader_2task.py:119,150-162), EGX_IMPL_WIDE
- * (compute = bf16 with d_model >= 256, d_model / d_ff / projected d_in multiples of 128, S <= 128 with head dim 32 / 64 / 96 / 128 or S <= 512 with head dim 32 / 64: all B*S tokens
+ * (compute = bf16 with d_model >= 256, d_model / d_ff / projected d_in multiples of 128, d_model <= 2048, S <= 128 with head dim 32 / 64 / 96 / 128, S <= 512 with head dim 32 / 64 or S <= 16 with head dim 256 / 512: all B*S tokens
  * through bf16-storage MFMA GEMMs and MFMA attention - BASELINE.json configs[3], configs[4]) or EGX_IMPL_GENERIC; -1 on an
  * invalid configuration. */
 int egx_encoder_impl(const egx_config* cfg, const egx_segment* segs, int B);
@@ -396,7 +401,7 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
                    const egx_head_grads* head_grads, int training, uint64_t seed, void* stream);
 
 /* pooled = mean_s tokens[b, s, :]; y = ln_w ? LN(pooled) : pooled; out = W ? y W^T + b : y.
- * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL; d <= 1024 (any d, multiple of 4 or not). Both are checked: a call
+ * `pooled_saved` (B, d) is kept for backward. n_out <= 64 when W != NULL; d <= 1024 (any d, multiple of 4 or not), or a multiple of 128 up to 2048 (the wide bf16 path's widths). Both are checked: a call
  * outside them returns non-zero and writes nothing.
  * Backward: d_tokens (B, S, d) is overwritten (=), the S rows of a clip all alike; d_ln_w, d_ln_b, d_W and d_b are added into (+=, the clips
  * meet in fp32 atomics) and may each be NULL. */
@@ -456,7 +461,9 @@ size_t egx_wide_gemm_scratch(int layout, int M, int N, int K);
 int egx_wide_gemm(int layout, const void* A, const void* B, float* Cf, void* Cb, int M, int N, int K, const float* bias,
                   int relu, const float* residual, void* scratch, void* stream);
 /* qkv: (B*S, 3d) packed bf16 in-projection rows; out: (B*S, d) bf16; lse: (B, H, S) fp32. S <= 128 with head dim 32/64/96/128,
- * or 128 < S <= 480 with head dim 32/64 (the EgoT2-g encoders on sequences of up to 3 x 150 tokens: online softmax).
+ * or 128 < S <= 480 with head dim 32/64 (the EgoT2-g encoders on sequences of up to 3 x 150 tokens: online softmax),
+ * or 1 <= S <= 16 with head dim 256/512 (the 2048-wide LTA 2-task translator: one wave per (clip, head)); a head dim of 256 / 512 with
+ * S > 16 is refused.
  * Backward: d_out (B*S, d) bf16 -> d_qkv (B*S, 3d) bf16 (probabilities recomputed from lse; every element written once).
  * S > 128 also reads `out` (the forward's output) and uses `delta` ((B, H, S) fp32 scratch); both may be NULL for S <= 128. */
 int egx_wide_attention_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, int d, float p_drop, uint64_t seed,
