@@ -212,6 +212,10 @@ SIGNATURES = {
                                        C.c_float, C.c_int, C.c_float, _fp]),
     "egx_sgd_step": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                C.c_float, _fp]),
+    # ABI v18, additions: the LTA criterion in one launch (col0 / C / ks are host int arrays)
+    "egx_segmented_ce_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "egx_segmented_ce": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

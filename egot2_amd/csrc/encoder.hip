@@ -822,6 +822,14 @@ int egx_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n,
                     (hipStream_t)stream);
 }
 
+// ABI v18, additions: the LTA criterion (seg_ce.hip); every argument is checked on the host before any device work
+size_t egx_segmented_ce_scratch(int B, int Z, int H, int n_ks) { return segmented_ce_scratch_bytes(B, Z, H, n_ks); }
+int egx_segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C, const int* ks,
+                     int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* d_logits, void* scratch, void* stream) {
+    return segmented_ce(logits, ld, target, B, Z, H, col0, C, ks, n_ks, loss, loss_terms, n_valid, correct, d_logits, scratch,
+                        (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

@@ -128,6 +128,12 @@ int lr_update(int kind, long long warmup, long long t_total, long long T_max, do
 int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
              float dampening, float wd, int nesterov, float grad_scale, hipStream_t st);
 
+// seg_ce.hip: the LTA criterion (per-(future step, head) mean cross-entropies summed, top-k counts, d loss / d logits) in one launch
+constexpr int SEG_CE_MAX_HEADS = 4, SEG_CE_MAX_KS = 4, SEG_CE_MAX_CLASSES = 2048, SEG_CE_MAX_ROWS = 1 << 28;
+size_t segmented_ce_scratch_bytes(int B, int Z, int H, int n_ks);
+int segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C, const int* ks,
+                 int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* dlogits, void* scratch, hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

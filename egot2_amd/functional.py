@@ -2000,6 +2000,133 @@ def linear_cross_entropy(x, W, b, target, weight=None):
     return LinearCEFn.apply(x, W, b, target, weight)
 
 
+# ---- the LTA criterion: per-(future step, head) cross-entropies and top-k counts in one launch (csrc/seg_ce.hip) ----------------
+SEG_CE_MAX_HEADS, SEG_CE_MAX_KS, SEG_CE_MAX_CLASSES = 4, 4, 2048
+
+
+def _seg_windows(preds):
+    """The heads as column windows of ONE (B, Z, ld) fp32 stack -> (address of row 0, ld, col0). Zero-copy when the (B, Z, C_h) tensors
+    are views of one storage with a common row stride whose windows lie side by side in a row (what `_LTATranslator.decode` returns:
+    torch.split of the (B, Z, 593) stack); None otherwise (the caller concatenates)."""
+    p0 = preds[0]
+    B, Z = p0.shape[0], p0.shape[1]
+    ld = p0.stride(1)
+    base = p0.untyped_storage().data_ptr()
+    if ld < 1 or any(p.untyped_storage().data_ptr() != base or p.stride() != (Z * ld, ld, 1) for p in preds):
+        return None
+    offs = [p.storage_offset() for p in preds]
+    col0 = [o - min(offs) for o in offs]
+    spans = sorted((c, c + p.shape[2]) for c, p in zip(col0, preds))
+    if spans[-1][1] > ld or any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        return None
+    return base + 4 * min(offs), ld, col0
+
+
+_SEG_SCRATCH = {}
+
+
+def _seg_scratch(device, Z: int, nbytes: int) -> torch.Tensor:
+    """Scratch of egx_segmented_ce, by the rules of _lce_scratch (one per device, zero-filled once, never created inside a capture, an
+    outgrown buffer stays alive) - and one per Z: the buffer begins with 64 * (1 + Z) bytes of arrival counters that every launch leaves
+    zero, and the partial sums behind them must not land where a launch with another Z keeps its counters."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), Z)
+    t = _SEG_SCRATCH.get(key)
+    if t is None or t.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("segmented_cross_entropy: run one eager step at this problem size before capturing it in a graph")
+        if t is not None:
+            _LCE_RETIRED.append(t)
+        t = _SEG_SCRATCH[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+class SegmentedCEFn(torch.autograd.Function):
+    """(loss, loss_terms, n_valid, correct) of egx_segmented_ce; the same launch leaves d loss / d logits of the whole stack behind, and the
+    backward hands out its column windows. `out` (optional dict of preallocated `loss`, `loss_terms`, `n_valid`, `correct`): where the results
+    go (train.LTACriterion's persistent buffers); only `loss` carries gradient."""
+
+    @staticmethod
+    def forward(ctx, labels, ks, out, *preds):
+        lib = _lib.load()
+        H = len(preds)
+        if not 1 <= H <= SEG_CE_MAX_HEADS:
+            raise ValueError(f"segmented_cross_entropy takes 1 to {SEG_CE_MAX_HEADS} heads, got {H}")
+        for h, p in enumerate(preds):
+            _dev_f32(p[:0], f"preds[{h}]")                   # device / dtype refusal only: the heads stay the views they are
+        p0 = preds[0]
+        if any(p.dim() != 3 or p.shape[:2] != p0.shape[:2] or p.device != p0.device for p in preds):
+            raise ValueError(f"segmented_cross_entropy expects (B, Z, C_h) heads of one batch, got {[tuple(p.shape) for p in preds]}")
+        B, Z = p0.shape[0], p0.shape[1]
+        widths = [p.shape[2] for p in preds]
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B, Z, H) or labels.device != p0.device:
+            raise ValueError(f"labels must be an int64 tensor of shape (B, Z, H) = {(B, Z, H)} on the predictions' device")
+        ks = tuple(int(k) for k in ks)
+        if len(ks) > SEG_CE_MAX_KS:
+            raise ValueError(f"segmented_cross_entropy takes at most {SEG_CE_MAX_KS} values of k, got {len(ks)}")
+        tgt = labels.contiguous()
+        win = _seg_windows(preds)
+        if win is None:                                     # one concatenation builds the stack
+            stack = torch.cat(preds, dim=-1).contiguous()
+            ld, col0, off = stack.shape[2], [], 0
+            for w in widths:
+                col0.append(off)
+                off += w
+            addr = stack.data_ptr()
+        else:
+            addr, ld, col0 = win
+        dev = p0.device
+        out = out or {}
+        loss = out["loss"] if "loss" in out else torch.empty((), dtype=torch.float32, device=dev)
+        terms = out["loss_terms"] if "loss_terms" in out else torch.empty((Z, H), dtype=torch.float32, device=dev)
+        n_valid = out["n_valid"] if "n_valid" in out else torch.empty((Z, H), dtype=torch.int32, device=dev)
+        correct = out["correct"] if "correct" in out else torch.empty((len(ks), Z, H), dtype=torch.int32, device=dev)
+        need = any(ctx.needs_input_grad[3:])
+        dl = torch.empty((B, Z, ld), dtype=torch.float32, device=dev) if need else None
+        nbytes = lib.egx_segmented_ce_scratch(B, Z, H, len(ks))
+        if nbytes == 0:
+            check(1)
+        scratch = _seg_scratch(dev, Z, nbytes)
+        ia = lambda v: (C.c_int * max(len(v), 1))(*v)  # noqa: E731
+        check(lib.egx_segmented_ce(addr, ld, ptr(tgt), B, Z, H, ia(col0), ia(widths), ia(ks), len(ks), ptr(loss), ptr(terms), ptr(n_valid),
+                                   ptr(correct) if len(ks) else None, ptr(dl), ptr(scratch), _stream()))
+        ctx.n_heads = H
+        ctx.windows = list(zip(col0, widths)) if need else None
+        if need:
+            ctx.save_for_backward(dl)
+        # fresh tensor objects over the result memory: a persistent buffer handed in through `out` must not become the owner of this call's
+        # autograd graph (it would keep the graph - and the logits' gradient accumulator, with the stream it was created on - alive into the
+        # next call, e.g. from an eager step on the default stream into a capture)
+        loss, terms, n_valid, correct = loss.detach(), terms.detach(), n_valid.detach(), correct.detach()
+        ctx.mark_non_differentiable(terms, n_valid, correct)
+        ctx.set_materialize_grads(False)
+        return loss, terms, n_valid, correct
+
+    @staticmethod
+    def backward(ctx, g_loss, _gt, _gn, _gc):
+        if ctx.windows is None or g_loss is None:
+            return (None,) * (3 + ctx.n_heads)
+        (dl,) = ctx.saved_tensors
+        u = _UNIT_GRAD.get(dl.device.index)
+        if u is None or g_loss.data_ptr() != u.data_ptr():
+            dl = dl * g_loss
+        return (None, None, None) + tuple(dl[..., c0:c0 + w] if ctx.needs_input_grad[3 + h] else None for h, (c0, w) in enumerate(ctx.windows))
+
+
+def segmented_cross_entropy(preds, labels, ks=(1, 5), out=None):
+    """-> (loss, stats): the criterion of the long-term-anticipation task (HOI/tasks/lta/long_term_anticipation.py:182-203) in one launch.
+
+    preds: list of (B, Z, C_h) fp32 tensors, one per head (1 .. 4 heads, C_h <= 2048); labels: int64 (B, Z, H).
+    loss = sum over heads h and future steps z of F.cross_entropy(preds[h][:, z], labels[:, z, h]) (mean over the clips with a valid
+    label). stats, all device tensors (nothing synchronises): `correct` (len(ks), Z, H) int32 - valid clips whose label is among the top k -,
+    `n_valid` (Z, H) int32, `loss_terms` (Z, H) - the terms of the sum. top-k error of a pair = (1 - correct / n_valid) * 100.
+    A label outside [0, C_h) (ignore index -100 included) contributes no loss, count or gradient; a (z, h) pair without a valid label adds
+    0 (torch: nan); among equal logits the lower class index ranks first (torch.topk: unspecified).
+    When the heads are views of one storage with a common row stride - what `forward_features` of the LTA translators returns - the kernel
+    reads them in place; otherwise one torch.cat builds the stack. `out`: preallocated result tensors (train.LTACriterion)."""
+    loss, terms, n_valid, correct = SegmentedCEFn.apply(labels, tuple(ks), out, *preds)
+    return loss, {"correct": correct, "n_valid": n_valid, "loss_terms": terms}
+
+
 # ---- EgoT2-g sequence decoder pieces (SURVEY.md §8f row F1; kernels in csrc/decoder.hip) ------------------------------
 class LayerNormFn(torch.autograd.Function):
     """y = LayerNorm(x + res) * w + b over the last dimension of 2-D inputs (post-LN residual blocks)."""

@@ -9,6 +9,8 @@ update is a single launch per buffer, with the step count in device memory (hipG
 `FusedSGD` mirrors `torch.optim.SGD` as HOI/optimizers/lta/optimizer.py:54-62 builds it on the same machinery, `LRSchedule` the reference's
 per-step learning-rate schedulers (HOI/optimizers/lta/lr_scheduler.py:11-41) evaluated on the device from that step count, and `construct_solver`
 restates construct_optimizer + lr_factory on both.
+`LTACriterion` is the criterion of the long-term-anticipation task (HOI/tasks/lta/long_term_anticipation.py:182-203: 40 cross-entropies
+and the top-1 / top-5 errors of every (future step, head) pair) as one launch without a host synchronisation.
 """
 from __future__ import annotations
 
@@ -31,6 +33,85 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return F_egx.weighted_cross_entropy(input, target, self.weight)
+
+
+class LTACriterion(nn.Module):
+    """The criterion of the long-term-anticipation task, LongTermAnticipationTask.training_step (HOI/tasks/lta/long_term_anticipation.py:182-203):
+
+        loss = sum over heads h, future steps z of nn.CrossEntropyLoss()(preds[h][:, z], labels[:, z, h])
+        step_result[f"train_{z}_{h}_top{k}_err"] = topk_errors(preds[h][:, z], labels[:, z, h], (1, 5))[..].item()
+
+    as ONE launch (functional.segmented_cross_entropy) without a host synchronisation, so it can be the `loss_fn` of a GraphedStep; the
+    reference's 40 cross-entropy calls, 40 topk calls and 80 `.item()` reads become that launch plus ONE device-to-host copy in
+    `step_result()`. preds: the list of (B, Z, C_h) tensors `forward_features` of the LTA translators returns; labels: int64 (B, Z, H).
+
+    The loss, its (Z, H) terms, the valid-label counts and the top-k correct counts live in ONE persistent buffer per (device, Z, H),
+    allocated on the first eager call (a capture cannot allocate it: run an eager step first, GraphedStep's warm-up does) and refreshed by
+    every call or replay. Labels outside [0, C_h) are ignored; a (z, h) pair without a valid label adds 0 to the loss and reports nan errors;
+    among equal logits the lower class index ranks first."""
+
+    def __init__(self, ks=(1, 5)):
+        super().__init__()
+        self.ks = tuple(int(k) for k in ks)
+        if not 1 <= len(self.ks) <= F_egx.SEG_CE_MAX_KS or min(self.ks) < 1:
+            raise ValueError(f"LTACriterion: ks={ks} (needs 1 to {F_egx.SEG_CE_MAX_KS} values >= 1)")
+        self._bufs: Dict[tuple, dict] = {}
+        self._last: Optional[dict] = None
+
+    def _result_buffers(self, device, Z: int, H: int) -> dict:
+        """loss | loss_terms (Z, H) | n_valid (Z, H) | correct (len(ks), Z, H) as views of one buffer of 4-byte words (`flat`)."""
+        device = torch.device(device)
+        key = (device.type, device.index, Z, H)
+        b = self._bufs.get(key)
+        if b is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # a buffer created inside a capture would live in that graph's private pool
+                raise RuntimeError("LTACriterion: run one eager step at this problem size before capturing it in a graph")
+            n = Z * H
+            flat = torch.zeros(1 + n * (2 + len(self.ks)), dtype=torch.int32, device=device)
+            b = self._bufs[key] = {"flat": flat, "Z": Z, "H": H,
+                                   "loss": flat[0:1].view(torch.float32).view(()),
+                                   "loss_terms": flat[1:1 + n].view(torch.float32).view(Z, H),
+                                   "n_valid": flat[1 + n:1 + 2 * n].view(Z, H),
+                                   "correct": flat[1 + 2 * n:].view(len(self.ks), Z, H)}
+        return b
+
+    def forward(self, preds, labels: torch.Tensor) -> torch.Tensor:
+        preds = list(preds)
+        b = self._result_buffers(preds[0].device, preds[0].shape[1], len(preds))
+        loss, _ = F_egx.segmented_cross_entropy(preds, labels, self.ks, out=b)
+        self._last = b
+        return loss
+
+    def stats(self) -> dict:
+        """Device tensors of the most recent call (or replay): `loss`, `loss_terms`, `n_valid`, `correct`. Reading them does not synchronise."""
+        if self._last is None:
+            raise RuntimeError("LTACriterion: no forward has run yet")
+        return {k: self._last[k] for k in ("loss", "loss_terms", "n_valid", "correct")}
+
+    def step_result(self, prefix: str = "train") -> Dict[str, float]:
+        """The reference's step_result of the most recent call (or replay), from ONE device-to-host copy (it synchronises: for logging):
+        f"{prefix}_{z}_{h}_top{k}_err" = (1 - correct / n_valid) * 100 for every k of `ks`, f"{prefix}_{h}_top{k}_err" = their mean over z,
+        f"{prefix}_loss"."""
+        if self._last is None:
+            raise RuntimeError("LTACriterion: no forward has run yet")
+        b = self._last
+        Z, H, n = b["Z"], b["H"], b["Z"] * b["H"]
+        host = b["flat"].cpu().numpy()
+        n_valid = host[1 + n:1 + 2 * n].reshape(Z, H).astype("float64")
+        correct = host[1 + 2 * n:].reshape(len(self.ks), Z, H).astype("float64")
+        res: Dict[str, float] = {}
+        for ki, k in enumerate(self.ks):
+            for h in range(H):
+                errs = []
+                for z in range(Z):
+                    nv = n_valid[z, h]
+                    e = (1.0 - correct[ki, z, h] / nv) * 100.0 if nv > 0 else float("nan")
+                    res[f"{prefix}_{z}_{h}_top{k}_err"] = float(e)
+                    errs.append(e)
+                res[f"{prefix}_{h}_top{k}_err"] = float(sum(errs) / len(errs))
+        res[f"{prefix}_loss"] = float(host[0:1].view("float32")[0])
+        return res
 
 
 class LRSchedule:

@@ -557,6 +557,36 @@ int egx_adam_step_dev_lr(float* param, const float* grad, float* exp_avg, float*
 int egx_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n, const int64_t* step, const float* lr_dev,
                  float lr, float momentum, float dampening, float weight_decay, int nesterov, float grad_scale,
                  void* stream);
+/* ---- ABI v18, additions: the criterion of the long-term-anticipation task in one launch ---------------------------
+ * LongTermAnticipationTask.training_step, HOI/tasks/lta/long_term_anticipation.py:182-203: on the model's [(B, Z, 115), (B, Z, 478)]
+ * output it sums CrossEntropyLoss(mean)(pred_h[:, z], labels[:, z, h]) over the 2 heads and 20 future steps (40 terms) and reads
+ * the top-1 / top-5 error of every (z, h) pair with .item() (evaluation/lta/lta_metrics.py:38-84). Here:
+ *   logits   fp32, R = B * Z rows (row b * Z + z) of row stride `ld` floats: the (B, Z, 593) stack the translator's decode() builds.
+ *            Rows need NO alignment (ld = 593 is odd). H heads (1 .. 4); head h owns columns [col0[h], col0[h] + C[h]) of every
+ *            row, 1 <= C[h] <= 2048; heads are disjoint, lie inside [0, ld) and need not cover the row. col0, C, ks: HOST arrays.
+ *   target   int64 (B, Z, H), contiguous. A label outside [0, C[h]) - the default ignore index -100 included - contributes no
+ *            loss, no count and no gradient (the rule of egx_weighted_ce).
+ *   ks       n_ks <= 4 values, each in 1 .. min_h C[h].
+ *   loss       = sum_{z,h} ( sum_{b valid} nll[b,z,h] ) / n_valid[z,h]                       (scalar)
+ *   loss_terms (Z, H), optional: the terms of that sum
+ *   n_valid    (Z, H) int32: clips with a valid label
+ *   correct    (n_ks, Z, H) int32 (NULL allowed when n_ks == 0): valid rows whose label has rank < k, where
+ *              rank = #{c : z_c > z_y} + #{c < y : z_c == z_y}
+ *   d_logits   (R, ld), optional, EVERY element written: (softmax - onehot) / n_valid[z,h] on the valid rows of a head; 0 on
+ *              invalid rows and on columns no head covers (egx_linear_bwd of the stacked head reads whole rows).
+ * Two deliberate differences from torch: (1) a (z, h) pair WITHOUT a valid label adds 0 to the loss and has zero gradient, where
+ * nn.CrossEntropyLoss gives nan (0 / 0); (2) torch.topk leaves the order of equal logits unspecified - the rank rule above is this
+ * library's: among equal logits the lower class index ranks first, so a row of all-equal logits is top-k correct iff y < k.
+ * The softmax is max-subtracted (a row holding +80 and -80 does not overflow). One launch on `stream`; every sum runs in a fixed order
+ * (per-workgroup partials in scratch, added by the last workgroup to arrive): the same bits on every run, no float atomics.
+ * `scratch`: egx_segmented_ce_scratch(B, Z, H, n_ks) bytes (0: invalid arguments, see egx_last_error), ZERO before the first use
+ * (it begins with 64 * (1 + Z) bytes of arrival counters; every launch leaves them zero again - so a buffer serves launches of ONE Z:
+ * zero it again before a launch with another Z, whose counters lie where this one's partial sums were). Refused on the host, before any device work, with a message that names
+ * the limit: null pointers; B, Z < 1 or B * Z > 2^28; H, n_ks, C[h], ks[k] or ld out of range; a head outside the row; overlapping heads. */
+size_t egx_segmented_ce_scratch(int B, int Z, int H, int n_ks);
+int egx_segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C,
+                     const int* ks, int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* d_logits,
+                     void* scratch, void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
