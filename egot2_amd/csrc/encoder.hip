@@ -830,6 +830,13 @@ int egx_segmented_ce(const float* logits, int ld, const int64_t* target, int B, 
                         (hipStream_t)stream);
 }
 
+// ABI v19 addition: the LTA validation step (lta_val.hip); every argument is checked on the host before any device work
+int egx_lta_validate(const float* logits, int ld, const int64_t* labels, int B, int Z, int H, const int* col0, const int* C, int K,
+                     uint64_t seed, const uint64_t* seed_ptr, const int64_t* preds_in, int64_t* preds, int* min_dist, int64_t* dist_sum,
+                     void* stream) {
+    return lta_validate(logits, ld, labels, B, Z, H, col0, C, K, seed, seed_ptr, preds_in, preds, min_dist, dist_sum, (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

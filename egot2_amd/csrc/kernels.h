@@ -134,6 +134,11 @@ size_t segmented_ce_scratch_bytes(int B, int Z, int H, int n_ks);
 int segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C, const int* ks,
                  int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* dlogits, void* scratch, hipStream_t st);
 
+// lta_val.hip: the LTA validation step (K sampled futures per clip and head, prefix edit distances, their sums) in one launch
+constexpr int LTA_VAL_MAX_K = 8, LTA_VAL_MAX_Z = 64;
+int lta_validate(const float* logits, int ld, const int64_t* labels, int B, int Z, int H, const int* col0, const int* C, int K, uint64_t seed,
+                 const uint64_t* seed_ptr, const int64_t* preds_in, int64_t* preds, int* min_dist, int64_t* dist_sum, hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

@@ -2127,6 +2127,91 @@ def segmented_cross_entropy(preds, labels, ks=(1, 5), out=None):
     return loss, {"correct": correct, "n_valid": n_valid, "loss_terms": terms}
 
 
+# ---- the LTA validation step: K sampled futures per clip and head + prefix edit distances in one launch (csrc/lta_val.hip) -----------
+LTA_VAL_MAX_K, LTA_VAL_MAX_Z = 8, 64
+_LTA_VAL_CALLS = [0]
+
+
+def _lta_val_host_seed() -> int:
+    """A fresh host seed per call, counter-based like the translators' dropout seed (no device sync); torch.manual_seed makes it repeatable."""
+    _LTA_VAL_CALLS[0] += 1
+    return (torch.initial_seed() * 0x9E3779B97F4A7C15 + _LTA_VAL_CALLS[0] * 0xD1B54A32D192ED03 + 0x17A) & (2**63 - 1)
+
+
+def lta_validate(preds, labels=None, k: int = 1, seed=None, seed_ptr=None, tokens=None, out=None):
+    """-> (tokens, stats): `generate(..., k)` of the LTA models and the integers behind AUED (HOI/tasks/lta/long_term_anticipation.py:222-248,
+    HOI/evaluation/lta/lta_metrics.py:86-114) in one launch (egx_lta_validate), nothing synchronises.
+
+    preds: list of (B, Z, C_h) fp32 heads (1 .. 4, C_h <= 2048, Z <= 64), read in place when they are views of one stack (`decode()`),
+    one torch.cat otherwise; labels: int64 (B, Z, H) or None (no metric); k: 1 .. 8 sequences per clip.
+    tokens: list of H (B, K, Z) int64 tensors. k = 1: the row argmax (lowest index among equals); k > 1: k independent draws per row from
+    the softmax of the head, by inverse cdf on words of the library's counter generator keyed by `seed` (an int; None: a fresh one per
+    call) or, with `seed_ptr` (a one-element int64 device tensor or its address), by the word that holds when the launch runs. A row with a
+    NaN or +inf, or without a finite logit, yields -1.
+    stats (labels given): `min_dist` int32 (B, Z, H) - min over k of the Levenshtein distance of the first z + 1 tokens to the first z + 1
+    labels - and `dist_sum` int64 (Z, H), its sum over the clips: ED_z = dist_sum[z, h] / (B (z + 1)).
+    tokens=[(B, K, Z) int64, ...] (or one (H, B, K, Z) tensor): the metric-only entry - no sampling, `preds` may be None, the metric of these
+    tokens against `labels`. out: preallocated `preds` (H, B, K, Z) int64, `min_dist`, `dist_sum` (train.LTAValidation's buffers)."""
+    lib = _lib.load()
+    k = int(k)
+    out = out or {}
+    with torch.no_grad():
+        tok_in = None
+        if tokens is not None:
+            tok_in = tokens if isinstance(tokens, torch.Tensor) else torch.stack(list(tokens), dim=0)
+            if tok_in.dim() != 4 or tok_in.dtype != torch.int64 or not tok_in.is_cuda:
+                raise ValueError("lta_validate: tokens must be int64 (B, K, Z) tensors, one per head, on the GPU")
+            tok_in = tok_in.contiguous()
+            H, B, k, Z = tok_in.shape
+            dev = tok_in.device
+            if labels is None:
+                raise ValueError("lta_validate: tokens= is the metric-only entry and needs labels")
+            addr, ld, col0, widths = None, 0, [], []
+        else:
+            preds = list(preds)
+            H = len(preds)
+            if not 1 <= H <= SEG_CE_MAX_HEADS:
+                raise ValueError(f"lta_validate takes 1 to {SEG_CE_MAX_HEADS} heads, got {H}")
+            for h, p in enumerate(preds):
+                _dev_f32(p[:0], f"preds[{h}]")                   # device / dtype refusal only: the heads stay the views they are
+            p0 = preds[0]
+            if any(p.dim() != 3 or p.shape[:2] != p0.shape[:2] or p.device != p0.device for p in preds):
+                raise ValueError(f"lta_validate expects (B, Z, C_h) heads of one batch, got {[tuple(p.shape) for p in preds]}")
+            B, Z, dev = p0.shape[0], p0.shape[1], p0.device
+            widths = [p.shape[2] for p in preds]
+            win = _seg_windows(preds)
+            if win is None:                                     # one concatenation builds the stack
+                stack = torch.cat(preds, dim=-1).contiguous()
+                ld, col0, off = stack.shape[2], [], 0
+                for w in widths:
+                    col0.append(off)
+                    off += w
+                addr = stack.data_ptr()
+            else:
+                addr, ld, col0 = win
+        if labels is not None:
+            if labels.dtype != torch.int64 or tuple(labels.shape) != (B, Z, H) or labels.device != dev:
+                raise ValueError(f"labels must be an int64 tensor of shape (B, Z, H) = {(B, Z, H)} on the predictions' device")
+            labels = labels.contiguous()
+        if isinstance(seed_ptr, torch.Tensor):
+            if seed_ptr.dtype != torch.int64 or seed_ptr.numel() != 1 or seed_ptr.device != dev:
+                raise ValueError("lta_validate: seed_ptr must be a one-element int64 tensor on the predictions' device")
+            seed_ptr = seed_ptr.data_ptr()
+        if seed is None:
+            seed = _lta_val_host_seed() if (k > 1 and not seed_ptr and tok_in is None) else 0
+        toks = out["preds"] if "preds" in out else torch.empty((H, B, k, Z), dtype=torch.int64, device=dev)
+        if tuple(toks.shape) != (H, B, k, Z) or toks.dtype != torch.int64 or not toks.is_contiguous():
+            raise ValueError(f"lta_validate: out['preds'] must be a contiguous int64 tensor of shape (H, B, K, Z) = {(H, B, k, Z)}")
+        md = ds = None
+        if labels is not None:
+            md = out["min_dist"] if "min_dist" in out else torch.empty((B, Z, H), dtype=torch.int32, device=dev)
+            ds = out["dist_sum"] if "dist_sum" in out else torch.empty((Z, H), dtype=torch.int64, device=dev)
+        ia = lambda v: (C.c_int * max(len(v), 1))(*v)  # noqa: E731
+        check(lib.egx_lta_validate(addr, ld, ptr(labels), B, Z, H, ia(col0), ia(widths), k, _seed64(seed), seed_ptr or None, ptr(tok_in),
+                                   ptr(toks), ptr(md), ptr(ds), _stream()))
+    return [toks[h] for h in range(H)], {"min_dist": md, "dist_sum": ds}
+
+
 # ---- EgoT2-g sequence decoder pieces (SURVEY.md §8f row F1; kernels in csrc/decoder.hip) ------------------------------
 class LayerNormFn(torch.autograd.Function):
     """y = LayerNorm(x + res) * w + b over the last dimension of 2-D inputs (post-LN residual blocks)."""

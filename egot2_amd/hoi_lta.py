@@ -164,7 +164,14 @@ class _LTATranslator(nn.Module, TranslatorMixin):
         assert isinstance(x, list) and len(x) >= 1
         return torch.stack([model([pathway[:, i] for pathway in x]) for i in range(x[0].shape[1])], dim=1)
 
+    # generate() runs functional.lta_validate (ONE egx_lta_validate launch: argmax at k = 1, k inverse-cdf draws per row from the library's
+    # counter generator otherwise) instead of the torch.distributions path below when this is set (the switch predict_ac of hoi_multitask
+    # uses). Off by default: the draws then come from torch's generator, as in the reference.
+    egx_generate = False
+
     def _generate(self, x, k):
+        if self.egx_generate:
+            return F_egx.lta_validate(x, None, k)[0]
         results = []
         for head_x in x:
             if k > 1:

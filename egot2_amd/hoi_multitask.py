@@ -436,7 +436,14 @@ class TaskTranslationPromptTransformerActionTask(nn.Module, TranslatorMixin, Dec
             preds_noun = preds_noun.unsqueeze(dim=1)
         return [preds_verb, preds_noun]
 
+    # generate() runs functional.lta_validate (one egx_lta_validate launch) instead of the torch.distributions path when this is set; off
+    # by default, as TaskPromptTransformer.egx_generate is
+    egx_generate = False
+
     def generate(self, x):
+        if self.egx_generate:
+            from .functional import lta_validate
+            return lta_validate(self.predict(x, 'lta'), None, self.k)[0]
         from torch.distributions.categorical import Categorical
         results = []
         for head_x in self.predict(x, 'lta'):

@@ -11,6 +11,8 @@ per-step learning-rate schedulers (HOI/optimizers/lta/lr_scheduler.py:11-41) eva
 restates construct_optimizer + lr_factory on both.
 `LTACriterion` is the criterion of the long-term-anticipation task (HOI/tasks/lta/long_term_anticipation.py:182-203: 40 cross-entropies
 and the top-1 / top-5 errors of every (future step, head) pair) as one launch without a host synchronisation.
+`LTAValidation` is that task's validation step (:222-248: K sampled futures per clip and head, and the edit distances behind AUED,
+HOI/evaluation/lta/lta_metrics.py:86-114) as one launch, capturable, with one device-to-host copy in step_result().
 """
 from __future__ import annotations
 
@@ -111,6 +113,117 @@ class LTACriterion(nn.Module):
                     errs.append(e)
                 res[f"{prefix}_{h}_top{k}_err"] = float(sum(errs) / len(errs))
         res[f"{prefix}_loss"] = float(host[0:1].view("float32")[0])
+        return res
+
+
+class LTAValidation(nn.Module):
+    """The validation step of the long-term-anticipation task, LongTermAnticipationTask.validation_step
+    (HOI/tasks/lta/long_term_anticipation.py:222-248; :313-341 for the sequence tasks):
+
+        preds = model.generate(input, k=K)                                   # K x Categorical(logits).sample() per head, argmax at K = 1
+        step_result[f"val_{h}_" + key] = AUED(pred.permute(0, 2, 1).cpu(), labels[:, :, h:h + 1])[key]       # one .cpu() per head, a Python
+                                                                             # loop of editdistance.eval (evaluation/lta/lta_metrics.py:86-114)
+
+    as ONE launch (functional.lta_validate) without a host synchronisation, capturable in a graph; `step_result()` is ONE device-to-host copy.
+    preds: the list of (B, Z, C_h) tensors `forward_features` of the LTA translators returns; labels: int64 (B, Z, H).
+
+    The tokens (H, B, K, Z), min_dist (B, Z, H) and dist_sum (Z, H) live in persistent buffers per (device, B, Z, H), allocated on the first
+    eager call (a capture cannot allocate them: run an eager call first) and refreshed by every call or replay. The module owns a seed word
+    per device; every call reads it on the stream and enqueues egx_seed_advance behind the launch, so consecutive calls - and replays of a
+    captured call - draw fresh sequences. `manual_seed(s)` sets it. A host `seed=` (repeatable draws) is refused inside a capture when K > 1,
+    as a host dropout seed is. A row with a NaN or +inf, or without a finite logit, yields token -1 (the reference raises); ties at K = 1 go
+    to the lowest index."""
+
+    def __init__(self, k: int = 5):
+        super().__init__()
+        self.k = int(k)
+        if not 1 <= self.k <= F_egx.LTA_VAL_MAX_K:
+            raise ValueError(f"LTAValidation: k={k} (needs 1 <= k <= {F_egx.LTA_VAL_MAX_K} sequences per clip)")
+        self._bufs: Dict[tuple, dict] = {}
+        self._seeds: Dict[tuple, torch.Tensor] = {}
+        self._seed0: Optional[int] = None
+        self._last: Optional[dict] = None
+
+    @staticmethod
+    def _capturing(device) -> bool:
+        return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def manual_seed(self, s: int) -> "LTAValidation":
+        """Set the device seed word (of every device used so far, and of those to come) to `s`."""
+        self._seed0 = int(s) & (2**64 - 1)
+        signed = self._seed0 - (1 << 64) if self._seed0 >= (1 << 63) else self._seed0
+        for t in self._seeds.values():
+            t.fill_(signed)
+        return self
+
+    def seed_word(self, device) -> torch.Tensor:
+        """The one-element int64 device tensor that holds the seed the NEXT call on `device` draws with (its bits are the uint64 seed)."""
+        device = torch.device(device)
+        key = (device.type, device.index)
+        t = self._seeds.get(key)
+        if t is None:
+            if self._capturing(device):
+                raise RuntimeError("LTAValidation: run one eager step at this problem size before capturing it in a graph")
+            s = self._seed0 if self._seed0 is not None else (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0x17A) & (2**64 - 1)
+            t = self._seeds[key] = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=device)
+        return t
+
+    def _result_buffers(self, device, B: int, Z: int, H: int) -> dict:
+        device = torch.device(device)
+        key = (device.type, device.index, B, Z, H)
+        b = self._bufs.get(key)
+        if b is None:
+            if self._capturing(device):
+                # a buffer created inside a capture would live in that graph's private pool
+                raise RuntimeError("LTAValidation: run one eager step at this problem size before capturing it in a graph")
+            b = self._bufs[key] = {"B": B, "Z": Z, "H": H,
+                                   "preds": torch.zeros((H, B, self.k, Z), dtype=torch.int64, device=device),
+                                   "min_dist": torch.zeros((B, Z, H), dtype=torch.int32, device=device),
+                                   "dist_sum": torch.zeros((Z, H), dtype=torch.int64, device=device)}
+        return b
+
+    def forward(self, preds, labels: torch.Tensor, seed: Optional[int] = None):
+        """-> tokens, the list of (B, K, Z) int64 tensors `generate` returns (views of the persistent buffer). seed: a host seed for
+        repeatable draws (the device word is then neither read nor advanced)."""
+        preds = list(preds)
+        dev = preds[0].device
+        b = self._result_buffers(dev, preds[0].shape[0], preds[0].shape[1], len(preds))
+        if seed is not None:
+            if self.k > 1 and self._capturing(dev):
+                raise RuntimeError("LTAValidation: k > 1 draws with a host seed cannot be captured in a graph: every replay would repeat the same "
+                                   "sequences; leave seed=None (the device seed word advances on the stream)")
+            tokens, _ = F_egx.lta_validate(preds, labels, self.k, seed=seed, out=b)
+        else:
+            word = self.seed_word(dev)
+            tokens, _ = F_egx.lta_validate(preds, labels, self.k, seed_ptr=word, out=b)
+            _lib.check(_lib.load().egx_seed_advance(word.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        self._last = b
+        return tokens
+
+    def stats(self) -> dict:
+        """Device tensors of the most recent call (or replay): `tokens` (H, B, K, Z), `min_dist`, `dist_sum`. Reading them does not synchronise."""
+        if self._last is None:
+            raise RuntimeError("LTAValidation: no forward has run yet")
+        return {"tokens": self._last["preds"], "min_dist": self._last["min_dist"], "dist_sum": self._last["dist_sum"]}
+
+    def step_result(self, prefix: str = "val") -> Dict[str, float]:
+        """The reference's step_result of the most recent call (or replay), from ONE device-to-host copy (it synchronises), in fp64:
+        f"{prefix}_{h}_ED_{z}" = dist_sum[z, h] / (B (z + 1)), f"{prefix}_{h}_AUED" = trapz over z / (Z - 1) (nan at Z = 1, as numpy gives
+        the reference). Across ranks: all-reduce dist_sum and B first."""
+        if self._last is None:
+            raise RuntimeError("LTAValidation: no forward has run yet")
+        import numpy as np
+        b = self._last
+        B, Z, H = b["B"], b["Z"], b["H"]
+        ds = b["dist_sum"].cpu().numpy().astype(np.float64)
+        res: Dict[str, float] = {}
+        for h in range(H):
+            ed = ds[:, h] / (B * np.arange(1, Z + 1, dtype=np.float64))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                area = float(((ed[1:] + ed[:-1]) / 2.0).sum()) if Z > 1 else 0.0        # np.trapz, dx = 1
+                res[f"{prefix}_{h}_AUED"] = float(np.float64(area) / np.float64(Z - 1))
+            for z in range(Z):
+                res[f"{prefix}_{h}_ED_{z}"] = float(ed[z])
         return res
 
 

@@ -587,6 +587,45 @@ size_t egx_segmented_ce_scratch(int B, int Z, int H, int n_ks);
 int egx_segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C,
                      const int* ks, int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* d_logits,
                      void* scratch, void* stream);
+/* ---- ABI v19 (additions over v18: new symbols only, no existing signature changes, so EGX_ABI_VERSION - which a binding compares
+ * for equality - stays 18): the validation step of the long-term-anticipation task in one launch -------------------------
+ * LongTermAnticipationTask.validation_step, HOI/tasks/lta/long_term_anticipation.py:222-248 (and :313-341 for the sequence tasks):
+ * model.generate(input, k = K) - Categorical(logits = head).sample() K times per head, argmax at K = 1,
+ * HOI/models/lta/lta_models_lta_transfer.py generate() - then a permute, one .cpu() per head and AUED
+ * (HOI/evaluation/lta/lta_metrics.py:86-114), a Python loop of editdistance.eval over every clip, prefix length and sequence. Here:
+ *   logits   fp32, R = B * Z rows (row b * Z + z) of row stride `ld`, H heads as column windows col0[h], C[h] (HOST arrays): the layout
+ *            and the rules of egx_segmented_ce (1 <= C[h] <= 2048, H <= 4, disjoint, rows unaligned). NULL allowed with preds_in.
+ *   labels   int64 (B, Z, H), contiguous. NULL: no metric (min_dist and dist_sum must then be NULL too).
+ *   K        1 .. 8 sequences per clip and head; Z <= 64 future steps; B * Z <= 2^28.
+ *   seed     by value; with seed_ptr (device address of a uint64, as egx_config.seed_ptr) the word is read on the stream instead, so
+ *            replays of a captured graph draw fresh sequences when egx_seed_advance follows the call in the graph. K > 1 with a host
+ *            seed is refused inside a stream capture (every replay would repeat the draws), as the dropout seed is.
+ *   preds_in optional int64 (H, B, K, Z): the metric-only entry. Sampling is skipped, the metric is computed on these tokens and
+ *            `preds` (NULL allowed here) receives a copy.
+ * Outputs, every element written by every call:
+ *   preds    int64 (H, B, K, Z); slice h is the (B, K, Z) tensor generate() returns for head h.
+ *            K = 1: the row argmax, the lowest index among equal logits.
+ *            K > 1: draw k of row r = b * Z + z of head h is the class j with cdf[j - 1] <= u < cdf[j], where cdf is the running sum of
+ *            the max-subtracted softmax of the head's window and u = (w + 0.5) / 2^32 with w the 32-bit word k of the row from the
+ *            library's counter generator (csrc/common.h): key = site_key(seed, layer = 0x17A, site = h); (x, y) = rand_quad(key, r, k >> 1);
+ *            w = x for even k, y for odd k. The K draws of a row are independent (K words), like K .sample() calls. A class with a -inf
+ *            logit has probability 0 and is never drawn. The cdf is accumulated in blocks (64 contiguous chunks of <= 32 classes, chunk
+ *            totals added in order: chains of <= 32 + 64 additions), is exactly non-decreasing, and the comparison u * cdf[C - 1] against
+ *            the unnormalised cdf runs in fp64; against an fp64 softmax the cdf is within 1e-5 (tests/lta_val_ref.py check_draws).
+ *   min_dist int32 (B, Z, H), optional: min over k of Lev(preds[h, b, k, :z + 1], labels[b, :z + 1, h]), the plain Levenshtein distance
+ *            (insert, delete, substitute; integer equality, no ignore index) - what the editdistance package computes. All Z prefixes
+ *            of a sequence are the diagonal of one table.
+ *   dist_sum int64 (Z, H), optional: sum of min_dist over b (a memset node + 64-bit integer atomics: the same bits on every run).
+ *            ED_z of the reference = dist_sum[z, h] / (B * (z + 1)); across ranks, all-reduce dist_sum and B.
+ * Two deliberate differences from the reference: (1) a row that holds a NaN or +inf, or has no finite logit, yields token -1 for every
+ * draw (Categorical raises), and a negative token - handed in through preds_in too - equals no label; (2) ties at K = 1 go to the
+ * lowest index (torch.argmax leaves them open).
+ * One launch on `stream` plus at most one memset node; no allocation, no scratch, capturable. Refused on the host, before any device
+ * work, with a message that names the limit: null pointers (logits and preds_in both NULL included); B, Z, K, H, C[h] or ld out of
+ * range; B * Z > 2^28; a head outside the row; overlapping heads. */
+int egx_lta_validate(const float* logits, int ld, const int64_t* labels, int B, int Z, int H, const int* col0, const int* C, int K,
+                     uint64_t seed, const uint64_t* seed_ptr, const int64_t* preds_in, int64_t* preds, int* min_dist,
+                     int64_t* dist_sum, void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
