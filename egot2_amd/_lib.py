@@ -219,6 +219,10 @@ SIGNATURES = {
     # ABI v19 addition: the LTA validation step in one launch (col0 / C are host int arrays; seed by value, seed_ptr a device address)
     "egx_lta_validate": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                    C.c_uint64, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # ABI v20 additions: the PNR keyframe criterion and metrics in one launch (cols is a host int array or NULL)
+    "egx_keyframe_scratch": (C.c_size_t, [C.c_int]),
+    "egx_keyframe_criterion": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp,
+                                         _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

@@ -837,6 +837,16 @@ int egx_lta_validate(const float* logits, int ld, const int64_t* labels, int B, 
     return lta_validate(logits, ld, labels, B, Z, H, col0, C, K, seed, seed_ptr, preds_in, preds, min_dist, dist_sum, (hipStream_t)stream);
 }
 
+// ABI v20 additions: the PNR keyframe criterion and metrics (keyframe.hip); every argument is checked on the host before any device work
+size_t egx_keyframe_scratch(int B) { return keyframe_scratch_bytes(B); }
+int egx_keyframe_criterion(const float* logits, int ld, int B, int T, const int* cols, int V, int kind, const float* target,
+                           const int64_t* label, const int64_t* state_change, const double* fps, const int64_t* clip_start,
+                           const int64_t* clip_end, const int64_t* pnr_frame, float* loss, float* loss_rows, float* d_logits, int* pred,
+                           int* label_frame, int* counts, double* dist, double* dist_sum, void* scratch, void* stream) {
+    return keyframe_criterion(logits, ld, B, T, cols, V, kind, target, label, state_change, fps, clip_start, clip_end, pnr_frame, loss,
+                              loss_rows, d_logits, pred, label_frame, counts, dist, dist_sum, scratch, (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

@@ -139,6 +139,15 @@ constexpr int LTA_VAL_MAX_K = 8, LTA_VAL_MAX_Z = 64;
 int lta_validate(const float* logits, int ld, const int64_t* labels, int B, int Z, int H, const int* col0, const int* C, int K, uint64_t seed,
                  const uint64_t* seed_ptr, const int64_t* preds_in, int64_t* preds, int* min_dist, int64_t* dist_sum, hipStream_t st);
 
+// keyframe.hip: the PNR keyframe criterion (BCE / masked CE on the T frame logits of a clip), keyframe distance and accuracy in one launch
+constexpr int KEYFRAME_MAX_T = 64, KEYFRAME_MAX_V = 2048, KEYFRAME_MAX_ROWS = 1 << 28;
+enum KeyframeKind { KEYFRAME_BCE = 0, KEYFRAME_CE = 1, KEYFRAME_METRIC = 2 };       // the values of the C ABI's EGX_KF_* enum
+size_t keyframe_scratch_bytes(int B);
+int keyframe_criterion(const float* logits, int ld, int B, int T, const int* cols, int V, int kind, const float* target, const int64_t* label,
+                       const int64_t* state_change, const double* fps, const int64_t* clip_start, const int64_t* clip_end,
+                       const int64_t* pnr_frame, float* loss, float* loss_rows, float* dlogits, int* pred, int* label_frame, int* counts,
+                       double* dist, double* dist_sum, void* scratch, hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

@@ -2127,6 +2127,141 @@ def segmented_cross_entropy(preds, labels, ks=(1, 5), out=None):
     return loss, {"correct": correct, "n_valid": n_valid, "loss_terms": terms}
 
 
+# ---- the PNR keyframe criterion: BCE / masked CE, keyframe distance and accuracy in one launch (csrc/keyframe.hip) -----------------------
+KEYFRAME_MAX_T, KEYFRAME_MAX_V = 64, 2048
+KEYFRAME_KINDS = {"bce": 0, "cross_entropy": 1, None: 2}
+_KF_SCRATCH = {}
+
+
+def _kf_scratch(device, nbytes: int) -> torch.Tensor:
+    """Scratch of egx_keyframe_criterion, by the rules of _seg_scratch: one per device, zero-filled once, never created inside a capture.
+    Its size does not depend on the shape and every launch leaves its arrival counter zero, so every shape shares it."""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    t = _KF_SCRATCH.get(key)
+    if t is None or t.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("keyframe_criterion: run one eager step at this problem size before capturing it in a graph")
+        if t is not None:
+            _LCE_RETIRED.append(t)
+        t = _KF_SCRATCH[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+def _kf_rows(t, B: int, dtype, dev, name: str):
+    """A per-clip argument as a contiguous (B,) device tensor of `dtype` ((B,), (B, 1) or (1, B) in; a no-op when it already is one)."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    if t.numel() != B:
+        raise ValueError(f"keyframe_criterion: {name} has {t.numel()} elements, expected one per clip ({B})")
+    return t.reshape(B).to(device=dev, dtype=dtype).contiguous()
+
+
+class KeyframeCriterionFn(torch.autograd.Function):
+    """(loss, loss_rows, pred, label_frame, counts, dist, dist_sum) of egx_keyframe_criterion; the same launch leaves d loss / d logits of the
+    whole (B, ld) block behind. `out` (optional dict of preallocated result tensors): where the results go (train.KeyframeCriterion's
+    persistent buffers); only `loss` carries gradient."""
+
+    @staticmethod
+    def forward(ctx, preds, target, label, state_change, fps, start, end, pnr, kind, cols, out):
+        lib = _lib.load()
+        _dev_f32(preds[:0], "preds")                        # device / dtype refusal only: the logits stay the view they are
+        if kind not in KEYFRAME_KINDS:
+            raise ValueError(f"keyframe_criterion: kind={kind!r} (needs 'bce', 'cross_entropy' or None for the metric alone)")
+        if preds.dim() == 3 and preds.shape[1] == 1:
+            x = preds[:, 0]                                 # the (B, 1, T) tensor forward_features returns
+        elif preds.dim() == 2:
+            x = preds
+        else:
+            raise ValueError(f"keyframe_criterion expects (B, T), (B, 1, T) or (B, V) logits, got {tuple(preds.shape)}")
+        B, V = x.shape
+        if B < 1:
+            raise ValueError("keyframe_criterion: empty batch")
+        cols = None if cols is None else [int(c) for c in cols]
+        T = V if cols is None else len(cols)
+        if x.stride(1) != 1 or (B > 1 and x.stride(0) < V):
+            x = x.contiguous()
+        ld = x.stride(0) if B > 1 else V                    # read in place: the row stride is the launch's ld
+        dev = x.device
+        tgt = None
+        if target is not None:
+            if tuple(target.shape) != (B, T):
+                raise ValueError(f"keyframe_criterion: target must have shape (B, T) = {(B, T)}, got {tuple(target.shape)}")
+            tgt = target.to(device=dev, dtype=torch.float32).contiguous()
+        lab = _kf_rows(label, B, torch.int64, dev, "label")
+        sc = _kf_rows(state_change, B, torch.int64, dev, "state_change")
+        timing = [_kf_rows(fps, B, torch.float64, dev, "fps"), _kf_rows(start, B, torch.int64, dev, "clip_start_frame"),
+                  _kf_rows(end, B, torch.int64, dev, "clip_end_frame"), _kf_rows(pnr, B, torch.int64, dev, "pnr_frame")]
+        if any(t is None for t in timing) and not all(t is None for t in timing):
+            raise ValueError("keyframe_criterion: fps and info (clip_start_frame, clip_end_frame, pnr_frame) go together: all, or none")
+        timed = timing[0] is not None
+        with_loss = kind is not None
+        out = out or {}
+
+        def buf(name, shape, dtype, wanted=True):
+            if not wanted:
+                return None
+            return out[name] if name in out else torch.empty(shape, dtype=dtype, device=dev)
+
+        loss = buf("loss", (), torch.float32, with_loss)
+        loss_rows = buf("loss_rows", (B,), torch.float32, with_loss)
+        pred = buf("pred", (B,), torch.int32)
+        label_frame = buf("label_frame", (B,), torch.int32)
+        counts = buf("counts", (4,), torch.int32)
+        dist = buf("dist", (B,), torch.float64, timed)
+        dist_sum = buf("dist_sum", (), torch.float64, timed)
+        need = with_loss and ctx.needs_input_grad[0]
+        dl = torch.empty((B, ld), dtype=torch.float32, device=dev) if need else None
+        nbytes = lib.egx_keyframe_scratch(B)
+        if nbytes == 0:
+            check(1)
+        scratch = _kf_scratch(dev, nbytes)
+        ca = (C.c_int * T)(*cols) if cols is not None else None
+        check(lib.egx_keyframe_criterion(x.data_ptr(), ld, B, T, ca, V, KEYFRAME_KINDS[kind], ptr(tgt), ptr(lab), ptr(sc), ptr(timing[0]),
+                                         ptr(timing[1]), ptr(timing[2]), ptr(timing[3]), ptr(loss), ptr(loss_rows), ptr(dl), ptr(pred),
+                                         ptr(label_frame), ptr(counts), ptr(dist), ptr(dist_sum), ptr(scratch), _stream()))
+        ctx.grad_shape = (tuple(preds.shape), V) if need else None
+        if need:
+            ctx.save_for_backward(dl)
+        # fresh tensor objects over the result memory, as in SegmentedCEFn: a persistent buffer must not own this call's autograd graph
+        res = tuple(None if t is None else t.detach() for t in (loss, loss_rows, pred, label_frame, counts, dist, dist_sum))
+        ctx.mark_non_differentiable(*[t for t in res[1:] if t is not None])
+        ctx.set_materialize_grads(False)
+        return res
+
+    @staticmethod
+    def backward(ctx, g_loss, *_rest):
+        if ctx.grad_shape is None or g_loss is None:
+            return (None,) * 11
+        (dl,) = ctx.saved_tensors
+        u = _UNIT_GRAD.get(dl.device.index)
+        if u is None or g_loss.data_ptr() != u.data_ptr():
+            dl = dl * g_loss
+        shape, V = ctx.grad_shape
+        return (dl[:, :V].reshape(shape),) + (None,) * 10
+
+
+def keyframe_criterion(preds, target=None, label=None, state_change=None, fps=None, info=None, kind="bce", cols=None, out=None):
+    """-> (loss or None, stats): the training step of the PNR keyframe task after the model (HOI/tasks/pnr/video_taskspecific_pnr.py:24-63:
+    the BCE - or masked CE - loss, keyframe_distance and keyframe_accuracy of HOI/evaluation/pnr/metrics.py:23-80) in one launch, and with
+    `cols` PnrOsccMetric.pnr_distance / oscc_acc (metrics.py:102-134) on decoder logits. Nothing synchronises.
+
+    preds: fp32 (B, T), or the (B, 1, T) tensor `forward_features` returns (read in place: ld = its row stride), or (B, V) decoder logits
+    with cols = the T vocabulary columns of the frames (T <= 64, V <= 2048). target: the one-hot (B, T) labels (any dtype; soft values
+    allowed); label: the label frame as an int64 index (B), default argmax of target; state_change: (B) or (B, 1), default every clip counts;
+    fps (B) and info = {clip_start_frame, clip_end_frame, pnr_frame} go together. kind: "bce" (BCELoss(sigmoid(x)) in logit form, mean over
+    B * T), "cross_entropy" (mean over B of the state-change clips' CE) or None (metric only, loss is None).
+    stats, all device tensors: `pred` (B) int32, `label_frame` (B) int32, `counts` int32 [n_sc, n_correct, n_outside, B], `loss_rows` (B),
+    `dist` (B) fp64 seconds and `dist_sum` fp64 (with fps / info). keyframe_distance = dist_sum / n_sc (0.0 without a state-change clip),
+    pseudo_acc = n_correct / n_sc. `out`: preallocated result tensors (train.KeyframeCriterion). For a captured step pass device tensors of
+    the final dtypes (target fp32, the others int64 / fps fp64): a conversion is a copy the capture would record."""
+    info = info or {}
+    start, end, pnr = (info.get(k) for k in ("clip_start_frame", "clip_end_frame", "pnr_frame"))
+    loss, loss_rows, pred, label_frame, counts, dist, dist_sum = KeyframeCriterionFn.apply(preds, target, label, state_change, fps, start, end,
+                                                                                         pnr, kind, cols, out)
+    return loss, {"pred": pred, "label_frame": label_frame, "counts": counts, "loss_rows": loss_rows, "dist": dist, "dist_sum": dist_sum}
+
+
 # ---- the LTA validation step: K sampled futures per clip and head + prefix edit distances in one launch (csrc/lta_val.hip) -----------
 LTA_VAL_MAX_K, LTA_VAL_MAX_Z = 8, 64
 _LTA_VAL_CALLS = [0]

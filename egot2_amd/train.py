@@ -13,6 +13,9 @@ restates construct_optimizer + lr_factory on both.
 and the top-1 / top-5 errors of every (future step, head) pair) as one launch without a host synchronisation.
 `LTAValidation` is that task's validation step (:222-248: K sampled futures per clip and head, and the edit distances behind AUED,
 HOI/evaluation/lta/lta_metrics.py:86-114) as one launch, capturable, with one device-to-host copy in step_result().
+`KeyframeCriterion` is the PNR keyframe task's step after the model (HOI/tasks/pnr/video_taskspecific_pnr.py:24-63: BCE or masked CE,
+keyframe_distance and keyframe_accuracy of HOI/evaluation/pnr/metrics.py:23-80; with `cols` the EgoT2-g PnrOsccMetric) as one launch, and
+`OSCCCriterion` the state-change classification step (:138-160) on the LTA criterion's launch.
 """
 from __future__ import annotations
 
@@ -225,6 +228,143 @@ class LTAValidation(nn.Module):
             for z in range(Z):
                 res[f"{prefix}_{h}_ED_{z}"] = float(ed[z])
         return res
+
+
+class KeyframeCriterion(nn.Module):
+    """The training / validation step of the PNR keyframe task after the model, KeyframeLocalisation2Loader.training_step
+    (HOI/tasks/pnr/video_taskspecific_pnr.py:24-63, recipe HOI/configs/pnr/ts_pnr.yaml: LOSS_FUNC "bce"):
+
+        loss = BCELoss(mean)(sigmoid(preds.squeeze(1)), labels.float())       # "cross_entropy": mean(state_change_label.T * CE(preds, argmax(labels)))
+        keyframe_distance(preds, labels, state_change_label, fps, info), keyframe_accuracy(...)          # evaluation/pnr/metrics.py:23-80
+
+    as ONE launch (functional.keyframe_criterion) without a host synchronisation, so it can be the `loss_fn` of a GraphedStep; the reference's
+    two Python loops with four to six `.item()` reads per clip become that launch plus ONE device-to-host copy in `step_result()`.
+    preds: the (B, 1, T) tensor `forward_features` of the PNR translators returns (or (B, T)); labels: the one-hot (B, T) labels.
+
+    With `cols=` (the vocabulary columns of the frames) and `loss_func=None` it is the EgoT2-g metric on (B, V) decoder logits,
+    PnrOsccMetric.pnr_distance / oscc_acc (metrics.py:102-134); `labels` is then the int64 (B,) label index (for the two-column OSCC use: the
+    state-change label) or None.
+
+    loss, the four counts and dist_sum live in ONE persistent buffer per (device, B, T), the per-clip results next to it, allocated on the
+    first eager call (a capture cannot allocate them: run an eager step first, GraphedStep's warm-up does) and refreshed by every call or
+    replay. The loss is evaluated in logit form (where fp32 sigmoid saturates, BCELoss(sigmoid(x)) returns its clamp of 100 and a zero
+    gradient; this returns the true softplus and sigmoid - y), and pseudo_acc without a state-change clip is NaN (the reference divides by
+    zero)."""
+
+    def __init__(self, loss_func: Optional[str] = "bce", cols=None):
+        super().__init__()
+        if loss_func not in F_egx.KEYFRAME_KINDS:
+            raise ValueError(f"KeyframeCriterion: loss_func={loss_func!r} (needs 'bce', 'cross_entropy' or None)")
+        self.loss_func = loss_func
+        self.cols = None if cols is None else tuple(int(c) for c in cols)
+        if self.cols is not None and not 1 <= len(self.cols) <= F_egx.KEYFRAME_MAX_T:
+            raise ValueError(f"KeyframeCriterion: {len(self.cols)} columns (needs 1 to {F_egx.KEYFRAME_MAX_T} frames)")
+        self._bufs: Dict[tuple, dict] = {}
+        self._last: Optional[dict] = None
+
+    def _result_buffers(self, device, B: int, T: int) -> dict:
+        """dist_sum (fp64) | loss | pad | counts [n_sc, n_correct, n_outside, B] as views of one buffer of 4-byte words (`flat`), and the
+        per-clip pred, label_frame, loss_rows, dist."""
+        device = torch.device(device)
+        key = (device.type, device.index, B, T)
+        b = self._bufs.get(key)
+        if b is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # a buffer created inside a capture would live in that graph's private pool
+                raise RuntimeError("KeyframeCriterion: run one eager step at this problem size before capturing it in a graph")
+            flat = torch.zeros(8, dtype=torch.int32, device=device)
+            b = self._bufs[key] = {"flat": flat, "B": B, "T": T,
+                                   "dist_sum": flat[0:2].view(torch.float64).view(()),
+                                   "loss": flat[2:3].view(torch.float32).view(()),
+                                   "counts": flat[4:8],
+                                   "pred": torch.zeros(B, dtype=torch.int32, device=device),
+                                   "label_frame": torch.zeros(B, dtype=torch.int32, device=device),
+                                   "loss_rows": torch.zeros(B, dtype=torch.float32, device=device),
+                                   "dist": torch.zeros(B, dtype=torch.float64, device=device)}
+        return b
+
+    def forward(self, preds, labels=None, state_change_label=None, fps=None, info=None):
+        """-> loss (None with loss_func=None). labels: (B, T) one-hot (the reference's `labels`), or - the metric with cols - the (B,) /
+        (B, 1) int64 label index."""
+        B = preds.shape[0]
+        T = len(self.cols) if self.cols is not None else preds.shape[-1]
+        b = self._result_buffers(preds.device, B, T)
+        target = label = None
+        if labels is not None:
+            if labels.dim() == 2 and tuple(labels.shape) == (B, T) and (T > 1 or self.loss_func is not None):
+                target = labels
+            else:
+                label = labels
+        loss, _ = F_egx.keyframe_criterion(preds, target, label, state_change_label, fps, info, kind=self.loss_func, cols=self.cols, out=b)
+        b["timed"] = fps is not None
+        self._last = b
+        return loss
+
+    def stats(self) -> dict:
+        """Device tensors of the most recent call (or replay): `loss`, `counts`, `dist_sum`, `pred`, `label_frame`, `loss_rows`, `dist`.
+        Reading them does not synchronise. What that call did not write is None, as functional.keyframe_criterion returns it: `dist` and
+        `dist_sum` without fps / info, `loss` and `loss_rows` with loss_func=None."""
+        if self._last is None:
+            raise RuntimeError("KeyframeCriterion: no forward has run yet")
+        b = self._last
+        unwritten = (() if b.get("timed", True) else ("dist", "dist_sum")) + (("loss", "loss_rows") if self.loss_func is None else ())
+        return {k: None if k in unwritten else b[k] for k in ("loss", "counts", "dist_sum", "pred", "label_frame", "loss_rows", "dist")}
+
+    def step_result(self, prefix: str = "train") -> Dict[str, float]:
+        """The reference's step_result of the most recent call (or replay), from ONE device-to-host copy (it synchronises: for logging).
+        "train": keyframe_loss, train_loss, loss, pseudo_acc = n_correct / n_sc (nan without a state-change clip),
+        keyframe_loc_metric_time_dist_train = dist_sum / n_sc (0.0 without one, as the reference returns). "val":
+        keyframe_loc_metric_time_dist_val, its negative (the checkpoint metric) and pseudo_acc. With cols and loss_func=None (the EgoT2-g
+        metric, any prefix): dist = dist_sum / B, err = n_outside / B, acc = n_correct / B. Across ranks: all-reduce counts and dist_sum."""
+        if self._last is None:
+            raise RuntimeError("KeyframeCriterion: no forward has run yet")
+        host = self._last["flat"].cpu().numpy()
+        dist_sum = float(host[0:2].view("float64")[0]) if self._last.get("timed", True) else float("nan")      # no fps / info: no distance
+        loss = float(host[2:3].view("float32")[0])
+        n_sc, n_correct, n_outside, B = (int(v) for v in host[4:8])
+        if self.cols is not None and self.loss_func is None:
+            return {"dist": dist_sum / B, "err": n_outside / B, "acc": n_correct / B}
+        acc = n_correct / n_sc if n_sc > 0 else float("nan")
+        dist = dist_sum / n_sc if n_sc > 0 else 0.0
+        if prefix == "train":
+            return {"keyframe_loss": loss, "train_loss": loss, "loss": loss, "pseudo_acc": acc, "keyframe_loc_metric_time_dist_train": dist}
+        if prefix == "val":
+            return {"keyframe_loc_metric_time_dist_val": dist, "keyframe_loc_metric_time_dist_val_neg": -dist, "pseudo_acc": acc}
+        raise ValueError(f"KeyframeCriterion.step_result: prefix={prefix!r} (needs 'train' or 'val')")
+
+
+class OSCCCriterion(nn.Module):
+    """The training step of the state-change classification task after the model, StateChangeClassification2Loader.training_step
+    (HOI/tasks/pnr/video_taskspecific_pnr.py:138-160): mean cross-entropy of the (B, 2, 1) output against the state-change label plus
+    state_change_accuracy (evaluation/pnr/metrics.py:11-20), as functional.segmented_cross_entropy with one future step, one head and
+    ks = (1,): one launch, no host synchronisation, `step_result()` is one device-to-host copy. Among equal logits the lower class wins."""
+
+    def __init__(self):
+        super().__init__()
+        self._crit = LTACriterion(ks=(1,))
+        self._B = 0
+
+    def forward(self, preds: torch.Tensor, state_change_label: torch.Tensor) -> torch.Tensor:
+        if preds.dim() != 3 or preds.shape[2] != 1:
+            raise ValueError(f"OSCCCriterion expects the (B, classes, 1) output of the OSCC translator, got {tuple(preds.shape)}")
+        B = preds.shape[0]
+        self._B = B
+        return self._crit([preds.squeeze(2).unsqueeze(1)], state_change_label.reshape(B, 1, 1).long())
+
+    def stats(self) -> dict:
+        return self._crit.stats()
+
+    def step_result(self, prefix: str = "train") -> Dict[str, float]:
+        """"train": state_change_loss, train_loss, loss, state_change_metric_train = correct / B; "val": state_change_metric_val."""
+        if self._crit._last is None:
+            raise RuntimeError("OSCCCriterion: no forward has run yet")
+        host = self._crit._last["flat"].cpu().numpy()           # loss | loss_terms (1) | n_valid (1) | correct (1)
+        loss, acc = float(host[0:1].view("float32")[0]), int(host[3]) / max(self._B, 1)
+        if prefix == "train":
+            return {"state_change_loss": loss, "train_loss": loss, "loss": loss, "state_change_metric_train": acc}
+        if prefix == "val":
+            return {"state_change_metric_val": acc}
+        raise ValueError(f"OSCCCriterion.step_result: prefix={prefix!r} (needs 'train' or 'val')")
 
 
 class LRSchedule:

@@ -626,6 +626,62 @@ int egx_segmented_ce(const float* logits, int ld, const int64_t* target, int B, 
 int egx_lta_validate(const float* logits, int ld, const int64_t* labels, int B, int Z, int H, const int* col0, const int* C, int K,
                      uint64_t seed, const uint64_t* seed_ptr, const int64_t* preds_in, int64_t* preds, int* min_dist,
                      int64_t* dist_sum, void* stream);
+/* ---- ABI v20 additions (new symbols only, as v19: EGX_ABI_VERSION stays 18): the criterion and the metrics of the PNR keyframe task
+ * in one launch -------------------------------------------------------------------------------------------------------------------
+ * KeyframeLocalisation2Loader.training_step, HOI/tasks/pnr/video_taskspecific_pnr.py:24-63 (also keyframe_detection.py:23-70; recipe
+ * HOI/configs/pnr/ts_pnr.yaml: LOSS_FUNC "bce", LOSS_REDUCTION "mean"): BCELoss(sigmoid(preds.squeeze(1)), labels.float()) - or, under
+ * LOSS_FUNC cross_entropy, mean(state_change_label.T * CE(preds, argmax(labels))) - then keyframe_distance and keyframe_accuracy
+ * (HOI/evaluation/pnr/metrics.py:23-80), two Python loops over the clips with four to six .item() reads per clip. The EgoT2-g HOI
+ * validation runs the same arithmetic on decoder logits (PnrOsccMetric.pnr_distance / oscc_acc, metrics.py:102-134, called at
+ * HOI/tasks/multitask/video_task.py:67,80): the argmax restricted to the vocabulary columns of '0'..'15' (or 'False' / 'True') and the
+ * share of rows whose unrestricted argmax falls outside that set. Here:
+ *   logits   fp32, B rows of row stride `ld` floats; rows need NO alignment. Frame t of row b is column cols[t] when `cols` (a HOST
+ *            int[T], copied into the launch; distinct entries in [0, V)) is given, else column t. 1 <= T <= 64 (the recipe: 16).
+ *            V = the meaningful columns of a row, T <= V <= ld, V <= 2048; without cols V == T. 1 <= B <= 2^28.
+ *   kind     EGX_KF_BCE needs target; EGX_KF_CE needs target or label; EGX_KF_METRIC takes no loss (loss, loss_rows, d_logits NULL).
+ *   target   fp32 (B, T) contiguous, values in [0, 1]: the one-hot labels.float() of the reference; soft values are allowed.
+ *   label    int64 (B): the label frame as an index. NULL: the label frame is argmax_t target (first maximum). Both NULL: no accuracy
+ *            is counted (n_correct = 0). A label outside [0, T) equals no prediction and, under CE, adds no loss and no gradient.
+ *   state_change  int64 (B), or NULL = every clip counts. Compared == 1, as `sc_label.item() == 1` is.
+ *   fps (fp64), clip_start, clip_end, pnr_frame (int64), each (B): all four, or none (then dist and dist_sum must be NULL).
+ * Outputs, every element written by every call:
+ *   loss       BCE: mean over B * T of min(softplus(-x), 100) * y + min(softplus(x), 100) * (1 - y).
+ *              CE: (1 / B) sum_b [sc_b == 1] nll_b, nll_b the max-subtracted log-softmax CE over the T frames against the label frame:
+ *              divided by B, NOT by the number of state-change clips, as torch.mean(state_change_label.T * loss) does.
+ *              loss = (sum_b loss_rows[b]) / B under both kinds.
+ *   loss_rows  (B), optional. BCE: the row's sum / T. CE: the masked nll_b.
+ *   d_logits   (B, ld), optional, EVERY element written: d loss / d logits. BCE: (sigmoid(x) - y) / (B * T) (the clamp at 100, reached
+ *              beyond |x| = 100, is not differentiated). CE: [sc_b == 1] (softmax - onehot) / B. Columns that are no frame: 0.
+ *   pred       (B) int32: argmax over the T frames with torch.argmax's rule: the first NaN if the row holds one, otherwise the lowest
+ *              index among equal maxima.
+ *   label_frame (B) int32, optional: the label frame, -1 where there is none.
+ *   counts     int32[4]: n_sc (clips with state_change == 1), n_correct (of those, pred == label frame), n_outside (rows whose argmax
+ *              over all V columns is not one of cols; 0 without cols), B.
+ *   dist       (B) fp64, optional: |((clip_end - clip_start) / T) * pred - (pnr_frame - clip_start)| / fps for a state-change clip,
+ *              evaluated in fp64 in exactly that order; 0 for the other clips. The reference's literal 16 is T; its fp32 rounding of the
+ *              first product is exact for every real clip (T = 16, spans below 2^20 frames), so on the recipe shape this is the
+ *              reference's number bit for bit.
+ *   dist_sum   fp64 scalar, optional: the sum of dist in a fixed order. keyframe_distance = dist_sum / n_sc, or 0.0 when n_sc == 0 (the
+ *              reference returns np.mean(0.0)). Across ranks: all-reduce counts and dist_sum.
+ * Two deliberate differences from torch: (1) the loss is evaluated in LOGIT form. BCELoss(sigmoid(x)) in fp32 rounds sigmoid to 1 for x
+ * above about 16.6 and returns its clamp of 100 with a zero gradient; this library returns the true softplus (clamped at 100) and the
+ * true gradient sigmoid - y. The two agree wherever fp32 sigmoid has not saturated. (2) pseudo_acc = n_correct / n_sc without a
+ * state-change clip is NaN here; the reference divides by zero.
+ * One launch on `stream`: a wave per clip, a lane per frame; no allocation, capturable. The clips are cut into at most 64 chunks, a
+ * workgroup of four waves each (a lane of the last workgroup adds one chunk): up to B = 256 every clip has a wave of its own, beyond that
+ * a wave walks ceil(B / 64) / 4 clips in turn, so the launch is sized for training batches, not for B near the 2^28 limit. Every sum runs in a fixed order (per-workgroup
+ * partials in scratch, added by the last workgroup to arrive): the same bits on every run, no float atomics.
+ * `scratch`: egx_keyframe_scratch(B) bytes (0: invalid B, see egx_last_error; the same size for every valid B), ZERO before the first
+ * use; it begins with a 64-byte arrival counter that every launch leaves zero, so one buffer serves launches of every shape.
+ * Refused on the host, before any device work, with a message that names the limit: null logits, pred, counts or scratch; B < 1 or
+ * B > 2^28; T, V or ld out of range; a cols entry outside [0, V) or a duplicate (so the kernel never reads outside a row); a kind
+ * whose inputs are missing; a loss output with EGX_KF_METRIC; only some of the four timing arrays; dist or dist_sum without them. */
+enum { EGX_KF_BCE = 0, EGX_KF_CE = 1, EGX_KF_METRIC = 2 };
+size_t egx_keyframe_scratch(int B);
+int egx_keyframe_criterion(const float* logits, int ld, int B, int T, const int* cols, int V, int kind, const float* target,
+                           const int64_t* label, const int64_t* state_change, const double* fps, const int64_t* clip_start,
+                           const int64_t* clip_end, const int64_t* pnr_frame, float* loss, float* loss_rows, float* d_logits,
+                           int* pred, int* label_frame, int* counts, double* dist, double* dist_sum, void* scratch, void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
