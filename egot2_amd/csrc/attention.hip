@@ -14,12 +14,6 @@
 
 namespace egx {
 
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    return v;
-}
-
 template <int DQ>
 __device__ __forceinline__ void stage_rows(float* dst, const float* __restrict__ src, int row_stride, int nrows) {
     // dst[r][DH + 4] <- src[r * row_stride + 0..DH)

@@ -73,6 +73,49 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_));
 }
 
+// Reductions over the 64 lanes of a wave by xor butterflies: every lane ends up with the result, the same bits in all of them.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// torch.argmax's order: a NaN beats every number, the larger number wins, and of two equals (two NaNs included) the lower index
+struct WaveBest { float v; int i; };
+__device__ __forceinline__ bool argmax_better(float va, int ia, float vb, int ib) {
+    const bool na = va != va, nb = vb != vb;
+    if (na != nb) return na;
+    if (na || va == vb) return ia < ib;
+    return va > vb;
+}
+__device__ __forceinline__ WaveBest wave_argmax(float v, int i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float vo = __shfl_xor(v, o, 64);
+        const int io = __shfl_xor(i, o, 64);
+        if (argmax_better(vo, io, v, i)) { v = vo; i = io; }
+    }
+    WaveBest b;
+    b.v = v; b.i = i;
+    return b;
+}
+// the sum over the 4 adjacent lanes of a quad
+__device__ __forceinline__ float quad_sum(float v) {
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    return v;
+}
+
 // Counter-based dropout RNG: a 64-bit (seed, site) key and a (row, column) element index -> 16 uniform bits.
 // Forward and backward regenerate identical masks; nothing is stored. ONE hash serves the four columns of a quad
 // (4c .. 4c+3): a multiply-fold round (32 x 32 -> 64, high ^ low: one v_mad_u64_u32) and one multiply-xorshift round give

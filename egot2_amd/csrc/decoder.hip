@@ -18,18 +18,6 @@ namespace egx {
 
 constexpr int SA_MAXQ = 8, SA_MAXK = 64, SA_MAXDH = 128;
 
-
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // grid = B * H, block = 64. LDS: K, V [Sk][dh + 1]; Q (and dO) [Sq][dh]; P / dS [Sq][64].
 template <bool BWD>
 __global__ __launch_bounds__(64) void small_attention_kernel(SmallAttnParams p) {
@@ -66,9 +54,9 @@ __global__ __launch_bounds__(64) void small_attention_kernel(SmallAttnParams p) 
             for (int c = 0; c < dh; ++c) s += Qs[i * dh + c] * Ks[lane * LDK + c];
             s *= p.scale;
         }
-        float m = wave_max64(s);
+        float m = wave_max(s);
         float e = live ? __expf(s - m) : 0.f;
-        float prob = e / wave_sum64(e);
+        float prob = e / wave_sum(e);
         float mask = 1.f;
         if (p.drop_thresh) mask = drop_scale(p.drop_key, (uint32_t)(blockIdx.x * SA_MAXQ + i), (uint32_t)lane, p.drop_thresh, p.drop_inv);
         Ps[i * 64 + lane] = prob * mask;
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(64) void small_attention_kernel(SmallAttnParams p) 
                 for (int c = 0; c < dh; ++c) dp += Gs[i * dh + c] * Vs[lane * LDK + c];
                 dp *= mask;
             }
-            float delta = wave_sum64(prob * dp);
+            float delta = wave_sum(prob * dp);
             Ds[i * 64 + lane] = live ? prob * (dp - delta) * p.scale : 0.f;
         }
     }
@@ -154,10 +142,10 @@ __global__ __launch_bounds__(SAL_NTH) void long_memory_attention_kernel(SmallAtt
     for (int i = wave; i < Sq; i += 4) {
         float m = -INFINITY;
         for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
-        m = wave_max64(m);
+        m = wave_max(m);
         float sum = 0.f;
         for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
-        sum = 1.f / wave_sum64(sum);
+        sum = 1.f / wave_sum(sum);
         for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;        // the plain probabilities (0 beyond Sk)
     }
     if constexpr (BWD) {
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(SAL_NTH) void long_memory_attention_kernel(SmallAtt
                 Ds[i * SKP + j] = dp;
                 delta += Ps[i * SKP + j] * dp;
             }
-            delta = wave_sum64(delta);
+            delta = wave_sum(delta);
             for (int j = lane; j < SKP; j += 64) {
                 float mask = 1.f;
                 if (p.drop_thresh) mask = drop_scale(p.drop_key, (uint32_t)(blockIdx.x * SA_MAXQ + i), (uint32_t)j, p.drop_thresh, p.drop_inv);

@@ -477,9 +477,9 @@ __global__ __launch_bounds__(CT) void ffn_fwd_kernel(FusedFwdParams p, int l) {
         __syncthreads();
         if (wave == 0) {
             float2 x = *reinterpret_cast<float2*>(pooled + 2 * lane);
-            float mean = wsum(x.x + x.y) * (1.f / FD);
+            float mean = wave_sum(x.x + x.y) * (1.f / FD);
             float dx = x.x - mean, dy = x.y - mean;
-            float rstd = rsqrtf(wsum(dx * dx + dy * dy) * (1.f / FD) + p.eps);
+            float rstd = rsqrtf(wave_sum(dx * dx + dy * dy) * (1.f / FD) + p.eps);
             float2 lw = *reinterpret_cast<const float2*>(CP + 3 * FD + 2 * lane);
             float2 lb = *reinterpret_cast<const float2*>(CP + 4 * FD + 2 * lane);
             float y0 = dx * rstd * lw.x + lb.x, y1 = dy * rstd * lw.y + lb.y;
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(CT) void ffn_fwd_kernel(FusedFwdParams p, int l) {
             float zmine = 0.f;
             for (int o = 0; o < p.head.n_out; ++o) {
                 float2 wv = w_lds ? *reinterpret_cast<const float2*>(CP + 1024 + o * FD + 2 * lane) : *reinterpret_cast<const float2*>(p.head.W + (size_t)o * FD + 2 * lane);
-                float sdot = wsum(y0 * wv.x + y1 * wv.y) + CP[5 * FD + o];
+                float sdot = wave_sum(y0 * wv.x + y1 * wv.y) + CP[5 * FD + o];
                 if (lane == 0) p.logits_out[(size_t)clip * p.head.n_out + o] = sdot;
                 zmine = lane == o ? sdot : zmine;
             }
@@ -613,9 +613,9 @@ __global__ __launch_bounds__(CT) void ffn_bwd_kernel(FusedBwdParams p, int l) {
         __syncthreads();
         if (wave == 0) {
             float2 x = *reinterpret_cast<float2*>(pooled + 2 * lane);
-            float mean = wsum(x.x + x.y) * (1.f / FD);
+            float mean = wave_sum(x.x + x.y) * (1.f / FD);
             float xh0 = x.x - mean, xh1 = x.y - mean;
-            float rstd = rsqrtf(wsum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
+            float rstd = rsqrtf(wave_sum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
             xh0 *= rstd; xh1 *= rstd;
             float2 lw = *reinterpret_cast<const float2*>(CP + 3 * FD + 2 * lane);
             float2 lb = *reinterpret_cast<const float2*>(CP + 4 * FD + 2 * lane);
@@ -632,8 +632,8 @@ __global__ __launch_bounds__(CT) void ffn_bwd_kernel(FusedBwdParams p, int l) {
             *reinterpret_cast<float2*>(hp + 2 * lane) = make_float2(d0 * xh0, d1 * xh1);          // d(head ln_w)
             *reinterpret_cast<float2*>(hp + 128 + 2 * lane) = make_float2(d0, d1);                // d(head ln_b)
             float g0 = d0 * lw.x, g1 = d1 * lw.y;
-            float s1 = wsum(g0 + g1) * (1.f / FD);
-            float s2 = wsum(g0 * xh0 + g1 * xh1) * (1.f / FD);
+            float s1 = wave_sum(g0 + g1) * (1.f / FD);
+            float s2 = wave_sum(g0 * xh0 + g1 * xh1) * (1.f / FD);
             float inv_s = 1.f / (float)S;
             *reinterpret_cast<float2*>(pooled + 128 + 2 * lane) =
                 make_float2(rstd * (g0 - s1 - xh0 * s2) * inv_s, rstd * (g1 - s1 - xh1 * s2) * inv_s);

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
 #pragma unroll
                 for (int u = 0; u < 16; ++u) tce_sw += tce_lab[u] == c ? cwc : 0.f;
             }
-        tce_sw = wsum(tce_sw);
+        tce_sw = wave_sum(tce_sw);
     }
     __syncthreads();
     const int nseg_t = TILED ? *nseg_slot : p.nseg;
@@ -1104,7 +1104,7 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
                         const float4 wv = *reinterpret_cast<const float4*>(TW + c * FD + part * 32 + 4 * j);
                         a += (x[4 * j] * wv.x + x[4 * j + 1] * wv.y) + (x[4 * j + 2] * wv.z + x[4 * j + 3] * wv.w);
                     }
-                    acc[c] = quad_sum4(a) + TW[8 * FD + c];
+                    acc[c] = quad_sum(a) + TW[8 * FD + c];
                 }
             }
         }
@@ -1135,7 +1135,7 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
             if (p.tce_pred) p.tce_pred[grow] = pl;
             if (C > 1 && pl == (float)yrow) cterm += 1.f;
         }
-        lterm = wsum(lterm); cterm = wsum(cterm);
+        lterm = wave_sum(lterm); cterm = wave_sum(cterm);
         if (lane == 0) { red[4 + wave] = lterm; red[8 + wave] = cterm; }
         __syncthreads();
         STAMP(13);
@@ -1170,16 +1170,16 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
         __syncthreads();
         if (wave == 0) {
             float2 x = *reinterpret_cast<float2*>(pooled + 2 * lane);
-            float mean = wsum(x.x + x.y) * (1.f / FD);
+            float mean = wave_sum(x.x + x.y) * (1.f / FD);
             float dx = x.x - mean, dy = x.y - mean;
-            float rstd = rsqrtf(wsum(dx * dx + dy * dy) * (1.f / FD) + p.eps);
+            float rstd = rsqrtf(wave_sum(dx * dx + dy * dy) * (1.f / FD) + p.eps);
             float2 lw = *reinterpret_cast<const float2*>(p.head.ln_w + 2 * lane);
             float2 lb = *reinterpret_cast<const float2*>(p.head.ln_b + 2 * lane);
             float y0 = dx * rstd * lw.x + lb.x, y1 = dy * rstd * lw.y + lb.y;
             float zmine = 0.f;
             for (int o = 0; o < p.head.n_out; ++o) {
                 float2 wv = *reinterpret_cast<const float2*>(p.head.W + (size_t)o * FD + 2 * lane);
-                float sdot = wsum(y0 * wv.x + y1 * wv.y) + p.head.b[o];
+                float sdot = wave_sum(y0 * wv.x + y1 * wv.y) + p.head.b[o];
                 if (lane == 0) p.logits_out[(size_t)clip * p.head.n_out + o] = sdot;
                 zmine = lane == o ? sdot : zmine;
             }

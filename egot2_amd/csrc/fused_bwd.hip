@@ -1465,9 +1465,9 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
             if (wave == 0) {
                 const float first = t0 == 0 ? 1.f : 0.f;
                 float2 x = *reinterpret_cast<float2*>(pooled + 2 * lane);
-                float mean = wsum(x.x + x.y) * (1.f / FD);
+                float mean = wave_sum(x.x + x.y) * (1.f / FD);
                 float xh0 = x.x - mean, xh1 = x.y - mean;
-                float rstd = rsqrtf(wsum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
+                float rstd = rsqrtf(wave_sum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
                 xh0 *= rstd; xh1 *= rstd;
                 float2 lw = *reinterpret_cast<const float2*>(p.head.ln_w + 2 * lane);
                 float2 lb = *reinterpret_cast<const float2*>(p.head.ln_b + 2 * lane);
@@ -1484,8 +1484,8 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
                 *reinterpret_cast<float2*>(hp + 2 * lane) = make_float2(first * d0 * xh0, first * d1 * xh1);      // d(head ln_w)
                 *reinterpret_cast<float2*>(hp + 128 + 2 * lane) = make_float2(first * d0, first * d1);            // d(head ln_b)
                 float g0 = d0 * lw.x, g1 = d1 * lw.y;
-                float s1 = wsum(g0 + g1) * (1.f / FD);
-                float s2 = wsum(g0 * xh0 + g1 * xh1) * (1.f / FD);
+                float s1 = wave_sum(g0 + g1) * (1.f / FD);
+                float s2 = wave_sum(g0 * xh0 + g1 * xh1) * (1.f / FD);
                 float inv_s = 1.f / (float)(RAGGED ? rrec[RG_S] : p.S_clip);
                 *reinterpret_cast<float2*>(pooled + 128 + 2 * lane) =
                     make_float2(rstd * (g0 - s1 - xh0 * s2) * inv_s, rstd * (g1 - s1 - xh1 * s2) * inv_s);
@@ -1550,9 +1550,9 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
         __syncthreads();
         if (wave == 0) {
             float2 x = *reinterpret_cast<float2*>(pooled + 2 * lane);
-            float mean = wsum(x.x + x.y) * (1.f / FD);
+            float mean = wave_sum(x.x + x.y) * (1.f / FD);
             float xh0 = x.x - mean, xh1 = x.y - mean;
-            float rstd = rsqrtf(wsum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
+            float rstd = rsqrtf(wave_sum(xh0 * xh0 + xh1 * xh1) * (1.f / FD) + p.eps);
             xh0 *= rstd; xh1 *= rstd;
             float2 lw = *reinterpret_cast<const float2*>(p.head.ln_w + 2 * lane);
             float2 lb = *reinterpret_cast<const float2*>(p.head.ln_b + 2 * lane);
@@ -1569,8 +1569,8 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
             *reinterpret_cast<float2*>(hp + 2 * lane) = make_float2(d0 * xh0, d1 * xh1);          // d(head ln_w)
             *reinterpret_cast<float2*>(hp + 128 + 2 * lane) = make_float2(d0, d1);                // d(head ln_b)
             float g0 = d0 * lw.x, g1 = d1 * lw.y;
-            float s1 = wsum(g0 + g1) * (1.f / FD);
-            float s2 = wsum(g0 * xh0 + g1 * xh1) * (1.f / FD);
+            float s1 = wave_sum(g0 + g1) * (1.f / FD);
+            float s2 = wave_sum(g0 * xh0 + g1 * xh1) * (1.f / FD);
             float inv_s = 1.f / (float)S;
             *reinterpret_cast<float2*>(pooled + 128 + 2 * lane) =
                 make_float2(rstd * (g0 - s1 - xh0 * s2) * inv_s, rstd * (g1 - s1 - xh1 * s2) * inv_s);

@@ -323,12 +323,6 @@ __device__ __forceinline__ Frag<CM> load_hid_frag(const void* tile_a, const void
     }
 }
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // TouchList (fused.h): this workgroup's share of the lines, ONE load per thread and stream, every load unconditional (unused streams repeat
 // stream 0; threads beyond the share re-read its last line; a share larger than the workgroup is cut short: this is a hint). The caller keeps
 // the values alive up to a point where every younger load of its prologue has been waited for anyway (touch_sink): no extra wait.
@@ -349,12 +343,6 @@ __device__ __forceinline__ Touched touch_lines(const TouchList& tl, int block, i
 __device__ __forceinline__ void touch_sink(const Touched& t) {
 #pragma unroll
     for (int k = 0; k < TOUCH_MAX; ++k) asm volatile("" :: "v"(t.v[k]));
-}
-
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // ---- weighted cross entropy fused into the pooled head (egx_ce, round 6) --------------------------------------------------------
@@ -397,7 +385,7 @@ __device__ __forceinline__ void ce_weight_partials(const FusedCe& ce, int n_out,
         const int64_t y = ce.target[i];
         if (y >= 0 && y < n_out) s += ce.class_weight ? ce.class_weight[y] : 1.f;
     }
-    s = wsum(s);
+    s = wave_sum(s);
     if ((tid & 63) == 0) red[tid >> 6] = s;
 }
 // wave 0 of the clip's workgroup: lane o < n_out holds logit o in `z`. Writes d_logits of the clip and adds the clip's loss term.
@@ -410,9 +398,9 @@ __device__ __forceinline__ void ce_clip(const FusedCe& ce, int n_out, int clip, 
     const bool valid = y >= 0 && y < n_out;
     const float wy = valid ? (ce.class_weight ? ce.class_weight[y] : 1.f) : 0.f;
     const float zl = lane < n_out ? z : -INFINITY;
-    const float m = wmax(zl);
+    const float m = wave_max(zl);
     const float e = lane < n_out ? __expf(zl - m) : 0.f;
-    const float s = wsum(e);
+    const float s = wave_sum(e);
     const float zy = __shfl(zl, valid ? (int)y : 0, 64);
     const float k = wy / wtot;
     if (lane < n_out) ce.d_logits[(size_t)clip * n_out + lane] = valid ? k * (e / s - (lane == (int)y ? 1.f : 0.f)) : 0.f;
@@ -437,11 +425,6 @@ __device__ __forceinline__ void ce_clip(const FusedCe& ce, int n_out, int clip, 
 // Row-parallel LayerNorm over a token-major LDS block: 4 adjacent lanes own one row (32 features each), so up
 // to 64 rows are normalised in one pass with quad (DPP) reductions. `fn(row, c0, x[32] pre-LN, y[32] post-LN)`
 // consumes the result (global saves, embeddings, dropout, write-back).
-__device__ __forceinline__ float quad_sum4(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    return v;
-}
 template <class Fn, class Hook>
 __device__ __forceinline__ void ln_rows(const float* buf, int S, const float* __restrict__ w, const float* __restrict__ b,
                                         float eps, Fn&& fn, Hook&& after_w) {
@@ -465,11 +448,11 @@ __device__ __forceinline__ void ln_rows(const float* buf, int S, const float* __
             x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
             s += (v.x + v.y) + (v.z + v.w);
         }
-        float mean = quad_sum4(s) * (1.f / FD);
+        float mean = quad_sum(s) * (1.f / FD);
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) { float t = x[j] - mean; ss += t * t; }
-        float rstd = rsqrtf(quad_sum4(ss) * (1.f / FD) + eps);
+        float rstd = rsqrtf(quad_sum(ss) * (1.f / FD) + eps);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
 #pragma unroll
@@ -478,8 +461,8 @@ __device__ __forceinline__ void ln_rows(const float* buf, int S, const float* __
         fn(row, c0, x, y);
     } else {
         // keep the quad shuffles convergent for partially filled waves
-        (void)quad_sum4(0.f);
-        (void)quad_sum4(0.f);
+        (void)quad_sum(0.f);
+        (void)quad_sum(0.f);
     }
 }
 template <class Fn>
@@ -505,11 +488,11 @@ __device__ __forceinline__ void ln_rows_lds(const float* buf, int S, const float
             x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
             s += (v.x + v.y) + (v.z + v.w);
         }
-        float mean = quad_sum4(s) * (1.f / FD);
+        float mean = quad_sum(s) * (1.f / FD);
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) { float t = x[j] - mean; ss += t * t; }
-        float rstd = rsqrtf(quad_sum4(ss) * (1.f / FD) + eps);
+        float rstd = rsqrtf(quad_sum(ss) * (1.f / FD) + eps);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float4 wq = *reinterpret_cast<const float4*>(wl + c0 + 4 * j), bq = *reinterpret_cast<const float4*>(bl + c0 + 4 * j);
@@ -520,8 +503,8 @@ __device__ __forceinline__ void ln_rows_lds(const float* buf, int S, const float
         }
         fn(row, c0, x, y);
     } else {
-        (void)quad_sum4(0.f);
-        (void)quad_sum4(0.f);
+        (void)quad_sum(0.f);
+        (void)quad_sum(0.f);
     }
 }
 __device__ __forceinline__ void store32(float* dst, const float (&v)[32]) {
@@ -588,11 +571,11 @@ __device__ __forceinline__ void ln_bwd_rows(int S, const float* __restrict__ w, 
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) s += x[j];
-        float mean = quad_sum4(s) * (1.f / FD);
+        float mean = quad_sum(s) * (1.f / FD);
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) { x[j] -= mean; ss += x[j] * x[j]; }
-        float rstd = rsqrtf(quad_sum4(ss) * (1.f / FD) + eps);
+        float rstd = rsqrtf(quad_sum(ss) * (1.f / FD) + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -607,8 +590,8 @@ __device__ __forceinline__ void ln_bwd_rows(int S, const float* __restrict__ w, 
                 s2 += g * x[i];
             }
         }
-        s1 = quad_sum4(s1) * (1.f / FD);
-        s2 = quad_sum4(s2) * (1.f / FD);
+        s1 = quad_sum(s1) * (1.f / FD);
+        s2 = quad_sum(s2) * (1.f / FD);
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
             dx[i] = rstd * (dx[i] - s1 - x[i] * s2);
@@ -618,7 +601,7 @@ __device__ __forceinline__ void ln_bwd_rows(int S, const float* __restrict__ w, 
         put(row, c0, dy, dx, x);
         LNB_STAMP(stamp_base, 4);
     } else {
-        (void)quad_sum4(0.f); (void)quad_sum4(0.f); (void)quad_sum4(0.f); (void)quad_sum4(0.f);
+        (void)quad_sum(0.f); (void)quad_sum(0.f); (void)quad_sum(0.f); (void)quad_sum(0.f);
     }
 }
 
@@ -641,11 +624,11 @@ __device__ __forceinline__ void ln_bwd_rows_lds(int S, const float* wl, float ep
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) s += x[j];
-        float mean = quad_sum4(s) * (1.f / FD);
+        float mean = quad_sum(s) * (1.f / FD);
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) { x[j] -= mean; ss += x[j] * x[j]; }
-        float rstd = rsqrtf(quad_sum4(ss) * (1.f / FD) + eps);
+        float rstd = rsqrtf(quad_sum(ss) * (1.f / FD) + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -661,8 +644,8 @@ __device__ __forceinline__ void ln_bwd_rows_lds(int S, const float* wl, float ep
                 s2 += g * x[i];
             }
         }
-        s1 = quad_sum4(s1) * (1.f / FD);
-        s2 = quad_sum4(s2) * (1.f / FD);
+        s1 = quad_sum(s1) * (1.f / FD);
+        s2 = quad_sum(s2) * (1.f / FD);
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
             dx[i] = rstd * (dx[i] - s1 - x[i] * s2);
@@ -672,7 +655,7 @@ __device__ __forceinline__ void ln_bwd_rows_lds(int S, const float* wl, float ep
         put(row, c0, dy, dx, x);
         LNB_STAMP(stamp_base, 4);
     } else {
-        (void)quad_sum4(0.f); (void)quad_sum4(0.f); (void)quad_sum4(0.f); (void)quad_sum4(0.f);
+        (void)quad_sum(0.f); (void)quad_sum(0.f); (void)quad_sum(0.f); (void)quad_sum(0.f);
     }
 }
 

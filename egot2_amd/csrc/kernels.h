@@ -133,6 +133,11 @@ constexpr int SEG_CE_MAX_HEADS = 4, SEG_CE_MAX_KS = 4, SEG_CE_MAX_CLASSES = 2048
 size_t segmented_ce_scratch_bytes(int B, int Z, int H, int n_ks);
 int segmented_ce(const float* logits, int ld, const int64_t* target, int B, int Z, int H, const int* col0, const int* C, const int* ks,
                  int n_ks, float* loss, float* loss_terms, int* n_valid, int* correct, float* dlogits, void* scratch, hipStream_t st);
+// host helpers of the one-launch criteria (seg_ce.hip). batch_chunks: the B clips as at most max_chunks chunks of at least `waves` clips.
+// check_head_windows (EGX_CHECK style, 0 or 1): every head h is a window [col0[h], col0[h] + C[h]) of 1 .. SEG_CE_MAX_CLASSES columns inside
+// a row of ld, and no two windows overlap.
+void batch_chunks(int B, int max_chunks, int waves, int* chunk, int* nchunks);
+int check_head_windows(const char* who, int ld, int H, const int* col0, const int* C);
 
 // lta_val.hip: the LTA validation step (K sampled futures per clip and head, prefix edit distances, their sums) in one launch
 constexpr int LTA_VAL_MAX_K = 8, LTA_VAL_MAX_Z = 64;

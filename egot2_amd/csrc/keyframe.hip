@@ -32,47 +32,6 @@ struct KeyframeParams {
     int* ipart;             // [KF_MAX_CHUNKS][3]   n_sc, n_correct, n_outside of the chunk
 };
 
-struct KfBest { float v; int i; };
-
-// torch.argmax's order: a NaN beats every number, the larger number wins, and of two equals (two NaNs included) the lower index
-__device__ __forceinline__ bool kf_better(float va, int ia, float vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na != nb) return na;
-    if (na || va == vb) return ia < ib;
-    return va > vb;
-}
-__device__ __forceinline__ KfBest kf_wave_argmax(float v, int i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float vo = __shfl_xor(v, o, 64);
-        const int io = __shfl_xor(i, o, 64);
-        if (kf_better(vo, io, v, i)) { v = vo; i = io; }
-    }
-    KfBest b;
-    b.v = v; b.i = i;
-    return b;
-}
-__device__ __forceinline__ float kf_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float kf_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int kf_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double kf_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 constexpr int KF_NO_FRAME = 1 << 30;        // index of a lane without a frame: it loses every tie
 
 __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams p) {
@@ -104,7 +63,7 @@ __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams 
     for (int b = blockIdx.x * p.chunk + wave; b < b_end; b += KF_WAVES) {
         const float* row = p.logits + (size_t)b * p.ld;
         const float x = is_frame ? row[col] : -INFINITY;
-        const KfBest best = kf_wave_argmax(x, is_frame ? lane : KF_NO_FRAME);
+        const WaveBest best = wave_argmax(x, is_frame ? lane : KF_NO_FRAME);
         const int pred = best.i;
 
         int lab = -1;               // the label frame; -1: none given
@@ -112,7 +71,7 @@ __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams 
             const int64_t l = p.label[b];
             lab = (l >= 0 && l < T) ? (int)l : -2;          // outside [0, T): equals no prediction, and adds no CE loss or gradient
         } else if (p.target) {
-            lab = kf_wave_argmax(is_frame ? p.target[(size_t)b * T + lane] : -INFINITY, is_frame ? lane : KF_NO_FRAME).i;
+            lab = wave_argmax(is_frame ? p.target[(size_t)b * T + lane] : -INFINITY, is_frame ? lane : KF_NO_FRAME).i;
         }
         const bool sc = p.state_change ? p.state_change[b] == 1 : true;
 
@@ -121,9 +80,9 @@ __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams 
             int gi = KF_NO_FRAME;
             for (int c = lane; c < p.V; c += 64) {
                 const float v = row[c];
-                if (kf_better(v, c, gv, gi)) { gv = v; gi = c; }
+                if (argmax_better(v, c, gv, gi)) { gv = v; gi = c; }
             }
-            const KfBest g = kf_wave_argmax(gv, gi);
+            const WaveBest g = wave_argmax(gv, gi);
             n_outside += frame_of_s[g.i] < 0 ? 1 : 0;
         }
         n_sc += sc ? 1 : 0;
@@ -138,14 +97,14 @@ __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams 
             const float sp_pos = fmaxf(x, 0.f) + l1p, sp_neg = fmaxf(-x, 0.f) + l1p;
             const float term = is_frame ? fminf(sp_neg, 100.f) * y + fminf(sp_pos, 100.f) * (1.f - y) : 0.f;
             const float inv_t = 1.f / (float)T;
-            row_loss = kf_wave_sum(term) * inv_t;
+            row_loss = wave_sum(term) * inv_t;
             const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
             g = (sig - y) * (inv_t / (float)p.B);
         } else if (p.kind == KEYFRAME_CE) {
             const bool on = sc && lab >= 0;
-            const float m = kf_wave_max(x);
+            const float m = wave_max(x);
             const float ex = is_frame ? expf(x - m) : 0.f;      // max-subtracted: the largest term is 1
-            const float s = kf_wave_sum(ex);
+            const float s = wave_sum(ex);
             const float xy = __shfl(x, lab >= 0 ? lab : 0, 64);
             row_loss = on ? (m - xy) + logf(s) : 0.f;
             g = on ? (ex / s - (lane == lab ? 1.f : 0.f)) / (float)p.B : 0.f;
@@ -211,22 +170,16 @@ __global__ __launch_bounds__(256) void keyframe_criterion_kernel(KeyframeParams 
     int iv[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) iv[k] = __hip_atomic_load(p.ipart + j * 3 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float fsum = kf_wave_sum(in ? fv : 0.f);
-    const double dsum = kf_wave_sum(in ? dv : 0.0);
+    const float fsum = wave_sum(in ? fv : 0.f);
+    const double dsum = wave_sum(in ? dv : 0.0);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) iv[k] = kf_wave_sum(in ? iv[k] : 0);
+    for (int k = 0; k < 3; ++k) iv[k] = wave_sum(in ? iv[k] : 0);
     if (lane == 0) {
         if (p.loss) *p.loss = fsum / (float)p.B;
         if (p.dist_sum) *p.dist_sum = dsum;
         p.counts[0] = iv[0]; p.counts[1] = iv[1]; p.counts[2] = iv[2]; p.counts[3] = p.B;
         *p.counter = 0u;            // left zero for the next launch
     }
-}
-
-static void kf_chunks(int B, int* chunk, int* nchunks) {
-    const int c = B / KF_MAX_CHUNKS + (B % KF_MAX_CHUNKS ? 1 : 0);
-    *chunk = c < KF_WAVES ? KF_WAVES : c;
-    *nchunks = (B + *chunk - 1) / *chunk;
 }
 
 static int kf_check_B(int B) {
@@ -270,7 +223,7 @@ int keyframe_criterion(const float* logits, int ld, int B, int T, const int* col
     p.logits = logits; p.target = target; p.label = label; p.state_change = state_change;
     p.fps = fps; p.clip_start = clip_start; p.clip_end = clip_end; p.pnr_frame = pnr_frame;
     p.B = B; p.T = T; p.V = V; p.ld = ld; p.kind = kind; p.has_cols = cols ? 1 : 0;
-    kf_chunks(B, &p.chunk, &p.nchunks);
+    batch_chunks(B, KF_MAX_CHUNKS, KF_WAVES, &p.chunk, &p.nchunks);
     for (int t = 0; t < KEYFRAME_MAX_T; ++t) p.cols[t] = (cols && t < T) ? cols[t] : 0;
     p.loss = loss; p.loss_rows = loss_rows; p.dlogits = dlogits; p.pred = pred; p.label_frame = label_frame; p.counts = counts;
     p.dist = dist; p.dist_sum = dist_sum;

@@ -36,12 +36,6 @@ struct LtaValParams {
     int64_t* preds; int* min_dist; unsigned long long* dist_sum;
 };
 
-__device__ __forceinline__ int lv_wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // The K tokens of one row (b, z) of head h into tok[k * LTA_VAL_MAX_Z + z] (lanes k < K write them); -1 for a row that cannot be sampled
 __device__ __forceinline__ void lv_draw_row(const float* __restrict__ seg, int C, int K, uint64_t key, uint32_t row, float* __restrict__ cdf,
                                             int64_t* __restrict__ tok_z, int64_t* __restrict__ preds_z, int Z, int lane) {
@@ -83,7 +77,7 @@ __device__ __forceinline__ void lv_draw_row(const float* __restrict__ seg, int C
             base = lane == l ? acc : base;
             acc += t;
         }
-        lastpos = lv_wave_max(lastpos);
+        lastpos = wave_max(lastpos);
         for (int i = i0; i < i1; ++i) cdf[i] += base;
         __builtin_amdgcn_wave_barrier();
         if (lane < K) {
@@ -178,14 +172,7 @@ int lta_validate(const float* logits, int ld, const int64_t* labels, int B, int 
     if (!preds_in) {
         EGX_CHECK(col0 && C, "lta_validate: null pointer argument (col0 / C)");
         EGX_CHECK(ld >= 1, "lta_validate: ld=%d (needs ld >= 1)", ld);
-        for (int h = 0; h < H; ++h) {
-            EGX_CHECK(C[h] >= 1 && C[h] <= SEG_CE_MAX_CLASSES, "lta_validate: head %d has C=%d classes (needs 1 <= C <= %d)", h, C[h], SEG_CE_MAX_CLASSES);
-            EGX_CHECK(col0[h] >= 0 && col0[h] <= ld - C[h], "lta_validate: head %d covers columns [%d, %d) of a row of ld=%d", h, col0[h],
-                      col0[h] + C[h], ld);
-            for (int g = 0; g < h; ++g)
-                EGX_CHECK(col0[h] >= col0[g] + C[g] || col0[g] >= col0[h] + C[h], "lta_validate: heads %d and %d overlap (columns [%d, %d) and [%d, %d))",
-                          g, h, col0[g], col0[g] + C[g], col0[h], col0[h] + C[h]);
-        }
+        if (check_head_windows("lta_validate", ld, H, col0, C)) return 1;
         // A HOST seed is baked into a captured graph: every replay would draw the SAME sequences (the rule of the dropout seed, encoder.hip)
         if (K > 1 && !seed_ptr) {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

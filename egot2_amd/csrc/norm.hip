@@ -11,12 +11,6 @@
 
 namespace egx {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int remap_row(int row, int T, int S, int off) { return (row / T) * S + off + (row % T); }
 
 // ---- LayerNorm forward ------------------------------------------------------------------------

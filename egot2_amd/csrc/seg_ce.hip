@@ -32,22 +32,6 @@ struct SegCeParams {
     unsigned* counter;      // arrival counters, zero before the first launch
 };
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct SegOut { float nll; int rank; };
 
 // rank of the label: #{c : z_c > z_y} + #{c < y : z_c == z_y} (among equal logits the lower class index ranks first)
@@ -277,10 +261,21 @@ __global__ __launch_bounds__(256, 6) void segmented_ce_kernel(SegCeParams p) {
     }
 }
 
-static void seg_chunks(int B, int* chunk, int* nchunks) {
-    const int c = B / SEG_MAX_CHUNKS + (B % SEG_MAX_CHUNKS ? 1 : 0);
-    *chunk = c < SEG_WAVES ? SEG_WAVES : c;
+void batch_chunks(int B, int max_chunks, int waves, int* chunk, int* nchunks) {
+    const int c = B / max_chunks + (B % max_chunks ? 1 : 0);
+    *chunk = c < waves ? waves : c;
     *nchunks = (B + *chunk - 1) / *chunk;
+}
+
+int check_head_windows(const char* who, int ld, int H, const int* col0, const int* C) {
+    for (int h = 0; h < H; ++h) {
+        EGX_CHECK(C[h] >= 1 && C[h] <= SEG_CE_MAX_CLASSES, "%s: head %d has C=%d classes (needs 1 <= C <= %d)", who, h, C[h], SEG_CE_MAX_CLASSES);
+        EGX_CHECK(col0[h] >= 0 && col0[h] <= ld - C[h], "%s: head %d covers columns [%d, %d) of a row of ld=%d", who, h, col0[h], col0[h] + C[h], ld);
+        for (int g = 0; g < h; ++g)
+            EGX_CHECK(col0[h] >= col0[g] + C[g] || col0[g] >= col0[h] + C[h], "%s: heads %d and %d overlap (columns [%d, %d) and [%d, %d))", who,
+                      g, h, col0[g], col0[g] + C[g], col0[h], col0[h] + C[h]);
+    }
+    return 0;
 }
 
 static size_t seg_counter_bytes(int Z) { return (size_t)(1 + Z) * SEG_COUNTER_WORDS * sizeof(unsigned); }
@@ -296,7 +291,7 @@ static int seg_ce_check_dims(int B, int Z, int H, int n_ks) {
 size_t segmented_ce_scratch_bytes(int B, int Z, int H, int n_ks) {
     if (seg_ce_check_dims(B, Z, H, n_ks)) return 0;
     int chunk, nchunks;
-    seg_chunks(B, &chunk, &nchunks);
+    batch_chunks(B, SEG_MAX_CHUNKS, SEG_WAVES, &chunk, &nchunks);
     // [arrival counters: 64 B each, the launch's and one per future step][nll partials][count partials]
     return seg_counter_bytes(Z) + (size_t)Z * nchunks * H * sizeof(float) + (size_t)Z * nchunks * (n_ks > 0 ? n_ks : 1) * H * sizeof(int);
 }
@@ -307,14 +302,9 @@ int segmented_ce(const float* logits, int ld, const int64_t* target, int B, int 
     if (seg_ce_check_dims(B, Z, H, n_ks)) return 1;
     EGX_CHECK(n_ks == 0 || (ks && correct), "segmented_ce: null pointer argument (ks / correct with n_ks=%d)", n_ks);
     EGX_CHECK(ld >= 1, "segmented_ce: ld=%d (needs ld >= 1)", ld);
+    if (check_head_windows("segmented_ce", ld, H, col0, C)) return 1;
     int min_c = SEG_CE_MAX_CLASSES, covered = 0;
     for (int h = 0; h < H; ++h) {
-        EGX_CHECK(C[h] >= 1 && C[h] <= SEG_CE_MAX_CLASSES, "segmented_ce: head %d has C=%d classes (needs 1 <= C <= %d)", h, C[h], SEG_CE_MAX_CLASSES);
-        EGX_CHECK(col0[h] >= 0 && col0[h] <= ld - C[h], "segmented_ce: head %d covers columns [%d, %d) of a row of ld=%d", h, col0[h],
-                  col0[h] + C[h], ld);
-        for (int g = 0; g < h; ++g)
-            EGX_CHECK(col0[h] >= col0[g] + C[g] || col0[g] >= col0[h] + C[h], "segmented_ce: heads %d and %d overlap (columns [%d, %d) and [%d, %d))",
-                      g, h, col0[g], col0[g] + C[g], col0[h], col0[h] + C[h]);
         min_c = C[h] < min_c ? C[h] : min_c;
         covered += C[h];
     }
@@ -322,7 +312,7 @@ int segmented_ce(const float* logits, int ld, const int64_t* target, int B, int 
         EGX_CHECK(ks[k] >= 1 && ks[k] <= min_c, "segmented_ce: ks[%d]=%d (needs 1 <= k <= %d, the narrowest head)", k, ks[k], min_c);
     SegCeParams p;
     p.logits = logits; p.target = target; p.B = B; p.Z = Z; p.H = H; p.ld = ld; p.nks = n_ks;
-    seg_chunks(B, &p.chunk, &p.nchunks);
+    batch_chunks(B, SEG_MAX_CHUNKS, SEG_WAVES, &p.chunk, &p.nchunks);
     p.gaps = covered != ld;
     for (int h = 0; h < SEG_CE_MAX_HEADS; ++h) { p.col0[h] = h < H ? col0[h] : 0; p.C[h] = h < H ? C[h] : 0; }
     for (int k = 0; k < SEG_CE_MAX_KS; ++k) p.ks[k] = k < n_ks ? ks[k] : 0;

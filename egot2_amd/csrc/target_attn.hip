@@ -22,17 +22,6 @@ namespace egx {
 
 constexpr int TA_MAXQ = 64, TA_MAXK = 1024, TA_MAXDH = 128, TA_GROUP = 8, TA_CHUNK = 64, TA_NTH = 256;
 
-__device__ __forceinline__ float ta_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float ta_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // grid = B * H, block = 256. LDS: K or V chunk [64][dh + 1]; Q, dO of the group [8][dh]; P, dS of the group [8][round_up(Sk, 64)].
 // acc[u] is indexed by unrolled loops only: a runtime-indexed register array would go to scratch.
 template <bool BWD>
@@ -80,10 +69,10 @@ __global__ __launch_bounds__(TA_NTH) void target_attention_kernel(SmallAttnParam
         for (int r = wave; r < ng; r += 4) {
             float m = -INFINITY;
             for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[r * SKP + j]);
-            m = ta_wave_max(m);
+            m = wave_max(m);
             float sum = 0.f;
             for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[r * SKP + j] - m); Ps[r * SKP + j] = e; sum += e; }
-            sum = 1.f / ta_wave_sum(sum);
+            sum = 1.f / wave_sum(sum);
             for (int j = lane; j < SKP; j += 64) Ps[r * SKP + j] *= sum;        // the plain probabilities (0 where masked and beyond Sk)
         }
         if constexpr (BWD) {
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(TA_NTH) void target_attention_kernel(SmallAttnParam
                     Ds[r * SKP + j] = dp;
                     delta += Ps[r * SKP + j] * dp;
                 }
-                delta = ta_wave_sum(delta);
+                delta = wave_sum(delta);
                 for (int j = lane; j < SKP; j += 64) {
                     float mask = 1.f;
                     if (p.drop_thresh) mask = drop_scale(p.drop_key, mrow, (uint32_t)j, p.drop_thresh, p.drop_inv);

@@ -28,16 +28,6 @@ namespace {
 
 constexpr int DA_MAXQ = 8, DA_MAXK = 64;
 
-__device__ __forceinline__ float wmax64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wsum64d(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 __device__ __forceinline__ float bf1(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
@@ -150,9 +140,9 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnParams p) {
             s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
         }
         s = live ? s * p.scale : -INFINITY;
-        const float m = wmax64(s);
+        const float m = wave_max(s);
         const float e = live ? __expf(s - m) : 0.f;
-        const float prob = e / wsum64d(e);
+        const float prob = e / wave_sum(e);
         float mask = 1.f;
         if (p.drop_thresh) mask = drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)lane, p.drop_thresh, p.drop_inv);
         sP[wave][i][lane] = prob * mask;
@@ -164,7 +154,7 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnParams p) {
                 dp += (gv.x * vr[c] + gv.y * vr[c + 1]) + (gv.z * vr[c + 2] + gv.w * vr[c + 3]);
             }
             dp = live ? dp * mask : 0.f;
-            const float delta = wsum64d(prob * dp);
+            const float delta = wave_sum(prob * dp);
             const float dsv = live ? prob * (dp - delta) * p.scale : 0.f;
             ds_reg[i] = dsv;
             sD[wave][i][lane] = dsv;
@@ -280,10 +270,10 @@ __global__ __launch_bounds__(256) void dec_attn_long_kernel(DecAttnParams p) {
     for (int i = wave; i < Sq; i += 4) {
         float m = -INFINITY;
         for (int j = lane; j < SKP; j += 64) m = fmaxf(m, Ps[i * SKP + j]);
-        m = wmax64(m);
+        m = wave_max(m);
         float sum = 0.f;
         for (int j = lane; j < SKP; j += 64) { const float e = __expf(Ps[i * SKP + j] - m); Ps[i * SKP + j] = e; sum += e; }
-        sum = 1.f / wsum64d(sum);
+        sum = 1.f / wave_sum(sum);
         for (int j = lane; j < SKP; j += 64) Ps[i * SKP + j] *= sum;
     }
     auto keep = [&](int i, int j) { return p.drop_thresh ? drop_scale(dkey, (uint32_t)(bh * DA_MAXQ + i), (uint32_t)j, p.drop_thresh, p.drop_inv) : 1.f; };
@@ -309,7 +299,7 @@ __global__ __launch_bounds__(256) void dec_attn_long_kernel(DecAttnParams p) {
                 Ds[i * SKP + j] = dp;
                 delta += Ps[i * SKP + j] * dp;
             }
-            delta = wsum64d(delta);
+            delta = wave_sum(delta);
             for (int j = lane; j < SKP; j += 64) {
                 const float pr = Ps[i * SKP + j];
                 Ds[i * SKP + j] = pr * (Ds[i * SKP + j] - delta) * p.scale;
@@ -485,7 +475,7 @@ __global__ __launch_bounds__(CW_THREADS) void dec_cross_weights_kernel(CrossWPar
             }
             m = fmaxf(m, s[c]);
         }
-        m = wmax64(m);
+        m = wave_max(m);
         if (lane == 0) sMax[wave] = m;
         __syncthreads();
         m = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
@@ -496,7 +486,7 @@ __global__ __launch_bounds__(CW_THREADS) void dec_cross_weights_kernel(CrossWPar
             e[c] = t + c * CW_THREADS < Sb ? __expf(s[c] - m) : 0.f;
             sum += e[c];
         }
-        sum = wsum64d(sum);
+        sum = wave_sum(sum);
         if (lane == 0) sSum[wave] = sum;
         __syncthreads();
         sum = ((sSum[0] + sSum[1]) + sSum[2]) + sSum[3];     // wave order
@@ -1456,9 +1446,9 @@ __global__ __launch_bounds__(256) void cached_self_attn_kernel(CachedAttnParams<
         s += (qv.x * kr[c] + qv.y * kr[c + 1]) + (qv.z * kr[c + 2] + qv.w * kr[c + 3]);
     }
     s = live ? s * p.scale : -INFINITY;
-    const float m = wmax64(s);
+    const float m = wave_max(s);
     const float e = live ? __expf(s - m) : 0.f;
-    sP[wave][lane] = e / wsum64d(e);
+    sP[wave][lane] = e / wave_sum(e);
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane < DH) {
@@ -1556,7 +1546,7 @@ __device__ __forceinline__ void head_logits_rows(const float* fc_w, const float*
             const float bias = fc_b && on ? fc_b[v] : 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const float sum = wsum64d(a[u][r]);
+                const float sum = wave_sum(a[u][r]);
                 if (lane == 0 && on) sl[r * V + v] = sum + bias;
             }
         }
@@ -1983,13 +1973,13 @@ __global__ __launch_bounds__(BH_THREADS) void beam_head_kernel(BeamHeadParams p)
             if (p.step_logits) p.step_logits[(r0 + wave) * V + v] = x;
             if (x == x) m = fmaxf(m, x);
         }
-        m = wmax64(m);
+        m = wave_max(m);
         float sum = 0.f;
         for (int v = lane; v < V; v += 64) {
             const float x = row[v];
             if (x == x) sum += expf(x - m);
         }
-        const float lse = logf(wsum64d(sum));
+        const float lse = logf(wave_sum(sum));
         for (int v = lane; v < V; v += 64) {
             const float x = row[v];
             row[v] = x == x ? prev + ((x - m) - lse) : -INFINITY;
@@ -2228,10 +2218,10 @@ __global__ __launch_bounds__(64 * GH_WAVES) void forced_head_kernel(ForcedHeadPa
         mx = fmaxf(mx, x);                      // (a NaN is skipped here and caught by the sum)
     }
     if (!p.logprob) return;
-    mx = wmax64(mx);
+    mx = wave_max(mx);
     float sum = 0.f;
     for (int v = lane; v < V; v += 64) sum += expf(row[v] - mx);
-    const float lse = logf(wsum64d(sum));
+    const float lse = logf(wave_sum(sum));
     if (lane == 0) {
         const int t = g / p.M, m = g - t * p.M;
         const size_t o = (size_t)m * p.n + t;

@@ -13,11 +13,6 @@ namespace egx {
 
 namespace {
 
-__device__ __forceinline__ float wsum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ uint32_t pk2(float a, float b) { return pack_bf16x2(a, b); }
 __device__ __forceinline__ float bff(uint32_t lo16) { return __builtin_bit_cast(float, lo16 << 16); }
 __device__ __forceinline__ int remap(int row, int T, int S, int off) { return (row / T) * S + off + (row % T); }
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
             if (i < nv && c < d) v[i] = *reinterpret_cast<const float4*>(x + c);
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
-        const float mean = wsum64(s) * inv_d;
+        const float mean = wave_sum(s) * inv_d;
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(256) void wide_ln_fwd_kernel(WideLnFwdParams p) {
                 ss += (a * a + b * b) + (cc * cc + dd * dd);
             }
         }
-        const float rstd = rsqrtf(wsum64(ss) * inv_d + p.eps);
+        const float rstd = rsqrtf(wave_sum(ss) * inv_d + p.eps);
         if (p.stats && lane == 0) *reinterpret_cast<float2*>(p.stats + 2 * (size_t)row) = make_float2(mean, rstd);
         const int t_in = MAPPED ? (p.src_map ? p.src_map[row] % p.T : 0) : row % p.T, orow = MAPPED ? p.out_map[row] : remap(row, p.T, p.S, p.off);
         const float* pos = p.pos ? p.pos + (size_t)t_in * p.pos_stride : nullptr;
@@ -155,8 +150,8 @@ __global__ __launch_bounds__(256) void wide_ln_bwd_kernel(WideLnBwdParams p, int
                 gq[i] = g; xh[i] = x;
             }
         }
-        s1 = wsum64(s1) * inv_d;
-        s2 = wsum64(s2) * inv_d;
+        s1 = wave_sum(s1) * inv_d;
+        s2 = wave_sum(s2) * inv_d;
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
             int c = 4 * lane + 256 * i;

@@ -1523,6 +1523,13 @@ def unit_grad(device) -> torch.Tensor:
     return t
 
 
+def _scaled_by_upstream(dl: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """d loss / d logits as the forward launch left it, times the upstream gradient `g` of the loss. `dl` itself when `g` is
+    unit_grad's tensor: multiplying by that 1 would be a launch."""
+    u = _UNIT_GRAD.get(dl.device.index)
+    return dl if u is not None and g.data_ptr() == u.data_ptr() else dl * g
+
+
 class WeightedCEFn(torch.autograd.Function):
     """loss = sum_i w[y_i] nll_i / sum_i w[y_i]; the same launch leaves d loss / d logits behind for backward."""
 
@@ -1552,10 +1559,7 @@ class WeightedCEFn(torch.autograd.Function):
         if not ctx.has_dl:
             return None, None, None
         (dl,) = ctx.saved_tensors
-        u = _UNIT_GRAD.get(dl.device.index)
-        if u is not None and grad_out.data_ptr() == u.data_ptr():
-            return dl, None, None
-        return dl * grad_out, None, None
+        return _scaled_by_upstream(dl, grad_out), None, None
 
 
 class DecoderFn(torch.autograd.Function):
@@ -1916,24 +1920,27 @@ def weighted_cross_entropy(logits, target, weight=None):
     return WeightedCEFn.apply(logits, target, weight)
 
 
-_LCE_SCRATCH = {}
-_LCE_RETIRED = []       # outgrown buffers stay alive: a hipGraph captured earlier still holds their addresses
+_SCRATCH = {}
+_SCRATCH_RETIRED = []
 
 
-def _lce_scratch(device, nbytes: int) -> torch.Tensor:
-    """Scratch of the fused classifier head: arrival counters (zero between launches) + partial sums. One per device (NOT per
-    stream: a hipGraph is captured on a stream of its own and must find the buffer its eager warm-up created — so two streams
-    must not run lossAV concurrently on one device), grown on demand; a new buffer is zero-filled once (the kernels leave the
-    counters zero again). An outgrown buffer is never freed: a graph captured at the smaller size keeps replaying into it."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    t = _LCE_SCRATCH.get(key)
+def _zeroed_scratch(who: str, device, nbytes: int, key=(), floor: int = 0) -> torch.Tensor:
+    """Scratch of a one-launch criterion (`who`: its public name): arrival counters (zero between launches) + partial sums. The rules:
+    - one buffer per (operator, device, *key) - NOT per stream: a hipGraph is captured on a stream of its own and must find the buffer
+      its eager warm-up created, so two streams must not run one operator concurrently on one device;
+    - grown on demand (to at least `floor` bytes), and a new buffer is zero-filled once: every launch leaves its counters zero again;
+    - never created inside a capture: the buffer would live in that graph's private pool, so the call raises;
+    - an outgrown buffer is retired, never freed: a graph captured at the smaller size still holds its address and keeps replaying into it.
+    `key` separates problem sizes whose layouts must not share memory. segmented_cross_entropy passes (Z,): its buffer begins with
+    64 * (1 + Z) bytes of counters, and the partial sums behind them must not land where a launch with another Z keeps its counters."""
+    key = (who, device.index if device.index is not None else torch.cuda.current_device(), *key)
+    t = _SCRATCH.get(key)
     if t is None or t.numel() < nbytes:
         if torch.cuda.is_current_stream_capturing():
-            # a buffer created inside a capture would live in that graph's private pool
-            raise RuntimeError("linear_cross_entropy: run one eager step at this problem size before capturing it in a graph")
+            raise RuntimeError(f"{who}: run one eager step at this problem size before capturing it in a graph")
         if t is not None:
-            _LCE_RETIRED.append(t)
-        t = _LCE_SCRATCH[key] = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
+            _SCRATCH_RETIRED.append(t)
+        t = _SCRATCH[key] = torch.zeros(max(nbytes, floor), dtype=torch.uint8, device=device)
     return t
 
 
@@ -1965,7 +1972,7 @@ class LinearCEFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         correct = torch.empty((), dtype=torch.float32, device=x.device)
         pred = torch.empty((M,), dtype=torch.float32, device=x.device)
-        scratch = _lce_scratch(x.device, lib.egx_linear_ce_scratch(M, K, Cn))
+        scratch = _zeroed_scratch("linear_cross_entropy", x.device, lib.egx_linear_ce_scratch(M, K, Cn), floor=1 << 16)
         check(lib.egx_linear_ce_fwd(ptr(x), ptr(W), ptr(b) if b is not None else None, ptr(tgt), ptr(w) if w is not None else None,
                                     M, K, Cn, ptr(logits), ptr(probs), ptr(dl) if dl is not None else None, ptr(loss), ptr(correct),
                                     ptr(pred), ptr(scratch), _stream()))
@@ -1988,7 +1995,7 @@ class LinearCEFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.empty_like(W)
         db = torch.empty((Cn,), dtype=torch.float32, device=x.device) if ctx.has_b else None
-        scratch = _lce_scratch(x.device, lib.egx_linear_ce_scratch(M, K, Cn))
+        scratch = _zeroed_scratch("linear_cross_entropy", x.device, lib.egx_linear_ce_scratch(M, K, Cn), floor=1 << 16)
         check(lib.egx_linear_ce_bwd(ptr(x), ptr(W), ptr(dl), ptr(g), M, K, Cn, ptr(dx) if dx is not None else None, ptr(dW),
                                     ptr(db) if db is not None else None, ptr(scratch), _stream()))
         return dx, dW if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None
@@ -2022,22 +2029,51 @@ def _seg_windows(preds):
     return base + 4 * min(offs), ld, col0
 
 
-_SEG_SCRATCH = {}
+def _head_stack(who: str, preds):
+    """The (B, Z, C_h) heads of `who` (segmented_cross_entropy, lta_validate), checked, as the launch's stack ->
+    (B, Z, H, dev, widths, addr, ld, col0, stack): in place where _seg_windows finds one, else one torch.cat - `stack` is then that tensor
+    (None otherwise), which the caller holds until after the launch."""
+    H = len(preds)
+    if not 1 <= H <= SEG_CE_MAX_HEADS:
+        raise ValueError(f"{who} takes 1 to {SEG_CE_MAX_HEADS} heads, got {H}")
+    for h, p in enumerate(preds):
+        _dev_f32(p[:0], f"preds[{h}]")                   # device / dtype refusal only: the heads stay the views they are
+    p0 = preds[0]
+    if any(p.dim() != 3 or p.shape[:2] != p0.shape[:2] or p.device != p0.device for p in preds):
+        raise ValueError(f"{who} expects (B, Z, C_h) heads of one batch, got {[tuple(p.shape) for p in preds]}")
+    B, Z = p0.shape[0], p0.shape[1]
+    widths = [p.shape[2] for p in preds]
+    win = _seg_windows(preds)
+    if win is not None:
+        return (B, Z, H, p0.device, widths, *win, None)
+    stack = torch.cat(preds, dim=-1).contiguous()       # one concatenation builds the stack
+    col0 = [sum(widths[:h]) for h in range(H)]
+    return B, Z, H, p0.device, widths, stack.data_ptr(), stack.shape[2], col0, stack
 
 
-def _seg_scratch(device, Z: int, nbytes: int) -> torch.Tensor:
-    """Scratch of egx_segmented_ce, by the rules of _lce_scratch (one per device, zero-filled once, never created inside a capture, an
-    outgrown buffer stays alive) - and one per Z: the buffer begins with 64 * (1 + Z) bytes of arrival counters that every launch leaves
-    zero, and the partial sums behind them must not land where a launch with another Z keeps its counters."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), Z)
-    t = _SEG_SCRATCH.get(key)
-    if t is None or t.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("segmented_cross_entropy: run one eager step at this problem size before capturing it in a graph")
-        if t is not None:
-            _LCE_RETIRED.append(t)
-        t = _SEG_SCRATCH[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-    return t
+def _head_labels(labels, B: int, Z: int, H: int, dev) -> torch.Tensor:
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B, Z, H) or labels.device != dev:
+        raise ValueError(f"labels must be an int64 tensor of shape (B, Z, H) = {(B, Z, H)} on the predictions' device")
+    return labels.contiguous()
+
+
+def _c_ints(v):
+    return (C.c_int * max(len(v), 1))(*v)
+
+
+def _out_tensor(out, name: str, shape, dtype, dev, wanted: bool = True):
+    """A result of a one-launch criterion: the caller's preallocated out[name] (the persistent buffers of the train.py modules), else a
+    new tensor; None for a result this call does not produce."""
+    if not wanted:
+        return None
+    return out[name] if name in out else torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _fresh(*results):
+    """New tensor objects over the result memory: a persistent buffer handed in through `out` must not become the owner of this call's
+    autograd graph (it would keep the graph - and the logits' gradient accumulator, with the stream it was created on - alive into the
+    next call, e.g. from an eager step on the default stream into a capture)."""
+    return tuple(None if t is None else t.detach() for t in results)
 
 
 class SegmentedCEFn(torch.autograd.Function):
@@ -2048,55 +2084,29 @@ class SegmentedCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, labels, ks, out, *preds):
         lib = _lib.load()
-        H = len(preds)
-        if not 1 <= H <= SEG_CE_MAX_HEADS:
-            raise ValueError(f"segmented_cross_entropy takes 1 to {SEG_CE_MAX_HEADS} heads, got {H}")
-        for h, p in enumerate(preds):
-            _dev_f32(p[:0], f"preds[{h}]")                   # device / dtype refusal only: the heads stay the views they are
-        p0 = preds[0]
-        if any(p.dim() != 3 or p.shape[:2] != p0.shape[:2] or p.device != p0.device for p in preds):
-            raise ValueError(f"segmented_cross_entropy expects (B, Z, C_h) heads of one batch, got {[tuple(p.shape) for p in preds]}")
-        B, Z = p0.shape[0], p0.shape[1]
-        widths = [p.shape[2] for p in preds]
-        if labels.dtype != torch.int64 or tuple(labels.shape) != (B, Z, H) or labels.device != p0.device:
-            raise ValueError(f"labels must be an int64 tensor of shape (B, Z, H) = {(B, Z, H)} on the predictions' device")
+        B, Z, H, dev, widths, addr, ld, col0, _stack = _head_stack("segmented_cross_entropy", preds)     # _stack: alive until the launch
+        tgt = _head_labels(labels, B, Z, H, dev)
         ks = tuple(int(k) for k in ks)
         if len(ks) > SEG_CE_MAX_KS:
             raise ValueError(f"segmented_cross_entropy takes at most {SEG_CE_MAX_KS} values of k, got {len(ks)}")
-        tgt = labels.contiguous()
-        win = _seg_windows(preds)
-        if win is None:                                     # one concatenation builds the stack
-            stack = torch.cat(preds, dim=-1).contiguous()
-            ld, col0, off = stack.shape[2], [], 0
-            for w in widths:
-                col0.append(off)
-                off += w
-            addr = stack.data_ptr()
-        else:
-            addr, ld, col0 = win
-        dev = p0.device
         out = out or {}
-        loss = out["loss"] if "loss" in out else torch.empty((), dtype=torch.float32, device=dev)
-        terms = out["loss_terms"] if "loss_terms" in out else torch.empty((Z, H), dtype=torch.float32, device=dev)
-        n_valid = out["n_valid"] if "n_valid" in out else torch.empty((Z, H), dtype=torch.int32, device=dev)
-        correct = out["correct"] if "correct" in out else torch.empty((len(ks), Z, H), dtype=torch.int32, device=dev)
+        loss = _out_tensor(out, "loss", (), torch.float32, dev)
+        terms = _out_tensor(out, "loss_terms", (Z, H), torch.float32, dev)
+        n_valid = _out_tensor(out, "n_valid", (Z, H), torch.int32, dev)
+        correct = _out_tensor(out, "correct", (len(ks), Z, H), torch.int32, dev)
         need = any(ctx.needs_input_grad[3:])
         dl = torch.empty((B, Z, ld), dtype=torch.float32, device=dev) if need else None
         nbytes = lib.egx_segmented_ce_scratch(B, Z, H, len(ks))
         if nbytes == 0:
             check(1)
-        scratch = _seg_scratch(dev, Z, nbytes)
-        ia = lambda v: (C.c_int * max(len(v), 1))(*v)  # noqa: E731
-        check(lib.egx_segmented_ce(addr, ld, ptr(tgt), B, Z, H, ia(col0), ia(widths), ia(ks), len(ks), ptr(loss), ptr(terms), ptr(n_valid),
-                                   ptr(correct) if len(ks) else None, ptr(dl), ptr(scratch), _stream()))
+        scratch = _zeroed_scratch("segmented_cross_entropy", dev, nbytes, key=(Z,))
+        check(lib.egx_segmented_ce(addr, ld, ptr(tgt), B, Z, H, _c_ints(col0), _c_ints(widths), _c_ints(ks), len(ks), ptr(loss), ptr(terms),
+                                   ptr(n_valid), ptr(correct) if len(ks) else None, ptr(dl), ptr(scratch), _stream()))
         ctx.n_heads = H
         ctx.windows = list(zip(col0, widths)) if need else None
         if need:
             ctx.save_for_backward(dl)
-        # fresh tensor objects over the result memory: a persistent buffer handed in through `out` must not become the owner of this call's
-        # autograd graph (it would keep the graph - and the logits' gradient accumulator, with the stream it was created on - alive into the
-        # next call, e.g. from an eager step on the default stream into a capture)
-        loss, terms, n_valid, correct = loss.detach(), terms.detach(), n_valid.detach(), correct.detach()
+        loss, terms, n_valid, correct = _fresh(loss, terms, n_valid, correct)
         ctx.mark_non_differentiable(terms, n_valid, correct)
         ctx.set_materialize_grads(False)
         return loss, terms, n_valid, correct
@@ -2105,10 +2115,7 @@ class SegmentedCEFn(torch.autograd.Function):
     def backward(ctx, g_loss, _gt, _gn, _gc):
         if ctx.windows is None or g_loss is None:
             return (None,) * (3 + ctx.n_heads)
-        (dl,) = ctx.saved_tensors
-        u = _UNIT_GRAD.get(dl.device.index)
-        if u is None or g_loss.data_ptr() != u.data_ptr():
-            dl = dl * g_loss
+        dl = _scaled_by_upstream(ctx.saved_tensors[0], g_loss)
         return (None, None, None) + tuple(dl[..., c0:c0 + w] if ctx.needs_input_grad[3 + h] else None for h, (c0, w) in enumerate(ctx.windows))
 
 
@@ -2130,21 +2137,6 @@ def segmented_cross_entropy(preds, labels, ks=(1, 5), out=None):
 # ---- the PNR keyframe criterion: BCE / masked CE, keyframe distance and accuracy in one launch (csrc/keyframe.hip) -----------------------
 KEYFRAME_MAX_T, KEYFRAME_MAX_V = 64, 2048
 KEYFRAME_KINDS = {"bce": 0, "cross_entropy": 1, None: 2}
-_KF_SCRATCH = {}
-
-
-def _kf_scratch(device, nbytes: int) -> torch.Tensor:
-    """Scratch of egx_keyframe_criterion, by the rules of _seg_scratch: one per device, zero-filled once, never created inside a capture.
-    Its size does not depend on the shape and every launch leaves its arrival counter zero, so every shape shares it."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    t = _KF_SCRATCH.get(key)
-    if t is None or t.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("keyframe_criterion: run one eager step at this problem size before capturing it in a graph")
-        if t is not None:
-            _LCE_RETIRED.append(t)
-        t = _KF_SCRATCH[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-    return t
 
 
 def _kf_rows(t, B: int, dtype, dev, name: str):
@@ -2197,25 +2189,20 @@ class KeyframeCriterionFn(torch.autograd.Function):
         timed = timing[0] is not None
         with_loss = kind is not None
         out = out or {}
-
-        def buf(name, shape, dtype, wanted=True):
-            if not wanted:
-                return None
-            return out[name] if name in out else torch.empty(shape, dtype=dtype, device=dev)
-
-        loss = buf("loss", (), torch.float32, with_loss)
-        loss_rows = buf("loss_rows", (B,), torch.float32, with_loss)
-        pred = buf("pred", (B,), torch.int32)
-        label_frame = buf("label_frame", (B,), torch.int32)
-        counts = buf("counts", (4,), torch.int32)
-        dist = buf("dist", (B,), torch.float64, timed)
-        dist_sum = buf("dist_sum", (), torch.float64, timed)
+        loss = _out_tensor(out, "loss", (), torch.float32, dev, with_loss)
+        loss_rows = _out_tensor(out, "loss_rows", (B,), torch.float32, dev, with_loss)
+        pred = _out_tensor(out, "pred", (B,), torch.int32, dev)
+        label_frame = _out_tensor(out, "label_frame", (B,), torch.int32, dev)
+        counts = _out_tensor(out, "counts", (4,), torch.int32, dev)
+        dist = _out_tensor(out, "dist", (B,), torch.float64, dev, timed)
+        dist_sum = _out_tensor(out, "dist_sum", (), torch.float64, dev, timed)
         need = with_loss and ctx.needs_input_grad[0]
         dl = torch.empty((B, ld), dtype=torch.float32, device=dev) if need else None
         nbytes = lib.egx_keyframe_scratch(B)
         if nbytes == 0:
             check(1)
-        scratch = _kf_scratch(dev, nbytes)
+        # the size does not depend on the shape and every launch leaves the arrival counter zero, so every shape shares the buffer
+        scratch = _zeroed_scratch("keyframe_criterion", dev, nbytes)
         ca = (C.c_int * T)(*cols) if cols is not None else None
         check(lib.egx_keyframe_criterion(x.data_ptr(), ld, B, T, ca, V, KEYFRAME_KINDS[kind], ptr(tgt), ptr(lab), ptr(sc), ptr(timing[0]),
                                          ptr(timing[1]), ptr(timing[2]), ptr(timing[3]), ptr(loss), ptr(loss_rows), ptr(dl), ptr(pred),
@@ -2223,8 +2210,7 @@ class KeyframeCriterionFn(torch.autograd.Function):
         ctx.grad_shape = (tuple(preds.shape), V) if need else None
         if need:
             ctx.save_for_backward(dl)
-        # fresh tensor objects over the result memory, as in SegmentedCEFn: a persistent buffer must not own this call's autograd graph
-        res = tuple(None if t is None else t.detach() for t in (loss, loss_rows, pred, label_frame, counts, dist, dist_sum))
+        res = _fresh(loss, loss_rows, pred, label_frame, counts, dist, dist_sum)
         ctx.mark_non_differentiable(*[t for t in res[1:] if t is not None])
         ctx.set_materialize_grads(False)
         return res
@@ -2233,10 +2219,7 @@ class KeyframeCriterionFn(torch.autograd.Function):
     def backward(ctx, g_loss, *_rest):
         if ctx.grad_shape is None or g_loss is None:
             return (None,) * 11
-        (dl,) = ctx.saved_tensors
-        u = _UNIT_GRAD.get(dl.device.index)
-        if u is None or g_loss.data_ptr() != u.data_ptr():
-            dl = dl * g_loss
+        dl = _scaled_by_upstream(ctx.saved_tensors[0], g_loss)
         shape, V = ctx.grad_shape
         return (dl[:, :V].reshape(shape),) + (None,) * 10
 
@@ -2303,47 +2286,22 @@ def lta_validate(preds, labels=None, k: int = 1, seed=None, seed_ptr=None, token
                 raise ValueError("lta_validate: tokens= is the metric-only entry and needs labels")
             addr, ld, col0, widths = None, 0, [], []
         else:
-            preds = list(preds)
-            H = len(preds)
-            if not 1 <= H <= SEG_CE_MAX_HEADS:
-                raise ValueError(f"lta_validate takes 1 to {SEG_CE_MAX_HEADS} heads, got {H}")
-            for h, p in enumerate(preds):
-                _dev_f32(p[:0], f"preds[{h}]")                   # device / dtype refusal only: the heads stay the views they are
-            p0 = preds[0]
-            if any(p.dim() != 3 or p.shape[:2] != p0.shape[:2] or p.device != p0.device for p in preds):
-                raise ValueError(f"lta_validate expects (B, Z, C_h) heads of one batch, got {[tuple(p.shape) for p in preds]}")
-            B, Z, dev = p0.shape[0], p0.shape[1], p0.device
-            widths = [p.shape[2] for p in preds]
-            win = _seg_windows(preds)
-            if win is None:                                     # one concatenation builds the stack
-                stack = torch.cat(preds, dim=-1).contiguous()
-                ld, col0, off = stack.shape[2], [], 0
-                for w in widths:
-                    col0.append(off)
-                    off += w
-                addr = stack.data_ptr()
-            else:
-                addr, ld, col0 = win
+            B, Z, H, dev, widths, addr, ld, col0, _stack = _head_stack("lta_validate", list(preds))      # _stack: alive until the launch
         if labels is not None:
-            if labels.dtype != torch.int64 or tuple(labels.shape) != (B, Z, H) or labels.device != dev:
-                raise ValueError(f"labels must be an int64 tensor of shape (B, Z, H) = {(B, Z, H)} on the predictions' device")
-            labels = labels.contiguous()
+            labels = _head_labels(labels, B, Z, H, dev)
         if isinstance(seed_ptr, torch.Tensor):
             if seed_ptr.dtype != torch.int64 or seed_ptr.numel() != 1 or seed_ptr.device != dev:
                 raise ValueError("lta_validate: seed_ptr must be a one-element int64 tensor on the predictions' device")
             seed_ptr = seed_ptr.data_ptr()
         if seed is None:
             seed = _lta_val_host_seed() if (k > 1 and not seed_ptr and tok_in is None) else 0
-        toks = out["preds"] if "preds" in out else torch.empty((H, B, k, Z), dtype=torch.int64, device=dev)
+        toks = _out_tensor(out, "preds", (H, B, k, Z), torch.int64, dev)
         if tuple(toks.shape) != (H, B, k, Z) or toks.dtype != torch.int64 or not toks.is_contiguous():
             raise ValueError(f"lta_validate: out['preds'] must be a contiguous int64 tensor of shape (H, B, K, Z) = {(H, B, k, Z)}")
-        md = ds = None
-        if labels is not None:
-            md = out["min_dist"] if "min_dist" in out else torch.empty((B, Z, H), dtype=torch.int32, device=dev)
-            ds = out["dist_sum"] if "dist_sum" in out else torch.empty((Z, H), dtype=torch.int64, device=dev)
-        ia = lambda v: (C.c_int * max(len(v), 1))(*v)  # noqa: E731
-        check(lib.egx_lta_validate(addr, ld, ptr(labels), B, Z, H, ia(col0), ia(widths), k, _seed64(seed), seed_ptr or None, ptr(tok_in),
-                                   ptr(toks), ptr(md), ptr(ds), _stream()))
+        md = _out_tensor(out, "min_dist", (B, Z, H), torch.int32, dev, labels is not None)
+        ds = _out_tensor(out, "dist_sum", (Z, H), torch.int64, dev, labels is not None)
+        check(lib.egx_lta_validate(addr, ld, ptr(labels), B, Z, H, _c_ints(col0), _c_ints(widths), k, _seed64(seed), seed_ptr or None,
+                                   ptr(tok_in), ptr(toks), ptr(md), ptr(ds), _stream()))
     return [toks[h] for h in range(H)], {"min_dist": md, "dist_sum": ds}
 
 

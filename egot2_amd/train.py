@@ -40,7 +40,37 @@ class CrossEntropyLoss(nn.Module):
         return F_egx.weighted_cross_entropy(input, target, self.weight)
 
 
-class LTACriterion(nn.Module):
+class _DeviceCriterion(nn.Module):
+    """What the one-launch criteria share: persistent result buffers per (device, *problem dims) - `_bufs`, laid out by the subclass's
+    `_allocate(device, *dims)` - and `_last`, the buffers of the most recent forward, which every call or replay refreshes."""
+
+    def __init__(self):
+        super().__init__()
+        self._bufs: Dict[tuple, dict] = {}
+        self._last: Optional[dict] = None
+
+    @staticmethod
+    def _capturing(device) -> bool:
+        return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def _result_buffers(self, device, *dims) -> dict:
+        device = torch.device(device)
+        key = (device.type, device.index, *dims)
+        b = self._bufs.get(key)
+        if b is None:
+            if self._capturing(device):
+                # a buffer created inside a capture would live in that graph's private pool
+                raise RuntimeError(f"{type(self).__name__}: run one eager step at this problem size before capturing it in a graph")
+            b = self._bufs[key] = self._allocate(device, *dims)
+        return b
+
+    def _latest(self) -> dict:
+        if self._last is None:
+            raise RuntimeError(f"{type(self).__name__}: no forward has run yet")
+        return self._last
+
+
+class LTACriterion(_DeviceCriterion):
     """The criterion of the long-term-anticipation task, LongTermAnticipationTask.training_step (HOI/tasks/lta/long_term_anticipation.py:182-203):
 
         loss = sum over heads h, future steps z of nn.CrossEntropyLoss()(preds[h][:, z], labels[:, z, h])
@@ -60,26 +90,16 @@ class LTACriterion(nn.Module):
         self.ks = tuple(int(k) for k in ks)
         if not 1 <= len(self.ks) <= F_egx.SEG_CE_MAX_KS or min(self.ks) < 1:
             raise ValueError(f"LTACriterion: ks={ks} (needs 1 to {F_egx.SEG_CE_MAX_KS} values >= 1)")
-        self._bufs: Dict[tuple, dict] = {}
-        self._last: Optional[dict] = None
 
-    def _result_buffers(self, device, Z: int, H: int) -> dict:
+    def _allocate(self, device, Z: int, H: int) -> dict:
         """loss | loss_terms (Z, H) | n_valid (Z, H) | correct (len(ks), Z, H) as views of one buffer of 4-byte words (`flat`)."""
-        device = torch.device(device)
-        key = (device.type, device.index, Z, H)
-        b = self._bufs.get(key)
-        if b is None:
-            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                # a buffer created inside a capture would live in that graph's private pool
-                raise RuntimeError("LTACriterion: run one eager step at this problem size before capturing it in a graph")
-            n = Z * H
-            flat = torch.zeros(1 + n * (2 + len(self.ks)), dtype=torch.int32, device=device)
-            b = self._bufs[key] = {"flat": flat, "Z": Z, "H": H,
-                                   "loss": flat[0:1].view(torch.float32).view(()),
-                                   "loss_terms": flat[1:1 + n].view(torch.float32).view(Z, H),
-                                   "n_valid": flat[1 + n:1 + 2 * n].view(Z, H),
-                                   "correct": flat[1 + 2 * n:].view(len(self.ks), Z, H)}
-        return b
+        n = Z * H
+        flat = torch.zeros(1 + n * (2 + len(self.ks)), dtype=torch.int32, device=device)
+        return {"flat": flat, "Z": Z, "H": H,
+                "loss": flat[0:1].view(torch.float32).view(()),
+                "loss_terms": flat[1:1 + n].view(torch.float32).view(Z, H),
+                "n_valid": flat[1 + n:1 + 2 * n].view(Z, H),
+                "correct": flat[1 + 2 * n:].view(len(self.ks), Z, H)}
 
     def forward(self, preds, labels: torch.Tensor) -> torch.Tensor:
         preds = list(preds)
@@ -90,21 +110,23 @@ class LTACriterion(nn.Module):
 
     def stats(self) -> dict:
         """Device tensors of the most recent call (or replay): `loss`, `loss_terms`, `n_valid`, `correct`. Reading them does not synchronise."""
-        if self._last is None:
-            raise RuntimeError("LTACriterion: no forward has run yet")
-        return {k: self._last[k] for k in ("loss", "loss_terms", "n_valid", "correct")}
+        b = self._latest()
+        return {k: b[k] for k in ("loss", "loss_terms", "n_valid", "correct")}
+
+    def host_result(self):
+        """-> (loss, n_valid (Z, H), correct (len(ks), Z, H)) of the most recent call (or replay) as host values, from ONE device-to-host
+        copy of `flat` (it synchronises)."""
+        b = self._latest()
+        Z, H, n = b["Z"], b["H"], b["Z"] * b["H"]
+        host = b["flat"].cpu().numpy()
+        return float(host[0:1].view("float32")[0]), host[1 + n:1 + 2 * n].reshape(Z, H), host[1 + 2 * n:].reshape(len(self.ks), Z, H)
 
     def step_result(self, prefix: str = "train") -> Dict[str, float]:
         """The reference's step_result of the most recent call (or replay), from ONE device-to-host copy (it synchronises: for logging):
         f"{prefix}_{z}_{h}_top{k}_err" = (1 - correct / n_valid) * 100 for every k of `ks`, f"{prefix}_{h}_top{k}_err" = their mean over z,
         f"{prefix}_loss"."""
-        if self._last is None:
-            raise RuntimeError("LTACriterion: no forward has run yet")
-        b = self._last
-        Z, H, n = b["Z"], b["H"], b["Z"] * b["H"]
-        host = b["flat"].cpu().numpy()
-        n_valid = host[1 + n:1 + 2 * n].reshape(Z, H).astype("float64")
-        correct = host[1 + 2 * n:].reshape(len(self.ks), Z, H).astype("float64")
+        loss, n_valid, correct = self.host_result()
+        (Z, H), n_valid, correct = n_valid.shape, n_valid.astype("float64"), correct.astype("float64")
         res: Dict[str, float] = {}
         for ki, k in enumerate(self.ks):
             for h in range(H):
@@ -115,11 +137,11 @@ class LTACriterion(nn.Module):
                     res[f"{prefix}_{z}_{h}_top{k}_err"] = float(e)
                     errs.append(e)
                 res[f"{prefix}_{h}_top{k}_err"] = float(sum(errs) / len(errs))
-        res[f"{prefix}_loss"] = float(host[0:1].view("float32")[0])
+        res[f"{prefix}_loss"] = loss
         return res
 
 
-class LTAValidation(nn.Module):
+class LTAValidation(_DeviceCriterion):
     """The validation step of the long-term-anticipation task, LongTermAnticipationTask.validation_step
     (HOI/tasks/lta/long_term_anticipation.py:222-248; :313-341 for the sequence tasks):
 
@@ -142,14 +164,8 @@ class LTAValidation(nn.Module):
         self.k = int(k)
         if not 1 <= self.k <= F_egx.LTA_VAL_MAX_K:
             raise ValueError(f"LTAValidation: k={k} (needs 1 <= k <= {F_egx.LTA_VAL_MAX_K} sequences per clip)")
-        self._bufs: Dict[tuple, dict] = {}
         self._seeds: Dict[tuple, torch.Tensor] = {}
         self._seed0: Optional[int] = None
-        self._last: Optional[dict] = None
-
-    @staticmethod
-    def _capturing(device) -> bool:
-        return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
     def manual_seed(self, s: int) -> "LTAValidation":
         """Set the device seed word (of every device used so far, and of those to come) to `s`."""
@@ -171,19 +187,11 @@ class LTAValidation(nn.Module):
             t = self._seeds[key] = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=device)
         return t
 
-    def _result_buffers(self, device, B: int, Z: int, H: int) -> dict:
-        device = torch.device(device)
-        key = (device.type, device.index, B, Z, H)
-        b = self._bufs.get(key)
-        if b is None:
-            if self._capturing(device):
-                # a buffer created inside a capture would live in that graph's private pool
-                raise RuntimeError("LTAValidation: run one eager step at this problem size before capturing it in a graph")
-            b = self._bufs[key] = {"B": B, "Z": Z, "H": H,
-                                   "preds": torch.zeros((H, B, self.k, Z), dtype=torch.int64, device=device),
-                                   "min_dist": torch.zeros((B, Z, H), dtype=torch.int32, device=device),
-                                   "dist_sum": torch.zeros((Z, H), dtype=torch.int64, device=device)}
-        return b
+    def _allocate(self, device, B: int, Z: int, H: int) -> dict:
+        return {"B": B, "Z": Z, "H": H,
+                "preds": torch.zeros((H, B, self.k, Z), dtype=torch.int64, device=device),
+                "min_dist": torch.zeros((B, Z, H), dtype=torch.int32, device=device),
+                "dist_sum": torch.zeros((Z, H), dtype=torch.int64, device=device)}
 
     def forward(self, preds, labels: torch.Tensor, seed: Optional[int] = None):
         """-> tokens, the list of (B, K, Z) int64 tensors `generate` returns (views of the persistent buffer). seed: a host seed for
@@ -205,18 +213,15 @@ class LTAValidation(nn.Module):
 
     def stats(self) -> dict:
         """Device tensors of the most recent call (or replay): `tokens` (H, B, K, Z), `min_dist`, `dist_sum`. Reading them does not synchronise."""
-        if self._last is None:
-            raise RuntimeError("LTAValidation: no forward has run yet")
-        return {"tokens": self._last["preds"], "min_dist": self._last["min_dist"], "dist_sum": self._last["dist_sum"]}
+        b = self._latest()
+        return {"tokens": b["preds"], "min_dist": b["min_dist"], "dist_sum": b["dist_sum"]}
 
     def step_result(self, prefix: str = "val") -> Dict[str, float]:
         """The reference's step_result of the most recent call (or replay), from ONE device-to-host copy (it synchronises), in fp64:
         f"{prefix}_{h}_ED_{z}" = dist_sum[z, h] / (B (z + 1)), f"{prefix}_{h}_AUED" = trapz over z / (Z - 1) (nan at Z = 1, as numpy gives
         the reference). Across ranks: all-reduce dist_sum and B first."""
-        if self._last is None:
-            raise RuntimeError("LTAValidation: no forward has run yet")
+        b = self._latest()
         import numpy as np
-        b = self._last
         B, Z, H = b["B"], b["Z"], b["H"]
         ds = b["dist_sum"].cpu().numpy().astype(np.float64)
         res: Dict[str, float] = {}
@@ -230,7 +235,7 @@ class LTAValidation(nn.Module):
         return res
 
 
-class KeyframeCriterion(nn.Module):
+class KeyframeCriterion(_DeviceCriterion):
     """The training / validation step of the PNR keyframe task after the model, KeyframeLocalisation2Loader.training_step
     (HOI/tasks/pnr/video_taskspecific_pnr.py:24-63, recipe HOI/configs/pnr/ts_pnr.yaml: LOSS_FUNC "bce"):
 
@@ -259,29 +264,19 @@ class KeyframeCriterion(nn.Module):
         self.cols = None if cols is None else tuple(int(c) for c in cols)
         if self.cols is not None and not 1 <= len(self.cols) <= F_egx.KEYFRAME_MAX_T:
             raise ValueError(f"KeyframeCriterion: {len(self.cols)} columns (needs 1 to {F_egx.KEYFRAME_MAX_T} frames)")
-        self._bufs: Dict[tuple, dict] = {}
-        self._last: Optional[dict] = None
 
-    def _result_buffers(self, device, B: int, T: int) -> dict:
+    def _allocate(self, device, B: int, T: int) -> dict:
         """dist_sum (fp64) | loss | pad | counts [n_sc, n_correct, n_outside, B] as views of one buffer of 4-byte words (`flat`), and the
         per-clip pred, label_frame, loss_rows, dist."""
-        device = torch.device(device)
-        key = (device.type, device.index, B, T)
-        b = self._bufs.get(key)
-        if b is None:
-            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                # a buffer created inside a capture would live in that graph's private pool
-                raise RuntimeError("KeyframeCriterion: run one eager step at this problem size before capturing it in a graph")
-            flat = torch.zeros(8, dtype=torch.int32, device=device)
-            b = self._bufs[key] = {"flat": flat, "B": B, "T": T,
-                                   "dist_sum": flat[0:2].view(torch.float64).view(()),
-                                   "loss": flat[2:3].view(torch.float32).view(()),
-                                   "counts": flat[4:8],
-                                   "pred": torch.zeros(B, dtype=torch.int32, device=device),
-                                   "label_frame": torch.zeros(B, dtype=torch.int32, device=device),
-                                   "loss_rows": torch.zeros(B, dtype=torch.float32, device=device),
-                                   "dist": torch.zeros(B, dtype=torch.float64, device=device)}
-        return b
+        flat = torch.zeros(8, dtype=torch.int32, device=device)
+        return {"flat": flat, "B": B, "T": T,
+                "dist_sum": flat[0:2].view(torch.float64).view(()),
+                "loss": flat[2:3].view(torch.float32).view(()),
+                "counts": flat[4:8],
+                "pred": torch.zeros(B, dtype=torch.int32, device=device),
+                "label_frame": torch.zeros(B, dtype=torch.int32, device=device),
+                "loss_rows": torch.zeros(B, dtype=torch.float32, device=device),
+                "dist": torch.zeros(B, dtype=torch.float64, device=device)}
 
     def forward(self, preds, labels=None, state_change_label=None, fps=None, info=None):
         """-> loss (None with loss_func=None). labels: (B, T) one-hot (the reference's `labels`), or - the metric with cols - the (B,) /
@@ -304,9 +299,7 @@ class KeyframeCriterion(nn.Module):
         """Device tensors of the most recent call (or replay): `loss`, `counts`, `dist_sum`, `pred`, `label_frame`, `loss_rows`, `dist`.
         Reading them does not synchronise. What that call did not write is None, as functional.keyframe_criterion returns it: `dist` and
         `dist_sum` without fps / info, `loss` and `loss_rows` with loss_func=None."""
-        if self._last is None:
-            raise RuntimeError("KeyframeCriterion: no forward has run yet")
-        b = self._last
+        b = self._latest()
         unwritten = (() if b.get("timed", True) else ("dist", "dist_sum")) + (("loss", "loss_rows") if self.loss_func is None else ())
         return {k: None if k in unwritten else b[k] for k in ("loss", "counts", "dist_sum", "pred", "label_frame", "loss_rows", "dist")}
 
@@ -316,10 +309,9 @@ class KeyframeCriterion(nn.Module):
         keyframe_loc_metric_time_dist_train = dist_sum / n_sc (0.0 without one, as the reference returns). "val":
         keyframe_loc_metric_time_dist_val, its negative (the checkpoint metric) and pseudo_acc. With cols and loss_func=None (the EgoT2-g
         metric, any prefix): dist = dist_sum / B, err = n_outside / B, acc = n_correct / B. Across ranks: all-reduce counts and dist_sum."""
-        if self._last is None:
-            raise RuntimeError("KeyframeCriterion: no forward has run yet")
-        host = self._last["flat"].cpu().numpy()
-        dist_sum = float(host[0:2].view("float64")[0]) if self._last.get("timed", True) else float("nan")      # no fps / info: no distance
+        b = self._latest()
+        host = b["flat"].cpu().numpy()
+        dist_sum = float(host[0:2].view("float64")[0]) if b.get("timed", True) else float("nan")      # no fps / info: no distance
         loss = float(host[2:3].view("float32")[0])
         n_sc, n_correct, n_outside, B = (int(v) for v in host[4:8])
         if self.cols is not None and self.loss_func is None:
@@ -358,8 +350,8 @@ class OSCCCriterion(nn.Module):
         """"train": state_change_loss, train_loss, loss, state_change_metric_train = correct / B; "val": state_change_metric_val."""
         if self._crit._last is None:
             raise RuntimeError("OSCCCriterion: no forward has run yet")
-        host = self._crit._last["flat"].cpu().numpy()           # loss | loss_terms (1) | n_valid (1) | correct (1)
-        loss, acc = float(host[0:1].view("float32")[0]), int(host[3]) / max(self._B, 1)
+        loss, _, correct = self._crit.host_result()             # one future step, one head, ks = (1,)
+        acc = int(correct[0, 0, 0]) / max(self._B, 1)
         if prefix == "train":
             return {"state_change_loss": loss, "train_loss": loss, "loss": loss, "state_change_metric_train": acc}
         if prefix == "val":

@@ -124,6 +124,53 @@ def test_shapes_can_alternate_on_the_shared_scratch(egx_lib, cuda):
         seen[i] = got
 
 
+def test_zeroed_scratch_rules(egx_lib, cuda, monkeypatch):
+    """functional._zeroed_scratch: one buffer per (operator, device, key), zero-filled when created, at least `floor` bytes, an outgrown one
+    retired instead of freed, and none created inside a capture."""
+    import re
+    from egot2_amd import functional as F_egx
+    who = "zeroed_scratch_rules"
+    a = F_egx._zeroed_scratch(who, cuda, 256, key=(1,))
+    assert a.dtype == torch.uint8 and a.numel() == 256 and a.device == cuda and not a.any()
+    assert F_egx._zeroed_scratch(who, cuda, 256, key=(1,)) is a
+    assert F_egx._zeroed_scratch(who, cuda, 64, key=(1,)) is a                  # a smaller request is served by the same buffer
+    z3 = F_egx._zeroed_scratch(who, cuda, 256, key=(3,))
+    assert z3 is not a and z3.data_ptr() != a.data_ptr()                        # another key (Z = 1 / Z = 3): another buffer
+    assert F_egx._zeroed_scratch(who + "_other", cuda, 256, key=(1,)) is not a  # another operator: another buffer
+    a.fill_(0xFF)
+    grown = F_egx._zeroed_scratch(who, cuda, 1024, key=(1,))
+    assert grown is not a and grown.numel() == 1024 and not grown.any()         # new memory, zero-filled
+    assert grown.data_ptr() != a.data_ptr() and any(t is a for t in F_egx._SCRATCH_RETIRED)      # the outgrown one is retired, not freed
+    assert bool((a == 0xFF).all())                                              # and untouched: a graph may still replay into it
+    assert F_egx._zeroed_scratch(who, cuda, 256, key=(1,)) is grown
+    floored = F_egx._zeroed_scratch(who, cuda, 100, key=("floor",), floor=1 << 16)
+    assert floored.numel() == 1 << 16 and not floored.any()
+    assert F_egx._zeroed_scratch(who, cuda, 1 << 16, key=("floor",), floor=1 << 16) is floored
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    assert F_egx._zeroed_scratch(who, cuda, 1024, key=(1,)) is grown             # an existing buffer serves a capture
+    with pytest.raises(RuntimeError, match="^" + re.escape(f"{who}: run one eager step at this problem size before capturing it in a graph") + "$"):
+        F_egx._zeroed_scratch(who, cuda, 256, key=("capture",))
+    with pytest.raises(RuntimeError, match="run one eager step at this problem size"):
+        F_egx._zeroed_scratch(who, cuda, 2048, key=(1,))                        # nor is one grown inside a capture
+
+
+def test_head_stack_routes(egx_lib, cuda):
+    """functional._head_stack: views of one (2, 3, 10) stack are addressed in place (no copy); separate contiguous tensors go through one
+    torch.cat with ld = 10 and col0 = [0, 3]; both report the same B, Z, H, widths."""
+    from egot2_amd import functional as F_egx
+    base = torch.arange(60, dtype=torch.float32, device=cuda).reshape(2, 3, 10)
+    views = list(torch.split(base, [3, 7], dim=-1))
+    B, Z, H, dev, widths, addr, ld, col0, stack = F_egx._head_stack("lta_validate", views)
+    assert (B, Z, H, dev, widths) == (2, 3, 2, cuda, [3, 7])
+    assert addr == base.data_ptr() and ld == 10 and list(col0) == [0, 3] and stack is None
+    B2, Z2, H2, dev2, widths2, addr2, ld2, col02, stack2 = F_egx._head_stack("lta_validate", [v.contiguous() for v in views])
+    assert (B2, Z2, H2, dev2, widths2) == (B, Z, H, dev, widths)
+    assert ld2 == 10 and list(col02) == [0, 3]
+    assert stack2 is not None and addr2 == stack2.data_ptr() and addr2 != base.data_ptr() and torch.equal(stack2, base)
+    with pytest.raises(ValueError, match="^lta_validate takes 1 to 4 heads, got 5$"):
+        F_egx._head_stack("lta_validate", views * 2 + views[:1])
+
+
 def test_upstream_gradient_scales_d_logits(egx_lib, cuda):
     from egot2_amd import functional as F_egx
     logits, labels, ks = sr.seg_inputs(2)
