@@ -70,6 +70,13 @@ class TokenCe(C.Structure):
                 ("loss", _fp), ("correct", _fp), ("d_logits", _fp), ("d_W", _fp), ("d_b", _fp)]
 
 
+class SeqTask(C.Structure):
+    """egx_seq_task: one task of egx_sequence_ce (strides in elements; d_logits, word_label, labels and pred may be NULL)."""
+    _fields_ = [("logits", _fp), ("stride_b", C.c_longlong), ("stride_s", C.c_longlong), ("B", C.c_int), ("sy", C.c_int), ("target", _fp),
+                ("target_stride_b", C.c_longlong), ("target_stride_s", C.c_longlong), ("ratio", C.c_float), ("d_logits", _fp),
+                ("word_label", _fp), ("labels", _fp), ("labels_stride_b", C.c_longlong), ("labels_stride_s", C.c_longlong), ("pred", _fp)]
+
+
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
 EGX_LR_CONSTANT, EGX_LR_COSINE_ANNEALING, EGX_LR_WARMUP_COSINE, EGX_LR_WARMUP_LINEAR, EGX_LR_TABLE = 0, 1, 2, 3, 4
@@ -223,6 +230,9 @@ SIGNATURES = {
     "egx_keyframe_scratch": (C.c_size_t, [C.c_int]),
     "egx_keyframe_criterion": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                          _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # ABI v21 additions: the EgoT2-g multi-task sequence criterion and metrics in one launch (tasks is a host array of egx_seq_task)
+    "egx_sequence_ce_scratch": (C.c_size_t, []),
+    "egx_sequence_ce": (C.c_int, [C.POINTER(SeqTask), C.c_int, C.c_int, _fp, _fp, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

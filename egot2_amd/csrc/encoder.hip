@@ -847,6 +847,20 @@ int egx_keyframe_criterion(const float* logits, int ld, int B, int T, const int*
                               loss_rows, d_logits, pred, label_frame, counts, dist, dist_sum, scratch, (hipStream_t)stream);
 }
 
+// ABI v21 additions: the EgoT2-g multi-task sequence criterion and metrics (seq_ce.hip); every argument is checked on the host before any
+// device work
+static_assert(sizeof(egx_seq_task) == 112, "egx_seq_task: the layout the bindings declare");
+size_t egx_sequence_ce_scratch(void) { return sequence_ce_scratch_bytes(); }
+int egx_sequence_ce(const egx_seq_task* tasks, int T, int V, void* result, void* scratch, void* stream) {
+    SeqCeTask k[SEQ_CE_MAX_TASKS];
+    for (int t = 0; tasks && t < T && t < SEQ_CE_MAX_TASKS; ++t) {
+        const egx_seq_task& a = tasks[t];
+        k[t] = SeqCeTask{a.logits, a.stride_b, a.stride_s, a.B, a.sy, a.target, a.target_stride_b, a.target_stride_s, a.ratio, a.d_logits,
+                         a.word_label, a.labels, a.labels_stride_b, a.labels_stride_s, a.pred};
+    }
+    return sequence_ce(tasks ? k : nullptr, T, V, (int*)result, scratch, (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

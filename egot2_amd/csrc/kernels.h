@@ -153,6 +153,22 @@ int keyframe_criterion(const float* logits, int ld, int B, int T, const int* col
                        const int64_t* pnr_frame, float* loss, float* loss_rows, float* dlogits, int* pred, int* label_frame, int* counts,
                        double* dist, double* dist_sum, void* scratch, hipStream_t st);
 
+// seq_ce.hip: the EgoT2-g multi-task criterion (per-task mean cross-entropies times their ratios, word-to-label metrics, d loss / d logits)
+// in one launch. SeqCeTask has the fields of the C ABI's egx_seq_task.
+constexpr int SEQ_CE_MAX_TASKS = 8, SEQ_CE_MAX_CLASSES = 2048, SEQ_CE_MAX_SY = 64, SEQ_CE_MAX_ROWS = 1 << 22;
+struct SeqCeTask {
+    const float* logits; long long stride_b, stride_s;
+    int B, sy;
+    const int64_t* target; long long target_stride_b, target_stride_s;
+    float ratio;
+    float* d_logits;
+    const int* word_label;
+    const int64_t* labels; long long labels_stride_b, labels_stride_s;
+    int* pred;
+};
+size_t sequence_ce_scratch_bytes();
+int sequence_ce(const SeqCeTask* tasks, int T, int V, int* result, void* scratch, hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

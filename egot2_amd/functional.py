@@ -2245,6 +2245,137 @@ def keyframe_criterion(preds, target=None, label=None, state_change=None, fps=No
     return loss, {"pred": pred, "label_frame": label_frame, "counts": counts, "loss_rows": loss_rows, "dist": dist, "dist_sum": dist_sum}
 
 
+# ---- the EgoT2-g multi-task criterion: per-task cross-entropies times their ratios + word-to-label metrics in one launch (csrc/seq_ce.hip) ---
+SEQ_CE_MAX_TASKS, SEQ_CE_MAX_CLASSES, SEQ_CE_MAX_SY = 8, 2048, 64
+SEQ_CE_STATS = ("loss_terms", "n_valid", "token_correct", "seq_correct", "scored", "invalid", "correct", "correct_restricted")
+
+
+def sequence_ce_views(flat: torch.Tensor, T: int) -> dict:
+    """The 1 + 8 T result words of egx_sequence_ce as named views: `loss` () and `loss_terms` (T,) fp32, the seven counts (T,) int32."""
+    v = {"loss": flat[0:1].view(torch.float32).view(()), "loss_terms": flat[1:1 + T].view(torch.float32)}
+    for i, name in enumerate(SEQ_CE_STATS[1:], start=1):
+        v[name] = flat[1 + i * T:1 + (i + 1) * T]
+    return v
+
+
+def _seq_positions(t, B: int, sy: int, dev, name: str):
+    """An int64 (B, sy) argument of sequence_cross_entropy, read in place through its strides (target[:, 1:] is no copy)."""
+    if t.dtype != torch.int64 or tuple(t.shape) != (B, sy) or t.device != dev:
+        raise ValueError(f"sequence_cross_entropy: {name} must be an int64 tensor of shape (B, sy) = {(B, sy)} on the logits' device")
+    return t
+
+
+class SequenceCEFn(torch.autograd.Function):
+    """(loss, flat, *pred) of egx_sequence_ce over the tasks' (B, V, sy) logits; the same launch leaves d loss / d logits of every task behind,
+    in the layout of its logits. `out` (optional {"flat": int32 (1 + 8 T,)}): where the results go (train.TranslationCriterion's persistent
+    buffer); only `loss` carries gradient."""
+
+    @staticmethod
+    def forward(ctx, targets, ratios, word_labels, labels, out, want_pred, *logits):
+        lib = _lib.load()
+        T = len(logits)
+        if not 1 <= T <= SEQ_CE_MAX_TASKS:
+            raise ValueError(f"sequence_cross_entropy takes 1 to {SEQ_CE_MAX_TASKS} tasks, got {T}")
+        if len(targets) != T or len(ratios) != T or len(word_labels) != T or len(labels) != T:
+            raise ValueError(f"sequence_cross_entropy: {T} logits need {T} targets, ratios, word_labels and labels")
+        for t, lg in enumerate(logits):
+            _dev_f32(lg[:0], f"logits[{t}]")                # device / dtype refusal only: the logits stay the views they are
+            if lg.dim() != 3 or lg.numel() == 0:
+                raise ValueError(f"sequence_cross_entropy expects non-empty (B, V, sy) logits, got {tuple(lg.shape)} for task {t}")
+        dev, V = logits[0].device, logits[0].shape[1]
+        if any(lg.shape[1] != V or lg.device != dev for lg in logits):
+            raise ValueError(f"sequence_cross_entropy: the tasks share one vocabulary and device, got {[tuple(lg.shape) for lg in logits]}")
+        tasks = (_lib.SeqTask * T)()
+        keep, dls, preds = [], [], []
+        for t, lg in enumerate(logits):
+            B, _, sy = lg.shape
+            x = lg.permute(0, 2, 1)                         # (B, sy, V): the rows the launch reads
+            if x.stride(2) != 1 or (B > 1 and x.stride(0) < V) or (sy > 1 and x.stride(1) < V):
+                x = x.contiguous()                          # a class axis that is not unit-stride (or rows that overlap): one copy
+            tgt = _seq_positions(targets[t], B, sy, dev, f"targets[{t}]")
+            wl, lab = word_labels[t], labels[t]
+            if (wl is None) != (lab is None):
+                raise ValueError(f"sequence_cross_entropy: task {t} needs word_labels and labels together (the metric inputs), or neither")
+            if wl is not None:
+                if wl.dtype != torch.int32 or tuple(wl.shape) != (V,) or wl.device != dev:
+                    raise ValueError(f"sequence_cross_entropy: word_labels[{t}] must be an int32 tensor of shape (V,) = {(V,)} on the logits' device")
+                wl = wl.contiguous()
+                if lab.dim() == 1 or (lab.dim() == 2 and lab.shape[1] == 1 and sy > 1):     # (B,) labels: position 0 is scored, the others are not
+                    full = torch.full((B, sy), -1, dtype=torch.int64, device=dev)
+                    full[:, 0] = lab.reshape(B)
+                    lab = full
+                lab = _seq_positions(lab, B, sy, dev, f"labels[{t}]")
+            need = ctx.needs_input_grad[6 + t]
+            dl = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev) if need else None
+            pred = None
+            if want_pred and wl is not None:
+                pred = out["pred"][t] if out and out.get("pred") is not None and out["pred"][t] is not None else \
+                    torch.empty((B, sy, 2), dtype=torch.int32, device=dev)
+            k = tasks[t]
+            k.logits, k.stride_b, k.stride_s, k.B, k.sy = x.data_ptr(), x.stride(0), x.stride(1), B, sy
+            k.target, k.target_stride_b, k.target_stride_s = tgt.data_ptr(), tgt.stride(0), tgt.stride(1)
+            k.ratio, k.d_logits, k.word_label = float(ratios[t]), ptr(dl), ptr(wl)
+            k.labels, k.labels_stride_b, k.labels_stride_s = (lab.data_ptr(), lab.stride(0), lab.stride(1)) if lab is not None else (None, 0, 0)
+            k.pred = ptr(pred)
+            keep.append((x, tgt, wl, lab))                  # alive until the launch
+            dls.append(dl)
+            preds.append(pred)
+        flat = out["flat"] if out and "flat" in out else torch.empty(1 + 8 * T, dtype=torch.int32, device=dev)
+        # one layout for every T and shape, and every launch leaves the arrival counters zero: every call shares the buffer
+        scratch = _zeroed_scratch("sequence_cross_entropy", dev, lib.egx_sequence_ce_scratch())
+        check(lib.egx_sequence_ce(tasks, T, V, ptr(flat), ptr(scratch), _stream()))
+        ctx.n_tasks = T
+        ctx.read_ptrs = tuple(k[0].data_ptr() for k in keep)        # the addresses the launch read the logits at (the tests compare them)
+        ctx.has_dl = [dl is not None for dl in dls]
+        ctx.save_for_backward(*[dl for dl in dls if dl is not None])
+        flat = flat.detach()
+        loss = flat[0:1].view(torch.float32).view(()).detach()
+        res = (loss, flat) + tuple(torch.empty(0, dtype=torch.int32, device=dev) if p is None else p.detach() for p in preds)
+        ctx.mark_non_differentiable(*res[1:])
+        ctx.set_materialize_grads(False)
+        return res
+
+    @staticmethod
+    def backward(ctx, g_loss, *_rest):
+        if g_loss is None or not any(ctx.has_dl):
+            return (None,) * (6 + ctx.n_tasks)
+        saved = iter(ctx.saved_tensors)
+        grads = []
+        for has in ctx.has_dl:                              # (B, sy, V) rows in the logits' own layout -> the (B, V, sy) input
+            grads.append(_scaled_by_upstream(next(saved), g_loss).permute(0, 2, 1) if has else None)
+        return (None,) * 6 + tuple(grads)
+
+
+def sequence_cross_entropy(logits, targets, ratios, word_labels=None, labels=None, out=None, want_pred=False):
+    """-> (loss, stats): the criterion of an EgoT2-g multi-task step (HHI/tasks/multitask/video_tasktranslation.py:39-66,
+    HOI/tasks/multitask/video_task.py:537-577) and the integers behind its validation metrics (:683-736) in one launch; nothing synchronises.
+
+    logits: list of 1 .. 8 fp32 (B_t, V, sy_t) tensors over ONE vocabulary (V <= 2048, sy_t <= 64) - what the EgoT2-g models return, a
+    permuted view of the decoder's (sy, B, V) output, which the kernel reads in place (so does it a permuted contiguous (B, sy, V) tensor; a
+    class axis that is not unit-stride costs one copy). targets: int64 (B_t, sy_t) each, read through their strides (target[:, 1:] is no
+    copy); a label outside [0, V) (ignore index -100 included) contributes no loss, count or gradient. ratios: one float per task.
+    loss = sum_t ratios[t] * F.cross_entropy(logits[t], targets[t]); a task without a valid label adds 0 (torch: nan).
+    word_labels / labels (per task, both or None): int32 (V,) device tensor - the original label of a vocabulary word or -1
+    (train.word_label_map) - and the int64 (B_t, sy_t) original labels, < 0 = not scored ((B_t,): position 0 is scored).
+    stats, all device tensors: `loss_terms` (T,) fp32; `n_valid`, `token_correct` (valid positions whose argmax is the target), `seq_correct`
+    (rows with a valid position and every valid position right), `scored`, `invalid` (scored positions whose argmax is no mapped word),
+    `correct` (its label is the position's), `correct_restricted` (the same for the argmax over the mapped words), each (T,) int32; among
+    equal logits the lower word wins. want_pred: `pred`, a list with an int32 (B_t, sy_t, 2) tensor (the label of the free and of the
+    restricted argmax) per task with metric inputs, None for the others. `out`: {"flat": int32 (1 + 8 T,)} preallocated results
+    (train.TranslationCriterion). The gradient of every logits tensor comes back in that tensor's own layout."""
+    logits = list(logits)
+    T = len(logits)
+    word_labels = list(word_labels) if word_labels is not None else [None] * T
+    labels = list(labels) if labels is not None else [None] * T
+    res = SequenceCEFn.apply(tuple(targets), tuple(float(r) for r in ratios), tuple(word_labels), tuple(labels), out, bool(want_pred), *logits)
+    stats = sequence_ce_views(res[1], T)
+    loss = res[0]
+    stats.pop("loss")
+    stats["flat"] = res[1]
+    stats["pred"] = [p if p.numel() else None for p in res[2:]] if want_pred else None
+    return loss, stats
+
+
 # ---- the LTA validation step: K sampled futures per clip and head + prefix edit distances in one launch (csrc/lta_val.hip) -----------
 LTA_VAL_MAX_K, LTA_VAL_MAX_Z = 8, 64
 _LTA_VAL_CALLS = [0]

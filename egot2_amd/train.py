@@ -16,6 +16,9 @@ HOI/evaluation/lta/lta_metrics.py:86-114) as one launch, capturable, with one de
 `KeyframeCriterion` is the PNR keyframe task's step after the model (HOI/tasks/pnr/video_taskspecific_pnr.py:24-63: BCE or masked CE,
 keyframe_distance and keyframe_accuracy of HOI/evaluation/pnr/metrics.py:23-80; with `cols` the EgoT2-g PnrOsccMetric) as one launch, and
 `OSCCCriterion` the state-change classification step (:138-160) on the LTA criterion's launch.
+`TranslationCriterion` is the criterion of the EgoT2-g multi-task steps (HHI/tasks/multitask/video_tasktranslation.py:39-66,
+HOI/tasks/multitask/video_task.py:537-577, :683-736: 3 or 6 cross-entropies on (B, |V|, sy) logits times their ratios, and the counts behind
+ARMetric / LTAMetric / PNRMetric / OSCCMetric) as one launch; `word_label_map` builds its vocabulary maps.
 """
 from __future__ import annotations
 
@@ -357,6 +360,154 @@ class OSCCCriterion(nn.Module):
         if prefix == "val":
             return {"state_change_metric_val": acc}
         raise ValueError(f"OSCCCriterion.step_result: prefix={prefix!r} (needs 'train' or 'val')")
+
+
+def word_label_map(vocab, label_words, size: Optional[int] = None) -> torch.Tensor:
+    """int32 (V,): the original label of every vocabulary word, -1 for a word that stands for none - the `word_labels` of
+    TranslationCriterion. vocab: a dict, or anything indexable by word (the reference's Vocabulary), word -> index; label_words:
+    {label: word} (the verb / noun dictionaries of map_label_to_action). A word that serves several labels keeps the LATER one, as the
+    reference's _map_vocab_to_orig_idx does (HOI/evaluation/lta/lta_metrics.py:178-183). size: V, default len(vocab)."""
+    V = int(size) if size is not None else len(vocab)
+    m = torch.full((V,), -1, dtype=torch.int32)
+    for label, word in label_words.items():
+        idx = int(vocab[word])
+        if not 0 <= idx < V:
+            raise ValueError(f"word_label_map: word {word!r} has index {idx}, outside the vocabulary of {V} words")
+        if int(label) < 0:
+            raise ValueError(f"word_label_map: label {label!r} of word {word!r} is negative (negative labels mean 'no label')")
+        m[idx] = int(label)
+    return m
+
+
+def binary_word_labels(vocab, size: Optional[int] = None) -> torch.Tensor:
+    """{'0': 0, '1': 1}: the HHI tasks' answers (Accuracy() on predict(...)[:, -2:], HHI/tasks/multitask/video_tasktranslation.py:101-102)."""
+    return word_label_map(vocab, {0: "0", 1: "1"}, size)
+
+
+def oscc_word_labels(vocab, size: Optional[int] = None) -> torch.Tensor:
+    """{'False': 0, 'True': 1}: OSCCMetric's oscc_indices (HOI/evaluation/pnr/metrics.py:224-226)."""
+    return word_label_map(vocab, {0: "False", 1: "True"}, size)
+
+
+def pnr_word_labels(vocab, size: Optional[int] = None) -> torch.Tensor:
+    """{'0': 0, ..., '15': 15}: PNRMetric's pnr_indices (HOI/evaluation/pnr/metrics.py:163-167)."""
+    return word_label_map(vocab, {i: str(i) for i in range(16)}, size)
+
+
+class TranslationCriterion(_DeviceCriterion):
+    """The criterion of an EgoT2-g multi-task step, Unified3TaskTranslation.training_step (HHI/tasks/multitask/video_tasktranslation.py:39-66)
+    and Unified6TaskTranslation.training_step / validation_step (HOI/tasks/multitask/video_task.py:537-577, :683-736):
+
+        loss_t = nn.CrossEntropyLoss()(logits_t, target_t[:, 1:]);  loss = sum_t ratio_t * loss_t;  self.log(..., loss_t.item())
+        metric_t.update(self.model.predict(...), labels_t)           # a second forward per task, Python loops with .item() per clip
+
+    as ONE launch (functional.sequence_cross_entropy) without a host synchronisation, so it can be the `loss_fn` of a GraphedStep; the
+    reference's 3 (6) cross-entropy calls - each on a copy of the permuted decoder output - and 4 (7) `.item()` reads become that launch
+    plus ONE device-to-host copy in `step_result()`. With the causal mask the position-0 logits of the teacher-forced forward are those
+    of predict(), so in eval mode the forward that gives the loss gives the metrics too.
+
+    ratios: one float per task; names: the log names (default: the reference's for 3 and 6 tasks); word_labels: per task None or the int32
+    (V,) map of `word_label_map` (a task with a map takes labels in forward). All results live in ONE persistent buffer per (device, T),
+    allocated on the first eager call (a capture cannot allocate it: run an eager step first, GraphedStep's warm-up does) and refreshed by
+    every call or replay. Labels outside [0, V) are ignored; a task without a valid label adds 0 to the loss (torch: nan); among equal
+    logits the lower word wins."""
+    NAMES = {3: ("lam", "ttm", "asd"), 6: ("pnr", "oscc", "ac_verb", "ac_noun", "lta_verb", "lta_noun")}
+
+    def __init__(self, ratios, names=None, word_labels=None, want_pred: bool = False):
+        super().__init__()
+        self.ratios = tuple(float(r) for r in ratios)
+        T = len(self.ratios)
+        if not 1 <= T <= F_egx.SEQ_CE_MAX_TASKS:
+            raise ValueError(f"TranslationCriterion: {T} ratios (needs 1 to {F_egx.SEQ_CE_MAX_TASKS} tasks)")
+        self.names = tuple(names) if names is not None else self.NAMES.get(T, tuple(f"task{t}" for t in range(T)))
+        if len(self.names) != T or len(set(self.names)) != T:
+            raise ValueError(f"TranslationCriterion: names={self.names} (needs {T} distinct names)")
+        word_labels = list(word_labels) if word_labels is not None else [None] * T
+        if len(word_labels) != T:
+            raise ValueError(f"TranslationCriterion: {len(word_labels)} word_labels for {T} tasks")
+        self._maps = [None if m is None else torch.as_tensor(m).to(dtype=torch.int32, device="cpu").contiguous() for m in word_labels]
+        self._maps_dev: Dict[tuple, list] = {}
+        self.want_pred = bool(want_pred)
+        self._pred = None
+
+    def _allocate(self, device, T: int) -> dict:
+        """loss | loss_terms (T) | n_valid | token_correct | seq_correct | scored | invalid | correct | correct_restricted (T each) as views of
+        one buffer of 4-byte words (`flat`)."""
+        flat = torch.zeros(1 + 8 * T, dtype=torch.int32, device=device)
+        return {"flat": flat, "T": T, **F_egx.sequence_ce_views(flat, T)}
+
+    def _device_maps(self, device) -> list:
+        device = torch.device(device)
+        key = (device.type, device.index)
+        m = self._maps_dev.get(key)
+        if m is None:
+            if self._capturing(device) and any(x is not None for x in self._maps):
+                raise RuntimeError(f"{type(self).__name__}: run one eager step at this problem size before capturing it in a graph")
+            m = self._maps_dev[key] = [None if x is None else x.to(device) for x in self._maps]
+        return m
+
+    def forward(self, logits_list, targets_list, labels_list=None) -> torch.Tensor:
+        """-> loss. logits_list: the tasks' (B_t, V, sy_t) logits; targets_list: their int64 (B_t, sy_t) targets (target[:, 1:] views are
+        read in place); labels_list: per task the int64 original labels ((B_t, sy_t), < 0 = not scored, or (B_t,) = position 0) or None -
+        None also for the whole list (a training step: no metric)."""
+        logits_list = list(logits_list)
+        T = len(self.ratios)
+        if len(logits_list) != T:
+            raise ValueError(f"TranslationCriterion: {len(logits_list)} logits for {T} tasks")
+        dev = logits_list[0].device
+        b = self._result_buffers(dev, T)
+        maps = self._device_maps(dev)
+        labels_list = list(labels_list) if labels_list is not None else [None] * T
+        maps = [m if lab is not None else None for m, lab in zip(maps, labels_list)]       # a task without labels in this call: no metric
+        if any(lab is not None and m is None for m, lab in zip(maps, labels_list)):
+            raise ValueError("TranslationCriterion: labels for a task that was built without word_labels")
+        loss, stats = F_egx.sequence_cross_entropy(logits_list, targets_list, self.ratios, maps, labels_list, out=b, want_pred=self.want_pred)
+        b["rows"] = tuple(int(lg.shape[0]) for lg in logits_list)
+        self._pred = stats["pred"]
+        self._last = b
+        return loss
+
+    def stats(self) -> dict:
+        """Device tensors of the most recent call (or replay): `loss`, `loss_terms` and the seven (T,) int32 counts of
+        functional.sequence_cross_entropy, plus `pred` (with want_pred). Reading them does not synchronise."""
+        b = self._latest()
+        return {**{k: b[k] for k in ("loss",) + F_egx.SEQ_CE_STATS}, "pred": self._pred}
+
+    def host_result(self) -> dict:
+        """The results of the most recent call (or replay) as host values, from ONE device-to-host copy of `flat` (it synchronises): `loss`
+        (float), `loss_terms` (T,) float32 and the seven (T,) int32 counts as numpy arrays."""
+        b = self._latest()
+        T = b["T"]
+        host = b["flat"].cpu().numpy()
+        res = {"loss": float(host[0:1].view("float32")[0]), "loss_terms": host[1:1 + T].view("float32").copy()}
+        for i, name in enumerate(F_egx.SEQ_CE_STATS[1:], start=1):
+            res[name] = host[1 + i * T:1 + (i + 1) * T].copy()
+        return res
+
+    def step_result(self, prefix: str = "train") -> Dict[str, float]:
+        """The reference's logged values of the most recent call (or replay), from ONE device-to-host copy (it synchronises: for logging):
+        f"{prefix}_loss_{name}" per task and f"{prefix}_loss" (train_loss_lam, val_loss_ac_verb, ...); f"{prefix}_{name}_token_acc" =
+        token_correct / n_valid and f"{prefix}_{name}_seq_acc" = seq_correct / B_t; and for a task with word_labels
+        f"{prefix}_{name}_acc" = correct / scored, f"{prefix}_{name}_err" = invalid / scored, f"{prefix}_{name}_acc_restricted" =
+        correct_restricted / scored. An accuracy is nan where nothing was scored (or valid). Across ranks: all-reduce the counts first."""
+        b = self._latest()
+        h = self.host_result()
+
+        def ratio(num, den):
+            return float(num) / float(den) if den > 0 else float("nan")
+
+        res: Dict[str, float] = {}
+        for t, name in enumerate(self.names):
+            res[f"{prefix}_loss_{name}"] = float(h["loss_terms"][t])
+            res[f"{prefix}_{name}_token_acc"] = ratio(h["token_correct"][t], h["n_valid"][t])
+            res[f"{prefix}_{name}_seq_acc"] = ratio(h["seq_correct"][t], b.get("rows", (0,) * len(self.names))[t])
+            if self._maps[t] is not None:
+                n = h["scored"][t]
+                res[f"{prefix}_{name}_acc"] = ratio(h["correct"][t], n)
+                res[f"{prefix}_{name}_err"] = ratio(h["invalid"][t], n)
+                res[f"{prefix}_{name}_acc_restricted"] = ratio(h["correct_restricted"][t], n)
+        res[f"{prefix}_loss"] = h["loss"]
+        return res
 
 
 class LRSchedule:

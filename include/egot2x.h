@@ -682,6 +682,61 @@ int egx_keyframe_criterion(const float* logits, int ld, int B, int T, const int*
                            const int64_t* label, const int64_t* state_change, const double* fps, const int64_t* clip_start,
                            const int64_t* clip_end, const int64_t* pnr_frame, float* loss, float* loss_rows, float* d_logits,
                            int* pred, int* label_frame, int* counts, double* dist, double* dist_sum, void* scratch, void* stream);
+/* ---- ABI v21 additions (new symbols only, as v19 and v20: EGX_ABI_VERSION stays 18): the criterion and the metrics of an EgoT2-g
+ * multi-task step in one launch ------------------------------------------------------------------------------------------------------
+ * Unified3TaskTranslation.training_step (HHI/tasks/multitask/video_tasktranslation.py:39-66; accuracy :101-102) and
+ * Unified6TaskTranslation.training_step / validation_step (HOI/tasks/multitask/video_task.py:537-577, :683-736):
+ * loss = sum_t ratio_t * nn.CrossEntropyLoss()(logits_t (B, |V|, sy), target_t[:, 1:]) over the 3 (6) tasks of one vocabulary, every term
+ * read with .item(); the validation step runs a second predict() forward per task for an argmax, and ARMetric / LTAMetric
+ * (HOI/evaluation/lta/lta_metrics.py:164-211, 229-292), PNRMetric / OSCCMetric (HOI/evaluation/pnr/metrics.py:139-257) map it from the
+ * vocabulary word to the task's original label in Python loops with .item() per clip. Here, for T tasks (1 .. 8; `tasks` is a HOST array,
+ * copied into the launch) that share one vocabulary of V words (2 .. 2048):
+ *   logits   fp32, element (b, s, c) at logits + b * stride_b + s * stride_s + c: the class axis is contiguous, the strides are in floats
+ *            and rows need NO alignment. The (sy, B, V) decoder output is read in place through the (B, V, sy) view the models return
+ *            (stride_b = V, stride_s = B * V), and equally a contiguous (B, sy, V) tensor. B >= 1, 1 <= sy <= 64, B * sy <= 2^22.
+ *   target   int64, element (b, s) at target + b * target_stride_b + s * target_stride_s, so target[:, 1:] is read in place. A label
+ *            outside [0, V) - the default ignore index -100 included - contributes no loss, no count and no gradient.
+ *   ratio    the task's weight in the loss; may be 0 (the gradient is then exactly zero).
+ *   d_logits optional, with the strides of logits (rows must not overlap: each stride >= V); EVERY row (b, s) is written:
+ *            ratio / n_valid_t * (softmax - onehot) at a valid position, zeros at an ignored one.
+ *   word_label  optional DEVICE int32[V]: the original label of a vocabulary word, or -1; goes together with
+ *   labels   int64, element (b, s) at labels + b * labels_stride_b + s * labels_stride_s: the original label of the position, < 0 = the
+ *            position is not scored.
+ *   pred     optional int32 (B, sy, 2), contiguous (needs word_label): word_label[a] and word_label[r] of every position (-1 for r
+ *            when no word is mapped), so the host can build PNRMetric.dist and the per-clip lists.
+ * `result`: 1 + 8 T words of 4 bytes, every one written by every call:
+ *   [0] loss = sum_t ratio_t * loss_terms[t], added for t = 0, 1, ... (fp32)
+ *   loss_terms[T] fp32 = (sum of nll over the valid positions of task t) / n_valid[t]: nn.CrossEntropyLoss() on (B, V, sy) against (B, sy)
+ *   n_valid[T], token_correct[T], seq_correct[T], scored[T], invalid[T], correct[T], correct_restricted[T]   (int32), where
+ *   a = argmax over all V words, r = argmax over the words with word_label >= 0; among equal logits the lower index wins (the rank rule
+ *   of egx_segmented_ce); token_correct = valid positions with a == target; seq_correct = rows b with at least one valid position and
+ *   every valid position correct; over the scored positions invalid += word_label[a] < 0, correct += word_label[a] == label,
+ *   correct_restricted += word_label[r] == label.
+ * ARMetric / LTAMetric: (v_cnt, v_err, v_correct) = (scored, invalid, correct) of the verb task scored at position 0, nouns likewise;
+ * OSCCMetric: (error, correct) = (invalid, correct_restricted) under {False: 0, True: 1}; PNRMetric.err = invalid under {'0'..'15': 0..15};
+ * the HHI accuracy = correct_restricted under {'0': 0, '1': 1}. With the causal mask the position-0 logits of the teacher-forced forward
+ * are those of predict(), so in eval mode the forward that gives the loss also gives the metrics.
+ * One deliberate difference from torch: a task WITHOUT a valid label adds 0 to the loss and has zero gradient, where nn.CrossEntropyLoss
+ * gives nan (0 / 0), as in egx_segmented_ce. The softmax is max-subtracted. One launch on `stream`: a wave per target row b walking its sy
+ * positions; the rows of a task are cut into at most 256 chunks, a workgroup of four waves each. Every sum runs in a fixed order
+ * (per-workgroup partials in scratch, added by the last workgroup to arrive): the same bits on every run, no float atomics.
+ * `scratch`: egx_sequence_ce_scratch() bytes (one size for every T and shape), ZERO before the first use; it begins with nine 64-byte
+ * arrival counters (the launch's and one per task, laid out for 8 tasks always) that every launch leaves zero, so one buffer serves
+ * launches of every T and shape. Refused on the host, before any device work, with a message that names the limit: null tasks, result,
+ * scratch, logits or target; T, V, B, sy or B * sy out of range; a negative stride; d_logits rows that overlap; labels without word_label
+ * or the reverse; pred without word_label. */
+typedef struct egx_seq_task {
+    const float* logits; long long stride_b, stride_s;
+    int B, sy;
+    const int64_t* target; long long target_stride_b, target_stride_s;
+    float ratio;
+    float* d_logits;
+    const int* word_label;
+    const int64_t* labels; long long labels_stride_b, labels_stride_s;
+    int* pred;
+} egx_seq_task;
+size_t egx_sequence_ce_scratch(void);
+int egx_sequence_ce(const egx_seq_task* tasks, int T, int V, void* result, void* scratch, void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
