@@ -233,6 +233,10 @@ SIGNATURES = {
     # ABI v21 additions: the EgoT2-g multi-task sequence criterion and metrics in one launch (tasks is a host array of egx_seq_task)
     "egx_sequence_ce_scratch": (C.c_size_t, []),
     "egx_sequence_ce": (C.c_int, [C.POINTER(SeqTask), C.c_int, C.c_int, _fp, _fp, _fp]),
+    # ABI v22 additions: the TTM / LAM validation accumulator (merged per-row scores) and its metric (AP of both classes, mAP, counts)
+    "egx_segment_ap_scratch": (C.c_size_t, [C.c_int]),
+    "egx_segment_scores_update": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "egx_segment_ap": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

@@ -861,6 +861,17 @@ int egx_sequence_ce(const egx_seq_task* tasks, int T, int V, void* result, void*
     return sequence_ce(tasks ? k : nullptr, T, V, (int*)result, scratch, (hipStream_t)stream);
 }
 
+// ABI v22 additions: the TTM / LAM validation accumulator and metric (segment_ap.hip); every argument is checked on the host before any
+// device work
+size_t egx_segment_ap_scratch(int capacity) { return segment_ap_scratch_bytes(capacity); }
+int egx_segment_scores_update(const float* logits, int ld, int B, const int64_t* slots, int slot0, const int64_t* labels, int capacity,
+                              void* scratch, void* stream) {
+    return segment_scores_update(logits, ld, B, slots, slot0, labels, capacity, scratch, (hipStream_t)stream);
+}
+int egx_segment_ap(int N, int capacity, void* scratch, float* score, int* order1, int* order0, void* result, void* stream) {
+    return segment_ap(N, capacity, scratch, score, order1, order0, result, (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

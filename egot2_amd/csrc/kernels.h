@@ -169,6 +169,15 @@ struct SeqCeTask {
 size_t sequence_ce_scratch_bytes();
 int sequence_ce(const SeqCeTask* tasks, int T, int V, int* result, void* scratch, hipStream_t st);
 
+// segment_ap.hip: the TTM / LAM validation epoch (merged per-row scores, a stable radix sort, both classes' average precision, confusion
+// counts). One scratch holds the persistent per-row state (zero = empty) and the sort / scan work area, carved for `capacity` rows.
+constexpr int SEG_AP_TILE = 4096, SEG_AP_MAX_ROWS = 1 << 24;
+constexpr size_t SEGMENT_AP_RESULT_BYTES = 7 * 8 + 4 * 8;          // int64 n, n_pos, TP, FN, FP, TN, n_nonfinite | fp64 AP0, AP1, mAP, acc
+size_t segment_ap_scratch_bytes(int capacity);
+int segment_scores_update(const float* logits, int ld, int B, const int64_t* slots, int slot0, const int64_t* labels, int capacity,
+                          void* scratch, hipStream_t st);
+int segment_ap(int N, int capacity, void* scratch, float* score, int* order1, int* order0, void* result, hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

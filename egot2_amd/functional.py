@@ -2376,6 +2376,85 @@ def sequence_cross_entropy(logits, targets, ratios, word_labels=None, labels=Non
     return loss, stats
 
 
+# ---- the TTM / LAM validation epoch: merged per-row scores, both classes' average precision, confusion counts (csrc/segment_ap.hip) ----
+SEG_AP_TILE, SEG_AP_MAX_ROWS = 4096, 1 << 24
+SEG_AP_COUNTS = ("n", "n_pos", "TP", "FN", "FP", "TN", "n_nonfinite")
+SEG_AP_VALUES = ("AP0", "AP1", "mAP", "acc")
+
+
+def segment_ap_views(flat: torch.Tensor) -> dict:
+    """The 11 result words of egx_segment_ap (`flat`: int64 (11,)) as named 0-d views: the seven int64 counts, then AP0, AP1, mAP, acc fp64."""
+    res = {name: flat[i] for i, name in enumerate(SEG_AP_COUNTS)}
+    values = flat[len(SEG_AP_COUNTS):].view(torch.float64)
+    res.update({name: values[i] for i, name in enumerate(SEG_AP_VALUES)})
+    return res
+
+
+def _seg_ap_capacity(who: str, capacity: int) -> int:
+    capacity = int(capacity)
+    if not 1 <= capacity <= SEG_AP_MAX_ROWS:
+        raise ValueError(f"{who}: capacity={capacity} (needs 1 <= capacity <= {SEG_AP_MAX_ROWS} rows)")
+    return capacity
+
+
+def segment_ap_state(capacity: int, device) -> torch.Tensor:
+    """The zeroed accumulator + work area of `capacity` rows (egx_segment_ap_scratch bytes). Zero it again to empty it."""
+    capacity = _seg_ap_capacity("segment_ap_state", capacity)
+    nbytes = _lib.load().egx_segment_ap_scratch(capacity)
+    if nbytes == 0:
+        check(1)
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def segment_scores_update(state: torch.Tensor, capacity: int, logits, labels, slots=None, slot0: int = 0) -> None:
+    """Fold a batch of window logits into the per-row sums of `state` (PostProcessor.update / _merge_output, HHI/utils/ttm/utils.py:57-80;
+    HHI/utils/lam/utils.py:34-47) in one launch; nothing synchronises.
+
+    logits: fp32 (B, 2) on the GPU, read in place (ld = its row stride); labels: int64 (B,), a row takes its first window's; slots: int64
+    (B,) device tensor of rows, non-decreasing within the call (a row may continue from an earlier call; a slot outside [0, capacity) is
+    dropped), or None: window i is row slot0 + i."""
+    lib = _lib.load()
+    _dev_f32(logits[:0], "logits")
+    if logits.dim() != 2 or logits.shape[1] != 2:
+        raise ValueError(f"segment_scores_update expects (B, 2) logits, got {tuple(logits.shape)}")
+    B = logits.shape[0]
+    if B < 1:
+        raise ValueError("segment_scores_update: empty batch")
+    x = logits if logits.stride(1) == 1 and (B == 1 or logits.stride(0) >= 2) else logits.contiguous()
+    ld = x.stride(0) if B > 1 else 2
+    dev = x.device
+    if labels.dtype != torch.int64 or labels.numel() != B or labels.device != dev:
+        raise ValueError(f"segment_scores_update: labels must be an int64 tensor of {B} elements on the logits' device")
+    lab = labels.reshape(B).contiguous()
+    sl = None
+    if slots is not None:
+        if slots.dtype != torch.int64 or slots.numel() != B or slots.device != dev:
+            raise ValueError(f"segment_scores_update: slots must be an int64 tensor of {B} elements on the logits' device")
+        sl = slots.reshape(B).contiguous()
+    check(lib.egx_segment_scores_update(x.data_ptr(), ld, B, ptr(sl), int(slot0), ptr(lab), int(capacity), ptr(state), _stream()))
+
+
+def segment_ap(state: torch.Tensor, capacity: int, n: int, out=None) -> dict:
+    """-> the metric of rows 0 .. n - 1 of `state` as device tensors (PostProcessor.get_mAP -> run_evaluation, HHI/utils/ttm/metrics.py:
+    26-71, 138-199, 232-247); nothing synchronises. `score` (n) fp32 = softmax(mean of the row's window logits)[1]; `order1` / `order0` (n)
+    int32: the rows by score descending / ascending, the lower row first among equal scores; the int64 counts `n`, `n_pos`, `TP`, `FN`, `FP`,
+    `TN` (at score >= 0.5), `n_nonfinite` and fp64 `AP0`, `AP1`, `mAP`, `acc` as 0-d views of `flat` (int64 (11,)). A class without a
+    positive row, or any non-finite score, gives nan. `out`: preallocated `flat`, `score`, `order1`, `order0` (train.SegmentAPValidation)."""
+    lib = _lib.load()
+    n, capacity = int(n), int(capacity)
+    if not state.is_cuda:
+        raise _lib.EgxError(f"state is on {state.device}: the metric runs only on the GPU through libegot2x.so (no CPU fallback)")
+    dev = state.device
+    out = out or {}
+    rows = max(n, 1)
+    flat = _out_tensor(out, "flat", (len(SEG_AP_COUNTS) + len(SEG_AP_VALUES),), torch.int64, dev)
+    score = _out_tensor(out, "score", (rows,), torch.float32, dev)
+    order1 = _out_tensor(out, "order1", (rows,), torch.int32, dev)
+    order0 = _out_tensor(out, "order0", (rows,), torch.int32, dev)
+    check(lib.egx_segment_ap(n, capacity, ptr(state), ptr(score), ptr(order1), ptr(order0), ptr(flat), _stream()))
+    return {"flat": flat, "score": score[:n], "order1": order1[:n], "order0": order0[:n], **segment_ap_views(flat)}
+
+
 # ---- the LTA validation step: K sampled futures per clip and head + prefix edit distances in one launch (csrc/lta_val.hip) -----------
 LTA_VAL_MAX_K, LTA_VAL_MAX_Z = 8, 64
 _LTA_VAL_CALLS = [0]

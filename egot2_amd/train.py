@@ -19,6 +19,9 @@ keyframe_distance and keyframe_accuracy of HOI/evaluation/pnr/metrics.py:23-80; 
 `TranslationCriterion` is the criterion of the EgoT2-g multi-task steps (HHI/tasks/multitask/video_tasktranslation.py:39-66,
 HOI/tasks/multitask/video_task.py:537-577, :683-736: 3 or 6 cross-entropies on (B, |V|, sy) logits times their ratios, and the counts behind
 ARMetric / LTAMetric / PNRMetric / OSCCMetric) as one launch; `word_label_map` builds its vocabulary maps.
+`SegmentAPValidation` is the validation epoch of the TTM and LAM tasks (HHI/tasks/ttm/video_task_2loader.py:38-50: PostProcessor.update /
+save / get_mAP, HHI/utils/ttm/utils.py:46-114, and run_evaluation, HHI/utils/ttm/metrics.py:26-247 - the checkpoint metric val_mAP) as a
+device-resident accumulator: reset / update per batch / step_result, with one 88-byte device-to-host copy per epoch.
 """
 from __future__ import annotations
 
@@ -507,6 +510,125 @@ class TranslationCriterion(_DeviceCriterion):
                 res[f"{prefix}_{name}_err"] = ratio(h["invalid"][t], n)
                 res[f"{prefix}_{name}_acc_restricted"] = ratio(h["correct_restricted"][t], n)
         res[f"{prefix}_loss"] = h["loss"]
+        return res
+
+
+class SegmentAPValidation(_DeviceCriterion):
+    """The validation epoch of the TTM and LAM tasks after the model (HHI/tasks/ttm/video_task_2loader.py:19,46-50): the reference's
+    PostProcessor (HHI/utils/ttm/utils.py:46-114, HHI/utils/lam/utils.py:24-81)
+
+        postprocess.update(outputs, targets)          # per batch: a Python list of window outputs, one .item() per segment
+        postprocess.save(); mAP, acc = postprocess.get_mAP()      # two CSV files per rank, `cat` in a subshell, pandas merge + sort, two
+                                                                  # Python loops over every row (HHI/utils/ttm/metrics.py:26-71, 138-199)
+
+    as a device-resident accumulator: `reset()` at the start of the epoch, `update(logits, labels, slots)` per batch (one launch, nothing
+    synchronises), `step_result()` at its end - the metric's launches (functional.segment_ap) and ONE device-to-host copy of 88 bytes.
+
+    A row is a segment (TTM) or a frame (LAM); score = softmax(mean of the row's window logits)[1], label = the label of its first window.
+    `update(logits (B, 2), labels (B,), slots)`: slots=None appends one row per input row (LAM). Otherwise `slots` names the row of every
+    window, non-decreasing within the call (the windows of a segment are adjacent; a segment may continue in the next call): a host
+    sequence or CPU tensor - checked here, the row count follows from it - or a device tensor together with `rows=`, the number of rows
+    it reaches (the metric covers the rows below the largest such count; a slot outside [0, capacity) is dropped on the device).
+    `merge=False` (LAM) refuses slots.
+
+    The row count is host state, so update and compute cannot be captured in a graph, and more than `capacity` rows raise here. Among equal
+    scores the lower row ranks first in both classes' passes (the reference's order of ties is unspecified), and rows are never
+    deduplicated (the reference's uid is start:end, which merges segments of different videos with equal frame ranges). Across ranks:
+    all-gather the logits, labels and slots (or the rows' sums) before update. Buffers are allocated per device on the first eager call."""
+
+    def __init__(self, capacity: int, merge: bool = True):
+        super().__init__()
+        self.capacity = F_egx._seg_ap_capacity("SegmentAPValidation", capacity)
+        self.merge = bool(merge)
+        self._rows = 0                  # the row cursor: rows 0 .. _rows - 1 hold (or are reserved for) a score
+        self._device: Optional[torch.device] = None
+        self._computed = False
+
+    def _allocate(self, device) -> dict:
+        """The accumulator + work area, the 11 result words (`flat`) and the per-row outputs."""
+        cap = self.capacity
+        if device.type != "cuda":       # host stand-in (the step_result arithmetic): no accumulator
+            state = torch.zeros(0, dtype=torch.uint8)
+        else:
+            state = F_egx.segment_ap_state(cap, device)
+        flat = torch.zeros(len(F_egx.SEG_AP_COUNTS) + len(F_egx.SEG_AP_VALUES), dtype=torch.int64, device=device)
+        return {"state": state, "flat": flat, **F_egx.segment_ap_views(flat),
+                "score": torch.zeros(cap, dtype=torch.float32, device=device),
+                "order1": torch.zeros(cap, dtype=torch.int32, device=device),
+                "order0": torch.zeros(cap, dtype=torch.int32, device=device)}
+
+    def _refuse_capture(self, device, what: str):
+        if self._capturing(device):
+            raise RuntimeError(f"SegmentAPValidation.{what} cannot be captured in a graph: the row cursor is host state (a replay would "
+                               "fold the batch into the same rows again); call it eagerly")
+
+    def reset(self) -> "SegmentAPValidation":
+        """Empty the accumulator (one memset on the stream) and rewind the row cursor."""
+        if self._device is not None:
+            self._refuse_capture(self._device, "reset")
+            self._result_buffers(self._device)["state"].zero_()
+        self._rows, self._computed, self._last = 0, False, None
+        return self
+
+    def update(self, logits: torch.Tensor, labels: torch.Tensor, slots=None, rows: Optional[int] = None) -> None:
+        dev = logits.device
+        self._refuse_capture(dev, "update")
+        B = int(logits.shape[0])
+        if slots is not None and not self.merge:
+            raise ValueError("SegmentAPValidation(merge=False): every input row is its own row, slots are not taken")
+        if self._device is not None and dev != self._device:
+            raise ValueError(f"SegmentAPValidation: logits on {dev}, the accumulator is on {self._device}")
+        if slots is None:
+            reach = self._rows + B
+            slot_t, slot0 = None, self._rows
+        elif isinstance(slots, torch.Tensor) and slots.is_cuda:
+            if rows is None:
+                raise ValueError("SegmentAPValidation.update: device slots need rows= (the number of rows they reach): the host cannot "
+                                 "read them without a synchronisation")
+            reach, slot_t, slot0 = max(self._rows, int(rows)), slots, 0
+        else:
+            host = torch.as_tensor(slots, dtype=torch.int64).reshape(-1)
+            if host.numel() != B:
+                raise ValueError(f"SegmentAPValidation.update: {host.numel()} slots for {B} windows")
+            if B and (int(host[0]) < 0 or bool((host[1:] < host[:-1]).any())):
+                raise ValueError("SegmentAPValidation.update: slots must be >= 0 and non-decreasing within a call")
+            reach, slot0 = max(self._rows, int(host[-1]) + 1 if B else 0), 0
+            slot_t = host
+        if reach > self.capacity:
+            raise ValueError(f"SegmentAPValidation.update: {reach} rows exceed capacity={self.capacity}")
+        b = self._result_buffers(dev)
+        if slot_t is not None and not slot_t.is_cuda:
+            slot_t = slot_t.to(dev)
+        F_egx.segment_scores_update(b["state"], self.capacity, logits, labels.to(device=dev, dtype=torch.int64), slot_t, slot0)
+        self._device, self._rows, self._computed = dev, reach, False
+
+    def compute(self) -> dict:
+        """-> device tensors of the rows so far: `score`, `order1`, `order0` (n), the int64 counts `n`, `n_pos`, `TP`, `FN`, `FP`, `TN`,
+        `n_nonfinite` and fp64 `AP0`, `AP1`, `mAP`, `acc`. Nothing synchronises."""
+        if self._device is None or self._rows == 0:
+            raise RuntimeError("SegmentAPValidation: no update has run yet")
+        self._refuse_capture(self._device, "compute")
+        b = self._result_buffers(self._device)
+        res = F_egx.segment_ap(b["state"], self.capacity, self._rows, out=b)
+        self._last = {"buffers": b, "result": {k: v for k, v in res.items() if k != "flat"}}
+        self._computed = True
+        return dict(self._last["result"])
+
+    def stats(self) -> dict:
+        """The device tensors of the most recent compute()."""
+        return dict(self._latest()["result"])
+
+    def step_result(self, prefix: str = "val") -> Dict[str, float]:
+        """The epoch's logged values from ONE device-to-host copy (it synchronises): f"{prefix}_mAP" (the checkpoint metric),
+        f"{prefix}_acc", f"{prefix}_AP0", f"{prefix}_AP1" and the counts f"{prefix}_TP", _FN, _FP, _TN, _n, _n_pos, _n_nonfinite.
+        Runs compute() first when rows arrived since the last one."""
+        if not self._computed and self._device is not None and self._rows > 0:
+            self.compute()
+        host = self._latest()["buffers"]["flat"].cpu().numpy()
+        nc = len(F_egx.SEG_AP_COUNTS)
+        res: Dict[str, float] = {f"{prefix}_{name}": int(host[i]) for i, name in enumerate(F_egx.SEG_AP_COUNTS)}
+        values = host[nc:].view("float64")
+        res.update({f"{prefix}_{name}": float(values[i]) for i, name in enumerate(F_egx.SEG_AP_VALUES)})
         return res
 
 

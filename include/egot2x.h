@@ -737,6 +737,51 @@ typedef struct egx_seq_task {
 } egx_seq_task;
 size_t egx_sequence_ce_scratch(void);
 int egx_sequence_ce(const egx_seq_task* tasks, int T, int V, void* result, void* scratch, void* stream);
+/* ---- ABI v22 additions (new symbols only, as v19 to v21: EGX_ABI_VERSION stays 18): the TTM / LAM validation epoch on the device -
+ * a per-row score accumulator and the checkpoint metric val_mAP (HHI/tasks/ttm/video_task_2loader.py:19,46-50) -------------------------
+ * Rows are segments (TTM) or frames (LAM). `scratch`: egx_segment_ap_scratch(capacity) bytes (0: capacity outside 1 .. 2^24, see
+ * egx_last_error), 36 bytes per row of capacity plus at most 9 MiB of tile tables; it begins with the persistent per-row state (sum of the two logits,
+ * window count, label) followed by the sort's work area. ZERO it to empty the accumulator; the same `capacity` goes into every call.
+ *
+ * egx_segment_scores_update replaces PostProcessor.update / _merge_output (HHI/utils/ttm/utils.py:57-80) and the LAM
+ * PostProcessor.update (HHI/utils/lam/utils.py:34-47): the Python list of per-window outputs, torch.cat and one .item() per segment.
+ *   logits   fp32, B windows of row stride `ld` >= 2 floats; columns 0 and 1 are the class logits.
+ *   slots    int64 (B), DEVICE: the row of every window, NON-DECREASING within a call (the windows of a row are adjacent, as the
+ *            reference's loader yields them); a row may continue from an earlier call. NULL: window i is row slot0 + i (LAM: one row per
+ *            input row; slot0 + B <= capacity is checked on the host). A slot outside [0, capacity) is dropped.
+ *   labels   int64 (B): a row takes the label of its FIRST window (utils.py:78); compared == 1, as label_groundtruth == 1 is.
+ * One launch, a thread per window: the first window of a run of equal slots adds the run's logits, in window order, onto the row's stored
+ * sum. The sum is one left fold per row and the stored score is bit-identical however a row's windows are split across calls; no atomics.
+ *
+ * egx_segment_ap replaces PostProcessor.save / get_mAP -> run_evaluation (utils.py:82-114; HHI/utils/ttm/metrics.py:26-71, 138-199,
+ * 232-247): two CSV files per rank joined by `cat` in a subshell, a pandas merge and sort, and two Python loops over every row. Over rows
+ * 0 .. N - 1 of the accumulator (1 <= N <= capacity):
+ *   score    (N) fp32 = softmax(sum / count)[1], the mean and the max-subtracted softmax in fp32 as the reference computes them. A row
+ *            whose score is not finite (a non-finite logit, or no window at all) holds the one NaN 0x7fc00000.
+ *   order1   (N) int32: the rows by score descending; order0: by score ascending (the class-0 pass on 1 - score). Among equal scores the
+ *            LOWER ROW COMES FIRST in both (the reference's pandas quicksort leaves the order of ties unspecified; and two scores that
+ *            differ by less than 2^-53 of 1 tie in its 1 - score, where this orders them by their fp32 values). The NaN ranks above every
+ *            number: first in order1, last in order0.
+ *   result   88 bytes, every one written by every call: int64 n, n_pos, TP, FN, FP, TN, n_nonfinite, then fp64 AP0, AP1, mAP, acc.
+ *            TP / FN / FP / TN at score >= 0.5 (metrics.py:232-238: exactly 0.5 is predicted positive; a NaN negative); acc = (TP + TN) / n.
+ *            AP of a class (metrics.py:61-71, 138-166): tp_k = cumsum(label) in the class's order, precision tp_k / k, made non-increasing
+ *            from the right, AP = sum over the positive rows of (tp_k / P - (tp_k - 1) / P) * precision_k; class 0 uses 1 - label.
+ *            mAP = (AP0 + AP1) / 2. A class without a positive row has AP = NaN (the reference's 0 / 0), and with n_nonfinite > 0 both
+ *            APs are NaN. Counts are integers; precisions are compared as exact rationals (tp_a k_b against tp_b k_a in 64 bits); the
+ *            terms are fp64, added in a fixed order (per tile of 4096 rows, then the tiles in order): the same bits on every run.
+ * NOT done here: the reference's uid handling (load_csv names fewer columns than the files hold, so its uid is start:end and
+ * drop_duplicates merges segments of different videos with equal frame ranges): rows are the caller's slots and nothing is deduplicated.
+ * Across ranks: all-gather the per-row state first. The test-set JSON writer stays on the host.
+ * Launches on `stream`, none synchronises, their number depends on N only: a memset, the score kernel, then up to N = 4096 ONE workgroup
+ * that runs the stable LSD radix sort (8-bit digits, ranks inside a wave by ballots) for both classes and both AP passes; beyond it
+ * 3 launches per sort pass (tile histograms, a scan per digit in tile order, scatter), 4 passes per class - class 0 runs the passes again
+ * on the plain digit where class 1 uses the complemented one, which keeps the tie rule without a tie-group pass - and 6 for the AP.
+ * Refused on the host, before any device work, with a message that names the limit: a null pointer; capacity or N outside
+ * 1 .. 2^24 (N also above capacity); ld < 2; B < 1; without slots, slot0 < 0 or slot0 + B > capacity. */
+size_t egx_segment_ap_scratch(int capacity);
+int egx_segment_scores_update(const float* logits, int ld, int B, const int64_t* slots, int slot0, const int64_t* labels, int capacity,
+                              void* scratch, void* stream);
+int egx_segment_ap(int N, int capacity, void* scratch, float* score, int* order1, int* order0, void* result, void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
