@@ -237,6 +237,11 @@ SIGNATURES = {
     "egx_segment_ap_scratch": (C.c_size_t, [C.c_int]),
     "egx_segment_scores_update": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp]),
     "egx_segment_ap": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # ABI v23 additions: the multi-view ensemble accumulator of the action-recognition test epoch and its top-k errors
+    "egx_view_ensemble_state": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "egx_view_ensemble_update": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _fp, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, _fp, _fp]),
+    "egx_view_ensemble_topk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "egx_pool_head_fwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, C.c_int,
                                     _fp, _fp, _fp]),
     "egx_pool_head_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, C.c_int,

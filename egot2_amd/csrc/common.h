@@ -109,6 +109,9 @@ __device__ __forceinline__ WaveBest wave_argmax(float v, int i) {
     b.v = v; b.i = i;
     return b;
 }
+// the top-k rank of label y is the number of classes c that outrank it: #{c : z_c > z_y} + #{c < y : z_c == z_y} (among equal values the
+// lower class index ranks first)
+__device__ __forceinline__ int outranks(float x, float zy, int c, int y) { return (x > zy || (x == zy && c < y)) ? 1 : 0; }
 // the sum over the 4 adjacent lanes of a quad
 __device__ __forceinline__ float quad_sum(float v) {
     v += __shfl_xor(v, 1, 64);

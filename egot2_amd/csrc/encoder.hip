@@ -872,6 +872,18 @@ int egx_segment_ap(int N, int capacity, void* scratch, float* score, int* order1
     return segment_ap(N, capacity, scratch, score, order1, order0, result, (hipStream_t)stream);
 }
 
+// ABI v23 additions: the multi-view ensemble of the action-recognition test epoch and its top-k errors (view_ensemble.hip); every argument
+// is checked on the host before any device work
+size_t egx_view_ensemble_state(int capacity, int H, const int* C, size_t* offsets) { return view_ensemble_state_bytes(capacity, H, C, offsets); }
+int egx_view_ensemble_update(const float* preds, int ld, int B, int H, const int* col0, const int* C, const int64_t* labels, const void* slots,
+                             int slot_bytes, int slot0, int method, int capacity, void* state, void* stream) {
+    return view_ensemble_update(preds, ld, B, H, col0, C, labels, slots, slot_bytes, slot0, method, capacity, state, (hipStream_t)stream);
+}
+int egx_view_ensemble_topk(int n, int capacity, int H, const int* C, const int* ks, int n_ks, void* state, int* rank, int* pred, void* result,
+                           void* stream) {
+    return view_ensemble_topk(n, capacity, H, C, ks, n_ks, state, rank, pred, (int*)result, (hipStream_t)stream);
+}
+
 // ---- EgoT2-g sequence decoder pieces (decoder.hip) ---------------------------------------------------------------
 static SmallAttnParams small_attn_params(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Sq,
                                          int Sk, int H, int dh, int causal, float p_drop, uint64_t seed, uint32_t site) {

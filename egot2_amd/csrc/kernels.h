@@ -178,6 +178,17 @@ int segment_scores_update(const float* logits, int ld, int B, const int64_t* slo
                           void* scratch, hipStream_t st);
 int segment_ap(int N, int capacity, void* scratch, float* score, int* order1, int* order0, void* result, hipStream_t st);
 
+// view_ensemble.hip: the test epoch of the action-recognition translators (multi-view ensemble per video, top-k errors over the videos).
+// One state holds the header (arrival counter, dropped clips), the per-video labels, view counts and rows, and the count partials; all zero =
+// empty. `offsets` (optional, 3 words): byte offsets of the labels (int64 (capacity, H)), the view counts (int32 (capacity)) and the rows
+// (fp32 (capacity, sum C)).
+constexpr int VIEW_ENS_SUM = 0, VIEW_ENS_MAX = 1, VIEW_ENS_MAX_BATCH = 1 << 16;
+size_t view_ensemble_state_bytes(int capacity, int H, const int* C, size_t* offsets);
+int view_ensemble_update(const float* preds, int ld, int B, int H, const int* col0, const int* C, const int64_t* labels, const void* slots,
+                         int slot_bytes, int slot0, int method, int capacity, void* state, hipStream_t st);
+int view_ensemble_topk(int n, int capacity, int H, const int* C, const int* ks, int n_ks, void* state, int* rank, int* pred, int* result,
+                       hipStream_t st);
+
 // decoder.hip
 struct SmallAttnParams {
     const float* q; const float* k; const float* v;

@@ -34,9 +34,6 @@ struct SegCeParams {
 
 struct SegOut { float nll; int rank; };
 
-// rank of the label: #{c : z_c > z_y} + #{c < y : z_c == z_y} (among equal logits the lower class index ranks first)
-__device__ __forceinline__ int outranks(float x, float zy, int c, int y) { return (x > zy || (x == zy && c < y)) ? 1 : 0; }
-
 // C <= 64 * NR: element c = lane + 64 j lives in register j
 template <int NR>
 __device__ __forceinline__ SegOut seg_regs(const float* __restrict__ seg, float* __restrict__ dseg, int C, int y, float inv, int lane) {

@@ -2455,6 +2455,130 @@ def segment_ap(state: torch.Tensor, capacity: int, n: int, out=None) -> dict:
     return {"flat": flat, "score": score[:n], "order1": order1[:n], "order0": order0[:n], **segment_ap_views(flat)}
 
 
+# ---- the action-recognition test epoch: multi-view ensemble per video, top-k errors over the videos (csrc/view_ensemble.hip) -----------
+VIEW_ENS_METHODS = {"sum": 0, "max": 1}
+VIEW_ENS_MAX_BATCH = 1 << 16
+VIEW_ENS_COUNTS = ("n", "n_dropped", "n_nonfinite")          # then n_invalid (H,) and correct (n_ks, H)
+
+
+def view_ensemble_views(flat: torch.Tensor, H: int, n_ks: int) -> dict:
+    """The result words of egx_view_ensemble_topk (`flat`: int32 (3 + H + n_ks * H,)) as named views: the 0-d counts `n`, `n_dropped`,
+    `n_nonfinite`, then `n_invalid` (H,) and `correct` (n_ks, H)."""
+    nc = len(VIEW_ENS_COUNTS)
+    res = {name: flat[i] for i, name in enumerate(VIEW_ENS_COUNTS)}
+    res["n_invalid"] = flat[nc:nc + H]
+    res["correct"] = flat[nc + H:nc + H + n_ks * H].view(n_ks, H)
+    return res
+
+
+def _view_ens_classes(who: str, classes) -> tuple:
+    classes = tuple(int(c) for c in classes)
+    if not 1 <= len(classes) <= SEG_CE_MAX_HEADS or any(not 1 <= c <= SEG_CE_MAX_CLASSES for c in classes):
+        raise ValueError(f"{who}: classes={classes} (needs 1 to {SEG_CE_MAX_HEADS} heads of 1 to {SEG_CE_MAX_CLASSES} classes)")
+    return classes
+
+
+def _view_ens_layout(who: str, capacity: int, classes):
+    """-> (bytes, (labels, views, rows) byte offsets) of the state of `capacity` videos (egx_view_ensemble_state)."""
+    offs = (C.c_size_t * 3)()
+    nbytes = _lib.load().egx_view_ensemble_state(int(capacity), len(classes), _c_ints(classes), offs)
+    if nbytes == 0:
+        check(1)
+    return nbytes, tuple(offs)
+
+
+def view_ensemble_state(capacity: int, classes, device) -> torch.Tensor:
+    """The zeroed accumulator of `capacity` videos with heads of `classes` classes (egx_view_ensemble_state bytes). Zero it again to empty
+    it: zero rows are the reference's torch.zeros initialisation, for "sum" and for "max"."""
+    classes = _view_ens_classes("view_ensemble_state", classes)
+    nbytes, _ = _view_ens_layout("view_ensemble_state", capacity, classes)
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def view_ensemble_rows(state: torch.Tensor, capacity: int, classes) -> dict:
+    """The per-video state as views of `state`: `rows` fp32 (capacity, sum classes) - the heads side by side -, `labels` int64
+    (capacity, H), `views` int32 (capacity)."""
+    classes = _view_ens_classes("view_ensemble_rows", classes)
+    capacity, H, ld = int(capacity), len(classes), sum(classes)
+    _, (o_lab, o_views, o_rows) = _view_ens_layout("view_ensemble_rows", capacity, classes)
+    return {"rows": state[o_rows:o_rows + 4 * capacity * ld].view(torch.float32).view(capacity, ld),
+            "labels": state[o_lab:o_lab + 8 * capacity * H].view(torch.int64).view(capacity, H),
+            "views": state[o_views:o_views + 4 * capacity].view(torch.int32)}
+
+
+def _clip_heads(preds):
+    """The (B, C_h) heads of a clip batch as the (B, 1, C_h) views _head_stack takes: a head with unit column stride keeps its row
+    stride (so heads that are column windows of one stack are read in place), any other becomes contiguous."""
+    heads = []
+    for p in preds:
+        if p.dim() != 2:
+            raise ValueError(f"view_ensemble_update expects (B, C_h) heads, got {[tuple(q.shape) for q in preds]}")
+        if p.stride(1) != 1 or (p.shape[0] > 1 and p.stride(0) < p.shape[1]):
+            p = p.contiguous()
+        row = p.stride(0) if p.shape[0] > 1 else p.shape[1]
+        heads.append(p.as_strided((p.shape[0], 1, p.shape[1]), (row, row, 1), p.storage_offset()))
+    return heads
+
+
+def view_ensemble_update(state: torch.Tensor, capacity: int, classes, preds, labels, slots=None, slot0: int = 0, method: str = "sum") -> None:
+    """Fold a batch of clip predictions into the per-video rows of `state` (the loop of MultiTaskClassificationTask.test_epoch_end,
+    HOI/tasks/lta/long_term_anticipation.py:116-140) in one launch; nothing synchronises.
+
+    preds: the list of (B, C_h) fp32 heads `forward_features` of the AR translators returns (or one (B, sum C) tensor for one head); heads
+    that are column windows of one stack are read in place, otherwise one torch.cat packs them (_head_stack's policy). labels: int64 (B, H),
+    a video keeps its last clip's. slots: int32 / int64 (B,) device tensor of video slots - in any order, with repeats; a slot outside
+    [0, capacity) is dropped and counted - or None: clip i is video slot0 + i. method "sum": fp32 adds in arrival order from 0; "max":
+    the running maximum from 0 (the reference starts from torch.zeros: an all-negative video ends as zeros)."""
+    lib = _lib.load()
+    classes = _view_ens_classes("view_ensemble_update", classes)
+    if method not in VIEW_ENS_METHODS:
+        raise ValueError(f"view_ensemble_update: method={method!r} (needs 'sum' or 'max')")
+    preds = [preds] if isinstance(preds, torch.Tensor) else list(preds)
+    for h, p in enumerate(preds):
+        _dev_f32(p[:0], f"preds[{h}]")
+    B, _Z, H, dev, widths, addr, ld, col0, _stack = _head_stack("view_ensemble_update", _clip_heads(preds))   # _stack: alive until the launch
+    if tuple(widths) != classes:
+        raise ValueError(f"view_ensemble_update: heads of {tuple(widths)} classes, the accumulator holds {classes}")
+    if B < 1:
+        raise ValueError("view_ensemble_update: empty batch")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B, H) or labels.device != dev:
+        raise ValueError(f"view_ensemble_update: labels must be an int64 tensor of shape (B, H) = {(B, H)} on the predictions' device")
+    lab = labels.contiguous()
+    sl, slot_bytes = None, 0
+    if slots is not None:
+        if slots.dtype not in (torch.int32, torch.int64) or slots.numel() != B or slots.device != dev:
+            raise ValueError(f"view_ensemble_update: slots must be an int32 or int64 tensor of {B} elements on the predictions' device")
+        sl = slots.reshape(B).contiguous()
+        slot_bytes = sl.element_size()
+    check(lib.egx_view_ensemble_update(addr, ld, B, H, _c_ints(col0), _c_ints(classes), ptr(lab), ptr(sl), slot_bytes, int(slot0),
+                                       VIEW_ENS_METHODS[method], int(capacity), ptr(state), _stream()))
+
+
+def view_ensemble_topk(state: torch.Tensor, capacity: int, classes, n: int, ks=(1, 5), out=None) -> dict:
+    """-> the top-k counts of videos 0 .. n - 1 of `state` as device tensors (the four topk_errors calls of test_epoch_end, :142-158;
+    HOI/evaluation/lta/lta_metrics.py:38-84); nothing synchronises. `rank` (n, H) int32: the rank of the video's label in its ensemble row,
+    the lower class first among equal values, a NaN as the greatest value, -1 for a label outside [0, C_h); `pred` (n, H) int32: the
+    class of rank 0; the int32 counts `n`, `n_dropped`, `n_nonfinite`, `n_invalid` (H,), `correct` (len(ks), H) as views of `flat`.
+    top-k error = (1 - correct / n) * 100. `out`: preallocated `flat`, `rank`, `pred` (train.ViewEnsembleTest)."""
+    lib = _lib.load()
+    classes = _view_ens_classes("view_ensemble_topk", classes)
+    ks = tuple(int(k) for k in ks)
+    n, capacity, H = int(n), int(capacity), len(classes)
+    if not state.is_cuda:
+        raise _lib.EgxError(f"state is on {state.device}: the metric runs only on the GPU through libegot2x.so (no CPU fallback)")
+    if not 1 <= len(ks) <= SEG_CE_MAX_KS:
+        raise ValueError(f"view_ensemble_topk takes 1 to {SEG_CE_MAX_KS} values of k, got {len(ks)}")
+    dev = state.device
+    out = out or {}
+    rows = max(n, 1)
+    flat = _out_tensor(out, "flat", (len(VIEW_ENS_COUNTS) + H + len(ks) * H,), torch.int32, dev)
+    rank = _out_tensor(out, "rank", (rows, H), torch.int32, dev)
+    pred = _out_tensor(out, "pred", (rows, H), torch.int32, dev)
+    check(lib.egx_view_ensemble_topk(n, capacity, H, _c_ints(classes), _c_ints(ks), len(ks), ptr(state), ptr(rank), ptr(pred), ptr(flat),
+                                     _stream()))
+    return {"flat": flat, "rank": rank[:n], "pred": pred[:n], **view_ensemble_views(flat, H, len(ks))}
+
+
 # ---- the LTA validation step: K sampled futures per clip and head + prefix edit distances in one launch (csrc/lta_val.hip) -----------
 LTA_VAL_MAX_K, LTA_VAL_MAX_Z = 8, 64
 _LTA_VAL_CALLS = [0]

@@ -22,6 +22,8 @@ ARMetric / LTAMetric / PNRMetric / OSCCMetric) as one launch; `word_label_map` b
 `SegmentAPValidation` is the validation epoch of the TTM and LAM tasks (HHI/tasks/ttm/video_task_2loader.py:38-50: PostProcessor.update /
 save / get_mAP, HHI/utils/ttm/utils.py:46-114, and run_evaluation, HHI/utils/ttm/metrics.py:26-247 - the checkpoint metric val_mAP) as a
 device-resident accumulator: reset / update per batch / step_result, with one 88-byte device-to-host copy per epoch.
+`ViewEnsembleTest` is the test epoch of the action-recognition translators (HOI/tasks/lta/long_term_anticipation.py:86-158: the sum or max of
+a video's clip predictions per clip id, then the top-1 / top-5 errors of verb and noun over the videos) on the same life cycle.
 """
 from __future__ import annotations
 
@@ -629,6 +631,174 @@ class SegmentAPValidation(_DeviceCriterion):
         res: Dict[str, float] = {f"{prefix}_{name}": int(host[i]) for i, name in enumerate(F_egx.SEG_AP_COUNTS)}
         values = host[nc:].view("float64")
         res.update({f"{prefix}_{name}": float(values[i]) for i, name in enumerate(F_egx.SEG_AP_VALUES)})
+        return res
+
+
+class ViewEnsembleTest(_DeviceCriterion):
+    """The test epoch of the action-recognition translators after the model: MultiTaskClassificationTask.test_step / test_epoch_end
+    (HOI/tasks/lta/long_term_anticipation.py:86-158; the same code in long_term_anticipation_taskspecfic.py:88-162), the number the
+    EgoT2-s AR models are reported with. Every video is seen as TEST.NUM_ENSEMBLE_VIEWS x TEST.NUM_SPATIAL_CROPS clips; the reference
+
+        torch.cat's every clip's logits of the epoch, walks the clips in a Python loop with three dicts of per-video tensors (one `+=` or
+        torch.max launch per clip and head), stacks the dict values and calls topk_errors four times, each read with .item()
+
+    Here: `reset()` at the start of the epoch, `update(preds, labels, clip_ids)` per batch (one launch, nothing synchronises),
+    `step_result()` at its end - one launch (functional.view_ensemble_topk) and ONE device-to-host copy of 3 + H + len(ks) * H words.
+
+    `ViewEnsembleTest(capacity, classes, method, ks)`: at most `capacity` videos; `classes` = cfg.MODEL.NUM_CLASSES; `method` =
+    cfg.DATA.ENSEMBLE_METHOD. "sum" adds a video's clips in fp32 in ARRIVAL order from 0 - the reference's operations in its order, so the
+    rows have its bits; "max" keeps the running maximum, which starts from 0 as the reference's torch.zeros makes it: a video whose
+    logits are all negative ends as a row of zeros (kept as it is, not "fixed"). A video's label is its last clip's.
+    `update(preds, labels, clip_ids=...)`: preds = the [(B, C_verb), (B, C_noun)] list `forward_features` returns, labels int64 (B, H),
+    clip_ids a host sequence of hashables (the loader's clip_id strings), mapped to dense slots in first-appearance order - the order of
+    the reference's dicts, so row i of every output is the reference's i-th video. `slots=` (instead of clip_ids) takes a host sequence /
+    CPU tensor of slots, or a device tensor together with `rows=`, the number of videos it reaches (a slot outside [0, capacity) is
+    dropped on the device and counted in n_dropped). The views of a video need not be adjacent and may be spread over batches.
+
+    The id map and the video count are host state, so update, compute and reset cannot be captured in a graph, and more than `capacity`
+    videos raise here. Ties go to the lower class (torch.topk: unspecified); a video whose label is outside [0, C_h) is never correct and
+    is counted in n_invalid; errors divide by the number of videos, as topk_errors divides by preds.size(0). Across ranks: gather
+    predictions, labels and ids before update - what the reference does (du.all_gather, :104-107). Buffers are allocated per device on the
+    first eager call."""
+
+    HEAD_NAMES = ("verb", "noun")
+
+    def __init__(self, capacity: int, classes, method: str = "sum", ks=(1, 5)):
+        super().__init__()
+        self.classes = F_egx._view_ens_classes("ViewEnsembleTest", classes)
+        self.capacity = int(capacity)
+        if not 1 <= self.capacity or self.capacity * sum(self.classes) > 1 << 31:
+            raise ValueError(f"ViewEnsembleTest: capacity={capacity} (needs capacity >= 1 and capacity * sum(classes) <= 2^31)")
+        if method not in F_egx.VIEW_ENS_METHODS:
+            raise ValueError(f"ViewEnsembleTest: method={method!r} (needs 'sum' or 'max', cfg.DATA.ENSEMBLE_METHOD)")
+        self.method = method
+        self.ks = tuple(int(k) for k in ks)
+        if not 1 <= len(self.ks) <= F_egx.SEG_CE_MAX_KS or min(self.ks) < 1 or max(self.ks) > min(self.classes):
+            raise ValueError(f"ViewEnsembleTest: ks={ks} (needs 1 to {F_egx.SEG_CE_MAX_KS} values in 1 .. {min(self.classes)}, the narrowest head)")
+        self._slot_of: Dict[object, int] = {}           # clip id -> slot, in first-appearance order (the reference's dict order)
+        self._rows = 0                                  # videos 0 .. _rows - 1 hold (or are reserved for) a row
+        self._device: Optional[torch.device] = None
+        self._computed = False
+
+    def _allocate(self, device) -> dict:
+        """The accumulator, the result words (`flat`) and the per-video outputs."""
+        cap, H = self.capacity, len(self.classes)
+        if device.type != "cuda":       # host stand-in (the step_result arithmetic): no accumulator
+            state = torch.zeros(0, dtype=torch.uint8)
+        else:
+            state = F_egx.view_ensemble_state(cap, self.classes, device)
+        flat = torch.zeros(len(F_egx.VIEW_ENS_COUNTS) + H + len(self.ks) * H, dtype=torch.int32, device=device)
+        return {"state": state, "flat": flat, **F_egx.view_ensemble_views(flat, H, len(self.ks)),
+                "rank": torch.zeros((cap, H), dtype=torch.int32, device=device),
+                "pred": torch.zeros((cap, H), dtype=torch.int32, device=device)}
+
+    def _refuse_capture(self, device, what: str):
+        if self._capturing(device):
+            raise RuntimeError(f"ViewEnsembleTest.{what} cannot be captured in a graph: the id map and the video count are host state (a "
+                               "replay would fold the batch into the same videos again); call it eagerly")
+
+    def reset(self) -> "ViewEnsembleTest":
+        """Empty the accumulator (one memset on the stream), forget the ids and rewind the video count."""
+        if self._device is not None:
+            self._refuse_capture(self._device, "reset")
+            self._result_buffers(self._device)["state"].zero_()
+        self._slot_of, self._rows, self._computed, self._last = {}, 0, False, None
+        return self
+
+    def _slots_of_ids(self, clip_ids) -> Tuple[List[int], Dict[object, int]]:
+        """-> (the slot of every id, the id map grown by the new ids); nothing of self changes (the caller commits after its checks)."""
+        grown = dict(self._slot_of)
+        base = self._rows
+        if base != len(grown):
+            raise ValueError("ViewEnsembleTest.update: clip_ids and slots cannot be mixed within an epoch")
+        return [grown.setdefault(cid, len(grown)) for cid in clip_ids], grown
+
+    def update(self, preds, labels: torch.Tensor, clip_ids=None, slots=None, rows: Optional[int] = None) -> None:
+        preds = [preds] if isinstance(preds, torch.Tensor) else list(preds)
+        dev = preds[0].device
+        self._refuse_capture(dev, "update")
+        B = int(preds[0].shape[0])
+        if (clip_ids is None) == (slots is None):
+            raise ValueError("ViewEnsembleTest.update takes exactly one of clip_ids and slots")
+        if self._device is not None and dev != self._device:
+            raise ValueError(f"ViewEnsembleTest: predictions on {dev}, the accumulator is on {self._device}")
+        grown = self._slot_of
+        if clip_ids is not None:
+            host, grown = self._slots_of_ids(list(clip_ids))
+            host = torch.tensor(host, dtype=torch.int32)
+            reach, slot_t = len(grown), host
+        elif isinstance(slots, torch.Tensor) and slots.is_cuda:
+            if rows is None:
+                raise ValueError("ViewEnsembleTest.update: device slots need rows= (the number of videos they reach): the host cannot "
+                                 "read them without a synchronisation")
+            reach, slot_t = max(self._rows, int(rows)), slots
+        else:
+            if self._slot_of:
+                raise ValueError("ViewEnsembleTest.update: clip_ids and slots cannot be mixed within an epoch")
+            host = torch.as_tensor(slots, dtype=torch.int64).reshape(-1)
+            if B and int(host.min()) < 0:
+                raise ValueError("ViewEnsembleTest.update: host slots must be >= 0")
+            reach, slot_t = max(self._rows, int(host.max()) + 1 if host.numel() else 0), host
+        if slot_t.numel() != B:
+            raise ValueError(f"ViewEnsembleTest.update: {slot_t.numel()} ids / slots for {B} clips")
+        if reach > self.capacity:
+            raise ValueError(f"ViewEnsembleTest.update: {reach} videos exceed capacity={self.capacity}")
+        b = self._result_buffers(dev)
+        if not slot_t.is_cuda:
+            slot_t = slot_t.to(dev, non_blocking=False)
+        F_egx.view_ensemble_update(b["state"], self.capacity, self.classes, preds, labels.to(device=dev, dtype=torch.int64), slot_t,
+                                   method=self.method)
+        self._device, self._rows, self._slot_of, self._computed = dev, reach, grown, False
+
+    def compute(self) -> dict:
+        """-> device tensors of the videos so far: `rank`, `pred` (n, H) int32 and the int32 counts `n`, `n_dropped`, `n_nonfinite`,
+        `n_invalid` (H,), `correct` (len(ks), H). Nothing synchronises."""
+        if self._device is None or self._rows == 0:
+            raise RuntimeError("ViewEnsembleTest: no update has run yet")
+        self._refuse_capture(self._device, "compute")
+        b = self._result_buffers(self._device)
+        res = F_egx.view_ensemble_topk(b["state"], self.capacity, self.classes, self._rows, self.ks, out=b)
+        self._last = {"buffers": b, "result": {k: v for k, v in res.items() if k != "flat"}}
+        self._computed = True
+        return dict(self._last["result"])
+
+    def stats(self) -> dict:
+        """The device tensors of the most recent compute()."""
+        return dict(self._latest()["result"])
+
+    def video_ids(self) -> list:
+        """The clip ids in row order (first appearance); with slots= the rows are the caller's slots and this is range(n)."""
+        return list(self._slot_of) if self._slot_of else list(range(self._rows))
+
+    def predictions(self):
+        """-> (pred (n, H), rank (n, H), video ids in row order) of the most recent compute(), for a submission file. Device tensors."""
+        r = self._latest()["result"]
+        return r["pred"], r["rank"], self.video_ids()
+
+    def head_names(self) -> Tuple[str, ...]:
+        return self.HEAD_NAMES if len(self.classes) == 2 else tuple(str(h) for h in range(len(self.classes)))
+
+    def step_result(self, prefix: str = "test") -> Dict[str, float]:
+        """The epoch's logged values from ONE device-to-host copy (it synchronises): f"{prefix}_top{k}_{head}_err" for every k of `ks` and
+        head (verb / noun with two heads: the reference's top1_verb_err, top5_verb_err, top1_noun_err, top5_noun_err; the head's index
+        otherwise) = (1 - correct / n) * 100 in fp32, as the reference's fp32 tensors compute it, with n = the number of videos; and the
+        counts f"{prefix}_n", _n_dropped, _n_nonfinite, f"{prefix}_n_invalid_{head}", f"{prefix}_correct{k}_{head}". Runs compute() first
+        when clips arrived since the last one. prefix="" gives the reference's bare keys."""
+        if not self._computed and self._device is not None and self._rows > 0:
+            self.compute()
+        host = self._latest()["buffers"]["flat"].cpu().numpy()
+        import numpy as np
+        H, nc = len(self.classes), len(F_egx.VIEW_ENS_COUNTS)
+        pre = f"{prefix}_" if prefix else ""
+        res: Dict[str, float] = {f"{pre}{name}": int(host[i]) for i, name in enumerate(F_egx.VIEW_ENS_COUNTS)}
+        n = np.float32(host[0])
+        invalid, correct = host[nc:nc + H], host[nc + H:].reshape(len(self.ks), H)
+        for h, name in enumerate(self.head_names()):
+            res[f"{pre}n_invalid_{name}"] = int(invalid[h])
+            for ki, k in enumerate(self.ks):
+                res[f"{pre}correct{k}_{name}"] = int(correct[ki, h])
+                err = (np.float32(1.0) - np.float32(correct[ki, h]) / n) * np.float32(100.0) if host[0] > 0 else np.float32("nan")
+                res[f"{pre}top{k}_{name}_err"] = float(err)
         return res
 
 

@@ -782,6 +782,50 @@ size_t egx_segment_ap_scratch(int capacity);
 int egx_segment_scores_update(const float* logits, int ld, int B, const int64_t* slots, int slot0, const int64_t* labels, int capacity,
                               void* scratch, void* stream);
 int egx_segment_ap(int N, int capacity, void* scratch, float* score, int* order1, int* order0, void* result, void* stream);
+/* ---- ABI v23 additions (new symbols only, as v19 to v22: EGX_ABI_VERSION stays 18): the test epoch of the action-recognition translators
+ * on the device - the multi-view ensemble per video and the top-k errors over the videos ---------------------------------------------------
+ * MultiTaskClassificationTask.test_epoch_end (HOI/tasks/lta/long_term_anticipation.py:96-158; the same code in
+ * long_term_anticipation_taskspecfic.py:100-162). A video is a slot 0 .. capacity - 1; the heads (H <= 4, C[h] <= 2048 classes) are packed
+ * side by side in a state row of sum(C) floats.
+ *
+ * egx_view_ensemble_state -> the bytes of the state for `capacity` videos (0: refused, see egx_last_error): a 256-byte header (the
+ * top-k launch's arrival counter, the dropped clips), the labels int64 (capacity, H), the view counts int32 (capacity), 24 KiB of count
+ * partials and the rows fp32 (capacity, sum C). `offsets` (may be NULL): 3 words, the byte offsets of labels, view counts and rows.
+ * ZERO the state to empty the accumulator (the reference's torch.zeros rows); the same capacity, H and C go into every call.
+ *
+ * egx_view_ensemble_update replaces the loop of :116-140 (three dicts of per-video tensors, one `+=` or torch.max launch per clip and head,
+ * after a torch.cat of every clip of the epoch) for one batch of clips:
+ *   preds    fp32, B clips of row stride `ld`; head h is columns [col0[h], col0[h] + C[h]) of a row.
+ *   labels   int64 (B, H): a video takes the labels of its LAST clip (:118).
+ *   slots    DEVICE, int32 (slot_bytes 4) or int64 (slot_bytes 8), (B): the video of every clip. The clips of a video need not be adjacent,
+ *            may repeat within a batch and may be spread over calls. A slot outside [0, capacity) is dropped and counted. NULL: clip i is
+ *            video slot0 + i (0 <= slot0, slot0 + B <= capacity is checked on the host).
+ *   method   0 "sum": row = ((0 + x_1) + x_2) + ... in fp32, the clips in ARRIVAL order (row order within a call, call order across calls);
+ *            1 "max": row = max(0, x_1, x_2, ...) - the running value starts from the reference's torch.zeros, so a video whose logits are
+ *            all negative ends as a row of zeros; a NaN stays, as in torch.max of two tensors.
+ * One launch, a workgroup per (clip, 256 columns): the workgroup of a video's first clip in the batch folds all its clips in a register and
+ * stores the row once. A row has the same bits on every run and however its clips are spread over rows and calls; no float atomics.
+ *
+ * egx_view_ensemble_topk replaces the torch.stack of the dict values and the four topk_errors calls of :142-158
+ * (HOI/evaluation/lta/lta_metrics.py:38-84) over videos 0 .. n - 1:
+ *   rank     (n, H) int32: #{c : x_c > x_y} + #{c < y : x_c == x_y} of the video's label y in its head's window (the rule of
+ *            egx_segmented_ce: among equal values the lower class ranks first; torch.topk leaves it unspecified). A NaN ranks as the greatest
+ *            value (as torch.topk has it). -1 where the label is outside [0, C[h]).
+ *   pred     (n, H) int32: the class of rank 0.
+ *   result   (3 + H + n_ks * H) int32, every one written by every call: n, n_dropped (clips dropped since the state was zeroed),
+ *            n_nonfinite (videos with a non-finite value in any head), n_invalid[h] (videos whose label is outside [0, C[h]): never correct),
+ *            correct[k][h] (videos with 0 <= rank < ks[k]). top-k error = (1 - correct / n) * 100: topk_errors divides by preds.size(0).
+ * One launch; counts go through per-workgroup partials that the last workgroup to arrive adds in a fixed order; the arrival counter
+ * leaves itself zero. Nothing synchronises.
+ * Refused on the host, before any device work, with a message that names the limit: a null pointer; capacity < 1; H outside 1 .. 4;
+ * C[h] outside 1 .. 2048; capacity * sum(C) > 2^31 state elements; B outside 1 .. 65536; ld < 1; windows that overlap or leave the row;
+ * an unknown method; slot_bytes other than 4 / 8; without slots, slot0 < 0 or slot0 + B > capacity; n outside 1 .. capacity; n_ks outside
+ * 1 .. 4; ks[k] outside 1 .. the narrowest head. */
+size_t egx_view_ensemble_state(int capacity, int H, const int* C, size_t* offsets);
+int egx_view_ensemble_update(const float* preds, int ld, int B, int H, const int* col0, const int* C, const int64_t* labels, const void* slots,
+                             int slot_bytes, int slot0, int method, int capacity, void* state, void* stream);
+int egx_view_ensemble_topk(int n, int capacity, int H, const int* C, const int* ks, int n_ks, void* state, int* rank, int* pred, void* result,
+                           void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
