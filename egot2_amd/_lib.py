@@ -143,6 +143,16 @@ SIGNATURES = {
     "egx_ragged_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.POINTER(Head), C.c_int,
                                  _fp, _fp, _fp, _fp, C.POINTER(SegmentGrads), _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads),
                                  C.c_int, C.c_uint64, _fp]),
+    "egx_ragged_table_host": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.c_int, _fp, C.POINTER(C.c_size_t)]),
+    "egx_ragged_cap_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, C.c_int, C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_size_t)]),
+    "egx_ragged_cap_table": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp,
+                                       C.POINTER(C.c_size_t), _fp]),
+    "egx_ragged_cap_train_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.POINTER(Head), C.c_int,
+                                           C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_uint64, _fp]),
+    "egx_ragged_cap_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.POINTER(Head), C.c_int,
+                                     C.c_int, _fp, _fp, _fp, _fp, C.POINTER(SegmentGrads), _fp, _fp, C.POINTER(LayerGrads),
+                                     C.POINTER(HeadGrads), _fp, C.c_int, C.c_uint64, _fp]),
     "egx_ragged_encode_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t)]),
     "egx_ragged_encode": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, _fp, C.POINTER(Layer), C.c_int, _fp, C.c_int, _fp, _fp]),
     "egx_ragged_encode_train_workspace": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.POINTER(C.c_size_t),

@@ -315,6 +315,33 @@ int upload_words(int* dst, const int* src, size_t n, hipStream_t st);
 // [rseg[b * FUSED_MAX_SEG + k], + T_{b,k}), T_{b,k} from the batch table): to_packed = 1 copies the valid frames into the packed rows,
 // 0 writes the packed rows back to the padded tensor and zeroes its padded frames. C % 4 == 0.
 int ragged_rows(float* padded, float* packed, const int* rtab, const int* rseg, int B, int T_pad, int C, int k, int to_packed, hipStream_t st);
+// ---- capacity plan (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd, ragged_table.hip): the same table built on the device from DEVICE lengths,
+// sized by a capacity (B_cap clips, tok_cap tokens, tile_cap = ceil(tok_cap / 48) + B_cap tiles) instead of by the batch. Words of the device
+// table: B_cap records | tile_cap tile -> clip entries (-1: a surplus tile, its workgroup leaves at once) | B_cap * FUSED_MAX_SEG packed first
+// rows (rseg) | RAGGED_META totals of the batch. A clip whose lengths are all 0 is empty: a zero record, no tile, no token, target -1.
+constexpr int RAGGED_META = 8;
+enum { RM_TOKENS = 0, RM_TILES = 1, RM_ANY = 2, RM_SEG_ROWS = 3 /* .. 6 */, RM_STATUS = 7 };
+// status bits (sticky in the caller's status word): a length outside 0 .. T_pad | a clip with some segments empty | S_b > TILED_MAX_S | sum S_b > tok_cap
+enum { RAGGED_BAD_LENGTH = 1, RAGGED_BAD_PARTIAL = 2, RAGGED_BAD_CLIP = 4, RAGGED_BAD_TOKENS = 8 };
+static inline size_t ragged_cap_table_words(int B_cap, int tile_cap) { return (size_t)B_cap * (RAGGED_REC + FUSED_MAX_SEG) + (size_t)tile_cap + RAGGED_META; }
+struct RaggedTableParams {
+    const int* lengths;             // DEVICE (B_cap, K)
+    int K, T_pad[FUSED_MAX_SEG], B_cap, tok_cap, tile_cap;
+    const int64_t* target;          // DEVICE (B_cap) or null
+    int64_t* eff_target;            // (B_cap) or null: target[b] of a non-empty clip, -1 of an empty one (what the cross entropy reads)
+    int* tab;                       // ragged_cap_table_words() ints
+    unsigned* status;               // sticky status word (DEVICE) or null
+};
+int ragged_table_build(const RaggedTableParams& p, hipStream_t st);
+// The rows no clip of this batch owns, zeroed from the table's totals: rows [first, cap_rows) of each listed array, first = the batch's tokens
+// (RS_TOKENS), tiles (RS_TILES) or packed rows of segment k (RS_SEG0 + k). Row sizes and bases are multiples of 16 bytes.
+enum { RS_TOKENS = 0, RS_TILES = 1, RS_SEG0 = 2 };
+constexpr int RAGGED_SLACK_MAX = 96;
+struct RaggedSlackDesc { char* base; unsigned row_bytes; int cap_rows; int kind; };
+struct RaggedSlackParams { RaggedSlackDesc d[RAGGED_SLACK_MAX]; int n; const int* meta; };
+int ragged_slack_add(RaggedSlackParams& p, void* base, size_t row_bytes, size_t cap_rows, int kind);
+int ragged_slack_zero(const RaggedSlackParams& p, hipStream_t st);
+int ragged_empty_loss(const int* meta, float* loss, hipStream_t st);      // *loss = 0 where the batch has no clip
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st);
 int tiled_attn_bwd(const TiledAttnParams& p, int compute, hipStream_t st);
 

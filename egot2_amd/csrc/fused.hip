@@ -159,6 +159,10 @@ __global__ __launch_bounds__(256, 1) void fused_fwd_kernel(FusedFwdParams p) {
     const int* rrec = nullptr;              // RAGGED: the clip's record of the batch table
     if constexpr (RAGGED) {
         c_real = p.rtab[(size_t)p.B_clips * RAGGED_REC + clip];
+        // capacity launches (egx_ragged_cap_train_fwd): the grid is the tile CAPACITY; a surplus tile (-1) owns no row of any array and its
+        // workgroup leaves as a whole, here, before the first barrier. (The forward has no arrival counter and no per-workgroup share of a
+        // fill: the fused losses of the one-launch kernels, the only counters in this file, are not compiled into the tiled instantiations.)
+        if (c_real < 0) return;
         rrec = p.rtab + (size_t)c_real * RAGGED_REC;
         t0 = (clip - rrec[RG_TILE0]) * 48;
         S = min(48, rrec[RG_S] - t0);

@@ -1320,7 +1320,9 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
     const int* rrec = nullptr;              // RAGGED: the clip's record of the batch table
     if constexpr (RAGGED) {
         c_real = p.rtab[(size_t)p.B_clips * RAGGED_REC + clip];
-        rrec = p.rtab + (size_t)c_real * RAGGED_REC;
+        // capacity launches (egx_ragged_cap_bwd): a surplus tile (-1) reads record 0 here — in bounds, never used — does its share of
+        // the zero_buf fill below and leaves
+        rrec = p.rtab + (size_t)max(c_real, 0) * RAGGED_REC;
         t0 = (clip - rrec[RG_TILE0]) * 48;
         S = min(48, rrec[RG_S] - t0);
         tok0 = (size_t)rrec[RG_TOK0] + t0;
@@ -1338,6 +1340,11 @@ __global__ __launch_bounds__(256, 1) void fused_bwd_kernel(FusedBwdParams p) {
         for (size_t k = b0 + threadIdx.x; k < b1; k += 256) reinterpret_cast<float4*>(p.zero_buf)[k] = make_float4(0, 0, 0, 0);
     }
     if constexpr (SLICED) { if (clip >= p.B || ((p.slice_drop >> slice) & 1)) return; }        // (the grid is round_up(B, 8) * n_slices)
+    // RAGGED, a surplus tile of a capacity launch: the workgroup leaves as a whole before the first barrier. The zero_buf fill above is the only
+    // thing a ragged launch shares out by gridDim.x, and the surplus workgroup has done its share; this kernel has no arrival counter (the sums
+    // over tiles are the tail launch's, whose grid does not depend on the batch). Its partial row, H / dH tiles and g2 planes are cleared by
+    // ragged_slack_zero (ragged_table.hip).
+    if constexpr (RAGGED) { if (c_real < 0) return; }
 
     BSTAMP(12);
     float* part = p.partials + (size_t)clip * p.P;

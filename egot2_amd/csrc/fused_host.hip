@@ -830,17 +830,15 @@ struct RaggedPlan {
     Plan vp;                    // vp.B clips, vp.vB tiles, vp.N = sum_b S_b tokens, vp.S = the longest clip
     size_t out_rows = 0;        // head-less output rows: sum_b T_{b,0}
     size_t off_attn = 0, off_lse = 0, off_tokens = 0, off_tab = 0, bytes = 0;
-    std::vector<int> tab;       // host copy of the batch table
+    std::vector<int> tab;       // host copy of the batch table (empty in a capacity plan: the device builds it, ragged_table.hip)
+    size_t tab_words = 0;       // ints of the device table
+    size_t off_efft = 0;        // capacity plan: the effective targets int64 (B) behind the table
     int tiles = 0;
     size_t seg_rows[FUSED_MAX_SEG] = {0, 0, 0, 0};    // training plan: sum_b T_{b,k}, the packed rows of segment k
 };
 
-// train (egx_ragged_train_*): dropout (but FEAT) and the weighted cross entropy are allowed; the table gets the packed first row of every
-// clip's segments behind the tile map (FusedBwdParams::rseg)
-int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp, bool train = false) {
-    Plan& vp = rp.vp;
-    if (make_plan(cfg, segs, B, vp)) return 1;
-    EGX_CHECK(lengths, "ragged batch: null lengths");
+// what a ragged call asks of its configuration, whatever the lengths (the host plan and the capacity plan)
+int ragged_config_ok(const egx_config* cfg, const egx_segment* segs, int B, const Plan& vp, bool train) {
     EGX_CHECK(B <= (1 << 20), "ragged batch: B=%d clips (at most %d)", B, 1 << 20);
     if (train) {
         EGX_CHECK(cfg->p_feat == 0.f, "ragged training: feature dropout (p_feat > 0) is not supported (got %g)", cfg->p_feat);
@@ -862,6 +860,25 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
               "ragged batch: needs d=128, h=4, d_ff%%128==0, <= %d segments, 1..%d layers, fp32 features, compute bf16 or f32s", FUSED_MAX_SEG, FUSED_MAX_LAYERS);
     for (int k = 0; k < vp.nseg; ++k)
         EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0, "ragged batch: segment %d needs a projection with d_in %% 128 == 0", k);
+    return 0;
+}
+// the workspace view of a plan whose vp (B clips, vB tiles, N tokens) and tab_words are set
+void ragged_layout(const egx_config* cfg, const egx_segment* segs, RaggedPlan& rp) {
+    const Plan& vp = rp.vp;
+    const size_t d = vp.d;
+    rp.off_attn = align_up(fused_x1f_offset(cfg, segs, vp), 256);        // (the tiled launches write no x1f rows: fused_core_bytes with tpc > 1)
+    rp.off_lse = rp.off_attn + align_up((size_t)vp.L * vp.N * d * 4, 256);
+    rp.off_tokens = rp.off_lse + align_up((size_t)vp.L * vp.H * vp.N * 4, 256);
+    rp.off_tab = rp.off_tokens + align_up((vp.N + (size_t)vp.B) * d * 4, 256);
+    rp.bytes = rp.off_tab + align_up(rp.tab_words * sizeof(int), 256);
+}
+// train (egx_ragged_train_*): dropout (but FEAT) and the weighted cross entropy are allowed; the table gets the packed first row of every
+// clip's segments behind the tile map (FusedBwdParams::rseg)
+int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp, bool train = false) {
+    Plan& vp = rp.vp;
+    if (make_plan(cfg, segs, B, vp)) return 1;
+    EGX_CHECK(lengths, "ragged batch: null lengths");
+    if (ragged_config_ok(cfg, segs, B, vp, train)) return 1;
     const int K = vp.nseg;
     rp.tab.assign((size_t)B * RAGGED_REC, 0);
     int tiles = 0, S_max = 0;
@@ -898,12 +915,8 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
     rp.tiles = tiles;
     vp.vB = tiles; vp.tpc = 0; vp.N = tok; vp.S = S_max;
     rp.out_rows = out;
-    const size_t d = vp.d;
-    rp.off_attn = align_up(fused_x1f_offset(cfg, segs, vp), 256);        // (the tiled launches write no x1f rows: fused_core_bytes with tpc > 1)
-    rp.off_lse = rp.off_attn + align_up((size_t)vp.L * vp.N * d * 4, 256);
-    rp.off_tokens = rp.off_lse + align_up((size_t)vp.L * vp.H * vp.N * 4, 256);
-    rp.off_tab = rp.off_tokens + align_up((vp.N + (size_t)B) * d * 4, 256);
-    rp.bytes = rp.off_tab + align_up(rp.tab.size() * sizeof(int), 256);
+    rp.tab_words = rp.tab.size();
+    ragged_layout(cfg, segs, rp);
     return 0;
 }
 // with a head the last layer leaves EVERY token of a clip (rows tok0 .. tok0 + S_b of the dense array); head-less its first segment, packed
@@ -934,14 +947,17 @@ TiledView ragged_view(const RaggedPlan& rp, int B, const void* workspace, const 
 // inference call's keys stay zero and its FFN keep-scale 1.
 int ragged_forward(const egx_config* cfg, const egx_segment* segs, RaggedPlan& rp, const float* ln_w, const float* ln_b, const egx_layer* layers,
                    const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, bool train, int training, uint64_t seed,
-                   hipStream_t st) {
+                   hipStream_t st, bool dev_table = false) {
     const Plan& vp = rp.vp;
     const bool with_head = head && head->W;
-    ragged_head_rows(rp, B, with_head);
     // the batch table to the device, stream-ordered, in the arguments of upload launches (no host buffer has to outlive the call). Its
     // contents depend on the lengths of THIS call: a captured hipGraph would replay them for every batch, so the call is not for capture.
+    // (dev_table: the capacity plan's table, already built in place by ragged_table_build on this stream.)
     int* tab = (int*)((char*)workspace + rp.off_tab);
-    if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    if (!dev_table) {
+        ragged_head_rows(rp, B, with_head);
+        if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
+    }
     const TiledView v = ragged_view(rp, B, workspace, tab, train);
     FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, workspace, vp));
     FusedFwdParams fp;
@@ -997,7 +1013,7 @@ RaggedTrainScratch ragged_train_scratch(const egx_config* cfg, const egx_segment
     s.datt = take(cur, nd); s.dres = take(cur, nd);
     s.delta = take(cur, (size_t)pl.H * pl.N * 4);
     s.bytes = cur;
-    r.tab = take(cur, rp.tab.size() * sizeof(int));
+    r.tab = take(cur, rp.tab_words * sizeof(int));
     size_t dfeat = 0;
     for (int i = 0; i < pl.nseg; ++i) {
         r.featp[i] = take(cur, rp.seg_rows[i] * segs[i].d_in * 4);
@@ -1007,6 +1023,11 @@ RaggedTrainScratch ragged_train_scratch(const egx_config* cfg, const egx_segment
     r.bytes = cur;
     return r;
 }
+int ragged_backward(const egx_config* cfg, const egx_segment* segs, const RaggedPlan& rp, const RaggedTrainScratch& RS, const int* tab,
+                    const int* rseg, const int* cap_meta, const float* ln_w, const float* ln_b, const egx_layer* layers, const egx_head* head, int B,
+                    const float* d_logits, const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                    float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, int training,
+                    uint64_t seed, hipStream_t st);
 }  // namespace
 
 extern "C" {
@@ -1039,20 +1060,33 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
                    const egx_head_grads* head_grads, int training, uint64_t seed, void* stream) {
     RaggedPlan rp;
     if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
-    const Plan& vp = rp.vp;
     const bool with_head = head && head->W;
     EGX_CHECK((with_head ? (const void*)d_logits : (const void*)d_tokens) && saved && scratch && ln_w && ln_b && layers && layer_grads,
               "ragged training: null pointer argument");
     if (check_head(head)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const int d = vp.d, comp = cfg->compute, L = vp.L;
     RaggedTrainScratch RS = ragged_train_scratch(cfg, segs, rp, with_head ? head->n_out : 0);
-    const FusedBwdScratch& SC = RS.sc;
     // the batch table again (the backward's own copy: nothing of the forward's call is trusted but `saved`)
     ragged_head_rows(rp, B, with_head);
     int* tab = (int*)((char*)scratch + RS.tab);
     if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
-    const int* rseg = tab + (size_t)B * RAGGED_REC + rp.tiles;
+    return ragged_backward(cfg, segs, rp, RS, tab, tab + (size_t)B * RAGGED_REC + rp.tiles, nullptr, ln_w, ln_b, layers, head, B, d_logits, d_tokens,
+                           saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
+}
+
+}  // extern "C"
+
+namespace {
+// The backward of egx_ragged_bwd and egx_ragged_cap_bwd behind their table (`tab` on the device, `rseg` inside it). cap_meta (the capacity
+// plan: the totals of the device-built table): every size below is the CAPACITY's, and the rows no clip of this batch owns are cleared first.
+int ragged_backward(const egx_config* cfg, const egx_segment* segs, const RaggedPlan& rp, const RaggedTrainScratch& RS, const int* tab,
+                    const int* rseg, const int* cap_meta, const float* ln_w, const float* ln_b, const egx_layer* layers, const egx_head* head, int B,
+                    const float* d_logits, const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                    float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, int training,
+                    uint64_t seed, hipStream_t st) {
+    const Plan& vp = rp.vp;
+    const int d = vp.d, comp = cfg->compute, L = vp.L;
+    const FusedBwdScratch& SC = RS.sc;
     bool want_pos = false;
     for (int i = 0; i < vp.nseg && seg_grads; ++i) want_pos = want_pos || seg_grads[i].pos;
     EGX_CHECK(!want_pos, "ragged training: learned positional tables (egx_segment_grads.pos) are not supported");
@@ -1061,6 +1095,44 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     FusedBwdParams bp;
     if (fill_bwd(bp, PL, SC, v, cfg, segs, vp, ln_w, ln_b, layers, head, d_logits, d_tokens, scratch, training, seed)) return 1;
     bp.rseg = rseg;
+    const float* featp[FUSED_MAX_SEG];
+    for (int i = 0; i < vp.nseg; ++i) featp[i] = fptr(scratch, RS.featp[i]);
+    if (cap_meta) {
+        // Capacity plan: the weight-gradient launches below run over tok_cap token rows, the tile capacity and capacity-sized packed segment
+        // rows. What no clip of THIS batch owns — token rows [N, tok_cap), the per-tile arrays of the surplus tiles, the packed rows beyond
+        // sum_b T_{b,k} — is written by no launch (a surplus workgroup leaves at once, fused_bwd.hip), so it is cleared here, both operands of
+        // every product (a stale NaN times zero is a NaN): those launches then add exact zeros. `saved` is the forward's of this very step.
+        // (Arrival counters: none of this call's launches has one. The tile and attention launches leave per-tile rows; ffn_dw, small_dw and
+        // the tail launch that sums them in a fixed order have grids of the capacity's sizes, which the host knows.)
+        RaggedSlackParams sl;
+        memset(&sl, 0, sizeof(sl));
+        sl.meta = cap_meta;
+        const bool bf = comp == EGX_BF16;
+        const int parts = bf ? 1 : 3;
+        const size_t tile_rows = (size_t)FUSED_TOK_PAD * d * 2, plane = (size_t)vp.vB * tile_rows;      // a tile / all tiles of one bf16 plane
+        const size_t hid_tile = fused_hid_bytes(1, vp.dff, bf), row = (size_t)d * 4;
+        char* sv = (char*)const_cast<void*>(saved);
+        int rc = 0;
+        for (int l = 0; l < L; ++l) {
+            const size_t lo = (size_t)l * fused_hid_bytes(vp.vB, vp.dff, bf);
+            rc |= ragged_slack_add(sl, sv + fused_hid_offset(cfg, segs, vp) + lo, hid_tile, vp.vB, RS_TILES);
+            rc |= ragged_slack_add(sl, (char*)scratch + SC.dhid + lo, hid_tile, vp.vB, RS_TILES);
+            for (int j = 0; j < parts; ++j) {
+                rc |= ragged_slack_add(sl, sv + fused_x1p_offset(cfg, segs, vp) + ((size_t)l * parts + j) * plane, tile_rows, vp.vB, RS_TILES);
+                rc |= ragged_slack_add(sl, (char*)bp.layer[l].g2_out + j * plane, tile_rows, vp.vB, RS_TILES);
+            }
+            rc |= ragged_slack_add(sl, bp.layer[l].g1_out, row, vp.N, RS_TOKENS);
+            rc |= ragged_slack_add(sl, bp.layer[l].attn_o_out, row, vp.N, RS_TOKENS);
+            rc |= ragged_slack_add(sl, bp.layer[l].dqkv_out, 3 * row, vp.N, RS_TOKENS);
+            rc |= ragged_slack_add(sl, bp.layer[l].x_in_out, row, vp.N, RS_TOKENS);
+        }
+        for (int i = 0; i < vp.nseg; ++i) {
+            rc |= ragged_slack_add(sl, bp.dseg_out[i], row, rp.seg_rows[i], RS_SEG0 + i);
+            rc |= ragged_slack_add(sl, const_cast<float*>(featp[i]), (size_t)segs[i].d_in * 4, rp.seg_rows[i], RS_SEG0 + i);
+        }
+        rc |= ragged_slack_add(sl, bp.partials, (size_t)bp.P * 4, vp.vB, RS_TILES);
+        if (rc || ragged_slack_zero(sl, st)) return 1;
+    }
     if (tiled_backward(bp, SC, v, cfg, vp, scratch, st)) return 1;
 
     // the small parameter gradients: the per-tile partial rows (padding rows of a clip's last tile add nothing: they are zero there)
@@ -1072,8 +1144,6 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     for (int l = 0; l < L; ++l)
         if (launch_ffn_dw(l, bp, PL, SC, v, cfg, segs, vp, layers, layer_grads, scratch, red, st)) return 1;
     // the projection-weight gradients read the valid feature frames only: gathered into packed rows that match the packed d(seg) rows
-    const float* featp[FUSED_MAX_SEG];
-    for (int i = 0; i < vp.nseg; ++i) featp[i] = fptr(scratch, RS.featp[i]);
     for (int i = 0; i < vp.nseg && seg_grads; ++i)
         if (seg_grads[i].proj_w && ragged_rows(const_cast<float*>(segs[i].feat), fptr(scratch, RS.featp[i]), tab, rseg, B, segs[i].T, segs[i].d_in, i, 1, st))
             return 1;
@@ -1091,6 +1161,130 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
         if (ragged_rows(seg_grads[i].feat, dfp, tab, rseg, B, segs[i].T, segs[i].d_in, i, 0, st)) return 1;
     }
     return 0;
+}
+
+// ---- capacity plan (egx_ragged_cap_*, ABI v24): one captured hipGraph for every batch that fits a declared capacity --------------------------
+// The layout of the host plan for B_cap clips, tok_cap tokens and ceil(tok_cap / 48) + B_cap tiles (which bounds sum_b ceil(S_b / 48) of every
+// batch that fits and leaves at least (tok_cap - N) / 48 surplus tiles); packed segment rows at min(tok_cap, B_cap T_k). Nothing here reads
+// a length: the table is built on the device (ragged_table.hip), stream-ordered, in front of each call's launches.
+constexpr int RAGGED_CAP_MAX_TOKENS = 1 << 24;
+int ragged_cap_plan(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, RaggedPlan& rp) {
+    EGX_CHECK(cfg && segs, "ragged capacity: null pointer argument");
+    EGX_CHECK(B_cap >= 1 && tok_cap >= 1, "ragged capacity: B_cap=%d clips and tok_cap=%d tokens must be at least 1", B_cap, tok_cap);
+    Plan& vp = rp.vp;
+    if (make_plan(cfg, segs, B_cap, vp)) return 1;
+    if (ragged_config_ok(cfg, segs, B_cap, vp, true)) return 1;
+    EGX_CHECK(tok_cap <= RAGGED_CAP_MAX_TOKENS, "ragged capacity: tok_cap=%d tokens (at most %d)", tok_cap, RAGGED_CAP_MAX_TOKENS);
+    EGX_CHECK((long long)tok_cap >= (long long)B_cap * vp.nseg,
+              "ragged capacity: tok_cap=%d tokens cannot hold B_cap=%d clips of %d segments (one frame per segment at least)", tok_cap, B_cap, vp.nseg);
+    long long s_pad = 0;
+    for (int k = 0; k < vp.nseg; ++k) {
+        s_pad += segs[k].T;
+        const long long r = (long long)B_cap * segs[k].T;
+        rp.seg_rows[k] = (size_t)(r < tok_cap ? r : tok_cap);
+    }
+    const int S_longest = (int)(s_pad < tok_cap ? s_pad : tok_cap);
+    rp.tiles = cdiv(tok_cap, FUSED_TOK_PAD) + B_cap;
+    vp.vB = rp.tiles; vp.tpc = 0; vp.N = (size_t)tok_cap; vp.S = S_longest < TILED_MAX_S ? S_longest : TILED_MAX_S;
+    rp.tab_words = ragged_cap_table_words(B_cap, rp.tiles);
+    ragged_layout(cfg, segs, rp);
+    rp.off_efft = rp.bytes;
+    rp.bytes += align_up((size_t)B_cap * sizeof(int64_t), 256);
+    return 0;
+}
+// what the two capacity calls refuse alike
+int ragged_cap_checks(const egx_config* cfg, const egx_head* head, int training, hipStream_t st) {
+    EGX_CHECK(head && head->W, "ragged capacity: a pooled head is required (the head-less rows of a captured batch are not supported yet)");
+    if (check_head(head) || check_ce(cfg->ce, true, "")) return 1;
+    // (as egx_translator_fwd: a host seed would be baked into the captured graph and every replay would repeat its masks)
+    if (training && !cfg->seed_ptr && (cfg->p_drop > 0.f || cfg->p_pos > 0.f)) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        EGX_CHECK(cs == hipStreamCaptureStatusNone, "training-mode dropout (p > 0) with a host seed cannot be captured in a hipGraph: every replay would "
+                  "repeat the same masks; pass egx_config.seed_ptr (model.enable_device_seed()), capture with p = 0, or launch eagerly");
+    }
+    return 0;
+}
+RaggedTableParams ragged_cap_table_params(const egx_segment* segs, const RaggedPlan& rp, int tok_cap, const int* lengths, const int64_t* target,
+                                          int64_t* eff_target, int* tab, unsigned* status) {
+    RaggedTableParams tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.lengths = lengths; tp.K = rp.vp.nseg; tp.B_cap = rp.vp.B; tp.tok_cap = tok_cap; tp.tile_cap = rp.tiles;
+    for (int k = 0; k < rp.vp.nseg; ++k) tp.T_pad[k] = segs[k].T;
+    tp.target = target; tp.eff_target = eff_target; tp.tab = tab; tp.status = status;
+    return tp;
+}
+}  // namespace
+
+extern "C" {
+
+int egx_ragged_table_host(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int train, int* out_words, size_t* n_words) {
+    EGX_CHECK(cfg && segs && n_words, "ragged table: null pointer argument");
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, train != 0)) return 1;
+    ragged_head_rows(rp, B, true);
+    *n_words = rp.tab.size();
+    if (out_words) memcpy(out_words, rp.tab.data(), rp.tab.size() * sizeof(int));
+    return 0;
+}
+
+int egx_ragged_cap_workspace(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, size_t* saved_bytes, size_t* scratch_bytes) {
+    RaggedPlan rp;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    if (saved_bytes) *saved_bytes = rp.bytes;
+    if (scratch_bytes) *scratch_bytes = ragged_train_scratch(cfg, segs, rp, FUSED_HEAD_MAX_OUT).bytes;
+    return 0;
+}
+
+int egx_ragged_cap_table(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, const int* lengths, const int64_t* target,
+                         int* table, int64_t* eff_target, unsigned* status, size_t* n_words, void* stream) {
+    RaggedPlan rp;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    if (n_words) *n_words = rp.tab_words;
+    if (!table) return 0;       // (the size query)
+    EGX_CHECK(lengths, "ragged capacity: null pointer argument");
+    return ragged_table_build(ragged_cap_table_params(segs, rp, tok_cap, lengths, target, eff_target, table, status), (hipStream_t)stream);
+}
+
+int egx_ragged_cap_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                             const egx_layer* layers, const egx_head* head, int B_cap, int tok_cap, float* logits_out, float* tokens_out,
+                             void* saved, void* scratch, unsigned* status, int training, uint64_t seed, void* stream) {
+    (void)scratch; (void)tokens_out;
+    RaggedPlan rp;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (ragged_cap_checks(cfg, head, training, st)) return 1;
+    EGX_CHECK(lengths && saved && ln_w && ln_b && layers && logits_out && status, "ragged capacity: null pointer argument");
+    int* tab = (int*)((char*)saved + rp.off_tab);
+    const int* meta = tab + rp.tab_words - RAGGED_META;
+    int64_t* efft = (int64_t*)((char*)saved + rp.off_efft);
+    const egx_ce* ce = cfg->ce;
+    if (ragged_table_build(ragged_cap_table_params(segs, rp, tok_cap, lengths, ce ? ce->target : nullptr, efft, tab, status), st)) return 1;
+    // the cross entropy reads the EFFECTIVE targets: an empty clip (and every clip of a refused batch) is -1 there, whatever the caller left
+    egx_config c2 = *cfg;
+    egx_ce ce2;
+    if (ce) { ce2 = *ce; ce2.target = efft; c2.ce = &ce2; }
+    if (ragged_forward(&c2, segs, rp, ln_w, ln_b, layers, head, B_cap, logits_out, nullptr, saved, true, training, seed, st, true)) return 1;
+    return ce ? ragged_empty_loss(meta, ce->loss, st) : 0;
+}
+
+int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                       const egx_layer* layers, const egx_head* head, int B_cap, int tok_cap, const float* d_logits, const float* d_tokens,
+                       const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b,
+                       const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, unsigned* status, int training, uint64_t seed,
+                       void* stream) {
+    RaggedPlan rp;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (ragged_cap_checks(cfg, head, training, st)) return 1;
+    EGX_CHECK(lengths && d_logits && saved && scratch && ln_w && ln_b && layers && layer_grads && status, "ragged capacity: null pointer argument");
+    RaggedTrainScratch RS = ragged_train_scratch(cfg, segs, rp, head->n_out);
+    // the table again, from the same device lengths (the backward's own copy, as egx_ragged_bwd's)
+    int* tab = (int*)((char*)scratch + RS.tab);
+    if (ragged_table_build(ragged_cap_table_params(segs, rp, tok_cap, lengths, nullptr, nullptr, tab, status), st)) return 1;
+    const int* rseg = tab + (size_t)B_cap * RAGGED_REC + rp.tiles;
+    return ragged_backward(cfg, segs, rp, RS, tab, rseg, rseg + (size_t)B_cap * FUSED_MAX_SEG, ln_w, ln_b, layers, head, B_cap, d_logits, d_tokens,
+                           saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
 }
 
 }  // extern "C"

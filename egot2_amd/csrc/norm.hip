@@ -481,6 +481,11 @@ __global__ __launch_bounds__(256) void pool_head_ragged_fwd_kernel(const float* 
                                                                    float* __restrict__ pooled, float* __restrict__ out) {
     const int b = blockIdx.x;
     const int* rec = rtab + (size_t)b * RAGGED_REC;
+    if (rec[RG_S] <= 0) {       // an empty clip of a capacity batch (ragged_table.hip): no token to average; a zero row of logits and of token means
+        for (int c = threadIdx.x; c < d; c += 256) pooled[(size_t)b * d + c] = 0.f;
+        for (int o = threadIdx.x; o < (W ? n_out : d); o += 256) out[(size_t)b * (W ? n_out : d) + o] = 0.f;
+        return;
+    }
     pool_head_fwd_clip<PH_MAXD>(tokens + (size_t)rec[RG_TOK0] * d, b, rec[RG_S], d, ln_w, ln_b, eps, W, bias, n_out, pooled, out);
 }
 

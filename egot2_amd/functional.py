@@ -104,7 +104,8 @@ _last_impl = [EGX_IMPL_AUTO]
 _last_slices = [1]
 # last_encoder_impl() of the ragged-batch forward (encoder_ragged): the ragged tiled kernels, or the per-length-group fallback
 IMPL_RAGGED, IMPL_GROUPED = 100, 101
-_IMPL_NAMES = {**{v: k for k, v in IMPL.items()}, IMPL_RAGGED: "ragged", IMPL_GROUPED: "grouped"}
+IMPL_RAGGED_CAP = 102       # encoder_ragged_train with device lengths and a capacity (the capturable form)
+_IMPL_NAMES = {**{v: k for k, v in IMPL.items()}, IMPL_RAGGED: "ragged", IMPL_GROUPED: "grouped", IMPL_RAGGED_CAP: "ragged_cap"}
 
 
 def last_encoder_slices() -> int:
@@ -115,7 +116,7 @@ def last_encoder_slices() -> int:
 
 def last_encoder_impl() -> str:
     """Diagnostic: the implementation the most recent encoder forward ran ("fused" | "wide" | "generic" | ...; "ragged" / "grouped" for
-    encoder_ragged and encoder_ragged_train)."""
+    encoder_ragged and encoder_ragged_train, "ragged_cap" for encoder_ragged_train with device lengths and a capacity)."""
     return _IMPL_NAMES.get(_last_impl[0], "auto")
 
 # EGX_POISON=1 (testing aid): every workspace handed to the library is filled with 0xFF bytes (NaN in fp32 and bf16) first,
@@ -933,6 +934,116 @@ class RaggedEncoderFn(torch.autograd.Function):
         return gr.result(2 if spec.ce else 0)
 
 
+_cap_status: dict = {}
+
+
+def ragged_cap_status_word(device: torch.device) -> torch.Tensor:
+    """The sticky int32 status word (one per device) that capacity-plan ragged calls OR their refusals into when no word of the caller's own
+    is passed (egx_ragged_cap_train_fwd `status`). Created outside any capture: inside one it would live in the graph's private pool."""
+    key = device.index
+    w = _cap_status.get(key)
+    if w is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ragged capacity: run one eager step before capturing (the status word is allocated outside the graph)")
+        w = _cap_status[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return w
+
+
+class RaggedCapEncoderFn(torch.autograd.Function):
+    """RaggedEncoderFn with the batch table built on the device (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd): capturable, one graph for
+    every batch that fits `capacity` = (B_cap, tok_cap). Argument order: spec, lengths (CUDA int32 (B_cap, K); all-zero rows are empty clips),
+    capacity, status (CUDA int32 (1,)), then RaggedEncoderFn's from task_embed on. A head is required. Returns logits (B_cap, n_out) [, loss]."""
+
+    @staticmethod
+    def forward(ctx, spec: EncoderSpec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *rest):
+        lib = _load()
+        feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest)
+        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
+                                                                                      pos_table, feat=_dev_f32)
+        B, tok_cap = capacity
+        device = feats[0].device
+        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
+        layers = _layers(layer_t, spec.n_layers)
+        cfg = _ragged_train_config(spec)
+        sv, sc = C.c_size_t(0), C.c_size_t(0)
+        check(lib.egx_ragged_cap_workspace(C.byref(cfg), segs, B, tok_cap, C.byref(sv), C.byref(sc)))
+        saved = _saved_buffer(any(ctx.needs_input_grad), "saved", device, sv.value)
+        keep = None
+        if spec.ce:
+            loss, ctx.ce_dl, keep = _ce_attach(spec, cfg, tail[0], tail[1], B, device)
+        head = _head(head_t, spec.head_n_out)
+        out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
+        check(lib.egx_ragged_cap_train_fwd(C.byref(cfg), segs, ptr(lengths), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, tok_cap, ptr(out),
+                                           None, ptr(saved), None, ptr(status), int(spec.training), _seed64(spec.seed), _stream()))
+        del keep
+        _last_impl[0] = IMPL_RAGGED_CAP
+        _last_slices[0] = 1
+        ctx.spec, ctx.lengths, ctx.capacity, ctx.status = spec, lengths, (B, tok_cap), status
+        ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
+        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t)
+        if spec.ce:
+            ctx.set_materialize_grads(False)
+            return out, loss
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out, d_loss=None):
+        spec: EncoderSpec = ctx.spec
+        dl_scale = None
+        if spec.ce:
+            up = _ce_upstream(ctx, d_out, d_loss)
+            if up is None:
+                return (None,) * len(ctx.needs_input_grad)
+            d_out, dl_scale = up
+        lib = _load()
+        tensors = _EncArgs.load(ctx)
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, _ = tensors
+        (B, tok_cap), device = ctx.capacity, d_out.device
+        need = ctx.needs_input_grad     # (spec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *rest)
+        if need[5]:
+            raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
+        gr = _EncGrads(spec, need, 8, tensors, device)
+        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
+        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
+        cfg = _ragged_train_config(spec)
+        gr.attach(cfg)
+        if dl_scale is not None:
+            cfg.d_logits_scale = dl_scale.data_ptr()
+        scratch = _workspace("scratch", device, ctx.scratch_bytes)
+        up = _f32c(d_out)
+        head, hg = _head(head_t, spec.head_n_out), gr.head_grads()
+        check(lib.egx_ragged_cap_bwd(C.byref(cfg), segs, ptr(ctx.lengths), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, tok_cap, ptr(up), None,
+                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, C.byref(hg),
+                                     ptr(ctx.status), int(spec.training), _seed64(spec.seed), _stream()))
+        return gr.result(2 if spec.ce else 0)
+
+
+def _encoder_ragged_cap(spec: EncoderSpec, feats, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params,
+                        ce):
+    """encoder_ragged_train with DEVICE lengths: the checks that need no look at the lengths (nothing here synchronises), then
+    RaggedCapEncoderFn. There is no fallback: a configuration the ragged kernels do not cover raises with the library's message."""
+    K = len(spec.segments)
+    if capacity is None or len(capacity) != 2:
+        raise ValueError("device lengths need capacity=(B_cap, tok_cap): the clips and the tokens the captured step is sized for")
+    B_cap, tok_cap = int(capacity[0]), int(capacity[1])
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B_cap, K) or lengths.device != feats[0].device:
+        raise ValueError(f"device lengths must be the ({B_cap}, {K}) int32 tensor of the capacity, on the features' device")
+    if any(f.shape[0] != B_cap for f in feats):
+        raise ValueError(f"the features of a capacity batch are padded to B_cap = {B_cap} clips (train.pad_ragged_batch)")
+    if not head_params:
+        raise ValueError("ragged capacity: a pooled head is required (head-less rows are not supported on the captured path)")
+    if pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled():
+        raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
+    if status is None:
+        status = ragged_cap_status_word(feats[0].device)
+    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != feats[0].device:
+        raise ValueError("status must be a one-element int32 tensor on the features' device")
+    args = [spec, lengths.contiguous(), (B_cap, tok_cap), status, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
+    if ce is not None:
+        args += [ce[0], ce[1]]
+    return RaggedCapEncoderFn.apply(*args)
+
+
 def _ragged_train_refused(spec: EncoderSpec, feats, lengths, task_embed, pos_table, proj, query: str) -> bool:
     """The pre-flight of encoder_ragged_train and encoder_ragged_tokens_train: does the call have to take the grouped path? It does where
     a learned positional table wants a gradient (the ragged kernels produce none) or where the workspace query refuses the configuration
@@ -947,20 +1058,29 @@ def _ragged_train_refused(spec: EncoderSpec, feats, lengths, task_embed, pos_tab
 
 def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: torch.Tensor, task_embed, pos_table, ln_w, ln_b,
                          proj: Sequence[torch.Tensor], layer_params: Sequence[torch.Tensor], head_params: Sequence[torch.Tensor] = (),
-                         ce=None):
+                         ce=None, capacity=None, status=None):
     """Differentiable forward over a batch of clips of their own lengths (training and evaluation): clip b's result is that of the same model
     on clip b alone, unpadded, and every clip keeps all of its frames. feats[k] is padded (B, spec.segments[k].T, d_in); `lengths` the (B, K)
     int32 host tensor of ragged_lengths(). Returns logits (B, n_out) with head_params — or (logits, loss) with ce = (target, class_weight |
     None), the weighted cross entropy over the batch — else the first segment's rows of every clip packed, (sum_b lengths[b, 0], d).
     Runs egx_ragged_train_fwd / egx_ragged_bwd (last_encoder_impl() == "ragged") where the tiled kernels cover the configuration. Elsewhere
     (exact fp32, a forced implementation, deeper stacks, clips beyond 512 tokens) the clips are grouped by their length tuple and each group
-    runs the differentiable batched forward ("grouped"); its dropout masks are keyed per group and differ from the ragged kernels'."""
+    runs the differentiable batched forward ("grouped"); its dropout masks are keyed per group and differ from the ragged kernels'.
+    Capturable form: `lengths` a CUDA int32 (B_cap, K) tensor with capacity = (B_cap, tok_cap) — features, lengths and target padded to
+    B_cap clips (train.pad_ragged_batch; an all-zero row of lengths is an empty clip: a zero row of logits, no part in the loss). The batch
+    table is then built on the device (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd, last_encoder_impl() == "ragged_cap"), nothing reads
+    the lengths on the host, and one captured graph serves every batch with at most tok_cap tokens. A batch that does not fit, or lengths
+    out of range, run as the empty batch and set `status` (int32 (1,), sticky; default ragged_cap_status_word()). A head is required."""
     if spec.token_ce or spec.out_tokens or spec.p_feat:
         raise ValueError("ragged training: no token loss, no out_tokens, no feature dropout")
     if spec.defer_small:
         raise ValueError("ragged training: the staged backward (defer_small) is not supported")
     if (ce is not None) != bool(spec.ce) or (ce is not None and not spec.head_n_out):
         raise ValueError("ce = (target, class_weight) goes with spec.ce and the pooled head")
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        return _encoder_ragged_cap(spec, feats, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
+    if capacity is not None:
+        raise ValueError("capacity= goes with device lengths (a CUDA int32 tensor); host lengths size the call themselves")
     lengths = _check_host_lengths(lengths, feats[0].shape[0], len(spec.segments))
     if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_train_workspace"):
         return _encoder_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)

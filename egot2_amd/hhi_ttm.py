@@ -77,16 +77,48 @@ class _TTMTranslator(TaskFusion3Task, TranslatorMixin):
                                 task_embed=self.task_embed, pos_table=self.pos_embed.pe,
                                 p_drop=self.dp_rate, p_pos=self.pos_embed.dropout.p, head=head, ce=ce, lengths=lengths)
 
-    def _ragged(self, feats, projs, task_ids, lengths, target, class_weight):
+    def _ragged(self, feats, projs, task_ids, lengths, target, class_weight, capacity=None):
         if class_weight is not None and target is None:
             raise ValueError("class_weight goes with target=")
         B = feats[0].shape[0]
-        lens = F_egx.ragged_lengths(lengths, B, [f.shape[1] for f in feats])
+        status = None
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            # the capturable form: nothing looks at the lengths on the host (device ops only; the kernels validate them, ragged_status())
+            if capacity is None:
+                raise ValueError("device lengths need capacity=(B_cap, tok_cap)")
+            lens = lengths if lengths.dim() == 2 else lengths[:, None].expand(B, len(feats))
+            lens = lens.to(torch.int32).contiguous()
+            status = self._ragged_status_word(feats[0].device)
+        else:
+            if capacity is not None:
+                raise ValueError("capacity= goes with device lengths (a CUDA tensor)")
+            lens = F_egx.ragged_lengths(lengths, B, [f.shape[1] for f in feats])
         segs = [SegmentSpec(T=f.shape[1], d_in=f.shape[2], has_proj=True, add_row=k, pos_row0=0) for f, k in zip(feats, task_ids)]
         return self._egx_train_ragged(feats, segs, lens, encoder=self.transformer_encoder, ln=self.ln, projs=projs,
                                       task_embed=self.task_embed, pos_table=self.pos_embed.pe, p_drop=self.dp_rate,
                                       p_pos=self.pos_embed.dropout.p, head=(self.linear_head[0], self.linear_head[1]),
-                                      ce=None if target is None else (target, class_weight))
+                                      ce=None if target is None else (target, class_weight), capacity=capacity, status=status)
+
+    def _ragged_status_word(self, device):
+        w = getattr(self, "_egx_ragged_status", None)
+        if w is None or w.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ragged capacity: run one eager step before capturing (the status word is allocated outside the graph)")
+            w = self._egx_ragged_status = torch.zeros(1, dtype=torch.int32, device=device)
+        return w
+
+    def ragged_status(self, clear: bool = False) -> int:
+        """The sticky status word of this model's capacity-plan ragged steps (forward_features_ragged with device lengths): 0, or the OR of
+        1 (a length outside 0 .. T_pad), 2 (a clip with some segments empty and others not), 4 (a clip beyond 512 tokens), 8 (more tokens
+        than tok_cap) over every step since it was cleared. Such a step ran as the empty batch: zero logits, loss 0, zero gradients. Reading
+        is ONE copy to the host and synchronises: the caller's choice of when, e.g. once per epoch. clear=True zeroes the word after reading."""
+        w = getattr(self, "_egx_ragged_status", None)
+        if w is None:
+            return 0
+        v = int(w.item())
+        if clear:
+            w.zero_()
+        return v
 
     def _head(self, tokens):
         ln, fc = self.linear_head[0], self.linear_head[1]
@@ -116,12 +148,15 @@ class TaskFusionMFTransformer2Task(_TTMTranslator):
         return self._tokens([ttm_out, lam_out], [self.proj_ttm, self.proj_lam], [0, 1], with_head=True,
                             ce=None if target is None else (target, class_weight), lengths=lengths)
 
-    def forward_features_ragged(self, ttm_out, lam_out, lengths, target=None, class_weight=None):
+    def forward_features_ragged(self, ttm_out, lam_out, lengths, target=None, class_weight=None, capacity=None):
         """A batch of clips of their own lengths, differentiable (training and evaluation): features padded to (B, T_max, 256) (padded
         frames are never read), lengths (B,) or (B, 2) frame counts in argument order (ttm, lam). -> (B, 2) logits, each clip's those of the
         clip alone with all of its frames; with target (B,) int64 [, class_weight (2,)] -> (logits, loss), the weighted cross entropy over
-        the batch (functional.encoder_ragged_train)."""
-        return self._ragged([ttm_out, lam_out], [self.proj_ttm, self.proj_lam], [0, 1], lengths, target, class_weight)
+        the batch (functional.encoder_ragged_train).
+        Capturable form (train.GraphedStep, train.pad_ragged_batch): lengths a CUDA tensor with capacity=(B_cap, tok_cap), every input padded
+        to B_cap clips; -> (B_cap, 2) logits with zero rows for empty clips (lengths 0), which take no part in the loss. A batch that does not
+        fit runs as the empty batch and sets ragged_status()."""
+        return self._ragged([ttm_out, lam_out], [self.proj_ttm, self.proj_lam], [0, 1], lengths, target, class_weight, capacity)
 
     def forward(self, video, audio):
         lam_out = self.lam_model(video, middle=True)  # (bs, T, 256)
@@ -153,13 +188,16 @@ class TaskFusionMFTransformer3Task(_TTMTranslator):
         return self._tokens([ttm_out, lam_out, asd_out], [self.proj_ttm, self.proj_lam, self.proj_asd], [0, 1, 2],
                             with_head=True, ce=None if target is None else (target, class_weight), lengths=lengths)
 
-    def forward_features_ragged(self, ttm_out, lam_out, asd_out, lengths, target=None, class_weight=None):
+    def forward_features_ragged(self, ttm_out, lam_out, asd_out, lengths, target=None, class_weight=None, capacity=None):
         """A batch of clips of their own lengths, differentiable (training and evaluation): features padded to (B, T_max, 256) (padded
         frames are never read), lengths (B,) or (B, 3) frame counts in argument order (ttm, lam, asd). -> (B, 2) logits, each clip's those
         of the clip alone with all of its frames; with target (B,) int64 [, class_weight (2,)] -> (logits, loss), the weighted cross
-        entropy over the batch (functional.encoder_ragged_train)."""
+        entropy over the batch (functional.encoder_ragged_train).
+        Capturable form (train.GraphedStep, train.pad_ragged_batch): lengths a CUDA tensor with capacity=(B_cap, tok_cap), every input padded
+        to B_cap clips; -> (B_cap, 2) logits with zero rows for empty clips (lengths 0), which take no part in the loss. A batch that does not
+        fit runs as the empty batch and sets ragged_status()."""
         return self._ragged([ttm_out, lam_out, asd_out], [self.proj_ttm, self.proj_lam, self.proj_asd], [0, 1, 2], lengths, target,
-                            class_weight)
+                            class_weight, capacity)
 
     def forward(self, video, video_asd, audio, audio_asd):
         N, D, H, W = video_asd.shape

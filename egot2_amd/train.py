@@ -1138,6 +1138,43 @@ def construct_solver(model, cfg, steps_in_epoch: int, lr_policy: Optional[str] =
     return opt, schedule
 
 
+def pad_ragged_batch(feats, lengths, target, capacity, T_pad=None):
+    """A sampler batch of B clips -> the fixed shapes of a capacity-plan ragged step (forward_features_ragged(..., lengths=<device tensor>,
+    capacity=)), so that ONE GraphedStep serves every batch: feats[k] (B, T, d_in) -> (B_cap, T_pad[k], d_in) zero-padded, lengths ((B,) or
+    (B, K) frame counts, list or tensor) -> int32 (B_cap, K) with 0 for the unused rows (empty clips), target (B,) -> int64 (B_cap,) with -1
+    there. capacity = (B_cap, tok_cap); T_pad (an int or one per segment; default: each tensor's own T) is the padded frame count the step
+    was captured with. Everything lands on feats[0]'s device. Checked on the host, where the sampler's lengths still are: B <= B_cap,
+    1 <= length <= T_pad and the batch's tokens <= tok_cap."""
+    B_cap, tok_cap = int(capacity[0]), int(capacity[1])
+    K, dev = len(feats), feats[0].device
+    B = feats[0].shape[0]
+    T_pad = [f.shape[1] for f in feats] if T_pad is None else ([int(T_pad)] * K if isinstance(T_pad, int) else [int(t) for t in T_pad])
+    lens = torch.as_tensor(lengths).to("cpu", torch.int64)
+    if lens.dim() == 1:
+        lens = lens[:, None].expand(B, K)
+    if tuple(lens.shape) != (B, K) or len(T_pad) != K:
+        raise ValueError(f"lengths must have shape ({B},) or ({B}, {K}) and T_pad one entry per segment")
+    if B > B_cap:
+        raise ValueError(f"{B} clips in a batch of capacity B_cap = {B_cap}")
+    for k, f in enumerate(feats):
+        if f.shape[0] != B or f.shape[1] > T_pad[k]:
+            raise ValueError(f"feats[{k}] has shape {tuple(f.shape)}: {B} clips of at most T_pad = {T_pad[k]} frames expected")
+        if B and (int(lens[:, k].min()) < 1 or int(lens[:, k].max()) > f.shape[1]):
+            raise ValueError(f"segment {k}: lengths must be 1 .. {f.shape[1]}, the frames feats[{k}] holds")
+    if int(lens.sum()) > tok_cap:
+        raise ValueError(f"the batch has {int(lens.sum())} tokens, the capacity tok_cap = {tok_cap}")
+    out = []
+    for k, f in enumerate(feats):
+        p = torch.zeros((B_cap, T_pad[k], f.shape[2]), dtype=f.dtype, device=dev)
+        p[:B, :f.shape[1]] = f
+        out.append(p)
+    lp = torch.zeros((B_cap, K), dtype=torch.int32)
+    lp[:B] = lens.to(torch.int32)
+    tp = torch.full((B_cap,), -1, dtype=torch.int64)
+    tp[:B] = torch.as_tensor(target).to("cpu", torch.int64)
+    return out, lp.to(dev), tp.to(dev)
+
+
 class GraphedStep:
     """One training step — forward, loss, backward and (optionally) the optimizer update — captured ONCE as a hipGraph and replayed.
 
@@ -1153,7 +1190,9 @@ class GraphedStep:
             loss = step(feats, target)          # copies the batch into the captured buffers, replays, returns the loss tensor (device)
 
     `loss_fn(*inputs)` must be a pure function of its (possibly nested list / tuple of) tensor arguments with FIXED shapes and dtypes: a batch of
-    another shape needs another GraphedStep (the reference's length-bucketed TTM sampler yields a handful of shapes — keep one per shape).
+    another shape needs another GraphedStep (the reference's length-bucketed TTM sampler yields a handful of shapes — keep one per shape, or
+    pad every batch to ONE capacity with pad_ragged_batch and capture forward_features_ragged(..., lengths=<device tensor>, capacity=): the
+    lengths are then data of the step like the features, INTEGRATION.md "Ragged batches in a captured step").
     Gradients stay in `.grad` after every replay (`optimizer=None`: update them yourself outside the graph)."""
 
     def __init__(self, loss_fn, example_inputs, params, optimizer=None, warmup: int = 3):

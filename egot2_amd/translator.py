@@ -177,9 +177,10 @@ class TranslatorMixin:
                                     encoder_layer_tensors(encoder), head_t)
 
     def _egx_train_ragged(self, feats, segments, lengths, *, encoder, ln, projs, task_embed, pos_table, p_drop, p_pos=0.0, head=None,
-                          ce=None):
+                          ce=None, capacity=None, status=None):
         """Ragged batch through the differentiable path (functional.encoder_ragged_train), in train and eval mode, with and without grad.
-        `lengths`: (B, K) int32 host tensor in SEGMENT order (functional.ragged_lengths)."""
+        `lengths`: (B, K) int32 host tensor in SEGMENT order (functional.ragged_lengths) - or, with capacity = (B_cap, tok_cap) and a status
+        word, the (B_cap, K) int32 DEVICE tensor of the capturable form."""
         if self.egx_defer_small:
             raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
         if ce is not None and head is None:
@@ -192,4 +193,4 @@ class TranslatorMixin:
                                               advance_seed=1 if (seed_dev is not None and training) else 0,     # fresh masks per call
                                               deterministic=bool(self.egx_deterministic), ce=ce is not None)
         return F_egx.encoder_ragged_train(spec, list(feats), lengths, task_embed, pos_table, ln.weight, ln.bias, proj_t,
-                                          encoder_layer_tensors(encoder), head_t, ce=ce)
+                                          encoder_layer_tensors(encoder), head_t, ce=ce, capacity=capacity, status=status)

@@ -389,7 +389,7 @@ int egx_ragged_encode_bwd(const egx_config* cfg, const egx_segment* segs, const 
  *              is WRITTEN as the padded (B, segs[k].T, d_in) gradient with exact zeros in the padded frames; pos gradients are refused.
  * Runs on the tiled kernels, limits of egx_ragged_fwd; refused: p_feat > 0, out_tokens, token_ce, bucket_cb, bwd_stage != 0.
  * `saved` / `scratch`: egx_ragged_train_workspace() bytes (functions of sum_b S_b and the tile count, not of B * max S_b). Each call
- * writes the batch table on `stream`: not for graph capture. */
+ * writes the batch table on `stream`: not for graph capture (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd below are). */
 int egx_ragged_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
                                size_t* scratch_bytes);
 int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
@@ -826,6 +826,44 @@ int egx_view_ensemble_update(const float* preds, int ld, int B, int H, const int
                              int slot_bytes, int slot0, int method, int capacity, void* state, void* stream);
 int egx_view_ensemble_topk(int n, int capacity, int H, const int* C, const int* ks, int n_ks, void* state, int* rank, int* pred, void* result,
                            void* stream);
+/* ---- ABI v24 additions (new symbols only, as v19 to v23: EGX_ABI_VERSION stays 18): ragged d = 128 training batches with the batch table
+ * built ON THE DEVICE, so that ONE captured hipGraph serves every batch that fits a declared capacity ------------------------------------
+ * egx_ragged_train_fwd / egx_ragged_bwd read HOST lengths and ship the table in launch arguments: a capture would replay that call's
+ * lengths for ever. The calls below take the lengths from DEVICE memory when the launches RUN and size every grid, workspace offset and
+ * weight-gradient launch by a capacity: B_cap clips, tok_cap tokens, ceil(tok_cap / 48) + B_cap tiles (a bound on sum_b ceil(S_b / 48) of
+ * every batch that fits, which leaves at least (tok_cap - N) / 48 surplus tiles).
+ *   lengths    DEVICE int (B_cap, n_segments). A clip whose lengths are ALL 0 is empty: no tile, no token, a zero row of logits, no part
+ *              in the loss (its label counts as -1, whatever `target` holds) and zero gradient; it may stand anywhere in the batch.
+ *   status     DEVICE uint32, sticky: the table kernel ORs in 1 (a length outside 0 .. segs[k].T), 2 (a clip with some segments empty and
+ *              others not), 4 (a clip beyond 512 tokens), 8 (sum_b S_b > tok_cap). A batch with any of them runs as the EMPTY batch - every
+ *              clip empty, so that no length indexes anything: zero logits, loss 0 and zero gradients (a captured optimizer step sees zero
+ *              gradients). Nothing reads the word or synchronises; the caller looks when it chooses to and clears it itself.
+ *   head       required (the head-less rows, egx_ragged_train_fwd's ASD output, are refused); tokens_out / d_tokens are ignored.
+ *   the rest   as egx_ragged_train_fwd / egx_ragged_bwd, whose refusals carry over (p_feat, out_tokens, token_ce, bucket_cb, bwd_stage,
+ *              learned positional gradients, d = 128 / h = 4 / f32s or bf16). Under capture, train-mode dropout needs egx_config.seed_ptr.
+ *              B_cap <= 2^20, tok_cap <= 2^24, tok_cap >= B_cap * n_segments.
+ * Results: a clip's logits and d(feature) rows are those of egx_ragged_train_fwd / egx_ragged_bwd on the same clips (the table is the same,
+ * word for word); the loss and the weight gradients are the same fixed-order sums regrouped over capacity-sized ranges (the launches run
+ * over tok_cap rows; the rows no clip owns are cleared first and add exact zeros). Bit-reproducible from replay to replay.
+ * egx_ragged_cap_workspace: `saved` / `scratch` bytes, functions of the capacity alone (pure host arithmetic).
+ * egx_ragged_cap_table: the table kernel alone (tests, diagnostics): table = B_cap records of 16 ints | tile -> clip map of the tile
+ *              capacity, -1 for surplus tiles | B_cap * 4 packed first rows | 8 totals (tokens, tiles, any clip, rows of segment 0 .. 3,
+ *              status bits of this build); eff_target (B_cap) int64 or NULL. table NULL: only *n_words (host only).
+ * egx_ragged_table_host: the table egx_ragged_train_fwd (train != 0: with the packed first rows) or egx_ragged_fwd builds on the host for
+ *              a batch with a head, without any device work: B records | tile -> clip map | B * 4 packed first rows. out_words NULL: only
+ *              *n_words. */
+int egx_ragged_table_host(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int train, int* out_words, size_t* n_words);
+int egx_ragged_cap_workspace(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, size_t* saved_bytes, size_t* scratch_bytes);
+int egx_ragged_cap_table(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, const int* lengths, const int64_t* target,
+                         int* table, int64_t* eff_target, unsigned* status, size_t* n_words, void* stream);
+int egx_ragged_cap_train_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                             const egx_layer* layers, const egx_head* head, int B_cap, int tok_cap, float* logits_out, float* tokens_out,
+                             void* saved, void* scratch, unsigned* status, int training, uint64_t seed, void* stream);
+int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
+                       const egx_layer* layers, const egx_head* head, int B_cap, int tok_cap, const float* d_logits, const float* d_tokens,
+                       const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b,
+                       const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, unsigned* status, int training, uint64_t seed,
+                       void* stream);
 /* ---- EgoT2-g sequence decoder + vocabulary head --------------------------------------------
  * decode() of HHI/models/multitask/task_prompt_model.py:260-269 and HOI/models/multitask/video_model_builder.py:150-159:
  * embedding * sqrt(d) + positional encoding -> nn.TransformerDecoder of CustomDecoderLayer (causal self-attention over
