@@ -107,6 +107,34 @@ class DecLayerGrads(C.Structure):
     _fields_ = [(n, _fp) for n in _DEC_LAYER_FIELDS]
 
 
+class WideGemmArgs(C.Structure):
+    """egx_wide_gemm_args: WideGemmParams in full (egx_wide_gemm_ex / egx_wide_gemm_tn_batch)."""
+    _fields_ = [("layout", C.c_int), ("A", _fp), ("B", _fp), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldb", C.c_int),
+                ("Cf", _fp), ("Cb", _fp), ("ldc", C.c_int), ("bias", _fp), ("relu", C.c_int), ("p_drop", C.c_float), ("seed", C.c_uint64),
+                ("layer", C.c_uint32), ("site", C.c_uint32), ("residual", _fp), ("ldr", C.c_int), ("mask", _fp), ("ldm", C.c_int),
+                ("mask_scale", C.c_float), ("colsum", _fp), ("accumulate", C.c_int), ("tn_queue", C.c_int), ("tn_defer", C.c_int), ("scratch", _fp)]
+
+
+class WideLnFwdArgs(C.Structure):
+    """egx_wide_ln_fwd_args (egx_wide_layernorm_fwd)."""
+    _fields_ = [("x", _fp), ("w", _fp), ("b", _fp), ("eps", C.c_float), ("stats", _fp), ("y32", _fp), ("y16", _fp), ("rows", C.c_int), ("d", C.c_int),
+                ("T", C.c_int), ("S", C.c_int), ("off", C.c_int), ("add_vec", _fp), ("pos", _fp), ("pos_stride", C.c_int), ("p_drop", C.c_float),
+                ("seed", C.c_uint64), ("layer", C.c_uint32), ("site", C.c_uint32), ("out_map", _fp), ("src_map", _fp)]
+
+
+class WideLnBwdArgs(C.Structure):
+    """egx_wide_ln_bwd_args (egx_wide_layernorm_bwd)."""
+    _fields_ = [("dy", _fp), ("pre", _fp), ("stats", _fp), ("w", _fp), ("dx32", _fp), ("dx16", _fp), ("rows", C.c_int), ("d", C.c_int), ("T", C.c_int),
+                ("S", C.c_int), ("off", C.c_int), ("p_drop", C.c_float), ("seed", C.c_uint64), ("layer", C.c_uint32), ("site", C.c_uint32),
+                ("p_out", C.c_float), ("out_layer", C.c_uint32), ("out_site", C.c_uint32), ("mask_dx32", C.c_int), ("dw", _fp), ("db", _fp),
+                ("dbias", _fp), ("dadd", _fp), ("dy_map", _fp), ("defer", C.c_int), ("scratch", _fp)]
+
+
+class WideColsumArgs(C.Structure):
+    """egx_wide_colsum_args (egx_wide_row_reduce_batch)."""
+    _fields_ = [("x", _fp), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int), ("out", _fp), ("scratch", _fp)]
+
+
 # symbol -> (restype, argtypes); every symbol include/egot2x.h declares
 SIGNATURES = {
     "egx_abi_version": (C.c_int, []),
@@ -122,6 +150,21 @@ SIGNATURES = {
     "egx_encoder_slices": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int]),
     "egx_wide_gemm_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "egx_wide_gemm": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
+    # ABI v25: unit hooks of the wide bf16 path
+    "egx_wide_gemm_ex": (C.c_int, [C.POINTER(WideGemmArgs), _fp]),
+    "egx_wide_gemm_tn_batch": (C.c_int, [C.POINTER(WideGemmArgs), C.c_int, _fp]),
+    "egx_wide_gemm_colsum_rows": (C.c_int, [C.c_int, C.c_int]),
+    "egx_wide_gemm_variant": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "egx_wide_layernorm_fwd": (C.c_int, [C.POINTER(WideLnFwdArgs), _fp]),
+    "egx_wide_layernorm_bwd_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "egx_wide_layernorm_bwd": (C.c_int, [C.POINTER(WideLnBwdArgs), _fp]),
+    "egx_wide_colsum_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "egx_wide_colsum": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "egx_wide_row_reduce_batch": (C.c_int, [C.POINTER(WideLnBwdArgs), C.c_int, C.POINTER(WideColsumArgs), C.c_int, _fp]),
+    "egx_wide_pos_grad_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "egx_wide_pos_grad": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
+                                    C.c_uint32, _fp, _fp]),
+    "egx_wide_cast": (C.c_int, [C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "egx_wide_attention_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
     "egx_wide_attention_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
     "egx_encoder_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.c_int,

@@ -270,6 +270,178 @@ int egx_wide_attention_bwd(const void* qkv, const void* out, const float* lse, c
     return wide_attn_hook(qkv, const_cast<void*>(out), const_cast<float*>(lse), d_out, d_qkv, delta, B, S, H, d, p_drop, seed, stream, true);
 }
 
+// ABI v25: every kernel of the wide path on its own. The hooks check their arguments, fill the production parameter structs and call the
+// production functions; the dropout triple is the one wide_host.hip's mkdrop forms from a host seed.
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int hook_drop(const char* who, float p, uint64_t seed, uint32_t layer, uint32_t site, uint64_t* key, uint32_t* thresh, float* inv) {
+    EGX_CHECK(p >= 0.f && p <= 1.f, "%s: dropout probability %g outside [0, 1]", who, (double)p);
+    *key = 0; *thresh = 0; *inv = 1.f;
+    if (p > 0.f) { *key = site_key(seed, layer, site); *thresh = drop_threshold(p); *inv = p < 1.f ? 1.f / (1.f - p) : 0.f; }
+    return 0;
+}
+static int wide_gemm_fill(const egx_wide_gemm_args* a, WideGemmParams& g) {
+    EGX_CHECK(a, "egx_wide_gemm_ex: null arguments");
+    EGX_CHECK(a->layout == 0 || a->layout == 2, "egx_wide_gemm_ex: layout %d (0 = NT, 2 = TN)", a->layout);
+    EGX_CHECK(a->A && a->B && a->scratch, "egx_wide_gemm_ex: null operand or scratch");
+    EGX_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "egx_wide_gemm_ex: empty problem %dx%dx%d", a->M, a->N, a->K);
+    EGX_CHECK(al16(a->A) && al16(a->B) && al16(a->Cf) && al16(a->Cb) && al16(a->bias) && al16(a->residual) && al16(a->mask) && al16(a->colsum) &&
+              al16(a->scratch), "egx_wide_gemm_ex: pointers must be 16-byte aligned");
+    EGX_CHECK(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0 && a->ldc >= a->N, "egx_wide_gemm_ex: lda %d, ldb %d (multiples of 8), ldc %d (multiple of 4, >= N)",
+              a->lda, a->ldb, a->ldc);
+    if (a->layout == 0) {
+        EGX_CHECK(a->Cf || a->Cb, "egx_wide_gemm_ex: NT needs Cf or Cb");
+        EGX_CHECK(a->K % 64 == 0 && a->N % 4 == 0, "egx_wide_gemm_ex: NT %dx%dx%d needs K %% 64 == 0 and N %% 4 == 0", a->M, a->N, a->K);
+        EGX_CHECK(a->lda >= a->K && a->ldb >= a->K, "egx_wide_gemm_ex: NT lda %d, ldb %d below K", a->lda, a->ldb);
+        EGX_CHECK(!a->residual || (a->ldr >= a->N && a->ldr % 4 == 0), "egx_wide_gemm_ex: ldr %d (multiple of 4, >= N)", a->ldr);
+        EGX_CHECK(!a->mask || (a->ldm >= a->N && a->ldm % 4 == 0), "egx_wide_gemm_ex: ldm %d (multiple of 4, >= N)", a->ldm);
+        EGX_CHECK(!a->accumulate && !a->tn_queue && !a->tn_defer, "egx_wide_gemm_ex: accumulate / tn_queue / tn_defer are TN switches");
+    } else {
+        EGX_CHECK(a->Cf && !a->Cb, "egx_wide_gemm_ex: TN writes Cf only");
+        EGX_CHECK(a->M % 128 == 0 && a->N % 128 == 0, "egx_wide_gemm_ex: TN %dx%dx%d needs M, N multiples of 128", a->M, a->N, a->K);
+        EGX_CHECK(a->lda >= a->M && a->ldb >= a->N, "egx_wide_gemm_ex: TN lda %d below M or ldb %d below N", a->lda, a->ldb);
+        EGX_CHECK(!a->bias && !a->relu && a->p_drop == 0.f && !a->residual && !a->mask && !a->colsum, "egx_wide_gemm_ex: TN has no epilogue");
+    }
+    g.A = (const bf16_t*)a->A; g.B = (const bf16_t*)a->B; g.M = a->M; g.N = a->N; g.K = a->K; g.lda = a->lda; g.ldb = a->ldb;
+    g.Cf = a->Cf; g.Cb = (bf16_t*)a->Cb; g.ldc = a->ldc; g.bias = a->bias; g.relu = a->relu;
+    if (hook_drop("egx_wide_gemm_ex", a->p_drop, a->seed, a->layer, a->site, &g.drop_key, &g.drop_thresh, &g.drop_inv)) return 1;
+    g.residual = a->residual; g.ldr = a->ldr; g.mask = (const bf16_t*)a->mask; g.ldm = a->ldm; g.mask_scale = a->mask_scale;
+    g.colsum = a->colsum; g.accumulate = a->accumulate; g.zero_page = a->scratch;
+    return 0;
+}
+int egx_wide_gemm_tn_batch(const egx_wide_gemm_args* args, int n, void* stream) {
+    EGX_CHECK(args && n >= 1 && n <= 32, "egx_wide_gemm_tn_batch: %d problems (1 .. 32)", n);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<WideGemmParams> g(n);
+    for (int i = 0; i < n; ++i) {
+        if (wide_gemm_fill(args + i, g[i])) return 1;
+        EGX_CHECK(args[i].layout == 2, "egx_wide_gemm_tn_batch: problem %d is not TN", i);
+    }
+    WideTnQueue Q;
+    WideReduceBatch red;
+    for (int i = 0; i < n; ++i) {
+        EGX_HIP(hipMemsetAsync(args[i].scratch, 0, 1024, st));
+        void* slabs = (char*)args[i].scratch + 1024;
+        if (args[i].tn_queue ? wide_tn_queue_add(Q, g[i], slabs, st, &red) : wide_gemm_tn(g[i], slabs, st, args[i].tn_defer ? &red : nullptr)) return 1;
+    }
+    if (wide_tn_queue_flush(Q, st)) return 1;
+    return wide_reduce_flush(red, st);
+}
+int egx_wide_gemm_ex(const egx_wide_gemm_args* args, void* stream) {
+    WideGemmParams g;
+    if (wide_gemm_fill(args, g)) return 1;
+    if (args->layout == 2) return egx_wide_gemm_tn_batch(args, 1, stream);
+    EGX_HIP(hipMemsetAsync(args->scratch, 0, 1024, (hipStream_t)stream));
+    return wide_gemm_nt(g, (hipStream_t)stream);
+}
+int egx_wide_gemm_colsum_rows(int M, int N) { return M > 0 && N > 0 ? wide_gemm_nt_colsum_rows(M, N) : 0; }
+int egx_wide_gemm_variant(int layout, int M, int N, int K, int colsum) {
+    if (M <= 0 || N <= 0 || K <= 0) return -1;
+    if (layout == 0) return K % 64 == 0 && N % 4 == 0 ? wide_gemm_nt_launch(M, N, colsum != 0) : -1;
+    return layout == 2 ? wide_gemm_tn_launch(M, N, K) : -1;
+}
+
+int egx_wide_layernorm_fwd(const egx_wide_ln_fwd_args* a, void* stream) {
+    EGX_CHECK(a, "egx_wide_layernorm_fwd: null arguments");
+    EGX_CHECK(a->x && a->w && a->b && (a->y32 || a->y16), "egx_wide_layernorm_fwd: null pointer");
+    EGX_CHECK(a->rows >= 0 && a->d > 0 && a->d % 4 == 0 && a->d <= (a->out_map ? 1024 : 2048), "egx_wide_layernorm_fwd: d=%d unsupported (multiple of 4, <= %d)",
+              a->d, a->out_map ? 1024 : 2048);
+    EGX_CHECK(al16(a->x) && al16(a->w) && al16(a->b) && al16(a->y32) && al16(a->y16) && al16(a->add_vec) && al16(a->pos) && ((uintptr_t)a->stats & 7) == 0,
+              "egx_wide_layernorm_fwd: pointers must be 16-byte aligned");
+    EGX_CHECK(a->T >= 1 && a->S >= 1 && (a->out_map || (a->off >= 0 && a->off + a->T <= a->S)), "egx_wide_layernorm_fwd: T=%d, S=%d, off=%d", a->T, a->S, a->off);
+    EGX_CHECK(!a->pos || (a->pos_stride >= a->d && a->pos_stride % 4 == 0), "egx_wide_layernorm_fwd: pos_stride %d (multiple of 4, >= d)", a->pos_stride);
+    EGX_CHECK(a->out_map || !a->src_map, "egx_wide_layernorm_fwd: src_map without out_map");
+    WideLnFwdParams p;
+    p.x = a->x; p.w = a->w; p.b = a->b; p.eps = a->eps; p.stats = a->stats; p.y32 = a->y32; p.y16 = (bf16_t*)a->y16;
+    p.rows = a->rows; p.d = a->d; p.T = a->T; p.S = a->S; p.off = a->off; p.add_vec = a->add_vec; p.pos = a->pos; p.pos_stride = a->pos_stride;
+    if (hook_drop("egx_wide_layernorm_fwd", a->p_drop, a->seed, a->layer, a->site, &p.drop_key, &p.drop_thresh, &p.drop_inv)) return 1;
+    p.out_map = a->out_map; p.src_map = a->src_map;
+    return a->out_map ? wide_ln_fwd_mapped(p, (hipStream_t)stream) : wide_ln_fwd(p, (hipStream_t)stream);
+}
+size_t egx_wide_layernorm_bwd_scratch(int rows, int d) { return rows > 0 && d > 0 ? wide_ln_bwd_scratch(rows, d) : 0; }
+static int ln_bwd_fill(const egx_wide_ln_bwd_args* a, WideLnBwdParams& p) {
+    EGX_CHECK(a, "egx_wide_layernorm_bwd: null arguments");
+    EGX_CHECK(a->dy && a->pre && a->stats && a->w && a->scratch, "egx_wide_layernorm_bwd: null pointer");
+    EGX_CHECK(a->rows >= 0 && a->d > 0 && a->d % 4 == 0 && a->d <= (a->dy_map ? 1024 : 2048), "egx_wide_layernorm_bwd: d=%d unsupported (multiple of 4, <= %d)",
+              a->d, a->dy_map ? 1024 : 2048);
+    EGX_CHECK(al16(a->dy) && al16(a->pre) && al16(a->w) && al16(a->dx32) && al16(a->dx16) && al16(a->scratch) && ((uintptr_t)a->stats & 7) == 0,
+              "egx_wide_layernorm_bwd: pointers must be 16-byte aligned");
+    EGX_CHECK(a->T >= 1 && a->S >= 1 && (a->dy_map || (a->off >= 0 && a->off + a->T <= a->S)), "egx_wide_layernorm_bwd: T=%d, S=%d, off=%d", a->T, a->S, a->off);
+    EGX_CHECK(!a->defer || !a->dy_map, "egx_wide_layernorm_bwd: the mapped form never defers its reduction");
+    p.dy = a->dy; p.pre = a->pre; p.stats = a->stats; p.w = a->w; p.dx32 = a->dx32; p.dx16 = (bf16_t*)a->dx16;
+    p.rows = a->rows; p.d = a->d; p.T = a->T; p.S = a->S; p.off = a->off;
+    if (hook_drop("egx_wide_layernorm_bwd", a->p_drop, a->seed, a->layer, a->site, &p.drop_key, &p.drop_thresh, &p.drop_inv)) return 1;
+    if (hook_drop("egx_wide_layernorm_bwd", a->p_out, a->seed, a->out_layer, a->out_site, &p.out_key, &p.out_thresh, &p.out_inv)) return 1;
+    p.mask_dx32 = a->mask_dx32; p.dw = a->dw; p.db = a->db; p.dbias = a->dbias; p.dadd = a->dadd; p.dy_map = a->dy_map;
+    return 0;
+}
+static int colsum_args_ok(const void* x, int rows, int cols, int ld, const float* out, const void* scratch) {
+    EGX_CHECK(x && out && scratch, "egx_wide_colsum: null pointer");
+    EGX_CHECK(rows >= 0 && cols > 0 && cols % 8 == 0 && ld % 8 == 0 && ld >= cols, "egx_wide_colsum: %dx%d, ld %d (cols, ld multiples of 8, ld >= cols)", rows, cols, ld);
+    EGX_CHECK(al16(x) && al16(scratch), "egx_wide_colsum: pointers must be 16-byte aligned");
+    return 0;
+}
+int egx_wide_row_reduce_batch(const egx_wide_ln_bwd_args* ln, int n_ln, const egx_wide_colsum_args* cs, int n_cs, void* stream) {
+    EGX_CHECK(n_ln >= 0 && n_cs >= 0 && n_ln + n_cs >= 1 && n_ln + n_cs <= WIDE_ROWRED_MAX && (ln || !n_ln) && (cs || !n_cs),
+              "egx_wide_row_reduce_batch: %d + %d reductions (1 .. %d)", n_ln, n_cs, WIDE_ROWRED_MAX);
+    std::vector<WideLnBwdParams> p(n_ln);
+    for (int i = 0; i < n_ln; ++i) {
+        if (ln_bwd_fill(ln + i, p[i])) return 1;
+        EGX_CHECK(!ln[i].dy_map, "egx_wide_row_reduce_batch: the mapped LayerNorm backward never defers its reduction");
+    }
+    for (int i = 0; i < n_cs; ++i)
+        if (colsum_args_ok(cs[i].x, cs[i].rows, cs[i].cols, cs[i].ld, cs[i].out, cs[i].scratch)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    WideRowReduceBatch red;
+    for (int i = 0; i < n_ln; ++i)
+        if (wide_ln_bwd(p[i], ln[i].scratch, st, &red)) return 1;
+    for (int i = 0; i < n_cs; ++i)
+        if (wide_colsum_bf16((const bf16_t*)cs[i].x, cs[i].rows, cs[i].cols, cs[i].ld, cs[i].out, cs[i].scratch, st, &red)) return 1;
+    return wide_row_reduce_flush(red, st);
+}
+int egx_wide_layernorm_bwd(const egx_wide_ln_bwd_args* a, void* stream) {
+    WideLnBwdParams p;
+    if (ln_bwd_fill(a, p)) return 1;
+    if (a->dy_map) return wide_ln_bwd_mapped(p, a->scratch, (hipStream_t)stream);
+    if (!a->defer) return wide_ln_bwd(p, a->scratch, (hipStream_t)stream);
+    return egx_wide_row_reduce_batch(a, 1, nullptr, 0, stream);
+}
+
+size_t egx_wide_colsum_scratch(int rows, int cols) { return rows > 0 && cols > 0 ? wide_colsum_scratch(rows, cols) : 0; }
+int egx_wide_colsum(const void* x, int rows, int cols, int ld, float* out, int defer, void* scratch, void* stream) {
+    if (colsum_args_ok(x, rows, cols, ld, out, scratch)) return 1;
+    if (!defer) return wide_colsum_bf16((const bf16_t*)x, rows, cols, ld, out, scratch, (hipStream_t)stream);
+    const egx_wide_colsum_args one = {x, rows, cols, ld, out, scratch};
+    return egx_wide_row_reduce_batch(nullptr, 0, &one, 1, stream);
+}
+size_t egx_wide_pos_grad_scratch(int B, int T, int d) { return B > 0 && T > 0 && d > 0 ? wide_pos_grad_scratch(B, T, d) : 0; }
+int egx_wide_pos_grad(const float* dtok, int B, int S, int off, int T, int d, float* dpos, int pos_stride, float p_drop, uint64_t seed,
+                      uint32_t layer, uint32_t site, void* scratch, void* stream) {
+    EGX_CHECK(dtok && dpos && scratch, "egx_wide_pos_grad: null pointer");
+    EGX_CHECK(B >= 1 && T >= 1 && off >= 0 && off + T <= S && d > 0 && d % 4 == 0 && pos_stride >= d, "egx_wide_pos_grad: B=%d, S=%d, off=%d, T=%d, d=%d, pos_stride=%d",
+              B, S, off, T, d, pos_stride);
+    EGX_CHECK(al16(dtok) && al16(scratch), "egx_wide_pos_grad: pointers must be 16-byte aligned");
+    uint64_t key; uint32_t thresh; float inv;
+    if (hook_drop("egx_wide_pos_grad", p_drop, seed, layer, site, &key, &thresh, &inv)) return 1;
+    return wide_pos_grad(dtok, B, S, off, T, d, dpos, pos_stride, key, thresh, inv, scratch, (hipStream_t)stream);
+}
+int egx_wide_cast(int mode, const void* src, int src_bf16, const int* rows, int R, int C, int ld, int pool, void* dst, void* dst_t, void* stream) {
+    EGX_CHECK(mode >= 0 && mode <= 2, "egx_wide_cast: mode %d (0 = plain / transposed, 1 = pooled, 2 = gathered)", mode);
+    EGX_CHECK(src && (dst || (mode == 0 && dst_t)), "egx_wide_cast: null pointer");
+    EGX_CHECK(R >= 0 && C > 0 && al16(src) && al16(dst) && al16(dst_t), "egx_wide_cast: %dx%d, pointers must be 16-byte aligned", R, C);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0) {
+        EGX_CHECK(!src_bf16 && C % 4 == 0 && ld % 4 == 0 && ld >= C && (!dst_t || R % 4 == 0), "egx_wide_cast: %dx%d, ld %d: fp32 source, multiples of 4", R, C, ld);
+        return wide_cast((const float*)src, R, C, ld, (bf16_t*)dst, (bf16_t*)dst_t, st);
+    }
+    EGX_CHECK(C % 8 == 0 && !dst_t, "egx_wide_cast: pooled / gathered need C %% 8 == 0 and have no transposed output");
+    if (mode == 1) {
+        EGX_CHECK(pool >= 1, "egx_wide_cast: pool %d", pool);
+        return wide_pool_cast(src, src_bf16, R, pool, C, (bf16_t*)dst, st);
+    }
+    EGX_CHECK(rows, "egx_wide_cast: gathered needs the row list");
+    return wide_gather_cast(src, src_bf16, rows, R, C, (bf16_t*)dst, st);
+}
+
 int egx_encoder_workspace(const egx_config* cfg, const egx_segment* segs, int B, size_t* saved_bytes, size_t* scratch_bytes) {
     Plan pl;
     if (make_plan(cfg, segs, B, pl)) return 1;

@@ -33,6 +33,11 @@ struct WideGemmParams {
 size_t wide_gemm_tn_scratch(int M, int N, int K);
 int wide_gemm_nt(const WideGemmParams& p, hipStream_t st);
 int wide_gemm_nt_colsum_rows(int M, int N);     // rows of WideGemmParams::colsum written for an (M, N) output
+// the launch wide_gemm_nt picks for an (M, N) output (with / without column sums), and what wide_gemm_tn / wide_tn_queue_add pick:
+// the tile variant (2 = 256 x 256, 1 = 256 x 128, 0 = 128 x 128) in the low byte, the split-K count above it
+enum { WIDE_NT_64X64 = 0, WIDE_NT_128_D4 = 1, WIDE_NT_128_D2 = 2, WIDE_NT_256X128 = 3, WIDE_NT_PP256 = 4, WIDE_NT_PP192 = 5 };
+int wide_gemm_nt_launch(int M, int N, bool colsum);
+int wide_gemm_tn_launch(int M, int N, int K);
 // `defer`: do not launch the slab reduction, queue it (then `scratch` must be a region of its own, wide_gemm_tn_scratch bytes,
 // untouched until wide_reduce_flush() has run)
 struct WideReduceDesc { const float* slabs; float* C; size_t stride; int splits, ldc, M, N, accumulate, first_block, blocks; };

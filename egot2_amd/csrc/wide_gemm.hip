@@ -657,6 +657,33 @@ int wide_gemm_nt_colsum_rows(int M, int N) { return nt_variant(M, N) ? cdiv(M, 2
 // WideGemmParams::epi_lds as every launch passes it: the epilogues go through LDS always (the kernels still decode 0 = accumulator-layout stores and
 // 1 = through LDS without mask / column sums)
 constexpr int EPI_LDS_ALWAYS = 2;
+// the launch of an (M, N) output: wide_gemm_nt runs it, the unit hooks report it (egx_wide_gemm_variant)
+int wide_gemm_nt_launch(int M, int N, bool colsum) {
+    const int v = nt_variant(M, N);
+    if (v == 3) {
+        // 256 x 192 tiles when they fill the last round better (cost = rounds x tile width): N = 768 is 1.5 rounds of 256-column
+        // tiles (2 rounds of time) or exactly 2 rounds of 192-column tiles (1.5).
+        if (!colsum && N % 192 == 0) {
+            const long tm = cdiv(M, 256);
+            const long c256 = cdiv(tm * cdiv(N, 256), 256) * 256, c192 = cdiv(tm * cdiv(N, 192), 256) * 192;
+            if (c192 * 5 <= c256 * 4) return WIDE_NT_PP192;       // a 192-column tile costs ~0.87, not 0.75, of a 256-column one (measured: N = 2304, 0.9 of the rounds x width, lost 9 %)
+        }
+        return WIDE_NT_PP256;
+    }
+    // 256-row tiles (8 waves, 3-stage ring) once they fill the chip twice over; 128-row tiles (4 waves) below
+    if (v == 1) return WIDE_NT_256X128;
+    // 128 x 128 tiles: two workgroups per CU with two stages each once the tiles outnumber the CUs; a launch that cannot
+    // give every CU a second workgroup anyway (the decoder's B * sy <= 2048 target rows: 16-64 tiles) runs four stages deep,
+    // so that a K step costs a third of a memory round trip instead of a whole one
+    const long tiles = (long)cdiv(M, 128) * cdiv(N, 128);
+    // at most one 128 x 128 tile per CU (the decoder's projections of its B * sy target rows: 16-64 tiles; the d = 256 encoder
+    // of the HHI EgoT2-g: 180): 64 x 64 tiles, four waves of 16 x 64 and four stages, put four times as many workgroups on a GEMM
+    // whose duration is a chain of memory round trips, not MFMA time. Same-box sweep of the threshold (64 / 128 / 256 tiles):
+    // C5 HOI 4.02 / 3.98 / 3.99 ms, C5 HHI 2.51 / 2.52 / 2.43 ms, C4 unchanged; without the variant 4.32 / 2.78 ms.
+    // (the column-sum epilogue needs 64-row waves: those launches keep the 128 x 128 tiles)
+    if (tiles <= 256 && !colsum) return WIDE_NT_64X64;
+    return tiles <= 256 ? WIDE_NT_128_D4 : WIDE_NT_128_D2;
+}
 int wide_gemm_nt(const WideGemmParams& p_in, hipStream_t st) {
     WideGemmParams p = p_in;
     p.epi_lds = EPI_LDS_ALWAYS;
@@ -664,30 +691,14 @@ int wide_gemm_nt(const WideGemmParams& p_in, hipStream_t st) {
     EGX_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "wide_gemm_nt: empty problem %dx%dx%d", p.M, p.N, p.K);
     EGX_CHECK(p.K % TBK == 0 && p.N % 4 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.ldc % 4 == 0,
               "wide_gemm_nt: %dx%dx%d needs K %% 64 == 0, N %% 4 == 0, 16-byte aligned rows", p.M, p.N, p.K);
-    const int v = nt_variant(p.M, p.N);
-    if (v == 3) {
-        // 256 x 192 tiles when they fill the last round better (cost = rounds x tile width): N = 768 is 1.5 rounds of 256-column
-        // tiles (2 rounds of time) or exactly 2 rounds of 192-column tiles (1.5).
-        if (!p.colsum && p.N % 192 == 0) {
-            const long tm = cdiv(p.M, 256);
-            const long c256 = cdiv(tm * cdiv(p.N, 256), 256) * 256, c192 = cdiv(tm * cdiv(p.N, 192), 256) * 192;
-            if (c192 * 5 <= c256 * 4) return launch_nt_pp<3>(p, st);       // a 192-column tile costs ~0.87, not 0.75, of a 256-column one (measured: N = 2304, 0.9 of the rounds x width, lost 9 %)
-        }
-        return launch_nt_pp<4>(p, st);
+    switch (wide_gemm_nt_launch(p.M, p.N, p.colsum != nullptr)) {
+        case WIDE_NT_PP192: return launch_nt_pp<3>(p, st);
+        case WIDE_NT_PP256: return launch_nt_pp<4>(p, st);
+        case WIDE_NT_256X128: return launch_nt<256, 128, 64, 3>(p, st);
+        case WIDE_NT_64X64: return launch_nt<64, 64, 16, 4>(p, st);
+        case WIDE_NT_128_D4: return launch_nt<128, 128, 64, 4>(p, st);
+        default: return launch_nt<128, 128, 64, 2>(p, st);
     }
-    // 256-row tiles (8 waves, 3-stage ring) once they fill the chip twice over; 128-row tiles (4 waves) below
-    if (v == 1) return launch_nt<256, 128, 64, 3>(p, st);
-    // 128 x 128 tiles: two workgroups per CU with two stages each once the tiles outnumber the CUs; a launch that cannot
-    // give every CU a second workgroup anyway (the decoder's B * sy <= 2048 target rows: 16-64 tiles) runs four stages deep,
-    // so that a K step costs a third of a memory round trip instead of a whole one
-    const long tiles = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
-    // at most one 128 x 128 tile per CU (the decoder's projections of its B * sy target rows: 16-64 tiles; the d = 256 encoder
-    // of the HHI EgoT2-g: 180): 64 x 64 tiles, four waves of 16 x 64 and four stages, put four times as many workgroups on a GEMM
-    // whose duration is a chain of memory round trips, not MFMA time. Same-box sweep of the threshold (64 / 128 / 256 tiles):
-    // C5 HOI 4.02 / 3.98 / 3.99 ms, C5 HHI 2.51 / 2.52 / 2.43 ms, C4 unchanged; without the variant 4.32 / 2.78 ms.
-    // (the column-sum epilogue needs 64-row waves: those launches keep the 128 x 128 tiles)
-    if (tiles <= 256 && !p.colsum) return launch_nt<64, 64, 16, 4>(p, st);
-    return tiles <= 256 ? launch_nt<128, 128, 64, 4>(p, st) : launch_nt<128, 128, 64, 2>(p, st);
 }
 
 // ---- TN ---------------------------------------------------------------------------------------------------------------
@@ -914,6 +925,10 @@ static int tn_splits(int M, int N, int K, int* kps_out) {
 size_t wide_gemm_tn_scratch(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     return (size_t)tn_splits(M, N, K, nullptr) * M * N * sizeof(float);
+}
+int wide_gemm_tn_launch(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0 || M % TBM || N % TBN) return -1;
+    return tn_variant(M, N) | tn_splits(M, N, K, nullptr) << 8;
 }
 
 // by_slice as every launch passes it: the workgroups of one token slice are consecutive, so an XCD's share of them re-reads one slice of the

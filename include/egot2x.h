@@ -470,6 +470,90 @@ int egx_wide_attention_fwd(const void* qkv, void* out, float* lse, int B, int S,
                            void* stream);
 int egx_wide_attention_bwd(const void* qkv, const void* out, const float* lse, const void* d_out, void* d_qkv, float* delta,
                            int B, int S, int H, int d, float p_drop, uint64_t seed, void* stream);
+/* ---- ABI v25 additions (new symbols only, as v19 to v24: EGX_ABI_VERSION stays 18): every kernel of the wide bf16 path on its own -------
+ * Each hook fills the parameter struct the encoder / decoder drivers fill and calls the function they call (wide_gemm_nt, wide_gemm_tn,
+ * wide_tn_queue_add / _flush, wide_reduce_flush, wide_ln_fwd / _bwd and their _mapped forms, wide_row_reduce_flush, wide_colsum_bf16,
+ * wide_pos_grad, wide_cast, wide_pool_cast, wide_gather_cast): no arithmetic of their own. Dropout is given as (p, seed, layer, site) and
+ * keyed as the drivers key it: site_key(seed, layer, site), threshold and 1 / (1 - p) of p (sites: 1 FEAT, 2 POS, 3 ATTN, 4 RES1, 5 FFN,
+ * 6 RES2). Bad arguments (null pointers, pointers that are not 16-byte aligned, leading dimensions below the width or unaligned, K % 64
+ * for NT, M / N % 128 for TN, d % 4 or d > 2048, ...) are refused before anything is enqueued.
+ *
+ * egx_wide_gemm_ex: WideGemmParams in full.
+ *   NT (layout 0)  C[m][n] = residual[m][n] + mask[m][n] ? mask_scale * v : 0, v = dropout_(m, n)(relu(sum_k A[m][k] B[n][k] + bias[n]));
+ *                  Cf (fp32) and / or Cb (bf16), both (M, ldc); colsum (egx_wide_gemm_colsum_rows(M, N), N): column sums of the result per
+ *                  64 output rows of every tile (of the bf16-rounded values when Cb is written); rows past M add nothing.
+ *   TN (layout 2)  Cf[m][n] (+)= sum_k A[k][m] B[k][n] (accumulate = 1: +=). tn_queue: through the grouped launch (wide_tn_queue_add, then
+ *                  wide_tn_queue_flush and wide_reduce_flush); tn_defer: wide_gemm_tn with its slab reduction deferred to wide_reduce_flush.
+ *                  bias, relu, dropout, residual, mask, colsum and Cb are refused.
+ *   scratch        egx_wide_gemm_scratch(layout, M, N, K) bytes of the problem's own (its first 1024 bytes become the zero page).
+ * egx_wide_gemm_tn_batch: n <= 32 TN problems; the queued ones share ONE grouped grid per tile variant, the deferred reductions one launch.
+ * egx_wide_gemm_variant: what the dispatcher picks. NT: 0 = 64 x 64 tiles, 1 = 128 x 128 with four stages, 2 = 128 x 128 with two,
+ *   3 = 256 x 128, 4 = ping-pong 256 x 256, 5 = ping-pong 256 x 192 (`colsum` != 0: for a launch with column sums). TN: tile variant
+ *   (0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256) + 256 * split-K count. -1: not a problem of that layout. */
+typedef struct egx_wide_gemm_args {
+    int layout;
+    const void* A; const void* B; int M, N, K, lda, ldb;
+    float* Cf; void* Cb; int ldc;
+    const float* bias; int relu;
+    float p_drop; uint64_t seed; uint32_t layer, site;
+    const float* residual; int ldr;
+    const void* mask; int ldm; float mask_scale;
+    float* colsum;
+    int accumulate;
+    int tn_queue, tn_defer;
+    void* scratch;
+} egx_wide_gemm_args;
+int egx_wide_gemm_ex(const egx_wide_gemm_args* args, void* stream);
+int egx_wide_gemm_tn_batch(const egx_wide_gemm_args* args, int n, void* stream);
+int egx_wide_gemm_colsum_rows(int M, int N);
+int egx_wide_gemm_variant(int layout, int M, int N, int K, int colsum);
+/* egx_wide_layernorm_fwd: y[orow] = dropout_(orow, c)(LN(x[row]) * w + b + add_vec + pos[t * pos_stride ...]), stats[row] = (mean, rstd).
+ *   uniform (out_map NULL): orow = (row / T) * S + off + row % T, t = row % T; d % 4 == 0, d <= 2048.
+ *   mapped (out_map given): orow = out_map[row], t = src_map[row] % T (pos needs src_map); d <= 1024.
+ * egx_wide_layernorm_bwd: g = dropout_(orow, c)(dy[orow]) (p_drop / layer / site; mapped: orow = dy_map[row]); dx = LN backward of g at
+ *   pre[row], stats[row]; m = dropout_(row, c)(dx) (p_out / out_layer / out_site). dx32 = mask_dx32 ? m : dx; dx16 = bf16(m);
+ *   dw += sum g xhat, db += sum g, dadd += sum g, dbias += column sums of m (of the bf16-rounded values when dx16 is written).
+ *   defer != 0 (uniform only): the reduction is queued and run by wide_row_reduce_flush. scratch: egx_wide_layernorm_bwd_scratch bytes. */
+typedef struct egx_wide_ln_fwd_args {
+    const float* x; const float* w; const float* b; float eps;
+    float* stats; float* y32; void* y16;
+    int rows, d, T, S, off;
+    const float* add_vec; const float* pos; int pos_stride;
+    float p_drop; uint64_t seed; uint32_t layer, site;
+    const int* out_map; const int* src_map;
+} egx_wide_ln_fwd_args;
+typedef struct egx_wide_ln_bwd_args {
+    const float* dy; const float* pre; const float* stats; const float* w;
+    float* dx32; void* dx16;
+    int rows, d, T, S, off;
+    float p_drop; uint64_t seed; uint32_t layer, site;
+    float p_out; uint32_t out_layer, out_site;
+    int mask_dx32;
+    float* dw; float* db; float* dbias; float* dadd;
+    const int* dy_map;
+    int defer;
+    void* scratch;
+} egx_wide_ln_bwd_args;
+int egx_wide_layernorm_fwd(const egx_wide_ln_fwd_args* args, void* stream);
+size_t egx_wide_layernorm_bwd_scratch(int rows, int d);
+int egx_wide_layernorm_bwd(const egx_wide_ln_bwd_args* args, void* stream);
+/* out[c] += sum_r x[r][c] over a bf16 (rows, ld) matrix, cols % 8 == 0 (defer != 0: second stage through wide_row_reduce_flush).
+ * dpos[t * pos_stride + c] += sum_b dropout_(b * S + off + t, c)(dtok[(b * S + off + t) * d + c]), t < T.
+ * The scratch queries return the drivers' own (wide_colsum_scratch, wide_pos_grad_scratch): a launch writes nothing beyond them. */
+size_t egx_wide_colsum_scratch(int rows, int cols);
+int egx_wide_colsum(const void* x, int rows, int cols, int ld, float* out, int defer, void* scratch, void* stream);
+/* n_ln deferred LayerNorm backwards (uniform form) and n_cs deferred column sums, n_ln + n_cs <= 48, each with a scratch of its own: their
+ * second stages run as ONE wide_row_reduce_flush launch, as at the end of a backward. */
+typedef struct egx_wide_colsum_args { const void* x; int rows, cols, ld; float* out; void* scratch; } egx_wide_colsum_args;
+int egx_wide_row_reduce_batch(const egx_wide_ln_bwd_args* ln, int n_ln, const egx_wide_colsum_args* cs, int n_cs, void* stream);
+size_t egx_wide_pos_grad_scratch(int B, int T, int d);
+int egx_wide_pos_grad(const float* dtok, int B, int S, int off, int T, int d, float* dpos, int pos_stride, float p_drop, uint64_t seed,
+                      uint32_t layer, uint32_t site, void* scratch, void* stream);
+/* mode 0: dst[r][c] = bf16(src[r][c]) and / or dst_t[c][r] (src fp32 (R, ld); C % 4 == 0, R % 4 == 0 with dst_t);
+ * mode 1: dst[r][c] = bf16(mean_{j < pool} src[r * pool + j][c]); mode 2: dst[r][c] = bf16(src[rows[r]][c]) (src fp32 or bf16 (., C),
+ * C % 8 == 0). No scratch. */
+int egx_wide_cast(int mode, const void* src, int src_bf16, const int* rows, int R, int C, int ld, int pool, void* dst, void* dst_t,
+                  void* stream);
 
 /* Fused FFN weight gradients (d_model = 128): dW1 += dH^T x1, db1 += colsum(dH), dW2 += g^T H where
  * H = dropout(relu(x1 W1^T + b1)) and dH = (g W2) .* mask are recomputed on chip. x1, g: (N, 128); S = tokens per
