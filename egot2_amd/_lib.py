@@ -165,6 +165,13 @@ SIGNATURES = {
     "egx_wide_pos_grad": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
                                     C.c_uint32, _fp, _fp]),
     "egx_wide_cast": (C.c_int, [C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    # ABI v26: stage-read test hooks of the d = 128 calls (cfg, segs, B[, lengths], head_n_out, [saved, scratch,] item, layer, ...)
+    "egx_encoder_stage_info": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "egx_encoder_stage_read": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "egx_ragged_stage_info": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "egx_ragged_stage_read": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "egx_wide_attention_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
     "egx_wide_attention_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
     "egx_encoder_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.c_int,

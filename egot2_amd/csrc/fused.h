@@ -345,6 +345,25 @@ int ragged_empty_loss(const int* meta, float* loss, hipStream_t st);      // *lo
 int tiled_attn_fwd(const TiledAttnParams& p, int compute, hipStream_t st);
 int tiled_attn_bwd(const TiledAttnParams& p, int compute, hipStream_t st);
 
+// ---- stage read (test hook, ABI v26; stage_read.hip): one intermediate of a d = 128 call out of `saved` / the backward's scratch as a
+// dense row-major fp32 matrix (rows = the batch's tokens in token order). Token n of clip c = n / S_clip sits at row c * tpc * 48 + n % S_clip
+// of the 48-row clip / tile grids; with a batch table (ragged), at row 48 tile0 + s of the clip that holds dense token n.
+enum { SR_DENSE = 0,        // fp32 rows in token order already
+       SR_GRID = 1,         // fp32 rows on the 48-row grid
+       SR_PLANES = 2,       // n_planes bf16 planes [part][grid rows][cols], summed (one: widened)
+       SR_HID = 3,          // FFN hidden tiles (store_hid_tile / store_hid_tile_bf16, fused_dev.h); bf16 = accumulator layout
+       SR_ALIVE = 4 };      // the "alive" words of the FFN loops -> 1.f / 0.f per hidden unit
+struct StageReadParams {
+    const void* src; void* out;
+    int layout, rows, cols;         // rows x cols of `out`
+    int S_clip, tpc;                // uniform batches
+    const int* rtab; int B_clips;   // ragged batches: the device batch table (RAGGED_REC records), else null
+    int n_planes; size_t plane_stride;      // SR_PLANES: elements between the planes
+    int bf16;                       // SR_HID: bf16 tiles
+    int out_bytes;                  // 4: fp32 values; 1: one byte per element (SR_ALIVE)
+};
+int stage_read(const StageReadParams& p, hipStream_t st);
+
 bool fused_supported(int d_model, int n_heads, int d_ff, int S, int nseg, const int* d_in, const int* T, const bool* has_proj);      // n_heads 4 or 8
 size_t fused_lds_bytes(int NT);
 long long slices_stolen_fwd(int reset);     // sliced-mode diagnostic (fused_dev.h slice_stolen_note); synchronous device reads

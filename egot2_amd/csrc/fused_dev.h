@@ -306,6 +306,14 @@ __device__ __forceinline__ void store_hid_tile_bf16(void* tile0, u32x4 u, int la
     reinterpret_cast<uint2*>(tile0)[lane] = make_uint2(u[0], u[1]);
     reinterpret_cast<uint2*>(tile0)[64 + lane] = make_uint2(u[2], u[3]);
 }
+// Where store_hid_tile / store_hid_tile_bf16 put element (token r, hidden unit u) of a 16 x 16 tile, both 0 .. 15 (the stage-read test
+// hook unpacks the tiles with these, stage_read.hip): accumulator layout [lane = r + 16 (u / 4)][u % 4], and the quad-transposed layout
+// [u + 16 (r / 4)][r % 4] of the fp32 / split tiles.
+__host__ __device__ __forceinline__ int hid_tile_index_bf16(int r, int u) { return (r + 16 * (u >> 2)) * 4 + (u & 3); }
+__host__ __device__ __forceinline__ int hid_tile_index_f32(int r, int u) { return (u + 16 * (r >> 2)) * 4 + (r & 3); }
+// Bit of unit u (0 .. 31 within its hidden block) and token tile t in the lane's "alive" word of the FFN loops (relu_bits: one word per
+// (hidden block, lane), lane = token % 16 + 16 ((u % 16) / 4)): k = ((u / 16) NT + t) 4 + u % 4, NT = FUSED_TOK_TILES
+__host__ __device__ __forceinline__ int alive_bit_index(int t, int u) { return ((u >> 4) * FUSED_TOK_TILES + t) * 4 + (u & 3); }
 // A/B operand of one K-block of 32 tokens = two consecutive 16-token tiles of one hidden tile
 template <int CM>
 __device__ __forceinline__ Frag<CM> load_hid_frag(const void* tile_a, const void* tile_b, int lane) {

@@ -26,8 +26,13 @@ bool fused_ok(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
     for (int i = 0; i < pl.nseg; ++i) { d_in[i] = segs[i].d_in; T[i] = segs[i].T; hp[i] = segs[i].proj_w != nullptr; }
     return fused_supported(pl.d, pl.H, pl.dff, pl.S, pl.nseg, d_in, T, hp);
 }
-static size_t fused_mask_words(const Plan& pl) { return (size_t)pl.L * pl.vB * (pl.dff / 32) * 64; }
+static size_t fused_mask_layer_words(const Plan& pl) { return (size_t)pl.vB * (pl.dff / 32) * 64; }       // one layer's alive words
+static size_t fused_mask_words(const Plan& pl) { return (size_t)pl.L * fused_mask_layer_words(pl); }
 static size_t fused_res_bytes(const Plan& pl) { return align_up((size_t)(1 + 2 * pl.L) * pl.N * pl.d * 4, 256); }
+// floats in front of residual block `which` (0 = res1, 1 = res2) of layer l in `saved`: [pre][res1, res2 per layer], (N, d) each
+static size_t fused_res_index(const Plan& pl, int l, int which) { return (size_t)(1 + 2 * l + which) * pl.N * pl.d; }
+// floats of one layer's log-sum-exp rows (tiled / ragged): H rows per token
+static size_t tiled_lse_layer_floats(const Plan& vp) { return (size_t)vp.H * vp.N; }
 // saved = [pre + 2L residual blocks][ReLU sign bits of the FFN hidden: one u32 per (layer, clip, hidden block, lane)][packs]
 static size_t fused_act_bytes(const Plan& pl) { return fused_res_bytes(pl) + align_up(fused_mask_words(pl) * 4, 256); }
 // Fragment-packed weight copies kept behind the saved activations (written by the forward, reused by the
@@ -394,7 +399,7 @@ static void fill_fwd(FusedFwdParams& fp, PackParams& pk, const FusedPackLayout& 
     fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = v.tiled ? FUSED_TOK_PAD : vp.S; fp.d_ff = vp.dff;
     fp.tpc = v.tpc; fp.S_clip = v.S_clip; fp.Ntok = vp.N; fp.mode = FUSED_MODE_FULL;
     fp.saved_pre = (float*)v.base;
-    fp.saved_res = (float*)v.base + vp.N * d;
+    fp.saved_res = (float*)v.base + fused_res_index(vp, 0, 0);
     fp.relu_bits = (uint32_t*)(v.base + fused_res_bytes(vp));
     fp.hid_out = v.base + fused_hid_offset(cfg, segs, vp);
     fp.x1p_out = split_planes(cfg) ? (unsigned short*)(v.base + fused_x1p_offset(cfg, segs, vp)) : nullptr;
@@ -417,7 +422,7 @@ static TiledAttnParams tiled_attn_params(const TiledView& v, const Plan& vp, int
     memset(&ap, 0, sizeof(ap));
     ap.qkv = qkv + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * vp.d;
     ap.attn_o = attn_o;
-    ap.lse = (float*)(v.base + v.off_lse) + (size_t)l * vp.H * vp.N;     // H N rows per layer (= B H S of a uniform batch: N = B S)
+    ap.lse = (float*)(v.base + v.off_lse) + (size_t)l * tiled_lse_layer_floats(vp);     // H N rows per layer (= B H S of a uniform batch: N = B S)
     ap.B = v.B_clips; ap.S = v.S_clip; ap.tpc = v.tpc;
     ap.drop_key = key; ap.drop_thresh = thresh; ap.drop_inv = inv;
     ap.seed_ptr = seed_ptr; ap.layer = l;
@@ -485,7 +490,7 @@ static int fill_bwd(FusedBwdParams& bp, const FusedPackLayout& PL, const FusedBw
         if (v.tiled) bp.pooled = (const float*)(v.base + v.off_tokens) + N * d;
     }
     bp.saved_pre = (const float*)v.base;
-    bp.saved_res = (const float*)v.base + N * d;
+    bp.saved_res = (const float*)v.base + fused_res_index(vp, 0, 0);
     bp.saved_qkv = (const float*)(v.base + fused_qkv_offset(cfg, segs, vp));
     bp.relu_bits = (const uint32_t*)(v.base + fused_res_bytes(vp));
     bp.dhid_out = (char*)scratch + SC.dhid;
@@ -1285,6 +1290,149 @@ int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int
     const int* rseg = tab + (size_t)B_cap * RAGGED_REC + rp.tiles;
     return ragged_backward(cfg, segs, rp, RS, tab, rseg, rseg + (size_t)B_cap * FUSED_MAX_SEG, ln_w, ln_b, layers, head, B_cap, d_logits, d_tokens,
                            saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
+}
+
+}  // extern "C"
+
+// ---- stage read (ABI v26, test hooks): the intermediates a d = 128 call leaves in `saved` and in the backward's scratch ---------------------
+// Read-only: where an item lives comes from the offset functions and the scratch plans the launches above use; stage_read.hip turns it into a
+// dense matrix in token order. An item the chosen implementation does not hold when its call returns is EGX_STAGE_NOT_KEPT, never a stale read:
+//   forward (in `saved` from the forward on, every d = 128 mode): PRE, XIN, QKV, RES1, RES2, HID, ALIVE, and X1 as the bf16 plane(s) the FFN
+//     loop multiplied (bf16: one plane, f32s: three, summed exactly); exact-fp32 calls: X1 and G2 are not served (NOT_KEPT);
+//   backward (in `scratch` once the backward has returned; per layer and disjoint, bwd_scratch_prefix): G2 (planes like X1), DHID, G1, DQKV,
+//     DSEG, and ATTN_O, which the per-clip kernels recompute in the backward and the tiled / ragged calls save in the forward;
+//   LSE leaves the attention kernel of the tiled / ragged calls only. DX0 (written only when a learned positional table wants a gradient, which
+//   the hook is not told) is UNSUPPORTED: it answers NOT_KEPT whatever the call did.
+namespace {
+struct StageWhere { bool in_scratch; size_t off; StageReadParams sr; int kind; };
+int stage_locate(const egx_config* cfg, const egx_segment* segs, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
+                 int item, int layer, StageWhere& w) {
+    memset(&w, 0, sizeof(w));
+    const int comp = cfg->compute;
+    const bool bf = comp == EGX_BF16, planes = split_planes(cfg);
+    const size_t N = vp.N, d = vp.d, nd = N * d * 4;
+    StageReadParams& sr = w.sr;
+    sr.out_bytes = 4; sr.rows = (int)N; sr.cols = (int)d; sr.layout = SR_DENSE;
+    sr.S_clip = vp.S; sr.tpc = v.tiled ? v.tpc : 1; sr.rtab = v.rtab; sr.B_clips = v.B_clips;
+    w.kind = EGX_STAGE_KIND_F32;
+    const bool per_seg = item == EGX_STAGE_DSEG;
+    EGX_CHECK(item >= 0 && item < EGX_STAGE_ITEMS, "stage read: item %d (0 .. %d)", item, EGX_STAGE_ITEMS - 1);
+    EGX_CHECK(item == EGX_STAGE_PRE || item == EGX_STAGE_DX0 || (layer >= 0 && layer < (per_seg ? vp.nseg : vp.L)),
+              "stage read: %s %d out of range", per_seg ? "segment" : "layer", layer);
+    const size_t grid = (size_t)vp.vB * FUSED_TOK_PAD;
+    auto operand_planes = [&](size_t off) {      // x1 / g2 as the weight-gradient kernel reads them
+        sr.layout = SR_PLANES; sr.n_planes = bf ? 1 : 3; sr.plane_stride = grid * d; w.off = off;
+        if (bf) w.kind = EGX_STAGE_KIND_BF16;
+    };
+    switch (item) {
+    case EGX_STAGE_PRE: w.off = 0; break;
+    case EGX_STAGE_RES1: w.off = fused_res_index(vp, layer, 0) * 4; break;
+    case EGX_STAGE_RES2: w.off = fused_res_index(vp, layer, 1) * 4; break;
+    case EGX_STAGE_XIN: w.off = fused_xin_offset(cfg, segs, vp) + layer * nd; break;
+    case EGX_STAGE_QKV: sr.layout = SR_GRID; sr.cols = 3 * (int)d; w.off = fused_qkv_offset(cfg, segs, vp) + (size_t)layer * grid * 3 * d * 4; break;
+    case EGX_STAGE_X1:
+        if (!planes) return EGX_STAGE_NOT_KEPT;         // exact fp32: dense rows in the backward's scratch, not served (no test reads them)
+        operand_planes(fused_x1p_offset(cfg, segs, vp) + (size_t)layer * grid * d * plane_elem_bytes(cfg));
+        break;
+    case EGX_STAGE_HID: case EGX_STAGE_DHID:
+        sr.layout = SR_HID; sr.cols = vp.dff; sr.bf16 = bf;
+        if (bf) w.kind = EGX_STAGE_KIND_BF16;
+        w.in_scratch = item == EGX_STAGE_DHID;
+        w.off = (w.in_scratch ? SC.dhid : fused_hid_offset(cfg, segs, vp)) + (size_t)layer * fused_hid_bytes(vp.vB, vp.dff, bf);
+        break;
+    case EGX_STAGE_ALIVE:
+        sr.layout = SR_ALIVE; sr.cols = vp.dff; sr.out_bytes = 1; w.kind = EGX_STAGE_KIND_BIT;
+        w.off = fused_res_bytes(vp) + (size_t)layer * fused_mask_layer_words(vp) * 4;
+        break;
+    case EGX_STAGE_G2:
+        if (!planes) return EGX_STAGE_NOT_KEPT;         // (as X1)
+        w.in_scratch = true;
+        operand_planes(SC.g2[layer]);
+        break;
+    case EGX_STAGE_G1: w.in_scratch = true; w.off = SC.g1[layer]; break;
+    case EGX_STAGE_DQKV: w.in_scratch = true; sr.cols = 3 * (int)d; w.off = SC.dqkv[layer]; break;
+    case EGX_STAGE_ATTN_O:
+        if (v.tiled) w.off = v.off_attn + layer * nd;
+        else { w.in_scratch = true; w.off = SC.attn_o[layer]; }
+        break;
+    case EGX_STAGE_DSEG: w.in_scratch = true; sr.rows = (int)seg_rows[layer]; w.off = SC.dseg[layer]; break;
+    case EGX_STAGE_LSE:         // (clip, head, token of the clip); a ragged clip's rows start at 4 tok0
+        if (!v.tiled) return EGX_STAGE_NOT_KEPT;
+        sr.rows = (int)tiled_lse_layer_floats(vp); sr.cols = 1; w.off = v.off_lse + (size_t)layer * tiled_lse_layer_floats(vp) * 4;
+        break;
+    default: return EGX_STAGE_NOT_KEPT;      // EGX_STAGE_DX0: unsupported (the hook is not told whether a position gradient was requested)
+    }
+    return 0;
+}
+int stage_run(const egx_config* cfg, const egx_segment* segs, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
+              size_t saved_bytes, size_t scratch_bytes, const void* saved, const void* scratch, int item, int layer, int* rows, int* cols, int* kind,
+              void* out, hipStream_t st) {
+    StageWhere w;
+    const int rc = stage_locate(cfg, segs, vp, v, SC, seg_rows, item, layer, w);
+    if (rc) return rc;
+    if (rows) *rows = w.sr.rows;
+    if (cols) *cols = w.sr.cols;
+    if (kind) *kind = w.kind;
+    if (!out) return 0;         // (the shape query)
+    const void* base = w.in_scratch ? scratch : saved;
+    EGX_CHECK(base, "stage read: the item lives in `%s`, which is null", w.in_scratch ? "scratch" : "saved");
+    EGX_CHECK(w.off < (w.in_scratch ? scratch_bytes : saved_bytes), "stage read: offset beyond the workspace");
+    w.sr.src = (const char*)base + w.off;
+    w.sr.out = out;
+    return stage_read(w.sr, st);
+}
+int stage_uniform(const egx_config* cfg, const egx_segment* segs, int B, int head_n_out, const void* saved, const void* scratch, int item, int layer,
+                  int* rows, int* cols, int* kind, void* out, void* stream) {
+    EGX_CHECK(cfg && segs, "stage read: null config / segments");
+    EGX_CHECK(head_n_out >= 0 && head_n_out <= FUSED_HEAD_MAX_OUT, "stage read: head_n_out=%d (0 .. %d)", head_n_out, FUSED_HEAD_MAX_OUT);
+    Plan pl;
+    if (make_plan(cfg, segs, B, pl)) return 1;
+    const int impl = egx_encoder_impl(cfg, segs, B);
+    if (impl < 0) return 1;
+    if (impl != EGX_IMPL_FUSED && impl != EGX_IMPL_TILED) return EGX_STAGE_NOT_KEPT;       // the generic and the wide kernels have workspaces of their own
+    const bool tiled = impl == EGX_IMPL_TILED;
+    Plan vp = pl;
+    if (tiled) plan_tiled(vp);
+    const TiledView v = uniform_view(cfg, segs, vp, saved, tiled);
+    const FusedBwdScratch SC = fused_bwd_scratch(cfg, segs, vp, head_n_out);
+    size_t seg_rows[EGX_MAX_SEGMENTS];
+    for (int i = 0; i < pl.nseg; ++i) seg_rows[i] = (size_t)B * segs[i].T;
+    return stage_run(cfg, segs, vp, v, SC, seg_rows, tiled ? tiled_saved_bytes(cfg, segs, vp) : fused_saved_bytes(cfg, segs, vp), SC.bytes, saved, scratch,
+                     item, layer, rows, cols, kind, out, (hipStream_t)stream);
+}
+int stage_ragged(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved, const void* scratch,
+                 int item, int layer, int* rows, int* cols, int* kind, void* out, void* stream) {
+    EGX_CHECK(cfg && segs, "stage read: null config / segments");
+    EGX_CHECK(head_n_out >= 0 && head_n_out <= FUSED_HEAD_MAX_OUT, "stage read: head_n_out=%d (0 .. %d)", head_n_out, FUSED_HEAD_MAX_OUT);
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    const RaggedTrainScratch RS = ragged_train_scratch(cfg, segs, rp, head_n_out);
+    // the forward's copy of the batch table (in `saved`): tile0, tok0 and S of every clip are the same with and without a head
+    const int* tab = saved ? (const int*)((const char*)saved + rp.off_tab) : nullptr;
+    EGX_CHECK(!out || tab, "stage read: the ragged batch table lives in `saved`, which is null");
+    const TiledView v = ragged_view(rp, B, saved, tab, true);
+    return stage_run(cfg, segs, rp.vp, v, RS.sc, rp.seg_rows, rp.bytes, RS.sc.bytes, saved, scratch, item, layer, rows, cols, kind, out, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" {
+
+int egx_encoder_stage_info(const egx_config* cfg, const egx_segment* segs, int B, int head_n_out, int item, int layer, int* rows, int* cols, int* kind) {
+    return stage_uniform(cfg, segs, B, head_n_out, nullptr, nullptr, item, layer, rows, cols, kind, nullptr, nullptr);
+}
+int egx_encoder_stage_read(const egx_config* cfg, const egx_segment* segs, int B, int head_n_out, const void* saved, const void* scratch, int item,
+                           int layer, void* out, void* stream) {
+    EGX_CHECK(out, "stage read: null output");
+    return stage_uniform(cfg, segs, B, head_n_out, saved, scratch, item, layer, nullptr, nullptr, nullptr, out, stream);
+}
+int egx_ragged_stage_info(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, int item, int layer, int* rows,
+                          int* cols, int* kind) {
+    return stage_ragged(cfg, segs, B, lengths, head_n_out, nullptr, nullptr, item, layer, rows, cols, kind, nullptr, nullptr);
+}
+int egx_ragged_stage_read(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved,
+                          const void* scratch, int item, int layer, void* out, void* stream) {
+    EGX_CHECK(out, "stage read: null output");
+    return stage_ragged(cfg, segs, B, lengths, head_n_out, saved, scratch, item, layer, nullptr, nullptr, nullptr, out, stream);
 }
 
 }  // extern "C"

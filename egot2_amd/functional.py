@@ -721,6 +721,81 @@ def encoder(spec: EncoderSpec, feats: Sequence[torch.Tensor], task_embed, pos_ta
     return EncoderFn.apply(spec, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params)
 
 
+STAGE_ITEMS = {"PRE": 0, "XIN": 1, "QKV": 2, "RES1": 3, "X1": 4, "HID": 5, "ALIVE": 6, "RES2": 7, "G2": 8, "DHID": 9, "G1": 10, "ATTN_O": 11,
+               "DQKV": 12, "DSEG": 13, "DX0": 14, "LSE": 15}        # include/egot2x.h EGX_STAGE_*
+STAGE_NOT_KEPT = 2
+
+
+class EncoderStages:
+    """TEST INFRASTRUCTURE (tests/test_gpu_bf16_stages.py): the intermediates of ONE d = 128 encoder call, read back through the stage hooks
+    (ABI v26, egx_encoder_stage_* / egx_ragged_stage_*). Construct it from any output of the call (logits, tokens or the fused loss) BEFORE the
+    backward: it finds the call's autograd node (EncoderFn / RaggedEncoderFn), keeps its configuration, segments and `saved` buffer and
+    rebuilds nothing else. The forward items can be read at once; the backward items live in the shared scratch workspace: read them after the
+    backward and before any other encoder call. read() returns a (rows, cols) tensor (fp32; ALIVE: uint8), prefilled with NaN (255) so that
+    an element the hook leaves unwritten shows, or None where the hook reports the item as not kept by this call's implementation."""
+
+    def __init__(self, out: torch.Tensor):
+        node = self._find(out.grad_fn)
+        if node is None:
+            raise _lib.EgxError("EncoderStages: no encoder call in the graph of this tensor")
+        self._lib = _load()
+        spec: EncoderSpec = node.spec
+        tensors = _EncArgs.load(node)
+        task_embed, pos_table, _, _, feats, proj, _, _, _ = tensors
+        self.B = node.B
+        self.ragged = isinstance(node, RaggedEncoderFn._backward_cls)
+        self.lengths = node.lengths if self.ragged else None
+        if self.ragged and (self.lengths.is_cuda or self.lengths.dtype != torch.int32):
+            raise _lib.EgxError("EncoderStages: the ragged hooks read HOST lengths (the (B, K) int32 CPU tensor of ragged_lengths())")
+        self.cfg = _ragged_train_config(spec) if self.ragged else spec.config()
+        self.segs = _segments(spec, feats, proj, task_embed, pos_table, self.B)
+        self.head_n_out = int(spec.head_n_out or spec.token_ce or 0)
+        self.saved, self.scratch_bytes, self.device = node.saved_buf, node.scratch_bytes, feats[0].device
+        self.spec = spec
+        self._keep = tensors        # the segment array holds raw addresses
+
+    @staticmethod
+    def _find(fn):
+        seen, todo = set(), [fn]
+        while todo:
+            f = todo.pop()
+            if f is None or f in seen:
+                continue
+            seen.add(f)
+            if isinstance(f, (EncoderFn._backward_cls, RaggedEncoderFn._backward_cls)):
+                return f
+            todo.extend(n for n, _ in f.next_functions)
+        return None
+
+    def _args(self):
+        head = (self.B,) + ((self.lengths.data_ptr(),) if self.ragged else ()) + (self.head_n_out,)
+        return (C.byref(self.cfg), self.segs) + head
+
+    def info(self, item: str, layer: int = 0):
+        """-> (rows, cols, kind) or None (not kept); kind 0 fp32, 1 bf16 values, 2 bits."""
+        r, c, k = C.c_int(0), C.c_int(0), C.c_int(0)
+        fn = self._lib.egx_ragged_stage_info if self.ragged else self._lib.egx_encoder_stage_info
+        rc = fn(*self._args(), STAGE_ITEMS[item], layer, C.byref(r), C.byref(c), C.byref(k))
+        if rc == STAGE_NOT_KEPT:
+            return None
+        check(rc)
+        return r.value, c.value, k.value
+
+    def read(self, item: str, layer: int = 0):
+        inf = self.info(item, layer)
+        if inf is None:
+            return None
+        rows, cols, kind = inf
+        if kind == 2:
+            out = torch.full((rows, cols), 255, dtype=torch.uint8, device=self.device)
+        else:
+            out = torch.full((rows, cols), float("nan"), dtype=torch.float32, device=self.device)
+        scratch = _scratch_cache.get(("scratch", self.device.index))
+        fn = self._lib.egx_ragged_stage_read if self.ragged else self._lib.egx_encoder_stage_read
+        check(fn(*self._args(), ptr(self.saved), ptr(scratch) if scratch is not None else None, STAGE_ITEMS[item], layer, ptr(out), _stream()))
+        return out
+
+
 def ragged_lengths(lengths, B: int, T_pad: Sequence[int], order: Optional[Sequence[int]] = None) -> torch.Tensor:
     """Frame counts of a ragged batch as the (B, K) int32 host tensor egx_ragged_fwd reads (K = len(T_pad) segments). `lengths` is a (B,)
     tensor / sequence (every segment of clip b has lengths[b] frames) or (B, K) with one column per feature argument; `order` maps segment k

@@ -555,6 +555,50 @@ int egx_wide_pos_grad(const float* dtok, int B, int S, int off, int T, int d, fl
 int egx_wide_cast(int mode, const void* src, int src_bf16, const int* rows, int R, int C, int ld, int pool, void* dst, void* dst_t,
                   void* stream);
 
+/* ---- ABI v26 additions (new symbols only, as v19 to v25: EGX_ABI_VERSION stays 18): the intermediates of a d = 128 call, stage by stage ---
+ * Read-only test hooks of the per-clip (one launch, cut, sliced), tiled and ragged-training calls (egx_encoder_impl() == EGX_IMPL_FUSED /
+ * EGX_IMPL_TILED, egx_ragged_train_fwd / egx_ragged_bwd): what the forward leaves in `saved` and the backward in `scratch`, one item at a
+ * time, as a dense row-major matrix whose rows are the batch's tokens in token order (clip by clip; a ragged batch: its packed tokens).
+ * tests/test_gpu_bf16_stages.py compares every stage of a bf16 call with a reference computed from the items the device itself held going
+ * into that stage. No forward or backward launch changes; the hooks add one small launch of their own per read.
+ *   item                 rows x cols      from                         what
+ *   EGX_STAGE_PRE        N x d            saved                        projected features (+ bias, feature dropout) before the shared LayerNorm
+ *   EGX_STAGE_XIN[l]     N x d            saved                        input of layer l
+ *   EGX_STAGE_QKV[l]     N x 3d           saved                        Q | K | V rows with bias
+ *   EGX_STAGE_RES1[l]    N x d            saved                        x + dropout(out-projection): the input of LayerNorm1
+ *   EGX_STAGE_X1[l]      N x d            saved                        LayerNorm1 output as the FFN loop multiplies it: the bf16 plane, or the three
+ *                                                                      f32s planes summed (exact); exact-fp32 calls (X1 and G2): EGX_STAGE_NOT_KEPT
+ *   EGX_STAGE_HID[l]     N x d_ff         saved                        dropout(relu(.)) with the keep-scale, out of its MFMA-lane tiles (bf16 in bf16 calls)
+ *   EGX_STAGE_ALIVE[l]   N x d_ff bytes   saved                        1 = ReLU active and kept by the dropout
+ *   EGX_STAGE_RES2[l]    N x d            saved                        x1 + dropout(FFN output): the input of LayerNorm2
+ *   EGX_STAGE_G2[l]      N x d            scratch                      gradient of the FFN output behind its dropout mask (planes like X1)
+ *   EGX_STAGE_DHID[l]    N x d_ff         scratch                      gradient of the FFN pre-activation (tiles like HID)
+ *   EGX_STAGE_G1[l]      N x d            scratch                      gradient of the out-projection output behind its dropout mask
+ *   EGX_STAGE_ATTN_O[l]  N x d            scratch (tiled, ragged: saved)   attention output, the operand of the out-projection
+ *   EGX_STAGE_DQKV[l]    N x 3d           scratch                      gradient of Q | K | V
+ *   EGX_STAGE_DSEG[i]    rows_i x d       scratch                      gradient of segment i's projected features (`layer` = i; ragged: packed rows)
+ *   EGX_STAGE_LSE[l]     4 N x 1          saved, tiled and ragged only log-sum-exp rows of the scaled scores, (clip, head, token of the clip)
+ *   EGX_STAGE_DX0        -                -                            UNSUPPORTED: written only when a learned positional table wants a gradient, which
+ *                                                                      the hook is not told; it answers EGX_STAGE_NOT_KEPT whatever the call did
+ * The scratch items are valid from the return of the backward until the next call that uses the same scratch. head_n_out: the pooled head's
+ * outputs (egx_translator_*; egx_config.token_ce: its classes; else 0): the scratch plan depends on it. `kind` (info): EGX_STAGE_KIND_F32,
+ * _BF16 (bf16 values, widened exactly to fp32), _BIT (one byte per element, 0 / 1). Return value: 0, 1 (an error: egx_last_error) or
+ * EGX_STAGE_NOT_KEPT: the item does not exist when this configuration's call returns (other implementations, LSE of a per-clip call, DX0). */
+enum { EGX_STAGE_PRE = 0, EGX_STAGE_XIN = 1, EGX_STAGE_QKV = 2, EGX_STAGE_RES1 = 3, EGX_STAGE_X1 = 4, EGX_STAGE_HID = 5, EGX_STAGE_ALIVE = 6,
+       EGX_STAGE_RES2 = 7, EGX_STAGE_G2 = 8, EGX_STAGE_DHID = 9, EGX_STAGE_G1 = 10, EGX_STAGE_ATTN_O = 11, EGX_STAGE_DQKV = 12, EGX_STAGE_DSEG = 13,
+       EGX_STAGE_DX0 = 14, EGX_STAGE_LSE = 15, EGX_STAGE_ITEMS = 16 };
+enum { EGX_STAGE_KIND_F32 = 0, EGX_STAGE_KIND_BF16 = 1, EGX_STAGE_KIND_BIT = 2 };
+#define EGX_STAGE_NOT_KEPT 2
+int egx_encoder_stage_info(const egx_config* cfg, const egx_segment* segs, int B, int head_n_out, int item, int layer, int* rows, int* cols,
+                           int* kind);
+int egx_encoder_stage_read(const egx_config* cfg, const egx_segment* segs, int B, int head_n_out, const void* saved, const void* scratch,
+                           int item, int layer, void* out, void* stream);
+/* The same for a ragged training batch; lengths: the host (B, K) frame counts of egx_ragged_train_fwd. */
+int egx_ragged_stage_info(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, int item, int layer,
+                          int* rows, int* cols, int* kind);
+int egx_ragged_stage_read(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved,
+                          const void* scratch, int item, int layer, void* out, void* stream);
+
 /* Fused FFN weight gradients (d_model = 128): dW1 += dH^T x1, db1 += colsum(dH), dW2 += g^T H where
  * H = dropout(relu(x1 W1^T + b1)) and dH = (g W2) .* mask are recomputed on chip. x1, g: (N, 128); S = tokens per
  * clip (dropout keying). scratch: egx_ffn_dw_scratch() bytes. Replaces the autograd of linear1/ReLU/linear2 weight
