@@ -174,6 +174,12 @@ SIGNATURES = {
     "egx_ragged_stage_read": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "egx_wide_attention_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
     "egx_wide_attention_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _fp]),
+    # ABI v27: the encoder's self-attention weights (primitive, rollout, and from a forward's `saved`)
+    "egx_self_attention_weights": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
+                                             C.c_int, _fp, _fp]),
+    "egx_attention_rollout_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "egx_attention_rollout": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp]),
+    "egx_encoder_self_weights": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), C.c_int, _fp, C.c_int, _fp, C.c_uint64, _fp, _fp, _fp]),
     "egx_encoder_fwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.c_int,
                                   _fp, _fp, _fp, C.c_int, C.c_uint64, _fp]),
     "egx_encoder_bwd": (C.c_int, [C.POINTER(Config), C.POINTER(Segment), _fp, _fp, C.POINTER(Layer), C.c_int,

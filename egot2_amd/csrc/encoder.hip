@@ -13,6 +13,7 @@
 #include "fused_host.h"
 #include "wide.h"
 #include "wide_host.h"
+#include "enc_attn_weights.h"
 
 namespace egx {
 
@@ -1101,6 +1102,57 @@ int egx_dropout(float* x, int rows, int cols, float p_drop, uint64_t seed, uint3
     EGX_CHECK(x || rows * cols == 0, "egx_dropout: null pointer");
     Drop dr = make_drop(p_drop > 0.f, p_drop, seed, site >> 8, site & 0xffu);
     return apply_dropout_mask(x, rows, cols, dr.key, dr.thresh, dr.inv_keep, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- ABI v27: the encoder's self-attention weights from the Q | K | V rows a forward left in `saved` (enc_attn_weights.hip) ----------------
+extern "C" {
+
+int egx_encoder_self_weights(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved,
+                             uint64_t layer_mask, float* w_out, float* seg_out, void* stream) {
+    const char* who = "egx_encoder_self_weights";
+    EGX_CHECK(cfg && segs, "%s: null config / segments", who);
+    EGX_CHECK(saved, "%s: null pointer argument (saved)", who);
+    EGX_CHECK(w_out || seg_out, "%s: null pointer argument (w_out and seg_out are both null)", who);
+    EGX_CHECK(head_n_out >= 0, "%s: head_n_out = %d", who, head_n_out);
+    EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f && cfg->p_feat == 0.f,
+              "%s: inference only: p_drop, p_pos and p_feat must be 0 (got %g, %g, %g); the weights behind the attention dropout are not modelled",
+              who, cfg->p_drop, cfg->p_pos, cfg->p_feat);
+    Plan pl;
+    if (make_plan(cfg, segs, B, pl)) return 1;
+    EGX_CHECK(pl.L >= 1, "%s: a configuration without encoder layers keeps no Q | K | V", who);
+    EGX_CHECK(layer_mask != 0 && (pl.L >= 64 || (layer_mask >> pl.L) == 0), "%s: layer_mask = 0x%llx selects no layer or one beyond the %d layers",
+              who, (unsigned long long)layer_mask, pl.L);
+    const int dh = pl.d / pl.H;
+    EGX_CHECK(dh == 16 || dh == 32 || dh == 64 || dh == 96 || dh == 128,
+              "%s: head dim %d (16, 32, 64, 96 or 128; the head dims 256 / 512 of the d = 2048 recipe are not served)", who, dh);
+    EGX_CHECK(pl.nseg <= SW_MAXSEG, "%s: %d segments (at most %d)", who, pl.nseg, SW_MAXSEG);
+    hipStream_t st = (hipStream_t)stream;
+    if (lengths) {
+        EGX_CHECK(pl.d == 128, "%s: ragged batches are served on the d = 128 kernels only (egx_ragged_train_fwd with training = 0); the wide path's "
+                  "ragged batches (egx_ragged_encode*) are not", who);
+        return ragged_self_weights(cfg, segs, B, lengths, saved, layer_mask, w_out, seg_out, st);
+    }
+    EGX_CHECK(pl.S <= SW_MAXS, "%s: S = %d (1..%d)", who, pl.S, SW_MAXS);
+    const int impl = egx_encoder_impl(cfg, segs, B);
+    if (impl < 0) return 1;
+    if (impl == EGX_IMPL_FUSED || impl == EGX_IMPL_TILED) return fused_self_weights(cfg, segs, pl, impl == EGX_IMPL_TILED, saved, layer_mask, w_out, seg_out, st);
+    SelfWParams p;
+    memset(&p, 0, sizeof(p));
+    p.ldq = p.ldk = 3 * pl.d; p.clip_rows = pl.S; p.K = pl.nseg; p.w = w_out; p.ldw = pl.S; p.seg = seg_out; p.B = B; p.H = pl.H; p.S = pl.S;
+    p.fixed_segs = 1;
+    for (int i = 0; i < pl.nseg; ++i) p.seg_fixed[i] = segs[i].T;
+    if (impl == EGX_IMPL_WIDE) {
+        size_t off[64];
+        wide_qkv_offsets(cfg, segs, B, off);
+        // (the wide plan's layers are laid out at one stride; checked, not assumed)
+        const size_t stride = pl.L > 1 ? off[1] - off[0] : 0;
+        for (int l = 1; l < pl.L; ++l) EGX_CHECK(off[l] == off[0] + l * stride, "%s: wide plan: layer %d not at the common stride", who, l);
+        return self_weights_layers(p, (const char*)saved + off[0], stride, pl.d, pl.L, layer_mask, false, st);
+    }
+    const size_t stride = pl.L > 1 ? pl.layer[1].qkv - pl.layer[0].qkv : 0;
+    return self_weights_layers(p, (const char*)saved + pl.layer[0].qkv, stride, pl.d, pl.L, layer_mask, true, st);
 }
 
 }  // extern "C"

@@ -69,5 +69,11 @@ int fused_path_bwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
                    const egx_layer* layers, const egx_head* head, float* d_tokens, const float* d_logits, const void* saved, void* scratch,
                    const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads,
                    const egx_head_grads* head_grads, int training, uint64_t seed, hipStream_t st);
+// the self-attention weights of a d = 128 call from the Q | K | V rows its forward left in `saved` (egx_encoder_self_weights, encoder.hip):
+// a uniform per-clip / tiled call, and a ragged call (egx_ragged_train_fwd's layout; *S_out: the longest clip)
+int fused_self_weights(const egx_config* cfg, const egx_segment* segs, const Plan& pl, bool tiled, const void* saved, uint64_t layer_mask,
+                       float* w_out, float* seg_out, hipStream_t st);
+int ragged_self_weights(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, const void* saved, uint64_t layer_mask,
+                        float* w_out, float* seg_out, hipStream_t st);
 
 }  // namespace egx

@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "fused.h"
 #include "fused_host.h"
+#include "enc_attn_weights.h"
 
 namespace egx {
 
@@ -1436,3 +1437,40 @@ int egx_ragged_stage_read(const egx_config* cfg, const egx_segment* segs, int B,
 }
 
 }  // extern "C"
+
+// ---- the self-attention weights of a d = 128 call (ABI v27, egx_encoder_self_weights) -------------------------------------------------------
+// Every d = 128 forward keeps each layer's fp32 Q | K | V rows on the 48-row tile grid at fused_qkv_offset (what EGX_STAGE_QKV reads): clip c
+// of a uniform call starts at row c * tpc * 48, a ragged clip at 48 x the first tile of its batch-table record, which enc_self_weights_kernel
+// reads in place (first tile, S_b and the segments' frame counts), so nothing is built or uploaded here.
+namespace egx {
+static void self_weights_common(SelfWParams& p, const Plan& vp, float* w_out, float* seg_out, int B, int S) {
+    memset(&p, 0, sizeof(p));
+    p.ldq = p.ldk = 3 * vp.d; p.K = vp.nseg; p.w = w_out; p.ldw = S; p.seg = seg_out; p.B = B; p.H = vp.H; p.S = S;
+}
+int fused_self_weights(const egx_config* cfg, const egx_segment* segs, const Plan& pl, bool tiled, const void* saved, uint64_t layer_mask,
+                       float* w_out, float* seg_out, hipStream_t st) {
+    Plan vp = pl;
+    if (tiled) plan_tiled(vp);
+    SelfWParams p;
+    self_weights_common(p, vp, w_out, seg_out, pl.B, pl.S);
+    p.clip_rows = (long long)vp.tpc * FUSED_TOK_PAD;
+    p.fixed_segs = 1;
+    for (int i = 0; i < vp.nseg; ++i) p.seg_fixed[i] = segs[i].T;
+    const size_t grid = (size_t)vp.vB * FUSED_TOK_PAD;
+    return self_weights_layers(p, (const char*)saved + fused_qkv_offset(cfg, segs, vp), grid * 3 * vp.d * 4, vp.d, vp.L, layer_mask, true, st);
+}
+int ragged_self_weights(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, const void* saved, uint64_t layer_mask,
+                        float* w_out, float* seg_out, hipStream_t st) {
+    RaggedPlan rp;
+    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    const Plan& vp = rp.vp;
+    const int* tab = (const int*)((const char*)saved + rp.off_tab);     // the forward's device copy of the batch table
+    SelfWParams p;
+    self_weights_common(p, vp, w_out, seg_out, B, vp.S);
+    p.rowtab = tab; p.tab_stride = RAGGED_REC; p.row_mul = FUSED_TOK_PAD;       // record: RG_TILE0, RG_S
+    p.segtab = tab + RG_T; p.seg_stride = RAGGED_REC;
+    static_assert(RG_TILE0 == 0 && RG_S == 1, "enc_self_weights_kernel reads (first tile, S_b) at the head of a record");
+    const size_t grid = (size_t)vp.vB * FUSED_TOK_PAD;
+    return self_weights_layers(p, (const char*)saved + fused_qkv_offset(cfg, segs, vp), grid * 3 * vp.d * 4, vp.d, vp.L, layer_mask, true, st);
+}
+}  // namespace egx

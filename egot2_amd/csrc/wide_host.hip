@@ -196,6 +196,13 @@ void wide_workspace(const egx_config* cfg, const egx_segment* segs, int B, size_
     *scratch = pl.scratch_bytes;
 }
 
+// where wide_encoder_fwd leaves layer l's bf16 Q | K | V rows (N x 3d) in `saved` (egx_encoder_self_weights reads them there)
+void wide_qkv_offsets(const egx_config* cfg, const egx_segment* segs, int B, size_t* off) {
+    WPlan pl;
+    make_wplan(cfg, segs, B, pl);
+    for (int l = 0; l < pl.L; ++l) off[l] = pl.layer[l].qkv;
+}
+
 namespace {
 // the wide forward over `pl`. rg (with `tab`, the device copy of its table): a ragged batch — token preparation through the row maps, the attention
 // one launch per kernel class over the batch table, and (rg->layout 1) the last LayerNorm's rows scattered to the frame-major output; every other

@@ -100,6 +100,9 @@ class EncoderSpec:
 reload_tuning_each_call = False
 
 _scratch_cache = {}
+# record_attention / encoder_attention (the AttentionRecorder at the end of this file) while active, else None: the encoder forwards call it
+# right behind their library call with that call's own configuration, segments and `saved`
+_attention_sink = None
 _last_impl = [EGX_IMPL_AUTO]
 _last_slices = [1]
 # last_encoder_impl() of the ragged-batch forward (encoder_ragged): the ragged tiled kernels, or the per-length-group fallback
@@ -580,6 +583,8 @@ class EncoderFn(torch.autograd.Function):
         _last_impl[0] = ctx.impl
         _last_slices[0] = lib.egx_encoder_slices(C.byref(cfg), segs, B) if ctx.impl == EGX_IMPL_FUSED else 1
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
+        if _attention_sink is not None:     # (record_attention / encoder_attention: one more launch per selected layer, behind the forward)
+            _attention_sink(lib, cfg, segs, B, None, spec, saved, device)
         _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, [t for t in (tw, tb) if t is not None])
         if spec.token_ce:
             ctx.mark_non_differentiable(*tce_out[1:])
@@ -877,6 +882,7 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
                                                                               layer_params, head_params, "egx_ragged_workspace")
         feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = params
         if nbytes is None:
+            _attention_unserved("a ragged batch outside the ragged d = 128 kernels (it runs as per-length groups)")
             return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
         B, device = feats[0].shape[0], feats[0].device
         ws = _workspace("saved", device, nbytes)
@@ -894,6 +900,8 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
             wc.sig = wc_sig
     _last_impl[0] = IMPL_RAGGED
     _last_slices[0] = 1
+    if _attention_sink is not None:
+        _attention_sink(lib, cfg, segs, B, lengths, spec, ws, device)
     return out
 
 
@@ -963,6 +971,8 @@ class RaggedEncoderFn(torch.autograd.Function):
         del keep
         _last_impl[0] = IMPL_RAGGED
         _last_slices[0] = 1
+        if _attention_sink is not None:
+            _attention_sink(lib, cfg, segs, B, lengths, spec, saved, device)
         ctx.spec, ctx.lengths, ctx.B = spec, lengths, B        # the host lengths: the backward rebuilds the same plan from them
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
         _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t)
@@ -1153,11 +1163,13 @@ def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengt
     if (ce is not None) != bool(spec.ce) or (ce is not None and not spec.head_n_out):
         raise ValueError("ce = (target, class_weight) goes with spec.ce and the pooled head")
     if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        _attention_unserved("the capacity form of a ragged batch (device lengths)")
         return _encoder_ragged_cap(spec, feats, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
     if capacity is not None:
         raise ValueError("capacity= goes with device lengths (a CUDA int32 tensor); host lengths size the call themselves")
     lengths = _check_host_lengths(lengths, feats[0].shape[0], len(spec.segments))
     if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_train_workspace"):
+        _attention_unserved("a ragged batch outside the ragged d = 128 kernels (it runs as per-length groups)")
         return _encoder_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
     args = [spec, lengths, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
     if ce is not None:
@@ -1220,6 +1232,7 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
     wide bf16 path (last_encoder_impl() == "ragged"); configurations it does not cover run one batched forward per length tuple ("grouped")."""
     if spec.training or spec.ce or spec.token_ce or spec.out_tokens or spec.head_n_out:
         raise ValueError("ragged batches are inference-only: no training mode, no fused losses, no out_tokens, no head")
+    _attention_unserved("a ragged batch on the wide path")
     with torch.no_grad():
         lib, lengths, params, segs, layers, cfg, nbytes = _ragged_infer_setup(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
                                                                               layer_params, (), "egx_ragged_encode_workspace", out_layout)
@@ -1305,6 +1318,7 @@ def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor]
     if bucket_hook is not None:
         raise ValueError("ragged training: the bucketed per-layer gradient exchange (bucket_cb) is not supported; exchange the gradients "
                          "after the backward (ddp.allreduce_gradients)")
+    _attention_unserved("a ragged batch on the wide path")
     B = feats[0].shape[0]
     lengths = _check_host_lengths(lengths, B, len(spec.segments))
     _check_out_layout(lengths, B, out_layout)
@@ -3043,3 +3057,222 @@ class CrossAttnTargetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         return _cross_attn_bwd(ctx, "egx_target_attention", d_out)
+
+
+# ---- the encoder's self-attention weights as an output (ABI v27: egx_self_attention_weights, egx_attention_rollout, egx_encoder_self_weights) ----
+SELF_WEIGHTS_HEAD_DIMS = (16, 32, 64, 96, 128)
+SELF_WEIGHTS_MAX_TOKENS = 512
+SELF_WEIGHTS_MAX_SEGMENTS = 16
+
+
+def check_self_weights(head_dim: int, S: int, K: int = 1) -> None:
+    """The limits of the self-attention weights as a ValueError that names them (host work, before any device call)."""
+    if head_dim not in SELF_WEIGHTS_HEAD_DIMS or not 1 <= S <= SELF_WEIGHTS_MAX_TOKENS or not 1 <= K <= SELF_WEIGHTS_MAX_SEGMENTS:
+        raise ValueError(f"self-attention weights are served for head dims {SELF_WEIGHTS_HEAD_DIMS}, 1..{SELF_WEIGHTS_MAX_TOKENS} tokens per clip "
+                         f"and 1..{SELF_WEIGHTS_MAX_SEGMENTS} segments: got head dim {head_dim}, {S} tokens, {K} segments")
+
+
+def _segment_table(segments, B: int, device, who: str) -> torch.Tensor:
+    """segments: K lengths shared by every clip, or (B, K) lengths per clip -> (B, K) int32 on the device"""
+    t = segments.detach() if isinstance(segments, torch.Tensor) else torch.as_tensor(segments)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.dim() not in (1, 2) or t.shape[-1] < 1:
+        raise ValueError(f"{who}: segments must be K integer lengths or a (B, K) integer table")
+    if t.dim() == 1:
+        t = t[None].expand(B, t.shape[0])
+    if t.shape[0] != B or t.shape[1] > SELF_WEIGHTS_MAX_SEGMENTS:
+        raise ValueError(f"{who}: segments has shape {tuple(t.shape)}: expected (K,) or ({B}, K) with K <= {SELF_WEIGHTS_MAX_SEGMENTS}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def self_attention_weights(q: torch.Tensor, k: torch.Tensor, n_heads: int, S: int, rowtab: Optional[torch.Tensor] = None, segments=None,
+                           B: Optional[int] = None, weights: bool = True):
+    """The head-averaged self-attention weights w[b, i, j] = (1 / H) sum_h softmax_j(q[b, i, h] . k[b, j, h] / sqrt(dh)), i, j < S_b, that
+    nn.MultiheadAttention returns with need_weights=True, and their per-segment sums seg[b, i, t] = sum_{j in segment t} w[b, i, j]
+    (egx_self_attention_weights; no autograd). q and k (rows, H * dh), both fp32 or both bf16, head h at columns h * dh; 2-D views with unit
+    column stride and a row stride that is a multiple of 8 elements are read in place (the q / k columns of a packed Q | K | V matrix).
+    Clip b's tokens are rows b * S .. of q and k, or, with rowtab ((B, 2) int32 on the device: first row, S_b <= S), rows first .. first +
+    S_b: ragged clips, gaps between clips, empty slots (S_b = 0: zeros). segments: K lengths, or a (B, K) table of per-clip lengths.
+    dh in (16, 32, 64, 96, 128), S <= 512. Returns w (B, S, S) fp32, or (w, seg (B, S, K)) with segments; weights=False: seg alone (w is
+    then never written to memory). Entries beyond a clip's S_b tokens are exact zeros."""
+    lib = _lib.load()
+    who = "self_attention_weights"
+    for name, t in (("q", q), ("k", k)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{who}: {name} must be a 2-D fp32 or bf16 tensor on the GPU")
+    if q.dtype != k.dtype or q.shape[1] != k.shape[1] or n_heads < 1 or q.shape[1] % n_heads:
+        raise ValueError(f"{who}: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} do not fit {n_heads} heads")
+    if segments is None and not weights:
+        raise ValueError(f"{who}: weights=False needs segments")
+    if rowtab is None:
+        if S < 1 or q.shape[0] % S or k.shape[0] != q.shape[0] or (B is not None and B * S != q.shape[0]):
+            raise ValueError(f"{who}: q and k have {q.shape[0]} and {k.shape[0]} rows, expected B * S with S = {S} in both")
+        B = q.shape[0] // S
+    else:
+        if not (isinstance(rowtab, torch.Tensor) and rowtab.is_cuda and rowtab.dtype == torch.int32 and rowtab.dim() == 2 and rowtab.shape[1] == 2):
+            raise ValueError(f"{who}: rowtab must be a (B, 2) int32 tensor on the GPU (first row, tokens)")
+        B = rowtab.shape[0]
+        rowtab = rowtab.contiguous()
+    segtab = _segment_table(segments, B, q.device, who) if segments is not None else None
+    K = segtab.shape[1] if segtab is not None else 0
+    check_self_weights(q.shape[1] // n_heads, S, max(K, 1))
+    q, k = [t if t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0 else t.contiguous() for t in (q.detach(), k.detach())]
+    w = torch.empty((B, S, S), dtype=torch.float32, device=q.device) if weights else None
+    seg = torch.empty((B, S, K), dtype=torch.float32, device=q.device) if segtab is not None else None
+    check(lib.egx_self_attention_weights(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), int(q.dtype == torch.bfloat16), ptr(rowtab),
+                                         ptr(segtab), K, B, n_heads, q.shape[1] // n_heads, S, ptr(w), S, ptr(seg), _stream()))
+    return w if seg is None else (w, seg) if weights else seg
+
+
+def attention_rollout(w: torch.Tensor, segments=None, lengths: Optional[torch.Tensor] = None):
+    """Attention rollout (Abnar & Zuidema 2020) over the layers of w (L, B, S, S) fp32 on the GPU: R_l = ((w_l + I) / 2) R_{l-1}, R_0 = I, per
+    clip, in fp32 with a fixed summation order (egx_attention_rollout; no autograd); L = 1 gives exactly (w_1 + I) / 2. lengths: (B,) int32 on
+    the device, clip b's tokens (zeros beyond them). Returns R (B, S, S), or (R, R_by_segment (B, S, K)) with segments (K lengths or a (B, K)
+    table)."""
+    lib = _lib.load()
+    who = "attention_rollout"
+    if not isinstance(w, torch.Tensor) or w.dim() != 4 or not w.is_cuda or w.dtype != torch.float32 or w.shape[2] != w.shape[3] or w.shape[0] < 1:
+        raise ValueError(f"{who}: w must be an (L, B, S, S) fp32 tensor on the GPU")
+    L, B, S, _ = w.shape
+    if not 1 <= S <= SELF_WEIGHTS_MAX_TOKENS:
+        raise ValueError(f"{who}: S = {S} tokens (1..{SELF_WEIGHTS_MAX_TOKENS})")
+    if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int32 and tuple(lengths.shape) == (B,)):
+        raise ValueError(f"{who}: lengths must be a ({B},) int32 tensor on the GPU")
+    segtab = _segment_table(segments, B, w.device, who) if segments is not None else None
+    K = segtab.shape[1] if segtab is not None else 0
+    w = w.detach().contiguous()
+    scratch = _workspace("rollout", w.device, lib.egx_attention_rollout_scratch(L, B, S))
+    out = torch.empty((B, S, S), dtype=torch.float32, device=w.device)
+    seg = torch.empty((B, S, K), dtype=torch.float32, device=w.device) if segtab is not None else None
+    check(lib.egx_attention_rollout(w.data_ptr(), L, B, S, ptr(lengths.contiguous()) if lengths is not None else None, ptr(segtab), K, ptr(scratch),
+                                    ptr(out), ptr(seg), _stream()))
+    return out if seg is None else (out, seg)
+
+
+@dataclass
+class AttentionRecord:
+    """What one encoder call left in an AttentionRecorder (None: not asked for). weights (L', B, S, S) and by_segment (L', B, S, K) of the
+    selected layers; rollout (B, S, S) and rollout_by_segment (B, S, K) over ALL layers; segments: the (B, K) int32 host table of per-clip
+    segment lengths that was used; layers: the selected layers; impl: last_encoder_impl() of the call. A ragged batch: S = max_b S_b, zeros
+    beyond each clip."""
+    weights: Optional[torch.Tensor] = None
+    by_segment: Optional[torch.Tensor] = None
+    rollout: Optional[torch.Tensor] = None
+    rollout_by_segment: Optional[torch.Tensor] = None
+    segments: Optional[torch.Tensor] = None
+    layers: tuple = ()
+    impl: str = ""
+
+
+class AttentionRecorder:
+    """Context manager: while active, every encoder forward of this process (EncoderFn, encoder_ragged, RaggedEncoderFn) is followed by
+    egx_encoder_self_weights on its own `saved`, and by the rollout if asked for; one AttentionRecord per call in `records`. The forwards
+    themselves issue the launches they issue without it. Inference only; not for capture in a hipGraph across calls of different shapes."""
+
+    def __init__(self, weights: bool = True, by_segment: bool = True, rollout: bool = False, layers=None, max_bytes: int = 1 << 30):
+        if not (weights or by_segment or rollout):
+            raise ValueError("record_attention: nothing to record (weights, by_segment and rollout are all off)")
+        if layers is not None:
+            layers = tuple(int(l) for l in layers)
+            if not layers or len(set(layers)) != len(layers) or list(layers) != sorted(layers) or layers[0] < 0:
+                raise ValueError(f"record_attention: layers must be distinct ascending layer indices, got {layers}")
+        self.weights, self.by_segment, self.rollout, self.layers, self.max_bytes = bool(weights), bool(by_segment), bool(rollout), layers, int(max_bytes)
+        self.records: List[AttentionRecord] = []
+        self._prev, self.last_call = None, None
+
+    def __enter__(self):
+        global _attention_sink
+        self._prev, _attention_sink = _attention_sink, self
+        return self
+
+    def __exit__(self, *exc):
+        global _attention_sink
+        _attention_sink = self._prev
+        return False
+
+    def plan(self, B: int, S: int, K: int, L: int, d_model: int, n_heads: int):
+        """Host checks of one call (ValueError before any device work): the limits, the layer selection and the byte budget. Returns
+        (selected layers, layers whose weights are computed, bytes)."""
+        if L < 1:
+            raise ValueError("record_attention: the encoder has no layers (its forward keeps no Q | K | V)")
+        if n_heads < 1 or d_model % n_heads:
+            raise ValueError(f"record_attention: d_model = {d_model} is not divisible by {n_heads} heads")
+        check_self_weights(d_model // n_heads, S, K)
+        sel = self.layers if self.layers is not None else tuple(range(L))
+        if sel[-1] >= L:
+            raise ValueError(f"record_attention: layers = {sel} but the encoder has {L} layers")
+        run = tuple(range(L)) if self.rollout else sel          # (the rollout multiplies every layer)
+        plane = B * S * S * 4
+        out_bytes = (len(sel) * plane if self.weights else 0) + (len(sel) * B * S * K * 4 if self.by_segment else 0)
+        tmp_bytes = 0
+        if self.rollout:
+            out_bytes += plane + (B * S * K * 4 if self.by_segment else 0)
+            tmp_bytes += min(L - 1, 2) * plane + (L * plane if not (self.weights and sel == run) else 0)
+        if out_bytes + tmp_bytes > self.max_bytes:
+            raise ValueError(f"record_attention: B = {B}, S = {S}, K = {K}, {len(sel)} of {L} layers need {out_bytes} bytes of outputs and "
+                             f"{tmp_bytes} bytes of scratch, above max_bytes = {self.max_bytes}; select fewer layers (layers=), drop the "
+                             f"(L', B, S, S) weights (weights=False) or raise max_bytes")
+        return sel, run, out_bytes + tmp_bytes
+
+    def __call__(self, lib, cfg, segs, B: int, lengths, spec: EncoderSpec, saved: torch.Tensor, device):
+        if spec.training:
+            raise ValueError("record_attention is inference-only: the encoder call ran in training mode (the reference's train-mode weights are "
+                             "post-dropout and are not modelled)")
+        K, L = len(spec.segments), spec.n_layers
+        if lengths is None:
+            S = sum(ss.T for ss in spec.segments)
+            table = torch.tensor([[ss.T for ss in spec.segments]] * B, dtype=torch.int32)
+        else:
+            S = int(lengths.sum(1).max())
+            table = lengths.clone()
+        sel, run, _ = self.plan(B, S, K, L, spec.d_model, spec.n_heads)
+        cfg2 = Config.from_buffer_copy(cfg)         # the call's own configuration; eval mode: its dropout probabilities were not used
+        cfg2.p_drop = cfg2.p_pos = cfg2.p_feat = 0.0
+        cfg2.ce = cfg2.token_ce = None
+        mask = sum(1 << l for l in run)
+        need_w = self.weights or self.rollout
+        w = torch.empty((len(run), B, S, S), dtype=torch.float32, device=device) if need_w else None
+        seg = torch.empty((len(run), B, S, K), dtype=torch.float32, device=device) if self.by_segment else None
+        try:
+            check(lib.egx_encoder_self_weights(C.byref(cfg2), segs, B, lengths.data_ptr() if lengths is not None else None,
+                                               int(spec.head_n_out or spec.token_ce or 0), ptr(saved), mask, ptr(w), ptr(seg), _stream()))
+        except _lib.EgxError as e:
+            raise ValueError(str(e)) from None
+        # (test infrastructure: what the stage hooks need to read this very call's Q | K | V back, tests/test_gpu_enc_attn.py)
+        self.last_call = dict(cfg=cfg2, segs=segs, B=B, lengths=lengths, head_n_out=int(spec.head_n_out or spec.token_ce or 0), saved=saved)
+        rec = AttentionRecord(segments=table, layers=sel, impl=last_encoder_impl())
+        pick = None if sel == run else torch.tensor([run.index(l) for l in sel], dtype=torch.int64, device=device)
+        if self.rollout:
+            lens = (lengths.sum(1).to(torch.int32).to(device) if lengths is not None else None)
+            segtab = table.to(device) if self.by_segment else None
+            r = attention_rollout(w, segments=segtab, lengths=lens)
+            rec.rollout, rec.rollout_by_segment = (r if self.by_segment else (r, None))
+        if self.weights:
+            rec.weights = w if pick is None else w.index_select(0, pick)
+        if self.by_segment:
+            rec.by_segment = seg if pick is None else seg.index_select(0, pick)
+        self.records.append(rec)
+
+
+def _attention_unserved(what: str) -> None:
+    """Called where an encoder call takes a path whose attention weights are not served: a ValueError while a recorder is active."""
+    if _attention_sink is not None:
+        raise ValueError(f"record_attention: {what} is not served (egx_encoder_self_weights)")
+
+
+def encoder_attention(spec: EncoderSpec, feats: Sequence[torch.Tensor], task_embed, pos_table, ln_w, ln_b, proj: Sequence[torch.Tensor],
+                      layer_params: Sequence[torch.Tensor], head_params: Sequence[torch.Tensor] = (), lengths: Optional[torch.Tensor] = None,
+                      weights: bool = True, by_segment: bool = True, rollout: bool = False, layers=None, max_bytes: int = 1 << 30):
+    """The no-autograd forward of encoder() (lengths: encoder_ragged()) followed by egx_encoder_self_weights on its `saved`, and the rollout if
+    asked for. Returns (the forward's output, AttentionRecord). The output has the bits of the same call without the record."""
+    if spec.training:
+        raise ValueError("encoder_attention is inference-only (spec.training is set)")
+    K, L, B = len(spec.segments), spec.n_layers, feats[0].shape[0]
+    rec = AttentionRecorder(weights, by_segment, rollout, layers, max_bytes)
+    S = sum(ss.T for ss in spec.segments) if lengths is None else int(lengths.sum(1).max())
+    rec.plan(B, S, K, L, spec.d_model, spec.n_heads)            # (refusals before any device work)
+    with torch.no_grad(), rec:
+        if lengths is None:
+            out = encoder(spec, feats, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params)
+        else:
+            out = encoder_ragged(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params)
+    return out, rec.records[-1]

@@ -122,6 +122,7 @@ class TaskTranslationPromptTransformer(nn.Module, TranslatorMixin, DecoderMixin)
     def _encode_ragged(self, task, lam_feat, ttm_feat, asd_feat, lengths, *, train: bool):
         """encode_features(..., lengths=) (train False: functional.encoder_ragged_tokens) and encode_features_ragged (train True:
         functional.encoder_ragged_tokens_train). The lengths are checked (host work) before any device work."""
+        self._egx_attention_unserved("a ragged batch on the wide path")
         feats, segs, projs = self._encoder_segments(task, lam_feat, ttm_feat, asd_feat)
         lens = self._ragged_lengths(task, feats, lengths)
         if train:

@@ -155,6 +155,7 @@ class TaskFusionMFTransformer(nn.Module, TranslatorMixin):
 
     def forward_features(self, pnr_feat, oscc_feat):
         """(B, 16, 8192) x 2 -> (B, 1 | ., num_classes)."""
+        self._egx_attention_unserved("the pre-LN simple_vit encoder (composed from unit operators)")
         comp = self.egx_compute
         B, S, d = pnr_feat.shape[0], pnr_feat.shape[1] + oscc_feat.shape[1], self.feature_dim
         if S != self.sequence_len:

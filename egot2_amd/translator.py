@@ -5,6 +5,7 @@ CONTAINERS so that state_dict keys, shapes and default initialisation are byte-c
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List, Optional, Sequence
 
@@ -130,6 +131,57 @@ class TranslatorMixin:
             raise ValueError(f"{subject} inference-only: run them under torch.no_grad() / torch.inference_mode() "
                              "(or with every parameter frozen)")
 
+    # ---- the encoder's self-attention weights (functional.AttentionRecorder, egx_encoder_self_weights) ----
+    @contextlib.contextmanager
+    def record_attention(self, weights: bool = True, by_segment: bool = True, rollout: bool = False, layers=None, max_bytes: int = 1 << 30):
+        """Context manager: while active, every encoder call of this model (forward, forward_features, the EgoT2-g encode / predict*, the
+        d = 128 forward_features(..., lengths=) / forward_features_ragged(..., lengths=) with host lengths) also records the head-averaged
+        self-attention weights of its encoder layers, what a forward hook on a patched reference layer (self_attn(..., need_weights=True))
+        sees. Yields the recorder; each call appends one functional.AttentionRecord to its `records`: weights (L', B, S, S), by_segment
+        (L', B, S, K) = the weights summed over every auxiliary task's tokens, rollout (B, S, S) and rollout_by_segment (B, S, K) (attention
+        rollout over all layers), segments (the per-clip segment lengths), impl. layers: the layers to return (default: all). A ragged batch:
+        S = max_b S_b, zeros beyond each clip. The calls return the bits they return without it and issue the same launches, followed by one
+        launch per recorded layer (and the rollout's). Inference only (eval mode, no autograd graph), as return_attention in the decoder:
+        ValueError otherwise. A call whose outputs plus scratch exceed max_bytes raises ValueError naming the sizes before any device work
+        (layers= and weights=False are the ways down); configurations the library does not serve raise ValueError with its text."""
+        rec = F_egx.AttentionRecorder(weights, by_segment, rollout, layers, max_bytes)
+        self._egx_check_recording()
+        prev, self._egx_recorder = getattr(self, "_egx_recorder", None), rec
+        try:
+            yield rec
+        finally:
+            self._egx_recorder = prev
+
+    def _egx_check_recording(self):
+        if self.training:
+            raise ValueError("record_attention is inference-only: call model.eval() first (the reference's train-mode weights are post-dropout "
+                             "and are not modelled)")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("record_attention is inference-only: run it under torch.no_grad() / torch.inference_mode() (or with every "
+                             "parameter frozen)")
+
+    def _egx_attention_unserved(self, what: str):
+        """For the encoder paths egx_encoder_self_weights does not serve: a ValueError while record_attention is active."""
+        if getattr(self, "_egx_recorder", None) is not None:
+            raise ValueError(f"record_attention: {what} is not served (egx_encoder_self_weights)")
+
+    def _egx_recorded(self, feats, segments, encoder, lengths, call):
+        """Run `call` (an encoder call of this model) under the model's recorder: the host checks first, no device work on a refusal."""
+        rec = self._egx_recorder
+        self._egx_check_recording()
+        B = feats[0].shape[0]
+        if lengths is None:
+            S = sum(s.T for s in segments)
+        elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            raise ValueError("record_attention: the capacity form of a ragged batch (device lengths) is not served (egx_encoder_self_weights)")
+        else:
+            S = int(F_egx.ragged_lengths(lengths, B, [s.T for s in segments]).sum(1).max())
+        layer0 = encoder.layers[0] if len(encoder.layers) else None
+        rec.plan(B, S, len(segments), len(encoder.layers), layer0.self_attn.embed_dim if layer0 is not None else 0,
+                 layer0.self_attn.num_heads if layer0 is not None else 1)
+        with rec:
+            return call()
+
     def _egx_encode(self, feats: Sequence[torch.Tensor], segments: List[SegmentSpec], *, encoder: nn.TransformerEncoder,
                     ln: nn.LayerNorm, projs: Sequence[Optional[nn.Linear]], task_embed: Optional[torch.Tensor],
                     pos_table: Optional[torch.Tensor], p_drop: float, p_pos: float = 0.0, p_feat: float = 0.0,
@@ -143,6 +195,10 @@ class TranslatorMixin:
         lengths: a ragged batch (inference only): (B,) or (B, K) frame counts in SEGMENT order (functional.ragged_lengths) of the padded
         feats; returns logits (B, n_out) with a head, else the first segment's rows of every clip packed, (sum_b T_{b,0}, d)
         (functional.encoder_ragged). out_tokens is then ignored: the first segment is what leaves the call."""
+        if getattr(self, "_egx_recorder", None) is not None and F_egx._attention_sink is not self._egx_recorder:
+            return self._egx_recorded(feats, segments, encoder, lengths, lambda: self._egx_encode(
+                feats, segments, encoder=encoder, ln=ln, projs=projs, task_embed=task_embed, pos_table=pos_table, p_drop=p_drop, p_pos=p_pos,
+                p_feat=p_feat, head=head, out_tokens=out_tokens, ce=ce, token_ce=token_ce, lengths=lengths))
         if lengths is not None:
             return self._egx_encode_ragged(feats, segments, lengths, encoder=encoder, ln=ln, projs=projs, task_embed=task_embed,
                                            pos_table=pos_table, head=head, ce=ce, token_ce=token_ce)
@@ -181,6 +237,10 @@ class TranslatorMixin:
         """Ragged batch through the differentiable path (functional.encoder_ragged_train), in train and eval mode, with and without grad.
         `lengths`: (B, K) int32 host tensor in SEGMENT order (functional.ragged_lengths) - or, with capacity = (B_cap, tok_cap) and a status
         word, the (B_cap, K) int32 DEVICE tensor of the capturable form."""
+        if getattr(self, "_egx_recorder", None) is not None and F_egx._attention_sink is not self._egx_recorder:
+            return self._egx_recorded(feats, segments, encoder, lengths, lambda: self._egx_train_ragged(
+                feats, segments, lengths, encoder=encoder, ln=ln, projs=projs, task_embed=task_embed, pos_table=pos_table, p_drop=p_drop,
+                p_pos=p_pos, head=head, ce=ce, capacity=capacity, status=status))
         if self.egx_defer_small:
             raise ValueError("ragged training: the staged backward (egx_defer_small) is not supported; clear it for ragged batches")
         if ce is not None and head is None:

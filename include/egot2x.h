@@ -599,6 +599,51 @@ int egx_ragged_stage_info(const egx_config* cfg, const egx_segment* segs, int B,
 int egx_ragged_stage_read(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved,
                           const void* scratch, int item, int layer, void* out, void* stream);
 
+/* ---- ABI v27 additions (new symbols only, as v19 to v26: EGX_ABI_VERSION stays 18): the encoder's self-attention weights as an output -----
+ * The head-averaged self-attention weights of the translators' nn.TransformerEncoder layers: which auxiliary task's tokens, at which time
+ * steps, every token reads (the interpretability claim of the translator design). The reference's nn.TransformerEncoderLayer calls
+ * self_attn(..., need_weights=False) (torch/nn/modules/transformer.py _sa_block), so there a user patches the layer; here the weights are
+ * recomputed from the Q | K | V rows every forward keeps in `saved`, by one launch per layer behind the forward. No forward launch changes.
+ *   w[b, i, j]   = (1 / H) sum_h softmax_j(q[b, i, h, :] . k[b, j, h, :] / sqrt(dh))      i, j < S_b
+ *   seg[b, i, t] = sum_{j in segment t of clip b} w[b, i, j]                                 t < K
+ * Scores, max, exp, sum and normalisation in fp32; products exact (v_mfma_f32_16x16x4_f32; bf16 operands are widened first); heads added in
+ * head order, then one multiplication by 1 / H; segment sums in key order; no atomics: a clip's rows do not depend on its place in the batch.
+ *
+ * egx_self_attention_weights: the primitive, on the caller's tensors (fp32, or bf16 with operands_bf16), addressed as in
+ * egx_cross_attention_weights: row pointer + row stride in elements (>= H * dh, a multiple of 8; q and k 16-byte aligned), head h at columns
+ * [h * dh, (h + 1) * dh). rowtab: DEVICE int[B][2] = (first row, S_b) of clip b in q and k alike (NULL: rows b * S, S_b = S); S_b is
+ * clamped to 0 .. S; S_b = 0 is an empty slot (zeros written, nothing read). segtab: DEVICE int[B][K] segment lengths of every clip
+ * (K <= 16; needed with seg_out). dh in {16, 32, 64, 96, 128}, 1 <= S <= 512. w_out: row b * S + i at w_out + (b * S + i) * ldw, S entries
+ * written (entries j >= S_b and rows i >= S_b are exact zeros), ldw >= S; seg_out (B, S, K). Either output may be NULL (not both): seg_out
+ * alone never writes w to memory. A workgroup owns 16 query rows of a clip, so a clip's K rows are read once per 16 query rows.
+ *
+ * egx_attention_rollout: R_l = ((w_l + I) / 2) R_{l-1}, R_0 = I (Abnar & Zuidema 2020) per clip over w (L, B, S, S) fp32, each product an
+ * fp32 fma chain in ascending k; L = 1 gives exactly (w_1 + I) / 2. rowlen: DEVICE int[B] tokens per clip (NULL: S), zeros beyond them.
+ * scratch: egx_attention_rollout_scratch(L, B, S) bytes (two (B, S, S) buffers the products ping-pong between; the last one goes straight
+ * to `out`). out (B, S, S) and / or seg_out (B, S, K), the per-task sums of the rollout through the same segment sums.
+ *
+ * egx_encoder_self_weights: right behind a forward of the same configuration on the same stream (egx_encoder_fwd, egx_translator_fwd;
+ * with `lengths`, HOST (B, K) frame counts: egx_ragged_train_fwd with training = 0), from that call's `saved`. Layer l's Q | K are found at
+ * the producers' own offsets (the 48-row tile grid of the d = 128 kernels, fp32; N x 3d bf16 of the wide path; N x 3d fp32 of the generic
+ * path); a ragged call's batch table is read in place from `saved`. layer_mask: bit l selects layer l; the L' selected layers are written
+ * in layer order to w_out (L', B, S, S) and seg_out (L', B, S, K) (either may be NULL), K = n_segments, S = the (longest) clip's tokens, one
+ * launch per selected layer. head_n_out: as in the stage hooks (the offsets in `saved` do not depend on it).
+ * All three are asynchronous and capturable. Refused before any device work (egx_last_error): null pointers, dh outside the set, S outside
+ * 1 .. 512, strides below H * dh or not a multiple of 8 elements, q or k not 16-byte aligned, ldw < S, p_drop / p_pos / p_feat > 0 (the
+ * reference's train-mode weights are post-dropout and not modelled), a configuration whose forward keeps no Q | K | V (no layers).
+ * OUT OF SCOPE here, refused likewise: the pre-LN simple_vit encoder (composed from unit operators, no `saved` of this layout), the head
+ * dims 256 / 512 of the d = 2048 recipe, ragged batches on the wide path (egx_ragged_encode*), and the capacity form with device lengths
+ * (egx_ragged_cap_*: `lengths` here is a host array). */
+int egx_self_attention_weights(const void* q, int ldq, const void* k, int ldk, int operands_bf16, const int* rowtab /* DEVICE int[B][2] or NULL */,
+                               const int* segtab /* DEVICE int[B][K] or NULL */, int K, int B, int H, int dh, int S, float* w_out, int ldw,
+                               float* seg_out, void* stream);
+size_t egx_attention_rollout_scratch(int L, int B, int S);
+int egx_attention_rollout(const float* w /* (L, B, S, S) */, int L, int B, int S, const int* rowlen /* DEVICE int[B] or NULL */,
+                          const int* segtab /* DEVICE int[B][K] or NULL */, int K, void* scratch, float* out, float* seg_out, void* stream);
+int egx_encoder_self_weights(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths /* HOST (B, K) or NULL */, int head_n_out,
+                             const void* saved, uint64_t layer_mask, float* w_out /* (L', B, S, S) or NULL */,
+                             float* seg_out /* (L', B, S, K) or NULL */, void* stream);
+
 /* Fused FFN weight gradients (d_model = 128): dW1 += dH^T x1, db1 += colsum(dH), dW2 += g^T H where
  * H = dropout(relu(x1 W1^T + b1)) and dH = (g W2) .* mask are recomputed on chip. x1, g: (N, 128); S = tokens per
  * clip (dropout keying). scratch: egx_ffn_dw_scratch() bytes. Replaces the autograd of linear1/ReLU/linear2 weight
