@@ -89,6 +89,20 @@ class LrSchedule(C.Structure):
                 ("factors", _fp), ("n", C.c_int64)]
 
 
+EGX_GRAD_NORM_TABLE = 32
+
+
+class GuardBlock(C.Structure):
+    """egx_guard_block: what egx_grad_norm leaves in device memory (40 bytes; train.GradGuard views a 5-word int64 tensor as its fields)."""
+    _fields_ = [("norm", C.c_double), ("coef", C.c_float), ("apply", C.c_int32), ("steps", C.c_int64), ("skipped", C.c_int64),
+                ("clipped", C.c_int64)]
+
+
+class GradNormCfg(C.Structure):
+    """egx_grad_norm_cfg: the clip threshold and the skip rule of one egx_grad_norm call (by value in the launch: baked into a capture)."""
+    _fields_ = [("max_norm", C.c_double), ("has_max_norm", C.c_int), ("skip_nonfinite", C.c_int)]
+
+
 class DecConfig(C.Structure):
     _fields_ = [("d_model", C.c_int), ("n_heads", C.c_int), ("d_ff", C.c_int), ("n_layers", C.c_int), ("vocab", C.c_int),
                 ("sy", C.c_int), ("S", C.c_int), ("ln_eps", C.c_float), ("compute", C.c_int), ("p_drop", C.c_float),
@@ -285,6 +299,15 @@ SIGNATURES = {
                                        C.c_float, C.c_int, C.c_float, _fp]),
     "egx_sgd_step": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                C.c_float, _fp]),
+    # ABI v28 additions: the gradient norm / clip / non-finite guard of the captured step (bufs and ns are host arrays; guard a device address)
+    "egx_grad_norm_scratch_bytes": (C.c_size_t, [C.POINTER(C.c_size_t), C.c_int]),
+    "egx_grad_norm": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, _fp, C.c_size_t, C.POINTER(GradNormCfg), _fp, _fp]),
+    "egx_counter_add_gated": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
+    "egx_lr_update_gated": (C.c_int, [C.POINTER(LrSchedule), _fp, C.POINTER(C.c_double), C.c_int, _fp, _fp, _fp]),
+    "egx_adam_step_guarded": (C.c_int, [_fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_int, _fp, _fp]),
+    "egx_sgd_step_guarded": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                       _fp, _fp]),
     # ABI v18, additions: the LTA criterion in one launch (col0 / C / ks are host int arrays)
     "egx_segmented_ce_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "egx_segmented_ce": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

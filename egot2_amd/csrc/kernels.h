@@ -127,6 +127,23 @@ int lr_update(int kind, long long warmup, long long t_total, long long T_max, do
               int64_t* step, const double* base_lr, int n_groups, float* lr_out, hipStream_t st);
 int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
              float dampening, float wd, int nesterov, float grad_scale, hipStream_t st);
+// The guard block of the clipped / guarded step (the layout of the C ABI's egx_guard_block; grad_guard.hip writes it, the twins below read it)
+struct GuardBlock {
+    double norm; float coef; int32_t apply; int64_t steps, skipped, clipped;
+};
+// train.hip: the bump and the updates behind a guard (no store when guard->apply == 0; grad_scale = guard->coef; lr = *lr_dev, or lr by value)
+int counter_add_gated(int64_t* c, int64_t inc, const GuardBlock* guard, hipStream_t st);
+int lr_update_gated(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
+                    int64_t* step, const double* base_lr, int n_groups, float* lr_out, const GuardBlock* guard, hipStream_t st);
+int adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, const int64_t* step, const float* lr_dev, float lr, float b1,
+                      float b2, float eps, float wd, int decoupled, const GuardBlock* guard, hipStream_t st);
+int sgd_step_guarded(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+                     float dampening, float wd, int nesterov, const GuardBlock* guard, hipStream_t st);
+// grad_guard.hip: the fp64 norm of G flat fp32 buffers in a fixed order, and the skip / clip decision (two launches per GRAD_NORM_TABLE buffers + 1)
+constexpr int GRAD_NORM_TABLE = 32, GRAD_NORM_MAX_BLOCKS = 2048;
+size_t grad_norm_scratch_bytes(const size_t* ns, int n_bufs);
+int grad_norm(const float* const* bufs, const size_t* ns, int n_bufs, void* scratch, size_t scratch_bytes, double max_norm, int has_max_norm,
+              int skip_nonfinite, GuardBlock* guard, hipStream_t st);
 
 // seg_ce.hip: the LTA criterion (per-(future step, head) mean cross-entropies summed, top-k counts, d loss / d logits) in one launch
 constexpr int SEG_CE_MAX_HEADS = 4, SEG_CE_MAX_KS = 4, SEG_CE_MAX_CLASSES = 2048, SEG_CE_MAX_ROWS = 1 << 28;

@@ -11,6 +11,9 @@
 //   lr_update     HOI/optimizers/lta/lr_scheduler.py:11-41 (lr_factory, "interval": "step"): the per-step learning rate as a
 //                 function of the device step count, so that a replay runs the schedule too.
 //   sgd_step      HOI/optimizers/lta/optimizer.py:54-62 (torch.optim.SGD; HOI/configs/recognition/ts_ar.yaml:39-45).
+//   *_gated / *_guarded   the bump (counter_add, lr_update) and the updates (adam, sgd) behind the guard block grad_guard.hip writes: no store
+//                 when the step is skipped (a non-finite gradient), else the same update text with grad_scale = the clip coefficient in
+//                 device memory. The unguarded kernels and entry points stay as they are.
 #include "common.h"
 #include "kernels.h"
 
@@ -433,6 +436,18 @@ __global__ __launch_bounds__(256) void adam_dev_lr_kernel(float* __restrict__ p,
     const float lr = *lr_dev;
     EGX_ADAM_UPDATE
 }
+// Behind a guard (grad_guard.hip): no store when the step is skipped, else the same text with grad_scale = the clip coefficient the norm
+// launches left in device memory (1.0f: the bits of the kernels above). lr: *lr_dev, or lr_val when lr_dev == NULL.
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, size_t n, const int64_t* __restrict__ step,
+                                                         const float* __restrict__ lr_dev, float lr_val, float b1, float b2, float eps,
+                                                         float wd, int decoupled, const GuardBlock* __restrict__ guard) {
+    if (guard->apply == 0) return;
+    const float grad_scale = guard->coef;
+    const float lr = lr_dev ? *lr_dev : lr_val;
+    EGX_ADAM_UPDATE
+}
 #undef EGX_ADAM_UPDATE
 
 // ---- per-step learning-rate schedule, on the device -------------------------------------------------------------------------
@@ -447,10 +462,9 @@ struct LrUpdateArgs {
     const double* factors;
     double base_lr[LR_MAX_GROUPS];
 };
-__global__ void lr_update_kernel(int64_t* step, LrUpdateArgs a, float* lr_out) {
+// f(k) and the learning rates of update k: shared by lr_update_kernel and its gated twin, so the closed forms stand once.
+__device__ __forceinline__ void lr_write(const LrUpdateArgs& a, long long t, float* lr_out) {
 #pragma clang fp contract(off)
-    const long long t = *step + 1;
-    *step = t;
     const long long k = t > 1 ? t - 1 : 0;
     const double pi = 3.141592653589793;
     double f = 1.0;
@@ -471,9 +485,23 @@ __global__ void lr_update_kernel(int64_t* step, LrUpdateArgs a, float* lr_out) {
     }
     for (int g = 0; g < a.n_groups; ++g) lr_out[g] = (float)(a.base_lr[g] * f);
 }
+__global__ void lr_update_kernel(int64_t* step, LrUpdateArgs a, float* lr_out) {
+    const long long t = *step + 1;
+    *step = t;
+    lr_write(a, t, lr_out);
+}
+// Behind a guard: a skipped step leaves the count and the learning rates alone, so the schedule index is the number of APPLIED updates.
+__global__ void lr_update_gated_kernel(int64_t* step, LrUpdateArgs a, float* lr_out, const GuardBlock* guard) {
+    if (guard->apply == 0) return;
+    const long long t = *step + 1;
+    *step = t;
+    lr_write(a, t, lr_out);
+}
 
-int lr_update(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
-              int64_t* step, const double* base_lr, int n_groups, float* lr_out, hipStream_t st) {
+static int lr_update_launch(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors,
+                            long long n_factors, int64_t* step, const double* base_lr, int n_groups, float* lr_out, const GuardBlock* guard,
+                            bool gated, hipStream_t st) {
+    EGX_CHECK(!gated || guard, "lr_update_gated: null pointer argument (guard)");
     EGX_CHECK(step && base_lr && lr_out, "lr_update: null pointer argument");
     EGX_CHECK(kind >= LR_CONSTANT && kind <= LR_TABLE, "lr_update: schedule kind %d outside 0..%d", kind, (int)LR_TABLE);
     EGX_CHECK(n_groups >= 1 && n_groups <= LR_MAX_GROUPS, "lr_update: n_groups=%d outside 1..%d", n_groups, LR_MAX_GROUPS);
@@ -487,9 +515,18 @@ int lr_update(int kind, long long warmup, long long t_total, long long T_max, do
     a.kind = kind; a.n_groups = n_groups; a.warmup = warmup; a.t_total = t_total; a.T_max = T_max; a.n_factors = n_factors;
     a.cycles = cycles; a.factors = factors;
     for (int g = 0; g < LR_MAX_GROUPS; ++g) a.base_lr[g] = g < n_groups ? base_lr[g] : 0.0;
-    hipLaunchKernelGGL(lr_update_kernel, dim3(1), dim3(1), 0, st, step, a, lr_out);
+    if (gated) hipLaunchKernelGGL(lr_update_gated_kernel, dim3(1), dim3(1), 0, st, step, a, lr_out, guard);
+    else hipLaunchKernelGGL(lr_update_kernel, dim3(1), dim3(1), 0, st, step, a, lr_out);
     EGX_LAUNCH_CHECK();
     return 0;
+}
+int lr_update(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
+              int64_t* step, const double* base_lr, int n_groups, float* lr_out, hipStream_t st) {
+    return lr_update_launch(kind, warmup, t_total, T_max, cycles, factors, n_factors, step, base_lr, n_groups, lr_out, nullptr, false, st);
+}
+int lr_update_gated(int kind, long long warmup, long long t_total, long long T_max, double cycles, const double* factors, long long n_factors,
+                    int64_t* step, const double* base_lr, int n_groups, float* lr_out, const GuardBlock* guard, hipStream_t st) {
+    return lr_update_launch(kind, warmup, t_total, T_max, cycles, factors, n_factors, step, base_lr, n_groups, lr_out, guard, true, st);
 }
 
 // ---- SGD (torch.optim.SGD semantics) over one flat fp32 buffer --------------------------------------------------------------
@@ -511,36 +548,48 @@ __device__ __forceinline__ float sgd_element(const SgdArgs& a, float lr, bool fi
     }
     return pp - lr * gg;
 }
+// EGX_SGD_UPDATE is the body of sgd_kernel and of its guarded twin over an SgdArgs `a` (a macro for the reason EGX_ADAM_UPDATE is one).
+#define EGX_SGD_UPDATE                                                                                                   \
+    const float lr = a.lr_dev ? *a.lr_dev : a.lr;                                                                        \
+    const bool mom = a.buf != nullptr;                                                                                   \
+    const bool first = mom && *a.step == 1;                                                                              \
+    const size_t stride = (size_t)gridDim.x * 256 * 4;                                                                   \
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < a.n; i += stride) {                                \
+        if (VEC && i + 4 <= a.n) {                                                                                       \
+            const float4 pv = *reinterpret_cast<const float4*>(a.p + i), gv = *reinterpret_cast<const float4*>(a.g + i); \
+            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);                                                                 \
+            if (mom && !first) bv = *reinterpret_cast<const float4*>(a.buf + i);                                         \
+            float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ba[4] = {bv.x, bv.y, bv.z, bv.w};                                    \
+            const float ga[4] = {gv.x, gv.y, gv.z, gv.w};                                                                \
+_Pragma("unroll")                                                                                                        \
+            for (int e = 0; e < 4; ++e) pa[e] = sgd_element(a, lr, first, pa[e], ga[e], mom ? &ba[e] : nullptr);         \
+            *reinterpret_cast<float4*>(a.p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);                               \
+            if (mom) *reinterpret_cast<float4*>(a.buf + i) = make_float4(ba[0], ba[1], ba[2], ba[3]);                    \
+        } else {                                                                                                         \
+            const size_t end = i + 4 < a.n ? i + 4 : a.n;                                                                \
+            for (size_t j = i; j < end; ++j) {                                                                           \
+                float b = (mom && !first) ? a.buf[j] : 0.f;                                                              \
+                a.p[j] = sgd_element(a, lr, first, a.p[j], a.g[j], mom ? &b : nullptr);                                  \
+                if (mom) a.buf[j] = b;                                                                                   \
+            }                                                                                                            \
+        }                                                                                                                \
+    }
 template <bool VEC>
 __global__ __launch_bounds__(256) void sgd_kernel(SgdArgs a) {
-    const float lr = a.lr_dev ? *a.lr_dev : a.lr;
-    const bool mom = a.buf != nullptr;
-    const bool first = mom && *a.step == 1;
-    const size_t stride = (size_t)gridDim.x * 256 * 4;
-    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < a.n; i += stride) {
-        if (VEC && i + 4 <= a.n) {
-            const float4 pv = *reinterpret_cast<const float4*>(a.p + i), gv = *reinterpret_cast<const float4*>(a.g + i);
-            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mom && !first) bv = *reinterpret_cast<const float4*>(a.buf + i);
-            float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ba[4] = {bv.x, bv.y, bv.z, bv.w};
-            const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pa[e] = sgd_element(a, lr, first, pa[e], ga[e], mom ? &ba[e] : nullptr);
-            *reinterpret_cast<float4*>(a.p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);
-            if (mom) *reinterpret_cast<float4*>(a.buf + i) = make_float4(ba[0], ba[1], ba[2], ba[3]);
-        } else {
-            const size_t end = i + 4 < a.n ? i + 4 : a.n;
-            for (size_t j = i; j < end; ++j) {
-                float b = (mom && !first) ? a.buf[j] : 0.f;
-                a.p[j] = sgd_element(a, lr, first, a.p[j], a.g[j], mom ? &b : nullptr);
-                if (mom) a.buf[j] = b;
-            }
-        }
-    }
+    EGX_SGD_UPDATE
 }
+// Behind a guard: no store when the step is skipped, else grad_scale = the clip coefficient in device memory (a.grad_scale is not read).
+template <bool VEC>
+__global__ __launch_bounds__(256) void sgd_guard_kernel(SgdArgs a, const GuardBlock* __restrict__ guard) {
+    if (guard->apply == 0) return;
+    a.grad_scale = guard->coef;
+    EGX_SGD_UPDATE
+}
+#undef EGX_SGD_UPDATE
 
-int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
-             float dampening, float wd, int nesterov, float grad_scale, hipStream_t st) {
+static int sgd_launch(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+                      float dampening, float wd, int nesterov, float grad_scale, const GuardBlock* guard, bool guarded, hipStream_t st) {
+    EGX_CHECK(!guarded || guard, "sgd_step_guarded: null pointer argument (guard)");
     EGX_CHECK(p && g, "sgd_step: null pointer argument");
     EGX_CHECK(lr_dev || lr >= 0.f, "sgd_step: lr=%g (needs lr >= 0)", (double)lr);
     EGX_CHECK(mu >= 0.f, "sgd_step: momentum=%g (needs momentum >= 0)", (double)mu);
@@ -556,10 +605,23 @@ int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step
     const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf)) & 15) == 0;
     size_t blocks = (n / 4 + 1 + 255) / 256;
     if (blocks > SGD_MAX_BLOCKS) blocks = SGD_MAX_BLOCKS;
-    if (vec) hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    if (guarded) {
+        if (vec) hipLaunchKernelGGL(sgd_guard_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a, guard);
+        else hipLaunchKernelGGL(sgd_guard_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a, guard);
+    } else {
+        if (vec) hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    }
     EGX_LAUNCH_CHECK();
     return 0;
+}
+int sgd_step(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+             float dampening, float wd, int nesterov, float grad_scale, hipStream_t st) {
+    return sgd_launch(p, g, buf, n, step, lr_dev, lr, mu, dampening, wd, nesterov, grad_scale, nullptr, false, st);
+}
+int sgd_step_guarded(float* p, const float* g, float* buf, size_t n, const int64_t* step, const float* lr_dev, float lr, float mu,
+                     float dampening, float wd, int nesterov, const GuardBlock* guard, hipStream_t st) {
+    return sgd_launch(p, g, buf, n, step, lr_dev, lr, mu, dampening, wd, nesterov, 1.f, guard, true, st);
 }
 
 __global__ void counter_add_kernel(int64_t* c, int64_t inc) { *c += inc; }
@@ -567,6 +629,18 @@ __global__ void counter_add_kernel(int64_t* c, int64_t inc) { *c += inc; }
 int counter_add(int64_t* c, int64_t inc, hipStream_t st) {
     EGX_CHECK(c, "counter_add: null pointer");
     hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, c, inc);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ void counter_add_gated_kernel(int64_t* c, int64_t inc, const GuardBlock* guard) {
+    if (guard->apply == 0) return;
+    *c += inc;
+}
+
+int counter_add_gated(int64_t* c, int64_t inc, const GuardBlock* guard, hipStream_t st) {
+    EGX_CHECK(c && guard, "counter_add_gated: null pointer argument");
+    hipLaunchKernelGGL(counter_add_gated_kernel, dim3(1), dim3(1), 0, st, c, inc, guard);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -591,6 +665,19 @@ int adam_step_dev_lr(float* p, const float* g, float* m, float* v, size_t n, con
     size_t blocks = (n / 4 + 1 + 255) / 256;
     if (vec) hipLaunchKernelGGL(adam_dev_lr_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
     else hipLaunchKernelGGL(adam_dev_lr_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr, b1, b2, eps, wd, decoupled, grad_scale);
+    EGX_LAUNCH_CHECK();
+    return 0;
+}
+
+int adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, const int64_t* step, const float* lr_dev, float lr, float b1,
+                      float b2, float eps, float wd, int decoupled, const GuardBlock* guard, hipStream_t st) {
+    EGX_CHECK(p && g && m && v && step && guard, "adam_step_guarded: null pointer argument");
+    EGX_CHECK(lr_dev || lr >= 0.f, "adam_step_guarded: lr=%g (needs lr >= 0)", (double)lr);
+    if (n == 0) return 0;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+    size_t blocks = (n / 4 + 1 + 255) / 256;
+    if (vec) hipLaunchKernelGGL(adam_guard_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr_dev, lr, b1, b2, eps, wd, decoupled, guard);
+    else hipLaunchKernelGGL(adam_guard_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, step, lr_dev, lr, b1, b2, eps, wd, decoupled, guard);
     EGX_LAUNCH_CHECK();
     return 0;
 }

@@ -9,6 +9,9 @@ update is a single launch per buffer, with the step count in device memory (hipG
 `FusedSGD` mirrors `torch.optim.SGD` as HOI/optimizers/lta/optimizer.py:54-62 builds it on the same machinery, `LRSchedule` the reference's
 per-step learning-rate schedulers (HOI/optimizers/lta/lr_scheduler.py:11-41) evaluated on the device from that step count, and `construct_solver`
 restates construct_optimizer + lr_factory on both.
+`GradGuard` (and `grad_norm`) is what Lightning's Trainer offers as gradient_clip_val / track_grad_norm (left at their defaults by the reference,
+HHI/scripts/run_ttm.py:21, HOI/scripts/lta/run_lta.py:238) for a captured step: the fp64 gradient norm in a fixed summation order, the clip
+coefficient and the decision to skip a step with a non-finite gradient, all on the device, obeyed by the optimizers' bump and update launches.
 `LTACriterion` is the criterion of the long-term-anticipation task (HOI/tasks/lta/long_term_anticipation.py:182-203: 40 cross-entropies
 and the top-1 / top-5 errors of every (future step, head) pair) as one launch without a host synchronisation.
 `LTAValidation` is that task's validation step (:222-248: K sampled futures per clip and head, and the edit distances behind AUED,
@@ -888,6 +891,124 @@ class LRSchedule:
         return s
 
 
+class GradGuard:
+    """Gradient-norm clipping and the non-finite guard of an optimizer step, decided on the device so that a captured step (GraphedStep)
+    replays the decision: what Lightning's Trainer offers as gradient_clip_val / track_grad_norm (the reference leaves both at their defaults,
+    HHI/scripts/run_ttm.py:21, HOI/scripts/lta/run_lta.py:238). Hand it to FusedAdam / FusedSGD / construct_solver as `guard=`. Every step then
+    measures the fp64 norm of ALL its gradient buffers in a fixed summation order (egx_grad_norm: two launches, one read of the gradients),
+
+        coef  = clip_grad_norm_'s max_norm / (norm + 1e-6) where that is below 1, else 1 (1 with max_norm=None: measure and guard only)
+        apply = every gradient element is finite, or not skip_nonfinite
+
+    and the step-count / learning-rate bump and the updates obey it: a skipped step changes nothing the optimizer owns (parameters, moments,
+    momentum buffers, the step count, the scheduled learning rates - the schedule index is the number of APPLIED updates), an applied one is
+    today's update with the gradients scaled by coef, bit for bit the unguarded step while coef == 1. A gradient of 3e38 is finite: its norm
+    is held in fp64 and the step is clipped, not skipped.
+
+    `max_norm` and `skip_nonfinite` are read when a step is enqueued and are therefore baked into a capture, as the base learning rate is: a
+    changed value needs a new capture. The guard owns a per-device scratch and a 40-byte guard block; the first EAGER step creates them
+    (GraphedStep's warm-up steps do), a capture refuses to. `block` holds the device tensors for sync-free use, `result()` copies them to the
+    host. The counters (`steps`, `skipped`, `clipped`) count since construction or reset_counters(); they are not part of any state_dict."""
+
+    def __init__(self, max_norm: Optional[float] = None, skip_nonfinite: bool = True):
+        if max_norm is not None:
+            if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)):
+                raise TypeError(f"GradGuard: max_norm must be a number or None, got {type(max_norm).__name__}")
+            if not max_norm >= 0:                       # refuses a NaN too
+                raise ValueError(f"GradGuard: max_norm={max_norm} (needs max_norm >= 0)")
+        if not isinstance(skip_nonfinite, bool):
+            raise TypeError(f"GradGuard: skip_nonfinite must be a bool, got {type(skip_nonfinite).__name__}")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = skip_nonfinite
+        self._bufs: Dict[tuple, dict] = {}
+        self._last: Optional[dict] = None
+
+    def _buffers(self, device, scratch_bytes: int) -> dict:
+        device = torch.device(device)
+        key = (device.type, device.index)
+        b = self._bufs.get(key)
+        if b is None or b["scratch"].numel() < scratch_bytes:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # a buffer created inside a capture would live in that graph's private pool
+                raise RuntimeError("GradGuard: run one eager step with these gradient buffers before capturing it in a graph")
+            if b is None:
+                words = torch.zeros(5, dtype=torch.int64, device=device)      # egx_guard_block: fp64 | fp32, int32 | 3 x int64
+                b = self._bufs[key] = {"words": words, "grad_norm": words[0:1].view(torch.float64)[0],
+                                       "clip_coef": words[1:2].view(torch.float32)[0], "applied": words[1:2].view(torch.int32)[1],
+                                       "steps": words[2], "skipped": words[3], "clipped": words[4]}
+            b["scratch"] = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+        return b
+
+    def measure(self, buffers, stream=None) -> dict:
+        """Enqueue the norm and the decision over `buffers` (flat contiguous fp32 device tensors; an empty one is legal) -> `block`."""
+        lib = _lib.load()
+        buffers = list(buffers)
+        if not buffers:
+            raise ValueError("GradGuard: no gradient buffers")
+        for t in buffers:
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("GradGuard needs contiguous fp32 gradients on the GPU")
+        n = len(buffers)
+        ns = (C.c_size_t * n)(*[t.numel() for t in buffers])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in buffers])
+        need = lib.egx_grad_norm_scratch_bytes(ns, n)
+        b = self._buffers(buffers[0].device, need)
+        cfg = _lib.GradNormCfg(0.0 if self.max_norm is None else self.max_norm, int(self.max_norm is not None), int(self.skip_nonfinite))
+        if stream is None:
+            stream = torch.cuda.current_stream(buffers[0].device).cuda_stream
+        check(lib.egx_grad_norm(ptrs, ns, n, ptr(b["scratch"]), b["scratch"].numel(), C.byref(cfg), ptr(b["words"]), stream))
+        self._last = b
+        return b
+
+    @property
+    def block(self) -> dict:
+        """The device tensors of the guard block the last step wrote: `grad_norm` (fp64), `clip_coef` (fp32), `applied` (int32) and the int64
+        counters `steps`, `skipped`, `clipped`; every call or replay refreshes them. Reading them does not synchronise."""
+        if self._last is None:
+            raise RuntimeError("GradGuard: no step has run yet")
+        return {k: v for k, v in self._last.items() if k not in ("words", "scratch")}
+
+    def result(self) -> dict:
+        """The guard block on the host (one 40-byte copy; it synchronises: for logging). Before the first step: zeros."""
+        if self._last is None:
+            return {"grad_norm": 0.0, "clip_coef": 1.0, "applied": 1, "steps": 0, "skipped": 0, "clipped": 0}
+        w = self._last["words"].cpu()
+        return {"grad_norm": float(w[0:1].view(torch.float64)[0]), "clip_coef": float(w[1:2].view(torch.float32)[0]),
+                "applied": int(w[1:2].view(torch.int32)[1]), "steps": int(w[2]), "skipped": int(w[3]), "clipped": int(w[4])}
+
+    def reset_counters(self) -> "GradGuard":
+        for b in self._bufs.values():
+            b["words"][2:].zero_()
+        return self
+
+
+def grad_norm(params) -> torch.Tensor:
+    """-> the 2-norm of every `.grad` of `params` as a device fp64 scalar, without a host synchronisation (Lightning's track_grad_norm=2):
+    GradGuard's norm - fp64 sums in a fixed order over the flat buffers the gradients are views of - without an optimizer. Parameters whose
+    `.grad` is None do not count, as for torch.nn.utils.clip_grad_norm_. Eager use (it allocates its result)."""
+    if isinstance(params, torch.Tensor):
+        params = [params]
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads:
+        raise ValueError("grad_norm: no parameter has a gradient")
+    return GradGuard().measure(_grad_buffers(grads))["grad_norm"].clone()
+
+
+def _grad_buffers(grads) -> List[torch.Tensor]:
+    """The distinct flat buffers a list of gradients lives in, each as ONE whole-storage view (the buffers _FlatOptimizer.step updates: all the
+    views _GradPacker carved out of a storage count once, through it; a stand-alone gradient is its own storage)."""
+    out, seen = [], set()
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+            raise ValueError("grad_norm needs contiguous fp32 gradients on the GPU")
+        key = g.untyped_storage().data_ptr()
+        if key in seen:
+            continue
+        seen.add(key)
+        out.append(F_egx.flat_storage_view(g).reshape(-1))
+    return out
+
+
 class _Bucket:
     __slots__ = ("sig", "param", "exp_avg", "exp_avg_sq", "momentum_buffer", "keys", "numel", "members")
 
@@ -898,11 +1019,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
     with a `schedule` - the learning rates of the parameter groups in device memory, advanced by the same launch that bumps the count.
     A subclass names its state buffers (_state_keys) and enqueues its update (_update)."""
 
-    def __init__(self, params, defaults, schedule: Optional[LRSchedule]):
+    def __init__(self, params, defaults, schedule: Optional[LRSchedule], guard: Optional[GradGuard] = None):
         super().__init__(params, defaults)
         if schedule is not None and len(self.param_groups) > _lib.EGX_LR_MAX_GROUPS:
             raise ValueError(f"{type(self).__name__}: a schedule serves at most {_lib.EGX_LR_MAX_GROUPS} parameter groups, got {len(self.param_groups)}")
+        if guard is not None and not isinstance(guard, GradGuard):
+            raise TypeError(f"{type(self).__name__}: guard must be a train.GradGuard or None, got {type(guard).__name__}")
         self.schedule = schedule
+        self.guard = guard
         self._buckets: Dict[tuple, _Bucket] = {}
         self._step_dev: Optional[torch.Tensor] = None
         self._lr_dev: Optional[torch.Tensor] = None
@@ -913,6 +1037,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _update(self, lib, b: _Bucket, gflat: torch.Tensor, group, lr_dev: Optional[int], stream):
         raise NotImplementedError
+
+    def _update_guarded(self, lib, b: _Bucket, gflat: torch.Tensor, group, lr_dev: Optional[int], guard: int, stream):
+        raise NotImplementedError
+
+    def guard_result(self) -> dict:
+        """The last step's `grad_norm`, `clip_coef`, `applied` and the counters `steps`, `skipped`, `clipped` of the optimizer's GradGuard, on
+        the host. It synchronises: for logging (optimizer.guard.block holds the device tensors)."""
+        if self.guard is None:
+            raise RuntimeError(f"{type(self).__name__}: constructed without a guard (guard=GradGuard(...))")
+        return self.guard.result()
 
     def _make_bucket(self, sig, base: torch.Tensor, members, keys) -> _Bucket:
         b = _Bucket()
@@ -978,19 +1112,26 @@ class _FlatOptimizer(torch.optim.Optimizer):
             return [float(g["lr"]) for g in self.param_groups]
         return self._lr_dev[:len(self.param_groups)].tolist()
 
-    def _bump(self, lib, device, stream):
-        """Advance the device step count once per step(); with a schedule the same launch writes every group's learning rate."""
+    def _bump(self, lib, device, stream, guard: Optional[int] = None):
+        """Advance the device step count once per step(); with a schedule the same launch writes every group's learning rate. `guard` (the
+        device address of a guard block): the gated twins, which leave both alone when the step is skipped."""
         if self._step_dev is None:
             self._step_dev = torch.full((), self._resume_step, dtype=torch.int64, device=device)
         if self.schedule is None:
-            check(lib.egx_counter_add(ptr(self._step_dev), 1, stream))
+            if guard is None:
+                check(lib.egx_counter_add(ptr(self._step_dev), 1, stream))
+            else:
+                check(lib.egx_counter_add_gated(ptr(self._step_dev), 1, guard, stream))
             return
         if self._lr_dev is None:
             self._lr_dev = torch.zeros(_lib.EGX_LR_MAX_GROUPS, dtype=torch.float32, device=device)
         n = len(self.param_groups)
         base = (C.c_double * n)(*[float(g["lr"]) for g in self.param_groups])     # read here: baked into a capture
         sched = self.schedule._struct(device)
-        check(lib.egx_lr_update(C.byref(sched), ptr(self._step_dev), base, n, ptr(self._lr_dev), stream))
+        if guard is None:
+            check(lib.egx_lr_update(C.byref(sched), ptr(self._step_dev), base, n, ptr(self._lr_dev), stream))
+        else:
+            check(lib.egx_lr_update_gated(C.byref(sched), ptr(self._step_dev), base, n, ptr(self._lr_dev), guard, stream))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -1000,35 +1141,65 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 loss = closure()
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
+        if self.guard is not None:
+            self._step_guarded(lib, stream)
+            return loss
         bumped = False
         for gi, group in enumerate(self.param_groups):
-            by_base: Dict[int, Tuple[torch.Tensor, List]] = {}
-            for p in group["params"]:
-                g = p.grad
-                if g is None:
-                    continue
-                if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
-                    raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients on the GPU")
-                key = g.untyped_storage().data_ptr()        # the flat buffer this gradient was carved out of: one view per buffer,
-                ent = by_base.get(key)                       # not one per parameter (25 tensor constructions per step on the TTM translator)
-                if ent is None:
-                    ent = by_base[key] = (F_egx.flat_storage_view(g), [])
-                ent[1].append((p, g.storage_offset()))
-            for base, members in by_base.values():
+            for base, members in self._by_base(group).values():
                 if not bumped:
                     self._bump(lib, base.device, stream)
                     bumped = True
-                sig = (gi,) + tuple((id(p), off) for p, off in members) + (base.numel(),)
-                b = self._buckets.get(sig)
-                if b is not None and any(p.data_ptr() != b.param.data_ptr() + 4 * off for p, off in members):
-                    b = None                                 # somebody re-allocated a parameter: rebuild the bucket
-                if b is None:
-                    b = self._buckets[sig] = self._make_bucket(sig, base.reshape(-1), members, self._state_keys(group))
+                b = self._bucket(gi, group, base, members)
                 gflat = base.reshape(-1)
                 F_egx.note_weights_changed()       # (raw-pointer update: no version counter moves; packed-weight caches re-pack)
                 lr_dev = None if self.schedule is None else self._lr_dev.data_ptr() + 4 * gi
                 self._update(lib, b, gflat, group, lr_dev, stream)
         return loss
+
+    def _by_base(self, group) -> Dict[int, Tuple[torch.Tensor, List]]:
+        """The group's gradients by the flat buffer they are views of: storage address -> (whole-storage view, [(parameter, offset)])."""
+        by_base: Dict[int, Tuple[torch.Tensor, List]] = {}
+        for p in group["params"]:
+            g = p.grad
+            if g is None:
+                continue
+            if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+                raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients on the GPU")
+            key = g.untyped_storage().data_ptr()        # the flat buffer this gradient was carved out of: one view per buffer,
+            ent = by_base.get(key)                       # not one per parameter (25 tensor constructions per step on the TTM translator)
+            if ent is None:
+                ent = by_base[key] = (F_egx.flat_storage_view(g), [])
+            ent[1].append((p, g.storage_offset()))
+        return by_base
+
+    def _bucket(self, gi: int, group, base: torch.Tensor, members) -> _Bucket:
+        sig = (gi,) + tuple((id(p), off) for p, off in members) + (base.numel(),)
+        b = self._buckets.get(sig)
+        if b is not None and any(p.data_ptr() != b.param.data_ptr() + 4 * off for p, off in members):
+            b = None                                 # somebody re-allocated a parameter: rebuild the bucket
+        if b is None:
+            b = self._buckets[sig] = self._make_bucket(sig, base.reshape(-1), members, self._state_keys(group))
+        return b
+
+    def _step_guarded(self, lib, stream):
+        """step() behind self.guard: every group's buffers are collected first, then the norm over all of them (a buffer two groups share
+        counts once), then the gated bump, then the guarded updates."""
+        work = [(gi, group, base, members) for gi, group in enumerate(self.param_groups) for base, members in self._by_base(group).values()]
+        if not work:
+            return
+        flats, seen = [], set()
+        for _, _, base, _ in work:
+            if base.data_ptr() not in seen:
+                seen.add(base.data_ptr())
+                flats.append(base.reshape(-1))
+        guard = self.guard.measure(flats, stream)["words"].data_ptr()
+        self._bump(lib, work[0][2].device, stream, guard)
+        for gi, group, base, members in work:
+            b = self._bucket(gi, group, base, members)
+            F_egx.note_weights_changed()
+            lr_dev = None if self.schedule is None else self._lr_dev.data_ptr() + 4 * gi
+            self._update_guarded(lib, b, base.reshape(-1), group, lr_dev, guard, stream)
 
 
 class FusedAdam(_FlatOptimizer):
@@ -1037,13 +1208,16 @@ class FusedAdam(_FlatOptimizer):
     `schedule` (an LRSchedule): the learning rate of update k is param_groups[g]["lr"] * schedule.factor(k), computed on the device from the
     step count, so a captured step replays the schedule. param_groups[g]["lr"] stays the BASE learning rate; it is read when the step is
     enqueued and is therefore baked into a capture: a changed base needs a new capture. Without a schedule nothing changes: the learning
-    rate goes to egx_adam_step by value."""
+    rate goes to egx_adam_step by value.
+
+    `guard` (a GradGuard): clip the gradients to guard.max_norm and skip a step with a non-finite gradient, decided on the device per step or
+    replay; guard_result() / guard.block report it. Without one the step enqueues exactly what it did before."""
 
     def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, adamw: bool = False, schedule: Optional[LRSchedule] = None):
+                 weight_decay: float = 0.0, adamw: bool = False, schedule: Optional[LRSchedule] = None, guard: Optional[GradGuard] = None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw), schedule)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw), schedule, guard)
 
     def _state_keys(self, group):
         return ("exp_avg", "exp_avg_sq")
@@ -1058,6 +1232,11 @@ class FusedAdam(_FlatOptimizer):
                                            ptr(self._step_dev), lr_dev, group["betas"][0], group["betas"][1],
                                            group["eps"], group["weight_decay"], int(group["adamw"]), 1.0, stream))
 
+    def _update_guarded(self, lib, b, gflat, group, lr_dev, guard, stream):
+        check(lib.egx_adam_step_guarded(ptr(b.param), ptr(gflat), ptr(b.exp_avg), ptr(b.exp_avg_sq), b.numel, ptr(self._step_dev), lr_dev,
+                                        group["lr"], group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"],
+                                        int(group["adamw"]), guard, stream))
+
 
 class FusedSGD(_FlatOptimizer):
     """torch.optim.SGD (momentum, dampening, weight decay, Nesterov) with one launch per flat gradient buffer: the optimizer the reference's
@@ -1065,19 +1244,20 @@ class FusedSGD(_FlatOptimizer):
 
     state[p] holds `momentum_buffer` (a view of the bucket's buffer; absent with momentum 0) and `step` (the device step count). The first
     update ASSIGNS momentum_buffer = g, decided on the device by step == 1, as torch does on a missing buffer; with a zeroed buffer and
-    dampening 0 that equals the recurrence bit for bit. `schedule` and param_groups[g]["lr"]: as for FusedAdam.
+    dampening 0 that equals the recurrence bit for bit. `schedule`, `guard` and param_groups[g]["lr"]: as for FusedAdam (a skipped first step
+    leaves the count at 0, so the first APPLIED update assigns the buffer).
 
     load_state_dict accepts this class's state dicts and torch.optim.SGD's. A torch state dict has momentum buffers and no step count: the
     count then starts at 1, so the first-update rule does not fire and the loaded buffers are continued (and a schedule continues at k = 1:
     torch keeps its position in the scheduler's own state dict, not here)."""
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, schedule: Optional[LRSchedule] = None):
+                 nesterov: bool = False, schedule: Optional[LRSchedule] = None, guard: Optional[GradGuard] = None):
         if lr < 0 or momentum < 0 or weight_decay < 0 or not (0 <= dampening <= 1):
             raise ValueError("invalid SGD hyper-parameters")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov), schedule)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov), schedule, guard)
 
     def _state_keys(self, group):
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
@@ -1093,18 +1273,24 @@ class FusedSGD(_FlatOptimizer):
         check(lib.egx_sgd_step(ptr(b.param), ptr(gflat), ptr(buf), b.numel, ptr(self._step_dev), lr_dev, group["lr"], group["momentum"],
                                group["dampening"], group["weight_decay"], int(group["nesterov"]), 1.0, stream))
 
+    def _update_guarded(self, lib, b, gflat, group, lr_dev, guard, stream):
+        buf = b.momentum_buffer if b.keys else None
+        check(lib.egx_sgd_step_guarded(ptr(b.param), ptr(gflat), ptr(buf), b.numel, ptr(self._step_dev), lr_dev, group["lr"],
+                                       group["momentum"], group["dampening"], group["weight_decay"], int(group["nesterov"]), guard, stream))
+
 
 SOLVER_POLICIES = ("cosine", "constant", "cosine_warmup", "linear_warmup")
 
 
-def construct_solver(model, cfg, steps_in_epoch: int, lr_policy: Optional[str] = None, lr_lambda=None):
+def construct_solver(model, cfg, steps_in_epoch: int, lr_policy: Optional[str] = None, lr_lambda=None, guard: Optional[GradGuard] = None):
     """-> (optimizer, schedule): the reference's construct_optimizer (HOI/optimizers/lta/optimizer.py:15-73) plus lr_factory
     (HOI/optimizers/lta/lr_scheduler.py:11-41) restated on the fused optimizers, reading the reference's config fields: cfg.SOLVER
     .OPTIMIZING_METHOD ("sgd" | "adam" | "adamw"), .BASE_LR, .MOMENTUM, .DAMPENING, .NESTEROV, .WEIGHT_DECAY, .LR_POLICY, .WARMUP_STEPS,
     .MAX_EPOCH and cfg.BN.WEIGHT_DECAY. Two parameter groups as there: names containing "bn" take BN.WEIGHT_DECAY (the group may be empty),
     the rest SOLVER.WEIGHT_DECAY. `lr_policy` (default cfg.SOLVER.LR_POLICY): "cosine", "constant", "cosine_warmup", "linear_warmup";
     any other policy is a LambdaLR in the reference and needs `lr_lambda`, the function of the 0-based step it hands LambdaLR (for the
-    get_epoch_lr policies: lambda step: get_epoch_lr(step / steps_in_epoch, cfg)), tabulated over MAX_EPOCH * steps_in_epoch steps."""
+    get_epoch_lr policies: lambda step: get_epoch_lr(step / steps_in_epoch, cfg)), tabulated over MAX_EPOCH * steps_in_epoch steps.
+    `guard` (a GradGuard, not a field of the reference's config): handed to the optimizer."""
     S = cfg.SOLVER
     bn, rest = [], []
     for name, p in model.named_parameters():
@@ -1128,11 +1314,11 @@ def construct_solver(model, cfg, steps_in_epoch: int, lr_policy: Optional[str] =
     method = S.OPTIMIZING_METHOD
     if method == "sgd":
         opt = FusedSGD(groups, lr=S.BASE_LR, momentum=S.MOMENTUM, dampening=S.DAMPENING, weight_decay=S.WEIGHT_DECAY,
-                       nesterov=S.NESTEROV, schedule=schedule)
+                       nesterov=S.NESTEROV, schedule=schedule, guard=guard)
     elif method == "adam":
-        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), weight_decay=S.WEIGHT_DECAY, schedule=schedule)
+        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), weight_decay=S.WEIGHT_DECAY, schedule=schedule, guard=guard)
     elif method == "adamw":
-        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), adamw=True, schedule=schedule)   # the groups' weight decays override the default
+        opt = FusedAdam(groups, lr=S.BASE_LR, betas=(0.9, 0.999), adamw=True, schedule=schedule, guard=guard)   # the groups' weight decays override the default
     else:
         raise NotImplementedError(f"Does not support {method} optimizer")
     return opt, schedule
@@ -1179,7 +1365,7 @@ class GraphedStep:
     """One training step — forward, loss, backward and (optionally) the optimizer update — captured ONCE as a hipGraph and replayed.
 
     The library only enqueues kernels on the current stream and keeps what changes from step to step in device memory (the dropout seed after
-    `model.enable_device_seed()`, the optimizer's step count and - with an `LRSchedule` - its learning rates), so a replay is exact training work with fresh masks; what the capture removes is the
+    `model.enable_device_seed()`, the optimizer's step count, - with an `LRSchedule` - its learning rates and - with a `GradGuard` - the clip / skip decision of the step), so a replay is exact training work with fresh masks; what the capture removes is the
     host side of the step (Python, the autograd engine's worker thread, a dozen launches: 0.54 - 0.90 ms per step on the bench configuration with
     FusedAdam against 0.41 ms of GPU time). This is the
     loop `bench.py` times, packaged for a training script:
@@ -1224,6 +1410,8 @@ class GraphedStep:
                     t.copy_(v)
             if optimizer is not None:
                 optimizer.load_state_dict(snap_o)
+                if getattr(optimizer, "guard", None) is not None:
+                    optimizer.guard.reset_counters()       # the warm-up steps are not the caller's: a fresh step reports steps == 0
             F_egx.note_weights_changed()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)

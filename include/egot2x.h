@@ -22,6 +22,10 @@
  *       HOI/models/lta/head_helper.py:245-248,281-283).
  *   egx_gemm / egx_layernorm_* / egx_attention_*
  *       the individual ATen ops (addmm, layer_norm, multi_head_attention_forward core) for unit parity tests.
+ *   egx_grad_norm + egx_counter_add_gated / egx_lr_update_gated / egx_adam_step_guarded / egx_sgd_step_guarded
+ *       what pytorch_lightning.Trainer(gradient_clip_val=, track_grad_norm=) does around the optimizer step (the reference
+ *       constructs its Trainer with the defaults, HHI/scripts/run_ttm.py:21, HOI/scripts/lta/run_lta.py:238) and an eager
+ *       loop's torch.isfinite(loss) test, as device work a captured step replays (ABI v28 additions below).
  *
  * Conventions
  *   - All tensors are dense fp32, row-major, device memory owned by the caller (PyTorch's caching
@@ -730,6 +734,64 @@ int egx_adam_step_dev_lr(float* param, const float* grad, float* exp_avg, float*
 int egx_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n, const int64_t* step, const float* lr_dev,
                  float lr, float momentum, float dampening, float weight_decay, int nesterov, float grad_scale,
                  void* stream);
+/* ---- ABI v28 additions (new symbols only, as v19 to v27: EGX_ABI_VERSION stays 18): gradient-norm clipping and a non-finite guard for the
+ * captured step ------------------------------------------------------------------------------------------------------------------------
+ * A replayed hipGraph cannot test torch.isfinite(loss) or call clip_grad_norm_ on the host: the norm, the decision and the launches that obey
+ * it all have to be device work. What Lightning's Trainer offers as gradient_clip_val / track_grad_norm (the reference constructs its Trainer
+ * with the defaults, HHI/scripts/run_ttm.py:21, HOI/scripts/lta/run_lta.py:238) is here, over the G flat fp32 gradient buffers (g_i, n_i) of
+ * one optimizer step:
+ *   sqsum  = sum_i sum_j (double)g_i[j]^2   each square exact in fp64, every sum in fp64 in a FIXED order that is a function of (n_i) alone
+ *                                           (not of timing, not of a buffer's alignment): no atomics on floating-point values, so ranks that
+ *                                           hold the same gradient bits after the exchange take the same decision without a collective
+ *   norm   = sqrt(sqsum)                    kept in fp64 (a gradient of all 3e38 has a norm above FLT_MAX and is finite)
+ *   finite = isfinite(sqsum)                exactly when every element is finite: a finite fp32 cannot overflow the fp64 sum of squares
+ *   coef   = c < 1 ? (float)c : 1.0f        c = max_norm / (norm + 1e-6) in fp64, the formula of torch.nn.utils.clip_grad_norm_; a comparison,
+ *                                           so a NaN norm gives 1; 1.0f without a max_norm
+ *   apply  = finite || !skip_nonfinite
+ * The guard block lives in device memory; egx_grad_norm rewrites norm / coef / apply on every call or replay and advances the counters:
+ * steps += 1, skipped += !apply, clipped += apply && coef < 1. Zero-fill it once before the first call.
+ * The gated and guarded twins below read it: with apply == 0 they return before any store, so NOTHING the optimizer owns changes (parameters,
+ * moments, momentum buffer, step count, learning rates: the schedule index is the number of APPLIED updates); with apply == 1 they are
+ * today's launches with grad_scale = coef read from device memory, bit for bit the unguarded step when coef == 1.0f. */
+typedef struct egx_guard_block {
+    double norm;     /* sqrt(sqsum), fp64 */
+    float coef;      /* the factor on every gradient element */
+    int32_t apply;   /* 0: the step is skipped */
+    int64_t steps;   /* calls of egx_grad_norm on this block */
+    int64_t skipped; /* ... of which apply == 0 */
+    int64_t clipped; /* ... of which apply == 1 and coef < 1 */
+} egx_guard_block;
+typedef struct egx_grad_norm_cfg {
+    double max_norm;    /* >= 0 (not NaN); read only with has_max_norm */
+    int has_max_norm;   /* 0: measure and guard, never clip */
+    int skip_nonfinite; /* 0: apply = 1 always (the norm and the counters are still written) */
+} egx_grad_norm_cfg;
+#define EGX_GRAD_NORM_TABLE 32
+/* Launch 1, grad_sqsum_kernel: one grouped launch per EGX_GRAD_NORM_TABLE buffers (a by-value table; more buffers chain further launches
+ * into later ranges of the partials), at most 2048 workgroups each, split among the buffers in proportion to their sizes and grid-striding
+ * over the rest; 16-byte loads where a buffer is 16-byte aligned, 4-byte loads of the same elements by the same threads otherwise; every
+ * thread keeps fp64 accumulators, a fixed wave and workgroup tree follows, and each workgroup writes ONE fp64 partial to its own slot of
+ * `scratch` with a plain store. Launch 2, guard_finish_kernel: one workgroup adds the partials in index order, takes the decision above and
+ * writes the block. Two launches and no last-arriver ticket: nothing spins. bufs and ns are HOST arrays of n_bufs >= 1 device pointers and
+ * element counts; n_i == 0 is legal (that buffer is not read, its pointer may be NULL). scratch: egx_grad_norm_scratch_bytes(ns, n_bufs)
+ * bytes of device memory, no initialisation needed (0 from the query: an argument was refused). Asynchronous and capturable; max_norm is
+ * copied into the launch (a captured graph keeps the value it was captured with). Refused before any device work (egx_last_error): null
+ * pointers, n_bufs < 1, a scratch smaller than the query's answer, max_norm < 0 or NaN, a buffer that is not 4-byte aligned. */
+size_t egx_grad_norm_scratch_bytes(const size_t* ns, int n_bufs);
+int egx_grad_norm(const float* const* bufs, const size_t* ns, int n_bufs, void* scratch, size_t scratch_bytes, const egx_grad_norm_cfg* cfg,
+                  egx_guard_block* guard, void* stream);
+/* egx_counter_add and egx_lr_update behind a guard: no store when guard->apply == 0 (same closed forms, one device function). */
+int egx_counter_add_gated(int64_t* counter, int64_t inc, const egx_guard_block* guard, void* stream);
+int egx_lr_update_gated(const egx_lr_schedule* schedule, int64_t* step, const double* base_lr, int n_groups, float* lr_out,
+                        const egx_guard_block* guard, void* stream);
+/* egx_adam_step / egx_adam_step_dev_lr and egx_sgd_step behind a guard: grad_scale = guard->coef, no store when guard->apply == 0; the
+ * learning rate is *lr_dev, or `lr` when lr_dev == NULL. The same update text as the unguarded kernels, which stay as they are. */
+int egx_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const int64_t* step,
+                          const float* lr_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                          const egx_guard_block* guard, void* stream);
+int egx_sgd_step_guarded(float* param, const float* grad, float* momentum_buf, size_t n, const int64_t* step, const float* lr_dev,
+                         float lr, float momentum, float dampening, float weight_decay, int nesterov, const egx_guard_block* guard,
+                         void* stream);
 /* ---- ABI v18, additions: the criterion of the long-term-anticipation task in one launch ---------------------------
  * LongTermAnticipationTask.training_step, HOI/tasks/lta/long_term_anticipation.py:182-203: on the model's [(B, Z, 115), (B, Z, 478)]
  * output it sums CrossEntropyLoss(mean)(pred_h[:, z], labels[:, z, h]) over the 2 heads and 20 future steps (40 terms) and reads
