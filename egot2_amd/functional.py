@@ -402,7 +402,7 @@ class _EncArgs:
 
 class _EncGrads:
     """The gradients of one encoder backward. Everything but the feature gradients is a view of ONE flat buffer (_GradPacker), registered in
-    argument order; `need` is ctx.needs_input_grad, `at` the index of feats[0] in it (5, 6 or 7). bucketed (EncoderFn under bucket_hook): the
+    argument order; `need` is ctx.needs_input_grad, `at` the index of feats[0] in it (5, 7 or 8). bucketed (EncoderFn under bucket_hook): the
     tensors of the layer the backward finishes first (the LAST one) get rank 0, ..., layer 0 rank L - 1, everything else L, so that each
     layer's gradients are one contiguous slice; late (EncoderFn without a hook): dW_proj, dW_in, dW_o lead the buffer (_GradPacker)."""
 
@@ -832,9 +832,8 @@ def _check_host_lengths(lengths, B: int, nseg: int) -> torch.Tensor:
 
 
 def _length_groups(spec: EncoderSpec, feats, lengths: torch.Tensor, first_only: bool = False):
-    """The clips of a ragged batch grouped by their length tuple, for the per-group fallbacks. Yields (clip indices, the same as an int64
-    tensor on the features' device, the group's spec with its segment lengths, the group's unpadded features); first_only: the group's spec
-    returns the first segment's tokens only (out_tokens)."""
+    """The clips of a ragged batch grouped by their length tuple, for the per-group fallback. Yields (clip indices, the group's spec with its
+    segment lengths, the group's unpadded features); first_only: the group's spec returns the first segment's tokens only (out_tokens)."""
     groups = {}
     for b, row in enumerate(lengths.tolist()):
         groups.setdefault(tuple(row), []).append(b)
@@ -843,7 +842,7 @@ def _length_groups(spec: EncoderSpec, feats, lengths: torch.Tensor, first_only: 
         fs = [f.index_select(0, it)[:, :T * max(ss.pool, 1)] for f, T, ss in zip(feats, key, spec.segments)]
         gspec = dataclasses.replace(spec, segments=[dataclasses.replace(ss, T=T) for ss, T in zip(spec.segments, key)],
                                     out_tokens=key[0] if first_only else spec.out_tokens)
-        yield idx, it, gspec, fs
+        yield idx, gspec, fs
 
 
 def _ragged_infer_setup(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, query: str,
@@ -883,7 +882,8 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
         feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = params
         if nbytes is None:
             _attention_unserved("a ragged batch outside the ragged d = 128 kernels (it runs as per-length groups)")
-            return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
+            rows = _clip_rows([1] * len(lengths) if head_t else lengths[:, 0].tolist())
+            return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t, rows, first_only=not head_t)
         B, device = feats[0].shape[0], feats[0].device
         ws = _workspace("saved", device, nbytes)
         wc, wc_sig = _attach_weight_cache(lib, spec, cfg, segs, proj, layer_t, device)
@@ -905,24 +905,29 @@ def encoder_ragged(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengths: to
     return out
 
 
-def _encoder_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t):
-    """encoder_ragged where the ragged kernels do not run (exact fp32, a forced implementation, deeper stacks, clips beyond 512 tokens):
-    one batched forward per group of clips with the same length tuple, on those clips' unpadded frames; results scattered to clip order."""
-    B, d = feats[0].shape[0], spec.d_model
-    device = feats[0].device
-    if head_t:
-        out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
-    else:
-        first = lengths[:, 0].to(torch.int64)
-        row0 = torch.cumsum(first, 0) - first           # first output row of every clip
-        out = torch.empty((int(first.sum()), d), dtype=torch.float32, device=device)
-    for idx, it, gspec, fs in _length_groups(spec, feats, lengths, first_only=not head_t):
+def _clip_rows(counts) -> tuple:
+    """Per clip the int64 host tensor of the output rows its result occupies when clip b fills counts[b] rows, clip after clip."""
+    return torch.arange(sum(counts), dtype=torch.int64).split(list(counts))
+
+
+def _encoder_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t, rows, first_only=False):
+    """The ragged entry points where the ragged kernels do not run (exact fp32, a forced implementation, deeper stacks, clips beyond the
+    kernels' reach): one batched encoder() per group of clips with the same length tuple, on those clips' unpadded frames. rows[b] names the
+    output rows of clip b's result (int64 host tensors: the clip index for the pooled head, the packed rows of the first segment, a slice of
+    ragged_token_rows()); the rows are put in place by one cat + index_select of the inverse permutation, which autograd flows through
+    unless the caller runs under no_grad."""
+    parts, dst = [], []
+    for idx, gspec, fs in _length_groups(spec, feats, lengths, first_only):
         r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
-        if head_t:
-            out.index_copy_(0, it, r)
-        else:
-            dst = (row0[idx][:, None] + torch.arange(gspec.out_tokens)[None, :]).reshape(-1).to(device)
-            out.index_copy_(0, dst, r.reshape(-1, d))
+        parts.append(r.reshape(-1, r.shape[-1]))
+        dst += [rows[b] for b in idx]
+    if parts:
+        dst = torch.cat(dst)
+        inv = torch.empty_like(dst)
+        inv[dst] = torch.arange(dst.numel())
+        out = torch.cat(parts, 0).index_select(0, inv.to(feats[0].device))
+    else:       # (a batch of no clips)
+        out = torch.empty((0, spec.head_n_out if head_t else spec.d_model), dtype=torch.float32, device=feats[0].device)
     _last_impl[0] = IMPL_GROUPED
     _last_slices[0] = 1
     return out
@@ -936,46 +941,82 @@ def _ragged_train_config(spec: EncoderSpec) -> Config:
     return cfg
 
 
+_NO_POS_GRAD = "ragged training: a learned positional table gets no gradient from the ragged kernels"
+
+
+def _ragged_train_setup(spec: EncoderSpec, rest, ln_w, ln_b, task_embed, pos_table, wide: bool = False):
+    """The start of a ragged training forward: `rest` split (_EncArgs.split; wide: RaggedWideEncoderFn's), the tensors on the device (the
+    features fp32, or bf16 too on the wide path), then the segments, the layers and the ragged training configuration.
+    Returns (tensors in _EncArgs.load's order, segments, layers, config)."""
+    feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest, wide)
+    feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
+                                                                                  pos_table, feat=_dev_feat if wide else _dev_f32)
+    segs = _segments(spec, feats, proj, task_embed, pos_table, feats[0].shape[0])
+    return (task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tail), segs, _layers(layer_t, spec.n_layers), _ragged_train_config(spec)
+
+
+def _ragged_train_plan(ctx, d_out, at: int):
+    """The start of a ragged training backward (ctx.spec, ctx.B, ctx.scratch_bytes and _EncArgs.save's tensors; `at`: the index of feats[0]
+    among the Function's arguments): a learned positional table's gradient refused, then the gradient plan attached to the configuration.
+    Returns (tensors, _EncGrads, (segments, their gradients), (layers, their gradients), config, scratch, the upstream gradient fp32)."""
+    spec, need = ctx.spec, ctx.needs_input_grad
+    if need[at - 3]:
+        raise _lib.EgxError(_NO_POS_GRAD)
+    tensors = _EncArgs.load(ctx)
+    task_embed, pos_table, _, _, feats, proj, layer_t, _, _ = tensors
+    gr = _EncGrads(spec, need, at, tensors, d_out.device)
+    segs = _segments(spec, feats, proj, task_embed, pos_table, ctx.B, grads=gr.segments())
+    layers = _layers(layer_t, spec.n_layers, gr.layers)
+    cfg = _ragged_train_config(spec)
+    gr.attach(cfg)
+    return tensors, gr, segs, layers, cfg, _workspace("scratch", d_out.device, ctx.scratch_bytes), _f32c(d_out)
+
+
 class RaggedEncoderFn(torch.autograd.Function):
-    """Training forward + backward over a ragged batch (egx_ragged_train_fwd / egx_ragged_bwd). Argument order: spec, lengths (the (B, K)
-    int32 host tensor of ragged_lengths()), then _EncArgs' (task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b)
-    per segment, 12 tensors per layer, (head_ln_w, head_ln_b, head_W, head_b) with spec.head_n_out, then (target, class_weight | None) with
-    spec.ce). Returns logits (B, n_out) [, loss] with a head, else the first segment's rows of every clip, packed (sum_b T_{b,0}, d)."""
+    """Training forward + backward of the d = 128 translators over a ragged batch. Argument order: spec, lengths, capacity, status, then
+    _EncArgs' (task_embed | None, pos_table | None, ln_w, ln_b, feats[n_seg], (proj_w, proj_b) per segment, 12 tensors per layer,
+    (head_ln_w, head_ln_b, head_W, head_b) with spec.head_n_out, then (target, class_weight | None) with spec.ce).
+    capacity None, the host-table form (egx_ragged_train_fwd / egx_ragged_bwd): lengths is the (B, K) int32 host tensor of ragged_lengths().
+    Returns logits (B, n_out) [, loss] with a head, else the first segment's rows of every clip, packed (sum_b T_{b,0}, d).
+    capacity (B_cap, tok_cap), the capturable form with the batch table built on the device (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd):
+    lengths is CUDA int32 (B_cap, K), all-zero rows are empty clips; status CUDA int32 (1,); one graph serves every batch that fits the
+    capacity. A head is required. Returns logits (B_cap, n_out) [, loss]."""
 
     @staticmethod
-    def forward(ctx, spec: EncoderSpec, lengths, task_embed, pos_table, ln_w, ln_b, *rest):
+    def forward(ctx, spec: EncoderSpec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *rest):
         lib = _load()
-        feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest)
-        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
-                                                                                      pos_table, feat=_dev_f32)
-        B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
-        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = _layers(layer_t, spec.n_layers)
-        cfg = _ragged_train_config(spec)
+        tensors, segs, layers, cfg = _ragged_train_setup(spec, rest, ln_w, ln_b, task_embed, pos_table)
+        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, tail = tensors
+        B, device = feats[0].shape[0], feats[0].device
+        host = capacity is None
         sv, sc = C.c_size_t(0), C.c_size_t(0)
-        check(lib.egx_ragged_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
+        if host:
+            check(lib.egx_ragged_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
+        else:
+            check(lib.egx_ragged_cap_workspace(C.byref(cfg), segs, B, capacity[1], C.byref(sv), C.byref(sc)))
         saved = _saved_buffer(any(ctx.needs_input_grad), "saved", device, sv.value)
         keep = None
         if spec.ce:
             loss, ctx.ce_dl, keep = _ce_attach(spec, cfg, tail[0], tail[1], B, device)
-        seed = _seed64(spec.seed)
         if head_t:
             head = _head(head_t, spec.head_n_out)
             out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
-            check(lib.egx_ragged_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(out),
-                                           None, ptr(saved), None, int(spec.training), seed, _stream()))
-        else:
-            out = torch.empty((int(lengths[:, 0].sum()), d), dtype=torch.float32, device=device)
-            check(lib.egx_ragged_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, None, B, None, ptr(out),
-                                           ptr(saved), None, int(spec.training), seed, _stream()))
+            outs = (ptr(out), None)
+        else:       # (the first segment's rows: the host form only, the capacity form's checks ask for a head)
+            out = torch.empty((int(lengths[:, 0].sum()), spec.d_model), dtype=torch.float32, device=device)
+            outs = (None, ptr(out))
+        fwd, cap, st = (lib.egx_ragged_train_fwd, (), ()) if host else (lib.egx_ragged_cap_train_fwd, (capacity[1],), (ptr(status),))
+        check(fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head) if head_t else None, B, *cap, *outs,
+                  ptr(saved), None, *st, int(spec.training), _seed64(spec.seed), _stream()))
         del keep
-        _last_impl[0] = IMPL_RAGGED
+        _last_impl[0] = IMPL_RAGGED if host else IMPL_RAGGED_CAP
         _last_slices[0] = 1
-        if _attention_sink is not None:
+        if host and _attention_sink is not None:
             _attention_sink(lib, cfg, segs, B, lengths, spec, saved, device)
-        ctx.spec, ctx.lengths, ctx.B = spec, lengths, B        # the host lengths: the backward rebuilds the same plan from them
+        # (the lengths: the backward rebuilds the same plan from them, on the host or on the device)
+        ctx.spec, ctx.lengths, ctx.B, ctx.capacity, ctx.status = spec, lengths, B, capacity, status
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
-        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t)
+        _EncArgs.save(ctx, *tensors[:8])
         if spec.ce:
             ctx.set_materialize_grads(False)
             return out, loss
@@ -991,31 +1032,18 @@ class RaggedEncoderFn(torch.autograd.Function):
                 return (None,) * len(ctx.needs_input_grad)
             d_out, dl_scale = up
         lib = _load()
-        tensors = _EncArgs.load(ctx)
-        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, _ = tensors
-        B, device = ctx.B, d_out.device
-        need = ctx.needs_input_grad     # (spec, lengths, task_embed, pos_table, ln_w, ln_b, *rest)
-        if need[3]:
-            raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
-        gr = _EncGrads(spec, need, 6, tensors, device)
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
-        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
-        cfg = _ragged_train_config(spec)
-        gr.attach(cfg)
+        tensors, gr, (segs, sgr), (layers, lgr), cfg, scratch, up = _ragged_train_plan(ctx, d_out, 8)
+        ln_w, ln_b, head_t = tensors[2], tensors[3], tensors[7]
         if dl_scale is not None:
             cfg.d_logits_scale = dl_scale.data_ptr()
-        scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        seed = _seed64(spec.seed)
-        up = _f32c(d_out)
         if head_t:
             head, hg = _head(head_t, spec.head_n_out), gr.head_grads()
-            check(lib.egx_ragged_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, ptr(up), None,
-                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, C.byref(hg),
-                                     int(spec.training), seed, _stream()))
+            p_head, p_hg, ups = C.byref(head), C.byref(hg), (ptr(up), None)
         else:
-            check(lib.egx_ragged_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, None, B, None, ptr(up),
-                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, None,
-                                     int(spec.training), seed, _stream()))
+            p_head, p_hg, ups = None, None, (None, ptr(up))
+        bwd, cap, st = (lib.egx_ragged_bwd, (), ()) if ctx.capacity is None else (lib.egx_ragged_cap_bwd, (ctx.capacity[1],), (ptr(ctx.status),))
+        check(bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, p_head, ctx.B, *cap, *ups, ptr(ctx.saved_buf),
+                  ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, p_hg, *st, int(spec.training), _seed64(spec.seed), _stream()))
         return gr.result(2 if spec.ce else 0)
 
 
@@ -1034,79 +1062,10 @@ def ragged_cap_status_word(device: torch.device) -> torch.Tensor:
     return w
 
 
-class RaggedCapEncoderFn(torch.autograd.Function):
-    """RaggedEncoderFn with the batch table built on the device (egx_ragged_cap_train_fwd / egx_ragged_cap_bwd): capturable, one graph for
-    every batch that fits `capacity` = (B_cap, tok_cap). Argument order: spec, lengths (CUDA int32 (B_cap, K); all-zero rows are empty clips),
-    capacity, status (CUDA int32 (1,)), then RaggedEncoderFn's from task_embed on. A head is required. Returns logits (B_cap, n_out) [, loss]."""
-
-    @staticmethod
-    def forward(ctx, spec: EncoderSpec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *rest):
-        lib = _load()
-        feats, proj, layer_t, head_t, tail = _EncArgs.split(spec, rest)
-        feats, proj, layer_t, head_t, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, head_t, ln_w, ln_b, task_embed,
-                                                                                      pos_table, feat=_dev_f32)
-        B, tok_cap = capacity
-        device = feats[0].device
-        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = _layers(layer_t, spec.n_layers)
-        cfg = _ragged_train_config(spec)
-        sv, sc = C.c_size_t(0), C.c_size_t(0)
-        check(lib.egx_ragged_cap_workspace(C.byref(cfg), segs, B, tok_cap, C.byref(sv), C.byref(sc)))
-        saved = _saved_buffer(any(ctx.needs_input_grad), "saved", device, sv.value)
-        keep = None
-        if spec.ce:
-            loss, ctx.ce_dl, keep = _ce_attach(spec, cfg, tail[0], tail[1], B, device)
-        head = _head(head_t, spec.head_n_out)
-        out = torch.empty((B, spec.head_n_out), dtype=torch.float32, device=device)
-        check(lib.egx_ragged_cap_train_fwd(C.byref(cfg), segs, ptr(lengths), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, tok_cap, ptr(out),
-                                           None, ptr(saved), None, ptr(status), int(spec.training), _seed64(spec.seed), _stream()))
-        del keep
-        _last_impl[0] = IMPL_RAGGED_CAP
-        _last_slices[0] = 1
-        ctx.spec, ctx.lengths, ctx.capacity, ctx.status = spec, lengths, (B, tok_cap), status
-        ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
-        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t)
-        if spec.ce:
-            ctx.set_materialize_grads(False)
-            return out, loss
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out, d_loss=None):
-        spec: EncoderSpec = ctx.spec
-        dl_scale = None
-        if spec.ce:
-            up = _ce_upstream(ctx, d_out, d_loss)
-            if up is None:
-                return (None,) * len(ctx.needs_input_grad)
-            d_out, dl_scale = up
-        lib = _load()
-        tensors = _EncArgs.load(ctx)
-        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, head_t, _ = tensors
-        (B, tok_cap), device = ctx.capacity, d_out.device
-        need = ctx.needs_input_grad     # (spec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *rest)
-        if need[5]:
-            raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
-        gr = _EncGrads(spec, need, 8, tensors, device)
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
-        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
-        cfg = _ragged_train_config(spec)
-        gr.attach(cfg)
-        if dl_scale is not None:
-            cfg.d_logits_scale = dl_scale.data_ptr()
-        scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        up = _f32c(d_out)
-        head, hg = _head(head_t, spec.head_n_out), gr.head_grads()
-        check(lib.egx_ragged_cap_bwd(C.byref(cfg), segs, ptr(ctx.lengths), ptr(ln_w), ptr(ln_b), layers, C.byref(head), B, tok_cap, ptr(up), None,
-                                     ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, C.byref(hg),
-                                     ptr(ctx.status), int(spec.training), _seed64(spec.seed), _stream()))
-        return gr.result(2 if spec.ce else 0)
-
-
-def _encoder_ragged_cap(spec: EncoderSpec, feats, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params,
-                        ce):
-    """encoder_ragged_train with DEVICE lengths: the checks that need no look at the lengths (nothing here synchronises), then
-    RaggedCapEncoderFn. There is no fallback: a configuration the ragged kernels do not cover raises with the library's message."""
+def _check_ragged_cap(spec: EncoderSpec, feats, lengths, capacity, status, pos_table, head_params):
+    """encoder_ragged_train with DEVICE lengths: the checks that need no look at the lengths (nothing here synchronises). Returns (lengths,
+    capacity, status) as RaggedEncoderFn takes them. There is no fallback: a configuration the ragged kernels do not cover raises with the
+    library's message."""
     K = len(spec.segments)
     if capacity is None or len(capacity) != 2:
         raise ValueError("device lengths need capacity=(B_cap, tok_cap): the clips and the tokens the captured step is sized for")
@@ -1118,15 +1077,12 @@ def _encoder_ragged_cap(spec: EncoderSpec, feats, lengths, capacity, status, tas
     if not head_params:
         raise ValueError("ragged capacity: a pooled head is required (head-less rows are not supported on the captured path)")
     if pos_table is not None and pos_table.requires_grad and torch.is_grad_enabled():
-        raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
+        raise _lib.EgxError(_NO_POS_GRAD)
     if status is None:
         status = ragged_cap_status_word(feats[0].device)
     elif status.dtype != torch.int32 or status.numel() != 1 or status.device != feats[0].device:
         raise ValueError("status must be a one-element int32 tensor on the features' device")
-    args = [spec, lengths.contiguous(), (B_cap, tok_cap), status, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
-    if ce is not None:
-        args += [ce[0], ce[1]]
-    return RaggedCapEncoderFn.apply(*args)
+    return lengths.contiguous(), (B_cap, tok_cap), status
 
 
 def _ragged_train_refused(spec: EncoderSpec, feats, lengths, task_embed, pos_table, proj, query: str) -> bool:
@@ -1164,40 +1120,22 @@ def encoder_ragged_train(spec: EncoderSpec, feats: Sequence[torch.Tensor], lengt
         raise ValueError("ce = (target, class_weight) goes with spec.ce and the pooled head")
     if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
         _attention_unserved("the capacity form of a ragged batch (device lengths)")
-        return _encoder_ragged_cap(spec, feats, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
-    if capacity is not None:
+        lengths, capacity, status = _check_ragged_cap(spec, feats, lengths, capacity, status, pos_table, head_params)
+    elif capacity is not None:
         raise ValueError("capacity= goes with device lengths (a CUDA int32 tensor); host lengths size the call themselves")
-    lengths = _check_host_lengths(lengths, feats[0].shape[0], len(spec.segments))
-    if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_train_workspace"):
-        _attention_unserved("a ragged batch outside the ragged d = 128 kernels (it runs as per-length groups)")
-        return _encoder_train_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params, head_params, ce)
-    args = [spec, lengths, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
+    else:
+        lengths, status = _check_host_lengths(lengths, feats[0].shape[0], len(spec.segments)), None
+        if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_train_workspace"):
+            _attention_unserved("a ragged batch outside the ragged d = 128 kernels (it runs as per-length groups)")
+            rows = _clip_rows([1] * len(lengths) if head_params else lengths[:, 0].tolist())
+            # (the groups run without the fused loss and the weight cache: the loss is taken over the whole batch's logits)
+            out = _encoder_grouped(dataclasses.replace(spec, ce=False, wcache=None), feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
+                                   layer_params, head_params, rows, first_only=not head_params)
+            return out if ce is None else (out, weighted_cross_entropy(out, ce[0], ce[1]))
+    args = [spec, lengths, capacity, status, task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params, *head_params]
     if ce is not None:
         args += [ce[0], ce[1]]
     return RaggedEncoderFn.apply(*args)
-
-
-def _encoder_train_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t, ce):
-    """encoder_ragged_train where the ragged kernels do not run: one differentiable batched forward per group of clips with the same length
-    tuple, on those clips' unpadded frames, the results put back in clip order (autograd flows through the gather and the reordering)."""
-    d = spec.d_model
-    device = feats[0].device
-    parts, order = [], []
-    first = lengths[:, 0].to(torch.int64)
-    row0 = (torch.cumsum(first, 0) - first).tolist()         # first output row of every clip (head-less)
-    gspec0 = dataclasses.replace(spec, ce=False, wcache=None)
-    for idx, _, gspec, fs in _length_groups(gspec0, feats, lengths, first_only=not head_t):
-        r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t, head_t)
-        parts.append(r if head_t else r.reshape(-1, d))
-        order += idx if head_t else [row0[b] + t for b in idx for t in range(gspec.out_tokens)]
-    inv = torch.empty(len(order), dtype=torch.int64)
-    inv[torch.tensor(order, dtype=torch.int64)] = torch.arange(len(order))
-    out = torch.cat(parts, 0).index_select(0, inv.to(device))
-    _last_impl[0] = IMPL_GROUPED
-    _last_slices[0] = 1
-    if ce is not None:
-        return out, weighted_cross_entropy(out, ce[0], ce[1])
-    return out
 
 
 def ragged_token_rows(lengths: torch.Tensor, out_layout: int = 0) -> torch.Tensor:
@@ -1238,7 +1176,8 @@ def encoder_ragged_tokens(spec: EncoderSpec, feats: Sequence[torch.Tensor], leng
                                                                               layer_params, (), "egx_ragged_encode_workspace", out_layout)
         feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = params
         if nbytes is None:
-            return _encoder_tokens_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout)
+            rows = ragged_token_rows(lengths, out_layout).split(lengths.sum(1).tolist())
+            return _encoder_grouped(spec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, (), rows)
         B, device = feats[0].shape[0], feats[0].device
         ws = _workspace("ragged_wide", device, nbytes)
         out = torch.empty((int(lengths.to(torch.int64).sum()), spec.d_model), dtype=torch.float32, device=device)
@@ -1259,45 +1198,30 @@ class RaggedWideEncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: EncoderSpec, lengths, out_layout: int, task_embed, pos_table, ln_w, ln_b, *rest):
         lib = _load()
-        feats, proj, layer_t, _, _ = _EncArgs.split(spec, rest, wide=True)
-        feats, proj, layer_t, _, ln_w, ln_b, task_embed, pos_table = _dev_params(feats, proj, layer_t, (), ln_w, ln_b, task_embed, pos_table)
-        B, d, device = feats[0].shape[0], spec.d_model, feats[0].device
-        segs = _segments(spec, feats, proj, task_embed, pos_table, B)
-        layers = _layers(layer_t, spec.n_layers)
-        cfg = _ragged_train_config(spec)
+        tensors, segs, layers, cfg = _ragged_train_setup(spec, rest, ln_w, ln_b, task_embed, pos_table, wide=True)
+        ln_w, ln_b, feats = tensors[2], tensors[3], tensors[4]
+        B, device = feats[0].shape[0], feats[0].device
         sv, sc = C.c_size_t(0), C.c_size_t(0)
         check(lib.egx_ragged_encode_train_workspace(C.byref(cfg), segs, B, lengths.data_ptr(), C.byref(sv), C.byref(sc)))
         saved = _saved_buffer(any(ctx.needs_input_grad), "ragged_wide_saved", device, sv.value)
-        out = torch.empty((int(lengths.to(torch.int64).sum()), d), dtype=torch.float32, device=device)
+        out = torch.empty((int(lengths.to(torch.int64).sum()), spec.d_model), dtype=torch.float32, device=device)
         check(lib.egx_ragged_encode_train_fwd(C.byref(cfg), segs, lengths.data_ptr(), ptr(ln_w), ptr(ln_b), layers, B, ptr(out), int(out_layout),
                                               ptr(saved), int(spec.training), _seed64(spec.seed), _stream()))
         _last_impl[0] = IMPL_RAGGED
         _last_slices[0] = 1
         ctx.spec, ctx.lengths, ctx.B, ctx.out_layout = spec, lengths, B, int(out_layout)
         ctx.saved_buf, ctx.scratch_bytes = saved, sc.value
-        _EncArgs.save(ctx, task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, [])
+        _EncArgs.save(ctx, *tensors[:8])
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         spec: EncoderSpec = ctx.spec
         lib = _load()
-        tensors = _EncArgs.load(ctx)
-        task_embed, pos_table, ln_w, ln_b, feats, proj, layer_t, _, _ = tensors
-        B, device = ctx.B, d_out.device
-        need = ctx.needs_input_grad     # (spec, lengths, out_layout, task_embed, pos_table, ln_w, ln_b, *rest)
-        if need[4]:
-            raise _lib.EgxError("ragged training: a learned positional table gets no gradient from the ragged kernels")
-        if any(need[7:7 + len(feats)]):
+        if any(ctx.needs_input_grad[7:7 + len(spec.segments)]):
             raise _lib.EgxError("ragged training: gradients into PROJECTED features are not supported on the wide path (detach the features)")
-        gr = _EncGrads(spec, need, 7, tensors, device)
-        segs, sgr = _segments(spec, feats, proj, task_embed, pos_table, B, grads=gr.segments())
-        layers, lgr = _layers(layer_t, spec.n_layers, gr.layers)
-        cfg = _ragged_train_config(spec)
-        gr.attach(cfg)
-        scratch = _workspace("scratch", device, ctx.scratch_bytes)
-        up = _f32c(d_out)
-        check(lib.egx_ragged_encode_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(ln_w), layers, B, ptr(up), ctx.out_layout,
+        tensors, gr, (segs, sgr), (layers, lgr), cfg, scratch, up = _ragged_train_plan(ctx, d_out, 7)
+        check(lib.egx_ragged_encode_bwd(C.byref(cfg), segs, ctx.lengths.data_ptr(), ptr(tensors[2]), layers, ctx.B, ptr(up), ctx.out_layout,
                                         ptr(ctx.saved_buf), ptr(scratch), sgr, ptr(gr.first[2]), ptr(gr.first[3]), lgr, int(spec.training),
                                         _seed64(spec.seed), _stream()))
         return gr.result()
@@ -1325,33 +1249,11 @@ def encoder_ragged_tokens_train(spec: EncoderSpec, feats: Sequence[torch.Tensor]
     if len(proj) != 2 * len(spec.segments):
         raise ValueError("ragged training on the wide path: every segment needs a projection")
     if _ragged_train_refused(spec, feats, lengths, task_embed, pos_table, proj, "egx_ragged_encode_train_workspace"):
-        return _encoder_tokens_grouped(dataclasses.replace(spec, wcache=None), feats, lengths, task_embed, pos_table, ln_w, ln_b, proj,
-                                       layer_params, out_layout)
+        rows = ragged_token_rows(lengths, out_layout).split(lengths.sum(1).tolist())
+        return _encoder_grouped(dataclasses.replace(spec, wcache=None), feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_params,
+                                (), rows)
     feats = [f.detach() for f in feats]      # (frozen backbone features: no gradient path on the wide projections)
     return RaggedWideEncoderFn.apply(spec, lengths, int(out_layout), task_embed, pos_table, ln_w, ln_b, *feats, *proj, *layer_params)
-
-
-def _encoder_tokens_grouped(spec: EncoderSpec, feats, lengths, task_embed, pos_table, ln_w, ln_b, proj, layer_t, out_layout):
-    """encoder_ragged_tokens(_train) where the ragged wide path does not run (compute other than bf16, a forced implementation, a clip beyond
-    the wide attention): one batched forward per group of clips with the same length tuple, on those clips' unpadded frames; the rows put in
-    their place (autograd flows through the gather and the reordering, unless the caller runs under no_grad)."""
-    d = spec.d_model
-    device = feats[0].device
-    rows = ragged_token_rows(lengths, out_layout)
-    S = lengths.to(torch.int64).sum(1)
-    tok0 = torch.cumsum(S, 0) - S
-    parts, dst = [], []
-    for idx, _, gspec, fs in _length_groups(spec, feats, lengths):
-        r = encoder(gspec, fs, task_embed, pos_table, ln_w, ln_b, proj, layer_t)        # (G, S_key, d), clip-major token order
-        parts.append(r.reshape(-1, d))
-        dst.append(rows[(tok0[idx][:, None] + torch.arange(r.shape[1])[None, :]).reshape(-1)])
-    dst = torch.cat(dst)
-    inv = torch.empty(dst.numel(), dtype=torch.int64)
-    inv[dst] = torch.arange(dst.numel())
-    out = torch.cat(parts, 0).index_select(0, inv.to(device))
-    _last_impl[0] = IMPL_GROUPED
-    _last_slices[0] = 1
-    return out
 
 
 _last_dec_impl = ["none"]

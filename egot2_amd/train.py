@@ -518,7 +518,79 @@ class TranslationCriterion(_DeviceCriterion):
         return res
 
 
-class SegmentAPValidation(_DeviceCriterion):
+class _EpochAccumulator(_DeviceCriterion):
+    """What the device-resident epoch accumulators share: the host state machine (`_rows`, the count of rows that hold or are reserved for
+    an entry; `_device`; `_computed`) behind reset() / update(...) per batch / compute() / step_result(). A subclass has `capacity`, the
+    wording of its messages (_INPUT, _UNIT, _HOST_STATE), `_allocate(device)` with the accumulator `state` and the result words `flat`,
+    `_metric(buffers)`, which runs the metric over the rows so far into the buffers, and its own slot rules in update()."""
+    _INPUT, _UNIT, _HOST_STATE = "input", "rows", "the row count is"
+
+    def __init__(self):
+        super().__init__()
+        self._rows = 0
+        self._device: Optional[torch.device] = None
+        self._computed = False
+
+    def _refuse_capture(self, device, what: str):
+        if self._capturing(device):
+            raise RuntimeError(f"{type(self).__name__}.{what} cannot be captured in a graph: {self._HOST_STATE} host state (a replay would "
+                               f"fold the batch into the same {self._UNIT} again); call it eagerly")
+
+    def _forget(self):
+        """reset(): whatever else a subclass keeps per epoch"""
+
+    def reset(self):
+        """Empty the accumulator (one memset on the stream) and forget the epoch's host state."""
+        if self._device is not None:
+            self._refuse_capture(self._device, "reset")
+            self._result_buffers(self._device)["state"].zero_()
+        self._rows, self._computed, self._last = 0, False, None
+        self._forget()
+        return self
+
+    def _on_device(self, dev):
+        if self._device is not None and dev != self._device:
+            raise ValueError(f"{type(self).__name__}: {self._INPUT} on {dev}, the accumulator is on {self._device}")
+
+    def _device_reach(self, rows: Optional[int]) -> int:
+        """The rows reached after an update with device slots, which the caller has to state."""
+        if rows is None:
+            raise ValueError(f"{type(self).__name__}.update: device slots need rows= (the number of {self._UNIT} they reach): the host cannot "
+                             "read them without a synchronisation")
+        return max(self._rows, int(rows))
+
+    def _stage(self, dev, reach: int, slot_t):
+        """The capacity check of an update that reaches `reach` rows -> (the buffers, the slots on the device)."""
+        if reach > self.capacity:
+            raise ValueError(f"{type(self).__name__}.update: {reach} {self._UNIT} exceed capacity={self.capacity}")
+        b = self._result_buffers(dev)
+        return b, (slot_t.to(dev) if slot_t is not None and not slot_t.is_cuda else slot_t)
+
+    def _commit(self, dev, reach: int):
+        self._device, self._rows, self._computed = dev, reach, False
+
+    def compute(self) -> dict:
+        """-> the device tensors of the subclass's metric over the rows so far. Nothing synchronises."""
+        if self._device is None or self._rows == 0:
+            raise RuntimeError(f"{type(self).__name__}: no update has run yet")
+        self._refuse_capture(self._device, "compute")
+        b = self._result_buffers(self._device)
+        self._last = {"buffers": b, "result": {k: v for k, v in self._metric(b).items() if k != "flat"}}
+        self._computed = True
+        return dict(self._last["result"])
+
+    def stats(self) -> dict:
+        """The device tensors of the most recent compute()."""
+        return dict(self._latest()["result"])
+
+    def _host_flat(self):
+        """The result words on the host: compute() first when rows arrived since the last one, then ONE device-to-host copy."""
+        if not self._computed and self._device is not None and self._rows > 0:
+            self.compute()
+        return self._latest()["buffers"]["flat"].cpu().numpy()
+
+
+class SegmentAPValidation(_EpochAccumulator):
     """The validation epoch of the TTM and LAM tasks after the model (HHI/tasks/ttm/video_task_2loader.py:19,46-50): the reference's
     PostProcessor (HHI/utils/ttm/utils.py:46-114, HHI/utils/lam/utils.py:24-81)
 
@@ -544,10 +616,9 @@ class SegmentAPValidation(_DeviceCriterion):
     def __init__(self, capacity: int, merge: bool = True):
         super().__init__()
         self.capacity = F_egx._seg_ap_capacity("SegmentAPValidation", capacity)
-        self.merge = bool(merge)
-        self._rows = 0                  # the row cursor: rows 0 .. _rows - 1 hold (or are reserved for) a score
-        self._device: Optional[torch.device] = None
-        self._computed = False
+        self.merge = bool(merge)         # (_rows is the row cursor: rows 0 .. _rows - 1 hold, or are reserved for, a score)
+
+    _INPUT, _UNIT, _HOST_STATE = "logits", "rows", "the row cursor is"
 
     def _allocate(self, device) -> dict:
         """The accumulator + work area, the 11 result words (`flat`) and the per-row outputs."""
@@ -562,35 +633,18 @@ class SegmentAPValidation(_DeviceCriterion):
                 "order1": torch.zeros(cap, dtype=torch.int32, device=device),
                 "order0": torch.zeros(cap, dtype=torch.int32, device=device)}
 
-    def _refuse_capture(self, device, what: str):
-        if self._capturing(device):
-            raise RuntimeError(f"SegmentAPValidation.{what} cannot be captured in a graph: the row cursor is host state (a replay would "
-                               "fold the batch into the same rows again); call it eagerly")
-
-    def reset(self) -> "SegmentAPValidation":
-        """Empty the accumulator (one memset on the stream) and rewind the row cursor."""
-        if self._device is not None:
-            self._refuse_capture(self._device, "reset")
-            self._result_buffers(self._device)["state"].zero_()
-        self._rows, self._computed, self._last = 0, False, None
-        return self
-
     def update(self, logits: torch.Tensor, labels: torch.Tensor, slots=None, rows: Optional[int] = None) -> None:
         dev = logits.device
         self._refuse_capture(dev, "update")
         B = int(logits.shape[0])
         if slots is not None and not self.merge:
             raise ValueError("SegmentAPValidation(merge=False): every input row is its own row, slots are not taken")
-        if self._device is not None and dev != self._device:
-            raise ValueError(f"SegmentAPValidation: logits on {dev}, the accumulator is on {self._device}")
+        self._on_device(dev)
         if slots is None:
             reach = self._rows + B
             slot_t, slot0 = None, self._rows
         elif isinstance(slots, torch.Tensor) and slots.is_cuda:
-            if rows is None:
-                raise ValueError("SegmentAPValidation.update: device slots need rows= (the number of rows they reach): the host cannot "
-                                 "read them without a synchronisation")
-            reach, slot_t, slot0 = max(self._rows, int(rows)), slots, 0
+            reach, slot_t, slot0 = self._device_reach(rows), slots, 0
         else:
             host = torch.as_tensor(slots, dtype=torch.int64).reshape(-1)
             if host.numel() != B:
@@ -599,37 +653,20 @@ class SegmentAPValidation(_DeviceCriterion):
                 raise ValueError("SegmentAPValidation.update: slots must be >= 0 and non-decreasing within a call")
             reach, slot0 = max(self._rows, int(host[-1]) + 1 if B else 0), 0
             slot_t = host
-        if reach > self.capacity:
-            raise ValueError(f"SegmentAPValidation.update: {reach} rows exceed capacity={self.capacity}")
-        b = self._result_buffers(dev)
-        if slot_t is not None and not slot_t.is_cuda:
-            slot_t = slot_t.to(dev)
+        b, slot_t = self._stage(dev, reach, slot_t)
         F_egx.segment_scores_update(b["state"], self.capacity, logits, labels.to(device=dev, dtype=torch.int64), slot_t, slot0)
-        self._device, self._rows, self._computed = dev, reach, False
+        self._commit(dev, reach)
 
-    def compute(self) -> dict:
-        """-> device tensors of the rows so far: `score`, `order1`, `order0` (n), the int64 counts `n`, `n_pos`, `TP`, `FN`, `FP`, `TN`,
-        `n_nonfinite` and fp64 `AP0`, `AP1`, `mAP`, `acc`. Nothing synchronises."""
-        if self._device is None or self._rows == 0:
-            raise RuntimeError("SegmentAPValidation: no update has run yet")
-        self._refuse_capture(self._device, "compute")
-        b = self._result_buffers(self._device)
-        res = F_egx.segment_ap(b["state"], self.capacity, self._rows, out=b)
-        self._last = {"buffers": b, "result": {k: v for k, v in res.items() if k != "flat"}}
-        self._computed = True
-        return dict(self._last["result"])
-
-    def stats(self) -> dict:
-        """The device tensors of the most recent compute()."""
-        return dict(self._latest()["result"])
+    def _metric(self, b: dict) -> dict:
+        """compute(): `score`, `order1`, `order0` (n), the int64 counts `n`, `n_pos`, `TP`, `FN`, `FP`, `TN`, `n_nonfinite` and fp64 `AP0`,
+        `AP1`, `mAP`, `acc`."""
+        return F_egx.segment_ap(b["state"], self.capacity, self._rows, out=b)
 
     def step_result(self, prefix: str = "val") -> Dict[str, float]:
         """The epoch's logged values from ONE device-to-host copy (it synchronises): f"{prefix}_mAP" (the checkpoint metric),
         f"{prefix}_acc", f"{prefix}_AP0", f"{prefix}_AP1" and the counts f"{prefix}_TP", _FN, _FP, _TN, _n, _n_pos, _n_nonfinite.
         Runs compute() first when rows arrived since the last one."""
-        if not self._computed and self._device is not None and self._rows > 0:
-            self.compute()
-        host = self._latest()["buffers"]["flat"].cpu().numpy()
+        host = self._host_flat()
         nc = len(F_egx.SEG_AP_COUNTS)
         res: Dict[str, float] = {f"{prefix}_{name}": int(host[i]) for i, name in enumerate(F_egx.SEG_AP_COUNTS)}
         values = host[nc:].view("float64")
@@ -637,7 +674,7 @@ class SegmentAPValidation(_DeviceCriterion):
         return res
 
 
-class ViewEnsembleTest(_DeviceCriterion):
+class ViewEnsembleTest(_EpochAccumulator):
     """The test epoch of the action-recognition translators after the model: MultiTaskClassificationTask.test_step / test_epoch_end
     (HOI/tasks/lta/long_term_anticipation.py:86-158; the same code in long_term_anticipation_taskspecfic.py:88-162), the number the
     EgoT2-s AR models are reported with. Every video is seen as TEST.NUM_ENSEMBLE_VIEWS x TEST.NUM_SPATIAL_CROPS clips; the reference
@@ -678,10 +715,10 @@ class ViewEnsembleTest(_DeviceCriterion):
         self.ks = tuple(int(k) for k in ks)
         if not 1 <= len(self.ks) <= F_egx.SEG_CE_MAX_KS or min(self.ks) < 1 or max(self.ks) > min(self.classes):
             raise ValueError(f"ViewEnsembleTest: ks={ks} (needs 1 to {F_egx.SEG_CE_MAX_KS} values in 1 .. {min(self.classes)}, the narrowest head)")
-        self._slot_of: Dict[object, int] = {}           # clip id -> slot, in first-appearance order (the reference's dict order)
-        self._rows = 0                                  # videos 0 .. _rows - 1 hold (or are reserved for) a row
-        self._device: Optional[torch.device] = None
-        self._computed = False
+        # clip id -> slot, in first-appearance order (the reference's dict order); videos 0 .. _rows - 1 hold (or are reserved for) a row
+        self._slot_of: Dict[object, int] = {}
+
+    _INPUT, _UNIT, _HOST_STATE = "predictions", "videos", "the id map and the video count are"
 
     def _allocate(self, device) -> dict:
         """The accumulator, the result words (`flat`) and the per-video outputs."""
@@ -695,18 +732,8 @@ class ViewEnsembleTest(_DeviceCriterion):
                 "rank": torch.zeros((cap, H), dtype=torch.int32, device=device),
                 "pred": torch.zeros((cap, H), dtype=torch.int32, device=device)}
 
-    def _refuse_capture(self, device, what: str):
-        if self._capturing(device):
-            raise RuntimeError(f"ViewEnsembleTest.{what} cannot be captured in a graph: the id map and the video count are host state (a "
-                               "replay would fold the batch into the same videos again); call it eagerly")
-
-    def reset(self) -> "ViewEnsembleTest":
-        """Empty the accumulator (one memset on the stream), forget the ids and rewind the video count."""
-        if self._device is not None:
-            self._refuse_capture(self._device, "reset")
-            self._result_buffers(self._device)["state"].zero_()
-        self._slot_of, self._rows, self._computed, self._last = {}, 0, False, None
-        return self
+    def _forget(self):
+        self._slot_of = {}
 
     def _slots_of_ids(self, clip_ids) -> Tuple[List[int], Dict[object, int]]:
         """-> (the slot of every id, the id map grown by the new ids); nothing of self changes (the caller commits after its checks)."""
@@ -723,18 +750,14 @@ class ViewEnsembleTest(_DeviceCriterion):
         B = int(preds[0].shape[0])
         if (clip_ids is None) == (slots is None):
             raise ValueError("ViewEnsembleTest.update takes exactly one of clip_ids and slots")
-        if self._device is not None and dev != self._device:
-            raise ValueError(f"ViewEnsembleTest: predictions on {dev}, the accumulator is on {self._device}")
+        self._on_device(dev)
         grown = self._slot_of
         if clip_ids is not None:
             host, grown = self._slots_of_ids(list(clip_ids))
             host = torch.tensor(host, dtype=torch.int32)
             reach, slot_t = len(grown), host
         elif isinstance(slots, torch.Tensor) and slots.is_cuda:
-            if rows is None:
-                raise ValueError("ViewEnsembleTest.update: device slots need rows= (the number of videos they reach): the host cannot "
-                                 "read them without a synchronisation")
-            reach, slot_t = max(self._rows, int(rows)), slots
+            reach, slot_t = self._device_reach(rows), slots
         else:
             if self._slot_of:
                 raise ValueError("ViewEnsembleTest.update: clip_ids and slots cannot be mixed within an epoch")
@@ -744,30 +767,16 @@ class ViewEnsembleTest(_DeviceCriterion):
             reach, slot_t = max(self._rows, int(host.max()) + 1 if host.numel() else 0), host
         if slot_t.numel() != B:
             raise ValueError(f"ViewEnsembleTest.update: {slot_t.numel()} ids / slots for {B} clips")
-        if reach > self.capacity:
-            raise ValueError(f"ViewEnsembleTest.update: {reach} videos exceed capacity={self.capacity}")
-        b = self._result_buffers(dev)
-        if not slot_t.is_cuda:
-            slot_t = slot_t.to(dev, non_blocking=False)
+        b, slot_t = self._stage(dev, reach, slot_t)
         F_egx.view_ensemble_update(b["state"], self.capacity, self.classes, preds, labels.to(device=dev, dtype=torch.int64), slot_t,
                                    method=self.method)
-        self._device, self._rows, self._slot_of, self._computed = dev, reach, grown, False
+        self._slot_of = grown
+        self._commit(dev, reach)
 
-    def compute(self) -> dict:
-        """-> device tensors of the videos so far: `rank`, `pred` (n, H) int32 and the int32 counts `n`, `n_dropped`, `n_nonfinite`,
-        `n_invalid` (H,), `correct` (len(ks), H). Nothing synchronises."""
-        if self._device is None or self._rows == 0:
-            raise RuntimeError("ViewEnsembleTest: no update has run yet")
-        self._refuse_capture(self._device, "compute")
-        b = self._result_buffers(self._device)
-        res = F_egx.view_ensemble_topk(b["state"], self.capacity, self.classes, self._rows, self.ks, out=b)
-        self._last = {"buffers": b, "result": {k: v for k, v in res.items() if k != "flat"}}
-        self._computed = True
-        return dict(self._last["result"])
-
-    def stats(self) -> dict:
-        """The device tensors of the most recent compute()."""
-        return dict(self._latest()["result"])
+    def _metric(self, b: dict) -> dict:
+        """compute(): `rank`, `pred` (n, H) int32 and the int32 counts `n`, `n_dropped`, `n_nonfinite`, `n_invalid` (H,), `correct`
+        (len(ks), H)."""
+        return F_egx.view_ensemble_topk(b["state"], self.capacity, self.classes, self._rows, self.ks, out=b)
 
     def video_ids(self) -> list:
         """The clip ids in row order (first appearance); with slots= the rows are the caller's slots and this is range(n)."""
@@ -787,9 +796,7 @@ class ViewEnsembleTest(_DeviceCriterion):
         otherwise) = (1 - correct / n) * 100 in fp32, as the reference's fp32 tensors compute it, with n = the number of videos; and the
         counts f"{prefix}_n", _n_dropped, _n_nonfinite, f"{prefix}_n_invalid_{head}", f"{prefix}_correct{k}_{head}". Runs compute() first
         when clips arrived since the last one. prefix="" gives the reference's bare keys."""
-        if not self._computed and self._device is not None and self._rows > 0:
-            self.compute()
-        host = self._latest()["buffers"]["flat"].cpu().numpy()
+        host = self._host_flat()
         import numpy as np
         H, nc = len(self.classes), len(F_egx.VIEW_ENS_COUNTS)
         pre = f"{prefix}_" if prefix else ""

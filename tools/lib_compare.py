@@ -29,11 +29,18 @@ Cases (d = 128, three segments of d_in 256, d_ff 2048, 4 heads; f32s and bf16 ea
   i ASD rows (out_tokens) with the fused token loss, B 3, T 15, L 2, weight cache (two steps: the cache filled, then valid)
   n generic implementation forced: TTM logits with feature gradients; ASD rows (out_tokens sliced behind the library call), B 3, T 15, L 2,
     deterministic (the generic backward sums its bias and LayerNorm gradients with float atomics otherwise: they would not repeat)
+  s ragged training in the capacity form (device lengths, the batch table built on the device): LENS padded to capacity (6 clips, 112 tokens),
+    L 2, p 0.1, head + CE, feature gradients, eager; the status word is recorded too
+  t the per-length-group fallback on LENS with compute "f32", which the ragged kernels refuse (once, outside the f32s / bf16 loop): inference
+    with head and head-less; training, L 2, p 0.1, head + CE, feature gradients, deterministic (as case n)
 Cases on the EgoT2-g HHI model (d 256, 4 heads, L 3 + 3, bf16, seeded weights; B 4, T_pad 16, lengths LENS, 2 target tokens):
   j uniform encode_features + decode, p 0.1, forward + backward with d_memory; again under a recording functional.bucket_hook (its (lo, hi) calls compared)
   k encode_features_ragged + decode_ragged, p 0.1, with d_memory: 'ttm' (packed rows) and 'asd' (frame-major tuples, decode() on S = 3)
   l the calls of k under no_grad (their `saved` in the shared workspace), and eval-mode ragged inference (encode_features / decode with lengths)
   m greedy_decode, 4 steps, with logits
+  u encode_features_ragged with compute "f32" (the per-length-group fallback of the wide ragged path), p 0.1: 'ttm' (packed rows) and 'asd'
+    (frame-major tuples), forward + backward of the memory, and again under no_grad. The deterministic mode does not reach this entry point, so
+    the backward runs on one-clip groups ('asd': frame counts ASD_T), which repeat; the two-clip group of LENS' first column runs under no_grad
 Cases on the cached step (egx_decoder_generate / _beam / _forced) with the seeded models of tests/greedy_ref.py (hhi_model d 256, 4 heads, L 2,
 V 40; B 4, S 19; eager; every returned tensor and the call's launch count):
   o greedy_decode, 5 steps, a period-2 schedule, logits and return_attention
@@ -54,6 +61,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENS = [[1, 1, 1], [16, 16, 16], [15, 7, 16], [16, 1, 1]]      # S_b = 3, 48 (one full tile), 38, 18
+ASD_T = [1, 16, 15, 7]      # case u, 'asd': frame counts that are all different (one clip per length group)
+CAPACITY = (6, 112)        # case s: B_cap clips, tok_cap tokens (LENS has 4 clips of 107 tokens)
 CE_W = [0.266, 0.734]
 CHILD_TIMEOUT = 420
 
@@ -66,6 +75,7 @@ def gpu_child(path):
     import egot2_amd
     from egot2_amd import _lib, functional as F_egx, hhi_asd, hhi_multitask, hhi_ttm
     from egot2_amd.synth import HHI_G_VOCAB, hhi_args
+    from egot2_amd.train import pad_ragged_batch
     import importlib.util
     spec = importlib.util.spec_from_file_location("egx_tests_util", os.path.join(ROOT, "tests", "util.py"))   # this checkout's, whichever tree is compared
     util = importlib.util.module_from_spec(spec)
@@ -186,6 +196,12 @@ def gpu_child(path):
         assert F_egx.last_encoder_impl() == "ragged", F_egx.last_encoder_impl()
         m = model_of(ASD, 1, 0.1, compute, s0 + 8)
         step(f"h_rows_{compute}", m, lambda: m.forward_features_ragged(*f16, lengths=lens))
+        fcap, lcap, tcap = pad_ragged_batch(f16, lens, tgt4, CAPACITY)
+        fcap = [f.requires_grad_(True) for f in fcap]
+        m = model_of(TTM, 2, 0.1, compute, s0 + 11)
+        step(f"s_{compute}", m, lambda: m.forward_features_ragged(*fcap, lengths=lcap, target=tcap, class_weight=w, capacity=CAPACITY), feats=fcap)
+        assert F_egx.last_encoder_impl() == "ragged_cap", F_egx.last_encoder_impl()
+        keep(f"s_{compute}", "status", m.ragged_status())
         f15g = feats_of(11, 3, 15, grad=True)
         m = model_of(TTM, 2, 0.1, compute, s0 + 10, det=True, impl="generic")
         step(f"n_{compute}", m, lambda: m.forward_features(*f15g), feats=f15g)
@@ -194,12 +210,26 @@ def gpu_child(path):
         step(f"n_rows_{compute}", m, lambda: m.forward_features(*f15))
         assert F_egx.last_encoder_impl() == "generic", F_egx.last_encoder_impl()
 
+    # the per-length-group fallback of the d = 128 ragged entry points: exact fp32, which the ragged kernels refuse
+    f16, tgt4 = feats_of(14, 4, 16), torch.tensor([0, 1, 1, 0], device=cuda)
+    with torch.no_grad():
+        m = model_of(TTM, 2, 0.0, "f32", 207).eval()
+        step("t_f32", m, lambda: m.forward_features(*f16, lengths=lens))
+        assert F_egx.last_encoder_impl() == "grouped", F_egx.last_encoder_impl()
+        m = model_of(ASD, 2, 0.0, "f32", 207).eval()
+        step("t_rows_f32", m, lambda: m.forward_features(*f16, lengths=lens))
+        assert F_egx.last_encoder_impl() == "grouped", F_egx.last_encoder_impl()
+    f16g = feats_of(14, 4, 16, grad=True)
+    m = model_of(TTM, 2, 0.1, "f32", 208, det=True)
+    step("t_train_f32", m, lambda: m.forward_features_ragged(*f16g, lengths=lens, target=tgt4, class_weight=w), feats=f16g)
+    assert F_egx.last_encoder_impl() == "grouped", F_egx.last_encoder_impl()
+
     # EgoT2-g HHI model: the wide encoder and the fused decoder, uniform and ragged
-    def g_model(seed, p=0.1):
+    def g_model(seed, p=0.1, compute="bf16"):
         m = hhi_multitask.TaskTranslationPromptTransformer(hhi_args(hidden_dim=256, num_heads=4, num_layers=3, dropout=p), HHI_G_VOCAB)
         m.load_state_dict(seeded_state_dict(m, seed))
         m.pos_embed.dropout.p = p
-        m = m.to(cuda).set_compute("bf16").train()
+        m = m.to(cuda).set_compute(compute).train()
         m._egx_seed = lambda: 0x5EED0000 + seed
         return m
 
@@ -219,7 +249,6 @@ def gpu_child(path):
             return mem, logits
         step(tag, m, run, feats=held)
 
-    f16 = feats_of(14, 4, 16)
     y4, frames = targets(4, "ttm", 21), lens[:, 0]
     y_asd = targets(int(frames.sum()), "asd", 22)
     S = F_egx.ragged_lengths(lens, 4, [16, 16, 16]).sum(1)
@@ -251,6 +280,15 @@ def gpu_child(path):
         m = g_model(32)
         g_step(tag, m, lambda: fwd(m))
         assert F_egx.last_encoder_impl() == "ragged", F_egx.last_encoder_impl()
+    # both out_layouts of the grouped fallback. encode_features_ragged does not hand the deterministic mode down, and the generic backward of a
+    # group of several clips sums its bias and LayerNorm gradients with float atomics: the backward runs on one-clip groups ('asd': ASD_T), the
+    # two-clip group of `frames` under no_grad
+    for tag, task, ln, ln_fwd in (("u_ttm", "ttm", lens, lens), ("u_asd", "asd", torch.tensor(ASD_T), frames)):
+        m = g_model(33, compute="f32")
+        step(tag, m, lambda: m.encode_features_ragged(task, *f16, lengths=ln))
+        assert F_egx.last_encoder_impl() == "grouped", F_egx.last_encoder_impl()
+        with torch.no_grad():
+            step(tag + "_nograd", m, lambda: m.encode_features_ragged(task, *f16, lengths=ln_fwd))
     with torch.no_grad():
         m = g_model(32)
         g_step("l_ttm", m, lambda: ragged_ttm(m))

@@ -10,7 +10,7 @@ per batch. Paths:
                     T = tokens / (3 B) frames per task): the cost yardstick of a (c) step.
 Each path is timed with device events over the whole set after a warm-up pass; one JSON line per path with clips/s and trained frames/s
 (frames that reach the loss: (a) counts the truncated frames only). The "parity" line holds max |d logit| and the largest relative gradient
-difference between a (c) batch and the per-length-group fallback (functional._encoder_train_grouped) at p = 0.
+difference between a (c) batch and the per-length-group fallback (functional._encoder_grouped) at p = 0.
 usage: python tools/ragged_train.py [--clips 1024] [--batches 64,256] [--compute f32s] [--out profiles/ragged_train_<tag>.json]"""
 from __future__ import annotations
 
@@ -146,16 +146,15 @@ def main():
     res = []
     for grouped in (False, True):
         model = make(0.0)
-        orig = F_egx.encoder_ragged_train
-        if grouped:
-            F_egx.encoder_ragged_train = lambda spec, fs, lens, te, pt, lw, lb, pr, lt, hd=(), ce=None: \
-                F_egx._encoder_train_grouped(spec, fs, lens, te, pt, lw, lb, pr, lt, hd, ce)
+        orig = F_egx._ragged_train_refused
+        if grouped:     # (encoder_ragged_train then takes functional._encoder_grouped, as it does where the ragged kernels refuse)
+            F_egx._ragged_train_refused = lambda *args: True
         try:
             logits, loss = model.forward_features_ragged(*feats, lengths=ln, target=target[idx], class_weight=cw)
             loss.backward()
             impl = F_egx.last_encoder_impl()
         finally:
-            F_egx.encoder_ragged_train = orig
+            F_egx._ragged_train_refused = orig
         torch.cuda.synchronize()
         res.append((impl, logits.detach(), {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}))
     (i0, l0, g0), (i1, l1, g1) = res
