@@ -27,17 +27,8 @@ bool fused_ok(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
     for (int i = 0; i < pl.nseg; ++i) { d_in[i] = segs[i].d_in; T[i] = segs[i].T; hp[i] = segs[i].proj_w != nullptr; }
     return fused_supported(pl.d, pl.H, pl.dff, pl.S, pl.nseg, d_in, T, hp);
 }
-static size_t fused_mask_layer_words(const Plan& pl) { return (size_t)pl.vB * (pl.dff / 32) * 64; }       // one layer's alive words
-static size_t fused_mask_words(const Plan& pl) { return (size_t)pl.L * fused_mask_layer_words(pl); }
-static size_t fused_res_bytes(const Plan& pl) { return align_up((size_t)(1 + 2 * pl.L) * pl.N * pl.d * 4, 256); }
-// floats in front of residual block `which` (0 = res1, 1 = res2) of layer l in `saved`: [pre][res1, res2 per layer], (N, d) each
-static size_t fused_res_index(const Plan& pl, int l, int which) { return (size_t)(1 + 2 * l + which) * pl.N * pl.d; }
-// floats of one layer's log-sum-exp rows (tiled / ragged): H rows per token
-static size_t tiled_lse_layer_floats(const Plan& vp) { return (size_t)vp.H * vp.N; }
-// saved = [pre + 2L residual blocks][ReLU sign bits of the FFN hidden: one u32 per (layer, clip, hidden block, lane)][packs]
-static size_t fused_act_bytes(const Plan& pl) { return fused_res_bytes(pl) + align_up(fused_mask_words(pl) * 4, 256); }
-// Fragment-packed weight copies kept behind the saved activations (written by the forward, reused by the
-// backward): per segment the projection, per layer each matrix in both orientations.
+// Fragment-packed weight copies (written by the forward, reused by the backward): per segment the projection, per layer each matrix in
+// both orientations. They live in the caller's persistent weight cache (egx_config.weight_cache, ABI v15) or in the `packs` section of `saved`.
 struct FusedPackLayout {
     void* proj[EGX_MAX_SEGMENTS];
     struct Layer { void* in_w; void* in_wt; void* out_w; void* out_wt; void* lin1_w; void* lin1_wt; void* lin2_w; void* lin2_wt; } layer[FUSED_MAX_LAYERS];
@@ -63,41 +54,100 @@ static FusedPackLayout fused_pack_layout(const egx_config* cfg, const egx_segmen
     L.bytes = cur;
     return L;
 }
-// where the packed copies live: the caller's persistent weight cache (egx_config.weight_cache, ABI v15) or behind the saved activations
-static char* fused_pack_base(const egx_config* cfg, const void* saved, const Plan& vp) {
-    return cfg->weight_cache ? (char*)cfg->weight_cache : (char*)const_cast<void*>(saved) + fused_act_bytes(vp);
-}
-// The FFN hidden activation H (forward) and its gradient dH (backward) are handed to the weight-gradient kernel as operand tiles
-// instead of being recomputed there (ffn_dw_kernel, the recompute variant, is kept as the egx_ffn_dw unit hook): the FFN loops of the
+// The FFN hidden activation H (forward, `saved`) and its gradient dH (backward, scratch) are handed to the weight-gradient kernel as operand
+// tiles instead of being recomputed there (ffn_dw_kernel, the recompute variant, is kept as the egx_ffn_dw unit hook): the FFN loops of the
 // clip kernels store them unconditionally.
-static size_t fused_hid_total(const egx_config* cfg, const Plan& pl) {
-    return align_up((size_t)pl.L * fused_hid_bytes(pl.vB, pl.dff, cfg->compute == EGX_BF16), 256);
-}
-// saved = [activations][packed weights][H tiles]
-static size_t fused_hid_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return align_up(fused_act_bytes(pl) + fused_pack_layout(cfg, segs, pl, nullptr).bytes, 256);
-}
-// split / bf16 mode: the FFN input x1 of every layer as bf16 planes (L, 3 or 1, B * 48, d), behind the hidden tiles
-static bool split_planes(const egx_config* cfg) {
-    return cfg->compute == EGX_F32_SPLIT || cfg->compute == EGX_BF16;
-}
+static size_t fused_hid_total(const egx_config* cfg, const Plan& pl) { return align_up((size_t)pl.L * fused_hid_bytes(pl.vB, pl.dff, cfg->compute == EGX_BF16), 256); }
+// split / bf16 mode: the FFN input x1 of every layer is kept as bf16 planes
+static bool split_planes(const egx_config* cfg) { return cfg->compute == EGX_F32_SPLIT || cfg->compute == EGX_BF16; }
 static size_t plane_elem_bytes(const egx_config* cfg) { return cfg->compute == EGX_BF16 ? 2 : 6; }   // one bf16 plane, or the three parts
-static size_t fused_x1p_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return fused_hid_offset(cfg, segs, pl) + fused_hid_total(cfg, pl);
+constexpr int SLICE_LAYOUT_CUS = 304;       // the largest compute-unit count of the supported parts (gfx942: 304, gfx950: 256) bounds the slice count the layout
+                                            // provides for (ADVICE r5: 512 reserved a two-slice exchange buffer, 12.6 MB per layer, for the B = 256 headline batch)
+static int fused_slices_layout(const Plan& pl) {
+    const int nit = pl.dff / 128, bq = (pl.B + 7) / 8 * 8;
+    int n = 1;
+    while (n * 2 <= 8 && nit % (n * 2) == 0 && bq * n * 2 <= SLICE_LAYOUT_CUS) n *= 2;
+    return n;
 }
-// behind them: the input of every layer (L, N, d) and its Q | K | V rows (L, B, 48, 3d), fp32 (the backward loads instead of recomputing)
-static size_t fused_xin_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return fused_x1p_offset(cfg, segs, pl) + (split_planes(cfg) ? align_up((size_t)pl.L * pl.vB * FUSED_TOK_PAD * pl.d * plane_elem_bytes(cfg), 256) : 0);
+// the exchange buffer of the sliced mode (L, B, n, 48, d): one in `saved` for the forward, one in the backward's scratch
+static size_t sliced_xchg_bytes(const Plan& pl) {
+    const int n = fused_slices_layout(pl);
+    return n > 1 ? align_up((size_t)pl.L * pl.B * n * FUSED_TOK_PAD * pl.d * 4, 256) : 0;
 }
-static size_t fused_qkv_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return fused_xin_offset(cfg, segs, pl) + align_up((size_t)pl.L * pl.N * pl.d * 4, 256);
-}
-// behind them: x1 = LayerNorm1 output of every layer as fp32 rows (L, N, d): what the cut mode's attention-side launch hands to ffn_fwd_kernel
-static size_t fused_x1f_offset(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return fused_qkv_offset(cfg, segs, pl) + align_up((size_t)pl.L * pl.vB * FUSED_TOK_PAD * 3 * pl.d * 4, 256);
-}
-static size_t fused_core_bytes(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    return fused_x1f_offset(cfg, segs, pl) + (pl.tpc > 1 ? (size_t)0 : align_up((size_t)pl.L * pl.N * pl.d * 4, 256));
+
+// ---- the `saved` block of every d = 128 call ----------------------------------------------------------------------------------------------
+// One layout for the one-launch, cut, sliced, tiled and ragged calls, built once per call by saved_layout() and read by every launch
+// sequence, workspace query and test hook below. vB: workgroups (clips, or 48-token tiles), grid = 48 vB rows, N: tokens (B S; ragged: sum_b S_b).
+// The sections in order, each 256-byte aligned; one a layout does not have takes no bytes, its offset stays 0 and nothing reads it:
+//   res          fp32 [pre][res1, res2 per layer], (N, d) each: the pre-LN rows and the residual sums (res_index)
+//   relu_bits    ReLU / dropout sign bits of the FFN hidden: one u32 per (layer, workgroup, hidden block, lane)
+//   packs        the fragment-packed weights; reserved also when they live in egx_config.weight_cache
+//   hid          the FFN hidden tiles H of every layer (fused_hid_bytes: fp32, or bf16 in bf16 mode)
+//   x1p          f32s / bf16 only: the FFN input x1 of every layer as bf16 planes (L, 3 or 1, grid, d)
+//   xin          the input of every layer, fp32 (L, N, d)                    } the backward loads them
+//   qkv          its Q | K | V rows on the tile grid, fp32 (L, grid, 3d)     } instead of recomputing
+//  per-clip layout (S <= 48) only:
+//   x1f          x1 = LayerNorm1 output of every layer as fp32 rows (L, N, d): what the cut mode's attention-side launch hands to ffn_fwd_kernel
+//   xchg         where the shape admits slices: the forward's exchange buffer (L, B, n, 48, d)
+//   xflags_fwd, xflags_bwd   then the "published" words of the forward and of the backward, (L, B, 8) each (one per layer, clip and slice: SLICE_MAX = 8)
+//  tiled and ragged layouts only (attention runs between the tile launches):
+//   attn         every layer's attention output, fp32 (L, N, d)
+//   lse          every layer's log-sum-exp rows, H per token: (L, H, N); a uniform batch reads it as (L, B, H, S), N = B S
+//   tokens       the last layer's dense tokens (N, d), then the token means (B, d) of a translator call
+//  ragged layouts only:
+//   tab, efft    the device copy of the batch table (fused.h RAGGED_REC); capacity plan only: the effective targets, int64 (B)
+struct SavedLayout {
+    char* base;                 // the caller's block (null in a size query)
+    size_t res, relu_bits, packs, hid, x1p, xin, qkv, x1f, xchg, xflags_fwd, xflags_bwd, attn, lse, tokens, tab, efft, bytes;
+    size_t relu_layer_words, hid_layer, x1p_layer, qkv_layer, lse_layer_floats;     // one layer of the section (bytes unless named otherwise)
+    size_t res_block, flag_words;       // floats of one (N, d) block of `res`; words of xflags_fwd and of xflags_bwd each
+    FusedPackLayout pack;               // resolved: in the weight cache, else in `packs` (null pointers in a size query)
+    char* at(size_t off) const { return base + off; }
+    size_t res_index(int l, int which) const { return (size_t)(1 + 2 * l + which) * res_block; }    // floats in front of block `which` (0 = res1, 1 = res2) of layer l
+};
+// tiled: the layout of the tile grid (vp planned by plan_tiled, or a ragged plan: tab_words > 0, and efft_rows > 0 for the capacity plan)
+static SavedLayout saved_layout(const egx_config* cfg, const egx_segment* segs, const Plan& vp, bool tiled, const void* saved = nullptr,
+                                size_t tab_words = 0, size_t efft_rows = 0) {
+    SavedLayout s;
+    memset(&s, 0, sizeof(s));
+    s.base = (char*)const_cast<void*>(saved);
+    const size_t nd = vp.N * vp.d * 4, grid = (size_t)vp.vB * FUSED_TOK_PAD;
+    s.res_block = vp.N * vp.d;
+    s.relu_layer_words = (size_t)vp.vB * (vp.dff / 32) * 64;
+    s.hid_layer = fused_hid_bytes(vp.vB, vp.dff, cfg->compute == EGX_BF16);
+    s.x1p_layer = split_planes(cfg) ? grid * vp.d * plane_elem_bytes(cfg) : 0;
+    s.qkv_layer = grid * 3 * vp.d * 4;
+    size_t cur = 0;
+    s.res = take(cur, (1 + 2 * vp.L) * nd);
+    s.relu_bits = take(cur, vp.L * s.relu_layer_words * 4);
+    s.pack = fused_pack_layout(cfg, segs, vp, cfg->weight_cache ? (char*)cfg->weight_cache : saved ? s.base + cur : nullptr);
+    s.packs = take(cur, s.pack.bytes);
+    s.hid = take(cur, fused_hid_total(cfg, vp));
+    s.x1p = take(cur, vp.L * s.x1p_layer);
+    s.xin = take(cur, vp.L * nd);
+    s.qkv = take(cur, vp.L * s.qkv_layer);
+    const bool per_clip = !tiled, sliced = per_clip && fused_slices_layout(vp) > 1, ragged = tab_words > 0, capacity = efft_rows > 0;
+    if (per_clip) s.x1f = take(cur, vp.L * nd);
+    if (sliced) {
+        // The exchange buffer and the flag words are laid out for the LARGEST slice count the shape admits on any device and under any
+        // EGX_FFN_SLICES (fused_slices_layout: a function of the shape alone), so that the workspace query, the forward and the backward —
+        // which each pick their own run-time count <= that bound (fused_slices) — agree on every offset whatever the environment or the
+        // current device did between the calls (a changed count used to move the flag words past the caller's buffer).
+        s.flag_words = (size_t)vp.L * vp.B * 8;
+        s.xchg = take(cur, sliced_xchg_bytes(vp));
+        s.xflags_fwd = take(cur, 2 * s.flag_words * 4);
+        s.xflags_bwd = s.xflags_fwd + s.flag_words * 4;
+    }
+    if (tiled) {
+        s.lse_layer_floats = (size_t)vp.H * vp.N;
+        s.attn = take(cur, vp.L * nd);
+        s.lse = take(cur, vp.L * s.lse_layer_floats * 4);
+        s.tokens = take(cur, (vp.N + (size_t)vp.B) * vp.d * 4);
+    }
+    if (ragged) s.tab = take(cur, tab_words * sizeof(int));
+    if (capacity) s.efft = take(cur, efft_rows * sizeof(int64_t));
+    s.bytes = cur;
+    return s;
 }
 // Cut mode (ffn_cut.hip): the per-clip kernels cut at the FFN, whose loops run as launches of their own with eight waves per clip. One
 // workgroup per clip only (the sliced mode of small batches keeps the one-launch kernels). Policy = where it measured faster on MI355X
@@ -109,17 +159,6 @@ static bool use_cut(const Plan& pl, int n_slices, bool tiled, int compute) {
     if (tiled || n_slices != 1 || !ffn_cut_supported(pl.dff)) return false;
     if (tuning().ffn_cut >= 0) return tuning().ffn_cut != 0;
     return compute == EGX_F32_SPLIT && pl.L == 1 && pl.dff >= 1024;
-}
-static int fused_slices_layout(const Plan& pl);
-static size_t sliced_xchg_bytes(const Plan& pl, int n);
-static size_t sliced_flag_bytes(const Plan& pl, int n);
-// The exchange buffer and the flag words are laid out for the LARGEST slice count the shape admits on any device and under any
-// EGX_FFN_SLICES (fused_slices_layout: a function of the shape alone), so that the workspace query, the forward and the backward —
-// which each pick their own run-time count <= that bound (fused_slices) — agree on every offset whatever the environment or the
-// current device did between the calls (a changed count used to move the flag words past the caller's buffer).
-static size_t fused_saved_bytes(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
-    const int n = (pl.tpc > 1 || pl.S > FUSED_TOK_PAD) ? 1 : fused_slices_layout(pl);
-    return fused_core_bytes(cfg, segs, pl) + sliced_xchg_bytes(pl, n) + sliced_flag_bytes(pl, n);
 }
 // ---- sliced mode (small batches): n workgroups per clip, each 1 / n of the FFN hidden blocks (FusedFwdParams::n_slices). Only when
 // the workgroups of the launch can all be resident at once: round_up(B, 8) * n <= CUs (a performance rule, not a protocol: a slice
@@ -154,14 +193,6 @@ static bool device_slicing_ok() {
     }
     return ok[dev] == 1;
 }
-constexpr int SLICE_LAYOUT_CUS = 304;       // the largest compute-unit count of the supported parts (gfx942: 304, gfx950: 256) bounds the slice count the layout
-                                            // provides for (ADVICE r5: 512 reserved a two-slice exchange buffer, 12.6 MB per layer, for the B = 256 headline batch)
-static int fused_slices_layout(const Plan& pl) {
-    const int nit = pl.dff / 128, bq = (pl.B + 7) / 8 * 8;
-    int n = 1;
-    while (n * 2 <= 8 && nit % (n * 2) == 0 && bq * n * 2 <= SLICE_LAYOUT_CUS) n *= 2;
-    return n;
-}
 int fused_slices(const Plan& pl, int compute) {
     if (!device_slicing_ok()) return 1;
     const bool e = tuning().has_slices;            // (EGX_FFN_SLICES; the LAYOUT does not depend on it)
@@ -175,21 +206,10 @@ int fused_slices(const Plan& pl, int compute) {
     const int cap_layout = fused_slices_layout(pl);
     return n < cap_layout ? n : cap_layout;
 }
-// behind the fused layout: the forward's exchange buffer (L, B, n, 48, d) and the "published" words of forward and backward (2, L, B, 8)
-static size_t sliced_xchg_bytes(const Plan& pl, int n) { return n > 1 ? align_up((size_t)pl.L * pl.B * n * FUSED_TOK_PAD * pl.d * 4, 256) : 0; }
-static size_t sliced_flag_words(const Plan& pl) { return (size_t)pl.L * pl.B * 8; }       // one "published" word per (layer, clip, slice): SLICE_MAX = 8
-static size_t sliced_flag_bytes(const Plan& pl, int n) { return n > 1 ? align_up(2 * sliced_flag_words(pl) * 4, 256) : 0; }
 
-// ---- tiled mode (d = 128, 48 < S <= 512): the same kernels over 48-token tiles, attention between the launches. Behind the fused
-// layout of the tile grid: every layer's attention output (L, N, d) and log-sum-exp (L, B, H, S), then room for the output tokens
-// and the pooled vector of a translator call
-static void plan_tiled(Plan& pl) { pl.tpc = cdiv(pl.S, FUSED_TOK_PAD); pl.vB = pl.B * pl.tpc; }
-static size_t tiled_attn_offset(const egx_config* cfg, const egx_segment* segs, const Plan& vp) { return align_up(fused_saved_bytes(cfg, segs, vp), 256); }
-static size_t tiled_lse_offset(const egx_config* cfg, const egx_segment* segs, const Plan& vp) { return tiled_attn_offset(cfg, segs, vp) + align_up((size_t)vp.L * vp.N * vp.d * 4, 256); }
-static size_t tiled_tokens_offset(const egx_config* cfg, const egx_segment* segs, const Plan& vp) { return tiled_lse_offset(cfg, segs, vp) + align_up((size_t)vp.L * vp.B * vp.H * vp.S * 4, 256); }
-static size_t tiled_saved_bytes(const egx_config* cfg, const egx_segment* segs, const Plan& vp) {
-    return tiled_tokens_offset(cfg, segs, vp) + align_up((vp.N + (size_t)vp.B) * vp.d * 4, 256);
-}
+// ---- tiled mode (d = 128, 48 < S <= 512): the same kernels over 48-token tiles, attention between the launches
+// sizes of the tile grid: vB workgroups ("virtual clips"); B / N stay the real clips / tokens
+static Plan plan_tiled(Plan pl) { pl.tpc = cdiv(pl.S, FUSED_TOK_PAD); pl.vB = pl.B * pl.tpc; return pl; }
 bool tiled_ok(const egx_config* cfg, const egx_segment* segs, const Plan& pl) {
     if (pl.d != 128 || pl.H != 4 || pl.dff % 128 != 0 || pl.dff < 128) return false;
     if (pl.S <= FUSED_TOK_PAD || pl.S > TILED_MAX_S) return false;
@@ -232,12 +252,13 @@ static size_t bwd_scratch_prefix(FusedBwdScratch& s, const egx_config* cfg, cons
     slab = size_max(slab, gemm_scratch_bytes(2, 3 * pl.d, pl.d, (int)pl.N));
     slab = size_max(slab, gemm_scratch_bytes(2, pl.d, pl.d, (int)pl.N));
     for (int i = 0; i < pl.nseg; ++i) slab = size_max(slab, gemm_scratch_bytes(2, pl.d, segs[i].d_in, (int)seg_rows[i]));
-    slab = size_max(slab, (size_t)(512 + SMALL_DW_MAX * 16) * 64 * 128 * sizeof(float));   // deterministic small_dw: one tile per workgroup
+    const size_t sdw_bytes = (size_t)(512 + SMALL_DW_MAX * 16) * 64 * 128 * sizeof(float);   // small_dw's tiles: one per workgroup
+    slab = size_max(slab, sdw_bytes);       // (deterministic small_dw of the staged backward leaves them in the slab area)
     s.slab_bytes = slab;
     s.slabs = take(cur, slab);
     s.ffn_slab[0] = s.slabs;
     for (int l = 1; l < pl.L && l < FUSED_MAX_LAYERS; ++l) s.ffn_slab[l] = take(cur, ffn_dw_scratch_bytes((int)pl.N, pl.dff, nullptr));
-    s.sdw_bytes = (size_t)(512 + SMALL_DW_MAX * 16) * 64 * 128 * sizeof(float);
+    s.sdw_bytes = sdw_bytes;
     s.sdw_tiles = take(cur, s.sdw_bytes);
     s.dhid = take(cur, fused_hid_total(cfg, pl));
     return cur;
@@ -255,7 +276,7 @@ static FusedBwdScratch fused_bwd_scratch(const egx_config* cfg, const egx_segmen
         s.delta = take(cur, (size_t)pl.B * pl.H * pl.S * 4);
         s.dtok = take(cur, nd);
     } else {
-        s.xchg = take(cur, sliced_xchg_bytes(pl, fused_slices_layout(pl)));
+        s.xchg = take(cur, sliced_xchg_bytes(pl));
     }
     s.bytes = cur;
     return s;
@@ -331,13 +352,12 @@ size_t fused_weight_cache_bytes(const egx_config* cfg, const egx_segment* segs, 
 void fused_workspace(const egx_config* cfg, const egx_segment* segs, const Plan& pl, size_t* saved, size_t* scratch) {
     *saved = 0; *scratch = 0;
     if (tiled_ok(cfg, segs, pl)) {
-        Plan vp = pl;
-        plan_tiled(vp);
-        *saved = tiled_saved_bytes(cfg, segs, vp);
+        const Plan vp = plan_tiled(pl);
+        *saved = saved_layout(cfg, segs, vp, true).bytes;
         *scratch = fused_bwd_scratch(cfg, segs, vp, FUSED_HEAD_MAX_OUT).bytes;       // (the pooled head's partial-row section: sized for the largest head)
     }
     if (fused_ok(cfg, segs, pl)) {
-        *saved = size_max(*saved, fused_saved_bytes(cfg, segs, pl));
+        *saved = size_max(*saved, saved_layout(cfg, segs, pl, false).bytes);
         *scratch = size_max(*scratch, fused_bwd_scratch(cfg, segs, pl, FUSED_HEAD_MAX_OUT).bytes);
     }
 }
@@ -355,19 +375,17 @@ int check_ce(const egx_ce* ce, bool with_head, const char* entry) {
 // ---- one driver for uniform and ragged batches -------------------------------------------------------------------------------------------
 // What differs between the callers of the clip / tile kernels. A ragged batch is a tiled batch with a batch table and another workspace view.
 struct TiledView {
-    char* base;                             // the saved block of the uniform call / the ragged workspace
-    size_t off_attn, off_lse, off_tokens;   // tiled: every layer's attention output (L, N, d) and log-sum-exp rows, then the dense tokens (N, d) + token means (B, d)
+    const SavedLayout* sl;                  // the saved block of the uniform call / the ragged workspace
     const int* rtab;                        // device batch table (fused.h RAGGED_REC); nullptr = uniform. Selects the pooled-head launch too
     int B_clips, tpc, S_clip;               // clips, tiles per clip (ragged: 0, the table has them), tokens of the (longest) clip
     bool tiled;
     int rot_mode;                           // hidden-block walk order of the FFN loops
     bool keys;                              // the forward hands on dropout keys, the device seed and its advance (all but ragged inference)
 };
-static TiledView uniform_view(const egx_config* cfg, const egx_segment* segs, const Plan& vp, const void* saved, bool tiled) {
+static TiledView uniform_view(const Plan& vp, const SavedLayout& SL, bool tiled) {
     TiledView v;
     memset(&v, 0, sizeof(v));
-    v.base = (char*)const_cast<void*>(saved);
-    if (tiled) { v.off_attn = tiled_attn_offset(cfg, segs, vp); v.off_lse = tiled_lse_offset(cfg, segs, vp); v.off_tokens = tiled_tokens_offset(cfg, segs, vp); }
+    v.sl = &SL;
     v.B_clips = vp.B; v.tpc = vp.tpc; v.S_clip = vp.S; v.tiled = tiled;
     v.rot_mode = FFN_ROT_XCD_STAGGER;
     v.keys = true;
@@ -376,9 +394,11 @@ static TiledView uniform_view(const egx_config* cfg, const egx_segment* segs, co
 
 // The part of FusedFwdParams and of the packing launch every forward fills alike. Left to the caller: the output pointers, and of the
 // uniform call seg[i].off / row0, the feature-dropout keys, out_T, the fused head and losses, the slices.
-static void fill_fwd(FusedFwdParams& fp, PackParams& pk, const FusedPackLayout& PL, const TiledView& v, const egx_config* cfg, const egx_segment* segs,
+static void fill_fwd(FusedFwdParams& fp, PackParams& pk, const TiledView& v, const egx_config* cfg, const egx_segment* segs,
                      const Plan& vp, const float* ln_w, const float* ln_b, const egx_layer* layers, int training, uint64_t seed) {
     const int d = vp.d;
+    const SavedLayout& SL = *v.sl;
+    const FusedPackLayout& PL = SL.pack;
     memset(&fp, 0, sizeof(fp));
     // rewrite the weights into MFMA-fragment order (once per forward; they live behind the saved activations or in the weight cache)
     memset(&pk, 0, sizeof(pk));
@@ -399,13 +419,13 @@ static void fill_fwd(FusedFwdParams& fp, PackParams& pk, const FusedPackLayout& 
     fp.ln_w = ln_w; fp.ln_b = ln_b; fp.eps = cfg->ln_eps;
     fp.nseg = vp.nseg; fp.n_layers = vp.L; fp.B = vp.vB; fp.S = v.tiled ? FUSED_TOK_PAD : vp.S; fp.d_ff = vp.dff;
     fp.tpc = v.tpc; fp.S_clip = v.S_clip; fp.Ntok = vp.N; fp.mode = FUSED_MODE_FULL;
-    fp.saved_pre = (float*)v.base;
-    fp.saved_res = (float*)v.base + fused_res_index(vp, 0, 0);
-    fp.relu_bits = (uint32_t*)(v.base + fused_res_bytes(vp));
-    fp.hid_out = v.base + fused_hid_offset(cfg, segs, vp);
-    fp.x1p_out = split_planes(cfg) ? (unsigned short*)(v.base + fused_x1p_offset(cfg, segs, vp)) : nullptr;
-    fp.xin_out = (float*)(v.base + fused_xin_offset(cfg, segs, vp));
-    fp.qkv_out = (float*)(v.base + fused_qkv_offset(cfg, segs, vp));
+    fp.saved_pre = (float*)SL.at(SL.res);
+    fp.saved_res = fp.saved_pre + SL.res_index(0, 0);
+    fp.relu_bits = (uint32_t*)SL.at(SL.relu_bits);
+    fp.hid_out = SL.at(SL.hid);
+    fp.x1p_out = split_planes(cfg) ? (unsigned short*)SL.at(SL.x1p) : nullptr;
+    fp.xin_out = (float*)SL.at(SL.xin);
+    fp.qkv_out = (float*)SL.at(SL.qkv);
     if (v.keys) {
         Drop dpz = make_drop(training, cfg->p_pos, seed, 0, SITE_POS);
         fp.pos_key = dpz.key; fp.pos_thresh = dpz.thresh; fp.pos_inv = dpz.inv_keep;
@@ -417,13 +437,13 @@ static void fill_fwd(FusedFwdParams& fp, PackParams& pk, const FusedPackLayout& 
 }
 
 // the attention launch of layer l between the tile launches, both directions
-static TiledAttnParams tiled_attn_params(const TiledView& v, const Plan& vp, int l, const float* qkv, float* attn_o, uint64_t key, uint32_t thresh,
+static TiledAttnParams tiled_attn_params(const TiledView& v, int l, const float* qkv, float* attn_o, uint64_t key, uint32_t thresh,
                                          float inv, const uint64_t* seed_ptr) {
     TiledAttnParams ap;
     memset(&ap, 0, sizeof(ap));
-    ap.qkv = qkv + (size_t)l * vp.vB * FUSED_TOK_PAD * 3 * vp.d;
+    ap.qkv = qkv + l * (v.sl->qkv_layer / 4);
     ap.attn_o = attn_o;
-    ap.lse = (float*)(v.base + v.off_lse) + (size_t)l * tiled_lse_layer_floats(vp);     // H N rows per layer (= B H S of a uniform batch: N = B S)
+    ap.lse = (float*)v.sl->at(v.sl->lse) + l * v.sl->lse_layer_floats;
     ap.B = v.B_clips; ap.S = v.S_clip; ap.tpc = v.tpc;
     ap.drop_key = key; ap.drop_thresh = thresh; ap.drop_inv = inv;
     ap.seed_ptr = seed_ptr; ap.layer = l;
@@ -435,19 +455,19 @@ static TiledAttnParams tiled_attn_params(const TiledView& v, const Plan& vp, int
 // + Q | K | V of the next layer] (2 L + 1 launches), then the pooled head on the output tokens and the cross entropy on its logits
 static int tiled_forward(FusedFwdParams& fp, const TiledView& v, const egx_config* cfg, const Plan& vp, const egx_head* head, float* logits_out, hipStream_t st) {
     const int d = vp.d, comp = cfg->compute;
-    float* attn = (float*)(v.base + v.off_attn);
+    float* attn = (float*)v.sl->at(v.sl->attn);
     fp.attn_in = attn;
     fp.mode = FUSED_MODE_PRE;
     if (fused_forward(fp, comp, st)) return 1;
     for (int l = 0; l < vp.L; ++l) {
         const FusedLayer& fl = fp.layer[l];
-        const TiledAttnParams ap = tiled_attn_params(v, vp, l, fp.qkv_out, attn + (size_t)l * vp.N * d, fl.attn_key, fl.attn_thresh, fl.drop_inv, fp.seed_ptr);
+        const TiledAttnParams ap = tiled_attn_params(v, l, fp.qkv_out, attn + (size_t)l * vp.N * d, fl.attn_key, fl.attn_thresh, fl.drop_inv, fp.seed_ptr);
         if (tiled_attn_fwd(ap, comp, st)) return 1;
         fp.mode = FUSED_MODE_POST; fp.l0 = l;
         if (fused_forward(fp, comp, st)) return 1;
     }
     if (head && head->W) {
-        float* pooled = (float*)(v.base + v.off_tokens) + vp.N * d;
+        float* pooled = (float*)v.sl->at(v.sl->tokens) + vp.N * d;
         if (v.rtab ? pool_head_ragged_fwd(fp.tokens_out, v.rtab, v.B_clips, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, pooled, logits_out, st)
                    : pool_head_fwd(fp.tokens_out, v.B_clips, v.S_clip, d, head->ln_w, head->ln_b, cfg->ln_eps, head->W, head->b, head->n_out, pooled, logits_out, st)) return 1;
         const egx_ce* ce = cfg->ce;
@@ -458,10 +478,11 @@ static int tiled_forward(FusedFwdParams& fp, const TiledView& v, const egx_confi
 
 // The part of FusedBwdParams every backward fills alike. Left to the caller: of the uniform call seg[i].off / row0, the feature-dropout
 // keys, out_T, dx0_out, token_ce and the slices; of the ragged call rseg.
-static int fill_bwd(FusedBwdParams& bp, const FusedPackLayout& PL, const FusedBwdScratch& SC, const TiledView& v, const egx_config* cfg,
+static int fill_bwd(FusedBwdParams& bp, const FusedBwdScratch& SC, const TiledView& v, const egx_config* cfg,
                     const egx_segment* segs, const Plan& vp, const float* ln_w, const float* ln_b, const egx_layer* layers, const egx_head* head,
                     const float* d_logits, const float* d_tokens, void* scratch, int training, uint64_t seed) {
     const size_t N = vp.N, d = vp.d;
+    const SavedLayout& SL = *v.sl;
     memset(&bp, 0, sizeof(bp));
     for (int i = 0; i < vp.nseg; ++i) {
         fill_seg(bp.seg[i], segs[i], i);
@@ -470,13 +491,13 @@ static int fill_bwd(FusedBwdParams& bp, const FusedPackLayout& PL, const FusedBw
     bp.n_heads = vp.H;
     for (int l = 0; l < vp.L; ++l) {
         FusedBwdLayer& fl = bp.layer[l];
-        fill_bwd_layer(fl, layers[l], PL.layer[l]);
+        fill_bwd_layer(fl, layers[l], SL.pack.layer[l]);
         set_layer_drop(fl, training, cfg->p_drop, seed, l);
         fl.x1_out = fptr(scratch, SC.x1[l]); fl.g2_out = fptr(scratch, SC.g2[l]);
         fl.g1_out = fptr(scratch, SC.g1[l]); fl.dqkv_out = fptr(scratch, SC.dqkv[l]);
-        fl.x_in_out = (float*)(v.base + fused_xin_offset(cfg, segs, vp)) + l * N * d;      // saved by the forward
+        fl.x_in_out = (float*)SL.at(SL.xin) + l * N * d;      // saved by the forward
         // tiled mode: the attention output was saved by the forward too (the per-clip kernels recompute it in P10)
-        fl.attn_o_out = v.tiled ? (float*)(v.base + v.off_attn) + l * N * d : fptr(scratch, SC.attn_o[l]);
+        fl.attn_o_out = v.tiled ? (float*)SL.at(SL.attn) + l * N * d : fptr(scratch, SC.attn_o[l]);
     }
     bp.ln_w = ln_w; bp.ln_b = ln_b; bp.eps = cfg->ln_eps;
     bp.nseg = vp.nseg; bp.n_layers = vp.L; bp.B = vp.vB; bp.S = v.tiled ? FUSED_TOK_PAD : vp.S; bp.d_ff = vp.dff;
@@ -488,12 +509,12 @@ static int fill_bwd(FusedBwdParams& bp, const FusedPackLayout& PL, const FusedBw
         bp.d_logits = d_logits;
         bp.d_logits_scale = cfg->d_logits_scale;
         bp.head_off = fused_partial_len(vp.L, vp.nseg);
-        if (v.tiled) bp.pooled = (const float*)(v.base + v.off_tokens) + N * d;
+        if (v.tiled) bp.pooled = (const float*)SL.at(SL.tokens) + N * d;
     }
-    bp.saved_pre = (const float*)v.base;
-    bp.saved_res = (const float*)v.base + fused_res_index(vp, 0, 0);
-    bp.saved_qkv = (const float*)(v.base + fused_qkv_offset(cfg, segs, vp));
-    bp.relu_bits = (const uint32_t*)(v.base + fused_res_bytes(vp));
+    bp.saved_pre = (const float*)SL.at(SL.res);
+    bp.saved_res = bp.saved_pre + SL.res_index(0, 0);
+    bp.saved_qkv = (const float*)SL.at(SL.qkv);
+    bp.relu_bits = (const uint32_t*)SL.at(SL.relu_bits);
     bp.dhid_out = (char*)scratch + SC.dhid;
     bp.xg_planes = split_planes(cfg) ? 1 : 0;
     EGX_CHECK(cfg->zero_bytes % 16 == 0 && (((uintptr_t)cfg->zero_buf) & 15) == 0, "zero_buf must be 16-byte aligned and sized");
@@ -516,7 +537,7 @@ static int tiled_backward(FusedBwdParams& bp, const FusedBwdScratch& SC, const T
         if (fused_backward(bp, comp, st)) return 1;
         bp.zero_buf = nullptr;
         const FusedBwdLayer& fl = bp.layer[l];
-        TiledAttnParams ap = tiled_attn_params(v, vp, l, bp.saved_qkv, fl.attn_o_out, fl.attn_key, fl.attn_thresh, fl.drop_inv, cfg->seed_ptr);
+        TiledAttnParams ap = tiled_attn_params(v, l, bp.saved_qkv, fl.attn_o_out, fl.attn_key, fl.attn_thresh, fl.drop_inv, cfg->seed_ptr);
         ap.d_o = bp.datt; ap.delta = fptr(scratch, SC.delta); ap.dqkv = fl.dqkv_out;
         if (tiled_attn_bwd(ap, comp, st)) return 1;
     }
@@ -559,25 +580,25 @@ static void partial_dsts(ReducePartialsParams& rp, const FusedBwdParams& bp, con
 // launch behind the last one. (Round 6 tried it right behind ffn_bwd_kernel of the same layer, while dH and g2 are still in the Infinity
 // Cache: three same-box pairs 372.1 / 374.9 / 371.9 vs 372.2 / 370.3 / 376.1 us, no difference; and the exact-fp32 mode needs x1 from the
 // attention-side launch first. It stays behind the whole backward.)
-static int launch_ffn_dw(int l, const FusedBwdParams& bp, const FusedPackLayout& PL, const FusedBwdScratch& SC, const TiledView& v, const egx_config* cfg,
-                         const egx_segment* segs, const Plan& vp, const egx_layer* layers, const egx_layer_grads* layer_grads, void* scratch,
+static int launch_ffn_dw(int l, const FusedBwdParams& bp, const FusedBwdScratch& SC, const TiledView& v, const egx_config* cfg,
+                         const Plan& vp, const egx_layer* layers, const egx_layer_grads* layer_grads, void* scratch,
                          SlabReduce& red, hipStream_t st) {
     const egx_layer_grads& gw = layer_grads[l];
     if (!(gw.lin1_w || gw.lin1_b || gw.lin2_w)) return 0;
     const int comp = cfg->compute;
+    const SavedLayout& SL = *v.sl;
     FfnDwParams fp;
     memset(&fp, 0, sizeof(fp));
     fp.x1 = bp.layer[l].x1_out; fp.g = bp.layer[l].g2_out;
-    fp.w1p = PL.layer[l].lin1_w; fp.w2tp = PL.layer[l].lin2_wt; fp.b1 = layers[l].lin1_b;
+    fp.w1p = SL.pack.layer[l].lin1_w; fp.w2tp = SL.pack.layer[l].lin2_wt; fp.b1 = layers[l].lin1_b;
     fp.N = (int)vp.N; fp.S = vp.S; fp.d_ff = vp.dff;
     fp.drop_key = bp.layer[l].ffn_key; fp.drop_thresh = bp.layer[l].ffn_thresh; fp.drop_inv = bp.layer[l].drop_inv;
     fp.seed_ptr = cfg->seed_ptr; fp.layer = l;
-    const size_t lo = (size_t)l * fused_hid_bytes(vp.vB, vp.dff, comp == EGX_BF16);
-    fp.hs = v.base + fused_hid_offset(cfg, segs, vp) + lo;
-    fp.dhs = (const char*)scratch + SC.dhid + lo;
+    fp.hs = SL.at(SL.hid + l * SL.hid_layer);
+    fp.dhs = (const char*)scratch + SC.dhid + l * SL.hid_layer;
     fp.B = vp.vB;
     fp.xg_planes = bp.xg_planes;
-    if (fp.xg_planes) fp.x1 = (const float*)(v.base + fused_x1p_offset(cfg, segs, vp) + (size_t)l * vp.vB * FUSED_TOK_PAD * vp.d * plane_elem_bytes(cfg));
+    if (fp.xg_planes) fp.x1 = (const float*)SL.at(SL.x1p + l * SL.x1p_layer);
     return ffn_dw(fp, comp, gw.lin1_w, gw.lin1_b, gw.lin2_w, (char*)scratch + SC.ffn_slab[l], st, nullptr, cfg->deterministic != 0, &red);
 }
 
@@ -633,13 +654,13 @@ int fused_path_fwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     const bool with_head = head && head->W;
     const egx_ce* ce = cfg->ce;
     const egx_token_ce* tce = cfg->token_ce;
-    Plan vp = pl;               // sizes of the tile grid: vp.vB workgroups ("virtual clips"); vp.B / vp.N stay the real clips / tokens
-    if (tiled) plan_tiled(vp);
-    const TiledView v = uniform_view(cfg, segs, vp, saved, tiled);
-    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
+    const Plan vp = tiled ? plan_tiled(pl) : pl;
+    const SavedLayout SL = saved_layout(cfg, segs, vp, tiled, saved);
+    const FusedPackLayout& PL = SL.pack;
+    const TiledView v = uniform_view(vp, SL, tiled);
     FusedFwdParams fp;
     PackParams pk;
-    fill_fwd(fp, pk, PL, v, cfg, segs, vp, ln_w, ln_b, layers, training, seed);
+    fill_fwd(fp, pk, v, cfg, segs, vp, ln_w, ln_b, layers, training, seed);
     for (int i = 0; i < pl.nseg; ++i) {
         fp.seg[i].off = pl.seg_off[i]; fp.seg[i].row0 = 0;
         Drop df = make_drop(training, cfg->p_feat, seed, (uint32_t)i, SITE_FEAT);
@@ -648,7 +669,7 @@ int fused_path_fwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     fp.tokens_out = tokens_out;
     fp.out_T = cfg->out_tokens > 0 ? cfg->out_tokens : S;
     if (tiled) {
-        if (!fp.tokens_out) fp.tokens_out = (float*)(v.base + v.off_tokens);
+        if (!fp.tokens_out) fp.tokens_out = (float*)SL.at(SL.tokens);
         if (pack_weights(pk, st)) return 1;
         return tiled_forward(fp, v, cfg, vp, head, logits_out, st);
     }
@@ -658,12 +679,11 @@ int fused_path_fwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     }
     fp.n_slices = fused_slices(pl, comp);
     if (fp.n_slices > 1) {
-        fp.xchg = (float*)((char*)saved + fused_core_bytes(cfg, segs, vp));
-        fp.xflags = (unsigned*)((char*)saved + fused_core_bytes(cfg, segs, vp) + sliced_xchg_bytes(pl, fused_slices_layout(pl)));
-        pk.zero_words = fp.xflags; pk.n_zero = (int)sliced_flag_words(pl);        // the packing launch (always in front) zeroes the flags
+        fp.xchg = (float*)SL.at(SL.xchg); fp.xflags = (unsigned*)SL.at(SL.xflags_fwd);
+        pk.zero_words = fp.xflags; pk.n_zero = (int)SL.flag_words;        // the packing launch (always in front) zeroes the flags
         fp.slice_drop = slice_drop_mask(fp.n_slices);
     }
-    fp.x1f_out = (float*)((char*)saved + fused_x1f_offset(cfg, segs, vp));
+    fp.x1f_out = (float*)SL.at(SL.x1f);
     const bool cut = use_cut(pl, fp.n_slices, false, comp);
     // fused weighted cross entropy (egx_ce): in the epilogue of the launch that writes the logits; every clip adds its term into *loss,
     // which the packing launch zeroes when there is one, else the first launch of a cut-mode forward, else a memset node
@@ -718,10 +738,10 @@ int fused_path_bwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
                    const egx_head_grads* head_grads, int training, uint64_t seed, hipStream_t st) {
     const int d = pl.d, S = pl.S, B = pl.B, comp = cfg->compute;
     const bool with_head = head && head->W;
-    Plan vp = pl;
-    if (tiled) plan_tiled(vp);
-    const TiledView v = uniform_view(cfg, segs, vp, saved, tiled);
-    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
+    const Plan vp = tiled ? plan_tiled(pl) : pl;
+    const SavedLayout SL = saved_layout(cfg, segs, vp, tiled, saved);
+    const FusedPackLayout& PL = SL.pack;
+    const TiledView v = uniform_view(vp, SL, tiled);
     const egx_token_ce* tce = cfg->token_ce;
     if (tce) {
         EGX_CHECK(!with_head && !tiled && fused_token_ce_ok(cfg, pl), "egx_config.token_ce: not on this configuration (egx_encoder_token_ce_ok)");
@@ -729,7 +749,7 @@ int fused_path_bwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     }
     FusedBwdScratch SC = fused_bwd_scratch(cfg, segs, vp, with_head ? head->n_out : tce ? tce->C : 0);
     FusedBwdParams bp;
-    if (fill_bwd(bp, PL, SC, v, cfg, segs, vp, ln_w, ln_b, layers, head, d_logits, d_tokens, scratch, training, seed)) return 1;
+    if (fill_bwd(bp, SC, v, cfg, segs, vp, ln_w, ln_b, layers, head, d_logits, d_tokens, scratch, training, seed)) return 1;
     const bool touch = cfg->weight_cache != nullptr && !tiled;      // (see the forward)
     const size_t ffn_pb = packed_bytes(pl.dff, d, comp), in_pb = packed_bytes(3 * d, d, comp), out_pb = packed_bytes(d, d, comp);
     for (int i = 0; i < pl.nseg; ++i) {
@@ -752,8 +772,8 @@ int fused_path_bwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     if (!tiled) bp.n_slices = fused_slices(pl, comp);
     if (bp.n_slices > 1 && stage != 2) {
         bp.xchg = fptr(scratch, SC.xchg);
-        bp.xflags = (unsigned*)((char*)const_cast<void*>(saved) + fused_core_bytes(cfg, segs, vp) + sliced_xchg_bytes(pl, fused_slices_layout(pl))) + sliced_flag_words(pl);
-        EGX_HIP(hipMemsetAsync(bp.xflags, 0, sliced_flag_words(pl) * 4, st));
+        bp.xflags = (unsigned*)SL.at(SL.xflags_bwd);
+        EGX_HIP(hipMemsetAsync(bp.xflags, 0, SL.flag_words * 4, st));
         bp.slice_drop = slice_drop_mask(bp.n_slices);
     }
     if (stage != 2 && tiled) {
@@ -790,7 +810,7 @@ int fused_path_bwd(const egx_config* cfg, const egx_segment* segs, const Plan& p
     SlabReduce red;
     red.narr = 0; red.nslab = 0;
     for (int l = 0; l < pl.L && stage != 2; ++l)
-        if (launch_ffn_dw(l, bp, PL, SC, v, cfg, segs, vp, layers, layer_grads, scratch, red, st)) return 1;
+        if (launch_ffn_dw(l, bp, SC, v, cfg, vp, layers, layer_grads, scratch, red, st)) return 1;
     // egx_config.advance_seed == 2: the backward advances the device seed behind its last reader (the last launch that can run here)
     uint64_t* adv = (cfg->advance_seed == 2 && cfg->seed_ptr && training && stage != 1) ? const_cast<uint64_t*>(cfg->seed_ptr) : nullptr;
     const float* feat[EGX_MAX_SEGMENTS];
@@ -835,10 +855,9 @@ namespace {
 struct RaggedPlan {
     Plan vp;                    // vp.B clips, vp.vB tiles, vp.N = sum_b S_b tokens, vp.S = the longest clip
     size_t out_rows = 0;        // head-less output rows: sum_b T_{b,0}
-    size_t off_attn = 0, off_lse = 0, off_tokens = 0, off_tab = 0, bytes = 0;
+    SavedLayout sl;             // the workspace (inference) / `saved` (training) of the call the plan was made for
     std::vector<int> tab;       // host copy of the batch table (empty in a capacity plan: the device builds it, ragged_table.hip)
     size_t tab_words = 0;       // ints of the device table
-    size_t off_efft = 0;        // capacity plan: the effective targets int64 (B) behind the table
     int tiles = 0;
     size_t seg_rows[FUSED_MAX_SEG] = {0, 0, 0, 0};    // training plan: sum_b T_{b,k}, the packed rows of segment k
 };
@@ -868,19 +887,9 @@ int ragged_config_ok(const egx_config* cfg, const egx_segment* segs, int B, cons
         EGX_CHECK(segs[k].proj_w && segs[k].d_in % 128 == 0, "ragged batch: segment %d needs a projection with d_in %% 128 == 0", k);
     return 0;
 }
-// the workspace view of a plan whose vp (B clips, vB tiles, N tokens) and tab_words are set
-void ragged_layout(const egx_config* cfg, const egx_segment* segs, RaggedPlan& rp) {
-    const Plan& vp = rp.vp;
-    const size_t d = vp.d;
-    rp.off_attn = align_up(fused_x1f_offset(cfg, segs, vp), 256);        // (the tiled launches write no x1f rows: fused_core_bytes with tpc > 1)
-    rp.off_lse = rp.off_attn + align_up((size_t)vp.L * vp.N * d * 4, 256);
-    rp.off_tokens = rp.off_lse + align_up((size_t)vp.L * vp.H * vp.N * 4, 256);
-    rp.off_tab = rp.off_tokens + align_up((vp.N + (size_t)vp.B) * d * 4, 256);
-    rp.bytes = rp.off_tab + align_up(rp.tab_words * sizeof(int), 256);
-}
 // train (egx_ragged_train_*): dropout (but FEAT) and the weighted cross entropy are allowed; the table gets the packed first row of every
-// clip's segments behind the tile map (FusedBwdParams::rseg)
-int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, RaggedPlan& rp, bool train = false) {
+// clip's segments behind the tile map (FusedBwdParams::rseg). saved: the call's block, null in a size query
+int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, const void* saved, RaggedPlan& rp, bool train = false) {
     Plan& vp = rp.vp;
     if (make_plan(cfg, segs, B, vp)) return 1;
     EGX_CHECK(lengths, "ragged batch: null lengths");
@@ -922,7 +931,7 @@ int ragged_plan(const egx_config* cfg, const egx_segment* segs, int B, const int
     vp.vB = tiles; vp.tpc = 0; vp.N = tok; vp.S = S_max;
     rp.out_rows = out;
     rp.tab_words = rp.tab.size();
-    ragged_layout(cfg, segs, rp);
+    rp.sl = saved_layout(cfg, segs, vp, true, saved, rp.tab_words);
     return 0;
 }
 // with a head the last layer leaves EVERY token of a clip (rows tok0 .. tok0 + S_b of the dense array); head-less its first segment, packed
@@ -934,11 +943,10 @@ void ragged_head_rows(RaggedPlan& rp, int B, bool with_head) {
     }
 }
 
-TiledView ragged_view(const RaggedPlan& rp, int B, const void* workspace, const int* tab, bool keys) {
+TiledView ragged_view(const RaggedPlan& rp, int B, const int* tab, bool keys) {
     TiledView v;
     memset(&v, 0, sizeof(v));
-    v.base = (char*)const_cast<void*>(workspace);
-    v.off_attn = rp.off_attn; v.off_lse = rp.off_lse; v.off_tokens = rp.off_tokens;
+    v.sl = &rp.sl;
     v.rtab = tab;
     v.B_clips = B; v.tpc = 0; v.S_clip = rp.vp.S; v.tiled = true;
     // every tile walks the FFN hidden blocks from block 0 (rot_mode 1, +2.5 % of the tiled launches' time against the staggered default):
@@ -948,29 +956,29 @@ TiledView ragged_view(const RaggedPlan& rp, int B, const void* workspace, const 
     return v;
 }
 
-// The forward of egx_ragged_fwd (`train` false) and egx_ragged_train_fwd (`train`) over the caller's plan (ragged_plan(..., train)) and its
-// workspace layout. Only the train call hands the kernels dropout keys, the device seed (and its advance) and runs the cross entropy; the
+// The forward of egx_ragged_fwd (`train` false) and egx_ragged_train_fwd (`train`) over the caller's plan (ragged_plan(..., train)) and the
+// workspace it was made for. Only the train call hands the kernels dropout keys, the device seed (and its advance) and runs the cross entropy; the
 // inference call's keys stay zero and its FFN keep-scale 1.
 int ragged_forward(const egx_config* cfg, const egx_segment* segs, RaggedPlan& rp, const float* ln_w, const float* ln_b, const egx_layer* layers,
-                   const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, bool train, int training, uint64_t seed,
+                   const egx_head* head, int B, float* logits_out, float* tokens_out, bool train, int training, uint64_t seed,
                    hipStream_t st, bool dev_table = false) {
     const Plan& vp = rp.vp;
     const bool with_head = head && head->W;
     // the batch table to the device, stream-ordered, in the arguments of upload launches (no host buffer has to outlive the call). Its
     // contents depend on the lengths of THIS call: a captured hipGraph would replay them for every batch, so the call is not for capture.
     // (dev_table: the capacity plan's table, already built in place by ragged_table_build on this stream.)
-    int* tab = (int*)((char*)workspace + rp.off_tab);
+    const SavedLayout& SL = rp.sl;
+    int* tab = (int*)SL.at(SL.tab);
     if (!dev_table) {
         ragged_head_rows(rp, B, with_head);
         if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
     }
-    const TiledView v = ragged_view(rp, B, workspace, tab, train);
-    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, workspace, vp));
+    const TiledView v = ragged_view(rp, B, tab, train);
     FusedFwdParams fp;
     PackParams pk;
-    fill_fwd(fp, pk, PL, v, cfg, segs, vp, ln_w, ln_b, layers, training, seed);     // (the clip's own segment pieces come from the batch table)
+    fill_fwd(fp, pk, v, cfg, segs, vp, ln_w, ln_b, layers, training, seed);     // (the clip's own segment pieces come from the batch table)
     // with a head: every token of the last layer (N, d) in the workspace, then the token means (B, d)
-    fp.tokens_out = with_head ? (float*)(v.base + v.off_tokens) : tokens_out;
+    fp.tokens_out = with_head ? (float*)SL.at(SL.tokens) : tokens_out;
     if (pack_weights(pk, st)) return 1;
     return tiled_forward(fp, v, cfg, vp, head, logits_out, st);     // (the inference plan refuses egx_config.ce)
 }
@@ -980,20 +988,20 @@ extern "C" {
 
 int egx_ragged_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* bytes) {
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
-    if (bytes) *bytes = rp.bytes;
+    if (ragged_plan(cfg, segs, B, lengths, nullptr, rp)) return 1;
+    if (bytes) *bytes = rp.sl.bytes;
     return 0;
 }
 
 int egx_ragged_fwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
                    const egx_layer* layers, const egx_head* head, int B, float* logits_out, float* tokens_out, void* workspace, void* stream) {
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, workspace, rp)) return 1;
     EGX_CHECK(workspace && ln_w && ln_b && layers, "ragged batch: null pointer argument");
     const bool with_head = head && head->W;
     EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged batch: null output pointer");
     if (check_head(head)) return 1;
-    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, workspace, false, 0, 0, (hipStream_t)stream);
+    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, false, 0, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1031,7 +1039,7 @@ RaggedTrainScratch ragged_train_scratch(const egx_config* cfg, const egx_segment
 }
 int ragged_backward(const egx_config* cfg, const egx_segment* segs, const RaggedPlan& rp, const RaggedTrainScratch& RS, const int* tab,
                     const int* rseg, const int* cap_meta, const float* ln_w, const float* ln_b, const egx_layer* layers, const egx_head* head, int B,
-                    const float* d_logits, const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                    const float* d_logits, const float* d_tokens, void* scratch, const egx_segment_grads* seg_grads,
                     float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, int training,
                     uint64_t seed, hipStream_t st);
 }  // namespace
@@ -1041,8 +1049,8 @@ extern "C" {
 int egx_ragged_train_workspace(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, size_t* saved_bytes,
                                size_t* scratch_bytes) {
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
-    if (saved_bytes) *saved_bytes = rp.bytes;
+    if (ragged_plan(cfg, segs, B, lengths, nullptr, rp, true)) return 1;
+    if (saved_bytes) *saved_bytes = rp.sl.bytes;
     if (scratch_bytes) *scratch_bytes = ragged_train_scratch(cfg, segs, rp, FUSED_HEAD_MAX_OUT).bytes;
     return 0;
 }
@@ -1052,12 +1060,12 @@ int egx_ragged_train_fwd(const egx_config* cfg, const egx_segment* segs, const i
                          void* scratch, int training, uint64_t seed, void* stream) {
     (void)scratch;
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, saved, rp, true)) return 1;
     EGX_CHECK(saved && ln_w && ln_b && layers, "ragged training: null pointer argument");
     const bool with_head = head && head->W;
     EGX_CHECK(with_head ? logits_out != nullptr : tokens_out != nullptr, "ragged training: null output pointer");
     if (check_head(head) || check_ce(cfg->ce, with_head, "")) return 1;
-    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, saved, true, training, seed, (hipStream_t)stream);
+    return ragged_forward(cfg, segs, rp, ln_w, ln_b, layers, head, B, logits_out, tokens_out, true, training, seed, (hipStream_t)stream);
 }
 
 int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* lengths, const float* ln_w, const float* ln_b,
@@ -1065,7 +1073,7 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
                    void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads,
                    const egx_head_grads* head_grads, int training, uint64_t seed, void* stream) {
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, saved, rp, true)) return 1;
     const bool with_head = head && head->W;
     EGX_CHECK((with_head ? (const void*)d_logits : (const void*)d_tokens) && saved && scratch && ln_w && ln_b && layers && layer_grads,
               "ragged training: null pointer argument");
@@ -1077,7 +1085,7 @@ int egx_ragged_bwd(const egx_config* cfg, const egx_segment* segs, const int* le
     int* tab = (int*)((char*)scratch + RS.tab);
     if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
     return ragged_backward(cfg, segs, rp, RS, tab, tab + (size_t)B * RAGGED_REC + rp.tiles, nullptr, ln_w, ln_b, layers, head, B, d_logits, d_tokens,
-                           saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
+                           scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
 }
 
 }  // extern "C"
@@ -1087,7 +1095,7 @@ namespace {
 // plan: the totals of the device-built table): every size below is the CAPACITY's, and the rows no clip of this batch owns are cleared first.
 int ragged_backward(const egx_config* cfg, const egx_segment* segs, const RaggedPlan& rp, const RaggedTrainScratch& RS, const int* tab,
                     const int* rseg, const int* cap_meta, const float* ln_w, const float* ln_b, const egx_layer* layers, const egx_head* head, int B,
-                    const float* d_logits, const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads,
+                    const float* d_logits, const float* d_tokens, void* scratch, const egx_segment_grads* seg_grads,
                     float* d_ln_w, float* d_ln_b, const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, int training,
                     uint64_t seed, hipStream_t st) {
     const Plan& vp = rp.vp;
@@ -1096,10 +1104,10 @@ int ragged_backward(const egx_config* cfg, const egx_segment* segs, const Ragged
     bool want_pos = false;
     for (int i = 0; i < vp.nseg && seg_grads; ++i) want_pos = want_pos || seg_grads[i].pos;
     EGX_CHECK(!want_pos, "ragged training: learned positional tables (egx_segment_grads.pos) are not supported");
-    const TiledView v = ragged_view(rp, B, saved, tab, true);
-    FusedPackLayout PL = fused_pack_layout(cfg, segs, vp, fused_pack_base(cfg, saved, vp));
+    const SavedLayout& SL = rp.sl;
+    const TiledView v = ragged_view(rp, B, tab, true);
     FusedBwdParams bp;
-    if (fill_bwd(bp, PL, SC, v, cfg, segs, vp, ln_w, ln_b, layers, head, d_logits, d_tokens, scratch, training, seed)) return 1;
+    if (fill_bwd(bp, SC, v, cfg, segs, vp, ln_w, ln_b, layers, head, d_logits, d_tokens, scratch, training, seed)) return 1;
     bp.rseg = rseg;
     const float* featp[FUSED_MAX_SEG];
     for (int i = 0; i < vp.nseg; ++i) featp[i] = fptr(scratch, RS.featp[i]);
@@ -1113,18 +1121,15 @@ int ragged_backward(const egx_config* cfg, const egx_segment* segs, const Ragged
         RaggedSlackParams sl;
         memset(&sl, 0, sizeof(sl));
         sl.meta = cap_meta;
-        const bool bf = comp == EGX_BF16;
-        const int parts = bf ? 1 : 3;
+        const int parts = comp == EGX_BF16 ? 1 : 3;
         const size_t tile_rows = (size_t)FUSED_TOK_PAD * d * 2, plane = (size_t)vp.vB * tile_rows;      // a tile / all tiles of one bf16 plane
-        const size_t hid_tile = fused_hid_bytes(1, vp.dff, bf), row = (size_t)d * 4;
-        char* sv = (char*)const_cast<void*>(saved);
+        const size_t hid_tile = SL.hid_layer / vp.vB, row = (size_t)d * 4;
         int rc = 0;
         for (int l = 0; l < L; ++l) {
-            const size_t lo = (size_t)l * fused_hid_bytes(vp.vB, vp.dff, bf);
-            rc |= ragged_slack_add(sl, sv + fused_hid_offset(cfg, segs, vp) + lo, hid_tile, vp.vB, RS_TILES);
-            rc |= ragged_slack_add(sl, (char*)scratch + SC.dhid + lo, hid_tile, vp.vB, RS_TILES);
+            rc |= ragged_slack_add(sl, SL.at(SL.hid + l * SL.hid_layer), hid_tile, vp.vB, RS_TILES);
+            rc |= ragged_slack_add(sl, (char*)scratch + SC.dhid + l * SL.hid_layer, hid_tile, vp.vB, RS_TILES);
             for (int j = 0; j < parts; ++j) {
-                rc |= ragged_slack_add(sl, sv + fused_x1p_offset(cfg, segs, vp) + ((size_t)l * parts + j) * plane, tile_rows, vp.vB, RS_TILES);
+                rc |= ragged_slack_add(sl, SL.at(SL.x1p + l * SL.x1p_layer + j * plane), tile_rows, vp.vB, RS_TILES);
                 rc |= ragged_slack_add(sl, (char*)bp.layer[l].g2_out + j * plane, tile_rows, vp.vB, RS_TILES);
             }
             rc |= ragged_slack_add(sl, bp.layer[l].g1_out, row, vp.N, RS_TOKENS);
@@ -1148,7 +1153,7 @@ int ragged_backward(const egx_config* cfg, const egx_segment* segs, const Ragged
     SlabReduce red;
     red.narr = 0; red.nslab = 0;
     for (int l = 0; l < L; ++l)
-        if (launch_ffn_dw(l, bp, PL, SC, v, cfg, segs, vp, layers, layer_grads, scratch, red, st)) return 1;
+        if (launch_ffn_dw(l, bp, SC, v, cfg, vp, layers, layer_grads, scratch, red, st)) return 1;
     // the projection-weight gradients read the valid feature frames only: gathered into packed rows that match the packed d(seg) rows
     for (int i = 0; i < vp.nseg && seg_grads; ++i)
         if (seg_grads[i].proj_w && ragged_rows(const_cast<float*>(segs[i].feat), fptr(scratch, RS.featp[i]), tab, rseg, B, segs[i].T, segs[i].d_in, i, 1, st))
@@ -1174,7 +1179,7 @@ int ragged_backward(const egx_config* cfg, const egx_segment* segs, const Ragged
 // batch that fits and leaves at least (tok_cap - N) / 48 surplus tiles); packed segment rows at min(tok_cap, B_cap T_k). Nothing here reads
 // a length: the table is built on the device (ragged_table.hip), stream-ordered, in front of each call's launches.
 constexpr int RAGGED_CAP_MAX_TOKENS = 1 << 24;
-int ragged_cap_plan(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, RaggedPlan& rp) {
+int ragged_cap_plan(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, const void* saved, RaggedPlan& rp) {
     EGX_CHECK(cfg && segs, "ragged capacity: null pointer argument");
     EGX_CHECK(B_cap >= 1 && tok_cap >= 1, "ragged capacity: B_cap=%d clips and tok_cap=%d tokens must be at least 1", B_cap, tok_cap);
     Plan& vp = rp.vp;
@@ -1193,9 +1198,7 @@ int ragged_cap_plan(const egx_config* cfg, const egx_segment* segs, int B_cap, i
     rp.tiles = cdiv(tok_cap, FUSED_TOK_PAD) + B_cap;
     vp.vB = rp.tiles; vp.tpc = 0; vp.N = (size_t)tok_cap; vp.S = S_longest < TILED_MAX_S ? S_longest : TILED_MAX_S;
     rp.tab_words = ragged_cap_table_words(B_cap, rp.tiles);
-    ragged_layout(cfg, segs, rp);
-    rp.off_efft = rp.bytes;
-    rp.bytes += align_up((size_t)B_cap * sizeof(int64_t), 256);
+    rp.sl = saved_layout(cfg, segs, vp, true, saved, rp.tab_words, (size_t)B_cap);
     return 0;
 }
 // what the two capacity calls refuse alike
@@ -1227,7 +1230,7 @@ extern "C" {
 int egx_ragged_table_host(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int train, int* out_words, size_t* n_words) {
     EGX_CHECK(cfg && segs && n_words, "ragged table: null pointer argument");
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, train != 0)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, nullptr, rp, train != 0)) return 1;
     ragged_head_rows(rp, B, true);
     *n_words = rp.tab.size();
     if (out_words) memcpy(out_words, rp.tab.data(), rp.tab.size() * sizeof(int));
@@ -1236,8 +1239,8 @@ int egx_ragged_table_host(const egx_config* cfg, const egx_segment* segs, int B,
 
 int egx_ragged_cap_workspace(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, size_t* saved_bytes, size_t* scratch_bytes) {
     RaggedPlan rp;
-    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
-    if (saved_bytes) *saved_bytes = rp.bytes;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, nullptr, rp)) return 1;
+    if (saved_bytes) *saved_bytes = rp.sl.bytes;
     if (scratch_bytes) *scratch_bytes = ragged_train_scratch(cfg, segs, rp, FUSED_HEAD_MAX_OUT).bytes;
     return 0;
 }
@@ -1245,7 +1248,7 @@ int egx_ragged_cap_workspace(const egx_config* cfg, const egx_segment* segs, int
 int egx_ragged_cap_table(const egx_config* cfg, const egx_segment* segs, int B_cap, int tok_cap, const int* lengths, const int64_t* target,
                          int* table, int64_t* eff_target, unsigned* status, size_t* n_words, void* stream) {
     RaggedPlan rp;
-    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, nullptr, rp)) return 1;
     if (n_words) *n_words = rp.tab_words;
     if (!table) return 0;       // (the size query)
     EGX_CHECK(lengths, "ragged capacity: null pointer argument");
@@ -1257,20 +1260,20 @@ int egx_ragged_cap_train_fwd(const egx_config* cfg, const egx_segment* segs, con
                              void* saved, void* scratch, unsigned* status, int training, uint64_t seed, void* stream) {
     (void)scratch; (void)tokens_out;
     RaggedPlan rp;
-    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, saved, rp)) return 1;
     hipStream_t st = (hipStream_t)stream;
     if (ragged_cap_checks(cfg, head, training, st)) return 1;
     EGX_CHECK(lengths && saved && ln_w && ln_b && layers && logits_out && status, "ragged capacity: null pointer argument");
-    int* tab = (int*)((char*)saved + rp.off_tab);
+    int* tab = (int*)rp.sl.at(rp.sl.tab);
     const int* meta = tab + rp.tab_words - RAGGED_META;
-    int64_t* efft = (int64_t*)((char*)saved + rp.off_efft);
+    int64_t* efft = (int64_t*)rp.sl.at(rp.sl.efft);
     const egx_ce* ce = cfg->ce;
     if (ragged_table_build(ragged_cap_table_params(segs, rp, tok_cap, lengths, ce ? ce->target : nullptr, efft, tab, status), st)) return 1;
     // the cross entropy reads the EFFECTIVE targets: an empty clip (and every clip of a refused batch) is -1 there, whatever the caller left
     egx_config c2 = *cfg;
     egx_ce ce2;
     if (ce) { ce2 = *ce; ce2.target = efft; c2.ce = &ce2; }
-    if (ragged_forward(&c2, segs, rp, ln_w, ln_b, layers, head, B_cap, logits_out, nullptr, saved, true, training, seed, st, true)) return 1;
+    if (ragged_forward(&c2, segs, rp, ln_w, ln_b, layers, head, B_cap, logits_out, nullptr, true, training, seed, st, true)) return 1;
     return ce ? ragged_empty_loss(meta, ce->loss, st) : 0;
 }
 
@@ -1280,7 +1283,7 @@ int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int
                        const egx_layer_grads* layer_grads, const egx_head_grads* head_grads, unsigned* status, int training, uint64_t seed,
                        void* stream) {
     RaggedPlan rp;
-    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, rp)) return 1;
+    if (ragged_cap_plan(cfg, segs, B_cap, tok_cap, saved, rp)) return 1;
     hipStream_t st = (hipStream_t)stream;
     if (ragged_cap_checks(cfg, head, training, st)) return 1;
     EGX_CHECK(lengths && d_logits && saved && scratch && ln_w && ln_b && layers && layer_grads && status, "ragged capacity: null pointer argument");
@@ -1290,13 +1293,13 @@ int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int
     if (ragged_table_build(ragged_cap_table_params(segs, rp, tok_cap, lengths, nullptr, nullptr, tab, status), st)) return 1;
     const int* rseg = tab + (size_t)B_cap * RAGGED_REC + rp.tiles;
     return ragged_backward(cfg, segs, rp, RS, tab, rseg, rseg + (size_t)B_cap * FUSED_MAX_SEG, ln_w, ln_b, layers, head, B_cap, d_logits, d_tokens,
-                           saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
+                           scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, head_grads, training, seed, st);
 }
 
 }  // extern "C"
 
 // ---- stage read (ABI v26, test hooks): the intermediates a d = 128 call leaves in `saved` and in the backward's scratch ---------------------
-// Read-only: where an item lives comes from the offset functions and the scratch plans the launches above use; stage_read.hip turns it into a
+// Read-only: where an item lives comes from the SavedLayout and the scratch plans the launches above use; stage_read.hip turns it into a
 // dense matrix in token order. An item the chosen implementation does not hold when its call returns is EGX_STAGE_NOT_KEPT, never a stale read:
 //   forward (in `saved` from the forward on, every d = 128 mode): PRE, XIN, QKV, RES1, RES2, HID, ALIVE, and X1 as the bf16 plane(s) the FFN
 //     loop multiplied (bf16: one plane, f32s: three, summed exactly); exact-fp32 calls: X1 and G2 are not served (NOT_KEPT);
@@ -1306,11 +1309,11 @@ int egx_ragged_cap_bwd(const egx_config* cfg, const egx_segment* segs, const int
 //   the hook is not told) is UNSUPPORTED: it answers NOT_KEPT whatever the call did.
 namespace {
 struct StageWhere { bool in_scratch; size_t off; StageReadParams sr; int kind; };
-int stage_locate(const egx_config* cfg, const egx_segment* segs, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
+int stage_locate(const egx_config* cfg, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
                  int item, int layer, StageWhere& w) {
     memset(&w, 0, sizeof(w));
-    const int comp = cfg->compute;
-    const bool bf = comp == EGX_BF16, planes = split_planes(cfg);
+    const SavedLayout& SL = *v.sl;
+    const bool bf = cfg->compute == EGX_BF16, planes = split_planes(cfg);
     const size_t N = vp.N, d = vp.d, nd = N * d * 4;
     StageReadParams& sr = w.sr;
     sr.out_bytes = 4; sr.rows = (int)N; sr.cols = (int)d; sr.layout = SR_DENSE;
@@ -1326,24 +1329,24 @@ int stage_locate(const egx_config* cfg, const egx_segment* segs, const Plan& vp,
         if (bf) w.kind = EGX_STAGE_KIND_BF16;
     };
     switch (item) {
-    case EGX_STAGE_PRE: w.off = 0; break;
-    case EGX_STAGE_RES1: w.off = fused_res_index(vp, layer, 0) * 4; break;
-    case EGX_STAGE_RES2: w.off = fused_res_index(vp, layer, 1) * 4; break;
-    case EGX_STAGE_XIN: w.off = fused_xin_offset(cfg, segs, vp) + layer * nd; break;
-    case EGX_STAGE_QKV: sr.layout = SR_GRID; sr.cols = 3 * (int)d; w.off = fused_qkv_offset(cfg, segs, vp) + (size_t)layer * grid * 3 * d * 4; break;
+    case EGX_STAGE_PRE: w.off = SL.res; break;
+    case EGX_STAGE_RES1: w.off = SL.res + SL.res_index(layer, 0) * 4; break;
+    case EGX_STAGE_RES2: w.off = SL.res + SL.res_index(layer, 1) * 4; break;
+    case EGX_STAGE_XIN: w.off = SL.xin + layer * nd; break;
+    case EGX_STAGE_QKV: sr.layout = SR_GRID; sr.cols = 3 * (int)d; w.off = SL.qkv + layer * SL.qkv_layer; break;
     case EGX_STAGE_X1:
         if (!planes) return EGX_STAGE_NOT_KEPT;         // exact fp32: dense rows in the backward's scratch, not served (no test reads them)
-        operand_planes(fused_x1p_offset(cfg, segs, vp) + (size_t)layer * grid * d * plane_elem_bytes(cfg));
+        operand_planes(SL.x1p + layer * SL.x1p_layer);
         break;
     case EGX_STAGE_HID: case EGX_STAGE_DHID:
         sr.layout = SR_HID; sr.cols = vp.dff; sr.bf16 = bf;
         if (bf) w.kind = EGX_STAGE_KIND_BF16;
         w.in_scratch = item == EGX_STAGE_DHID;
-        w.off = (w.in_scratch ? SC.dhid : fused_hid_offset(cfg, segs, vp)) + (size_t)layer * fused_hid_bytes(vp.vB, vp.dff, bf);
+        w.off = (w.in_scratch ? SC.dhid : SL.hid) + layer * SL.hid_layer;
         break;
     case EGX_STAGE_ALIVE:
         sr.layout = SR_ALIVE; sr.cols = vp.dff; sr.out_bytes = 1; w.kind = EGX_STAGE_KIND_BIT;
-        w.off = fused_res_bytes(vp) + (size_t)layer * fused_mask_layer_words(vp) * 4;
+        w.off = SL.relu_bits + layer * SL.relu_layer_words * 4;
         break;
     case EGX_STAGE_G2:
         if (!planes) return EGX_STAGE_NOT_KEPT;         // (as X1)
@@ -1353,31 +1356,30 @@ int stage_locate(const egx_config* cfg, const egx_segment* segs, const Plan& vp,
     case EGX_STAGE_G1: w.in_scratch = true; w.off = SC.g1[layer]; break;
     case EGX_STAGE_DQKV: w.in_scratch = true; sr.cols = 3 * (int)d; w.off = SC.dqkv[layer]; break;
     case EGX_STAGE_ATTN_O:
-        if (v.tiled) w.off = v.off_attn + layer * nd;
+        if (v.tiled) w.off = SL.attn + layer * nd;
         else { w.in_scratch = true; w.off = SC.attn_o[layer]; }
         break;
     case EGX_STAGE_DSEG: w.in_scratch = true; sr.rows = (int)seg_rows[layer]; w.off = SC.dseg[layer]; break;
     case EGX_STAGE_LSE:         // (clip, head, token of the clip); a ragged clip's rows start at 4 tok0
         if (!v.tiled) return EGX_STAGE_NOT_KEPT;
-        sr.rows = (int)tiled_lse_layer_floats(vp); sr.cols = 1; w.off = v.off_lse + (size_t)layer * tiled_lse_layer_floats(vp) * 4;
+        sr.rows = (int)SL.lse_layer_floats; sr.cols = 1; w.off = SL.lse + layer * SL.lse_layer_floats * 4;
         break;
     default: return EGX_STAGE_NOT_KEPT;      // EGX_STAGE_DX0: unsupported (the hook is not told whether a position gradient was requested)
     }
     return 0;
 }
-int stage_run(const egx_config* cfg, const egx_segment* segs, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
-              size_t saved_bytes, size_t scratch_bytes, const void* saved, const void* scratch, int item, int layer, int* rows, int* cols, int* kind,
-              void* out, hipStream_t st) {
+int stage_run(const egx_config* cfg, const Plan& vp, const TiledView& v, const FusedBwdScratch& SC, const size_t* seg_rows,
+              const void* scratch, int item, int layer, int* rows, int* cols, int* kind, void* out, hipStream_t st) {
     StageWhere w;
-    const int rc = stage_locate(cfg, segs, vp, v, SC, seg_rows, item, layer, w);
+    const int rc = stage_locate(cfg, vp, v, SC, seg_rows, item, layer, w);
     if (rc) return rc;
     if (rows) *rows = w.sr.rows;
     if (cols) *cols = w.sr.cols;
     if (kind) *kind = w.kind;
     if (!out) return 0;         // (the shape query)
-    const void* base = w.in_scratch ? scratch : saved;
+    const void* base = w.in_scratch ? scratch : v.sl->base;
     EGX_CHECK(base, "stage read: the item lives in `%s`, which is null", w.in_scratch ? "scratch" : "saved");
-    EGX_CHECK(w.off < (w.in_scratch ? scratch_bytes : saved_bytes), "stage read: offset beyond the workspace");
+    EGX_CHECK(w.off < (w.in_scratch ? SC.bytes : v.sl->bytes), "stage read: offset beyond the workspace");
     w.sr.src = (const char*)base + w.off;
     w.sr.out = out;
     return stage_read(w.sr, st);
@@ -1392,27 +1394,26 @@ int stage_uniform(const egx_config* cfg, const egx_segment* segs, int B, int hea
     if (impl < 0) return 1;
     if (impl != EGX_IMPL_FUSED && impl != EGX_IMPL_TILED) return EGX_STAGE_NOT_KEPT;       // the generic and the wide kernels have workspaces of their own
     const bool tiled = impl == EGX_IMPL_TILED;
-    Plan vp = pl;
-    if (tiled) plan_tiled(vp);
-    const TiledView v = uniform_view(cfg, segs, vp, saved, tiled);
+    const Plan vp = tiled ? plan_tiled(pl) : pl;
+    const SavedLayout SL = saved_layout(cfg, segs, vp, tiled, saved);
+    const TiledView v = uniform_view(vp, SL, tiled);
     const FusedBwdScratch SC = fused_bwd_scratch(cfg, segs, vp, head_n_out);
     size_t seg_rows[EGX_MAX_SEGMENTS];
     for (int i = 0; i < pl.nseg; ++i) seg_rows[i] = (size_t)B * segs[i].T;
-    return stage_run(cfg, segs, vp, v, SC, seg_rows, tiled ? tiled_saved_bytes(cfg, segs, vp) : fused_saved_bytes(cfg, segs, vp), SC.bytes, saved, scratch,
-                     item, layer, rows, cols, kind, out, (hipStream_t)stream);
+    return stage_run(cfg, vp, v, SC, seg_rows, scratch, item, layer, rows, cols, kind, out, (hipStream_t)stream);
 }
 int stage_ragged(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, int head_n_out, const void* saved, const void* scratch,
                  int item, int layer, int* rows, int* cols, int* kind, void* out, void* stream) {
     EGX_CHECK(cfg && segs, "stage read: null config / segments");
     EGX_CHECK(head_n_out >= 0 && head_n_out <= FUSED_HEAD_MAX_OUT, "stage read: head_n_out=%d (0 .. %d)", head_n_out, FUSED_HEAD_MAX_OUT);
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, saved, rp, true)) return 1;
     const RaggedTrainScratch RS = ragged_train_scratch(cfg, segs, rp, head_n_out);
     // the forward's copy of the batch table (in `saved`): tile0, tok0 and S of every clip are the same with and without a head
-    const int* tab = saved ? (const int*)((const char*)saved + rp.off_tab) : nullptr;
+    const int* tab = saved ? (const int*)rp.sl.at(rp.sl.tab) : nullptr;
     EGX_CHECK(!out || tab, "stage read: the ragged batch table lives in `saved`, which is null");
-    const TiledView v = ragged_view(rp, B, saved, tab, true);
-    return stage_run(cfg, segs, rp.vp, v, RS.sc, rp.seg_rows, rp.bytes, RS.sc.bytes, saved, scratch, item, layer, rows, cols, kind, out, (hipStream_t)stream);
+    const TiledView v = ragged_view(rp, B, tab, true);
+    return stage_run(cfg, rp.vp, v, RS.sc, rp.seg_rows, scratch, item, layer, rows, cols, kind, out, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -1439,7 +1440,7 @@ int egx_ragged_stage_read(const egx_config* cfg, const egx_segment* segs, int B,
 }  // extern "C"
 
 // ---- the self-attention weights of a d = 128 call (ABI v27, egx_encoder_self_weights) -------------------------------------------------------
-// Every d = 128 forward keeps each layer's fp32 Q | K | V rows on the 48-row tile grid at fused_qkv_offset (what EGX_STAGE_QKV reads): clip c
+// Every d = 128 forward keeps each layer's fp32 Q | K | V rows on the 48-row tile grid in SavedLayout::qkv (what EGX_STAGE_QKV reads): clip c
 // of a uniform call starts at row c * tpc * 48, a ragged clip at 48 x the first tile of its batch-table record, which enc_self_weights_kernel
 // reads in place (first tile, S_b and the segments' frame counts), so nothing is built or uploaded here.
 namespace egx {
@@ -1449,28 +1450,27 @@ static void self_weights_common(SelfWParams& p, const Plan& vp, float* w_out, fl
 }
 int fused_self_weights(const egx_config* cfg, const egx_segment* segs, const Plan& pl, bool tiled, const void* saved, uint64_t layer_mask,
                        float* w_out, float* seg_out, hipStream_t st) {
-    Plan vp = pl;
-    if (tiled) plan_tiled(vp);
+    const Plan vp = tiled ? plan_tiled(pl) : pl;
     SelfWParams p;
     self_weights_common(p, vp, w_out, seg_out, pl.B, pl.S);
     p.clip_rows = (long long)vp.tpc * FUSED_TOK_PAD;
     p.fixed_segs = 1;
     for (int i = 0; i < vp.nseg; ++i) p.seg_fixed[i] = segs[i].T;
-    const size_t grid = (size_t)vp.vB * FUSED_TOK_PAD;
-    return self_weights_layers(p, (const char*)saved + fused_qkv_offset(cfg, segs, vp), grid * 3 * vp.d * 4, vp.d, vp.L, layer_mask, true, st);
+    const SavedLayout SL = saved_layout(cfg, segs, vp, tiled, saved);
+    return self_weights_layers(p, SL.at(SL.qkv), SL.qkv_layer, vp.d, vp.L, layer_mask, true, st);
 }
 int ragged_self_weights(const egx_config* cfg, const egx_segment* segs, int B, const int* lengths, const void* saved, uint64_t layer_mask,
                         float* w_out, float* seg_out, hipStream_t st) {
     RaggedPlan rp;
-    if (ragged_plan(cfg, segs, B, lengths, rp, true)) return 1;
+    if (ragged_plan(cfg, segs, B, lengths, saved, rp, true)) return 1;
     const Plan& vp = rp.vp;
-    const int* tab = (const int*)((const char*)saved + rp.off_tab);     // the forward's device copy of the batch table
+    const SavedLayout& SL = rp.sl;
+    const int* tab = (const int*)SL.at(SL.tab);     // the forward's device copy of the batch table
     SelfWParams p;
     self_weights_common(p, vp, w_out, seg_out, B, vp.S);
     p.rowtab = tab; p.tab_stride = RAGGED_REC; p.row_mul = FUSED_TOK_PAD;       // record: RG_TILE0, RG_S
     p.segtab = tab + RG_T; p.seg_stride = RAGGED_REC;
     static_assert(RG_TILE0 == 0 && RG_S == 1, "enc_self_weights_kernel reads (first tile, S_b) at the head of a record");
-    const size_t grid = (size_t)vp.vB * FUSED_TOK_PAD;
-    return self_weights_layers(p, (const char*)saved + fused_qkv_offset(cfg, segs, vp), grid * 3 * vp.d * 4, vp.d, vp.L, layer_mask, true, st);
+    return self_weights_layers(p, SL.at(SL.qkv), SL.qkv_layer, vp.d, vp.L, layer_mask, true, st);
 }
 }  // namespace egx

@@ -52,6 +52,25 @@ def test_host_entry_points_sweep(egx_lib):
     assert host_paths.exercise(host_paths.bind(_lib.LIB_PATH)) > 10000
 
 
+def test_d128_workspace_sizes_match_the_committed_table(egx_lib):
+    """The `saved` / scratch / weight-cache / ragged workspace sizes of the d = 128 paths, at the smallest shape of every branch of
+    fused_host.hip's SavedLayout (tests/host_paths_d128_sizes.py), equal tests/d128_workspace_sizes.json, which was written from a build of
+    the commit its first key names: a refactor of the layout code must leave every size alone."""
+    import json
+    from egot2_amd import _lib
+    from tests import host_paths, host_paths_d128_sizes
+    table = json.load(open(os.path.join(ROOT, "tests", "d128_workspace_sizes.json")))
+    assert list(table)[0] == "generated_from" and table["generated_from"]
+    got = host_paths_d128_sizes.sizes(host_paths.bind(_lib.LIB_PATH))
+    want = table["sizes"]
+    assert len(want) >= 200 and set(got) == set(want), sorted(set(got) ^ set(want))
+    assert any(v[0] == 0 and v[1] > 0 for k, v in want.items() if k.endswith("ragged_cap")), "the table holds no accepted capacity plan"
+    changed = {k: (want[k], got[k]) for k in want if got[k] != want[k]}
+    assert not changed, (f"{len(changed)} d = 128 workspace sizes differ from tests/d128_workspace_sizes.json (table, library): {sorted(changed.items())[:8]}. "
+                         "A changed size is an intended layout change only if the table is regenerated in the same commit "
+                         "(python tests/host_paths_d128_sizes.py <lib.so> <commit>); a refactor changes none")
+
+
 def test_host_code_under_address_and_ub_sanitizers():
     """SURVEY.md §5 / VERDICT r4 item 9d: the same sweep against a build whose C++ orchestration (encoder.hip, fused_host.hip,
     wide_host.hip, wide_decoder.hip, comm.hip) is compiled with AddressSanitizer + UBSan on the HOST side (egot2_amd/build.py build_sanitized;
