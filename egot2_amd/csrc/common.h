@@ -57,6 +57,14 @@ const Tuning& tuning();
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// NOT ::max: in hipcc host code the unqualified call resolves to max(int, int) and truncates sizes above 2 GiB
+static inline size_t size_max(size_t a, size_t b) { return a > b ? a : b; }
+// workspace layouts: the offset of the next `bytes` behind `cur`, every buffer on a 256-byte boundary
+static inline size_t take(size_t& cur, size_t bytes) {
+    size_t o = cur;
+    cur = align_up(cur + bytes, 256);
+    return o;
+}
 
 // fp32 -> bf16 round-to-nearest-even (plain cast keeps NaNs, v_cvt_pk_bf16_f32 on gfx950).
 __device__ __forceinline__ unsigned short f2bf(float x) {

@@ -23,13 +23,6 @@ struct Plan {
 };
 int make_plan(const egx_config* cfg, const egx_segment* segs, int B, Plan& pl);
 
-// NOT ::max: in hipcc host code the unqualified call resolves to max(int, int) and truncates sizes above 2 GiB
-static inline size_t size_max(size_t a, size_t b) { return a > b ? a : b; }
-static inline size_t take(size_t& cur, size_t bytes) {
-    size_t o = cur;
-    cur = align_up(cur + bytes, 256);
-    return o;
-}
 static inline float* fptr(void* base, size_t off) { return (float*)((char*)base + off); }
 static inline const float* cfptr(const void* base, size_t off) { return (const float*)((const char*)base + off); }
 

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "wide.h"
+#include "wide_run.h"
 #include "fused.h"      // (upload_words: the ragged batch table)
 
 namespace egx {
@@ -608,8 +609,9 @@ __global__ __launch_bounds__(1024) void dec_embed_grad_small_kernel(const int64_
         }
 }
 
+struct DecW { size_t sa_in, sa_o, q, kv, ca_o, w1, w2; };      // a layer's bf16 weights (ca_in_w as its q and k | v rows)
 struct DLayer {
-    size_t w_sa_in, w_sa_in_t, w_sa_o, w_sa_o_t, w_q, w_q_t, w_kv, w_kv_t, w_ca_o, w_ca_o_t, w1, w1_t, w2, w2_t;   // bf16 weights
+    DecW w, wt;                                                 // W and W^T
     size_t x32, x16, qkv, sa, res1, st1, x1_32, x1_16, q, kv, ca, res2, st2, x2_32, x2_16, hid, res3, st3;
 };
 struct DPlan {
@@ -623,10 +625,6 @@ struct DPlan {
     // chain (decoder_bwd), so the chain must not overwrite an operand while its weight gradient may still be reading it
     struct { size_t dy16[3], dhid16, dqkv16, dq16, dkv16; } g[16];
 };
-size_t dtake(size_t& cur, size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
-size_t dmax(size_t a, size_t b) { return a > b ? a : b; }
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>((char*)base + off); }
-template <class T> const T* cat(const void* base, size_t off) { return reinterpret_cast<const T*>((const char*)base + off); }
 
 // mem_rows > 0 (ragged memories): the memory is that many packed rows instead of B * S
 int make_dplan(const egx_dec_config* c, int B, DPlan& pl, size_t mem_rows = 0) {
@@ -644,77 +642,59 @@ int make_dplan(const egx_dec_config* c, int B, DPlan& pl, size_t mem_rows = 0) {
     pl.Md = (size_t)B * c->sy; pl.Nm = mem_rows ? mem_rows : (size_t)B * c->S;
     const size_t d = pl.d, dff = pl.dff, Md = pl.Md, Nm = pl.Nm;
     size_t cur = 0;
-    pl.zero = dtake(cur, 1024);
-    pl.keys = dtake(cur, (size_t)16 * DROP_KEY_SLOTS * sizeof(uint64_t));
-    pl.mem16 = dtake(cur, Nm * d * 2);
+    pl.zero = take(cur, 1024);
+    pl.keys = take(cur, (size_t)16 * DROP_KEY_SLOTS * sizeof(uint64_t));
+    pl.mem16 = take(cur, Nm * d * 2);
     for (int l = 0; l < pl.L; ++l) {
         DLayer& o = pl.layer[l];
-        o.w_sa_in = dtake(cur, 3 * d * d * 2); o.w_sa_in_t = dtake(cur, 3 * d * d * 2);
-        o.w_sa_o = dtake(cur, d * d * 2); o.w_sa_o_t = dtake(cur, d * d * 2);
-        o.w_q = dtake(cur, d * d * 2); o.w_q_t = dtake(cur, d * d * 2);
-        o.w_kv = dtake(cur, 2 * d * d * 2); o.w_kv_t = dtake(cur, 2 * d * d * 2);
-        o.w_ca_o = dtake(cur, d * d * 2); o.w_ca_o_t = dtake(cur, d * d * 2);
-        o.w1 = dtake(cur, dff * d * 2); o.w1_t = dtake(cur, dff * d * 2);
-        o.w2 = dtake(cur, dff * d * 2); o.w2_t = dtake(cur, dff * d * 2);
-        o.x32 = dtake(cur, Md * d * 4); o.x16 = dtake(cur, Md * d * 2);
-        o.qkv = dtake(cur, Md * 3 * d * 2); o.sa = dtake(cur, Md * d * 2);
-        o.res1 = dtake(cur, Md * d * 4); o.st1 = dtake(cur, Md * 8);
-        o.x1_32 = dtake(cur, Md * d * 4); o.x1_16 = dtake(cur, Md * d * 2);
-        o.q = dtake(cur, Md * d * 2); o.kv = dtake(cur, Nm * 2 * d * 2); o.ca = dtake(cur, Md * d * 2);
-        o.res2 = dtake(cur, Md * d * 4); o.st2 = dtake(cur, Md * 8);
-        o.x2_32 = dtake(cur, Md * d * 4); o.x2_16 = dtake(cur, Md * d * 2);
-        o.hid = dtake(cur, Md * dff * 2);
-        o.res3 = dtake(cur, Md * d * 4); o.st3 = dtake(cur, Md * 8);
+        o.w.sa_in = take(cur, 3 * d * d * 2); o.wt.sa_in = take(cur, 3 * d * d * 2);
+        o.w.sa_o = take(cur, d * d * 2); o.wt.sa_o = take(cur, d * d * 2);
+        o.w.q = take(cur, d * d * 2); o.wt.q = take(cur, d * d * 2);
+        o.w.kv = take(cur, 2 * d * d * 2); o.wt.kv = take(cur, 2 * d * d * 2);
+        o.w.ca_o = take(cur, d * d * 2); o.wt.ca_o = take(cur, d * d * 2);
+        o.w.w1 = take(cur, dff * d * 2); o.wt.w1 = take(cur, dff * d * 2);
+        o.w.w2 = take(cur, dff * d * 2); o.wt.w2 = take(cur, dff * d * 2);
+        o.x32 = take(cur, Md * d * 4); o.x16 = take(cur, Md * d * 2);
+        o.qkv = take(cur, Md * 3 * d * 2); o.sa = take(cur, Md * d * 2);
+        o.res1 = take(cur, Md * d * 4); o.st1 = take(cur, Md * 8);
+        o.x1_32 = take(cur, Md * d * 4); o.x1_16 = take(cur, Md * d * 2);
+        o.q = take(cur, Md * d * 2); o.kv = take(cur, Nm * 2 * d * 2); o.ca = take(cur, Md * d * 2);
+        o.res2 = take(cur, Md * d * 4); o.st2 = take(cur, Md * 8);
+        o.x2_32 = take(cur, Md * d * 4); o.x2_16 = take(cur, Md * d * 2);
+        o.hid = take(cur, Md * dff * 2);
+        o.res3 = take(cur, Md * d * 4); o.st3 = take(cur, Md * 8);
     }
-    pl.xL32 = dtake(cur, Md * d * 4);
-    pl.qkv32 = dtake(cur, Md * 3 * d * 4);
+    pl.xL32 = take(cur, Md * d * 4);
+    pl.qkv32 = take(cur, Md * 3 * d * 4);
     pl.saved_bytes = cur;
 
     size_t sc = 0;
-    pl.gA = dtake(sc, Md * d * 4); pl.gB = dtake(sc, Md * d * 4); pl.dres = dtake(sc, Md * d * 4);
-    pl.dattn16 = dtake(sc, Md * d * 2); pl.dqkv32 = dtake(sc, Md * 3 * d * 4);
+    pl.gA = take(sc, Md * d * 4); pl.gB = take(sc, Md * d * 4); pl.dres = take(sc, Md * d * 4);
+    pl.dattn16 = take(sc, Md * d * 2); pl.dqkv32 = take(sc, Md * 3 * d * 4);
     for (int l = 0; l < pl.L; ++l) {
-        for (int u = 0; u < 3; ++u) pl.g[l].dy16[u] = dtake(sc, Md * d * 2);
-        pl.g[l].dhid16 = dtake(sc, Md * dff * 2); pl.g[l].dqkv16 = dtake(sc, Md * 3 * d * 2);
-        pl.g[l].dq16 = dtake(sc, Md * d * 2); pl.g[l].dkv16 = dtake(sc, Nm * 2 * d * 2);
+        for (int u = 0; u < 3; ++u) pl.g[l].dy16[u] = take(sc, Md * d * 2);
+        pl.g[l].dhid16 = take(sc, Md * dff * 2); pl.g[l].dqkv16 = take(sc, Md * 3 * d * 2);
+        pl.g[l].dq16 = take(sc, Md * d * 2); pl.g[l].dkv16 = take(sc, Nm * 2 * d * 2);
     }
-    size_t all = 0;
-    auto add = [&](int M, int Nn, size_t K) { all += align_up(wide_gemm_tn_scratch(M, Nn, (int)K), 256); };
-    for (int l = 0; l < pl.L; ++l) {
-        add(pl.d, pl.dff, Md); add(pl.dff, pl.d, Md); add(pl.d, pl.d, Md); add(pl.d, pl.d, Md); add(pl.d, pl.d, Md);
-        add(3 * pl.d, pl.d, Md); add(2 * pl.d, pl.d, Nm);
-    }
-    pl.slab_all = dtake(sc, all); pl.slab_all_bytes = all;
-    pl.lnpart = dtake(sc, wide_ln_bwd_scratch((int)Md, pl.d));
-    size_t cs = dmax(wide_colsum_scratch((int)Md, 3 * pl.d), wide_colsum_scratch((int)Nm, 2 * pl.d));
-    cs = dmax(cs, (size_t)(4 * cdiv((int)Md, 256) + 4) * pl.dff * 4);
-    pl.cspart = dtake(sc, cs);
-    pl.cspart_side = dtake(sc, cs);
+    pl.slab_all_bytes = pl.L * wide_slab_bytes({{pl.d, pl.dff, Md}, {pl.dff, pl.d, Md}, {pl.d, pl.d, Md}, {pl.d, pl.d, Md}, {pl.d, pl.d, Md},
+                                                {3 * pl.d, pl.d, Md}, {2 * pl.d, pl.d, Nm}});
+    pl.slab_all = take(sc, pl.slab_all_bytes);
+    pl.lnpart = take(sc, wide_ln_bwd_scratch((int)Md, pl.d));
+    size_t cs = size_max(wide_colsum_scratch((int)Md, 3 * pl.d), wide_colsum_scratch((int)Nm, 2 * pl.d));
+    cs = size_max(cs, wide_ffn_colsum_bytes((int)Md, pl.dff));
+    pl.cspart = take(sc, cs);
+    pl.cspart_side = take(sc, cs);
     // a partial buffer per deferred row reduction of the backward (wide.h WideRowReduceBatch): per layer three LayerNorm backwards,
     // the lin1 bias sums and three bf16 column sums (self-attention in-projection, cross-attention q and k | v)
-    pl.rowpart_bytes = (size_t)pl.L * (3 * align_up(wide_ln_bwd_scratch((int)Md, pl.d), 256) + 4 * align_up(cs, 256));
-    pl.rowpart = dtake(sc, pl.rowpart_bytes);
-    pl.fcslab_bytes = dmax(gemm_scratch_bytes(2, pl.V, pl.d, (int)Md), gemm_scratch_bytes(1, (int)Md, pl.d, pl.V));
-    pl.fcslab_bytes = dmax(pl.fcslab_bytes, dmax(gemm_scratch_bytes(2, 3 * pl.d, pl.d, (int)Md), gemm_scratch_bytes(1, (int)Md, pl.d, 3 * pl.d)));
-    pl.fcslab = dtake(sc, pl.fcslab_bytes);
+    pl.rowpart_bytes = wide_rowpart_bytes(pl.L, 3, (int)Md, pl.d, {cs, cs, cs, cs});
+    pl.rowpart = take(sc, pl.rowpart_bytes);
+    pl.fcslab_bytes = size_max(gemm_scratch_bytes(2, pl.V, pl.d, (int)Md), gemm_scratch_bytes(1, (int)Md, pl.d, pl.V));
+    pl.fcslab_bytes = size_max(pl.fcslab_bytes, size_max(gemm_scratch_bytes(2, 3 * pl.d, pl.d, (int)Md), gemm_scratch_bytes(1, (int)Md, pl.d, 3 * pl.d)));
+    pl.fcslab = take(sc, pl.fcslab_bytes);
     pl.scratch_bytes = sc;
     return 0;
 }
 
-struct DDrop { uint64_t key = 0; uint32_t thresh = 0; float inv = 1.f; };
-thread_local const uint64_t* g_dkeys = nullptr;     // device-resident seed: table of this call's keys (layers 0x40 + l), see derive_keys
-DDrop ddrop(int training, float p, uint64_t seed, uint32_t layer, uint32_t site) {
-    DDrop dr;
-    if (training && p > 0.f) {
-        dr.key = g_dkeys ? key_slot(g_dkeys, layer, site) : site_key(seed, 0x40u + layer, site);
-        dr.thresh = drop_threshold(p); dr.inv = p < 1.f ? 1.f / (1.f - p) : 0.f;
-    }
-    return dr;
-}
-struct DKeyScope {
-    DKeyScope(const uint64_t* t) { g_dkeys = t; }
-    ~DKeyScope() { g_dkeys = nullptr; }
-};
 enum { DS_SELF = 1, DS_SA_OUT = 2, DS_CROSS = 3, DS_CA_OUT = 4, DS_FFN = 5, DS_FFN_OUT = 6, DS_EMBED = 7 };
 
 // The decoder's weight gradients (small TN GEMMs over B * sy target rows, bias column sums) are off the critical path of its
@@ -812,58 +792,127 @@ struct DecRagged {
     const int* clips[2]; int n[2], Sk_max[2];      // class 0: Sk <= 64 (dec_attn_kernel), class 1: the chunked kernel
 };
 
+// the context of one decoder call over `pl` (wide_run.h): the decoder's keys are those of layers 0x40 + l; with a device-resident seed the
+// kernels read them from the table in `saved` (the forward derives it there, the backward finds it)
+WideRun decoder_run(const egx_dec_config* cfg, const DPlan& pl, const void* saved, void* scratch, int training, uint64_t seed, hipStream_t st) {
+    WideRun r;
+    r.saved = (char*)const_cast<void*>(saved); r.scratch = (char*)scratch; r.st = st; r.zero = r.sv<char>(pl.zero);
+    r.ln_eps = cfg->ln_eps; r.p_drop = cfg->p_drop; r.training = training; r.seed = seed; r.layer_base = 0x40u;
+    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f);
+    r.keys = dev_keys ? r.sv<uint64_t>(pl.keys) : nullptr;
+    return r;
+}
+
+// One layer's weights -> bf16 at `o`, with the transposes at `ot` for a call that runs backward; skip_in: not the self-attention
+// in-projection (the cached step's layer 0 runs it in fp32 on the caller's weight and lays no copy out)
+int dec_cast_layer(WideCastBatch& cb, const WideRun& r, const egx_dec_layer& w, const DecW& o, const DecW* ot, bool skip_in, int d, int dff) {
+    auto t = [&](size_t DecW::*m) { return ot ? r.sv<bf16_t>(ot->*m) : nullptr; };
+    if (!skip_in && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, r.sv<bf16_t>(o.sa_in), t(&DecW::sa_in), r.st)) return 1;
+    if (wide_cast_add(cb, w.sa_out_w, d, d, d, r.sv<bf16_t>(o.sa_o), t(&DecW::sa_o), r.st)) return 1;
+    if (wide_cast_add(cb, w.ca_in_w, d, d, d, r.sv<bf16_t>(o.q), t(&DecW::q), r.st)) return 1;
+    if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, r.sv<bf16_t>(o.kv), t(&DecW::kv), r.st)) return 1;
+    if (wide_cast_add(cb, w.ca_out_w, d, d, d, r.sv<bf16_t>(o.ca_o), t(&DecW::ca_o), r.st)) return 1;
+    if (wide_cast_add(cb, w.lin1_w, dff, d, d, r.sv<bf16_t>(o.w1), t(&DecW::w1), r.st)) return 1;
+    return wide_cast_add(cb, w.lin2_w, d, dff, dff, r.sv<bf16_t>(o.w2), t(&DecW::w2), r.st);
+}
+
+// What one decoder layer reads and writes: filled per layer from a DPlan (every layer its own buffers, kept for the backward) or from a
+// StepPlan (one shared set). The cross-attention's K | V and the caches belong to the callers' attention callables.
+struct DecLayerView {
+    const float* x32; const bf16_t* x16;            // the layer's input rows (layer 0 reads the fp32 ones only)
+    const bf16_t* w_sa_in; const bf16_t* w_q;       // (the other weights: in the sublayers)
+    float* qkv32; bf16_t* qkv16; bf16_t* q;         // the self-attention's q | k | v (fp32: layer 0) and the cross-attention's queries
+    WideProjLn sa_out, ca_out;                      // behind the two attentions, whose outputs are their a16
+    WideFfn ffn;
+};
+// the weights W at `o` (W^T at `ot`, or none), the sublayers' three (pre-LN sum, statistics) pairs and outputs; y: the layer's output rows
+void dec_view_sublayers(DecLayerView& v, const WideRun& r, const egx_dec_layer& w, const DecW& o, const DecW* ot, int d, int dff, bf16_t* sa, bf16_t* ca,
+                        bf16_t* hid, float* const (&res)[3], float* const (&stats)[3], float* x1_32, bf16_t* x1_16, float* x2_32, bf16_t* x2_16,
+                        float* y32, bf16_t* y16) {
+    auto t = [&](size_t DecW::*m) { return ot ? r.sv<bf16_t>(ot->*m) : nullptr; };
+    v.w_sa_in = r.sv<bf16_t>(o.sa_in); v.w_q = r.sv<bf16_t>(o.q);
+    v.sa_out = {sa, d, r.sv<bf16_t>(o.sa_o), t(&DecW::sa_o), w.sa_out_b, v.x32, res[0], stats[0], w.norm1_w, w.norm1_b, x1_32, x1_16, DS_SA_OUT};
+    v.ca_out = {ca, d, r.sv<bf16_t>(o.ca_o), t(&DecW::ca_o), w.ca_out_b, x1_32, res[1], stats[1], w.norm2_w, w.norm2_b, x2_32, x2_16, DS_CA_OUT};
+    v.ffn = {x2_16, r.sv<bf16_t>(o.w1), t(&DecW::w1), w.lin1_b, dff, DS_FFN,
+             {hid, dff, r.sv<bf16_t>(o.w2), t(&DecW::w2), w.lin2_b, x2_32, res[2], stats[2], w.norm3_w, w.norm3_b, y32, y16, DS_FFN_OUT}};
+}
+DecLayerView dplan_view(const WideRun& r, const DPlan& pl, int l, const egx_dec_layer& w) {
+    const DLayer& o = pl.layer[l];
+    const bool last = l + 1 == pl.L;
+    DecLayerView v;
+    v.x32 = r.sv<float>(o.x32); v.x16 = r.sv<bf16_t>(o.x16);
+    v.qkv32 = r.sv<float>(pl.qkv32); v.qkv16 = r.sv<bf16_t>(o.qkv); v.q = r.sv<bf16_t>(o.q);
+    float* const res[3] = {r.sv<float>(o.res1), r.sv<float>(o.res2), r.sv<float>(o.res3)};
+    float* const stats[3] = {r.sv<float>(o.st1), r.sv<float>(o.st2), r.sv<float>(o.st3)};
+    dec_view_sublayers(v, r, w, o.w, &o.wt, pl.d, pl.dff, r.sv<bf16_t>(o.sa), r.sv<bf16_t>(o.ca), r.sv<bf16_t>(o.hid), res, stats, r.sv<float>(o.x1_32),
+                       r.sv<bf16_t>(o.x1_16), r.sv<float>(o.x2_32), r.sv<bf16_t>(o.x2_16), r.sv<float>(last ? pl.xL32 : pl.layer[l + 1].x32),
+                       last ? nullptr : r.sv<bf16_t>(pl.layer[l + 1].x16));
+    return v;
+}
+
+// the cross-attention of Sq query rows per clip onto the clip's Sk memory rows (k | v rows of 2d); the callers add dropout, ragged
+// tables and the backward's gradients
+DecAttnParams cross_attn_params(const bf16_t* q, const bf16_t* kv, bf16_t* o, int d, int B, int H, int Sq, int Sk) {
+    DecAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = o; a.ldo = d;
+    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.causal = 0;
+    return a;
+}
+
+// ONE decoder layer's forward over M target rows, for training (decoder_fwd_run) and for the cached step (StepRun::layers): nine launches
+// around the callers' two attentions. self_attn(l, v, f32) reads v.qkv32 (f32) or v.qkv16 and writes v.sa_out.a16; cross_attn(l, v) reads v.q and
+// writes v.ca_out.a16, behind whatever makes the memory's K | V ready. Dropout is the context's (a cached step's draws none).
+// Causal self-attention over the target tokens: layer 0 sees the embeddings scaled by sqrt(d): its q / k are an order of magnitude larger
+// than a LayerNorm output's and bf16-rounded scores would move the (near-saturated) softmax, so its in-projection runs on the exact
+// fp32 MFMA GEMM and its attention reads fp32 q / k / v (three small GEMMs per step).
+template <class SelfAttn, class CrossAttn>
+int decoder_layer_fwd(const WideRun& r, const egx_dec_layer& w, const DecLayerView& v, int l, int M, int d, SelfAttn&& self_attn, CrossAttn&& cross_attn) {
+    const bool f32_self = l == 0;
+    if (f32_self) {
+        GemmParams g;
+        g.A = v.x32; g.B = w.sa_in_w; g.C = v.qkv32; g.M = M; g.N = 3 * d; g.K = d; g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
+        if (gemm(0, g, 0, 0, nullptr, 0, r.st)) return 1;
+    } else if (r.nt(v.x16, v.w_sa_in, M, 3 * d, d, w.sa_in_b, nullptr, v.qkv16, 0, WideDrop(), nullptr)) return 1;
+    if (self_attn(l, v, f32_self)) return 1;
+    if (wide_proj_ln_fwd(r, v.sa_out, (uint32_t)l, M, d)) return 1;
+    // cross-attention onto the memory
+    if (r.nt(v.sa_out.y16, v.w_q, M, d, d, w.ca_in_b, nullptr, v.q, 0, WideDrop(), nullptr)) return 1;
+    if (cross_attn(l, v)) return 1;
+    if (wide_proj_ln_fwd(r, v.ca_out, (uint32_t)l, M, d)) return 1;
+    return wide_ffn_fwd(r, v.ffn, (uint32_t)l, M, d);
+}
+
 int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* tokens, const float* memory, const float* emb, const float* pe,
                     int pe_stride, const egx_dec_layer* layers, const float* fc_w, const float* fc_b, int B, float* logits, void* saved,
                     int training, uint64_t seed, hipStream_t st, const DecRagged* rg) {
     if (refuse_captured_dropout(cfg, training, st)) return 1;
-    const int d = pl.d, dff = pl.dff, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
+    const int d = pl.d, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
+    const WideRun r = decoder_run(cfg, pl, saved, nullptr, training, seed, st);
     // device-resident seed (the encoder's forward of this step has advanced it): this call's keys, derived on the stream
-    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f);
-    if (dev_keys && derive_keys(const_cast<uint64_t*>(cfg->seed_ptr), at<uint64_t>(saved, pl.keys), 0x40u, 16, 0, st)) return 1;
-    DKeyScope key_scope(dev_keys ? cat<uint64_t>(saved, pl.keys) : nullptr);
-    EGX_HIP(hipMemsetAsync(at<char>(saved, pl.zero), 0, 1024, st));
-    const void* zero = at<char>(saved, pl.zero);
-    bf16_t* mem16 = at<bf16_t>(saved, pl.mem16);
+    if (r.keys && derive_keys(const_cast<uint64_t*>(cfg->seed_ptr), r.sv<uint64_t>(pl.keys), 0x40u, 16, 0, st)) return 1;
+    EGX_HIP(hipMemsetAsync(r.sv<char>(pl.zero), 0, 1024, st));
+    bf16_t* mem16 = r.sv<bf16_t>(pl.mem16);
     if (wide_cast(memory, Nm, d, d, mem16, nullptr, st)) return 1;
     {   // every weight -> bf16 (W and W^T), one launch
         WideCastBatch cb;
-        for (int l = 0; l < pl.L; ++l) {
-            const DLayer& o = pl.layer[l];
-            const egx_dec_layer& w = layers[l];
-            if (wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(saved, o.w_sa_in), at<bf16_t>(saved, o.w_sa_in_t), st)) return 1;
-            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(saved, o.w_sa_o), at<bf16_t>(saved, o.w_sa_o_t), st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(saved, o.w_q), at<bf16_t>(saved, o.w_q_t), st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(saved, o.w_kv), at<bf16_t>(saved, o.w_kv_t), st)) return 1;
-            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(saved, o.w_ca_o), at<bf16_t>(saved, o.w_ca_o_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(saved, o.w1), at<bf16_t>(saved, o.w1_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(saved, o.w2), at<bf16_t>(saved, o.w2_t), st)) return 1;
-        }
+        for (int l = 0; l < pl.L; ++l)
+            if (dec_cast_layer(cb, r, layers[l], pl.layer[l].w, &pl.layer[l].wt, false, d, pl.dff)) return 1;
         if (wide_cast_flush(cb, st)) return 1;
     }
     {   // embedding * sqrt(d) + positional encoding (+ dropout)
-        DDrop de = ddrop(training, cfg->p_pos, seed, 0, DS_EMBED);
+        const WideDrop de = r.drop(cfg->p_pos, 0, DS_EMBED);
         const size_t n4 = pl.Md * (d / 4);
         hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, tokens, emb, pe, pe_stride, sqrtf((float)d),
-                           at<float>(saved, pl.layer[0].x32), at<bf16_t>(saved, pl.layer[0].x16), Md, pl.sy, d, pl.V, de.key, de.thresh, de.inv);
+                           r.sv<float>(pl.layer[0].x32), r.sv<bf16_t>(pl.layer[0].x16), Md, pl.sy, d, pl.V, de.key, de.thresh, de.inv);
         EGX_LAUNCH_CHECK();
     }
-    auto nt_on = [&](hipStream_t s_, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                     const DDrop& dr, const float* residual) -> int {
-        WideGemmParams g;
-        g.A = A; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
-        g.drop_key = dr.key; g.drop_thresh = dr.thresh; g.drop_inv = dr.inv; g.residual = residual; g.ldr = N; g.zero_page = zero;
-        return wide_gemm_nt(g, s_);
+    // the K | V projection of the memory for layer l (the one large GEMM of a layer), on stream s
+    auto project_kv = [&](int l, hipStream_t s) {
+        return r.nt_on(s, mem16, r.sv<bf16_t>(pl.layer[l].w.kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, r.sv<bf16_t>(pl.layer[l].kv), 0, WideDrop(), nullptr);
     };
-    auto nt = [&](const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-                  const DDrop& dr, const float* residual) -> int { return nt_on(st, A, lda, W, M, N, K, bias, Cf, Cb, relu, dr, residual); };
-    auto ln = [&](const float* x, const float* w, const float* b, float* stats, float* y32, bf16_t* y16) -> int {
-        WideLnFwdParams lp;
-        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = stats; lp.y32 = y32; lp.y16 = y16; lp.rows = Md; lp.d = d;
-        return wide_ln_fwd(lp, st);
-    };
-    const DDrop none;
-    // the K | V projections of the memory (the one large GEMM of a layer) depend on nothing the target-token chain computes: all
-    // of them go to the side stream now, beside the chain's 16-WG launches; a layer's cross-attention waits for its own
+    // these depend on nothing the target-token chain computes: all of them go to the side stream now, beside the chain's 16-WG
+    // launches; a layer's cross-attention waits for its own
     SideStream& SS = side_stream();
     SideJoin sj(SS, st);        // error paths: join whatever was forked
     const bool side = side_wanted(SS, st);
@@ -871,74 +920,40 @@ int decoder_fwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
         if (SS.order(st, SS.s)) return 1;
         sj.forked = true;
         for (int l = 0; l < pl.L; ++l) {
-            const DLayer& o = pl.layer[l];
-            if (nt_on(SS.s, mem16, d, cat<bf16_t>(saved, o.w_kv), Nm, 2 * d, d, layers[l].ca_in_b + d, nullptr, at<bf16_t>(saved, o.kv), 0, none, nullptr)) return 1;
+            if (project_kv(l, SS.s)) return 1;
             EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
         }
     }
-    for (int l = 0; l < pl.L; ++l) {
-        const DLayer& o = pl.layer[l];
-        const egx_dec_layer& w = layers[l];
-        const bool last = l + 1 == pl.L;
-        float* xo32 = last ? at<float>(saved, pl.xL32) : at<float>(saved, pl.layer[l + 1].x32);
-        bf16_t* xo16 = last ? nullptr : at<bf16_t>(saved, pl.layer[l + 1].x16);
-        // causal self-attention over the target tokens. Layer 0 sees the embeddings scaled by sqrt(d): its q / k are an order
-        // of magnitude larger than a LayerNorm output's and bf16-rounded scores would move the (near-saturated) softmax, so
-        // its in-projection runs on the exact fp32 MFMA GEMM and its attention reads fp32 q / k / v (three small GEMMs per step)
-        const bool f32_self = l == 0;
-        if (f32_self) {
-            GemmParams g;
-            g.A = cat<float>(saved, o.x32); g.B = w.sa_in_w; g.C = at<float>(saved, pl.qkv32); g.M = Md; g.N = 3 * d; g.K = d;
-            g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
-            if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
-        } else if (nt(cat<bf16_t>(saved, o.x16), d, cat<bf16_t>(saved, o.w_sa_in), Md, 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(saved, o.qkv), 0, none, nullptr)) return 1;
-        {
-            DecAttnParams a;
-            memset(&a, 0, sizeof(a));
-            if (f32_self) { const float* qkv = cat<float>(saved, pl.qkv32); a.q = qkv; a.k = qkv + d; a.v = qkv + 2 * d; }
-            else { const bf16_t* qkv = cat<bf16_t>(saved, o.qkv); a.q = qkv; a.k = qkv + d; a.v = qkv + 2 * d; }
-            a.ldq = a.ldk = a.ldv = 3 * d; a.o = at<bf16_t>(saved, o.sa); a.ldo = d;
-            a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.sy; a.causal = 1;
-            DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_SELF);
-            a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (dec_attn<false>(a, dh, f32_self, st)) return 1;
-        }
-        if (nt(cat<bf16_t>(saved, o.sa), d, cat<bf16_t>(saved, o.w_sa_o), Md, d, d, w.sa_out_b, at<float>(saved, o.res1), nullptr, 0,
-               ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_SA_OUT), cat<float>(saved, o.x32))) return 1;
-        if (ln(cat<float>(saved, o.res1), w.norm1_w, w.norm1_b, at<float>(saved, o.st1), at<float>(saved, o.x1_32), at<bf16_t>(saved, o.x1_16))) return 1;
-        // cross-attention onto the memory
-        if (nt(cat<bf16_t>(saved, o.x1_16), d, cat<bf16_t>(saved, o.w_q), Md, d, d, w.ca_in_b, nullptr, at<bf16_t>(saved, o.q), 0, none, nullptr)) return 1;
+    auto self_attn = [&](int l, const DecLayerView& v, bool f32) -> int {
+        DecAttnParams a;
+        memset(&a, 0, sizeof(a));
+        if (f32) { a.q = v.qkv32; a.k = v.qkv32 + d; a.v = v.qkv32 + 2 * d; }
+        else { a.q = v.qkv16; a.k = v.qkv16 + d; a.v = v.qkv16 + 2 * d; }
+        a.ldq = a.ldk = a.ldv = 3 * d; a.o = v.sa_out.a16; a.ldo = d;
+        a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.sy; a.causal = 1;
+        const WideDrop da = r.drop(cfg->p_drop, (uint32_t)l, DS_SELF);
+        a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
+        return dec_attn<false>(a, dh, f32, st);
+    };
+    auto cross_attn = [&](int l, const DecLayerView& v) -> int {
         if (side) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
-        else if (nt(mem16, d, cat<bf16_t>(saved, o.w_kv), Nm, 2 * d, d, w.ca_in_b + d, nullptr, at<bf16_t>(saved, o.kv), 0, none, nullptr)) return 1;
-        {
-            DecAttnParams a;
-            memset(&a, 0, sizeof(a));
-            const bf16_t* kv = cat<bf16_t>(saved, o.kv);
-            a.q = cat<bf16_t>(saved, o.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(saved, o.ca); a.ldo = d;
-            a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.S; a.causal = 0;
-            DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CROSS);
-            a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (rg) {
-                a.mtab = rg->mtab;
-                for (int c = 0; c < 2; ++c) {
-                    a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
-                    if (dec_attn_ragged_train<false>(a, dh, c == 1, st)) return 1;
-                }
-            } else if (dec_attn<false>(a, dh, false, st)) return 1;
+        else if (project_kv(l, st)) return 1;
+        DecAttnParams a = cross_attn_params(v.q, r.sv<bf16_t>(pl.layer[l].kv), v.ca_out.a16, d, B, pl.H, pl.sy, pl.S);
+        const WideDrop da = r.drop(cfg->p_drop, (uint32_t)l, DS_CROSS);
+        a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
+        if (!rg) return dec_attn<false>(a, dh, false, st);
+        a.mtab = rg->mtab;
+        for (int c = 0; c < 2; ++c) {
+            a.clips = rg->clips[c]; a.B = rg->n[c]; a.Sk = rg->Sk_max[c];
+            if (dec_attn_ragged_train<false>(a, dh, c == 1, st)) return 1;
         }
-        if (nt(cat<bf16_t>(saved, o.ca), d, cat<bf16_t>(saved, o.w_ca_o), Md, d, d, w.ca_out_b, at<float>(saved, o.res2), nullptr, 0,
-               ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CA_OUT), cat<float>(saved, o.x1_32))) return 1;
-        if (ln(cat<float>(saved, o.res2), w.norm2_w, w.norm2_b, at<float>(saved, o.st2), at<float>(saved, o.x2_32), at<bf16_t>(saved, o.x2_16))) return 1;
-        // FFN
-        if (nt(cat<bf16_t>(saved, o.x2_16), d, cat<bf16_t>(saved, o.w1), Md, dff, d, w.lin1_b, nullptr, at<bf16_t>(saved, o.hid), 1,
-               ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_FFN), nullptr)) return 1;
-        if (nt(cat<bf16_t>(saved, o.hid), dff, cat<bf16_t>(saved, o.w2), Md, d, dff, w.lin2_b, at<float>(saved, o.res3), nullptr, 0,
-               ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_FFN_OUT), cat<float>(saved, o.x2_32))) return 1;
-        if (ln(cat<float>(saved, o.res3), w.norm3_w, w.norm3_b, at<float>(saved, o.st3), xo32, xo16)) return 1;
-    }
+        return 0;
+    };
+    for (int l = 0; l < pl.L; ++l)
+        if (decoder_layer_fwd(r, layers[l], dplan_view(r, pl, l, layers[l]), l, Md, d, self_attn, cross_attn)) return 1;
     {   // vocabulary head (|V| is 7..12: the shape-generic GEMM, fp32 rows in, fp32 logits out)
         GemmParams g;
-        g.A = cat<float>(saved, pl.xL32); g.B = fc_w; g.C = logits; g.M = Md; g.N = pl.V; g.K = d; g.lda = d; g.ldb = d; g.ldc = pl.V; g.bias = fc_b;
+        g.A = r.sv<float>(pl.xL32); g.B = fc_w; g.C = logits; g.M = Md; g.N = pl.V; g.K = d; g.lda = d; g.ldb = d; g.ldc = pl.V; g.bias = fc_b;
         if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
     }
     sj.forked = false;      // joined already: every layer's cross-attention waited for its kv_ev, the last side-stream operation
@@ -1012,7 +1027,7 @@ int egx_decoder_ragged_fwd(const egx_dec_config* cfg, const int64_t* tokens, con
     EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && workspace, "egx_decoder_ragged_fwd: null pointer argument");
     hipStream_t st = (hipStream_t)stream;
     // the table goes to the device in the arguments of upload launches (stream-ordered; a captured graph would replay THESE lengths)
-    int* dtab = reinterpret_cast<int*>((char*)workspace + off_tab);
+    int* dtab = at<int>(workspace, off_tab);
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
     const DecRagged rg = dec_ragged_view(dtab, B, n, smax);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, workspace, 0, 0, st, &rg);
@@ -1062,18 +1077,14 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
                     float* d_fc_w, float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, hipStream_t st,
                     const DecRagged* rg) {
     if (refuse_captured_dropout(cfg, training, st)) return 1;
-    const int d = pl.d, dff = pl.dff, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
-    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f);
-    DKeyScope key_scope(dev_keys ? cat<uint64_t>(saved, pl.keys) : nullptr);
-    const void* zero = cat<char>(saved, pl.zero);
+    const int d = pl.d, Md = (int)pl.Md, Nm = (int)pl.Nm, dh = d / pl.H;
+    WideRun r = decoder_run(cfg, pl, saved, scratch, training, seed, st);
     if (zero_buf && zero_bytes) EGX_HIP(hipMemsetAsync(zero_buf, 0, zero_bytes, st));
-    float* gA = at<float>(scratch, pl.gA);
-    float* gB = at<float>(scratch, pl.gB);
-    float* dres = at<float>(scratch, pl.dres);
-    bf16_t* dattn16 = at<bf16_t>(scratch, pl.dattn16);
-    void* lnpart = at<char>(scratch, pl.lnpart);
-    float* cspart = at<float>(scratch, pl.cspart);
-    float* cspart_side = at<float>(scratch, pl.cspart_side);
+    float* gA = r.sc<float>(pl.gA);
+    float* gB = r.sc<float>(pl.gB);
+    float* dres = r.sc<float>(pl.dres);
+    bf16_t* dattn16 = r.sc<bf16_t>(pl.dattn16);
+    float* cspart_side = r.sc<float>(pl.cspart_side);
     // side stream for the weight gradients: fork() orders it behind everything enqueued on `st` so far
     SideStream& SS = side_stream();
     const bool side = side_wanted(SS, st);
@@ -1085,116 +1096,65 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
         sj.forked = true;
         return 0;
     };
-    const bf16_t* mem16 = cat<bf16_t>(saved, pl.mem16);
+    const bf16_t* mem16 = r.sv<bf16_t>(pl.mem16);
 
-    WideReduceBatch rb;
-    size_t slab_cur = 0;
-    // second stages of the two-stage column sums (LayerNorm / bias gradients): queued with a partial buffer of their own each, summed
-    // by ONE launch at the end (every target is a different parameter: concurrent sums never meet)
-    WideRowReduceBatch rrb;
-    size_t row_cur = 0;
-    auto row_region = [&](size_t need) -> void* {
-        need = align_up(need, 256);
-        if (row_cur + need > pl.rowpart_bytes) return nullptr;
-        void* r = at<char>(scratch, pl.rowpart) + row_cur;
-        row_cur += need;
-        return r;
-    };
+    // The ledger (wide_run.h): every weight gradient has a slab region of its own (none left: refused) and their split-K sums run as one
+    // launch at the end; the second stages of the two-stage column sums (LayerNorm / bias gradients) are queued with a partial buffer of
+    // their own each and summed by ONE launch at the end (every target is a different parameter: concurrent sums never meet).
     // Round 5: the weight gradients are QUEUED and leave as one grouped launch per tile variant at the end of the call (wide_gemm.hip
     // wide_tn_queue_*): 35 launches of 14 us each over 512 target rows become one or two grids that fill the chip. Their operands sit in
     // per-(layer, use) buffers until then. Used where the side stream is not (a captured step, EGX_DEC_SIDE=0): with eager launches the
     // side stream already hides these GEMMs beside the target-token chain and grouping them at the end measured 1.4 % slower (C5 HOI
     // 3.80 -> 3.86 ms); captured, C5 HHI 2.42 -> 2.26 ms (profiles/r05_dec_group.txt). EGX_DEC_GROUP=0 / 1 forces either.
-    WideTnQueue tq;
-    const int group_env = tuning().dec_group;
-    const bool grouped = group_env >= 0 ? group_env != 0 : !side;
     // (ungrouped: enqueued on the side stream; the caller forks first)
-    auto dw_tn = [&](const bf16_t* dy, int ldy, const bf16_t* x, int ldx, float* dW, int n_out, int k_in, int tokens_k) -> int {
-        if (!dW) return 0;
-        WideGemmParams t;
-        t.A = dy; t.B = x; t.M = n_out; t.N = k_in; t.K = tokens_k; t.lda = ldy; t.ldb = ldx;
-        t.Cf = dW; t.ldc = k_in; t.zero_page = zero;
-        // (Writing straight into dW with one split over <= 1024 target rows - no slab, no batched reduction of 55-73 us - lengthened the side
-        // stream: same-box C5 HOI 3.95 = 3.95 ms, C5 HHI 2.46 -> 2.62 ms. That variant last existed at 3b19ffd.)
-        // a target inside the buffer this call has just zero-filled is overwritten (saves the read of the += ), anything else keeps
-        // the += contract of the header
-        const char* zb = (const char*)zero_buf;
-        const bool zeroed = zb && (const char*)dW >= zb && (const char*)(dW + (size_t)n_out * k_in) <= zb + zero_bytes;
-        t.accumulate = zeroed ? 0 : 1;
-        const size_t need = align_up(wide_gemm_tn_scratch(n_out, k_in, tokens_k), 256);
-        EGX_CHECK(slab_cur + need <= pl.slab_all_bytes, "decoder backward: slab region exhausted");
-        void* region = at<char>(scratch, pl.slab_all) + slab_cur;
-        slab_cur += need;
-        if (grouped) return wide_tn_queue_add(tq, t, region, st, &rb);
-        return wide_gemm_tn(t, region, sd, &rb);
-    };
-    auto nt = [&](const bf16_t* A, int lda, const bf16_t* Wt, int M, int N, int K, float* Cf, bf16_t* Cb, const float* residual,
-                  const bf16_t* mask, float mask_scale, float* colsum) -> int {
-        WideGemmParams g;
-        g.A = A; g.B = Wt; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N;
-        g.residual = residual; g.ldr = N; g.mask = mask; g.ldm = N; g.mask_scale = mask_scale; g.colsum = colsum; g.zero_page = zero;
-        return wide_gemm_nt(g, st);
-    };
-    auto ln_bwd = [&](const float* dy, const float* pre, const float* stats, const float* w, const DDrop& outm, float* dw, float* db, float* dbias, bf16_t* dy16) -> int {
-        WideLnBwdParams b;
-        b.dy = dy; b.pre = pre; b.stats = stats; b.w = w; b.dx32 = dres; b.dx16 = dy16; b.rows = Md; b.d = d;
-        b.out_key = outm.key; b.out_thresh = outm.thresh; b.out_inv = outm.inv;
-        b.dw = dw; b.db = db; b.dbias = dbias;
-        void* reg = row_region(wide_ln_bwd_scratch(b.rows, b.d));
-        return reg ? wide_ln_bwd(b, reg, st, &rrb) : wide_ln_bwd(b, lnpart, st);
-    };
+    // (Writing straight into dW with one split over <= 1024 target rows - no slab, no batched reduction of 55-73 us - lengthened the side
+    // stream: same-box C5 HOI 3.95 = 3.95 ms, C5 HHI 2.46 -> 2.62 ms. That variant last existed at 3b19ffd.)
+    WideLedger led;
+    led.st = st; led.tn_stream = sd; led.zero = r.zero;
+    led.slab = r.sc<char>(pl.slab_all); led.slab_bytes = pl.slab_all_bytes;
+    led.rows = r.sc<char>(pl.rowpart); led.rows_bytes = pl.rowpart_bytes;
+    led.lnpart = r.sc<char>(pl.lnpart); led.cspart = r.sc<float>(pl.cspart);
+    led.fresh = (const char*)zero_buf; led.fresh_bytes = zero_bytes;
+    const int group_env = tuning().dec_group;
+    led.grouped = group_env >= 0 ? group_env != 0 : !side;
+    r.led = &led;
 
     // vocabulary head: d(fc_w) += d_logits^T x, d(fc_b) += colsum, g = d_logits fc_w
     float* g = gA;
     {
-        const float* xL = cat<float>(saved, pl.xL32);
+        const float* xL = r.sv<float>(pl.xL32);
         if (d_fc_w) {
             GemmParams t;
             t.A = d_logits; t.B = xL; t.C = d_fc_w; t.M = pl.V; t.N = d; t.K = Md; t.lda = pl.V; t.ldb = d; t.ldc = d;
-            if (gemm(2, t, 0, 1, at<char>(scratch, pl.fcslab), pl.fcslab_bytes, st)) return 1;
+            if (gemm(2, t, 0, 1, r.sc<char>(pl.fcslab), pl.fcslab_bytes, st)) return 1;
         }
         if (d_fc_b && colsum_accum(d_logits, Md, pl.V, pl.V, d_fc_b, st)) return 1;
         GemmParams q;
         q.A = d_logits; q.B = fc_w; q.C = g; q.M = Md; q.N = d; q.K = pl.V; q.lda = pl.V; q.ldb = d; q.ldc = d;
-        if (gemm(1, q, 0, 0, at<char>(scratch, pl.fcslab), pl.fcslab_bytes, st)) return 1;
+        if (gemm(1, q, 0, 0, r.sc<char>(pl.fcslab), pl.fcslab_bytes, st)) return 1;
     }
     bool mem_started = false;
     for (int l = pl.L - 1; l >= 0; --l) {
         const DLayer& o = pl.layer[l];
-        const egx_dec_layer& w = layers[l];
         const egx_dec_layer_grads& gw = grads[l];
-        bf16_t* dy16a = at<bf16_t>(scratch, pl.g[l].dy16[0]);
-        bf16_t* dy16b = at<bf16_t>(scratch, pl.g[l].dy16[1]);
-        bf16_t* dy16c = at<bf16_t>(scratch, pl.g[l].dy16[2]);
-        bf16_t* dhid16 = at<bf16_t>(scratch, pl.g[l].dhid16);
-        bf16_t* dqkv16 = at<bf16_t>(scratch, pl.g[l].dqkv16);
-        bf16_t* dq16 = at<bf16_t>(scratch, pl.g[l].dq16);
-        bf16_t* dkv16 = at<bf16_t>(scratch, pl.g[l].dkv16);
+        const DecLayerView v = dplan_view(r, pl, l, layers[l]);
+        bf16_t* dy16a = r.sc<bf16_t>(pl.g[l].dy16[0]);
+        bf16_t* dy16b = r.sc<bf16_t>(pl.g[l].dy16[1]);
+        bf16_t* dy16c = r.sc<bf16_t>(pl.g[l].dy16[2]);
+        bf16_t* dqkv16 = r.sc<bf16_t>(pl.g[l].dqkv16);
+        bf16_t* dq16 = r.sc<bf16_t>(pl.g[l].dq16);
+        bf16_t* dkv16 = r.sc<bf16_t>(pl.g[l].dkv16);
         // FFN
-        if (ln_bwd(g, cat<float>(saved, o.res3), cat<float>(saved, o.st3), w.norm3_w, ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_FFN_OUT),
-                   gw.norm3_w, gw.norm3_b, gw.lin2_b, dy16a)) return 1;
-        if (fork() || dw_tn(dy16a, d, cat<bf16_t>(saved, o.hid), dff, gw.lin2_w, d, dff, Md)) return 1;
-        float* cs_l1 = cspart;
-        if (gw.lin1_b) { void* rg = row_region((size_t)wide_gemm_nt_colsum_rows(Md, dff) * dff * 4); if (rg) cs_l1 = (float*)rg; }
-        if (nt(dy16a, d, cat<bf16_t>(saved, o.w2_t), Md, dff, d, nullptr, dhid16, nullptr, cat<bf16_t>(saved, o.hid),
-               ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_FFN).inv, gw.lin1_b ? cs_l1 : nullptr)) return 1;
-        if (gw.lin1_b && wide_reduce_rows(cs_l1, wide_gemm_nt_colsum_rows(Md, dff), dff, gw.lin1_b, st, cs_l1 != cspart ? &rrb : nullptr)) return 1;
-        if (fork() || dw_tn(dhid16, dff, cat<bf16_t>(saved, o.x2_16), d, gw.lin1_w, dff, d, Md)) return 1;
         float* g1 = (g == gA) ? gB : gA;
-        if (nt(dhid16, dff, cat<bf16_t>(saved, o.w1_t), Md, d, dff, g1, nullptr, dres, nullptr, 1.f, nullptr)) return 1;
+        if (wide_ffn_bwd(r, v.ffn, {gw.lin1_w, gw.lin1_b, {gw.lin2_w, gw.lin2_b, gw.norm3_w, gw.norm3_b}}, (uint32_t)l, Md, d, g, dres, dy16a,
+                         r.sc<bf16_t>(pl.g[l].dhid16), g1, fork)) return 1;
         // cross-attention
-        if (ln_bwd(g1, cat<float>(saved, o.res2), cat<float>(saved, o.st2), w.norm2_w, ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CA_OUT),
-                   gw.norm2_w, gw.norm2_b, gw.ca_out_b, dy16b)) return 1;
-        if (fork() || dw_tn(dy16b, d, cat<bf16_t>(saved, o.ca), d, gw.ca_out_w, d, d, Md)) return 1;
-        if (nt(dy16b, d, cat<bf16_t>(saved, o.w_ca_o_t), Md, d, d, nullptr, dattn16, nullptr, nullptr, 1.f, nullptr)) return 1;
+        if (wide_proj_ln_bwd(r, v.ca_out, {gw.ca_out_w, gw.ca_out_b, gw.norm2_w, gw.norm2_b}, (uint32_t)l, Md, d, g1, dres, dy16b, fork)) return 1;
+        if (r.nt_bwd(dy16b, v.ca_out.w_t, Md, d, d, nullptr, dattn16, nullptr)) return 1;
         {
-            DecAttnParams a;
-            memset(&a, 0, sizeof(a));
-            const bf16_t* kv = cat<bf16_t>(saved, o.kv);
-            a.q = cat<bf16_t>(saved, o.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.ldo = d;
+            DecAttnParams a = cross_attn_params(v.q, r.sv<bf16_t>(o.kv), nullptr, d, B, pl.H, pl.sy, pl.S);
             a.d_o = dattn16; a.dq = dq16; a.dk = dkv16; a.dv = dkv16 + d;
-            a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.S; a.causal = 0;
-            DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_CROSS);
+            const WideDrop da = r.drop(cfg->p_drop, (uint32_t)l, DS_CROSS);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
             if (rg) {
                 a.mtab = rg->mtab;
@@ -1205,40 +1165,31 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
             } else if (dec_attn<true>(a, dh, false, st)) return 1;
         }
         if (fork()) return 1;
-        if (gw.ca_in_b) {
-            void* r1 = row_region(wide_colsum_scratch(Md, d));
-            void* r2 = row_region(wide_colsum_scratch(Nm, 2 * d));
-            if (wide_colsum_bf16(dq16, Md, d, d, gw.ca_in_b, r1 ? r1 : (void*)cspart_side, sd, r1 ? &rrb : nullptr)) return 1;
-            if (wide_colsum_bf16(dkv16, Nm, 2 * d, 2 * d, gw.ca_in_b + d, r2 ? r2 : (void*)cspart_side, sd, r2 ? &rrb : nullptr)) return 1;
-        }
-        if (dw_tn(dq16, d, cat<bf16_t>(saved, o.x1_16), d, gw.ca_in_w, d, d, Md)) return 1;
-        if (dw_tn(dkv16, 2 * d, mem16, d, gw.ca_in_w ? gw.ca_in_w + (size_t)d * d : nullptr, 2 * d, d, Nm)) return 1;
+        if (gw.ca_in_b && (led.colsum(dq16, Md, d, gw.ca_in_b, cspart_side, sd) || led.colsum(dkv16, Nm, 2 * d, gw.ca_in_b + d, cspart_side, sd))) return 1;
+        if (led.dw_tn(dq16, v.sa_out.y16, gw.ca_in_w, d, d, Md)) return 1;
+        if (led.dw_tn(dkv16, mem16, gw.ca_in_w ? gw.ca_in_w + (size_t)d * d : nullptr, 2 * d, d, Nm)) return 1;
         if (d_memory) {     // d(memory) (+)= d(kv) W_kv, summed over the layers
-            if (nt(dkv16, 2 * d, cat<bf16_t>(saved, o.w_kv_t), Nm, d, 2 * d, d_memory, nullptr, mem_started ? d_memory : nullptr, nullptr, 1.f, nullptr)) return 1;
+            if (r.nt_bwd(dkv16, r.sv<bf16_t>(o.wt.kv), Nm, d, 2 * d, d_memory, nullptr, mem_started ? d_memory : nullptr)) return 1;
             mem_started = true;
         }
         float* g2 = (g1 == gA) ? gB : gA;
-        if (nt(dq16, d, cat<bf16_t>(saved, o.w_q_t), Md, d, d, g2, nullptr, dres, nullptr, 1.f, nullptr)) return 1;
+        if (r.nt_bwd(dq16, r.sv<bf16_t>(o.wt.q), Md, d, d, g2, nullptr, dres)) return 1;
         // self-attention
-        if (ln_bwd(g2, cat<float>(saved, o.res1), cat<float>(saved, o.st1), w.norm1_w, ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_SA_OUT),
-                   gw.norm1_w, gw.norm1_b, gw.sa_out_b, dy16c)) return 1;
-        if (fork() || dw_tn(dy16c, d, cat<bf16_t>(saved, o.sa), d, gw.sa_out_w, d, d, Md)) return 1;
-        if (nt(dy16c, d, cat<bf16_t>(saved, o.w_sa_o_t), Md, d, d, nullptr, dattn16, nullptr, nullptr, 1.f, nullptr)) return 1;
+        if (wide_proj_ln_bwd(r, v.sa_out, {gw.sa_out_w, gw.sa_out_b, gw.norm1_w, gw.norm1_b}, (uint32_t)l, Md, d, g2, dres, dy16c, fork)) return 1;
+        if (r.nt_bwd(dy16c, v.sa_out.w_t, Md, d, d, nullptr, dattn16, nullptr)) return 1;
         const bool f32_self = l == 0;
-        float* dqkv32 = at<float>(scratch, pl.dqkv32);
+        float* dqkv32 = r.sc<float>(pl.dqkv32);
         {
             DecAttnParams a;
             memset(&a, 0, sizeof(a));
             if (f32_self) {
-                const float* qkv = cat<float>(saved, pl.qkv32);
-                a.q = qkv; a.k = qkv + d; a.v = qkv + 2 * d; a.dq = dqkv32; a.dk = dqkv32 + d; a.dv = dqkv32 + 2 * d;
+                a.q = v.qkv32; a.k = v.qkv32 + d; a.v = v.qkv32 + 2 * d; a.dq = dqkv32; a.dk = dqkv32 + d; a.dv = dqkv32 + 2 * d;
             } else {
-                const bf16_t* qkv = cat<bf16_t>(saved, o.qkv);
-                a.q = qkv; a.k = qkv + d; a.v = qkv + 2 * d; a.dq = dqkv16; a.dk = dqkv16 + d; a.dv = dqkv16 + 2 * d;
+                a.q = v.qkv16; a.k = v.qkv16 + d; a.v = v.qkv16 + 2 * d; a.dq = dqkv16; a.dk = dqkv16 + d; a.dv = dqkv16 + 2 * d;
             }
             a.ldq = a.ldk = a.ldv = 3 * d; a.ldo = d; a.d_o = dattn16;
             a.B = B; a.H = pl.H; a.Sq = pl.sy; a.Sk = pl.sy; a.causal = 1;
-            DDrop da = ddrop(training, cfg->p_drop, seed, (uint32_t)l, DS_SELF);
+            const WideDrop da = r.drop(cfg->p_drop, (uint32_t)l, DS_SELF);
             a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
             if (dec_attn<true>(a, dh, f32_self, st)) return 1;
         }
@@ -1248,27 +1199,23 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
             if (gw.sa_in_b && colsum_accum(dqkv32, Md, 3 * d, 3 * d, gw.sa_in_b, st)) return 1;
             if (gw.sa_in_w) {
                 GemmParams t;
-                t.A = dqkv32; t.B = cat<float>(saved, o.x32); t.C = gw.sa_in_w; t.M = 3 * d; t.N = d; t.K = Md; t.lda = 3 * d; t.ldb = d; t.ldc = d;
-                if (gemm(2, t, 0, 1, at<char>(scratch, pl.fcslab), pl.fcslab_bytes, st)) return 1;
+                t.A = dqkv32; t.B = v.x32; t.C = gw.sa_in_w; t.M = 3 * d; t.N = d; t.K = Md; t.lda = 3 * d; t.ldb = d; t.ldc = d;
+                if (gemm(2, t, 0, 1, r.sc<char>(pl.fcslab), pl.fcslab_bytes, st)) return 1;
             }
             // d(layer input): only the embedding gradient reads it -> the bf16 GEMM like the other layers, on a bf16 copy of dqkv
             if (wide_cast(dqkv32, Md, 3 * d, 3 * d, dqkv16, nullptr, st)) return 1;
-            if (nt(dqkv16, 3 * d, cat<bf16_t>(saved, o.w_sa_in_t), Md, d, 3 * d, g0, nullptr, dres, nullptr, 1.f, nullptr)) return 1;
         } else {
             if (fork()) return 1;
-            if (gw.sa_in_b) {
-                void* r3 = row_region(wide_colsum_scratch(Md, 3 * d));
-                if (wide_colsum_bf16(dqkv16, Md, 3 * d, 3 * d, gw.sa_in_b, r3 ? r3 : (void*)cspart_side, sd, r3 ? &rrb : nullptr)) return 1;
-            }
-            if (dw_tn(dqkv16, 3 * d, cat<bf16_t>(saved, o.x16), d, gw.sa_in_w, 3 * d, d, Md)) return 1;
-            if (nt(dqkv16, 3 * d, cat<bf16_t>(saved, o.w_sa_in_t), Md, d, 3 * d, g0, nullptr, dres, nullptr, 1.f, nullptr)) return 1;
+            if (gw.sa_in_b && led.colsum(dqkv16, Md, 3 * d, gw.sa_in_b, cspart_side, sd)) return 1;
+            if (led.dw_tn(dqkv16, v.x16, gw.sa_in_w, 3 * d, d, Md)) return 1;
         }
+        if (r.nt_bwd(dqkv16, r.sv<bf16_t>(o.wt.sa_in), Md, d, 3 * d, g0, nullptr, dres)) return 1;
         g = g0;
     }
     if (sj.join()) return 1;    // the slab reduction below (and whatever the caller enqueues next) comes after the side stream's work
     if (d_memory && !mem_started) EGX_HIP(hipMemsetAsync(d_memory, 0, pl.Nm * d * sizeof(float), st));
     if (d_emb) {
-        DDrop de = ddrop(training, cfg->p_pos, seed, 0, DS_EMBED);
+        const WideDrop de = r.drop(cfg->p_pos, 0, DS_EMBED);
         if (pl.V <= EMB_VMAX)
         {
             int G = 65536 / (pl.V * 256);
@@ -1281,9 +1228,7 @@ int decoder_bwd_run(const egx_dec_config* cfg, const DPlan& pl, const int64_t* t
                                de.key, de.thresh, de.inv);
         EGX_LAUNCH_CHECK();
     }
-    if (wide_row_reduce_flush(rrb, st)) return 1;   // every queued LayerNorm / bias column sum
-    if (wide_tn_queue_flush(tq, st)) return 1;      // every queued weight gradient: one grid per tile variant, then their slab sums
-    return wide_reduce_flush(rb, st);
+    return led.flush();
 }
 }  // namespace
 
@@ -1323,7 +1268,7 @@ int egx_decoder_ragged_train_fwd(const egx_dec_config* cfg, const int64_t* token
     EGX_CHECK(tokens && memory && emb && pe && layers && fc_w && logits && saved, "egx_decoder_ragged_train_fwd: null pointer argument");
     (void)scratch;
     hipStream_t st = (hipStream_t)stream;
-    int* dtab = reinterpret_cast<int*>((char*)saved + off_tab);       // (kept in `saved`: the backward reads the same table)
+    int* dtab = at<int>(saved, off_tab);       // (kept in `saved`: the backward reads the same table)
     if (upload_words(dtab, tab.data(), tab.size(), st)) return 1;
     const DecRagged rg = dec_ragged_view(dtab, B, n, smax);
     return decoder_fwd_run(cfg, pl, tokens, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, logits, saved, training, seed, st, &rg);
@@ -1340,7 +1285,7 @@ int egx_decoder_ragged_bwd(const egx_dec_config* cfg, const int64_t* tokens, con
     if (decoder_ragged_plan(cfg, B, mem_lengths, pl, tab, n, smax, off_tab, nb, true)) return 1;
     EGX_CHECK(tokens && layers && fc_w && d_logits && saved && scratch && grads, "egx_decoder_ragged_bwd: null pointer argument");
     // (the forward left the table in `saved`; the host copy rebuilt from the same lengths gives its layout)
-    const DecRagged rg = dec_ragged_view(reinterpret_cast<const int*>((const char*)saved + off_tab), B, n, smax);
+    const DecRagged rg = dec_ragged_view(cat<int>(saved, off_tab), B, n, smax);
     return decoder_bwd_run(cfg, pl, tokens, layers, fc_w, B, d_logits, saved, scratch, d_memory, d_emb, grads, d_fc_w, d_fc_b, zero_buf, zero_bytes,
                            training, seed, (hipStream_t)stream, &rg);
 }
@@ -1612,7 +1557,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gen_head_kernel(GenHeadParams p
     }
 }
 
-struct GLayer { size_t w_sa_in, w_sa_o, w_q, w_kv, w_ca_o, w1, w2, kv, cache; };
+struct GLayer { DecW w; size_t kv, cache; };
 
 // The host checks of a token schedule (egx_decoder_generate_sched / egx_decoder_beam_sched), before any device work: period rows (0: no
 // schedule), counts a HOST int[period] with every count in 1 .. vocab, words the DEVICE int32[period][vocab] table (not read here). W > 0:
@@ -1638,7 +1583,7 @@ struct StepPlan {
     size_t zero, mem16, x32, x16, qkv32, qkv16, sa, res, st, x1_32, x1_16, q, ca, x2_32, x2_16, hid, xL32;
     size_t xin32, score, anc[2], hist[2];       // a call's own buffers, taken behind the shared layout (beam_plan, forced_plan)
     GLayer layer[16];
-    size_t bytes;                               // the running total: dtake(pl.bytes, ...) appends
+    size_t bytes;                               // the running total: take(pl.bytes, ...) appends
 };
 
 // The checks every cached-step entry point and workspace query opens with, under its own name; the call's own range checks follow.
@@ -1671,22 +1616,22 @@ int step_layout(const egx_dec_config* c, int B, int rows, int n_steps, size_t st
     pl.M = (size_t)B * rows; pl.Nm = (size_t)B * c->S;
     const size_t d = pl.d, dff = pl.dff, Nm = pl.Nm, M = pl.M;
     size_t& cur = pl.bytes;
-    pl.zero = dtake(cur, 1024);
-    pl.mem16 = dtake(cur, Nm * d * 2);
+    pl.zero = take(cur, 1024);
+    pl.mem16 = take(cur, Nm * d * 2);
     for (int l = 0; l < pl.L; ++l) {
         GLayer& o = pl.layer[l];
-        o.w_sa_in = l ? dtake(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
-        o.w_sa_o = dtake(cur, d * d * 2); o.w_q = dtake(cur, d * d * 2); o.w_kv = dtake(cur, 2 * d * d * 2); o.w_ca_o = dtake(cur, d * d * 2);
-        o.w1 = dtake(cur, dff * d * 2); o.w2 = dtake(cur, dff * d * 2);
-        o.kv = dtake(cur, Nm * 2 * d * 2);
-        o.cache = dtake(cur, M * n_steps * 2 * d * (l ? 2 : 4));
+        o.w.sa_in = l ? take(cur, 3 * d * d * 2) : 0;      // (layer 0's in-projection runs in fp32 on the caller's weight)
+        o.w.sa_o = take(cur, d * d * 2); o.w.q = take(cur, d * d * 2); o.w.kv = take(cur, 2 * d * d * 2); o.w.ca_o = take(cur, d * d * 2);
+        o.w.w1 = take(cur, dff * d * 2); o.w.w2 = take(cur, dff * d * 2);
+        o.kv = take(cur, Nm * 2 * d * 2);
+        o.cache = take(cur, M * n_steps * 2 * d * (l ? 2 : 4));
     }
-    pl.x32 = dtake(cur, M * d * 4); pl.x16 = dtake(cur, M * d * 2);
-    pl.qkv32 = dtake(cur, M * 3 * d * 4); pl.qkv16 = dtake(cur, M * 3 * d * 2); pl.sa = dtake(cur, M * d * 2);
-    pl.res = dtake(cur, M * d * 4); pl.st = dtake(cur, M * st_row);
-    pl.x1_32 = dtake(cur, M * d * 4); pl.x1_16 = dtake(cur, M * d * 2); pl.q = dtake(cur, M * d * 2); pl.ca = dtake(cur, M * d * 2);
-    pl.x2_32 = dtake(cur, M * d * 4); pl.x2_16 = dtake(cur, M * d * 2); pl.hid = dtake(cur, M * dff * 2);
-    pl.xL32 = dtake(cur, M * xL_steps * d * 4);
+    pl.x32 = take(cur, M * d * 4); pl.x16 = take(cur, M * d * 2);
+    pl.qkv32 = take(cur, M * 3 * d * 4); pl.qkv16 = take(cur, M * 3 * d * 2); pl.sa = take(cur, M * d * 2);
+    pl.res = take(cur, M * d * 4); pl.st = take(cur, M * st_row);
+    pl.x1_32 = take(cur, M * d * 4); pl.x1_16 = take(cur, M * d * 2); pl.q = take(cur, M * d * 2); pl.ca = take(cur, M * d * 2);
+    pl.x2_32 = take(cur, M * d * 4); pl.x2_16 = take(cur, M * d * 2); pl.hid = take(cur, M * dff * 2);
+    pl.xL32 = take(cur, M * xL_steps * d * 4);
     return 0;
 }
 
@@ -1695,43 +1640,20 @@ int step_layout(const egx_dec_config* c, int B, int rows, int n_steps, size_t st
 // stream on every error return.
 struct StepRun {
     const egx_dec_config* cfg; const StepPlan& pl; const egx_dec_layer* lw; void* ws; hipStream_t st;
+    WideRun r;                  // no dropout, no keys: inference
     SideStream& SS; SideJoin sj; bool side = false;
     StepRun(const egx_dec_config* c, const StepPlan& p, const egx_dec_layer* layers, void* workspace, hipStream_t s)
-        : cfg(c), pl(p), lw(layers), ws(workspace), st(s), SS(side_stream()), sj(SS, s) {}
-
-    int nt_on(hipStream_t s_, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu,
-              const float* residual) {
-        WideGemmParams g;
-        g.A = A; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.Cf = Cf; g.Cb = Cb; g.ldc = N; g.bias = bias; g.relu = relu;
-        g.residual = residual; g.ldr = N; g.zero_page = at<char>(ws, pl.zero);
-        return wide_gemm_nt(g, s_);
-    }
-    int nt(const bf16_t* A, int lda, const bf16_t* W, int N, int K, const float* bias, float* Cf, bf16_t* Cb, int relu, const float* residual) {
-        return nt_on(st, A, lda, W, (int)pl.M, N, K, bias, Cf, Cb, relu, residual);
-    }
-    int ln(const float* x, const float* w, const float* b, float* y32, bf16_t* y16) {
-        WideLnFwdParams lp;
-        lp.x = x; lp.w = w; lp.b = b; lp.eps = cfg->ln_eps; lp.stats = at<float>(ws, pl.st); lp.y32 = y32; lp.y16 = y16; lp.rows = (int)pl.M; lp.d = pl.d;
-        return wide_ln_fwd(lp, st);
+        : cfg(c), pl(p), lw(layers), ws(workspace), st(s), SS(side_stream()), sj(SS, s) {
+        r.saved = (char*)ws; r.st = st; r.zero = r.sv<char>(pl.zero); r.ln_eps = cfg->ln_eps;
     }
 
     // the zero page, the memory -> bf16, every weight -> bf16 once (no transposed copies: nothing runs backward), one launch
     int begin(const float* memory) {
-        const int d = pl.d, dff = pl.dff;
-        EGX_HIP(hipMemsetAsync(at<char>(ws, pl.zero), 0, 1024, st));
-        if (wide_cast(memory, (int)pl.Nm, d, d, at<bf16_t>(ws, pl.mem16), nullptr, st)) return 1;
+        EGX_HIP(hipMemsetAsync(r.sv<char>(pl.zero), 0, 1024, st));
+        if (wide_cast(memory, (int)pl.Nm, pl.d, pl.d, r.sv<bf16_t>(pl.mem16), nullptr, st)) return 1;
         WideCastBatch cb;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = lw[l];
-            if (l && wide_cast_add(cb, w.sa_in_w, 3 * d, d, d, at<bf16_t>(ws, o.w_sa_in), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.sa_out_w, d, d, d, at<bf16_t>(ws, o.w_sa_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w, d, d, d, at<bf16_t>(ws, o.w_q), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_in_w + (size_t)d * d, 2 * d, d, d, at<bf16_t>(ws, o.w_kv), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.ca_out_w, d, d, d, at<bf16_t>(ws, o.w_ca_o), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(ws, o.w1), nullptr, st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(ws, o.w2), nullptr, st)) return 1;
-        }
+        for (int l = 0; l < pl.L; ++l)
+            if (dec_cast_layer(cb, r, lw[l], pl.layer[l].w, nullptr, l == 0, pl.d, pl.dff)) return 1;
         return wide_cast_flush(cb, st);
     }
 
@@ -1745,59 +1667,48 @@ struct StepRun {
         }
         for (int l = 0; l < pl.L; ++l) {
             const GLayer& o = pl.layer[l];
-            if (nt_on(side ? SS.s : st, cat<bf16_t>(ws, pl.mem16), d, cat<bf16_t>(ws, o.w_kv), (int)pl.Nm, 2 * d, d, lw[l].ca_in_b + d, nullptr,
-                      at<bf16_t>(ws, o.kv), 0, nullptr)) return 1;
+            if (r.nt_on(side ? SS.s : st, r.sv<bf16_t>(pl.mem16), r.sv<bf16_t>(o.w.kv), (int)pl.Nm, 2 * d, d, lw[l].ca_in_b + d, nullptr, r.sv<bf16_t>(o.kv), 0,
+                        WideDrop(), nullptr)) return 1;
             if (side) EGX_HIP(hipEventRecord(SS.kv_ev[l], SS.s));
         }
         return 0;
     }
 
-    // Step t's M new rows through the layers. xin: layer 0's fp32 input rows (and the residual of its out-projection); xL: where the last
-    // layer's LN3 writes; self_attn(qkv, cache, o, f32, t, st): the call's cached self-attention of one layer; attn_out, when given,
-    // (L, n_steps, B, S): every layer's cross-attention is followed by one dec_cross_weights_kernel launch on the same q and k.
+    // Step t's M new rows through the layers (decoder_layer_fwd over the one shared buffer set). xin: layer 0's fp32 input rows (and the
+    // residual of its out-projection); xL: where the last layer's LN3 writes; self_attn(qkv, cache, o, f32, t, st): the call's cached
+    // self-attention of one layer; attn_out, when given, (L, n_steps, B, S): every layer's cross-attention is followed by one
+    // dec_cross_weights_kernel launch on the same q and k.
     template <class SelfAttn>
     int layers(int t, const float* xin, float* xL, SelfAttn&& self_attn, float* attn_out) {
-        const int d = pl.d, dff = pl.dff, dh = d / pl.H;
-        for (int l = 0; l < pl.L; ++l) {
-            const GLayer& o = pl.layer[l];
-            const egx_dec_layer& w = lw[l];
-            const bool last = l + 1 == pl.L;
-            const bool f32_self = l == 0;       // (decoder_fwd_run: layer 0 sees the embeddings scaled by sqrt(d))
-            const float* x32 = f32_self ? xin : cat<float>(ws, pl.x32);
-            if (f32_self) {
-                GemmParams g;
-                g.A = x32; g.B = w.sa_in_w; g.C = at<float>(ws, pl.qkv32); g.M = (int)pl.M; g.N = 3 * d; g.K = d;
-                g.lda = d; g.ldb = d; g.ldc = 3 * d; g.bias = w.sa_in_b;
-                if (gemm(0, g, 0, 0, nullptr, 0, st)) return 1;
-            } else if (nt(cat<bf16_t>(ws, pl.x16), d, cat<bf16_t>(ws, o.w_sa_in), 3 * d, d, w.sa_in_b, nullptr, at<bf16_t>(ws, pl.qkv16), 0, nullptr)) return 1;
-            if (self_attn(f32_self ? (const void*)cat<float>(ws, pl.qkv32) : (const void*)cat<bf16_t>(ws, pl.qkv16), at<char>(ws, o.cache),
-                          at<bf16_t>(ws, pl.sa), f32_self, t, st)) return 1;
-            if (nt(cat<bf16_t>(ws, pl.sa), d, cat<bf16_t>(ws, o.w_sa_o), d, d, w.sa_out_b, at<float>(ws, pl.res), nullptr, 0, x32)) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm1_w, w.norm1_b, at<float>(ws, pl.x1_32), at<bf16_t>(ws, pl.x1_16))) return 1;
-            // cross-attention of the clip's new rows onto its S memory rows: dec_attn with Sq = the rows per clip
-            if (nt(cat<bf16_t>(ws, pl.x1_16), d, cat<bf16_t>(ws, o.w_q), d, d, w.ca_in_b, nullptr, at<bf16_t>(ws, pl.q), 0, nullptr)) return 1;
+        const int d = pl.d, dh = d / pl.H;
+        auto self = [&](int l, const DecLayerView& v, bool f32) -> int {
+            return self_attn(f32 ? (const void*)v.qkv32 : (const void*)v.qkv16, r.sv<char>(pl.layer[l].cache), v.sa_out.a16, f32, t, st);
+        };
+        // cross-attention of the clip's new rows onto its S memory rows: dec_attn with Sq = the rows per clip
+        auto cross = [&](int l, const DecLayerView& v) -> int {
             if (side && t == 0) EGX_HIP(hipStreamWaitEvent(st, SS.kv_ev[l], 0));
-            {
-                DecAttnParams a;
-                memset(&a, 0, sizeof(a));
-                const bf16_t* kv = cat<bf16_t>(ws, o.kv);
-                a.q = cat<bf16_t>(ws, pl.q); a.ldq = d; a.k = kv; a.v = kv + d; a.ldk = a.ldv = 2 * d; a.o = at<bf16_t>(ws, pl.ca); a.ldo = d;
-                a.B = pl.B; a.H = pl.H; a.Sq = pl.rows; a.Sk = pl.S; a.causal = 0;
-                if (dec_attn<false>(a, dh, false, st)) return 1;
-                if (attn_out) {     // (egx_decoder_generate_attn, one row per clip) this step's head-averaged weights of the layer: attn_out[l][t] (B, S)
-                    CrossWParams cw;
-                    memset(&cw, 0, sizeof(cw));
-                    cw.q = a.q; cw.ldq = d; cw.k = kv; cw.ldk = 2 * d; cw.out = attn_out + ((size_t)l * pl.n + t) * pl.B * pl.S; cw.ldo = pl.S;
-                    cw.B = pl.B; cw.H = pl.H; cw.Sq = 1; cw.Sk = pl.S;
-                    if (cross_weights(cw, dh, false, st)) return 1;
-                }
-            }
-            if (nt(cat<bf16_t>(ws, pl.ca), d, cat<bf16_t>(ws, o.w_ca_o), d, d, w.ca_out_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x1_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm2_w, w.norm2_b, at<float>(ws, pl.x2_32), at<bf16_t>(ws, pl.x2_16))) return 1;
-            // FFN
-            if (nt(cat<bf16_t>(ws, pl.x2_16), d, cat<bf16_t>(ws, o.w1), dff, d, w.lin1_b, nullptr, at<bf16_t>(ws, pl.hid), 1, nullptr)) return 1;
-            if (nt(cat<bf16_t>(ws, pl.hid), dff, cat<bf16_t>(ws, o.w2), d, dff, w.lin2_b, at<float>(ws, pl.res), nullptr, 0, cat<float>(ws, pl.x2_32))) return 1;
-            if (ln(cat<float>(ws, pl.res), w.norm3_w, w.norm3_b, last ? xL : at<float>(ws, pl.x32), last ? nullptr : at<bf16_t>(ws, pl.x16))) return 1;
+            const bf16_t* kv = r.sv<bf16_t>(pl.layer[l].kv);
+            const DecAttnParams a = cross_attn_params(v.q, kv, v.ca_out.a16, d, pl.B, pl.H, pl.rows, pl.S);
+            if (dec_attn<false>(a, dh, false, st)) return 1;
+            if (!attn_out) return 0;
+            // (egx_decoder_generate_attn, one row per clip) this step's head-averaged weights of the layer: attn_out[l][t] (B, S)
+            CrossWParams cw;
+            memset(&cw, 0, sizeof(cw));
+            cw.q = a.q; cw.ldq = d; cw.k = kv; cw.ldk = 2 * d; cw.out = attn_out + ((size_t)l * pl.n + t) * pl.B * pl.S; cw.ldo = pl.S;
+            cw.B = pl.B; cw.H = pl.H; cw.Sq = 1; cw.Sk = pl.S;
+            return cross_weights(cw, dh, false, st);
+        };
+        float* const res[3] = {r.sv<float>(pl.res), r.sv<float>(pl.res), r.sv<float>(pl.res)};
+        float* const stats[3] = {r.sv<float>(pl.st), r.sv<float>(pl.st), r.sv<float>(pl.st)};
+        for (int l = 0; l < pl.L; ++l) {
+            const bool last = l + 1 == pl.L;
+            DecLayerView v;
+            v.x32 = l == 0 ? xin : r.sv<float>(pl.x32); v.x16 = r.sv<bf16_t>(pl.x16);
+            v.qkv32 = r.sv<float>(pl.qkv32); v.qkv16 = r.sv<bf16_t>(pl.qkv16); v.q = r.sv<bf16_t>(pl.q);
+            dec_view_sublayers(v, r, lw[l], pl.layer[l].w, nullptr, d, pl.dff, r.sv<bf16_t>(pl.sa), r.sv<bf16_t>(pl.ca), r.sv<bf16_t>(pl.hid), res, stats,
+                               r.sv<float>(pl.x1_32), r.sv<bf16_t>(pl.x1_16), r.sv<float>(pl.x2_32), r.sv<bf16_t>(pl.x2_16),
+                               last ? xL : r.sv<float>(pl.x32), last ? nullptr : r.sv<bf16_t>(pl.x16));
+            if (decoder_layer_fwd(r, lw[l], v, l, (int)pl.M, d, self, cross)) return 1;
         }
         return 0;
     }
@@ -2066,10 +1977,10 @@ int beam_plan(const egx_dec_config* c, int B, int n_steps, int W, StepPlan& pl) 
     EGX_CHECK(beam_head_lds(W, c->d_model, c->vocab) <= (size_t)BEAM_LDS_LIMIT, "egx_decoder_beam: the head needs %zu bytes of LDS (at most %d)",
               beam_head_lds(W, c->d_model, c->vocab), BEAM_LDS_LIMIT);
     if (step_rows_fit("egx_decoder_beam", 'W', c, B, W)) return 1;
-    pl.score = dtake(pl.bytes, pl.M * 256);
+    pl.score = take(pl.bytes, pl.M * 256);
     for (int u = 0; u < 2; ++u) {
-        pl.anc[u] = dtake(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int));
-        pl.hist[u] = dtake(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int64_t));
+        pl.anc[u] = take(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int));
+        pl.hist[u] = take(pl.bytes, pl.M * BEAM_DEPTH * sizeof(int64_t));
     }
     return 0;
 }
@@ -2237,7 +2148,7 @@ int forced_plan(const egx_dec_config* c, int B, int R, int n_steps, StepPlan& pl
     EGX_CHECK(R >= 1 && R <= FORCED_MAX_R, "egx_decoder_forced: R = %d (1..%d)", R, FORCED_MAX_R);
     if (step_layout(c, B, R, n_steps, 256, n_steps, pl)) return 1;
     if (step_rows_fit("egx_decoder_forced", 'R', c, B, R)) return 1;
-    pl.xin32 = dtake(pl.bytes, pl.M * n_steps * pl.d * 4);
+    pl.xin32 = take(pl.bytes, pl.M * n_steps * pl.d * 4);
     return 0;
 }
 

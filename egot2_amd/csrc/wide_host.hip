@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "wide.h"
 #include "wide_host.h"
+#include "wide_run.h"
 #include "fused.h"      // (upload_words: the ragged batch table)
 
 namespace egx {
@@ -46,9 +47,6 @@ struct WRagged {
     int ncls[3] = {0, 0, 0}, Smax[3] = {0, 0, 0};
 };
 
-size_t take(size_t& cur, size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
-size_t smax(size_t a, size_t b) { return a > b ? a : b; }
-
 // rg: a ragged batch — N = sum_b S_b packed token rows and R_k compacted rows of segment k instead of B * S and B * T_k; nothing is sized by B * max S_b.
 // An inference batch (rg->train false: egx_ragged_encode) keeps nothing for a backward: one set of activation buffers serves every layer and every
 // segment, res2 / stats2 reuse res1 / stats1, and no W^T is laid out (offset 0, the zero page's); only `saved` is used.
@@ -60,7 +58,7 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
     pl.S = S; pl.N = rg ? rg->N : (size_t)B * S;
     const bool infer = rg && !rg->train;
     size_t din_max = 0;
-    for (int i = 0; i < pl.nseg; ++i) din_max = smax(din_max, (size_t)segs[i].d_in);
+    for (int i = 0; i < pl.nseg; ++i) din_max = size_max(din_max, (size_t)segs[i].d_in);
     auto seg_rows = [&](int i) { return rg ? rg->R[i] : (size_t)B * segs[i].T; };
     const size_t d = pl.d, N = pl.N, dff = pl.dff;
     size_t cur = 0;
@@ -116,60 +114,36 @@ void make_wplan(const egx_config* cfg, const egx_segment* segs, int B, WPlan& pl
     pl.dqkv16 = take(sc, N * 3 * d * 2);
     pl.adelta = take(sc, rg ? (rg->ncls[2] ? N * pl.H * sizeof(float) : 0) : wide_attn_delta_bytes(B, pl.H, S));
     size_t segrows = 0;
-    for (int i = 0; i < pl.nseg; ++i) segrows = smax(segrows, seg_rows(i));
+    for (int i = 0; i < pl.nseg; ++i) segrows = size_max(segrows, seg_rows(i));
     pl.dseg16 = take(sc, segrows * d * 2);
     size_t slab = 0;
-    slab = smax(slab, wide_gemm_tn_scratch(3 * pl.d, pl.d, (int)N));
-    slab = smax(slab, wide_gemm_tn_scratch(pl.d, pl.d, (int)N));
-    slab = smax(slab, wide_gemm_tn_scratch(pl.dff, pl.d, (int)N));
-    slab = smax(slab, wide_gemm_tn_scratch(pl.d, pl.dff, (int)N));
+    slab = size_max(slab, wide_gemm_tn_scratch(3 * pl.d, pl.d, (int)N));
+    slab = size_max(slab, wide_gemm_tn_scratch(pl.d, pl.d, (int)N));
+    slab = size_max(slab, wide_gemm_tn_scratch(pl.dff, pl.d, (int)N));
+    slab = size_max(slab, wide_gemm_tn_scratch(pl.d, pl.dff, (int)N));
     for (int i = 0; i < pl.nseg; ++i)
-        if (segs[i].proj_w) slab = smax(slab, wide_gemm_tn_scratch(pl.d, segs[i].d_in, (int)seg_rows(i)));
+        if (segs[i].proj_w) slab = size_max(slab, wide_gemm_tn_scratch(pl.d, segs[i].d_in, (int)seg_rows(i)));
     pl.slabs = take(sc, slab);
     // one slab region per weight gradient of a backward (their reductions run as ONE launch at its end)
-    size_t all = 0;
-    auto add = [&](int M, int Nn, int K) { all += (wide_gemm_tn_scratch(M, Nn, K) + 255) / 256 * 256; };
-    for (int l = 0; l < pl.L; ++l) { add(pl.d, pl.dff, (int)N); add(pl.dff, pl.d, (int)N); add(pl.d, pl.d, (int)N); add(3 * pl.d, pl.d, (int)N); }
+    size_t all = pl.L * wide_slab_bytes({{pl.d, pl.dff, N}, {pl.dff, pl.d, N}, {pl.d, pl.d, N}, {3 * pl.d, pl.d, N}});
     for (int i = 0; i < pl.nseg; ++i)
-        if (segs[i].proj_w) add(pl.d, segs[i].d_in, (int)seg_rows(i));
+        if (segs[i].proj_w) all += wide_slab_bytes({{pl.d, segs[i].d_in, seg_rows(i)}});
     if (all > ((size_t)400 << 20)) all = 0;      // measured break-even (wide_encoder_bwd): 283 MB pays, 764 MB does not
     pl.slab_all = take(sc, all);
     pl.slab_all_bytes = all;
     pl.lnpart = take(sc, wide_ln_bwd_scratch((int)N, pl.d));
-    size_t cs = smax(wide_colsum_scratch((int)N, 3 * pl.d), (size_t)(4 * cdiv((int)N, 256) + 4) * pl.dff * 4);
-    if (!rg) for (int i = 0; i < pl.nseg; ++i) cs = smax(cs, wide_pos_grad_scratch(B, segs[i].T, pl.d));      // (ragged: no learned-position gradient)
+    const size_t cs_ffn = wide_ffn_colsum_bytes((int)N, pl.dff), cs_in = wide_colsum_scratch((int)N, 3 * pl.d);
+    size_t cs = size_max(cs_in, cs_ffn);
+    if (!rg) for (int i = 0; i < pl.nseg; ++i) cs = size_max(cs, wide_pos_grad_scratch(B, segs[i].T, pl.d));      // (ragged: no learned-position gradient)
     pl.cspart = take(sc, cs);
     // a partial buffer per deferred row reduction of a backward (wide_row_reduce_flush: ONE launch sums them all at its end):
     // two LayerNorm backwards + the lin1 / in-projection bias column sums per layer
-    {
-        const size_t ln = (wide_ln_bwd_scratch((int)N, pl.d) + 255) / 256 * 256;
-        const size_t c1 = ((size_t)(4 * cdiv((int)N, 256) + 4) * pl.dff * 4 + 255) / 256 * 256, c2 = (wide_colsum_scratch((int)N, 3 * pl.d) + 255) / 256 * 256;
-        size_t all_r = (size_t)pl.L * (2 * ln + c1 + c2);
-        if (all_r > ((size_t)256 << 20)) all_r = 0;
-        pl.rowpart = take(sc, all_r);
-        pl.rowpart_bytes = all_r;
-    }
+    size_t all_r = wide_rowpart_bytes(pl.L, 2, (int)N, pl.d, {cs_ffn, cs_in});
+    if (all_r > ((size_t)256 << 20)) all_r = 0;
+    pl.rowpart = take(sc, all_r);
+    pl.rowpart_bytes = all_r;
     pl.scratch_bytes = sc;
 }
-
-struct Drop { uint64_t key = 0; uint32_t thresh = 0; float inv = 1.f; };
-// g_keys != null (device-resident seed): the key is the ADDRESS of its slot in the table derive_keys() filled on the stream
-thread_local const uint64_t* g_keys = nullptr;
-Drop mkdrop(int training, float p, uint64_t seed, uint32_t layer, uint32_t site) {
-    Drop dr;
-    if (training && p > 0.f) {
-        dr.key = g_keys ? key_slot(g_keys, layer, site) : site_key(seed, layer, site);
-        dr.thresh = drop_threshold(p); dr.inv = p < 1.f ? 1.f / (1.f - p) : 0.f;
-    }
-    return dr;
-}
-struct KeyScope {       // sets the table for the mkdrop calls of one forward / backward
-    KeyScope(const uint64_t* t) { g_keys = t; }
-    ~KeyScope() { g_keys = nullptr; }
-};
-
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>((char*)base + off); }
-template <class T> const T* cat(const void* base, size_t off) { return reinterpret_cast<const T*>((const char*)base + off); }
 
 }  // namespace
 
@@ -204,35 +178,73 @@ void wide_qkv_offsets(const egx_config* cfg, const egx_segment* segs, int B, siz
 }
 
 namespace {
+// the context of one encoder call over `pl`: with a device-resident seed the kernels read their keys from the table in `saved` (the forward
+// derives it there, the backward finds it)
+WideRun encoder_run(const egx_config* cfg, const WPlan& pl, const void* saved, void* scratch, int training, uint64_t seed, hipStream_t st) {
+    WideRun r;
+    r.saved = (char*)const_cast<void*>(saved); r.scratch = (char*)scratch; r.st = st; r.zero = r.sv<char>(pl.zero);
+    r.ln_eps = cfg->ln_eps; r.p_drop = cfg->p_drop; r.training = training; r.seed = seed;
+    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f || cfg->p_feat > 0.f);
+    r.keys = dev_keys ? r.sv<uint64_t>(pl.keys) : nullptr;
+    return r;
+}
+// layer l's two post-LN sublayers over the plan's buffers; y32 / y16: where the forward's last LayerNorm writes
+void encoder_sublayers(const WideRun& r, const WPlan& pl, int l, const egx_layer& w, float* y32, bf16_t* y16, WideProjLn& attn_out, WideFfn& ffn) {
+    const WLayer& o = pl.layer[l];
+    auto wt = [&](size_t off) { return off ? r.sv<bf16_t>(off) : nullptr; };       // (0: the plan laid out no W^T)
+    attn_out = {r.sv<bf16_t>(o.attn), pl.d, r.sv<bf16_t>(o.w_o), wt(o.w_o_t), w.out_proj_b, r.sv<float>(o.x32), r.sv<float>(o.res1),
+                r.sv<float>(o.stats1), w.norm1_w, w.norm1_b, r.sv<float>(o.x1_32), r.sv<bf16_t>(o.x1_16), SITE_RES1};
+    ffn = {r.sv<bf16_t>(o.x1_16), r.sv<bf16_t>(o.w1), wt(o.w1_t), w.lin1_b, pl.dff, SITE_FFN,
+           {r.sv<bf16_t>(o.hid), pl.dff, r.sv<bf16_t>(o.w2), wt(o.w2_t), w.lin2_b, r.sv<float>(o.x1_32), r.sv<float>(o.res2), r.sv<float>(o.stats2),
+            w.norm2_w, w.norm2_b, y32, y16, SITE_RES2}};
+}
+// the self-attention of layer l, forward or (BWD) backward: uniform, or a ragged batch's one launch per attention kernel class
+template <bool BWD>
+int encoder_attn(const WideRun& r, const WPlan& pl, int l, int B, const WRagged* rg, const int* tab) {
+    const WLayer& o = pl.layer[l];
+    WideAttnParams a;
+    a.qkv = r.sv<bf16_t>(o.qkv); a.out = r.sv<bf16_t>(o.attn); a.lse = r.sv<float>(o.lse);
+    if (BWD) { a.delta = r.sc<float>(pl.adelta); a.d_out = r.sc<bf16_t>(pl.dattn16); a.d_qkv = r.sc<bf16_t>(pl.dqkv16); }
+    a.B = B; a.S = pl.S; a.H = pl.H; a.d = pl.d;
+    const WideDrop da = r.drop(r.p_drop, (uint32_t)l, SITE_ATTN);
+    a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
+    if (!rg) return BWD ? wide_attn_bwd(a, r.st) : wide_attn_fwd(a, r.st);
+    a.rtab = tab;
+    for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {
+        if (!rg->ncls[c]) continue;
+        a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
+        if (BWD ? wide_attn_ragged_bwd(a, r.st) : wide_attn_ragged_fwd(a, r.st)) return 1;
+    }
+    return 0;
+}
+
 // the wide forward over `pl`. rg (with `tab`, the device copy of its table): a ragged batch — token preparation through the row maps, the attention
 // one launch per kernel class over the batch table, and (rg->layout 1) the last LayerNorm's rows scattered to the frame-major output; every other
 // launch is the uniform one over the pl.N packed token rows.
 int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* segs, const float* ln_w, const float* ln_b, const egx_layer* layers,
                     int B, float* tokens_out, void* saved, int training, uint64_t seed, hipStream_t st, const WRagged* rg, const int* tab) {
     const int d = pl.d, S = pl.S, dff = pl.dff, N = (int)pl.N;
+    const WideRun r = encoder_run(cfg, pl, saved, nullptr, training, seed, st);
     // device-resident seed: one small launch advances it (training forward with advance_seed) and derives every key of this
     // call into `saved`; the kernels below read their keys from there, and so does the backward
-    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f || cfg->p_feat > 0.f);
-    if (dev_keys && derive_keys(const_cast<uint64_t*>(cfg->seed_ptr), at<uint64_t>(saved, pl.keys), 0, 64, cfg->advance_seed, st)) return 1;
-    KeyScope key_scope(dev_keys ? cat<uint64_t>(saved, pl.keys) : nullptr);
-    EGX_HIP(hipMemsetAsync(at<char>(saved, pl.zero), 0, 1024, st));
-    const void* zero = at<char>(saved, pl.zero);
+    if (r.keys && derive_keys(const_cast<uint64_t*>(cfg->seed_ptr), r.sv<uint64_t>(pl.keys), 0, 64, cfg->advance_seed, st)) return 1;
+    EGX_HIP(hipMemsetAsync(r.sv<char>(pl.zero), 0, 1024, st));
 
     // token preparation
-    float* x0 = at<float>(saved, pl.layer[0].x32);
-    bf16_t* x0_16 = at<bf16_t>(saved, pl.layer[0].x16);
+    float* x0 = r.sv<float>(pl.layer[0].x32);
+    bf16_t* x0_16 = r.sv<bf16_t>(pl.layer[0].x16);
     {   // every weight of this forward -> bf16 (W for the forward, W^T for the input gradients), one launch
         WideCastBatch cb;
         for (int i = 0; i < pl.nseg; ++i)
-            if (segs[i].proj_w && wide_cast_add(cb, segs[i].proj_w, d, segs[i].d_in, segs[i].d_in, at<bf16_t>(saved, pl.seg_w[i]), nullptr, st)) return 1;
-        auto wt = [&](size_t off) { return off ? at<bf16_t>(saved, off) : nullptr; };       // (0: the plan laid out no W^T)
+            if (segs[i].proj_w && wide_cast_add(cb, segs[i].proj_w, d, segs[i].d_in, segs[i].d_in, r.sv<bf16_t>(pl.seg_w[i]), nullptr, st)) return 1;
+        auto wt = [&](size_t off) { return off ? r.sv<bf16_t>(off) : nullptr; };       // (0: the plan laid out no W^T)
         for (int l = 0; l < pl.L; ++l) {
             const WLayer& o = pl.layer[l];
             const egx_layer& w = layers[l];
-            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, at<bf16_t>(saved, o.w_in), wt(o.w_in_t), st)) return 1;
-            if (wide_cast_add(cb, w.out_proj_w, d, d, d, at<bf16_t>(saved, o.w_o), wt(o.w_o_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin1_w, dff, d, d, at<bf16_t>(saved, o.w1), wt(o.w1_t), st)) return 1;
-            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, at<bf16_t>(saved, o.w2), wt(o.w2_t), st)) return 1;
+            if (wide_cast_add(cb, w.in_proj_w, 3 * d, d, d, r.sv<bf16_t>(o.w_in), wt(o.w_in_t), st)) return 1;
+            if (wide_cast_add(cb, w.out_proj_w, d, d, d, r.sv<bf16_t>(o.w_o), wt(o.w_o_t), st)) return 1;
+            if (wide_cast_add(cb, w.lin1_w, dff, d, d, r.sv<bf16_t>(o.w1), wt(o.w1_t), st)) return 1;
+            if (wide_cast_add(cb, w.lin2_w, d, dff, dff, r.sv<bf16_t>(o.w2), wt(o.w2_t), st)) return 1;
         }
         if (wide_cast_flush(cb, st)) return 1;
     }
@@ -241,27 +253,22 @@ int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
         const int rows = rg ? (int)rg->R[i] : B * sg.T;
         const float* pre = sg.feat;
         if (sg.proj_w) {
-            bf16_t* w16 = at<bf16_t>(saved, pl.seg_w[i]);
             const bool in_place = !rg && sg.feat_bf16 && sg.pool <= 1;
-            const bf16_t* f16 = in_place ? reinterpret_cast<const bf16_t*>(sg.feat) : at<bf16_t>(saved, pl.seg_feat16[i]);
-            float* po = at<float>(saved, pl.seg_pre[i]);
+            bf16_t* f16 = r.sv<bf16_t>(pl.seg_feat16[i]);
+            float* po = r.sv<float>(pl.seg_pre[i]);
             // ragged: the valid frames only, compacted (kept in `saved`: the operand of the projection's weight gradient)
-            if (rg && wide_gather_cast(sg.feat, sg.feat_bf16, tab + rg->gmap[i], rows, sg.d_in, at<bf16_t>(saved, pl.seg_feat16[i]), st)) return 1;
-            if (!rg && !in_place && wide_pool_cast(sg.feat, sg.feat_bf16, rows, sg.pool > 1 ? sg.pool : 1, sg.d_in, at<bf16_t>(saved, pl.seg_feat16[i]), st)) return 1;
-            WideGemmParams g;
-            g.A = f16; g.B = w16; g.M = rows; g.N = d; g.K = sg.d_in; g.lda = sg.d_in; g.ldb = sg.d_in;
-            g.Cf = po; g.ldc = d; g.bias = sg.proj_b; g.zero_page = zero;
-            Drop df = mkdrop(training, cfg->p_feat, seed, (uint32_t)i, SITE_FEAT);
-            g.drop_key = df.key; g.drop_thresh = df.thresh; g.drop_inv = df.inv;
-            if (wide_gemm_nt(g, st)) return 1;
+            if (rg && wide_gather_cast(sg.feat, sg.feat_bf16, tab + rg->gmap[i], rows, sg.d_in, f16, st)) return 1;
+            if (!rg && !in_place && wide_pool_cast(sg.feat, sg.feat_bf16, rows, sg.pool > 1 ? sg.pool : 1, sg.d_in, f16, st)) return 1;
+            if (r.nt(in_place ? reinterpret_cast<const bf16_t*>(sg.feat) : f16, r.sv<bf16_t>(pl.seg_w[i]), rows, d, sg.d_in, sg.proj_b, po, nullptr, 0,
+                     r.drop(cfg->p_feat, (uint32_t)i, SITE_FEAT), nullptr)) return 1;
             pre = po;
         }
         WideLnFwdParams lp;
         lp.x = pre; lp.w = ln_w; lp.b = ln_b; lp.eps = cfg->ln_eps;
-        lp.stats = at<float>(saved, pl.seg_stats[i]);
+        lp.stats = r.sv<float>(pl.seg_stats[i]);
         lp.y32 = x0; lp.y16 = x0_16; lp.rows = rows; lp.d = d; lp.T = sg.T; lp.S = S; lp.off = pl.seg_off[i];
         lp.add_vec = sg.add_vec; lp.pos = sg.pos; lp.pos_stride = sg.pos_stride;
-        Drop dp = mkdrop(training, cfg->p_pos, seed, 0, SITE_POS);
+        const WideDrop dp = r.drop(cfg->p_pos, 0, SITE_POS);
         lp.drop_key = dp.key; lp.drop_thresh = dp.thresh; lp.drop_inv = dp.inv;
         if (rg) {       // compacted row -> its token row (the positional dropout keys on that row, as in the uniform layout)
             lp.out_map = tab + rg->omap[i]; lp.src_map = tab + rg->gmap[i];
@@ -271,76 +278,18 @@ int encoder_fwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
 
     for (int l = 0; l < pl.L; ++l) {
         const WLayer& o = pl.layer[l];
-        const egx_layer& w = layers[l];
-        bf16_t* w_in = at<bf16_t>(saved, o.w_in); bf16_t* w_o = at<bf16_t>(saved, o.w_o);
-        bf16_t* w1 = at<bf16_t>(saved, o.w1); bf16_t* w2 = at<bf16_t>(saved, o.w2);
-        const float* x32 = cat<float>(saved, o.x32);
-        const bf16_t* x16 = cat<bf16_t>(saved, o.x16);
         const bool last = l + 1 == pl.L;
-        float* xo32 = last ? tokens_out : at<float>(saved, pl.layer[l + 1].x32);
-        bf16_t* xo16 = last ? nullptr : at<bf16_t>(saved, pl.layer[l + 1].x16);
-        {   // packed in-projection
-            WideGemmParams g;
-            g.A = x16; g.B = w_in; g.M = N; g.N = 3 * d; g.K = d; g.lda = d; g.ldb = d;
-            g.Cb = at<bf16_t>(saved, o.qkv); g.ldc = 3 * d; g.bias = w.in_proj_b; g.zero_page = zero;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {
-            WideAttnParams a;
-            a.qkv = cat<bf16_t>(saved, o.qkv); a.out = at<bf16_t>(saved, o.attn); a.lse = at<float>(saved, o.lse);
-            a.B = B; a.S = S; a.H = pl.H; a.d = d;
-            Drop da = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-            a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (rg) {
-                a.rtab = tab;
-                for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {       // one launch per attention kernel class
-                    if (!rg->ncls[c]) continue;
-                    a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
-                    if (wide_attn_ragged_fwd(a, st)) return 1;
-                }
-            } else if (wide_attn_fwd(a, st)) return 1;
-        }
-        {   // out-projection + dropout1 + residual -> res1
-            WideGemmParams g;
-            g.A = cat<bf16_t>(saved, o.attn); g.B = w_o; g.M = N; g.N = d; g.K = d; g.lda = d; g.ldb = d;
-            g.Cf = at<float>(saved, o.res1); g.ldc = d; g.bias = w.out_proj_b; g.residual = x32; g.ldr = d; g.zero_page = zero;
-            Drop d1 = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1);
-            g.drop_key = d1.key; g.drop_thresh = d1.thresh; g.drop_inv = d1.inv;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {
-            WideLnFwdParams lp;
-            lp.x = cat<float>(saved, o.res1); lp.w = w.norm1_w; lp.b = w.norm1_b; lp.eps = cfg->ln_eps;
-            lp.stats = at<float>(saved, o.stats1); lp.y32 = at<float>(saved, o.x1_32); lp.y16 = at<bf16_t>(saved, o.x1_16);
-            lp.rows = N; lp.d = d;
-            if (wide_ln_fwd(lp, st)) return 1;
-        }
-        {   // linear1 + ReLU + dropout -> hidden (bf16)
-            WideGemmParams g;
-            g.A = cat<bf16_t>(saved, o.x1_16); g.B = w1; g.M = N; g.N = dff; g.K = d; g.lda = d; g.ldb = d;
-            g.Cb = at<bf16_t>(saved, o.hid); g.ldc = dff; g.bias = w.lin1_b; g.relu = 1; g.zero_page = zero;
-            Drop dh = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN);
-            g.drop_key = dh.key; g.drop_thresh = dh.thresh; g.drop_inv = dh.inv;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {   // linear2 + dropout2 + residual -> res2
-            WideGemmParams g;
-            g.A = cat<bf16_t>(saved, o.hid); g.B = w2; g.M = N; g.N = d; g.K = dff; g.lda = dff; g.ldb = dff;
-            g.Cf = at<float>(saved, o.res2); g.ldc = d; g.bias = w.lin2_b; g.residual = cat<float>(saved, o.x1_32); g.ldr = d;
-            g.zero_page = zero;
-            Drop d2 = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2);
-            g.drop_key = d2.key; g.drop_thresh = d2.thresh; g.drop_inv = d2.inv;
-            if (wide_gemm_nt(g, st)) return 1;
-        }
-        {
-            WideLnFwdParams lp;
-            lp.x = cat<float>(saved, o.res2); lp.w = w.norm2_w; lp.b = w.norm2_b; lp.eps = cfg->ln_eps;
-            lp.stats = at<float>(saved, o.stats2); lp.y32 = xo32; lp.y16 = xo16; lp.rows = N; lp.d = d;
-            if (last && rg && rg->layout == 1) {        // the output in frame-major segment tuples
-                lp.out_map = tab + rg->outmap;
-                if (wide_ln_fwd_mapped(lp, st)) return 1;
-            } else if (wide_ln_fwd(lp, st)) return 1;
-        }
+        WideProjLn attn_out;
+        WideFfn ffn;
+        encoder_sublayers(r, pl, l, layers[l], last ? tokens_out : r.sv<float>(pl.layer[l + 1].x32), last ? nullptr : r.sv<bf16_t>(pl.layer[l + 1].x16),
+                          attn_out, ffn);
+        // packed in-projection
+        if (r.nt(r.sv<bf16_t>(o.x16), r.sv<bf16_t>(o.w_in), N, 3 * d, d, layers[l].in_proj_b, nullptr, r.sv<bf16_t>(o.qkv), 0, WideDrop(), nullptr)) return 1;
+        if (encoder_attn<false>(r, pl, l, B, rg, tab)) return 1;
+        if (wide_proj_ln_fwd(r, attn_out, (uint32_t)l, N, d)) return 1;        // out-projection + dropout1 + residual -> res1 -> LayerNorm1
+        // linear1 + ReLU + dropout -> hidden; linear2 + dropout2 + residual -> res2 -> LayerNorm2 (the last one of a ragged batch with
+        // rg->layout 1: the output in frame-major segment tuples)
+        if (wide_ffn_fwd(r, ffn, (uint32_t)l, N, d, last && rg && rg->layout == 1 ? tab + rg->outmap : nullptr)) return 1;
     }
     return 0;
 }
@@ -360,145 +309,58 @@ int encoder_bwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
                     const float* d_tokens, const void* saved, void* scratch, const egx_segment_grads* seg_grads, float* d_ln_w,
                     float* d_ln_b, const egx_layer_grads* layer_grads, int training, uint64_t seed, hipStream_t st, const WRagged* rg,
                     const int* tab) {
-    const int d = pl.d, S = pl.S, dff = pl.dff, N = (int)pl.N;
-    const void* zero = cat<char>(saved, pl.zero);
-    // device-resident seed: the forward left this step's keys in `saved`
-    const bool dev_keys = cfg->seed_ptr && training && (cfg->p_drop > 0.f || cfg->p_pos > 0.f || cfg->p_feat > 0.f);
-    KeyScope key_scope(dev_keys ? cat<uint64_t>(saved, pl.keys) : nullptr);
+    const int d = pl.d, S = pl.S, N = (int)pl.N;
+    WideRun r = encoder_run(cfg, pl, saved, scratch, training, seed, st);      // (device-resident seed: the forward left this step's keys in `saved`)
     if (cfg->zero_buf && cfg->zero_bytes) EGX_HIP(hipMemsetAsync(cfg->zero_buf, 0, cfg->zero_bytes, st));
-    float* gA = at<float>(scratch, pl.gA);
-    float* gB = at<float>(scratch, pl.gB);
-    float* dres = at<float>(scratch, pl.dres);
-    bf16_t* dy16 = at<bf16_t>(scratch, pl.dy16);
-    bf16_t* dhid16 = at<bf16_t>(scratch, pl.dhid16);
-    bf16_t* dattn16 = at<bf16_t>(scratch, pl.dattn16);
-    bf16_t* dqkv16 = at<bf16_t>(scratch, pl.dqkv16);
-    void* slabs = at<char>(scratch, pl.slabs);
-    void* lnpart = at<char>(scratch, pl.lnpart);
-    float* cspart = at<float>(scratch, pl.cspart);
+    float* gA = r.sc<float>(pl.gA);
+    float* gB = r.sc<float>(pl.gB);
+    float* dres = r.sc<float>(pl.dres);
+    bf16_t* dy16 = r.sc<bf16_t>(pl.dy16);
+    bf16_t* dattn16 = r.sc<bf16_t>(pl.dattn16);
+    bf16_t* dqkv16 = r.sc<bf16_t>(pl.dqkv16);
     const float* g = d_tokens;
 
     // weight gradients: when the split-K slabs of the whole backward are small (the d = 256 EgoT2-g encoder: 283 MB, 15
     // reductions of 8 us in 1.6 ms of work) every gradient gets a slab region of its own and ALL slab reductions run as one
     // launch at the end (-2.5 %); for larger problems that reduction reads its slabs back from HBM instead of the Infinity
-    // Cache (d = 512: 764 MB, +1.5 %; C4: 1.1 GB, +0.8 %), so they keep the reduction right behind each GEMM.
-    WideReduceBatch rb;
-    size_t slab_cur = 0;
-    const bool defer_ok = pl.slab_all_bytes > 0 && !cfg->bucket_cb;     // bucketed exchange: a layer's gradients must be final when its bucket is announced
-    // second stages of the two-stage column sums (LayerNorm / bias gradients): queued, one launch at the end (wide.h WideRowReduceBatch);
-    // each gets a partial buffer of its own out of `rowpart` (none left, or a bucketed exchange: the shared buffer and its own launch)
-    WideRowReduceBatch rrb;
-    size_t row_cur = 0;
-    const bool row_defer = pl.rowpart_bytes > 0 && !cfg->bucket_cb;
-    auto row_region = [&](size_t need) -> void* {
-        need = (need + 255) / 256 * 256;
-        if (!row_defer || row_cur + need > pl.rowpart_bytes) return nullptr;
-        void* r = at<char>(scratch, pl.rowpart) + row_cur;
-        row_cur += need;
-        return r;
-    };
-    auto ln_bwd_q = [&](WideLnBwdParams& b) -> int {
-        void* reg = row_region(wide_ln_bwd_scratch(b.rows, b.d));
-        return reg ? wide_ln_bwd(b, reg, st, &rrb) : wide_ln_bwd(b, lnpart, st);
-    };
-    auto dw_tn = [&](const bf16_t* dy, int ldy, const bf16_t* x, int ldx, float* dW, int n_out, int k_in, int tokens) -> int {
-        if (!dW) return 0;
-        WideGemmParams t;
-        t.A = dy; t.B = x; t.M = n_out; t.N = k_in; t.K = tokens; t.lda = ldy; t.ldb = ldx;
-        t.Cf = dW; t.ldc = k_in; t.accumulate = 1; t.zero_page = zero;
-        const size_t need = (wide_gemm_tn_scratch(n_out, k_in, tokens) + 255) / 256 * 256;
-        if (!defer_ok || slab_cur + need > pl.slab_all_bytes) return wide_gemm_tn(t, slabs, st);
-        void* region = at<char>(scratch, pl.slab_all) + slab_cur;
-        slab_cur += need;
-        return wide_gemm_tn(t, region, st, &rb);
-    };
+    // Cache (d = 512: 764 MB, +1.5 %; C4: 1.1 GB, +0.8 %), so they keep the reduction right behind each GEMM on the shared slab.
+    // The second stages of the two-stage column sums (LayerNorm / bias gradients) are queued likewise, each with a partial buffer of its
+    // own out of `rowpart` (none left: the shared buffer and its own launch). A bucketed exchange defers neither: a layer's gradients
+    // must be final when its bucket is announced.
+    WideLedger led;
+    led.st = led.tn_stream = st; led.zero = r.zero;
+    led.slab = r.sc<char>(pl.slab_all); led.slab_bytes = cfg->bucket_cb ? 0 : pl.slab_all_bytes;
+    led.rows = r.sc<char>(pl.rowpart); led.rows_bytes = cfg->bucket_cb ? 0 : pl.rowpart_bytes;
+    led.lnpart = r.sc<char>(pl.lnpart); led.cspart = r.sc<float>(pl.cspart); led.shared_slab = r.sc<char>(pl.slabs);
+    r.led = &led;
+    auto no_fork = []() { return 0; };
 
     for (int l = pl.L - 1; l >= 0; --l) {
         const WLayer& o = pl.layer[l];
-        const egx_layer& w = layers[l];
         const egx_layer_grads& gw = layer_grads[l];
-        {   // LayerNorm2 backward: dres = d(res2), dy16 = dropout2-mask .* d(res2)
-            WideLnBwdParams b;
-            b.dy = g; b.pre = cat<float>(saved, o.res2); b.stats = cat<float>(saved, o.stats2); b.w = w.norm2_w;
-            b.dx32 = dres; b.dx16 = dy16; b.rows = N; b.d = d;
-            Drop d2 = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES2);
-            b.out_key = d2.key; b.out_thresh = d2.thresh; b.out_inv = d2.inv;
-            b.dw = gw.norm2_w; b.db = gw.norm2_b; b.dbias = gw.lin2_b;
-            if (rg && rg->layout == 1 && l == pl.L - 1) {       // d_tokens arrives in the frame-major layout: read back through the same map
-                b.dy_map = tab + rg->outmap;
-                if (wide_ln_bwd_mapped(b, lnpart, st)) return 1;
-            } else if (ln_bwd_q(b)) return 1;
-        }
-        if (dw_tn(dy16, d, cat<bf16_t>(saved, o.hid), dff, gw.lin2_w, d, dff, N)) return 1;
-        {   // d(hidden) = (dy W2) .* alive / keep, column sums -> d(lin1_b)
-            WideGemmParams q;
-            q.A = dy16; q.B = cat<bf16_t>(saved, o.w2_t); q.M = N; q.N = dff; q.K = d; q.lda = d; q.ldb = d;
-            q.Cb = dhid16; q.ldc = dff; q.mask = cat<bf16_t>(saved, o.hid); q.ldm = dff; q.zero_page = zero;
-            q.mask_scale = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_FFN).inv;
-            float* cs_reg = gw.lin1_b ? (float*)row_region((size_t)wide_gemm_nt_colsum_rows(N, dff) * dff * 4) : nullptr;
-            q.colsum = gw.lin1_b ? (cs_reg ? cs_reg : cspart) : nullptr;
-            if (wide_gemm_nt(q, st)) return 1;
-            if (gw.lin1_b && wide_reduce_rows(q.colsum, wide_gemm_nt_colsum_rows(N, dff), dff, gw.lin1_b, st, cs_reg ? &rrb : nullptr)) return 1;
-        }
-        if (dw_tn(dhid16, dff, cat<bf16_t>(saved, o.x1_16), d, gw.lin1_w, dff, d, N)) return 1;
+        WideProjLn attn_out;
+        WideFfn ffn;
+        encoder_sublayers(r, pl, l, layers[l], nullptr, nullptr, attn_out, ffn);
+        // LayerNorm2 and the FFN: g1 = d(x1). d_tokens of a ragged batch in the frame-major layout is read back through the forward's map
         float* g1 = (g == gA) ? gB : gA;
-        {   // d(x1) = d(hidden) W1 + d(res2)
-            WideGemmParams q;
-            q.A = dhid16; q.B = cat<bf16_t>(saved, o.w1_t); q.M = N; q.N = d; q.K = dff; q.lda = dff; q.ldb = dff;
-            q.Cf = g1; q.ldc = d; q.residual = dres; q.ldr = d; q.zero_page = zero;
-            if (wide_gemm_nt(q, st)) return 1;
-        }
-        {   // LayerNorm1 backward: dres = d(res1), dy16 = dropout1-mask .* d(res1)
-            WideLnBwdParams b;
-            b.dy = g1; b.pre = cat<float>(saved, o.res1); b.stats = cat<float>(saved, o.stats1); b.w = w.norm1_w;
-            b.dx32 = dres; b.dx16 = dy16; b.rows = N; b.d = d;
-            Drop d1 = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_RES1);
-            b.out_key = d1.key; b.out_thresh = d1.thresh; b.out_inv = d1.inv;
-            b.dw = gw.norm1_w; b.db = gw.norm1_b; b.dbias = gw.out_proj_b;
-            if (ln_bwd_q(b)) return 1;
-        }
-        if (dw_tn(dy16, d, cat<bf16_t>(saved, o.attn), d, gw.out_proj_w, d, d, N)) return 1;
-        {   // d(attention output) = dy W_o
-            WideGemmParams q;
-            q.A = dy16; q.B = cat<bf16_t>(saved, o.w_o_t); q.M = N; q.N = d; q.K = d; q.lda = d; q.ldb = d;
-            q.Cb = dattn16; q.ldc = d; q.zero_page = zero;
-            if (wide_gemm_nt(q, st)) return 1;
-        }
-        {
-            WideAttnParams a;
-            a.qkv = cat<bf16_t>(saved, o.qkv); a.lse = const_cast<float*>(cat<float>(saved, o.lse));
-            a.out = const_cast<bf16_t*>(cat<bf16_t>(saved, o.attn)); a.delta = at<float>(scratch, pl.adelta);
-            a.d_out = dattn16; a.d_qkv = dqkv16; a.B = B; a.S = S; a.H = pl.H; a.d = d;
-            Drop da = mkdrop(training, cfg->p_drop, seed, (uint32_t)l, SITE_ATTN);
-            a.drop_key = da.key; a.drop_thresh = da.thresh; a.drop_inv = da.inv;
-            if (rg) {
-                a.rtab = tab;
-                for (int c = 0, first = 0; c < 3; first += rg->ncls[c], ++c) {
-                    if (!rg->ncls[c]) continue;
-                    a.B = rg->ncls[c]; a.S = rg->Smax[c]; a.clips = tab + rg->cls0 + first;
-                    if (wide_attn_ragged_bwd(a, st)) return 1;
-                }
-            } else if (wide_attn_bwd(a, st)) return 1;
-        }
-        if (gw.in_proj_b) {
-            void* reg = row_region(wide_colsum_scratch(N, 3 * d));
-            if (wide_colsum_bf16(dqkv16, N, 3 * d, 3 * d, gw.in_proj_b, reg ? reg : (void*)cspart, st, reg ? &rrb : nullptr)) return 1;
-        }
-        if (dw_tn(dqkv16, 3 * d, cat<bf16_t>(saved, o.x16), d, gw.in_proj_w, 3 * d, d, N)) return 1;
+        if (wide_ffn_bwd(r, ffn, {gw.lin1_w, gw.lin1_b, {gw.lin2_w, gw.lin2_b, gw.norm2_w, gw.norm2_b}}, (uint32_t)l, N, d, g, dres, dy16,
+                         r.sc<bf16_t>(pl.dhid16), g1, no_fork, rg && rg->layout == 1 && l == pl.L - 1 ? tab + rg->outmap : nullptr)) return 1;
+        // LayerNorm1 and the out-projection: dres = d(res1), dy16 = dropout1-mask .* d(res1); d(attention output) = dy W_o
+        if (wide_proj_ln_bwd(r, attn_out, {gw.out_proj_w, gw.out_proj_b, gw.norm1_w, gw.norm1_b}, (uint32_t)l, N, d, g1, dres, dy16, no_fork)) return 1;
+        if (r.nt_bwd(dy16, attn_out.w_t, N, d, d, nullptr, dattn16, nullptr)) return 1;
+        if (encoder_attn<true>(r, pl, l, B, rg, tab)) return 1;
+        if (gw.in_proj_b && led.colsum(dqkv16, N, 3 * d, gw.in_proj_b, led.cspart, st)) return 1;
+        if (led.dw_tn(dqkv16, r.sv<bf16_t>(o.x16), gw.in_proj_w, 3 * d, d, N)) return 1;
+        // d(layer input) = dqkv W_in + d(res1)
         float* g0 = (g1 == gA) ? gB : gA;
-        {   // d(layer input) = dqkv W_in + d(res1)
-            WideGemmParams q;
-            q.A = dqkv16; q.B = cat<bf16_t>(saved, o.w_in_t); q.M = N; q.N = d; q.K = 3 * d; q.lda = 3 * d; q.ldb = 3 * d;
-            q.Cf = g0; q.ldc = d; q.residual = dres; q.ldr = d; q.zero_page = zero;
-            if (wide_gemm_nt(q, st)) return 1;
-        }
+        if (r.nt_bwd(dqkv16, r.sv<bf16_t>(o.w_in_t), N, d, 3 * d, g0, nullptr, dres)) return 1;
         g = g0;
         if (cfg->bucket_cb) cfg->bucket_cb(cfg->bucket_user, pl.L - 1 - l);     // every gradient of layer l is enqueued
     }
 
     // token preparation backward
-    Drop dp = mkdrop(training, cfg->p_pos, seed, 0, SITE_POS);
-    bf16_t* dseg16 = at<bf16_t>(scratch, pl.dseg16);
+    const WideDrop dp = r.drop(cfg->p_pos, 0, SITE_POS);
+    bf16_t* dseg16 = r.sc<bf16_t>(pl.dseg16);
     for (int i = 0; i < pl.nseg; ++i) {
         const egx_segment& sg = segs[i];
         egx_segment_grads sgr;
@@ -509,28 +371,27 @@ int encoder_bwd_run(const egx_config* cfg, const WPlan& pl, const egx_segment* s
         EGX_CHECK(!sgr.feat || !sg.proj_w, "wide path: gradients into PROJECTED features are not supported (use impl = generic)");
         const int rows = rg ? (int)rg->R[i] : B * sg.T;
         EGX_CHECK(!rg || !sgr.pos, "ragged encode: a learned positional table gets no gradient from the ragged kernels");
-        if (sgr.pos && wide_pos_grad(g, B, S, pl.seg_off[i], sg.T, d, sgr.pos, sg.pos_stride, dp.key, dp.thresh, dp.inv, cspart, st)) return 1;
+        if (sgr.pos && wide_pos_grad(g, B, S, pl.seg_off[i], sg.T, d, sgr.pos, sg.pos_stride, dp.key, dp.thresh, dp.inv, led.cspart, st)) return 1;
         const bool need = (sg.proj_w && (sgr.proj_w || sgr.proj_b)) || d_ln_w || d_ln_b || sgr.add_vec || sgr.feat;
         if (!need) continue;
         WideLnBwdParams b;
-        b.dy = g; b.pre = sg.proj_w ? cat<float>(saved, pl.seg_pre[i]) : sg.feat; b.stats = cat<float>(saved, pl.seg_stats[i]);
+        b.dy = g; b.pre = sg.proj_w ? r.sv<float>(pl.seg_pre[i]) : sg.feat; b.stats = r.sv<float>(pl.seg_stats[i]);
         b.w = ln_w; b.dx16 = sg.proj_w ? dseg16 : nullptr; b.dx32 = sg.proj_w ? nullptr : sgr.feat; b.rows = rows; b.d = d; b.T = sg.T; b.S = S; b.off = pl.seg_off[i];
         b.drop_key = dp.key; b.drop_thresh = dp.thresh; b.drop_inv = dp.inv;
         if (sg.proj_w) {
-            Drop df = mkdrop(training, cfg->p_feat, seed, (uint32_t)i, SITE_FEAT);
+            const WideDrop df = r.drop(cfg->p_feat, (uint32_t)i, SITE_FEAT);
             b.out_key = df.key; b.out_thresh = df.thresh; b.out_inv = df.inv;
         }
         b.dw = d_ln_w; b.db = d_ln_b; b.dadd = sgr.add_vec; b.dbias = sg.proj_w ? sgr.proj_b : nullptr;
         // (not queued: every segment adds into the SAME shared-LayerNorm gradient; queued reductions run concurrently and must have targets of their own)
         if (rg) {       // compacted row r reads the gradient of its token row (and that row's positional mask)
             b.dy_map = tab + rg->omap[i];
-            if (wide_ln_bwd_mapped(b, lnpart, st)) return 1;
-        } else if (wide_ln_bwd(b, lnpart, st)) return 1;
-        const bf16_t* f16 = (!rg && sg.feat_bf16 && sg.pool <= 1) ? reinterpret_cast<const bf16_t*>(sg.feat) : cat<bf16_t>(saved, pl.seg_feat16[i]);
-        if (sg.proj_w && dw_tn(dseg16, d, f16, sg.d_in, sgr.proj_w, d, sg.d_in, rows)) return 1;
+            if (wide_ln_bwd_mapped(b, led.lnpart, st)) return 1;
+        } else if (wide_ln_bwd(b, led.lnpart, st)) return 1;
+        const bf16_t* f16 = (!rg && sg.feat_bf16 && sg.pool <= 1) ? reinterpret_cast<const bf16_t*>(sg.feat) : r.sv<bf16_t>(pl.seg_feat16[i]);
+        if (sg.proj_w && led.dw_tn(dseg16, f16, sgr.proj_w, d, sg.d_in, rows)) return 1;
     }
-    if (wide_row_reduce_flush(rrb, st)) return 1;
-    return wide_reduce_flush(rb, st);
+    return led.flush();
 }
 }  // namespace
 
@@ -613,7 +474,7 @@ int ragged_encode_plan(const egx_config* cfg, const egx_segment* segs, int B, co
                 rp.tab[rp.omap[k] + r] = rec[WRG_TOK0] + rec[WRG_OFF + k] + t;
             }
         }
-        rp.Rmax = smax(rp.Rmax, rp.R[k]);
+        rp.Rmax = size_max(rp.Rmax, rp.R[k]);
     }
     if (out_layout == 1) {      // token (clip b, segment k, frame t) -> row K (F0_b + t) + k, F0_b = frames of the clips before b
         rp.outmap = rp.tab.size();
@@ -640,7 +501,7 @@ int ragged_encode_fwd(const egx_config* cfg, const egx_segment* segs, const int*
     hipStream_t st = (hipStream_t)stream;
     // the batch table into `saved` (a training backward reads it there), stream-ordered in the arguments of upload launches: a captured hipGraph
     // would replay THIS call's lengths for every batch, so the call is not meant for capture
-    int* tab = (int*)((char*)saved + pl.tab);
+    int* tab = at<int>(saved, pl.tab);
     if (upload_words(tab, rp.tab.data(), rp.tab.size(), st)) return 1;
     return encoder_fwd_run(cfg, pl, segs, ln_w, ln_b, layers, B, tokens_out, saved, training, seed, st, &rp, tab);
 }
@@ -700,7 +561,7 @@ int egx_ragged_encode_bwd(const egx_config* cfg, const egx_segment* segs, const 
     make_wplan(cfg, segs, B, pl, &rp);
     // (the host copy of the table rebuilt from the same lengths gives the offsets; the device copy is the forward's)
     return encoder_bwd_run(cfg, pl, segs, ln_w, layers, B, d_tokens, saved, scratch, seg_grads, d_ln_w, d_ln_b, layer_grads, training, seed,
-                           (hipStream_t)stream, &rp, (const int*)((const char*)saved + pl.tab));
+                           (hipStream_t)stream, &rp, cat<int>(saved, pl.tab));
 }
 
 }  // extern "C"

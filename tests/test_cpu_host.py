@@ -71,6 +71,27 @@ def test_d128_workspace_sizes_match_the_committed_table(egx_lib):
                          "(python tests/host_paths_d128_sizes.py <lib.so> <commit>); a refactor changes none")
 
 
+def test_wide_workspace_sizes_match_the_committed_table(egx_lib):
+    """The workspace sizes of the wide bf16 encoder, the fused decoder and the cached step, at the smallest shapes of every branch of their
+    plans (tests/host_paths_wide_sizes.py), equal tests/wide_workspace_sizes.json, which was written from a build of the commit its first
+    key names: a refactor of the wide host drivers must leave every size (and the refusals recorded beside them) alone."""
+    import json
+    from egot2_amd import _lib
+    from tests import host_paths, host_paths_wide_sizes
+    table = json.load(open(os.path.join(ROOT, "tests", "wide_workspace_sizes.json")))
+    assert list(table)[0] == "generated_from" and table["generated_from"]
+    got = host_paths_wide_sizes.sizes(host_paths.bind(_lib.LIB_PATH))
+    want = table["sizes"]
+    assert len(want) >= 1400 and set(got) == set(want), sorted(set(got) ^ set(want))
+    assert want["enc slab_all on both sides of its cut-off"] == [1], "the table's encoder shapes no longer straddle the 400 MB cut-off"
+    for prefix in ("enc ", "ragged_enc ", "dec ", "step "):
+        assert any(v[0] == 0 and v[1] > 0 for k, v in want.items() if k.startswith(prefix)), f"the table holds no accepted '{prefix}' plan"
+    changed = {k: (want[k], got[k]) for k in want if got[k] != want[k]}
+    assert not changed, (f"{len(changed)} wide workspace sizes differ from tests/wide_workspace_sizes.json (table, library): {sorted(changed.items())[:8]}. "
+                         "A changed size is an intended layout change only if the table is regenerated in the same commit "
+                         "(python tests/host_paths_wide_sizes.py <lib.so> <commit>); a refactor changes none")
+
+
 def test_host_code_under_address_and_ub_sanitizers():
     """SURVEY.md §5 / VERDICT r4 item 9d: the same sweep against a build whose C++ orchestration (encoder.hip, fused_host.hip,
     wide_host.hip, wide_decoder.hip, comm.hip) is compiled with AddressSanitizer + UBSan on the HOST side (egot2_amd/build.py build_sanitized;

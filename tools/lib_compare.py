@@ -33,6 +33,10 @@ Cases (d = 128, three segments of d_in 256, d_ff 2048, 4 heads; f32s and bf16 ea
     L 2, p 0.1, head + CE, feature gradients, eager; the status word is recorded too
   t the per-length-group fallback on LENS with compute "f32", which the ragged kernels refuse (once, outside the f32s / bf16 loop): inference
     with head and head-less; training, L 2, p 0.1, head + CE, feature gradients, deterministic (as case n)
+Case on the wide encoder alone (functional.encoder, bf16, eager, forward + backward), for what the EgoT2-g cases do not reach:
+  v an HOI-style stack, d 256, 8 heads (head dim 32), L 2, d_ff 256, B 3, four segments of T 5: projected fp32 with p_feat 0.1, projected with
+    pool 2, projected bf16 features used in place, identity with a feature gradient; learned positional table and task rows with their
+    gradients; p_drop = p_pos = 0.1
 Cases on the EgoT2-g HHI model (d 256, 4 heads, L 3 + 3, bf16, seeded weights; B 4, T_pad 16, lengths LENS, 2 target tokens):
   j uniform encode_features + decode, p 0.1, forward + backward with d_memory; again under a recording functional.bucket_hook (its (lo, hi) calls compared)
   k encode_features_ragged + decode_ragged, p 0.1, with d_memory: 'ttm' (packed rows) and 'asd' (frame-major tuples, decode() on S = 3)
@@ -223,6 +227,34 @@ def gpu_child(path):
     m = model_of(TTM, 2, 0.1, "f32", 208, det=True)
     step("t_train_f32", m, lambda: m.forward_features_ragged(*f16g, lengths=lens, target=tgt4, class_weight=w), feats=f16g)
     assert F_egx.last_encoder_impl() == "grouped", F_egx.last_encoder_impl()
+
+    # an HOI-style stack on the wide encoder, through functional.encoder: what the EgoT2-g cases below do not reach
+    class WideStack(nn.Module):
+        """d 256, 8 heads, L 2, d_ff 256; four segments of 5 tokens: projected fp32 (cast copy, p_feat), projected with pool 2, projected
+        bf16 (used in place), identity (its features take a gradient); a learned positional table and task-embedding rows"""
+
+        def __init__(self, seed, d=256, dff=256, L=2, T=5):
+            super().__init__()
+            g = torch.Generator().manual_seed(seed)
+            rnd = lambda *s: nn.Parameter(torch.randn(*s, generator=g) * 0.05)       # noqa: E731
+            self.dims = [256, 128, 256, d]
+            self.spec = F_egx.EncoderSpec(d, 8, dff, L, [F_egx.SegmentSpec(T, k, i < 3, add_row=i, pos_row0=i * T, pool=2 if i == 1 else 1)
+                                                          for i, k in enumerate(self.dims)],
+                                          compute="bf16", p_drop=0.1, p_pos=0.1, p_feat=0.1, training=True, seed=0x5EED0000 + seed)
+            self.task_embed, self.pos, self.ln_w, self.ln_b = rnd(1, 4, d), rnd(4 * T, d), nn.Parameter(torch.ones(d)), rnd(d)
+            self.proj = nn.ParameterList([q for k in self.dims[:3] for q in (rnd(d, k), rnd(d))])
+            shapes = [(3 * d, d), (3 * d,), (d, d), (d,), (dff, d), (dff,), (d, dff), (d,), (d,), (d,), (d,), (d,)]
+            self.layers = nn.ParameterList([rnd(*s) for _ in range(L) for s in shapes])
+
+        def forward(self, feats):
+            return F_egx.encoder(self.spec, feats, self.task_embed, self.pos, self.ln_w, self.ln_b, list(self.proj), list(self.layers))
+
+    m = WideStack(41).to(cuda)
+    rng = np.random.default_rng(42)
+    fv = [torch.from_numpy(rng.standard_normal((3, 5 * (2 if i == 1 else 1), k), dtype=np.float32)).to(cuda) for i, k in enumerate(m.dims)]
+    fv[2], fv[3] = fv[2].to(torch.bfloat16), fv[3].requires_grad_(True)
+    step("v", m, lambda: m(fv), feats=fv)
+    assert F_egx.last_encoder_impl() == "wide" and m.pos.grad is not None and fv[3].grad is not None, F_egx.last_encoder_impl()
 
     # EgoT2-g HHI model: the wide encoder and the fused decoder, uniform and ragged
     def g_model(seed, p=0.1, compute="bf16"):
