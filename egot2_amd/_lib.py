@@ -129,6 +129,14 @@ class WideGemmArgs(C.Structure):
                 ("mask_scale", C.c_float), ("colsum", _fp), ("accumulate", C.c_int), ("tn_queue", C.c_int), ("tn_defer", C.c_int), ("scratch", _fp)]
 
 
+class DecAttnArgs(C.Structure):
+    """egx_dec_attn_args (egx_decoder_attention_fwd / _bwd): one launch of the sequence decoder's attention."""
+    _fields_ = [("q", _fp), ("k", _fp), ("v", _fp), ("ldq", C.c_int), ("ldk", C.c_int), ("ldv", C.c_int), ("operands_bf16", C.c_int),
+                ("o", _fp), ("ldo", C.c_int), ("d_o", _fp), ("dq", _fp), ("dk", _fp), ("dv", _fp),
+                ("B", C.c_int), ("H", C.c_int), ("dh", C.c_int), ("Sq", C.c_int), ("Sk", C.c_int), ("causal", C.c_int),
+                ("p_drop", C.c_float), ("seed", C.c_uint64), ("layer", C.c_uint32), ("site", C.c_uint32), ("stream", _fp)]
+
+
 class WideLnFwdArgs(C.Structure):
     """egx_wide_ln_fwd_args (egx_wide_layernorm_fwd)."""
     _fields_ = [("x", _fp), ("w", _fp), ("b", _fp), ("eps", C.c_float), ("stats", _fp), ("y32", _fp), ("y16", _fp), ("rows", C.c_int), ("d", C.c_int),
@@ -299,6 +307,9 @@ SIGNATURES = {
                                        C.c_float, C.c_int, C.c_float, _fp]),
     "egx_sgd_step": (C.c_int, [_fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                C.c_float, _fp]),
+    # ABI v29 additions: the unit hooks of the sequence decoder's attention (head dim 32 / 64 and 256 / 512)
+    "egx_decoder_attention_fwd": (C.c_int, [C.POINTER(DecAttnArgs)]),
+    "egx_decoder_attention_bwd": (C.c_int, [C.POINTER(DecAttnArgs)]),
     # ABI v28 additions: the gradient norm / clip / non-finite guard of the captured step (bufs and ns are host arrays; guard a device address)
     "egx_grad_norm_scratch_bytes": (C.c_size_t, [C.POINTER(C.c_size_t), C.c_int]),
     "egx_grad_norm": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, _fp, C.c_size_t, C.POINTER(GradNormCfg), _fp, _fp]),

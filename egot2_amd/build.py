@@ -12,8 +12,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libegot2x.so")
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "ffn_cut.hip", "tiled_attn.hip", "ragged_table.hip", "stage_read.hip", "feature_sink.hip", "train.hip", "grad_guard.hip", "seg_ce.hip", "lta_val.hip", "keyframe.hip", "seq_ce.hip", "segment_ap.hip", "view_ensemble.hip", "decoder.hip", "target_attn.hip", "wide_gemm.hip", "wide_attn.hip", "wide_attn_bighead.hip", "wide_rows.hip", "wide_host.hip", "wide_decoder.hip", "enc_attn_weights.hip", "comm.hip", "fused_host.hip", "encoder.hip"]
-HEADERS = ["common.h", "kernels.h", "fused.h", "fused_dev.h", "wide.h", "wide_host.h", "wide_run.h", "fused_host.h", "enc_attn_weights.h", os.path.join("..", "..", "include", "egot2x.h")]
+SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "ffn_cut.hip", "tiled_attn.hip", "ragged_table.hip", "stage_read.hip", "feature_sink.hip", "train.hip", "grad_guard.hip", "seg_ce.hip", "lta_val.hip", "keyframe.hip", "seq_ce.hip", "segment_ap.hip", "view_ensemble.hip", "decoder.hip", "target_attn.hip", "wide_gemm.hip", "wide_attn.hip", "wide_attn_bighead.hip", "wide_rows.hip", "wide_host.hip", "wide_decoder.hip", "wide_decoder_bighead.hip", "enc_attn_weights.hip", "comm.hip", "fused_host.hip", "encoder.hip"]
+HEADERS = ["common.h", "kernels.h", "fused.h", "fused_dev.h", "wide.h", "wide_host.h", "wide_run.h", "dec_attn.h", "fused_host.h", "enc_attn_weights.h", os.path.join("..", "..", "include", "egot2x.h")]
 EXTRA = os.environ.get("EGX_CXXFLAGS", "").split()
 FLAGS = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 

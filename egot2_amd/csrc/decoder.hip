@@ -260,7 +260,8 @@ static int small_attention_check(const SmallAttnParams& p) {
     EGX_CHECK(p.B >= 1 && p.H >= 1, "small_attention: B=%d H=%d", p.B, p.H);
     EGX_CHECK(p.Sq >= 1 && p.Sq <= SA_MAXQ, "small_attention: Sq=%d outside 1..%d (target tokens)", p.Sq, SA_MAXQ);
     EGX_CHECK(p.Sk >= 1 && p.Sk <= SAL_MAXK, "small_attention: Sk=%d outside 1..%d", p.Sk, SAL_MAXK);
-    EGX_CHECK(p.dh >= 1 && p.dh <= SA_MAXDH, "small_attention: head dim %d outside 1..%d", p.dh, SA_MAXDH);
+    EGX_CHECK(p.dh >= 1 && p.dh <= SA_MAXDH, "small_attention: head dim %d outside 1..%d%s", p.dh, SA_MAXDH,
+              p.dh == 256 || p.dh == 512 ? " (compute = bf16 serves head dim 256 / 512: the fused decoder, S <= 16 memory rows)" : "");
     EGX_CHECK(!p.causal || p.Sq == p.Sk, "small_attention: the causal mask needs Sq == Sk");
     return 0;
 }

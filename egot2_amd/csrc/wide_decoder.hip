@@ -9,7 +9,8 @@
 // residual, column sums), LayerNorms through the row kernels with bf16 side outputs, the two tiny attentions through a
 // register-resident kernel (one wave per (clip, head)), every gradient accumulates into ONE caller-provided flat buffer
 // that the first memset zeroes, and the split-K slabs of all weight gradients are summed by one launch at the end.
-// Supported: compute = bf16, d_model a multiple of 128 in [256, 1024], head dim 32 or 64, sy <= 8, S <= 1024 (one wave per (clip, head) up to 64 memory tokens, a chunked four-wave kernel beyond); anything else
+// Supported: compute = bf16, d_model a multiple of 128 in [256, 1024], head dim 32 or 64, sy <= 8, S <= 1024 (one wave per (clip, head) up to 64 memory tokens, a chunked four-wave kernel beyond),
+// or head dim 256 / 512 with d_model <= 2048, sy <= 8, S <= 16 (wide_decoder_bighead.hip; the cached step's big-head self-attention below); anything else
 // stays on the composed path (egot2_amd/decoder.py).
 #include <string.h>
 #include <mutex>
@@ -21,67 +22,16 @@
 #include "kernels.h"
 #include "wide.h"
 #include "wide_run.h"
+#include "dec_attn.h"
 #include "fused.h"      // (upload_words: the ragged batch table)
 
 namespace egx {
 
 namespace {
 
-constexpr int DA_MAXQ = 8, DA_MAXK = 64;
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float bf1(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-
-struct DecAttnParams {
-    const void* q; const void* k; const void* v; int ldq, ldk, ldv;           // rows b * Sq + i / b * Sk + j; head h at columns h * DH
-    bf16_t* o; int ldo;                                                        // (q / k / v and their gradients: bf16, or fp32 with F32 = true)
-    const bf16_t* d_o; void* dq; void* dk; void* dv;                           // backward (same strides as o / q / k / v)
-    int B, H, Sq, Sk, causal;
-    float scale;
-    uint64_t drop_key; uint32_t drop_thresh; float drop_inv;
-    // ragged memories (dec_attn_ragged_train, RAGGED kernels): the B clips of `clips`; clip c's Sk_c = mtab[2c + 1] keys are rows [mtab[2c], + Sk_c)
-    // of k / v, its query / output rows c * Sq + i. Sk = the longest memory of the launch.
-    const int* mtab; const int* clips;
-};
-
 // One wave per (clip, head), four per workgroup. Lane j holds key row j (and, in the backward, value row j) in registers,
 // lane c holds column c of V (forward) / of K and dO (backward); the Sq <= 8 query rows and the probabilities go through a
 // per-wave LDS slice as broadcast reads. Probabilities are recomputed in the backward (nothing saved).
-// 8 consecutive elements of a q / k / v row as fp32
-template <bool F32>
-__device__ __forceinline__ void load8(const void* base, size_t idx, float (&o)[8]) {
-    if constexpr (F32) {
-        const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + idx);
-        const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + idx + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    } else {
-        const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + idx);
-        o[0] = bf_lo(u.x); o[1] = bf_hi(u.x); o[2] = bf_lo(u.y); o[3] = bf_hi(u.y);
-        o[4] = bf_lo(u.z); o[5] = bf_hi(u.z); o[6] = bf_lo(u.w); o[7] = bf_hi(u.w);
-    }
-}
-template <bool F32>
-__device__ __forceinline__ float load1(const void* base, size_t idx) {
-    if constexpr (F32) return reinterpret_cast<const float*>(base)[idx];
-    else return bf1(reinterpret_cast<const bf16_t*>(base)[idx]);
-}
-template <bool F32>
-__device__ __forceinline__ void store1(void* base, size_t idx, float v) {
-    if constexpr (F32) reinterpret_cast<float*>(base)[idx] = v;
-    else reinterpret_cast<bf16_t*>(base)[idx] = f2bf(v);
-}
-template <bool F32>
-__device__ __forceinline__ void store8(void* base, size_t idx, const float (&a)[8]) {
-    if constexpr (F32) {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + idx) = make_float4(a[0], a[1], a[2], a[3]);
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + idx + 4) = make_float4(a[4], a[5], a[6], a[7]);
-    } else {
-        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(base) + idx) =
-            make_uint4(pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(a[4], a[5]), pack_bf16x2(a[6], a[7]));
-    }
-}
-
 // RAGGED (ragged memories, bf16 operands): wave (i, h) serves clip p.clips[i] with its own memory rows [mtab[2c], + mtab[2c + 1]); its query / output
 // rows and its dropout rows are those of the clip's batch position, as in a uniform batch. A flag on the kernel template, so that the uniform
 // kernels keep their code: see the note at wide_attn_fwd_kernel (wide_attn.hip).
@@ -382,6 +332,7 @@ int dec_attn_long(const DecAttnParams& p, hipStream_t st) {
 template <bool BWD>
 int dec_attn(DecAttnParams p, int dh, bool f32, hipStream_t st) {
     p.scale = 1.f / sqrtf((float)dh);
+    if (dec_attn_bighead_dim(dh)) return dec_attn_bighead(p, dh, f32, BWD, "decoder attention", st);       // (wide_decoder_bighead.hip)
     if (p.Sk > DA_MAXK) {
         EGX_CHECK(!f32 && !p.causal && (dh == 32 || dh == 64), "decoder attention: a memory of %d tokens needs bf16 operands and head dim 32 / 64", p.Sk);
         return dh == 64 ? dec_attn_long<64, BWD, false>(p, st) : dec_attn_long<32, BWD, false>(p, st);
@@ -630,12 +581,19 @@ struct DPlan {
 int make_dplan(const egx_dec_config* c, int B, DPlan& pl, size_t mem_rows = 0) {
     EGX_CHECK(c, "null decoder config");
     EGX_CHECK(c->compute == EGX_BF16, "the fused decoder runs compute = bf16 (the composed path serves the other modes)");
-    EGX_CHECK(c->d_model >= 256 && c->d_model <= 1024 && c->d_model % 128 == 0, "fused decoder: d_model = %d (multiples of 128 in [256, 1024])", c->d_model);
-    EGX_CHECK(c->n_heads > 0 && c->d_model % c->n_heads == 0 && (c->d_model / c->n_heads == 32 || c->d_model / c->n_heads == 64),
-              "fused decoder: head dim %d (32 or 64)", c->n_heads > 0 ? c->d_model / c->n_heads : 0);
+    // head dim 32 / 64: d_model <= 1024, S <= 1024 (dec_attn_kernel, dec_attn_long_kernel); head dim 256 / 512: d_model <= 2048, S <= 16
+    // (wide_decoder_bighead.hip)
+    const int dh_ = c->n_heads > 0 && c->d_model % c->n_heads == 0 ? c->d_model / c->n_heads : 0;
+    const bool big = dec_attn_bighead_dim(dh_);
+    EGX_CHECK(c->d_model >= 256 && c->d_model <= (big ? 2048 : 1024) && c->d_model % 128 == 0,
+              "fused decoder: d_model = %d (multiples of 128 in [256, 1024]; up to 2048 with head dim 256 / 512)", c->d_model);
+    EGX_CHECK(dh_ == 32 || dh_ == 64 || big, "fused decoder: head dim %d (32 or 64; 256 or 512 with S <= %d)", c->n_heads > 0 ? c->d_model / c->n_heads : 0,
+              DA_BIGHEAD_MAXK);
     EGX_CHECK(c->d_ff >= 128 && c->d_ff % 128 == 0, "fused decoder: d_ff = %d (multiples of 128)", c->d_ff);
     EGX_CHECK(c->n_layers >= 1 && c->n_layers <= 16, "fused decoder: %d layers (1..16)", c->n_layers);
     EGX_CHECK(c->sy >= 1 && c->sy <= DA_MAXQ && c->S >= 1 && c->S <= DAL_MAXK, "fused decoder: sy = %d (1..%d), S = %d (1..%d)", c->sy, DA_MAXQ, c->S, DAL_MAXK);
+    EGX_CHECK(!big || c->S <= DA_BIGHEAD_MAXK, "fused decoder: head dim 256 / 512 serves S <= %d memory rows (got S=%d, head dim %d)", DA_BIGHEAD_MAXK,
+              c->S, dh_);
     EGX_CHECK(c->vocab >= 1 && B >= 1, "fused decoder: vocab = %d, B = %d", c->vocab, B);
     memset(&pl, 0, sizeof(pl));
     pl.B = B; pl.sy = c->sy; pl.S = c->S; pl.d = c->d_model; pl.H = c->n_heads; pl.dff = c->d_ff; pl.L = c->n_layers; pl.V = c->vocab;
@@ -966,6 +924,9 @@ int decoder_ragged_plan(const egx_dec_config* cfg, int B, const int* mem_lengths
                         size_t& off_tab, size_t& bytes, bool train = false) {
     EGX_CHECK(cfg && mem_lengths, "egx_decoder_ragged: null argument");
     EGX_CHECK(B >= 1 && B <= (1 << 20), "egx_decoder_ragged: B=%d clips (1 .. %d)", B, 1 << 20);
+    EGX_CHECK(!(cfg->n_heads > 0 && cfg->d_model % cfg->n_heads == 0 && dec_attn_bighead_dim(cfg->d_model / cfg->n_heads)),
+              "egx_decoder_ragged: ragged memories serve head dim 32 / 64 (head dim %d: the 256 / 512 class runs uniform batches only, egx_decoder_fwd)",
+              cfg->d_model / cfg->n_heads);
     EGX_CHECK(train || (cfg->p_drop == 0.f && cfg->p_pos == 0.f), "egx_decoder_ragged: inference only: p_drop and p_pos must be 0 (got %g, %g)", cfg->p_drop, cfg->p_pos);
     size_t rows = 0;
     n[0] = n[1] = 0; smax[0] = smax[1] = 0;
@@ -1045,6 +1006,8 @@ int egx_decoder_cross_weights(const egx_dec_config* cfg, int B, const int* mem_l
     EGX_CHECK(cfg, "egx_decoder_cross_weights: null decoder config");
     EGX_CHECK(cfg->p_drop == 0.f && cfg->p_pos == 0.f, "egx_decoder_cross_weights: inference only: p_drop and p_pos must be 0 (got %g, %g)",
               cfg->p_drop, cfg->p_pos);
+    EGX_CHECK(!(cfg->n_heads > 0 && cfg->d_model % cfg->n_heads == 0 && dec_attn_bighead_dim(cfg->d_model / cfg->n_heads)),
+              "egx_decoder_cross_weights: head dim %d (16, 32, 64 or 128: the weights of the 256 / 512 class are not served)", cfg->d_model / cfg->n_heads);
     DPlan pl;
     size_t off_tab = 0;
     int S = cfg->S;
@@ -1410,6 +1373,100 @@ __global__ __launch_bounds__(256) void cached_self_attn_kernel(CachedAttnParams<
     }
 }
 
+// Head dim 256 / 512 (the 2048-wide LTA sequence decoders): a key row per lane would be the whole register file, so here the LANES SPLIT THE
+// HEAD DIM, NC = DH / 64 consecutive columns each, and the wave walks the history: row j's score is the wave sum of the lanes' partial
+// products and stays on lane j; the softmax runs across the lanes as above; the output is the walk again, P[j] broadcast from lane j. No
+// LDS, no barrier; NC-element registers whatever the history's length. Cache layout, appended row and ancestry as cached_self_attn_kernel.
+template <bool F32, int NC>
+__device__ __forceinline__ void loadc(const void* base, size_t idx, float (&o)[NC]) {
+    if constexpr (NC == 8) {
+        load8<F32>(base, idx, o);
+    } else if constexpr (F32) {
+        const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + idx);
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+    } else {
+        const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(base) + idx);
+        o[0] = bf_lo(u.x); o[1] = bf_hi(u.x); o[2] = bf_lo(u.y); o[3] = bf_hi(u.y);
+    }
+}
+template <bool F32, int NC>
+__device__ __forceinline__ void storec(void* base, size_t idx, const float (&a)[NC]) {
+    if constexpr (NC == 8) {
+        store8<F32>(base, idx, a);
+    } else if constexpr (F32) {
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + idx) = make_float4(a[0], a[1], a[2], a[3]);
+    } else {
+        *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(base) + idx) = make_uint2(pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]));
+    }
+}
+template <int DH, bool F32, bool ANC>
+__global__ __launch_bounds__(256) void cached_self_attn_bighead_kernel(CachedAttnParams<ANC> p) {
+    constexpr int NC = DH / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rh = blockIdx.x * 4 + wave;
+    int W = 1;
+    if constexpr (ANC) W = p.W;
+    if (rh >= p.B * W * p.H) return;            // (no barrier below: every wave works alone)
+    const int r = rh / p.H, h = rh % p.H, t = p.t, d = p.d, b = r / W;
+    const size_t col = (size_t)h * DH + lane * NC;                          // this lane's columns of a d-wide row
+    const size_t nrow = (size_t)r * 3 * d + col;                            // q; k at + d, v at + 2d
+    int slot = 0;
+    if constexpr (ANC) {
+        slot = lane < t ? p.anc[(size_t)r * BEAM_DEPTH + lane] : 0;
+        slot = slot < 0 ? 0 : (slot >= p.W ? p.W - 1 : slot);               // (the head writes 0 .. W - 1)
+    }
+    // cache row (row, j): k at crow(j), v at + d
+    auto crow = [&](int j) -> size_t {
+        size_t row = (size_t)r;
+        if constexpr (ANC) row = (size_t)b * W + __shfl(slot, j, 64);
+        return (row * p.n_steps + j) * 2 * d + col;
+    };
+    float q[NC], kn[NC], vn[NC];
+    loadc<F32, NC>(p.qkv, nrow, q);
+    loadc<F32, NC>(p.qkv, nrow + d, kn);
+    loadc<F32, NC>(p.qkv, nrow + 2 * d, vn);
+    {   // append row t (read by later steps only)
+        const size_t cnew = ((size_t)r * p.n_steps + t) * 2 * d + col;
+        storec<F32, NC>(p.cache, cnew, kn);
+        storec<F32, NC>(p.cache, cnew + d, vn);
+    }
+    float s = -INFINITY;
+    for (int j = 0; j <= t; ++j) {
+        float kj[NC];
+        if (j < t) {
+            loadc<F32, NC>(p.cache, crow(j), kj);
+        } else {
+#pragma unroll
+            for (int e = 0; e < NC; ++e) kj[e] = kn[e];
+        }
+        float part = 0.f;
+#pragma unroll
+        for (int e = 0; e < NC; ++e) part = fmaf(q[e], kj[e], part);
+        const float tot = wave_sum(part);
+        if (lane == j) s = tot * p.scale;
+    }
+    const bool live = lane <= t;
+    const float m = wave_max(s);
+    const float e = live ? __expf(s - m) : 0.f;
+    const float prob = e / wave_sum(e);
+    float acc[NC];
+#pragma unroll
+    for (int x = 0; x < NC; ++x) acc[x] = 0.f;
+    for (int j = 0; j < t; ++j) {
+        float vj[NC];
+        loadc<F32, NC>(p.cache, crow(j) + d, vj);
+        const float pj = __shfl(prob, j, 64);
+#pragma unroll
+        for (int x = 0; x < NC; ++x) acc[x] = fmaf(pj, vj[x], acc[x]);
+    }
+    {
+        const float pt = __shfl(prob, t, 64);
+#pragma unroll
+        for (int x = 0; x < NC; ++x) acc[x] = fmaf(pt, vn[x], acc[x]);
+    }
+    storec<false, NC>(p.o, (size_t)r * d + col, acc);
+}
+
 template <bool ANC>
 int cached_self_attn(CachedAttnParams<ANC> p, int dh, bool f32, hipStream_t st) {
     const char* who = ANC ? "beam self-attention" : "cached self-attention";
@@ -1421,11 +1478,15 @@ int cached_self_attn(CachedAttnParams<ANC> p, int dh, bool f32, hipStream_t st) 
     }
     p.scale = 1.f / sqrtf((float)dh);
     const dim3 grid(cdiv(p.B * W * p.H, 4)), block(256);
-    if (dh == 64 && !f32) hipLaunchKernelGGL((cached_self_attn_kernel<64, false, ANC>), grid, block, 0, st, p);
+    if (dh == 512 && !f32) hipLaunchKernelGGL((cached_self_attn_bighead_kernel<512, false, ANC>), grid, block, 0, st, p);
+    else if (dh == 256 && !f32) hipLaunchKernelGGL((cached_self_attn_bighead_kernel<256, false, ANC>), grid, block, 0, st, p);
+    else if (dh == 512) hipLaunchKernelGGL((cached_self_attn_bighead_kernel<512, true, ANC>), grid, block, 0, st, p);
+    else if (dh == 256) hipLaunchKernelGGL((cached_self_attn_bighead_kernel<256, true, ANC>), grid, block, 0, st, p);
+    else if (dh == 64 && !f32) hipLaunchKernelGGL((cached_self_attn_kernel<64, false, ANC>), grid, block, 0, st, p);
     else if (dh == 32 && !f32) hipLaunchKernelGGL((cached_self_attn_kernel<32, false, ANC>), grid, block, 0, st, p);
     else if (dh == 64) hipLaunchKernelGGL((cached_self_attn_kernel<64, true, ANC>), grid, block, 0, st, p);
     else if (dh == 32) hipLaunchKernelGGL((cached_self_attn_kernel<32, true, ANC>), grid, block, 0, st, p);
-    else EGX_CHECK(false, "%s: head dim %d (32 or 64)", who, dh);
+    else EGX_CHECK(false, "%s: head dim %d (32, 64, 256 or 512)", who, dh);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -1727,9 +1788,20 @@ auto own_history_attn(const StepPlan& pl) {
     };
 }
 
+// The greedy and the forced head keep GH_CLIPS rows of d inputs and V logits in dynamic LDS and set no limit of their own on the launch: the
+// default 64 KiB must hold them (49152 bytes at d = 2048, V = 1024, the widest configuration step_layout and step_checks let through)
+constexpr int GEN_HEAD_LDS_LIMIT = 64 * 1024;
+size_t gen_head_lds(int d, int V) { return (size_t)GH_CLIPS * ((size_t)d + V) * sizeof(float); }
+int gen_head_fits(const char* who, int d, int V) {
+    EGX_CHECK(gen_head_lds(d, V) <= (size_t)GEN_HEAD_LDS_LIMIT, "%s: the head needs %zu bytes of LDS for d = %d, V = %d (at most %d)", who, gen_head_lds(d, V), d,
+              V, GEN_HEAD_LDS_LIMIT);
+    return 0;
+}
+
 int generate_plan(const egx_dec_config* c, int B, int n_steps, StepPlan& pl) {
     if (step_checks("egx_decoder_generate", c, n_steps)) return 1;
-    return step_layout(c, B, 1, n_steps, 8, 1, pl);
+    if (step_layout(c, B, 1, n_steps, 8, 1, pl)) return 1;
+    return gen_head_fits("egx_decoder_generate", pl.d, pl.V);
 }
 
 // The one body of egx_decoder_generate (period = 0), egx_decoder_generate_sched and egx_decoder_generate_attn: step t's head takes row
@@ -1764,7 +1836,7 @@ int generate_run(const egx_dec_config* cfg, const int64_t* start, const float* m
         hp.logits = logits_out ? logits_out + (size_t)t * B * pl.V : nullptr;
         hp.x32 = x32; hp.x16 = x16; hp.B = B; hp.d = d; hp.V = pl.V; hp.scale = sqrtf((float)d);
         hp.words = period ? words + (size_t)(t % period) * pl.V : nullptr; hp.n_words = period ? counts[t % period] : 0;
-        hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
+        hipLaunchKernelGGL(gen_head_kernel, dim3(cdiv(B, GH_CLIPS)), dim3(64 * GH_WAVES), gen_head_lds(d, pl.V), st, hp);
         EGX_LAUNCH_CHECK();
     }
     run.joined();
@@ -1802,6 +1874,8 @@ int egx_decoder_generate_attn(const egx_dec_config* cfg, const int64_t* start, c
                               int64_t* tokens_out, float* logits_out, void* workspace, void* stream, int period, const int* counts,
                               const int32_t* words, float* attn_out) {
     EGX_CHECK(attn_out, "egx_decoder_generate_attn: null attn_out (egx_decoder_generate / egx_decoder_generate_sched are the calls without it)");
+    EGX_CHECK(!(cfg && cfg->n_heads > 0 && cfg->d_model % cfg->n_heads == 0 && dec_attn_bighead_dim(cfg->d_model / cfg->n_heads)),
+              "egx_decoder_generate_attn: head dim %d (16, 32, 64 or 128: the weights of the 256 / 512 class are not served)", cfg->d_model / cfg->n_heads);
     return generate_run(cfg, start, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, n_steps, tokens_out, logits_out, workspace, stream,
                         period, counts, words, attn_out);
 }
@@ -2147,6 +2221,7 @@ int forced_plan(const egx_dec_config* c, int B, int R, int n_steps, StepPlan& pl
     if (step_checks("egx_decoder_forced", c, n_steps)) return 1;
     EGX_CHECK(R >= 1 && R <= FORCED_MAX_R, "egx_decoder_forced: R = %d (1..%d)", R, FORCED_MAX_R);
     if (step_layout(c, B, R, n_steps, 256, n_steps, pl)) return 1;
+    if (gen_head_fits("egx_decoder_forced", pl.d, pl.V)) return 1;
     if (step_rows_fit("egx_decoder_forced", 'R', c, B, R)) return 1;
     pl.xin32 = take(pl.bytes, pl.M * n_steps * pl.d * 4);
     return 0;
@@ -2178,7 +2253,7 @@ int forced_run(const egx_dec_config* cfg, const int64_t* tokens, const int64_t* 
     ForcedHeadParams hp;
     hp.x = cat<float>(ws, pl.xL32); hp.fc_w = fc_w; hp.fc_b = fc_b; hp.targets = targets; hp.logits = logits_out; hp.logprob = logprob_out;
     hp.rows = M * n_steps; hp.M = M; hp.n = n_steps; hp.d = d; hp.V = pl.V;
-    hipLaunchKernelGGL(forced_head_kernel, dim3(cdiv(hp.rows, GH_CLIPS)), dim3(64 * GH_WAVES), (size_t)GH_CLIPS * (d + pl.V) * sizeof(float), st, hp);
+    hipLaunchKernelGGL(forced_head_kernel, dim3(cdiv(hp.rows, GH_CLIPS)), dim3(64 * GH_WAVES), gen_head_lds(d, pl.V), st, hp);
     EGX_LAUNCH_CHECK();
     return 0;
 }
@@ -2199,5 +2274,45 @@ int egx_decoder_forced(const egx_dec_config* cfg, const int64_t* tokens, const i
                        int n_steps, float* logits_out, float* logprob_out, void* workspace, void* stream) {
     return forced_run(cfg, tokens, targets, memory, emb, pe, pe_stride, layers, fc_w, fc_b, B, R, n_steps, logits_out, logprob_out, workspace, stream);
 }
+
+}  // extern "C"
+
+// ---- unit hooks of the decoder's attention (ABI v29): exactly the launches decoder_fwd_run / decoder_bwd_run and the cached step's
+// cross-attention make (dec_attn), on the caller's operands. Every check runs before the launch.
+namespace {
+int dec_attn_hook(const char* who, const egx_dec_attn_args* a, bool bwd) {
+    EGX_CHECK(a, "%s: null arguments", who);
+    EGX_CHECK(a->p_drop >= 0.f && a->p_drop <= 1.f, "%s: dropout probability %g outside [0, 1]", who, (double)a->p_drop);
+    EGX_CHECK(a->B >= 1 && a->H >= 1 && a->Sq >= 1 && a->Sk >= 1, "%s: B = %d, H = %d, Sq = %d, Sk = %d", who, a->B, a->H, a->Sq, a->Sk);
+    EGX_CHECK(a->dh == 32 || a->dh == 64 || dec_attn_bighead_dim(a->dh), "%s: head dim %d (32 or 64; 256 / 512 with Sk <= %d)", who, a->dh, DA_BIGHEAD_MAXK);
+    DecAttnParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = a->q; p.k = a->k; p.v = a->v; p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.o = (bf16_t*)a->o; p.ldo = a->ldo;
+    p.d_o = (const bf16_t*)a->d_o; p.dq = a->dq; p.dk = a->dk; p.dv = a->dv;
+    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk; p.causal = a->causal ? 1 : 0;
+    if (a->p_drop > 0.f) {
+        p.drop_key = site_key(a->seed, 0x40u + a->layer, a->site);
+        p.drop_thresh = drop_threshold(a->p_drop); p.drop_inv = a->p_drop < 1.f ? 1.f / (1.f - a->p_drop) : 0.f;
+    }
+    if (!dec_attn_bighead_dim(a->dh)) {       // (the big-head class checks its own operands: dec_attn_bighead)
+        const int w = a->H * a->dh;
+        EGX_CHECK(a->Sq <= DA_MAXQ && a->Sk <= DAL_MAXK && (!a->causal || a->Sq == a->Sk), "%s: Sq = %d (1..%d), Sk = %d (1..%d; causal: Sk = Sq)", who,
+                  a->Sq, DA_MAXQ, a->Sk, DAL_MAXK);
+        EGX_CHECK(p.q && p.k && p.v && (bwd ? p.d_o && p.dq && p.dk && p.dv : p.o != nullptr), "%s: null pointer argument", who);
+        EGX_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 8 == 0 && p.ldq >= w && p.ldk >= w && p.ldv >= w && p.ldo >= w,
+                  "%s: ldq = %d, ldk = %d, ldv = %d, ldo = %d (multiples of 8, >= H * head dim = %d)", who, p.ldq, p.ldk, p.ldv, p.ldo, w);
+        EGX_CHECK((((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.o | (uintptr_t)p.d_o | (uintptr_t)p.dq | (uintptr_t)p.dk | (uintptr_t)p.dv) & 15) == 0,
+                  "%s: pointers must be 16-byte aligned", who);
+        EGX_CHECK(a->Sk <= DA_MAXK || (a->operands_bf16 && !a->causal), "%s: a memory of %d tokens needs bf16 operands", who, a->Sk);
+    }
+    hipStream_t st = (hipStream_t)a->stream;
+    return bwd ? dec_attn<true>(p, a->dh, !a->operands_bf16, st) : dec_attn<false>(p, a->dh, !a->operands_bf16, st);
+}
+}  // namespace
+
+extern "C" {
+
+int egx_decoder_attention_fwd(const egx_dec_attn_args* a) { return dec_attn_hook("egx_decoder_attention_fwd", a, false); }
+int egx_decoder_attention_bwd(const egx_dec_attn_args* a) { return dec_attn_hook("egx_decoder_attention_bwd", a, true); }
 
 }  // extern "C"

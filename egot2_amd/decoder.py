@@ -170,7 +170,10 @@ class DecoderMixin:
             if n_heads < 1 or d % n_heads:
                 raise ValueError(f"d_model {d} is not a multiple of {n_heads} heads")
             F_egx.check_cross_weights(d // n_heads, S_max)
-        if self._egx_fused_decoder_ok(decoder, d, n_heads, sy, S_max):
+        # (head dim 256 / 512 has no ragged kernels: its clips run grouped by memory length, each group one fused call)
+        if (self._egx_fused_decoder_ok(decoder, d, n_heads, sy, S_max)
+                and F_egx.decoder_ragged_supported(getattr(self, "egx_compute", "f32"), d, n_heads, decoder.layers[0].linear1.out_features, sy, S_max,
+                                                   len(decoder.layers))):
             meta, params = self._egx_decoder_args(decoder, pos_embed, n_heads, p_drop)
             args = (meta, y, memory, ml.to(torch.int32), embedding.weight, pos_embed.pe[:sy, 0, :])
             if want_attn:
@@ -413,7 +416,7 @@ class DecoderMixin:
         post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
         if not (post_ln and F_egx.decoder_forced_supported(compute, d, self.n_heads, d_ff, S, len(decoder.layers), V, sy, K)):
             raise ValueError(f"teacher-forced decoding is outside egx_decoder_forced's limits (compute bf16, post-LN layers, d_model a multiple "
-                             f"of 128 in [256, 1024], head dim 32 or 64, d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= "
+                             f"of 128 in [256, 1024], head dim 32 or 64 (or head dim 256 / 512 with d_model <= 2048 and S <= 16), d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= "
                              f"1024, sy <= 64, K <= 8): got compute {compute}, d = {d}, {self.n_heads} heads, d_ff = {d_ff}, S = {S}, "
                              f"{len(decoder.layers)} layers, vocabulary {V}, sy = {sy}, K = {K}")
         y3, t3 = y.reshape(B, K, sy), (targets.reshape(B, K, sy) if targets is not None else None)
@@ -453,7 +456,7 @@ class DecoderMixin:
         post_ln = not any(getattr(layer, "norm_first", False) for layer in decoder.layers)
         if not (post_ln and F_egx.decoder_beam_supported(compute, d, self.n_heads, d_ff, S, len(decoder.layers), V, n_steps, beam_width)):
             raise ValueError(f"beam search is outside egx_decoder_beam's limits (compute bf16, post-LN layers, d_model a multiple of 128 in "
-                             f"[256, 1024], head dim 32 or 64, d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= 1024, "
+                             f"[256, 1024], head dim 32 or 64 (or head dim 256 / 512 with d_model <= 2048, S <= 16 and beam_width <= 4 at d_model 2048), d_ff a multiple of 128, S <= 1024, at most 16 layers, vocabulary <= 1024, "
                              f"n_steps <= 64, beam_width <= 8): got compute {compute}, d = {d}, {self.n_heads} heads, d_ff = {d_ff}, S = {S}, "
                              f"{len(decoder.layers)} layers, vocabulary {V}, n_steps = {n_steps}, beam_width = {beam_width}")
         if schedule is not None:

@@ -1819,9 +1819,23 @@ def cross_attention_weights(q: torch.Tensor, k: torch.Tensor, n_heads: int, Sq: 
 
 
 def decoder_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S: int, n_layers: int) -> bool:
-    """Shapes egx_decoder_fwd / egx_decoder_bwd serve (include/egot2x.h); everything else stays on the composed decoder."""
-    return (compute == "bf16" and 256 <= d <= 1024 and d % 128 == 0 and n_heads > 0 and d % n_heads == 0 and d // n_heads in (32, 64)
-            and d_ff >= 128 and d_ff % 128 == 0 and 1 <= sy <= 8 and 1 <= S <= 1024 and 1 <= n_layers <= 16)
+    """Shapes egx_decoder_fwd / egx_decoder_bwd serve (include/egot2x.h); everything else stays on the composed decoder. Head dim 32 / 64:
+    d <= 1024, S <= 1024; head dim 256 / 512 (the 2048-wide LTA sequence decoders): d <= 2048, S <= 16."""
+    if not (compute == "bf16" and d >= 256 and d % 128 == 0 and n_heads > 0 and d % n_heads == 0):
+        return False
+    dh = d // n_heads
+    if not ((dh in (32, 64) and d <= 1024 and 1 <= S <= 1024) or (dh in DECODER_BIG_HEAD_DIMS and d <= 2048 and 1 <= S <= DECODER_BIG_HEAD_MAX_S)):
+        return False
+    return d_ff >= 128 and d_ff % 128 == 0 and 1 <= sy <= 8 and 1 <= n_layers <= 16
+
+
+DECODER_BIG_HEAD_DIMS = (256, 512)      # wide_decoder_bighead.hip
+DECODER_BIG_HEAD_MAX_S = 16
+
+
+def decoder_ragged_supported(compute: str, d: int, n_heads: int, d_ff: int, sy: int, S: int, n_layers: int) -> bool:
+    """Shapes egx_decoder_ragged_* serve: the fused decoder's at head dim 32 / 64 (the 256 / 512 class runs uniform batches only)."""
+    return decoder_supported(compute, d, n_heads, d_ff, sy, S, n_layers) and d // n_heads not in DECODER_BIG_HEAD_DIMS
 
 
 def decoder_generate_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int) -> bool:
@@ -1942,7 +1956,9 @@ def decoder_generate(meta, start, mem2d, emb, pe, layer_params: Sequence[torch.T
 
 def decoder_beam_supported(compute: str, d: int, n_heads: int, d_ff: int, S: int, n_layers: int, vocab: int, n_steps: int, beam_width: int) -> bool:
     """Configurations egx_decoder_beam serves (include/egot2x.h): egx_decoder_generate's limits, 1 <= beam_width <= 8, beam_width <= vocab."""
-    return decoder_generate_supported(compute, d, n_heads, d_ff, S, n_layers, vocab, n_steps) and 1 <= beam_width <= min(8, vocab)
+    # (the head's LDS, 64 KiB: never the limit at d <= 1024; at d = 2048 it leaves beam_width <= 4)
+    return (decoder_generate_supported(compute, d, n_heads, d_ff, S, n_layers, vocab, n_steps) and 1 <= beam_width <= min(8, vocab)
+            and (4 if beam_width <= 4 else 8) * (d + vocab) * 4 <= 65536)
 
 
 class BeamTrace:

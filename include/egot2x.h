@@ -1132,8 +1132,10 @@ int egx_embed_pos_bwd(const int64_t* tokens, const float* dy, float* d_emb, floa
  * task_prompt_model.py:163-172). compute = EGX_BF16 only: the B * sy target rows and the B * S memory rows run through the
  * bf16 MFMA GEMMs of the wide path with fused epilogues, the LayerNorms through its row kernels, the two attentions through
  * a register-resident kernel (one wave per (clip, head)). d_model a multiple of 128 in [256, 1024], head dim 32 or 64,
- * sy <= 8 target tokens, S <= 1024 memory tokens per clip; other configurations return an error (the caller composes the
- * decoder from the entry points above instead). Parameters are torch-layout fp32 ([out, in] row-major); `ca_in_w` /
+ * sy <= 8 target tokens, S <= 1024 memory tokens per clip; or (ABI v29) head dim 256 or 512 with d_model a multiple of 128 in
+ * [256, 2048], sy <= 8 and S <= 16 (the 2048-wide LTA sequence decoders: 8 or 4 heads over a memory of 2 or 4 clip rows). Other
+ * configurations return an error (the caller composes the decoder from the entry points above instead; head dim 256 / 512 is
+ * served by compute = EGX_BF16 only). Parameters are torch-layout fp32 ([out, in] row-major); `ca_in_w` /
  * `ca_in_b` are the packed in-projection of the cross-attention (rows [0, d): query, rows [d, 3d): key / value). */
 typedef struct egx_dec_config {
     int d_model, n_heads, d_ff, n_layers;
@@ -1169,6 +1171,35 @@ int egx_decoder_fwd(const egx_dec_config* cfg, const int64_t* tokens, const floa
 int egx_decoder_bwd(const egx_dec_config* cfg, const int64_t* tokens, const egx_dec_layer* layers, const float* fc_w, int B, const float* d_logits,
                     const void* saved, void* scratch, float* d_memory, float* d_emb, const egx_dec_layer_grads* grads, float* d_fc_w,
                     float* d_fc_b, void* zero_buf, size_t zero_bytes, int training, uint64_t seed, void* stream);
+/* ---- ABI v29 additions (new symbols only, as v19 to v28: EGX_ABI_VERSION stays 18): head dim 256 / 512 in the sequence decoder ----------
+ * d_model above 1024 is served at head dim 256 / 512 ONLY: head dim 32 / 64 keeps d_model <= 1024 (and S <= 1024), as before; e.g. d_model 1152
+ * with 18 heads of 64 is still refused.
+ * egx_decoder_workspace / _fwd / _bwd, egx_decoder_generate[_sched], egx_decoder_forced and egx_decoder_beam[_sched] accept head dim 256 /
+ * 512 with d_model <= 2048 and S <= 16 memory rows (forward and backward attention: one wave per (clip, head), fp32 FMAs over a wave-
+ * private LDS slice of the query rows; the cached step's self-attention splits the head dim over the lanes and walks the history).
+ * Everything else keeps its limits: sy <= 8, vocabulary <= 1024 and n_steps <= 64 for the cached step, the beam head's 64 KiB of LDS
+ * (at d_model 2048: beam_width <= 4). Refused at head dim 256 / 512, on the host, before any launch: the ragged entry points
+ * (egx_decoder_ragged_*), the cross-attention weights (egx_decoder_cross_weights, egx_cross_attention_weights,
+ * egx_decoder_generate_attn), S > 16, and compute f32 / f32s.
+ *
+ * The unit hook pair of the decoder's attention, the decoder-side twin of egx_wide_attention_fwd / _bwd: exactly the launch
+ * egx_decoder_fwd / _bwd and the cached step's cross-attention make. q rows b * Sq + i (leading dimension ldq), k / v rows b * Sk + j,
+ * head h at columns [h * dh, + dh); operands_bf16 != 0: q / k / v and dq / dk / dv are bf16, else fp32 (layer 0's self-attention); o and
+ * d_o are bf16. causal: key j <= query i (Sk = Sq). Scores scaled by 1 / sqrt(dh). Dropout on the probabilities keyed as the decoder keys
+ * it: site_key(seed, 0x40 + layer, site) (sites: 1 self-attention, 3 cross-attention), row (b * H + h) * 8 + i, column j. The backward
+ * recomputes the probabilities; every element of dq (B * Sq rows), dk and dv (B * Sk rows) within the head columns is written once.
+ * dh 32 / 64: Sq <= 8, Sk <= 1024 (Sk > 64: bf16 operands, not causal). dh 256 / 512: Sq <= 8, Sk <= 16. Pointers 16-byte aligned,
+ * leading dimensions multiples of 8 and >= H * dh. A refusal names the limit and launches nothing. */
+typedef struct egx_dec_attn_args {
+    const void* q; const void* k; const void* v; int ldq, ldk, ldv; int operands_bf16;
+    void* o; int ldo;                                           /* forward: (B * Sq, ldo) bf16 out */
+    const void* d_o; void* dq; void* dk; void* dv;              /* backward */
+    int B, H, dh, Sq, Sk, causal;
+    float p_drop; uint64_t seed; uint32_t layer, site;
+    void* stream;
+} egx_dec_attn_args;
+int egx_decoder_attention_fwd(const egx_dec_attn_args* args);
+int egx_decoder_attention_bwd(const egx_dec_attn_args* args);
 /* ---- ABI v18: the decoder over ragged memories (inference) ----
  * decode() (task_prompt_model.py:260-269) of B clips whose memories differ in length: `memory` holds sum_b S_b packed rows (clip after
  * clip, S_b = mem_lengths[b], HOST int[B]; egx_ragged_encode's out_layout 0 output), clip b's target rows cross-attend to its own S_b rows
